@@ -30,6 +30,10 @@ Rank 0 prints one JSON line.  Extra objects:
   `cpu_baseline` — the scalar C++ oracle (a port, not the reference) timed on the host cores for a bounded sample of the same workload.
 URT_BENCH_VERIFY=1: after the timed region (outside it) the presented image is compared bit for bit with the oracle's accumulation of the
 same W + K frames (N = 1), or with a single-rank render (N > 1).
+--dump-outputs DIR: after the timed region, rank 0 writes what the last timed step handed its caller — the presented image (N > 1: the
+gathered image) — as DIR/presented.npy, float32 H x W x 4; a frame over DUMP_BYTES is cut to a seeded sample of its rows (same rows for
+the same frame size).  The inputs are the same from run to run (seeded scenes, documented frame sequence), so two builds compare output
+for output.
 """
 from __future__ import annotations
 
@@ -56,6 +60,29 @@ BYTES_8D = {"tlas_nodes": 28, "blas_nodes": 64, "tri_tests": 36, "sphere_tests":
 # records (v0,e1,e2 as float4), 48 B of normals + 40 B material per triangle hit, and the 4 sky texels of a path's last bounce
 BYTES_PADDED = {"tlas_nodes": 28, "blas_nodes": 64, "tri_tests": 48, "sphere_tests": 16, "hit_tri": 88, "hit_sphere": 40,
                 "hit_sky": 64, "pixels": 16}
+
+
+DUMP_BYTES = 64_000_000       # --dump-outputs: at most this much in all (.npy headers included)
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Each array as out_dir/<name>.npy in float32; when together they exceed DUMP_BYTES, each is cut to the rows of a sample seeded by
+    its shape alone (sorted, without repeats).  Returns {name: {"shape": [...], "rows": null or the number of rows kept}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_BYTES - 4096 * len(arrays)                         # room for the .npy headers
+    out = {}
+    for name, a in arrays.items():
+        rows = None
+        if total > budget:
+            n = a.shape[0] * budget // total
+            rows = np.sort(np.random.default_rng(list(a.shape)).choice(a.shape[0], n, replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        out[name] = {"shape": list(a.shape), "rows": None if rows is None else int(len(rows))}
+    return out
 
 
 def algorithmic_bytes(c: dict, table=BYTES_8D) -> int:
@@ -98,7 +125,11 @@ def main():
                     help="before the W warm-up steps: run the same step untimed for this long so that the GPU has left its idle clocks "
                          "(a step is 0.25 ms: W = 5 steps are 1.3 ms of GPU work, far less than the clock governor's reaction time; measured: "
                          "the 20-frame launch takes 5.2 ms from idle clocks, 4.75 ms after >= 15 ms of load).  Reported as `clock_warmup`; 0 = off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write the image the last timed step presented as DIR/presented.npy (float32; see the module doc)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` as issued by hand or by a driver that does not wrap it in torch.distributed.run: this process
@@ -333,6 +364,10 @@ def main():
     verify_img = None
     if world == 1 and os.environ.get("URT_BENCH_VERIFY") == "1":
         verify_img = (destination.GetPixels(), master._converged.GetPixels())
+    # ---- --dump-outputs: the image the last timed step presented, read back before the counting replay below renders over it ----
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"presented": (destination if world == 1 else full).GetPixels()})
 
     # ---- roofline of the dominant kernel (rank 0): replay the same frames with traversal counters on -----------
     roofline = None
@@ -490,6 +525,7 @@ def main():
                        **({"gather_every": args.gather_every} if world > 1 else {}), **({"options": args.opt} if args.opt else {})},
             "roofline": roofline, "issue": issue, "cpu_baseline": cpu,
             **({"verified_against_oracle": verified} if verified is not None else {}),
+            **({"outputs_dumped": dumped} if dumped is not None else {}),
         }
         print(json.dumps(out), flush=True)
     master.OnDisable()

@@ -2,6 +2,10 @@ import os
 import sys
 
 import pytest
+# torch before anything loads libunityraytracer_amd.so: torch's libraries ask for libamdhip64.so, the library for libamdhip64.so.7.
+# Loaded first, torch's runtime answers both (as in bench.py); loaded after the library, torch brings a second HIP / HSA runtime into
+# the process, and once torch has initialised its own (torch.cuda.is_available() in test_abi.py), the library's finds no device.
+import torch  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

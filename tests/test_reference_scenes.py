@@ -41,14 +41,53 @@ def test_fixtures_hold_what_the_scene_files_say():
     assert all(o["albedoColor"] == [0.0, 0.4, 1.0] and o["smoothness"] == 0.69 for o in s2["objects"])    # script defaults, RO:12-15
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Assets/Scenes"), reason="the reference tree is only present in the build container")
+def scene_yaml(fx, rto_guid, builtin_meshes):
+    """Unity scene YAML (the serialisation mine() reads) of a fixture: one GameObject + Transform per object with its MeshFilter,
+    SphereCollider and RayTraceObject MonoBehaviour (colour fields only when the fixture says they were serialised), and the camera
+    with its Camera and the RayTraceMaster MonoBehaviour.  Written here from the fixture, so the round trip needs no scene file."""
+    mesh_ids = {v: k for k, v in builtin_meshes.items()}
+    lines, ids = ["%YAML 1.1", "%TAG !u! tag:unity3d.com,2011:"], iter(range(1000, 100000))
+    vec = lambda v, keys="xyzw": "{" + ", ".join(f"{k}: {x!r}" for k, x in zip(keys, v)) + "}"
+
+    def doc(cls, kind, fields):
+        fid = next(ids)
+        lines.extend([f"--- !u!{cls} &{fid}", f"{kind}:"] + [f"  {k}: {v}" for k, v in fields])
+        return fid
+
+    def game_object(name, pos, rot, scale):
+        go = doc(1, "GameObject", [("m_Name", name), ("m_IsActive", 1)])
+        doc(4, "Transform", [("m_GameObject", f"{{fileID: {go}}}"), ("m_LocalRotation", vec(rot)), ("m_LocalPosition", vec(pos)),
+                             ("m_LocalScale", vec(scale)), ("m_Father", "{fileID: 0}")])
+        return f"{{fileID: {go}}}"
+
+    for o in fx["objects"]:
+        go = game_object(o["name"], o["position"], o["rotation"], o["scale"])
+        doc(33, "MeshFilter", [("m_GameObject", go), ("m_Mesh", f"{{fileID: {mesh_ids[o['mesh']]}, guid: 0000000000000000e000000000000000, type: 0}}")])
+        if o["type"] == "sphere":
+            doc(135, "SphereCollider", [("m_GameObject", go), ("m_Radius", repr(o["collider_radius"]))])
+        mb = [("m_GameObject", go), ("m_Enabled", int(o["enabled"])), ("m_Script", f"{{fileID: 11500000, guid: {rto_guid}, type: 3}}")]
+        if o["serialized_material"]:
+            mb += [(c, vec(o[c] + [1.0], "rgba")) for c in ("albedoColor", "specularColor", "emissionColor")] + [("smoothness", repr(o["smoothness"]))]
+        doc(114, "MonoBehaviour", mb)
+    cam = fx["camera"]
+    go = game_object("Main Camera", cam["position"], cam["rotation"], (1, 1, 1))
+    doc(20, "Camera", [("m_GameObject", go), ("near clip plane", repr(cam["near"])), ("far clip plane", repr(cam["far"])),
+                       ("field of view", repr(cam["field_of_view"]))])
+    doc(114, "MonoBehaviour", [("m_GameObject", go), ("m_Enabled", 1), ("m_Script", "{fileID: 11500000, guid: 0123456789abcdef0123456789abcdef, type: 3}"),
+                               ("numBounces", fx["numBounces"]), ("numRays", fx["numRays"])])
+    return "\n".join(lines) + "\n"
+
+
 def test_fixtures_regenerate_identically(tmp_path):
-    """The committed JSON is exactly what the committed script mines from the reference's files."""
+    """The committed script mines exactly the committed JSON back from scene YAML that holds the same scene (written from the
+    fixture, above): its YAML reader, component grouping, sphere radius and material defaults agree with the fixtures."""
     sys.path.insert(0, GOLD)
     import make_scene_fixtures as mk
-    guid = mk.re.search(r"guid:\s*(\w+)", open("/root/reference/Assets/Scripts/RayTraceObject.cs.meta").read()).group(1)
+    guid = "fedcba9876543210fedcba9876543210"
     for name in ("Scene1", "SampleScene"):
-        again = mk.mine(f"/root/reference/Assets/Scenes/{name}.unity", guid)
+        path = tmp_path / f"{name}.unity"
+        path.write_text(scene_yaml(fixture(name), guid, mk.BUILTIN_MESHES))
+        again = mk.mine(str(path), guid)
         assert json.loads(json.dumps(again, sort_keys=True)) == fixture(name)
 
 
