@@ -50,7 +50,8 @@ enum {
 };
 
 /* ---- library / context ------------------------------------------------------------------- */
-URT_API int urt_abi_version(void);                       /* bumps when this header changes */
+URT_API int urt_abi_version(void);                       /* bumps when this header changes incompatibly (still 4: the ray queries were
+                                                            added without changing anything that existed) */
 URT_API int urt_device_count(int* out_count);
 /* One context per process and GPU (the one-process-per-GPU model).  device = HIP ordinal. */
 URT_API int urt_context_create(int device, urt_context** out_ctx);
@@ -179,6 +180,23 @@ URT_API int urt_texture_pack_rows_rgb(urt_context* ctx, urt_handle texture, int 
                                       void* device_dst, uint64_t* out_bytes);
 URT_API int urt_texture_unpack_rows_rgb(urt_context* ctx, urt_handle texture, int first_group_row, int row_stride,
                                         const void* device_src, float alpha, void* hip_stream);
+
+/* ---- ray queries -------------------------------------------------------------------------- */
+/* Batched "what does this ray hit?" against the scene bound to kernel 0 (RS:364-383 Trace, outside a frame): picking, line of sight,
+ * shadow / occlusion tests.  With t_max = +inf a closest-hit query returns exactly what the frame kernels' Trace returns for that ray —
+ * distance, position and normal by the same expressions, the ground plane, the reference's object walk and its tie rules included.
+ *  - t_max is exclusive: a hit counts only if 0 < t < t_max; NaN or t_max <= 0 is a miss.
+ *  - flags URT_QUERY_CLOSEST: out = urt_RayHit[n]; URT_QUERY_ANY: out = int32_t[n], 1 if anything is hit with 0 < t < t_max (the walk
+ *    stops at the first such hit).
+ *  - the scene is the one bound at call time: a changed scene is prepared first (after the deferred frames that read the old one);
+ *    otherwise deferred frames stay deferred.  Queries never change urt_counters (rays, launches, ...) or the frame batching.
+ *  - n == 0: URT_OK, nothing is launched; n < 0, a NULL pointer with n > 0 or unknown flags: URT_ERR_INVALID_ARGUMENT.
+ * urt_ray_query: host memory; returns when `out` is filled (a synchronising call: it reports URT_ERR_WATCHDOG like urt_synchronize).
+ * urt_ray_query_device: device pointers (d_rays 16-byte aligned, d_out 16-byte aligned for urt_RayHit, 4-byte for int32); enqueued on
+ * the context's stream, returns at once — the caller orders and synchronises it, as with urt_texture_unpack_rows_on. */
+enum { URT_QUERY_CLOSEST = 0, URT_QUERY_ANY = 1 };
+URT_API int urt_ray_query(urt_context* ctx, const urt_Ray* rays, int n, void* out, int flags);
+URT_API int urt_ray_query_device(urt_context* ctx, const void* d_rays, int n, void* d_out, int flags);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 typedef struct urt_counters {

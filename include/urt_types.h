@@ -5,6 +5,9 @@
 //   Sphere          56 B   RayTraceMaster.cs:116-119               / RayTraceShader.compute:51-55
 //   BVHNode         28 B   RayTraceMaster.cs:148-152               / RayTraceShader.compute:57-61
 // Strides are asserted by the reference at RayTraceMaster.cs:42-45 and used at :738-745.
+// The ray-query records (urt_ray_query, urt.h) are the library's own: 16-byte aligned rows for coalesced dwordx4 loads and stores.
+//   Ray             32 B
+//   RayHit          48 B
 #pragma once
 #include <stdint.h>
 
@@ -38,6 +41,23 @@ typedef struct urt_BVHNode {
   float vmax[3];                /* @12 */
   int32_t index;                /* @24 <0: interior/filler, >=0: object id (implicit heap 2i+1, 2i+2) */
 } urt_BVHNode;
+
+typedef struct urt_Ray {
+  float origin[3];              /* @0  */
+  float t_max;                  /* @12 a hit counts only if 0 < t < t_max (exclusive; NaN or <= 0: no hit) */
+  float direction[3];           /* @16 used as given (not normalised): distance is in units of |direction| */
+  int32_t reserved;             /* @28 */
+} urt_Ray;
+
+typedef struct urt_RayHit {
+  float distance;               /* @0  +inf: miss */
+  float position[3];            /* @4  origin + distance * direction */
+  float normal[3];              /* @16 */
+  int32_t kind;                 /* @28 0 miss, 1 ground plane, 2 sphere, 3 triangle */
+  int32_t object;               /* @32 sphere index or MeshObject index; -1 for a miss or the ground plane */
+  int32_t primitive;            /* @36 triangle: its first index slot in _Indices (i of RS:243); -1 otherwise */
+  float u, v;                   /* @40 triangle: barycentrics of the hit; 0 otherwise */
+} urt_RayHit;
 #pragma pack(pop)
 
 #define URT_STRIDE_PARAMS 40
@@ -46,6 +66,8 @@ typedef struct urt_BVHNode {
 #define URT_STRIDE_BVHNODE 28
 #define URT_STRIDE_VEC3 12
 #define URT_STRIDE_INDEX 4
+#define URT_STRIDE_RAY 32
+#define URT_STRIDE_RAYHIT 48
 
 #ifdef __cplusplus
 }
@@ -53,4 +75,6 @@ static_assert(sizeof(urt_RayTraceParams) == URT_STRIDE_PARAMS, "RM:42");
 static_assert(sizeof(urt_MeshObject) == URT_STRIDE_MESHOBJECT, "RM:43");
 static_assert(sizeof(urt_Sphere) == URT_STRIDE_SPHERE, "RM:44");
 static_assert(sizeof(urt_BVHNode) == URT_STRIDE_BVHNODE, "RM:45");
+static_assert(sizeof(urt_Ray) == URT_STRIDE_RAY, "urt_Ray");
+static_assert(sizeof(urt_RayHit) == URT_STRIDE_RAYHIT, "urt_RayHit");
 #endif

@@ -59,6 +59,24 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_texture_pack_rows_rgb(IntPtr ctx, ulong texture, int firstGroupRow, int rowStride, IntPtr deviceDst, out ulong bytes);
     [DllImport(Lib)] internal static extern int urt_texture_unpack_rows_rgb(IntPtr ctx, ulong texture, int firstGroupRow, int rowStride, IntPtr deviceSrc, float alpha, IntPtr hipStream);
 
+    // ---- ray queries (include/urt.h "ray queries"; records of include/urt_types.h) -------------------------------------
+    [StructLayout(LayoutKind.Sequential, Pack = 1)]
+    internal struct Ray {                                   // urt_Ray, 32 B
+        public float ox, oy, oz, tMax;
+        public float dx, dy, dz;
+        public int reserved;
+    }
+    [StructLayout(LayoutKind.Sequential, Pack = 1)]
+    internal struct RayHit {                                // urt_RayHit, 48 B
+        public float distance, px, py, pz, nx, ny, nz;
+        public int kind, obj, primitive;                    // kind: 0 miss, 1 ground plane, 2 sphere, 3 triangle
+        public float u, v;
+    }
+    internal const int QueryClosest = 0, QueryAny = 1;
+    [DllImport(Lib)] internal static extern int urt_ray_query(IntPtr ctx, [In] Ray[] rays, int n, [Out] RayHit[] hits, int flags);
+    [DllImport(Lib, EntryPoint = "urt_ray_query")] internal static extern int urt_ray_query_any(IntPtr ctx, [In] Ray[] rays, int n, [Out] int[] occluded, int flags);
+    [DllImport(Lib)] internal static extern int urt_ray_query_device(IntPtr ctx, IntPtr deviceRays, int n, IntPtr deviceOut, int flags);
+
     // ---- measurement ----------------------------------------------------------------------------------------------------
     [StructLayout(LayoutKind.Sequential)]
     internal struct Counters {

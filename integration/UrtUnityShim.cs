@@ -32,6 +32,25 @@ public static class UrtDevice {
     }
 }
 
+/// Physics.Raycast-style queries against the scene the bound shader renders (include/urt.h urt_ray_query): picking, line of sight,
+/// the "test ray" of RayTraceDebug.cs:119-129.  One context only (a group user queries urt_group_context(g, r)).
+internal static class UrtRaycast {                   // internal: it hands out UrtNative records (same assembly as RM)
+    static readonly UrtNative.Ray[] one = new UrtNative.Ray[1];
+    static readonly UrtNative.RayHit[] oneHit = new UrtNative.RayHit[1];
+    public static bool Raycast(Vector3 origin, Vector3 direction, out UrtNative.RayHit hit, float maxDistance = float.PositiveInfinity) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("Raycast: query one rank's context (urt_group_context)");
+        one[0] = new UrtNative.Ray { ox = origin.x, oy = origin.y, oz = origin.z, tMax = maxDistance, dx = direction.x, dy = direction.y, dz = direction.z };
+        UrtDevice.Check(UrtNative.urt_ray_query(UrtDevice.Handle, one, 1, oneHit, UrtNative.QueryClosest));
+        hit = oneHit[0];
+        return hit.kind != 0;
+    }
+    /// Occlusion of many segments at once: occluded[i] = 1 if anything lies strictly between 0 and rays[i].tMax.
+    public static void Occluded(UrtNative.Ray[] rays, int[] occluded) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("Occluded: query one rank's context (urt_group_context)");
+        UrtDevice.Check(UrtNative.urt_ray_query_any(UrtDevice.Handle, rays, rays.Length, occluded, UrtNative.QueryAny));
+    }
+}
+
 /// new ComputeBuffer(count, stride); .SetData(List<T>); .Release(); .count; .stride            (RM:233-252)
 public sealed class UrtComputeBuffer {
     internal ulong handle;

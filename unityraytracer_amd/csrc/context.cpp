@@ -28,6 +28,7 @@
 #include "qnodes.h"
 #include "cullflags.h"
 #include "present.h"
+#include "query.h"
 #include "urt_device.h"
 
 #include <chrono>
@@ -221,6 +222,8 @@ struct urt_context {
   bool main_touched = true;                 // something other than the frame loop's own blends / presents / readbacks was enqueued on the main stream since the last launch
   int slab_cursor = 0, prev_base = 0, prev_n = 0;
   uint64_t overlapped_launches = 0;
+  // urt_ray_query (host memory): grow-only device scratch for the rays and the results, q_cap rays each
+  float4* q_rays = nullptr; float4* q_out = nullptr; size_t q_cap = 0;
 };
 
 namespace { inline hipStream_t touch(urt_context* ctx) { ctx->main_touched = true; return ctx->stream; } }
@@ -1483,6 +1486,8 @@ int urt_context_destroy(urt_context* ctx) {
     if (ctx->pre_ev[k]) (void)hipEventDestroy(ctx->pre_ev[k]);
   }
   if (ctx->dep_ev) (void)hipEventDestroy(ctx->dep_ev);
+  if (ctx->q_rays) (void)hipFree(ctx->q_rays);
+  if (ctx->q_out) (void)hipFree(ctx->q_out);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
   return URT_OK;
@@ -1940,6 +1945,56 @@ int urt_texture_unpack_rows(urt_context* ctx, urt_handle texture, int first_grou
 }
 
 /* ---- measurement ---- */
+/* ---- ray queries ---- */
+// Both entry points read the scene bound to kernel 0 as it is now: a stale scene is prepared first (after the deferred frames that read
+// the old one), as do_dispatch does; otherwise the deferred batch stays deferred — a query only reads the scene.  The query is enqueued
+// on the context's stream WITHOUT marking it touched (the frame loop's overlap bookkeeping, counters and launches are not affected).
+static int query_prepare(urt_context* ctx, const void* rays, int n, const void* out, int flags) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (n < 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "ray query: negative ray count");
+  if (flags != URT_QUERY_CLOSEST && flags != URT_QUERY_ANY) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "ray query: unknown flags");
+  if (n > 0 && (!rays || !out)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "ray query: rays / out is NULL");
+  if (n == 0) return URT_OK;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  if (ctx->scene_dirty) {
+    int rc = flush_pending(ctx); if (rc) return rc;       // the deferred frames read the scene that is about to be replaced
+    rc = prepare_scene(ctx); if (rc) return rc;
+  }
+  return URT_OK;
+}
+
+int urt_ray_query(urt_context* ctx, const urt_Ray* rays, int n, void* out, int flags) {
+  URT_GUARD_BEGIN
+  int rc = query_prepare(ctx, rays, n, out, flags);
+  if (rc || n == 0) return rc;
+  if ((size_t)n > ctx->q_cap) {                           // grow-only; no query still reads the old pair (this form synchronises before it returns)
+    if (ctx->q_rays) { (void)hipFree(ctx->q_rays); ctx->q_rays = nullptr; }
+    if (ctx->q_out) { (void)hipFree(ctx->q_out); ctx->q_out = nullptr; }
+    ctx->q_cap = 0;
+    URT_HIP(ctx, hipMalloc((void**)&ctx->q_rays, (size_t)n * sizeof(urt_Ray)));
+    URT_HIP(ctx, hipMalloc((void**)&ctx->q_out, (size_t)n * sizeof(urt_RayHit)));
+    ctx->q_cap = (size_t)n;
+  }
+  const size_t out_bytes = (size_t)n * (flags == URT_QUERY_ANY ? sizeof(int32_t) : sizeof(urt_RayHit));
+  URT_HIP(ctx, hipMemcpyAsync(ctx->q_rays, rays, (size_t)n * sizeof(urt_Ray), hipMemcpyHostToDevice, ctx->stream));
+  URT_HIP(ctx, launch_query(ctx->ds, ctx->tlas_stack, ctx->blas_stack, ctx->q_rays, n, ctx->q_out, flags == URT_QUERY_ANY, ctx->stream));
+  URT_HIP(ctx, hipMemcpyAsync(out, ctx->q_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  URT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return check_watchdog(ctx);
+  URT_GUARD_END(ctx)
+}
+
+int urt_ray_query_device(urt_context* ctx, const void* d_rays, int n, void* d_out, int flags) {
+  URT_GUARD_BEGIN
+  int rc = query_prepare(ctx, d_rays, n, d_out, flags);
+  if (rc || n == 0) return rc;
+  if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & (flags == URT_QUERY_ANY ? 3u : 15u)))
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "ray query: d_rays must be 16-byte aligned, d_out 16-byte (closest hit) / 4-byte (any hit) aligned");
+  URT_HIP(ctx, launch_query(ctx->ds, ctx->tlas_stack, ctx->blas_stack, (const float4*)d_rays, n, d_out, flags == URT_QUERY_ANY, ctx->stream));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
 int urt_set_option(urt_context* ctx, const char* name, int value) {
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   if (!name) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "option name is NULL");

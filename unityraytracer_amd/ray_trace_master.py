@@ -223,6 +223,23 @@ class RayTraceMaster:
         self.SetShaderParameters()
         self.Render(destination)
 
+    # The "Raycast" every engine binding offers (and the "test ray" of the reference's RayTraceDebug.cs:119-129): one closest-hit query
+    # against the scene this master renders (include/urt.h urt_ray_query).  None for a miss, else the urt_RayHit fields as a dict.
+    def Raycast(self, origin, direction, max_distance: float = math.inf):
+        if self._treesNeedRebuilding:                                             # the scene buffers exist once OnRenderImage has run once
+            self._currentSample = 0
+            self._treesNeedRebuilding = False
+            if self._rayTraceObjects:
+                self.RebuildObjectLists()
+            self.RebuildTrees()
+        self.SetShaderParameters()
+        o = np.asarray(origin, dtype=np.float32).reshape(1, 3)
+        d = np.asarray(direction, dtype=np.float32).reshape(1, 3)
+        h = self.ctx.ray_query(o, d, t_max=float(max_distance))[0]
+        if h["kind"] == 0:
+            return None
+        return {k: (h[k].copy() if h[k].shape else h[k].item()) for k in h.dtype.names}
+
     # RM:760-769: a camera move resets the running mean
     def ResetAccumulation(self):
         self._currentSample = 0

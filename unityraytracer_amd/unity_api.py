@@ -108,6 +108,102 @@ class Context:
         self.check(self.lib.urt_debug_read_scene_blas(self._h, nodes.ctypes.data_as(C.c_void_p), tri.ctypes.data_as(C.c_void_p), root.ctypes.data_as(C.c_void_p)))
         return nodes, tri, root, info
 
+    def ray_query(self, origins, directions, t_max=None, any_hit: bool = False):
+        """Batched ray queries against the bound scene (include/urt.h urt_ray_query): what the frame kernels' Trace (RS:364-383)
+        returns for each ray, bounded by t_max (exclusive; None = +inf; a scalar or one value per ray).
+
+        numpy float32 arrays (n, 3): returns a RAYHIT_DT structured array (n,), or int32 (n,) occlusion flags with any_hit.
+        torch float32 tensors (n, 3) on this context's device: the device entry point on device-resident rays; returns a dict of
+        tensor views (distance, position, normal, kind, object, primitive, u, v), or an int32 tensor with any_hit.  The call is
+        ordered after torch's current stream and has completed when it returns."""
+        if _is_torch(origins) or _is_torch(directions):
+            return self._ray_query_torch(origins, directions, t_max, any_hit)
+        o = _rays_arg(origins, "origins")
+        d = _rays_arg(directions, "directions")
+        if o.shape != d.shape:
+            raise ValueError(f"ray_query: origins {o.shape} and directions {d.shape} differ in shape")
+        n = o.shape[0]
+        tm = _t_max_arg(t_max, n)
+        rays = np.zeros(n, dtype=RAY_DT)
+        rays["origin"], rays["t_max"], rays["direction"] = o, tm, d
+        out = np.zeros(n, dtype=np.int32 if any_hit else RAYHIT_DT)
+        flags = _lib.URT_QUERY_ANY if any_hit else _lib.URT_QUERY_CLOSEST
+        self.check(self.lib.urt_ray_query(self._h, rays.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p), flags))
+        return out
+
+    def _ray_query_torch(self, origins, directions, t_max, any_hit):
+        import torch
+        for name, a in (("origins", origins), ("directions", directions)):
+            if not _is_torch(a):
+                raise TypeError(f"ray_query: {name} must be a torch tensor when the other one is")
+            if a.dtype != torch.float32:
+                raise TypeError(f"ray_query: {name} must be float32, not {a.dtype}")
+            if a.dim() != 2 or a.shape[1] != 3:
+                raise ValueError(f"ray_query: {name} must have shape (n, 3), not {tuple(a.shape)}")
+            if a.device.type != "cuda" or a.device.index != self.device:
+                raise ValueError(f"ray_query: {name} must be on cuda:{self.device}, not {a.device}")
+        if origins.shape != directions.shape:
+            raise ValueError(f"ray_query: origins {tuple(origins.shape)} and directions {tuple(directions.shape)} differ in shape")
+        n = origins.shape[0]
+        if n > 0x7fffffff:
+            raise ValueError("ray_query: more than 2^31 - 1 rays")
+        if t_max is None:
+            tm = torch.full((n, 1), float("inf"), dtype=torch.float32, device=origins.device)
+        elif _is_torch(t_max):
+            if t_max.dtype != torch.float32 or t_max.shape != (n,) or t_max.device != origins.device:
+                raise ValueError("ray_query: t_max must be a float32 tensor of shape (n,) on the rays' device")
+            tm = t_max.reshape(n, 1)
+        else:
+            tm = torch.full((n, 1), float(np.float32(t_max)), dtype=torch.float32, device=origins.device)
+        rays = torch.cat([origins, tm, directions, torch.zeros((n, 1), dtype=torch.float32, device=origins.device)], dim=1).contiguous()
+        out = torch.empty(n if any_hit else (n, 12), dtype=torch.int32 if any_hit else torch.float32, device=origins.device)
+        # the rays are written on torch's current stream, the query runs on the library's: order them (as gather_converged does)
+        torch.cuda.current_stream(origins.device).synchronize()
+        flags = _lib.URT_QUERY_ANY if any_hit else _lib.URT_QUERY_CLOSEST
+        self.check(self.lib.urt_ray_query_device(self._h, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr()), flags))
+        torch.cuda.synchronize(origins.device)                   # the device entry point returns at once: wait for the library's stream
+        if any_hit:
+            return out
+        bits = out.view(torch.int32)
+        return {"distance": out[:, 0], "position": out[:, 1:4], "normal": out[:, 4:7], "kind": bits[:, 7], "object": bits[:, 8],
+                "primitive": bits[:, 9], "u": out[:, 10], "v": out[:, 11]}
+
+
+# urt_Ray / urt_RayHit (include/urt_types.h) as numpy records
+RAY_DT = np.dtype([("origin", np.float32, 3), ("t_max", np.float32), ("direction", np.float32, 3), ("reserved", np.int32)])
+RAYHIT_DT = np.dtype([("distance", np.float32), ("position", np.float32, 3), ("normal", np.float32, 3), ("kind", np.int32),
+                      ("object", np.int32), ("primitive", np.int32), ("u", np.float32), ("v", np.float32)])
+
+
+def _is_torch(a) -> bool:
+    return type(a).__module__.startswith("torch")
+
+
+def _rays_arg(a, name: str) -> np.ndarray:
+    if not isinstance(a, np.ndarray):
+        raise TypeError(f"ray_query: {name} must be a numpy array (or a torch tensor), not {type(a).__name__}")
+    if a.dtype != np.float32:
+        raise TypeError(f"ray_query: {name} must be float32, not {a.dtype}")
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f"ray_query: {name} must have shape (n, 3), not {a.shape}")
+    if a.shape[0] > 0x7fffffff:
+        raise ValueError("ray_query: more than 2^31 - 1 rays")
+    return a
+
+
+def _t_max_arg(t_max, n: int) -> np.ndarray:
+    if t_max is None:
+        return np.full(n, np.inf, dtype=np.float32)
+    if isinstance(t_max, np.ndarray):
+        if t_max.dtype != np.float32:
+            raise TypeError(f"ray_query: t_max must be float32, not {t_max.dtype}")
+        if t_max.shape != (n,):
+            raise ValueError(f"ray_query: t_max must be a scalar or have shape ({n},), not {t_max.shape}")
+        return t_max
+    if not isinstance(t_max, (int, float, np.floating, np.integer)):
+        raise TypeError(f"ray_query: t_max must be a number or a float32 array, not {type(t_max).__name__}")
+    return np.full(n, t_max, dtype=np.float32)
+
 
 class _GroupLib:
     """Maps the per-context entry points onto their urt_group_* counterparts, so that ComputeBuffer / RenderTexture /
