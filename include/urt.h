@@ -50,8 +50,8 @@ enum {
 };
 
 /* ---- library / context ------------------------------------------------------------------- */
-URT_API int urt_abi_version(void);                       /* bumps when this header changes incompatibly (still 4: the ray queries were
-                                                            added without changing anything that existed) */
+URT_API int urt_abi_version(void);                       /* bumps when this header changes incompatibly (still 4: the ray queries and
+                                                            the feature buffers were added without changing anything that existed) */
 URT_API int urt_device_count(int* out_count);
 /* One context per process and GPU (the one-process-per-GPU model).  device = HIP ordinal. */
 URT_API int urt_context_create(int device, urt_context** out_ctx);
@@ -197,6 +197,29 @@ URT_API int urt_texture_unpack_rows_rgb(urt_context* ctx, urt_handle texture, in
 enum { URT_QUERY_CLOSEST = 0, URT_QUERY_ANY = 1 };
 URT_API int urt_ray_query(urt_context* ctx, const urt_Ray* rays, int n, void* out, int flags);
 URT_API int urt_ray_query_device(urt_context* ctx, const void* d_rays, int n, void* d_out, int flags);
+
+/* ---- feature buffers ---------------------------------------------------------------------- */
+/* Per-pixel first-hit feature buffers ("AOVs") of the bound camera: what each pixel's camera ray hits, for denoiser guides (albedo,
+ * normal), compositing (depth) and whole-frame picking (ids).  Each handle is an existing texture (own or external) or 0 for "not
+ * wanted"; all given targets have the same size, and that size is the pixel grid.  Pixel (x, y) is texel y * width + x, row 0 at the
+ * bottom, where the frame kernels write Result.
+ *  - the camera ray uses the scene bound to kernel 0 and the uniforms set at call time (_CameraToWorld, _CameraInverseProjection):
+ *    URT_AOV_PIXEL_CENTER: u = ((float)x + 0.5f) / (float)width * 2.0f - 1.0f (v likewise), then CreateCameraRay (RS:142-153); no jitter.
+ *    URT_AOV_FRAME_RAY: the first camera ray (sample 0) that a frame dispatched now would trace for the pixel (_Seed, _PixelOffset and the
+ *    two rand() draws of RS:448-449).
+ *  - the ray is traced with t_max = +inf: the result is exactly what urt_ray_query returns for it (and the frame kernels' Trace).
+ *  - targets (RGBA32F; int fields are stored as their bits):
+ *      hit     position.xyz, distance                                  miss: (0, 0, 0, +inf)
+ *      normal  normal.xyz, kind as a float value (1 ground, 2 sphere, 3 triangle)   miss: (0, 0, 0, 0)
+ *      albedo  min(1 - specular, albedo) (RS:390; ground (0.5, 0.3, 0.15)), smoothness   miss: the sky radiance Shade returns (RS:420-427), 0
+ *      id      object (sphere / MeshObject index, else -1), primitive (index slot of RS:243, else -1), u | v   miss: (-1, -1, 0, 0)
+ *  - like every call that could observe the images, it submits the deferred frames first; then a stale scene is prepared.  The kernel
+ *    is enqueued on the context's stream and the call returns without synchronising.  urt_counters are not changed.
+ *  - URT_ERR_INVALID_ARGUMENT: all four handles 0, a handle given twice, sizes differ, a target bound as _SkyboxTexture, unknown flags;
+ *    URT_ERR_INVALID_HANDLE: an unknown handle; URT_ERR_UNBOUND: _CameraToWorld or _CameraInverseProjection never set.  On any error
+ *    nothing is written. */
+enum { URT_AOV_PIXEL_CENTER = 0, URT_AOV_FRAME_RAY = 1 };
+URT_API int urt_render_aov(urt_context* ctx, urt_handle hit, urt_handle normal, urt_handle albedo, urt_handle id, int flags);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 typedef struct urt_counters {

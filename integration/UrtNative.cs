@@ -77,6 +77,10 @@ internal static class UrtNative {
     [DllImport(Lib, EntryPoint = "urt_ray_query")] internal static extern int urt_ray_query_any(IntPtr ctx, [In] Ray[] rays, int n, [Out] int[] occluded, int flags);
     [DllImport(Lib)] internal static extern int urt_ray_query_device(IntPtr ctx, IntPtr deviceRays, int n, IntPtr deviceOut, int flags);
 
+    // ---- feature buffers (include/urt.h "feature buffers"): hit, normal, albedo, id texture handles, 0 = not wanted --------
+    internal const int AovPixelCenter = 0, AovFrameRay = 1;
+    [DllImport(Lib)] internal static extern int urt_render_aov(IntPtr ctx, ulong hit, ulong normal, ulong albedo, ulong id, int flags);
+
     // ---- measurement ----------------------------------------------------------------------------------------------------
     [StructLayout(LayoutKind.Sequential)]
     internal struct Counters {

@@ -51,6 +51,33 @@ internal static class UrtRaycast {                   // internal: it hands out U
     }
 }
 
+/// Per-pixel first-hit feature buffers (include/urt.h urt_render_aov) written straight into device memory the engine owns — how a Unity
+/// RenderTexture (ARGBFloat, enableRandomWrite) is bound: pass each texture's device pointer (GetNativeTexturePtr on a HIP-interop
+/// backend) or IntPtr.Zero for a buffer not wanted.  Call it when the camera moves, after SetShaderParameters (the accumulation resets then too).
+public static class UrtFeatureBuffers {
+    static IntPtr boundCtx = IntPtr.Zero;
+    static readonly ulong[] handles = new ulong[4];
+    static readonly IntPtr[] ptrs = new IntPtr[4];
+    static int w, h;
+    public static void Render(IntPtr hit, IntPtr normal, IntPtr albedo, IntPtr id, int width, int height, bool frameRay = false) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtFeatureBuffers: render on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        IntPtr[] want = { hit, normal, albedo, id };
+        for (int k = 0; k < 4; k++) {                                  // the external textures are re-wrapped when a pointer or the size changes
+            if (handles[k] != 0 && (boundCtx != ctx || ptrs[k] != want[k] || w != width || h != height)) {
+                if (boundCtx == ctx) UrtDevice.Check(UrtNative.urt_texture_release(ctx, handles[k]));
+                handles[k] = 0;
+            }
+            if (handles[k] == 0 && want[k] != IntPtr.Zero)
+                UrtDevice.Check(UrtNative.urt_texture_create_external(ctx, width, height, want[k], out handles[k]));
+            ptrs[k] = want[k];
+        }
+        boundCtx = ctx; w = width; h = height;
+        UrtDevice.Check(UrtNative.urt_render_aov(ctx, handles[0], handles[1], handles[2], handles[3],
+                                                 frameRay ? UrtNative.AovFrameRay : UrtNative.AovPixelCenter));
+    }
+}
+
 /// new ComputeBuffer(count, stride); .SetData(List<T>); .Release(); .count; .stride            (RM:233-252)
 public sealed class UrtComputeBuffer {
     internal ulong handle;

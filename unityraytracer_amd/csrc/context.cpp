@@ -29,6 +29,7 @@
 #include "cullflags.h"
 #include "present.h"
 #include "query.h"
+#include "aov.h"
 #include "urt_device.h"
 
 #include <chrono>
@@ -82,6 +83,7 @@ struct urt_context {
   urt_handle bound[B_COUNT] = {0, 0, 0, 0, 0, 0, 0};
   urt_handle t_sky = 0, t_result = 0;
   float c2w[16] = {0}, invp[16] = {0};
+  bool c2w_set = false, invp_set = false;  // SetMatrix has given the camera matrices (urt_render_aov needs both)
   float pixel_off[2] = {0, 0};
   float seed = 0;
   int num_bounces = 0, num_rays = 0;     // shader uniforms default to 0 until SetInt (RM:780-781)
@@ -109,6 +111,9 @@ struct urt_context {
     bool ready = false;
   } refit;
   size_t cap_materials = 0, cap_mesh_tlas = 0, cap_sphere_tlas = 0, cap_sphere_pr = 0;   // float4 capacities of the arrays updated in place
+  // urt_render_aov: one float4 per material in the order of DevScene::materials (pack_albedo), part of the prepared scene (scene_allocs).
+  // Not a DevScene member: DevScene is an argument of every frame kernel, and the camera-matrix loads of k_sched depend on its size
+  const float4* aov_albedo = nullptr; size_t cap_aov_albedo = 0;
   uint64_t refitted_meshes = 0, incremental_preps = 0;
   DevScene ds{};
   std::vector<void*> scene_allocs;
@@ -275,6 +280,7 @@ void free_scene(urt_context* ctx) {
   ctx->refit = urt_context::RefitAux{};
   ctx->qbuf = nullptr; ctx->cbuf = nullptr; ctx->d_mesh_leaf = nullptr; ctx->cap_mesh_leaf = 0;
   ctx->cap_materials = ctx->cap_mesh_tlas = ctx->cap_sphere_tlas = ctx->cap_sphere_pr = 0;
+  ctx->aov_albedo = nullptr; ctx->cap_aov_albedo = 0;
   ctx->slab_oom_stride = 0;                                // device memory came back: the next batch may try the Result slots again
 }
 
@@ -326,6 +332,17 @@ void pack_material(const urt_RayTraceParams& m, float* dst) {
   dst[4] = ks.x; dst[5] = ks.y; dst[6] = ks.z; dst[7] = specChance + diffChance;
   dst[8] = m.emission[0]; dst[9] = m.emission[1]; dst[10] = m.emission[2]; dst[11] = diffChance;
   dst[12] = alpha; dst[13] = 1.0f / (alpha + 1.0f); dst[14] = (alpha + 2) / (alpha + 1); dst[15] = 0.0f;   // RS:104, 404
+}
+
+// The albedo feature buffer's entry of a material (urt_render_aov): the clamped albedo Shade uses (RS:390), as pack_material computes it,
+// and the smoothness.
+constexpr int kAlbedoFloats = 4;
+void pack_albedo(const urt_RayTraceParams& m, float* dst) {
+  using namespace urt;
+  v3 albedo = mk3(m.color_albedo[0], m.color_albedo[1], m.color_albedo[2]);
+  v3 spec = mk3(m.color_specular[0], m.color_specular[1], m.color_specular[2]);
+  albedo = vmin3(mk3(1.0f, 1.0f, 1.0f) - spec, albedo);                          // RS:390
+  dst[0] = albedo.x; dst[1] = albedo.y; dst[2] = albedo.z; dst[3] = m.smoothness;
 }
 
 int heap_levels(int n) { int l = 0; while (n > 0) { l++; n >>= 1; } return l; }   // floor(log2 n) + 1
@@ -556,21 +573,25 @@ int prepare_incremental(urt_context* ctx) {
   int rc;
   // materials: spheres, mesh objects, ground plane (pack_material: what Shade derives from the material alone)
   {
-    std::vector<float> mats((size_t)(n_meshes + n_spheres + 1) * kMatFloats);
+    std::vector<float> mats((size_t)(n_meshes + n_spheres + 1) * kMatFloats), albedo((size_t)(n_meshes + n_spheres + 1) * kAlbedoFloats);
     urt_RayTraceParams ground{};
     ground.color_albedo[0] = 0.5f; ground.color_albedo[1] = 0.3f; ground.color_albedo[2] = 0.15f; ground.smoothness = 0.3f;
     pack_material(ground, mats.data() + (size_t)(n_meshes + n_spheres) * kMatFloats);
+    pack_albedo(ground, albedo.data() + (size_t)(n_meshes + n_spheres) * kAlbedoFloats);
     for (int m = 0; m < n_meshes; m++) {
       urt_MeshObject mo; std::memcpy(&mo, bm->host.data() + (size_t)m * URT_STRIDE_MESHOBJECT, sizeof mo);
       pack_material(mo.lighting, mats.data() + (size_t)(n_spheres + m) * kMatFloats);
+      pack_albedo(mo.lighting, albedo.data() + (size_t)(n_spheres + m) * kAlbedoFloats);
     }
     std::vector<float> pr((size_t)n_spheres * 4);
     for (int i = 0; i < n_spheres; i++) {
       urt_Sphere sp; std::memcpy(&sp, bs->host.data() + (size_t)i * URT_STRIDE_SPHERE, sizeof sp);
       pr[4 * (size_t)i] = sp.position[0]; pr[4 * (size_t)i + 1] = sp.position[1]; pr[4 * (size_t)i + 2] = sp.position[2]; pr[4 * (size_t)i + 3] = sp.radius;
       pack_material(sp.lighting, mats.data() + (size_t)i * kMatFloats);
+      pack_albedo(sp.lighting, albedo.data() + (size_t)i * kAlbedoFloats);
     }
     if ((rc = update_array(ctx, mats, &S.materials, &ctx->cap_materials))) return rc;
+    if ((rc = update_array(ctx, albedo, &ctx->aov_albedo, &ctx->cap_aov_albedo))) return rc;
     if (n_spheres > 0 && (rc = update_array(ctx, pr, &S.sphere_pr, &ctx->cap_sphere_pr))) return rc;
   }
   // object-level heaps (+ the masked-walk table of a small mesh heap)
@@ -633,11 +654,13 @@ int prepare_scene(urt_context* ctx) {
   int n_meshes = bm ? bm->count : 0;
   int n_spheres = bs ? bs->count : 0;
   std::vector<float> mats((size_t)(n_meshes + n_spheres + 1) * kMatFloats);   // spheres first, then mesh objects, then the ground plane
+  std::vector<float> albedo((size_t)(n_meshes + n_spheres + 1) * kAlbedoFloats);   // the same order (urt_render_aov)
   {
     urt_RayTraceParams ground{};                                                 // RS:164-170: hard-coded material of the y = 0 plane
     ground.color_albedo[0] = 0.5f; ground.color_albedo[1] = 0.3f; ground.color_albedo[2] = 0.15f;
     ground.smoothness = 0.3f;
     pack_material(ground, mats.data() + (size_t)(n_meshes + n_spheres) * kMatFloats);
+    pack_albedo(ground, albedo.data() + (size_t)(n_meshes + n_spheres) * kAlbedoFloats);
   }
   // meshes: the triangle BVH ("BLAS") of every MeshObject, by the host SAH builder or by the GPU LBVH builder
   auto t_begin = std::chrono::steady_clock::now();
@@ -649,6 +672,7 @@ int prepare_scene(urt_context* ctx) {
       urt_MeshObject mo;
       std::memcpy(&mo, bm->host.data() + (size_t)m * URT_STRIDE_MESHOBJECT, sizeof mo);
       pack_material(mo.lighting, mats.data() + (size_t)(n_spheres + m) * kMatFloats);
+      pack_albedo(mo.lighting, albedo.data() + (size_t)(n_spheres + m) * kAlbedoFloats);
     }
     const float4* p;
     // auto: the host builder up to kGpuBuildTriangles triangles (C3's 69,600: 12 ms on the host, 6 on the GPU — and small scenes are what the
@@ -732,6 +756,7 @@ int prepare_scene(urt_context* ctx) {
       pr[4 * (size_t)i] = sp.position[0]; pr[4 * (size_t)i + 1] = sp.position[1]; pr[4 * (size_t)i + 2] = sp.position[2];
       pr[4 * (size_t)i + 3] = sp.radius;
       pack_material(sp.lighting, mats.data() + (size_t)i * kMatFloats);
+      pack_albedo(sp.lighting, albedo.data() + (size_t)i * kAlbedoFloats);
     }
     const float4* p;
     if ((rc = upload(ctx, pr, &p))) return rc; S.sphere_pr = p;
@@ -739,6 +764,7 @@ int prepare_scene(urt_context* ctx) {
   {
     const float4* p;
     if ((rc = upload(ctx, mats, &p))) return rc; S.materials = p; ctx->cap_materials = mats.size() / 4;
+    if ((rc = upload(ctx, albedo, &p))) return rc; ctx->aov_albedo = p; ctx->cap_aov_albedo = albedo.size() / 4;
   }
   S.n_spheres = n_spheres;
   ctx->cap_sphere_pr = (size_t)n_spheres;
@@ -1231,6 +1257,20 @@ int batch_limit(urt_context* ctx, const FrameParams& P) {
   return std::max(1, std::min(lim, (int)kMaxFramesPerLaunch));
 }
 
+// The sky the kernels sample: the texture bound as _SkyboxTexture, or one black texel (an unbound SRV reads zeros).
+int bind_sky(urt_context* ctx, DevScene& S) {
+  Texture* sky = find_texture(ctx, ctx->t_sky);
+  if (sky) { S.sky = sky->dev; S.sky_w = sky->w; S.sky_h = sky->h; }
+  else {     // an unbound SRV reads zeros
+    if (!ctx->zero_sky) {
+      URT_HIP(ctx, hipMalloc((void**)&ctx->zero_sky, sizeof(float4)));
+      URT_HIP(ctx, hipMemsetAsync(ctx->zero_sky, 0, sizeof(float4), touch(ctx)));
+    }
+    S.sky = ctx->zero_sky; S.sky_w = 1; S.sky_h = 1;
+  }
+  return URT_OK;
+}
+
 int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_row, int row_stride) {
   if (kernel != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "kernel index must be 0 (CSMain)");
   if (gx < 0 || gy < 0 || gz < 0 || first_row < 0 || row_stride < 1)
@@ -1248,15 +1288,7 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
   if (gx == 0 || gy == 0 || gz == 0) return URT_OK;
 
   DevScene S = ctx->ds;
-  Texture* sky = find_texture(ctx, ctx->t_sky);
-  if (sky) { S.sky = sky->dev; S.sky_w = sky->w; S.sky_h = sky->h; }
-  else {     // an unbound SRV reads zeros
-    if (!ctx->zero_sky) {
-      URT_HIP(ctx, hipMalloc((void**)&ctx->zero_sky, sizeof(float4)));
-      URT_HIP(ctx, hipMemsetAsync(ctx->zero_sky, 0, sizeof(float4), touch(ctx)));
-    }
-    S.sky = ctx->zero_sky; S.sky_w = 1; S.sky_h = 1;
-  }
+  { int rc = bind_sky(ctx, S); if (rc) return rc; }
 
   FrameParams P{};
   std::memcpy(P.c2w, ctx->c2w, sizeof P.c2w);
@@ -1777,8 +1809,8 @@ int urt_shader_set_texture(urt_context* ctx, int kernel, const char* name, urt_h
 int urt_shader_set_matrix(urt_context* ctx, const char* name, const float* m16) {
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   if (!name || !m16) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "SetMatrix: NULL argument");
-  if (std::strcmp(name, "_CameraToWorld") == 0) std::memcpy(ctx->c2w, m16, sizeof ctx->c2w);
-  else if (std::strcmp(name, "_CameraInverseProjection") == 0) std::memcpy(ctx->invp, m16, sizeof ctx->invp);
+  if (std::strcmp(name, "_CameraToWorld") == 0) { std::memcpy(ctx->c2w, m16, sizeof ctx->c2w); ctx->c2w_set = true; }
+  else if (std::strcmp(name, "_CameraInverseProjection") == 0) { std::memcpy(ctx->invp, m16, sizeof ctx->invp); ctx->invp_set = true; }
   return URT_OK;   // undeclared names are ignored, as Unity does
 }
 
@@ -1991,6 +2023,55 @@ int urt_ray_query_device(urt_context* ctx, const void* d_rays, int n, void* d_ou
   if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & (flags == URT_QUERY_ANY ? 3u : 15u)))
     return fail(ctx, URT_ERR_INVALID_ARGUMENT, "ray query: d_rays must be 16-byte aligned, d_out 16-byte (closest hit) / 4-byte (any hit) aligned");
   URT_HIP(ctx, launch_query(ctx->ds, ctx->tlas_stack, ctx->blas_stack, (const float4*)d_rays, n, d_out, flags == URT_QUERY_ANY, ctx->stream));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+/* ---- feature buffers ---- */
+// Everything else that could observe the images flushes first: the deferred frames are submitted, then a stale scene is prepared, then
+// the kernel is enqueued on the main stream (marked touched, as urt_texture_set_pixels does).  Every argument is checked before anything
+// is submitted or written.  The counters are not changed.
+int urt_render_aov(urt_context* ctx, urt_handle hit, urt_handle normal, urt_handle albedo, urt_handle id, int flags) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  if (flags != URT_AOV_PIXEL_CENTER && flags != URT_AOV_FRAME_RAY) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "render_aov: unknown flags");
+  const urt_handle h[4] = {hit, normal, albedo, id};
+  Texture* t[4] = {nullptr, nullptr, nullptr, nullptr};
+  int width = 0, height = 0, n = 0;
+  for (int k = 0; k < 4; k++) {
+    if (!h[k]) continue;
+    for (int j = 0; j < k; j++)
+      if (h[j] == h[k]) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "render_aov: a texture is given for two targets");
+    t[k] = find_texture(ctx, h[k]);
+    if (!t[k]) return fail(ctx, URT_ERR_INVALID_HANDLE, "render_aov: unknown texture handle");
+  }
+  for (int k = 0; k < 4; k++) {
+    if (!t[k]) continue;
+    if (h[k] == ctx->t_sky) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "render_aov: a target is the texture bound as _SkyboxTexture");
+    if (n++ == 0) { width = t[k]->w; height = t[k]->h; }
+    else if (t[k]->w != width || t[k]->h != height) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "render_aov: the targets differ in size");
+  }
+  if (n == 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "render_aov: no target given");
+  if ((height + 15) / 16 > 65535) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "render_aov: targets taller than 1048560 pixels");
+  if (!ctx->c2w_set || !ctx->invp_set)
+    return fail(ctx, URT_ERR_UNBOUND, "render_aov: _CameraToWorld / _CameraInverseProjection not set");
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  if (ctx->scene_dirty) { int rc = prepare_scene(ctx); if (rc) return rc; }
+  DevScene S = ctx->ds;
+  { int rc = bind_sky(ctx, S); if (rc) return rc; }
+  AovCamera C{};
+  std::memcpy(C.c2w, ctx->c2w, sizeof C.c2w);
+  std::memcpy(C.invp, ctx->invp, sizeof C.invp);
+  C.pixel_off_x = ctx->pixel_off[0]; C.pixel_off_y = ctx->pixel_off[1];
+  C.seed = ctx->seed;
+  C.frame_ray = flags == URT_AOV_FRAME_RAY ? 1 : 0;
+  AovTargets T{};
+  T.hit = t[0] ? t[0]->dev : nullptr; T.normal = t[1] ? t[1]->dev : nullptr;
+  T.albedo = t[2] ? t[2]->dev : nullptr; T.id = t[3] ? t[3]->dev : nullptr;
+  T.width = width; T.height = height;
+  for (int k = 0; k < 4; k++) if (t[k]) t[k]->other_writes = true;
+  URT_HIP(ctx, launch_aov(S, ctx->aov_albedo, ctx->tlas_stack, ctx->blas_stack, C, T, touch(ctx)));
   return URT_OK;
   URT_GUARD_END(ctx)
 }

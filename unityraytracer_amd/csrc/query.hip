@@ -2,7 +2,7 @@
 //
 // One ray per lane, wave64, 256 threads per workgroup; per-lane LDS stacks laid out [entry][lane] as the frame kernels' (kernels.hip
 // lane_stacks), sized from the prepared scene.  The walk is kernels.hip trace() — the same device functions (trace_device.h), the same
-// arithmetic, the reference's "tests never reset" object walk (A.5) and the (t, index slot) tie rule — with two changes:
+// arithmetic, the reference's "tests never reset" object walk (A.5) and the (t, index slot) tie rule (query_device.h) — with two changes:
 //  * best.t starts at the ray's t_max, so a hit counts only when t < t_max (exclusive); the object-level cull still compares with the
 //    ground-plane distance alone, exactly as trace() does, so its argument does not depend on t_max;
 //  * the any-hit form returns at the first hit with 0 < t < t_max (ground plane, a leaf's triangles, a sphere).
@@ -13,97 +13,10 @@
 #include "../../include/urt_math.h"
 #include "urt_device.h"
 #include "trace_device.h"
+#include "query_device.h"   // query_trace, hit_record, st_nt (shared with aov.hip)
 #include "query.h"
 
 namespace {
-
-// intersect_mesh with an early exit after the first leaf that produced a hit (any-hit form)
-__device__ __forceinline__ void intersect_mesh_any(const DevScene& S, int32_t root, v3 o, v3 d, HitRec& best, int* stk, LocalCounters& lc) {
-  if (root == kEmptyMeshRoot) return;
-  BlasRay R = blas_ray(o, d);
-  int best_i = -1;
-  int sp = 0;
-  int32_t cur = root;
-  while (cur != kBlasDone) {
-    if (cur >= 0) {
-      cur = blas_node_step<false>(S, cur, R, best.t, stk, sp, lc);
-    } else {
-      test_leaf<false>(S, cur, o, d, best, best_i, lc);
-      if (best.kid != 0) return;
-      cur = blas_pop(stk, sp);
-    }
-  }
-}
-
-// trace() of kernels.hip bounded by t_max (> 0, not NaN: the caller answers the others with a miss); kind 0 = nothing with t < t_max
-template <bool ANY>
-__device__ __forceinline__ HitRec query_trace(const DevScene& S, v3 o, v3 d, float t_max, int* tl, int* bl) {
-  LocalCounters lc;                                             // never counted: queries leave urt_counters alone
-  HitRec best; best.t = t_max; best.kid = 0; best.u = 0; best.v = 0;
-  float t_ground = URT_INF;                                     // what trace() hands the object-level cull: the ground hit, t_max aside
-  {
-    float t = -o.y / d.y;
-    if (t > 0 && t < URT_INF) t_ground = t;
-    if (t > 0 && t < best.t) { best.t = t; best.kid = 1; }
-    if (ANY && best.kid != 0) return best;
-  }
-  v3 rcp = mk3(1.0f / (d.x + kEPSILON), 1.0f / (d.y + kEPSILON), 1.0f / (d.z + kEPSILON));
-  if (S.n_meshes > 0) {
-    int check = 1; tl[0] = 0; bool seen = false;
-    while (check > 0) {
-      check--;
-      int bi = tl[check * 64];
-      bool hit = false, culled = false; int index = -1;
-      if (bi < S.n_mesh_tlas) {
-        float4 a = S.mesh_tlas[2 * bi], b = S.mesh_tlas[2 * bi + 1];
-        index = as_int(a.w);
-        float t_min, t_max2;
-        hit = tlas_slab_t(a, b, o, rcp, t_min, t_max2);
-        culled = leaf_culled(b, t_min, t_max2, t_ground);
-      }
-      if (hit) {
-        if (index < 0) { tl[check * 64] = bi * 2 + 1; check++; tl[check * 64] = bi * 2 + 2; check++; }
-        else seen = true;
-      }
-      if (seen && !culled && index >= 0 && index < S.n_meshes) {
-        if (ANY) {
-          intersect_mesh_any(S, S.mesh_root[index], o, d, best, bl, lc);
-          if (best.kid != 0) return best;
-        } else {
-          intersect_mesh<false>(S, S.mesh_root[index], o, d, best, bl, lc);
-        }
-      }
-    }
-  }
-  if (S.n_spheres > 0) {
-    int check = 1; tl[0] = 0; bool seen = false;
-    while (check > 0) {
-      check--;
-      int bi = tl[check * 64];
-      bool hit = false; int index = -1;
-      if (bi < S.n_sphere_tlas) {
-        float4 a = S.sphere_tlas[2 * bi], b = S.sphere_tlas[2 * bi + 1];
-        index = as_int(a.w);
-        hit = tlas_slab(a, b, o, rcp);
-      }
-      if (hit) {
-        if (index < 0) { tl[check * 64] = bi * 2 + 1; check++; tl[check * 64] = bi * 2 + 2; check++; }
-        else seen = true;
-      }
-      if (seen && index >= 0 && index < S.n_spheres) {
-        intersect_sphere<false>(S, index, o, d, best, lc);
-        if (ANY && best.kid != 0) return best;
-      }
-    }
-  }
-  return best;
-}
-
-typedef float f4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void st_nt(float4* p, float4 v) {   // streaming store: the results are not read again by this kernel
-  f4v w = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(w, (f4v*)p);
-}
 
 // out: 3 float4 per ray = urt_RayHit { distance, position.xyz | normal.xyz, kind | object, primitive, u, v } (ints as bits)
 template <bool ANY>
@@ -124,33 +37,9 @@ __global__ __launch_bounds__(256) void k_query(DevScene S, int tlas_stack, int b
     ((int32_t*)out)[i] = h.kind() != 0 ? 1 : 0;
     return;
   }
-  float4 r0 = make_float4(URT_INF, 0, 0, 0), r1 = make_float4(0, 0, 0, 0), r2 = make_float4(as_float(-1), as_float(-1), 0, 0);
-  if (h.kind() != 0) {
-    // position and normal: the expressions of kernels.hip shade_surface (RS:164-170, 192-194, 259-264)
-    v3 pos = madd(h.t, d, o);
-    v3 nrm;
-    int object = -1, primitive = -1;
-    float u = 0, v = 0;
-    if (h.kind() == 1) {
-      nrm = mk3(0, 1, 0);
-    } else if (h.kind() == 2) {
-      nrm = normalize(pos - xyz(S.sphere_pr[h.id()]));
-      object = h.id();
-    } else {
-      const float4* tn = S.tri_norms + 3 * (size_t)h.id();
-      v3 n0 = xyz(tn[0]), n1 = xyz(tn[1]), n2 = xyz(tn[2]);
-      float w = 1.0f - h.u - h.v;
-      nrm = normalize((n0 * w) + (n1 * h.u) + (n2 * h.v));
-      primitive = as_int(S.tri_verts[3 * (size_t)h.id()].w);      // index slot i of RS:243
-      object = as_int(S.tri_verts[3 * (size_t)h.id() + 1].w);     // MeshObject
-      u = h.u; v = h.v;
-    }
-    r0 = make_float4(h.t, pos.x, pos.y, pos.z);
-    r1 = make_float4(nrm.x, nrm.y, nrm.z, as_float(h.kind()));
-    r2 = make_float4(as_float(object), as_float(primitive), u, v);
-  }
+  const HitRecord r = hit_record(S, h, o, d);
   float4* o4 = (float4*)out + 3 * i;
-  st_nt(o4, r0); st_nt(o4 + 1, r1); st_nt(o4 + 2, r2);
+  st_nt(o4, r.r0); st_nt(o4 + 1, r.r1); st_nt(o4 + 2, r.r2);
 }
 
 }  // namespace

@@ -68,6 +68,7 @@ class RayTraceMaster:
         self._meshObjectBuffer = self._vertexBuffer = self._indexBuffer = self._normalBuffer = None
         self._sphereBuffer = self._meshObjectBVHBuffer = self._sphereBVHBuffer = None
         self.screen_width, self.screen_height = scene.width, scene.height
+        self._aov = None                             # RenderFeatureBuffers: (hit, normal, albedo, id) of the screen size
 
     # RM:215-230
     def RegisterObject(self, obj: RayTraceObject):
@@ -240,6 +241,26 @@ class RayTraceMaster:
             return None
         return {k: (h[k].copy() if h[k].shape else h[k].item()) for k in h.dtype.names}
 
+    # Per-pixel first-hit feature buffers of the camera this master renders with (include/urt.h urt_render_aov): hit, normal, albedo and
+    # id textures of the screen size, re-created with it as InitRenderTexture re-creates the frame's (RM:834-840).  A host calls it when
+    # the camera moves — when the accumulation resets too.  Returns the four RenderTextures (filled once the deferred work has run:
+    # GetPixels waits for it).
+    def RenderFeatureBuffers(self, frame_ray: bool = False):
+        if self._treesNeedRebuilding:
+            self._currentSample = 0
+            self._treesNeedRebuilding = False
+            if self._rayTraceObjects:
+                self.RebuildObjectLists()
+            self.RebuildTrees()
+        self.SetShaderParameters()
+        if self._aov is None or self._aov[0].width != self.screen_width or self._aov[0].height != self.screen_height:
+            if self._aov is not None:
+                for t in self._aov:
+                    t.Release()
+            self._aov = tuple(RenderTexture(self.ctx, self.screen_width, self.screen_height) for _ in range(4))
+        self.ctx.render_aov(*self._aov, frame_ray=frame_ray)
+        return self._aov
+
     # RM:760-769: a camera move resets the running mean
     def ResetAccumulation(self):
         self._currentSample = 0
@@ -293,10 +314,11 @@ class RayTraceMaster:
                   self._sphereBVHBuffer, self._meshObjectBVHBuffer):
             if b is not None:
                 b.Release()
-        for t in (self._target, self._converged, self.SkyboxTexture):
+        for t in (self._target, self._converged, self.SkyboxTexture) + (self._aov or ()):
             if t is not None:
                 t.Release()
         self._target = self._converged = self.SkyboxTexture = None
+        self._aov = None
 
     # ---- multi-GPU frame-end gather (no counterpart in the reference: it is single-GPU) -----------
     def gather_converged(self, dist, device):

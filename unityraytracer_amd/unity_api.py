@@ -168,6 +168,45 @@ class Context:
         return {"distance": out[:, 0], "position": out[:, 1:4], "normal": out[:, 4:7], "kind": bits[:, 7], "object": bits[:, 8],
                 "primitive": bits[:, 9], "u": out[:, 10], "v": out[:, 11]}
 
+    def render_aov(self, hit=None, normal=None, albedo=None, id=None, frame_ray: bool = False):
+        """Per-pixel first-hit feature buffers of the bound camera into RenderTextures of one size (include/urt.h urt_render_aov):
+        hit = position.xyz, distance; normal = normal.xyz, kind; albedo = clamped albedo.xyz, smoothness (a miss: sky radiance, 0);
+        id = object, primitive (int32 bits), u, v.  None = not wanted.  frame_ray: the first camera ray of a frame dispatched now instead
+        of the pixel centre.  Enqueued on the context's stream after the deferred frames; a later GetPixels sees the result."""
+        targets = (("hit", hit), ("normal", normal), ("albedo", albedo), ("id", id))
+        for name, t in targets:
+            if t is not None and not isinstance(t, RenderTexture):
+                raise TypeError(f"render_aov: {name} must be a RenderTexture or None, not {type(t).__name__}")
+            if t is not None and t.ctx is not self:
+                raise ValueError(f"render_aov: {name} belongs to another context")
+            if t is not None and not t.handle:
+                raise ValueError(f"render_aov: {name} was released")
+        if all(t is None for _, t in targets):
+            raise ValueError("render_aov: no target given")
+        if not isinstance(frame_ray, (bool, np.bool_)):
+            raise TypeError(f"render_aov: frame_ray must be a bool, not {type(frame_ray).__name__}")
+        flags = _lib.URT_AOV_FRAME_RAY if frame_ray else _lib.URT_AOV_PIXEL_CENTER
+        h = [t.handle if t is not None else 0 for _, t in targets]
+        self.check(self.lib.urt_render_aov(self._h, h[0], h[1], h[2], h[3], flags))
+
+    def render_aov_arrays(self, width: int, height: int, frame_ray: bool = False) -> dict:
+        """render_aov into four temporary width x height textures, read back as numpy arrays indexed [y, x] (row 0 = bottom):
+        position (h, w, 3), distance, normal (h, w, 3), kind (int32), albedo (h, w, 3), smoothness, object and primitive (int32), u, v."""
+        width, height = int(width), int(height)
+        if width <= 0 or height <= 0:
+            raise ValueError(f"render_aov_arrays: size must be positive, not {width} x {height}")
+        tex = [RenderTexture(self, width, height) for _ in range(4)]
+        try:
+            self.render_aov(*tex, frame_ray=frame_ray)
+            hit, nrm, alb, ids = (t.GetPixels() for t in tex)
+        finally:
+            for t in tex:
+                t.Release()
+        bits = ids.view(np.int32)
+        return {"position": hit[..., :3], "distance": hit[..., 3], "normal": nrm[..., :3], "kind": nrm[..., 3].astype(np.int32),
+                "albedo": alb[..., :3], "smoothness": alb[..., 3], "object": bits[..., 0].copy(), "primitive": bits[..., 1].copy(),
+                "u": ids[..., 2], "v": ids[..., 3]}
+
 
 # urt_Ray / urt_RayHit (include/urt_types.h) as numpy records
 RAY_DT = np.dtype([("origin", np.float32, 3), ("t_max", np.float32), ("direction", np.float32, 3), ("reserved", np.int32)])
