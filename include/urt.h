@@ -50,8 +50,9 @@ enum {
 };
 
 /* ---- library / context ------------------------------------------------------------------- */
-URT_API int urt_abi_version(void);                       /* bumps when this header changes incompatibly (still 4: the ray queries and
-                                                            the feature buffers were added without changing anything that existed) */
+URT_API int urt_abi_version(void);                       /* bumps when this header changes incompatibly (still 4: the ray queries,
+                                                            the feature buffers and the denoiser were added without changing anything
+                                                            that existed) */
 URT_API int urt_device_count(int* out_count);
 /* One context per process and GPU (the one-process-per-GPU model).  device = HIP ordinal. */
 URT_API int urt_context_create(int device, urt_context** out_ctx);
@@ -220,6 +221,43 @@ URT_API int urt_ray_query_device(urt_context* ctx, const void* d_rays, int n, vo
  *    nothing is written. */
 enum { URT_AOV_PIXEL_CENTER = 0, URT_AOV_FRAME_RAY = 1 };
 URT_API int urt_render_aov(urt_context* ctx, urt_handle hit, urt_handle normal, urt_handle albedo, urt_handle id, int flags);
+
+/* ---- denoising ---------------------------------------------------------------------------- */
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over the colour of `src` (typically the accumulated image, RM:12 _converged),
+ * guided by the `hit` and `normal` feature buffers of urt_render_aov and optionally by `albedo` (0 = no demodulation).  All five images
+ * are existing RGBA32F textures (own or external) of one size.  Per pixel p: c_p = src.rgb, a_p = src.a, n_p = normal.xyz,
+ * k_p = normal.w, z_p = hit.w, A_p = albedo.rgb.
+ *  1. p passes through when k_p == 0, z_p is not finite or <= 0, or a component of c_p or n_p is not finite: dst = src bit for bit, and
+ *     p is never a tap of another pixel.  Every other pixel is a surface pixel.
+ *  2. demodulation: d_p = fmaxf(A_p, 1e-3f) per channel (a NaN channel gives 1e-3) with an albedo target, else 1; the filter runs on
+ *     c_p / d_p.
+ *  3. pass i = 0 .. iterations - 1, tap spacing s = 2^i: taps q = p + s (dx, dy), dx, dy in -2..2; taps outside the image and pass-through
+ *     taps are skipped (no clamping, no mirroring).  h = {1/16, 1/4, 3/8, 1/4, 1/16};
+ *       w_pq = h[dx] h[dy] exp(-(|c_p - c_q|^2 / (sigma_color 2^-i)^2 + |n_p - n_q|^2 / sigma_normal^2 + ((z_p - z_q) / (sigma_depth z_p))^2))
+ *     where a term whose sigma is <= 0 is left out;  c'_p = sum w_pq c_q / sum w_pq  (the centre tap always counts).  c is the previous
+ *     pass's output.
+ *  4. dst.rgb = c_p d_p after the last pass, dst.a = a_p.
+ * The kernels fold the constants so that each tap costs one exp2f; per channel, |result - formula in float64| <= 1e-4 (1 + |formula|).
+ * params == NULL: the defaults below (chosen on 4-frame accumulations of the mixed test scene and C4, DESIGN.md "Denoising").
+ *  - like urt_render_aov, it submits the deferred frames first (src is usually a deferred blit's destination), then enqueues the passes
+ *    on the context's stream and returns without synchronising.  The scene is not read (not prepared); urt_counters are not changed.
+ *  - dst == src is allowed (the last pass reads src only at its own pixel).
+ *  - scratch: three float4 images of the size, held by the context and grown on demand (URT_ERR_OUT_OF_MEMORY when that fails).
+ *  - URT_ERR_INVALID_ARGUMENT: dst equal to hit, normal or albedo, or bound as _SkyboxTexture; sizes differ; iterations outside 1..5; a
+ *    NaN sigma.  URT_ERR_INVALID_HANDLE: src, dst, hit or normal 0 or unknown, albedo unknown.  On any error nothing is written and
+ *    nothing is enqueued. */
+typedef struct urt_DenoiseParams {   /* 16 bytes */
+  int32_t iterations;   /* 1..5: passes with tap spacing s = 1, 2, 4, 8, 16 */
+  float sigma_color;    /* colour edge stop, halved every pass; <= 0: no colour term */
+  float sigma_normal;   /* normal edge stop; <= 0: no normal term */
+  float sigma_depth;    /* relative-depth edge stop; <= 0: no depth term */
+} urt_DenoiseParams;
+#define URT_DENOISE_DEFAULT_ITERATIONS 5
+#define URT_DENOISE_DEFAULT_SIGMA_COLOR 8.0f
+#define URT_DENOISE_DEFAULT_SIGMA_NORMAL 0.5f
+#define URT_DENOISE_DEFAULT_SIGMA_DEPTH 0.1f
+URT_API int urt_denoise(urt_context* ctx, urt_handle src, urt_handle dst, urt_handle hit, urt_handle normal, urt_handle albedo,
+                        const urt_DenoiseParams* params);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 typedef struct urt_counters {

@@ -81,6 +81,16 @@ internal static class UrtNative {
     internal const int AovPixelCenter = 0, AovFrameRay = 1;
     [DllImport(Lib)] internal static extern int urt_render_aov(IntPtr ctx, ulong hit, ulong normal, ulong albedo, ulong id, int flags);
 
+    // ---- denoising (include/urt.h "denoising"): src, dst, hit, normal, albedo (0 = no demodulation) texture handles --------
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct DenoiseParams {                         // urt_DenoiseParams, 16 B; a sigma <= 0 leaves its term out
+        public int iterations;                              // 1..5
+        public float sigmaColor;
+        public float sigmaNormal;
+        public float sigmaDepth;
+    }
+    [DllImport(Lib)] internal static extern int urt_denoise(IntPtr ctx, ulong src, ulong dst, ulong hit, ulong normal, ulong albedo, in DenoiseParams p);
+
     // ---- measurement ----------------------------------------------------------------------------------------------------
     [StructLayout(LayoutKind.Sequential)]
     internal struct Counters {

@@ -78,6 +78,36 @@ public static class UrtFeatureBuffers {
     }
 }
 
+/// Edge-aware denoise (include/urt.h urt_denoise) of device images the engine owns: the accumulated image `src` (RM:12 _converged's
+/// RenderTexture), the output `dst` (may be src) and the hit / normal / albedo feature buffers UrtFeatureBuffers.Render wrote
+/// (IntPtr.Zero albedo = no demodulation), all ARGBFloat of one size.  Call it every frame before the present; refresh the guides with
+/// UrtFeatureBuffers.Render when the camera moves (the accumulation resets then too).  Defaults: include/urt.h URT_DENOISE_DEFAULT_*.
+public static class UrtDenoiser {
+    static IntPtr boundCtx = IntPtr.Zero;
+    static readonly ulong[] handles = new ulong[5];
+    static readonly IntPtr[] ptrs = new IntPtr[5];
+    static int w, h;
+    public static void Denoise(IntPtr src, IntPtr dst, IntPtr hit, IntPtr normal, IntPtr albedo, int width, int height,
+                               int iterations = 5, float sigmaColor = 8.0f, float sigmaNormal = 0.5f, float sigmaDepth = 0.1f) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtDenoiser: denoise on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        IntPtr[] want = { src, dst, hit, normal, albedo };
+        for (int k = 0; k < 5; k++) {                                  // the external textures are re-wrapped when a pointer or the size changes
+            if (handles[k] != 0 && (boundCtx != ctx || ptrs[k] != want[k] || w != width || h != height)) {
+                if (boundCtx == ctx) UrtDevice.Check(UrtNative.urt_texture_release(ctx, handles[k]));
+                handles[k] = 0;
+            }
+            if (handles[k] == 0 && want[k] != IntPtr.Zero && !(k == 1 && want[1] == want[0]))
+                UrtDevice.Check(UrtNative.urt_texture_create_external(ctx, width, height, want[k], out handles[k]));
+            ptrs[k] = want[k];
+        }
+        boundCtx = ctx; w = width; h = height;
+        ulong dstHandle = dst == src ? handles[0] : handles[1];           // in place: one handle for both
+        var p = new UrtNative.DenoiseParams { iterations = iterations, sigmaColor = sigmaColor, sigmaNormal = sigmaNormal, sigmaDepth = sigmaDepth };
+        UrtDevice.Check(UrtNative.urt_denoise(ctx, handles[0], dstHandle, handles[2], handles[3], handles[4], in p));
+    }
+}
+
 /// new ComputeBuffer(count, stride); .SetData(List<T>); .Release(); .count; .stride            (RM:233-252)
 public sealed class UrtComputeBuffer {
     internal ulong handle;

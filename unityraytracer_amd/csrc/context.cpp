@@ -30,6 +30,7 @@
 #include "present.h"
 #include "query.h"
 #include "aov.h"
+#include "denoise.h"
 #include "urt_device.h"
 
 #include <chrono>
@@ -229,6 +230,8 @@ struct urt_context {
   uint64_t overlapped_launches = 0;
   // urt_ray_query (host memory): grow-only device scratch for the rays and the results, q_cap rays each
   float4* q_rays = nullptr; float4* q_out = nullptr; size_t q_cap = 0;
+  // urt_denoise: grow-only device scratch of 3 float4 images (guide, two colour images) of dn_cap pixels each
+  float4* dn_scratch = nullptr; size_t dn_cap = 0;
 };
 
 namespace { inline hipStream_t touch(urt_context* ctx) { ctx->main_touched = true; return ctx->stream; } }
@@ -1496,6 +1499,7 @@ int urt_context_destroy(urt_context* ctx) {
   for (int a = 0; a < 2; a++) for (int r = 0; r < 4; r++) if (ctx->q.s[a][r]) (void)hipFree(ctx->q.s[a][r]);
   if (ctx->q.counts) (void)hipFree(ctx->q.counts);
   if (ctx->zero_sky) (void)hipFree(ctx->zero_sky);
+  if (ctx->dn_scratch) (void)hipFree(ctx->dn_scratch);
   if (ctx->d_counters) (void)hipFree(ctx->d_counters);
   if (ctx->d_next) (void)hipFree(ctx->d_next);
   if (ctx->d_next2) (void)hipFree(ctx->d_next2);
@@ -2072,6 +2076,63 @@ int urt_render_aov(urt_context* ctx, urt_handle hit, urt_handle normal, urt_hand
   T.width = width; T.height = height;
   for (int k = 0; k < 4; k++) if (t[k]) t[k]->other_writes = true;
   URT_HIP(ctx, launch_aov(S, ctx->aov_albedo, ctx->tlas_stack, ctx->blas_stack, C, T, touch(ctx)));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+/* ---- denoising ---- */
+// Every argument is checked and the scratch is grown before anything is submitted: on an error nothing is enqueued.  Then the deferred
+// frames are submitted (src is usually a deferred blit's destination) and the passes are enqueued on the main stream.  The scene is not
+// read and the counters are not changed.
+int urt_denoise(urt_context* ctx, urt_handle src, urt_handle dst, urt_handle hit, urt_handle normal, urt_handle albedo,
+                const urt_DenoiseParams* params) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  urt_DenoiseParams P{URT_DENOISE_DEFAULT_ITERATIONS, URT_DENOISE_DEFAULT_SIGMA_COLOR, URT_DENOISE_DEFAULT_SIGMA_NORMAL,
+                      URT_DENOISE_DEFAULT_SIGMA_DEPTH};
+  if (params) P = *params;
+  if (P.iterations < 1 || P.iterations > 5) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "denoise: iterations must be 1..5");
+  if (std::isnan(P.sigma_color) || std::isnan(P.sigma_normal) || std::isnan(P.sigma_depth))
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "denoise: a sigma is NaN");
+  const urt_handle h[5] = {src, dst, hit, normal, albedo};
+  const char* const names[5] = {"src", "dst", "hit", "normal", "albedo"};
+  Texture* t[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int k = 0; k < 5; k++) {
+    if (k == 4 && !h[k]) continue;                                 // no albedo: no demodulation
+    t[k] = find_texture(ctx, h[k]);
+    if (!t[k]) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string("denoise: unknown ") + names[k] + " texture handle");
+  }
+  if (dst == hit || dst == normal || dst == albedo)
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "denoise: dst is one of the guide textures");
+  if (dst == ctx->t_sky) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "denoise: dst is the texture bound as _SkyboxTexture");
+  const int width = t[0]->w, height = t[0]->h;
+  for (int k = 1; k < 5; k++)
+    if (t[k] && (t[k]->w != width || t[k]->h != height)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "denoise: the textures differ in size");
+  if ((height + 15) / 16 > 65535) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "denoise: textures taller than 1048560 pixels");
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t n = (size_t)width * (size_t)height;
+  if (n > ctx->dn_cap) {
+    if (ctx->dn_scratch) {
+      URT_HIP(ctx, hipStreamSynchronize(ctx->stream));             // queued passes may still use the old scratch
+      (void)hipFree(ctx->dn_scratch);
+      ctx->dn_scratch = nullptr; ctx->dn_cap = 0;
+    }
+    hipError_t e = hipMalloc((void**)&ctx->dn_scratch, 3 * n * sizeof(float4));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->dn_scratch = nullptr;
+      return fail(ctx, e == hipErrorOutOfMemory ? URT_ERR_OUT_OF_MEMORY : URT_ERR_HIP,
+                  std::string("denoise: scratch allocation: ") + hipGetErrorString(e));
+    }
+    ctx->dn_cap = n;
+  }
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  DenoiseImages I{};                                               // device pointers after the flush (a Result texture may be renamed)
+  I.src = t[0]->dev; I.dst = t[1]->dev; I.hit = t[2]->dev; I.normal = t[3]->dev; I.albedo = t[4] ? t[4]->dev : nullptr;
+  I.scratch = ctx->dn_scratch; I.width = width; I.height = height;
+  DenoiseSettings S{P.iterations, P.sigma_color, P.sigma_normal, P.sigma_depth};
+  t[1]->other_writes = true;
+  URT_HIP(ctx, launch_denoise(I, S, touch(ctx)));
   return URT_OK;
   URT_GUARD_END(ctx)
 }

@@ -23,7 +23,7 @@ import numpy as np
 from dataclasses import dataclass, field
 
 from . import host_scene, scenes
-from .unity_api import ComputeBuffer, ComputeShader, Context, Graphics, Material, RenderTexture
+from .unity_api import ComputeBuffer, ComputeShader, Context, Graphics, Material, RenderTexture, denoise_params
 
 
 @dataclass
@@ -69,6 +69,7 @@ class RayTraceMaster:
         self._sphereBuffer = self._meshObjectBVHBuffer = self._sphereBVHBuffer = None
         self.screen_width, self.screen_height = scene.width, scene.height
         self._aov = None                             # RenderFeatureBuffers: (hit, normal, albedo, id) of the screen size
+        self._denoised = None                        # Denoise without a destination: the denoised image
 
     # RM:215-230
     def RegisterObject(self, obj: RayTraceObject):
@@ -261,6 +262,31 @@ class RayTraceMaster:
         self.ctx.render_aov(*self._aov, frame_ray=frame_ray)
         return self._aov
 
+    # The progressive image `_converged` (RM:12), denoised with this master's feature buffers as guides (include/urt.h urt_denoise):
+    # hit, normal and albedo of RenderFeatureBuffers, rendered here when they do not exist yet or have another size (a host refreshes
+    # them when the camera moves).  Writes into `destination`, or into a screen-sized texture this master owns, and returns it.
+    # params: iterations, sigma_color, sigma_normal, sigma_depth of Context.denoise.
+    def Denoise(self, destination: RenderTexture | None = None, **params):
+        from ._lib import UrtError
+        if self._converged is None or not self._converged.handle:
+            raise UrtError(2, "Denoise: no accumulated image yet (render a frame first)")
+        if destination is not None and not isinstance(destination, RenderTexture):
+            raise TypeError(f"Denoise: destination must be a RenderTexture or None, not {type(destination).__name__}")
+        if destination is not None and (destination.ctx is not self.ctx or not destination.handle):
+            raise ValueError("Denoise: destination belongs to another context or was released")
+        denoise_params(**params)                                                  # checked before anything reaches the library
+        if self._aov is None or self._aov[0].width != self._converged.width or self._aov[0].height != self._converged.height:
+            self.RenderFeatureBuffers()
+        if destination is None:
+            if self._denoised is None or self._denoised.width != self._converged.width or self._denoised.height != self._converged.height:
+                if self._denoised is not None:
+                    self._denoised.Release()
+                self._denoised = RenderTexture(self.ctx, self._converged.width, self._converged.height)
+            destination = self._denoised
+        hit, normal, albedo, _ = self._aov
+        self.ctx.denoise(self._converged, destination, hit, normal, albedo, **params)
+        return destination
+
     # RM:760-769: a camera move resets the running mean
     def ResetAccumulation(self):
         self._currentSample = 0
@@ -314,10 +340,10 @@ class RayTraceMaster:
                   self._sphereBVHBuffer, self._meshObjectBVHBuffer):
             if b is not None:
                 b.Release()
-        for t in (self._target, self._converged, self.SkyboxTexture) + (self._aov or ()):
+        for t in (self._target, self._converged, self.SkyboxTexture, self._denoised) + (self._aov or ()):
             if t is not None:
                 t.Release()
-        self._target = self._converged = self.SkyboxTexture = None
+        self._target = self._converged = self.SkyboxTexture = self._denoised = None
         self._aov = None
 
     # ---- multi-GPU frame-end gather (no counterpart in the reference: it is single-GPU) -----------

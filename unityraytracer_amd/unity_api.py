@@ -207,11 +207,78 @@ class Context:
                 "albedo": alb[..., :3], "smoothness": alb[..., 3], "object": bits[..., 0].copy(), "primitive": bits[..., 1].copy(),
                 "u": ids[..., 2], "v": ids[..., 3]}
 
+    def denoise(self, src, dst, hit, normal, albedo=None, iterations: int = _lib.DENOISE_DEFAULTS["iterations"],
+                sigma_color: float = _lib.DENOISE_DEFAULTS["sigma_color"], sigma_normal: float = _lib.DENOISE_DEFAULTS["sigma_normal"],
+                sigma_depth: float = _lib.DENOISE_DEFAULTS["sigma_depth"]):
+        """Edge-aware a-trous denoise of src's colour into dst, guided by the hit and normal feature buffers of render_aov and optionally
+        by albedo (include/urt.h urt_denoise).  RenderTextures of one size; dst may be src.  A sigma <= 0 leaves its term out.  Enqueued on
+        the context's stream after the deferred frames; a later GetPixels sees the result."""
+        targets = (("src", src), ("dst", dst), ("hit", hit), ("normal", normal), ("albedo", albedo))
+        for name, t in targets:
+            if t is None and name == "albedo":
+                continue
+            if not isinstance(t, RenderTexture):
+                raise TypeError(f"denoise: {name} must be a RenderTexture{' or None' if name == 'albedo' else ''}, not {type(t).__name__}")
+            if t.ctx is not self:
+                raise ValueError(f"denoise: {name} belongs to another context")
+            if not t.handle:
+                raise ValueError(f"denoise: {name} was released")
+            if (t.width, t.height) != (src.width, src.height):
+                raise ValueError(f"denoise: {name} is {t.width} x {t.height}, src is {src.width} x {src.height}")
+        if any(dst is t for t in (hit, normal, albedo)):
+            raise ValueError("denoise: dst is one of the guide textures")
+        p = denoise_params(iterations, sigma_color, sigma_normal, sigma_depth)
+        self.check(self.lib.urt_denoise(self._h, src.handle, dst.handle, hit.handle, normal.handle, albedo.handle if albedo is not None else 0,
+                                        C.byref(p)))
+
+    def denoise_arrays(self, color, hit, normal, albedo=None, **params) -> np.ndarray:
+        """denoise on numpy images (h, w, 4) float32, row 0 = bottom (the layouts of render_aov: hit.w = distance, normal.w = kind,
+        albedo.rgb), through temporary textures; returns the denoised (h, w, 4) image."""
+        imgs = [np.ascontiguousarray(a, dtype=np.float32) for a in (color, hit, normal) + ((albedo,) if albedo is not None else ())]
+        shape = imgs[0].shape
+        if len(shape) != 3 or shape[2] != 4 or shape[0] <= 0 or shape[1] <= 0:
+            raise ValueError(f"denoise_arrays: color must be (h, w, 4), not {shape}")
+        for a in imgs[1:]:
+            if a.shape != shape:
+                raise ValueError(f"denoise_arrays: the images differ in shape ({a.shape} vs {shape})")
+        h, w = shape[:2]
+        tex = []
+        try:
+            for a in imgs + [None]:
+                tex.append(RenderTexture(self, w, h))
+                if a is not None:
+                    tex[-1].SetPixels(a)
+            src, hit_t, nrm_t = tex[:3]
+            alb_t = tex[3] if albedo is not None else None
+            out = tex[-1]
+            self.denoise(src, out, hit_t, nrm_t, alb_t, **params)
+            return out.GetPixels()
+        finally:
+            for t in tex:
+                t.Release()
+
 
 # urt_Ray / urt_RayHit (include/urt_types.h) as numpy records
 RAY_DT = np.dtype([("origin", np.float32, 3), ("t_max", np.float32), ("direction", np.float32, 3), ("reserved", np.int32)])
 RAYHIT_DT = np.dtype([("distance", np.float32), ("position", np.float32, 3), ("normal", np.float32, 3), ("kind", np.int32),
                       ("object", np.int32), ("primitive", np.int32), ("u", np.float32), ("v", np.float32)])
+
+
+def denoise_params(iterations: int = _lib.DENOISE_DEFAULTS["iterations"], sigma_color: float = _lib.DENOISE_DEFAULTS["sigma_color"],
+                   sigma_normal: float = _lib.DENOISE_DEFAULTS["sigma_normal"],
+                   sigma_depth: float = _lib.DENOISE_DEFAULTS["sigma_depth"]) -> _lib.DenoiseParams:
+    """The checked urt_DenoiseParams of Context.denoise: iterations an int in 1..5, each sigma a number that is not NaN."""
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)):
+        raise TypeError(f"denoise: iterations must be an int, not {type(iterations).__name__}")
+    if not 1 <= iterations <= 5:
+        raise ValueError(f"denoise: iterations must be 1..5, not {iterations}")
+    sigmas = {"sigma_color": sigma_color, "sigma_normal": sigma_normal, "sigma_depth": sigma_depth}
+    for name, v in sigmas.items():
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError(f"denoise: {name} must be a number, not {type(v).__name__}")
+        if np.isnan(v):
+            raise ValueError(f"denoise: {name} is NaN")
+    return _lib.DenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_depth))
 
 
 def _is_torch(a) -> bool:
