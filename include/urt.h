@@ -322,7 +322,8 @@ typedef struct urt_counters {
  *          "stack_pad" (0..96: test hook, unused extra entries per traversal stack -> the > 64 KiB LDS launch path),
  *          "qnodes" (0 off, the default | 1 on | -1 on unless some MeshObject spans fewer than 1024 grid cells: the traversal loop of the default
  *                    kernel reads 32-byte quantized copies of the triangle-BVH nodes — two vector loads per node step instead of four; conservative
- *                    boxes on one 16-bit grid over the whole forest, csrc/qnodes.hip.  A measured alternative: same pixels, -1.3 % frame time on
+ *                    boxes on one 16-bit grid over the whole forest, csrc/qnodes.hip; a forest too large for the grid's plane arithmetic (cell
+ *                    > 2^43) keeps the float nodes, see urt_debug_read_scene_qnodes.  A measured alternative: same pixels, -1.3 % frame time on
  *                    single-mesh scenes, +1.3 % on C4 / C5: the loop waits on the latency of one dependent fetch per step, not on its width),
  *          "refit" (0/1, default 1: moved MeshObjects are refitted on the GPU instead of rebuilt — see urt_debug_refit_stats),
  *          "watchdog_cap" (test hook: scheduler trips a wave may make before it gives up; 0 = auto = 2^24 x frames of the launch x
@@ -482,6 +483,11 @@ typedef struct urt_launch_info {
 } urt_launch_info;
 URT_API int urt_debug_launch_info(urt_context* ctx, urt_launch_info* out_info);
 URT_API int urt_debug_read_scene_blas(urt_context* ctx, float* nodes, int32_t* tri_index, int32_t* mesh_root);
+/* The 32-byte quantized triangle-BVH nodes of option "qnodes" (prepares a stale scene first): out receives 2 + 2 n float4 — grid
+ * origin.xyz and quality (the smallest MeshObject in cells), cell.xyz and 0, then one 32-byte node per float node (csrc/qnodes.hip).
+ * *out_n_nodes = n, or 0 while "qnodes" is 0 (then nothing is written; out may be NULL to ask for n first).  *out_in_use = 1 when
+ * the traversal loop of the default trace kernel reads them (qnodes = 1, or -1 and a fine enough grid), else 0. */
+URT_API int urt_debug_read_scene_qnodes(urt_context* ctx, float* out, int* out_n_nodes, int* out_in_use);
 /* Scene preparation of a context keeps the triangle BVH of every MeshObject and reuses it at the next preparation when the
  * MeshObject's matrix and the positions behind its index slots are unchanged (the reference re-uploads every buffer when
  * any object moves, RM:262-336).  Reports how many MeshObject BVHs were reused / built since the context was created. */

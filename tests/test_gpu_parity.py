@@ -88,9 +88,13 @@ SCHED_VARIANTS = [
     {"refill_min": 64, "blas_min": 64, "blas_exit": 64, "shade_min": 64, "waves_per_cu": 32},
     {"front_list": 2},                                        # the listed FRONT (the default for this scene is the masked one)
     {"front_list": 0},                                        # neither: the heap walk with the BVH top inside it
+    {"shade_split": 0},                                       # surface hits and misses shaded in one trip
+    {"sky_min": 1},
+    {"sky_min": 64},
 ]
 SCHED_DEFAULTS = {"sched_block": 0, "top_nodes": -1, "top_front": -1, "lds_tlas": 1, "tile_order": -1, "xcd_run": 0,
-                  "refill_min": 16, "blas_min": 0, "blas_exit": 0, "waves_per_cu": 0, "shade_min": 32, "front_list": -1}
+                  "refill_min": 16, "blas_min": 0, "blas_exit": 0, "waves_per_cu": 0, "shade_min": 32, "front_list": -1,
+                  "shade_split": -1, "sky_min": 32}
 
 
 @pytest.mark.parametrize("variant", range(len(SCHED_VARIANTS)))

@@ -514,13 +514,16 @@ int requantize(urt_context* ctx) {
   S.blas_qnodes = nullptr;
   if (ctx->opt_qnodes == 0 || !ctx->qbuf || ctx->n_blas_nodes <= 0) return URT_OK;
   URT_HIP(ctx, quantize_nodes(S.blas_nodes, ctx->n_blas_nodes, S.mesh_root, S.n_meshes, ctx->qbuf, touch(ctx)));
-  float4 f0;
-  URT_HIP(ctx, hipMemcpyAsync(&f0, ctx->qbuf, sizeof f0, hipMemcpyDeviceToHost, touch(ctx)));
+  float4 f[2];
+  URT_HIP(ctx, hipMemcpyAsync(f, ctx->qbuf, sizeof f, hipMemcpyDeviceToHost, touch(ctx)));
   URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
-  ctx->qnode_quality = f0.w;
+  ctx->qnode_quality = f[0].w;
+  // the traversal's planes are fma(2^23 + q, S, B) with S = cell / d and |1 / d| <= 1e18 (blas_rcp): 2^24 S must stay finite, so a
+  // forest whose grid cell exceeds 2^43 (an extent of ~5.8e17) cannot use them, whatever the option says (tests/test_qnodes_ref.py)
+  const bool fits = std::max(std::max(f[1].x, f[1].y), f[1].z) <= 8796093022208.0f;
   // one grid for the whole forest: a MeshObject that spans only a few hundred cells would have boxes of a few cells — every ray through
   // it would walk most of its tree.  Such scenes keep the float nodes (auto); "qnodes" = 1 insists.
-  if (ctx->opt_qnodes == 1 || f0.w >= 1024.0f) S.blas_qnodes = ctx->qbuf;
+  if (fits && (ctx->opt_qnodes == 1 || f[0].w >= 1024.0f)) S.blas_qnodes = ctx->qbuf;
   return URT_OK;
 }
 
@@ -2407,6 +2410,21 @@ int urt_debug_read_scene_blas(urt_context* ctx, float* nodes, int32_t* tri_index
     URT_HIP(ctx, hipMemcpy(tv.data(), S.tri_verts, tv.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (int k = 0; k < ctx->n_scene_tris; k++) std::memcpy(&tri_index[k], &tv[(size_t)k * 12 + 3], 4);     // index slot kept in v0.w
   }
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+int urt_debug_read_scene_qnodes(urt_context* ctx, float* out, int* out_n_nodes, int* out_in_use) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  if (ctx->scene_dirty) { int rc = flush_pending(ctx); if (rc) return rc; rc = prepare_scene(ctx); if (rc) return rc; }
+  URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
+  // qbuf exists (and is current) only while the option is on: it is derived after every build and refit (rederive_nodes)
+  const bool have = ctx->opt_qnodes != 0 && ctx->qbuf && ctx->n_blas_nodes > 0;
+  if (out_n_nodes) *out_n_nodes = have ? ctx->n_blas_nodes : 0;
+  if (out_in_use) *out_in_use = ctx->ds.blas_qnodes != nullptr ? 1 : 0;
+  if (out && have) URT_HIP(ctx, hipMemcpy(out, ctx->qbuf, (2 + 2 * (size_t)ctx->n_blas_nodes) * sizeof(float4), hipMemcpyDeviceToHost));
   return URT_OK;
   URT_GUARD_END(ctx)
 }

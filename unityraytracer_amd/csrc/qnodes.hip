@@ -6,11 +6,14 @@
 // codes) takes four; the form built here takes two:
 //     dwords 0-2: child 0  lo.x | lo.y << 16,  lo.z | hi.x << 16,  hi.y | hi.z << 16      (16-bit grid coordinates)
 //     dwords 3-5: child 1, the same            dwords 6-7: the two child codes, unchanged
-// The grid is ONE frame for the whole forest: origin = the lower corner of the union of all root boxes, cell = extent / 65531 per
-// axis.  A box is rounded OUTWARD and widened by two more cells, which covers the rounding of the traversal's own arithmetic
-// (kernels.hip qnode_eval_flat: t = fma(2^23 + q, cell / d, B) with B folding origin, ray and the 2^23 offset: error <= 0.5 cell).
-// Quantized boxes only CULL — conservatively; the Moller-Trumbore tests decide the hits — so pixels are the float nodes' pixels;
-// visit counts differ slightly (the counting instantiation of the kernel walks the float nodes, like the oracle).
+// The grid is ONE frame for the whole forest: per axis, cell = max(extent / 65525, 2^-20 max |coordinate|) and origin = 3 cells below
+// the lower corner of the union of all root boxes, so the union occupies codes [3, 65531].  A box is rounded OUTWARD and widened by two
+// more cells on every face — the grid's corners included: no face is clamped into its margin —, which covers the rounding of the
+// traversal's own arithmetic (trace_device.h make_qray / qnode_eval_ptr: t = fma(2^23 + q, cell / d, B) with B folding origin, ray and
+// the 2^23 offset: error <= 1 cell, plus 2^-24 |origin| <= 1/16 cell).  Quantized boxes only CULL — conservatively; the Moller-Trumbore
+// tests decide the hits — so pixels are the float nodes' pixels; visit counts differ slightly (the counting instantiation of the kernel
+// walks the float nodes, like the oracle).  tests/qnodes_ref.py restates both kernels and the slab test; tests/test_qnodes_ref.py checks
+// the margins and the slab test on millions of rays near box faces, tests/test_gpu_qnodes.py the read-back and the frames bit for bit.
 // qbuf[0] = origin.xyz, quality (smallest MeshObject extent in cells);  qbuf[1] = cell.xyz, 0;  node n at qbuf[2 + 2 n].
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,9 +55,12 @@ __global__ __launch_bounds__(256) void k_qframe(const float4* __restrict__ nodes
     for (int k = 0; k < 3; k++) {
       float a = slo[k][0], b = shi[k][0];
       if (!(a <= b)) { a = 0.0f; b = 0.0f; }
-      float ext = b - a;
-      org[k] = a;
-      cell[k] = f_max(ext * (1.0f / 65531.0f), 1e-30f) * 1.0000002f;      // (a hair more than extent / 65531: the top plane lands below 65533)
+      float ext = b - a, mag = f_max(f_abs(a), f_abs(b));
+      // a hair more than extent / 65525, and at least 2^-20 of the largest |coordinate| (the traversal's fma(origin, 1/d, ..) rounds
+      // by 2^-24 |origin|: 1/16 cell at most).  The union then starts 3 cells above the origin and ends 4 below code 65535, so that no
+      // face is clamped into its two cells of margin (tests/test_qnodes_ref.py)
+      cell[k] = f_max(f_max(ext * (1.0f / 65525.0f), mag * 9.5367431640625e-7f), 1e-30f) * 1.0000002f;
+      org[k] = a - 3.0f * cell[k];
     }
     qbuf[1] = make_float4(cell[0], cell[1], cell[2], 0.0f);
   }

@@ -225,8 +225,10 @@ __device__ __forceinline__ int32_t blas_node_eval_ptr(float4 q0, float4 q1, floa
 // The same step on a 32-byte QUANTIZED node (csrc/qnodes.hip): two dwordx4 loads instead of four.  The twelve planes are 16-bit grid
 // coordinates q; a plane's slab value is t = (origin + q cell - (o +- pad)) / d = fma(Q, S, B) with Q = 2^23 + q — built in ONE
 // instruction per plane by putting q into the mantissa of 2^23 (0x4B000000 | q) —, S = cell / d and B = (origin - (o +- pad)) / d - 2^23 S
-// per axis (QRay, derived from the ray at phase entry).  The 2^23 S terms cancel exactly but for the rounding of B: half a cell
-// at worst, covered by the two cells the quantizer adds on every side.  Conservative culling only: the hits are the triangle tests'.
+// per axis (QRay, derived from the ray at phase entry).  The 2^23 S terms cancel exactly but for the rounding of B: one cell at worst
+// (|B| < 2^24 S), plus 2^-24 |origin| from the inner fma (<= 1/16 cell: the grid's cell is at least 2^-20 of it); the per-ray pad covers
+// the rounding of o.  The two cells the quantizer adds on every face cover the rest (tests/test_qnodes_ref.py checks both on rays near
+// box faces, grazing and axis-parallel ones included).  Conservative culling only: the hits are the triangle tests'.
 struct QRay { v3 S, Bp, Bm; };
 __device__ __forceinline__ QRay make_qray(v3 o, v3 d, float4 forg, float4 fcell) {
   // the quantized planes are [lo, hi] planes: their per-ray constants are -(o +- pad) / d

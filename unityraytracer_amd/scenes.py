@@ -557,6 +557,66 @@ def deep_chain_scene(width=96, height=64, n=40, ratio=3.0, grow=1.8) -> Scene:
     return Scene("deep-chain", width, height, 3, 1, mesh_objects=mo, vertices=vv, indices=ii, normals=nn, mesh_bvh=bvh, sky=make_sky(64, 32))
 
 
+def grid_quad(corner, u, v, n, facing):
+    """A planar n x n grid of quads (2 n^2 triangles) over corner + [0, 1] u + [0, 1] v, oriented so that rays travelling along `facing`
+    hit its front side."""
+    corner, u, v = (np.asarray(x, np.float64) for x in (corner, u, v))
+    g = np.linspace(0.0, 1.0, n + 1)
+    verts = (corner + g[:, None, None] * u + g[None, :, None] * v).reshape(-1, 3).astype(np.float32)
+    k = np.arange(n * (n + 1)).reshape(n, n + 1)[:, :n].reshape(-1)
+    tris = np.concatenate([np.stack([k, k + n + 1, k + n + 2], 1), np.stack([k, k + n + 2, k + 1], 1)]).astype(np.int32)
+    v0, v1, v2 = (verts[tris[:, i]].astype(np.float64) for i in range(3))
+    ok = front_facing(v0, v1, v2, np.asarray(facing, np.float64))
+    tris[~ok] = tris[~ok][:, [0, 2, 1]]
+    return verts, tris
+
+
+QNODE_EDGE_KINDS = ("floor", "wall_x", "wall_z", "flat", "degenerate", "far", "axis")
+
+
+def qnode_edge_scene(kind: str, width=97, height=61) -> Scene:
+    """Scenes at the edges of the quantized triangle-BVH nodes (option "qnodes", csrc/qnodes.hip: one 16-bit grid over the whole forest):
+    floor / wall_x / wall_z   a tessellated floor (y = 0.5) or wall that is the forest's lowest mesh along y / x / z, small coordinates,
+                              a tall mesh stretching the grid far along that axis, and a low camera looking across the near edge;
+    flat                      every mesh planar in y at the same height: that axis spans only the builder's pad;
+    degenerate                one MeshObject whose vertices all sit at 0 (scale 0) and a floor: the 1e-30 floor of the cell size;
+    far                       the floor scene moved (with its camera) by 1e4 in x and z;
+    axis                      the floor scene from a level, unrotated camera: odd width and height give direction components of 0."""
+    b = MeshSceneBuilder()
+    white, red = _params((0.7, 0.7, 0.7), (0.1, 0.1, 0.1), (0, 0, 0), 0.4), _params((0.8, 0.2, 0.1), (0.2, 0.2, 0.2), (0, 0, 0), 0.7)
+    cam = dict(position=(0.3, 0.9, -2.6), pitch_deg=14.0, yaw_deg=8.0, fov_deg=70.0)
+    off = np.zeros(3)
+    if kind in ("floor", "far", "axis", "degenerate"):
+        off = np.array([1e4, 0.0, 1e4]) if kind == "far" else off
+        b.add(*grid_quad(off + (-1, 0.5, -1), (2, 0, 0), (0, 0, 2), 16, (0, -1, 0)), trs(), white)
+        if kind == "degenerate":
+            v, t = uv_blob(8, 6)
+            b.add(v, t, trs(translate=(0, 0, 0), scale=0.0), red)
+        else:
+            b.add(*grid_quad(off + (-1, 10, 3), (2, 0, 0), (0, 990, 0), 2, (0, 0, 1)), trs(), red)
+        if kind == "far":
+            cam["position"] = tuple(np.add(cam["position"], off))
+        if kind == "axis":
+            cam = dict(position=(0.0, 1.0, -4.0), fov_deg=60.0)
+    elif kind == "wall_x":
+        b.add(*grid_quad((-1.5, 0.5, -1), (0, 2, 0), (0, 0, 2), 16, (-1, 0, 0)), trs(), white)
+        b.add(*grid_quad((10, 3.0, -1), (990, 0, 0), (0, 0, 2), 2, (0, -1, 0)), trs(), red)
+        cam = dict(position=(1.2, 1.4, -2.8), yaw_deg=-38.0, pitch_deg=4.0, fov_deg=70.0)
+    elif kind == "wall_z":
+        b.add(*grid_quad((-1, 0.5, -1), (2, 0, 0), (0, 2, 0), 16, (0, 0, 1)), trs(), white)
+        b.add(*grid_quad((-1, 3.0, 10), (2, 0, 0), (0, 0, 990), 2, (0, -1, 0)), trs(), red)
+        cam = dict(position=(1.9, 1.3, -2.4), yaw_deg=-30.0, pitch_deg=5.0, fov_deg=70.0)
+    elif kind == "flat":
+        for k, (x, z, s) in enumerate(((-1.2, -0.8, 1.0), (0.9, 0.4, 0.7), (-0.2, 1.6, 1.4))):
+            b.add(*grid_quad((x - s, 0.7, z - s), (2 * s, 0, 0), (0, 0, 2 * s), 10, (0, -1, 0)), trs(), red if k == 1 else white)
+        cam = dict(position=(0.2, 1.6, -3.2), pitch_deg=22.0, fov_deg=70.0)
+    else:
+        raise ValueError(kind)
+    mo, vv, ii, nn, bvh = b.finish()
+    sc = Scene(f"qnode-edge-{kind}", width, height, 3, 1, mesh_objects=mo, vertices=vv, indices=ii, normals=nn, mesh_bvh=bvh, sky=make_sky(64, 32))
+    return sc.resized(width, height, **cam)
+
+
 def trs_quat(translate=(0, 0, 0), quat=(0, 0, 0, 1), scale=(1, 1, 1)) -> np.ndarray:
     """Matrix4x4.TRS(position, rotation, scale) as 16 floats in Unity memory order (column-major); quat = (x, y, z, w)."""
     x, y, z, w = (float(c) for c in quat)

@@ -108,6 +108,19 @@ class Context:
         self.check(self.lib.urt_debug_read_scene_blas(self._h, nodes.ctypes.data_as(C.c_void_p), tri.ctypes.data_as(C.c_void_p), root.ctypes.data_as(C.c_void_p)))
         return nodes, tri, root, info
 
+    def read_scene_qnodes(self):
+        """(frame[2, 4] f32, nodes[n, 8] u32, in_use) of the current device scene: the quantized triangle-BVH nodes of option "qnodes"
+        (include/urt.h urt_debug_read_scene_qnodes), read back from the GPU.  frame[0] = grid origin.xyz, quality; frame[1] = cell.xyz, 0.
+        n = 0 (and an empty frame) while the option is 0; in_use says whether the traversal reads them."""
+        n, use = C.c_int(), C.c_int()
+        self.check(self.lib.urt_debug_read_scene_qnodes(self._h, None, C.byref(n), C.byref(use)))
+        buf = np.zeros((2 + 2 * n.value, 4), dtype=np.float32)
+        if n.value:
+            n2 = C.c_int()
+            self.check(self.lib.urt_debug_read_scene_qnodes(self._h, buf.ctypes.data_as(C.c_void_p), C.byref(n2), C.byref(use)))
+            assert n2.value == n.value
+        return buf[:2].copy(), buf[2:].view(np.uint32).reshape(n.value, 8), bool(use.value)
+
     def ray_query(self, origins, directions, t_max=None, any_hit: bool = False):
         """Batched ray queries against the bound scene (include/urt.h urt_ray_query): what the frame kernels' Trace (RS:364-383)
         returns for each ray, bounded by t_max (exclusive; None = +inf; a scalar or one value per ray).
