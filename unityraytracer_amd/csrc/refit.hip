@@ -12,8 +12,12 @@
 //                  level below (interior children), written with the builder's pad of 2^-16 x largest |coordinate| (blas_builder.cpp).
 // Which nodes belong to which MeshObject, every node's parent and its depth are derived once per full scene preparation (k_parents,
 // k_node_mesh, k_depth) from the node array itself, so the refit works on trees of either builder (host SAH, GPU LBVH).
-// Pixels do not depend on the boxes (they only cull; the Moller-Trumbore test decides): tests/test_gpu_refit.py compares moved
-// scenes with a full rebuild and with the oracle bit for bit.
+// The box rule: a leaf child's box is the min / max of the RECONSTRUCTED vertices r0, r0 + e1, r0 + e2 of its records (what the triangle
+// test sees; not w1, w2), an interior child's box the unpadded union of the level below, and the pad (2^-16 x the largest finite
+// |coordinate| of the node's OWN MeshObject + 1e-30) is added only where a box is written into a node.  Nodes of MeshObjects that did not
+// move are not touched.  Pixels do not depend on the boxes only while they contain their triangles (they only cull; the Moller-Trumbore
+// test decides): tests/refit_ref.py restates this rule, tests/test_refit_ref.py checks its margins, tests/test_gpu_refit_edges.py compares
+// the refitted nodes with it bit for bit, and tests/test_gpu_refit.py compares moved scenes with a full rebuild and with the oracle.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
