@@ -51,8 +51,8 @@ enum {
 
 /* ---- library / context ------------------------------------------------------------------- */
 URT_API int urt_abi_version(void);                       /* bumps when this header changes incompatibly (still 4: the ray queries,
-                                                            the feature buffers and the denoiser were added without changing anything
-                                                            that existed) */
+                                                            the feature buffers, the denoiser and the temporal reprojection were added
+                                                            without changing anything that existed) */
 URT_API int urt_device_count(int* out_count);
 /* One context per process and GPU (the one-process-per-GPU model).  device = HIP ordinal. */
 URT_API int urt_context_create(int device, urt_context** out_ctx);
@@ -258,6 +258,77 @@ typedef struct urt_DenoiseParams {   /* 16 bytes */
 #define URT_DENOISE_DEFAULT_SIGMA_DEPTH 0.1f
 URT_API int urt_denoise(urt_context* ctx, urt_handle src, urt_handle dst, urt_handle hit, urt_handle normal, urt_handle albedo,
                         const urt_DenoiseParams* params);
+
+/* ---- temporal reprojection ---------------------------------------------------------------- */
+/* Keeps the accumulated image across a camera move (the "temporal" stage of SVGF-style pipelines): urt_reproject carries the history
+ * accumulated under the previous camera into the current view, using the pixel-centre feature buffers of urt_render_aov under both
+ * cameras, and urt_blit_add_history blends new frames in with a per-pixel sample count instead of the single _Sample of urt_blit_add.
+ * A COUNT TEXTURE is an RGBA32F texture whose .x holds the per-pixel sample count (a float, may be fractional); .yzw are written as 0
+ * and are reserved.  All images of one call are existing RGBA32F textures (own or external) of one size W x H, row 0 at the bottom.
+ *
+ * Arithmetic (normative): float32 with one rounding per operation, no fma, evaluated left to right as written; division is IEEE.
+ * bits(f) = the int32 pattern of f.  Per pixel p = (x, y): k = normal.w, z = hit.w, P = hit.xyz, n = normal.xyz, o = bits(id.x);
+ * M = prev_world_to_clip, C = _CameraToWorld, I = _CameraInverseProjection (the current uniforms).
+ *  1. class of p: surface when k != 0, z finite and > 0, P and n finite; sky when k == 0; anything else has no history.
+ *  2. projection into the previous view:
+ *       surface: c_r = ((M[r]*P.x + M[4+r]*P.y) + M[8+r]*P.z) + M[12+r], r = 0 (cx), 1 (cy), 3 (cw);
+ *       sky: the current pixel-centre ray: u = ((float)x + 0.5f) / (float)W * 2.0f - 1.0f, v likewise from y and H;
+ *            e_r = (I[r]*u + I[4+r]*v) + I[12+r] (r = 0..2); d_r = (C[r]*e0 + C[4+r]*e1) + C[8+r]*e2;
+ *            c_r = (M[r]*d0 + M[4+r]*d1) + M[8+r]*d2 for r = 0, 1, 3 (the direction at infinity, w = 0);
+ *     then qx = ((cx / cw + 1.0f) * 0.5f) * (float)W - 0.5f, qy likewise from cy and H.  No history unless cw > 0 and
+ *     qx > -1 && qx < W && qy > -1 && qy < H (NaN fails every comparison).
+ *  3. bilinear taps: fx = qx - floorf(qx), gx = 1.0f - fx (fy, gy likewise), x0 = (int)floorf(qx), y0 = (int)floorf(qy); taps in this
+ *     order: (x0,y0) gx*gy, (x0+1,y0) fx*gy, (x0,y0+1) gx*fy, (x0+1,y0+1) fx*fy.  A tap q is valid when it is inside the image, its weight
+ *     is > 0, prev_count[q].x is finite and > 0 and all four components of prev_color[q] are finite, and in addition
+ *       sky p: prev_normal[q].w == 0;
+ *       surface p: prev_normal[q].w == k, bits(prev_id[q].x) == o, prev_hit[q].w finite and > 0,
+ *                  (n.x*m.x + n.y*m.y) + n.z*m.z >= normal_threshold with m = prev_normal[q].xyz, and
+ *                  fabsf((n.x*(Q.x-P.x) + n.y*(Q.y-P.y)) + n.z*(Q.z-P.z)) <= plane_threshold * z with Q = prev_hit[q].xyz.
+ *  4. sums over the valid taps in tap order from 0.0f: S = sum w, A = sum w*prev_color[q] (per component), N = sum w*prev_count[q].x.
+ *     History exists when S >= 0.01f: color = A / S per component, count = N / S, and count = fminf(count, max_history) when
+ *     max_history > 0.  Without history color = (0,0,0,0), count = 0.  The count texel is written as (count, 0, 0, 0).
+ *  5. motion (when wanted): (qx - (float)x, qy - (float)y, S, 0) when step 2's window test passed, else (0,0,0,0).
+ * urt_blit_add_history(src, dst, count, max_history): the AdditionShader blend of urt_blit_add with a per-pixel sample count.  n =
+ *     count.x; s = 0 when n is not finite or < 0, else s = max_history > 0 ? fminf(n, max_history - 1.0f) : n; then as urt_blit_add
+ *     a = 1.0f / (s + 1.0f), ia = 1.0f - a, dst.rgb = t.rgb*a + c.rgb*ia, dst.a = a*a + c.a*ia (t = src, c = dst); count = (s + 1, 0, 0, 0).
+ *     With a uniform count n and max_history == 0 it is bit for bit urt_blit_add(src, dst, n).
+ * Calls:
+ *  - urt_reproject is an observer like urt_denoise: it submits the deferred frames first (prev_color is usually a deferred blend's
+ *    destination), then enqueues one kernel on the context's stream and returns without synchronising.  The scene is not read (not
+ *    prepared); urt_counters are not changed.  motion = 0: not written.
+ *  - urt_blit_add_history is deferred like urt_blit_add when src is the pending batch's Result texture; runs of such blends of consecutive
+ *    frames into one dst / count / max_history, and a present (urt_blit) of dst after them, are fused into one pass with the same per-pixel
+ *    operations.  Every call that observes dst or count submits them first.
+ *  - URT_ERR_INVALID_ARGUMENT: NULL images or params; nonzero flags; a NaN threshold; max_history NaN, negative or in (0, 1); sizes that
+ *    differ; an output equal to an input or to another output; an output bound as _SkyboxTexture; for the blend: count equal to src or
+ *    dst, or src == dst.  URT_ERR_INVALID_HANDLE: a required handle 0 or unknown (motion may be 0).  URT_ERR_UNBOUND (urt_reproject):
+ *    _CameraToWorld or _CameraInverseProjection never set.  Every argument is checked first: on any error nothing is written and nothing
+ *    is enqueued.
+ * Moving objects have no motion vectors: a MeshObject moved by a refit keeps its history only where the id, normal and plane tests still
+ * accept it.  The defaults below were chosen with the quality test of tests/test_gpu_reproject.py (DESIGN.md "Temporal reprojection"). */
+typedef struct urt_ReprojectParams {     /* 80 bytes */
+  float prev_world_to_clip[16];  /* the PREVIOUS camera's projection * worldToCamera, Unity Matrix4x4 memory order (column-major), the
+                                    order urt_shader_set_matrix takes.  A Unity host: _camera.projectionMatrix *
+                                    _camera.worldToCameraMatrix, kept from the frame before the move (RM:774 uses projectionMatrix). */
+  float max_history;             /* 0 = unlimited, else >= 1: reprojected counts are clamped to it */
+  float normal_threshold;        /* a history tap needs dot(n_p, n_q) >= this */
+  float plane_threshold;         /* a history tap needs |dot(n_p, Q - P)| <= this * z_p */
+  int32_t flags;                 /* 0 (reserved) */
+} urt_ReprojectParams;
+#define URT_REPROJECT_DEFAULT_MAX_HISTORY 64.0f
+#define URT_REPROJECT_DEFAULT_NORMAL_THRESHOLD 0.9f
+#define URT_REPROJECT_DEFAULT_PLANE_THRESHOLD 0.02f
+
+typedef struct urt_ReprojectImages {     /* 11 handles, 88 bytes */
+  urt_handle prev_color, prev_count;               /* the history as accumulated under the previous camera */
+  urt_handle prev_hit, prev_normal, prev_id;       /* urt_render_aov(URT_AOV_PIXEL_CENTER) under the previous camera */
+  urt_handle hit, normal, id;                      /* urt_render_aov(URT_AOV_PIXEL_CENTER) under the current camera */
+  urt_handle color, count;                         /* out: the reprojected history */
+  urt_handle motion;                               /* out, optional (0 = not wanted) */
+} urt_ReprojectImages;
+
+URT_API int urt_reproject(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params);
+URT_API int urt_blit_add_history(urt_context* ctx, urt_handle src, urt_handle dst, urt_handle count, float max_history);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 typedef struct urt_counters {

@@ -91,6 +91,28 @@ internal static class UrtNative {
     }
     [DllImport(Lib)] internal static extern int urt_denoise(IntPtr ctx, ulong src, ulong dst, ulong hit, ulong normal, ulong albedo, in DenoiseParams p);
 
+    // ---- temporal reprojection (include/urt.h "temporal reprojection"): count textures hold the per-pixel sample count in .x ----
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct ReprojectParams {                       // urt_ReprojectParams, 80 B
+        [MarshalAs(UnmanagedType.ByValArray, SizeConst = 16)]
+        public float[] prevWorldToClip;                     // the previous camera's projectionMatrix * worldToCameraMatrix, column-major
+        public float maxHistory;                            // 0 = unlimited, else >= 1
+        public float normalThreshold;
+        public float planeThreshold;
+        public int flags;                                   // 0
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct ReprojectImages {                       // urt_ReprojectImages, 88 B: texture handles, motion 0 = not wanted
+        public ulong prevColor, prevCount;
+        public ulong prevHit, prevNormal, prevId;
+        public ulong hit, normal, id;
+        public ulong color, count;
+        public ulong motion;
+    }
+    internal const float ReprojectDefaultMaxHistory = 64.0f, ReprojectDefaultNormalThreshold = 0.9f, ReprojectDefaultPlaneThreshold = 0.02f;
+    [DllImport(Lib)] internal static extern int urt_reproject(IntPtr ctx, in ReprojectImages images, in ReprojectParams p);
+    [DllImport(Lib)] internal static extern int urt_blit_add_history(IntPtr ctx, ulong src, ulong dst, ulong count, float maxHistory);
+
     // ---- measurement ----------------------------------------------------------------------------------------------------
     [StructLayout(LayoutKind.Sequential)]
     internal struct Counters {

@@ -108,6 +108,53 @@ public static class UrtDenoiser {
     }
 }
 
+/// Temporal accumulation (include/urt.h urt_reproject / urt_blit_add_history) over device images the engine owns, all ARGBFloat of one
+/// size.  Per camera move: keep the previous camera's `prevViewProj` (_camera.projectionMatrix * _camera.worldToCameraMatrix) and its
+/// pixel-centre feature buffers (UrtFeatureBuffers.Render into a second set), render the new camera's, then Reproject the accumulated
+/// image and its count texture into a spare pair and swap.  Per frame: BlitAddHistory(_target, _converged, count) in place of the
+/// AdditionShader blit.  A count texture starts as zeros (write them; creation is not assumed to zero).  Defaults: include/urt.h
+/// URT_REPROJECT_DEFAULT_*.
+public static class UrtTemporal {
+    static IntPtr boundCtx = IntPtr.Zero;
+    static readonly Dictionary<IntPtr, ulong> wrapped = new Dictionary<IntPtr, ulong>();
+    static int w, h;
+    static ulong Wrap(IntPtr ctx, IntPtr p, int width, int height) {  // external textures, re-wrapped when the context or the size changes
+        if (p == IntPtr.Zero) return 0;
+        if (boundCtx != ctx || w != width || h != height) {
+            if (boundCtx == ctx) foreach (ulong t in wrapped.Values) UrtDevice.Check(UrtNative.urt_texture_release(ctx, t));
+            wrapped.Clear();
+            boundCtx = ctx; w = width; h = height;
+        }
+        if (!wrapped.TryGetValue(p, out ulong handle)) {
+            UrtDevice.Check(UrtNative.urt_texture_create_external(ctx, width, height, p, out handle));
+            wrapped[p] = handle;
+        }
+        return handle;
+    }
+    public static void Reproject(IntPtr prevColor, IntPtr prevCount, IntPtr prevHit, IntPtr prevNormal, IntPtr prevId,
+                                 IntPtr hit, IntPtr normal, IntPtr id, IntPtr color, IntPtr count, IntPtr motion, int width, int height,
+                                 Matrix4x4 prevViewProj, float maxHistory = 64.0f, float normalThreshold = 0.9f, float planeThreshold = 0.02f) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtTemporal: reproject on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        var m = new float[16];
+        for (int k = 0; k < 16; k++) m[k] = prevViewProj[k];          // Matrix4x4's indexer is column-major: the order of the ABI
+        var im = new UrtNative.ReprojectImages {
+            prevColor = Wrap(ctx, prevColor, width, height), prevCount = Wrap(ctx, prevCount, width, height),
+            prevHit = Wrap(ctx, prevHit, width, height), prevNormal = Wrap(ctx, prevNormal, width, height), prevId = Wrap(ctx, prevId, width, height),
+            hit = Wrap(ctx, hit, width, height), normal = Wrap(ctx, normal, width, height), id = Wrap(ctx, id, width, height),
+            color = Wrap(ctx, color, width, height), count = Wrap(ctx, count, width, height), motion = Wrap(ctx, motion, width, height) };
+        var p = new UrtNative.ReprojectParams { prevWorldToClip = m, maxHistory = maxHistory, normalThreshold = normalThreshold,
+                                                planeThreshold = planeThreshold, flags = 0 };
+        UrtDevice.Check(UrtNative.urt_reproject(ctx, in im, in p));
+    }
+    public static void BlitAddHistory(IntPtr src, IntPtr dst, IntPtr count, int width, int height, float maxHistory = 64.0f) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtTemporal: blend on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        UrtDevice.Check(UrtNative.urt_blit_add_history(ctx, Wrap(ctx, src, width, height), Wrap(ctx, dst, width, height),
+                                                       Wrap(ctx, count, width, height), maxHistory));
+    }
+}
+
 /// new ComputeBuffer(count, stride); .SetData(List<T>); .Release(); .count; .stride            (RM:233-252)
 public sealed class UrtComputeBuffer {
     internal ulong handle;

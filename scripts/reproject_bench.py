@@ -1,0 +1,150 @@
+"""Time of the temporal reprojection (include/urt.h urt_reproject) and of the history blend (urt_blit_add_history) at 1920x1080 and
+3840x2160, on the analytic feature buffers of tests/reproject_ref.py (a small camera move: most pixels keep their history).
+
+Cases, each timed with device events on a torch stream the context is set to issue on, `--iters` calls after `--warmup`, in `--repeats`
+repeats (median and spread reported):
+  reproject        one urt_reproject call with a motion image;
+  blend            one urt_blit_add_history call that is not deferred (its source is not a pending frame);
+  fused20_present  20 frames of C1 (16 spheres, 1 bounce), each dispatched, blended with urt_blit_add_history and presented, submitted
+                   as one batch (frames_per_launch 20): the per-launch time minus that of the same 20 dispatches without the blends and
+                   presents, i.e. the one fused pass, per launch.
+Bytes per pixel are the compulsory traffic (reproject: 48 B of current AOVs, 80 B of previous history and AOVs, 48 B out; blend: 64 B;
+fused n frames with a present: 16 n + 64 B) and `of_6p3TBs` the fraction of the ~6.3 TB/s a float4 copy reaches on the chip.  Kernel times
+come from a separate `rocprofv3 --kernel-trace --stats` run of this script.
+
+    python scripts/reproject_bench.py [--sizes 1080p,2160p] [--iters 20] [--repeats 5] [--json out.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import torch  # noqa: E402  (before the library: one HIP runtime in the process, tests/conftest.py)
+
+from unityraytracer_amd import Context, RayTraceMaster, scenes  # noqa: E402
+from unityraytracer_amd.unity_api import ComputeShader, RenderTexture  # noqa: E402
+
+SIZES = {"1080p": (1920, 1080), "2160p": (3840, 2160)}
+PEAK = 6.3e12
+
+
+def timed(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def report(name, case, w, h, ms, bpp, results):
+    med = float(np.median(ms))
+    r = {"size": name, "case": case, "width": w, "height": h, "ms": ms, "ms_median": med,
+         "spread_pct": float((max(ms) - min(ms)) / med * 100) if med > 0 else 0.0, "bytes_per_pixel": bpp,
+         "of_6p3TBs": float(w * h * bpp / (med * 1e-3) / PEAK) if med > 0 else 0.0}
+    print(json.dumps(r), flush=True)
+    results.append(r)
+
+
+def main():
+    from reproject_ref import analytic_aovs
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="1080p,2160p")
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    results = []
+    ctx = Context(0)
+    stream = torch.cuda.Stream(dev)                             # a real stream (torch's default one is handle 0 = "the library's own")
+    torch.cuda.set_stream(stream)
+    ctx.set_stream(stream.cuda_stream)                          # the calls go where the events are recorded
+    rng = np.random.default_rng(1)
+    for name in args.sizes.split(","):
+        w, h = SIZES[name]
+        cam_a = scenes.camera_matrices(w, h)
+        cam_b = scenes.camera_matrices(w, h, position=(0.1, 1.0, -10.0), yaw_deg=1.0)
+        prev, cur = analytic_aovs(w, h, *cam_a), analytic_aovs(w, h, *cam_b)
+        color = rng.uniform(0, 1, (h, w, 4)).astype(np.float32)
+        count = np.zeros((h, w, 4), np.float32)
+        count[..., 0] = 16.0
+        tex = [RenderTexture(ctx, w, h) for _ in range(11)]
+        for t, a in zip(tex, [color, count] + list(prev) + list(cur)):
+            t.SetPixels(a)
+        sh = ComputeShader(ctx)
+        sh.SetMatrix("_CameraToWorld", cam_b[0])
+        sh.SetMatrix("_CameraInverseProjection", cam_b[1])
+        M = scenes.world_to_clip(*cam_a)
+        fn = lambda: ctx.reproject(*tex[:10], M, motion=tex[10])  # noqa: E731
+        report(name, "reproject", w, h, [timed(fn, args.iters, args.warmup) for _ in range(args.repeats)], 176, results)
+        fn = lambda: ctx.blit_add_history(tex[0], tex[8], tex[9], 64.0)  # noqa: E731
+        report(name, "blend", w, h, [timed(fn, args.iters, args.warmup) for _ in range(args.repeats)], 64, results)
+        for t in tex:
+            t.Release()
+
+        # 20 deferred frames per launch, with and without the blends and presents
+        ctx.set_stream(None)                                    # batching needs the library's own stream
+        ctx.set_option("frames_per_launch", 20)
+        sc = scenes.config1(w, h)
+        m = RayTraceMaster(ctx, sc)
+        m.EnableTemporalAccumulation()
+        present = RenderTexture(ctx, w, h)
+        m.OnRenderImage(present)
+        ctx.synchronize()
+
+        def batch(blend):
+            def run():
+                for _ in range(20):
+                    if blend:
+                        m.OnRenderImage(present)
+                    else:
+                        m.SetShaderParameters()
+                        m.RayTraceShader.SetTexture(0, "Result", m._target)
+                        m.RayTraceShader.Dispatch(0, (w + 7) // 8, (h + 7) // 8, 1)
+                        m._frame += 1
+                ctx.flush()
+            return run
+
+        def host_timed(fn):
+            import time
+            fn()
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.iters // 4 or 1):
+                fn()
+            ctx.synchronize()
+            return (time.perf_counter() - t0) * 1e3 / (args.iters // 4 or 1)
+
+        with_b = [host_timed(batch(True)) for _ in range(args.repeats)]
+        without = [host_timed(batch(False)) for _ in range(args.repeats)]
+        diff = [a - b for a, b in zip(sorted(with_b), sorted(without))]
+        r = {"size": name, "case": "fused20_batch", "ms_with_blends": with_b, "ms_without": without,
+             "ms_with_median": float(np.median(with_b)), "ms_without_median": float(np.median(without))}
+        print(json.dumps(r), flush=True)
+        results.append(r)
+        report(name, "fused20_present", w, h, diff, 16 * 20 + 64, results)
+        present.Release()
+        m.OnDisable()
+        ctx.set_option("frames_per_launch", 0)
+        ctx.set_stream(stream.cuda_stream)
+    ctx.set_stream(None)
+    ctx.close()
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(results, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -31,6 +31,7 @@
 #include "query.h"
 #include "aov.h"
 #include "denoise.h"
+#include "reproject.h"
 #include "urt_device.h"
 
 #include <chrono>
@@ -178,7 +179,8 @@ struct urt_context {
   int scene_max_depth = 0;
   int opt_frames_per_launch = 0;            // 0 = auto (own stream: 64 frames per launch, fewer when the Result slots would exceed 8 GiB; caller's stream: 1), 1 = off, 2..64
   uint64_t scene_epoch = 0;                 // bumps at every scene preparation
-  struct PostOp { int kind; int frame; urt_handle tex; urt_handle dst; float sample; int first_row, row_stride; void* dense; };   // kind 0 = blit_add(tex@frame -> dst), 1 = pack_rows(tex -> dense), 2 = blit(tex -> dst), the present of RM:819
+  struct PostOp { int kind; int frame; urt_handle tex; urt_handle dst; float sample; int first_row, row_stride; void* dense; urt_handle count; };   // kind 0 = blit_add(tex@frame -> dst), 1 = pack_rows(tex -> dense), 2 = blit(tex -> dst), the present of RM:819,
+                                                                                                                                  // 3 = blit_add_history(tex@frame -> dst, count; sample = max_history)
   struct Pending {
     int n = 0, limit = 1;
     urt_handle tex = 0;                     // the Result texture of the batch
@@ -1225,6 +1227,36 @@ int flush_pending(urt_context* ctx) {
                                          : launch_blit_add_multi(src, ctx->slab_stride, cnt, samples, d->dev, pdev, (size_t)d->w * d->h, ctx->stream);
       if (e != hipSuccess) return fail(ctx, URT_ERR_HIP, std::string("deferred Blit: ") + hipGetErrorString(e));
       i = j;
+    } else if (op.kind == 3) {
+      Texture* d = find_texture(ctx, op.dst);
+      Texture* c = find_texture(ctx, op.count);
+      if (!d || !c) return fail(ctx, URT_ERR_INVALID_HANDLE, "deferred blit_add_history: texture was released");
+      // The same fusion as kind 0: a run of blends of consecutive frames into one dst / count with one max_history, each possibly followed
+      // by the present of dst, in ONE pass that reads and writes the count once (same per-pixel operations, include/urt.h)
+      size_t j = i, j_present = i;
+      int cnt = 0, cnt_present = 0;
+      urt_handle present = 0;
+      while (j < ops.size() && cnt <= kMaxFramesPerLaunch) {
+        const urt_context::PostOp& q = ops[j];
+        if (q.kind == 3 && q.dst == op.dst && q.count == op.count && q.sample == op.sample && q.frame == op.frame + cnt &&
+            cnt < kMaxFramesPerLaunch) { cnt++; j++; }
+        else if (q.kind == 2 && q.tex == op.dst && q.dst != op.dst && q.dst != op.count && q.dst != B.tex && (present == 0 || q.dst == present)) {
+          present = q.dst; j++; j_present = j; cnt_present = cnt;
+        } else break;
+      }
+      if (present) { j = j_present; cnt = cnt_present; }
+      float4* pdev = nullptr;
+      if (present) {
+        Texture* pt = find_texture(ctx, present);
+        if (!pt) return fail(ctx, URT_ERR_INVALID_HANDLE, "deferred Blit: destination texture was released");
+        pdev = pt->dev;
+      }
+      const float4* src = slots + (size_t)op.frame * ctx->slab_stride;
+      const size_t npix = (size_t)d->w * d->h;
+      hipError_t e = (cnt == 1 && !pdev) ? launch_blit_add_history(src, d->dev, c->dev, npix, op.sample, ctx->stream)
+                                         : launch_blit_add_history_multi(src, ctx->slab_stride, cnt, d->dev, c->dev, pdev, npix, op.sample, ctx->stream);
+      if (e != hipSuccess) return fail(ctx, URT_ERR_HIP, std::string("deferred blit_add_history: ") + hipGetErrorString(e));
+      i = j;
     } else if (op.kind == 2) {
       Texture* t = find_texture(ctx, op.tex);
       Texture* d = find_texture(ctx, op.dst);
@@ -1882,6 +1914,39 @@ int urt_blit_add(urt_context* ctx, urt_handle src, urt_handle dst, float sample)
   URT_GUARD_END(ctx)
 }
 
+// max_history of urt_reproject / urt_blit_add_history: 0 (unlimited) or >= 1
+static bool valid_max_history(float v) { return !std::isnan(v) && (v == 0.0f || v >= 1.0f); }
+
+// AdditionShader blend with a per-pixel sample count (include/urt.h).  Deferred like urt_blit_add when src is the pending batch's Result
+// texture (flush_pending fuses runs of them); otherwise the deferred frames are submitted and the blend is enqueued.
+int urt_blit_add_history(urt_context* ctx, urt_handle src, urt_handle dst, urt_handle count, float max_history) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  Texture* s = find_texture(ctx, src);
+  Texture* d = find_texture(ctx, dst);
+  Texture* c = find_texture(ctx, count);
+  if (!s || !d || !c) return fail(ctx, URT_ERR_INVALID_HANDLE, "blit_add_history: unknown texture handle");
+  if (s->w != d->w || s->h != d->h || c->w != d->w || c->h != d->h)
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "blit_add_history: the textures differ in size");
+  if (src == dst || count == src || count == dst) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "blit_add_history: src, dst and count must differ");
+  if (dst == ctx->t_sky || count == ctx->t_sky)
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "blit_add_history: dst or count is the texture bound as _SkyboxTexture");
+  if (!valid_max_history(max_history)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "blit_add_history: max_history must be 0 or >= 1");
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  URT_GUARD_BEGIN
+  d->other_writes = true;
+  c->other_writes = true;
+  urt_context::Pending& B = ctx->pend;
+  if (B.n > 0 && src == B.tex && (const float4*)d->dev != B.S.sky && (const float4*)c->dev != B.S.sky) {
+    urt_context::PostOp op{3, B.n - 1, src, dst, max_history, 0, 1, nullptr, count};
+    B.ops.push_back(op);
+    return URT_OK;
+  }
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  URT_HIP(ctx, launch_blit_add_history(s->dev, d->dev, c->dev, (size_t)s->w * s->h, max_history, touch(ctx)));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
 int urt_blit(urt_context* ctx, urt_handle src, urt_handle dst) {
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   Texture* s = find_texture(ctx, src);
@@ -1946,7 +2011,7 @@ static int unpack_on_impl(urt_context* ctx, urt_handle texture, int first_group_
   if (first_group_row < 0 || row_stride < 1) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "bad strip arguments");
   if (ctx->pend.n > 0) {                                  // never the case for a dedicated gather target
     bool touched = ctx->pend.tex == texture;
-    for (const urt_context::PostOp& q : ctx->pend.ops) touched = touched || q.tex == texture || q.dst == texture;
+    for (const urt_context::PostOp& q : ctx->pend.ops) touched = touched || q.tex == texture || q.dst == texture || q.count == texture;
     if (touched) { int rc = flush_pending(ctx); if (rc) return rc; }
   }
   if (in_slab(ctx, *t)) { int rc = detach_from_slab(ctx, *t); if (rc) return rc; }
@@ -2136,6 +2201,61 @@ int urt_denoise(urt_context* ctx, urt_handle src, urt_handle dst, urt_handle hit
   DenoiseSettings S{P.iterations, P.sigma_color, P.sigma_normal, P.sigma_depth};
   t[1]->other_writes = true;
   URT_HIP(ctx, launch_denoise(I, S, touch(ctx)));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+/* ---- temporal reprojection ---- */
+// Every argument is checked before anything is submitted: on an error nothing is enqueued.  Then the deferred frames are submitted
+// (prev_color is usually a deferred blend's destination) and k_reproject is enqueued on the main stream.  The scene is not read and the
+// counters are not changed.
+int urt_reproject(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (!images || !params) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: images or params is NULL");
+  URT_GUARD_BEGIN
+  const urt_ReprojectParams P = *params;
+  if (P.flags != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: flags must be 0");
+  if (std::isnan(P.normal_threshold) || std::isnan(P.plane_threshold)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: a threshold is NaN");
+  if (!valid_max_history(P.max_history)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: max_history must be 0 or >= 1");
+  enum { kInputs = 8, kImages = 11 };
+  const urt_handle h[kImages] = {images->prev_color, images->prev_count, images->prev_hit, images->prev_normal, images->prev_id,
+                                 images->hit, images->normal, images->id, images->color, images->count, images->motion};
+  const char* const names[kImages] = {"prev_color", "prev_count", "prev_hit", "prev_normal", "prev_id", "hit", "normal", "id", "color",
+                                      "count", "motion"};
+  Texture* t[kImages] = {};
+  for (int k = 0; k < kImages; k++) {
+    if (k == kImages - 1 && !h[k]) continue;                       // no motion image wanted
+    t[k] = find_texture(ctx, h[k]);
+    if (!t[k]) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string("reproject: unknown ") + names[k] + " texture handle");
+  }
+  const int width = t[0]->w, height = t[0]->h;
+  for (int k = 1; k < kImages; k++)
+    if (t[k] && (t[k]->w != width || t[k]->h != height)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: the textures differ in size");
+  for (int k = kInputs; k < kImages; k++) {
+    if (!h[k]) continue;
+    for (int j = 0; j < kImages; j++)
+      if (j != k && h[j] == h[k])
+        return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("reproject: the output ") + names[k] + " is also " + names[j]);
+    if (h[k] == ctx->t_sky)
+      return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("reproject: the output ") + names[k] + " is the texture bound as _SkyboxTexture");
+  }
+  if ((height + 15) / 16 > 65535) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: textures taller than 1048560 pixels");
+  if (!ctx->c2w_set || !ctx->invp_set)
+    return fail(ctx, URT_ERR_UNBOUND, "reproject: _CameraToWorld / _CameraInverseProjection never set (SetMatrix, RM:774-775)");
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  ReprojectImages I{};                                             // device pointers after the flush (a Result texture may be renamed)
+  I.prev_color = t[0]->dev; I.prev_count = t[1]->dev; I.prev_hit = t[2]->dev; I.prev_normal = t[3]->dev; I.prev_id = t[4]->dev;
+  I.hit = t[5]->dev; I.normal = t[6]->dev; I.id = t[7]->dev;
+  I.color = t[8]->dev; I.count = t[9]->dev; I.motion = t[10] ? t[10]->dev : nullptr;
+  I.width = width; I.height = height;
+  ReprojectSettings S{};
+  std::memcpy(S.m, P.prev_world_to_clip, sizeof S.m);
+  std::memcpy(S.c2w, ctx->c2w, sizeof S.c2w);
+  std::memcpy(S.invp, ctx->invp, sizeof S.invp);
+  S.max_history = P.max_history; S.normal_threshold = P.normal_threshold; S.plane_threshold = P.plane_threshold;
+  for (int k = kInputs; k < kImages; k++) if (t[k]) t[k]->other_writes = true;
+  URT_HIP(ctx, launch_reproject(I, S, touch(ctx)));
   return URT_OK;
   URT_GUARD_END(ctx)
 }

@@ -1,0 +1,44 @@
+// reproject.h — host-callable launchers of the temporal reprojection (reproject.hip): urt_reproject and urt_blit_add_history
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+namespace urtd {
+
+// The images of one urt_reproject call: RGBA32F, width x height, row 0 = bottom (the urt_render_aov layouts; a count texel holds the
+// per-pixel sample count in .x).
+struct ReprojectImages {
+  const float4* prev_color;     // the history under the previous camera
+  const float4* prev_count;
+  const float4* prev_hit;       // urt_render_aov(URT_AOV_PIXEL_CENTER) under the previous camera: position.xyz, distance
+  const float4* prev_normal;    // normal.xyz, kind
+  const float4* prev_id;        // object (int bits), ...
+  const float4* hit;            // the same under the current camera
+  const float4* normal;
+  const float4* id;
+  float4* color;                // out: the reprojected history
+  float4* count;                // out: (count, 0, 0, 0)
+  float4* motion;               // out or null: (qx - x, qy - y, S, 0)
+  int width, height;
+};
+
+// The matrices and thresholds (include/urt.h urt_ReprojectParams plus the current camera uniforms), already checked.
+struct ReprojectSettings {
+  float m[16];                  // prev_world_to_clip, column-major
+  float c2w[16];                // _CameraToWorld
+  float invp[16];               // _CameraInverseProjection
+  float max_history, normal_threshold, plane_threshold;
+};
+
+// Enqueues k_reproject on `st`.  hipErrorInvalidValue when the grid is too tall.
+hipError_t launch_reproject(const ReprojectImages& I, const ReprojectSettings& P, hipStream_t st);
+
+// One AdditionShader blend with the per-pixel sample count of `count` (urt_blit_add_history), in place on dst and count.
+hipError_t launch_blit_add_history(const float4* src, float4* dst, float4* count, size_t n_pixels, float max_history, hipStream_t st);
+
+// n consecutive such blends of the frames src + f * frame_stride (f = 0 .. n-1) in one pass, with the same per-pixel operations in the
+// same order as n launch_blit_add_history calls; `present` (or null) also receives the final dst value (the present of RM:819).
+hipError_t launch_blit_add_history_multi(const float4* src, size_t frame_stride, int n, float4* dst, float4* count, float4* present,
+                                         size_t n_pixels, float max_history, hipStream_t st);
+
+}  // namespace urtd

@@ -1,0 +1,190 @@
+// reproject.hip — temporal reprojection of an accumulated image across a camera move (urt_reproject) and the AdditionShader blend with a
+// per-pixel sample count (urt_blit_add_history).  include/urt.h states the arithmetic; the library is built with -ffp-contract=off, so
+// every expression below is evaluated with one rounding per operation, as written there.
+//
+// k_reproject: one pixel per lane, wave64.  A wave covers one 8 x 8 pixel tile and a 256-thread workgroup a 16 x 16 block, as k_aov /
+// k_denoise_*.  A pixel loads its three current feature texels, projects its hit point (or, for a sky pixel, its pixel-centre direction)
+// into the previous view and gathers the 2 x 2 bilinear footprint around it from the previous history and feature buffers: for small
+// motions the taps of a wave are the wave's own 8 x 8 block shifted, so they coalesce as the current loads do.  No LDS.
+// k_blit_add_history / k_blit_add_history_multi: grid-stride over the pixels as k_blit_add / k_blit_add_multi; the fused form reads the
+// count and dst once, blends n frames and writes both (and the present) once: 16 n + 64 bytes per pixel with a present.
+#include <hip/hip_runtime.h>
+
+#include "reproject.h"
+
+namespace {
+
+struct Params {
+  urtd::ReprojectImages I;
+  urtd::ReprojectSettings P;
+};
+
+__device__ __forceinline__ bool finite3(float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
+__device__ __forceinline__ bool finite4(float4 v) { return finite3(v) && isfinite(v.w); }
+
+__global__ __launch_bounds__(256) void k_reproject(const Params A) {
+  const urtd::ReprojectImages& I = A.I;
+  const urtd::ReprojectSettings& P = A.P;
+  const int W = I.width, H = I.height;
+  // workgroup = 16 x 16 pixels, wave = the 8 x 8 tile (wave & 1, wave >> 1) of it, lane = (lane & 7, lane >> 3) of the tile
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int x = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+  const int y = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+  if (x >= W || y >= H) return;                                  // partial tiles at the right and top edges
+  const size_t pix = (size_t)y * (size_t)W + (size_t)x;
+
+  const float4 h = I.hit[pix], nr = I.normal[pix];
+  const float k = nr.w, z = h.w;
+  const bool sky = k == 0.0f;
+  const bool surface = !sky && isfinite(z) && z > 0.0f && finite3(h) && finite3(nr);
+  const float* M = P.m;
+
+  // 2. the point (w = 1) or the direction (w = 0) in the previous camera's clip space
+  float cx = 0.0f, cy = 0.0f, cw = 0.0f;
+  if (surface) {
+    cx = ((M[0] * h.x + M[4] * h.y) + M[8] * h.z) + M[12];
+    cy = ((M[1] * h.x + M[5] * h.y) + M[9] * h.z) + M[13];
+    cw = ((M[3] * h.x + M[7] * h.y) + M[11] * h.z) + M[15];
+  } else if (sky) {
+    const float* C = P.c2w;
+    const float* Iv = P.invp;
+    const float u = ((float)x + 0.5f) / (float)W * 2.0f - 1.0f;
+    const float v = ((float)y + 0.5f) / (float)H * 2.0f - 1.0f;
+    const float e0 = (Iv[0] * u + Iv[4] * v) + Iv[12];
+    const float e1 = (Iv[1] * u + Iv[5] * v) + Iv[13];
+    const float e2 = (Iv[2] * u + Iv[6] * v) + Iv[14];
+    const float d0 = (C[0] * e0 + C[4] * e1) + C[8] * e2;
+    const float d1 = (C[1] * e0 + C[5] * e1) + C[9] * e2;
+    const float d2 = (C[2] * e0 + C[6] * e1) + C[10] * e2;
+    cx = (M[0] * d0 + M[4] * d1) + M[8] * d2;
+    cy = (M[1] * d0 + M[5] * d1) + M[9] * d2;
+    cw = (M[3] * d0 + M[7] * d1) + M[11] * d2;
+  }
+  const float qx = ((cx / cw + 1.0f) * 0.5f) * (float)W - 0.5f;
+  const float qy = ((cy / cw + 1.0f) * 0.5f) * (float)H - 0.5f;
+  const bool window = (surface || sky) && cw > 0.0f && qx > -1.0f && qx < (float)W && qy > -1.0f && qy < (float)H;
+
+  float S = 0.0f, N = 0.0f;
+  float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (window) {
+    // 3. the bilinear footprint
+    const float flx = floorf(qx), fly = floorf(qy);
+    const float fx = qx - flx, gx = 1.0f - fx, fy = qy - fly, gy = 1.0f - fy;
+    const int x0 = (int)flx, y0 = (int)fly;
+    const float wt[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
+    const int o = __float_as_int(I.id[pix].x);
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      const int tx = x0 + (t & 1), ty = y0 + (t >> 1);
+      const float w = wt[t];
+      if (!(tx >= 0 && tx < W && ty >= 0 && ty < H && w > 0.0f)) continue;
+      const size_t q = (size_t)ty * (size_t)W + (size_t)tx;
+      const float4 pc = I.prev_count[q], col = I.prev_color[q], m = I.prev_normal[q];
+      bool ok = isfinite(pc.x) && pc.x > 0.0f && finite4(col);
+      if (sky) {
+        ok = ok && m.w == 0.0f;
+      } else {
+        const float4 Q = I.prev_hit[q];
+        const int oq = __float_as_int(I.prev_id[q].x);
+        const float nd = (nr.x * m.x + nr.y * m.y) + nr.z * m.z;
+        const float pd = fabsf((nr.x * (Q.x - h.x) + nr.y * (Q.y - h.y)) + nr.z * (Q.z - h.z));
+        ok = ok && m.w == k && oq == o && isfinite(Q.w) && Q.w > 0.0f && nd >= P.normal_threshold && pd <= P.plane_threshold * z;
+      }
+      if (ok) {                                                  // 4. in tap order
+        S = S + w;
+        acc.x = acc.x + w * col.x;
+        acc.y = acc.y + w * col.y;
+        acc.z = acc.z + w * col.z;
+        acc.w = acc.w + w * col.w;
+        N = N + w * pc.x;
+      }
+    }
+  }
+  float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float n = 0.0f;
+  if (S >= 0.01f) {
+    c = make_float4(acc.x / S, acc.y / S, acc.z / S, acc.w / S);
+    n = N / S;
+    if (P.max_history > 0.0f) n = fminf(n, P.max_history);
+  }
+  I.color[pix] = c;
+  I.count[pix] = make_float4(n, 0.0f, 0.0f, 0.0f);
+  if (I.motion)
+    I.motion[pix] = window ? make_float4(qx - (float)x, qy - (float)y, S, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// the sample count a blend uses: s = 0 for a count that is not finite or negative, else the count, capped at max_history - 1
+__device__ __forceinline__ float history_samples(float n, float max_history) {
+  if (!isfinite(n) || n < 0.0f) return 0.0f;
+  return max_history > 0.0f ? fminf(n, max_history - 1.0f) : n;
+}
+
+// k_blit_add's operations with s in place of _Sample
+__device__ __forceinline__ float4 blend(float4 c, float4 t, float s) {
+  const float a = 1.0f / (s + 1.0f);
+  const float ia = 1.0f - a;
+  c.x = t.x * a + c.x * ia;
+  c.y = t.y * a + c.y * ia;
+  c.z = t.z * a + c.z * ia;
+  c.w = a * a + c.w * ia;
+  return c;
+}
+
+__global__ __launch_bounds__(256) void k_blit_add_history(const float4* __restrict__ src, float4* __restrict__ dst, float4* __restrict__ count,
+                                                          size_t npix, float max_history) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
+    const float s = history_samples(count[i].x, max_history);
+    dst[i] = blend(dst[i], src[i], s);
+    count[i] = make_float4(s + 1.0f, 0.0f, 0.0f, 0.0f);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_blit_add_history_multi(const float4* __restrict__ src, size_t frame_stride, int n,
+                                                                float4* __restrict__ dst, float4* __restrict__ count,
+                                                                float4* __restrict__ present, size_t npix, float max_history) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
+    float4 c = dst[i];
+    float cnt = count[i].x;
+    for (int f = 0; f < n; f++) {
+      const float s = history_samples(cnt, max_history);
+      c = blend(c, src[(size_t)f * frame_stride + i], s);
+      cnt = s + 1.0f;                                            // what the count texel of a separate call would hold
+    }
+    dst[i] = c;
+    count[i] = make_float4(cnt, 0.0f, 0.0f, 0.0f);
+    if (present) present[i] = c;
+  }
+}
+
+size_t grid_of(size_t n_pixels, size_t cap) {
+  const size_t nb = (n_pixels + 255) / 256;
+  return nb > cap ? cap : nb;
+}
+
+}  // namespace
+
+namespace urtd {
+
+hipError_t launch_reproject(const ReprojectImages& I, const ReprojectSettings& P, hipStream_t st) {
+  if (I.width <= 0 || I.height <= 0) return hipSuccess;
+  const dim3 grid((unsigned int)((I.width + 15) / 16), (unsigned int)((I.height + 15) / 16));
+  if (grid.y > 65535u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_reproject, grid, dim3(256), 0, st, Params{I, P});
+  return hipGetLastError();
+}
+
+hipError_t launch_blit_add_history(const float4* src, float4* dst, float4* count, size_t n_pixels, float max_history, hipStream_t st) {
+  if (n_pixels == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_blit_add_history, dim3((unsigned)grid_of(n_pixels, 2048)), dim3(256), 0, st, src, dst, count, n_pixels, max_history);
+  return hipGetLastError();
+}
+
+hipError_t launch_blit_add_history_multi(const float4* src, size_t frame_stride, int n, float4* dst, float4* count, float4* present,
+                                         size_t n_pixels, float max_history, hipStream_t st) {
+  if (n_pixels == 0 || n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_blit_add_history_multi, dim3((unsigned)grid_of(n_pixels, 4096)), dim3(256), 0, st, src, frame_stride, n, dst, count,
+                     present, n_pixels, max_history);
+  return hipGetLastError();
+}
+
+}  // namespace urtd

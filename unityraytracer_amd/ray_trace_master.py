@@ -23,7 +23,7 @@ import numpy as np
 from dataclasses import dataclass, field
 
 from . import host_scene, scenes
-from .unity_api import ComputeBuffer, ComputeShader, Context, Graphics, Material, RenderTexture, denoise_params
+from .unity_api import ComputeBuffer, ComputeShader, Context, Graphics, Material, RenderTexture, denoise_params, reproject_params
 
 
 @dataclass
@@ -70,6 +70,9 @@ class RayTraceMaster:
         self.screen_width, self.screen_height = scene.width, scene.height
         self._aov = None                             # RenderFeatureBuffers: (hit, normal, albedo, id) of the screen size
         self._denoised = None                        # Denoise without a destination: the denoised image
+        self._temporal = None                        # EnableTemporalAccumulation: the reprojection settings (None = off, the reference's behaviour)
+        self._tcount = self._tspare = None           # temporal: the count texture of _converged; the spare (colour, count) pair reprojection writes
+        self._taov = None                            # temporal: two (hit, normal, id) sets, the previous and the new camera's
 
     # RM:215-230
     def RegisterObject(self, obj: RayTraceObject):
@@ -198,6 +201,10 @@ class RayTraceMaster:
     # RM:798-821
     def Render(self, destination: RenderTexture | None = None):
         self.InitRenderTexture()
+        if self._temporal is not None:
+            self._ensure_temporal_textures()
+            if self._currentSample == 0:                                      # the accumulation restarted (rebuild, resize, reset): so do the counts
+                self._tcount.SetPixels(np.zeros((self.screen_height, self.screen_width, 4), np.float32))
         self.RayTraceShader.SetTexture(0, "Result", self._target)
         threadGroupsX = math.ceil(self.screen_width / 8.0)
         threadGroupsY = math.ceil(self.screen_height / 8.0)
@@ -205,10 +212,13 @@ class RayTraceMaster:
             self.RayTraceShader.Dispatch(0, threadGroupsX, threadGroupsY, 1)
         else:
             self.RayTraceShader.DispatchRows(0, threadGroupsX, threadGroupsY, 1, self.rank, self.world_size)
-        if self._additionMaterial is None:
-            self._additionMaterial = Material("Hidden/AdditionShader")
-        self._additionMaterial.SetFloat("_Sample", self._currentSample)
-        Graphics.Blit(self._target, self._converged, self._additionMaterial)
+        if self._temporal is not None:
+            self.ctx.blit_add_history(self._target, self._converged, self._tcount, self._temporal["max_history"])
+        else:
+            if self._additionMaterial is None:
+                self._additionMaterial = Material("Hidden/AdditionShader")
+            self._additionMaterial.SetFloat("_Sample", self._currentSample)
+            Graphics.Blit(self._target, self._converged, self._additionMaterial)
         if destination is not None:
             Graphics.Blit(self._converged, destination)
         self._currentSample += 1
@@ -291,6 +301,71 @@ class RayTraceMaster:
     def ResetAccumulation(self):
         self._currentSample = 0
 
+    # ---- temporal accumulation (no counterpart in the reference, which restarts the mean at every camera move, RM:765-767) ----
+    # Opt-in: once enabled, every frame blends with a per-pixel sample count (include/urt.h urt_blit_add_history) and MoveCamera carries
+    # the accumulated image into the new view (urt_reproject) instead of restarting it.  The settings are urt_ReprojectParams' (defaults:
+    # include/urt.h URT_REPROJECT_DEFAULT_*); max_history also caps the count the blend uses, so a still view keeps a running mean of its
+    # last max_history frames (0 = unlimited).
+    def EnableTemporalAccumulation(self, max_history: float = None, normal_threshold: float = None, plane_threshold: float = None):
+        from ._lib import REPROJECT_DEFAULTS
+        given = {"max_history": max_history, "normal_threshold": normal_threshold, "plane_threshold": plane_threshold}
+        settings = {k: (REPROJECT_DEFAULTS[k] if v is None else v) for k, v in given.items()}
+        p = reproject_params(np.eye(4, dtype=np.float32).reshape(16), **settings)   # checked before anything is created
+        self._temporal = {"max_history": p.max_history, "normal_threshold": p.normal_threshold, "plane_threshold": p.plane_threshold}
+        self._ensure_temporal_textures()
+        self._tcount.SetPixels(np.zeros((self.screen_height, self.screen_width, 4), np.float32))   # creation is not assumed to zero
+        self._currentSample = 0                                               # the count texture starts empty: so does the mean
+
+    def DisableTemporalAccumulation(self):
+        self._release_temporal()
+        self._temporal = None
+        self._currentSample = 0
+
+    def _release_temporal(self):
+        for t in (self._tcount,) + (self._tspare or ()) + sum(self._taov or (), ()):
+            if t is not None:
+                t.Release()
+        self._tcount = self._tspare = self._taov = None
+
+    def _ensure_temporal_textures(self):
+        w, h = self.screen_width, self.screen_height
+        if self._tcount is not None and (self._tcount.width, self._tcount.height) == (w, h):
+            return
+        self._release_temporal()
+        self._tcount = RenderTexture(self.ctx, w, h)
+        self._tspare = (RenderTexture(self.ctx, w, h), RenderTexture(self.ctx, w, h))
+        self._taov = tuple(tuple(RenderTexture(self.ctx, w, h) for _ in range(3)) for _ in range(2))
+        self._currentSample = 0                                               # a new count texture: the next frame zeroes it
+
+    # A camera move.  camera_to_world / camera_inverse_projection: 16 floats each in Unity Matrix4x4 memory order (the inverse projection
+    # stays when not given).  Temporal accumulation off: the new matrices and ResetAccumulation() (RM:765-767).  On: the pixel-centre
+    # feature buffers of the previous and the new camera are rendered, the accumulated image and its counts are reprojected into the new
+    # view, and the next frame blends into them.
+    def MoveCamera(self, camera_to_world, camera_inverse_projection=None):
+        s = self.scene
+        c2w = np.ascontiguousarray(camera_to_world, dtype=np.float32).reshape(16).copy()
+        invp = s.camera_inverse_projection if camera_inverse_projection is None else \
+            np.ascontiguousarray(camera_inverse_projection, dtype=np.float32).reshape(16).copy()
+        history = self._temporal is not None and self._converged is not None and self._currentSample > 0 and not self._treesNeedRebuilding \
+            and (self._converged.width, self._converged.height) == (self.screen_width, self.screen_height)
+        if not history:
+            s.camera_to_world, s.camera_inverse_projection = c2w, invp
+            self.ResetAccumulation()
+            return
+        self._ensure_temporal_textures()
+        prev_m = scenes.world_to_clip(s.camera_to_world, s.camera_inverse_projection)
+        prev, cur = self._taov
+        self.SetShaderParameters()
+        self.ctx.render_aov(prev[0], prev[1], None, prev[2])                   # the previous camera's buffers
+        s.camera_to_world, s.camera_inverse_projection = c2w, invp
+        self.SetShaderParameters()
+        self.ctx.render_aov(cur[0], cur[1], None, cur[2])                      # the new camera's
+        color, count = self._tspare
+        self.ctx.reproject(self._converged, self._tcount, prev[0], prev[1], prev[2], cur[0], cur[1], cur[2], color, count, prev_m,
+                           **self._temporal)
+        self._tspare = (self._converged, self._tcount)
+        self._converged, self._tcount = color, count
+
     # RM:761-763: F12 -> ScreenCapture.CaptureScreenshot("Screenshots/" + Time.time + "-" + _currentSample + ".png")
     def CaptureScreenshot(self, directory: str, time_seconds: float) -> str:
         import os
@@ -345,6 +420,7 @@ class RayTraceMaster:
                 t.Release()
         self._target = self._converged = self.SkyboxTexture = self._denoised = None
         self._aov = None
+        self._release_temporal()
 
     # ---- multi-GPU frame-end gather (no counterpart in the reference: it is single-GPU) -----------
     def gather_converged(self, dist, device):

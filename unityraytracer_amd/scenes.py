@@ -89,6 +89,15 @@ def camera_matrices(width: int, height: int, position=(0.0, 1.0, -10.0), fov_deg
     return (np.ascontiguousarray(c2w.T.astype(np.float32).reshape(16)), np.ascontiguousarray(invp.T.astype(np.float32).reshape(16)))
 
 
+def world_to_clip(camera_to_world16, camera_inverse_projection16) -> np.ndarray:
+    """projection * worldToCamera of a camera given by its (_CameraToWorld, _CameraInverseProjection): both inverted in float64, the
+    product rounded to float32, 16 floats in Unity Matrix4x4 memory order (column-major) — urt_ReprojectParams.prev_world_to_clip."""
+    c2w = np.asarray(camera_to_world16, dtype=np.float64).reshape(4, 4).T
+    invp = np.asarray(camera_inverse_projection16, dtype=np.float64).reshape(4, 4).T
+    m = np.linalg.inv(invp) @ np.linalg.inv(c2w)
+    return np.ascontiguousarray(m.T.astype(np.float32).reshape(16))
+
+
 # --- sky ----------------------------------------------------------------------------------------
 def make_sky(width: int = 2048, height: int = 1024) -> np.ndarray:
     """Analytic equirect RGBA32F sky (H, W, 4), row 0 = bottom (v = 0): zenith-horizon gradient plus a

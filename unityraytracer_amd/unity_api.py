@@ -270,6 +270,121 @@ class Context:
             for t in tex:
                 t.Release()
 
+    REPROJECT_INPUTS = ("prev_color", "prev_count", "prev_hit", "prev_normal", "prev_id", "hit", "normal", "id")
+
+    def reproject(self, prev_color, prev_count, prev_hit, prev_normal, prev_id, hit, normal, id, color, count, prev_world_to_clip,
+                  motion=None, max_history: float = _lib.REPROJECT_DEFAULTS["max_history"],
+                  normal_threshold: float = _lib.REPROJECT_DEFAULTS["normal_threshold"],
+                  plane_threshold: float = _lib.REPROJECT_DEFAULTS["plane_threshold"]):
+        """Temporal reprojection (include/urt.h urt_reproject): the history prev_color / prev_count accumulated under the previous camera,
+        whose world-to-clip matrix is prev_world_to_clip (16 floats, column-major: scenes.world_to_clip), carried into the current view
+        (the bound _CameraToWorld / _CameraInverseProjection) -> color / count, and the optional motion image.  prev_hit / prev_normal /
+        prev_id and hit / normal / id are render_aov's pixel-centre buffers under the previous and the current camera.  RenderTextures
+        of one size.  Enqueued after the deferred frames; a later GetPixels sees the result."""
+        images = dict(zip(self.REPROJECT_INPUTS, (prev_color, prev_count, prev_hit, prev_normal, prev_id, hit, normal, id)))
+        images.update(color=color, count=count, motion=motion)
+        for name, t in images.items():
+            if t is None and name == "motion":
+                continue
+            _check_texture(self, "reproject", name, t, prev_color, optional=name == "motion")
+        outs = [n for n in ("color", "count", "motion") if images[n] is not None]
+        for o in outs:
+            for name, t in images.items():
+                if name != o and t is images[o]:
+                    raise ValueError(f"reproject: the output {o} is also {name}")
+        p = reproject_params(prev_world_to_clip, max_history, normal_threshold, plane_threshold)
+        im = _lib.ReprojectImages(*(images[n].handle if images[n] is not None else 0 for n, _ in _lib.ReprojectImages._fields_))
+        self.check(self.lib.urt_reproject(self._h, C.byref(im), C.byref(p)))
+
+    def reproject_arrays(self, prev_color, prev_count, prev_hit, prev_normal, prev_id, hit, normal, id, prev_world_to_clip,
+                         camera_to_world, camera_inverse_projection, motion: bool = True, **params) -> dict:
+        """reproject on numpy images (h, w, 4) float32, row 0 = bottom, through temporary textures.  camera_to_world /
+        camera_inverse_projection (16 floats each) are bound as the context's current camera uniforms first (they stay bound).  Returns
+        {"color", "count"[, "motion"]} as (h, w, 4) arrays."""
+        imgs = [np.ascontiguousarray(a, dtype=np.float32) for a in (prev_color, prev_count, prev_hit, prev_normal, prev_id, hit, normal, id)]
+        shape = imgs[0].shape
+        if len(shape) != 3 or shape[2] != 4 or shape[0] <= 0 or shape[1] <= 0:
+            raise ValueError(f"reproject_arrays: prev_color must be (h, w, 4), not {shape}")
+        for a in imgs[1:]:
+            if a.shape != shape:
+                raise ValueError(f"reproject_arrays: the images differ in shape ({a.shape} vs {shape})")
+        reproject_params(prev_world_to_clip, **params)
+        c2w, invp = _matrix16(camera_to_world, "camera_to_world"), _matrix16(camera_inverse_projection, "camera_inverse_projection")
+        h, w = shape[:2]
+        tex = []
+        try:
+            for a in imgs + [None] * (3 if motion else 2):
+                tex.append(RenderTexture(self, w, h))
+                if a is not None:
+                    tex[-1].SetPixels(a)
+            self.check(self.lib.urt_shader_set_matrix(self._h, b"_CameraToWorld", c2w.ctypes.data_as(C.c_void_p)))
+            self.check(self.lib.urt_shader_set_matrix(self._h, b"_CameraInverseProjection", invp.ctypes.data_as(C.c_void_p)))
+            outs = tex[8:]
+            self.reproject(*tex[:8], outs[0], outs[1], prev_world_to_clip, motion=outs[2] if motion else None, **params)
+            res = {"color": outs[0].GetPixels(), "count": outs[1].GetPixels()}
+            if motion:
+                res["motion"] = outs[2].GetPixels()
+            return res
+        finally:
+            for t in tex:
+                t.Release()
+
+    def blit_add_history(self, src, dst, count, max_history: float = 0.0):
+        """The AdditionShader blend of src into dst with the per-pixel sample count of `count` (include/urt.h urt_blit_add_history);
+        count.x becomes the samples used plus one.  Deferred with a batched frame as Graphics.Blit with the AdditionShader is."""
+        for name, t in (("src", src), ("dst", dst), ("count", count)):
+            _check_texture(self, "blit_add_history", name, t, src)
+        if src is dst or count is src or count is dst:
+            raise ValueError("blit_add_history: src, dst and count must be three different textures")
+        _max_history_arg(max_history, "blit_add_history")
+        self.check(self.lib.urt_blit_add_history(self._h, src.handle, dst.handle, count.handle, float(max_history)))
+
+
+def _check_texture(ctx, what: str, name: str, t, like, optional: bool = False):
+    if not isinstance(t, RenderTexture):
+        raise TypeError(f"{what}: {name} must be a RenderTexture{' or None' if optional else ''}, not {type(t).__name__}")
+    if t.ctx is not ctx:
+        raise ValueError(f"{what}: {name} belongs to another context")
+    if not t.handle:
+        raise ValueError(f"{what}: {name} was released")
+    if (t.width, t.height) != (like.width, like.height):
+        raise ValueError(f"{what}: {name} is {t.width} x {t.height}, not {like.width} x {like.height}")
+
+
+def _number_arg(v, name: str, what: str) -> float:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{what}: {name} must be a number, not {type(v).__name__}")
+    if np.isnan(v):
+        raise ValueError(f"{what}: {name} is NaN")
+    return float(v)
+
+
+def _max_history_arg(v, what: str) -> float:
+    v = _number_arg(v, "max_history", what)
+    if not (v == 0.0 or v >= 1.0):
+        raise ValueError(f"{what}: max_history must be 0 (unlimited) or >= 1, not {v}")
+    return v
+
+
+def _matrix16(m, name: str) -> np.ndarray:
+    if isinstance(m, (str, bytes)):
+        raise TypeError(f"{name} must be 16 numbers")
+    a = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+    if a.size != 16:
+        raise ValueError(f"{name} must be 16 numbers (a 4 x 4 matrix in column-major order), not {a.size}")
+    return a
+
+
+def reproject_params(prev_world_to_clip, max_history: float = _lib.REPROJECT_DEFAULTS["max_history"],
+                     normal_threshold: float = _lib.REPROJECT_DEFAULTS["normal_threshold"],
+                     plane_threshold: float = _lib.REPROJECT_DEFAULTS["plane_threshold"]) -> _lib.ReprojectParams:
+    """The checked urt_ReprojectParams of Context.reproject: 16 matrix entries, max_history 0 or >= 1, thresholds that are not NaN."""
+    m = _matrix16(prev_world_to_clip, "reproject: prev_world_to_clip")
+    mh = _max_history_arg(max_history, "reproject")
+    nt = _number_arg(normal_threshold, "normal_threshold", "reproject")
+    pt = _number_arg(plane_threshold, "plane_threshold", "reproject")
+    return _lib.ReprojectParams((C.c_float * 16)(*m.tolist()), mh, nt, pt, 0)
+
 
 # urt_Ray / urt_RayHit (include/urt_types.h) as numpy records
 RAY_DT = np.dtype([("origin", np.float32, 3), ("t_max", np.float32), ("direction", np.float32, 3), ("reserved", np.int32)])
