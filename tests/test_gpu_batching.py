@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle
-from unityraytracer_amd import Graphics, RayTraceMaster, RenderTexture, debug_build_blas, scenes
+from unityraytracer_amd import Graphics, Material, RayTraceMaster, RenderTexture, debug_build_blas, scenes
 
 pytestmark = pytest.mark.gpu
 
@@ -280,6 +280,60 @@ def test_present_of_the_result_and_into_odd_targets(gpu_ctx):
         got = protocol(fpl)
         for x, y in zip(got, ref):
             assert bits_equal(x, y), fpl
+
+
+def test_interleaved_blend_kinds_and_presents(gpu_ctx):
+    """Additive blends into one image and history blends (urt_blit_add_history) into another, each presented now and then, in one
+    deferred batch: runs of one kind, the two kinds interleaved frame by frame, and 140 frames, so that the batches end at the
+    64-frame cap.  Every image equals one launch per frame, where nothing is deferred."""
+    sc = scenes.mixed_test_scene(40, 24)
+    n = 140
+    gx, gy = (sc.width + 7) // 8, (sc.height + 7) // 8
+
+    def protocol(fpl):
+        gpu_ctx.set_option("kernel_mode", 3)
+        gpu_ctx.set_option("frames_per_launch", fpl)
+        gpu_ctx.reset_counters()
+        m = RayTraceMaster(gpu_ctx, sc)
+        m.OnRenderImage()                                      # frame 0: scene, textures, the first additive blend
+        extra = [RenderTexture(gpu_ctx, sc.width, sc.height) for _ in range(4)]
+        add_out, hist, count, hist_out = extra
+        for t in (hist, count):
+            t.SetPixels(np.zeros((sc.height, sc.width, 4), np.float32))
+        mat = Material("Hidden/AdditionShader")
+        for i in range(1, n):
+            m._frame = i
+            m.SetShaderParameters()
+            m.RayTraceShader.SetTexture(0, "Result", m._target)
+            m.RayTraceShader.Dispatch(0, gx, gy, 1)
+            additive = i < 30 or (i >= 50 and i % 7 != 3)      # 1..29 alone, then with the history blends, but not every frame
+            history = i >= 20 and i % 5 != 0                    # 30..49 alone
+            if additive:
+                mat.SetFloat("_Sample", m._currentSample)
+                m._currentSample += 1
+                Graphics.Blit(m._target, m._converged, mat)
+                if i % 3 != 1:
+                    Graphics.Blit(m._converged, add_out)
+            if history:
+                gpu_ctx.blit_add_history(m._target, hist, count, 8.0)
+                if i % 4 != 2:
+                    Graphics.Blit(hist, hist_out)
+        out = [t.GetPixels() for t in [m._converged] + extra]
+        c = gpu_ctx.counters()
+        for t in extra:
+            t.Release()
+        m.OnDisable()
+        gpu_ctx.set_option("frames_per_launch", 0)
+        return out, c
+
+    ref, c1 = protocol(1)
+    assert c1["launches"] == n
+    assert (ref[3][..., 0] == 8.0).all()                        # every history pixel reached max_history
+    for fpl in (5, 0):
+        got, c = protocol(fpl)
+        for k, (x, y) in enumerate(zip(got, ref)):
+            assert bits_equal(x, y), (fpl, k)
+        assert c["launches"] < n and c["rays"] == c1["rays"] and c["watchdog_trips"] == 0, (fpl, c)
 
 
 def test_watchdog_trip_is_an_error_not_a_silent_hole(gpu_ctx):

@@ -179,8 +179,19 @@ struct urt_context {
   int scene_max_depth = 0;
   int opt_frames_per_launch = 0;            // 0 = auto (own stream: 64 frames per launch, fewer when the Result slots would exceed 8 GiB; caller's stream: 1), 1 = off, 2..64
   uint64_t scene_epoch = 0;                 // bumps at every scene preparation
-  struct PostOp { int kind; int frame; urt_handle tex; urt_handle dst; float sample; int first_row, row_stride; void* dense; urt_handle count; };   // kind 0 = blit_add(tex@frame -> dst), 1 = pack_rows(tex -> dense), 2 = blit(tex -> dst), the present of RM:819,
-                                                                                                                                  // 3 = blit_add_history(tex@frame -> dst, count; sample = max_history)
+  // An operation deferred behind the batch's frames (flush_pending runs them in program order): urt_blit_add(src@frame -> dst, sample),
+  // urt_blit_add_history(src@frame -> dst, count, max_history), urt_blit(src -> dst) — the present of RM:819 —, urt_texture_pack_rows[_rgb]
+  // (src -> dense).  `frame`: the batch's last frame when it was queued, the slot `src` names when it is the batch's Result texture.
+  enum class OpKind { BlendAdd, BlendHistory, Copy, PackRows };
+  struct PostOp {
+    OpKind kind;
+    int frame;
+    urt_handle src = 0, dst = 0;
+    float sample = 0;                                                             // BlendAdd
+    urt_handle count = 0; float max_history = 0;                                  // BlendHistory
+    void* dense = nullptr; int first_row = 0, row_stride = 1; bool rgb = false;   // PackRows
+    bool touches(urt_handle t) const { return src == t || dst == t || count == t; }
+  };
   struct Pending {
     int n = 0, limit = 1;
     urt_handle tex = 0;                     // the Result texture of the batch
@@ -239,6 +250,9 @@ struct urt_context {
 namespace { inline hipStream_t touch(urt_context* ctx) { ctx->main_touched = true; return ctx->stream; } }
 
 namespace {
+
+using PostOp = urt_context::PostOp;
+using OpKind = urt_context::OpKind;
 
 int fail(urt_context* ctx, int code, const std::string& msg) {
   if (ctx) ctx->err = msg; else g_create_error = msg;
@@ -348,6 +362,11 @@ void pack_albedo(const urt_RayTraceParams& m, float* dst) {
   v3 spec = mk3(m.color_specular[0], m.color_specular[1], m.color_specular[2]);
   albedo = vmin3(mk3(1.0f, 1.0f, 1.0f) - spec, albedo);                          // RS:390
   dst[0] = albedo.x; dst[1] = albedo.y; dst[2] = albedo.z; dst[3] = m.smoothness;
+}
+
+// strips first_row, first_row + row_stride, ... of 8-row groups that lie in the first group_rows
+int strip_count(int group_rows, int first_row, int row_stride) {
+  return first_row < group_rows ? (group_rows - first_row + row_stride - 1) / row_stride : 0;
 }
 
 int heap_levels(int n) { int l = 0; while (n > 0) { l++; n >>= 1; } return l; }   // floor(log2 n) + 1
@@ -1057,10 +1076,9 @@ int configure_sched(urt_context* ctx, const DevScene& S, FrameParams& P, bool to
   return mode;
 }
 
-// What urt_debug_launch_info reports: taken right after a launcher of kernels.hip returned (one host thread per context)
-void record_launch(urt_context* ctx, int kernel_mode, int front_mode, const FrameParams& P, bool count, int waves_per_cu) {
+// What urt_debug_launch_info reports: the record a launcher of kernels.hip filled, and the launch's configuration
+void record_launch(urt_context* ctx, const TraceLaunchRecord& R, int kernel_mode, int front_mode, const FrameParams& P, bool count, int waves_per_cu) {
   urt_launch_info& I = ctx->last_launch;
-  const TraceLaunchRecord& R = last_trace_launch();
   std::memset(&I, 0, sizeof I);
   std::snprintf(I.kernel, sizeof I.kernel, "%s", R.kernel);
   I.kernel_mode = kernel_mode; I.front_mode = front_mode; I.count_stats = count ? 1 : 0;
@@ -1071,6 +1089,28 @@ void record_launch(urt_context* ctx, int kernel_mode, int front_mode, const Fram
   I.lds_tables = (P.lds_mesh ? 1 : 0) | (P.lds_sphere ? 2 : 0) | (P.lds_small ? 4 : 0) | (P.walk_f4 > 0 ? 8 : 0);
   I.slab_frames = ctx->slab_frames; I.slab_frames_max = ctx->slab_frames_max; I.slab_out_of_memory = ctx->slab_oom_stride != 0 ? 1 : 0;
   I.experiment = URT_ABI_SIGN < 0 ? 1 : 0;
+}
+
+// One trace launch on stream `st`: `launch(TraceLaunchRecord*)` enqueues it through a launcher of kernels.hip, between two timing events
+// when "time_dispatch" is on; then the launch is counted and recorded (record_launch)
+template <typename Launch>
+int timed_launch(urt_context* ctx, hipStream_t st, int kernel_mode, int front_mode, const FrameParams& P, bool count, int waves_per_cu, Launch launch) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (ctx->opt_time_dispatch) {
+    int rc = take_event(ctx, &e0); if (rc) return rc;
+    rc = take_event(ctx, &e1); if (rc) return rc;
+    URT_HIP(ctx, hipEventRecord(e0, st));
+  }
+  TraceLaunchRecord rec{};
+  hipError_t le = launch(&rec);
+  if (ctx->opt_time_dispatch) {
+    (void)hipEventRecord(e1, st);
+    ctx->timing.emplace_back(e0, e1);
+  }
+  ctx->launches++;
+  if (le != hipSuccess) return fail(ctx, URT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(le));
+  record_launch(ctx, rec, kernel_mode, front_mode, P, count, waves_per_cu);
+  return URT_OK;
 }
 
 // Launch the phase-scheduled trace kernel for P.n_frames frames (uniforms T) into result + f * P.frame_stride.
@@ -1110,32 +1150,43 @@ int launch_sched_frames(urt_context* ctx, const DevScene& S, const FrameParams& 
       ctx->mail_slots = slots;
     }
   }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->opt_time_dispatch) {
-    int rc = take_event(ctx, &e0); if (rc) return rc;
-    rc = take_event(ctx, &e1); if (rc) return rc;
-    URT_HIP(ctx, hipEventRecord(e0, st));
-  }
-  hipError_t le = P.serve ? launch_serve(S, P, d_table, result, ctx->d_counters, next, ctx->d_mail, nb, front_mode, count, st)
-                          : launch_sched(S, P, d_table, result, ctx->d_counters, next, nb, front_mode, count, st);
-  if (ctx->opt_time_dispatch) {
-    (void)hipEventRecord(e1, st);
-    ctx->timing.emplace_back(e0, e1);
-  }
-  ctx->launches++;
-  if (le != hipSuccess) return fail(ctx, URT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(le));
-  record_launch(ctx, P.serve ? 5 : 3, front_mode, P, count, wpc);
-  return URT_OK;
+  return timed_launch(ctx, st, P.serve ? 5 : 3, front_mode, P, count, wpc, [&](TraceLaunchRecord* rec) {
+    return P.serve ? launch_serve(S, P, d_table, result, ctx->d_counters, next, ctx->d_mail, nb, front_mode, count, st, rec)
+                   : launch_sched(S, P, d_table, result, ctx->d_counters, next, nb, front_mode, count, st, rec);
+  });
 }
 
-// Submit the deferred frames: ONE trace launch, then the deferred blits in program order.  Runs of AdditionShader blits of
-// consecutive frames into one image are fused into a single pass (same per-pixel operations in the same order).
+// The run of deferred blends that starts at ops[i], which flush_pending makes ONE pass (the same per-pixel operations in the same order):
+// blends of the same kind into the same dst (history blends: also the same count and max_history; an additive blend has 0, 0) of
+// consecutive frames, up to kMaxFramesPerLaunch, each possibly followed by the present of dst (RM:818-819) — a copy that reads dst and
+// writes the run's one target, none of dst, count and the batch's Result `result_tex`.  Only the last present is observable: every call
+// that could observe the target submits this work first (as-if rule, include/urt.h); the run ends at that present, so the image
+// presented is the one it was presented with.  `samples` receives the _Sample of the additive blends.
+struct BlendRun { int frames; urt_handle present; size_t end; };   // present: 0 = none; end: the index after the run
+BlendRun blend_run(const std::vector<PostOp>& ops, size_t i, urt_handle result_tex, float* samples) {
+  const PostOp& op = ops[i];
+  size_t j = i, j_present = i;
+  int cnt = 0, cnt_present = 0;
+  urt_handle present = 0;
+  while (j < ops.size() && cnt <= kMaxFramesPerLaunch) {
+    const PostOp& q = ops[j];
+    if (q.kind == op.kind && q.dst == op.dst && q.count == op.count && q.max_history == op.max_history && q.frame == op.frame + cnt &&
+        cnt < kMaxFramesPerLaunch) { samples[cnt++] = q.sample; j++; }
+    else if (q.kind == OpKind::Copy && q.src == op.dst && q.dst != op.dst && q.dst != op.count && q.dst != result_tex && (present == 0 || q.dst == present)) {
+      present = q.dst; j++; j_present = j; cnt_present = cnt;
+    } else break;
+  }
+  if (present) return BlendRun{cnt_present, present, j_present};
+  return BlendRun{cnt, 0, j};
+}
+
+// Submit the deferred frames: ONE trace launch, then the deferred operations in program order, each run of blends (blend_run) in one pass.
 int flush_pending(urt_context* ctx) {
   urt_context::Pending& B = ctx->pend;
   if (B.n == 0) return URT_OK;
   int n = B.n;
   B.n = 0;                                               // whatever happens below, the batch is gone
-  std::vector<urt_context::PostOp> ops;
+  std::vector<PostOp> ops;
   ops.swap(B.ops);
   URT_HIP(ctx, hipSetDevice(ctx->device));
   FrameParams P = B.P;
@@ -1195,83 +1246,45 @@ int flush_pending(urt_context* ctx) {
   const float4* const slots = ctx->slab + (size_t)base * ctx->slab_stride;
   size_t i = 0;
   while (i < ops.size()) {
-    const urt_context::PostOp& op = ops[i];
-    if (op.kind == 0) {
+    const PostOp& op = ops[i];
+    if (op.kind == OpKind::BlendAdd || op.kind == OpKind::BlendHistory) {
+      const bool history = op.kind == OpKind::BlendHistory;
       Texture* d = find_texture(ctx, op.dst);
-      if (!d) return fail(ctx, URT_ERR_INVALID_HANDLE, "deferred Blit: destination texture was released");
-      // A run of AdditionShader blends of consecutive frames into one image, each possibly followed by the present of that image
-      // (RM:818-819: Blit(_target, _converged, mat); Blit(_converged, destination)) — ONE pass.  Of the presents only the last
-      // is observable: every call that could observe `destination` submits this work first, so an earlier present is overwritten
-      // unseen (as-if rule, include/urt.h); the run ends at its last present so that the image presented is the mean it was
-      // presented with.
+      Texture* c = history ? find_texture(ctx, op.count) : nullptr;
+      if (!d || (history && !c))
+        return fail(ctx, URT_ERR_INVALID_HANDLE, history ? "deferred blit_add_history: texture was released" : "deferred Blit: destination texture was released");
       float samples[kMaxFramesPerLaunch];
-      size_t j = i, j_present = i;
-      int cnt = 0, cnt_present = 0;
-      urt_handle present = 0;
-      while (j < ops.size() && cnt <= kMaxFramesPerLaunch) {
-        const urt_context::PostOp& q = ops[j];
-        if (q.kind == 0 && q.dst == op.dst && q.frame == op.frame + cnt && cnt < kMaxFramesPerLaunch) { samples[cnt++] = q.sample; j++; }
-        else if (q.kind == 2 && q.tex == op.dst && q.dst != op.dst && q.dst != B.tex && (present == 0 || q.dst == present)) {
-          present = q.dst; j++; j_present = j; cnt_present = cnt;
-        } else break;
-      }
-      if (present) { j = j_present; cnt = cnt_present; }
+      const BlendRun run = blend_run(ops, i, B.tex, samples);
       float4* pdev = nullptr;
-      if (present) {
-        Texture* pt = find_texture(ctx, present);
-        if (!pt) return fail(ctx, URT_ERR_INVALID_HANDLE, "deferred Blit: destination texture was released");
-        pdev = pt->dev;
-      }
-      const float4* src = slots + (size_t)op.frame * ctx->slab_stride;
-      hipError_t e = (cnt == 1 && !pdev) ? launch_blit_add(src, d->dev, (size_t)d->w * d->h, samples[0], ctx->stream)
-                                         : launch_blit_add_multi(src, ctx->slab_stride, cnt, samples, d->dev, pdev, (size_t)d->w * d->h, ctx->stream);
-      if (e != hipSuccess) return fail(ctx, URT_ERR_HIP, std::string("deferred Blit: ") + hipGetErrorString(e));
-      i = j;
-    } else if (op.kind == 3) {
-      Texture* d = find_texture(ctx, op.dst);
-      Texture* c = find_texture(ctx, op.count);
-      if (!d || !c) return fail(ctx, URT_ERR_INVALID_HANDLE, "deferred blit_add_history: texture was released");
-      // The same fusion as kind 0: a run of blends of consecutive frames into one dst / count with one max_history, each possibly followed
-      // by the present of dst, in ONE pass that reads and writes the count once (same per-pixel operations, include/urt.h)
-      size_t j = i, j_present = i;
-      int cnt = 0, cnt_present = 0;
-      urt_handle present = 0;
-      while (j < ops.size() && cnt <= kMaxFramesPerLaunch) {
-        const urt_context::PostOp& q = ops[j];
-        if (q.kind == 3 && q.dst == op.dst && q.count == op.count && q.sample == op.sample && q.frame == op.frame + cnt &&
-            cnt < kMaxFramesPerLaunch) { cnt++; j++; }
-        else if (q.kind == 2 && q.tex == op.dst && q.dst != op.dst && q.dst != op.count && q.dst != B.tex && (present == 0 || q.dst == present)) {
-          present = q.dst; j++; j_present = j; cnt_present = cnt;
-        } else break;
-      }
-      if (present) { j = j_present; cnt = cnt_present; }
-      float4* pdev = nullptr;
-      if (present) {
-        Texture* pt = find_texture(ctx, present);
+      if (run.present) {
+        Texture* pt = find_texture(ctx, run.present);
         if (!pt) return fail(ctx, URT_ERR_INVALID_HANDLE, "deferred Blit: destination texture was released");
         pdev = pt->dev;
       }
       const float4* src = slots + (size_t)op.frame * ctx->slab_stride;
       const size_t npix = (size_t)d->w * d->h;
-      hipError_t e = (cnt == 1 && !pdev) ? launch_blit_add_history(src, d->dev, c->dev, npix, op.sample, ctx->stream)
-                                         : launch_blit_add_history_multi(src, ctx->slab_stride, cnt, d->dev, c->dev, pdev, npix, op.sample, ctx->stream);
-      if (e != hipSuccess) return fail(ctx, URT_ERR_HIP, std::string("deferred blit_add_history: ") + hipGetErrorString(e));
-      i = j;
-    } else if (op.kind == 2) {
-      Texture* t = find_texture(ctx, op.tex);
+      const bool single = run.frames == 1 && !pdev;
+      hipError_t e;
+      if (history) e = single ? launch_blit_add_history(src, d->dev, c->dev, npix, op.max_history, ctx->stream)
+                              : launch_blit_add_history_multi(src, ctx->slab_stride, run.frames, d->dev, c->dev, pdev, npix, op.max_history, ctx->stream);
+      else e = single ? launch_blit_add(src, d->dev, npix, samples[0], ctx->stream)
+                      : launch_blit_add_multi(src, ctx->slab_stride, run.frames, samples, d->dev, pdev, npix, ctx->stream);
+      if (e != hipSuccess) return fail(ctx, URT_ERR_HIP, std::string(history ? "deferred blit_add_history: " : "deferred Blit: ") + hipGetErrorString(e));
+      i = run.end;
+    } else if (op.kind == OpKind::Copy) {
+      Texture* t = find_texture(ctx, op.src);
       Texture* d = find_texture(ctx, op.dst);
       if (!t || !d) return fail(ctx, URT_ERR_INVALID_HANDLE, "deferred Blit: texture was released");
-      const float4* img = op.tex == B.tex ? slots + (size_t)op.frame * ctx->slab_stride : t->dev;
+      const float4* img = op.src == B.tex ? slots + (size_t)op.frame * ctx->slab_stride : t->dev;
       URT_HIP(ctx, hipMemcpyAsync(d->dev, img, (size_t)t->w * t->h * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
       i++;
     } else {
-      Texture* t = find_texture(ctx, op.tex);
+      Texture* t = find_texture(ctx, op.src);
       if (!t) return fail(ctx, URT_ERR_INVALID_HANDLE, "deferred pack_rows: texture was released");
-      const float4* img = op.tex == B.tex ? slots + (size_t)op.frame * ctx->slab_stride : t->dev;
-      int group_rows = (t->h + 7) / 8;
-      int n_strips = op.first_row < group_rows ? (group_rows - op.first_row + op.row_stride - 1) / op.row_stride : 0;
-      hipError_t e = op.sample != 0.0f ? launch_pack_rows_rgb(const_cast<float4*>(img), (float*)op.dense, t->w, t->h, op.first_row, op.row_stride, n_strips, true, 0.0f, ctx->stream)
-                                       : launch_pack_rows(const_cast<float4*>(img), (float4*)op.dense, t->w, t->h, op.first_row, op.row_stride, n_strips, true, ctx->stream);
+      const float4* img = op.src == B.tex ? slots + (size_t)op.frame * ctx->slab_stride : t->dev;
+      int n_strips = strip_count((t->h + 7) / 8, op.first_row, op.row_stride);
+      hipError_t e = op.rgb ? launch_pack_rows_rgb(const_cast<float4*>(img), (float*)op.dense, t->w, t->h, op.first_row, op.row_stride, n_strips, true, 0.0f, ctx->stream)
+                            : launch_pack_rows(const_cast<float4*>(img), (float4*)op.dense, t->w, t->h, op.first_row, op.row_stride, n_strips, true, ctx->stream);
       if (e != hipSuccess) return fail(ctx, URT_ERR_HIP, std::string("deferred pack_rows: ") + hipGetErrorString(e));
       i++;
     }
@@ -1338,9 +1351,8 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
   long rw = std::min<long>((long)gx * 8, res->w), rh = std::min<long>((long)gy * 8, res->h);
   P.region_w = (int)rw; P.region_h = (int)rh;
   P.tiles_x = (P.region_w + 7) / 8;
-  int group_rows = (P.region_h + 7) / 8;
   P.first_group_row = first_row; P.row_stride = row_stride;
-  P.n_strips = first_row < group_rows ? (group_rows - first_row + row_stride - 1) / row_stride : 0;
+  P.n_strips = strip_count((P.region_h + 7) / 8, first_row, row_stride);      // rows of the dispatched region
   P.tlas_stack = ctx->tlas_stack; P.blas_stack = ctx->blas_stack + ctx->opt_stack_pad; P.watchdog_steps = ctx->watchdog_steps;
   P.block_threads = ctx->opt_block_threads; P.xcd_run = ctx->opt_xcd_run; P.tile_order = ctx->opt_tile_order >= 0 ? ctx->opt_tile_order : (S.n_meshes == 0 ? 1 : 0); P.refill_min = ctx->opt_refill_min;
   // lanes parked at a triangle BVH before the traversal phase runs: 16 with one mesh (C3 -2 %, C3D -6 % against 28), 24 when rays walk
@@ -1418,49 +1430,42 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
     }
   } else {
     int rc = flush_pending(ctx); if (rc) return rc;
+    int nb = 0, k = 0;
     if (mode == 1) {
       size_t n_paths = (size_t)P.tiles_x * 64 * (size_t)P.n_strips;
       rc = ensure_queues(ctx, n_paths, (size_t)P.num_rays * (size_t)(P.num_bounces + 1));
       if (rc) return rc;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ctx->opt_time_dispatch) {
-      rc = take_event(ctx, &e0); if (rc) return rc;
-      rc = take_event(ctx, &e1); if (rc) return rc;
-      URT_HIP(ctx, hipEventRecord(e0, touch(ctx)));
-    }
-    hipError_t le;
-    if (mode == 1) le = launch_wavefront(S, P, ctx->q, res->dev, ctx->d_counters, count, touch(ctx));
-    else if (mode == 2) {
+    } else if (mode == 2) {
       int waves_per_block = P.block_threads / 64;
       long want = ((long)P.tiles_x * P.n_strips + waves_per_block - 1) / waves_per_block;
       int wpc = ctx->opt_waves_per_cu;
       if (wpc <= 0) wpc = 20;
       long resident = (long)ctx->n_cus * wpc / waves_per_block;
-      int nb = (int)std::max(1L, std::min(want, resident));
-      le = launch_persist(S, P, res->dev, ctx->d_counters, ctx->d_next, nb, count, touch(ctx));
+      nb = (int)std::max(1L, std::min(want, resident));
     } else if (mode == 4) {
       // one wave per workgroup; residency is bounded by the LDS one wave's path pool takes (kernels.hip k_pool)
       P.block_threads = 64;
       P.refill_min = ctx->opt_pool_refill; P.blas_min = ctx->opt_pool_blas_min; P.blas_exit = ctx->opt_pool_blas_exit;
       P.pool_inloop = ctx->opt_pool_inloop; P.pool_other_min = ctx->opt_pool_other_min;
-      int k = ctx->opt_pool_k;
+      k = ctx->opt_pool_k;
       size_t lds = pool_lds_bytes(P, k);
       while (k > 1 && lds > 160 * 1024) { k--; lds = pool_lds_bytes(P, k); }
       if (lds > 160 * 1024) return fail(ctx, URT_ERR_OUT_OF_MEMORY, "kernel_mode 4: the scene's traversal stacks do not fit the LDS of one CU; use kernel_mode 3");
       int fit = (int)std::max<size_t>(1, (160 * 1024) / lds);
       int wpc = ctx->opt_waves_per_cu > 0 ? ctx->opt_waves_per_cu : fit;
       long want = ((long)P.tiles_x * P.n_strips * 64 + 64L * k - 1) / (64L * k);
-      int nb = (int)std::max(1L, std::min(want, (long)ctx->n_cus * wpc));
-      le = launch_pool(S, P, res->dev, ctx->d_counters, ctx->d_next, nb, k, count, touch(ctx));
-    } else le = launch_mega(S, P, res->dev, ctx->d_counters, count, touch(ctx));
-    if (ctx->opt_time_dispatch) {
-      (void)hipEventRecord(e1, touch(ctx));
-      ctx->timing.emplace_back(e0, e1);
+      nb = (int)std::max(1L, std::min(want, (long)ctx->n_cus * wpc));
     }
-    ctx->launches++;
-    if (le != hipSuccess) return fail(ctx, URT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(le));
-    record_launch(ctx, mode, 0, P, count, ctx->opt_waves_per_cu);
+    const hipStream_t st = touch(ctx);
+    rc = timed_launch(ctx, st, mode, 0, P, count, ctx->opt_waves_per_cu, [&](TraceLaunchRecord* rec) {
+      switch (mode) {
+        case 1: return launch_wavefront(S, P, ctx->q, res->dev, ctx->d_counters, count, st, rec);
+        case 2: return launch_persist(S, P, res->dev, ctx->d_counters, ctx->d_next, nb, count, st, rec);
+        case 4: return launch_pool(S, P, res->dev, ctx->d_counters, ctx->d_next, nb, k, count, st, rec);
+        default: return launch_mega(S, P, res->dev, ctx->d_counters, count, st, rec);
+      }
+    });
+    if (rc) return rc;
   }
   // remember what has written the image (see Texture)
   if (res->n_regions == 0) { res->n_regions = 1; std::memcpy(res->rg, region, sizeof region); }
@@ -1905,7 +1910,7 @@ int urt_blit_add(urt_context* ctx, urt_handle src, urt_handle dst, float sample)
   if (B.n > 0 && src == B.tex && dst != src && (const float4*)d->dev != B.S.sky) {
     // the source is a frame that has not been traced yet: the blend is deferred with it (flush_pending runs it in order)
     // (a full batch is submitted by the next dispatch or observer — the present of this frame, RM:819, may still follow)
-    B.ops.push_back(urt_context::PostOp{0, B.n - 1, src, dst, sample, 0, 1, nullptr});
+    B.ops.push_back(PostOp{.kind = OpKind::BlendAdd, .frame = B.n - 1, .src = src, .dst = dst, .sample = sample});
     return URT_OK;
   }
   { int rc = flush_pending(ctx); if (rc) return rc; }
@@ -1937,8 +1942,7 @@ int urt_blit_add_history(urt_context* ctx, urt_handle src, urt_handle dst, urt_h
   c->other_writes = true;
   urt_context::Pending& B = ctx->pend;
   if (B.n > 0 && src == B.tex && (const float4*)d->dev != B.S.sky && (const float4*)c->dev != B.S.sky) {
-    urt_context::PostOp op{3, B.n - 1, src, dst, max_history, 0, 1, nullptr, count};
-    B.ops.push_back(op);
+    B.ops.push_back(PostOp{.kind = OpKind::BlendHistory, .frame = B.n - 1, .src = src, .dst = dst, .count = count, .max_history = max_history});
     return URT_OK;
   }
   { int rc = flush_pending(ctx); if (rc) return rc; }
@@ -1960,7 +1964,7 @@ int urt_blit(urt_context* ctx, urt_handle src, urt_handle dst) {
     // frames are deferred: the copy is queued behind them, in program order (the present of RM:819 — its source is the image
     // the deferred blends accumulate into).  flush_pending fuses it into the blend pass.
     d->other_writes = true;
-    B.ops.push_back(urt_context::PostOp{2, B.n - 1, src, dst, 0.0f, 0, 1, nullptr});
+    B.ops.push_back(PostOp{.kind = OpKind::Copy, .frame = B.n - 1, .src = src, .dst = dst});
     if (B.n >= B.limit) return flush_pending(ctx);        // the batch is full and its last frame is presented: go
     return URT_OK;
   }
@@ -1978,15 +1982,15 @@ static int pack_impl(urt_context* ctx, urt_handle texture, int first_group_row, 
   Texture* t = find_texture(ctx, texture);
   if (!t) return fail(ctx, URT_ERR_INVALID_HANDLE, "unknown texture handle");
   if (first_group_row < 0 || row_stride < 1) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "bad strip arguments");
-  int group_rows = (t->h + 7) / 8;
-  int n_strips = first_group_row < group_rows ? (group_rows - first_group_row + row_stride - 1) / row_stride : 0;
+  int n_strips = strip_count((t->h + 7) / 8, first_group_row, row_stride);
   if (out_bytes) *out_bytes = (uint64_t)n_strips * 8u * (uint64_t)t->w * (rgb ? 3 * sizeof(float) : sizeof(float4));
   if (!dense) return URT_OK;   // size query
   URT_HIP(ctx, hipSetDevice(ctx->device));
   URT_GUARD_BEGIN
   urt_context::Pending& B = ctx->pend;
   if (to_dense && B.n > 0) {     // reads an image that deferred work is still going to write: deferred with it, in order
-    B.ops.push_back(urt_context::PostOp{1, B.n - 1, texture, 0, rgb ? 1.0f : 0.0f, first_group_row, row_stride, dense});   // (sample != 0: the RGB form)
+    B.ops.push_back(PostOp{.kind = OpKind::PackRows, .frame = B.n - 1, .src = texture, .dense = dense,
+                           .first_row = first_group_row, .row_stride = row_stride, .rgb = rgb});
     return URT_OK;
   }
   { int rc = flush_pending(ctx); if (rc) return rc; }
@@ -2011,12 +2015,11 @@ static int unpack_on_impl(urt_context* ctx, urt_handle texture, int first_group_
   if (first_group_row < 0 || row_stride < 1) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "bad strip arguments");
   if (ctx->pend.n > 0) {                                  // never the case for a dedicated gather target
     bool touched = ctx->pend.tex == texture;
-    for (const urt_context::PostOp& q : ctx->pend.ops) touched = touched || q.tex == texture || q.dst == texture || q.count == texture;
+    for (const PostOp& q : ctx->pend.ops) touched = touched || q.touches(texture);
     if (touched) { int rc = flush_pending(ctx); if (rc) return rc; }
   }
   if (in_slab(ctx, *t)) { int rc = detach_from_slab(ctx, *t); if (rc) return rc; }
-  int group_rows = (t->h + 7) / 8;
-  int n_strips = first_group_row < group_rows ? (group_rows - first_group_row + row_stride - 1) / row_stride : 0;
+  int n_strips = strip_count((t->h + 7) / 8, first_group_row, row_stride);
   t->other_writes = true;
   URT_HIP(ctx, hipSetDevice(ctx->device));
   if (rgb) URT_HIP(ctx, launch_pack_rows_rgb(t->dev, (float*)const_cast<void*>(device_src), t->w, t->h, first_group_row, row_stride, n_strips, false,

@@ -33,10 +33,10 @@ struct urt_group {
   std::vector<void*> recv;                             // [rank] on rank 0's device:   kSlots x stage_bytes
   std::vector<std::vector<hipEvent_t>> ev_copy;        // [rank][slot] the peer copy of that slot has landed on rank 0
   std::vector<std::vector<hipEvent_t>> ev_free;        // [rank][slot] rank 0 has unpacked it (the slot may be reused)
-  // gathers whose packs are queued but whose copies are not issued yet (kind 0, staging slot `slot`), and — in program order
-  // between them — the plain blits that read or write an image such a gather writes (kind 1: the present of the gathered image,
-  // RM:819): they must run after the unpack that is still to be issued
-  struct PendingGather { int kind; urt_handle src, dst; int slot; };
+  // gathers whose packs are queued but whose copies are not issued yet (staging slot `slot`), and — in program order between them —
+  // the plain blits that read or write an image such a gather writes (`blit`: the present of the gathered image, RM:819): they must
+  // run after the unpack that is still to be issued
+  struct PendingGather { bool blit; urt_handle src, dst; int slot; };
   std::vector<PendingGather> pending;
   int pending_gathers = 0;
   uint64_t gathers = 0;
@@ -119,7 +119,7 @@ int flush_gathers(urt_group* g) {
     hipStream_t st = urtd::context_stream(c);
     GROUP_HIP(g, hipSetDevice(dev));
     for (const urt_group::PendingGather& op : todo) {
-      if (op.kind == 0) {
+      if (!op.blit) {
         char* src = (char*)g->stage[r] + (size_t)op.slot * g->stage_bytes;
         char* dst = (char*)g->recv[r] + (size_t)op.slot * g->stage_bytes;
         GROUP_HIP(g, hipMemcpyPeerAsync(dst, dev0, src, dev, g->stage_bytes, st));   // xGMI point-to-point (or on-device when the ordinals coincide)
@@ -133,7 +133,7 @@ int flush_gathers(urt_group* g) {
   GROUP_HIP(g, hipSetDevice(dev0));
   hipStream_t st0 = urtd::context_stream(root);
   for (const urt_group::PendingGather& op : todo) {
-    if (op.kind == 1) {                                                 // in program order after the unpacks before it
+    if (op.blit) {                                                      // in program order after the unpacks before it
       int rc = urt_blit(root, op.src, op.dst);
       if (rc) return rank_fail(g, 0, rc);
       continue;
@@ -280,7 +280,7 @@ int urt_group_blit(urt_group* g, urt_handle src, urt_handle dst) {
   if (g && written_by_pending(g, src, dst)) {
     // the present of a gathered image (gather(_converged -> full); Blit(full, destination), RM:819): queued with the gathers, it
     // runs right after the unpack it depends on — the ranks keep batching their frames
-    g->pending.push_back(urt_group::PendingGather{1, src, dst, 0});
+    g->pending.push_back(urt_group::PendingGather{true, src, dst, 0});
     return URT_OK;
   }
   FORWARD(g, urt_blit(c, src, dst));
@@ -320,7 +320,7 @@ int urt_group_gather(urt_group* g, urt_handle src_texture, urt_handle dst_textur
     rc = urt_texture_pack_rows(c, src_texture, (int)r, (int)n, (char*)g->stage[r] + slot * g->stage_bytes, nullptr);   // deferred behind the rank's batched frames
     if (rc) return rank_fail(g, (int)r, rc);
   }
-  g->pending.push_back(urt_group::PendingGather{0, src_texture, dst_texture, (int)slot});
+  g->pending.push_back(urt_group::PendingGather{false, src_texture, dst_texture, (int)slot});
   g->pending_gathers++;
   g->gathers++;
   // submit when the burst is full, or at once when the ranks are not deferring frames (then there is nothing to wait for)

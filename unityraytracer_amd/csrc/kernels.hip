@@ -2050,74 +2050,70 @@ static inline size_t stack_lds_bytes(const FrameParams& P) {
   return (size_t)(P.tlas_stack + P.blas_stack) * 64 * (size_t)(P.block_threads / 64) * sizeof(int);
 }
 
-// What the last trace launch of this process was (urt_debug_launch_info): the instantiation's name as rocprofv3 prints it, its grid
-// and its dynamic LDS.  Written by the launchers below on the caller's (single) host thread; context.cpp copies it per context.
-static TraceLaunchRecord g_last_trace;
-const TraceLaunchRecord& last_trace_launch() { return g_last_trace; }
-static void note_launch(int n_blocks, int block_threads, size_t lds, const char* fmt, ...) __attribute__((format(printf, 4, 5)));
-static void note_launch(int n_blocks, int block_threads, size_t lds, const char* fmt, ...) {
+// Names the trace launch *rec describes (urt_debug_launch_info): the kernel instantiation by the name rocprofv3 prints for it
+static TraceLaunchRecord* named(TraceLaunchRecord* rec, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+static TraceLaunchRecord* named(TraceLaunchRecord* rec, const char* fmt, ...) {
   va_list ap; va_start(ap, fmt);
-  vsnprintf(g_last_trace.kernel, sizeof g_last_trace.kernel, fmt, ap);
+  vsnprintf(rec->kernel, sizeof rec->kernel, fmt, ap);
   va_end(ap);
-  g_last_trace.n_blocks = n_blocks; g_last_trace.block_threads = block_threads; g_last_trace.lds_bytes = (int)lds;
+  return rec;
 }
 static const char* tf(bool b) { return b ? "true" : "false"; }
 
-// dynamic LDS above the default 64 KiB per workgroup (very deep BVHs): the kernel's limit has to be raised first
-template <typename K>
-static hipError_t allow_lds(K kernel, size_t lds) {
-  if (lds <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
-hipError_t launch_mega(const DevScene& S, const FrameParams& P, float4* result, DevCounters* ctr, bool count, hipStream_t st) {
-  int nb = blocks_for_tiles(P);
-  if (nb == 0) return hipSuccess;
-  size_t lds = stack_lds_bytes(P);
-  hipError_t ea = count ? allow_lds(k_mega<true>, lds) : allow_lds(k_mega<false>, lds);
-  if (ea != hipSuccess) return ea;
-  if (count) hipLaunchKernelGGL(k_mega<true>, dim3(nb), dim3(P.block_threads), lds, st, S, P, result, ctr);
-  else hipLaunchKernelGGL(k_mega<false>, dim3(nb), dim3(P.block_threads), lds, st, S, P, result, ctr);
-  note_launch(nb, P.block_threads, lds, "k_mega<%s>", tf(count));
+// One trace-kernel launch: dynamic LDS above the default 64 KiB per workgroup (very deep BVHs) raises the kernel's limit first; *rec
+// (named by the caller) receives the grid and the dynamic LDS
+template <typename... KP, typename... A>
+static hipError_t launch_traced(TraceLaunchRecord* rec, void (*kernel)(KP...), int n_blocks, int block_threads, size_t lds, hipStream_t st,
+                                const A&... args) {
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(block_threads), lds, st, args...);
+  rec->n_blocks = n_blocks; rec->block_threads = block_threads; rec->lds_bytes = (int)lds;
   return hipGetLastError();
 }
 
+hipError_t launch_mega(const DevScene& S, const FrameParams& P, float4* result, DevCounters* ctr, bool count, hipStream_t st,
+                       TraceLaunchRecord* rec) {
+  int nb = blocks_for_tiles(P);
+  if (nb == 0) return hipSuccess;
+  return launch_traced(named(rec, "k_mega<%s>", tf(count)), count ? k_mega<true> : k_mega<false>, nb, P.block_threads, stack_lds_bytes(P), st,
+                       S, P, result, ctr);
+}
+
 hipError_t launch_wavefront(const DevScene& S, const FrameParams& P, const PathQueues& Q, float4* result, DevCounters* ctr,
-                            bool count, hipStream_t st) {
+                            bool count, hipStream_t st, TraceLaunchRecord* rec) {
   int nb = blocks_for_tiles(P);
   if (nb == 0) return hipSuccess;
   size_t lds = stack_lds_bytes(P);
   size_t n_counts = (size_t)P.num_rays * (P.num_bounces + 1);
   hipError_t e = hipMemsetAsync(Q.counts, 0, n_counts * sizeof(unsigned int), st);
   if (e != hipSuccess) return e;
-  e = count ? allow_lds(k_bounce<true>, lds) : allow_lds(k_bounce<false>, lds);
-  if (e != hipSuccess) return e;
+  auto bounce = count ? k_bounce<true> : k_bounce<false>;
+  if (lds > 64 * 1024) {                     // as in launch_traced
+    e = hipFuncSetAttribute((const void*)bounce, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
   size_t npix = (size_t)P.region_w * 8 * P.n_strips;
   int bt = P.block_threads;
   int nbb = (int)((npix + bt - 1) / bt);
   for (int i = 0; i < P.num_rays; i++) {
     hipLaunchKernelGGL(k_generate, dim3(nb), dim3(bt), 0, st, P, Q, (const float4*)result, i, ctr);
-    for (int k = 0; k < P.num_bounces; k++) {
-      if (count) hipLaunchKernelGGL(k_bounce<true>, dim3(nbb), dim3(bt), lds, st, S, P, Q, result, i, k, ctr);
-      else hipLaunchKernelGGL(k_bounce<false>, dim3(nbb), dim3(bt), lds, st, S, P, Q, result, i, k, ctr);
-    }
+    for (int k = 0; k < P.num_bounces; k++) hipLaunchKernelGGL(bounce, dim3(nbb), dim3(bt), lds, st, S, P, Q, result, i, k, ctr);
   }
-  note_launch(nbb, bt, lds, "k_generate + k_bounce<%s> x %d", tf(count), P.num_rays * P.num_bounces);
+  named(rec, "k_generate + k_bounce<%s> x %d", tf(count), P.num_rays * P.num_bounces);
+  rec->n_blocks = nbb; rec->block_threads = bt; rec->lds_bytes = (int)lds;
   return hipGetLastError();
 }
 
 hipError_t launch_persist(const DevScene& S, const FrameParams& P, float4* result, DevCounters* ctr, unsigned int* next,
-                          int n_blocks, bool count, hipStream_t st) {
+                          int n_blocks, bool count, hipStream_t st, TraceLaunchRecord* rec) {
   if (n_blocks <= 0) return hipSuccess;
   hipError_t e = hipMemsetAsync(next, 0, kWorkShards * 32 * sizeof(unsigned int), st);
   if (e != hipSuccess) return e;
-  size_t lds = stack_lds_bytes(P);
-  e = count ? allow_lds(k_persist<true>, lds) : allow_lds(k_persist<false>, lds);
-  if (e != hipSuccess) return e;
-  if (count) hipLaunchKernelGGL(k_persist<true>, dim3(n_blocks), dim3(P.block_threads), lds, st, S, P, result, ctr, next);
-  else hipLaunchKernelGGL(k_persist<false>, dim3(n_blocks), dim3(P.block_threads), lds, st, S, P, result, ctr, next);
-  note_launch(n_blocks, P.block_threads, lds, "k_persist<%s>", tf(count));
-  return hipGetLastError();
+  return launch_traced(named(rec, "k_persist<%s>", tf(count)), count ? k_persist<true> : k_persist<false>, n_blocks, P.block_threads,
+                       stack_lds_bytes(P), st, S, P, result, ctr, next);
 }
 
 size_t sched_lds_bytes(const DevScene& S, const FrameParams& P) {
@@ -2132,41 +2128,36 @@ size_t sched_lds_bytes(const DevScene& S, const FrameParams& P) {
 
 template <bool COUNT, int BLOCK, int FMODE, bool MULTI, bool QN>
 static hipError_t launch_sched_q(const DevScene& S, const FrameParams& P, const FrameUniforms* T, float4* result, DevCounters* ctr,
-                                 unsigned int* next, int n_blocks, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_sched<COUNT, BLOCK, FMODE, MULTI, QN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((k_sched<COUNT, BLOCK, FMODE, MULTI, QN>), dim3(n_blocks), dim3(BLOCK), lds, st, S, P, T, result, ctr, next);
-  note_launch(n_blocks, BLOCK, lds, "k_sched<%s, %d, %d, %s, %s>", tf(COUNT), BLOCK, FMODE, tf(MULTI), tf(QN));
-  return hipGetLastError();
+                                 unsigned int* next, int n_blocks, size_t lds, hipStream_t st, TraceLaunchRecord* rec) {
+  return launch_traced(named(rec, "k_sched<%s, %d, %d, %s, %s>", tf(COUNT), BLOCK, FMODE, tf(MULTI), tf(QN)), k_sched<COUNT, BLOCK, FMODE, MULTI, QN>,
+                       n_blocks, BLOCK, lds, st, S, P, T, result, ctr, next);
 }
 
 template <bool COUNT, int BLOCK, int FMODE, bool MULTI>
 static hipError_t launch_sched_t(const DevScene& S, const FrameParams& P, const FrameUniforms* T, float4* result, DevCounters* ctr,
-                                 unsigned int* next, int n_blocks, size_t lds, hipStream_t st) {
-  if (!COUNT && S.blas_qnodes) return launch_sched_q<false, BLOCK, FMODE, MULTI, true>(S, P, T, result, ctr, next, n_blocks, lds, st);
-  return launch_sched_q<COUNT, BLOCK, FMODE, MULTI, false>(S, P, T, result, ctr, next, n_blocks, lds, st);
+                                 unsigned int* next, int n_blocks, size_t lds, hipStream_t st, TraceLaunchRecord* rec) {
+  if (!COUNT && S.blas_qnodes) return launch_sched_q<false, BLOCK, FMODE, MULTI, true>(S, P, T, result, ctr, next, n_blocks, lds, st, rec);
+  return launch_sched_q<COUNT, BLOCK, FMODE, MULTI, false>(S, P, T, result, ctr, next, n_blocks, lds, st, rec);
 }
 
 template <bool COUNT, int BLOCK, int FMODE>
 static hipError_t launch_sched_m(const DevScene& S, const FrameParams& P, const FrameUniforms* T, float4* result, DevCounters* ctr,
-                                 unsigned int* next, int n_blocks, size_t lds, hipStream_t st) {
-  return P.num_rays > 1 ? launch_sched_t<COUNT, BLOCK, FMODE, true>(S, P, T, result, ctr, next, n_blocks, lds, st)
-                        : launch_sched_t<COUNT, BLOCK, FMODE, false>(S, P, T, result, ctr, next, n_blocks, lds, st);
+                                 unsigned int* next, int n_blocks, size_t lds, hipStream_t st, TraceLaunchRecord* rec) {
+  return P.num_rays > 1 ? launch_sched_t<COUNT, BLOCK, FMODE, true>(S, P, T, result, ctr, next, n_blocks, lds, st, rec)
+                        : launch_sched_t<COUNT, BLOCK, FMODE, false>(S, P, T, result, ctr, next, n_blocks, lds, st, rec);
 }
 
 template <bool COUNT, int BLOCK>
 static hipError_t launch_sched_b(const DevScene& S, const FrameParams& P, const FrameUniforms* T, float4* result, DevCounters* ctr,
-                                 unsigned int* next, int n_blocks, size_t lds, int front_mode, hipStream_t st) {
-  if (front_mode == 3) return launch_sched_m<COUNT, BLOCK, 3>(S, P, T, result, ctr, next, n_blocks, lds, st);
-  if (front_mode == 2) return launch_sched_m<COUNT, BLOCK, 2>(S, P, T, result, ctr, next, n_blocks, lds, st);
-  if (front_mode == 1) return launch_sched_m<COUNT, BLOCK, 1>(S, P, T, result, ctr, next, n_blocks, lds, st);
-  return launch_sched_m<COUNT, BLOCK, 0>(S, P, T, result, ctr, next, n_blocks, lds, st);
+                                 unsigned int* next, int n_blocks, size_t lds, int front_mode, hipStream_t st, TraceLaunchRecord* rec) {
+  if (front_mode == 3) return launch_sched_m<COUNT, BLOCK, 3>(S, P, T, result, ctr, next, n_blocks, lds, st, rec);
+  if (front_mode == 2) return launch_sched_m<COUNT, BLOCK, 2>(S, P, T, result, ctr, next, n_blocks, lds, st, rec);
+  if (front_mode == 1) return launch_sched_m<COUNT, BLOCK, 1>(S, P, T, result, ctr, next, n_blocks, lds, st, rec);
+  return launch_sched_m<COUNT, BLOCK, 0>(S, P, T, result, ctr, next, n_blocks, lds, st, rec);
 }
 
 hipError_t launch_sched(const DevScene& S, const FrameParams& P, const FrameUniforms* T, float4* result, DevCounters* ctr,
-                        unsigned int* next, int n_blocks, int front_mode, bool count, hipStream_t st) {
+                        unsigned int* next, int n_blocks, int front_mode, bool count, hipStream_t st, TraceLaunchRecord* rec) {
   if (n_blocks <= 0) return hipSuccess;
   if (P.block_threads != 64 && P.block_threads != 256) return hipErrorInvalidValue;   // independent waves; a workgroup shares the LDS top-of-tree copy
   if (P.n_frames < 1 || P.n_frames > kMaxFramesPerLaunch) return hipErrorInvalidValue;
@@ -2177,41 +2168,36 @@ hipError_t launch_sched(const DevScene& S, const FrameParams& P, const FrameUnif
   if (e != hipSuccess) return e;
   size_t lds = sched_lds_bytes(S, P);
   if (P.top_nodes <= 0 && front_mode == 1) front_mode = 0;
-  if (P.block_threads == 64) return count ? launch_sched_b<true, 64>(S, P, T, result, ctr, next, n_blocks, lds, front_mode, st)
-                                          : launch_sched_b<false, 64>(S, P, T, result, ctr, next, n_blocks, lds, front_mode, st);
-  return count ? launch_sched_b<true, 256>(S, P, T, result, ctr, next, n_blocks, lds, front_mode, st)
-               : launch_sched_b<false, 256>(S, P, T, result, ctr, next, n_blocks, lds, front_mode, st);
+  if (P.block_threads == 64) return count ? launch_sched_b<true, 64>(S, P, T, result, ctr, next, n_blocks, lds, front_mode, st, rec)
+                                          : launch_sched_b<false, 64>(S, P, T, result, ctr, next, n_blocks, lds, front_mode, st, rec);
+  return count ? launch_sched_b<true, 256>(S, P, T, result, ctr, next, n_blocks, lds, front_mode, st, rec)
+               : launch_sched_b<false, 256>(S, P, T, result, ctr, next, n_blocks, lds, front_mode, st, rec);
 }
 
 template <bool COUNT, int FMODE, bool MULTI>
 static hipError_t launch_serve_t(const DevScene& S, const FrameParams& P, const FrameUniforms* T, float4* result, DevCounters* ctr,
-                                 unsigned int* next, float4* mail, int n_blocks, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_serve<COUNT, 256, FMODE, MULTI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((k_serve<COUNT, 256, FMODE, MULTI>), dim3(n_blocks), dim3(256), lds, st, S, P, T, result, ctr, next, mail);
-  note_launch(n_blocks, 256, lds, "k_serve<%s, 256, %d, %s>", tf(COUNT), FMODE, tf(MULTI));
-  return hipGetLastError();
+                                 unsigned int* next, float4* mail, int n_blocks, size_t lds, hipStream_t st, TraceLaunchRecord* rec) {
+  return launch_traced(named(rec, "k_serve<%s, 256, %d, %s>", tf(COUNT), FMODE, tf(MULTI)), k_serve<COUNT, 256, FMODE, MULTI>, n_blocks, 256, lds, st,
+                       S, P, T, result, ctr, next, mail);
 }
 
 template <bool COUNT, int FMODE>
 static hipError_t launch_serve_m(const DevScene& S, const FrameParams& P, const FrameUniforms* T, float4* result, DevCounters* ctr,
-                                 unsigned int* next, float4* mail, int n_blocks, size_t lds, hipStream_t st) {
-  return P.num_rays > 1 ? launch_serve_t<COUNT, FMODE, true>(S, P, T, result, ctr, next, mail, n_blocks, lds, st)
-                        : launch_serve_t<COUNT, FMODE, false>(S, P, T, result, ctr, next, mail, n_blocks, lds, st);
+                                 unsigned int* next, float4* mail, int n_blocks, size_t lds, hipStream_t st, TraceLaunchRecord* rec) {
+  return P.num_rays > 1 ? launch_serve_t<COUNT, FMODE, true>(S, P, T, result, ctr, next, mail, n_blocks, lds, st, rec)
+                        : launch_serve_t<COUNT, FMODE, false>(S, P, T, result, ctr, next, mail, n_blocks, lds, st, rec);
 }
 
 template <bool COUNT>
 static hipError_t launch_serve_b(const DevScene& S, const FrameParams& P, const FrameUniforms* T, float4* result, DevCounters* ctr,
-                                 unsigned int* next, float4* mail, int n_blocks, size_t lds, int front_mode, hipStream_t st) {
-  if (front_mode == 2) return launch_serve_m<COUNT, 2>(S, P, T, result, ctr, next, mail, n_blocks, lds, st);
-  if (front_mode == 1) return launch_serve_m<COUNT, 1>(S, P, T, result, ctr, next, mail, n_blocks, lds, st);
-  return launch_serve_m<COUNT, 0>(S, P, T, result, ctr, next, mail, n_blocks, lds, st);
+                                 unsigned int* next, float4* mail, int n_blocks, size_t lds, int front_mode, hipStream_t st, TraceLaunchRecord* rec) {
+  if (front_mode == 2) return launch_serve_m<COUNT, 2>(S, P, T, result, ctr, next, mail, n_blocks, lds, st, rec);
+  if (front_mode == 1) return launch_serve_m<COUNT, 1>(S, P, T, result, ctr, next, mail, n_blocks, lds, st, rec);
+  return launch_serve_m<COUNT, 0>(S, P, T, result, ctr, next, mail, n_blocks, lds, st, rec);
 }
 
 hipError_t launch_serve(const DevScene& S, const FrameParams& P, const FrameUniforms* T, float4* result, DevCounters* ctr,
-                        unsigned int* next, float4* mail, int n_blocks, int front_mode, bool count, hipStream_t st) {
+                        unsigned int* next, float4* mail, int n_blocks, int front_mode, bool count, hipStream_t st, TraceLaunchRecord* rec) {
   if (n_blocks <= 0) return hipSuccess;
   if (P.block_threads != 256 || !P.serve || !mail) return hipErrorInvalidValue;
   if (P.n_frames < 1 || P.n_frames > kMaxFramesPerLaunch) return hipErrorInvalidValue;
@@ -2220,8 +2206,8 @@ hipError_t launch_serve(const DevScene& S, const FrameParams& P, const FrameUnif
   if (e != hipSuccess) return e;
   size_t lds = sched_lds_bytes(S, P);
   if (P.top_nodes <= 0 && front_mode == 1) front_mode = 0;
-  return count ? launch_serve_b<true>(S, P, T, result, ctr, next, mail, n_blocks, lds, front_mode, st)
-               : launch_serve_b<false>(S, P, T, result, ctr, next, mail, n_blocks, lds, front_mode, st);
+  return count ? launch_serve_b<true>(S, P, T, result, ctr, next, mail, n_blocks, lds, front_mode, st, rec)
+               : launch_serve_b<false>(S, P, T, result, ctr, next, mail, n_blocks, lds, front_mode, st, rec);
 }
 
 size_t pool_lds_bytes(const FrameParams& P, int k) {
@@ -2232,30 +2218,22 @@ size_t pool_lds_bytes(const FrameParams& P, int k) {
 
 template <int K>
 static hipError_t launch_pool_k(const DevScene& S, const FrameParams& P, float4* result, DevCounters* ctr, unsigned int* next,
-                                int n_blocks, bool count, hipStream_t st) {
-  size_t lds = pool_lds_bytes(P, K);
-  if (lds > 64 * 1024) {            // above the default dynamic-LDS limit the kernel attribute has to be raised
-    hipError_t e = count ? hipFuncSetAttribute((const void*)k_pool<true, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                         : hipFuncSetAttribute((const void*)k_pool<false, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  if (count) hipLaunchKernelGGL((k_pool<true, K>), dim3(n_blocks), dim3(64), lds, st, S, P, result, ctr, next);
-  else hipLaunchKernelGGL((k_pool<false, K>), dim3(n_blocks), dim3(64), lds, st, S, P, result, ctr, next);
-  note_launch(n_blocks, 64, lds, "k_pool<%s, %d>", tf(count), K);
-  return hipGetLastError();
+                                int n_blocks, bool count, hipStream_t st, TraceLaunchRecord* rec) {
+  return launch_traced(named(rec, "k_pool<%s, %d>", tf(count), K), count ? k_pool<true, K> : k_pool<false, K>, n_blocks, 64, pool_lds_bytes(P, K), st,
+                       S, P, result, ctr, next);
 }
 
 hipError_t launch_pool(const DevScene& S, const FrameParams& P, float4* result, DevCounters* ctr, unsigned int* next,
-                       int n_blocks, int k, bool count, hipStream_t st) {
+                       int n_blocks, int k, bool count, hipStream_t st, TraceLaunchRecord* rec) {
   if (n_blocks <= 0) return hipSuccess;
   if (P.width > 65535 || P.height > 65535 || k < 1 || k > 4) return hipErrorInvalidValue;   // pixel packed as y << 16 | x
   hipError_t e = hipMemsetAsync(next, 0, kWorkShards * 32 * sizeof(unsigned int), st);
   if (e != hipSuccess) return e;
   switch (k) {
-    case 1: return launch_pool_k<1>(S, P, result, ctr, next, n_blocks, count, st);
-    case 2: return launch_pool_k<2>(S, P, result, ctr, next, n_blocks, count, st);
-    case 3: return launch_pool_k<3>(S, P, result, ctr, next, n_blocks, count, st);
-    default: return launch_pool_k<4>(S, P, result, ctr, next, n_blocks, count, st);
+    case 1: return launch_pool_k<1>(S, P, result, ctr, next, n_blocks, count, st, rec);
+    case 2: return launch_pool_k<2>(S, P, result, ctr, next, n_blocks, count, st, rec);
+    case 3: return launch_pool_k<3>(S, P, result, ctr, next, n_blocks, count, st, rec);
+    default: return launch_pool_k<4>(S, P, result, ctr, next, n_blocks, count, st, rec);
   }
 }
 
