@@ -304,8 +304,9 @@ URT_API int urt_denoise(urt_context* ctx, urt_handle src, urt_handle dst, urt_ha
  *    dst, or src == dst.  URT_ERR_INVALID_HANDLE: a required handle 0 or unknown (motion may be 0).  URT_ERR_UNBOUND (urt_reproject):
  *    _CameraToWorld or _CameraInverseProjection never set.  Every argument is checked first: on any error nothing is written and nothing
  *    is enqueued.
- * Moving objects have no motion vectors: a MeshObject moved by a refit keeps its history only where the id, normal and plane tests still
- * accept it.  The defaults below were chosen with the quality test of tests/test_gpu_reproject.py (DESIGN.md "Temporal reprojection"). */
+ * The defaults below were chosen with the quality test of tests/test_gpu_reproject.py (DESIGN.md "Temporal reprojection").
+ * urt_reproject projects the CURRENT world position of a pixel's hit point: right for a camera move over a still scene.  For objects that
+ * have moved since the history was accumulated, urt_reproject_objects (below) projects the point where it WAS. */
 typedef struct urt_ReprojectParams {     /* 80 bytes */
   float prev_world_to_clip[16];  /* the PREVIOUS camera's projection * worldToCamera, Unity Matrix4x4 memory order (column-major), the
                                     order urt_shader_set_matrix takes.  A Unity host: _camera.projectionMatrix *
@@ -329,6 +330,46 @@ typedef struct urt_ReprojectImages {     /* 11 handles, 88 bytes */
 
 URT_API int urt_reproject(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params);
 URT_API int urt_blit_add_history(urt_context* ctx, urt_handle src, urt_handle dst, urt_handle count, float max_history);
+
+/* Per-object motion: urt_reproject for a scene whose MeshObjects and spheres have moved between the previous and the current feature
+ * buffers (a refit, csrc/refit.hip).  A motion table is an ordinary buffer of urt_buffer_create with stride 48 whose entry i is the
+ * urt_ObjectMotion (urt_types.h) of MeshObject i (mesh_motion) or of sphere i (sphere_motion): the affine map a[12] that takes a point of
+ * the object in the CURRENT world to where it was in the PREVIOUS world.  A host fills the tables as it fills _MeshObjects;
+ * urt_host_mesh_motion / urt_host_sphere_motion (below) compute the entries from the previous and the current object lists.  Motions
+ * are meant to be rigid, optionally with uniform scale (normals are carried by the linear part, not by its inverse transpose).
+ *
+ * Arithmetic (normative), as urt_reproject's; only what differs:
+ *  - moved pixel: a surface pixel with k == 3 (triangle) looks up mesh_motion[o], with k == 2 (sphere) sphere_motion[o], o = bits(id.x).
+ *    The ground plane (k == 1), any other kind and the sky never move.  The pixel is MOVED when its table is given (handle != 0) and the
+ *    twelve floats of its entry are not bit for bit the identity (1,0,0, 0,1,0, 0,0,1, 0,0,0).  A pixel that is not moved follows
+ *    urt_reproject's steps exactly, operation for operation.  o outside 0 .. count-1 of a given table (count: the buffer's): the pixel
+ *    has no history, as a pixel of no class in step 1 (colour, count and motion are 0).
+ *  - position: P'.r = ((a[r]*P.x + a[3+r]*P.y) + a[6+r]*P.z) + a[9+r], r = 0..2.  A moved pixel uses P' in place of P in step 2.
+ *  - normal: n'.r = (a[r]*n.x + a[3+r]*n.y) + a[6+r]*n.z, L = f_sqrt((n'.x*n'.x + n'.y*n'.y) + n'.z*n'.z) (f_sqrt of urt_math.h,
+ *    correctly rounded on both sides).  L keeps the tests below free of the motion's scale without a division.
+ *    A moved pixel has no history (as above: colour, count and motion are 0) unless P' is finite, L > 0 and L is finite.
+ *  - tap tests of a moved pixel, evaluated in the previous frame: kind, id, prev_hit.w, count and colour as in step 3, and
+ *      (n'.x*m.x + n'.y*m.y) + n'.z*m.z >= normal_threshold * L,
+ *      fabsf((n'.x*(Q.x-P'.x) + n'.y*(Q.y-P'.y)) + n'.z*(Q.z-P'.z)) <= (plane_threshold * z) * L      (z = hit.w, the current distance).
+ *  - count: after max_history's clamp, count = fminf(count, moved_max_history) on a moved pixel when moved_max_history > 0.  (Lighting
+ *    on a moved object is stale - reflections, the sky it faces - so a host wants it to re-converge faster than the rest.)
+ *  - motion image: unchanged in form, (qx - x, qy - y, S, 0); with P' it holds true screen-space motion vectors.
+ * With motion == NULL, with both handles 0, or with tables that hold only identity entries, the three outputs equal urt_reproject's bit
+ * for bit.  Calls and errors as urt_reproject (an observer: deferred frames submitted first, the tables uploaded and one kernel enqueued
+ * on the context's stream, no synchronisation; the scene is not prepared, urt_counters are not changed; every argument is checked first).
+ * motion == NULL is allowed and means both handles 0 and moved_max_history 0.  URT_ERR_INVALID_HANDLE: a table handle that is not 0 and
+ * unknown.  URT_ERR_INVALID_ARGUMENT: a table whose stride is not 48; nonzero flags; moved_max_history NaN, negative or in (0, 1).
+ * What remains untracked: shadows and reflections CAST BY a moved object onto other surfaces (those pixels keep their history and
+ * converge to the new lighting at the rate max_history allows). */
+typedef struct urt_ReprojectMotion {     /* 24 bytes */
+  urt_handle mesh_motion;        /* buffer of urt_ObjectMotion (stride 48), entry i = MeshObject i; 0 = no mesh has moved */
+  urt_handle sphere_motion;      /* the same for spheres; 0 = no sphere has moved */
+  float moved_max_history;       /* 0 = none, else >= 1: extra clamp of the reprojected count on moved-object pixels */
+  int32_t flags;                 /* 0 (reserved) */
+} urt_ReprojectMotion;
+
+URT_API int urt_reproject_objects(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params,
+                                  const urt_ReprojectMotion* motion);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 typedef struct urt_counters {
@@ -471,6 +512,14 @@ URT_API int urt_host_build_object_bvh(const urt_BVHNode* leaves, int n_objects, 
  * candidate list is aliased, RM:670), lone trees joined under a copy of their own root, layers woven into the implicit heap.
  * Only the order of exact ties in the ranking sort (an unstable List.Sort in the reference) is this library's choice (stable). */
 URT_API int urt_host_build_object_bvh_pairing(const urt_BVHNode* leaves, int n_objects, urt_BVHNode* out_nodes, int capacity);
+/* The motion tables of urt_reproject_objects from the object lists before and after a move (n entries of _MeshObjects / _Spheres
+ * each), entry i = current world -> previous world of object i.  Mesh: prevL * inverse(curL) of the two localToWorldMatrix fields
+ * (their affine 3 x 4 parts), computed in float64 and rounded once to float32.  Sphere: linear part (r_prev / r_cur) * I, translation
+ * c_prev - (r_prev / r_cur) * c_cur.  An object whose previous and current fields (the matrix; position and radius) are bit for bit
+ * equal gets the exact identity bits, which is what urt_reproject_objects calls "not moved".  A singular curL or r_cur <= 0 gives an
+ * all-NaN entry (that object then has no history) and is not an error.  URT_ERR_INVALID_ARGUMENT: n < 0, or a NULL pointer with n > 0. */
+URT_API int urt_host_mesh_motion(const void* prev_mesh_objects, const void* cur_mesh_objects, int n, urt_ObjectMotion* out);
+URT_API int urt_host_sphere_motion(const void* prev_spheres, const void* cur_spheres, int n, urt_ObjectMotion* out);
 URT_API const char* urt_host_last_error(void);
 
 /* ---- host-side image I/O (no GPU needed) ---------------------------------- */

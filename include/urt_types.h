@@ -8,6 +8,8 @@
 // The ray-query records (urt_ray_query, urt.h) are the library's own: 16-byte aligned rows for coalesced dwordx4 loads and stores.
 //   Ray             32 B
 //   RayHit          48 B
+// The per-object motion entries of urt_reproject_objects (urt.h) are the library's own too: 48 bytes, three dwordx4 loads.
+//   ObjectMotion    48 B
 #pragma once
 #include <stdint.h>
 
@@ -58,6 +60,11 @@ typedef struct urt_RayHit {
   int32_t primitive;            /* @36 triangle: its first index slot in _Indices (i of RS:243); -1 otherwise */
   float u, v;                   /* @40 triangle: barycentrics of the hit; 0 otherwise */
 } urt_RayHit;
+
+typedef struct urt_ObjectMotion {
+  float a[12];                  /* @0  current world -> previous world, affine: columns of the linear part a[0..2], a[3..5], a[6..8], then
+                                       the translation a[9..11]:  P'.r = ((a[r]*P.x + a[3+r]*P.y) + a[6+r]*P.z) + a[9+r],  r = 0..2 */
+} urt_ObjectMotion;
 #pragma pack(pop)
 
 #define URT_STRIDE_PARAMS 40
@@ -68,6 +75,7 @@ typedef struct urt_RayHit {
 #define URT_STRIDE_INDEX 4
 #define URT_STRIDE_RAY 32
 #define URT_STRIDE_RAYHIT 48
+#define URT_STRIDE_OBJECTMOTION 48
 
 #ifdef __cplusplus
 }
@@ -77,4 +85,5 @@ static_assert(sizeof(urt_Sphere) == URT_STRIDE_SPHERE, "RM:44");
 static_assert(sizeof(urt_BVHNode) == URT_STRIDE_BVHNODE, "RM:45");
 static_assert(sizeof(urt_Ray) == URT_STRIDE_RAY, "urt_Ray");
 static_assert(sizeof(urt_RayHit) == URT_STRIDE_RAYHIT, "urt_RayHit");
+static_assert(sizeof(urt_ObjectMotion) == URT_STRIDE_OBJECTMOTION, "urt_ObjectMotion");
 #endif

@@ -112,6 +112,20 @@ internal static class UrtNative {
     internal const float ReprojectDefaultMaxHistory = 64.0f, ReprojectDefaultNormalThreshold = 0.9f, ReprojectDefaultPlaneThreshold = 0.02f;
     [DllImport(Lib)] internal static extern int urt_reproject(IntPtr ctx, in ReprojectImages images, in ReprojectParams p);
     [DllImport(Lib)] internal static extern int urt_blit_add_history(IntPtr ctx, ulong src, ulong dst, ulong count, float maxHistory);
+    // per-object motion (include/urt.h urt_reproject_objects): tables are buffers of urt_buffer_create with stride 48, entry i = object i
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct ObjectMotion {                          // urt_ObjectMotion, 48 B: current world -> previous world
+        [MarshalAs(UnmanagedType.ByValArray, SizeConst = 12)]
+        public float[] a;                                   // three columns of the linear part, then the translation
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct ReprojectMotion {                       // urt_ReprojectMotion, 24 B
+        public ulong meshMotion, sphereMotion;              // buffer handles; 0 = no object of that kind has moved
+        public float movedMaxHistory;                       // 0 = none, else >= 1
+        public int flags;                                   // 0
+    }
+    internal const int ObjectMotionStride = 48;
+    [DllImport(Lib)] internal static extern int urt_reproject_objects(IntPtr ctx, in ReprojectImages images, in ReprojectParams p, in ReprojectMotion motion);
 
     // ---- measurement ----------------------------------------------------------------------------------------------------
     [StructLayout(LayoutKind.Sequential)]
@@ -171,6 +185,8 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_host_dump_bvh(string path, IntPtr nodes, int nNodes, int depth, float[] rayStart3, float[] rayEnd3, out int lines);
     [DllImport(Lib)] internal static extern int urt_host_dump_normals(string path, IntPtr meshObjects, int nMeshes, float[] vertices, int nVertices, int[] indices, int nIndices, float[] normals, int nNormals, out int lines);
     [DllImport(Lib)] internal static extern int urt_debug_refit_stats(IntPtr ctx, out ulong refittedMeshes, out ulong incrementalPreparations);
+    [DllImport(Lib)] internal static extern int urt_host_mesh_motion(IntPtr prevMeshObjects, IntPtr curMeshObjects, int n, IntPtr outMotion);   // 48 B per entry
+    [DllImport(Lib)] internal static extern int urt_host_sphere_motion(IntPtr prevSpheres, IntPtr curSpheres, int n, IntPtr outMotion);
     [DllImport(Lib)] internal static extern int urt_host_build_object_bvh_pairing(IntPtr leaves, int nObjects, IntPtr outNodes, int capacity);   // RM:459-722's pairing builder, restated
     [DllImport(Lib)] internal static extern int urt_host_resize_rgba(float[] src, int width, int height, [Out] float[] dst, int newWidth, int newHeight);
     [DllImport(Lib)] internal static extern IntPtr urt_host_last_error();          // const char* (thread-local, like the two below)

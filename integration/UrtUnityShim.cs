@@ -147,6 +147,69 @@ public static class UrtTemporal {
                                                 planeThreshold = planeThreshold, flags = 0 };
         UrtDevice.Check(UrtNative.urt_reproject(ctx, in im, in p));
     }
+    // ---- objects that move (include/urt.h urt_reproject_objects) ----
+    static ulong meshTable, sphereTable;
+    static int meshTableCount, sphereTableCount;
+    static IntPtr tableCtx = IntPtr.Zero;
+    // the motion table of one kind of object: urt_host_*_motion over the pinned previous and current lists -> a stride-48 buffer
+    static ulong Table<T>(IntPtr ctx, List<T> prev, List<T> cur, bool mesh, ref ulong handle, ref int count) where T : struct {
+        if (prev == null || cur == null || cur.Count == 0) return 0;
+        if (prev.Count != cur.Count) throw new ArgumentException("UrtTemporal.MoveObjects: the previous and the current list differ in length");
+        int n = cur.Count;
+        var table = new float[12 * n];
+        GCHandle a = GCHandle.Alloc(prev.ToArray(), GCHandleType.Pinned), b = GCHandle.Alloc(cur.ToArray(), GCHandleType.Pinned),
+                 o = GCHandle.Alloc(table, GCHandleType.Pinned);
+        try {
+            int rc = mesh ? UrtNative.urt_host_mesh_motion(a.AddrOfPinnedObject(), b.AddrOfPinnedObject(), n, o.AddrOfPinnedObject())
+                          : UrtNative.urt_host_sphere_motion(a.AddrOfPinnedObject(), b.AddrOfPinnedObject(), n, o.AddrOfPinnedObject());
+            if (rc != 0) throw new InvalidOperationException("urt_host_" + (mesh ? "mesh" : "sphere") + "_motion: " +
+                                                             Marshal.PtrToStringAnsi(UrtNative.urt_host_last_error()));
+            if (handle != 0 && (tableCtx != ctx || count != n)) {
+                if (tableCtx == ctx) UrtDevice.Check(UrtNative.urt_buffer_release(ctx, handle));
+                handle = 0;
+            }
+            if (handle == 0) UrtDevice.Check(UrtNative.urt_buffer_create(ctx, n, UrtNative.ObjectMotionStride, out handle));
+            count = n;
+            UrtDevice.Check(UrtNative.urt_buffer_set_data(ctx, handle, o.AddrOfPinnedObject(), n));
+        } finally { a.Free(); b.Free(); o.Free(); }
+        return handle;
+    }
+    /// Objects (and optionally the camera) move while the accumulated image is kept.  The steps of RayTraceMaster.MoveObjects of the Python
+    /// mirror: (a) renderFeatureBuffers(prevHit, prevNormal, prevId) while the old scene and camera are still bound, (b) applyEdits(): the
+    /// host changes its _meshObjects / _spheres, rebuilds the object-level heaps and re-uploads through SetData as RebuildTrees does, and
+    /// sets the new camera matrices if the camera moves too, (c) renderFeatureBuffers(hit, normal, id), (d) the two tables from the lists
+    /// before and after (a list pair that is null means no object of that kind has moved), (e) urt_reproject_objects.  prevViewProj is
+    /// the projectionMatrix * worldToCameraMatrix the history was accumulated under.  The host then swaps (color, count) with its
+    /// _converged / count pair as after Reproject.  MeshObject / Sphere are the host's own sequential structs (RM:82-86, RM:116-119).
+    public static void MoveObjects<TMesh, TSphere>(List<TMesh> prevMeshObjects, List<TMesh> meshObjects, List<TSphere> prevSpheres, List<TSphere> spheres,
+                                                   Action applyEdits, Action<IntPtr, IntPtr, IntPtr> renderFeatureBuffers,
+                                                   IntPtr prevColor, IntPtr prevCount, IntPtr prevHit, IntPtr prevNormal, IntPtr prevId,
+                                                   IntPtr hit, IntPtr normal, IntPtr id, IntPtr color, IntPtr count, IntPtr motion, int width, int height,
+                                                   Matrix4x4 prevViewProj, float maxHistory = 64.0f, float normalThreshold = 0.9f, float planeThreshold = 0.02f,
+                                                   float movedMaxHistory = 0.0f) where TMesh : struct where TSphere : struct {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtTemporal: reproject on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        List<TMesh> meshBefore = prevMeshObjects != null ? new List<TMesh>(prevMeshObjects) : null;      // copies: applyEdits may edit in place
+        List<TSphere> spheresBefore = prevSpheres != null ? new List<TSphere>(prevSpheres) : null;
+        renderFeatureBuffers(prevHit, prevNormal, prevId);                                               // (a)
+        applyEdits();                                                                                    // (b)
+        renderFeatureBuffers(hit, normal, id);                                                           // (c)
+        var mo = new UrtNative.ReprojectMotion {                                                         // (d)
+            meshMotion = Table(ctx, meshBefore, meshObjects, true, ref meshTable, ref meshTableCount),
+            sphereMotion = Table(ctx, spheresBefore, spheres, false, ref sphereTable, ref sphereTableCount),
+            movedMaxHistory = movedMaxHistory, flags = 0 };
+        tableCtx = ctx;
+        var m = new float[16];
+        for (int k = 0; k < 16; k++) m[k] = prevViewProj[k];
+        var im = new UrtNative.ReprojectImages {
+            prevColor = Wrap(ctx, prevColor, width, height), prevCount = Wrap(ctx, prevCount, width, height),
+            prevHit = Wrap(ctx, prevHit, width, height), prevNormal = Wrap(ctx, prevNormal, width, height), prevId = Wrap(ctx, prevId, width, height),
+            hit = Wrap(ctx, hit, width, height), normal = Wrap(ctx, normal, width, height), id = Wrap(ctx, id, width, height),
+            color = Wrap(ctx, color, width, height), count = Wrap(ctx, count, width, height), motion = Wrap(ctx, motion, width, height) };
+        var p = new UrtNative.ReprojectParams { prevWorldToClip = m, maxHistory = maxHistory, normalThreshold = normalThreshold,
+                                                planeThreshold = planeThreshold, flags = 0 };
+        UrtDevice.Check(UrtNative.urt_reproject_objects(ctx, in im, in p, in mo));                       // (e)
+    }
     public static void BlitAddHistory(IntPtr src, IntPtr dst, IntPtr count, int width, int height, float maxHistory = 64.0f) {
         if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtTemporal: blend on one rank's context (urt_group_context)");
         IntPtr ctx = UrtDevice.Handle;

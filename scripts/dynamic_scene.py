@@ -1,12 +1,42 @@
 # Scene-preparation time (SetData -> ready device scene, host wall clock reported by the library) for the reference's dynamic-scene
 # protocol (RM:215-230: any move re-uploads EVERY buffer): nothing moved / one MeshObject moved / all moved, with the host SAH builder
 # (per-MeshObject BVH cache) and with the three GPU builders (1 Karras radix tree, 2 depth-budgeted radix tree, 3 binned SAH).   python scripts/dynamic_scene.py [C4 C5]
+# --move-objects: instead, RayTraceMaster.MoveObjects with temporal accumulation on (default builder): the whole step from the edits to the
+# reprojected history (previous feature buffers, re-upload + refit, current feature buffers, motion tables, urt_reproject_objects), host wall
+# clock to GPU-done, for one MeshObject moved and for all of them, and the share of the image that keeps its history.
 import sys, time
 sys.path.insert(0, '.')
 import numpy as np
 from unityraytracer_amd import Context, RayTraceMaster, scenes
 ctx = Context(0)
-for name in (sys.argv[1:] or ["C4", "C5"]):
+names = [a for a in sys.argv[1:] if not a.startswith("--")] or ["C4", "C5"]
+if "--move-objects" in sys.argv:
+    for name in names:
+        sc = scenes.CONFIGS[name](640, 360)
+        m = RayTraceMaster(ctx, sc)
+        m.EnableTemporalAccumulation()
+        for _ in range(8):
+            m.OnRenderImage()
+        ctx.synchronize()
+        out = []
+        for label, ks in (("one moved", [len(sc.mesh_objects) - 1]), ("all moved", range(len(sc.mesh_objects))), ("all moved again", range(len(sc.mesh_objects)))):
+            edits = {}
+            for k in ks:
+                mat = np.asarray(sc.mesh_objects[k]["localToWorldMatrix"], np.float32).copy(); mat[12] += 0.05; edits[k] = mat
+            t0 = time.perf_counter()
+            m.MoveObjects(edits)
+            t_host = (time.perf_counter() - t0) * 1e3
+            ctx.synchronize()
+            wall = (time.perf_counter() - t0) * 1e3
+            kept = float((m._tcount.GetPixels()[..., 0] > 0).mean())
+            out.append(f"{label}: host {t_host:.1f} ms, edits-to-GPU-done {wall:.1f} ms, {kept:.3f} of the pixels keep history")
+            for _ in range(4):
+                m.OnRenderImage()
+            ctx.synchronize()
+        print(f"{name} {sc.n_triangles} triangles, {len(sc.mesh_objects)} MeshObjects, 640x360, MoveObjects with temporal accumulation: " + "; ".join(out), flush=True)
+        m.OnDisable()
+    sys.exit(0)
+for name in names:
     sc = scenes.CONFIGS[name](640, 360)
     for builder in (0, 1, 2, 3):
         ctx.set_option("blas_builder", builder)

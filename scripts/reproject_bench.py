@@ -8,11 +8,16 @@ repeats (median and spread reported):
   fused20_present  20 frames of C1 (16 spheres, 1 bounce), each dispatched, blended with urt_blit_add_history and presented, submitted
                    as one batch (frames_per_launch 20): the per-launch time minus that of the same 20 dispatches without the blends and
                    presents, i.e. the one fused pass, per launch.
+With --motion, instead of the blend cases (urt_reproject_objects, per-object motion tables), `reproject` and these alternate in every
+repeat, so that the three are compared under the same conditions:
+  objects_static   urt_reproject_objects with tables that hold only identity entries (a static scene that still passes its tables);
+  objects_moved    the same with every wall ("mesh") entry a small rigid motion: every mesh pixel loads its entry and takes the moved path
+                   (`moved_share` is the share of such pixels in the image).
 Bytes per pixel are the compulsory traffic (reproject: 48 B of current AOVs, 80 B of previous history and AOVs, 48 B out; blend: 64 B;
 fused n frames with a present: 16 n + 64 B) and `of_6p3TBs` the fraction of the ~6.3 TB/s a float4 copy reaches on the chip.  Kernel times
 come from a separate `rocprofv3 --kernel-trace --stats` run of this script.
 
-    python scripts/reproject_bench.py [--sizes 1080p,2160p] [--iters 20] [--repeats 5] [--json out.json]
+    python scripts/reproject_bench.py [--sizes 1080p,2160p] [--iters 20] [--repeats 5] [--motion] [--json out.json]
 """
 import argparse
 import json
@@ -28,7 +33,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402  (before the library: one HIP runtime in the process, tests/conftest.py)
 
 from unityraytracer_amd import Context, RayTraceMaster, scenes  # noqa: E402
-from unityraytracer_amd.unity_api import ComputeShader, RenderTexture  # noqa: E402
+from unityraytracer_amd.unity_api import ComputeBuffer, ComputeShader, RenderTexture  # noqa: E402
 
 SIZES = {"1080p": (1920, 1080), "2160p": (3840, 2160)}
 PEAK = 6.3e12
@@ -63,6 +68,7 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--motion", action="store_true", help="time urt_reproject_objects (static and all-moved tables) next to urt_reproject")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -87,6 +93,31 @@ def main():
         sh.SetMatrix("_CameraToWorld", cam_b[0])
         sh.SetMatrix("_CameraInverseProjection", cam_b[1])
         M = scenes.world_to_clip(*cam_a)
+        if args.motion:
+            n = 6                                               # the analytic scene's ids: ground 0, spheres 1..3, walls ("meshes") 4 and 5
+            ident = np.tile(np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], np.float32), (n, 1))
+            moved = ident.copy()
+            a = np.radians(2.0)
+            moved[:, [0, 2, 6, 8]] = (np.cos(a), -np.sin(a), np.sin(a), np.cos(a))        # 2 degrees about y ...
+            moved[:, 9:] = (0.05, 0.0, 0.02)                                              # ... and a small step
+            bufs = {}
+            for key, t in (("ident", ident), ("moved", moved)):
+                bufs[key] = ComputeBuffer(ctx, n, 48)
+                bufs[key].SetData(t)
+            share = float((cur[1][..., 3] == 3).mean())
+            cases = {"reproject": lambda: ctx.reproject(*tex[:10], M, motion=tex[10]),
+                     "objects_static": lambda: ctx.reproject(*tex[:10], M, motion=tex[10], mesh_motion=bufs["ident"], sphere_motion=bufs["ident"]),
+                     "objects_moved": lambda: ctx.reproject(*tex[:10], M, motion=tex[10], mesh_motion=bufs["moved"], sphere_motion=bufs["ident"])}
+            ms = {c: [] for c in cases}
+            for _ in range(args.repeats):                       # alternate the three within every repeat
+                for c, fn in cases.items():
+                    ms[c].append(timed(fn, args.iters, args.warmup))
+            for c in cases:
+                report(name, c, w, h, ms[c], 176, results)
+                results[-1]["moved_share"] = share if c == "objects_moved" else 0.0
+            for t in tex + list(bufs.values()):
+                t.Release()
+            continue
         fn = lambda: ctx.reproject(*tex[:10], M, motion=tex[10])  # noqa: E731
         report(name, "reproject", w, h, [timed(fn, args.iters, args.warmup) for _ in range(args.repeats)], 176, results)
         fn = lambda: ctx.blit_add_history(tex[0], tex[8], tex[9], 64.0)  # noqa: E731

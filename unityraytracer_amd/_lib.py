@@ -21,9 +21,9 @@ ABI_SYMBOLS = [
     "urt_texture_create_external", "urt_texture_set_pixels", "urt_texture_get_pixels", "urt_texture_get_info", "urt_texture_read_begin", "urt_texture_read_end", "urt_texture_read_begin_format", "urt_texture_read_end_format", "urt_texture_release",
     "urt_shader_set_buffer", "urt_shader_set_texture", "urt_shader_set_matrix", "urt_shader_set_vector", "urt_shader_set_float",
     "urt_shader_set_int", "urt_shader_dispatch", "urt_shader_dispatch_rows", "urt_blit_add", "urt_blit", "urt_texture_pack_rows",
-    "urt_texture_unpack_rows", "urt_texture_unpack_rows_on", "urt_texture_pack_rows_rgb", "urt_texture_unpack_rows_rgb", "urt_ray_query", "urt_ray_query_device", "urt_render_aov", "urt_denoise", "urt_reproject", "urt_blit_add_history", "urt_set_option", "urt_get_counters", "urt_reset_counters", "urt_debug_build_blas", "urt_debug_get_blas", "urt_debug_blas_cache_stats",
+    "urt_texture_unpack_rows", "urt_texture_unpack_rows_on", "urt_texture_pack_rows_rgb", "urt_texture_unpack_rows_rgb", "urt_ray_query", "urt_ray_query_device", "urt_render_aov", "urt_denoise", "urt_reproject", "urt_reproject_objects", "urt_blit_add_history", "urt_set_option", "urt_get_counters", "urt_reset_counters", "urt_debug_build_blas", "urt_debug_get_blas", "urt_debug_blas_cache_stats",
     "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_build_walk_table", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
-    "urt_host_build_object_bvh", "urt_host_build_object_bvh_pairing", "urt_host_last_error", "urt_host_load_hdr", "urt_host_write_pfm", "urt_host_write_png", "urt_host_encode_srgb8", "urt_host_srgb8_first_floats",
+    "urt_host_build_object_bvh", "urt_host_build_object_bvh_pairing", "urt_host_mesh_motion", "urt_host_sphere_motion", "urt_host_last_error", "urt_host_load_hdr", "urt_host_write_pfm", "urt_host_write_png", "urt_host_encode_srgb8", "urt_host_srgb8_first_floats",
     "urt_host_resize_rgba", "urt_host_io_last_error", "urt_host_log", "urt_host_log_scene_counts", "urt_host_log_tree_report", "urt_host_dump_bvh", "urt_host_dump_normals",
     "urt_host_debug_last_error",
     "urt_group_create", "urt_group_destroy", "urt_group_size", "urt_group_context", "urt_group_last_error", "urt_group_buffer_create",
@@ -79,6 +79,16 @@ class ReprojectImages(C.Structure):
     """urt_ReprojectImages (include/urt.h), 11 texture handles, 88 B; motion 0 = not wanted."""
     _fields_ = [(n, C.c_uint64) for n in ("prev_color", "prev_count", "prev_hit", "prev_normal", "prev_id", "hit", "normal", "id", "color",
                                           "count", "motion")]
+
+
+class ObjectMotion(C.Structure):
+    """urt_ObjectMotion (include/urt_types.h), 48 B: current world -> previous world, three columns of the linear part, then the translation."""
+    _fields_ = [("a", C.c_float * 12)]
+
+
+class ReprojectMotion(C.Structure):
+    """urt_ReprojectMotion (include/urt.h), 24 B: the two motion-table buffer handles (0 = not moved) of urt_reproject_objects."""
+    _fields_ = [("mesh_motion", C.c_uint64), ("sphere_motion", C.c_uint64), ("moved_max_history", C.c_float), ("flags", C.c_int32)]
 
 
 # the starting values a host passes to urt_reproject / urt_blit_add_history (include/urt.h URT_REPROJECT_DEFAULT_*)
@@ -167,6 +177,7 @@ def load():
         "urt_render_aov": ([vp, u64, u64, u64, u64, i], i),
         "urt_denoise": ([vp, u64, u64, u64, u64, u64, C.POINTER(DenoiseParams)], i),
         "urt_reproject": ([vp, C.POINTER(ReprojectImages), C.POINTER(ReprojectParams)], i),
+        "urt_reproject_objects": ([vp, C.POINTER(ReprojectImages), C.POINTER(ReprojectParams), C.POINTER(ReprojectMotion)], i),
         "urt_blit_add_history": ([vp, u64, u64, u64, f], i),
         "urt_set_option": ([vp, C.c_char_p, i], i),
         "urt_get_counters": ([vp, C.POINTER(Counters)], i),
@@ -188,6 +199,8 @@ def load():
         "urt_host_object_bvh_length": ([i], i),
         "urt_host_build_object_bvh": ([vp, i, vp, i], i),
         "urt_host_build_object_bvh_pairing": ([vp, i, vp, i], i),
+        "urt_host_mesh_motion": ([vp, vp, i, vp], i),
+        "urt_host_sphere_motion": ([vp, vp, i, vp], i),
         "urt_host_last_error": ([], C.c_char_p),
         "urt_host_load_hdr": ([C.c_char_p, pi, pi, vp, C.c_size_t], i),
         "urt_host_write_pfm": ([C.c_char_p, vp, i, i], i),

@@ -245,6 +245,8 @@ struct urt_context {
   float4* q_rays = nullptr; float4* q_out = nullptr; size_t q_cap = 0;
   // urt_denoise: grow-only device scratch of 3 float4 images (guide, two colour images) of dn_cap pixels each
   float4* dn_scratch = nullptr; size_t dn_cap = 0;
+  // urt_reproject_objects: grow-only device copies of the mesh and the sphere motion table, mo_cap[k] bytes each
+  float4* mo_table[2] = {nullptr, nullptr}; size_t mo_cap[2] = {0, 0};
 };
 
 namespace { inline hipStream_t touch(urt_context* ctx) { ctx->main_touched = true; return ctx->stream; } }
@@ -1540,6 +1542,7 @@ int urt_context_destroy(urt_context* ctx) {
   if (ctx->q.counts) (void)hipFree(ctx->q.counts);
   if (ctx->zero_sky) (void)hipFree(ctx->zero_sky);
   if (ctx->dn_scratch) (void)hipFree(ctx->dn_scratch);
+  for (float4* t : ctx->mo_table) if (t) (void)hipFree(t);
   if (ctx->d_counters) (void)hipFree(ctx->d_counters);
   if (ctx->d_next) (void)hipFree(ctx->d_next);
   if (ctx->d_next2) (void)hipFree(ctx->d_next2);
@@ -2211,12 +2214,31 @@ int urt_denoise(urt_context* ctx, urt_handle src, urt_handle dst, urt_handle hit
 /* ---- temporal reprojection ---- */
 // Every argument is checked before anything is submitted: on an error nothing is enqueued.  Then the deferred frames are submitted
 // (prev_color is usually a deferred blend's destination) and k_reproject is enqueued on the main stream.  The scene is not read and the
-// counters are not changed.
-int urt_reproject(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params) {
+// counters are not changed.  with_motion: urt_reproject_objects, whose tables (ComputeBuffers: host copies) are uploaded on the same
+// stream in front of k_reproject_objects; without a table given the call is urt_reproject's, kernel included.
+static int reproject_impl(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params,
+                          const urt_ReprojectMotion* motion, bool with_motion) {
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   if (!images || !params) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: images or params is NULL");
   URT_GUARD_BEGIN
   const urt_ReprojectParams P = *params;
+  urt_ReprojectMotion Mo{};
+  if (with_motion && motion) Mo = *motion;
+  const Buffer* tab[2] = {nullptr, nullptr};
+  if (with_motion) {
+    if (Mo.flags != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: motion flags must be 0");
+    if (!valid_max_history(Mo.moved_max_history)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: moved_max_history must be 0 or >= 1");
+    const urt_handle th[2] = {Mo.mesh_motion, Mo.sphere_motion};
+    for (int k = 0; k < 2; k++) {
+      if (!th[k]) continue;
+      auto it = ctx->buffers.find(th[k]);
+      if (it == ctx->buffers.end())
+        return fail(ctx, URT_ERR_INVALID_HANDLE, std::string("reproject: unknown ") + (k ? "sphere_motion" : "mesh_motion") + " buffer handle");
+      if (it->second.stride != (int)sizeof(urt_ObjectMotion))
+        return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("reproject: the stride of ") + (k ? "sphere_motion" : "mesh_motion") + " is not 48");
+      tab[k] = &it->second;
+    }
+  }
   if (P.flags != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: flags must be 0");
   if (std::isnan(P.normal_threshold) || std::isnan(P.plane_threshold)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: a threshold is NaN");
   if (!valid_max_history(P.max_history)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: max_history must be 0 or >= 1");
@@ -2257,10 +2279,48 @@ int urt_reproject(urt_context* ctx, const urt_ReprojectImages* images, const urt
   std::memcpy(S.c2w, ctx->c2w, sizeof S.c2w);
   std::memcpy(S.invp, ctx->invp, sizeof S.invp);
   S.max_history = P.max_history; S.normal_threshold = P.normal_threshold; S.plane_threshold = P.plane_threshold;
+  if (tab[0] || tab[1]) {
+    ReprojectMotion T{};
+    for (int k = 0; k < 2; k++) {
+      if (!tab[k]) continue;
+      const size_t bytes = (size_t)tab[k]->count * sizeof(urt_ObjectMotion);
+      if (bytes > ctx->mo_cap[k]) {
+        if (ctx->mo_table[k]) {
+          URT_HIP(ctx, hipStreamSynchronize(ctx->stream));             // a queued reprojection may still read the old copy
+          (void)hipFree(ctx->mo_table[k]);
+          ctx->mo_table[k] = nullptr; ctx->mo_cap[k] = 0;
+        }
+        hipError_t e = hipMalloc((void**)&ctx->mo_table[k], bytes);
+        if (e != hipSuccess) {
+          (void)hipGetLastError();
+          ctx->mo_table[k] = nullptr;
+          return fail(ctx, e == hipErrorOutOfMemory ? URT_ERR_OUT_OF_MEMORY : URT_ERR_HIP,
+                      std::string("reproject: motion table allocation: ") + hipGetErrorString(e));
+        }
+        ctx->mo_cap[k] = bytes;
+      }
+      URT_HIP(ctx, hipMemcpyAsync(ctx->mo_table[k], tab[k]->host.data(), bytes, hipMemcpyHostToDevice, touch(ctx)));
+    }
+    T.mesh = tab[0] ? ctx->mo_table[0] : nullptr; T.n_mesh = tab[0] ? tab[0]->count : 0;
+    T.sphere = tab[1] ? ctx->mo_table[1] : nullptr; T.n_sphere = tab[1] ? tab[1]->count : 0;
+    T.moved_max_history = Mo.moved_max_history;
+    for (int k = kInputs; k < kImages; k++) if (t[k]) t[k]->other_writes = true;
+    URT_HIP(ctx, launch_reproject_objects(I, S, T, touch(ctx)));
+    return URT_OK;
+  }
   for (int k = kInputs; k < kImages; k++) if (t[k]) t[k]->other_writes = true;
   URT_HIP(ctx, launch_reproject(I, S, touch(ctx)));
   return URT_OK;
   URT_GUARD_END(ctx)
+}
+
+int urt_reproject(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params) {
+  return reproject_impl(ctx, images, params, nullptr, false);
+}
+
+int urt_reproject_objects(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params,
+                          const urt_ReprojectMotion* motion) {
+  return reproject_impl(ctx, images, params, motion, true);
 }
 
 int urt_set_option(urt_context* ctx, const char* name, int value) {

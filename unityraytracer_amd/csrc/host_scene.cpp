@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -413,6 +414,69 @@ int urt_host_build_object_bvh(const urt_BVHNode* leaves, int n_objects, urt_BVHN
     }
     return URT_OK;
   } catch (...) { return host_fail(URT_ERR_OUT_OF_MEMORY, "CreateBVH: allocation failed"); }
+}
+
+}  // extern "C"
+
+// ---- per-object motion entries of urt_reproject_objects (include/urt.h): current world -> previous world ----
+namespace {
+
+const float kIdentityMotion[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+
+inline void nan_motion(urt_ObjectMotion* e) { for (float& v : e->a) v = std::numeric_limits<float>::quiet_NaN(); }
+
+}  // namespace
+
+extern "C" {
+
+// prevL * inverse(curL) of the affine 3 x 4 parts, in float64 (the inverse by cofactors), rounded once to float32
+int urt_host_mesh_motion(const void* prev_mesh_objects, const void* cur_mesh_objects, int n, urt_ObjectMotion* out) {
+  if (n < 0) return host_fail(URT_ERR_INVALID_ARGUMENT, "mesh_motion: n is negative");
+  if (n > 0 && (!prev_mesh_objects || !cur_mesh_objects || !out)) return host_fail(URT_ERR_INVALID_ARGUMENT, "mesh_motion: a pointer is NULL");
+  const urt_MeshObject* prev = (const urt_MeshObject*)prev_mesh_objects;
+  const urt_MeshObject* cur = (const urt_MeshObject*)cur_mesh_objects;
+  for (int i = 0; i < n; i++) {
+    const float* p = prev[i].localToWorldMatrix;
+    const float* c = cur[i].localToWorldMatrix;
+    if (std::memcmp(p, c, sizeof prev[i].localToWorldMatrix) == 0) { std::memcpy(out[i].a, kIdentityMotion, sizeof kIdentityMotion); continue; }
+    double C[3][3], P[3][3], inv[3][3];                       // [row][col] of the linear parts (memory is column-major: m[col*4+row])
+    for (int r = 0; r < 3; r++) for (int k = 0; k < 3; k++) { C[r][k] = c[k * 4 + r]; P[r][k] = p[k * 4 + r]; }
+    const double c00 = C[1][1] * C[2][2] - C[1][2] * C[2][1], c01 = C[1][2] * C[2][0] - C[1][0] * C[2][2], c02 = C[1][0] * C[2][1] - C[1][1] * C[2][0];
+    const double det = C[0][0] * c00 + C[0][1] * c01 + C[0][2] * c02;
+    if (!(det != 0.0) || !std::isfinite(det)) { nan_motion(&out[i]); continue; }      // a singular (or NaN) curL: that object gets no history
+    inv[0][0] = c00 / det; inv[1][0] = c01 / det; inv[2][0] = c02 / det;
+    inv[0][1] = (C[0][2] * C[2][1] - C[0][1] * C[2][2]) / det;
+    inv[1][1] = (C[0][0] * C[2][2] - C[0][2] * C[2][0]) / det;
+    inv[2][1] = (C[0][1] * C[2][0] - C[0][0] * C[2][1]) / det;
+    inv[0][2] = (C[0][1] * C[1][2] - C[0][2] * C[1][1]) / det;
+    inv[1][2] = (C[0][2] * C[1][0] - C[0][0] * C[1][2]) / det;
+    inv[2][2] = (C[0][0] * C[1][1] - C[0][1] * C[1][0]) / det;
+    double A[3][3];
+    for (int r = 0; r < 3; r++) for (int k = 0; k < 3; k++) A[r][k] = (P[r][0] * inv[0][k] + P[r][1] * inv[1][k]) + P[r][2] * inv[2][k];
+    for (int r = 0; r < 3; r++) {
+      const double t = (double)p[12 + r] - ((A[r][0] * (double)c[12] + A[r][1] * (double)c[13]) + A[r][2] * (double)c[14]);
+      for (int k = 0; k < 3; k++) out[i].a[3 * k + r] = (float)A[r][k];
+      out[i].a[9 + r] = (float)t;
+    }
+  }
+  return URT_OK;
+}
+
+// s = r_prev / r_cur: linear part s * I, translation c_prev - s * c_cur, in float64, rounded once to float32
+int urt_host_sphere_motion(const void* prev_spheres, const void* cur_spheres, int n, urt_ObjectMotion* out) {
+  if (n < 0) return host_fail(URT_ERR_INVALID_ARGUMENT, "sphere_motion: n is negative");
+  if (n > 0 && (!prev_spheres || !cur_spheres || !out)) return host_fail(URT_ERR_INVALID_ARGUMENT, "sphere_motion: a pointer is NULL");
+  const urt_Sphere* prev = (const urt_Sphere*)prev_spheres;
+  const urt_Sphere* cur = (const urt_Sphere*)cur_spheres;
+  for (int i = 0; i < n; i++) {
+    if (std::memcmp(&prev[i], &cur[i], 16) == 0) { std::memcpy(out[i].a, kIdentityMotion, sizeof kIdentityMotion); continue; }   // position, radius
+    if (!(cur[i].radius > 0.0f)) { nan_motion(&out[i]); continue; }
+    const double s = (double)prev[i].radius / (double)cur[i].radius;
+    for (float& v : out[i].a) v = 0.0f;
+    out[i].a[0] = out[i].a[4] = out[i].a[8] = (float)s;
+    for (int r = 0; r < 3; r++) out[i].a[9 + r] = (float)((double)prev[i].position[r] - s * (double)cur[i].position[r]);
+  }
+  return URT_OK;
 }
 
 }  // extern "C"

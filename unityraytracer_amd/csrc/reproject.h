@@ -1,4 +1,5 @@
-// reproject.h — host-callable launchers of the temporal reprojection (reproject.hip): urt_reproject and urt_blit_add_history
+// reproject.h — host-callable launchers of the temporal reprojection (reproject.hip): urt_reproject, urt_reproject_objects and
+// urt_blit_add_history
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -30,8 +31,20 @@ struct ReprojectSettings {
   float max_history, normal_threshold, plane_threshold;
 };
 
+// The per-object motion tables of urt_reproject_objects: entries of 48 bytes (include/urt.h urt_ObjectMotion) at 16-byte aligned
+// device addresses, read as three float4; null = that kind of object has not moved.
+struct ReprojectMotion {
+  const float4* mesh;           // entry i = MeshObject i
+  const float4* sphere;
+  int n_mesh, n_sphere;         // entries of each table
+  float moved_max_history;      // 0 = none
+};
+
 // Enqueues k_reproject on `st`.  hipErrorInvalidValue when the grid is too tall.
 hipError_t launch_reproject(const ReprojectImages& I, const ReprojectSettings& P, hipStream_t st);
+
+// The same with the tables: enqueues k_reproject_objects.
+hipError_t launch_reproject_objects(const ReprojectImages& I, const ReprojectSettings& P, const ReprojectMotion& T, hipStream_t st);
 
 // One AdditionShader blend with the per-pixel sample count of `count` (urt_blit_add_history), in place on dst and count.
 hipError_t launch_blit_add_history(const float4* src, float4* dst, float4* count, size_t n_pixels, float max_history, hipStream_t st);

@@ -6,10 +6,15 @@
 // k_denoise_*.  A pixel loads its three current feature texels, projects its hit point (or, for a sky pixel, its pixel-centre direction)
 // into the previous view and gathers the 2 x 2 bilinear footprint around it from the previous history and feature buffers: for small
 // motions the taps of a wave are the wave's own 8 x 8 block shifted, so they coalesce as the current loads do.  No LDS.
+// k_reproject<true> (urt_reproject_objects) is the same kernel instantiated with MOTION: a triangle or sphere pixel also loads its
+// object's 48-byte "current world -> previous world" entry (three dwordx4 loads; the object id is uniform over most waves, so the entry
+// comes from one or two cache lines) and projects the point where it WAS.  Ground, sky and scenes without tables pay one uniform branch;
+// k_reproject<false> keeps its argument struct and takes none of the new branches.
 // k_blit_add_history / k_blit_add_history_multi: grid-stride over the pixels as k_blit_add / k_blit_add_multi; the fused form reads the
 // count and dst once, blends n frames and writes both (and the present) once: 16 n + 64 bytes per pixel with a present.
 #include <hip/hip_runtime.h>
 
+#include "../../include/urt_math.h"
 #include "reproject.h"
 
 namespace {
@@ -19,12 +24,29 @@ struct Params {
   urtd::ReprojectSettings P;
 };
 
+struct ParamsObjects : Params {
+  urtd::ReprojectMotion T;
+};
+
 __device__ __forceinline__ bool finite3(float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
 __device__ __forceinline__ bool finite4(float4 v) { return finite3(v) && isfinite(v.w); }
 
-__global__ __launch_bounds__(256) void k_reproject(const Params A) {
+// the twelve floats of an entry are bit for bit (1,0,0, 0,1,0, 0,0,1, 0,0,0)
+__device__ __forceinline__ bool identity_entry(float4 a, float4 b, float4 c) {
+  const int one = 0x3f800000;
+  return ((__float_as_int(a.x) ^ one) | __float_as_int(a.y) | __float_as_int(a.z) | __float_as_int(a.w) | (__float_as_int(b.x) ^ one) |
+          __float_as_int(b.y) | __float_as_int(b.z) | __float_as_int(b.w) | (__float_as_int(c.x) ^ one) | __float_as_int(c.y) |
+          __float_as_int(c.z) | __float_as_int(c.w)) == 0;
+}
+
+// urt_reproject (MOTION false, PARAMS = Params) and urt_reproject_objects (MOTION true, PARAMS = ParamsObjects).  A pixel that is not
+// moved takes exactly the operations of the instantiation without MOTION.
+template <bool MOTION, class PARAMS>
+__global__ __launch_bounds__(256) void k_reproject(const PARAMS A) {
   const urtd::ReprojectImages& I = A.I;
   const urtd::ReprojectSettings& P = A.P;
+  const urtd::ReprojectMotion* T = nullptr;
+  if constexpr (MOTION) T = &A.T;
   const int W = I.width, H = I.height;
   // workgroup = 16 x 16 pixels, wave = the 8 x 8 tile (wave & 1, wave >> 1) of it, lane = (lane & 7, lane >> 3) of the tile
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -36,15 +58,43 @@ __global__ __launch_bounds__(256) void k_reproject(const Params A) {
   const float4 h = I.hit[pix], nr = I.normal[pix];
   const float k = nr.w, z = h.w;
   const bool sky = k == 0.0f;
-  const bool surface = !sky && isfinite(z) && z > 0.0f && finite3(h) && finite3(nr);
+  const bool surface_in = !sky && isfinite(z) && z > 0.0f && finite3(h) && finite3(nr);
   const float* M = P.m;
+
+  // the point and the normal the previous frame knew this surface by: the pixel's own unless its object has moved
+  float4 hp = h, np = nr;
+  float L = 1.0f;
+  bool moved = false, dead = false;
+  if (MOTION && surface_in && (k == 2.0f || k == 3.0f)) {
+    const float4* tab = k == 3.0f ? T->mesh : T->sphere;
+    if (tab) {                                                   // uniform: a scene without tables stops here
+      const int o = __float_as_int(I.id[pix].x);
+      if (o < 0 || o >= (k == 3.0f ? T->n_mesh : T->n_sphere)) {
+        dead = true;                                             // no such entry: no history
+      } else {
+        const float4 a = tab[3 * (size_t)o], b = tab[3 * (size_t)o + 1], c = tab[3 * (size_t)o + 2];   // a[0..3], a[4..7], a[8..11]
+        if (!identity_entry(a, b, c)) {
+          moved = true;
+          hp.x = ((a.x * h.x + a.w * h.y) + b.z * h.z) + c.y;
+          hp.y = ((a.y * h.x + b.x * h.y) + b.w * h.z) + c.z;
+          hp.z = ((a.z * h.x + b.y * h.y) + c.x * h.z) + c.w;
+          np.x = (a.x * nr.x + a.w * nr.y) + b.z * nr.z;
+          np.y = (a.y * nr.x + b.x * nr.y) + b.w * nr.z;
+          np.z = (a.z * nr.x + b.y * nr.y) + c.x * nr.z;
+          L = urt::f_sqrt((np.x * np.x + np.y * np.y) + np.z * np.z);
+          if (!(finite3(hp) && L > 0.0f && isfinite(L))) dead = true;
+        }
+      }
+    }
+  }
+  const bool surface = MOTION ? surface_in && !dead : surface_in;
 
   // 2. the point (w = 1) or the direction (w = 0) in the previous camera's clip space
   float cx = 0.0f, cy = 0.0f, cw = 0.0f;
   if (surface) {
-    cx = ((M[0] * h.x + M[4] * h.y) + M[8] * h.z) + M[12];
-    cy = ((M[1] * h.x + M[5] * h.y) + M[9] * h.z) + M[13];
-    cw = ((M[3] * h.x + M[7] * h.y) + M[11] * h.z) + M[15];
+    cx = ((M[0] * hp.x + M[4] * hp.y) + M[8] * hp.z) + M[12];
+    cy = ((M[1] * hp.x + M[5] * hp.y) + M[9] * hp.z) + M[13];
+    cw = ((M[3] * hp.x + M[7] * hp.y) + M[11] * hp.z) + M[15];
   } else if (sky) {
     const float* C = P.c2w;
     const float* Iv = P.invp;
@@ -86,9 +136,11 @@ __global__ __launch_bounds__(256) void k_reproject(const Params A) {
       } else {
         const float4 Q = I.prev_hit[q];
         const int oq = __float_as_int(I.prev_id[q].x);
-        const float nd = (nr.x * m.x + nr.y * m.y) + nr.z * m.z;
-        const float pd = fabsf((nr.x * (Q.x - h.x) + nr.y * (Q.y - h.y)) + nr.z * (Q.z - h.z));
-        ok = ok && m.w == k && oq == o && isfinite(Q.w) && Q.w > 0.0f && nd >= P.normal_threshold && pd <= P.plane_threshold * z;
+        const float nd = (np.x * m.x + np.y * m.y) + np.z * m.z;
+        const float pd = fabsf((np.x * (Q.x - hp.x) + np.y * (Q.y - hp.y)) + np.z * (Q.z - hp.z));
+        const float nt = MOTION && moved ? P.normal_threshold * L : P.normal_threshold;
+        const float pt = MOTION && moved ? (P.plane_threshold * z) * L : P.plane_threshold * z;
+        ok = ok && m.w == k && oq == o && isfinite(Q.w) && Q.w > 0.0f && nd >= nt && pd <= pt;
       }
       if (ok) {                                                  // 4. in tap order
         S = S + w;
@@ -106,6 +158,7 @@ __global__ __launch_bounds__(256) void k_reproject(const Params A) {
     c = make_float4(acc.x / S, acc.y / S, acc.z / S, acc.w / S);
     n = N / S;
     if (P.max_history > 0.0f) n = fminf(n, P.max_history);
+    if (MOTION && moved && T->moved_max_history > 0.0f) n = fminf(n, T->moved_max_history);
   }
   I.color[pix] = c;
   I.count[pix] = make_float4(n, 0.0f, 0.0f, 0.0f);
@@ -169,7 +222,17 @@ hipError_t launch_reproject(const ReprojectImages& I, const ReprojectSettings& P
   if (I.width <= 0 || I.height <= 0) return hipSuccess;
   const dim3 grid((unsigned int)((I.width + 15) / 16), (unsigned int)((I.height + 15) / 16));
   if (grid.y > 65535u) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_reproject, grid, dim3(256), 0, st, Params{I, P});
+  hipLaunchKernelGGL((k_reproject<false, Params>), grid, dim3(256), 0, st, Params{I, P});
+  return hipGetLastError();
+}
+
+hipError_t launch_reproject_objects(const ReprojectImages& I, const ReprojectSettings& P, const ReprojectMotion& T, hipStream_t st) {
+  if (I.width <= 0 || I.height <= 0) return hipSuccess;
+  const dim3 grid((unsigned int)((I.width + 15) / 16), (unsigned int)((I.height + 15) / 16));
+  if (grid.y > 65535u) return hipErrorInvalidValue;
+  ParamsObjects A{};
+  A.I = I; A.P = P; A.T = T;
+  hipLaunchKernelGGL((k_reproject<true, ParamsObjects>), grid, dim3(256), 0, st, A);
   return hipGetLastError();
 }
 

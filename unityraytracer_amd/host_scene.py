@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import UrtError
-from .scenes import BVHNODE_DT
+from .scenes import BVHNODE_DT, MESHOBJECT_DT, SPHERE_DT
 
 
 def _check(lib, rc):
@@ -60,3 +60,25 @@ def build_object_bvh(leaves: np.ndarray, pairing: bool = False) -> np.ndarray:
     fn = lib.urt_host_build_object_bvh_pairing if pairing else lib.urt_host_build_object_bvh
     _check(lib, fn(_p(lv), len(lv), _p(out), n))
     return out
+
+
+def _motion(fn, prev, cur, dt, what: str) -> np.ndarray:
+    lib = _lib.load()
+    a, b = np.ascontiguousarray(prev, dtype=dt).reshape(-1), np.ascontiguousarray(cur, dtype=dt).reshape(-1)
+    if len(a) != len(b):
+        raise ValueError(f"{what}: the previous list has {len(a)} objects, the current one {len(b)}")
+    out = np.zeros((len(a), 12), dtype=np.float32)
+    _check(lib, getattr(lib, fn)(_p(a), _p(b), len(a), _p(out)))
+    return out
+
+
+def mesh_motion(prev, cur) -> np.ndarray:
+    """The mesh motion table of Context.reproject (include/urt.h urt_host_mesh_motion) from the MeshObject lists (scenes.MESHOBJECT_DT)
+    before and after a move: (n, 12) float32, entry i = current world -> previous world of MeshObject i, the exact identity where the
+    matrix did not change."""
+    return _motion("urt_host_mesh_motion", prev, cur, MESHOBJECT_DT, "mesh_motion")
+
+
+def sphere_motion(prev, cur) -> np.ndarray:
+    """The same for the sphere lists (scenes.SPHERE_DT): urt_host_sphere_motion."""
+    return _motion("urt_host_sphere_motion", prev, cur, SPHERE_DT, "sphere_motion")

@@ -23,7 +23,8 @@ import numpy as np
 from dataclasses import dataclass, field
 
 from . import host_scene, scenes
-from .unity_api import ComputeBuffer, ComputeShader, Context, Graphics, Material, RenderTexture, denoise_params, reproject_params
+from .unity_api import ComputeBuffer, ComputeShader, Context, Graphics, Material, RenderTexture, _matrix16, _max_history_arg, \
+    denoise_params, reproject_params
 
 
 @dataclass
@@ -73,6 +74,8 @@ class RayTraceMaster:
         self._temporal = None                        # EnableTemporalAccumulation: the reprojection settings (None = off, the reference's behaviour)
         self._tcount = self._tspare = None           # temporal: the count texture of _converged; the spare (colour, count) pair reprojection writes
         self._taov = None                            # temporal: two (hit, normal, id) sets, the previous and the new camera's
+        self._moved_max_history = 0.0                # temporal: extra clamp of the count on pixels of moved objects (MoveObjects; 0 = none)
+        self._tmotion = [None, None]                 # temporal: the mesh and the sphere motion table of the last MoveObjects (ComputeBuffers)
 
     # RM:215-230
     def RegisterObject(self, obj: RayTraceObject):
@@ -306,12 +309,15 @@ class RayTraceMaster:
     # the accumulated image into the new view (urt_reproject) instead of restarting it.  The settings are urt_ReprojectParams' (defaults:
     # include/urt.h URT_REPROJECT_DEFAULT_*); max_history also caps the count the blend uses, so a still view keeps a running mean of its
     # last max_history frames (0 = unlimited).
-    def EnableTemporalAccumulation(self, max_history: float = None, normal_threshold: float = None, plane_threshold: float = None):
+    def EnableTemporalAccumulation(self, max_history: float = None, normal_threshold: float = None, plane_threshold: float = None,
+                                   moved_max_history: float = 0.0):
         from ._lib import REPROJECT_DEFAULTS
+        mmh = _max_history_arg(moved_max_history, "EnableTemporalAccumulation", "moved_max_history")
         given = {"max_history": max_history, "normal_threshold": normal_threshold, "plane_threshold": plane_threshold}
         settings = {k: (REPROJECT_DEFAULTS[k] if v is None else v) for k, v in given.items()}
         p = reproject_params(np.eye(4, dtype=np.float32).reshape(16), **settings)   # checked before anything is created
         self._temporal = {"max_history": p.max_history, "normal_threshold": p.normal_threshold, "plane_threshold": p.plane_threshold}
+        self._moved_max_history = mmh
         self._ensure_temporal_textures()
         self._tcount.SetPixels(np.zeros((self.screen_height, self.screen_width, 4), np.float32))   # creation is not assumed to zero
         self._currentSample = 0                                               # the count texture starts empty: so does the mean
@@ -326,6 +332,10 @@ class RayTraceMaster:
             if t is not None:
                 t.Release()
         self._tcount = self._tspare = self._taov = None
+        for b in self._tmotion:
+            if b is not None:
+                b.Release()
+        self._tmotion = [None, None]
 
     def _ensure_temporal_textures(self):
         w, h = self.screen_width, self.screen_height
@@ -365,6 +375,87 @@ class RayTraceMaster:
                            **self._temporal)
         self._tspare = (self._converged, self._tcount)
         self._converged, self._tcount = color, count
+
+    # Objects move (and, optionally, the camera with them).  mesh_edits: {MeshObject index: 16-float localToWorldMatrix}; sphere_edits:
+    # {sphere index: (position, radius)}.  The edits go into the scene's lists, the object-level heaps are rebuilt and everything is
+    # re-uploaded through SetData as RebuildTrees does (moved meshes are refitted on the GPU, csrc/refit.hip).  Temporal accumulation
+    # off, or no history yet: the accumulation restarts, the reference's behaviour for a moved object (RM:765-767).  On: the pixel-centre
+    # feature buffers are rendered before the edits (old scene, old camera) and after them, the per-object "current world -> previous
+    # world" tables are made from the two object lists (host_scene.mesh_motion / sphere_motion) and the accumulated image is reprojected
+    # with them (include/urt.h urt_reproject_objects): a moved object keeps its history, clamped to moved_max_history when that is set.
+    def MoveObjects(self, mesh_edits=None, sphere_edits=None, camera_to_world=None, camera_inverse_projection=None):
+        s = self.scene
+        mesh_edits = {} if mesh_edits is None else dict(mesh_edits)
+        sphere_edits = {} if sphere_edits is None else dict(sphere_edits)
+        if self._treesNeedRebuilding and self._rayTraceObjects:                    # the lists the indices refer to do not exist yet
+            self.RebuildObjectLists()
+        new_mo, new_sp = s.mesh_objects.copy(), s.spheres.copy()
+        for what, edits, n in (("mesh_edits", mesh_edits, len(new_mo)), ("sphere_edits", sphere_edits, len(new_sp))):
+            for k in edits:
+                if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+                    raise TypeError(f"MoveObjects: the keys of {what} must be ints, not {type(k).__name__}")
+                if not 0 <= k < n:
+                    raise IndexError(f"MoveObjects: {what} names object {k}, the scene has {n}")
+        for k, mat in mesh_edits.items():
+            new_mo[k]["localToWorldMatrix"] = _matrix16(mat, f"MoveObjects: mesh_edits[{k}]")
+        for k, edit in sphere_edits.items():
+            try:
+                pos, radius = edit
+                pos = np.asarray(pos, dtype=np.float32).reshape(3)
+                radius = np.float32(radius)
+            except (TypeError, ValueError):
+                raise ValueError(f"MoveObjects: sphere_edits[{k}] must be (position of 3 floats, radius)") from None
+            new_sp[k]["position"], new_sp[k]["radius"] = pos, radius
+        c2w = s.camera_to_world if camera_to_world is None else _matrix16(camera_to_world, "MoveObjects: camera_to_world").copy()
+        invp = s.camera_inverse_projection if camera_inverse_projection is None else \
+            _matrix16(camera_inverse_projection, "MoveObjects: camera_inverse_projection").copy()
+        history = self._temporal is not None and self._converged is not None and self._currentSample > 0 and not self._treesNeedRebuilding \
+            and (self._converged.width, self._converged.height) == (self.screen_width, self.screen_height)
+        if history:
+            self._ensure_temporal_textures()
+            prev_m = scenes.world_to_clip(s.camera_to_world, s.camera_inverse_projection)
+            prev, cur = self._taov
+            self.SetShaderParameters()
+            self.ctx.render_aov(prev[0], prev[1], None, prev[2])               # the scene and the camera as the history saw them
+        prev_mo, prev_sp = s.mesh_objects, s.spheres
+        self._apply_object_edits(new_mo, new_sp, mesh_edits, sphere_edits)
+        s.camera_to_world, s.camera_inverse_projection = c2w, invp
+        if not history:
+            self.ResetAccumulation()
+            return
+        self.SetShaderParameters()
+        self.ctx.render_aov(cur[0], cur[1], None, cur[2])                      # the moved scene under the new camera
+        tables = [host_scene.mesh_motion(prev_mo, new_mo) if mesh_edits else None,
+                  host_scene.sphere_motion(prev_sp, new_sp) if sphere_edits else None]
+        for k, t in enumerate(tables):
+            self._tmotion[k] = self.CreateComputeBuffer(self._tmotion[k], t if t is not None else np.zeros((0, 12), np.float32), 48)
+        color, count = self._tspare
+        self.ctx.reproject(self._converged, self._tcount, prev[0], prev[1], prev[2], cur[0], cur[1], cur[2], color, count, prev_m,
+                           mesh_motion=self._tmotion[0], sphere_motion=self._tmotion[1], moved_max_history=self._moved_max_history,
+                           **self._temporal)
+        self._tspare = (self._converged, self._tcount)
+        self._converged, self._tcount = color, count
+
+    # the edited lists become the scene's, with the object-level heaps RebuildObjectLists / the scene builders make for them, and are
+    # uploaded (RebuildTrees: SetData of data a buffer already holds changes nothing)
+    def _apply_object_edits(self, new_mo, new_sp, mesh_edits, sphere_edits):
+        s = self.scene
+        s.mesh_objects, s.spheres = new_mo, new_sp
+        if self._rayTraceObjects:                                                 # keep the registered objects in step with the lists
+            meshes = [o for o in self._rayTraceObjects if o.type != 1]
+            spheres = [o for o in self._rayTraceObjects if o.type == 1]
+            for k in mesh_edits:
+                meshes[k].localToWorldMatrix = np.array(new_mo[k]["localToWorldMatrix"], np.float32)
+            for k in sphere_edits:
+                spheres[k].position, spheres[k].radius = tuple(float(v) for v in new_sp[k]["position"]), float(new_sp[k]["radius"])
+        if mesh_edits:
+            s.mesh_bvh = host_scene.build_object_bvh(host_scene.mesh_leaf_bounds(new_mo, s.vertices, s.indices)) if self._rayTraceObjects \
+                else scenes.build_object_bvh(*scenes.mesh_bounds(new_mo, s.vertices, s.indices))
+        if sphere_edits:
+            s.sphere_bvh = host_scene.build_object_bvh(host_scene.sphere_leaf_bounds(new_sp)) if self._rayTraceObjects \
+                else scenes.build_object_bvh(*scenes.sphere_bounds(new_sp))
+        if not self._treesNeedRebuilding:                                          # else the next frame uploads everything anyway
+            self.RebuildTrees()
 
     # RM:761-763: F12 -> ScreenCapture.CaptureScreenshot("Screenshots/" + Time.time + "-" + _currentSample + ".png")
     def CaptureScreenshot(self, directory: str, time_seconds: float) -> str:

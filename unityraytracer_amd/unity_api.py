@@ -275,12 +275,16 @@ class Context:
     def reproject(self, prev_color, prev_count, prev_hit, prev_normal, prev_id, hit, normal, id, color, count, prev_world_to_clip,
                   motion=None, max_history: float = _lib.REPROJECT_DEFAULTS["max_history"],
                   normal_threshold: float = _lib.REPROJECT_DEFAULTS["normal_threshold"],
-                  plane_threshold: float = _lib.REPROJECT_DEFAULTS["plane_threshold"]):
+                  plane_threshold: float = _lib.REPROJECT_DEFAULTS["plane_threshold"], *, mesh_motion=None, sphere_motion=None,
+                  moved_max_history: float = 0.0):
         """Temporal reprojection (include/urt.h urt_reproject): the history prev_color / prev_count accumulated under the previous camera,
         whose world-to-clip matrix is prev_world_to_clip (16 floats, column-major: scenes.world_to_clip), carried into the current view
         (the bound _CameraToWorld / _CameraInverseProjection) -> color / count, and the optional motion image.  prev_hit / prev_normal /
         prev_id and hit / normal / id are render_aov's pixel-centre buffers under the previous and the current camera.  RenderTextures
-        of one size.  Enqueued after the deferred frames; a later GetPixels sees the result."""
+        of one size.  Enqueued after the deferred frames; a later GetPixels sees the result.
+        mesh_motion / sphere_motion: ComputeBuffers of stride 48 (urt_ObjectMotion: host_scene.mesh_motion / sphere_motion) for objects
+        that have moved between the two sets of feature buffers, moved_max_history an extra clamp of the count on their pixels: with
+        any of the three given the call is urt_reproject_objects, else urt_reproject."""
         images = dict(zip(self.REPROJECT_INPUTS, (prev_color, prev_count, prev_hit, prev_normal, prev_id, hit, normal, id)))
         images.update(color=color, count=count, motion=motion)
         for name, t in images.items():
@@ -293,14 +297,42 @@ class Context:
                 if name != o and t is images[o]:
                     raise ValueError(f"reproject: the output {o} is also {name}")
         p = reproject_params(prev_world_to_clip, max_history, normal_threshold, plane_threshold)
+        for name, b in (("mesh_motion", mesh_motion), ("sphere_motion", sphere_motion)):
+            if b is None:
+                continue
+            if not isinstance(b, ComputeBuffer):
+                raise TypeError(f"reproject: {name} must be a ComputeBuffer or None, not {type(b).__name__}")
+            if b.ctx is not self:
+                raise ValueError(f"reproject: {name} belongs to another context")
+            if not b.handle:
+                raise ValueError(f"reproject: {name} was released")
+            if b.stride != C.sizeof(_lib.ObjectMotion):
+                raise ValueError(f"reproject: the stride of {name} is {b.stride}, not {C.sizeof(_lib.ObjectMotion)}")
+        mmh = _max_history_arg(moved_max_history, "reproject", "moved_max_history")
         im = _lib.ReprojectImages(*(images[n].handle if images[n] is not None else 0 for n, _ in _lib.ReprojectImages._fields_))
-        self.check(self.lib.urt_reproject(self._h, C.byref(im), C.byref(p)))
+        if mesh_motion is None and sphere_motion is None and mmh == 0.0:
+            self.check(self.lib.urt_reproject(self._h, C.byref(im), C.byref(p)))
+            return
+        mo = _lib.ReprojectMotion(mesh_motion.handle if mesh_motion is not None else 0,
+                                  sphere_motion.handle if sphere_motion is not None else 0, mmh, 0)
+        self.check(self.lib.urt_reproject_objects(self._h, C.byref(im), C.byref(p), C.byref(mo)))
 
     def reproject_arrays(self, prev_color, prev_count, prev_hit, prev_normal, prev_id, hit, normal, id, prev_world_to_clip,
-                         camera_to_world, camera_inverse_projection, motion: bool = True, **params) -> dict:
+                         camera_to_world, camera_inverse_projection, motion: bool = True, mesh_motion=None, sphere_motion=None,
+                         moved_max_history: float = 0.0, **params) -> dict:
         """reproject on numpy images (h, w, 4) float32, row 0 = bottom, through temporary textures.  camera_to_world /
-        camera_inverse_projection (16 floats each) are bound as the context's current camera uniforms first (they stay bound).  Returns
+        camera_inverse_projection (16 floats each) are bound as the context's current camera uniforms first (they stay bound).
+        mesh_motion / sphere_motion: the motion tables as (n, 12) float32 arrays (n >= 1) or None.  Returns
         {"color", "count"[, "motion"]} as (h, w, 4) arrays."""
+        tables = {}
+        for name, a in (("mesh_motion", mesh_motion), ("sphere_motion", sphere_motion)):
+            if a is None:
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 12 or a.shape[0] < 1:
+                raise ValueError(f"reproject_arrays: {name} must have shape (n, 12) with n >= 1, not {a.shape}")
+            tables[name] = a
+        _max_history_arg(moved_max_history, "reproject", "moved_max_history")
         imgs = [np.ascontiguousarray(a, dtype=np.float32) for a in (prev_color, prev_count, prev_hit, prev_normal, prev_id, hit, normal, id)]
         shape = imgs[0].shape
         if len(shape) != 3 or shape[2] != 4 or shape[0] <= 0 or shape[1] <= 0:
@@ -311,22 +343,27 @@ class Context:
         reproject_params(prev_world_to_clip, **params)
         c2w, invp = _matrix16(camera_to_world, "camera_to_world"), _matrix16(camera_inverse_projection, "camera_inverse_projection")
         h, w = shape[:2]
-        tex = []
+        tex, bufs = [], {}
         try:
+            for name, a in tables.items():
+                bufs[name] = ComputeBuffer(self, len(a), 48)
+                bufs[name].SetData(a)
             for a in imgs + [None] * (3 if motion else 2):
                 tex.append(RenderTexture(self, w, h))
                 if a is not None:
                     tex[-1].SetPixels(a)
-            self.check(self.lib.urt_shader_set_matrix(self._h, b"_CameraToWorld", c2w.ctypes.data_as(C.c_void_p)))
-            self.check(self.lib.urt_shader_set_matrix(self._h, b"_CameraInverseProjection", invp.ctypes.data_as(C.c_void_p)))
+            sh = ComputeShader(self)                               # through the wrapper: it remembers what the context last received, and a
+            sh.SetMatrix("_CameraToWorld", c2w)                    # later RayTraceMaster on this context skips a matrix only if it really is bound
+            sh.SetMatrix("_CameraInverseProjection", invp)
             outs = tex[8:]
-            self.reproject(*tex[:8], outs[0], outs[1], prev_world_to_clip, motion=outs[2] if motion else None, **params)
+            self.reproject(*tex[:8], outs[0], outs[1], prev_world_to_clip, motion=outs[2] if motion else None,
+                           moved_max_history=moved_max_history, **bufs, **params)
             res = {"color": outs[0].GetPixels(), "count": outs[1].GetPixels()}
             if motion:
                 res["motion"] = outs[2].GetPixels()
             return res
         finally:
-            for t in tex:
+            for t in tex + list(bufs.values()):
                 t.Release()
 
     def blit_add_history(self, src, dst, count, max_history: float = 0.0):
@@ -359,10 +396,10 @@ def _number_arg(v, name: str, what: str) -> float:
     return float(v)
 
 
-def _max_history_arg(v, what: str) -> float:
-    v = _number_arg(v, "max_history", what)
+def _max_history_arg(v, what: str, name: str = "max_history") -> float:
+    v = _number_arg(v, name, what)
     if not (v == 0.0 or v >= 1.0):
-        raise ValueError(f"{what}: max_history must be 0 (unlimited) or >= 1, not {v}")
+        raise ValueError(f"{what}: {name} must be 0 (unlimited) or >= 1, not {v}")
     return v
 
 
