@@ -25,7 +25,12 @@
 //   3  BINNED SAH, the host builder's algorithm level by level (k_sah_*): bins filled with LDS-privatised atomics, one thread per node
 //      sweeps them, a flag + scan + scatter pass partitions every range in place — the host's trees in a fifth of the time.
 // Any conservative BVH gives the same pixels: the closest-hit rule (strict t <, ties to the lower index slot, A.4) is in
-// the traversal, not in the tree.  tests/test_gpu_lbvh.py checks structure, bit-identical frames and the build time of all three.
+// the traversal, not in the tree.  tests/test_gpu_lbvh.py checks structure, bit-identical frames and the build time of all three;
+// tests/test_gpu_lbvh_exact.py holds every word of every node, the leaf order and the roots to the numpy restatement of the three
+// builders (tests/lbvh_ref.py), bit for bit.
+// Float -> integer conversions are never left to what the cast does out of range: a NaN or negative Morton cell is cell 0 and a cell
+// beyond 1023 is 1023 (k_morton); a NaN or negative SAH bin is bin 0 and one beyond the last is the last (sah_bin).  NaN centroids are
+// kept out of every centroid bound (test c == c first).
 #include <hip/hip_runtime.h>
 #include <string.h>                      // rocprim's texture_cache_iterator.hpp calls memset unqualified
 #include <cstring>
@@ -441,8 +446,9 @@ __device__ __forceinline__ float3 tri_centroid(const Dev& D, unsigned int g) {
   return make_float3(0.5f * lo.x + 0.5f * hi.x, 0.5f * lo.y + 0.5f * hi.y, 0.5f * lo.z + 0.5f * hi.z);
 }
 __device__ __forceinline__ int sah_bin(float c, float lo, float ext, int nb) {       // blas_builder.cpp: (int)((c - lo) * (bins / ext)), clamped
-  int b = (int)((c - lo) * ((float)nb / ext));
-  return min(max(b, 0), nb - 1);
+  const float x = (c - lo) * ((float)nb / ext);
+  if (!(x >= 0.0f)) return 0;                              // NaN (a non-finite centroid, 0 * inf) and negatives: bin 0, stated rather than left to the conversion
+  return x >= (float)nb ? nb - 1 : (int)x;                 // +inf and everything beyond the last bin: the last bin
 }
 
 __global__ __launch_bounds__(64) void k_sah_roots(Dev D) {        // one lane: level 0 = the MeshObjects that need a tree, in MeshObject order
