@@ -583,7 +583,7 @@ URT_API int urt_debug_scene_info(urt_context* ctx, int* out_n_nodes, int* out_n_
 /* The last trace launch of this context (deferred frames are submitted first): which kernel instantiation ran — by the name rocprofv3
  * prints for it, so that bench.py and the profile reducers name the kernel that really ran instead of re-deriving the dispatch logic —,
  * its grid, its dynamic LDS and what the frame batching did (slab_frames_max < the requested batch, or slab_out_of_memory: the Result
- * slots did not fit and the batch was halved / switched off, context.cpp ensure_slab).  No counterpart in the reference (one Dispatch
+ * slots did not fit and the batch was halved / switched off, frame_batch.cpp ensure_slab).  No counterpart in the reference (one Dispatch
  * per frame, RM:806-810); measurement only. */
 typedef struct urt_launch_info {
   char kernel[96];            /* e.g. "k_sched<false, 256, 0, false, false>" (COUNT, BLOCK, FMODE, MULTI, QN: kernels.hip) */

@@ -527,7 +527,7 @@ int oracle_render(const OracleScene* scene, int x0, int y0, int x1, int y1, int 
   return 0;
 }
 
-// The product's eligibility + verification rule for the object-level cull (csrc/context.cpp cull_words, csrc/cullflags.hip), restated:
+// The product's eligibility + verification rule for the object-level cull (csrc/scene_prep.cpp cull_words, csrc/cullflags.hip), restated:
 // MeshObject m may be culled iff exactly one node of the mesh heap names m, that node's box is not
 // empty (RS:273), m has at least one triangle, and every vertex of m's triangle records (v0, v0 + e1, v0 + e2 with e = v - v0 in
 // float32, as the product stores them) lies inside that box widened by 2^-20 of its largest |coordinate|.  out: n_mesh_objects ints.

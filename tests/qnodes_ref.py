@@ -78,7 +78,7 @@ MAX_CELL = 2.0 ** 43      # the traversal's 2^23 offset times S = cell / d (|1 /
 
 
 def in_use(frame, option):
-    """Whether the traversal loop reads the quantized nodes (csrc/context.cpp requantize): option 1, or -1 with a quality of at least 1024
+    """Whether the traversal loop reads the quantized nodes (csrc/scene_prep.cpp requantize): option 1, or -1 with a quality of at least 1024
     cells, and in either case a grid whose cells are at most 2^43 on every axis."""
     return bool(frame[1, :3].max() <= MAX_CELL and (option == 1 or (option == -1 and frame[0, 3] >= 1024)))
 

@@ -1,5 +1,5 @@
 """GPU: overlapped launches (include/urt.h option "overlap_launches" — here 2 = always, so that the pipelined readbacks the tests observe the
-frames with do not switch it off as the default "auto" would; context.cpp flush_pending).
+frames with do not switch it off as the default "auto" would; frame_batch.cpp flush_pending).
 
 A host that presents or reads back EVERY frame (RM:798-821 once per displayed frame — how the reference really runs) submits one-frame
 launches; the library alternates them between two trace streams of its own, takes their Result slots round-robin from the slab and lets

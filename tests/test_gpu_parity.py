@@ -155,7 +155,7 @@ def test_deep_stacks_use_the_large_lds_launch_path(gpu_ctx):
 
 def test_masked_phase_at_fewer_workgroups_per_cu(gpu_ctx):
     """Deep traversal stacks in a multi-mesh scene (C4 in small: Cornell box + 3 blobs, masked object-level phase): when 5 workgroups of
-    stacks no longer fit a CU's LDS, the launch counts on 4 or 3 and keeps the masked phase and the LDS copies (context.cpp
+    stacks no longer fit a CU's LDS, the launch counts on 4 or 3 and keeps the masked phase and the LDS copies (frame_batch.cpp
     configure_sched) before it falls back to the large-LDS path.  `stack_pad` walks through all of these layouts; the GPU-built
     (deeper) tree is one of them for real.  Pixels and counters == oracle in each."""
     sc = scenes.config4(160, 90, slices=40, stacks=31, sky=scenes.make_sky(64, 32))

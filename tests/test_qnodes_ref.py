@@ -166,7 +166,7 @@ def slab_failures(nodes, root, grid=Q.GRID, n_rays=300_000, seed=0):
 
 def test_a_forest_too_large_for_the_grid_keeps_the_float_nodes():
     """deep_chain reaches 3^39 ~ 4e18: its cell (~6e13) times the clamped 1 / d of an axis-parallel ray (1e18) times 2^23 overflows float32,
-    and the plane arithmetic returns infinities.  Such a frame is never used (context.cpp requantize), not even with qnodes = 1."""
+    and the plane arithmetic returns infinities.  Such a frame is never used (scene_prep.cpp requantize), not even with qnodes = 1."""
     frame, _ = Q.quantized_nodes(*tree("deep_chain"))
     assert frame[1, :3].max() > Q.MAX_CELL and not Q.in_use(frame, 1) and not Q.in_use(frame, -1)
     for name in SCENES:

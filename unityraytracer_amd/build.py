@@ -18,7 +18,9 @@ HIPCC_FLAGS = [
     "-Xarch_device", "-fno-slp-vectorize",   # v_pk_fma_f32 issues at half rate on gfx950 and its operand pairs cost moves: -0.5 .. -1.4 % frame time (r3_ab_cnodes_noslp.log)
     "-Wall", "-Wno-unused-function",
 ]
-SOURCES = ["kernels.hip", "query.hip", "aov.hip", "denoise.hip", "reproject.hip", "lbvh.hip", "refit.hip", "qnodes.hip", "cullflags.hip", "present.hip", "context.cpp", "blas_builder.cpp", "host_scene.cpp", "host_io.cpp", "host_debug.cpp", "group.cpp"]
+# the sources that see the -D switches of an A/B build (through csrc/experiments.h); build_variant recompiles exactly these
+VARIANT_SOURCES = ["kernels.hip", "context.cpp", "scene_prep.cpp", "frame_batch.cpp", "image_ops.cpp", "blas_builder.cpp"]
+SOURCES = ["kernels.hip", "query.hip", "aov.hip", "denoise.hip", "reproject.hip", "lbvh.hip", "refit.hip", "qnodes.hip", "cullflags.hip", "present.hip", "context.cpp", "scene_prep.cpp", "frame_batch.cpp", "image_ops.cpp", "blas_builder.cpp", "host_scene.cpp", "host_io.cpp", "host_debug.cpp", "group.cpp"]
 
 
 def _newer(target: str, deps) -> bool:
@@ -48,7 +50,7 @@ def build_variant(out: str, defines, verbose: bool = False) -> str:
     objs, jobs = [], []
     for src in srcs:
         name = os.path.basename(src)
-        if name in ("kernels.hip", "context.cpp", "blas_builder.cpp") or not os.path.exists(os.path.join(base, name + ".o")):   # the rest does not depend on the defines
+        if name in VARIANT_SOURCES or not os.path.exists(os.path.join(base, name + ".o")):   # the rest does not depend on the defines
             obj = os.path.join(objdir, name + ".o")
             jobs.append([hipcc] + cflags + ["-c", src, "-o", obj])
         else:

@@ -1,0 +1,295 @@
+// context_impl.h — the context behind the C ABI of include/urt.h, as the translation units that implement it share it:
+//   context.cpp      context lifetime, stream, buffers, textures, readback, uniforms, blits, strip packing, options, counters, debug accessors
+//   scene_prep.cpp   bound buffers -> device scene (full and in-place preparation)
+//   frame_batch.cpp  deferred frames, the Result slab, trace launches (do_dispatch, flush_pending)
+//   image_ops.cpp    ray queries, feature buffers, denoiser, reprojection
+// Private: nothing else includes it.  What crosses the files lives in namespace urtd and stays hidden (-fvisibility=hidden).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <string>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+#include "../../include/urt.h"
+#include "../../include/urt_math.h"
+#include "blas_builder.h"
+#include "kernels.h"
+#include "urt_device.h"
+
+namespace urtd {
+
+struct Buffer {
+  int count = 0, stride = 0;
+  std::vector<uint8_t> host;   // SetData copy (RM:250): the caller keeps ownership of its list
+  bool has_data = false;
+};
+
+struct Texture {
+  int w = 0, h = 0;
+  float4* dev = nullptr;        // where the CURRENT contents live: `own`, or a frame slot of the context's slab (a Result
+                                // texture is renamed to a fresh slot by every batched dispatch)
+  float4* own = nullptr;        // the allocation made at creation (or the caller's memory when external)
+  bool external = false;
+  bool ptr_exposed = false;     // urt_texture_get_info handed out the device pointer: never renamed again
+  // What has written the image since its zero-filled creation.  A dispatch that covers only part of the image may be renamed
+  // to a (zero-filled) slab slot only while the pixels outside its region are still the zeros of creation, i.e. while
+  // nothing but dispatches of that SAME region has written the image.
+  bool other_writes = false;    // SetPixels / Blit destination / unpack_rows
+  int n_regions = 0;            // 0 none yet, 1 = every dispatch so far had region `rg`, 2 = mixed
+  int rg[4] = {0, 0, 0, 0};     // region_w, region_h, first_group_row, row_stride
+};
+
+enum BindSlot { B_MESHOBJECTS, B_VERTICES, B_INDICES, B_NORMALS, B_SPHERES, B_MESHBVH, B_SPHEREBVH, B_COUNT };
+
+}  // namespace urtd
+
+struct urt_context {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipStream_t own_stream = nullptr;
+  std::string err;
+  std::unordered_map<urt_handle, urtd::Buffer> buffers;
+  std::unordered_map<urt_handle, urtd::Texture> textures;
+  urt_handle next_id = 1;
+
+  urt_handle bound[urtd::B_COUNT] = {0, 0, 0, 0, 0, 0, 0};
+  urt_handle t_sky = 0, t_result = 0;
+  float c2w[16] = {0}, invp[16] = {0};
+  bool c2w_set = false, invp_set = false;  // SetMatrix has given the camera matrices (urt_render_aov needs both)
+  float pixel_off[2] = {0, 0};
+  float seed = 0;
+  int num_bounces = 0, num_rays = 0;     // shader uniforms default to 0 until SetInt (RM:780-781)
+
+  // ---- options (urt_set_option; the table of names and ranges is in context.cpp) ------------------------------------------
+  struct Options {
+    int refit = 1;                          // 0 = always prepare from scratch
+    int qnodes = 0;                         // 32-byte quantized nodes in the traversal loop: 0 = off (default: measured -1.3 % on C3 / C3D, +1.3 % on C4 / C5 — the loop waits on the latency of ONE dependent fetch per step, not on its width), 1 = on, -1 = on unless a MeshObject is only a few grid cells wide
+    int count_stats = 0, time_dispatch = 0, kernel_mode = 3;
+    int block_threads = 64, xcd_run = 0 /* auto */, work_shards = 64, frame_group = 64, refill_min = 16, waves_per_cu = 0 /* auto */, blas_min = 0 /* auto */, blas_exit = 0 /* auto */;
+    int pool_k = 2, pool_refill = 32, pool_blas_min = 48, pool_blas_exit = 8, pool_inloop = 16, pool_other_min = 24;   // kernel_mode 4
+    int sched_block = 0;                    // kernel_mode 3: threads per workgroup (64 or 256; 0 = 256 when there is a BVH top to share)
+    int stack_pad = 0;                      // test hook: extra (unused) entries per traversal stack, to reach the > 64 KiB LDS launch path
+    int shade_min = 32, sky_min = 32;       // kernel_mode 3
+    int serve_refill = 16;                  // kernel_mode 5: idle lanes of the traversal service that trigger a claim of waiting rays
+    int front_list = -1;                    // kernel_mode 3: listed FRONT for scenes of <= 12 MeshObjects (-1 auto = on, 0 off)
+    int shade_split = -1;                   // kernel_mode 3: -1 = auto (= split: measured better or equal on C2-C5), 0 = surface hits and misses shaded in one trip
+    int tile_order = -1;                    // persistent modes: order in which the frame's tiles are handed out: 0 bottom strip first, 1 top strip first (a launch then ENDS with the
+                                            // bottom rows), -1 = auto: top first for scenes without triangle meshes (C2: -3.6 % in bench.py, -9 .. -12 % for launches of 1 - 20 frames),
+                                            // bottom first otherwise (C3, driver's 20-frame launch: top first +1.5 %; 64-frame launches, C3D, C4, C5: +-0.4 %) —
+                                            // profiles/r03_logs/r3_probe_tile_order.log; any order draws the same pixels
+    int lds_tlas = 1;                       // kernel_mode 3: object-level heaps, roots and spheres in LDS when small
+    int top_front = -1;                     // kernel_mode 3: top-of-forest walk inside the object-level phase (-1 = when the scene has several meshes)
+    int top_nodes = -1;                     // kernel_mode 3: triangle-BVH nodes kept in LDS (0 = none; -1 = auto: 64, or with the masked object-level phase twice the number of
+                                            // MeshObjects that have a BVH, rounded up to a power of two — there the top is walked lane by lane inside that phase and only its first level pays)
+    int blas_builder = -1;                  // -1 = auto (default): 0 below kGpuBuildTriangles triangles, 3 from there on; 0 = binned SAH on host threads, 1 = Karras radix tree built on the GPU,
+                                            // 2 = the same tree built top-down within a depth budget, 3 = binned SAH on the GPU (csrc/lbvh.hip): the host's trees at a fifth of the time on big scenes
+    int frames_per_launch = 0;              // 0 = auto (own stream: 64 frames per launch, fewer when the Result slots would exceed 8 GiB; caller's stream: 1), 1 = off, 2..64
+    int watchdog_cap = 0;                   // test hook: scheduler trips per wave (0 = auto, scaled with the launch)
+    int lbvh_slack = 6;                     // blas_builder 2: levels of slack in the depth budget (csrc/lbvh.hip k_td_level)
+    int front_cull = 1;                     // object-level cull (urt_math.h tlas_cull; csrc/cullflags.hip): 0 = every popped object is intersected, as the reference does
+    int overlap_launches = 1;               // see "Overlapped launches" below
+  } opt;
+
+  // ---- derived device scene ---------------------------------------------------------------------------------------------
+  bool scene_dirty = true;
+  // what made it dirty: SetData on a bound buffer sets the slot's bit; anything else (binding changes, options) asks for a full
+  // preparation.  When only _MeshObjects / _MeshBVH / _Spheres / _SphereBVH contents changed, the scene is updated in place
+  // (prepare_incremental: moved MeshObjects are refitted on the GPU, csrc/refit.hip)
+  unsigned int dirty_slots = 0;
+  bool dirty_full = true;
+  // Everything that belongs to ONE prepared scene: free_scene frees scene_allocs and assigns Scene{}.
+  struct Scene {
+    urtd::DevScene ds{};
+    std::vector<void*> scene_allocs;
+    struct RefitAux {                       // device-resident (scene_allocs)
+      const float* vertices = nullptr; const int32_t* indices = nullptr;      // copies of _Vertices / _Indices
+      int32_t* parent = nullptr; int32_t* node_mesh = nullptr; int32_t* depth = nullptr;
+      float4* cbox = nullptr; unsigned int* ext = nullptr;
+      float* matrices = nullptr; int32_t* moved = nullptr;
+      bool ready = false;
+    } refit;
+    float4* qbuf = nullptr;                 // frame + quantized nodes (in scene_allocs)
+    float4* cbuf = nullptr;                 // centre / half-extent copy of the nodes (in scene_allocs): DevScene::blas_cnodes
+    float qnode_quality = 0;                // smallest MeshObject extent in grid cells (csrc/qnodes.hip)
+    // urt_render_aov: one float4 per material in the order of DevScene::materials (pack_albedo), in scene_allocs.
+    // Not a DevScene member: DevScene is an argument of every frame kernel, and the camera-matrix loads of k_sched depend on its size
+    const float4* aov_albedo = nullptr;
+    size_t cap_materials = 0, cap_mesh_tlas = 0, cap_sphere_tlas = 0, cap_sphere_pr = 0, cap_aov_albedo = 0;   // float4 capacities of the arrays updated in place
+    int32_t* d_mesh_leaf = nullptr;         // per MeshObject: its heap leaf, or < 0 (in scene_allocs)
+    size_t cap_mesh_leaf = 0;
+    int walk_f4 = 0;                        // float4s of the masked-walk table behind the mesh heap's device copy (0 = none: heap > 31 nodes)
+    int n_blas_nodes = 0;                   // interior nodes of the triangle-BVH forest (all meshes)
+    int n_scene_tris = 0;                   // triangles of the prepared scene
+    int scene_max_depth = 0;
+    int tlas_stack = 2, blas_stack = 2;
+    unsigned int watchdog_steps = 1u << 16;
+    std::vector<int32_t> h_mesh_root, h_small_first;
+    std::vector<uint8_t> prev_mesh_objects; // the _MeshObjects records the scene was prepared from
+  } scene;
+  // These outlive a scene:
+  uint64_t scene_epoch = 0;                 // bumps at every scene preparation
+  float last_prepare_ms = 0;                // host wall time of the last scene preparation (buffers -> device scene)
+  int last_builder = 0;                     // the triangle-BVH builder the last full preparation of a scene WITH MeshObjects used (0..3): one without leaves it as it was
+  uint64_t refitted_meshes = 0, incremental_preps = 0;
+  urtd::BlasCache blas_cache;               // per-MeshObject BVHs of the previous scene (reused when a MeshObject is unchanged)
+  int sched_groups = 0;                     // kernel_mode 3: workgroups per CU the last configuration counts on when fewer than the default fit (0 = default)
+  float4* zero_sky = nullptr;
+
+  // wavefront queues
+  urtd::PathQueues q{};
+  size_t q_capacity = 0, counts_capacity = 0;
+
+  urtd::DevCounters* d_counters = nullptr;  // kCounterShards shards
+  unsigned int* d_next = nullptr;           // persistent mode: frame work counter
+  float4* d_mail = nullptr; size_t mail_slots = 0;   // kernel_mode 5: posted rays (2 float4 per thread of the resident grid)
+  // frame tables of the batched launches: kTableSlots pinned host images + device copies, used round-robin; a slot is reused
+  // once the copy of its previous use has left the host image (event)
+  static constexpr int kTableSlots = 4;
+  urtd::FrameUniforms* h_tables = nullptr; urtd::FrameUniforms* d_tables = nullptr;
+  hipEvent_t table_ev[kTableSlots] = {nullptr, nullptr, nullptr, nullptr};
+  unsigned int table_next = 0;
+  uint64_t pixels_dispatched = 0;
+  int n_cus = 256;
+
+  uint64_t dispatches = 0;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> timing;   // unresolved event pairs
+  float trace_ms = 0;
+
+  // ---- frame batching (kernel_mode 3) --------------------------------------------------------------------------------
+  // A 1080p frame is small for this chip: ~40 % of its kernel time is the drain of the last long paths.
+  // So dispatches are DEFERRED: consecutive frames that differ only in their per-frame uniforms (camera, _PixelOffset,
+  // _Seed) are collected and traced by ONE persistent launch whose lanes move on to the next frame's pixels as soon as
+  // the current frame is handed out.  Each frame's Result goes to its own slot of a slab (the Result texture is renamed
+  // per dispatch), the AdditionShader blits that follow the dispatches are deferred with them and run in order after the
+  // launch.  Everything else that could observe the images flushes first, so the in-order semantics of RM:806-820
+  // stay exactly observable.
+  // An operation deferred behind the batch's frames (flush_pending runs them in program order): urt_blit_add(src@frame -> dst, sample),
+  // urt_blit_add_history(src@frame -> dst, count, max_history), urt_blit(src -> dst) — the present of RM:819 —, urt_texture_pack_rows[_rgb]
+  // (src -> dense).  `frame`: the batch's last frame when it was queued, the slot `src` names when it is the batch's Result texture.
+  enum class OpKind { BlendAdd, BlendHistory, Copy, PackRows };
+  struct PostOp {
+    OpKind kind;
+    int frame;
+    urt_handle src = 0, dst = 0;
+    float sample = 0;                                                             // BlendAdd
+    urt_handle count = 0; float max_history = 0;                                  // BlendHistory
+    void* dense = nullptr; int first_row = 0, row_stride = 1; bool rgb = false;   // PackRows
+    bool touches(urt_handle t) const { return src == t || dst == t || count == t; }
+  };
+  struct Pending {
+    int n = 0, limit = 1;
+    urt_handle tex = 0;                     // the Result texture of the batch
+    uint64_t scene_epoch = 0;
+    urtd::DevScene S{};
+    urtd::FrameParams P{};                  // frame 0's; the frames agree on everything but the table entries
+    urtd::FrameTable T{};
+    int front_mode = 0; bool count = false;
+    std::vector<PostOp> ops;
+  } pend;
+  float4* slab = nullptr;                   // slab_frames x slab_stride float4: Result slots of the batched frames
+  size_t slab_stride = 0;
+  int slab_frames = 0;
+  urt_handle slab_tex = 0;                  // the texture whose `dev` may point into the slab
+  int slab_frames_max = 0;                  // largest batch the Result slab could be allocated for (after out-of-memory retries)
+  size_t slab_oom_stride = 0;               // image size (pixels) for which not even two slots could be allocated
+  std::vector<hipEvent_t> event_pool;       // recycled timing events
+  hipEvent_t ev_switch = nullptr;           // orders the old stream before the new one in urt_context_set_stream
+  uint64_t launches = 0;                    // trace-kernel launches (a batched launch counts once)
+  urt_launch_info last_launch{};            // the last trace launch of this context (urt_debug_launch_info)
+  // a wave that left a persistent kernel through one of its caps has not written its pixels: the kernels raise this host-mapped
+  // word (kernels.hip report_watchdog) and the next synchronising call fails with URT_ERR_WATCHDOG
+  unsigned int* h_trip_flag = nullptr;      // pinned, device-visible
+  unsigned int* d_trip_flag = nullptr;      // its device address
+  // Overlapped launches (option "overlap_launches", flush_pending): a host that SUBMITS every frame (urt_flush, a present into an external
+  // texture) produces one-frame launches, and a one-frame launch is mostly ramp and drain.  Small launches therefore alternate between two trace streams and take their Result slots
+  // round-robin from the slab, so that launch L+1 fills the wave slots launch L's draining waves give back; the blends / presents /
+  // readbacks stay on the main stream, in program order, each behind its own launch.
+  static constexpr int kOverlapFrames = 8;  // launches of up to this many frames take part
+  hipStream_t trace_q[2] = {nullptr, nullptr};
+  hipEvent_t trace_done[2] = {nullptr, nullptr}, pre_ev[2] = {nullptr, nullptr}, dep_ev = nullptr;
+  unsigned int* d_next2 = nullptr;          // the second launch in flight needs work counters of its own
+  unsigned int trace_parity = 0;
+  bool main_touched = true;                 // something other than the frame loop's own blends / presents / readbacks was enqueued on the main stream since the last launch
+  int slab_cursor = 0, prev_base = 0, prev_n = 0;
+  uint64_t overlapped_launches = 0;
+
+  // pipelined readback (urt_texture_read_begin / _end): kReadSlots snapshots in flight, each a device copy + a pinned host image
+  static constexpr int kReadSlots = 3;
+  struct ReadSlot { float4* dev = nullptr; float4* host = nullptr; size_t pixels = 0; size_t bytes = 0; int format = 0; hipEvent_t snap = nullptr, done = nullptr; bool busy = false; uint64_t ticket = 0; } rslot[kReadSlots];
+  float* srgb_first = nullptr;                // device: first float of every 8-bit sRGB code (csrc/present.hip), made at the first RGBA8 readback
+  hipStream_t copy_stream = nullptr;
+  uint64_t read_next = 0;
+
+  // urt_ray_query (host memory): grow-only device scratch for the rays and the results, q_cap rays each
+  float4* q_rays = nullptr; float4* q_out = nullptr; size_t q_cap = 0;
+  // urt_denoise: grow-only device scratch of 3 float4 images (guide, two colour images) of dn_cap pixels each
+  float4* dn_scratch = nullptr; size_t dn_cap = 0;
+  // urt_reproject_objects: grow-only device copies of the mesh and the sphere motion table, mo_cap[k] bytes each
+  float4* mo_table[2] = {nullptr, nullptr}; size_t mo_cap[2] = {0, 0};
+};
+
+namespace urtd {
+
+using PostOp = urt_context::PostOp;
+using OpKind = urt_context::OpKind;
+
+int fail(urt_context* ctx, int code, const std::string& msg);   // sets urt_last_error(ctx) (ctx NULL: the creation error); returns code
+
+#define URT_HIP(ctx, expr)                                                                         \
+  do {                                                                                             \
+    hipError_t e__ = (expr);                                                                       \
+    if (e__ != hipSuccess)                                                                         \
+      return fail(ctx, e__ == hipErrorOutOfMemory ? URT_ERR_OUT_OF_MEMORY : URT_ERR_HIP,           \
+                  std::string(#expr) + ": " + hipGetErrorString(e__));                            \
+  } while (0)
+
+#define URT_GUARD_BEGIN try {
+#define URT_GUARD_END(ctx)                                                                         \
+  } catch (const std::bad_alloc&) { return fail(ctx, URT_ERR_OUT_OF_MEMORY, "host allocation failed"); } \
+  catch (const std::exception& ex) { return fail(ctx, URT_ERR_INVALID_ARGUMENT, ex.what()); }        \
+  catch (...) { return fail(ctx, URT_ERR_INVALID_ARGUMENT, "unknown exception"); }
+
+inline hipStream_t touch(urt_context* ctx) { ctx->main_touched = true; return ctx->stream; }
+
+inline Texture* find_texture(urt_context* ctx, urt_handle h) {
+  auto it = ctx->textures.find(h);
+  return it == ctx->textures.end() ? nullptr : &it->second;
+}
+
+inline const Buffer* bound_buffer(urt_context* ctx, int slot) {
+  urt_handle h = ctx->bound[slot];
+  if (!h) return nullptr;
+  auto it = ctx->buffers.find(h);
+  if (it == ctx->buffers.end() || !it->second.has_data || it->second.count == 0) return nullptr;
+  return &it->second;
+}
+
+inline int heap_levels(int n) { int l = 0; while (n > 0) { l++; n >>= 1; } return l; }   // floor(log2 n) + 1
+
+// max_history of urt_reproject / urt_blit_add_history: 0 (unlimited) or >= 1
+inline bool valid_max_history(float v) { return !std::isnan(v) && (v == 0.0f || v >= 1.0f); }
+
+// context.cpp
+int check_watchdog(urt_context* ctx);
+int strip_count(int group_rows, int first_row, int row_stride);
+// scene_prep.cpp
+int prepare_scene(urt_context* ctx);
+void free_scene(urt_context* ctx);
+bool build_walk_table(const Buffer* heap, int n_meshes, const std::vector<int32_t>& mesh_root, const std::vector<int32_t>& small_first,
+                      std::vector<float>& out);
+// frame_batch.cpp
+int flush_pending(urt_context* ctx);
+int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_row, int row_stride);
+int bind_sky(urt_context* ctx, DevScene& S);
+bool in_slab(urt_context* ctx, const Texture& t);
+int detach_from_slab(urt_context* ctx, Texture& t);
+int resolve_timing(urt_context* ctx);
+
+}  // namespace urtd

@@ -11,7 +11,7 @@
 //     (k_pack_rows), the peers' strips travel to rank 0 with hipMemcpyPeerAsync — point-to-point over xGMI, each peer on its own
 //     link to the root, no ring — and rank 0 de-interleaves them into a full image.  No host synchronisation: streams are
 //     ordered by events.  Gathers are queued behind the ranks' deferred (batched) frames and submitted in bursts, so the
-//     per-rank frame batching of context.cpp keeps working under a gather-every-frame protocol.
+//     per-rank frame batching of frame_batch.cpp keeps working under a gather-every-frame protocol.
 // The device list may name one ordinal several times (N contexts on one card): that is how the path is tested on a 1-GPU box.
 #include <hip/hip_runtime.h>
 

@@ -1,0 +1,294 @@
+// image_ops.cpp — the entry points of include/urt.h that work on whole images or ray batches next to the frame loop: ray queries,
+// feature buffers, the denoiser, temporal reprojection.
+#include "experiments.h"
+#include "context_impl.h"
+
+#include "query.h"
+#include "aov.h"
+#include "denoise.h"
+#include "reproject.h"
+
+using namespace urtd;
+
+namespace {
+
+// Checks the image-space entry points share; each caller runs them in its own order (it decides which error a doubly-wrong call reports).
+struct TexArg { urt_handle h; const char* name; bool optional; };   // name NULL: the message names no argument
+
+// t[k] = the texture of a[k] (NULL for an optional one that is not given).  dup_msg: a handle given twice fails with it.
+int resolve_textures(urt_context* ctx, const char* prefix, const TexArg* a, int n, Texture** t, const char* dup_msg = nullptr) {
+  for (int k = 0; k < n; k++) {
+    t[k] = nullptr;
+    if (a[k].optional && !a[k].h) continue;
+    for (int j = 0; dup_msg && j < k; j++)
+      if (a[j].h == a[k].h) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(prefix) + ": " + dup_msg);
+    t[k] = find_texture(ctx, a[k].h);
+    if (!t[k]) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string(prefix) + ": unknown " + (a[k].name ? std::string(a[k].name) + " " : "") + "texture handle");
+  }
+  return URT_OK;
+}
+
+// every texture given has the size of t[0]
+int check_same_size(urt_context* ctx, const char* prefix, Texture* const* t, int n) {
+  for (int k = 1; k < n; k++)
+    if (t[k] && (t[k]->w != t[0]->w || t[k]->h != t[0]->h)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(prefix) + ": the textures differ in size");
+  return URT_OK;
+}
+
+// the image kernels run 16 rows per workgroup and a grid holds 65535 of them
+int check_height(urt_context* ctx, const char* prefix, const char* what, int height) {
+  if ((height + 15) / 16 > 65535) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(prefix) + ": " + what + " taller than 1048560 pixels");
+  return URT_OK;
+}
+
+// the outputs a[first..n) that are given are no other image of the call and not the sky
+int check_outputs(urt_context* ctx, const char* prefix, const TexArg* a, int first, int n) {
+  for (int k = first; k < n; k++) {
+    if (!a[k].h) continue;
+    for (int j = 0; j < n; j++)
+      if (j != k && a[j].h == a[k].h)
+        return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(prefix) + ": the output " + a[k].name + " is also " + a[j].name);
+    if (a[k].h == ctx->t_sky)
+      return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(prefix) + ": the output " + a[k].name + " is the texture bound as _SkyboxTexture");
+  }
+  return URT_OK;
+}
+
+// Grow-only device scratch: *p holds *cap units; when `need` exceeds them it is replaced by an allocation of `bytes` (after the work
+// queued on the stream, which may still use the old one).  On failure *p is NULL, *cap 0 and the error names `what`.
+int grow_scratch(urt_context* ctx, void** p, size_t* cap, size_t need, size_t bytes, const char* what) {
+  if (need <= *cap) return URT_OK;
+  if (*p) {
+    URT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+  }
+  hipError_t e = hipMalloc(p, bytes);
+  if (e == hipSuccess) { *cap = need; return URT_OK; }
+  (void)hipGetLastError();
+  *p = nullptr;
+  return fail(ctx, e == hipErrorOutOfMemory ? URT_ERR_OUT_OF_MEMORY : URT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+}  // namespace
+
+extern "C" {
+
+/* ---- ray queries ---- */
+// Both entry points read the scene bound to kernel 0 as it is now: a stale scene is prepared first (after the deferred frames that read
+// the old one), as do_dispatch does; otherwise the deferred batch stays deferred — a query only reads the scene.  The query is enqueued
+// on the context's stream WITHOUT marking it touched (the frame loop's overlap bookkeeping, counters and launches are not affected).
+static int query_prepare(urt_context* ctx, const void* rays, int n, const void* out, int flags) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (n < 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "ray query: negative ray count");
+  if (flags != URT_QUERY_CLOSEST && flags != URT_QUERY_ANY) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "ray query: unknown flags");
+  if (n > 0 && (!rays || !out)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "ray query: rays / out is NULL");
+  if (n == 0) return URT_OK;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  if (ctx->scene_dirty) {
+    int rc = flush_pending(ctx); if (rc) return rc;       // the deferred frames read the scene that is about to be replaced
+    rc = prepare_scene(ctx); if (rc) return rc;
+  }
+  return URT_OK;
+}
+
+int urt_ray_query(urt_context* ctx, const urt_Ray* rays, int n, void* out, int flags) {
+  URT_GUARD_BEGIN
+  int rc = query_prepare(ctx, rays, n, out, flags);
+  if (rc || n == 0) return rc;
+  if ((size_t)n > ctx->q_cap) {                           // grow-only; no query still reads the old pair (this form synchronises before it returns)
+    if (ctx->q_rays) { (void)hipFree(ctx->q_rays); ctx->q_rays = nullptr; }
+    if (ctx->q_out) { (void)hipFree(ctx->q_out); ctx->q_out = nullptr; }
+    ctx->q_cap = 0;
+    URT_HIP(ctx, hipMalloc((void**)&ctx->q_rays, (size_t)n * sizeof(urt_Ray)));
+    URT_HIP(ctx, hipMalloc((void**)&ctx->q_out, (size_t)n * sizeof(urt_RayHit)));
+    ctx->q_cap = (size_t)n;
+  }
+  const size_t out_bytes = (size_t)n * (flags == URT_QUERY_ANY ? sizeof(int32_t) : sizeof(urt_RayHit));
+  URT_HIP(ctx, hipMemcpyAsync(ctx->q_rays, rays, (size_t)n * sizeof(urt_Ray), hipMemcpyHostToDevice, ctx->stream));
+  URT_HIP(ctx, launch_query(ctx->scene.ds, ctx->scene.tlas_stack, ctx->scene.blas_stack, ctx->q_rays, n, ctx->q_out, flags == URT_QUERY_ANY, ctx->stream));
+  URT_HIP(ctx, hipMemcpyAsync(out, ctx->q_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  URT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return check_watchdog(ctx);
+  URT_GUARD_END(ctx)
+}
+
+int urt_ray_query_device(urt_context* ctx, const void* d_rays, int n, void* d_out, int flags) {
+  URT_GUARD_BEGIN
+  int rc = query_prepare(ctx, d_rays, n, d_out, flags);
+  if (rc || n == 0) return rc;
+  if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & (flags == URT_QUERY_ANY ? 3u : 15u)))
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "ray query: d_rays must be 16-byte aligned, d_out 16-byte (closest hit) / 4-byte (any hit) aligned");
+  URT_HIP(ctx, launch_query(ctx->scene.ds, ctx->scene.tlas_stack, ctx->scene.blas_stack, (const float4*)d_rays, n, d_out, flags == URT_QUERY_ANY, ctx->stream));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+/* ---- feature buffers ---- */
+// Everything else that could observe the images flushes first: the deferred frames are submitted, then a stale scene is prepared, then
+// the kernel is enqueued on the main stream (marked touched, as urt_texture_set_pixels does).  Every argument is checked before anything
+// is submitted or written.  The counters are not changed.
+int urt_render_aov(urt_context* ctx, urt_handle hit, urt_handle normal, urt_handle albedo, urt_handle id, int flags) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  if (flags != URT_AOV_PIXEL_CENTER && flags != URT_AOV_FRAME_RAY) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "render_aov: unknown flags");
+  const TexArg a[4] = {{hit, nullptr, true}, {normal, nullptr, true}, {albedo, nullptr, true}, {id, nullptr, true}};
+  Texture* t[4];
+  int width = 0, height = 0, n = 0;
+  if (int rc = resolve_textures(ctx, "render_aov", a, 4, t, "a texture is given for two targets")) return rc;
+  for (int k = 0; k < 4; k++) {
+    if (!t[k]) continue;
+    if (a[k].h == ctx->t_sky) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "render_aov: a target is the texture bound as _SkyboxTexture");
+    if (n++ == 0) { width = t[k]->w; height = t[k]->h; }
+    else if (t[k]->w != width || t[k]->h != height) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "render_aov: the targets differ in size");
+  }
+  if (n == 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "render_aov: no target given");
+  if (int rc = check_height(ctx, "render_aov", "targets", height)) return rc;
+  if (!ctx->c2w_set || !ctx->invp_set)
+    return fail(ctx, URT_ERR_UNBOUND, "render_aov: _CameraToWorld / _CameraInverseProjection not set");
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  if (ctx->scene_dirty) { int rc = prepare_scene(ctx); if (rc) return rc; }
+  DevScene S = ctx->scene.ds;
+  { int rc = bind_sky(ctx, S); if (rc) return rc; }
+  AovCamera C{};
+  std::memcpy(C.c2w, ctx->c2w, sizeof C.c2w);
+  std::memcpy(C.invp, ctx->invp, sizeof C.invp);
+  C.pixel_off_x = ctx->pixel_off[0]; C.pixel_off_y = ctx->pixel_off[1];
+  C.seed = ctx->seed;
+  C.frame_ray = flags == URT_AOV_FRAME_RAY ? 1 : 0;
+  AovTargets T{};
+  T.hit = t[0] ? t[0]->dev : nullptr; T.normal = t[1] ? t[1]->dev : nullptr;
+  T.albedo = t[2] ? t[2]->dev : nullptr; T.id = t[3] ? t[3]->dev : nullptr;
+  T.width = width; T.height = height;
+  for (int k = 0; k < 4; k++) if (t[k]) t[k]->other_writes = true;
+  URT_HIP(ctx, launch_aov(S, ctx->scene.aov_albedo, ctx->scene.tlas_stack, ctx->scene.blas_stack, C, T, touch(ctx)));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+/* ---- denoising ---- */
+// Every argument is checked and the scratch is grown before anything is submitted: on an error nothing is enqueued.  Then the deferred
+// frames are submitted (src is usually a deferred blit's destination) and the passes are enqueued on the main stream.  The scene is not
+// read and the counters are not changed.
+int urt_denoise(urt_context* ctx, urt_handle src, urt_handle dst, urt_handle hit, urt_handle normal, urt_handle albedo,
+                const urt_DenoiseParams* params) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  urt_DenoiseParams P{URT_DENOISE_DEFAULT_ITERATIONS, URT_DENOISE_DEFAULT_SIGMA_COLOR, URT_DENOISE_DEFAULT_SIGMA_NORMAL,
+                      URT_DENOISE_DEFAULT_SIGMA_DEPTH};
+  if (params) P = *params;
+  if (P.iterations < 1 || P.iterations > 5) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "denoise: iterations must be 1..5");
+  if (std::isnan(P.sigma_color) || std::isnan(P.sigma_normal) || std::isnan(P.sigma_depth))
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "denoise: a sigma is NaN");
+  const TexArg a[5] = {{src, "src", false}, {dst, "dst", false}, {hit, "hit", false}, {normal, "normal", false},
+                       {albedo, "albedo", true}};                  // no albedo: no demodulation
+  Texture* t[5];
+  if (int rc = resolve_textures(ctx, "denoise", a, 5, t)) return rc;
+  if (dst == hit || dst == normal || dst == albedo)
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "denoise: dst is one of the guide textures");
+  if (dst == ctx->t_sky) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "denoise: dst is the texture bound as _SkyboxTexture");
+  const int width = t[0]->w, height = t[0]->h;
+  if (int rc = check_same_size(ctx, "denoise", t, 5)) return rc;
+  if (int rc = check_height(ctx, "denoise", "textures", height)) return rc;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t n = (size_t)width * (size_t)height;
+  if (int rc = grow_scratch(ctx, (void**)&ctx->dn_scratch, &ctx->dn_cap, n, 3 * n * sizeof(float4), "denoise: scratch allocation")) return rc;
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  DenoiseImages I{};                                               // device pointers after the flush (a Result texture may be renamed)
+  I.src = t[0]->dev; I.dst = t[1]->dev; I.hit = t[2]->dev; I.normal = t[3]->dev; I.albedo = t[4] ? t[4]->dev : nullptr;
+  I.scratch = ctx->dn_scratch; I.width = width; I.height = height;
+  DenoiseSettings S{P.iterations, P.sigma_color, P.sigma_normal, P.sigma_depth};
+  t[1]->other_writes = true;
+  URT_HIP(ctx, launch_denoise(I, S, touch(ctx)));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+/* ---- temporal reprojection ---- */
+// Every argument is checked before anything is submitted: on an error nothing is enqueued.  Then the deferred frames are submitted
+// (prev_color is usually a deferred blend's destination) and k_reproject is enqueued on the main stream.  The scene is not read and the
+// counters are not changed.  with_motion: urt_reproject_objects, whose tables (ComputeBuffers: host copies) are uploaded on the same
+// stream in front of k_reproject_objects; without a table given the call is urt_reproject's, kernel included.
+static int reproject_impl(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params,
+                          const urt_ReprojectMotion* motion, bool with_motion) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (!images || !params) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: images or params is NULL");
+  URT_GUARD_BEGIN
+  const urt_ReprojectParams P = *params;
+  urt_ReprojectMotion Mo{};
+  if (with_motion && motion) Mo = *motion;
+  const Buffer* tab[2] = {nullptr, nullptr};
+  if (with_motion) {
+    if (Mo.flags != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: motion flags must be 0");
+    if (!valid_max_history(Mo.moved_max_history)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: moved_max_history must be 0 or >= 1");
+    const urt_handle th[2] = {Mo.mesh_motion, Mo.sphere_motion};
+    for (int k = 0; k < 2; k++) {
+      if (!th[k]) continue;
+      auto it = ctx->buffers.find(th[k]);
+      if (it == ctx->buffers.end())
+        return fail(ctx, URT_ERR_INVALID_HANDLE, std::string("reproject: unknown ") + (k ? "sphere_motion" : "mesh_motion") + " buffer handle");
+      if (it->second.stride != (int)sizeof(urt_ObjectMotion))
+        return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("reproject: the stride of ") + (k ? "sphere_motion" : "mesh_motion") + " is not 48");
+      tab[k] = &it->second;
+    }
+  }
+  if (P.flags != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: flags must be 0");
+  if (std::isnan(P.normal_threshold) || std::isnan(P.plane_threshold)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: a threshold is NaN");
+  if (!valid_max_history(P.max_history)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: max_history must be 0 or >= 1");
+  enum { kInputs = 8, kImages = 11 };
+  const TexArg a[kImages] = {{images->prev_color, "prev_color", false}, {images->prev_count, "prev_count", false}, {images->prev_hit, "prev_hit", false},
+                             {images->prev_normal, "prev_normal", false}, {images->prev_id, "prev_id", false}, {images->hit, "hit", false},
+                             {images->normal, "normal", false}, {images->id, "id", false}, {images->color, "color", false},
+                             {images->count, "count", false}, {images->motion, "motion", true}};   // no motion image wanted: 0
+  Texture* t[kImages];
+  if (int rc = resolve_textures(ctx, "reproject", a, kImages, t)) return rc;
+  const int width = t[0]->w, height = t[0]->h;
+  if (int rc = check_same_size(ctx, "reproject", t, kImages)) return rc;
+  if (int rc = check_outputs(ctx, "reproject", a, kInputs, kImages)) return rc;
+  if (int rc = check_height(ctx, "reproject", "textures", height)) return rc;
+  if (!ctx->c2w_set || !ctx->invp_set)
+    return fail(ctx, URT_ERR_UNBOUND, "reproject: _CameraToWorld / _CameraInverseProjection never set (SetMatrix, RM:774-775)");
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  ReprojectImages I{};                                             // device pointers after the flush (a Result texture may be renamed)
+  I.prev_color = t[0]->dev; I.prev_count = t[1]->dev; I.prev_hit = t[2]->dev; I.prev_normal = t[3]->dev; I.prev_id = t[4]->dev;
+  I.hit = t[5]->dev; I.normal = t[6]->dev; I.id = t[7]->dev;
+  I.color = t[8]->dev; I.count = t[9]->dev; I.motion = t[10] ? t[10]->dev : nullptr;
+  I.width = width; I.height = height;
+  ReprojectSettings S{};
+  std::memcpy(S.m, P.prev_world_to_clip, sizeof S.m);
+  std::memcpy(S.c2w, ctx->c2w, sizeof S.c2w);
+  std::memcpy(S.invp, ctx->invp, sizeof S.invp);
+  S.max_history = P.max_history; S.normal_threshold = P.normal_threshold; S.plane_threshold = P.plane_threshold;
+  if (tab[0] || tab[1]) {
+    ReprojectMotion T{};
+    for (int k = 0; k < 2; k++) {
+      if (!tab[k]) continue;
+      const size_t bytes = (size_t)tab[k]->count * sizeof(urt_ObjectMotion);
+      if (int rc = grow_scratch(ctx, (void**)&ctx->mo_table[k], &ctx->mo_cap[k], bytes, bytes, "reproject: motion table allocation")) return rc;
+      URT_HIP(ctx, hipMemcpyAsync(ctx->mo_table[k], tab[k]->host.data(), bytes, hipMemcpyHostToDevice, touch(ctx)));
+    }
+    T.mesh = tab[0] ? ctx->mo_table[0] : nullptr; T.n_mesh = tab[0] ? tab[0]->count : 0;
+    T.sphere = tab[1] ? ctx->mo_table[1] : nullptr; T.n_sphere = tab[1] ? tab[1]->count : 0;
+    T.moved_max_history = Mo.moved_max_history;
+    for (int k = kInputs; k < kImages; k++) if (t[k]) t[k]->other_writes = true;
+    URT_HIP(ctx, launch_reproject_objects(I, S, T, touch(ctx)));
+    return URT_OK;
+  }
+  for (int k = kInputs; k < kImages; k++) if (t[k]) t[k]->other_writes = true;
+  URT_HIP(ctx, launch_reproject(I, S, touch(ctx)));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+int urt_reproject(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params) {
+  return reproject_impl(ctx, images, params, nullptr, false);
+}
+
+int urt_reproject_objects(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params,
+                          const urt_ReprojectMotion* motion) {
+  return reproject_impl(ctx, images, params, motion, true);
+}
+
+}  // extern "C"

@@ -105,7 +105,7 @@ __device__ __forceinline__ HitRec trace(const DevScene& S, v3 o, v3 d, int* tl, 
 // ---------------------------------------------------------------------------------------------------
 // Shade — RS:386-428 (+ SampleHemisphere RS:103-111, GetTangentSpace RS:89-100, sky lookup A.11)
 // ---------------------------------------------------------------------------------------------------
-// inv_alpha1 = 1 / (alpha + 1) (RS:104), precomputed per material on the host (context.cpp pack_material); 0.5 for the diffuse lobe
+// inv_alpha1 = 1 / (alpha + 1) (RS:104), precomputed per material on the host (scene_prep.cpp pack_material); 0.5 for the diffuse lobe
 __device__ __forceinline__ v3 sample_hemisphere(v3 normal, float inv_alpha1, float& seed, float px, float py) {
   float cosTheta = f_pow(rand_next(seed, px, py), inv_alpha1);
   float sinTheta = f_sqrt(1.0f - cosTheta * cosTheta);
@@ -157,7 +157,7 @@ __device__ __forceinline__ bool shade_surface(const DevScene& S, const HitRec& h
       n = normalize((n0 * w) + (n1 * h.u) + (n2 * h.v));
       mat = S.n_spheres + as_int(S.tri_verts[3 * (size_t)h.id() + 1].w);
     }
-    // what RS:390-395, 401, 404-405, 411 derive from the material alone comes precomputed (context.cpp pack_material)
+    // what RS:390-395, 401, 404-405, 411 derive from the material alone comes precomputed (scene_prep.cpp pack_material)
     const float4* m = S.materials + 4 * (size_t)mat;
     float4 m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3];
     float specChance = m0.w, bothChances = m1.w, diffChance = m2.w;
@@ -771,7 +771,7 @@ __device__ __forceinline__ int front_listed(const DevScene& S, const FrameParams
 //     T = the MeshObjects to test: popped leaves from the first popped-AND-hit leaf on in pop order (`tests` is never reset: A.5),
 // and keeps T in one register: bit order = the reference's test order.  The wave then works the masks off exactly as front_listed
 // works its lists off (inline triangle tests for lanes at a single-leaf MeshObject, one BVH-top walk for lanes at a big one).
-// W = the walk table in LDS (context.cpp build_walk_table).  cs = T.  Returns 0 / 1 / 2 like front_listed.
+// W = the walk table in LDS (scene_prep.cpp build_walk_table).  cs = T.  Returns 0 / 1 / 2 like front_listed.
 struct WalkLds {
   const int* hdr = nullptr;            // [0] n_eval, levels, interior mask, exist mask  [4] leaf_any, leaf_valid  [8..11] depth masks  [12..15] left-child shifts
   const int* pos_tab = nullptr;        // [2p] triangle-BVH root of the object at position p, [2p+1] its first triangle in small_tris or -1
@@ -910,7 +910,7 @@ __device__ __forceinline__ int front_masked(const DevScene& S, const FrameParams
 // ---------------------------------------------------------------------------------------------------
 enum : int { ST_DEAD = 0, ST_FRONT = 1, ST_RESUME = 2, ST_BLAS = 3, ST_SHADE = 4, ST_SKY = 5 };
 // Every persistent kernel leaves its scheduler loop after P.sched_trips trips per wave, whatever the data (a frame needs ~1e3-1e5;
-// the host scales the cap with the launch: frames x rays x bounces, context.cpp).  A wave that leaves that way — or through the
+// the host scales the cap with the launch: frames x rays x bounces, frame_batch.cpp).  A wave that leaves that way — or through the
 // per-phase traversal cap — counts itself in DevCounters::watchdog and raises the host-visible flag: its pixels are missing.
 __device__ __forceinline__ void report_watchdog(const FrameParams& P, DevCounters* shard) {
   atomicAdd(&shard->watchdog, 1ull);
@@ -1969,7 +1969,7 @@ __global__ __launch_bounds__(256) void k_blit_add(const float4* __restrict__ src
 // k_blit_add launches, with 16 (n + 2) bytes of traffic per pixel instead of 48 n.
 // `present` (may be null): the image the host presents the accumulated frame to after every blend (Graphics.Blit(_converged,
 // destination), RM:819).  Of the n presents of a fused run only the last is observable (every observer of `present` submits the
-// deferred work first, context.cpp), so the last blended value is stored to both images: the bytes a copy of dst would carry.
+// deferred work first, frame_batch.cpp), so the last blended value is stored to both images: the bytes a copy of dst would carry.
 struct BlendSamples { float s[kMaxFramesPerLaunch]; };
 __global__ __launch_bounds__(256) void k_blit_add_multi(const float4* __restrict__ src, size_t frame_stride, int n, BlendSamples smp,
                                                         float4* __restrict__ dst, float4* __restrict__ present, size_t npix) {

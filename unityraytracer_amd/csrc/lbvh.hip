@@ -19,7 +19,7 @@
 //   8. k_emit_nodes / k_emit_tris   64-byte two-child nodes with padded boxes, 48-byte triangle and normal records in
 //                     sorted (= leaf) order — the formats of urt_device.h, so the trace kernels do not know which builder ran.
 // Round 4 added two more builders on the same inputs and outputs ("blas_builder" 2 and 3; the default -1 = auto picks 3 for scenes of
-// 200,000 triangles or more, context.cpp prepare_scene):
+// 200,000 triangles or more, scene_prep.cpp prepare_scene):
 //   2  the radix tree built TOP-DOWN, one launch per level, with a depth budget (k_td_roots / k_td_level instead of k_karras): the
 //      traversal stacks live in LDS, and a 30-level Karras tree costs workgroups per CU;
 //   3  BINNED SAH, the host builder's algorithm level by level (k_sah_*): bins filled with LDS-privatised atomics, one thread per node

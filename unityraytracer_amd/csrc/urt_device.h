@@ -1,4 +1,4 @@
-// urt_device.h — device-side scene/frame descriptors shared by the host library (context.cpp) and the
+// urt_device.h — device-side scene/frame descriptors shared by the host library (context_impl.h) and the
 // HIP kernels (kernels.hip).  Layouts are the library's own (SoA / 16-byte records for coalesced
 // dwordx4 loads); they are derived on upload from the reference layouts of urt_types.h.
 #pragma once
@@ -23,7 +23,7 @@ struct DevScene {
   // spheres (RS:51-55): position.xyz + radius; materials as 3 x float4
   const float4* sphere_pr;   int n_spheres;
   // materials: spheres [0, n_spheres), then the mesh objects, then the ground plane (RS:164-170); 4 x float4 each, holding what
-  // Shade derives from the material alone, precomputed on the host (context.cpp pack_material):
+  // Shade derives from the material alone, precomputed on the host (scene_prep.cpp pack_material):
   //   [4i] (1/diffChance) * albedo', specChance   [4i+1] (1/specChance) * specular, specChance + diffChance
   //   [4i+2] emission, diffChance                  [4i+3] alpha, 1/(alpha+1), (alpha+2)/(alpha+1), 0
   const float4* materials;
@@ -75,15 +75,15 @@ struct FrameParams {
   int lds_small;            // mode 3: triangle records of the single-leaf MeshObjects in LDS (needs lds_mesh) (0/1)
   int lds_mesh, lds_sphere; // mode 3: keep the object-level mesh heap + roots / sphere heap + spheres in LDS (0/1)
   int walk_f4;              // mode 3, masked FRONT (front mode 3): float4s of the walk table behind the mesh heap's device copy, kept in LDS
-                            // instead of the heap itself (context.cpp build_walk_table); 0 = not in use
+                            // instead of the heap itself (scene_prep.cpp build_walk_table); 0 = not in use
   int serve;                // mode 5: the traversal phase is a service shared by the waves of a workgroup (kernels.hip k_serve) (0/1)
   int pool_inloop;          // modes 4, 5: idle lanes that trigger a re-feed of the traversal phase from the waiting rays (1..64)
   int pool_other_min;       // mode 4: lanes of FRONT / SHADE work that make those phases worth a trip while rays queue for the BVH
   unsigned int watchdog_steps;  // cap on traversal trips per scheduled BLAS phase: a few times (nodes + leaves) of the scene
-  unsigned int sched_trips;     // persistent modes: cap on scheduler trips per wave, scaled with the launch (frames x rays x bounces; context.cpp)
+  unsigned int sched_trips;     // persistent modes: cap on scheduler trips per wave, scaled with the launch (frames x rays x bounces; frame_batch.cpp)
   unsigned int* trip_flag;      // host-mapped word: a wave that leaves through a cap adds 1 (the next synchronising call reports URT_ERR_WATCHDOG)
   // mode 3, frame batching: ONE launch traces n_frames consecutive frames of the same scene/resolution (the library defers
-  // dispatches, context.cpp).  Frame f's uniforms are entry f of the launch's table in device memory; its Result image starts
+  // dispatches, frame_batch.cpp).  Frame f's uniforms are entry f of the launch's table in device memory; its Result image starts
   // at result + f * frame_stride.  The c2w/invp/pixel_off/seed above are those of frame 0 (all the other kernel modes read).
   int n_frames;                 // >= 1
   unsigned int frame_stride;    // float4 elements between the Result images of consecutive frames of the launch
@@ -98,7 +98,7 @@ struct FrameUniforms {
   float seed;               // _Seed
   float pad;
 };
-static constexpr int kMaxFramesPerLaunch = 64;      // the table lives in device memory (context.cpp stages it through pinned host slots): 64 x 144 B
+static constexpr int kMaxFramesPerLaunch = 64;      // the table lives in device memory (frame_batch.cpp stages it through pinned host slots): 64 x 144 B
 struct FrameTable { FrameUniforms f[kMaxFramesPerLaunch]; };   // host-side image of one launch's table
 
 static constexpr unsigned int kWorkShards = 64;   // work counters of the persistent kernels (power of two), 128 B apart
