@@ -199,6 +199,35 @@ enum { URT_QUERY_CLOSEST = 0, URT_QUERY_ANY = 1 };
 URT_API int urt_ray_query(urt_context* ctx, const urt_Ray* rays, int n, void* out, int flags);
 URT_API int urt_ray_query_device(urt_context* ctx, const void* d_rays, int n, void* d_out, int flags);
 
+/* ---- radiance queries --------------------------------------------------------------------- */
+/* Batched "how much light arrives along this ray?": path-traced samples with the scene's own materials, emission and sky — the whole of
+ * CSMain's per-pixel loop (RS:440-468) outside a frame.  Light probes, irradiance volumes and lightmap texels (rays), and extra samples
+ * for chosen pixels of the bound camera, e.g. the ones urt_reproject left without history (pixels).  out = n RGBA32F texels.  All
+ * arithmetic is the normative float32 of urt_math.h; Trace and Shade are the frame kernels' own.
+ *  - URT_RADIANCE_RAYS: in = urt_PathRay[n].  Query i: seed = in[i].seed, avg = 0; for each of the `samples` samples: res = 0,
+ *    energy = 1, (o, d) = (origin, direction), then up to `bounces` iterations of  h = Trace(o, d); if (!Shade(...)) break;  with
+ *    rand() = rand_next(seed, px, py); then avg += res.  out[i] = (avg.x / (float)samples, avg.y / ..., avg.z / ..., 1.0f).  The seed
+ *    carries over from one sample to the next, as between a pixel's rays (RS:444); no camera-ray draws are made.
+ *  - URT_RADIANCE_PIXELS: in = urt_PathPixel[n].  out[i] = the texel a frame dispatched now with _numRays = samples and
+ *    _numBounces = bounces would write to Result[y * width + x]: the uniforms bound at call time (_CameraToWorld,
+ *    _CameraInverseProjection, _PixelOffset, _Seed), the size of the texture bound as Result; each sample draws its two jitter rand()
+ *    values and runs CreateCameraRay (RS:142-153, 448-449).  With samples == _numRays and bounces == _numBounces the output equals the
+ *    frame's pixel bit for bit.
+ *  - samples 1..4096; bounces 0..64 (0: every output is (0, 0, 0, 1)); n == 0: URT_OK, nothing is launched.
+ *  - scene, ordering and counters as urt_ray_query: a changed scene is prepared first (after the deferred frames that read the old one);
+ *    otherwise deferred frames stay deferred — unless pending work writes the texture bound as _SkyboxTexture, which is then submitted
+ *    first.  urt_counters and the frame batching are never changed.
+ *  - errors, checked before anything is enqueued or written: URT_ERR_INVALID_ARGUMENT for n < 0, a NULL pointer with n > 0, unknown
+ *    flags, samples or bounces out of range and (host form) a pixel outside 0..width-1 x 0..height-1; URT_ERR_UNBOUND (pixels mode) when
+ *    no texture is bound as Result or a camera matrix was never set.  The device form cannot look at its pixels: one outside the range
+ *    gets (0, 0, 0, 0) and is not traced.
+ * urt_radiance_query: host memory; returns when `out_rgba` is filled (a synchronising call, as urt_ray_query).
+ * urt_radiance_query_device: device pointers (rays and output 16-byte aligned, pixels 8-byte aligned); enqueued on the context's stream,
+ * returns at once — the caller orders and synchronises it. */
+enum { URT_RADIANCE_RAYS = 0, URT_RADIANCE_PIXELS = 1 };
+URT_API int urt_radiance_query(urt_context* ctx, const void* in, int n, int samples, int bounces, float* out_rgba, int flags);
+URT_API int urt_radiance_query_device(urt_context* ctx, const void* d_in, int n, int samples, int bounces, void* d_out_rgba, int flags);
+
 /* ---- feature buffers ---------------------------------------------------------------------- */
 /* Per-pixel first-hit feature buffers ("AOVs") of the bound camera: what each pixel's camera ray hits, for denoiser guides (albedo,
  * normal), compositing (depth) and whole-frame picking (ids).  Each handle is an existing texture (own or external) or 0 for "not
@@ -432,6 +461,8 @@ typedef struct urt_counters {
  *          "blas_leaf_max" (1..8: triangles per BVH leaf, default 2 or the environment variable URT_BLAS_LEAF_MAX read when the
  *          library is loaded — a process-wide builder setting; rebuilds the BVH),
  *          "stack_pad" (0..96: test hook, unused extra entries per traversal stack -> the > 64 KiB LDS launch path),
+ *          "radiance_persist" (-1 auto, the default | 0 | 1: urt_radiance_query on a resident grid whose lanes take the next query from a
+ *                              work counter when theirs is finished, instead of one query per thread; same results),
  *          "qnodes" (0 off, the default | 1 on | -1 on unless some MeshObject spans fewer than 1024 grid cells: the traversal loop of the default
  *                    kernel reads 32-byte quantized copies of the triangle-BVH nodes — two vector loads per node step instead of four; conservative
  *                    boxes on one 16-bit grid over the whole forest, csrc/qnodes.hip; a forest too large for the grid's plane arithmetic (cell

@@ -8,6 +8,9 @@
 // The ray-query records (urt_ray_query, urt.h) are the library's own: 16-byte aligned rows for coalesced dwordx4 loads and stores.
 //   Ray             32 B
 //   RayHit          48 B
+// The radiance-query records (urt_radiance_query, urt.h) likewise: three dwordx4 loads per ray, one 8-byte load per pixel.
+//   PathRay         48 B
+//   PathPixel        8 B
 // The per-object motion entries of urt_reproject_objects (urt.h) are the library's own too: 48 bytes, three dwordx4 loads.
 //   ObjectMotion    48 B
 #pragma once
@@ -61,6 +64,19 @@ typedef struct urt_RayHit {
   float u, v;                   /* @40 triangle: barycentrics of the hit; 0 otherwise */
 } urt_RayHit;
 
+typedef struct urt_PathRay {
+  float origin[3];              /* @0  */
+  float seed;                   /* @12 the running _Seed the path's first rand() starts from (RS:16) */
+  float direction[3];           /* @16 used as given (not normalised), as urt_Ray's */
+  int32_t reserved0;            /* @28 */
+  float px, py;                 /* @32 the "pixel" of rand() (RS:77-81): any two floats; they select the query's random stream */
+  int32_t reserved1[2];         /* @40 */
+} urt_PathRay;
+
+typedef struct urt_PathPixel {
+  int32_t x, y;                 /* @0, @4: pixel (x, y) of the texture bound as Result, row 0 at the bottom */
+} urt_PathPixel;
+
 typedef struct urt_ObjectMotion {
   float a[12];                  /* @0  current world -> previous world, affine: columns of the linear part a[0..2], a[3..5], a[6..8], then
                                        the translation a[9..11]:  P'.r = ((a[r]*P.x + a[3+r]*P.y) + a[6+r]*P.z) + a[9+r],  r = 0..2 */
@@ -76,6 +92,8 @@ typedef struct urt_ObjectMotion {
 #define URT_STRIDE_RAY 32
 #define URT_STRIDE_RAYHIT 48
 #define URT_STRIDE_OBJECTMOTION 48
+#define URT_STRIDE_PATHRAY 48
+#define URT_STRIDE_PATHPIXEL 8
 
 #ifdef __cplusplus
 }
@@ -86,4 +104,6 @@ static_assert(sizeof(urt_BVHNode) == URT_STRIDE_BVHNODE, "RM:45");
 static_assert(sizeof(urt_Ray) == URT_STRIDE_RAY, "urt_Ray");
 static_assert(sizeof(urt_RayHit) == URT_STRIDE_RAYHIT, "urt_RayHit");
 static_assert(sizeof(urt_ObjectMotion) == URT_STRIDE_OBJECTMOTION, "urt_ObjectMotion");
+static_assert(sizeof(urt_PathRay) == URT_STRIDE_PATHRAY, "urt_PathRay");
+static_assert(sizeof(urt_PathPixel) == URT_STRIDE_PATHPIXEL, "urt_PathPixel");
 #endif

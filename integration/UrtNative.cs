@@ -77,6 +77,22 @@ internal static class UrtNative {
     [DllImport(Lib, EntryPoint = "urt_ray_query")] internal static extern int urt_ray_query_any(IntPtr ctx, [In] Ray[] rays, int n, [Out] int[] occluded, int flags);
     [DllImport(Lib)] internal static extern int urt_ray_query_device(IntPtr ctx, IntPtr deviceRays, int n, IntPtr deviceOut, int flags);
 
+    // ---- radiance queries (include/urt.h "radiance queries"; records of include/urt_types.h) ---------------------------
+    [StructLayout(LayoutKind.Sequential, Pack = 1)]
+    internal struct PathRay {                               // urt_PathRay, 48 B
+        public float ox, oy, oz, seed;                      // seed: the running _Seed the path's first rand() starts from
+        public float dx, dy, dz;
+        public int reserved0;
+        public float px, py;                                // the "pixel" of rand(): selects the query's random stream
+        public int reserved1a, reserved1b;
+    }
+    [StructLayout(LayoutKind.Sequential, Pack = 1)]
+    internal struct PathPixel { public int x, y; }          // urt_PathPixel, 8 B
+    internal const int RadianceRays = 0, RadiancePixels = 1;
+    [DllImport(Lib)] internal static extern int urt_radiance_query(IntPtr ctx, [In] PathRay[] rays, int n, int samples, int bounces, [Out] float[] outRgba, int flags);
+    [DllImport(Lib, EntryPoint = "urt_radiance_query")] internal static extern int urt_radiance_query_pixels(IntPtr ctx, [In] PathPixel[] pixels, int n, int samples, int bounces, [Out] float[] outRgba, int flags);
+    [DllImport(Lib)] internal static extern int urt_radiance_query_device(IntPtr ctx, IntPtr deviceIn, int n, int samples, int bounces, IntPtr deviceOutRgba, int flags);
+
     // ---- feature buffers (include/urt.h "feature buffers"): hit, normal, albedo, id texture handles, 0 = not wanted --------
     internal const int AovPixelCenter = 0, AovFrameRay = 1;
     [DllImport(Lib)] internal static extern int urt_render_aov(IntPtr ctx, ulong hit, ulong normal, ulong albedo, ulong id, int flags);

@@ -51,6 +51,24 @@ internal static class UrtRaycast {                   // internal: it hands out U
     }
 }
 
+/// Path-traced radiance outside a frame (include/urt.h urt_radiance_query): light probes / lightmap texels (SampleRadiance) and fresh
+/// samples for chosen pixels of the bound camera, e.g. the ones a reprojection left without history (ResamplePixels).  Results are
+/// RGBA floats, four per query.  One context only (a group user queries urt_group_context(g, r)).
+internal static class UrtRadiance {                  // internal: it takes UrtNative records (same assembly as RM)
+    /// rays[i].seed and (px, py) select each query's random stream; samples 1..4096 paths of up to `bounces` (0..64) bounces each.
+    public static void SampleRadiance(UrtNative.PathRay[] rays, int samples, int bounces, float[] outRgba) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("SampleRadiance: query one rank's context (urt_group_context)");
+        if (outRgba.Length < 4 * rays.Length) throw new ArgumentException("SampleRadiance: outRgba holds fewer than 4 floats per ray");
+        UrtDevice.Check(UrtNative.urt_radiance_query(UrtDevice.Handle, rays, rays.Length, samples, bounces, outRgba, UrtNative.RadianceRays));
+    }
+    /// What a frame dispatched now with _numRays = samples and _numBounces = bounces would write to the pixels (of the texture bound as Result).
+    public static void ResamplePixels(UrtNative.PathPixel[] pixels, int samples, int bounces, float[] outRgba) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("ResamplePixels: query one rank's context (urt_group_context)");
+        if (outRgba.Length < 4 * pixels.Length) throw new ArgumentException("ResamplePixels: outRgba holds fewer than 4 floats per pixel");
+        UrtDevice.Check(UrtNative.urt_radiance_query_pixels(UrtDevice.Handle, pixels, pixels.Length, samples, bounces, outRgba, UrtNative.RadiancePixels));
+    }
+}
+
 /// Per-pixel first-hit feature buffers (include/urt.h urt_render_aov) written straight into device memory the engine owns — how a Unity
 /// RenderTexture (ARGBFloat, enableRandomWrite) is bound: pass each texture's device pointer (GetNativeTexturePtr on a HIP-interop
 /// backend) or IntPtr.Zero for a buffer not wanted.  Call it when the camera moves, after SetShaderParameters (the accumulation resets then too).

@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "urt_texture_create_external", "urt_texture_set_pixels", "urt_texture_get_pixels", "urt_texture_get_info", "urt_texture_read_begin", "urt_texture_read_end", "urt_texture_read_begin_format", "urt_texture_read_end_format", "urt_texture_release",
     "urt_shader_set_buffer", "urt_shader_set_texture", "urt_shader_set_matrix", "urt_shader_set_vector", "urt_shader_set_float",
     "urt_shader_set_int", "urt_shader_dispatch", "urt_shader_dispatch_rows", "urt_blit_add", "urt_blit", "urt_texture_pack_rows",
-    "urt_texture_unpack_rows", "urt_texture_unpack_rows_on", "urt_texture_pack_rows_rgb", "urt_texture_unpack_rows_rgb", "urt_ray_query", "urt_ray_query_device", "urt_render_aov", "urt_denoise", "urt_reproject", "urt_reproject_objects", "urt_blit_add_history", "urt_set_option", "urt_get_counters", "urt_reset_counters", "urt_debug_build_blas", "urt_debug_get_blas", "urt_debug_blas_cache_stats",
+    "urt_texture_unpack_rows", "urt_texture_unpack_rows_on", "urt_texture_pack_rows_rgb", "urt_texture_unpack_rows_rgb", "urt_ray_query", "urt_ray_query_device", "urt_radiance_query", "urt_radiance_query_device", "urt_render_aov", "urt_denoise", "urt_reproject", "urt_reproject_objects", "urt_blit_add_history", "urt_set_option", "urt_get_counters", "urt_reset_counters", "urt_debug_build_blas", "urt_debug_get_blas", "urt_debug_blas_cache_stats",
     "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_build_walk_table", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
     "urt_host_build_object_bvh", "urt_host_build_object_bvh_pairing", "urt_host_mesh_motion", "urt_host_sphere_motion", "urt_host_last_error", "urt_host_load_hdr", "urt_host_write_pfm", "urt_host_write_png", "urt_host_encode_srgb8", "urt_host_srgb8_first_floats",
     "urt_host_resize_rgba", "urt_host_io_last_error", "urt_host_log", "urt_host_log_scene_counts", "urt_host_log_tree_report", "urt_host_dump_bvh", "urt_host_dump_normals",
@@ -56,7 +56,23 @@ class RayHit(C.Structure):
                 ("object", C.c_int32), ("primitive", C.c_int32), ("u", C.c_float), ("v", C.c_float)]
 
 
+class PathRay(C.Structure):
+    """urt_PathRay (include/urt_types.h), 48 B."""
+    _pack_ = 1
+    _fields_ = [("origin", C.c_float * 3), ("seed", C.c_float), ("direction", C.c_float * 3), ("reserved0", C.c_int32),
+                ("px", C.c_float), ("py", C.c_float), ("reserved1", C.c_int32 * 2)]
+
+
+class PathPixel(C.Structure):
+    """urt_PathPixel (include/urt_types.h), 8 B."""
+    _pack_ = 1
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32)]
+
+
+URT_STRIDE_PATHRAY, URT_STRIDE_PATHPIXEL = 48, 8
 URT_QUERY_CLOSEST, URT_QUERY_ANY = 0, 1
+URT_RADIANCE_RAYS, URT_RADIANCE_PIXELS = 0, 1
+RADIANCE_MAX_SAMPLES, RADIANCE_MAX_BOUNCES = 4096, 64            # include/urt.h: samples 1..4096, bounces 0..64
 URT_AOV_PIXEL_CENTER, URT_AOV_FRAME_RAY = 0, 1
 
 
@@ -174,6 +190,8 @@ def load():
         "urt_texture_unpack_rows_rgb": ([vp, u64, i, i, vp, f, vp], i),
         "urt_ray_query": ([vp, vp, i, vp, i], i),
         "urt_ray_query_device": ([vp, vp, i, vp, i], i),
+        "urt_radiance_query": ([vp, vp, i, i, i, vp, i], i),
+        "urt_radiance_query_device": ([vp, vp, i, i, i, vp, i], i),
         "urt_render_aov": ([vp, u64, u64, u64, u64, i], i),
         "urt_denoise": ([vp, u64, u64, u64, u64, u64, C.POINTER(DenoiseParams)], i),
         "urt_reproject": ([vp, C.POINTER(ReprojectImages), C.POINTER(ReprojectParams)], i),

@@ -142,6 +142,9 @@ int urt_context_destroy(urt_context* ctx) {
   if (ctx->dep_ev) (void)hipEventDestroy(ctx->dep_ev);
   if (ctx->q_rays) (void)hipFree(ctx->q_rays);
   if (ctx->q_out) (void)hipFree(ctx->q_out);
+  if (ctx->rq_in) (void)hipFree(ctx->rq_in);
+  if (ctx->rq_out) (void)hipFree(ctx->rq_out);
+  if (ctx->rq_next) (void)hipFree(ctx->rq_next);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
   return URT_OK;
@@ -648,6 +651,7 @@ const OptionRow kOptions[] = {
   {"waves_per_cu", &O::waves_per_cu, 0, 32, "waves_per_cu must be in [0, 32] (0 = auto)", 0, nullptr},
   {"sched_block", &O::sched_block, 0, 256, "sched_block must be 0 (auto), 64 or 256", 0, [](int v) { return v == 0 || v == 64 || v == 256; }},
   {"stack_pad", &O::stack_pad, 0, 96, "stack_pad must be in [0, 96]", 0, nullptr},
+  {"radiance_persist", &O::radiance_persist, -1, 1, "radiance_persist must be -1 (auto), 0 or 1", 0, nullptr},
   {"shade_min", &O::shade_min, 1, 64, "shade_min must be in [1, 64]", 0, nullptr},
   {"front_list", &O::front_list, -1, 2, "front_list must be -1 (auto), 0, 1 or 2", 0, nullptr},
   {"shade_split", &O::shade_split, -1, 1, "shade_split must be -1 (auto), 0 or 1", 0, nullptr},

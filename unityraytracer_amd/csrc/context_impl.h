@@ -2,7 +2,7 @@
 //   context.cpp      context lifetime, stream, buffers, textures, readback, uniforms, blits, strip packing, options, counters, debug accessors
 //   scene_prep.cpp   bound buffers -> device scene (full and in-place preparation)
 //   frame_batch.cpp  deferred frames, the Result slab, trace launches (do_dispatch, flush_pending)
-//   image_ops.cpp    ray queries, feature buffers, denoiser, reprojection
+//   image_ops.cpp    ray queries, radiance queries, feature buffers, denoiser, reprojection
 // Private: nothing else includes it.  What crosses the files lives in namespace urtd and stays hidden (-fvisibility=hidden).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -76,6 +76,7 @@ struct urt_context {
     int pool_k = 2, pool_refill = 32, pool_blas_min = 48, pool_blas_exit = 8, pool_inloop = 16, pool_other_min = 24;   // kernel_mode 4
     int sched_block = 0;                    // kernel_mode 3: threads per workgroup (64 or 256; 0 = 256 when there is a BVH top to share)
     int stack_pad = 0;                      // test hook: extra (unused) entries per traversal stack, to reach the > 64 KiB LDS launch path
+    int radiance_persist = -1;              // urt_radiance_query: -1 = auto, 0 = one query per thread (k_radiance), 1 = resident grid + work counter (k_radiance_persist)
     int shade_min = 32, sky_min = 32;       // kernel_mode 3
     int serve_refill = 16;                  // kernel_mode 5: idle lanes of the traversal service that trigger a claim of waiting rays
     int front_list = -1;                    // kernel_mode 3: listed FRONT for scenes of <= 12 MeshObjects (-1 auto = on, 0 off)
@@ -229,6 +230,11 @@ struct urt_context {
 
   // urt_ray_query (host memory): grow-only device scratch for the rays and the results, q_cap rays each
   float4* q_rays = nullptr; float4* q_out = nullptr; size_t q_cap = 0;
+  // urt_radiance_query (host memory): grow-only device scratch for the queries (rq_in_cap bytes) and the results (rq_out_cap texels);
+  // rq_next: the work counter of k_radiance_persist (one word; each launch zeroes it on the stream in front of itself)
+  void* rq_in = nullptr; size_t rq_in_cap = 0;
+  float4* rq_out = nullptr; size_t rq_out_cap = 0;
+  unsigned int* rq_next = nullptr;
   // urt_denoise: grow-only device scratch of 3 float4 images (guide, two colour images) of dn_cap pixels each
   float4* dn_scratch = nullptr; size_t dn_cap = 0;
   // urt_reproject_objects: grow-only device copies of the mesh and the sphere motion table, mo_cap[k] bytes each

@@ -1,9 +1,10 @@
 // image_ops.cpp — the entry points of include/urt.h that work on whole images or ray batches next to the frame loop: ray queries,
-// feature buffers, the denoiser, temporal reprojection.
+// radiance queries, feature buffers, the denoiser, temporal reprojection.
 #include "experiments.h"
 #include "context_impl.h"
 
 #include "query.h"
+#include "radiance.h"
 #include "aov.h"
 #include "denoise.h"
 #include "reproject.h"
@@ -70,6 +71,10 @@ int grow_scratch(urt_context* ctx, void** p, size_t* cap, size_t need, size_t by
   return fail(ctx, e == hipErrorOutOfMemory ? URT_ERR_OUT_OF_MEMORY : URT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// urt_radiance_query with option "radiance_persist" at -1: k_radiance_persist, measured faster on full-frame pixel batches in any order and
+// within 1.5 % on the probe bake (profiles/r10_logs/r10_radiance_query_bench.log)
+constexpr bool kRadiancePersistAuto = true;
+
 }  // namespace
 
 extern "C" {
@@ -120,6 +125,89 @@ int urt_ray_query_device(urt_context* ctx, const void* d_rays, int n, void* d_ou
   if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & (flags == URT_QUERY_ANY ? 3u : 15u)))
     return fail(ctx, URT_ERR_INVALID_ARGUMENT, "ray query: d_rays must be 16-byte aligned, d_out 16-byte (closest hit) / 4-byte (any hit) aligned");
   URT_HIP(ctx, launch_query(ctx->scene.ds, ctx->scene.tlas_stack, ctx->scene.blas_stack, (const float4*)d_rays, n, d_out, flags == URT_QUERY_ANY, ctx->stream));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+/* ---- radiance queries ---- */
+// Scene, ordering and counters as the ray queries: enqueued on the context's stream WITHOUT marking it touched.  Unlike them the kernel
+// reads the sky, so deferred work that writes the texture bound as _SkyboxTexture is submitted first.  Everything is checked before
+// anything is enqueued; on success *launch holds the batch but for its pointers.
+static int radiance_prepare(urt_context* ctx, const void* in, int n, int samples, int bounces, const void* out, int flags, bool host,
+                            DevScene* S, RadianceCamera* C, RadianceBatch* launch) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (n < 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "radiance query: negative query count");
+  if (flags != URT_RADIANCE_RAYS && flags != URT_RADIANCE_PIXELS) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "radiance query: unknown flags");
+  if (samples < 1 || samples > 4096) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "radiance query: samples must be 1..4096");
+  if (bounces < 0 || bounces > 64) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "radiance query: bounces must be 0..64");
+  if (n > 0 && (!in || !out)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "radiance query: in / out is NULL");
+  if (n == 0) return URT_OK;
+  const bool pixels = flags == URT_RADIANCE_PIXELS;
+  *C = RadianceCamera{};
+  if (pixels) {
+    const Texture* res = find_texture(ctx, ctx->t_result);
+    if (!res) return fail(ctx, URT_ERR_UNBOUND, "radiance query: no texture bound to \"Result\"");
+    if (!ctx->c2w_set || !ctx->invp_set)
+      return fail(ctx, URT_ERR_UNBOUND, "radiance query: _CameraToWorld / _CameraInverseProjection not set");
+    std::memcpy(C->c2w, ctx->c2w, sizeof C->c2w);
+    std::memcpy(C->invp, ctx->invp, sizeof C->invp);
+    C->pixel_off_x = ctx->pixel_off[0]; C->pixel_off_y = ctx->pixel_off[1];
+    C->seed = ctx->seed;
+    C->width = res->w; C->height = res->h;
+    if (host) {
+      const urt_PathPixel* p = (const urt_PathPixel*)in;
+      for (int i = 0; i < n; i++)
+        if (p[i].x < 0 || p[i].x >= res->w || p[i].y < 0 || p[i].y >= res->h)
+          return fail(ctx, URT_ERR_INVALID_ARGUMENT, "radiance query: pixel " + std::to_string(i) + " lies outside the texture bound as Result");
+    }
+  }
+  if (!host && (((uintptr_t)in & (pixels ? 7u : 15u)) || ((uintptr_t)out & 15u)))
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "radiance query: device rays and output must be 16-byte aligned, pixels 8-byte aligned");
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  const urt_context::Pending& B = ctx->pend;
+  bool sky_written = false;                                  // (the deferring calls keep such work out of a batch; a texture bound as the sky afterwards is not covered by that)
+  if (B.n > 0 && ctx->t_sky) {
+    sky_written = B.tex == ctx->t_sky;
+    for (const PostOp& q : B.ops) sky_written = sky_written || q.dst == ctx->t_sky || q.count == ctx->t_sky;
+  }
+  if (ctx->scene_dirty || sky_written) { int rc = flush_pending(ctx); if (rc) return rc; }   // the deferred frames read the scene that is about to be replaced
+  if (ctx->scene_dirty) { int rc = prepare_scene(ctx); if (rc) return rc; }
+  *S = ctx->scene.ds;
+  { int rc = bind_sky(ctx, *S); if (rc) return rc; }
+  *launch = RadianceBatch{};
+  launch->n = n; launch->samples = samples; launch->bounces = bounces; launch->pixels = pixels;
+  const bool persist = ctx->opt.radiance_persist < 0 ? kRadiancePersistAuto : ctx->opt.radiance_persist != 0;
+  if (persist) {
+    if (!ctx->rq_next) URT_HIP(ctx, hipMalloc((void**)&ctx->rq_next, sizeof(unsigned int)));
+    launch->work_counter = ctx->rq_next; launch->n_cus = ctx->n_cus;
+  }
+  return URT_OK;
+}
+
+int urt_radiance_query(urt_context* ctx, const void* in, int n, int samples, int bounces, float* out_rgba, int flags) {
+  URT_GUARD_BEGIN
+  DevScene S; RadianceCamera C; RadianceBatch B;
+  int rc = radiance_prepare(ctx, in, n, samples, bounces, out_rgba, flags, true, &S, &C, &B);
+  if (rc || n == 0) return rc;
+  const size_t in_bytes = (size_t)n * (B.pixels ? sizeof(urt_PathPixel) : sizeof(urt_PathRay));
+  if (int r = grow_scratch(ctx, &ctx->rq_in, &ctx->rq_in_cap, in_bytes, in_bytes, "radiance query: scratch allocation")) return r;
+  if (int r = grow_scratch(ctx, (void**)&ctx->rq_out, &ctx->rq_out_cap, (size_t)n, (size_t)n * sizeof(float4), "radiance query: scratch allocation")) return r;
+  B.in = ctx->rq_in; B.out = ctx->rq_out;
+  URT_HIP(ctx, hipMemcpyAsync(ctx->rq_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  URT_HIP(ctx, launch_radiance(S, ctx->scene.tlas_stack, ctx->scene.blas_stack + ctx->opt.stack_pad, C, B, ctx->stream));
+  URT_HIP(ctx, hipMemcpyAsync(out_rgba, ctx->rq_out, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  URT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return check_watchdog(ctx);
+  URT_GUARD_END(ctx)
+}
+
+int urt_radiance_query_device(urt_context* ctx, const void* d_in, int n, int samples, int bounces, void* d_out_rgba, int flags) {
+  URT_GUARD_BEGIN
+  DevScene S; RadianceCamera C; RadianceBatch B;
+  int rc = radiance_prepare(ctx, d_in, n, samples, bounces, d_out_rgba, flags, false, &S, &C, &B);
+  if (rc || n == 0) return rc;
+  B.in = d_in; B.out = (float4*)d_out_rgba;
+  URT_HIP(ctx, launch_radiance(S, ctx->scene.tlas_stack, ctx->scene.blas_stack + ctx->opt.stack_pad, C, B, ctx->stream));
   return URT_OK;
   URT_GUARD_END(ctx)
 }

@@ -255,6 +255,40 @@ class RayTraceMaster:
             return None
         return {k: (h[k].copy() if h[k].shape else h[k].item()) for k in h.dtype.names}
 
+    def _bind_for_queries(self):
+        if self._treesNeedRebuilding:                                             # the scene buffers exist once OnRenderImage has run once
+            self._currentSample = 0
+            self._treesNeedRebuilding = False
+            if self._rayTraceObjects:
+                self.RebuildObjectLists()
+            self.RebuildTrees()
+        self.SetShaderParameters()
+
+    # Path-traced radiance arriving along rays of the host's own — light probes, irradiance volumes, lightmap texels — with the scene
+    # this master renders (include/urt.h urt_radiance_query): `samples` paths per ray of up to numBounces bounces, starting from the
+    # current _Seed.  The "pixel" of query i is (i mod 4096, i div 4096) as floats, so every query has its own random stream.
+    # origins, directions: (n, 3) float32 (numpy, or torch tensors on the context's device); returns (n, 4).
+    def SampleRadiance(self, origins, directions, samples: int):
+        self._bind_for_queries()
+        n = int(origins.shape[0])
+        seed = self.RayTraceShader._bound[("f", "_Seed")]                         # the float32 SetShaderParameters has just bound
+        if type(origins).__module__.startswith("torch"):
+            import torch
+            i = torch.arange(n, dtype=torch.int64, device=origins.device)
+            pixels = torch.stack([(i % 4096).to(torch.float32), (i // 4096).to(torch.float32)], dim=1)
+        else:
+            i = np.arange(n, dtype=np.int64)
+            pixels = np.stack([(i % 4096).astype(np.float32), (i // 4096).astype(np.float32)], axis=1)
+        return self.ctx.radiance_query(origins, directions, pixels, seed, samples, self.numBounces)
+
+    # Fresh samples for chosen pixels of the camera this master renders with — e.g. the ones a reprojection left without history:
+    # exactly what the next frame writes to them (urt_radiance_query, pixels mode, with numRays and numBounces).  xy: (n, 2) int32.
+    def ResamplePixels(self, xy):
+        self._bind_for_queries()
+        self.InitRenderTexture()
+        self.RayTraceShader.SetTexture(0, "Result", self._target)
+        return self.ctx.radiance_query_pixels(xy, self.numRays, self.numBounces)
+
     # Per-pixel first-hit feature buffers of the camera this master renders with (include/urt.h urt_render_aov): hit, normal, albedo and
     # id textures of the screen size, re-created with it as InitRenderTexture re-creates the frame's (RM:834-840).  A host calls it when
     # the camera moves — when the accumulation resets too.  Returns the four RenderTextures (filled once the deferred work has run:

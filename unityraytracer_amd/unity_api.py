@@ -181,6 +181,104 @@ class Context:
         return {"distance": out[:, 0], "position": out[:, 1:4], "normal": out[:, 4:7], "kind": bits[:, 7], "object": bits[:, 8],
                 "primitive": bits[:, 9], "u": out[:, 10], "v": out[:, 11]}
 
+    def radiance_query(self, origins, directions, pixels, seeds, samples: int, bounces: int):
+        """Path-traced radiance arriving along each ray (include/urt.h urt_radiance_query, URT_RADIANCE_RAYS): `samples` paths of up to
+        `bounces` bounces per ray with the bound scene's materials, emission and sky, averaged.  origins, directions (n, 3); pixels (n, 2):
+        the two floats that select each query's random stream (the "pixel" of rand(), RS:77-81); seeds: the running seed each query starts
+        from, a number or (n,).  numpy float32 arrays: returns (n, 4) float32.  torch float32 tensors on this context's device: the device
+        entry point; returns an (n, 4) tensor.  The call is ordered after torch's current stream and has completed when it returns."""
+        samples, bounces = _radiance_counts(samples, bounces)
+        if any(_is_torch(a) for a in (origins, directions, pixels)):
+            return self._radiance_query_torch(origins, directions, pixels, seeds, samples, bounces)
+        o = _rays_arg(origins, "origins", "radiance_query")
+        d = _rays_arg(directions, "directions", "radiance_query")
+        if o.shape != d.shape:
+            raise ValueError(f"radiance_query: origins {o.shape} and directions {d.shape} differ in shape")
+        n = o.shape[0]
+        if not isinstance(pixels, np.ndarray):
+            raise TypeError(f"radiance_query: pixels must be a numpy array (or a torch tensor), not {type(pixels).__name__}")
+        if pixels.dtype != np.float32:
+            raise TypeError(f"radiance_query: pixels must be float32, not {pixels.dtype}")
+        if pixels.shape != (n, 2):
+            raise ValueError(f"radiance_query: pixels must have shape ({n}, 2), not {pixels.shape}")
+        rays = np.zeros(n, dtype=PATHRAY_DT)
+        rays["origin"], rays["direction"], rays["seed"] = o, d, _per_ray_arg(seeds, n, "seeds", "radiance_query")
+        rays["px"], rays["py"] = pixels[:, 0], pixels[:, 1]
+        out = np.zeros((n, 4), dtype=np.float32)
+        self.check(self.lib.urt_radiance_query(self._h, rays.ctypes.data_as(C.c_void_p), n, samples, bounces, out.ctypes.data_as(C.c_void_p),
+                                               _lib.URT_RADIANCE_RAYS))
+        return out
+
+    def _radiance_query_torch(self, origins, directions, pixels, seeds, samples, bounces):
+        import torch
+        for name, a, cols in (("origins", origins, 3), ("directions", directions, 3), ("pixels", pixels, 2)):
+            self._torch_arg(a, name, "radiance_query", torch.float32, cols)
+        n = origins.shape[0]
+        if directions.shape[0] != n or pixels.shape[0] != n:
+            raise ValueError(f"radiance_query: origins {tuple(origins.shape)}, directions {tuple(directions.shape)} and pixels "
+                             f"{tuple(pixels.shape)} differ in length")
+        if n > 0x7fffffff:
+            raise ValueError("radiance_query: more than 2^31 - 1 rays")
+        if _is_torch(seeds):
+            if seeds.dtype != torch.float32 or seeds.shape != (n,) or seeds.device != origins.device:
+                raise ValueError("radiance_query: seeds must be a float32 tensor of shape (n,) on the rays' device")
+            sd = seeds.reshape(n, 1)
+        else:
+            if isinstance(seeds, (bool, np.bool_)) or not isinstance(seeds, (int, float, np.floating, np.integer)):
+                raise TypeError(f"radiance_query: seeds must be a number or a float32 tensor, not {type(seeds).__name__}")
+            sd = torch.full((n, 1), float(np.float32(seeds)), dtype=torch.float32, device=origins.device)
+        zero = torch.zeros((n, 1), dtype=torch.float32, device=origins.device)
+        rays = torch.cat([origins, sd, directions, zero, pixels, zero, zero], dim=1).contiguous()
+        out = torch.empty((n, 4), dtype=torch.float32, device=origins.device)
+        torch.cuda.current_stream(origins.device).synchronize()    # the rays are written on torch's stream, the query runs on the library's
+        self.check(self.lib.urt_radiance_query_device(self._h, C.c_void_p(rays.data_ptr()), n, samples, bounces, C.c_void_p(out.data_ptr()),
+                                                      _lib.URT_RADIANCE_RAYS))
+        torch.cuda.synchronize(origins.device)                     # the device entry point returns at once: wait for the library's stream
+        return out
+
+    def radiance_query_pixels(self, xy, samples: int, bounces: int):
+        """What a frame dispatched now with _numRays = samples and _numBounces = bounces would write to the given pixels of the texture
+        bound as Result (include/urt.h urt_radiance_query, URT_RADIANCE_PIXELS): the camera, _PixelOffset and _Seed bound at call time.
+        xy: (n, 2) int32, numpy — returns (n, 4) float32 and refuses pixels outside the texture — or a torch tensor on this context's
+        device: the device entry point, which gives (0, 0, 0, 0) to a pixel outside the texture; returns an (n, 4) tensor."""
+        samples, bounces = _radiance_counts(samples, bounces)
+        if _is_torch(xy):
+            import torch
+            self._torch_arg(xy, "xy", "radiance_query_pixels", torch.int32, 2)
+            n = xy.shape[0]
+            if n > 0x7fffffff:
+                raise ValueError("radiance_query_pixels: more than 2^31 - 1 pixels")
+            px = xy.contiguous()
+            out = torch.empty((n, 4), dtype=torch.float32, device=xy.device)
+            torch.cuda.current_stream(xy.device).synchronize()
+            self.check(self.lib.urt_radiance_query_device(self._h, C.c_void_p(px.data_ptr()), n, samples, bounces, C.c_void_p(out.data_ptr()),
+                                                          _lib.URT_RADIANCE_PIXELS))
+            torch.cuda.synchronize(xy.device)
+            return out
+        if not isinstance(xy, np.ndarray):
+            raise TypeError(f"radiance_query_pixels: xy must be a numpy array (or a torch tensor), not {type(xy).__name__}")
+        if xy.dtype != np.int32:
+            raise TypeError(f"radiance_query_pixels: xy must be int32, not {xy.dtype}")
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError(f"radiance_query_pixels: xy must have shape (n, 2), not {xy.shape}")
+        if xy.shape[0] > 0x7fffffff:
+            raise ValueError("radiance_query_pixels: more than 2^31 - 1 pixels")
+        px = np.ascontiguousarray(xy)
+        out = np.zeros((len(px), 4), dtype=np.float32)
+        self.check(self.lib.urt_radiance_query(self._h, px.ctypes.data_as(C.c_void_p), len(px), samples, bounces, out.ctypes.data_as(C.c_void_p),
+                                               _lib.URT_RADIANCE_PIXELS))
+        return out
+
+    def _torch_arg(self, a, name: str, who: str, dtype, cols: int):
+        if not _is_torch(a):
+            raise TypeError(f"{who}: {name} must be a torch tensor when another argument is")
+        if a.dtype != dtype:
+            raise TypeError(f"{who}: {name} must be {str(dtype).replace('torch.', '')}, not {a.dtype}")
+        if a.dim() != 2 or a.shape[1] != cols:
+            raise ValueError(f"{who}: {name} must have shape (n, {cols}), not {tuple(a.shape)}")
+        if a.device.type != "cuda" or a.device.index != self.device:
+            raise ValueError(f"{who}: {name} must be on cuda:{self.device}, not {a.device}")
+
     def render_aov(self, hit=None, normal=None, albedo=None, id=None, frame_ray: bool = False):
         """Per-pixel first-hit feature buffers of the bound camera into RenderTextures of one size (include/urt.h urt_render_aov):
         hit = position.xyz, distance; normal = normal.xyz, kind; albedo = clamped albedo.xyz, smoothness (a miss: sky radiance, 0);
@@ -429,6 +527,35 @@ RAYHIT_DT = np.dtype([("distance", np.float32), ("position", np.float32, 3), ("n
                       ("object", np.int32), ("primitive", np.int32), ("u", np.float32), ("v", np.float32)])
 
 
+# urt_PathRay / urt_PathPixel (include/urt_types.h) as numpy records
+PATHRAY_DT = np.dtype([("origin", np.float32, 3), ("seed", np.float32), ("direction", np.float32, 3), ("reserved0", np.int32),
+                       ("px", np.float32), ("py", np.float32), ("reserved1", np.int32, 2)])
+PATHPIXEL_DT = np.dtype([("x", np.int32), ("y", np.int32)])
+
+
+def _radiance_counts(samples, bounces):
+    """The checked (samples, bounces) of Context.radiance_query*: ints in 1..4096 and 0..64 (include/urt.h)."""
+    for name, v, lo, hi in (("samples", samples, 1, _lib.RADIANCE_MAX_SAMPLES), ("bounces", bounces, 0, _lib.RADIANCE_MAX_BOUNCES)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"radiance_query: {name} must be an int, not {type(v).__name__}")
+        if not lo <= v <= hi:
+            raise ValueError(f"radiance_query: {name} must be {lo}..{hi}, not {v}")
+    return int(samples), int(bounces)
+
+
+def _per_ray_arg(v, n: int, name: str, who: str) -> np.ndarray:
+    """A number, or a float32 array (n,)."""
+    if isinstance(v, np.ndarray):
+        if v.dtype != np.float32:
+            raise TypeError(f"{who}: {name} must be float32, not {v.dtype}")
+        if v.shape != (n,):
+            raise ValueError(f"{who}: {name} must be a scalar or have shape ({n},), not {v.shape}")
+        return v
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.floating, np.integer)):
+        raise TypeError(f"{who}: {name} must be a number or a float32 array, not {type(v).__name__}")
+    return np.full(n, v, dtype=np.float32)
+
+
 def denoise_params(iterations: int = _lib.DENOISE_DEFAULTS["iterations"], sigma_color: float = _lib.DENOISE_DEFAULTS["sigma_color"],
                    sigma_normal: float = _lib.DENOISE_DEFAULTS["sigma_normal"],
                    sigma_depth: float = _lib.DENOISE_DEFAULTS["sigma_depth"]) -> _lib.DenoiseParams:
@@ -450,15 +577,15 @@ def _is_torch(a) -> bool:
     return type(a).__module__.startswith("torch")
 
 
-def _rays_arg(a, name: str) -> np.ndarray:
+def _rays_arg(a, name: str, who: str = "ray_query") -> np.ndarray:
     if not isinstance(a, np.ndarray):
-        raise TypeError(f"ray_query: {name} must be a numpy array (or a torch tensor), not {type(a).__name__}")
+        raise TypeError(f"{who}: {name} must be a numpy array (or a torch tensor), not {type(a).__name__}")
     if a.dtype != np.float32:
-        raise TypeError(f"ray_query: {name} must be float32, not {a.dtype}")
+        raise TypeError(f"{who}: {name} must be float32, not {a.dtype}")
     if a.ndim != 2 or a.shape[1] != 3:
-        raise ValueError(f"ray_query: {name} must have shape (n, 3), not {a.shape}")
+        raise ValueError(f"{who}: {name} must have shape (n, 3), not {a.shape}")
     if a.shape[0] > 0x7fffffff:
-        raise ValueError("ray_query: more than 2^31 - 1 rays")
+        raise ValueError(f"{who}: more than 2^31 - 1 rays")
     return a
 
 
