@@ -3,14 +3,17 @@
 # (VGPRs / AGPRs / SGPRs / scratch / occupancy / LDS).  Usage: scripts/build_remarks.sh [out.so] [extra hipcc flags...]
 cd "$(dirname "$0")/../unityraytracer_amd" || exit 1
 OUT=${1:-/tmp/urt_remarks.so}; shift
-# KERNELS_ONLY=1: compile csrc/kernels.hip alone (-c): the trace kernels' numbers in half a minute
+# The flags and the source list are build.py's own.  KERNELS_ONLY=1: compile the trace translation units alone (-c each: kernels.hip and
+# kernels_basic / _serve / _pool.hip): the trace kernels' numbers in half a minute
+FLAGS=$(python3 -c "from build import HIPCC_FLAGS as F; print(' '.join(f for f in F if f != '-shared'))")
+SRCS=$(python3 -c "from build import SOURCES as S; print(' '.join('csrc/' + s for s in S))")
 if [ -n "$KERNELS_ONLY" ]; then
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -fvisibility=hidden -pthread -Xarch_host -march=x86-64-v3 -Xarch_device -fno-slp-vectorize \
-    -Wall -Wno-unused-function -Rpass-analysis=kernel-resource-usage "$@" -c csrc/kernels.hip -o "$OUT" 2> /tmp/urt_remarks.log
+  : > /tmp/urt_remarks.log
+  for src in csrc/kernels.hip csrc/kernels_basic.hip csrc/kernels_serve.hip csrc/kernels_pool.hip; do
+    hipcc $FLAGS -Rpass-analysis=kernel-resource-usage "$@" -c $src -o "$OUT" 2>> /tmp/urt_remarks.log || break
+  done
 else
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -fvisibility=hidden -pthread -Xarch_host -march=x86-64-v3 -Xarch_device -fno-slp-vectorize \
-  -Wall -Wno-unused-function -Rpass-analysis=kernel-resource-usage "$@" -o "$OUT" \
-  csrc/kernels.hip csrc/query.hip csrc/aov.hip csrc/denoise.hip csrc/reproject.hip csrc/lbvh.hip csrc/refit.hip csrc/qnodes.hip csrc/cullflags.hip csrc/present.hip csrc/context.cpp csrc/scene_prep.cpp csrc/frame_batch.cpp csrc/image_ops.cpp csrc/blas_builder.cpp csrc/host_scene.cpp csrc/host_io.cpp csrc/host_debug.cpp csrc/group.cpp 2> /tmp/urt_remarks.log
+  hipcc $FLAGS -shared -Rpass-analysis=kernel-resource-usage "$@" -o "$OUT" $SRCS 2> /tmp/urt_remarks.log
 fi
 rc=$?
 grep -E "error" -A6 /tmp/urt_remarks.log | head -40

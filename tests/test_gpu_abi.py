@@ -248,7 +248,8 @@ def test_launch_info_names_the_kernel_that_ran(gpu_ctx):
     sc = scenes.mixed_test_scene(96, 64)
     m = RayTraceMaster(gpu_ctx, sc)
     try:
-        for mode, name in ((0, "k_mega<false>"), (2, "k_persist<false>"), (3, "k_sched<false, 256, ")):
+        for mode, name in ((0, "k_mega<false>"), (1, "k_generate + k_bounce<false> x "), (2, "k_persist<false>"), (4, "k_pool<false, "),
+                           (5, "k_serve<false, 256, "), (3, "k_sched<false, 256, ")):      # one launcher of every trace translation unit
             gpu_ctx.set_option("kernel_mode", mode)
             m.OnRenderImage()
             info = gpu_ctx.launch_info()
@@ -257,6 +258,10 @@ def test_launch_info_names_the_kernel_that_ran(gpu_ctx):
         gpu_ctx.set_option("count_stats", 1)
         m.OnRenderImage()
         assert gpu_ctx.launch_info()["kernel"].startswith("k_sched<true, 256, ")
+        gpu_ctx.set_option("kernel_mode", 5)
+        m.OnRenderImage()
+        info = gpu_ctx.launch_info()
+        assert info["kernel"].startswith("k_serve<true, 256, ") and info["n_blocks"] > 0, info
     finally:
         gpu_ctx.set_option("count_stats", 0)
         gpu_ctx.set_option("kernel_mode", 3)

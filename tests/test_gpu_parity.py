@@ -182,7 +182,7 @@ def test_masked_phase_at_fewer_workgroups_per_cu(gpu_ctx):
 def test_chain_shaped_triangle_bvh_fills_the_traversal_stack(gpu_ctx):
     """A triangle BVH that is a chain (one triangle per leaf, every split peels off the far end) is as deep as it has leaves, and a ray
     down its axis has the far child of EVERY level on its stack at once: the per-lane LDS stacks (depth + free slot + the sentinel
-    entry of the pointer-form loop, kernels.hip blas_node_eval_ptr) are used to the last entry.  Pixels and counters == oracle in every mode."""
+    entry of the pointer-form loop, trace_device.h blas_node_eval_ptr) are used to the last entry.  Pixels and counters == oracle in every mode."""
     sc = scenes.deep_chain_scene()
     try:
         gpu_ctx.set_option("blas_leaf_max", 1)                 # (process-wide builder setting: the oracle's copy of the BVH follows)

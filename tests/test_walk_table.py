@@ -1,4 +1,4 @@
-"""CPU: the masked object-level walk (DESIGN.md §5 "masked FRONT", kernels.hip front_masked) against the LITERAL walk RS:294-326.
+"""CPU: the masked object-level walk (DESIGN.md §5 "masked FRONT", front_device.h front_masked) against the LITERAL walk RS:294-326.
 The kernel never walks the heap: it evaluates one slab-test bit per node and derives, with shifts and masks over the nodes in POP
 order, which nodes the reference's stack walk would pop (its BVHNode fetch count) and which MeshObjects it would test, in which order
 (`tests` is never reset: A.5).  Here the table the library builds (urt_debug_build_walk_table) is interpreted in numpy exactly as the

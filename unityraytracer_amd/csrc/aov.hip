@@ -4,7 +4,7 @@
 // One camera ray per lane, wave64.  A wave covers one 8 x 8 pixel tile and a 256-thread workgroup a 16 x 16 block, so the rays of a wave
 // leave the camera in a narrow cone and walk the same BVH nodes (the frame kernels' tiles are 8 x 8 for the same reason).  Per-lane LDS
 // stacks laid out [entry][lane] as k_query's, sized from the prepared scene.  The camera ray is CreateCameraRay RS:142-153 with either
-// the pixel centre or the uv of a frame's first sample (RS:448-449, bit-identical to kernels.hip camera_ray); the trace is
+// the pixel centre or the uv of a frame's first sample (RS:448-449, bit-identical to frame_device.h camera_ray); the trace is
 // query_trace<false> with t_max = +inf, i.e. exactly what urt_ray_query and the frame kernels' Trace return for that ray.
 // Stores: one non-temporal float4 per pixel into each target that is present; an absent target costs nothing.
 #include <hip/hip_runtime.h>
@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void k_aov(DevScene S, const float4* __restric
   // CreateCameraRay RS:142-153
   const float px = (float)x, py = (float)y;
   float u, v;
-  if (C.frame_ray) {                                             // RS:448-449, sample 0 of a frame dispatched now (kernels.hip camera_ray)
+  if (C.frame_ray) {                                             // RS:448-449, sample 0 of a frame dispatched now (frame_device.h camera_ray)
     float seed = C.seed;
     float r0 = rand_next(seed, px, py);
     float r1 = rand_next(seed, px, py);
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void k_aov(DevScene S, const float4* __restric
   if (T.albedo) {
     float4 a;
     if (h.kind() != 0) {
-      // the material table's order (kernels.hip shade_surface): spheres, then MeshObjects, then the ground plane
+      // the material table's order (shade_device.h shade_surface): spheres, then MeshObjects, then the ground plane
       const int object = as_int(r.r2.x);
       a = albedo_tab[h.kind() == 1 ? S.n_spheres + S.n_meshes : h.kind() == 2 ? object : S.n_spheres + object];
     } else {

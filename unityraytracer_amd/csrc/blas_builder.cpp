@@ -329,7 +329,7 @@ bool build_blas(const uint8_t* mesh_objects, int n_meshes, const float* vertices
   }
   // Renumber the interior nodes so that the first kTopOrderNodes indices are the TOP of the forest in breadth-first order
   // (all roots, then their children, ...): the phase-scheduled kernel keeps nodes [0, T) in LDS and walks them before a ray
-  // joins the wave-wide traversal loop (kernels.hip trace_front).  Deeper nodes keep their depth-first order (subtree
+  // joins the wave-wide traversal loop (front_device.h trace_front).  Deeper nodes keep their depth-first order (subtree
   // locality).  Only indices change: every ray visits the same nodes in the same order as before.
   {
     size_t nn = out.nodes.size() / kBlasNodeFloats;

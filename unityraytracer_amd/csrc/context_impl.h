@@ -205,7 +205,7 @@ struct urt_context {
   uint64_t launches = 0;                    // trace-kernel launches (a batched launch counts once)
   urt_launch_info last_launch{};            // the last trace launch of this context (urt_debug_launch_info)
   // a wave that left a persistent kernel through one of its caps has not written its pixels: the kernels raise this host-mapped
-  // word (kernels.hip report_watchdog) and the next synchronising call fails with URT_ERR_WATCHDOG
+  // word (frame_device.h report_watchdog) and the next synchronising call fails with URT_ERR_WATCHDOG
   unsigned int* h_trip_flag = nullptr;      // pinned, device-visible
   unsigned int* d_trip_flag = nullptr;      // its device address
   // Overlapped launches (option "overlap_launches", flush_pending): a host that SUBMITS every frame (urt_flush, a present into an external

@@ -1,4 +1,4 @@
-// cullflags.hip — verification pass behind the object-level cull (include/urt_math.h tlas_cull; kernels.hip front_masked / trace_front).
+// cullflags.hip — verification pass behind the object-level cull (include/urt_math.h tlas_cull; front_device.h front_masked / trace_front).
 //
 // The reference intersects every MeshObject whose heap leaf is popped after the first hit leaf box (RS:294-326, `tests` never reset) —
 // also objects whose box the ray misses.  Skipping such an object is only sound if the leaf's box (the SCENE's data: `_MeshBVH`, RM:148-152,

@@ -146,10 +146,10 @@ static int configure_sched_at(urt_context* ctx, const DevScene& S, FrameParams& 
   }
   if (sched_lds_bytes(S, P) * groups > budget) { P.lds_mesh = 0; P.lds_sphere = 0; P.lds_small = 0; }
   *degraded = (t > 0 && P.top_nodes == 0) || (wanted_tables && !(P.lds_mesh || P.lds_sphere)) || sched_lds_bytes(S, P) * groups > budget;
-  // listed FRONT (kernels.hip front_listed): scenes of a few MeshObjects whose heap is in LDS; the list of objects a ray has to test
+  // listed FRONT (front_device.h front_listed): scenes of a few MeshObjects whose heap is in LDS; the list of objects a ray has to test
   // (<= 12 ids of 5 bits) lives in the first two entries of the lane's object-level stack, so it costs no LDS
   bool listed = top_in_front && P.top_nodes > 0 && P.lds_mesh && S.n_meshes <= 12 && ctx->opt.front_list != 0;
-  // masked FRONT (kernels.hip front_masked): mesh heaps of <= 31 nodes are walked with mask arithmetic instead of a stack; the walk
+  // masked FRONT (front_device.h front_masked): mesh heaps of <= 31 nodes are walked with mask arithmetic instead of a stack; the walk
   // table takes the heap's place in LDS.  "front_list" 2 forces the listed form (A/B), -1 / 1 prefer the masked one.
   bool masked = top_in_front && t > 0 && ctx->opt.lds_tlas && ctx->scene.walk_f4 > 0 && !P.serve && ctx->opt.front_list != 0 && ctx->opt.front_list != 2;
   if (masked) {
@@ -207,7 +207,7 @@ static int configure_sched(urt_context* ctx, const DevScene& S, FrameParams& P, 
   return mode;
 }
 
-// What urt_debug_launch_info reports: the record a launcher of kernels.hip filled, and the launch's configuration
+// What urt_debug_launch_info reports: the record a launcher of kernels.h filled, and the launch's configuration
 static void record_launch(urt_context* ctx, const TraceLaunchRecord& R, int kernel_mode, int front_mode, const FrameParams& P, bool count, int waves_per_cu) {
   urt_launch_info& I = ctx->last_launch;
   std::memset(&I, 0, sizeof I);
@@ -222,7 +222,7 @@ static void record_launch(urt_context* ctx, const TraceLaunchRecord& R, int kern
   I.experiment = URT_ABI_SIGN < 0 ? 1 : 0;
 }
 
-// One trace launch on stream `st`: `launch(TraceLaunchRecord*)` enqueues it through a launcher of kernels.hip, between two timing events
+// One trace launch on stream `st`: `launch(TraceLaunchRecord*)` enqueues it through a launcher of kernels.h, between two timing events
 // when "time_dispatch" is on; then the launch is counted and recorded (record_launch)
 template <typename Launch>
 static int timed_launch(urt_context* ctx, hipStream_t st, int kernel_mode, int front_mode, const FrameParams& P, bool count, int waves_per_cu, Launch launch) {
@@ -267,7 +267,7 @@ static int launch_sched_frames(urt_context* ctx, const DevScene& S, const FrameP
   long want = ((long)P.tiles_x * P.n_strips * P.n_frames + waves_per_block - 1) / waves_per_block;
   // resident waves per CU: every slot the registers allow (k_sched: 96 VGPRs -> 5 waves/SIMD = 20 per CU).  While the
   // frame's work counter was one address, fewer and fatter waves were faster at 1080p (12 per CU); since it is sharded
-  // (kernels.hip wave_fetch_pixels) the full 20 win at every frame size measured (profiles/README.md).
+  // (frame_device.h wave_fetch_pixels) the full 20 win at every frame size measured (profiles/README.md).
   int wpc = ctx->opt.waves_per_cu;
   if (wpc <= 0) wpc = P.serve ? 16 : 20;
   if (ctx->sched_groups > 0) wpc = ctx->sched_groups * waves_per_block;       // deep stacks: fewer workgroups per CU, LDS features kept (configure_sched)
@@ -574,7 +574,7 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
       long resident = (long)ctx->n_cus * wpc / waves_per_block;
       nb = (int)std::max(1L, std::min(want, resident));
     } else if (mode == 4) {
-      // one wave per workgroup; residency is bounded by the LDS one wave's path pool takes (kernels.hip k_pool)
+      // one wave per workgroup; residency is bounded by the LDS one wave's path pool takes (kernels_pool.hip k_pool)
       P.block_threads = 64;
       P.refill_min = ctx->opt.pool_refill; P.blas_min = ctx->opt.pool_blas_min; P.blas_exit = ctx->opt.pool_blas_exit;
       P.pool_inloop = ctx->opt.pool_inloop; P.pool_other_min = ctx->opt.pool_other_min;

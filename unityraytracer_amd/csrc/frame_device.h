@@ -1,0 +1,321 @@
+// frame_device.h — the device functions every frame kernel uses, whatever its mode (kernels.hip, kernels_basic.hip, kernels_serve.hip,
+// kernels_pool.hip): Trace() as one call, the camera ray, tile and work-counter hand-out, the counter flush, the watchdog report.
+// Everything here is inlined into its kernels; a translation unit includes it after experiments.h and gets the common preamble with it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/urt_math.h"
+#include "urt_device.h"
+#include "kernels.h"
+
+using namespace urt;
+using namespace urtd;
+
+#include "trace_device.h"     // HitRec, slab tests, triangle / sphere / leaf tests, triangle-BVH node steps, intersect_mesh
+#include "sky_device.h"       // sample_sky, sky_radiance: the sky lookup of Shade's miss branch
+#include "shade_device.h"     // sample_hemisphere, shade_surface, shade_sky, shade: Shade RS:386-428
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------------
+// Trace — RS:364-383: ground plane, then the mesh object BVH, then the sphere BVH.
+// tl / bl: this lane's LDS stacks for the object-level and the triangle-level traversals.
+// ---------------------------------------------------------------------------------------------------
+template <bool COUNT>
+__device__ __forceinline__ HitRec trace(const DevScene& S, v3 o, v3 d, int* tl, int* bl, LocalCounters& lc) {
+  lc.rays++;
+  HitRec best; best.t = URT_INF; best.kid = 0; best.u = 0; best.v = 0;
+  // IntersectGroundPlane RS:156-172
+  {
+    float t = -o.y / d.y;
+    if (t > 0 && t < best.t) { best.t = t; best.kid = 1; }
+  }
+  // one reciprocal per axis for the object-level slab test (normative form of RS:282-283)
+  v3 rcp = mk3(1.0f / (d.x + kEPSILON), 1.0f / (d.y + kEPSILON), 1.0f / (d.z + kEPSILON));
+  // IntersectMeshBVH RS:294-326 (`tests` is never reset: once a leaf was reached, every later popped
+  // node has its object intersected, A.5; object ids < 0 or out of range are skipped, not read)
+  if (S.n_meshes > 0) {
+    const float t_ground = best.t;                              // what the object-level cull compares with (urt_math.h tlas_cull)
+    int check = 1; tl[0] = 0; bool seen = false;
+    while (check > 0) {
+      check--;
+      int bi = tl[check * 64];
+      bool hit = false, culled = false; int index = -1;
+      if (bi < S.n_mesh_tlas) {
+        if (COUNT) lc.tlas_nodes++;
+        float4 a = S.mesh_tlas[2 * bi], b = S.mesh_tlas[2 * bi + 1];
+        index = as_int(a.w);
+        float t_min, t_max;
+        hit = tlas_slab_t(a, b, o, rcp, t_min, t_max);
+        culled = leaf_culled(b, t_min, t_max, t_ground);
+      }
+      if (hit) {
+        if (index < 0) { tl[check * 64] = bi * 2 + 1; check++; tl[check * 64] = bi * 2 + 2; check++; }
+        else seen = true;
+      }
+      if (seen && !culled && index >= 0 && index < S.n_meshes) intersect_mesh<COUNT>(S, S.mesh_root[index], o, d, best, bl, lc);
+    }
+  }
+  // IntersectSphereBVH RS:329-361
+  if (S.n_spheres > 0) {
+    int check = 1; tl[0] = 0; bool seen = false;
+    while (check > 0) {
+      check--;
+      int bi = tl[check * 64];
+      bool hit = false; int index = -1;
+      if (bi < S.n_sphere_tlas) {
+        if (COUNT) lc.tlas_nodes++;
+        float4 a = S.sphere_tlas[2 * bi], b = S.sphere_tlas[2 * bi + 1];
+        index = as_int(a.w);
+        hit = tlas_slab(a, b, o, rcp);
+      }
+      if (hit) {
+        if (index < 0) { tl[check * 64] = bi * 2 + 1; check++; tl[check * 64] = bi * 2 + 2; check++; }
+        else seen = true;
+      }
+      if (seen && index >= 0 && index < S.n_spheres) intersect_sphere<COUNT>(S, index, o, d, best, lc);
+    }
+  }
+  return best;
+}
+
+// The result image is written once per pixel and not read by this kernel: stored non-temporally so that it does not push
+// BVH lines out of the L2 (measured -1 %; the same hint on the sky's texel loads costs +3 % and is not used).
+typedef float f4v __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void st_result(float4* p, float4 v) {
+  f4v q = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(q, (f4v*)p);
+}
+
+// Cold per-pixel uniforms (the two camera matrices, 128 B) are read from the kernel-argument segment AT USE through a
+// laundered pointer instead of living in 32 SGPRs for the whole kernel: with them resident the register allocator spilled
+// and re-loaded the hot BVH pointers inside the traversal loop (an s_load + s_waitcnt on every node step).
+typedef const __attribute__((address_space(4))) float* kfloatp;
+__device__ __forceinline__ kfloatp kernarg_floats(unsigned byte_offset) {
+  const __attribute__((address_space(4))) char* p = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+  p += byte_offset;
+  asm volatile("" : "+s"(p));                      // opaque to LICM: the loads below stay where they are written
+  return (kfloatp)p;
+}
+__device__ __forceinline__ v3 mul_m4_k(kfloatp m, float x, float y, float z, float w) {   // urt::mul_m4 on a kernarg matrix
+  v3 r;
+  r.x = f_fma(m[12], w, f_fma(m[8], z, f_fma(m[4], y, m[0] * x)));
+  r.y = f_fma(m[13], w, f_fma(m[9], z, f_fma(m[5], y, m[1] * x)));
+  r.z = f_fma(m[14], w, f_fma(m[10], z, f_fma(m[6], y, m[2] * x)));
+  return r;
+}
+
+// CreateCameraRay RS:142-153 with the uv of RS:448-449.  p_off = byte offset of the FrameParams argument in the kernarg segment.
+template <unsigned P_OFF>
+__device__ __forceinline__ void camera_ray(const FrameParams& P, int x, int y, float& seed, v3& o, v3& d) {
+  float px = (float)x, py = (float)y;
+  float r0 = rand_next(seed, px, py);
+  float r1 = rand_next(seed, px, py);
+  float u = (px + r0 + P.pixel_off_x) / (float)P.width * 2.0f - 1.0f;
+  float v = (py + r1 + P.pixel_off_y) / (float)P.height * 2.0f - 1.0f;
+  kfloatp c2w = kernarg_floats(P_OFF + (unsigned)__builtin_offsetof(FrameParams, c2w));
+  kfloatp invp = kernarg_floats(P_OFF + (unsigned)__builtin_offsetof(FrameParams, invp));
+  o = mul_m4_k(c2w, 0.0f, 0.0f, 0.0f, 1.0f);
+  v3 dir = mul_m4_k(invp, u, v, 0.0f, 1.0f);
+  dir = mul_m4_k(c2w, dir.x, dir.y, dir.z, 0.0f);
+  d = normalize(dir);
+}
+// The same for a batched launch (modes 3, 5): the uniforms of the path's frame come from the launch's frame table in device
+// memory, read with scalar loads (table pointer and frame index are wave-uniform).  `f` must be wave-uniform.
+__device__ __forceinline__ void camera_ray_frame(const FrameUniforms* T, int f, const FrameParams& P, int x, int y, bool new_pixel, float& seed, v3& o, v3& d) {
+  kfloatp q = (kfloatp)(unsigned long long)(T + __builtin_amdgcn_readfirstlane(f));
+  if (new_pixel) seed = q[34];                     // RS:16: every pixel starts from the frame's _Seed; it carries over between a pixel's rays (RS:444)
+  float px = (float)x, py = (float)y;
+  float r0 = rand_next(seed, px, py);
+  float r1 = rand_next(seed, px, py);
+  float u = (px + r0 + q[32]) / (float)P.width * 2.0f - 1.0f;
+  float v = (py + r1 + q[33]) / (float)P.height * 2.0f - 1.0f;
+  kfloatp c2w = q, invp = q + 16;
+  o = mul_m4_k(c2w, 0.0f, 0.0f, 0.0f, 1.0f);
+  v3 dir = mul_m4_k(invp, u, v, 0.0f, 1.0f);
+  dir = mul_m4_k(c2w, dir.x, dir.y, dir.z, 0.0f);
+  d = normalize(dir);
+}
+static_assert(__builtin_offsetof(FrameUniforms, invp) == 64 && __builtin_offsetof(FrameUniforms, pixel_off_x) == 128 &&
+              __builtin_offsetof(FrameUniforms, seed) == 136, "camera_ray_frame indexes the table as floats");
+
+// Runs body(frame index as a wave-uniform value, lane predicate) once per distinct frame among the lanes of `pred` (almost
+// always one: a wave's refill straddles two frames only at a frame boundary of the launch).
+template <typename F>
+__device__ __forceinline__ void for_each_frame(bool pred, int frame, F&& body) {
+  unsigned long long todo = wballot(pred);
+  while (todo) {
+    int f = __builtin_amdgcn_readlane(frame, __builtin_ctzll(todo));
+    bool mine = pred && frame == f;
+    body(f, mine);
+    todo &= ~wballot(mine);
+  }
+}
+
+// kernels take (DevScene, FrameParams, ...) or (FrameParams, ...): by-value aggregates are laid out like C struct members
+static constexpr unsigned kPOffAfterScene = (unsigned)((sizeof(DevScene) + alignof(FrameParams) - 1) / alignof(FrameParams) * alignof(FrameParams));
+
+// tile -> pixel: one 8x8 tile per wave (the reference's [numthreads(8,8,1)] group, RS:431).
+// Blocks are dealt round-robin to the 8 XCDs (b % 8 shares an XCD, each XCD has a private 4 MiB L2).
+// xcd_run = G makes every XCD walk runs of G consecutive blocks (G * waves-per-block adjacent tiles):
+// G = 1 is plain linear order, large G approaches one contiguous image band per XCD (best L2 locality,
+// worst load balance: sky bands finish early).  Only speed depends on it, never results.
+__device__ __forceinline__ bool tile_pixel(const FrameParams& P, int& x, int& y) {
+  int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  int b = blockIdx.x;
+  int G = P.xcd_run;
+  int sb = ((b / (8 * G)) * 8 + (b & 7)) * G + ((b >> 3) % G);
+  int tile = sb * (blockDim.x >> 6) + wave;
+  int ntiles = P.tiles_x * P.n_strips;
+  if (tile >= ntiles) return false;
+  int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
+  x = tx * 8 + (lane & 7);
+  y = (P.first_group_row + ty * P.row_stride) * 8 + (lane >> 3);
+  return x < P.region_w && y < P.region_h;
+}
+
+__device__ __forceinline__ unsigned int wave_sum(unsigned int v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <bool COUNT>
+__device__ __forceinline__ void flush_counters(const LocalCounters& lc, DevCounters* ctr) {
+  // wave-reduce, then one atomic per wave and counter into one of kCounterShards slots: tens of
+  // thousands of same-address atomics serialise at ~88/us on this chip, sharded ones do not.
+  ctr += (blockIdx.x & (kCounterShards - 1));
+  unsigned int r = wave_sum(lc.rays);
+  unsigned int tn = 0, bn = 0, tt = 0, st = 0, ht = 0, hs = 0, hg = 0, hk = 0;
+  if (COUNT) {
+    tn = wave_sum(lc.tlas_nodes); bn = wave_sum(lc.blas_nodes); tt = wave_sum(lc.tri_tests); st = wave_sum(lc.sphere_tests);
+    ht = wave_sum(lc.hit_tri); hs = wave_sum(lc.hit_sphere); hg = wave_sum(lc.hit_ground); hk = wave_sum(lc.hit_sky);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (r) atomicAdd(&ctr->rays, (unsigned long long)r);
+    if (COUNT) {
+      if (tn) atomicAdd(&ctr->tlas_nodes, (unsigned long long)tn);
+      if (bn) atomicAdd(&ctr->blas_nodes, (unsigned long long)bn);
+      if (tt) atomicAdd(&ctr->tri_tests, (unsigned long long)tt);
+      if (st) atomicAdd(&ctr->sphere_tests, (unsigned long long)st);
+      if (ht) atomicAdd(&ctr->hit_tri, (unsigned long long)ht);
+      if (hs) atomicAdd(&ctr->hit_sphere, (unsigned long long)hs);
+      if (hg) atomicAdd(&ctr->hit_ground, (unsigned long long)hg);
+      if (hk) atomicAdd(&ctr->hit_sky, (unsigned long long)hk);
+    }
+  }
+}
+
+__device__ __forceinline__ void lane_stacks(const FrameParams& P, int*& tl, int*& bl) {
+  extern __shared__ int lds[];
+  int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  int per_wave = (P.tlas_stack + P.blas_stack) * 64;
+  tl = lds + wave * per_wave + lane;
+  bl = tl + P.tlas_stack * 64;
+}
+
+// Work distribution of the persistent kernels.  The frame is a sequence of pixel slots in tile order (64 consecutive slots
+// = one 8x8 tile).  One shared counter would be hit ~40,000 times per 1080p frame, and same-address atomics serialise at
+// ~88/us on this chip — that alone cost 0.4 ms.  So the tiles are dealt round-robin to kWorkShards counters (tile t belongs
+// to shard t % kWorkShards, each counter on its own 128-byte line); a wave draws from its home shard (its workgroup index)
+// and moves on to the next shard when that one is dry.  All shards advance at a similar pace, so the frame is still swept
+// roughly in natural order.
+struct WorkCursor {
+  unsigned int shard;       // shard this wave currently draws from
+};
+static_assert(kWorkShards == 64, "the dry-shard probe reads one counter per lane");
+
+// Tiles are dealt to the shards in RUNS of G = P.xcd_run consecutive tiles (run r belongs to shard r % kWorkShards).  G = 1
+// interleaves single tiles; a large G gives every shard contiguous image bands, and because workgroup b runs on XCD b % 8
+// and starts on shard b % kWorkShards, each XCD's L2 then serves a few bands of the image instead of all of it.
+__device__ __forceinline__ unsigned int shard_slots(unsigned int ntiles, unsigned int shard, unsigned int G, unsigned int NS) {   // slots owned by a shard
+  unsigned int cycle = NS * G;
+  unsigned int full = ntiles / cycle, rem = ntiles - full * cycle;
+  unsigned int extra = rem > shard * G ? min(rem - shard * G, G) : 0u;
+  return (full * G + extra) * 64u;
+}
+__device__ __forceinline__ unsigned int shard_tile(unsigned int shard, unsigned int q, unsigned int G, unsigned int NS) {   // q-th tile of a shard
+  unsigned int run = q / G;
+  return (run * NS + shard) * G + (q - run * G);
+}
+
+// slot -> pixel; false for slots that fall outside the dispatched region (ragged right/top edge)
+__device__ __forceinline__ bool slot_pixel(const FrameParams& P, unsigned int tile, unsigned int l, int& x, int& y) {
+  int ty = (int)tile / P.tiles_x, tx = (int)tile - ty * P.tiles_x;
+  x = tx * 8 + (int)(l & 7u);
+  y = (P.first_group_row + ty * P.row_stride) * 8 + (int)(l >> 3);
+  return x < P.region_w && y < P.region_h;
+}
+
+// The wave takes popcount(want) slots with ONE atomic; each lane of `want` gets its own slot (prefix popcount).  Returns true
+// and the pixel for lanes that received a valid one.  Sets `exhausted` when every shard is dry.
+// Batched launches (mode 3): the work is the concatenation of the frames' tile sequences (ntiles = frames x tiles_per_frame,
+// frame-major, so the launch sweeps frame 0 first); `frame` receives the frame a slot belongs to.
+__device__ __forceinline__ bool wave_fetch_pixels(const FrameParams& P, unsigned long long want, bool mine, unsigned int* next,
+                                                  unsigned int ntiles, WorkCursor& wc, bool& exhausted, int& x, int& y,
+                                                  unsigned int tiles_per_frame = 0, int* frame = nullptr) {
+  const int lane = threadIdx.x & 63;
+  unsigned int n = (unsigned int)__popcll(want);
+  const unsigned int G = (unsigned int)P.xcd_run, NS = (unsigned int)P.n_shards;
+  unsigned int own = shard_slots(ntiles, wc.shard, G, NS);
+  unsigned int base = 0;
+  if (lane == 0) base = atomicAdd(next + wc.shard * 32u, n);
+  base = (unsigned int)__builtin_amdgcn_readfirstlane((int)base);   // called by the whole wave: lane 0's value, and wave-uniform for the compiler (what hangs off it — shard moves, `exhausted` — stays in scalar registers)
+  unsigned int shard = wc.shard;
+  if (base + n >= own) {   // this shard is (now) dry: every lane looks at one counter, the wave moves to the next shard with work
+    unsigned int seen = __hip_atomic_load(next + lane * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned long long avail = wballot((unsigned int)lane < NS && seen < shard_slots(ntiles, (unsigned int)lane, G, NS)) & ~(1ull << shard);
+    if (!avail) {
+      exhausted = true;    // counters only grow, so this is final
+    } else {
+      unsigned long long after = shard == 63u ? 0ull : avail & ~((2ull << shard) - 1ull);
+      wc.shard = (unsigned int)__builtin_ctzll(after ? after : avail);
+    }
+  }
+  unsigned int local = base + (unsigned int)__popcll(want & ((1ull << lane) - 1ull));
+  if (!mine || local >= own) return false;
+  unsigned int tile = shard_tile(shard, local >> 6, G, NS);
+  if (frame) {
+    const unsigned int FG = (unsigned int)P.frame_group;
+    if (FG <= 1u) { unsigned int f = tile / tiles_per_frame; tile -= f * tiles_per_frame; *frame = (int)f; }
+    else {
+      // frames interleaved in groups of FG: the global sequence is run 0 of frames 0..FG-1, run 1 of frames 0..FG-1, ... — the same
+      // tiles of consecutive frames (same pixels, other jitter and seeds) are traced back to back, while their BVH subtrees are hot
+      unsigned int rg = tile / G, w = tile - rg * G;
+      unsigned int runs_pf = (tiles_per_frame + G - 1u) / G, group_runs = runs_pf * FG;
+      unsigned int grp = rg / group_runs, r = rg - grp * group_runs;
+      unsigned int f = grp * FG + r % FG;
+      tile = (r / FG) * G + w;
+      *frame = (int)f;
+      if (tile >= tiles_per_frame || f >= (unsigned int)P.n_frames) return false;
+    }
+    ntiles = tiles_per_frame;
+  }
+  if (P.tile_order == 1) tile = ntiles - 1u - tile;            // top strip first
+  return slot_pixel(P, tile, local & 63u, x, y);
+}
+
+// Every persistent kernel leaves its scheduler loop after P.sched_trips trips per wave, whatever the data (a frame needs ~1e3-1e5;
+// the host scales the cap with the launch: frames x rays x bounces, frame_batch.cpp).  A wave that leaves that way — or through the
+// per-phase traversal cap — counts itself in DevCounters::watchdog and raises the host-visible flag: its pixels are missing.
+__device__ __forceinline__ void report_watchdog(const FrameParams& P, DevCounters* shard) {
+  atomicAdd(&shard->watchdog, 1ull);
+  if (P.trip_flag) __hip_atomic_fetch_add(P.trip_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Path finished: fold its radiance into the pixel.  Result.xyz holds the running resultAverage
+// (RS:441,464) and .w the running _Seed between the rays of one pixel; the last ray writes RS:468.
+__device__ __forceinline__ void finish_path(const FrameParams& P, float4* result, int pixel, int ray_index, v3 res, float seed) {
+  int x = pixel & 0xffff, y = (unsigned)pixel >> 16;
+  size_t at = (size_t)y * P.width + x;
+  v3 avg = res;
+  if (ray_index > 0) { float4 prev = result[at]; avg = xyz(prev) + res; }
+  if (ray_index == P.num_rays - 1) {
+    float n = (float)P.num_rays;
+    result[at] = make_float4(avg.x / n, avg.y / n, avg.z / n, 1.0f);
+  } else {
+    result[at] = make_float4(avg.x, avg.y, avg.z, seed);
+  }
+}
+
+}  // namespace

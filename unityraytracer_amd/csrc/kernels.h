@@ -1,4 +1,5 @@
-// kernels.h — host-callable launchers of the HIP kernels in kernels.hip
+// kernels.h — host-callable launchers of the frame kernels: kernels.hip (mode 3, blends, strip packers), kernels_basic.hip (modes 0 - 2),
+// kernels_pool.hip (mode 4), kernels_serve.hip (mode 5)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "urt_device.h"
@@ -22,7 +23,7 @@ hipError_t launch_persist(const DevScene& S, const FrameParams& P, float4* resul
 // One launch traces P.n_frames consecutive frames (uniforms: T[0 .. n_frames) in DEVICE memory, Result images P.frame_stride apart from `result`).
 // front_mode: 0 = rays enter a triangle BVH through the BLAS phase only, 1 = they first walk its LDS-resident top inside FRONT,
 // 2 = listed form of 1 (needs P.lds_mesh and n_meshes <= 12), 3 = masked form of 2 (mesh heap of <= 31 nodes: P.walk_f4 float4s of walk
-// table behind S.mesh_tlas, P.lds_mesh = 0; kernels.hip front_masked)
+// table behind S.mesh_tlas, P.lds_mesh = 0; front_device.h front_masked)
 hipError_t launch_sched(const DevScene& S, const FrameParams& P, const FrameUniforms* T, float4* result, DevCounters* ctr,
                         unsigned int* next, int n_blocks, int front_mode, bool count, hipStream_t st, TraceLaunchRecord* rec);
 // mode 5: mode 3 with the triangle-BVH phase as a service shared by the 4 waves of a workgroup (k_serve); `mail` = 2 float4 per

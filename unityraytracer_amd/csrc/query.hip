@@ -1,7 +1,7 @@
 // query.hip — batched ray queries against the prepared device scene (urt_ray_query / urt_ray_query_device, include/urt.h).
 //
-// One ray per lane, wave64, 256 threads per workgroup; per-lane LDS stacks laid out [entry][lane] as the frame kernels' (kernels.hip
-// lane_stacks), sized from the prepared scene.  The walk is kernels.hip trace() — the same device functions (trace_device.h), the same
+// One ray per lane, wave64, 256 threads per workgroup; per-lane LDS stacks laid out [entry][lane] as the frame kernels' (frame_device.h
+// lane_stacks), sized from the prepared scene.  The walk is frame_device.h trace() — the same device functions (trace_device.h), the same
 // arithmetic, the reference's "tests never reset" object walk (A.5) and the (t, index slot) tie rule (query_device.h) — with two changes:
 //  * best.t starts at the ray's t_max, so a hit counts only when t < t_max (exclusive); the object-level cull still compares with the
 //    ground-plane distance alone, exactly as trace() does, so its argument does not depend on t_max;

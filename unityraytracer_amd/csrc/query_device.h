@@ -1,5 +1,5 @@
 // query_device.h — one ray's trace outside a frame and the fields of its hit record, shared by the ray queries (query.hip k_query) and
-// the feature buffers (aov.hip k_aov).  The walk is kernels.hip trace() — the same device functions (trace_device.h), the same arithmetic,
+// the feature buffers (aov.hip k_aov).  The walk is frame_device.h trace() — the same device functions (trace_device.h), the same arithmetic,
 // the reference's "tests never reset" object walk (A.5) and the (t, index slot) tie rule — bounded by t_max.  Internal to the library;
 // included by .hip translation units only, after trace_device.h.
 #pragma once
@@ -30,7 +30,7 @@ __device__ __forceinline__ void intersect_mesh_any(const DevScene& S, int32_t ro
   }
 }
 
-// trace() of kernels.hip bounded by t_max (> 0, not NaN: the caller answers the others with a miss); kind 0 = nothing with t < t_max
+// trace() of frame_device.h bounded by t_max (> 0, not NaN: the caller answers the others with a miss); kind 0 = nothing with t < t_max
 template <bool ANY>
 __device__ __forceinline__ HitRec query_trace(const DevScene& S, v3 o, v3 d, float t_max, int* tl, int* bl) {
   LocalCounters lc;                                             // never counted: queries leave urt_counters alone
@@ -101,7 +101,7 @@ struct HitRecord { float4 r0, r1, r2; };
 __device__ __forceinline__ HitRecord hit_record(const DevScene& S, const HitRec& h, v3 o, v3 d) {
   float4 r0 = make_float4(URT_INF, 0, 0, 0), r1 = make_float4(0, 0, 0, 0), r2 = make_float4(as_float(-1), as_float(-1), 0, 0);
   if (h.kind() != 0) {
-    // position and normal: the expressions of kernels.hip shade_surface (RS:164-170, 192-194, 259-264)
+    // position and normal: the expressions of shade_device.h shade_surface (RS:164-170, 192-194, 259-264)
     v3 pos = madd(h.t, d, o);
     v3 nrm;
     int object = -1, primitive = -1;

@@ -6,13 +6,13 @@
 // scene.  A query is the body of k_mega's pixel (RS:440-468): `samples` paths, one after the other on the same lane because the running
 // seed chains them (RS:444), each of up to `bounces` iterations of Trace + Shade.  Trace is query_trace<false> with t_max = +inf (held
 // bit-identical to the frame kernels' trace); Shade is the frame kernels' own (shade_device.h), never counted.  Pixels mode builds its
-// camera ray with the fma chains of kernels.hip camera_ray, the matrices arriving as a kernel-argument struct (as aov.hip's).
+// camera ray with the fma chains of frame_device.h camera_ray, the matrices arriving as a kernel-argument struct (as aov.hip's).
 // Loads: three float4 per ray or one 8-byte record per pixel; stores: one non-temporal float4 per query.
 //
 // Two kernels run the same per-lane steps (query_begin / sample_begin / bounce_step) and differ only in which lane a query runs on:
 //  * k_radiance: query i on thread i of the grid;
 //  * k_radiance_persist: a resident grid whose lanes take the next query index from a work counter when theirs is finished (ballot of the
-//    free lanes, ONE atomic per wave, prefix popcount — kernels.hip k_persist's scheme), so a lane whose paths died on the sky does not
+//    free lanes, ONE atomic per wave, prefix popcount — kernels_basic.hip k_persist's scheme), so a lane whose paths died on the sky does not
 //    idle while a neighbour runs bounces x samples.  Its loop ends when the counter has passed n: no watchdog.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -56,7 +56,7 @@ __device__ __forceinline__ bool query_begin(const RadianceCamera& C, const void*
 }
 
 // The start of one sample: res = 0, energy = 1 and the sample's first ray — the query's own, or CreateCameraRay RS:142-153 with the uv of
-// RS:448-449 (two rand() draws; the expressions of kernels.hip camera_ray).
+// RS:448-449 (two rand() draws; the expressions of frame_device.h camera_ray).
 template <bool PIXELS>
 __device__ __forceinline__ void sample_begin(const RadianceCamera& C, Lane& L) {
   L.res = mk3(0, 0, 0); L.energy = mk3(1, 1, 1);

@@ -75,13 +75,13 @@ void pack_albedo(const urt_RayTraceParams& m, float* dst) {
   dst[0] = albedo.x; dst[1] = albedo.y; dst[2] = albedo.z; dst[3] = m.smoothness;
 }
 
-// "Masked" object-level walk (kernels.hip front_masked): for a mesh heap of <= 31 nodes the walk RS:294-326 is evaluated without
+// "Masked" object-level walk (front_device.h front_masked): for a mesh heap of <= 31 nodes the walk RS:294-326 is evaluated without
 // a stack.  Which nodes a ray pops depends only on the slab tests of their ancestors, and the pop order (children pushed 2i+1
 // then 2i+2, so the right child is popped first) is a static pre-order of the heap.  The heap is therefore re-indexed in that
 // order ("position"): the right child of the node at position p sits at p + 1, the left child at p + 2^(h-1), h = levels below and
 // including p.  One bit per position: H = slab test passed, P = popped (root; children of a popped, hit, interior node — a shift
 // per level), objects to test = popped leaves from the first popped-and-hit leaf on (`tests` is never reset, A.5), in position
-// order = pop order.  The table appended to the device copy of the heap (float4 units; layout shared with kernels.hip):
+// order = pop order.  The table appended to the device copy of the heap (float4 units; layout shared with front_device.h front_masked):
 //   [0]  n_eval, levels, interior mask, exist mask          [1] leaf_any mask, leaf_valid mask, 0, 0
 //   [2]  depth masks d = 0..3                                [3] left-child shifts d = 0..3
 //   [4 .. 20)  per position p = 0..31: int2 {triangle-BVH root of the MeshObject, first triangle in the LDS copy of the single-leaf
@@ -280,7 +280,7 @@ urt_MeshObject mesh_object(const std::vector<uint8_t>& records, int i) {
 struct SceneTables {
   std::vector<float> mats, albedo;              // spheres first, then mesh objects, then the ground plane (pack_material, pack_albedo)
   std::vector<float> sphere_pr;                 // position, radius
-  std::vector<float> mesh_tlas, sphere_tlas;    // object-level heaps (pack_tlas); a small mesh heap's masked-walk table rides behind it (kernels.hip front_masked)
+  std::vector<float> mesh_tlas, sphere_tlas;    // object-level heaps (pack_tlas); a small mesh heap's masked-walk table rides behind it (front_device.h front_masked)
   std::vector<int32_t> cull, mesh_leaf;         // cull_words
   int walk_f4 = 0, n_mesh_tlas = 0, n_sphere_tlas = 0, tlas_stack = 2;
 };
@@ -491,7 +491,7 @@ int prepare_scene(urt_context* ctx) {
   // triangle-BVH traversal stack budget (per lane, LDS)
   if (n_blas_nodes >= (1u << 26)) return fail(ctx, URT_ERR_SCENE, "triangle BVH larger than 2^26 nodes (4 GiB)");   // kernels address nodes by 32-bit byte offsets
   if ((uint64_t)n_tris * 48ull >= (1ull << 32)) return fail(ctx, URT_ERR_SCENE, "more than 2^32 / 48 triangles (4 GiB of triangle records)");   // 32-bit byte offsets as well
-  C.blas_stack = std::max(2, blas_max_depth + 1) + 1;      // + the sentinel entry below the stack (kernels.hip blas_node_eval_ptr)
+  C.blas_stack = std::max(2, blas_max_depth + 1) + 1;      // + the sentinel entry below the stack (trace_device.h blas_node_eval_ptr)
   C.n_blas_nodes = (int)std::min<size_t>(0x7fffffff, n_blas_nodes);
   C.n_scene_tris = (int)n_tris; C.scene_max_depth = blas_max_depth;
   if ((rc = verify_cull_flags(ctx, T.cull, T.mesh_leaf))) return rc;

@@ -1,4 +1,4 @@
-// sky_device.h — the sky lookup of Shade's miss branch (RS:420-427, A.11) that the frame kernels (kernels.hip shade_sky) and the
+// sky_device.h — the sky lookup of Shade's miss branch (RS:420-427, A.11) that the frame kernels (shade_device.h shade_sky) and the
 // feature buffers (aov.hip) share: the direction -> (u, v) math and the bilinear, repeat-wrapped texel fetch.  Internal to the library;
 // included by .hip translation units only, after trace_device.h.
 #pragma once

@@ -62,7 +62,7 @@ struct FrameParams {
   int blas_stack;           // LDS entries per lane reserved for the triangle-BVH stack
   int block_threads;        // workgroup size (64, 128 or 256)
   int tile_order;           // persistent modes: 0 = strips bottom to top (natural), 1 = top to bottom
-  int xcd_run;              // blocks per XCD run in the tile order (kernels.hip tile_pixel); persistent modes: tiles per run of a work-counter shard
+  int xcd_run;              // blocks per XCD run in the tile order (frame_device.h tile_pixel); persistent modes: tiles per run of a work-counter shard
   int n_shards;             // persistent modes: work-counter shards in use (power of two, 1..kWorkShards)
   int frame_group;          // batched launches: frames whose tile runs are interleaved (1 = frame after frame)
   int refill_min;           // persistent modes: dead lanes per wave that trigger a refill (1..64)
@@ -76,7 +76,7 @@ struct FrameParams {
   int lds_mesh, lds_sphere; // mode 3: keep the object-level mesh heap + roots / sphere heap + spheres in LDS (0/1)
   int walk_f4;              // mode 3, masked FRONT (front mode 3): float4s of the walk table behind the mesh heap's device copy, kept in LDS
                             // instead of the heap itself (scene_prep.cpp build_walk_table); 0 = not in use
-  int serve;                // mode 5: the traversal phase is a service shared by the waves of a workgroup (kernels.hip k_serve) (0/1)
+  int serve;                // mode 5: the traversal phase is a service shared by the waves of a workgroup (kernels_serve.hip k_serve) (0/1)
   int pool_inloop;          // modes 4, 5: idle lanes that trigger a re-feed of the traversal phase from the waiting rays (1..64)
   int pool_other_min;       // mode 4: lanes of FRONT / SHADE work that make those phases worth a trip while rays queue for the BVH
   unsigned int watchdog_steps;  // cap on traversal trips per scheduled BLAS phase: a few times (nodes + leaves) of the scene
