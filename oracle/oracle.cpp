@@ -503,7 +503,10 @@ extern "C" {
 int oracle_render(const OracleScene* scene, int x0, int y0, int x1, int y1, int mode, int n_threads,
                   float* out, OracleCounters* counters) {
   if (!scene || !out || x0 < 0 || y0 < 0 || x1 > scene->width || y1 > scene->height || x0 > x1 || y0 > y1) return 1;
-  if (mode == 1 && scene->n_mesh_objects > 0 && (!scene->blas_nodes || !scene->blas_tri_index || !scene->blas_mesh_root || scene->n_blas_nodes <= 0)) return 1;   // mode 1 walks the triangle BVH: it must be there
+  if (mode == 1 && scene->n_mesh_objects > 0 && (!scene->blas_tri_index || !scene->blas_mesh_root || scene->n_blas_nodes < 0 || (scene->n_blas_nodes > 0 && !scene->blas_nodes))) return 1;   // mode 1 walks the triangle BVH: it must be there (no node at all when every MeshObject is a single leaf: the roots are leaf codes)
+  if (mode == 1 && scene->n_blas_nodes == 0)
+    for (int32_t m = 0; m < scene->n_mesh_objects; m++)
+      if (scene->blas_mesh_root[m] >= 0 && scene->blas_mesh_root[m] != 0x7fffffff) return 1;   // a root that names a node, and no node
   if (n_threads < 1) n_threads = 1;
   std::vector<OracleCounters> cs((size_t)n_threads);
   auto work = [&](int tid) {

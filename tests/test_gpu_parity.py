@@ -128,12 +128,18 @@ def test_many_meshes_beyond_the_lds_tables(gpu_ctx):
         assert_same(gpu, ref, f"many meshes, mode {mode}")
         for k in ("rays", "tlas_nodes", "blas_nodes", "tri_tests", "hit_tri", "hit_ground", "hit_sky", "pixels"):
             assert gc[k] == oc[k], (mode, k, gc[k], oc[k])
+        if mode in (3, 5):                                    # which of the two ran: the fallbacks (lds_tables bit 0 = mesh heap + roots, 3 = walk table)
+            info = gpu_ctx.launch_info()
+            assert info["kernel_mode"] == mode and info["lds_tables"] == 0 and info["front_mode"] == 1 and info["tlas_stack"] == 11, info
     try:
-        for tn, tf in ((256, 1), (256, 0), (32, 1), (1, 1), (0, 0)):
+        # (256 nodes are 16 KiB; with the 11-entry object-level stacks five such workgroups do not fit a CU's LDS, so the top is halved once)
+        for tn, tf, front, top in ((256, 1, 1, 128), (256, 0, 0, 128), (32, 1, 1, 32), (1, 1, 1, 1), (0, 0, 0, 0)):
             gpu_ctx.set_option("top_nodes", tn); gpu_ctx.set_option("top_front", tf)
             gpu, _, gc = render_gpu(gpu_ctx, sc, 3, count=True)
             assert_same(gpu, ref, f"many meshes, top_nodes {tn} top_front {tf}")
             assert gc["blas_nodes"] == oc["blas_nodes"] and gc["tri_tests"] == oc["tri_tests"] and gc["watchdog_trips"] == 0
+            info = gpu_ctx.launch_info()
+            assert (info["top_nodes"], info["front_mode"], info["lds_tables"]) == (top, front, 0), (tn, tf, info)
     finally:
         gpu_ctx.set_option("top_nodes", -1); gpu_ctx.set_option("top_front", -1)
 
