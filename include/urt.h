@@ -51,8 +51,8 @@ enum {
 
 /* ---- library / context ------------------------------------------------------------------- */
 URT_API int urt_abi_version(void);                       /* bumps when this header changes incompatibly (still 4: the ray queries,
-                                                            the feature buffers, the denoiser and the temporal reprojection were added
-                                                            without changing anything that existed) */
+                                                            the feature buffers, the denoiser, the temporal reprojection and the
+                                                            resampling were added without changing anything that existed) */
 URT_API int urt_device_count(int* out_count);
 /* One context per process and GPU (the one-process-per-GPU model).  device = HIP ordinal. */
 URT_API int urt_context_create(int device, urt_context** out_ctx);
@@ -399,6 +399,63 @@ typedef struct urt_ReprojectMotion {     /* 24 bytes */
 
 URT_API int urt_reproject_objects(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params,
                                   const urt_ReprojectMotion* motion);
+
+/* ---- resampling --------------------------------------------------------------------------- */
+/* The step after urt_reproject, kept on the GPU: find the pixels whose history is short (urt_select_pixels), trace fresh samples for them
+ * (urt_radiance_query_device, URT_RADIANCE_PIXELS, over the list) and blend the samples back into the accumulated image and its count
+ * texture (urt_blend_samples); urt_resample_below is the three in one call for hosts without device memory of their own.  With
+ * below == 1 the pixels a reprojection left without history are resampled; with below > 1 the same calls are a simple adaptive sampler
+ * that gives more samples to pixels whose history is short.  Count textures and image layout as in "temporal reprojection" above.
+ *
+ * urt_select_pixels(count, below, d_pixels, capacity, out_n): ordered stream compaction of a count texture (W x H) into a pixel list.
+ *  - pixel (x, y) is selected when !(count[y * W + x].x >= below): NaN, negative and -inf counts are selected, +inf is not.
+ *  - the selected pixels are written as urt_PathPixel {x, y} in ascending texel index y * W + x: a dense list that starts at d_pixels[0]
+ *    and holds at most `capacity` entries; entries from `capacity` on are not touched.  The same texture and `below` give the same list.
+ *  - *out_n = the total number selected, which may exceed capacity.  capacity == 0 with d_pixels == NULL only counts.
+ *  - the call observes `count`: like urt_reproject it submits the deferred frames first; then it enqueues its kernels on the context's
+ *    stream and SYNCHRONISES to return *out_n (it reports URT_ERR_WATCHDOG as urt_synchronize does).  The scene is not read (not
+ *    prepared); urt_counters and the frame batching are not changed.
+ *  - d_pixels: device memory, 8-byte aligned.  W * H <= 2^31 - 1.
+ *  - errors, checked before anything is enqueued or written: URT_ERR_INVALID_ARGUMENT for a NaN `below`, capacity < 0, d_pixels == NULL
+ *    with capacity > 0, d_pixels not 8-byte aligned, out_n == NULL, a texture of more than 2^31 - 1 texels; URT_ERR_INVALID_HANDLE for
+ *    `count` 0 or unknown.
+ *
+ * urt_blend_samples(d_pixels, d_samples, n, weight, dst, count, max_history): for i = 0 .. n-1 with (x, y) = d_pixels[i] inside dst — an
+ * entry whose pixel lies outside is skipped, nothing is written for it —, t = d_samples[i] (RGBA32F), c = the dst texel and N = the .x of
+ * the count texel at (x, y); arithmetic as stated in "temporal reprojection": float32, one rounding per operation, no fma:
+ *     s  = 0 when N is not finite or < 0, else max_history > 0 ? fminf(N, fmaxf(max_history - weight, 0.0f)) : N
+ *     a  = weight / (s + weight);  ia = 1.0f - a
+ *     dst.rgb = t.rgb*a + c.rgb*ia;  dst.a = a*a + c.a*ia;  count = (s + weight, 0, 0, 0)
+ *  - with weight == 1.0f this is urt_blit_add_history operation for operation: blending every pixel of an image with weight 1 gives the
+ *    dst and count that urt_blit_add_history(src, dst, count, max_history) gives, bit for bit.
+ *  - weight: the number of frame-equivalents the sample stands for (a sample of k times the frame's _numRays: k).
+ *  - the pixels of a list must be distinct, as urt_select_pixels makes them.  For a duplicated pixel one of its entries wins; which one
+ *    is unspecified.  Nothing else is affected.
+ *  - the call writes dst and count: it submits the deferred frames first, then enqueues one kernel on the context's stream and returns
+ *    without synchronising.  n == 0: URT_OK (after the checks), nothing is launched.  urt_counters are not changed.
+ *  - d_pixels: device memory, 8-byte aligned; d_samples: device memory, 16-byte aligned.
+ *  - errors, checked before anything is enqueued or written: URT_ERR_INVALID_ARGUMENT for n < 0, a NULL or misaligned pointer with n > 0,
+ *    a weight that is not finite or <= 0, max_history NaN, negative or in (0, 1), dst == count, sizes that differ, dst or count bound as
+ *    _SkyboxTexture; URT_ERR_INVALID_HANDLE for dst or count 0 or unknown.
+ *
+ * urt_resample_below(dst, count, below, samples, bounces, weight, max_history, out_n): urt_select_pixels(count, below), then
+ * urt_radiance_query_device(URT_RADIANCE_PIXELS, samples, bounces) over the list, then urt_blend_samples(weight, dst, count, max_history).
+ *  - dst, count and *out_n are bit for bit what the three separate calls produce.  The uniforms, _Seed included, are those bound at call
+ *    time.
+ *  - the pixel list and the samples live in scratch held by the context, grown on demand to what the SELECTED count needs (8 + 16 bytes
+ *    per selected pixel, plus one word per 2048 texels): not image-sized.  URT_ERR_OUT_OF_MEMORY when that fails.
+ *  - *out_n (out_n may be NULL) = the number of pixels resampled; when it is 0 nothing more is launched.
+ *  - the call synchronises once, for the selected count; the trace and the blend are only enqueued.  urt_counters and the frame batching
+ *    are not changed; a changed scene is prepared as urt_radiance_query_device does.
+ *  - errors, checked before anything is enqueued or written: those of urt_blend_samples for weight, max_history, dst and count; a NaN
+ *    `below`, samples outside 1..4096 or bounces outside 0..64 (as urt_radiance_query): URT_ERR_INVALID_ARGUMENT; URT_ERR_UNBOUND when no
+ *    texture is bound as Result or a camera matrix was never set (the cases of pixels mode; here also when nothing is selected);
+ *    URT_ERR_INVALID_ARGUMENT when dst and count do not have the size of the texture bound as Result. */
+URT_API int urt_select_pixels(urt_context* ctx, urt_handle count, float below, void* d_pixels, int capacity, int* out_n);
+URT_API int urt_blend_samples(urt_context* ctx, const void* d_pixels, const void* d_samples, int n, float weight, urt_handle dst,
+                              urt_handle count, float max_history);
+URT_API int urt_resample_below(urt_context* ctx, urt_handle dst, urt_handle count, float below, int samples, int bounces, float weight,
+                               float max_history, int* out_n);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 typedef struct urt_counters {

@@ -128,6 +128,10 @@ internal static class UrtNative {
     internal const float ReprojectDefaultMaxHistory = 64.0f, ReprojectDefaultNormalThreshold = 0.9f, ReprojectDefaultPlaneThreshold = 0.02f;
     [DllImport(Lib)] internal static extern int urt_reproject(IntPtr ctx, in ReprojectImages images, in ReprojectParams p);
     [DllImport(Lib)] internal static extern int urt_blit_add_history(IntPtr ctx, ulong src, ulong dst, ulong count, float maxHistory);
+    // resampling (include/urt.h "resampling"): devicePixels = urt_PathPixel[], 8-byte aligned; deviceSamples = RGBA32F, 16-byte aligned
+    [DllImport(Lib)] internal static extern int urt_select_pixels(IntPtr ctx, ulong count, float below, IntPtr devicePixels, int capacity, out int n);
+    [DllImport(Lib)] internal static extern int urt_blend_samples(IntPtr ctx, IntPtr devicePixels, IntPtr deviceSamples, int n, float weight, ulong dst, ulong count, float maxHistory);
+    [DllImport(Lib)] internal static extern int urt_resample_below(IntPtr ctx, ulong dst, ulong count, float below, int samples, int bounces, float weight, float maxHistory, out int n);
     // per-object motion (include/urt.h urt_reproject_objects): tables are buffers of urt_buffer_create with stride 48, entry i = object i
     [StructLayout(LayoutKind.Sequential)]
     internal struct ObjectMotion {                          // urt_ObjectMotion, 48 B: current world -> previous world

@@ -234,6 +234,18 @@ public static class UrtTemporal {
         UrtDevice.Check(UrtNative.urt_blit_add_history(ctx, Wrap(ctx, src, width, height), Wrap(ctx, dst, width, height),
                                                        Wrap(ctx, count, width, height), maxHistory));
     }
+    /// After Reproject (or MoveObjects): fresh samples for the pixels the reprojection left with a count below `below` (1: no history at
+    /// all), traced and blended into `converged` and `count` on the GPU (include/urt.h urt_resample_below).  The Result texture, the camera
+    /// matrices, _PixelOffset and _Seed are those bound at call time: set a fresh _Seed first, as for a frame.  samples / bounces: the
+    /// frame's _numRays / _numBounces make a resampled pixel exactly one frame's worth (weight 1).  Returns the number of pixels resampled.
+    public static int ResampleDisocclusions(IntPtr converged, IntPtr count, int width, int height, int samples, int bounces,
+                                            float below = 1.0f, float weight = 1.0f, float maxHistory = 64.0f) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtTemporal: resample on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        UrtDevice.Check(UrtNative.urt_resample_below(ctx, Wrap(ctx, converged, width, height), Wrap(ctx, count, width, height), below,
+                                                     samples, bounces, weight, maxHistory, out int n));
+        return n;
+    }
 }
 
 /// new ComputeBuffer(count, stride); .SetData(List<T>); .Release(); .count; .stride            (RM:233-252)

@@ -145,6 +145,10 @@ int urt_context_destroy(urt_context* ctx) {
   if (ctx->rq_in) (void)hipFree(ctx->rq_in);
   if (ctx->rq_out) (void)hipFree(ctx->rq_out);
   if (ctx->rq_next) (void)hipFree(ctx->rq_next);
+  if (ctx->rs_counts) (void)hipFree(ctx->rs_counts);
+  if (ctx->rs_total) (void)hipHostFree(ctx->rs_total);
+  if (ctx->rs_pixels) (void)hipFree(ctx->rs_pixels);
+  if (ctx->rs_samples) (void)hipFree(ctx->rs_samples);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
   return URT_OK;

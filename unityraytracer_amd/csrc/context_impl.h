@@ -2,7 +2,7 @@
 //   context.cpp      context lifetime, stream, buffers, textures, readback, uniforms, blits, strip packing, options, counters, debug accessors
 //   scene_prep.cpp   bound buffers -> device scene (full and in-place preparation)
 //   frame_batch.cpp  deferred frames, the Result slab, trace launches (do_dispatch, flush_pending)
-//   image_ops.cpp    ray queries, radiance queries, feature buffers, denoiser, reprojection
+//   image_ops.cpp    ray queries, radiance queries, feature buffers, denoiser, reprojection, resampling
 // Private: nothing else includes it.  What crosses the files lives in namespace urtd and stays hidden (-fvisibility=hidden).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -239,6 +239,13 @@ struct urt_context {
   float4* dn_scratch = nullptr; size_t dn_cap = 0;
   // urt_reproject_objects: grow-only device copies of the mesh and the sphere motion table, mo_cap[k] bytes each
   float4* mo_table[2] = {nullptr, nullptr}; size_t mo_cap[2] = {0, 0};
+  // urt_select_pixels / urt_resample_below: grow-only device scratch for the per-block counts and the total behind them (rs_counts_cap
+  // words) and a pinned host word the total is copied to; urt_resample_below: the pixel list (rs_pixels_cap entries of 8 bytes) and its
+  // samples (rs_samples_cap texels), both sized by the selected count, not by the image
+  unsigned int* rs_counts = nullptr; size_t rs_counts_cap = 0;
+  unsigned int* rs_total = nullptr;
+  void* rs_pixels = nullptr; size_t rs_pixels_cap = 0;
+  float4* rs_samples = nullptr; size_t rs_samples_cap = 0;
 };
 
 namespace urtd {

@@ -1,5 +1,5 @@
 // image_ops.cpp — the entry points of include/urt.h that work on whole images or ray batches next to the frame loop: ray queries,
-// radiance queries, feature buffers, the denoiser, temporal reprojection.
+// radiance queries, feature buffers, the denoiser, temporal reprojection, resampling.
 #include "experiments.h"
 #include "context_impl.h"
 
@@ -8,6 +8,7 @@
 #include "aov.h"
 #include "denoise.h"
 #include "reproject.h"
+#include "resample.h"
 
 using namespace urtd;
 
@@ -74,6 +75,46 @@ int grow_scratch(urt_context* ctx, void** p, size_t* cap, size_t need, size_t by
 // urt_radiance_query with option "radiance_persist" at -1: k_radiance_persist, measured faster on full-frame pixel batches in any order and
 // within 1.5 % on the probe bake (profiles/r10_logs/r10_radiance_query_bench.log)
 constexpr bool kRadiancePersistAuto = true;
+
+// urt_select_pixels / urt_resample_below: the count texture fits the selection kernels (width * height <= 2^31 - 1: the total is an int)
+int check_select_size(urt_context* ctx, const char* prefix, const Texture* c) {
+  if ((size_t)c->w * (size_t)c->h > 0x7fffffffull)
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(prefix) + ": the count texture has more than 2^31 - 1 texels");
+  return URT_OK;
+}
+
+// the per-block counts of a selection over n_texels texels and the pinned word its total comes back in
+int select_scratch(urt_context* ctx, const char* what, size_t n_texels) {
+  const size_t words = select_scratch_words(n_texels);
+  if (int rc = grow_scratch(ctx, (void**)&ctx->rs_counts, &ctx->rs_counts_cap, words, words * sizeof(unsigned int), what)) return rc;
+  if (!ctx->rs_total) URT_HIP(ctx, hipHostMalloc((void**)&ctx->rs_total, 64, hipHostMallocDefault));
+  return URT_OK;
+}
+
+// after launch_select_count (and whatever else was enqueued behind it): the call's one synchronisation; *total = the number selected
+int select_total(urt_context* ctx, size_t n_texels, int* total) {
+  URT_HIP(ctx, hipMemcpyAsync(ctx->rs_total, ctx->rs_counts + select_blocks(n_texels), sizeof(unsigned int), hipMemcpyDeviceToHost, touch(ctx)));
+  URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
+  if (int rc = check_watchdog(ctx)) return rc;
+  *total = (int)*ctx->rs_total;
+  return URT_OK;
+}
+
+// weight and max_history of urt_blend_samples / urt_resample_below
+int check_blend_numbers(urt_context* ctx, const char* prefix, float weight, float max_history) {
+  if (!std::isfinite(weight) || !(weight > 0.0f)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(prefix) + ": weight must be finite and > 0");
+  if (!valid_max_history(max_history)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(prefix) + ": max_history must be 0 or >= 1");
+  return URT_OK;
+}
+
+// dst and count of urt_blend_samples / urt_resample_below: two known textures of one size, neither bound as the sky
+int resolve_blend_targets(urt_context* ctx, const char* prefix, urt_handle dst, urt_handle count, Texture** t) {
+  const TexArg a[2] = {{dst, "dst", false}, {count, "count", false}};
+  if (int rc = resolve_textures(ctx, prefix, a, 2, t)) return rc;
+  if (dst == count) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(prefix) + ": dst and count are the same texture");
+  if (int rc = check_same_size(ctx, prefix, t, 2)) return rc;
+  return check_outputs(ctx, prefix, a, 0, 2);
+}
 
 }  // namespace
 
@@ -377,6 +418,104 @@ int urt_reproject(urt_context* ctx, const urt_ReprojectImages* images, const urt
 int urt_reproject_objects(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params,
                           const urt_ReprojectMotion* motion) {
   return reproject_impl(ctx, images, params, motion, true);
+}
+
+/* ---- resampling ---- */
+// urt_select_pixels observes the count texture: every argument is checked and the scratch is grown first, then the deferred frames are
+// submitted, the three phases of csrc/resample.hip are enqueued on the main stream and the call waits once, for the total.  The scene is
+// not read and the counters are not changed.
+int urt_select_pixels(urt_context* ctx, urt_handle count, float below, void* d_pixels, int capacity, int* out_n) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  if (!out_n) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "select_pixels: out_n is NULL");
+  if (std::isnan(below)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "select_pixels: below is NaN");
+  if (capacity < 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "select_pixels: negative capacity");
+  if (capacity > 0 && !d_pixels) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "select_pixels: d_pixels is NULL");
+  if (capacity > 0 && ((uintptr_t)d_pixels & 7u)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "select_pixels: d_pixels must be 8-byte aligned");
+  Texture* c = find_texture(ctx, count);
+  if (!c) return fail(ctx, URT_ERR_INVALID_HANDLE, "select_pixels: unknown count texture handle");
+  if (int rc = check_select_size(ctx, "select_pixels", c)) return rc;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t n_texels = (size_t)c->w * (size_t)c->h;
+  if (int rc = select_scratch(ctx, "select_pixels: scratch allocation", n_texels)) return rc;
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  URT_HIP(ctx, launch_select_count(c->dev, n_texels, below, ctx->rs_counts, touch(ctx)));   // the device pointer after the flush (a Result texture may be renamed)
+  URT_HIP(ctx, launch_select_write(c->dev, c->w, n_texels, below, ctx->rs_counts, (int2*)d_pixels, capacity, touch(ctx)));
+  int total = 0;
+  if (int rc = select_total(ctx, n_texels, &total)) return rc;
+  *out_n = total;
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+// urt_blend_samples writes dst and count: checked first, then the deferred frames are submitted and k_blend_samples is enqueued.
+int urt_blend_samples(urt_context* ctx, const void* d_pixels, const void* d_samples, int n, float weight, urt_handle dst, urt_handle count,
+                      float max_history) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  if (n < 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "blend_samples: negative sample count");
+  if (n > 0 && (!d_pixels || !d_samples)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "blend_samples: d_pixels / d_samples is NULL");
+  if (n > 0 && (((uintptr_t)d_pixels & 7u) || ((uintptr_t)d_samples & 15u)))
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "blend_samples: d_pixels must be 8-byte aligned, d_samples 16-byte aligned");
+  if (int rc = check_blend_numbers(ctx, "blend_samples", weight, max_history)) return rc;
+  Texture* t[2];
+  if (int rc = resolve_blend_targets(ctx, "blend_samples", dst, count, t)) return rc;
+  if (n == 0) return URT_OK;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  t[0]->other_writes = true;
+  t[1]->other_writes = true;
+  URT_HIP(ctx, launch_blend_samples((const int2*)d_pixels, (const float4*)d_samples, n, weight, t[0]->dev, t[1]->dev, t[0]->w, t[0]->h,
+                                    max_history, touch(ctx)));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+// The three steps in one call, for hosts without device pointers: count + scan, ONE synchronisation for the selected count n, then the
+// scratch for n pixels and n samples, the write phase, the radiance query (pixels mode, device form) and the blend, all only enqueued.
+// Everything the three separate calls would refuse is refused before anything is enqueued.
+int urt_resample_below(urt_context* ctx, urt_handle dst, urt_handle count, float below, int samples, int bounces, float weight,
+                       float max_history, int* out_n) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  if (std::isnan(below)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "resample_below: below is NaN");
+  if (samples < 1 || samples > 4096) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "resample_below: samples must be 1..4096");
+  if (bounces < 0 || bounces > 64) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "resample_below: bounces must be 0..64");
+  if (int rc = check_blend_numbers(ctx, "resample_below", weight, max_history)) return rc;
+  Texture* t[2];
+  if (int rc = resolve_blend_targets(ctx, "resample_below", dst, count, t)) return rc;
+  if (int rc = check_select_size(ctx, "resample_below", t[1])) return rc;
+  const Texture* res = find_texture(ctx, ctx->t_result);
+  if (!res) return fail(ctx, URT_ERR_UNBOUND, "resample_below: no texture bound to \"Result\"");
+  if (!ctx->c2w_set || !ctx->invp_set)
+    return fail(ctx, URT_ERR_UNBOUND, "resample_below: _CameraToWorld / _CameraInverseProjection not set");
+  if (res->w != t[0]->w || res->h != t[0]->h)
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "resample_below: dst and count must have the size of the texture bound as Result");
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  const int width = t[1]->w, height = t[1]->h;
+  const size_t n_texels = (size_t)width * (size_t)height;
+  if (int rc = select_scratch(ctx, "resample_below: scratch allocation", n_texels)) return rc;
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  URT_HIP(ctx, launch_select_count(t[1]->dev, n_texels, below, ctx->rs_counts, touch(ctx)));
+  int n = 0;
+  if (int rc = select_total(ctx, n_texels, &n)) return rc;
+  if (out_n) *out_n = n;
+  if (n == 0) return URT_OK;
+  if (int rc = grow_scratch(ctx, &ctx->rs_pixels, &ctx->rs_pixels_cap, (size_t)n, (size_t)n * sizeof(urt_PathPixel), "resample_below: scratch allocation")) return rc;
+  if (int rc = grow_scratch(ctx, (void**)&ctx->rs_samples, &ctx->rs_samples_cap, (size_t)n, (size_t)n * sizeof(float4), "resample_below: scratch allocation")) return rc;
+  URT_HIP(ctx, launch_select_write(t[1]->dev, width, n_texels, below, ctx->rs_counts, (int2*)ctx->rs_pixels, n, touch(ctx)));
+  DevScene S; RadianceCamera C; RadianceBatch B;
+  if (int rc = radiance_prepare(ctx, ctx->rs_pixels, n, samples, bounces, ctx->rs_samples, URT_RADIANCE_PIXELS, false, &S, &C, &B)) return rc;
+  B.in = ctx->rs_pixels; B.out = ctx->rs_samples;
+  URT_HIP(ctx, launch_radiance(S, ctx->scene.tlas_stack, ctx->scene.blas_stack + ctx->opt.stack_pad, C, B, touch(ctx)));
+  Texture* d = find_texture(ctx, dst);
+  Texture* c = find_texture(ctx, count);
+  if (!d || !c) return fail(ctx, URT_ERR_INVALID_HANDLE, "resample_below: a texture was released during the call");
+  d->other_writes = true;
+  c->other_writes = true;
+  URT_HIP(ctx, launch_blend_samples((const int2*)ctx->rs_pixels, ctx->rs_samples, n, weight, d->dev, c->dev, width, height, max_history, touch(ctx)));
+  return URT_OK;
+  URT_GUARD_END(ctx)
 }
 
 }  // extern "C"

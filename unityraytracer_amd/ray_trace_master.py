@@ -289,6 +289,21 @@ class RayTraceMaster:
         self.RayTraceShader.SetTexture(0, "Result", self._target)
         return self.ctx.radiance_query_pixels(xy, self.numRays, self.numBounces)
 
+    # After MoveCamera / MoveObjects with temporal accumulation: fresh samples for the pixels the reprojection left with a count below
+    # `below` (1.0: no history at all), selected, traced and blended into _converged and its count texture on the GPU (include/urt.h
+    # urt_resample_below) — each gets what a frame of numRays x numBounces would write to it, under a fresh _Seed, as one frame's worth
+    # (weight 1).  The host decides when to call it; returns the number of pixels resampled.
+    def ResampleDisocclusions(self, below: float = 1.0) -> int:
+        from ._lib import UrtError
+        if self._temporal is None:
+            raise UrtError(1, "ResampleDisocclusions: temporal accumulation is off (EnableTemporalAccumulation)")
+        if self._converged is None or not self._converged.handle or self._tcount is None or self._currentSample == 0:
+            raise UrtError(2, "ResampleDisocclusions: no accumulated image yet (render a frame first)")
+        self._bind_for_queries()
+        self.InitRenderTexture()
+        self.RayTraceShader.SetTexture(0, "Result", self._target)
+        return self.ctx.resample_below(self._converged, self._tcount, below, self.numRays, self.numBounces, 1.0, self._temporal["max_history"])
+
     # Per-pixel first-hit feature buffers of the camera this master renders with (include/urt.h urt_render_aov): hit, normal, albedo and
     # id textures of the screen size, re-created with it as InitRenderTexture re-creates the frame's (RM:834-840).  A host calls it when
     # the camera moves — when the accumulation resets too.  Returns the four RenderTextures (filled once the deferred work has run:

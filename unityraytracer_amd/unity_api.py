@@ -474,6 +474,75 @@ class Context:
         _max_history_arg(max_history, "blit_add_history")
         self.check(self.lib.urt_blit_add_history(self._h, src.handle, dst.handle, count.handle, float(max_history)))
 
+    def select_pixels(self, count, below: float = 1.0):
+        """The pixels of the count texture whose count is not >= below (include/urt.h urt_select_pixels), found on the GPU: an (n, 2)
+        int32 torch tensor of (x, y) on this context's device, in ascending texel order y * width + x — the list radiance_query_pixels
+        and blend_samples take.  NaN and negative counts are selected.  Counts first, then allocates n entries and fills them."""
+        _check_texture(self, "select_pixels", "count", count, count)
+        below = _number_arg(below, "below", "select_pixels")
+        import torch
+        dev = torch.device("cuda", self.device)
+        n = C.c_int(-1)
+        self.check(self.lib.urt_select_pixels(self._h, count.handle, below, None, 0, C.byref(n)))
+        xy = torch.empty((n.value, 2), dtype=torch.int32, device=dev)
+        if n.value > 0:
+            torch.cuda.current_stream(dev).synchronize()           # the allocator may hand out memory torch's stream still works on
+            m = C.c_int(-1)
+            self.check(self.lib.urt_select_pixels(self._h, count.handle, below, C.c_void_p(xy.data_ptr()), n.value, C.byref(m)))
+            if m.value != n.value:
+                raise RuntimeError(f"select_pixels: the count texture changed between the two passes ({n.value} then {m.value} pixels)")
+        return xy
+
+    def blend_samples(self, xy, samples, dst, count, weight: float = 1.0, max_history: float = 0.0):
+        """Blends samples[i] into pixel xy[i] of dst with the per-pixel sample count of `count` (include/urt.h urt_blend_samples): the
+        arithmetic of blit_add_history with `weight` frame-equivalents per sample; count.x becomes the samples used plus weight.  xy:
+        (n, 2) int32 and samples: (n, 4) float32 torch tensors on this context's device; the pixels must be distinct; one outside dst is
+        skipped.  The call is ordered after torch's current stream and has completed when it returns."""
+        import torch
+        weight = _weight_arg(weight, "blend_samples")
+        max_history = _max_history_arg(max_history, "blend_samples")
+        for name, t in (("dst", dst), ("count", count)):
+            _check_texture(self, "blend_samples", name, t, dst)
+        if dst is count:
+            raise ValueError("blend_samples: dst and count must be two different textures")
+        lists = (("xy", xy, torch.int32, 2), ("samples", samples, torch.float32, 4))
+        for name, a, dtype, cols in lists:                         # type, dtype and shape of both lists, then where they live
+            if not _is_torch(a):
+                raise TypeError(f"blend_samples: {name} must be a torch tensor, not {type(a).__name__}")
+            if a.dtype != dtype:
+                raise TypeError(f"blend_samples: {name} must be {str(dtype).replace('torch.', '')}, not {a.dtype}")
+            if a.dim() != 2 or a.shape[1] != cols:
+                raise ValueError(f"blend_samples: {name} must have shape (n, {cols}), not {tuple(a.shape)}")
+        for name, a, dtype, cols in lists:
+            self._torch_arg(a, name, "blend_samples", dtype, cols)
+        n = xy.shape[0]
+        if samples.shape[0] != n:
+            raise ValueError(f"blend_samples: xy {tuple(xy.shape)} and samples {tuple(samples.shape)} differ in length")
+        if n > 0x7fffffff:
+            raise ValueError("blend_samples: more than 2^31 - 1 samples")
+        px, sm = xy.contiguous(), samples.contiguous()
+        torch.cuda.current_stream(xy.device).synchronize()         # the lists are written on torch's stream, the blend runs on the library's
+        self.check(self.lib.urt_blend_samples(self._h, C.c_void_p(px.data_ptr() if n else 0), C.c_void_p(sm.data_ptr() if n else 0), n, weight,
+                                              dst.handle, count.handle, max_history))
+        torch.cuda.synchronize(xy.device)                          # returns at once: wait before torch may free the lists
+
+    def resample_below(self, dst, count, below: float, samples: int, bounces: int, weight: float = 1.0, max_history: float = 0.0) -> int:
+        """select_pixels(count, below), radiance_query_pixels over the list with `samples` and `bounces`, blend_samples into dst and count
+        — in one call, lists and samples in scratch of the context (include/urt.h urt_resample_below).  dst and count have the size of
+        the texture bound as Result; the camera, _PixelOffset and _Seed are those bound at call time.  Returns the number of pixels
+        resampled; the trace and the blend are enqueued, a later GetPixels sees them."""
+        samples, bounces = _radiance_counts(samples, bounces)
+        for name, t in (("dst", dst), ("count", count)):
+            _check_texture(self, "resample_below", name, t, dst)
+        if dst is count:
+            raise ValueError("resample_below: dst and count must be two different textures")
+        below = _number_arg(below, "below", "resample_below")
+        weight = _weight_arg(weight, "resample_below")
+        max_history = _max_history_arg(max_history, "resample_below")
+        n = C.c_int(-1)
+        self.check(self.lib.urt_resample_below(self._h, dst.handle, count.handle, below, samples, bounces, weight, max_history, C.byref(n)))
+        return n.value
+
 
 def _check_texture(ctx, what: str, name: str, t, like, optional: bool = False):
     if not isinstance(t, RenderTexture):
@@ -498,6 +567,14 @@ def _max_history_arg(v, what: str, name: str = "max_history") -> float:
     v = _number_arg(v, name, what)
     if not (v == 0.0 or v >= 1.0):
         raise ValueError(f"{what}: {name} must be 0 (unlimited) or >= 1, not {v}")
+    return v
+
+
+def _weight_arg(v, what: str) -> float:
+    """weight of urt_blend_samples: finite and > 0."""
+    v = _number_arg(v, "weight", what)
+    if not (np.isfinite(v) and v > 0.0):
+        raise ValueError(f"{what}: weight must be finite and > 0, not {v}")
     return v
 
 
@@ -531,6 +608,9 @@ RAYHIT_DT = np.dtype([("distance", np.float32), ("position", np.float32, 3), ("n
 PATHRAY_DT = np.dtype([("origin", np.float32, 3), ("seed", np.float32), ("direction", np.float32, 3), ("reserved0", np.int32),
                        ("px", np.float32), ("py", np.float32), ("reserved1", np.int32, 2)])
 PATHPIXEL_DT = np.dtype([("x", np.int32), ("y", np.int32)])
+
+# texels one workgroup of the selection kernels handles (csrc/resample.h kSelectChunk): the sizes at which urt_select_pixels changes path
+SELECT_CHUNK = 2048
 
 
 def _radiance_counts(samples, bounces):
