@@ -713,6 +713,10 @@ URT_API int urt_debug_build_walk_table(const urt_BVHNode* heap, int n_nodes, int
  * triangle records and boxes are recomputed on the GPU (csrc/refit.hip; option "refit" = 0 turns this off).  Reports MeshObjects
  * refitted and in-place preparations since the context was created. */
 URT_API int urt_debug_refit_stats(urt_context* ctx, uint64_t* out_refitted_meshes, uint64_t* out_incremental_preparations);
+/* What the library holds right now, PROCESS-WIDE (every context and group of the process; needs none): out4 = device bytes, pinned host
+ * bytes, events, streams.  Counts only the library's own holders (csrc/owned.h) — not external textures, the caller's streams or what
+ * the HIP runtime keeps for itself.  A context or group that is destroyed gives back everything it took. */
+URT_API int urt_debug_live_resources(uint64_t out4[4]);
 /* kernel_mode 5 with "count_stats" = 1: what the shared traversal service did since the last urt_reset_counters —
  * out6 = visits of the service, its trips, active lanes summed over the trips, claim rounds, rays claimed, rays suspended. */
 URT_API int urt_debug_serve_stats(urt_context* ctx, unsigned long long* out6);

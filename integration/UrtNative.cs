@@ -205,6 +205,7 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_host_dump_bvh(string path, IntPtr nodes, int nNodes, int depth, float[] rayStart3, float[] rayEnd3, out int lines);
     [DllImport(Lib)] internal static extern int urt_host_dump_normals(string path, IntPtr meshObjects, int nMeshes, float[] vertices, int nVertices, int[] indices, int nIndices, float[] normals, int nNormals, out int lines);
     [DllImport(Lib)] internal static extern int urt_debug_refit_stats(IntPtr ctx, out ulong refittedMeshes, out ulong incrementalPreparations);
+    [DllImport(Lib)] internal static extern int urt_debug_live_resources([Out] ulong[] out4);   // process-wide: device bytes, pinned bytes, events, streams
     [DllImport(Lib)] internal static extern int urt_host_mesh_motion(IntPtr prevMeshObjects, IntPtr curMeshObjects, int n, IntPtr outMotion);   // 48 B per entry
     [DllImport(Lib)] internal static extern int urt_host_sphere_motion(IntPtr prevSpheres, IntPtr curSpheres, int n, IntPtr outMotion);
     [DllImport(Lib)] internal static extern int urt_host_build_object_bvh_pairing(IntPtr leaves, int nObjects, IntPtr outNodes, int capacity);   // RM:459-722's pairing builder, restated

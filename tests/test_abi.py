@@ -99,6 +99,21 @@ def test_product_never_touches_the_oracle():
         assert not bad.search(open(os.path.join(ROOT, "include", f)).read()), f
 
 
+def test_only_the_holders_allocate_and_create():
+    """csrc/owned.h is the one place that takes a GPU resource and gives it back: every other file of csrc/ reaches device memory, pinned
+    memory, events and streams through its holders, so that a destroyed context or group leaks nothing (tests/test_gpu_resources.py)
+    and urt_debug_live_resources counts everything.  Comments and string literals may name the calls."""
+    calls = ("hipMalloc(", "hipHostMalloc(", "hipFree(", "hipHostFree(", "hipEventCreate", "hipEventDestroy(", "hipStreamCreate", "hipStreamDestroy(")
+    csrc = os.path.join(ROOT, "unityraytracer_amd", "csrc")
+    strip = re.compile(r'//[^\n]*|/\*.*?\*/|"(?:\\.|[^"\\\n])*"', re.S)
+    code = {f: strip.sub(" ", open(os.path.join(csrc, f)).read()) for f in sorted(os.listdir(csrc))}
+    assert len(code) > 40 and "owned.h" in code
+    for c in calls:
+        assert c in code["owned.h"], f"the scan does not find {c} in owned.h"
+    found = [(f, c) for f, text in code.items() if f != "owned.h" for c in calls if c in text]
+    assert not found, found
+
+
 def test_header_is_plain_c99_and_the_c_example_compiles(tmp_path):
     """include/urt.h is the drop-in boundary: it must parse as C (not only C++), warning-free, and examples/frame_loop.c — the
     reference's frame protocol written in C99 against it — must compile (linking/running it needs the GPU: tests/test_gpu_c_host.py)."""

@@ -10,6 +10,7 @@
 #include "context_impl.h"
 
 #include <climits>
+#include <memory>
 
 #include "present.h"
 #include "reproject.h"
@@ -39,7 +40,7 @@ int fail(urt_context* ctx, int code, const std::string& msg) {
 // After the stream has been waited for: did a wave of the work just completed leave through a cap?
 int check_watchdog(urt_context* ctx) {
   if (!ctx->h_trip_flag) return URT_OK;
-  unsigned int n = __atomic_exchange_n(ctx->h_trip_flag, 0u, __ATOMIC_ACQ_REL);
+  unsigned int n = __atomic_exchange_n(ctx->h_trip_flag.get(), 0u, __ATOMIC_ACQ_REL);
   if (n == 0) return URT_OK;
   return fail(ctx, URT_ERR_WATCHDOG, std::to_string(n) + " wave(s) of a trace launch hit the kernel's iteration cap and left pixels unwritten "
                                      "(urt_counters.watchdog_trips): the images written since the last successful synchronisation are incomplete");
@@ -75,81 +76,37 @@ int urt_context_create(int device, urt_context** out_ctx) {
     return fail(nullptr, URT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
   if (device < 0 || device >= n) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "device ordinal out of range");
   URT_HIP(nullptr, hipSetDevice(device));
-  urt_context* ctx = new urt_context();
+  std::unique_ptr<urt_context> ctx(new urt_context());
   ctx->device = device;
-  e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking);
-  if (e != hipSuccess) { delete ctx; return fail(nullptr, URT_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }
-  ctx->stream = ctx->own_stream;
-  e = hipMalloc((void**)&ctx->d_counters, sizeof(DevCounters) * kCounterShards);
-  if (e == hipSuccess) e = hipMemset(ctx->d_counters, 0, sizeof(DevCounters) * kCounterShards);
-  if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_next, kWorkShards * 128 + 65536 * 16 * sizeof(unsigned long long));   // work-counter shards; the rest: diagnostic stamps (URT_STAMPS builds)
-  if (e == hipSuccess) e = hipMemset(ctx->d_next, 0, kWorkShards * 128 + 65536 * 16 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_next2, kWorkShards * 128 + 65536 * 16 * sizeof(unsigned long long));    // the launch on the second trace stream (same layout)
-  if (e == hipSuccess) e = hipMemset(ctx->d_next2, 0, kWorkShards * 128 + 65536 * 16 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipHostMalloc((void**)&ctx->h_trip_flag, 64, hipHostMallocMapped | hipHostMallocCoherent);   // the watchdog word the kernels raise (system-scope atomic)
-  if (e == hipSuccess) { *ctx->h_trip_flag = 0; e = hipHostGetDevicePointer((void**)&ctx->d_trip_flag, ctx->h_trip_flag, 0); }
-  if (e == hipSuccess) { int n = 0; if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n > 0) ctx->n_cus = n; }
-  if (e != hipSuccess) {
-    if (ctx->d_counters) (void)hipFree(ctx->d_counters);
-    if (ctx->d_next) (void)hipFree(ctx->d_next);
-    if (ctx->d_next2) (void)hipFree(ctx->d_next2);
-    if (ctx->h_trip_flag) (void)hipHostFree(ctx->h_trip_flag);
-    (void)hipStreamDestroy(ctx->own_stream); delete ctx;
-    return fail(nullptr, URT_ERR_HIP, std::string("counter allocation: ") + hipGetErrorString(e));
+  e = ctx->own_stream.create(hipStreamNonBlocking);
+  if (e != hipSuccess) return fail(nullptr, URT_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+  ctx->stream = ctx->own_stream.get();
+  e = ctx->d_counters.alloc(kCounterShards);
+  if (e == hipSuccess) e = hipMemset(ctx->d_counters.get(), 0, sizeof(DevCounters) * kCounterShards);
+  for (auto* next : {&ctx->d_next, &ctx->d_next2}) {       // d_next2: the launch on the second trace stream (same layout)
+    if (e == hipSuccess) e = next->alloc(urt_context::kWorkCounterBytes / sizeof(unsigned int));
+    if (e == hipSuccess) e = hipMemset(next->get(), 0, urt_context::kWorkCounterBytes);
   }
-  *out_ctx = ctx;
+  if (e == hipSuccess) e = ctx->h_trip_flag.alloc(1, 64, hipHostMallocMapped | hipHostMallocCoherent);   // the watchdog word the kernels raise (system-scope atomic)
+  if (e == hipSuccess) { *ctx->h_trip_flag.get() = 0; e = hipHostGetDevicePointer((void**)&ctx->d_trip_flag, ctx->h_trip_flag.get(), 0); }
+  if (e == hipSuccess) { int n = 0; if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n > 0) ctx->n_cus = n; }
+  if (e != hipSuccess) return fail(nullptr, URT_ERR_HIP, std::string("counter allocation: ") + hipGetErrorString(e));
+  *out_ctx = ctx.release();
   return URT_OK;
   URT_GUARD_END(nullptr)
 }
 
+// What destructors cannot order is done by hand: the deferred work is submitted and waited for on every stream that carries some
+// (main, copy, trace) before any holder gives its resource back.
 int urt_context_destroy(urt_context* ctx) {
   if (!ctx) return URT_OK;
   (void)hipSetDevice(ctx->device);
   (void)flush_pending(ctx);
   (void)hipStreamSynchronize(touch(ctx));
   resolve_timing(ctx);
+  for (auto& r : ctx->rslot) if (r.done) (void)hipEventSynchronize(r.done.get());
+  for (auto& q : ctx->trace_q) if (q) (void)hipStreamSynchronize(q.get());
   free_scene(ctx);
-  for (auto& kv : ctx->textures) if (!kv.second.external && kv.second.own) (void)hipFree(kv.second.own);
-  if (ctx->slab) (void)hipFree(ctx->slab);
-  for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
-  if (ctx->ev_switch) (void)hipEventDestroy(ctx->ev_switch);
-  for (int a = 0; a < 2; a++) for (int r = 0; r < 4; r++) if (ctx->q.s[a][r]) (void)hipFree(ctx->q.s[a][r]);
-  if (ctx->q.counts) (void)hipFree(ctx->q.counts);
-  if (ctx->zero_sky) (void)hipFree(ctx->zero_sky);
-  if (ctx->dn_scratch) (void)hipFree(ctx->dn_scratch);
-  for (float4* t : ctx->mo_table) if (t) (void)hipFree(t);
-  if (ctx->d_counters) (void)hipFree(ctx->d_counters);
-  if (ctx->d_next) (void)hipFree(ctx->d_next);
-  if (ctx->d_next2) (void)hipFree(ctx->d_next2);
-  if (ctx->d_mail) (void)hipFree(ctx->d_mail);
-  if (ctx->d_tables) (void)hipFree(ctx->d_tables);
-  if (ctx->h_tables) (void)hipHostFree(ctx->h_tables);
-  if (ctx->h_trip_flag) (void)hipHostFree(ctx->h_trip_flag);
-  for (hipEvent_t e : ctx->table_ev) if (e) (void)hipEventDestroy(e);
-  for (auto& r : ctx->rslot) {
-    if (r.done) { (void)hipEventSynchronize(r.done); (void)hipEventDestroy(r.done); }
-    if (r.snap) (void)hipEventDestroy(r.snap);
-    if (r.dev) (void)hipFree(r.dev);
-    if (r.host) (void)hipHostFree(r.host);
-  }
-  if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-  if (ctx->srgb_first) (void)hipFree(ctx->srgb_first);
-  for (int k = 0; k < 2; k++) {
-    if (ctx->trace_q[k]) { (void)hipStreamSynchronize(ctx->trace_q[k]); (void)hipStreamDestroy(ctx->trace_q[k]); }
-    if (ctx->trace_done[k]) (void)hipEventDestroy(ctx->trace_done[k]);
-    if (ctx->pre_ev[k]) (void)hipEventDestroy(ctx->pre_ev[k]);
-  }
-  if (ctx->dep_ev) (void)hipEventDestroy(ctx->dep_ev);
-  if (ctx->q_rays) (void)hipFree(ctx->q_rays);
-  if (ctx->q_out) (void)hipFree(ctx->q_out);
-  if (ctx->rq_in) (void)hipFree(ctx->rq_in);
-  if (ctx->rq_out) (void)hipFree(ctx->rq_out);
-  if (ctx->rq_next) (void)hipFree(ctx->rq_next);
-  if (ctx->rs_counts) (void)hipFree(ctx->rs_counts);
-  if (ctx->rs_total) (void)hipHostFree(ctx->rs_total);
-  if (ctx->rs_pixels) (void)hipFree(ctx->rs_pixels);
-  if (ctx->rs_samples) (void)hipFree(ctx->rs_samples);
-  if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
   return URT_OK;
 }
@@ -160,13 +117,13 @@ int urt_context_set_stream(urt_context* ctx, void* hip_stream) {
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   URT_HIP(ctx, hipSetDevice(ctx->device));
   { int rc = flush_pending(ctx); if (rc) return rc; }
-  hipStream_t to = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
+  hipStream_t to = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream.get();
   if (to == ctx->stream) return URT_OK;
   // no host synchronisation: everything issued so far on the old stream is ordered before whatever is issued on the new
   // one by an event (a caller that ping-pongs between a render and a communication stream must not stall on either)
-  if (!ctx->ev_switch) URT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_switch, hipEventDisableTiming));
-  URT_HIP(ctx, hipEventRecord(ctx->ev_switch, touch(ctx)));
-  URT_HIP(ctx, hipStreamWaitEvent(to, ctx->ev_switch, 0));
+  if (!ctx->ev_switch) URT_HIP(ctx, ctx->ev_switch.create(hipEventDisableTiming));
+  URT_HIP(ctx, hipEventRecord(ctx->ev_switch.get(), touch(ctx)));
+  URT_HIP(ctx, hipStreamWaitEvent(to, ctx->ev_switch.get(), 0));
   ctx->stream = to;
   return URT_OK;
 }
@@ -248,13 +205,14 @@ static int texture_create_impl(urt_context* ctx, int width, int height, void* ex
   size_t bytes = (size_t)width * (size_t)height * sizeof(float4);
   if (ext) { t.dev = (float4*)ext; t.external = true; t.other_writes = true; /* caller memory: contents unknown */ }
   else {
-    URT_HIP(ctx, hipMalloc((void**)&t.dev, bytes));
+    URT_HIP(ctx, t.storage.alloc((size_t)width * (size_t)height));
+    t.dev = t.storage.get();
     hipError_t e = hipMemsetAsync(t.dev, 0, bytes, touch(ctx));
-    if (e != hipSuccess) { (void)hipFree(t.dev); return fail(ctx, URT_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(ctx, URT_ERR_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
   }
   t.own = t.dev;
   urt_handle h = ctx->next_id++;
-  ctx->textures.emplace(h, t);
+  ctx->textures.emplace(h, std::move(t));
   *out_texture = h;
   return URT_OK;
   URT_GUARD_END(ctx)
@@ -311,37 +269,33 @@ int urt_texture_read_begin_format(urt_context* ctx, urt_handle texture, int form
   URT_HIP(ctx, hipSetDevice(ctx->device));
   { int rc = flush_pending(ctx); if (rc) return rc; }
   t = find_texture(ctx, texture);
-  if (!ctx->copy_stream) URT_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+  if (!ctx->copy_stream) URT_HIP(ctx, ctx->copy_stream.create(hipStreamNonBlocking));
   urt_context::ReadSlot& r = ctx->rslot[ctx->read_next % urt_context::kReadSlots];
   if (r.busy) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "urt_texture_read_begin: three readbacks are in flight — end the oldest first");
   const size_t px = (size_t)t->w * (size_t)t->h;
-  if (r.pixels < px) {
-    if (r.done) URT_HIP(ctx, hipEventSynchronize(r.done));
-    if (r.dev) (void)hipFree(r.dev);
-    if (r.host) (void)hipHostFree(r.host);
-    r.dev = nullptr; r.host = nullptr; r.pixels = 0;
-    URT_HIP(ctx, hipMalloc((void**)&r.dev, px * sizeof(float4)));
-    URT_HIP(ctx, hipHostMalloc((void**)&r.host, px * sizeof(float4), hipHostMallocDefault));
-    r.pixels = px;
+  if (r.dev.cap() < px || r.host.cap() < px) {               // the pair grows together, after the slot's last copy
+    if (r.done) URT_HIP(ctx, hipEventSynchronize(r.done.get()));
+    URT_HIP(ctx, r.dev.alloc(px));
+    URT_HIP(ctx, r.host.alloc(px));
   }
-  if (!r.snap) { URT_HIP(ctx, hipEventCreateWithFlags(&r.snap, hipEventDisableTiming)); URT_HIP(ctx, hipEventCreateWithFlags(&r.done, hipEventDisableTiming)); }
+  if (!r.snap) { URT_HIP(ctx, r.snap.create(hipEventDisableTiming)); URT_HIP(ctx, r.done.create(hipEventDisableTiming)); }
   if (format == urtd::kFormatRGBA32F) {
-    URT_HIP(ctx, hipMemcpyAsync(r.dev, t->dev, px * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+    URT_HIP(ctx, hipMemcpyAsync(r.dev.get(), t->dev, px * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
   } else {
     if (format == urtd::kFormatRGBA8sRGB && !ctx->srgb_first) {
       float first[urtd::kSrgbCodes];
       (void)urt_host_srgb8_first_floats(first);
-      URT_HIP(ctx, hipMalloc((void**)&ctx->srgb_first, sizeof(first)));
-      URT_HIP(ctx, hipMemcpy(ctx->srgb_first, first, sizeof(first), hipMemcpyHostToDevice));
+      URT_HIP(ctx, ctx->srgb_first.alloc(urtd::kSrgbCodes));
+      URT_HIP(ctx, hipMemcpy(ctx->srgb_first.get(), first, sizeof(first), hipMemcpyHostToDevice));
     }
-    URT_HIP(ctx, urtd::launch_encode(t->dev, r.dev, px, format, ctx->srgb_first, ctx->stream));
+    URT_HIP(ctx, urtd::launch_encode(t->dev, r.dev.get(), px, format, ctx->srgb_first.get(), ctx->stream));
   }
   r.format = format;
   r.bytes = px * bpp;
-  URT_HIP(ctx, hipEventRecord(r.snap, ctx->stream));
-  URT_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, r.snap, 0));
-  URT_HIP(ctx, hipMemcpyAsync(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost, ctx->copy_stream));
-  URT_HIP(ctx, hipEventRecord(r.done, ctx->copy_stream));
+  URT_HIP(ctx, hipEventRecord(r.snap.get(), ctx->stream));
+  URT_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream.get(), r.snap.get(), 0));
+  URT_HIP(ctx, hipMemcpyAsync(r.host.get(), r.dev.get(), r.bytes, hipMemcpyDeviceToHost, ctx->copy_stream.get()));
+  URT_HIP(ctx, hipEventRecord(r.done.get(), ctx->copy_stream.get()));
   r.busy = true;
   r.ticket = ++ctx->read_next;                               // tickets start at 1; slot = (ticket - 1) % kReadSlots
   *out_ticket = r.ticket;
@@ -366,9 +320,9 @@ int urt_texture_read_end_format(urt_context* ctx, uint64_t ticket, const void** 
   urt_context::ReadSlot& r = ctx->rslot[(ticket - 1) % urt_context::kReadSlots];
   if (!r.busy || r.ticket != ticket) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "urt_texture_read_end: this ticket is not in flight");
   URT_HIP(ctx, hipSetDevice(ctx->device));
-  URT_HIP(ctx, hipEventSynchronize(r.done));
+  URT_HIP(ctx, hipEventSynchronize(r.done.get()));
   r.busy = false;
-  *out_pixels = r.host;                                      // valid until the third urt_texture_read_begin after this one
+  *out_pixels = r.host.get();                                      // valid until the third urt_texture_read_begin after this one
   if (out_bytes) *out_bytes = r.bytes;
   return check_watchdog(ctx);
 }
@@ -398,7 +352,6 @@ int urt_texture_release(urt_context* ctx, urt_handle texture) {
   URT_HIP(ctx, hipSetDevice(ctx->device));
   { int rc = flush_pending(ctx); if (rc) return rc; }
   URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
-  if (!it->second.external && it->second.own) (void)hipFree(it->second.own);
   ctx->slab_oom_stride = 0;                                // device memory came back: the next batch may try the Result slots again
   if (ctx->slab_tex == texture) ctx->slab_tex = 0;
   if (ctx->t_sky == texture) ctx->t_sky = 0;
@@ -706,7 +659,7 @@ int urt_get_counters(urt_context* ctx, urt_counters* out) {
   URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
   resolve_timing(ctx);
   std::vector<DevCounters> shards(kCounterShards);
-  URT_HIP(ctx, hipMemcpy(shards.data(), ctx->d_counters, sizeof(DevCounters) * kCounterShards, hipMemcpyDeviceToHost));
+  URT_HIP(ctx, hipMemcpy(shards.data(), ctx->d_counters.get(), sizeof(DevCounters) * kCounterShards, hipMemcpyDeviceToHost));
   std::memset(out, 0, sizeof *out);
   for (const DevCounters& dc : shards) {
     out->rays += dc.rays; out->tlas_nodes += dc.tlas_nodes; out->blas_nodes += dc.blas_nodes; out->tri_tests += dc.tri_tests;
@@ -727,8 +680,8 @@ int urt_reset_counters(urt_context* ctx) {
   { int rc = flush_pending(ctx); if (rc) return rc; }
   URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
   resolve_timing(ctx);
-  URT_HIP(ctx, hipMemset(ctx->d_counters, 0, sizeof(DevCounters) * kCounterShards));
-  if (ctx->h_trip_flag) __atomic_store_n(ctx->h_trip_flag, 0u, __ATOMIC_RELEASE);
+  URT_HIP(ctx, hipMemset(ctx->d_counters.get(), 0, sizeof(DevCounters) * kCounterShards));
+  if (ctx->h_trip_flag) __atomic_store_n(ctx->h_trip_flag.get(), 0u, __ATOMIC_RELEASE);
   ctx->dispatches = 0;
   ctx->launches = 0;
   ctx->pixels_dispatched = 0;
@@ -740,8 +693,8 @@ int urt_reset_counters(urt_context* ctx) {
 /* diagnostic builds only: per-wave (start, pool-exhausted, end, iters<<32|fetches) of the last persistent launch */
 __attribute__((visibility("default"))) int urt_debug_read_stamps(urt_context* ctx, unsigned long long* out, int n_waves) {
   (void)hipStreamSynchronize(touch(ctx));
-  hipError_t e = hipMemcpy(out, (char*)ctx->d_next + kWorkShards * 128, (size_t)n_waves * sizeof(unsigned long long), hipMemcpyDeviceToHost);   // n_waves = number of u64 words
-  (void)hipMemset((char*)ctx->d_next + kWorkShards * 128, 0, 65536 * 16 * sizeof(unsigned long long));
+  hipError_t e = hipMemcpy(out, (char*)ctx->d_next.get() + urt_context::kStampOffset, (size_t)n_waves * sizeof(unsigned long long), hipMemcpyDeviceToHost);   // n_waves = number of u64 words
+  (void)hipMemset((char*)ctx->d_next.get() + urt_context::kStampOffset, 0, urt_context::kStampBytes);
   return (int)e;
 }
 #endif
@@ -755,7 +708,7 @@ int urt_debug_serve_stats(urt_context* ctx, unsigned long long* out6) {
   { int rc = flush_pending(ctx); if (rc) return rc; }
   URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
   std::vector<DevCounters> shards(kCounterShards);
-  URT_HIP(ctx, hipMemcpy(shards.data(), ctx->d_counters, sizeof(DevCounters) * kCounterShards, hipMemcpyDeviceToHost));
+  URT_HIP(ctx, hipMemcpy(shards.data(), ctx->d_counters.get(), sizeof(DevCounters) * kCounterShards, hipMemcpyDeviceToHost));
   for (int q = 0; q < 6; q++) out6[q] = 0;
   for (const DevCounters& dc : shards) for (int q = 0; q < 6; q++) out6[q] += dc.serve[q];
   return URT_OK;
@@ -812,6 +765,12 @@ int urt_debug_refit_stats(urt_context* ctx, uint64_t* out_refitted_meshes, uint6
   return URT_OK;
 }
 
+int urt_debug_live_resources(uint64_t out4[4]) {
+  if (!out4) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "out4 is NULL");
+  out4[0] = g_live.device_bytes; out4[1] = g_live.pinned_bytes; out4[2] = g_live.events; out4[3] = g_live.streams;
+  return URT_OK;
+}
+
 int urt_debug_launch_info(urt_context* ctx, urt_launch_info* out) {
   if (!ctx || !out) return URT_ERR_INVALID_ARGUMENT;
   int rc = flush_pending(ctx); if (rc) return rc;          // "the last launch" includes the frames still deferred
@@ -826,7 +785,7 @@ int urt_debug_scene_info(urt_context* ctx, int* out_n_nodes, int* out_n_tris, in
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   URT_GUARD_BEGIN
   URT_HIP(ctx, hipSetDevice(ctx->device));
-  if (ctx->scene_dirty) { int rc = flush_pending(ctx); if (rc) return rc; rc = prepare_scene(ctx); if (rc) return rc; }
+  if (int rc = current_scene(ctx)) return rc;
   if (out_n_nodes) *out_n_nodes = ctx->scene.n_blas_nodes;
   if (out_n_tris) *out_n_tris = ctx->scene.n_scene_tris;
   if (out_max_depth) *out_max_depth = ctx->scene.scene_max_depth;
@@ -839,7 +798,7 @@ int urt_debug_read_scene_blas(urt_context* ctx, float* nodes, int32_t* tri_index
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   URT_GUARD_BEGIN
   URT_HIP(ctx, hipSetDevice(ctx->device));
-  if (ctx->scene_dirty) { int rc = flush_pending(ctx); if (rc) return rc; rc = prepare_scene(ctx); if (rc) return rc; }
+  if (int rc = current_scene(ctx)) return rc;
   URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
   const DevScene& S = ctx->scene.ds;
   if (nodes && ctx->scene.n_blas_nodes > 0) URT_HIP(ctx, hipMemcpy(nodes, S.blas_nodes, (size_t)ctx->scene.n_blas_nodes * kBlasNodeFloats * sizeof(float), hipMemcpyDeviceToHost));
@@ -857,7 +816,7 @@ int urt_debug_read_scene_qnodes(urt_context* ctx, float* out, int* out_n_nodes, 
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   URT_GUARD_BEGIN
   URT_HIP(ctx, hipSetDevice(ctx->device));
-  if (ctx->scene_dirty) { int rc = flush_pending(ctx); if (rc) return rc; rc = prepare_scene(ctx); if (rc) return rc; }
+  if (int rc = current_scene(ctx)) return rc;
   URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
   // qbuf exists (and is current) only while the option is on: it is derived after every build and refit (rederive_nodes)
   const bool have = ctx->opt.qnodes != 0 && ctx->scene.qbuf && ctx->scene.n_blas_nodes > 0;

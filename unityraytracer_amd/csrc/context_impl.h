@@ -3,6 +3,7 @@
 //   scene_prep.cpp   bound buffers -> device scene (full and in-place preparation)
 //   frame_batch.cpp  deferred frames, the Result slab, trace launches (do_dispatch, flush_pending)
 //   image_ops.cpp    ray queries, radiance queries, feature buffers, denoiser, reprojection, resampling
+//   owned.h          the holders every GPU resource below lives in (DeviceBuf, PinnedBuf, Event, Stream) and `reserve`, the grow-only policy
 // Private: nothing else includes it.  What crosses the files lives in namespace urtd and stays hidden (-fvisibility=hidden).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 #include "../../include/urt_math.h"
 #include "blas_builder.h"
 #include "kernels.h"
+#include "owned.h"
 #include "urt_device.h"
 
 namespace urtd {
@@ -36,6 +38,7 @@ struct Texture {
   float4* dev = nullptr;        // where the CURRENT contents live: `own`, or a frame slot of the context's slab (a Result
                                 // texture is renamed to a fresh slot by every batched dispatch)
   float4* own = nullptr;        // the allocation made at creation (or the caller's memory when external)
+  DeviceBuf<float4> storage;    // owns `own`; empty when external
   bool external = false;
   bool ptr_exposed = false;     // urt_texture_get_info handed out the device pointer: never renamed again
   // What has written the image since its zero-filled creation.  A dispatch that covers only part of the image may be renamed
@@ -51,9 +54,9 @@ enum BindSlot { B_MESHOBJECTS, B_VERTICES, B_INDICES, B_NORMALS, B_SPHERES, B_ME
 }  // namespace urtd
 
 struct urt_context {
+  urtd::Stream own_stream;                  // first: destroyed last, after everything that was used on it
   int device = 0;
   hipStream_t stream = nullptr;
-  hipStream_t own_stream = nullptr;
   std::string err;
   std::unordered_map<urt_handle, urtd::Buffer> buffers;
   std::unordered_map<urt_handle, urtd::Texture> textures;
@@ -108,7 +111,7 @@ struct urt_context {
   // Everything that belongs to ONE prepared scene: free_scene frees scene_allocs and assigns Scene{}.
   struct Scene {
     urtd::DevScene ds{};
-    std::vector<void*> scene_allocs;
+    std::vector<urtd::DeviceBuf<char>> scene_allocs;
     struct RefitAux {                       // device-resident (scene_allocs)
       const float* vertices = nullptr; const int32_t* indices = nullptr;      // copies of _Vertices / _Indices
       int32_t* parent = nullptr; int32_t* node_mesh = nullptr; int32_t* depth = nullptr;
@@ -141,26 +144,29 @@ struct urt_context {
   uint64_t refitted_meshes = 0, incremental_preps = 0;
   urtd::BlasCache blas_cache;               // per-MeshObject BVHs of the previous scene (reused when a MeshObject is unchanged)
   int sched_groups = 0;                     // kernel_mode 3: workgroups per CU the last configuration counts on when fewer than the default fit (0 = default)
-  float4* zero_sky = nullptr;
+  urtd::DeviceBuf<float4> zero_sky;
 
   // wavefront queues
-  urtd::PathQueues q{};
-  size_t q_capacity = 0, counts_capacity = 0;
+  urtd::PathQueues q{};                     // views of q_store / q_counts
+  urtd::DeviceBuf<float4> q_store[2][4];
+  urtd::DeviceBuf<unsigned int> q_counts;
 
-  urtd::DevCounters* d_counters = nullptr;  // kCounterShards shards
-  unsigned int* d_next = nullptr;           // persistent mode: frame work counter
-  float4* d_mail = nullptr; size_t mail_slots = 0;   // kernel_mode 5: posted rays (2 float4 per thread of the resident grid)
+  urtd::DeviceBuf<urtd::DevCounters> d_counters;   // kCounterShards shards
+  // d_next / d_next2: the work-counter shards, then the diagnostic stamps (URT_STAMPS builds)
+  static constexpr size_t kStampOffset = urtd::kWorkShards * 128, kStampBytes = 65536 * 16 * sizeof(unsigned long long), kWorkCounterBytes = kStampOffset + kStampBytes;
+  urtd::DeviceBuf<unsigned int> d_next;     // persistent mode: frame work counter
+  urtd::DeviceBuf<float4> d_mail;           // kernel_mode 5: posted rays (2 float4 per thread of the resident grid)
   // frame tables of the batched launches: kTableSlots pinned host images + device copies, used round-robin; a slot is reused
   // once the copy of its previous use has left the host image (event)
   static constexpr int kTableSlots = 4;
-  urtd::FrameUniforms* h_tables = nullptr; urtd::FrameUniforms* d_tables = nullptr;
-  hipEvent_t table_ev[kTableSlots] = {nullptr, nullptr, nullptr, nullptr};
+  urtd::PinnedBuf<urtd::FrameUniforms> h_tables; urtd::DeviceBuf<urtd::FrameUniforms> d_tables;
+  urtd::Event table_ev[kTableSlots];
   unsigned int table_next = 0;
   uint64_t pixels_dispatched = 0;
   int n_cus = 256;
 
   uint64_t dispatches = 0;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> timing;   // unresolved event pairs
+  std::vector<std::pair<urtd::Event, urtd::Event>> timing;   // unresolved event pairs
   float trace_ms = 0;
 
   // ---- frame batching (kernel_mode 3) --------------------------------------------------------------------------------
@@ -194,28 +200,28 @@ struct urt_context {
     int front_mode = 0; bool count = false;
     std::vector<PostOp> ops;
   } pend;
-  float4* slab = nullptr;                   // slab_frames x slab_stride float4: Result slots of the batched frames
+  urtd::DeviceBuf<float4> slab;             // slab_frames x slab_stride float4: Result slots of the batched frames
   size_t slab_stride = 0;
   int slab_frames = 0;
   urt_handle slab_tex = 0;                  // the texture whose `dev` may point into the slab
   int slab_frames_max = 0;                  // largest batch the Result slab could be allocated for (after out-of-memory retries)
   size_t slab_oom_stride = 0;               // image size (pixels) for which not even two slots could be allocated
-  std::vector<hipEvent_t> event_pool;       // recycled timing events
-  hipEvent_t ev_switch = nullptr;           // orders the old stream before the new one in urt_context_set_stream
+  std::vector<urtd::Event> event_pool;      // recycled timing events
+  urtd::Event ev_switch;                    // orders the old stream before the new one in urt_context_set_stream
   uint64_t launches = 0;                    // trace-kernel launches (a batched launch counts once)
   urt_launch_info last_launch{};            // the last trace launch of this context (urt_debug_launch_info)
   // a wave that left a persistent kernel through one of its caps has not written its pixels: the kernels raise this host-mapped
   // word (frame_device.h report_watchdog) and the next synchronising call fails with URT_ERR_WATCHDOG
-  unsigned int* h_trip_flag = nullptr;      // pinned, device-visible
+  urtd::PinnedBuf<unsigned int> h_trip_flag;   // pinned, device-visible
   unsigned int* d_trip_flag = nullptr;      // its device address
   // Overlapped launches (option "overlap_launches", flush_pending): a host that SUBMITS every frame (urt_flush, a present into an external
   // texture) produces one-frame launches, and a one-frame launch is mostly ramp and drain.  Small launches therefore alternate between two trace streams and take their Result slots
   // round-robin from the slab, so that launch L+1 fills the wave slots launch L's draining waves give back; the blends / presents /
   // readbacks stay on the main stream, in program order, each behind its own launch.
   static constexpr int kOverlapFrames = 8;  // launches of up to this many frames take part
-  hipStream_t trace_q[2] = {nullptr, nullptr};
-  hipEvent_t trace_done[2] = {nullptr, nullptr}, pre_ev[2] = {nullptr, nullptr}, dep_ev = nullptr;
-  unsigned int* d_next2 = nullptr;          // the second launch in flight needs work counters of its own
+  urtd::Stream trace_q[2];
+  urtd::Event trace_done[2], pre_ev[2], dep_ev;
+  urtd::DeviceBuf<unsigned int> d_next2;    // the second launch in flight needs work counters of its own
   unsigned int trace_parity = 0;
   bool main_touched = true;                 // something other than the frame loop's own blends / presents / readbacks was enqueued on the main stream since the last launch
   int slab_cursor = 0, prev_base = 0, prev_n = 0;
@@ -223,37 +229,27 @@ struct urt_context {
 
   // pipelined readback (urt_texture_read_begin / _end): kReadSlots snapshots in flight, each a device copy + a pinned host image
   static constexpr int kReadSlots = 3;
-  struct ReadSlot { float4* dev = nullptr; float4* host = nullptr; size_t pixels = 0; size_t bytes = 0; int format = 0; hipEvent_t snap = nullptr, done = nullptr; bool busy = false; uint64_t ticket = 0; } rslot[kReadSlots];
-  float* srgb_first = nullptr;                // device: first float of every 8-bit sRGB code (csrc/present.hip), made at the first RGBA8 readback
-  hipStream_t copy_stream = nullptr;
+  struct ReadSlot { urtd::DeviceBuf<float4> dev; urtd::PinnedBuf<float4> host; size_t bytes = 0; int format = 0; urtd::Event snap, done; bool busy = false; uint64_t ticket = 0; } rslot[kReadSlots];
+  urtd::DeviceBuf<float> srgb_first;          // device: first float of every 8-bit sRGB code (csrc/present.hip), made at the first RGBA8 readback
+  urtd::Stream copy_stream;
   uint64_t read_next = 0;
 
-  // urt_ray_query (host memory): grow-only device scratch for the rays and the results, q_cap rays each
-  float4* q_rays = nullptr; float4* q_out = nullptr; size_t q_cap = 0;
-  // urt_radiance_query (host memory): grow-only device scratch for the queries (rq_in_cap bytes) and the results (rq_out_cap texels);
-  // rq_next: the work counter of k_radiance_persist (one word; each launch zeroes it on the stream in front of itself)
-  void* rq_in = nullptr; size_t rq_in_cap = 0;
-  float4* rq_out = nullptr; size_t rq_out_cap = 0;
-  unsigned int* rq_next = nullptr;
-  // urt_denoise: grow-only device scratch of 3 float4 images (guide, two colour images) of dn_cap pixels each
-  float4* dn_scratch = nullptr; size_t dn_cap = 0;
-  // urt_reproject_objects: grow-only device copies of the mesh and the sphere motion table, mo_cap[k] bytes each
-  float4* mo_table[2] = {nullptr, nullptr}; size_t mo_cap[2] = {0, 0};
-  // urt_select_pixels / urt_resample_below: grow-only device scratch for the per-block counts and the total behind them (rs_counts_cap
-  // words) and a pinned host word the total is copied to; urt_resample_below: the pixel list (rs_pixels_cap entries of 8 bytes) and its
-  // samples (rs_samples_cap texels), both sized by the selected count, not by the image
-  unsigned int* rs_counts = nullptr; size_t rs_counts_cap = 0;
-  unsigned int* rs_total = nullptr;
-  void* rs_pixels = nullptr; size_t rs_pixels_cap = 0;
-  float4* rs_samples = nullptr; size_t rs_samples_cap = 0;
+  // Grow-only device scratch (owned.h reserve) of the calls that take host memory or need room of their own:
+  urtd::DeviceBuf<urt_Ray> q_rays; urtd::DeviceBuf<urt_RayHit> q_out;   // urt_ray_query: the rays and the results
+  urtd::DeviceBuf<char> rq_in; urtd::DeviceBuf<float4> rq_out;          // urt_radiance_query: the queries (bytes) and the results (texels)
+  urtd::DeviceBuf<unsigned int> rq_next;      // the work counter of k_radiance_persist (one word; each launch zeroes it on the stream in front of itself)
+  urtd::DeviceBuf<float4> dn_scratch;         // urt_denoise: 3 images (guide, two colour images)
+  urtd::DeviceBuf<urt_ObjectMotion> mo_table[2];   // urt_reproject_objects: copies of the mesh and the sphere motion table
+  // urt_select_pixels / urt_resample_below: the per-block counts and the total behind them, and a pinned host word the total is copied to;
+  // urt_resample_below: the pixel list and its samples, both sized by the selected count, not by the image
+  urtd::DeviceBuf<unsigned int> rs_counts; urtd::PinnedBuf<unsigned int> rs_total;
+  urtd::DeviceBuf<urt_PathPixel> rs_pixels; urtd::DeviceBuf<float4> rs_samples;
 };
 
 namespace urtd {
 
 using PostOp = urt_context::PostOp;
 using OpKind = urt_context::OpKind;
-
-int fail(urt_context* ctx, int code, const std::string& msg);   // sets urt_last_error(ctx) (ctx NULL: the creation error); returns code
 
 #define URT_HIP(ctx, expr)                                                                         \
   do {                                                                                             \
@@ -304,5 +300,12 @@ int bind_sky(urt_context* ctx, DevScene& S);
 bool in_slab(urt_context* ctx, const Texture& t);
 int detach_from_slab(urt_context* ctx, Texture& t);
 int resolve_timing(urt_context* ctx);
+
+// The scene the bound buffers describe: a stale one is prepared first, after the deferred frames that read the one it replaces.
+inline int current_scene(urt_context* ctx) {
+  if (!ctx->scene_dirty) return URT_OK;
+  if (int rc = flush_pending(ctx)) return rc;
+  return prepare_scene(ctx);
+}
 
 }  // namespace urtd

@@ -16,47 +16,36 @@ static unsigned int sched_trip_cap(urt_context* ctx, const FrameParams& P, int n
   return (unsigned int)std::min<uint64_t>(cap, 0xfffffff0ull);
 }
 
-static int ensure_queues(urt_context* ctx, size_t n_paths, size_t n_counts) {
-  if (n_paths > ctx->q_capacity) {
-    for (int a = 0; a < 2; a++)
-      for (int r = 0; r < 4; r++) {
-        if (ctx->q.s[a][r]) (void)hipFree(ctx->q.s[a][r]);
-        ctx->q.s[a][r] = nullptr;
-      }
-    ctx->q_capacity = 0;
-    for (int a = 0; a < 2; a++)
-      for (int r = 0; r < 4; r++) URT_HIP(ctx, hipMalloc((void**)&ctx->q.s[a][r], n_paths * sizeof(float4)));
-    ctx->q_capacity = n_paths;
+static int ensure_queues(urt_context* ctx, size_t n_paths, size_t n_counts) {   // (the wait for the main stream at growth is new; the launch that follows touches it anyway)
+  for (int k = 0; k < 8; k++) {
+    if (int rc = reserve(ctx, ctx->q_store[k / 4][k % 4], n_paths, "path queue allocation", touch(ctx))) return rc;
+    ctx->q.s[k / 4][k % 4] = ctx->q_store[k / 4][k % 4].get();
   }
-  if (n_counts > ctx->counts_capacity) {
-    if (ctx->q.counts) (void)hipFree(ctx->q.counts);
-    ctx->q.counts = nullptr; ctx->counts_capacity = 0;
-    URT_HIP(ctx, hipMalloc((void**)&ctx->q.counts, n_counts * sizeof(unsigned int)));
-    ctx->counts_capacity = n_counts;
-  }
+  if (int rc = reserve(ctx, ctx->q_counts, n_counts, "path queue allocation", touch(ctx))) return rc;
+  ctx->q.counts = ctx->q_counts.get();
   return URT_OK;
 }
 
 int resolve_timing(urt_context* ctx) {
   for (auto& pr : ctx->timing) {
     float ms = 0;
-    if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) ctx->trace_ms += ms;
-    ctx->event_pool.push_back(pr.first);
-    ctx->event_pool.push_back(pr.second);
+    if (hipEventElapsedTime(&ms, pr.first.get(), pr.second.get()) == hipSuccess) ctx->trace_ms += ms;
+    ctx->event_pool.push_back(std::move(pr.first));
+    ctx->event_pool.push_back(std::move(pr.second));
   }
   ctx->timing.clear();
   return URT_OK;
 }
 
-static int take_event(urt_context* ctx, hipEvent_t* out) {
-  if (!ctx->event_pool.empty()) { *out = ctx->event_pool.back(); ctx->event_pool.pop_back(); return URT_OK; }
-  URT_HIP(ctx, hipEventCreate(out));
+static int take_event(urt_context* ctx, Event* out) {
+  if (!ctx->event_pool.empty()) { *out = std::move(ctx->event_pool.back()); ctx->event_pool.pop_back(); return URT_OK; }
+  URT_HIP(ctx, out->create(hipEventDefault));
   return URT_OK;
 }
 
 // ---- Result renaming: the slab of frame slots ---------------------------------------------------------------------------
 bool in_slab(urt_context* ctx, const Texture& t) {
-  return ctx->slab && t.dev >= ctx->slab && t.dev < ctx->slab + ctx->slab_stride * (size_t)ctx->slab_frames;
+  return ctx->slab && t.dev >= ctx->slab.get() && t.dev < ctx->slab.get() + ctx->slab_stride * (size_t)ctx->slab_frames;
 }
 
 // Give a texture its own storage back (its current contents are copied out of the slab slot they live in).
@@ -83,20 +72,17 @@ static int ensure_slab(urt_context* ctx, urt_handle h, Texture& t, int frames) {
   if (!ctx->slab || ctx->slab_stride * (size_t)ctx->slab_frames < stride * (size_t)frames) {
     if (ctx->slab) {
       URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));   // queued kernels may still use the old slab
-      (void)hipFree(ctx->slab);
-      ctx->slab = nullptr; ctx->slab_frames = 0; ctx->slab_stride = 0;
+      ctx->slab.reset(); ctx->slab_frames = 0; ctx->slab_stride = 0;
     }
     // out of memory (several contexts on one card, a huge image): halve the batch until the slots fit; one frame = no slab at
     // all (the caller then renders unbatched, straight into the texture)
     hipError_t e = hipErrorOutOfMemory;
     while (frames >= 2) {
-      e = hipMalloc((void**)&ctx->slab, stride * (size_t)frames * sizeof(float4));
+      e = ctx->slab.alloc(stride * (size_t)frames);
       if (e != hipErrorOutOfMemory) break;
-      (void)hipGetLastError();
-      ctx->slab = nullptr;
       frames /= 2;
     }
-    if (e == hipErrorOutOfMemory) { ctx->slab = nullptr; ctx->slab_frames = 0; ctx->slab_stride = 0; ctx->slab_frames_max = 1; ctx->slab_oom_stride = stride; return URT_OK; }
+    if (e == hipErrorOutOfMemory) { ctx->slab_frames = 0; ctx->slab_stride = 0; ctx->slab_frames_max = 1; ctx->slab_oom_stride = stride; return URT_OK; }
     URT_HIP(ctx, e);
     ctx->slab_frames = frames;
     ctx->slab_frames_max = frames;
@@ -105,7 +91,7 @@ static int ensure_slab(urt_context* ctx, urt_handle h, Texture& t, int frames) {
   }
   ctx->slab_stride = stride;
   if (ctx->slab_frames < 2) return URT_OK;               // (re-cut for a larger image: no room for two slots -> unbatched)
-  URT_HIP(ctx, hipMemsetAsync(ctx->slab, 0, stride * (size_t)ctx->slab_frames * sizeof(float4), touch(ctx)));   // a new RenderTexture is zero-filled
+  URT_HIP(ctx, hipMemsetAsync(ctx->slab.get(), 0, stride * (size_t)ctx->slab_frames * sizeof(float4), touch(ctx)));   // a new RenderTexture is zero-filled
   ctx->slab_tex = h;
   return URT_OK;
 }
@@ -226,17 +212,17 @@ static void record_launch(urt_context* ctx, const TraceLaunchRecord& R, int kern
 // when "time_dispatch" is on; then the launch is counted and recorded (record_launch)
 template <typename Launch>
 static int timed_launch(urt_context* ctx, hipStream_t st, int kernel_mode, int front_mode, const FrameParams& P, bool count, int waves_per_cu, Launch launch) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  Event e0, e1;
   if (ctx->opt.time_dispatch) {
     int rc = take_event(ctx, &e0); if (rc) return rc;
     rc = take_event(ctx, &e1); if (rc) return rc;
-    URT_HIP(ctx, hipEventRecord(e0, st));
+    URT_HIP(ctx, hipEventRecord(e0.get(), st));
   }
   TraceLaunchRecord rec{};
   hipError_t le = launch(&rec);
   if (ctx->opt.time_dispatch) {
-    (void)hipEventRecord(e1, st);
-    ctx->timing.emplace_back(e0, e1);
+    (void)hipEventRecord(e1.get(), st);
+    ctx->timing.emplace_back(std::move(e0), std::move(e1));
   }
   ctx->launches++;
   if (le != hipSuccess) return fail(ctx, URT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(le));
@@ -249,20 +235,20 @@ static constexpr int kAutoFrames = 64;     // frames per launch when "frames_per
 
 static int launch_sched_frames(urt_context* ctx, const DevScene& S, const FrameParams& P, const FrameTable& T, float4* result,
                         int front_mode, bool count, hipStream_t st = nullptr, unsigned int* next = nullptr) {
-  if (!st) { st = touch(ctx); next = ctx->d_next; }       // the main stream; flush_pending may pass one of its trace streams and that stream's work counters
+  if (!st) { st = touch(ctx); next = ctx->d_next.get(); }       // the main stream; flush_pending may pass one of its trace streams and that stream's work counters
   // the launch's frame table -> device memory, in stream order (pinned staging slot: the copy does not wait for the stream)
   if (!ctx->h_tables) {
-    URT_HIP(ctx, hipHostMalloc((void**)&ctx->h_tables, sizeof(FrameUniforms) * kMaxFramesPerLaunch * urt_context::kTableSlots, hipHostMallocDefault));
-    URT_HIP(ctx, hipMalloc((void**)&ctx->d_tables, sizeof(FrameUniforms) * kMaxFramesPerLaunch * urt_context::kTableSlots));
-    for (int k = 0; k < urt_context::kTableSlots; k++) URT_HIP(ctx, hipEventCreateWithFlags(&ctx->table_ev[k], hipEventDisableTiming));
+    URT_HIP(ctx, ctx->h_tables.alloc((size_t)kMaxFramesPerLaunch * urt_context::kTableSlots));
+    URT_HIP(ctx, ctx->d_tables.alloc((size_t)kMaxFramesPerLaunch * urt_context::kTableSlots));
+    for (Event& ev : ctx->table_ev) URT_HIP(ctx, ev.create(hipEventDisableTiming));
   }
   const unsigned int slot = ctx->table_next++ % (unsigned int)urt_context::kTableSlots;
-  if (ctx->table_next > (unsigned int)urt_context::kTableSlots) URT_HIP(ctx, hipEventSynchronize(ctx->table_ev[slot]));   // (four launches ago: long done)
-  FrameUniforms* h_slot = ctx->h_tables + (size_t)slot * kMaxFramesPerLaunch;
-  FrameUniforms* d_table = ctx->d_tables + (size_t)slot * kMaxFramesPerLaunch;
+  if (ctx->table_next > (unsigned int)urt_context::kTableSlots) URT_HIP(ctx, hipEventSynchronize(ctx->table_ev[slot].get()));   // (four launches ago: long done)
+  FrameUniforms* h_slot = ctx->h_tables.get() + (size_t)slot * kMaxFramesPerLaunch;
+  FrameUniforms* d_table = ctx->d_tables.get() + (size_t)slot * kMaxFramesPerLaunch;
   std::memcpy(h_slot, T.f, sizeof(FrameUniforms) * (size_t)P.n_frames);
   URT_HIP(ctx, hipMemcpyAsync(d_table, h_slot, sizeof(FrameUniforms) * (size_t)P.n_frames, hipMemcpyHostToDevice, st));
-  URT_HIP(ctx, hipEventRecord(ctx->table_ev[slot], st));
+  URT_HIP(ctx, hipEventRecord(ctx->table_ev[slot].get(), st));
   int waves_per_block = P.block_threads / 64;
   long want = ((long)P.tiles_x * P.n_strips * P.n_frames + waves_per_block - 1) / waves_per_block;
   // resident waves per CU: every slot the registers allow (k_sched: 96 VGPRs -> 5 waves/SIMD = 20 per CU).  While the
@@ -274,16 +260,11 @@ static int launch_sched_frames(urt_context* ctx, const DevScene& S, const FrameP
   long resident = (long)ctx->n_cus * wpc / waves_per_block;
   int nb = (int)std::max(1L, std::min(want, resident));
   if (P.serve) {                                             // mailbox of the posted rays: 32 B per thread of the grid
-    size_t slots = (size_t)nb * (size_t)P.block_threads;
-    if (slots > ctx->mail_slots) {
-      if (ctx->d_mail) { URT_HIP(ctx, hipStreamSynchronize(touch(ctx))); (void)hipFree(ctx->d_mail); ctx->d_mail = nullptr; ctx->mail_slots = 0; }
-      URT_HIP(ctx, hipMalloc((void**)&ctx->d_mail, slots * 2 * sizeof(float4)));
-      ctx->mail_slots = slots;
-    }
+    if (int rc = reserve(ctx, ctx->d_mail, (size_t)nb * (size_t)P.block_threads * 2, "mailbox allocation", touch(ctx))) return rc;
   }
   return timed_launch(ctx, st, P.serve ? 5 : 3, front_mode, P, count, wpc, [&](TraceLaunchRecord* rec) {
-    return P.serve ? launch_serve(S, P, d_table, result, ctx->d_counters, next, ctx->d_mail, nb, front_mode, count, st, rec)
-                   : launch_sched(S, P, d_table, result, ctx->d_counters, next, nb, front_mode, count, st, rec);
+    return P.serve ? launch_serve(S, P, d_table, result, ctx->d_counters.get(), next, ctx->d_mail.get(), nb, front_mode, count, st, rec)
+                   : launch_sched(S, P, d_table, result, ctx->d_counters.get(), next, nb, front_mode, count, st, rec);
   });
 }
 
@@ -336,45 +317,45 @@ int flush_pending(urt_context* ctx) {
   int base = 0;
   bool reading = false;                                  // a pipelined readback in flight: the host paces itself on FINISHED frames, and two launches sharing
   for (const auto& r : ctx->rslot) reading = reading || r.busy;   // the chip finish later than one after the other (measured: +6 % C3, +21 % C2 with two tickets in flight)
-  const bool eligible = (ctx->opt.overlap_launches == 2 || (ctx->opt.overlap_launches == 1 && !reading)) && ctx->stream == ctx->own_stream && !P.serve && !ctx->opt.time_dispatch &&
+  const bool eligible = (ctx->opt.overlap_launches == 2 || (ctx->opt.overlap_launches == 1 && !reading)) && ctx->stream == ctx->own_stream.get() && !P.serve && !ctx->opt.time_dispatch &&
                         n <= urt_context::kOverlapFrames && ctx->slab_frames >= 2 * urt_context::kOverlapFrames && ctx->d_next2;
   if (eligible) {
     base = ctx->slab_cursor + n <= ctx->slab_frames ? ctx->slab_cursor : 0;
     if (!ctx->trace_q[0]) {
       for (int k = 0; k < 2; k++) {
-        URT_HIP(ctx, hipStreamCreateWithFlags(&ctx->trace_q[k], hipStreamNonBlocking));
-        URT_HIP(ctx, hipEventCreateWithFlags(&ctx->trace_done[k], hipEventDisableTiming));
-        URT_HIP(ctx, hipEventCreateWithFlags(&ctx->pre_ev[k], hipEventDisableTiming));
+        URT_HIP(ctx, ctx->trace_q[k].create(hipStreamNonBlocking));
+        URT_HIP(ctx, ctx->trace_done[k].create(hipEventDisableTiming));
+        URT_HIP(ctx, ctx->pre_ev[k].create(hipEventDisableTiming));
       }
-      URT_HIP(ctx, hipEventCreateWithFlags(&ctx->dep_ev, hipEventDisableTiming));
+      URT_HIP(ctx, ctx->dep_ev.create(hipEventDisableTiming));
     }
     const unsigned int k = ctx->trace_parity++ & 1u;
     const bool disjoint = base >= ctx->prev_base + ctx->prev_n || base + n <= ctx->prev_base;
     if (ctx->main_touched || !disjoint) {
-      URT_HIP(ctx, hipEventRecord(ctx->dep_ev, ctx->stream));
-      URT_HIP(ctx, hipStreamWaitEvent(ctx->trace_q[k], ctx->dep_ev, 0));
+      URT_HIP(ctx, hipEventRecord(ctx->dep_ev.get(), ctx->stream));
+      URT_HIP(ctx, hipStreamWaitEvent(ctx->trace_q[k].get(), ctx->dep_ev.get(), 0));
     } else {
-      URT_HIP(ctx, hipStreamWaitEvent(ctx->trace_q[k], ctx->pre_ev[k ^ 1u], 0));
+      URT_HIP(ctx, hipStreamWaitEvent(ctx->trace_q[k].get(), ctx->pre_ev[k ^ 1u].get(), 0));
       ctx->overlapped_launches++;
     }
     const bool narrow = !(ctx->main_touched || !disjoint);
-    int rc = launch_sched_frames(ctx, B.S, P, B.T, ctx->slab + (size_t)base * ctx->slab_stride, B.front_mode, B.count, ctx->trace_q[k], k ? ctx->d_next2 : ctx->d_next);
+    int rc = launch_sched_frames(ctx, B.S, P, B.T, ctx->slab.get() + (size_t)base * ctx->slab_stride, B.front_mode, B.count, ctx->trace_q[k].get(), (k ? ctx->d_next2 : ctx->d_next).get());
     if (rc) { ctx->main_touched = true; return rc; }
     ctx->last_launch.trace_stream = 1 + (int)k; ctx->last_launch.slab_base = base; ctx->last_launch.overlapped = narrow ? 1 : 0;
-    URT_HIP(ctx, hipEventRecord(ctx->trace_done[k], ctx->trace_q[k]));
-    URT_HIP(ctx, hipEventRecord(ctx->pre_ev[k], ctx->stream));
-    URT_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->trace_done[k], 0));
+    URT_HIP(ctx, hipEventRecord(ctx->trace_done[k].get(), ctx->trace_q[k].get()));
+    URT_HIP(ctx, hipEventRecord(ctx->pre_ev[k].get(), ctx->stream));
+    URT_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->trace_done[k].get(), 0));
     ctx->main_touched = false;
   } else {
-    int rc = launch_sched_frames(ctx, B.S, P, B.T, ctx->slab, B.front_mode, B.count);     // on the main stream (marks it touched)
+    int rc = launch_sched_frames(ctx, B.S, P, B.T, ctx->slab.get(), B.front_mode, B.count);     // on the main stream (marks it touched)
     if (rc) return rc;
   }
   ctx->prev_base = base; ctx->prev_n = n; ctx->slab_cursor = base + n;
   if (base) {                                            // the Result texture names the LAST frame's slot (do_dispatch named it assuming slot 0)
     Texture* rt = find_texture(ctx, B.tex);
-    if (rt && in_slab(ctx, *rt)) rt->dev = ctx->slab + (size_t)(base + n - 1) * ctx->slab_stride;
+    if (rt && in_slab(ctx, *rt)) rt->dev = ctx->slab.get() + (size_t)(base + n - 1) * ctx->slab_stride;
   }
-  const float4* const slots = ctx->slab + (size_t)base * ctx->slab_stride;
+  const float4* const slots = ctx->slab.get() + (size_t)base * ctx->slab_stride;
   size_t i = 0;
   while (i < ops.size()) {
     const PostOp& op = ops[i];
@@ -427,7 +408,7 @@ int flush_pending(urt_context* ctx) {
 static int batch_limit(urt_context* ctx, const FrameParams& P) {
   int lim = ctx->opt.frames_per_launch;
   if (lim == 0) {
-    if (ctx->stream != ctx->own_stream) return 1;        // a caller that shares its stream expects the work ON the stream when dispatch returns
+    if (ctx->stream != ctx->own_stream.get()) return 1;        // a caller that shares its stream expects the work ON the stream when dispatch returns
     // kAutoFrames frames per launch, within 8 GiB of Result slots: 2160p still gains from long launches (profiles/r02_logs/r2_fpl4k.log),
     // and 32 x 133 MB is nothing on a 288 GB part
     uint64_t frame_bytes = (uint64_t)P.width * (uint64_t)P.height * sizeof(float4);
@@ -445,10 +426,10 @@ int bind_sky(urt_context* ctx, DevScene& S) {
   if (sky) { S.sky = sky->dev; S.sky_w = sky->w; S.sky_h = sky->h; }
   else {     // an unbound SRV reads zeros
     if (!ctx->zero_sky) {
-      URT_HIP(ctx, hipMalloc((void**)&ctx->zero_sky, sizeof(float4)));
-      URT_HIP(ctx, hipMemsetAsync(ctx->zero_sky, 0, sizeof(float4), touch(ctx)));
+      URT_HIP(ctx, ctx->zero_sky.alloc(1));
+      URT_HIP(ctx, hipMemsetAsync(ctx->zero_sky.get(), 0, sizeof(float4), touch(ctx)));
     }
-    S.sky = ctx->zero_sky; S.sky_w = 1; S.sky_h = 1;
+    S.sky = ctx->zero_sky.get(); S.sky_w = 1; S.sky_h = 1;
   }
   return URT_OK;
 }
@@ -462,10 +443,7 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
   if (!res) return fail(ctx, URT_ERR_UNBOUND, "Dispatch: no texture bound to \"Result\" (RM:803)");
   if (res->w > 65535 || res->h > 65535) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "Result larger than 65535 pixels per side");
   URT_HIP(ctx, hipSetDevice(ctx->device));
-  if (ctx->scene_dirty) {
-    int rc = flush_pending(ctx); if (rc) return rc;      // the deferred frames read the scene that is about to be replaced
-    rc = prepare_scene(ctx); if (rc) return rc;
-  }
+  if (int rc = current_scene(ctx)) return rc;
   ctx->dispatches++;
   if (gx == 0 || gy == 0 || gz == 0) return URT_OK;
 
@@ -556,7 +534,7 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
         B.tex = res_h; B.scene_epoch = ctx->scene_epoch; B.S = S; B.P = P; B.front_mode = front_mode; B.count = count;
       }
       B.T.f[B.n] = fu;
-      res->dev = ctx->slab + (size_t)B.n * ctx->slab_stride;   // Result now names this frame's slot
+      res->dev = ctx->slab.get() + (size_t)B.n * ctx->slab_stride;   // Result now names this frame's slot
       B.n++;
     }
   } else {
@@ -590,10 +568,10 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
     const hipStream_t st = touch(ctx);
     rc = timed_launch(ctx, st, mode, 0, P, count, ctx->opt.waves_per_cu, [&](TraceLaunchRecord* rec) {
       switch (mode) {
-        case 1: return launch_wavefront(S, P, ctx->q, res->dev, ctx->d_counters, count, st, rec);
-        case 2: return launch_persist(S, P, res->dev, ctx->d_counters, ctx->d_next, nb, count, st, rec);
-        case 4: return launch_pool(S, P, res->dev, ctx->d_counters, ctx->d_next, nb, k, count, st, rec);
-        default: return launch_mega(S, P, res->dev, ctx->d_counters, count, st, rec);
+        case 1: return launch_wavefront(S, P, ctx->q, res->dev, ctx->d_counters.get(), count, st, rec);
+        case 2: return launch_persist(S, P, res->dev, ctx->d_counters.get(), ctx->d_next.get(), nb, count, st, rec);
+        case 4: return launch_pool(S, P, res->dev, ctx->d_counters.get(), ctx->d_next.get(), nb, k, count, st, rec);
+        default: return launch_mega(S, P, res->dev, ctx->d_counters.get(), count, st, rec);
       }
     });
     if (rc) return rc;

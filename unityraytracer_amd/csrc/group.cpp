@@ -22,6 +22,7 @@
 
 #include "../../include/urt.h"
 #include "context_internal.h"
+#include "owned.h"
 
 struct urt_group {
   std::vector<urt_context*> ctx;
@@ -29,10 +30,12 @@ struct urt_group {
   // gather staging: slot s of rank r = that rank's packed strips of pending gather s
   static constexpr int kSlots = 16;
   size_t stage_bytes = 0;                              // per rank and slot (packed strips of the largest rank)
-  std::vector<void*> stage;                            // [rank] on that rank's device: kSlots x stage_bytes
-  std::vector<void*> recv;                             // [rank] on rank 0's device:   kSlots x stage_bytes
-  std::vector<std::vector<hipEvent_t>> ev_copy;        // [rank][slot] the peer copy of that slot has landed on rank 0
-  std::vector<std::vector<hipEvent_t>> ev_free;        // [rank][slot] rank 0 has unpacked it (the slot may be reused)
+  struct Rank {
+    urtd::DeviceBuf<char> stage, recv;                 // kSlots x stage_bytes each: stage on the rank's device, recv on rank 0's
+    urtd::Event ev_copy[kSlots];                       // [slot] on the rank's device: the peer copy of that slot has landed on rank 0
+    urtd::Event ev_free[kSlots];                       // [slot] on rank 0's device: rank 0 has unpacked it (the slot may be reused)
+  };
+  std::vector<Rank> rank;
   // gathers whose packs are queued but whose copies are not issued yet (staging slot `slot`), and — in program order between them —
   // the plain blits that read or write an image such a gather writes (`blit`: the present of the gathered image, RM:819): they must
   // run after the unpack that is still to be issued
@@ -74,12 +77,15 @@ int rank_fail(urt_group* g, int rank, int code) {
     return URT_OK;                                                                                      \
   } while (0)
 
+// each buffer is reset with its own device current: the rank's for stage, rank 0's for recv
 void free_staging(urt_group* g) {
-  for (size_t r = 0; r < g->ctx.size(); r++) {
-    if (r < g->stage.size() && g->stage[r]) { (void)hipSetDevice(urtd::context_device(g->ctx[r])); (void)hipFree(g->stage[r]); }
-    if (r < g->recv.size() && g->recv[r]) { (void)hipSetDevice(urtd::context_device(g->ctx[0])); (void)hipFree(g->recv[r]); }
+  for (size_t r = 0; r < g->rank.size(); r++) {
+    (void)hipSetDevice(urtd::context_device(g->ctx[r]));
+    g->rank[r].stage.reset();
+    (void)hipSetDevice(urtd::context_device(g->ctx[0]));
+    g->rank[r].recv.reset();
   }
-  g->stage.clear(); g->recv.clear(); g->stage_bytes = 0;
+  g->stage_bytes = 0;
 }
 
 int flush_gathers(urt_group* g);
@@ -89,13 +95,11 @@ int ensure_staging(urt_group* g, size_t bytes) {
   { int rc = flush_gathers(g); if (rc) return rc; }                      // queued gathers have packed into the old buffers: copy + unpack them first
   for (urt_context* c : g->ctx) { int rc = urt_synchronize(c); if (rc) return gfail(g, rc, urt_last_error(c)); }
   free_staging(g);
-  size_t n = g->ctx.size();
-  g->stage.assign(n, nullptr); g->recv.assign(n, nullptr);
-  for (size_t r = 0; r < n; r++) {
+  for (size_t r = 0; r < g->ctx.size(); r++) {
     GROUP_HIP(g, hipSetDevice(urtd::context_device(g->ctx[r])));
-    GROUP_HIP(g, hipMalloc(&g->stage[r], bytes * urt_group::kSlots));
+    GROUP_HIP(g, g->rank[r].stage.alloc(bytes * urt_group::kSlots));
     GROUP_HIP(g, hipSetDevice(urtd::context_device(g->ctx[0])));
-    GROUP_HIP(g, hipMalloc(&g->recv[r], bytes * urt_group::kSlots));
+    GROUP_HIP(g, g->rank[r].recv.alloc(bytes * urt_group::kSlots));
   }
   g->stage_bytes = bytes;
   return URT_OK;
@@ -120,10 +124,10 @@ int flush_gathers(urt_group* g) {
     GROUP_HIP(g, hipSetDevice(dev));
     for (const urt_group::PendingGather& op : todo) {
       if (!op.blit) {
-        char* src = (char*)g->stage[r] + (size_t)op.slot * g->stage_bytes;
-        char* dst = (char*)g->recv[r] + (size_t)op.slot * g->stage_bytes;
+        char* src = g->rank[r].stage.get() + (size_t)op.slot * g->stage_bytes;
+        char* dst = g->rank[r].recv.get() + (size_t)op.slot * g->stage_bytes;
         GROUP_HIP(g, hipMemcpyPeerAsync(dst, dev0, src, dev, g->stage_bytes, st));   // xGMI point-to-point (or on-device when the ordinals coincide)
-        GROUP_HIP(g, hipEventRecord(g->ev_copy[r][(size_t)op.slot], st));
+        GROUP_HIP(g, hipEventRecord(g->rank[r].ev_copy[op.slot].get(), st));
       } else if (r != 0) {
         rc = urt_blit(c, op.src, op.dst);                               // replicated like every blit (only rank 0's copy shows the gathered image)
         if (rc) return rank_fail(g, (int)r, rc);
@@ -139,10 +143,10 @@ int flush_gathers(urt_group* g) {
       continue;
     }
     for (size_t r = 0; r < n; r++) {
-      GROUP_HIP(g, hipStreamWaitEvent(st0, g->ev_copy[r][(size_t)op.slot], 0));
-      int rc = urt_texture_unpack_rows(root, op.dst, (int)r, (int)n, (char*)g->recv[r] + (size_t)op.slot * g->stage_bytes);
+      GROUP_HIP(g, hipStreamWaitEvent(st0, g->rank[r].ev_copy[op.slot].get(), 0));
+      int rc = urt_texture_unpack_rows(root, op.dst, (int)r, (int)n, g->rank[r].recv.get() + (size_t)op.slot * g->stage_bytes);
       if (rc) return rank_fail(g, 0, rc);
-      GROUP_HIP(g, hipEventRecord(g->ev_free[r][(size_t)op.slot], st0));
+      GROUP_HIP(g, hipEventRecord(g->rank[r].ev_free[op.slot].get(), st0));
     }
   }
   return URT_OK;
@@ -193,15 +197,14 @@ int urt_group_create(const int* devices, int n_devices, urt_group** out_group) {
       if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();   // the copy engine falls back to staging through the host
     }
   }
-  g->ev_copy.resize((size_t)n_devices); g->ev_free.resize((size_t)n_devices);
+  g->rank.resize((size_t)n_devices);
   for (int r = 0; r < n_devices; r++) {
     for (int s = 0; s < urt_group::kSlots; s++) {
-      hipEvent_t a = nullptr, b = nullptr;
       (void)hipSetDevice(devices[r]);
-      if (hipEventCreateWithFlags(&a, hipEventDisableTiming) != hipSuccess) { urt_group_destroy(g); return gfail(nullptr, URT_ERR_HIP, "hipEventCreate failed"); }
+      hipError_t e = g->rank[(size_t)r].ev_copy[s].create(hipEventDisableTiming);
       (void)hipSetDevice(dev0);
-      if (hipEventCreateWithFlags(&b, hipEventDisableTiming) != hipSuccess) { (void)hipEventDestroy(a); urt_group_destroy(g); return gfail(nullptr, URT_ERR_HIP, "hipEventCreate failed"); }
-      g->ev_copy[(size_t)r].push_back(a); g->ev_free[(size_t)r].push_back(b);
+      if (e == hipSuccess) e = g->rank[(size_t)r].ev_free[s].create(hipEventDisableTiming);
+      if (e != hipSuccess) { urt_group_destroy(g); return gfail(nullptr, URT_ERR_HIP, "hipEventCreate failed"); }
     }
   }
   *out_group = g;
@@ -211,9 +214,8 @@ int urt_group_create(const int* devices, int n_devices, urt_group** out_group) {
 int urt_group_destroy(urt_group* g) {
   if (!g) return URT_OK;
   for (urt_context* c : g->ctx) (void)urt_synchronize(c);
-  for (auto& v : g->ev_copy) for (hipEvent_t e : v) (void)hipEventDestroy(e);
-  for (auto& v : g->ev_free) for (hipEvent_t e : v) (void)hipEventDestroy(e);
   free_staging(g);
+  g->rank.clear();                                     // the events, before the contexts as ever; destroying one needs no device current
   for (urt_context* c : g->ctx) (void)urt_context_destroy(c);
   delete g;
   return URT_OK;
@@ -316,8 +318,8 @@ int urt_group_gather(urt_group* g, urt_handle src_texture, urt_handle dst_textur
     // the slot's previous use must have been unpacked on rank 0 before this rank's next peer copy overwrites the receive
     // buffer (a never-recorded event counts as complete)
     GROUP_HIP(g, hipSetDevice(urtd::context_device(c)));
-    GROUP_HIP(g, hipStreamWaitEvent(urtd::context_stream(c), g->ev_free[r][slot], 0));
-    rc = urt_texture_pack_rows(c, src_texture, (int)r, (int)n, (char*)g->stage[r] + slot * g->stage_bytes, nullptr);   // deferred behind the rank's batched frames
+    GROUP_HIP(g, hipStreamWaitEvent(urtd::context_stream(c), g->rank[r].ev_free[slot].get(), 0));
+    rc = urt_texture_pack_rows(c, src_texture, (int)r, (int)n, g->rank[r].stage.get() + slot * g->stage_bytes, nullptr);   // deferred behind the rank's batched frames
     if (rc) return rank_fail(g, (int)r, rc);
   }
   g->pending.push_back(urt_group::PendingGather{false, src_texture, dst_texture, (int)slot});

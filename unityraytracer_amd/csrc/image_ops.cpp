@@ -56,22 +56,6 @@ int check_outputs(urt_context* ctx, const char* prefix, const TexArg* a, int fir
   return URT_OK;
 }
 
-// Grow-only device scratch: *p holds *cap units; when `need` exceeds them it is replaced by an allocation of `bytes` (after the work
-// queued on the stream, which may still use the old one).  On failure *p is NULL, *cap 0 and the error names `what`.
-int grow_scratch(urt_context* ctx, void** p, size_t* cap, size_t need, size_t bytes, const char* what) {
-  if (need <= *cap) return URT_OK;
-  if (*p) {
-    URT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-  }
-  hipError_t e = hipMalloc(p, bytes);
-  if (e == hipSuccess) { *cap = need; return URT_OK; }
-  (void)hipGetLastError();
-  *p = nullptr;
-  return fail(ctx, e == hipErrorOutOfMemory ? URT_ERR_OUT_OF_MEMORY : URT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 // urt_radiance_query with option "radiance_persist" at -1: k_radiance_persist, measured faster on full-frame pixel batches in any order and
 // within 1.5 % on the probe bake (profiles/r10_logs/r10_radiance_query_bench.log)
 constexpr bool kRadiancePersistAuto = true;
@@ -85,18 +69,17 @@ int check_select_size(urt_context* ctx, const char* prefix, const Texture* c) {
 
 // the per-block counts of a selection over n_texels texels and the pinned word its total comes back in
 int select_scratch(urt_context* ctx, const char* what, size_t n_texels) {
-  const size_t words = select_scratch_words(n_texels);
-  if (int rc = grow_scratch(ctx, (void**)&ctx->rs_counts, &ctx->rs_counts_cap, words, words * sizeof(unsigned int), what)) return rc;
-  if (!ctx->rs_total) URT_HIP(ctx, hipHostMalloc((void**)&ctx->rs_total, 64, hipHostMallocDefault));
+  if (int rc = reserve(ctx, ctx->rs_counts, select_scratch_words(n_texels), what, ctx->stream)) return rc;
+  if (!ctx->rs_total) URT_HIP(ctx, ctx->rs_total.alloc(1, 64));
   return URT_OK;
 }
 
 // after launch_select_count (and whatever else was enqueued behind it): the call's one synchronisation; *total = the number selected
 int select_total(urt_context* ctx, size_t n_texels, int* total) {
-  URT_HIP(ctx, hipMemcpyAsync(ctx->rs_total, ctx->rs_counts + select_blocks(n_texels), sizeof(unsigned int), hipMemcpyDeviceToHost, touch(ctx)));
+  URT_HIP(ctx, hipMemcpyAsync(ctx->rs_total.get(), ctx->rs_counts.get() + select_blocks(n_texels), sizeof(unsigned int), hipMemcpyDeviceToHost, touch(ctx)));
   URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
   if (int rc = check_watchdog(ctx)) return rc;
-  *total = (int)*ctx->rs_total;
+  *total = (int)*ctx->rs_total.get();
   return URT_OK;
 }
 
@@ -131,29 +114,21 @@ static int query_prepare(urt_context* ctx, const void* rays, int n, const void* 
   if (n > 0 && (!rays || !out)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "ray query: rays / out is NULL");
   if (n == 0) return URT_OK;
   URT_HIP(ctx, hipSetDevice(ctx->device));
-  if (ctx->scene_dirty) {
-    int rc = flush_pending(ctx); if (rc) return rc;       // the deferred frames read the scene that is about to be replaced
-    rc = prepare_scene(ctx); if (rc) return rc;
-  }
-  return URT_OK;
+  return current_scene(ctx);
 }
 
 int urt_ray_query(urt_context* ctx, const urt_Ray* rays, int n, void* out, int flags) {
   URT_GUARD_BEGIN
   int rc = query_prepare(ctx, rays, n, out, flags);
   if (rc || n == 0) return rc;
-  if ((size_t)n > ctx->q_cap) {                           // grow-only; no query still reads the old pair (this form synchronises before it returns)
-    if (ctx->q_rays) { (void)hipFree(ctx->q_rays); ctx->q_rays = nullptr; }
-    if (ctx->q_out) { (void)hipFree(ctx->q_out); ctx->q_out = nullptr; }
-    ctx->q_cap = 0;
-    URT_HIP(ctx, hipMalloc((void**)&ctx->q_rays, (size_t)n * sizeof(urt_Ray)));
-    URT_HIP(ctx, hipMalloc((void**)&ctx->q_out, (size_t)n * sizeof(urt_RayHit)));
-    ctx->q_cap = (size_t)n;
-  }
+  // the wait for the stream at growth is new here and costs nothing: no query still reads the old pair, as this form synchronises the
+  // same stream before it returns; device-form queries the caller enqueued since are ordered like everything else on it
+  if (int r = reserve(ctx, ctx->q_rays, (size_t)n, "ray query: scratch allocation", ctx->stream)) return r;
+  if (int r = reserve(ctx, ctx->q_out, (size_t)n, "ray query: scratch allocation", ctx->stream)) return r;
   const size_t out_bytes = (size_t)n * (flags == URT_QUERY_ANY ? sizeof(int32_t) : sizeof(urt_RayHit));
-  URT_HIP(ctx, hipMemcpyAsync(ctx->q_rays, rays, (size_t)n * sizeof(urt_Ray), hipMemcpyHostToDevice, ctx->stream));
-  URT_HIP(ctx, launch_query(ctx->scene.ds, ctx->scene.tlas_stack, ctx->scene.blas_stack, ctx->q_rays, n, ctx->q_out, flags == URT_QUERY_ANY, ctx->stream));
-  URT_HIP(ctx, hipMemcpyAsync(out, ctx->q_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  URT_HIP(ctx, hipMemcpyAsync(ctx->q_rays.get(), rays, (size_t)n * sizeof(urt_Ray), hipMemcpyHostToDevice, ctx->stream));
+  URT_HIP(ctx, launch_query(ctx->scene.ds, ctx->scene.tlas_stack, ctx->scene.blas_stack, (const float4*)ctx->q_rays.get(), n, ctx->q_out.get(), flags == URT_QUERY_ANY, ctx->stream));
+  URT_HIP(ctx, hipMemcpyAsync(out, ctx->q_out.get(), out_bytes, hipMemcpyDeviceToHost, ctx->stream));
   URT_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return check_watchdog(ctx);
   URT_GUARD_END(ctx)
@@ -219,8 +194,8 @@ static int radiance_prepare(urt_context* ctx, const void* in, int n, int samples
   launch->n = n; launch->samples = samples; launch->bounces = bounces; launch->pixels = pixels;
   const bool persist = ctx->opt.radiance_persist < 0 ? kRadiancePersistAuto : ctx->opt.radiance_persist != 0;
   if (persist) {
-    if (!ctx->rq_next) URT_HIP(ctx, hipMalloc((void**)&ctx->rq_next, sizeof(unsigned int)));
-    launch->work_counter = ctx->rq_next; launch->n_cus = ctx->n_cus;
+    if (!ctx->rq_next) URT_HIP(ctx, ctx->rq_next.alloc(1));
+    launch->work_counter = ctx->rq_next.get(); launch->n_cus = ctx->n_cus;
   }
   return URT_OK;
 }
@@ -231,12 +206,12 @@ int urt_radiance_query(urt_context* ctx, const void* in, int n, int samples, int
   int rc = radiance_prepare(ctx, in, n, samples, bounces, out_rgba, flags, true, &S, &C, &B);
   if (rc || n == 0) return rc;
   const size_t in_bytes = (size_t)n * (B.pixels ? sizeof(urt_PathPixel) : sizeof(urt_PathRay));
-  if (int r = grow_scratch(ctx, &ctx->rq_in, &ctx->rq_in_cap, in_bytes, in_bytes, "radiance query: scratch allocation")) return r;
-  if (int r = grow_scratch(ctx, (void**)&ctx->rq_out, &ctx->rq_out_cap, (size_t)n, (size_t)n * sizeof(float4), "radiance query: scratch allocation")) return r;
-  B.in = ctx->rq_in; B.out = ctx->rq_out;
-  URT_HIP(ctx, hipMemcpyAsync(ctx->rq_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (int r = reserve(ctx, ctx->rq_in, in_bytes, "radiance query: scratch allocation", ctx->stream)) return r;
+  if (int r = reserve(ctx, ctx->rq_out, (size_t)n, "radiance query: scratch allocation", ctx->stream)) return r;
+  B.in = ctx->rq_in.get(); B.out = ctx->rq_out.get();
+  URT_HIP(ctx, hipMemcpyAsync(ctx->rq_in.get(), in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
   URT_HIP(ctx, launch_radiance(S, ctx->scene.tlas_stack, ctx->scene.blas_stack + ctx->opt.stack_pad, C, B, ctx->stream));
-  URT_HIP(ctx, hipMemcpyAsync(out_rgba, ctx->rq_out, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  URT_HIP(ctx, hipMemcpyAsync(out_rgba, ctx->rq_out.get(), (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
   URT_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return check_watchdog(ctx);
   URT_GUARD_END(ctx)
@@ -322,11 +297,11 @@ int urt_denoise(urt_context* ctx, urt_handle src, urt_handle dst, urt_handle hit
   if (int rc = check_height(ctx, "denoise", "textures", height)) return rc;
   URT_HIP(ctx, hipSetDevice(ctx->device));
   const size_t n = (size_t)width * (size_t)height;
-  if (int rc = grow_scratch(ctx, (void**)&ctx->dn_scratch, &ctx->dn_cap, n, 3 * n * sizeof(float4), "denoise: scratch allocation")) return rc;
+  if (int rc = reserve(ctx, ctx->dn_scratch, 3 * n, "denoise: scratch allocation", ctx->stream)) return rc;
   { int rc = flush_pending(ctx); if (rc) return rc; }
   DenoiseImages I{};                                               // device pointers after the flush (a Result texture may be renamed)
   I.src = t[0]->dev; I.dst = t[1]->dev; I.hit = t[2]->dev; I.normal = t[3]->dev; I.albedo = t[4] ? t[4]->dev : nullptr;
-  I.scratch = ctx->dn_scratch; I.width = width; I.height = height;
+  I.scratch = ctx->dn_scratch.get(); I.width = width; I.height = height;
   DenoiseSettings S{P.iterations, P.sigma_color, P.sigma_normal, P.sigma_depth};
   t[1]->other_writes = true;
   URT_HIP(ctx, launch_denoise(I, S, touch(ctx)));
@@ -395,11 +370,11 @@ static int reproject_impl(urt_context* ctx, const urt_ReprojectImages* images, c
     for (int k = 0; k < 2; k++) {
       if (!tab[k]) continue;
       const size_t bytes = (size_t)tab[k]->count * sizeof(urt_ObjectMotion);
-      if (int rc = grow_scratch(ctx, (void**)&ctx->mo_table[k], &ctx->mo_cap[k], bytes, bytes, "reproject: motion table allocation")) return rc;
-      URT_HIP(ctx, hipMemcpyAsync(ctx->mo_table[k], tab[k]->host.data(), bytes, hipMemcpyHostToDevice, touch(ctx)));
+      if (int rc = reserve(ctx, ctx->mo_table[k], (size_t)tab[k]->count, "reproject: motion table allocation", ctx->stream)) return rc;
+      URT_HIP(ctx, hipMemcpyAsync(ctx->mo_table[k].get(), tab[k]->host.data(), bytes, hipMemcpyHostToDevice, touch(ctx)));
     }
-    T.mesh = tab[0] ? ctx->mo_table[0] : nullptr; T.n_mesh = tab[0] ? tab[0]->count : 0;
-    T.sphere = tab[1] ? ctx->mo_table[1] : nullptr; T.n_sphere = tab[1] ? tab[1]->count : 0;
+    T.mesh = tab[0] ? (const float4*)ctx->mo_table[0].get() : nullptr; T.n_mesh = tab[0] ? tab[0]->count : 0;
+    T.sphere = tab[1] ? (const float4*)ctx->mo_table[1].get() : nullptr; T.n_sphere = tab[1] ? tab[1]->count : 0;
     T.moved_max_history = Mo.moved_max_history;
     for (int k = kInputs; k < kImages; k++) if (t[k]) t[k]->other_writes = true;
     URT_HIP(ctx, launch_reproject_objects(I, S, T, touch(ctx)));
@@ -439,8 +414,8 @@ int urt_select_pixels(urt_context* ctx, urt_handle count, float below, void* d_p
   const size_t n_texels = (size_t)c->w * (size_t)c->h;
   if (int rc = select_scratch(ctx, "select_pixels: scratch allocation", n_texels)) return rc;
   { int rc = flush_pending(ctx); if (rc) return rc; }
-  URT_HIP(ctx, launch_select_count(c->dev, n_texels, below, ctx->rs_counts, touch(ctx)));   // the device pointer after the flush (a Result texture may be renamed)
-  URT_HIP(ctx, launch_select_write(c->dev, c->w, n_texels, below, ctx->rs_counts, (int2*)d_pixels, capacity, touch(ctx)));
+  URT_HIP(ctx, launch_select_count(c->dev, n_texels, below, ctx->rs_counts.get(), touch(ctx)));   // the device pointer after the flush (a Result texture may be renamed)
+  URT_HIP(ctx, launch_select_write(c->dev, c->w, n_texels, below, ctx->rs_counts.get(), (int2*)d_pixels, capacity, touch(ctx)));
   int total = 0;
   if (int rc = select_total(ctx, n_texels, &total)) return rc;
   *out_n = total;
@@ -496,24 +471,24 @@ int urt_resample_below(urt_context* ctx, urt_handle dst, urt_handle count, float
   const size_t n_texels = (size_t)width * (size_t)height;
   if (int rc = select_scratch(ctx, "resample_below: scratch allocation", n_texels)) return rc;
   { int rc = flush_pending(ctx); if (rc) return rc; }
-  URT_HIP(ctx, launch_select_count(t[1]->dev, n_texels, below, ctx->rs_counts, touch(ctx)));
+  URT_HIP(ctx, launch_select_count(t[1]->dev, n_texels, below, ctx->rs_counts.get(), touch(ctx)));
   int n = 0;
   if (int rc = select_total(ctx, n_texels, &n)) return rc;
   if (out_n) *out_n = n;
   if (n == 0) return URT_OK;
-  if (int rc = grow_scratch(ctx, &ctx->rs_pixels, &ctx->rs_pixels_cap, (size_t)n, (size_t)n * sizeof(urt_PathPixel), "resample_below: scratch allocation")) return rc;
-  if (int rc = grow_scratch(ctx, (void**)&ctx->rs_samples, &ctx->rs_samples_cap, (size_t)n, (size_t)n * sizeof(float4), "resample_below: scratch allocation")) return rc;
-  URT_HIP(ctx, launch_select_write(t[1]->dev, width, n_texels, below, ctx->rs_counts, (int2*)ctx->rs_pixels, n, touch(ctx)));
+  if (int rc = reserve(ctx, ctx->rs_pixels, (size_t)n, "resample_below: scratch allocation", ctx->stream)) return rc;
+  if (int rc = reserve(ctx, ctx->rs_samples, (size_t)n, "resample_below: scratch allocation", ctx->stream)) return rc;
+  URT_HIP(ctx, launch_select_write(t[1]->dev, width, n_texels, below, ctx->rs_counts.get(), (int2*)ctx->rs_pixels.get(), n, touch(ctx)));
   DevScene S; RadianceCamera C; RadianceBatch B;
-  if (int rc = radiance_prepare(ctx, ctx->rs_pixels, n, samples, bounces, ctx->rs_samples, URT_RADIANCE_PIXELS, false, &S, &C, &B)) return rc;
-  B.in = ctx->rs_pixels; B.out = ctx->rs_samples;
+  if (int rc = radiance_prepare(ctx, ctx->rs_pixels.get(), n, samples, bounces, ctx->rs_samples.get(), URT_RADIANCE_PIXELS, false, &S, &C, &B)) return rc;
+  B.in = ctx->rs_pixels.get(); B.out = ctx->rs_samples.get();
   URT_HIP(ctx, launch_radiance(S, ctx->scene.tlas_stack, ctx->scene.blas_stack + ctx->opt.stack_pad, C, B, touch(ctx)));
   Texture* d = find_texture(ctx, dst);
   Texture* c = find_texture(ctx, count);
   if (!d || !c) return fail(ctx, URT_ERR_INVALID_HANDLE, "resample_below: a texture was released during the call");
   d->other_writes = true;
   c->other_writes = true;
-  URT_HIP(ctx, launch_blend_samples((const int2*)ctx->rs_pixels, ctx->rs_samples, n, weight, d->dev, c->dev, width, height, max_history, touch(ctx)));
+  URT_HIP(ctx, launch_blend_samples((const int2*)ctx->rs_pixels.get(), ctx->rs_samples.get(), n, weight, d->dev, c->dev, width, height, max_history, touch(ctx)));
   return URT_OK;
   URT_GUARD_END(ctx)
 }

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include <vector>
+#include "owned.h"
 
 namespace urtd {
 
@@ -22,13 +23,13 @@ struct LbvhInput {
 };
 
 struct LbvhOutput {
-  // device arrays in the layouts of urt_device.h; owned by the caller after a successful build (hipFree each of `allocs`)
+  // device arrays in the layouts of urt_device.h; owned by `allocs`, which the caller takes over after a successful build
   float4* nodes = nullptr; int n_nodes = 0;
   float4* tri_verts = nullptr; float4* tri_norms = nullptr; int n_tris = 0;
   int32_t* mesh_root = nullptr;                                 // device, one per MeshObject
   std::vector<int32_t> h_mesh_root;                             // the same on the host
   int max_depth = 0;                                            // deepest level (root = 1, leaves included)
-  std::vector<void*> allocs;
+  std::vector<DeviceBuf<char>> allocs;
 };
 
 // Builds one LBVH per MeshObject on the GPU (Morton sort + Karras hierarchy + bottom-up fit), in the node / triangle-record

@@ -729,16 +729,14 @@ namespace urtd {
     hipError_t e__ = (expr);                                                                        \
     if (e__ != hipSuccess) {                                                                        \
       err = std::string(#expr) + ": " + hipGetErrorString(e__);                                     \
-      if (temp) (void)hipFree(temp);                                                                \
-      for (void* p : out.allocs) (void)hipFree(p);                                                  \
-      out = LbvhOutput();                                                                           \
+      out = LbvhOutput();   /* gives back what was allocated; `temp` goes with the scope */          \
       return e__ == hipErrorOutOfMemory ? URT_ERR_OUT_OF_MEMORY : URT_ERR_HIP;                      \
     }                                                                                               \
   } while (0)
 
 int lbvh_build(const LbvhInput& in, hipStream_t st, LbvhOutput& out, std::string& err) {
   out = LbvhOutput();
-  void* temp = nullptr;
+  DeviceBuf<char> temp;
   const int nm = in.n_meshes;
   out.h_mesh_root.assign((size_t)nm, kEmptyMeshRoot);
   std::vector<int32_t> first((size_t)nm + 1, 0);
@@ -756,8 +754,9 @@ int lbvh_build(const LbvhInput& in, hipStream_t st, LbvhOutput& out, std::string
   out.n_tris = T;
   // outputs
   auto alloc_out = [&](void** p, size_t bytes) -> hipError_t {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e == hipSuccess) out.allocs.push_back(*p);
+    out.allocs.emplace_back();
+    hipError_t e = out.allocs.back().alloc(bytes, 16);
+    *p = out.allocs.back().get();
     return e;
   };
   LBVH_HIP(alloc_out((void**)&out.mesh_root, sizeof(int32_t) * (size_t)std::max(nm, 1)));
@@ -806,8 +805,8 @@ int lbvh_build(const LbvhInput& in, hipStream_t st, LbvhOutput& out, std::string
   }
   const size_t o_tdq0 = in.depth_budget ? carve(sizeof(int4) * (size_t)T) : 0, o_tdq1 = in.depth_budget ? carve(sizeof(int4) * (size_t)T) : 0;
   const size_t o_sort = carve(sort_bytes), o_scan = carve(scan_bytes);
-  LBVH_HIP(hipMalloc(&temp, at));
-  char* base = (char*)temp;
+  LBVH_HIP(temp.alloc(at));
+  char* base = temp.get();
 
   Dev D{};
   D.mesh_objects = in.mesh_objects; D.n_meshes = nm;
@@ -867,7 +866,7 @@ int lbvh_build(const LbvhInput& in, hipStream_t st, LbvhOutput& out, std::string
     size_t n = (size_t)sc[3], words = (size_t)sc[2];
     int src = 0, level_base = 0;
     while (n > 0) {
-      if (n > LN || words > bin_words || sah_levels >= 120) { err = "GPU SAH builder: level " + std::to_string(sah_levels) + " does not fit its buffers"; if (temp) (void)hipFree(temp); for (void* q : out.allocs) (void)hipFree(q); out = LbvhOutput(); return URT_ERR_SCENE; }
+      if (n > LN || words > bin_words || sah_levels >= 120) { err = "GPU SAH builder: level " + std::to_string(sah_levels) + " does not fit its buffers"; out = LbvhOutput(); return URT_ERR_SCENE; }
       hipLaunchKernelGGL(k_sah_bins_init, blocks(words, 256), dim3(256), 0, st, D, (int)words);
       hipLaunchKernelGGL(k_sah_bin, dim3(gb), dim3(256), 0, st, D, src);
       hipLaunchKernelGGL(k_sah_eval, blocks(n, 64), dim3(64), 0, st, D, src, (int)n, sah_levels);
@@ -922,12 +921,9 @@ int lbvh_build(const LbvhInput& in, hipStream_t st, LbvhOutput& out, std::string
   LBVH_HIP(hipMemcpyAsync(&last_flag, D.flag + (T - 1), sizeof(int), hipMemcpyDeviceToHost, st));
   LBVH_HIP(hipMemcpyAsync(out.h_mesh_root.data(), out.mesh_root, sizeof(int32_t) * (size_t)nm, hipMemcpyDeviceToHost, st));
   LBVH_HIP(hipStreamSynchronize(st));
-  (void)hipFree(temp);
-  temp = nullptr;
   if (scalars[0] != 0) {
     int at_slot = scalars[0] - 1;
     err = "_Indices[" + std::to_string(at_slot) + "] is outside _Vertices/_Normals";
-    for (void* p : out.allocs) (void)hipFree(p);
     out = LbvhOutput();
     return URT_ERR_SCENE;
   }

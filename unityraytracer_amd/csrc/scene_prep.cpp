@@ -15,24 +15,29 @@ namespace urtd {
 
 void free_scene(urt_context* ctx) {
   if (!ctx->scene.scene_allocs.empty()) (void)hipStreamSynchronize(touch(ctx));   // queued kernels may still read them
-  for (void* p : ctx->scene.scene_allocs) (void)hipFree(p);
   ctx->scene = urt_context::Scene{};
   ctx->slab_oom_stride = 0;                                // device memory came back: the next batch may try the Result slots again
 }
 
 namespace {
 
+// `bytes` (at least 16) of device memory that lives as long as the prepared scene
+template <typename P>
+int scene_alloc(urt_context* ctx, P** out, size_t bytes) {
+  DeviceBuf<char>& b = ctx->scene.scene_allocs.emplace_back();
+  URT_HIP(ctx, b.alloc(bytes, 16));
+  *out = (P*)b.get();
+  return URT_OK;
+}
+
 template <typename T>
 int upload(urt_context* ctx, const std::vector<T>& v, const float4** out) {
   *out = nullptr;
   if (v.empty()) return URT_OK;
-  void* d = nullptr;
-  URT_HIP(ctx, hipMalloc(&d, v.size() * sizeof(T)));
-  ctx->scene.scene_allocs.push_back(d);
+  if (int rc = scene_alloc(ctx, out, v.size() * sizeof(T))) return rc;
   // synchronous on purpose: `v` is a short-lived staging vector, and a pageable-memory hipMemcpyAsync may
   // still be reading it after this function returns
-  URT_HIP(ctx, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = (const float4*)d;
+  URT_HIP(ctx, hipMemcpy(const_cast<float4*>(*out), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   return URT_OK;
 }
 
@@ -212,10 +217,8 @@ int verify_cull_flags(urt_context* ctx, const std::vector<int32_t>& words, const
   if (!any || S.n_mesh_tlas <= 0 || !S.mesh_tlas) return URT_OK;
   S.cull_any = 1;
   if (mesh_leaf.size() > ctx->scene.cap_mesh_leaf || !ctx->scene.d_mesh_leaf) {
-    void* p = nullptr;
-    URT_HIP(ctx, hipMalloc(&p, std::max<size_t>(16, mesh_leaf.size() * sizeof(int32_t))));
-    ctx->scene.scene_allocs.push_back(p);
-    ctx->scene.d_mesh_leaf = (int32_t*)p; ctx->scene.cap_mesh_leaf = mesh_leaf.size();
+    if (int rc = scene_alloc(ctx, &ctx->scene.d_mesh_leaf, mesh_leaf.size() * sizeof(int32_t))) return rc;
+    ctx->scene.cap_mesh_leaf = mesh_leaf.size();
   }
   URT_HIP(ctx, hipMemcpy(ctx->scene.d_mesh_leaf, mesh_leaf.data(), mesh_leaf.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   int* mask = ctx->scene.walk_f4 > 0 ? (int*)const_cast<float4*>(S.mesh_tlas + 2 * (size_t)S.n_mesh_tlas) + 6 : nullptr;      // header word [6] of the walk table behind the heap
@@ -431,17 +434,17 @@ int prepare_scene(urt_context* ctx) {
     ctx->last_builder = builder;
     if (builder >= 1) {
       // device copies of the buffers exactly as SetData delivered them; the whole build runs on the GPU (csrc/lbvh.hip)
-      void* raw = nullptr;
+      DeviceBuf<char> raw;
       size_t b_mo = ((size_t)n_meshes * URT_STRIDE_MESHOBJECT + 255) & ~(size_t)255;
       size_t b_v = bv ? (((size_t)bv->count * 12 + 255) & ~(size_t)255) : 0, b_i = bi ? (((size_t)bi->count * 4 + 255) & ~(size_t)255) : 0;
       size_t b_n = bn ? (((size_t)bn->count * 12 + 255) & ~(size_t)255) : 0;
-      URT_HIP(ctx, hipMalloc(&raw, b_mo + b_v + b_i + b_n + 256));
-      char* rb = (char*)raw;
+      URT_HIP(ctx, raw.alloc(b_mo + b_v + b_i + b_n + 256));
+      char* rb = raw.get();
       hipError_t e = hipMemcpy(rb, bm->host.data(), (size_t)n_meshes * URT_STRIDE_MESHOBJECT, hipMemcpyHostToDevice);
       if (e == hipSuccess && bv) e = hipMemcpy(rb + b_mo, bv->host.data(), (size_t)bv->count * 12, hipMemcpyHostToDevice);
       if (e == hipSuccess && bi) e = hipMemcpy(rb + b_mo + b_v, bi->host.data(), (size_t)bi->count * 4, hipMemcpyHostToDevice);
       if (e == hipSuccess && bn) e = hipMemcpy(rb + b_mo + b_v + b_i, bn->host.data(), (size_t)bn->count * 12, hipMemcpyHostToDevice);
-      if (e != hipSuccess) { (void)hipFree(raw); return fail(ctx, URT_ERR_HIP, std::string("scene upload: ") + hipGetErrorString(e)); }
+      if (e != hipSuccess) return fail(ctx, URT_ERR_HIP, std::string("scene upload: ") + hipGetErrorString(e));
       LbvhInput in;
       in.mesh_objects = (const uint8_t*)rb; in.n_meshes = n_meshes;
       in.vertices = bv ? (const float*)(rb + b_mo) : nullptr; in.n_vertices = bv ? bv->count : 0;
@@ -451,10 +454,10 @@ int prepare_scene(urt_context* ctx) {
       LbvhOutput o;
       std::string err;
       rc = lbvh_build(in, touch(ctx), o, err);
-      if (rc) { (void)hipFree(raw); return fail(ctx, rc, err); }
-      ctx->scene.scene_allocs.push_back(raw);                     // _Vertices / _Indices stay resident: a moved MeshObject is refitted from them
+      if (rc) return fail(ctx, rc, err);
+      ctx->scene.scene_allocs.push_back(std::move(raw));                 // _Vertices / _Indices stay resident: a moved MeshObject is refitted from them
       ctx->scene.refit.vertices = in.vertices; ctx->scene.refit.indices = in.indices;
-      for (void* a : o.allocs) ctx->scene.scene_allocs.push_back(a);
+      for (DeviceBuf<char>& a : o.allocs) ctx->scene.scene_allocs.push_back(std::move(a));
       S.mesh_root = o.mesh_root; S.blas_nodes = o.nodes; S.tri_verts = o.tri_verts; S.tri_norms = o.tri_norms;
       mesh_root_host = o.h_mesh_root; blas_max_depth = o.max_depth; n_blas_nodes = (size_t)o.n_nodes; n_tris = (size_t)o.n_tris;
     } else {
@@ -501,16 +504,10 @@ int prepare_scene(urt_context* ctx) {
   if ((size_t)(ctx->scene.tlas_stack + ctx->scene.blas_stack) * 64 * 4 * sizeof(int) > 150 * 1024)   // 4-wave workgroup; a CU has 160 KiB
     return fail(ctx, URT_ERR_SCENE, "traversal stacks exceed the LDS of a compute unit");
   if (n_blas_nodes > 0) {                                     // the copy of the nodes the trace kernels traverse: child boxes as (centre, half extent)
-    void* c = nullptr;
-    URT_HIP(ctx, hipMalloc(&c, 4 * n_blas_nodes * sizeof(float4)));
-    ctx->scene.scene_allocs.push_back(c);
-    ctx->scene.cbuf = (float4*)c;
+    if ((rc = scene_alloc(ctx, &ctx->scene.cbuf, 4 * n_blas_nodes * sizeof(float4)))) return rc;
   }
   if (ctx->opt.qnodes != 0 && n_blas_nodes > 0) {             // 32-byte quantized nodes for the traversal loop (csrc/qnodes.hip)
-    void* q = nullptr;
-    URT_HIP(ctx, hipMalloc(&q, (2 + 2 * n_blas_nodes) * sizeof(float4)));
-    ctx->scene.scene_allocs.push_back(q);
-    ctx->scene.qbuf = (float4*)q;
+    if ((rc = scene_alloc(ctx, &ctx->scene.qbuf, (2 + 2 * n_blas_nodes) * sizeof(float4)))) return rc;
   }
   if ((rc = rederive_nodes(ctx))) return rc;
   // what a later in-place update needs (prepare_incremental): the records this scene was prepared from, and — when it has triangle
@@ -519,27 +516,22 @@ int prepare_scene(urt_context* ctx) {
   ctx->scene.h_mesh_root = mesh_root_host; ctx->scene.h_small_first = small_first;
   if (ctx->opt.refit && n_meshes > 0 && n_tris > 0 && bv && bi) {
     urt_context::Scene::RefitAux& R = ctx->scene.refit;
-    auto dev_alloc = [&](void** ptr, size_t bytes) -> int {
-      URT_HIP(ctx, hipMalloc(ptr, std::max<size_t>(bytes, 16)));
-      ctx->scene.scene_allocs.push_back(*ptr);
-      return URT_OK;
-    };
     if (!R.vertices) {                                        // (the GPU builder has left its copies in place)
-      void *dv = nullptr, *di = nullptr;
-      if ((rc = dev_alloc(&dv, (size_t)bv->count * 12))) return rc;
-      if ((rc = dev_alloc(&di, (size_t)bi->count * 4))) return rc;
+      float* dv = nullptr; int32_t* di = nullptr;
+      if ((rc = scene_alloc(ctx, &dv, (size_t)bv->count * 12))) return rc;
+      if ((rc = scene_alloc(ctx, &di, (size_t)bi->count * 4))) return rc;
       URT_HIP(ctx, hipMemcpy(dv, bv->host.data(), (size_t)bv->count * 12, hipMemcpyHostToDevice));
       URT_HIP(ctx, hipMemcpy(di, bi->host.data(), (size_t)bi->count * 4, hipMemcpyHostToDevice));
-      R.vertices = (const float*)dv; R.indices = (const int32_t*)di;
+      R.vertices = dv; R.indices = di;
     }
     size_t nn = std::max<size_t>(1, n_blas_nodes);
-    if ((rc = dev_alloc((void**)&R.parent, nn * 4))) return rc;
-    if ((rc = dev_alloc((void**)&R.node_mesh, nn * 4))) return rc;
-    if ((rc = dev_alloc((void**)&R.cbox, nn * 64))) return rc;
-    if ((rc = dev_alloc((void**)&R.depth, nn * 4))) return rc;
-    if ((rc = dev_alloc((void**)&R.ext, (size_t)n_meshes * 4))) return rc;
-    if ((rc = dev_alloc((void**)&R.matrices, (size_t)n_meshes * 64))) return rc;
-    if ((rc = dev_alloc((void**)&R.moved, (size_t)n_meshes * 4))) return rc;
+    if ((rc = scene_alloc(ctx, &R.parent, nn * 4))) return rc;
+    if ((rc = scene_alloc(ctx, &R.node_mesh, nn * 4))) return rc;
+    if ((rc = scene_alloc(ctx, &R.cbox, nn * 64))) return rc;
+    if ((rc = scene_alloc(ctx, &R.depth, nn * 4))) return rc;
+    if ((rc = scene_alloc(ctx, &R.ext, (size_t)n_meshes * 4))) return rc;
+    if ((rc = scene_alloc(ctx, &R.matrices, (size_t)n_meshes * 64))) return rc;
+    if ((rc = scene_alloc(ctx, &R.moved, (size_t)n_meshes * 4))) return rc;
     URT_HIP(ctx, refit_prepare(S.blas_nodes, (int)n_blas_nodes, S.tri_verts, R.parent, R.node_mesh, R.depth, touch(ctx)));
     R.ready = true;
   }

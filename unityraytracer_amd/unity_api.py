@@ -955,6 +955,16 @@ class Graphics:
             ctx.check(ctx.lib.urt_blit_add(ctx._h, source.handle, dest.handle, mat.floats["_Sample"]))
 
 
+def live_resources() -> dict:
+    """What the library holds right now, process-wide (urt_debug_live_resources): device bytes, pinned host bytes, events, streams."""
+    lib = _lib.load()
+    out = (C.c_uint64 * 4)()
+    rc = lib.urt_debug_live_resources(out)
+    if rc != 0:
+        raise UrtError(rc, lib.urt_last_error(None).decode())
+    return dict(zip(("device_bytes", "pinned_bytes", "events", "streams"), (int(v) for v in out)))
+
+
 def debug_build_blas(mesh_objects: np.ndarray, vertices: np.ndarray, indices: np.ndarray):
     """Run the library's triangle-BVH builder on host arrays (no GPU needed) and return
     (nodes[n,16] f32, tri_index[n_tris] i32, mesh_root[n_meshes] i32, mesh_first_tri, max_depth)."""
