@@ -315,6 +315,44 @@ def test_large_lds_launch(ctx, shaped):
         ctx.set_option("radiance_persist", -1)
 
 
+def same_bytes(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def test_large_lds_launch_of_ray_queries(ctx, shaped):
+    """stack_pad reaches k_query's launch too: 257 rays = one full workgroup and a ragged one, closest hit and any hit."""
+    m = shaped[0]
+    rebind(ctx, m)
+    O, D = camera_rays(m.scene, 40, 24)
+    pick = np.random.default_rng(7).permutation(40 * 24)[:257]       # rays all over the image (the fixture's own 257 all end on the ground)
+    O, D = O.reshape(-1, 3)[pick].copy(), D.reshape(-1, 3)[pick].copy()
+    ref_c, ref_a = ctx.ray_query(O, D), ctx.ray_query(O, D, any_hit=True)
+    assert len(np.unique(ref_c["kind"])) == 4 and 0 < ref_a.sum() < len(ref_a)      # misses, the ground, spheres and triangles
+    try:
+        ctx.set_option("stack_pad", 96)                              # > 64 KiB of stacks per workgroup
+        assert same_bytes(ctx.ray_query(O, D), ref_c)
+        assert same_bytes(ctx.ray_query(O, D, any_hit=True), ref_a)
+    finally:
+        ctx.set_option("stack_pad", 0)
+
+
+def test_large_lds_launch_of_feature_buffers(ctx, shaped):
+    """stack_pad reaches k_aov's launch too: 24 x 17 has ragged tiles on both edges; both camera-ray forms."""
+    rebind(ctx, shaped[0])
+    ref = [ctx.render_aov_arrays(24, 17, frame_ray=fr) for fr in (False, True)]
+    assert len(np.unique(ref[0]["kind"])) == 4 and not same_bytes(ref[0]["position"], ref[1]["position"])
+    try:
+        ctx.set_option("stack_pad", 96)
+        for fr in (False, True):
+            got = ctx.render_aov_arrays(24, 17, frame_ray=fr)
+            assert got.keys() == ref[fr].keys()
+            for k in got:
+                assert same_bytes(got[k], ref[fr][k]), (fr, k)
+    finally:
+        ctx.set_option("stack_pad", 0)
+
+
 def test_argument_errors_write_nothing(gpu_ctx):
     import torch
     w, h = 40, 24

@@ -280,6 +280,19 @@ inline const Buffer* bound_buffer(urt_context* ctx, int slot) {
   return &it->second;
 }
 
+// The camera uniforms bound now (RS:5-7, 16), as the kernels that draw camera rays outside a FrameParams take them
+inline FrameUniforms bound_camera(const urt_context* ctx) {
+  FrameUniforms C{};
+  std::memcpy(C.c2w, ctx->c2w, sizeof C.c2w);
+  std::memcpy(C.invp, ctx->invp, sizeof C.invp);
+  C.pixel_off_x = ctx->pixel_off[0]; C.pixel_off_y = ctx->pixel_off[1];
+  C.seed = ctx->seed;
+  return C;
+}
+
+// LDS entries per lane of the prepared scene's two traversal stacks, for every kernel that traces one ray per lane; stack_pad is unused room
+inline LaneStackSize lane_stack_size(const urt_context* ctx) { return {ctx->scene.tlas_stack, ctx->scene.blas_stack + ctx->opt.stack_pad}; }
+
 inline int heap_levels(int n) { int l = 0; while (n > 0) { l++; n >>= 1; } return l; }   // floor(log2 n) + 1
 
 // max_history of urt_reproject / urt_blit_add_history: 0 (unlimited) or >= 1

@@ -462,7 +462,7 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
   P.tiles_x = (P.region_w + 7) / 8;
   P.first_group_row = first_row; P.row_stride = row_stride;
   P.n_strips = strip_count((P.region_h + 7) / 8, first_row, row_stride);      // rows of the dispatched region
-  P.tlas_stack = ctx->scene.tlas_stack; P.blas_stack = ctx->scene.blas_stack + ctx->opt.stack_pad; P.watchdog_steps = ctx->scene.watchdog_steps;
+  P.tlas_stack = lane_stack_size(ctx).tlas; P.blas_stack = lane_stack_size(ctx).blas; P.watchdog_steps = ctx->scene.watchdog_steps;
   P.block_threads = ctx->opt.block_threads; P.xcd_run = ctx->opt.xcd_run; P.tile_order = ctx->opt.tile_order >= 0 ? ctx->opt.tile_order : (S.n_meshes == 0 ? 1 : 0); P.refill_min = ctx->opt.refill_min;
   // lanes parked at a triangle BVH before the traversal phase runs: 16 with one mesh (C3 -2 %, C3D -6 % against 28), 24 when rays walk
   // several (C4, C5 -1 %) — re-measured after the work distribution became local (profiles/r02_logs/r2_blas_min.log)
@@ -500,10 +500,7 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
     P.pool_inloop = ctx->opt.serve_refill;
     int front_mode = configure_sched(ctx, S, P, top_in_front);
     P.shade_split = ctx->opt.shade_split != 0;
-    FrameUniforms fu{};
-    std::memcpy(fu.c2w, P.c2w, sizeof fu.c2w);
-    std::memcpy(fu.invp, P.invp, sizeof fu.invp);
-    fu.pixel_off_x = P.pixel_off_x; fu.pixel_off_y = P.pixel_off_y; fu.seed = P.seed;
+    const FrameUniforms fu = bound_camera(ctx);                   // the uniforms P's head holds
     // May this dispatch be renamed to a fresh slab slot?  Its unwritten pixels must read as before: none (full cover), or
     // still the zeros of creation (only dispatches of this same region ever wrote the image).
     bool same_region = res->n_regions == 1 && std::memcmp(res->rg, region, sizeof region) == 0;

@@ -12,80 +12,17 @@
 using namespace urt;
 using namespace urtd;
 
-#include "trace_device.h"     // HitRec, slab tests, triangle / sphere / leaf tests, triangle-BVH node steps, intersect_mesh
+#include "camera_device.h"    // jitter_uv, camera_ray_uv: the camera ray of a pixel
+#include "trace_device.h"     // HitRec, slab tests, triangle / sphere / leaf tests, triangle-BVH node steps, intersect_mesh, trace_ray, lane_stacks, st_nt
 #include "sky_device.h"       // sample_sky, sky_radiance: the sky lookup of Shade's miss branch
 #include "shade_device.h"     // sample_hemisphere, shade_surface, shade_sky, shade: Shade RS:386-428
 
 namespace {
 
-// ---------------------------------------------------------------------------------------------------
-// Trace — RS:364-383: ground plane, then the mesh object BVH, then the sphere BVH.
-// tl / bl: this lane's LDS stacks for the object-level and the triangle-level traversals.
-// ---------------------------------------------------------------------------------------------------
+// Trace — RS:364-383 — of the frame kernels that trace one ray per lane (modes 0 - 2): trace_device.h trace_ray, unbounded
 template <bool COUNT>
 __device__ __forceinline__ HitRec trace(const DevScene& S, v3 o, v3 d, int* tl, int* bl, LocalCounters& lc) {
-  lc.rays++;
-  HitRec best; best.t = URT_INF; best.kid = 0; best.u = 0; best.v = 0;
-  // IntersectGroundPlane RS:156-172
-  {
-    float t = -o.y / d.y;
-    if (t > 0 && t < best.t) { best.t = t; best.kid = 1; }
-  }
-  // one reciprocal per axis for the object-level slab test (normative form of RS:282-283)
-  v3 rcp = mk3(1.0f / (d.x + kEPSILON), 1.0f / (d.y + kEPSILON), 1.0f / (d.z + kEPSILON));
-  // IntersectMeshBVH RS:294-326 (`tests` is never reset: once a leaf was reached, every later popped
-  // node has its object intersected, A.5; object ids < 0 or out of range are skipped, not read)
-  if (S.n_meshes > 0) {
-    const float t_ground = best.t;                              // what the object-level cull compares with (urt_math.h tlas_cull)
-    int check = 1; tl[0] = 0; bool seen = false;
-    while (check > 0) {
-      check--;
-      int bi = tl[check * 64];
-      bool hit = false, culled = false; int index = -1;
-      if (bi < S.n_mesh_tlas) {
-        if (COUNT) lc.tlas_nodes++;
-        float4 a = S.mesh_tlas[2 * bi], b = S.mesh_tlas[2 * bi + 1];
-        index = as_int(a.w);
-        float t_min, t_max;
-        hit = tlas_slab_t(a, b, o, rcp, t_min, t_max);
-        culled = leaf_culled(b, t_min, t_max, t_ground);
-      }
-      if (hit) {
-        if (index < 0) { tl[check * 64] = bi * 2 + 1; check++; tl[check * 64] = bi * 2 + 2; check++; }
-        else seen = true;
-      }
-      if (seen && !culled && index >= 0 && index < S.n_meshes) intersect_mesh<COUNT>(S, S.mesh_root[index], o, d, best, bl, lc);
-    }
-  }
-  // IntersectSphereBVH RS:329-361
-  if (S.n_spheres > 0) {
-    int check = 1; tl[0] = 0; bool seen = false;
-    while (check > 0) {
-      check--;
-      int bi = tl[check * 64];
-      bool hit = false; int index = -1;
-      if (bi < S.n_sphere_tlas) {
-        if (COUNT) lc.tlas_nodes++;
-        float4 a = S.sphere_tlas[2 * bi], b = S.sphere_tlas[2 * bi + 1];
-        index = as_int(a.w);
-        hit = tlas_slab(a, b, o, rcp);
-      }
-      if (hit) {
-        if (index < 0) { tl[check * 64] = bi * 2 + 1; check++; tl[check * 64] = bi * 2 + 2; check++; }
-        else seen = true;
-      }
-      if (seen && index >= 0 && index < S.n_spheres) intersect_sphere<COUNT>(S, index, o, d, best, lc);
-    }
-  }
-  return best;
-}
-
-// The result image is written once per pixel and not read by this kernel: stored non-temporally so that it does not push
-// BVH lines out of the L2 (measured -1 %; the same hint on the sky's texel loads costs +3 % and is not used).
-typedef float f4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void st_result(float4* p, float4 v) {
-  f4v q = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(q, (f4v*)p);
+  return trace_ray<COUNT, false>(S, o, d, URT_INF, tl, bl, lc);
 }
 
 // Cold per-pixel uniforms (the two camera matrices, 128 B) are read from the kernel-argument segment AT USE through a
@@ -98,28 +35,15 @@ __device__ __forceinline__ kfloatp kernarg_floats(unsigned byte_offset) {
   asm volatile("" : "+s"(p));                      // opaque to LICM: the loads below stay where they are written
   return (kfloatp)p;
 }
-__device__ __forceinline__ v3 mul_m4_k(kfloatp m, float x, float y, float z, float w) {   // urt::mul_m4 on a kernarg matrix
-  v3 r;
-  r.x = f_fma(m[12], w, f_fma(m[8], z, f_fma(m[4], y, m[0] * x)));
-  r.y = f_fma(m[13], w, f_fma(m[9], z, f_fma(m[5], y, m[1] * x)));
-  r.z = f_fma(m[14], w, f_fma(m[10], z, f_fma(m[6], y, m[2] * x)));
-  return r;
-}
 
-// CreateCameraRay RS:142-153 with the uv of RS:448-449.  p_off = byte offset of the FrameParams argument in the kernarg segment.
+// The camera ray of pixel (x, y), camera_device.h.  P_OFF = byte offset of the FrameParams argument in the kernarg segment.
 template <unsigned P_OFF>
 __device__ __forceinline__ void camera_ray(const FrameParams& P, int x, int y, float& seed, v3& o, v3& d) {
-  float px = (float)x, py = (float)y;
-  float r0 = rand_next(seed, px, py);
-  float r1 = rand_next(seed, px, py);
-  float u = (px + r0 + P.pixel_off_x) / (float)P.width * 2.0f - 1.0f;
-  float v = (py + r1 + P.pixel_off_y) / (float)P.height * 2.0f - 1.0f;
+  float u, v;
+  jitter_uv(seed, (float)x, (float)y, P.pixel_off_x, P.pixel_off_y, P.width, P.height, u, v);
   kfloatp c2w = kernarg_floats(P_OFF + (unsigned)__builtin_offsetof(FrameParams, c2w));
   kfloatp invp = kernarg_floats(P_OFF + (unsigned)__builtin_offsetof(FrameParams, invp));
-  o = mul_m4_k(c2w, 0.0f, 0.0f, 0.0f, 1.0f);
-  v3 dir = mul_m4_k(invp, u, v, 0.0f, 1.0f);
-  dir = mul_m4_k(c2w, dir.x, dir.y, dir.z, 0.0f);
-  d = normalize(dir);
+  camera_ray_uv(c2w, invp, u, v, o, d);
 }
 // The same for a batched launch (modes 3, 5): the uniforms of the path's frame come from the launch's frame table in device
 // memory, read with scalar loads (table pointer and frame index are wave-uniform).  `f` must be wave-uniform.
@@ -129,13 +53,9 @@ __device__ __forceinline__ void camera_ray_frame(const FrameUniforms* T, int f, 
   float px = (float)x, py = (float)y;
   float r0 = rand_next(seed, px, py);
   float r1 = rand_next(seed, px, py);
-  float u = (px + r0 + q[32]) / (float)P.width * 2.0f - 1.0f;
-  float v = (py + r1 + q[33]) / (float)P.height * 2.0f - 1.0f;
-  kfloatp c2w = q, invp = q + 16;
-  o = mul_m4_k(c2w, 0.0f, 0.0f, 0.0f, 1.0f);
-  v3 dir = mul_m4_k(invp, u, v, 0.0f, 1.0f);
-  dir = mul_m4_k(c2w, dir.x, dir.y, dir.z, 0.0f);
-  d = normalize(dir);
+  float u = axis_uv(px + r0 + q[32], P.width);     // jitter_uv written out: called through it, the table entry's scalar loads land elsewhere and k_sched's bytes change
+  float v = axis_uv(py + r1 + q[33], P.height);
+  camera_ray_uv(q, q + 16, u, v, o, d);
 }
 static_assert(__builtin_offsetof(FrameUniforms, invp) == 64 && __builtin_offsetof(FrameUniforms, pixel_off_x) == 128 &&
               __builtin_offsetof(FrameUniforms, seed) == 136, "camera_ray_frame indexes the table as floats");
@@ -206,13 +126,7 @@ __device__ __forceinline__ void flush_counters(const LocalCounters& lc, DevCount
   }
 }
 
-__device__ __forceinline__ void lane_stacks(const FrameParams& P, int*& tl, int*& bl) {
-  extern __shared__ int lds[];
-  int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  int per_wave = (P.tlas_stack + P.blas_stack) * 64;
-  tl = lds + wave * per_wave + lane;
-  bl = tl + P.tlas_stack * 64;
-}
+__device__ __forceinline__ void lane_stacks(const FrameParams& P, int*& tl, int*& bl) { lane_stacks(P.tlas_stack, P.blas_stack, tl, bl); }
 
 // Work distribution of the persistent kernels.  The frame is a sequence of pixel slots in tile order (64 consecutive slots
 // = one 8x8 tile).  One shared counter would be hit ~40,000 times per 1080p frame, and same-address atomics serialise at

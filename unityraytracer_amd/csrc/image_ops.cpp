@@ -127,7 +127,7 @@ int urt_ray_query(urt_context* ctx, const urt_Ray* rays, int n, void* out, int f
   if (int r = reserve(ctx, ctx->q_out, (size_t)n, "ray query: scratch allocation", ctx->stream)) return r;
   const size_t out_bytes = (size_t)n * (flags == URT_QUERY_ANY ? sizeof(int32_t) : sizeof(urt_RayHit));
   URT_HIP(ctx, hipMemcpyAsync(ctx->q_rays.get(), rays, (size_t)n * sizeof(urt_Ray), hipMemcpyHostToDevice, ctx->stream));
-  URT_HIP(ctx, launch_query(ctx->scene.ds, ctx->scene.tlas_stack, ctx->scene.blas_stack, (const float4*)ctx->q_rays.get(), n, ctx->q_out.get(), flags == URT_QUERY_ANY, ctx->stream));
+  URT_HIP(ctx, launch_query(ctx->scene.ds, lane_stack_size(ctx), (const float4*)ctx->q_rays.get(), n, ctx->q_out.get(), flags == URT_QUERY_ANY, ctx->stream));
   URT_HIP(ctx, hipMemcpyAsync(out, ctx->q_out.get(), out_bytes, hipMemcpyDeviceToHost, ctx->stream));
   URT_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return check_watchdog(ctx);
@@ -140,7 +140,7 @@ int urt_ray_query_device(urt_context* ctx, const void* d_rays, int n, void* d_ou
   if (rc || n == 0) return rc;
   if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & (flags == URT_QUERY_ANY ? 3u : 15u)))
     return fail(ctx, URT_ERR_INVALID_ARGUMENT, "ray query: d_rays must be 16-byte aligned, d_out 16-byte (closest hit) / 4-byte (any hit) aligned");
-  URT_HIP(ctx, launch_query(ctx->scene.ds, ctx->scene.tlas_stack, ctx->scene.blas_stack, (const float4*)d_rays, n, d_out, flags == URT_QUERY_ANY, ctx->stream));
+  URT_HIP(ctx, launch_query(ctx->scene.ds, lane_stack_size(ctx), (const float4*)d_rays, n, d_out, flags == URT_QUERY_ANY, ctx->stream));
   return URT_OK;
   URT_GUARD_END(ctx)
 }
@@ -150,7 +150,7 @@ int urt_ray_query_device(urt_context* ctx, const void* d_rays, int n, void* d_ou
 // reads the sky, so deferred work that writes the texture bound as _SkyboxTexture is submitted first.  Everything is checked before
 // anything is enqueued; on success *launch holds the batch but for its pointers.
 static int radiance_prepare(urt_context* ctx, const void* in, int n, int samples, int bounces, const void* out, int flags, bool host,
-                            DevScene* S, RadianceCamera* C, RadianceBatch* launch) {
+                            DevScene* S, FrameUniforms* C, RadianceBatch* launch) {
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   if (n < 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "radiance query: negative query count");
   if (flags != URT_RADIANCE_RAYS && flags != URT_RADIANCE_PIXELS) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "radiance query: unknown flags");
@@ -159,17 +159,14 @@ static int radiance_prepare(urt_context* ctx, const void* in, int n, int samples
   if (n > 0 && (!in || !out)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "radiance query: in / out is NULL");
   if (n == 0) return URT_OK;
   const bool pixels = flags == URT_RADIANCE_PIXELS;
-  *C = RadianceCamera{};
+  *C = pixels ? bound_camera(ctx) : FrameUniforms{};
+  int width = 0, height = 0;
   if (pixels) {
     const Texture* res = find_texture(ctx, ctx->t_result);
     if (!res) return fail(ctx, URT_ERR_UNBOUND, "radiance query: no texture bound to \"Result\"");
     if (!ctx->c2w_set || !ctx->invp_set)
       return fail(ctx, URT_ERR_UNBOUND, "radiance query: _CameraToWorld / _CameraInverseProjection not set");
-    std::memcpy(C->c2w, ctx->c2w, sizeof C->c2w);
-    std::memcpy(C->invp, ctx->invp, sizeof C->invp);
-    C->pixel_off_x = ctx->pixel_off[0]; C->pixel_off_y = ctx->pixel_off[1];
-    C->seed = ctx->seed;
-    C->width = res->w; C->height = res->h;
+    width = res->w; height = res->h;
     if (host) {
       const urt_PathPixel* p = (const urt_PathPixel*)in;
       for (int i = 0; i < n; i++)
@@ -191,7 +188,7 @@ static int radiance_prepare(urt_context* ctx, const void* in, int n, int samples
   *S = ctx->scene.ds;
   { int rc = bind_sky(ctx, *S); if (rc) return rc; }
   *launch = RadianceBatch{};
-  launch->n = n; launch->samples = samples; launch->bounces = bounces; launch->pixels = pixels;
+  launch->n = n; launch->samples = samples; launch->bounces = bounces; launch->pixels = pixels; launch->width = width; launch->height = height;
   const bool persist = ctx->opt.radiance_persist < 0 ? kRadiancePersistAuto : ctx->opt.radiance_persist != 0;
   if (persist) {
     if (!ctx->rq_next) URT_HIP(ctx, ctx->rq_next.alloc(1));
@@ -202,7 +199,7 @@ static int radiance_prepare(urt_context* ctx, const void* in, int n, int samples
 
 int urt_radiance_query(urt_context* ctx, const void* in, int n, int samples, int bounces, float* out_rgba, int flags) {
   URT_GUARD_BEGIN
-  DevScene S; RadianceCamera C; RadianceBatch B;
+  DevScene S; FrameUniforms C; RadianceBatch B;
   int rc = radiance_prepare(ctx, in, n, samples, bounces, out_rgba, flags, true, &S, &C, &B);
   if (rc || n == 0) return rc;
   const size_t in_bytes = (size_t)n * (B.pixels ? sizeof(urt_PathPixel) : sizeof(urt_PathRay));
@@ -210,7 +207,7 @@ int urt_radiance_query(urt_context* ctx, const void* in, int n, int samples, int
   if (int r = reserve(ctx, ctx->rq_out, (size_t)n, "radiance query: scratch allocation", ctx->stream)) return r;
   B.in = ctx->rq_in.get(); B.out = ctx->rq_out.get();
   URT_HIP(ctx, hipMemcpyAsync(ctx->rq_in.get(), in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  URT_HIP(ctx, launch_radiance(S, ctx->scene.tlas_stack, ctx->scene.blas_stack + ctx->opt.stack_pad, C, B, ctx->stream));
+  URT_HIP(ctx, launch_radiance(S, lane_stack_size(ctx), C, B, ctx->stream));
   URT_HIP(ctx, hipMemcpyAsync(out_rgba, ctx->rq_out.get(), (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
   URT_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return check_watchdog(ctx);
@@ -219,11 +216,11 @@ int urt_radiance_query(urt_context* ctx, const void* in, int n, int samples, int
 
 int urt_radiance_query_device(urt_context* ctx, const void* d_in, int n, int samples, int bounces, void* d_out_rgba, int flags) {
   URT_GUARD_BEGIN
-  DevScene S; RadianceCamera C; RadianceBatch B;
+  DevScene S; FrameUniforms C; RadianceBatch B;
   int rc = radiance_prepare(ctx, d_in, n, samples, bounces, d_out_rgba, flags, false, &S, &C, &B);
   if (rc || n == 0) return rc;
   B.in = d_in; B.out = (float4*)d_out_rgba;
-  URT_HIP(ctx, launch_radiance(S, ctx->scene.tlas_stack, ctx->scene.blas_stack + ctx->opt.stack_pad, C, B, ctx->stream));
+  URT_HIP(ctx, launch_radiance(S, lane_stack_size(ctx), C, B, ctx->stream));
   return URT_OK;
   URT_GUARD_END(ctx)
 }
@@ -255,18 +252,12 @@ int urt_render_aov(urt_context* ctx, urt_handle hit, urt_handle normal, urt_hand
   if (ctx->scene_dirty) { int rc = prepare_scene(ctx); if (rc) return rc; }
   DevScene S = ctx->scene.ds;
   { int rc = bind_sky(ctx, S); if (rc) return rc; }
-  AovCamera C{};
-  std::memcpy(C.c2w, ctx->c2w, sizeof C.c2w);
-  std::memcpy(C.invp, ctx->invp, sizeof C.invp);
-  C.pixel_off_x = ctx->pixel_off[0]; C.pixel_off_y = ctx->pixel_off[1];
-  C.seed = ctx->seed;
-  C.frame_ray = flags == URT_AOV_FRAME_RAY ? 1 : 0;
   AovTargets T{};
   T.hit = t[0] ? t[0]->dev : nullptr; T.normal = t[1] ? t[1]->dev : nullptr;
   T.albedo = t[2] ? t[2]->dev : nullptr; T.id = t[3] ? t[3]->dev : nullptr;
   T.width = width; T.height = height;
   for (int k = 0; k < 4; k++) if (t[k]) t[k]->other_writes = true;
-  URT_HIP(ctx, launch_aov(S, ctx->scene.aov_albedo, ctx->scene.tlas_stack, ctx->scene.blas_stack, C, T, touch(ctx)));
+  URT_HIP(ctx, launch_aov(S, ctx->scene.aov_albedo, lane_stack_size(ctx), bound_camera(ctx), flags == URT_AOV_FRAME_RAY, T, touch(ctx)));
   return URT_OK;
   URT_GUARD_END(ctx)
 }
@@ -479,10 +470,10 @@ int urt_resample_below(urt_context* ctx, urt_handle dst, urt_handle count, float
   if (int rc = reserve(ctx, ctx->rs_pixels, (size_t)n, "resample_below: scratch allocation", ctx->stream)) return rc;
   if (int rc = reserve(ctx, ctx->rs_samples, (size_t)n, "resample_below: scratch allocation", ctx->stream)) return rc;
   URT_HIP(ctx, launch_select_write(t[1]->dev, width, n_texels, below, ctx->rs_counts.get(), (int2*)ctx->rs_pixels.get(), n, touch(ctx)));
-  DevScene S; RadianceCamera C; RadianceBatch B;
+  DevScene S; FrameUniforms C; RadianceBatch B;
   if (int rc = radiance_prepare(ctx, ctx->rs_pixels.get(), n, samples, bounces, ctx->rs_samples.get(), URT_RADIANCE_PIXELS, false, &S, &C, &B)) return rc;
   B.in = ctx->rs_pixels.get(); B.out = ctx->rs_samples.get();
-  URT_HIP(ctx, launch_radiance(S, ctx->scene.tlas_stack, ctx->scene.blas_stack + ctx->opt.stack_pad, C, B, touch(ctx)));
+  URT_HIP(ctx, launch_radiance(S, lane_stack_size(ctx), C, B, touch(ctx)));
   Texture* d = find_texture(ctx, dst);
   Texture* c = find_texture(ctx, count);
   if (!d || !c) return fail(ctx, URT_ERR_INVALID_HANDLE, "resample_below: a texture was released during the call");

@@ -314,7 +314,7 @@ __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, Fram
           if (MULTI) { avg = sum; ray_i++; next_ray = ray_i < P.num_rays; }
           if (!next_ray) {
             float n = (float)P.num_rays;                      // (!MULTI: n = 1 and x / 1 = x — no divisions)
-            st_result(result + (size_t)((unsigned)kf >> 24) * P.frame_stride + (size_t)((unsigned)xy >> 16) * P.width + (xy & 0xffff),
+            st_nt(result + (size_t)((unsigned)kf >> 24) * P.frame_stride + (size_t)((unsigned)xy >> 16) * P.width + (xy & 0xffff),
                       MULTI ? make_float4(sum.x / n, sum.y / n, sum.z / n, 1.0f) : make_float4(sum.x, sum.y, sum.z, 1.0f));   // RS:468
             st = ST_DEAD;
           }

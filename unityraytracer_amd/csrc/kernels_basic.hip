@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void k_mega(DevScene S, FrameParams P, float4*
       avg = avg + res;
     }
     float n = (float)P.num_rays;
-    st_result(result + (size_t)y * P.width + x, make_float4(avg.x / n, avg.y / n, avg.z / n, 1.0f));
+    st_nt(result + (size_t)y * P.width + x, make_float4(avg.x / n, avg.y / n, avg.z / n, 1.0f));
   }
   flush_counters<COUNT>(lc, ctr);
 }
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void k_persist(DevScene S, FrameParams P, floa
           camera_ray<kPOffAfterScene>(P, x, y, seed, o, d);
         } else {
           float n = (float)P.num_rays;
-          st_result(result + (size_t)y * P.width + x, make_float4(avg.x / n, avg.y / n, avg.z / n, 1.0f));   // RS:468
+          st_nt(result + (size_t)y * P.width + x, make_float4(avg.x / n, avg.y / n, avg.z / n, 1.0f));   // RS:468
           alive = false;
         }
       }

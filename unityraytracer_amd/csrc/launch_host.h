@@ -1,5 +1,5 @@
-// launch_host.h — what the host-side launchers of the trace kernels share (kernels.hip and kernels_basic / _serve / _pool.hip; the
-// launchers are declared in kernels.h).  Included after the device headers, outside any namespace.
+// launch_host.h — what the host-side launchers of the trace kernels share (kernels.hip and kernels_basic / _serve / _pool.hip, declared
+// in kernels.h; query.hip, aov.hip, radiance.hip).  Included after the device headers, outside any namespace.
 #pragma once
 #include <stdarg.h>
 #include <stdio.h>
@@ -16,9 +16,11 @@ static inline int blocks_for_tiles(const FrameParams& P) {
   return ((nblocks + q - 1) / q) * q;
 }
 
-static inline size_t stack_lds_bytes(const FrameParams& P) {
-  return (size_t)(P.tlas_stack + P.blas_stack) * 64 * (size_t)(P.block_threads / 64) * sizeof(int);
+// Dynamic LDS of a workgroup whose lanes each keep the two traversal stacks of trace_device.h lane_stacks
+static inline size_t stack_lds_bytes(LaneStackSize E, int block_threads) {
+  return (size_t)(E.tlas + E.blas) * 64 * (size_t)(block_threads / 64) * sizeof(int);
 }
+static inline size_t stack_lds_bytes(const FrameParams& P) { return stack_lds_bytes({P.tlas_stack, P.blas_stack}, P.block_threads); }
 
 // Names the trace launch *rec describes (urt_debug_launch_info): the kernel instantiation by the name rocprofv3 prints for it
 static TraceLaunchRecord* named(TraceLaunchRecord* rec, const char* fmt, ...) __attribute__((format(printf, 2, 3)));

@@ -2,11 +2,11 @@
 // include/urt.h): "how much light arrives along this ray?" for arbitrary rays, and "what would a frame dispatched now write to this
 // pixel?" for pixels of the bound camera.
 //
-// One query per lane, wave64, 256 threads per workgroup; per-lane LDS stacks laid out [entry][lane] as k_query's, sized from the prepared
+// One query per lane, wave64, 256 threads per workgroup; per-lane LDS stacks (trace_device.h lane_stacks) sized from the prepared
 // scene.  A query is the body of k_mega's pixel (RS:440-468): `samples` paths, one after the other on the same lane because the running
-// seed chains them (RS:444), each of up to `bounces` iterations of Trace + Shade.  Trace is query_trace<false> with t_max = +inf (held
-// bit-identical to the frame kernels' trace); Shade is the frame kernels' own (shade_device.h), never counted.  Pixels mode builds its
-// camera ray with the fma chains of frame_device.h camera_ray, the matrices arriving as a kernel-argument struct (as aov.hip's).
+// seed chains them (RS:444), each of up to `bounces` iterations of Trace + Shade.  Trace is the frame kernels' (trace_device.h trace_ray,
+// t_max = +inf) and so is Shade (shade_device.h), never counted.  Pixels mode builds its camera ray with the frame kernels' functions
+// (camera_device.h), the uniforms arriving as a kernel-argument struct (as aov.hip's).
 // Loads: three float4 per ray or one 8-byte record per pixel; stores: one non-temporal float4 per query.
 //
 // Two kernels run the same per-lane steps (query_begin / sample_begin / bounce_step) and differ only in which lane a query runs on:
@@ -19,11 +19,12 @@
 
 #include "../../include/urt_math.h"
 #include "urt_device.h"
+#include "camera_device.h"
 #include "trace_device.h"
 #include "sky_device.h"
 #include "shade_device.h"
-#include "query_device.h"   // query_trace, st_nt
 #include "radiance.h"
+#include "launch_host.h"
 
 namespace {
 
@@ -39,13 +40,13 @@ struct Lane {
 
 // Reads query i.  false: a pixel outside the Result (device form; the host form refuses it) — it gets (0, 0, 0, 0) and is not traced.
 template <bool PIXELS>
-__device__ __forceinline__ bool query_begin(const RadianceCamera& C, const void* __restrict__ in, size_t i, Lane& L) {
+__device__ __forceinline__ bool query_begin(const FrameUniforms& C, int width, int height, const void* __restrict__ in, size_t i, Lane& L) {
   L.avg = mk3(0, 0, 0);
   if (PIXELS) {
     const int2 p = ((const int2*)in)[i];
     L.px = (float)p.x; L.py = (float)p.y;
     L.seed = C.seed;                                             // RS:16: every pixel starts from the frame's _Seed
-    return p.x >= 0 && p.x < C.width && p.y >= 0 && p.y < C.height;
+    return p.x >= 0 && p.x < width && p.y >= 0 && p.y < height;
   }
   const float4* r = (const float4*)in + 3 * i;
   const float4 ra = r[0], rb = r[1], rc = r[2];
@@ -55,20 +56,14 @@ __device__ __forceinline__ bool query_begin(const RadianceCamera& C, const void*
   return true;
 }
 
-// The start of one sample: res = 0, energy = 1 and the sample's first ray — the query's own, or CreateCameraRay RS:142-153 with the uv of
-// RS:448-449 (two rand() draws; the expressions of frame_device.h camera_ray).
+// The start of one sample: res = 0, energy = 1 and the sample's first ray — the query's own, or the camera ray of the pixel's next sample
 template <bool PIXELS>
-__device__ __forceinline__ void sample_begin(const RadianceCamera& C, Lane& L) {
+__device__ __forceinline__ void sample_begin(const FrameUniforms& C, int width, int height, Lane& L) {
   L.res = mk3(0, 0, 0); L.energy = mk3(1, 1, 1);
   if (PIXELS) {
-    float r0 = rand_next(L.seed, L.px, L.py);
-    float r1 = rand_next(L.seed, L.px, L.py);
-    float u = (L.px + r0 + C.pixel_off_x) / (float)C.width * 2.0f - 1.0f;
-    float v = (L.py + r1 + C.pixel_off_y) / (float)C.height * 2.0f - 1.0f;
-    L.o = mul_m4(C.c2w, 0.0f, 0.0f, 0.0f, 1.0f);
-    v3 dir = mul_m4(C.invp, u, v, 0.0f, 1.0f);
-    dir = mul_m4(C.c2w, dir.x, dir.y, dir.z, 0.0f);
-    L.d = normalize(dir);
+    float u, v;
+    jitter_uv(L.seed, L.px, L.py, C.pixel_off_x, C.pixel_off_y, width, height, u, v);
+    camera_ray_uv(C.c2w, C.invp, u, v, L.o, L.d);
   } else {
     L.o = L.o0; L.d = L.d0;
   }
@@ -77,7 +72,7 @@ __device__ __forceinline__ void sample_begin(const RadianceCamera& C, Lane& L) {
 // One iteration of RS:453-460: Trace, then Shade; false = the path ends here
 __device__ __forceinline__ bool bounce_step(const DevScene& S, Lane& L, int* tl, int* bl) {
   LocalCounters lc;                                              // never counted: queries leave urt_counters alone
-  const HitRec h = query_trace<false>(S, L.o, L.d, URT_INF, tl, bl);
+  const HitRec h = trace_ray<false, false>(S, L.o, L.d, URT_INF, tl, bl, lc);
   return shade<false>(S, h, L.o, L.d, L.energy, L.res, L.seed, L.px, L.py, lc);
 }
 
@@ -87,18 +82,16 @@ __device__ __forceinline__ void query_store(float4* __restrict__ out, size_t i, 
 }
 
 template <bool PIXELS>
-__global__ __launch_bounds__(256) void k_radiance(DevScene S, int tlas_stack, int blas_stack, RadianceCamera C, const void* __restrict__ in,
-                                                  int n, int samples, int bounces, float4* __restrict__ out) {
-  extern __shared__ int lds[];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  int* tl = lds + wave * (tlas_stack + blas_stack) * 64 + lane;
-  int* bl = tl + tlas_stack * 64;
+__global__ __launch_bounds__(256) void k_radiance(DevScene S, int tlas_stack, int blas_stack, FrameUniforms C, int width, int height,
+                                                  const void* __restrict__ in, int n, int samples, int bounces, float4* __restrict__ out) {
+  int *tl, *bl;
+  lane_stacks(tlas_stack, blas_stack, tl, bl);
   const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
   if (i >= (size_t)n) return;
   Lane L;
-  if (!query_begin<PIXELS>(C, in, i, L)) { st_nt(out + i, make_float4(0, 0, 0, 0)); return; }
+  if (!query_begin<PIXELS>(C, width, height, in, i, L)) { st_nt(out + i, make_float4(0, 0, 0, 0)); return; }
   for (int s = 0; s < samples; s++) {
-    sample_begin<PIXELS>(C, L);
+    sample_begin<PIXELS>(C, width, height, L);
     for (int k = 0; k < bounces; k++)
       if (!bounce_step(S, L, tl, bl)) break;
     L.avg = L.avg + L.res;                                       // RS:464
@@ -108,13 +101,12 @@ __global__ __launch_bounds__(256) void k_radiance(DevScene S, int tlas_stack, in
 
 // bounces >= 1 (launch_radiance sends bounces == 0 to k_radiance: its paths have no step to schedule)
 template <bool PIXELS>
-__global__ __launch_bounds__(256) void k_radiance_persist(DevScene S, int tlas_stack, int blas_stack, RadianceCamera C,
+__global__ __launch_bounds__(256) void k_radiance_persist(DevScene S, int tlas_stack, int blas_stack, FrameUniforms C, int width, int height,
                                                           const void* __restrict__ in, int n, int samples, int bounces,
                                                           float4* __restrict__ out, unsigned int* __restrict__ next) {
-  extern __shared__ int lds[];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  int* tl = lds + wave * (tlas_stack + blas_stack) * 64 + lane;
-  int* bl = tl + tlas_stack * 64;
+  const int lane = threadIdx.x & 63;
+  int *tl, *bl;
+  lane_stacks(tlas_stack, blas_stack, tl, bl);
   Lane L;
   L.px = L.py = L.seed = 0;
   L.o0 = L.o = mk3(0, 0, 0); L.d0 = L.d = mk3(0, 0, 1);
@@ -133,9 +125,9 @@ __global__ __launch_bounds__(256) void k_radiance_persist(DevScene S, int tlas_s
       const unsigned int mine = base + (unsigned int)__popcll(dead & ((1ull << lane) - 1ull));
       if (!alive && mine < (unsigned int)n) {
         i = mine;
-        if (query_begin<PIXELS>(C, in, i, L)) {
+        if (query_begin<PIXELS>(C, width, height, in, i, L)) {
           alive = true; s = 0; k = 0;
-          sample_begin<PIXELS>(C, L);
+          sample_begin<PIXELS>(C, width, height, L);
         } else {
           st_nt(out + i, make_float4(0, 0, 0, 0));
         }
@@ -151,7 +143,7 @@ __global__ __launch_bounds__(256) void k_radiance_persist(DevScene S, int tlas_s
       if (!cont || k >= bounces) {
         L.avg = L.avg + L.res;                                   // RS:464
         s++;
-        if (s < samples) { k = 0; sample_begin<PIXELS>(C, L); }  // RS:444: the next sample, the seed carries over
+        if (s < samples) { k = 0; sample_begin<PIXELS>(C, width, height, L); }  // RS:444: the next sample, the seed carries over
         else { query_store(out, i, L, samples); alive = false; }
       }
     }
@@ -159,14 +151,11 @@ __global__ __launch_bounds__(256) void k_radiance_persist(DevScene S, int tlas_s
 }
 
 template <bool PIXELS>
-hipError_t launch_t(const DevScene& S, int tlas_stack, int blas_stack, const RadianceCamera& C, const RadianceBatch& B, hipStream_t st) {
-  const size_t lds = (size_t)(tlas_stack + blas_stack) * 256 * sizeof(int);
+hipError_t launch_t(const DevScene& S, LaneStackSize E, const FrameUniforms& C, const RadianceBatch& B, hipStream_t st) {
+  const size_t lds = stack_lds_bytes(E, 256);
   const bool persist = B.work_counter != nullptr && B.bounces > 0 && B.n_cus > 0;
   const void* fn = persist ? (const void*)k_radiance_persist<PIXELS> : (const void*)k_radiance<PIXELS>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  if (hipError_t e = raise_lds_limit(fn, lds)) return e;
   const unsigned int all = (unsigned int)(((size_t)B.n + 255) / 256);
   if (persist) {
     hipError_t e = hipMemsetAsync(B.work_counter, 0, sizeof(unsigned int), st);
@@ -176,10 +165,11 @@ hipError_t launch_t(const DevScene& S, int tlas_stack, int blas_stack, const Rad
     if (e != hipSuccess) return e;
     const unsigned int fit = (unsigned int)B.n_cus * (unsigned int)(per_cu > 0 ? per_cu : 1);
     const unsigned int nb = all < fit ? all : fit;
-    hipLaunchKernelGGL(k_radiance_persist<PIXELS>, dim3(nb), dim3(256), lds, st, S, tlas_stack, blas_stack, C, B.in, B.n, B.samples, B.bounces,
-                       B.out, B.work_counter);
+    hipLaunchKernelGGL(k_radiance_persist<PIXELS>, dim3(nb), dim3(256), lds, st, S, E.tlas, E.blas, C, B.width, B.height, B.in, B.n, B.samples,
+                       B.bounces, B.out, B.work_counter);
   } else {
-    hipLaunchKernelGGL(k_radiance<PIXELS>, dim3(all), dim3(256), lds, st, S, tlas_stack, blas_stack, C, B.in, B.n, B.samples, B.bounces, B.out);
+    hipLaunchKernelGGL(k_radiance<PIXELS>, dim3(all), dim3(256), lds, st, S, E.tlas, E.blas, C, B.width, B.height, B.in, B.n, B.samples, B.bounces,
+                       B.out);
   }
   return hipGetLastError();
 }
@@ -188,9 +178,9 @@ hipError_t launch_t(const DevScene& S, int tlas_stack, int blas_stack, const Rad
 
 namespace urtd {
 
-hipError_t launch_radiance(const DevScene& S, int tlas_stack, int blas_stack, const RadianceCamera& C, const RadianceBatch& B, hipStream_t st) {
+hipError_t launch_radiance(const DevScene& S, LaneStackSize E, const FrameUniforms& C, const RadianceBatch& B, hipStream_t st) {
   if (B.n <= 0) return hipSuccess;
-  return B.pixels ? launch_t<true>(S, tlas_stack, blas_stack, C, B, st) : launch_t<false>(S, tlas_stack, blas_stack, C, B, st);
+  return B.pixels ? launch_t<true>(S, E, C, B, st) : launch_t<false>(S, E, C, B, st);
 }
 
 }  // namespace urtd

@@ -1,6 +1,7 @@
-// trace_device.h — the device functions of one ray's trace that the frame kernels (kernels.hip) and the ray queries (query.hip) share:
-// the hit record, the object-level slab tests and cull, sphere / triangle / leaf intersection, the triangle-BVH node steps and the
-// per-MeshObject traversal.  Internal to the library; included by .hip translation units only, after the kernels' own headers.
+// trace_device.h — the device functions of one ray's trace that the frame kernels (kernels*.hip) and the single-ray kernels outside a
+// frame (query.hip, aov.hip, radiance.hip) share: the hit record, the object-level slab tests and cull, sphere / triangle / leaf
+// intersection, the triangle-BVH node steps, the per-MeshObject traversal, Trace() itself (trace_ray), its per-lane LDS stacks and the
+// streaming store of a result.  Internal to the library; included by .hip translation units only, after the kernels' own headers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -313,6 +314,117 @@ __device__ __forceinline__ void intersect_mesh(const DevScene& S, int32_t root, 
       cur = blas_pop(stk, sp);
     }
   }
+}
+
+// intersect_mesh with an early exit after the first leaf that produced a hit (any-hit form)
+__device__ __forceinline__ void intersect_mesh_any(const DevScene& S, int32_t root, v3 o, v3 d, HitRec& best, int* stk, LocalCounters& lc) {
+  if (root == kEmptyMeshRoot) return;
+  BlasRay R = blas_ray(o, d);
+  int best_i = -1;
+  int sp = 0;
+  int32_t cur = root;
+  while (cur != kBlasDone) {
+    if (cur >= 0) {
+      cur = blas_node_step<false>(S, cur, R, best.t, stk, sp, lc);
+    } else {
+      test_leaf<false>(S, cur, o, d, best, best_i, lc);
+      if (best.kid != 0) return;
+      cur = blas_pop(stk, sp);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Trace — RS:364-383: ground plane, then the mesh object BVH, then the sphere BVH, for hits with 0 < t < t_max (t_max > 0, not NaN;
+// +inf is the reference's Trace; kind 0 = nothing nearer than t_max).  ANY: return at the first such hit (ground plane, a leaf's
+// triangles, a sphere).  tl / bl: this lane's LDS stacks for the object-level and the triangle-level traversals (lane_stacks).
+// The ONE walk of a single ray: the frame kernels of modes 0 - 2, the ray queries, the feature buffers and the radiance queries call it.
+// ---------------------------------------------------------------------------------------------------
+template <bool COUNT, bool ANY>
+__device__ __forceinline__ HitRec trace_ray(const DevScene& S, v3 o, v3 d, float t_max, int* tl, int* bl, LocalCounters& lc) {
+  lc.rays++;
+  HitRec best; best.t = t_max; best.kid = 0; best.u = 0; best.v = 0;
+  float t_ground = URT_INF;                                     // what the object-level cull compares with (urt_math.h tlas_cull): the ground hit, whatever t_max
+  // IntersectGroundPlane RS:156-172
+  {
+    float t = -o.y / d.y;
+    if (t > 0 && t < URT_INF) t_ground = t;
+    if (t > 0 && t < best.t) { best.t = t; best.kid = 1; }
+    if (ANY && best.kid != 0) return best;
+  }
+  // one reciprocal per axis for the object-level slab test (normative form of RS:282-283)
+  v3 rcp = mk3(1.0f / (d.x + kEPSILON), 1.0f / (d.y + kEPSILON), 1.0f / (d.z + kEPSILON));
+  // IntersectMeshBVH RS:294-326 (`tests` is never reset: once a leaf was reached, every later popped
+  // node has its object intersected, A.5; object ids < 0 or out of range are skipped, not read)
+  if (S.n_meshes > 0) {
+    int check = 1; tl[0] = 0; bool seen = false;
+    while (check > 0) {
+      check--;
+      int bi = tl[check * 64];
+      bool hit = false, culled = false; int index = -1;
+      if (bi < S.n_mesh_tlas) {
+        if (COUNT) lc.tlas_nodes++;
+        float4 a = S.mesh_tlas[2 * bi], b = S.mesh_tlas[2 * bi + 1];
+        index = as_int(a.w);
+        float t_min, t_far;
+        hit = tlas_slab_t(a, b, o, rcp, t_min, t_far);
+        culled = leaf_culled(b, t_min, t_far, t_ground);
+      }
+      if (hit) {
+        if (index < 0) { tl[check * 64] = bi * 2 + 1; check++; tl[check * 64] = bi * 2 + 2; check++; }
+        else seen = true;
+      }
+      if (seen && !culled && index >= 0 && index < S.n_meshes) {
+        if (ANY) {
+          intersect_mesh_any(S, S.mesh_root[index], o, d, best, bl, lc);
+          if (best.kid != 0) return best;
+        } else {
+          intersect_mesh<COUNT>(S, S.mesh_root[index], o, d, best, bl, lc);
+        }
+      }
+    }
+  }
+  // IntersectSphereBVH RS:329-361
+  if (S.n_spheres > 0) {
+    int check = 1; tl[0] = 0; bool seen = false;
+    while (check > 0) {
+      check--;
+      int bi = tl[check * 64];
+      bool hit = false; int index = -1;
+      if (bi < S.n_sphere_tlas) {
+        if (COUNT) lc.tlas_nodes++;
+        float4 a = S.sphere_tlas[2 * bi], b = S.sphere_tlas[2 * bi + 1];
+        index = as_int(a.w);
+        hit = tlas_slab(a, b, o, rcp);
+      }
+      if (hit) {
+        if (index < 0) { tl[check * 64] = bi * 2 + 1; check++; tl[check * 64] = bi * 2 + 2; check++; }
+        else seen = true;
+      }
+      if (seen && index >= 0 && index < S.n_spheres) {
+        intersect_sphere<COUNT>(S, index, o, d, best, lc);
+        if (ANY && best.kid != 0) return best;
+      }
+    }
+  }
+  return best;
+}
+
+// This lane's two stacks in the workgroup's dynamic LDS, laid out [entry][lane] per wave: tlas_stack + blas_stack entries per lane
+__device__ __forceinline__ void lane_stacks(int tlas_stack, int blas_stack, int*& tl, int*& bl) {
+  extern __shared__ int lds[];
+  int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  int per_wave = (tlas_stack + blas_stack) * 64;
+  tl = lds + wave * per_wave + lane;
+  bl = tl + tlas_stack * 64;
+}
+
+// A result is written once and not read again by its kernel: stored non-temporally so that it does not push BVH lines out of the L2
+// (measured -1 % on the frame kernels; the same hint on the sky's texel loads costs +3 % and is not used).
+typedef float f4v __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void st_nt(float4* p, float4 v) {
+  f4v q = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(q, (f4v*)p);
 }
 
 }  // namespace

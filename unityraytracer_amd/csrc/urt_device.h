@@ -101,6 +101,9 @@ struct FrameUniforms {
 static constexpr int kMaxFramesPerLaunch = 64;      // the table lives in device memory (frame_batch.cpp stages it through pinned host slots): 64 x 144 B
 struct FrameTable { FrameUniforms f[kMaxFramesPerLaunch]; };   // host-side image of one launch's table
 
+// LDS entries per lane of the two traversal stacks of a kernel that traces one ray per lane (trace_device.h lane_stacks)
+struct LaneStackSize { int tlas, blas; };
+
 static constexpr unsigned int kWorkShards = 64;   // work counters of the persistent kernels (power of two), 128 B apart
 static constexpr int kCounterShards = 256;   // power of two; a block adds to shard blockIdx & (N-1)
 struct alignas(128) DevCounters {            // one shard = one 128-byte line of 64-bit counters
