@@ -69,7 +69,11 @@ typedef struct urt_PathRay {
   float seed;                   /* @12 the running _Seed the path's first rand() starts from (RS:16) */
   float direction[3];           /* @16 used as given (not normalised), as urt_Ray's */
   int32_t reserved0;            /* @28 */
-  float px, py;                 /* @32 the "pixel" of rand() (RS:77-81): any two floats; they select the query's random stream */
+  float px, py;                 /* @32 the "pixel" of rand() (RS:77-81): two finite floats, they select the query's random stream.  Any
+                                       sign, fractions included, as long as  |a * d| * 0.6366 < 2^30  for every rand() of the query, with
+                                       a = (seed + seed / 17) / 100, d = px * 12.9898 + py * 78.233 (urt_math.h rand_next) and the seed
+                                       growing by 0.5 per draw: beyond that f_sincos's (int)k is not defined on the host.  |px|, |py| <=
+                                       4096 with |seed| <= 64 is well inside */
   int32_t reserved1[2];         /* @40 */
 } urt_PathRay;
 

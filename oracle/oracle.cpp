@@ -483,6 +483,27 @@ struct Tracer {
     out4[0] = resultAverage.x / n; out4[1] = resultAverage.y / n; out4[2] = resultAverage.z / n; out4[3] = 1.0f;
     C.pixels++;
   }
+
+  // include/urt.h URT_RADIANCE_RAYS for one urt_PathRay: CSMain's loop from the query's own ray, no camera-ray draws
+  void Radiance(const urt_PathRay& q, int samples, int bounces, float* out4) {
+    _PixelX = q.px; _PixelY = q.py;
+    _Seed = q.seed;                               // once per query: it carries over from one sample to the next (RS:444)
+    v3 resultAverage = mk3(0, 0, 0);
+    for (int i = 0; i < samples; i++) {
+      v3 result = mk3(0, 0, 0);
+      Ray ray = CreateRay(ld3(q.origin), ld3(q.direction));
+      for (int k = 0; k < bounces; k++) {
+        RayHit hit = Trace(ray);
+        v3 e = ray.energy;
+        v3 s = Shade(ray, hit);
+        result = result + e * s;
+        if (!any_nonzero(ray.energy)) break;
+      }
+      resultAverage = resultAverage + result;
+    }
+    float n = (float)samples;
+    out4[0] = resultAverage.x / n; out4[1] = resultAverage.y / n; out4[2] = resultAverage.z / n; out4[3] = 1.0f;
+  }
 };
 
 static void add_counters(OracleCounters& a, const OracleCounters& b) {
@@ -661,6 +682,29 @@ void oracle_probe_sky(const OracleScene* scene, const float* dir3, float* rgb) {
   RayHit h = Tracer::CreateRayHit();
   v3 c = T.Shade(r, h);
   rgb[0] = c.x; rgb[1] = c.y; rgb[2] = c.z;
+}
+
+// Radiance queries (include/urt.h urt_radiance_query, URT_RADIANCE_RAYS): rays12 = n urt_PathRay records, out4 = n RGBA texels.
+// Queries are dealt round-robin to n_threads std::threads, one Tracer each (Radiance sets its state per query).  mode as oracle_render
+// (mode 1 needs the triangle BVH set).  Returns 0, or 1 on bad arguments.
+int oracle_probe_radiance(const OracleScene* scene, int mode, const void* rays12, int n, int samples, int bounces, float* out4,
+                          int n_threads) {
+  if (!scene || n < 0 || (n > 0 && (!rays12 || !out4)) || samples < 1 || bounces < 0) return 1;
+  if (mode == 1 && scene->n_mesh_objects > 0 && (!scene->blas_tri_index || !scene->blas_mesh_root)) return 1;
+  const urt_PathRay* q = (const urt_PathRay*)rays12;
+  if (n_threads < 1) n_threads = 1;
+  auto work = [&](int tid) {
+    Tracer T(*scene, mode);
+    for (int i = tid; i < n; i += n_threads) T.Radiance(q[i], samples, bounces, out4 + 4 * (size_t)i);
+  };
+  if (n_threads == 1) {
+    work(0);
+  } else {
+    std::vector<std::thread> th;
+    for (int t = 0; t < n_threads; t++) th.emplace_back(work, t);
+    for (auto& t : th) t.join();
+  }
+  return 0;
 }
 
 // An independent, deliberately simple triangle-BVH builder (median split on the longest axis of the

@@ -76,6 +76,8 @@ def load(build: bool = True):
     lib.oracle_probe_trace.restype = None
     lib.oracle_probe_sky.argtypes = [C.POINTER(OracleScene), vp, vp]
     lib.oracle_probe_sky.restype = None
+    lib.oracle_probe_radiance.argtypes = [C.POINTER(OracleScene), i, vp, i, i, i, vp, i]
+    lib.oracle_probe_radiance.restype = i
     lib.oracle_build_blas.argtypes = [C.POINTER(OracleScene), vp, i, vp, vp]
     lib.oracle_build_blas.restype = i
     lib.oracle_compute_normals.argtypes = [vp, i, vp, i, vp]
@@ -192,6 +194,31 @@ class Oracle:
         out = np.zeros(3, dtype=np.float32)
         self.lib.oracle_probe_sky(C.byref(self.s), _ptr(d), _ptr(out))
         return out
+
+
+def radiance(oracle: Oracle, rays, samples: int, bounces: int, mode: int = 0, threads: int | None = None) -> np.ndarray:
+    """include/urt.h urt_radiance_query, URT_RADIANCE_RAYS, restated over the Tracer's own Trace and Shade (oracle_probe_radiance).
+    rays: n urt_PathRay records — a structured array of 48-byte items or float32 (n, 12): origin, seed @12, direction @16, px, py @32.
+    Returns (n, 4) float32.  threads: default min(16, hardware threads); the answer does not depend on it."""
+    r = np.ascontiguousarray(rays)
+    if r.dtype.itemsize != 48 and not (r.dtype == np.float32 and r.ndim == 2 and r.shape[1] == 12):
+        raise ValueError("radiance: rays must be urt_PathRay records (48 bytes each) or float32 (n, 12)")
+    n = r.shape[0]
+    if threads is None:
+        threads = max(1, min(16, hardware_threads()))
+    out = np.zeros((n, 4), dtype=np.float32)
+    rc = oracle.lib.oracle_probe_radiance(C.byref(oracle.s), int(mode), _ptr(r), n, int(samples), int(bounces), _ptr(out), int(threads))
+    if rc != 0:
+        raise ValueError("oracle_probe_radiance: bad arguments")
+    return out
+
+
+def path_rays(origins, directions, pixels, seeds) -> np.ndarray:
+    """float32 (n, 12) urt_PathRay records from origins, directions (n, 3), pixels (n, 2) and seeds (a number or (n,))."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    r = np.zeros((len(o), 12), dtype=np.float32)
+    r[:, 0:3], r[:, 3], r[:, 4:7], r[:, 8:10] = o, seeds, np.asarray(directions, dtype=np.float32).reshape(-1, 3), pixels
+    return r
 
 
 def accumulate(target: np.ndarray, converged: np.ndarray, sample: float) -> np.ndarray:
