@@ -1,12 +1,10 @@
 """Radiance .hdr loader and frame writers (csrc/host_io.cpp through the C ABI).  The reference's sky
 assets are absent from its tree, so the loader is pinned on synthetic RGBE files written here (flat and new-style RLE) —
 "parity unpinned" against Unity's own importer.  CPU only."""
-import struct
-import zlib
-
 import numpy as np
 import pytest
 
+from png_ref import read_png
 from unityraytracer_amd import UrtError, host_io
 
 
@@ -112,20 +110,8 @@ def test_write_png_is_a_valid_srgb_png(built_library, tmp_path):
     img[4, 0] = (np.nan, -1.0, 7.0, 1.0)                        # NaN and out-of-range values clamp
     p = str(tmp_path / "shot.png")
     host_io.write_png(p, img)
-    data = open(p, "rb").read()
-    assert data[:8] == b"\x89PNG\r\n\x1a\n"
-    pos, chunks = 8, {}
-    while pos < len(data):
-        n, tag = struct.unpack(">I4s", data[pos:pos + 8])
-        body = data[pos + 8:pos + 8 + n]
-        assert struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])[0] == zlib.crc32(tag + body)
-        chunks[tag] = body
-        pos += 12 + n
-    w, h, depth, ctype = struct.unpack(">IIBB", chunks[b"IHDR"][:10])
-    assert (w, h, depth, ctype) == (6, 5, 8, 2)
-    raw = np.frombuffer(zlib.decompress(chunks[b"IDAT"]), np.uint8).reshape(5, 1 + 6 * 3)
-    assert (raw[:, 0] == 0).all()
-    px = raw[:, 1:].reshape(5, 6, 3)
+    w, h, depth, ctype, px = read_png(p)                        # signature, chunk CRCs, IHDR, zlib, filter bytes: tests/png_ref.py
+    assert (w, h, depth, ctype) == (6, 5, 8, 2) and px.shape == (5, 6, 3)
     assert (px[4, :, 1] == 255).all()                           # our row 0 (bottom) is the LAST PNG row
     assert px[0, 0].tolist() == [0, 0, 255]                     # NaN -> 0, negative -> 0, > 1 -> 255 (top-left = our row 4)
     lin = np.linspace(0, 1, 6)

@@ -1,8 +1,9 @@
 """The reference's OWN scenes as fixtures: tests/golden/scene_Scene1.json and scene_SampleScene.json are
 mined from Assets/Scenes/*.unity by tests/golden/make_scene_fixtures.py (camera, numBounces / numRays, every enabled RayTraceObject
 with its transform, collider radius and material); Unity's built-in meshes are synthesised (scenes.unity_builtin_mesh), the sky is
-procedural (the .hdr blobs are not in the reference's tree).  Parity stays UNPINNED — no reference output exists for these scenes
-either — but the configurations the reference's authors actually ran are exercised: Scene1.unity:1777-1779,1804-1805,1826-1827
+procedural (the .hdr blobs are not in the reference's tree).  Radiance parity stays UNPINNED — no reference output with a known sky
+exists for these scenes (where the objects stand IS pinned, on the capture of Scene1: tests/test_reference_silhouettes.py) — but the
+configurations the reference's authors actually ran are exercised: Scene1.unity:1777-1779,1804-1805,1826-1827
 (camera (0,1,-10), fov 81, numBounces 2, numRays 1, 6 spheres + 4 meshes) and SampleScene.unity:386,411-412,433-434 (camera pitched
 10 degrees at (0,30,-80), fov 60, numBounces 10 x numRays 25).  CPU part: the fixtures, the stand-in meshes, and the qualitative
 checks SURVEY §4 lists against statistics of the reference's screenshots (tests/golden/screenshot_stats.json)."""
@@ -142,7 +143,20 @@ def test_scene1_looks_like_the_reference_screenshots():
     k = 3
     drop = np.array([lum[y - k:y].mean() - lum[y:y + k].mean() for y in range(k, h - k)])
     assert abs((int(np.argmax(drop)) + k) / h - shot["ground_starts_at_row_fraction"]) < 0.03                 # 0.50 in both
-    # the small rotated cube 1.3 units in front of the camera: dark in the capture (the black pentagon), dark here
+    # the capture's black pentagon is Cube (1), the 1.12 x 2.06 x 1.38 mirror cube rotated about all three axes (its spans are mined in
+    # tests/golden/screenshot_silhouettes.json; the geometry is pinned in tests/test_reference_silhouettes.py): black there, dark here
+    # inside the capture's own mask, sampled at this render's pixel centres (rows of the mask run top-down)
+    spans = json.load(open(os.path.join(GOLD, "screenshot_silhouettes.json")))
+    mask = np.zeros((spans["capture"]["height"], spans["capture"]["width"]), bool)
+    for row, x0, x1 in spans["objects"]["Cube (1)"]["spans"]:
+        mask[row, x0:x1 + 1] = True
+    ys = ((np.arange(h) + 0.5) / h * mask.shape[0]).astype(int)
+    xs = ((np.arange(sc.width) + 0.5) / sc.width * mask.shape[1]).astype(int)
+    inside = mask[np.ix_(ys, xs)][::-1]                                      # row 0 = bottom, like img
+    assert inside.sum() > 1000
+    pentagon = img[inside][:, :3].mean()
+    assert pentagon < 0.5 * sky.mean(), (pentagon, sky.mean())               # measured: 0.097 against a sky mean of 0.61
+    # the small rotated cube 1.3 units in front of the camera (not in the capture: it shows sky there) renders dark as well
     cube = next(o for o in fixture("Scene1")["objects"] if o["name"] == "Cube")
     assert cube["enabled"] and max(abs(c) for c in cube["rotation"][:3]) > 0.01
     o = pyoracle.Oracle(sc)
