@@ -525,6 +525,12 @@ typedef struct urt_counters {
  *                    boxes on one 16-bit grid over the whole forest, csrc/qnodes.hip; a forest too large for the grid's plane arithmetic (cell
  *                    > 2^43) keeps the float nodes, see urt_debug_read_scene_qnodes.  A measured alternative: same pixels, -1.3 % frame time on
  *                    single-mesh scenes, +1.3 % on C4 / C5: the loop waits on the latency of one dependent fetch per step, not on its width),
+ *          "blas_cones" (-1 auto, the default = on | 0 off | 1 on: every child of a triangle-BVH node carries a cone that holds the normals of all
+ *                        triangles below it — four signed bytes in the node's spare dwords, derived on the GPU after every build and refit,
+ *                        csrc/cones.hip — and the traversal of the default kernel skips a child whose triangles the ray can only see from
+ *                        behind: the reference's own back-face culling (RS:211) rejects every one of them, so the skip is exact.  A ray
+ *                        that leaves a closed mesh no longer walks the boxes around its origin down to their leaves.  The counting
+ *                        instantiation ("count_stats") and "qnodes" walk without it.  See urt_debug_read_scene_cones),
  *          "refit" (0/1, default 1: moved MeshObjects are refitted on the GPU instead of rebuilt — see urt_debug_refit_stats),
  *          "watchdog_cap" (test hook: scheduler trips a wave may make before it gives up; 0 = auto = 2^24 x frames of the launch x
  *                          max(1, numRays x numBounces / 8))
@@ -688,6 +694,7 @@ typedef struct urt_launch_info {
   int slab_base;              /* first Result slot of the launch */
   int overlapped;             /* 1: the launch did not wait for the previous launch (it waited for the main stream as of the previous submission) */
   int overlapped_launches;    /* such launches since the context was created */
+  int cones;                  /* 1: the launch's traversal applied the normal cones of option "blas_cones" (kernel_mode 3, not counting, no qnodes) */
 } urt_launch_info;
 URT_API int urt_debug_launch_info(urt_context* ctx, urt_launch_info* out_info);
 URT_API int urt_debug_read_scene_blas(urt_context* ctx, float* nodes, int32_t* tri_index, int32_t* mesh_root);
@@ -696,6 +703,12 @@ URT_API int urt_debug_read_scene_blas(urt_context* ctx, float* nodes, int32_t* t
  * *out_n_nodes = n, or 0 while "qnodes" is 0 (then nothing is written; out may be NULL to ask for n first).  *out_in_use = 1 when
  * the traversal loop of the default trace kernel reads them (qnodes = 1, or -1 and a fine enough grid), else 0. */
 URT_API int urt_debug_read_scene_qnodes(urt_context* ctx, float* out, int* out_n_nodes, int* out_in_use);
+/* The normal cones of option "blas_cones" as the trace kernel reads them (prepares a stale scene first): words = 2 n_nodes dwords, the cone
+ * of child 0 and of child 1 of every node — four signed bytes (ax, ay, az, T), ax in the lowest; the child is skipped iff
+ * ax rx + ay ry + az rz - 127 T > 0 for the ray's bytes r = round(127 d); 0 = no cone —, and tri_edges = 6 n_tris floats, e1.xyz and
+ * e2.xyz of every leaf-order triangle of the world-space records the cones were derived from (what Moller-Trumbore reads).  Either may
+ * be NULL.  *out_in_use = 1 when the words are filled in (the option is on and the scene has triangle BVHs), else they are all 0. */
+URT_API int urt_debug_read_scene_cones(urt_context* ctx, uint32_t* words, float* tri_edges, int* out_in_use);
 /* Scene preparation of a context keeps the triangle BVH of every MeshObject and reuses it at the next preparation when the
  * MeshObject's matrix and the positions behind its index slots are unchanged (the reference re-uploads every buffer when
  * any object moves, RM:262-336).  Reports how many MeshObject BVHs were reused / built since the context was created. */

@@ -629,6 +629,7 @@ const OptionRow kOptions[] = {
   {"qnodes", &O::qnodes, -1, 1, "qnodes must be -1 (auto), 0 or 1", kStale, nullptr},
   {"lbvh_slack", &O::lbvh_slack, 0, 16, "lbvh_slack must be 0..16", kStale | kOnChange, nullptr},
   {"overlap_launches", &O::overlap_launches, 0, 2, "overlap_launches must be 0 (off), 1 (auto) or 2 (always)", kFlushAgain, nullptr},
+  {"blas_cones", &O::blas_cones, -1, 1, "blas_cones must be -1 (auto), 0 or 1", kStale | kOnChange, nullptr},
   {"front_cull", &O::front_cull, 0, 1, "front_cull must be 0 or 1", kFlushAgain | kStale | kOnChange, nullptr},
   {"refit", &O::refit, INT_MIN, INT_MAX, "", kBool | kStale, nullptr},
   {"watchdog_cap", &O::watchdog_cap, 0, INT_MAX, "watchdog_cap must be >= 0 (0 = auto)", 0, nullptr},
@@ -823,6 +824,29 @@ int urt_debug_read_scene_qnodes(urt_context* ctx, float* out, int* out_n_nodes, 
   if (out_n_nodes) *out_n_nodes = have ? ctx->scene.n_blas_nodes : 0;
   if (out_in_use) *out_in_use = ctx->scene.ds.blas_qnodes != nullptr ? 1 : 0;
   if (out && have) URT_HIP(ctx, hipMemcpy(out, ctx->scene.qbuf, (2 + 2 * (size_t)ctx->scene.n_blas_nodes) * sizeof(float4), hipMemcpyDeviceToHost));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+int urt_debug_read_scene_cones(urt_context* ctx, uint32_t* words, float* tri_edges, int* out_in_use) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = current_scene(ctx)) return rc;
+  URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
+  const DevScene& S = ctx->scene.ds;
+  const size_t nn = (size_t)std::max(0, ctx->scene.n_blas_nodes), nt = (size_t)std::max(0, ctx->scene.n_scene_tris);
+  if (out_in_use) *out_in_use = ctx->scene.cones_in_use ? 1 : 0;
+  if (words && nn > 0 && S.blas_cnodes) {
+    std::vector<float> cn(nn * 16);
+    URT_HIP(ctx, hipMemcpy(cn.data(), S.blas_cnodes, cn.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t n = 0; n < nn; n++) std::memcpy(&words[2 * n], &cn[n * 16 + 14], 8);
+  }
+  if (tri_edges && nt > 0) {
+    std::vector<float> tv(nt * 12);
+    URT_HIP(ctx, hipMemcpy(tv.data(), S.tri_verts, tv.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < nt; k++) { std::memcpy(&tri_edges[6 * k], &tv[k * 12 + 4], 12); std::memcpy(&tri_edges[6 * k + 3], &tv[k * 12 + 8], 12); }
+  }
   return URT_OK;
   URT_GUARD_END(ctx)
 }

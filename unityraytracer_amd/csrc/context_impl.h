@@ -99,6 +99,8 @@ struct urt_context {
     int lbvh_slack = 6;                     // blas_builder 2: levels of slack in the depth budget (csrc/lbvh.hip k_td_level)
     int front_cull = 1;                     // object-level cull (urt_math.h tlas_cull; csrc/cullflags.hip): 0 = every popped object is intersected, as the reference does
     int overlap_launches = 1;               // see "Overlapped launches" below
+    int blas_cones = -1;                    // normal cones per triangle-BVH child (csrc/cones.hip): the scheduled kernel skips children whose triangles the ray sees from behind.
+                                            // -1 = auto (= on), 0 = off (the words stay 0), 1 = on
   } opt;
 
   // ---- derived device scene ---------------------------------------------------------------------------------------------
@@ -122,6 +124,9 @@ struct urt_context {
     float4* qbuf = nullptr;                 // frame + quantized nodes (in scene_allocs)
     float4* cbuf = nullptr;                 // centre / half-extent copy of the nodes (in scene_allocs): DevScene::blas_cnodes
     float qnode_quality = 0;                // smallest MeshObject extent in grid cells (csrc/qnodes.hip)
+    int4* cone_rng[2] = {nullptr, nullptr}; // option "blas_cones": the triangle range below every child and the relaxation's second buffer (in scene_allocs)
+    const int4* cone_ranges = nullptr;      // the one of the two that holds the ranges, once they are found (csrc/cones.hip cone_ranges)
+    bool cones_in_use = false;              // the cone words of cbuf are filled in (else they are 0)
     // urt_render_aov: one float4 per material in the order of DevScene::materials (pack_albedo), in scene_allocs.
     // Not a DevScene member: DevScene is an argument of every frame kernel, and the camera-matrix loads of k_sched depend on its size
     const float4* aov_albedo = nullptr;

@@ -262,10 +262,13 @@ static int launch_sched_frames(urt_context* ctx, const DevScene& S, const FrameP
   if (P.serve) {                                             // mailbox of the posted rays: 32 B per thread of the grid
     if (int rc = reserve(ctx, ctx->d_mail, (size_t)nb * (size_t)P.block_threads * 2, "mailbox allocation", touch(ctx))) return rc;
   }
-  return timed_launch(ctx, st, P.serve ? 5 : 3, front_mode, P, count, wpc, [&](TraceLaunchRecord* rec) {
+  int rc = timed_launch(ctx, st, P.serve ? 5 : 3, front_mode, P, count, wpc, [&](TraceLaunchRecord* rec) {
     return P.serve ? launch_serve(S, P, d_table, result, ctx->d_counters.get(), next, ctx->d_mail.get(), nb, front_mode, count, st, rec)
                    : launch_sched(S, P, d_table, result, ctx->d_counters.get(), next, nb, front_mode, count, st, rec);
   });
+  // the cone test runs in the instantiations of k_sched that neither count nor read quantized nodes (kernels.hip), on the words of this scene
+  if (rc == URT_OK) ctx->last_launch.cones = !P.serve && !count && !S.blas_qnodes && S.blas_cnodes && ctx->scene.cones_in_use ? 1 : 0;
+  return rc;
 }
 
 // The run of deferred blends that starts at ops[i], which flush_pending makes ONE pass (the same per-pixel operations in the same order):

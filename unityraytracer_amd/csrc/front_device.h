@@ -26,7 +26,8 @@ struct FrontLds {
 };
 
 // SP0: the height an empty triangle-BVH stack has for the caller (1 = a sentinel sits in entry 0: k_sched)
-template <bool COUNT, bool TOPF = false, bool RAYS = true, int SP0 = 0>
+// CONES (with SP0 = 1 only: k_sched): the walk of the BVH top applies the normal-cone test (trace_device.h cone_skips)
+template <bool COUNT, bool TOPF = false, bool RAYS = true, int SP0 = 0, bool CONES = false>
 __device__ __forceinline__ bool trace_front(const DevScene& S, bool fresh, v3 o, v3 d, HitRec& best, int& check, bool& seen,
                                             int* tl, int stride, int32_t& cur, LocalCounters& lc, const FrontLds& L = FrontLds(),
                                             const float4* top = nullptr, int top_nodes = 0, int* bl = nullptr, int* sp_out = nullptr) {
@@ -74,7 +75,7 @@ __device__ __forceinline__ bool trace_front(const DevScene& S, bool fresh, v3 o,
           int sp = SP0;
           if (root < top_nodes) {
             BlasRay R = blas_ray(o, d);    // recomputed per MeshObject entered: keeping it live across the heap walk costs more (spills)
-            if (SP0 == 1) root = blas_walk_top_ptr<COUNT>(top, top_nodes, root, R, best.t, bl, sp, lc);
+            if (SP0 == 1) root = blas_walk_top_ptr<COUNT, CONES>(top, top_nodes, root, R, best.t, bl, sp, lc, CONES ? cone_ray_word(d) : 0);
             else do root = blas_node_step_top<COUNT>(top, root, R, best.t, bl, sp, lc); while (root >= 0 && root < top_nodes);
           }
           *sp_out = sp;
@@ -141,7 +142,7 @@ __device__ __forceinline__ int list_get(const int* tl, int j) {
 #define URT_FS_ARG
 #define URT_FS(stmt)
 #endif
-template <bool COUNT, int SP0 = 0>
+template <bool COUNT, int SP0 = 0, bool CONES = false>
 __device__ __forceinline__ int front_listed(const DevScene& S, const FrameParams& P, bool mine, bool fresh, v3 o, v3 d, HitRec& best, int& cs,
                                             int* tl, int32_t& cur, LocalCounters& lc, const FrontLds& L, const float4* top, int* bl, int& sp,
                                             unsigned int& wave_rays URT_FS_DECL) {
@@ -215,7 +216,7 @@ __device__ __forceinline__ int front_listed(const DevScene& S, const FrameParams
       sp = SP0;
       if (root < P.top_nodes) {
         BlasRay R = blas_ray(o, d);
-        if (SP0 == 1) root = blas_walk_top_ptr<COUNT>(top, P.top_nodes, root, R, best.t, bl, sp, lc);
+        if (SP0 == 1) root = blas_walk_top_ptr<COUNT, CONES>(top, P.top_nodes, root, R, best.t, bl, sp, lc, CONES ? cone_ray_word(d) : 0);
         else do root = blas_node_step_top<COUNT>(top, root, R, best.t, bl, sp, lc); while (root >= 0 && root < P.top_nodes);
       }
       cursor++; remaining--;
@@ -266,7 +267,7 @@ struct WalkLds {
   const int* pos_tab = nullptr;        // [2p] triangle-BVH root of the object at position p, [2p+1] its first triangle in small_tris or -1
   const float4* eval = nullptr;        // [2e] vmin.xyz, position bit of the parent (0: the root)  [2e+1] vmax.xyz, position bit
 };
-template <bool COUNT, int SP0 = 0>
+template <bool COUNT, int SP0 = 0, bool CONES = false>
 __device__ __forceinline__ int front_masked(const DevScene& S, const FrameParams& P, bool mine, bool fresh, v3 o, v3 d, HitRec& best, int& cs,
                                             int* tl, int32_t& cur, LocalCounters& lc, const FrontLds& L, const WalkLds& W, const float4* top, int* bl, int& sp,
                                             unsigned int& wave_rays URT_FS_DECL) {
@@ -346,7 +347,7 @@ __device__ __forceinline__ int front_masked(const DevScene& S, const FrameParams
       sp = SP0;
       if (root < P.top_nodes) {
         BlasRay R = blas_ray(o, d);
-        if (SP0 == 1) root = blas_walk_top_ptr<COUNT>(top, P.top_nodes, root, R, best.t, bl, sp, lc);
+        if (SP0 == 1) root = blas_walk_top_ptr<COUNT, CONES>(top, P.top_nodes, root, R, best.t, bl, sp, lc, CONES ? cone_ray_word(d) : 0);
         else do root = blas_node_step_top<COUNT>(top, root, R, best.t, bl, sp, lc); while (root >= 0 && root < P.top_nodes);
       }
       T &= T - 1u;

@@ -58,11 +58,16 @@ namespace {
 // 1: it first walks the LDS-resident top of that BVH inside FRONT (several meshes); 2: listed form of 1 (front_listed above).
 // QN: the traversal loop reads the 32-byte quantized nodes (S.blas_qnodes; never together with COUNT: the counting instantiation walks
 // the float nodes, like the oracle).
+// Normal cones (trace_device.h cone_skips, csrc/cones.hip): the instantiations that neither count nor read quantized nodes and-in "the ray does
+// not see this child's triangles from behind" into both child hits of every node step, in the walk of the LDS top and in the wave-wide loop.
+// The cone words ride in the nodes' two spare dwords and are 0 (never skip) while option "blas_cones" is off, so the instantiation — and its
+// name — is the same either way; the counting instantiation walks like the oracle, event for event.
 template <bool COUNT, int BLOCK, int FMODE, bool MULTI, bool QN = false>
 __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, FrameParams P, const FrameUniforms* __restrict__ T, float4* __restrict__ result, DevCounters* ctr,
                                                unsigned int* __restrict__ next) {
   // LDS of the workgroup: [top of the triangle-BVH forest: top_nodes x 64 B, shared by its waves][stacks of wave 0][wave 1]...
   // The waves of a workgroup share nothing else and never synchronise after this copy.
+  constexpr bool CONES = !COUNT && !QN;
   extern __shared__ int lds[];
   float4* lds4 = (float4*)lds;
   const float4* top = lds4;
@@ -221,8 +226,8 @@ __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, Fram
       if (FMODE < 2) wave_rays += (unsigned int)__popcll(wballot(st == ST_FRONT));     // Trace() invocations (RS:454), counted per wave
       if (FMODE >= 2) {
         bool mine = st == ST_FRONT || st == ST_RESUME;
-        int r = FMODE == 3 ? front_masked<COUNT, 1>(S, P, mine, st == ST_FRONT, o, d, best, cs, tl, cur, lc, L, W, top, bl, sp, wave_rays URT_FS_ARG)
-                           : front_listed<COUNT, 1>(S, P, mine, st == ST_FRONT, o, d, best, cs, tl, cur, lc, L, top, bl, sp, wave_rays URT_FS_ARG);
+        int r = FMODE == 3 ? front_masked<COUNT, 1, CONES>(S, P, mine, st == ST_FRONT, o, d, best, cs, tl, cur, lc, L, W, top, bl, sp, wave_rays URT_FS_ARG)
+                           : front_listed<COUNT, 1, CONES>(S, P, mine, st == ST_FRONT, o, d, best, cs, tl, cur, lc, L, top, bl, sp, wave_rays URT_FS_ARG);
         if (mine && r != 2) {
           if (r == 1) { best_i = -1; st = ST_BLAS; }
           else st = best.t < URT_INF ? ST_SHADE : ST_SKY;
@@ -230,7 +235,7 @@ __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, Fram
       } else if (st == ST_FRONT || st == ST_RESUME) {
         sp = 1;
         int check = cs & 0xff; bool seen = (cs >> 8) != 0;
-        bool need = FMODE == 1 ? trace_front<COUNT, true, false, 1>(S, st == ST_FRONT, o, d, best, check, seen, tl, 64, cur, lc, L, top, P.top_nodes, bl, &sp)
+        bool need = FMODE == 1 ? trace_front<COUNT, true, false, 1, CONES>(S, st == ST_FRONT, o, d, best, check, seen, tl, 64, cur, lc, L, top, P.top_nodes, bl, &sp)
                                : trace_front<COUNT, false, false, 1>(S, st == ST_FRONT, o, d, best, check, seen, tl, 64, cur, lc, L);
         cs = check | (seen ? 256 : 0);
         if (need) { best_i = -1; st = ST_BLAS; }
@@ -244,11 +249,12 @@ __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, Fram
       // own, at LDS latency: the first ~6 of its ~12 node visits then never wait for another lane's cache miss.  Same
       // visits in the same order as the wave-wide loop below would make; far children go on the lane's stack as usual.
       int* spp = bl + (sp - 1) * 64;                         // the top entry of the lane's stack: what a pop returns (height 1 = the sentinel)
+      const int rw = CONES ? cone_ray_word(d) : 0;           // the ray's word of the cone test: one register, live across the loop
       if (mine && cur >= 0 && cur < P.top_nodes) {           // (pointer-form stack here too: no address arithmetic per step)
         do {
           if (COUNT) lc.blas_nodes++;
           const float4* n = top + 4 * cur;
-          cur = blas_node_eval_ptr(n[0], n[1], n[2], n[3], R, best.t, spp);
+          cur = CONES ? blas_node_eval_cone_ptr(n[0], n[1], n[2], n[3], R, best.t, rw, spp) : blas_node_eval_ptr(n[0], n[1], n[2], n[3], R, best.t, spp);
         } while (cur >= 0 && cur < P.top_nodes);
       }
       // The loop works on ONE integer per lane: c = the cursor of the lanes that take part, kBlasDone for every other lane.  Both
@@ -285,7 +291,7 @@ __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, Fram
             if (COUNT) lc.blas_nodes++;
             const float4* n = (const float4*)((const char*)S.blas_cnodes + ((uint32_t)c << 6));
             float4 q0 = n[0], q1 = n[1], q2 = n[2], q3 = n[3];
-            c = blas_node_eval_ptr(q0, q1, q2, q3, R, best.t, spp);
+            c = CONES ? blas_node_eval_cone_ptr(q0, q1, q2, q3, R, best.t, rw, spp) : blas_node_eval_ptr(q0, q1, q2, q3, R, best.t, spp);
           }
         } else if (c < 0 && c != kBlasDone) {
           test_leaf<COUNT>(S, c, o, d, best, best_i, lc);

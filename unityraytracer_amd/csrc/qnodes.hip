@@ -117,7 +117,9 @@ __global__ __launch_bounds__(256) void k_quantize(const float4* __restrict__ nod
 }
 
 // The traversal's copy of the nodes: every child box as centre / half extent (include/urt_math.h box_center_form), child codes unchanged.
-//   q0 = c0.xyz, h0.x   q1 = h0.yz, c1.xy   q2 = c1.z, h1.xyz   q3 = child0, child1, 0, 0
+//   q0 = c0.xyz, h0.x   q1 = h0.yz, c1.xy   q2 = c1.z, h1.xyz   q3 = child0, child1, cone word of child 0, of child 1
+// The cone words are written as 0 here ("never skip", whatever the builder left in the node's spare dwords); csrc/cones.hip fills them
+// in afterwards while option "blas_cones" is on.
 __global__ __launch_bounds__(256) void k_center(const float4* __restrict__ nodes, int n_nodes, float4* __restrict__ cnodes) {
   int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= n_nodes) return;
@@ -129,7 +131,7 @@ __global__ __launch_bounds__(256) void k_center(const float4* __restrict__ nodes
   cnodes[4 * (size_t)n] = make_float4(c0[0], c0[1], c0[2], e0[0]);
   cnodes[4 * (size_t)n + 1] = make_float4(e0[1], e0[2], c1[0], c1[1]);
   cnodes[4 * (size_t)n + 2] = make_float4(c1[2], e1[0], e1[1], e1[2]);
-  cnodes[4 * (size_t)n + 3] = q3;
+  cnodes[4 * (size_t)n + 3] = make_float4(q3.x, q3.y, 0.0f, 0.0f);
 }
 
 }  // namespace

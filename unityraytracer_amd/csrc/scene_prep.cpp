@@ -9,6 +9,7 @@
 #include "lbvh.h"
 #include "refit.h"
 #include "qnodes.h"
+#include "cones.h"
 #include "cullflags.h"
 
 namespace urtd {
@@ -228,13 +229,22 @@ int verify_cull_flags(urt_context* ctx, const std::vector<int32_t>& words, const
 
 int requantize(urt_context* ctx);
 // (Re)derive what the trace kernels read from the [lo, hi] nodes of the prepared scene — after a build and after every refit: the
-// centre / half-extent copy (always) and the quantized copy (option qnodes).
+// centre / half-extent copy (always), the normal cones in its spare dwords (option blas_cones: a moved MeshObject turns its normals) and
+// the quantized copy (option qnodes).
 int rederive_nodes(urt_context* ctx) {
-  DevScene& S = ctx->scene.ds;
+  urt_context::Scene& C = ctx->scene;
+  DevScene& S = C.ds;
   S.blas_cnodes = nullptr;
-  if (ctx->scene.cbuf && ctx->scene.n_blas_nodes > 0) {
-    URT_HIP(ctx, center_nodes(S.blas_nodes, ctx->scene.n_blas_nodes, ctx->scene.cbuf, touch(ctx)));
-    S.blas_cnodes = ctx->scene.cbuf;
+  C.cones_in_use = false;
+  if (C.cbuf && C.n_blas_nodes > 0) {
+    URT_HIP(ctx, center_nodes(S.blas_nodes, C.n_blas_nodes, C.cbuf, touch(ctx)));
+    S.blas_cnodes = C.cbuf;
+    if (C.cone_rng[0] && C.cone_rng[1] && C.n_scene_tris > 0) {
+      if (!C.cone_ranges)         // the topology's: found once per prepared scene
+        URT_HIP(ctx, cone_ranges(S.blas_nodes, C.n_blas_nodes, std::max(1, C.scene_max_depth), C.cone_rng[0], C.cone_rng[1], &C.cone_ranges, touch(ctx)));
+      URT_HIP(ctx, cone_words(C.cone_ranges, C.n_blas_nodes, S.tri_verts, C.n_scene_tris, C.cbuf, touch(ctx)));
+      C.cones_in_use = true;
+    }
   }
   return requantize(ctx);
 }
@@ -505,6 +515,10 @@ int prepare_scene(urt_context* ctx) {
     return fail(ctx, URT_ERR_SCENE, "traversal stacks exceed the LDS of a compute unit");
   if (n_blas_nodes > 0) {                                     // the copy of the nodes the trace kernels traverse: child boxes as (centre, half extent)
     if ((rc = scene_alloc(ctx, &ctx->scene.cbuf, 4 * n_blas_nodes * sizeof(float4)))) return rc;
+  }
+  if (ctx->opt.blas_cones != 0 && n_blas_nodes > 0 && n_tris > 0) {      // normal cones (csrc/cones.hip): the children's triangle ranges, 2 x 16 B per node
+    if ((rc = scene_alloc(ctx, &ctx->scene.cone_rng[0], n_blas_nodes * sizeof(int4)))) return rc;
+    if ((rc = scene_alloc(ctx, &ctx->scene.cone_rng[1], n_blas_nodes * sizeof(int4)))) return rc;
   }
   if (ctx->opt.qnodes != 0 && n_blas_nodes > 0) {             // 32-byte quantized nodes for the traversal loop (csrc/qnodes.hip)
     if ((rc = scene_alloc(ctx, &ctx->scene.qbuf, (2 + 2 * n_blas_nodes) * sizeof(float4)))) return rc;

@@ -152,7 +152,7 @@ static constexpr int32_t kBlasDone = (int32_t)0x80000000;   // never a valid lea
 
 // per-ray constants of the slab test on centre / half-extent boxes (include/urt_math.h "Slab test of the triangle BVH ..."): the
 // traversal reads S.blas_cnodes, the (c, h) copy of the builders' [lo, hi] nodes —
-//   q0 = c0.xyz, h0.x   q1 = h0.yz, c1.xy   q2 = c1.z, h1.xyz   q3 = child0, child1 (int bits), 0, 0
+//   q0 = c0.xyz, h0.x   q1 = h0.yz, c1.xy   q2 = c1.z, h1.xyz   q3 = child0, child1 (int bits), cone words of the two children (0 = none)
 using BlasRay = CRay;
 __device__ __forceinline__ BlasRay blas_ray(v3 o, v3 d) { return cray(o, d); }
 // both children's [t near, t far]
@@ -223,6 +223,29 @@ __device__ __forceinline__ int32_t blas_node_eval_ptr(float4 q0, float4 q1, floa
   return blas_node_select_ptr(tn0 <= tf0, tn1 <= tf1, tn0, tn1, as_int(q3.x), as_int(q3.y), below, top_);
 }
 
+// Normal cones (csrc/cones.hip, option "blas_cones"): q3.z / q3.w of a (c, h) node hold one dword per child, four signed bytes
+// (ax, ay, az, T): every triangle below the child has its normal inside a cone about the axis a, and T is chosen so that
+//     ax rx + ay ry + az rz - 127 T > 0,   r = round(127 d),
+// implies d . (e1 x e2) >= 2^-16 |e1| |e2| for all of them (for | |d| - 1 | <= 2^-10; derivation in cones.hip): Moller-Trumbore's
+// det = -d . (e1 x e2) is then negative, test_triangle rejects every one of them (det < kEPSILON), and the child need not be entered.
+// Word 0 never skips (the test is strict): a child without a cone, and every child while the option is off.
+// The ray's word: the three rounded components and -127, one register, derived once per phase entry.
+__device__ __forceinline__ int cone_ray_word(v3 d) {
+  int x = (int)__builtin_rintf(f_max(f_min(127.0f * d.x, 127.0f), -127.0f));      // (minNum / maxNum: a NaN component becomes a bound)
+  int y = (int)__builtin_rintf(f_max(f_min(127.0f * d.y, 127.0f), -127.0f));
+  int z = (int)__builtin_rintf(f_max(f_min(127.0f * d.z, 127.0f), -127.0f));
+  return (x & 0xff) | ((y & 0xff) << 8) | ((z & 0xff) << 16) | (int)0x81000000u;
+}
+__device__ __forceinline__ bool cone_skips(float word, int rw) { return __builtin_amdgcn_sdot4(as_int(word), rw, 0, false) > 0; }
+// blas_node_eval_ptr with the cone test: a child the ray sees from behind counts as missed
+__device__ __forceinline__ int32_t blas_node_eval_cone_ptr(float4 q0, float4 q1, float4 q2, float4 q3, const BlasRay& R, float tbest, int rw, int*& top_) {
+  int32_t below = *top_;
+  float tn0, tf0, tn1, tf1;
+  cnode_slabs(q0, q1, q2, R, tbest, tn0, tf0, tn1, tf1);
+  bool h0 = tn0 <= tf0 && !cone_skips(q3.z, rw), h1 = tn1 <= tf1 && !cone_skips(q3.w, rw);
+  return blas_node_select_ptr(h0, h1, tn0, tn1, as_int(q3.x), as_int(q3.y), below, top_);
+}
+
 // The same step on a 32-byte QUANTIZED node (csrc/qnodes.hip): two dwordx4 loads instead of four.  The twelve planes are 16-bit grid
 // coordinates q; a plane's slab value is t = (origin + q cell - (o +- pad)) / d = fma(Q, S, B) with Q = 2^23 + q — built in ONE
 // instruction per plane by putting q into the mantissa of 2^23 (0x4B000000 | q) —, S = cell / d and B = (origin - (o +- pad)) / d - 2^23 S
@@ -286,13 +309,15 @@ __device__ __forceinline__ int32_t blas_node_step_top(const float4* top, int32_t
 
 // The walk of the LDS-resident top with the stack in pointer form (entry 0 of `bl` holds the sentinel, heights start at 1: k_sched and
 // k_serve): `sp` is the height before and after.  Six half-rate instructions fewer per step than the index form above.
-template <bool COUNT>
-__device__ __forceinline__ int32_t blas_walk_top_ptr(const float4* top, int top_nodes, int32_t cur, const BlasRay& R, float tbest, int* bl, int& sp, LocalCounters& lc) {
+// CONES: with the cone test (rw = cone_ray_word of the ray); never together with COUNT.
+template <bool COUNT, bool CONES = false>
+__device__ __forceinline__ int32_t blas_walk_top_ptr(const float4* top, int top_nodes, int32_t cur, const BlasRay& R, float tbest, int* bl, int& sp, LocalCounters& lc,
+                                                     int rw = 0) {
   int* spp = bl + (sp - 1) * 64;
   do {
     if (COUNT) lc.blas_nodes++;
     const float4* n = top + 4 * cur;
-    cur = blas_node_eval_ptr(n[0], n[1], n[2], n[3], R, tbest, spp);
+    cur = CONES ? blas_node_eval_cone_ptr(n[0], n[1], n[2], n[3], R, tbest, rw, spp) : blas_node_eval_ptr(n[0], n[1], n[2], n[3], R, tbest, spp);
   } while (cur >= 0 && cur < top_nodes);
   sp = ((int)(spp - bl) >> 6) + 1;
   return cur;

@@ -121,6 +121,16 @@ class Context:
             assert n2.value == n.value
         return buf[:2].copy(), buf[2:].view(np.uint32).reshape(n.value, 8), bool(use.value)
 
+    def read_scene_cones(self):
+        """(words[n_nodes, 2] u32, e1[n_tris, 3] f32, e2[n_tris, 3] f32, in_use) of the current device scene: the normal cones of option
+        "blas_cones" (include/urt.h urt_debug_read_scene_cones) and the edges of the leaf-order triangle records they were derived from."""
+        info = self.scene_info()
+        words = np.zeros((info["n_nodes"], 2), dtype=np.uint32)
+        edges = np.zeros((info["n_tris"], 6), dtype=np.float32)
+        use = C.c_int()
+        self.check(self.lib.urt_debug_read_scene_cones(self._h, words.ctypes.data_as(C.c_void_p), edges.ctypes.data_as(C.c_void_p), C.byref(use)))
+        return words, edges[:, :3].copy(), edges[:, 3:].copy(), bool(use.value)
+
     def ray_query(self, origins, directions, t_max=None, any_hit: bool = False):
         """Batched ray queries against the bound scene (include/urt.h urt_ray_query): what the frame kernels' Trace (RS:364-383)
         returns for each ray, bounded by t_max (exclusive; None = +inf; a scalar or one value per ray).
