@@ -256,8 +256,10 @@ URT_API int urt_render_aov(urt_context* ctx, urt_handle hit, urt_handle normal, 
  * guided by the `hit` and `normal` feature buffers of urt_render_aov and optionally by `albedo` (0 = no demodulation).  All five images
  * are existing RGBA32F textures (own or external) of one size.  Per pixel p: c_p = src.rgb, a_p = src.a, n_p = normal.xyz,
  * k_p = normal.w, z_p = hit.w, A_p = albedo.rgb.
- *  1. p passes through when k_p == 0, z_p is not finite or <= 0, or a component of c_p or n_p is not finite: dst = src bit for bit, and
- *     p is never a tap of another pixel.  Every other pixel is a surface pixel.
+ *  1. p passes through when k_p == 0, z_p is not finite or <= 0, a component of c_p or n_p is not finite, or a component of the float
+ *     quotient c_p / d_p (rule 2) is not finite or exceeds 2^120 in magnitude: dst = src bit for bit, and p is never a tap of another
+ *     pixel.  Every other pixel is a surface pixel.  (2^120: every pass output is a convex combination of values <= 2^120, weights >= 0
+ *     of sum <= 1, and its float evaluation adds at most ~28 roundings, so no sum reaches FLT_MAX and no later pass sees inf.)
  *  2. demodulation: d_p = fmaxf(A_p, 1e-3f) per channel (a NaN channel gives 1e-3) with an albedo target, else 1; the filter runs on
  *     c_p / d_p.
  *  3. pass i = 0 .. iterations - 1, tap spacing s = 2^i: taps q = p + s (dx, dy), dx, dy in -2..2; taps outside the image and pass-through
@@ -266,7 +268,12 @@ URT_API int urt_render_aov(urt_context* ctx, urt_handle hit, urt_handle normal, 
  *     where a term whose sigma is <= 0 is left out;  c'_p = sum w_pq c_q / sum w_pq  (the centre tap always counts).  c is the previous
  *     pass's output.
  *  4. dst.rgb = c_p d_p after the last pass, dst.a = a_p.
- * The kernels fold the constants so that each tap costs one exp2f; per channel, |result - formula in float64| <= 1e-4 (1 + |formula|).
+ * The kernels fold the constants so that each tap costs one exp2f.  Domain: per channel, |result - formula in float64| <= 1e-4 (1 +
+ * |formula|) where |c_p / d_p| <= 2^60 and every positive sigma (sigma_color 2^-i for each pass i that runs) and z_p lie in
+ * [2^-60, 2^60]: there the squares and the folded constants stay normal floats.  Outside that, for every input that rule 1 lets through,
+ * every filtered value c'_p before rule 4 is finite and lies within [min, max] of the c_q / d_q of the surface pixels q it can reach
+ * (|q - p| <= 2 (2^iterations - 1) in x and y), widened by 1e-5 of the largest magnitude among them; dst.rgb = c'_p d_p may overflow,
+ * at its own pixel only.
  * params == NULL: the defaults below (chosen on 4-frame accumulations of the mixed test scene and C4, DESIGN.md "Denoising").
  *  - like urt_render_aov, it submits the deferred frames first (src is usually a deferred blit's destination), then enqueues the passes
  *    on the context's stream and returns without synchronising.  The scene is not read (not prepared); urt_counters are not changed.

@@ -1,6 +1,7 @@
 """CPU: the denoiser entry point (include/urt.h urt_denoise) — the header compiles as C99, urt_DenoiseParams has one layout in gcc, ctypes
 and the C# binding, the defaults agree, the symbol is exported, Context.denoise and RayTraceMaster.Denoise validate their arguments
-before they call the library, and the float64 reference (tests/denoise_ref.py) passes its own sanity checks."""
+before they call the library, and the float64 reference (tests/denoise_ref.py) passes its own sanity checks, among them rule 1's clause
+on the demodulated colour and the containment and scale invariance that tests/test_gpu_denoise_range.py asks of the library."""
 import ctypes as C
 import os
 import re
@@ -10,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from denoise_ref import H, denoise_ref, surface_mask
+from denoise_ref import H, MAX_COLOR, demodulator, denoise_ref, reach, surface_mask, window_min_max
 from unityraytracer_amd import RayTraceMaster, _lib, unity_api
 from unityraytracer_amd._lib import UrtError
 
@@ -292,3 +293,87 @@ def test_reference_pass_through_rules():
     normal[0, 4, 2] = np.inf                    # normal not finite
     surf = surface_mask(color, hit, normal)
     assert not surf[0].any() and surf[1:].all()
+
+
+def test_reference_passes_through_an_overflowing_demodulated_colour():
+    """Rule 1 on the float32 quotient c / d: not finite, or above 2^120 in magnitude."""
+    rng = np.random.default_rng(4)
+    hit, normal = _guides(rng, 3, 8)
+    color = rng.uniform(0, 1, (3, 8, 4)).astype(np.float32)
+    albedo = np.full((3, 8, 4), 0.5, np.float32)
+    above = np.nextafter(MAX_COLOR, np.float32(np.inf))
+    color[0, 0, 0], albedo[0, 0, 0] = 1e36, 0.0             # finite over the 1e-3 floor: inf
+    color[0, 1, 1], albedo[0, 1, 1] = 1e36, np.nan          # a NaN albedo channel is 1e-3 too
+    color[0, 2, 2], albedo[0, 2, 2] = -3e38, 0.5            # -inf
+    color[0, 3, 0], albedo[0, 3, 0] = MAX_COLOR, 0.99       # finite, above 2^120
+    color[0, 4, 1], albedo[0, 4, 1] = -above, 1.0           # the first float past -2^120
+    color[0, 5, 2], albedo[0, 5, 2] = above, 8.0            # above 2^120 itself, but its quotient is not
+    color[0, 6, 0], albedo[0, 6, 0] = MAX_COLOR, 1.0        # 2^120 exactly is filtered
+    color[0, 7, 1], albedo[0, 7, 1] = -MAX_COLOR, 2.0
+    surf = surface_mask(color, hit, normal, albedo)
+    assert surf[0].tolist() == [False] * 5 + [True] * 3 and surf[1:].all()
+    plain = surface_mask(color, hit, normal)                # without albedo the quotient is the colour
+    assert plain[0].tolist() == [True, True, False, True, False, False, True, True] and plain[1:].all()
+    for alb, mask in ((albedo, surf), (None, plain)):
+        out = denoise_ref(color, hit, normal, alb, iterations=3, sigma_color=0, sigma_normal=0, sigma_depth=0)
+        np.testing.assert_array_equal(out[~mask], color[~mask])
+        assert np.isfinite(out).all() and (out[mask][:, :3] != color[mask][:, :3]).any(-1).all()
+
+
+def test_reference_survives_one_overflowing_texel():
+    """One texel of colour 1e36 over albedo 0 in a 67 x 33 all-surface image: the formula is finite and float32-representable at
+    every pixel, and equals the formula of the image with that pixel's kind set to 0."""
+    rng = np.random.default_rng(6)
+    h, w = 33, 67
+    hit, normal = _guides(rng, h, w)
+    color = (10.0 ** rng.uniform(-3, 3, (h, w, 4))).astype(np.float32)
+    albedo = rng.uniform(0, 1, (h, w, 4)).astype(np.float32)
+    color[h // 2, w // 2, :3], albedo[h // 2, w // 2, :3] = 1e36, 0.0
+    out = denoise_ref(color, hit, normal, albedo)
+    assert np.isfinite(out.astype(np.float32)).all()
+    masked = normal.copy()
+    masked[h // 2, w // 2, 3] = 0
+    np.testing.assert_array_equal(out, denoise_ref(color, hit, masked, albedo))
+    np.testing.assert_array_equal(out[h // 2, w // 2], color[h // 2, w // 2])
+
+
+@pytest.mark.parametrize("sig", ["all", "none", "color_1e-30", "color_1e38"])
+def test_formula_stays_within_the_hull_of_its_reach(sig):
+    """Property B of tests/test_gpu_denoise_range.py is a property of the formula: over the whole finite float range every filtered
+    value lies in [min, max] of the demodulated colours of the surface pixels within reach (float64: 125 roundings of 2^-53)."""
+    from test_gpu_denoise_range import B_SIGMAS, range_inputs
+    w, h = 41, 29
+    for it in (1, 5):
+        color, hit, normal, albedo = range_inputs(10 * w + it, w, h)
+        for alb in (None, albedo):
+            surf = surface_mask(color, hit, normal, alb)
+            s3 = np.broadcast_to(surf[..., None], (h, w, 3))
+            assert 0.5 * h * w < surf.sum() < h * w
+            d = demodulator(alb, color.shape).astype(np.float64)
+            out = denoise_ref(color, hit, normal, alb, iterations=it, **B_SIGMAS[sig])
+            np.testing.assert_array_equal(out[~surf], color[~surf])
+            with np.errstate(all="ignore"):
+                lo, hi = window_min_max(color[..., :3].astype(np.float64) / d, surf, reach(it))
+            slack = 1e-12 * np.maximum(np.abs(lo), np.abs(hi))
+            g = out[..., :3] / d
+            assert np.isfinite(g[s3]).all() and ((g >= lo - slack) & (g <= hi + slack))[s3].all()
+
+
+@pytest.mark.parametrize("k", [-40, -8, 8, 40])
+def test_formula_is_invariant_under_powers_of_two(k):
+    """Property C of tests/test_gpu_denoise_range.py is a property of the formula: colour and sigma_color times 2^k scale the result by
+    2^k, depth times 2^k leaves it alone (to 1e-12 relative)."""
+    from test_gpu_denoise_range import invariance_inputs
+    w, h = 41, 29
+    color, hit, normal, albedo = invariance_inputs(31 * w + k, w, h)
+    sig = dict(sigma_color=50.0, sigma_normal=0.5, sigma_depth=0.3)
+    c_scaled, z_scaled = color.copy(), hit.copy()
+    c_scaled[..., :3] = np.ldexp(color[..., :3], k)
+    z_scaled[..., 3] = np.ldexp(hit[..., 3], k)
+    for alb in (None, albedo):
+        surf = surface_mask(color, hit, normal, alb)
+        base = denoise_ref(color, hit, normal, alb, **sig)[..., :3][surf]
+        got = denoise_ref(c_scaled, hit, normal, alb, **dict(sig, sigma_color=50.0 * 2.0 ** k))[..., :3][surf]
+        np.testing.assert_allclose(got, base * 2.0 ** k, rtol=1e-12, atol=0)
+        got = denoise_ref(color, z_scaled, normal, alb, **sig)[..., :3][surf]
+        np.testing.assert_allclose(got, base, rtol=1e-12, atol=0)

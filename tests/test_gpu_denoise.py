@@ -40,7 +40,7 @@ def random_inputs(seed, w, h, miss=0.1, bad_color=0.02):
 
 def assert_matches_reference(got, color, hit, normal, albedo, what, **params):
     ref = denoise_ref(color, hit, normal, albedo, **params)
-    surf = surface_mask(color, hit, normal)
+    surf = surface_mask(color, hit, normal, albedo)
     assert got.view(np.uint32)[~surf].tobytes() == color.view(np.uint32)[~surf].tobytes(), f"{what}: pass-through texels"
     assert got[..., 3].view(np.uint32).tobytes() == color[..., 3].view(np.uint32).tobytes(), f"{what}: alpha"
     g, r = got[..., :3][surf].astype(np.float64), ref[..., :3][surf]

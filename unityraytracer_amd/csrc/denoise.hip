@@ -4,11 +4,17 @@
 // Two kernels, one pixel per lane, wave64.  A wave covers one 8 x 8 pixel tile and a 256-thread workgroup a 16 x 16 block, as k_aov:
 // the 25 taps of a wave are then the same 8 x 8 block shifted by s * (dx, dy), so each tap's loads coalesce into 8 rows of 128 bytes.
 //  - k_denoise_pack reads src, normal, hit and albedo once and writes one guide texel per pixel (n.xyz, z; z = -1 marks a pass-through
-//    pixel) and the demodulated colour (0 for a pass-through pixel, so that every colour texel a tap loads is finite).
+//    pixel) and the demodulated colour (0 for a pass-through pixel).  A pixel whose demodulated colour is not finite or exceeds 2^120
+//    passes through as well (rule 1), so every colour texel a tap loads is finite and at most 2^120 in magnitude.
 //  - k_denoise_pass<last> runs pass i with tap spacing s = 2^i: 25 taps, each two float4 loads (colour, guide) at clamped addresses and
 //    one exp2f; taps outside the image or on pass-through pixels get weight 0 by a select.  Passes ping-pong between two colour images;
 //    the last one remodulates into dst and copies src at pass-through pixels.
 // The constants of the exponent are folded on the host (log2(e), 4^i / sigma_c^2, 1 / sigma_n^2) and per pixel (1 / (sigma_z z_p)).
+// Domain (include/urt.h): the 1e-4 bound is promised where |c_p / d_p| <= 2^60 and every positive sigma (sigma_color 2^-i for each pass
+// i that runs) and z_p lie in [2^-60, 2^60]: there the squares and the folded constants stay normal floats.  Outside that, for every
+// finite input, no exponent is NaN (each term is a square times a positive constant; a square or a product that overflows gives
+// exp2f(-inf) = 0) and every filtered colour is finite and within the hull of the colours in its reach; only the last pass's
+// remodulation c'_p d_p may overflow, at its own pixel.
 #include <hip/hip_runtime.h>
 #include <float.h>
 
@@ -36,6 +42,10 @@ __device__ __forceinline__ PixelXY pixel_of_lane() {
   return {(int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3)};
 }
 
+// Largest demodulated colour that is filtered (include/urt.h rule 1).  Every pass output is a convex combination of its taps, and its
+// float evaluation adds at most ~28 roundings, so from values <= 2^120 no sum of the five passes reaches FLT_MAX.
+constexpr float kMaxColor = 0x1p120f;
+
 __device__ __forceinline__ bool finite3(float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
 
 __device__ __forceinline__ float4 demod(const float4* albedo, size_t pix) {
@@ -51,19 +61,22 @@ __global__ __launch_bounds__(256) void k_denoise_pack(const float4* __restrict__
   const size_t pix = (size_t)p.y * (size_t)width + (size_t)p.x;
   const float4 c = src[pix], n = normal[pix];
   const float z = hit[pix].w;
-  const bool surface = n.w != 0.0f && isfinite(z) && z > 0.0f && finite3(c) && finite3(n);
+  bool surface = n.w != 0.0f && isfinite(z) && z > 0.0f && finite3(c) && finite3(n);
+  float4 v = make_float4(c.x, c.y, c.z, 0.0f);
+  if (albedo) {
+    const float4 d = demod(albedo, pix);
+    v = make_float4(c.x / d.x, c.y / d.y, c.z / d.z, 0.0f);
+  }
+  // the demodulated colour must stay within 2^120: an inf quotient (a finite colour over a small albedo) or a larger value would turn
+  // the tap sums of the passes into inf and NaN.  The compare is false for NaN and inf as well.
+  surface = surface && fabsf(v.x) <= kMaxColor && fabsf(v.y) <= kMaxColor && fabsf(v.z) <= kMaxColor;
   if (!surface) {
     guide[pix] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
     col[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     return;
   }
   guide[pix] = make_float4(n.x, n.y, n.z, z);
-  if (albedo) {
-    const float4 d = demod(albedo, pix);
-    col[pix] = make_float4(c.x / d.x, c.y / d.y, c.z / d.z, 0.0f);
-  } else {
-    col[pix] = make_float4(c.x, c.y, c.z, 0.0f);
-  }
+  col[pix] = v;
 }
 
 template <bool kLast>
@@ -94,7 +107,7 @@ __global__ __launch_bounds__(256) void k_denoise_pass(const float4* __restrict__
       const int qx = p.x + K.step * (i - 2);
       const bool inside = in_y && qx >= 0 && qx < width;
       const size_t q = row + (size_t)min(max(qx, 0), width - 1);
-      const float4 gq = guide[q], cq = in[q];                    // finite for every pixel (pass-through: zeros, z = -1)
+      const float4 gq = guide[q], cq = in[q];                    // finite, |cq| <~ 2^120, for every pixel (pass-through: zeros, z = -1)
       float e = 0.0f;
       if (use_c) {
         const float dr = c.x - cq.x, dg = c.y - cq.y, db = c.z - cq.z;
