@@ -84,6 +84,11 @@ URT_API int urt_flush(urt_context* ctx);
 URT_API int urt_buffer_create(urt_context* ctx, int count, int stride, urt_handle* out_buffer);
 /* buffer.SetData(List<T>) — synchronous copy of count*stride bytes   RM:250 */
 URT_API int urt_buffer_set_data(urt_context* ctx, urt_handle buffer, const void* data, int count);
+/* buffer.SetData(data, managedStart, computeStart, count): elements first .. first+count-1 (Unity's ranged overload).  `data` points at
+ * the first of the `count` elements and is copied before the call returns; elements of a buffer that were never set read as zero bytes.
+ * count == 0 changes nothing; data equal to what the buffer holds dirties nothing, as with urt_buffer_set_data.
+ * URT_ERR_INVALID_ARGUMENT (nothing is written): first < 0, count < 0, first + count beyond the buffer, NULL data with count > 0. */
+URT_API int urt_buffer_set_data_range(urt_context* ctx, urt_handle buffer, int first, const void* data, int count);
 /* buffer.count / buffer.stride                                       RM:237 */
 URT_API int urt_buffer_get_info(urt_context* ctx, urt_handle buffer, int* out_count, int* out_stride);
 /* buffer.Release()                                                   RM:195-210, 238 */
@@ -538,7 +543,15 @@ typedef struct urt_counters {
  *                        behind: the reference's own back-face culling (RS:211) rejects every one of them, so the skip is exact.  A ray
  *                        that leaves a closed mesh no longer walks the boxes around its origin down to their leaves.  The counting
  *                        instantiation ("count_stats") and "qnodes" walk without it.  See urt_debug_read_scene_cones),
- *          "refit" (0/1, default 1: moved MeshObjects are refitted on the GPU instead of rebuilt — see urt_debug_refit_stats),
+ *          "refit" (0/1, default 1: moved and deformed MeshObjects are refitted on the GPU instead of rebuilt — see urt_debug_refit_stats;
+ *                   0 turns the in-place update off altogether),
+ *          "refit_vertices" (0/1, default 1: a SetData that changes elements of _Vertices / _Normals — same counts, _Indices untouched — is
+ *                            taken in place: only the changed element range is copied to the device, and the MeshObjects whose vertex
+ *                            span it meets are refitted / get their shading normals re-gathered; 0 = such a change prepares from scratch,
+ *                            matrix moves are still refitted — see urt_debug_deform_stats),
+ *          "refit_rebuild_pct" (0, the default = never | > 100: when the surface-area cost of a deformed MeshObject's refitted tree exceeds
+ *                               pct / 100 x the cost it had at the last full preparation, the in-place update is abandoned and the scene is
+ *                               prepared from scratch — see urt_debug_scene_cost),
  *          "watchdog_cap" (test hook: scheduler trips a wave may make before it gives up; 0 = auto = 2^24 x frames of the launch x
  *                          max(1, numRays x numBounces / 8))
  *          — tuning knobs; they change speed only, never pixels. */
@@ -568,6 +581,7 @@ URT_API urt_context* urt_group_context(urt_group* group, int rank);
 URT_API const char* urt_group_last_error(urt_group* group);          /* group may be NULL for create failures */
 URT_API int urt_group_buffer_create(urt_group* group, int count, int stride, urt_handle* out_buffer);            /* RM:247 */
 URT_API int urt_group_buffer_set_data(urt_group* group, urt_handle buffer, const void* data, int count);          /* RM:250 */
+URT_API int urt_group_buffer_set_data_range(urt_group* group, urt_handle buffer, int first, const void* data, int count);
 URT_API int urt_group_buffer_release(urt_group* group, urt_handle buffer);
 URT_API int urt_group_texture_create(urt_group* group, int width, int height, urt_handle* out_texture);          /* RM:834-840 */
 URT_API int urt_group_texture_set_pixels(urt_group* group, urt_handle texture, const float* rgba);
@@ -731,8 +745,19 @@ URT_API int urt_debug_build_walk_table(const urt_BVHNode* heap, int n_nodes, int
  * reference re-uploads every list when one object moves, RM:215-230 -> 262-336), the device scene is updated in place: materials and
  * object-level tables are re-packed, and MeshObjects whose localToWorldMatrix changed keep the topology of their triangle BVH — their
  * triangle records and boxes are recomputed on the GPU (csrc/refit.hip; option "refit" = 0 turns this off).  Reports MeshObjects
- * refitted and in-place preparations since the context was created. */
+ * refitted and in-place preparations since the context was created.  A deformed MeshObject (changed _Vertices, urt_debug_deform_stats)
+ * counts as refitted and its update as in place; a full preparation forced by "refit_rebuild_pct" counts as neither. */
 URT_API int urt_debug_refit_stats(urt_context* ctx, uint64_t* out_refitted_meshes, uint64_t* out_incremental_preparations);
+/* Deformation (option "refit_vertices"): a MeshObject is DEFORMED when the dirty element range of _Vertices meets the span of vertices its
+ * index range refers to, and has its normals changed when the dirty range of _Normals does.
+ * out6: deformed MeshObjects refitted, MeshObjects whose normals were re-gathered, vertex + normal bytes copied to the device by in-place
+ * updates, full preparations forced by "refit_rebuild_pct" — all since the context was created; then the largest cost ratio of the last
+ * in-place update as float bits, and 0 (reserved) */
+URT_API int urt_debug_deform_stats(urt_context* ctx, uint64_t out6[6]);
+/* The surface-area cost of every MeshObject's triangle BVH: the sum over its nodes and both children of area(child box) x (its triangle
+ * count for a leaf, 1 for a node) / area(root box); 0 for a MeshObject without nodes or with a root box of zero or non-finite area.
+ * per MeshObject: cost now and baseline cost (2 floats each); prepares a stale scene first */
+URT_API int urt_debug_scene_cost(urt_context* ctx, float* out, int n_meshes);
 /* What the library holds right now, PROCESS-WIDE (every context and group of the process; needs none): out4 = device bytes, pinned host
  * bytes, events, streams.  Counts only the library's own holders (csrc/owned.h) — not external textures, the caller's streams or what
  * the HIP runtime keeps for itself.  A context or group that is destroyed gives back everything it took. */

@@ -22,6 +22,7 @@ internal static class UrtNative {
     // ---- ComputeBuffer                                                                     RM:233-252, 195-210 --------
     [DllImport(Lib)] internal static extern int urt_buffer_create(IntPtr ctx, int count, int stride, out ulong buffer);
     [DllImport(Lib)] internal static extern int urt_buffer_set_data(IntPtr ctx, ulong buffer, IntPtr data, int count);
+    [DllImport(Lib)] internal static extern int urt_buffer_set_data_range(IntPtr ctx, ulong buffer, int first, IntPtr data, int count);
     [DllImport(Lib)] internal static extern int urt_buffer_get_info(IntPtr ctx, ulong buffer, out int count, out int stride);
     [DllImport(Lib)] internal static extern int urt_buffer_release(IntPtr ctx, ulong buffer);
 
@@ -167,6 +168,7 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern IntPtr urt_group_last_error(IntPtr group);
     [DllImport(Lib)] internal static extern int urt_group_buffer_create(IntPtr group, int count, int stride, out ulong buffer);
     [DllImport(Lib)] internal static extern int urt_group_buffer_set_data(IntPtr group, ulong buffer, IntPtr data, int count);
+    [DllImport(Lib)] internal static extern int urt_group_buffer_set_data_range(IntPtr group, ulong buffer, int first, IntPtr data, int count);
     [DllImport(Lib)] internal static extern int urt_group_buffer_release(IntPtr group, ulong buffer);
     [DllImport(Lib)] internal static extern int urt_group_texture_create(IntPtr group, int width, int height, out ulong texture);
     [DllImport(Lib)] internal static extern int urt_group_texture_set_pixels(IntPtr group, ulong texture, float[] rgba);
@@ -205,6 +207,8 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_host_dump_bvh(string path, IntPtr nodes, int nNodes, int depth, float[] rayStart3, float[] rayEnd3, out int lines);
     [DllImport(Lib)] internal static extern int urt_host_dump_normals(string path, IntPtr meshObjects, int nMeshes, float[] vertices, int nVertices, int[] indices, int nIndices, float[] normals, int nNormals, out int lines);
     [DllImport(Lib)] internal static extern int urt_debug_refit_stats(IntPtr ctx, out ulong refittedMeshes, out ulong incrementalPreparations);
+    [DllImport(Lib)] internal static extern int urt_debug_deform_stats(IntPtr ctx, [Out] ulong[] out6);   // deformed, renormed, bytes copied, forced rebuilds, cost-ratio float bits, 0
+    [DllImport(Lib)] internal static extern int urt_debug_scene_cost(IntPtr ctx, [Out] float[] out2PerMesh, int nMeshes);
     [DllImport(Lib)] internal static extern int urt_debug_live_resources([Out] ulong[] out4);   // process-wide: device bytes, pinned bytes, events, streams
     [DllImport(Lib)] internal static extern int urt_host_mesh_motion(IntPtr prevMeshObjects, IntPtr curMeshObjects, int n, IntPtr outMotion);   // 48 B per entry
     [DllImport(Lib)] internal static extern int urt_host_sphere_motion(IntPtr prevSpheres, IntPtr curSpheres, int n, IntPtr outMotion);

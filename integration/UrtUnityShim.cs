@@ -228,6 +228,50 @@ public static class UrtTemporal {
                                                 planeThreshold = planeThreshold, flags = 0 };
         UrtDevice.Check(UrtNative.urt_reproject_objects(ctx, in im, in p, in mo));                       // (e)
     }
+    /// Meshes change shape while the accumulated image is kept: RayTraceMaster.DeformMeshes of the Python mirror.  The steps of MoveObjects
+    /// with applyEdits() writing the new positions (and normals) of the deformed meshes' vertex spans through the ranged SetData and
+    /// re-uploading the rebuilt object-level heap; the library refits those meshes on the GPU (option "refit_vertices").  The motion table
+    /// holds the identity for every MeshObject but the deformed ones, whose entries are all NaN: urt_reproject_objects defines that as "no
+    /// history", so they restart at count 0, everything else keeps its history, and ResampleDisocclusions fills them.  (No per-vertex
+    /// motion vectors.)  nMeshObjects: length of _meshObjects; deformed: the indices of the deformed MeshObjects.
+    public static void DeformMeshes(int nMeshObjects, IEnumerable<int> deformed, Action applyEdits, Action<IntPtr, IntPtr, IntPtr> renderFeatureBuffers,
+                                    IntPtr prevColor, IntPtr prevCount, IntPtr prevHit, IntPtr prevNormal, IntPtr prevId,
+                                    IntPtr hit, IntPtr normal, IntPtr id, IntPtr color, IntPtr count, IntPtr motion, int width, int height,
+                                    Matrix4x4 prevViewProj, float maxHistory = 64.0f, float normalThreshold = 0.9f, float planeThreshold = 0.02f) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtTemporal: reproject on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        var table = new float[12 * nMeshObjects];
+        for (int k = 0; k < nMeshObjects; k++) table[12 * k] = table[12 * k + 4] = table[12 * k + 8] = 1.0f;      // the exact identity: not moved
+        foreach (int k in deformed) {
+            if (k < 0 || k >= nMeshObjects) throw new ArgumentOutOfRangeException(nameof(deformed), "UrtTemporal.DeformMeshes: no such MeshObject");
+            for (int j = 0; j < 12; j++) table[12 * k + j] = float.NaN;
+        }
+        renderFeatureBuffers(prevHit, prevNormal, prevId);
+        applyEdits();
+        renderFeatureBuffers(hit, normal, id);
+        if (meshTable != 0 && (tableCtx != ctx || meshTableCount != nMeshObjects)) {
+            if (tableCtx == ctx) UrtDevice.Check(UrtNative.urt_buffer_release(ctx, meshTable));
+            meshTable = 0;
+        }
+        GCHandle o = GCHandle.Alloc(table, GCHandleType.Pinned);
+        try {
+            if (meshTable == 0) UrtDevice.Check(UrtNative.urt_buffer_create(ctx, nMeshObjects, UrtNative.ObjectMotionStride, out meshTable));
+            meshTableCount = nMeshObjects;
+            UrtDevice.Check(UrtNative.urt_buffer_set_data(ctx, meshTable, o.AddrOfPinnedObject(), nMeshObjects));
+        } finally { o.Free(); }
+        tableCtx = ctx;
+        var mo = new UrtNative.ReprojectMotion { meshMotion = meshTable, sphereMotion = 0, movedMaxHistory = 0.0f, flags = 0 };
+        var m = new float[16];
+        for (int k = 0; k < 16; k++) m[k] = prevViewProj[k];
+        var im = new UrtNative.ReprojectImages {
+            prevColor = Wrap(ctx, prevColor, width, height), prevCount = Wrap(ctx, prevCount, width, height),
+            prevHit = Wrap(ctx, prevHit, width, height), prevNormal = Wrap(ctx, prevNormal, width, height), prevId = Wrap(ctx, prevId, width, height),
+            hit = Wrap(ctx, hit, width, height), normal = Wrap(ctx, normal, width, height), id = Wrap(ctx, id, width, height),
+            color = Wrap(ctx, color, width, height), count = Wrap(ctx, count, width, height), motion = Wrap(ctx, motion, width, height) };
+        var p = new UrtNative.ReprojectParams { prevWorldToClip = m, maxHistory = maxHistory, normalThreshold = normalThreshold,
+                                                planeThreshold = planeThreshold, flags = 0 };
+        UrtDevice.Check(UrtNative.urt_reproject_objects(ctx, in im, in p, in mo));
+    }
     public static void BlitAddHistory(IntPtr src, IntPtr dst, IntPtr count, int width, int height, float maxHistory = 64.0f) {
         if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtTemporal: blend on one rank's context (urt_group_context)");
         IntPtr ctx = UrtDevice.Handle;
@@ -265,6 +309,18 @@ public sealed class UrtComputeBuffer {
             IntPtr p = pin.AddrOfPinnedObject();
             UrtDevice.Check(UrtDevice.IsGroup ? UrtNative.urt_group_buffer_set_data(UrtDevice.Handle, handle, p, a.Length)
                                               : UrtNative.urt_buffer_set_data(UrtDevice.Handle, handle, p, a.Length));
+        } finally { pin.Free(); }
+    }
+    /// SetData(data, managedBufferStartIndex, computeBufferStartIndex, count): Unity's ranged overload (include/urt.h urt_buffer_set_data_range)
+    public void SetData<T>(List<T> data, int managedBufferStartIndex, int computeBufferStartIndex, int count) where T : struct {
+        if (managedBufferStartIndex < 0 || count < 0 || managedBufferStartIndex + count > data.Count)
+            throw new ArgumentOutOfRangeException(nameof(count), "SetData: the element range lies outside data");
+        T[] a = data.GetRange(managedBufferStartIndex, count).ToArray();
+        GCHandle pin = GCHandle.Alloc(a, GCHandleType.Pinned);
+        try {
+            IntPtr p = pin.AddrOfPinnedObject();
+            UrtDevice.Check(UrtDevice.IsGroup ? UrtNative.urt_group_buffer_set_data_range(UrtDevice.Handle, handle, computeBufferStartIndex, p, a.Length)
+                                              : UrtNative.urt_buffer_set_data_range(UrtDevice.Handle, handle, computeBufferStartIndex, p, a.Length));
         } finally { pin.Free(); }
     }
     public void Release() {

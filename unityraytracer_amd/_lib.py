@@ -17,17 +17,17 @@ ERROR_NAMES = {1: "INVALID_ARGUMENT", 2: "INVALID_HANDLE", 3: "NO_DEVICE", 4: "H
 # every symbol include/urt.h declares (tests check that the .so exports each of them)
 ABI_SYMBOLS = [
     "urt_abi_version", "urt_device_count", "urt_context_create", "urt_context_destroy", "urt_last_error", "urt_context_set_stream",
-    "urt_synchronize", "urt_flush", "urt_buffer_create", "urt_buffer_set_data", "urt_buffer_get_info", "urt_buffer_release", "urt_texture_create",
+    "urt_synchronize", "urt_flush", "urt_buffer_create", "urt_buffer_set_data", "urt_buffer_set_data_range", "urt_buffer_get_info", "urt_buffer_release", "urt_texture_create",
     "urt_texture_create_external", "urt_texture_set_pixels", "urt_texture_get_pixels", "urt_texture_get_info", "urt_texture_read_begin", "urt_texture_read_end", "urt_texture_read_begin_format", "urt_texture_read_end_format", "urt_texture_release",
     "urt_shader_set_buffer", "urt_shader_set_texture", "urt_shader_set_matrix", "urt_shader_set_vector", "urt_shader_set_float",
     "urt_shader_set_int", "urt_shader_dispatch", "urt_shader_dispatch_rows", "urt_blit_add", "urt_blit", "urt_texture_pack_rows",
     "urt_texture_unpack_rows", "urt_texture_unpack_rows_on", "urt_texture_pack_rows_rgb", "urt_texture_unpack_rows_rgb", "urt_ray_query", "urt_ray_query_device", "urt_radiance_query", "urt_radiance_query_device", "urt_render_aov", "urt_denoise", "urt_reproject", "urt_reproject_objects", "urt_blit_add_history", "urt_select_pixels", "urt_blend_samples", "urt_resample_below", "urt_set_option", "urt_get_counters", "urt_reset_counters", "urt_debug_build_blas", "urt_debug_get_blas", "urt_debug_blas_cache_stats",
-    "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_read_scene_cones", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_live_resources", "urt_debug_build_walk_table", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
+    "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_read_scene_cones", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_deform_stats", "urt_debug_scene_cost", "urt_debug_live_resources", "urt_debug_build_walk_table", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
     "urt_host_build_object_bvh", "urt_host_build_object_bvh_pairing", "urt_host_mesh_motion", "urt_host_sphere_motion", "urt_host_last_error", "urt_host_load_hdr", "urt_host_write_pfm", "urt_host_write_png", "urt_host_encode_srgb8", "urt_host_srgb8_first_floats",
     "urt_host_resize_rgba", "urt_host_io_last_error", "urt_host_log", "urt_host_log_scene_counts", "urt_host_log_tree_report", "urt_host_dump_bvh", "urt_host_dump_normals",
     "urt_host_debug_last_error",
     "urt_group_create", "urt_group_destroy", "urt_group_size", "urt_group_context", "urt_group_last_error", "urt_group_buffer_create",
-    "urt_group_buffer_set_data", "urt_group_buffer_release", "urt_group_texture_create", "urt_group_texture_set_pixels",
+    "urt_group_buffer_set_data", "urt_group_buffer_set_data_range", "urt_group_buffer_release", "urt_group_texture_create", "urt_group_texture_set_pixels",
     "urt_group_texture_get_pixels", "urt_group_texture_release", "urt_group_shader_set_buffer", "urt_group_shader_set_texture",
     "urt_group_shader_set_matrix", "urt_group_shader_set_vector", "urt_group_shader_set_float", "urt_group_shader_set_int",
     "urt_group_set_option", "urt_group_shader_dispatch", "urt_group_blit_add", "urt_group_blit", "urt_group_gather", "urt_group_flush",
@@ -161,6 +161,7 @@ def load():
         "urt_flush": ([vp], i),
         "urt_buffer_create": ([vp, i, i, C.POINTER(u64)], i),
         "urt_buffer_set_data": ([vp, u64, vp, i], i),
+        "urt_buffer_set_data_range": ([vp, u64, i, vp, i], i),
         "urt_buffer_get_info": ([vp, u64, pi, pi], i),
         "urt_buffer_release": ([vp, u64], i),
         "urt_texture_create": ([vp, i, i, C.POINTER(u64)], i),
@@ -210,6 +211,8 @@ def load():
         "urt_debug_launch_info": ([vp, C.POINTER(LaunchInfo)], i),
         "urt_debug_serve_stats": ([vp, vp], i),
         "urt_debug_refit_stats": ([vp, vp, vp], i),
+        "urt_debug_deform_stats": ([vp, vp], i),
+        "urt_debug_scene_cost": ([vp, vp, i], i),
         "urt_debug_live_resources": ([vp], i),
         "urt_debug_build_walk_table": ([vp, i, i, vp, vp, vp, i, pi], i),
         "urt_host_dump_normals": ([C.c_char_p, vp, i, vp, i, vp, i, vp, i, pi], i),
@@ -244,6 +247,7 @@ def load():
         "urt_group_last_error": ([vp], C.c_char_p),
         "urt_group_buffer_create": ([vp, i, i, C.POINTER(u64)], i),
         "urt_group_buffer_set_data": ([vp, u64, vp, i], i),
+        "urt_group_buffer_set_data_range": ([vp, u64, i, vp, i], i),
         "urt_group_buffer_release": ([vp, u64], i),
         "urt_group_texture_create": ([vp, i, i, C.POINTER(u64)], i),
         "urt_group_texture_set_pixels": ([vp, u64, vp], i),

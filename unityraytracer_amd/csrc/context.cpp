@@ -159,6 +159,39 @@ int urt_buffer_create(urt_context* ctx, int count, int stride, urt_handle* out_b
   URT_GUARD_END(ctx)
 }
 
+// The first and the last byte at which two ranges differ (false: they are equal): two passes of memcmp over blocks, then over bytes,
+// which costs what the one memcmp of equal data would.
+static bool differing_bytes(const uint8_t* a, const uint8_t* b, size_t n, size_t* first, size_t* last) {
+  constexpr size_t kBlock = 4096;
+  size_t i = 0;
+  while (i < n) { size_t len = std::min(kBlock, n - i); if (std::memcmp(a + i, b + i, len) != 0) break; i += len; }
+  if (i >= n) return false;
+  while (a[i] == b[i]) i++;
+  size_t j = n;
+  while (j > i + 1) { size_t len = std::min(kBlock, j - (i + 1)); if (std::memcmp(a + j - len, b + j - len, len) != 0) break; j -= len; }
+  while (j > i + 1 && a[j - 1] == b[j - 1]) j--;
+  *first = i; *last = j - 1;
+  return true;
+}
+
+// SetData of elements first .. first + count - 1 (arguments checked by the callers): data equal to what the buffer holds changes nothing and
+// dirties nothing (the reference re-uploads EVERY list whenever anything changed, RM:738-745; a compare costs what the copy would);
+// else the elements between the first and the last differing byte join the buffer's dirty range.
+static int set_data_elements(urt_context* ctx, urt_handle buffer, Buffer& b, int first, const void* data, int count) {
+  const size_t bytes = (size_t)count * (size_t)b.stride, at = (size_t)first * (size_t)b.stride;
+  int d0 = 0, d1 = b.count - 1;                              // a buffer that is set for the first time is new as a whole
+  if (b.has_data) {
+    size_t f = 0, l = 0;
+    if (bytes == 0 || !differing_bytes(b.host.data() + at, (const uint8_t*)data, bytes, &f, &l)) return URT_OK;
+    d0 = first + (int)(f / (size_t)b.stride); d1 = first + (int)(l / (size_t)b.stride);
+  }
+  if (bytes > 0) std::memcpy(b.host.data() + at, data, bytes);
+  b.has_data = true;
+  b.mark_dirty(d0, d1);
+  for (int s = 0; s < B_COUNT; s++) if (ctx->bound[s] == buffer) { ctx->scene_dirty = true; ctx->dirty_slots |= 1u << s; }
+  return URT_OK;
+}
+
 int urt_buffer_set_data(urt_context* ctx, urt_handle buffer, const void* data, int count) {
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   auto it = ctx->buffers.find(buffer);
@@ -166,14 +199,19 @@ int urt_buffer_set_data(urt_context* ctx, urt_handle buffer, const void* data, i
   Buffer& b = it->second;
   if (count < 0 || count > b.count) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "SetData: more elements than the buffer holds");
   if (count > 0 && !data) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "SetData: data is NULL");
-  // The reference re-uploads EVERY list whenever anything changed (RM:738-745): data equal to what the buffer already holds changes
-  // nothing and dirties nothing (a compare costs what the copy would)
-  const size_t bytes = (size_t)count * (size_t)b.stride;
-  if (b.has_data && (bytes == 0 || std::memcmp(b.host.data(), data, bytes) == 0)) return URT_OK;
-  if (count > 0) std::memcpy(b.host.data(), data, bytes);
-  b.has_data = true;
-  for (int s = 0; s < B_COUNT; s++) if (ctx->bound[s] == buffer) { ctx->scene_dirty = true; ctx->dirty_slots |= 1u << s; }
-  return URT_OK;
+  return set_data_elements(ctx, buffer, b, 0, data, count);
+}
+
+int urt_buffer_set_data_range(urt_context* ctx, urt_handle buffer, int first, const void* data, int count) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  auto it = ctx->buffers.find(buffer);
+  if (it == ctx->buffers.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "SetData: unknown buffer handle");
+  Buffer& b = it->second;
+  if (first < 0 || count < 0 || (long long)first + (long long)count > (long long)b.count)
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "SetData: the element range lies outside the buffer");
+  if (count > 0 && !data) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "SetData: data is NULL");
+  if (count == 0) return URT_OK;
+  return set_data_elements(ctx, buffer, b, first, data, count);
 }
 
 int urt_buffer_get_info(urt_context* ctx, urt_handle buffer, int* out_count, int* out_stride) {
@@ -632,6 +670,8 @@ const OptionRow kOptions[] = {
   {"blas_cones", &O::blas_cones, -1, 1, "blas_cones must be -1 (auto), 0 or 1", kStale | kOnChange, nullptr},
   {"front_cull", &O::front_cull, 0, 1, "front_cull must be 0 or 1", kFlushAgain | kStale | kOnChange, nullptr},
   {"refit", &O::refit, INT_MIN, INT_MAX, "", kBool | kStale, nullptr},
+  {"refit_vertices", &O::refit_vertices, INT_MIN, INT_MAX, "", kBool, nullptr},
+  {"refit_rebuild_pct", &O::refit_rebuild_pct, 0, INT_MAX, "refit_rebuild_pct must be 0 (never rebuild) or greater than 100", 0, [](int v) { return v == 0 || v > 100; }},
   {"watchdog_cap", &O::watchdog_cap, 0, INT_MAX, "watchdog_cap must be >= 0 (0 = auto)", 0, nullptr},
   {"xcd_run", &O::xcd_run, 0, 4096, "xcd_run must be in [0, 4096] (0 = auto)", 0, nullptr},
 };
@@ -764,6 +804,30 @@ int urt_debug_refit_stats(urt_context* ctx, uint64_t* out_refitted_meshes, uint6
   if (out_refitted_meshes) *out_refitted_meshes = ctx->refitted_meshes;
   if (out_incremental_preparations) *out_incremental_preparations = ctx->incremental_preps;
   return URT_OK;
+}
+
+int urt_debug_deform_stats(urt_context* ctx, uint64_t out6[6]) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (!out6) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "out6 is NULL");
+  uint32_t ratio_bits;
+  std::memcpy(&ratio_bits, &ctx->last_cost_ratio, 4);
+  out6[0] = ctx->deformed_meshes; out6[1] = ctx->renormed_meshes; out6[2] = ctx->deform_bytes; out6[3] = ctx->forced_rebuilds;
+  out6[4] = ratio_bits; out6[5] = 0;
+  return URT_OK;
+}
+
+int urt_debug_scene_cost(urt_context* ctx, float* out, int n_meshes) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (n_meshes < 0 || (n_meshes > 0 && !out)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "urt_debug_scene_cost: out is NULL or n_meshes negative");
+  URT_GUARD_BEGIN
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = current_scene(ctx)) return rc;
+  if (n_meshes != ctx->scene.ds.n_meshes) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "urt_debug_scene_cost: n_meshes is not the scene's number of MeshObjects");
+  std::vector<float> now, base;
+  if (int rc = scene_cost(ctx, now, base)) return rc;
+  for (int m = 0; m < n_meshes; m++) { out[2 * m] = now[(size_t)m]; out[2 * m + 1] = base[(size_t)m]; }
+  return URT_OK;
+  URT_GUARD_END(ctx)
 }
 
 int urt_debug_live_resources(uint64_t out4[4]) {

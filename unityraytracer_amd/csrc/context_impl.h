@@ -31,6 +31,13 @@ struct Buffer {
   int count = 0, stride = 0;
   std::vector<uint8_t> host;   // SetData copy (RM:250): the caller keeps ownership of its list
   bool has_data = false;
+  // elements that differ from what the prepared scene was made from: the union over every SetData / ranged SetData since the last
+  // preparation (empty while dirty_last < dirty_first); every preparation clears it
+  int dirty_first = 0, dirty_last = -1;
+  void mark_dirty(int first, int last) {
+    if (dirty_last < dirty_first) { dirty_first = first; dirty_last = last; }
+    else { dirty_first = std::min(dirty_first, first); dirty_last = std::max(dirty_last, last); }
+  }
 };
 
 struct Texture {
@@ -73,6 +80,8 @@ struct urt_context {
   // ---- options (urt_set_option; the table of names and ranges is in context.cpp) ------------------------------------------
   struct Options {
     int refit = 1;                          // 0 = always prepare from scratch
+    int refit_vertices = 1;                 // 0 = changed _Vertices / _Normals prepare from scratch (matrix moves are still refitted)
+    int refit_rebuild_pct = 0;              // a deformed MeshObject whose tree cost exceeds pct / 100 x its baseline forces a full preparation (0 = never, else > 100)
     int qnodes = 0;                         // 32-byte quantized nodes in the traversal loop: 0 = off (default: measured -1.3 % on C3 / C3D, +1.3 % on C4 / C5 — the loop waits on the latency of ONE dependent fetch per step, not on its width), 1 = on, -1 = on unless a MeshObject is only a few grid cells wide
     int count_stats = 0, time_dispatch = 0, kernel_mode = 3;
     int block_threads = 64, xcd_run = 0 /* auto */, work_shards = 64, frame_group = 64, refill_min = 16, waves_per_cu = 0 /* auto */, blas_min = 0 /* auto */, blas_exit = 0 /* auto */;
@@ -116,6 +125,9 @@ struct urt_context {
     std::vector<urtd::DeviceBuf<char>> scene_allocs;
     struct RefitAux {                       // device-resident (scene_allocs)
       const float* vertices = nullptr; const int32_t* indices = nullptr;      // copies of _Vertices / _Indices
+      const float* normals = nullptr;         // copy of _Normals (null when the scene has none)
+      int32_t* renormed = nullptr;            // per MeshObject: its shading normals are re-gathered by this update
+      double* cost_base = nullptr; double* cost_now = nullptr;   // per MeshObject (cost sum, root area): at the full preparation / now (csrc/refit.hip tree_cost)
       int32_t* parent = nullptr; int32_t* node_mesh = nullptr; int32_t* depth = nullptr;
       float4* cbox = nullptr; unsigned int* ext = nullptr;
       float* matrices = nullptr; int32_t* moved = nullptr;
@@ -140,6 +152,9 @@ struct urt_context {
     int tlas_stack = 2, blas_stack = 2;
     unsigned int watchdog_steps = 1u << 16;
     std::vector<int32_t> h_mesh_root, h_small_first;
+    std::vector<int32_t> h_vert_lo, h_vert_hi;   // per MeshObject: the smallest and largest vertex its index range refers to (lo > hi: none)
+    int n_vertices = 0, n_normals = 0;      // elements of _Vertices / _Normals the scene was prepared from
+    std::vector<float> h_cost_base;         // per MeshObject: tree cost at the full preparation (read back at the first need)
     std::vector<uint8_t> prev_mesh_objects; // the _MeshObjects records the scene was prepared from
   } scene;
   // These outlive a scene:
@@ -147,6 +162,8 @@ struct urt_context {
   float last_prepare_ms = 0;                // host wall time of the last scene preparation (buffers -> device scene)
   int last_builder = 0;                     // the triangle-BVH builder the last full preparation of a scene WITH MeshObjects used (0..3): one without leaves it as it was
   uint64_t refitted_meshes = 0, incremental_preps = 0;
+  uint64_t deformed_meshes = 0, renormed_meshes = 0, deform_bytes = 0, forced_rebuilds = 0;   // urt_debug_deform_stats
+  float last_cost_ratio = 0;                // largest cost / baseline among the deformed MeshObjects of the last in-place update
   urtd::BlasCache blas_cache;               // per-MeshObject BVHs of the previous scene (reused when a MeshObject is unchanged)
   int sched_groups = 0;                     // kernel_mode 3: workgroups per CU the last configuration counts on when fewer than the default fit (0 = default)
   urtd::DeviceBuf<float4> zero_sky;
@@ -308,6 +325,7 @@ int check_watchdog(urt_context* ctx);
 int strip_count(int group_rows, int first_row, int row_stride);
 // scene_prep.cpp
 int prepare_scene(urt_context* ctx);
+int scene_cost(urt_context* ctx, std::vector<float>& now, std::vector<float>& base);
 void free_scene(urt_context* ctx);
 bool build_walk_table(const Buffer* heap, int n_meshes, const std::vector<int32_t>& mesh_root, const std::vector<int32_t>& small_first,
                       std::vector<float>& out);

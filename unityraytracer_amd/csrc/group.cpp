@@ -251,6 +251,7 @@ int urt_group_buffer_create(urt_group* g, int count, int stride, urt_handle* out
   return create_replicated(g, out_buffer, "buffer_create", [](urt_context* c, void* a, urt_handle* h) { return urt_buffer_create(c, ((int*)a)[0], ((int*)a)[1], h); }, args);
 }
 int urt_group_buffer_set_data(urt_group* g, urt_handle buffer, const void* data, int count) { FORWARD(g, urt_buffer_set_data(c, buffer, data, count)); }
+int urt_group_buffer_set_data_range(urt_group* g, urt_handle buffer, int first, const void* data, int count) { FORWARD(g, urt_buffer_set_data_range(c, buffer, first, data, count)); }
 int urt_group_buffer_release(urt_group* g, urt_handle buffer) { FORWARD(g, urt_buffer_release(c, buffer)); }
 int urt_group_texture_create(urt_group* g, int width, int height, urt_handle* out_texture) {
   int args[2] = {width, height};

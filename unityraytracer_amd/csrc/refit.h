@@ -17,4 +17,13 @@ hipError_t refit_moved(float4* nodes, int n_nodes, float4* tri_verts, int n_tris
                        const int32_t* depth, int max_level, const int32_t* node_mesh, const float* matrices, const int32_t* moved,
                        unsigned int* ext, int n_meshes, float4* cbox, hipStream_t st);
 
+// MeshObjects with flagged[m] != 0 get the three object-space shading normals of each of their leaf-order triangles gathered again from
+// `normals` (device copy of _Normals) into tri_norms, as a build writes them.
+hipError_t refit_norms(float4* tri_norms, const float4* tri_verts, int n_tris, const float* normals, const int32_t* indices,
+                       const int32_t* flagged, hipStream_t st);
+
+// Surface-area cost of every MeshObject's tree, from the [lo, hi] nodes: out[2 m] = sum over its nodes and both children of area(child box)
+// x (triangles of a leaf, 1 for a node), out[2 m + 1] = area of its root box (0 for a MeshObject without nodes).  parent / node_mesh: refit_prepare's.
+hipError_t tree_cost(const float4* nodes, int n_nodes, const int32_t* parent, const int32_t* node_mesh, int n_meshes, double* out, hipStream_t st);
+
 }  // namespace urtd

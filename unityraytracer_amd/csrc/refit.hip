@@ -10,6 +10,12 @@
 //                  rebuild writes (blas_builder.cpp `records`) — and the MeshObject's largest |coordinate| (the box pad's scale);
 //   k_refit_level  bottom-up, one launch per tree level: a node's two child boxes from the new records (leaf children) or from the
 //                  level below (interior children), written with the builder's pad of 2^-16 x largest |coordinate| (blas_builder.cpp).
+// A DEFORMED MeshObject (elements of _Vertices changed under an unchanged topology: skinning, cloth, blend shapes) takes the same two passes
+// — the kernels do not distinguish a new matrix from new vertices — and two more exist for it:
+//   k_refit_norms  one lane per leaf-order triangle of a MeshObject whose _Normals changed: its three object-space shading normals are
+//                  gathered again into tri_norms, bit-identical to what blas_builder.cpp / lbvh.hip write at a build (RS:259-261);
+//   k_tree_cost    the surface-area cost of every MeshObject's tree from the [lo, hi] nodes, so that the host can tell a tree that a large
+//                  deformation has spoilt (scene_prep.cpp, option "refit_rebuild_pct").  It steers speed, never pixels.
 // Which nodes belong to which MeshObject, every node's parent and its depth are derived once per full scene preparation (k_parents,
 // k_node_mesh, k_depth) from the node array itself, so the refit works on trees of either builder (host SAH, GPU LBVH).
 // The box rule: a leaf child's box is the min / max of the RECONSTRUCTED vertices r0, r0 + e1, r0 + e2 of its records (what the triangle
@@ -149,9 +155,98 @@ __global__ __launch_bounds__(256) void k_refit_level(float4* __restrict__ nodes,
   nodes[4 * (size_t)n + 2] = make_float4(lo[1].z - pad, hi[1].x + pad, hi[1].y + pad, hi[1].z + pad);
 }
 
+// The shading normals of the leaf-order triangles of every MeshObject with flagged[m] != 0, from the device copy of _Normals: the slot of a
+// triangle's first index is kept in its record (v0.w), its MeshObject in e1.w, as k_refit_tris reads them.
+__global__ __launch_bounds__(256) void k_refit_norms(float4* __restrict__ tri_norms, const float4* __restrict__ tri_verts, int n_tris,
+                                                     const float* __restrict__ normals, const int32_t* __restrict__ indices,
+                                                     const int32_t* __restrict__ flagged) {
+  int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_tris) return;
+  const int slot = as_i(tri_verts[3 * (size_t)k].w), m = as_i(tri_verts[3 * (size_t)k + 1].w);
+  if (!flagged[m]) return;
+  for (int j = 0; j < 3; j++) {
+    const float* p = normals + 3 * (size_t)indices[slot + j];                   // RS:259-261
+    tri_norms[3 * (size_t)k + j] = make_float4(p[0], p[1], p[2], 0.0f);
+  }
+}
+
+__device__ __forceinline__ double box_area(float lx, float ly, float lz, float hx, float hy, float hz) {
+  const double dx = (double)hx - (double)lx, dy = (double)hy - (double)ly, dz = (double)hz - (double)lz;
+  return 2.0 * (dx * dy + dy * dz + dz * dx);
+}
+
+// Surface-area cost: every node adds area(child box) x (triangles of a leaf child, 1 for an interior child) for both children to its
+// MeshObject's sum out[2 m]; a root also writes the area of the union of its two child boxes to out[2 m + 1] (the host divides).  Terms that
+// are not finite add nothing.  The sums are float64 and added with the hardware's float64 atomic (`out` is the library's own device memory).
+// Same-address atomics are what bounds this kernel (one per wave: 6 - 15 ns each), so they are made few: a wave reduces the terms of its
+// first pending lane's MeshObject, then of the next one's, until none is left — neighbouring nodes nearly always belong to one MeshObject,
+// whichever builder numbered them — and the first such sum of each of a workgroup's four waves is combined in LDS before it is added.
+__global__ __launch_bounds__(256) void k_tree_cost(const float4* __restrict__ nodes, int n_nodes, const int32_t* __restrict__ parent,
+                                                   const int32_t* __restrict__ node_mesh, int n_meshes, double* __restrict__ out) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  int m = n < n_nodes ? node_mesh[n] : -1;
+  if (m >= n_meshes) m = -1;
+  double t = 0.0;
+  if (m >= 0) {
+    const float4 q0 = nodes[4 * (size_t)n], q1 = nodes[4 * (size_t)n + 1], q2 = nodes[4 * (size_t)n + 2], q3 = nodes[4 * (size_t)n + 3];
+    const int c0 = as_i(q3.x), c1 = as_i(q3.y);
+    const double a0 = box_area(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y) * (c0 < 0 ? (double)(((~(uint32_t)c0) & 7u) + 1u) : 1.0);
+    const double a1 = box_area(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w) * (c1 < 0 ? (double)(((~(uint32_t)c1) & 7u) + 1u) : 1.0);
+    if (a0 - a0 == 0.0) t += a0;                                                  // finite
+    if (a1 - a1 == 0.0) t += a1;
+    if (parent[n] < 0)
+      out[2 * (size_t)m + 1] = box_area(f_min(q0.x, q1.z), f_min(q0.y, q1.w), f_min(q0.z, q2.x), f_max(q0.w, q2.y), f_max(q1.x, q2.z), f_max(q1.y, q2.w));
+  }
+  __shared__ int s_mesh[4];
+  __shared__ double s_sum[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { s_mesh[wave] = -1; s_sum[wave] = 0.0; }
+  unsigned long long pending = __ballot(m >= 0 && t != 0.0);
+  for (bool first = true; pending; first = false) {
+    const int leader = __ffsll((long long)pending) - 1;
+    const int ml = __shfl(m, leader, 64);
+    double v = m == ml ? t : 0.0;
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == leader) {
+      if (first) { s_mesh[wave] = ml; s_sum[wave] = v; }
+      else unsafeAtomicAdd(&out[2 * (size_t)ml], v);
+    }
+    pending &= ~__ballot(m == ml);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int cm = -1;
+    double cv = 0.0;
+    for (int w = 0; w < 4; w++) {
+      if (s_mesh[w] < 0) continue;
+      if (s_mesh[w] != cm) {
+        if (cm >= 0) unsafeAtomicAdd(&out[2 * (size_t)cm], cv);
+        cm = s_mesh[w]; cv = 0.0;
+      }
+      cv += s_sum[w];
+    }
+    if (cm >= 0) unsafeAtomicAdd(&out[2 * (size_t)cm], cv);
+  }
+}
+
 }  // namespace
 
 namespace urtd {
+
+hipError_t refit_norms(float4* tri_norms, const float4* tri_verts, int n_tris, const float* normals, const int32_t* indices,
+                       const int32_t* flagged, hipStream_t st) {
+  if (n_tris <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_refit_norms, dim3((n_tris + 255) / 256), dim3(256), 0, st, tri_norms, tri_verts, n_tris, normals, indices, flagged);
+  return hipGetLastError();
+}
+
+hipError_t tree_cost(const float4* nodes, int n_nodes, const int32_t* parent, const int32_t* node_mesh, int n_meshes, double* out, hipStream_t st) {
+  if (n_meshes <= 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(out, 0, 2 * sizeof(double) * (size_t)n_meshes, st);
+  if (e != hipSuccess || n_nodes <= 0) return e;
+  hipLaunchKernelGGL(k_tree_cost, dim3((n_nodes + 255) / 256), dim3(256), 0, st, nodes, n_nodes, parent, node_mesh, n_meshes, out);
+  return hipGetLastError();
+}
 
 hipError_t refit_prepare(const float4* nodes, int n_nodes, const float4* tri_verts, int32_t* parent, int32_t* node_mesh, int32_t* depth, hipStream_t st) {
   if (n_nodes <= 0) return hipSuccess;

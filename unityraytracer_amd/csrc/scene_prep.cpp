@@ -354,30 +354,100 @@ int store_scene_tables(urt_context* ctx, const SceneTables& T) {
   return URT_OK;
 }
 
+// Every preparation ends the dirty element ranges of the bound buffers: they are relative to the scene that now exists.
+void clear_dirty_ranges(urt_context* ctx) {
+  for (int s = 0; s < B_COUNT; s++) {
+    auto it = ctx->buffers.find(ctx->bound[s]);
+    if (it != ctx->buffers.end()) { it->second.dirty_first = 0; it->second.dirty_last = -1; }
+  }
+}
+
+// Tree cost of every MeshObject from the (sum, root area) pairs of csrc/refit.hip tree_cost: 0 without nodes or with a root box of zero or
+// non-finite area.
+void costs_from_pairs(const std::vector<double>& pairs, std::vector<float>& out) {
+  out.assign(pairs.size() / 2, 0.0f);
+  for (size_t m = 0; m < out.size(); m++) {
+    const double sum = pairs[2 * m], area = pairs[2 * m + 1];
+    if (area > 0.0 && std::isfinite(area) && std::isfinite(sum)) out[m] = (float)(sum / area);
+  }
+}
+
+// The baseline costs (measured on the stream by the full preparation) reach the host at the first need.  Waits for the stream.
+int fetch_cost_base(urt_context* ctx) {
+  urt_context::Scene& C = ctx->scene;
+  const size_t n = (size_t)std::max(0, C.ds.n_meshes);
+  if (C.h_cost_base.size() == n) return URT_OK;
+  std::vector<double> pairs(2 * n, 0.0);
+  if (n > 0 && C.refit.cost_base) {
+    URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
+    URT_HIP(ctx, hipMemcpy(pairs.data(), C.refit.cost_base, pairs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  costs_from_pairs(pairs, C.h_cost_base);
+  return URT_OK;
+}
+
+// The costs of the trees as they are now.  Waits for the stream.
+int measure_cost_now(urt_context* ctx, std::vector<float>& now) {
+  urt_context::Scene& C = ctx->scene;
+  const size_t n = (size_t)std::max(0, C.ds.n_meshes);
+  std::vector<double> pairs(2 * n, 0.0);
+  if (n > 0 && C.refit.cost_now && C.refit.ready) {
+    URT_HIP(ctx, tree_cost(C.ds.blas_nodes, C.n_blas_nodes, C.refit.parent, C.refit.node_mesh, (int)n, C.refit.cost_now, touch(ctx)));
+    URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
+    URT_HIP(ctx, hipMemcpy(pairs.data(), C.refit.cost_now, pairs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  costs_from_pairs(pairs, now);
+  return URT_OK;
+}
+
 // The dynamic-scene path (RM:215-230: a moved object makes the reference re-upload every buffer).  When the only contents that changed
 // since the scene was prepared are those of _MeshObjects / _MeshBVH / _Spheres / _SphereBVH — same counts, same index ranges per
 // MeshObject — the device scene is UPDATED: materials, object-level heaps and sphere tables are re-packed (a few KB), and every
 // MeshObject whose localToWorldMatrix changed keeps its triangle BVH's topology: its triangle records and boxes are recomputed on the
-// GPU (csrc/refit.hip).  Returns 1 when the change is not of that kind (the caller prepares from scratch).
+// GPU (csrc/refit.hip).  Changed contents of _Vertices / _Normals — same counts, _Indices untouched — are taken the same way (option
+// "refit_vertices"): only the dirty element range is copied into the device copy, a MeshObject whose vertex span meets the dirty range of
+// _Vertices is DEFORMED and refitted together with the moved ones, and one whose span meets the dirty range of _Normals has its shading
+// normals gathered again.  Returns 1 when the change is not of that kind, or when option "refit_rebuild_pct" finds the refitted tree of a
+// deformed MeshObject too costly (the caller prepares from scratch).
 int prepare_incremental(urt_context* ctx) {
   const unsigned int small = (1u << B_MESHOBJECTS) | (1u << B_MESHBVH) | (1u << B_SPHERES) | (1u << B_SPHEREBVH);
+  const unsigned int geometry = (1u << B_VERTICES) | (1u << B_NORMALS);
   urt_context::Scene& C = ctx->scene;
-  if (!ctx->opt.refit || ctx->dirty_full || C.scene_allocs.empty() || (ctx->dirty_slots & ~small)) return 1;
+  if (!ctx->opt.refit || ctx->dirty_full || C.scene_allocs.empty()) return 1;
+  if (ctx->dirty_slots & ~(small | (ctx->opt.refit_vertices ? geometry : 0u))) return 1;
   DevScene& S = C.ds;
   const Buffer* bm = bound_buffer(ctx, B_MESHOBJECTS);
   const Buffer* bs = bound_buffer(ctx, B_SPHERES);
   const int n_meshes = bm ? bm->count : 0, n_spheres = bs ? bs->count : 0;
   if (n_meshes != S.n_meshes || n_spheres != S.n_spheres) return 1;
   if ((size_t)n_meshes * URT_STRIDE_MESHOBJECT != C.prev_mesh_objects.size()) return 1;
+  // changed vertices / normals: the buffers must be the ones (by size) the scene was prepared from
+  const Buffer* bv = (ctx->dirty_slots & (1u << B_VERTICES)) ? bound_buffer(ctx, B_VERTICES) : nullptr;
+  const Buffer* bn = (ctx->dirty_slots & (1u << B_NORMALS)) ? bound_buffer(ctx, B_NORMALS) : nullptr;
+  if (ctx->dirty_slots & geometry) {
+    const Buffer* v = bound_buffer(ctx, B_VERTICES); const Buffer* n = bound_buffer(ctx, B_NORMALS);
+    if ((v ? v->count : 0) != C.n_vertices || (n ? n->count : 0) != C.n_normals) return 1;
+    if (!C.refit.ready || C.n_scene_tris <= 0 || C.h_vert_lo.size() != (size_t)n_meshes) return 1;
+    if (bv && (!C.refit.vertices || bv->dirty_last < bv->dirty_first)) return 1;
+    if (bn && (!C.refit.normals || !C.refit.renormed || bn->dirty_last < bn->dirty_first)) return 1;
+  }
   auto t_begin = std::chrono::steady_clock::now();
-  std::vector<int32_t> moved((size_t)n_meshes, 0);
+  std::vector<int32_t> moved((size_t)n_meshes, 0), renormed((size_t)n_meshes, 0);
+  std::vector<char> deformed((size_t)n_meshes, 0);
   std::vector<float> matrices((size_t)n_meshes * 16, 0.0f);
-  int n_moved = 0;
+  int n_moved = 0, n_deformed = 0, n_renormed = 0;
   for (int m = 0; m < n_meshes; m++) {
     const urt_MeshObject a = mesh_object(C.prev_mesh_objects, m), b = mesh_object(bm->host, m);
     if (a.indices_offset != b.indices_offset || a.indices_count != b.indices_count) return 1;
     std::memcpy(&matrices[(size_t)m * 16], b.localToWorldMatrix, 64);
-    if (std::memcmp(a.localToWorldMatrix, b.localToWorldMatrix, 64) != 0 && b.indices_count >= 3) { moved[(size_t)m] = 1; n_moved++; }
+    if (b.indices_count < 3) continue;
+    bool refit = std::memcmp(a.localToWorldMatrix, b.localToWorldMatrix, 64) != 0;
+    if (bv || bn) {
+      const int lo = C.h_vert_lo[(size_t)m], hi = C.h_vert_hi[(size_t)m];      // (conservative: a vertex inside the span that no index names counts)
+      if (bv && lo <= bv->dirty_last && hi >= bv->dirty_first) { deformed[(size_t)m] = 1; n_deformed++; refit = true; }
+      if (bn && lo <= bn->dirty_last && hi >= bn->dirty_first) { renormed[(size_t)m] = 1; n_renormed++; }
+    }
+    if (refit) { moved[(size_t)m] = 1; n_moved++; }
   }
   if (n_moved > 0 && (!C.refit.ready || C.n_scene_tris <= 0)) return 1;
   URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));           // frames in flight read the arrays that are about to change
@@ -385,17 +455,52 @@ int prepare_incremental(urt_context* ctx) {
   SceneTables T;
   if ((rc = pack_scene_tables(ctx, bm, bs, bound_buffer(ctx, B_MESHBVH), bound_buffer(ctx, B_SPHEREBVH), C.h_mesh_root, C.h_small_first, T))) return rc;
   if ((rc = store_scene_tables(ctx, T))) return rc;
+  // the dirty element ranges go into the device copies, on the stream, behind the wait above and ahead of the kernels that read them
+  // (the host memory is the buffer's own copy; the stream is waited for below, before a later SetData can change it)
+  uint64_t copied = 0;
+  if (bv) {
+    const size_t at = (size_t)bv->dirty_first * 12, bytes = (size_t)(bv->dirty_last - bv->dirty_first + 1) * 12;
+    URT_HIP(ctx, hipMemcpyAsync((char*)const_cast<float*>(C.refit.vertices) + at, bv->host.data() + at, bytes, hipMemcpyHostToDevice, touch(ctx)));
+    copied += bytes;
+  }
+  if (bn) {
+    const size_t at = (size_t)bn->dirty_first * 12, bytes = (size_t)(bn->dirty_last - bn->dirty_first + 1) * 12;
+    URT_HIP(ctx, hipMemcpyAsync((char*)const_cast<float*>(C.refit.normals) + at, bn->host.data() + at, bytes, hipMemcpyHostToDevice, touch(ctx)));
+    copied += bytes;
+  }
   if (n_moved > 0) {
     URT_HIP(ctx, hipMemcpy(C.refit.matrices, matrices.data(), matrices.size() * sizeof(float), hipMemcpyHostToDevice));
     URT_HIP(ctx, hipMemcpy(C.refit.moved, moved.data(), moved.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     URT_HIP(ctx, refit_moved(const_cast<float4*>(S.blas_nodes), C.n_blas_nodes, const_cast<float4*>(S.tri_verts), C.n_scene_tris,
                              C.refit.vertices, C.refit.indices, C.refit.depth, std::max(0, C.scene_max_depth - 1), C.refit.node_mesh,
                              C.refit.matrices, C.refit.moved, C.refit.ext, n_meshes, C.refit.cbox, touch(ctx)));
-    ctx->refitted_meshes += (uint64_t)n_moved;
-    if ((rc = rederive_nodes(ctx))) return rc;
   }
+  if (n_renormed > 0 && S.tri_norms) {
+    URT_HIP(ctx, hipMemcpy(C.refit.renormed, renormed.data(), renormed.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    URT_HIP(ctx, refit_norms(const_cast<float4*>(S.tri_norms), S.tri_verts, C.n_scene_tris, C.refit.normals, C.refit.indices, C.refit.renormed, touch(ctx)));
+  }
+  if (n_moved > 0 && (rc = rederive_nodes(ctx))) return rc;
   if ((rc = verify_cull_flags(ctx, T.cull, T.mesh_leaf))) return rc;       // against the (refitted) triangle records
+  if (copied > 0) URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));            // the copies have left the buffers' host memory
+  if (n_deformed > 0) {
+    // a refit keeps the topology, and a large deformation can make it a bad one: the cost of each deformed MeshObject's refitted tree
+    // against what it was when the tree was built
+    std::vector<float> now;
+    if ((rc = fetch_cost_base(ctx))) return rc;
+    if ((rc = measure_cost_now(ctx, now))) return rc;
+    float worst = 0.0f;
+    for (int m = 0; m < n_meshes; m++)
+      if (deformed[(size_t)m] && C.h_cost_base[(size_t)m] > 0.0f) worst = std::max(worst, now[(size_t)m] / C.h_cost_base[(size_t)m]);
+    ctx->last_cost_ratio = worst;
+    if (ctx->opt.refit_rebuild_pct > 0 && worst * 100.0f > (float)ctx->opt.refit_rebuild_pct) {
+      ctx->forced_rebuilds++;
+      return 1;                                               // the full preparation reads the buffers, not what was refitted here
+    }
+  }
+  ctx->refitted_meshes += (uint64_t)n_moved;
+  ctx->deformed_meshes += (uint64_t)n_deformed; ctx->renormed_meshes += (uint64_t)n_renormed; ctx->deform_bytes += copied;
   if (bm) C.prev_mesh_objects.assign(bm->host.begin(), bm->host.begin() + (ptrdiff_t)((size_t)n_meshes * URT_STRIDE_MESHOBJECT));
+  clear_dirty_ranges(ctx);
   ctx->scene_dirty = false; ctx->dirty_slots = 0; ctx->dirty_full = false;
   ctx->scene_epoch++;
   ctx->incremental_preps++;
@@ -466,7 +571,7 @@ int prepare_scene(urt_context* ctx) {
       rc = lbvh_build(in, touch(ctx), o, err);
       if (rc) return fail(ctx, rc, err);
       ctx->scene.scene_allocs.push_back(std::move(raw));                 // _Vertices / _Indices stay resident: a moved MeshObject is refitted from them
-      ctx->scene.refit.vertices = in.vertices; ctx->scene.refit.indices = in.indices;
+      ctx->scene.refit.vertices = in.vertices; ctx->scene.refit.indices = in.indices; ctx->scene.refit.normals = in.normals;
       for (DeviceBuf<char>& a : o.allocs) ctx->scene.scene_allocs.push_back(std::move(a));
       S.mesh_root = o.mesh_root; S.blas_nodes = o.nodes; S.tri_verts = o.tri_verts; S.tri_norms = o.tri_norms;
       mesh_root_host = o.h_mesh_root; blas_max_depth = o.max_depth; n_blas_nodes = (size_t)o.n_nodes; n_tris = (size_t)o.n_tris;
@@ -537,6 +642,23 @@ int prepare_scene(urt_context* ctx) {
       URT_HIP(ctx, hipMemcpy(dv, bv->host.data(), (size_t)bv->count * 12, hipMemcpyHostToDevice));
       URT_HIP(ctx, hipMemcpy(di, bi->host.data(), (size_t)bi->count * 4, hipMemcpyHostToDevice));
       R.vertices = dv; R.indices = di;
+      if (bn) {
+        float* dn = nullptr;
+        if ((rc = scene_alloc(ctx, &dn, (size_t)bn->count * 12))) return rc;
+        URT_HIP(ctx, hipMemcpy(dn, bn->host.data(), (size_t)bn->count * 12, hipMemcpyHostToDevice));
+        R.normals = dn;
+      }
+    }
+    {   // the span of vertices every MeshObject's index range refers to: a later SetData of _Vertices / _Normals deforms the MeshObjects
+        // whose span its dirty range meets (prepare_incremental).  The builders have checked the ranges and the indices.
+      C.h_vert_lo.assign((size_t)n_meshes, 0); C.h_vert_hi.assign((size_t)n_meshes, -1);
+      const int32_t* idx = (const int32_t*)bi->host.data();
+      for (int m = 0; m < n_meshes; m++) {
+        const urt_MeshObject mo = mesh_object(bm->host, m);
+        int32_t lo = INT32_MAX, hi = -1;
+        for (long i = mo.indices_offset, e = (long)mo.indices_offset + (long)(mo.indices_count / 3) * 3; i < e; i++) { lo = std::min(lo, idx[i]); hi = std::max(hi, idx[i]); }
+        C.h_vert_lo[(size_t)m] = lo; C.h_vert_hi[(size_t)m] = hi;
+      }
     }
     size_t nn = std::max<size_t>(1, n_blas_nodes);
     if ((rc = scene_alloc(ctx, &R.parent, nn * 4))) return rc;
@@ -546,13 +668,27 @@ int prepare_scene(urt_context* ctx) {
     if ((rc = scene_alloc(ctx, &R.ext, (size_t)n_meshes * 4))) return rc;
     if ((rc = scene_alloc(ctx, &R.matrices, (size_t)n_meshes * 64))) return rc;
     if ((rc = scene_alloc(ctx, &R.moved, (size_t)n_meshes * 4))) return rc;
+    if ((rc = scene_alloc(ctx, &R.renormed, (size_t)n_meshes * 4))) return rc;
+    if ((rc = scene_alloc(ctx, &R.cost_base, (size_t)n_meshes * 16))) return rc;
+    if ((rc = scene_alloc(ctx, &R.cost_now, (size_t)n_meshes * 16))) return rc;
     URT_HIP(ctx, refit_prepare(S.blas_nodes, (int)n_blas_nodes, S.tri_verts, R.parent, R.node_mesh, R.depth, touch(ctx)));
+    // the cost of every tree as built: the baseline a deformed MeshObject's refitted tree is held against (read back when first needed)
+    URT_HIP(ctx, tree_cost(S.blas_nodes, (int)n_blas_nodes, R.parent, R.node_mesh, n_meshes, R.cost_base, touch(ctx)));
     R.ready = true;
   }
+  C.n_vertices = bv ? bv->count : 0; C.n_normals = bn ? bn->count : 0;
+  clear_dirty_ranges(ctx);
   ctx->scene_dirty = false; ctx->dirty_slots = 0; ctx->dirty_full = false;
   ctx->scene_epoch++;
   ctx->last_prepare_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   return URT_OK;
+}
+
+// urt_debug_scene_cost: per MeshObject the cost of its tree now and at the last full preparation (all 0 without "refit": nothing is kept).
+int scene_cost(urt_context* ctx, std::vector<float>& now, std::vector<float>& base) {
+  if (int rc = fetch_cost_base(ctx)) return rc;
+  base = ctx->scene.h_cost_base;
+  return measure_cost_now(ctx, now);
 }
 
 }  // namespace urtd

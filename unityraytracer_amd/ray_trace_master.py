@@ -485,6 +485,91 @@ class RayTraceMaster:
         self._tspare = (self._converged, self._tcount)
         self._converged, self._tcount = color, count
 
+    def vertex_span(self, k: int) -> tuple:
+        """(first, last) vertex the index range of MeshObject k refers to; (0, -1) when it has no triangle."""
+        s = self.scene
+        mo = s.mesh_objects[k]
+        sl = np.asarray(s.indices[int(mo["indices_offset"]): int(mo["indices_offset"]) + int(mo["indices_count"]) // 3 * 3])
+        return (int(sl.min()), int(sl.max())) if sl.size else (0, -1)
+
+    # Meshes change SHAPE (skinning, cloth, blend shapes): edits = {MeshObject index: (n, 3) object-space positions for that mesh's vertex
+    # span}, the span being the vertices its index range refers to, first to last (vertex_span).  The positions go into the scene's
+    # vertex list and reach the library through ranged SetData, one call per span; with recompute_normals the normals are recomputed
+    # (host_scene.compute_normals welds across meshes, so whatever changed is uploaded); the object-level heap is rebuilt from the new
+    # bounds.  The library refits the deformed meshes on the GPU (include/urt.h option "refit_vertices").  Temporal accumulation off, or
+    # no history yet: the accumulation restarts.  On: the MoveObjects protocol with an all-NaN motion entry for each deformed mesh, which
+    # urt_reproject_objects defines as "no history": the deformed meshes restart at count 0, everything else keeps its history, and
+    # ResampleDisocclusions fills them.  (Per-vertex motion vectors are out of scope.)
+    def DeformMeshes(self, edits, recompute_normals: bool = True):
+        s = self.scene
+        edits = dict(edits)
+        if self._treesNeedRebuilding and self._rayTraceObjects:                    # the lists the indices refer to do not exist yet
+            self.RebuildObjectLists()
+        n = len(s.mesh_objects)
+        for k in edits:
+            if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+                raise TypeError(f"DeformMeshes: the keys of edits must be ints, not {type(k).__name__}")
+            if not 0 <= k < n:
+                raise IndexError(f"DeformMeshes: edits names MeshObject {k}, the scene has {n}")
+        spans, checked = {}, {}
+        for k, pos in edits.items():
+            lo, hi = spans[k] = self.vertex_span(k)
+            try:
+                a = np.ascontiguousarray(pos, dtype=np.float32)
+            except (TypeError, ValueError):
+                raise ValueError(f"DeformMeshes: edits[{k}] must be an (n, 3) array of positions") from None
+            if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] != hi - lo + 1:
+                raise ValueError(f"DeformMeshes: edits[{k}] must have shape ({hi - lo + 1}, 3), the vertex span of MeshObject {k}, not {a.shape}")
+            checked[k] = a
+        history = self._temporal is not None and self._converged is not None and self._currentSample > 0 and not self._treesNeedRebuilding \
+            and (self._converged.width, self._converged.height) == (self.screen_width, self.screen_height)
+        if history:
+            self._ensure_temporal_textures()
+            prev_m = scenes.world_to_clip(s.camera_to_world, s.camera_inverse_projection)
+            prev, cur = self._taov
+            self.SetShaderParameters()
+            self.ctx.render_aov(prev[0], prev[1], None, prev[2])               # the scene as the history saw it
+        vertices = np.array(s.vertices, dtype=np.float32).reshape(-1, 3)           # (a copy: the caller's scene arrays are not written)
+        for k, a in checked.items():
+            vertices[spans[k][0]: spans[k][1] + 1] = a
+        s.vertices = vertices
+        uploaded = not self._treesNeedRebuilding and self._vertexBuffer is not None      # else the next frame uploads everything anyway
+        if uploaded:
+            for k, a in checked.items():
+                if len(a):
+                    self._vertexBuffer.SetData(a, 0, spans[k][0], len(a))
+        if recompute_normals:
+            s.normals = host_scene.compute_normals(s.vertices, s.indices)
+            if uploaded:
+                self._normalBuffer = self.CreateComputeBuffer(self._normalBuffer, np.ascontiguousarray(s.normals, np.float32), 12)
+        if edits:
+            s.mesh_bvh = host_scene.build_object_bvh(host_scene.mesh_leaf_bounds(s.mesh_objects, s.vertices, s.indices)) if self._rayTraceObjects \
+                else scenes.build_object_bvh(*scenes.mesh_bounds(s.mesh_objects, s.vertices, s.indices))
+            if self._rayTraceObjects:                                             # keep the registered objects in step with the lists
+                meshes, first = [o for o in self._rayTraceObjects if o.type != 1], 0
+                for o in meshes:
+                    nv = len(np.asarray(o.vertices).reshape(-1, 3))
+                    o.vertices = s.vertices[first: first + nv].copy()
+                    first += nv
+            if uploaded:
+                self._meshObjectBVHBuffer = self.CreateComputeBuffer(self._meshObjectBVHBuffer, s.mesh_bvh, self.BVHNodeSize)
+        if not history:
+            self.ResetAccumulation()
+            return
+        self.SetShaderParameters()
+        self.ctx.render_aov(cur[0], cur[1], None, cur[2])                      # the deformed scene
+        table = host_scene.mesh_motion(s.mesh_objects, s.mesh_objects)             # nothing else has moved: identity entries
+        for k in edits:
+            table[k] = np.nan
+        self._tmotion[0] = self.CreateComputeBuffer(self._tmotion[0], table if edits else np.zeros((0, 12), np.float32), 48)
+        self._tmotion[1] = self.CreateComputeBuffer(self._tmotion[1], np.zeros((0, 12), np.float32), 48)
+        color, count = self._tspare
+        self.ctx.reproject(self._converged, self._tcount, prev[0], prev[1], prev[2], cur[0], cur[1], cur[2], color, count, prev_m,
+                           mesh_motion=self._tmotion[0], sphere_motion=self._tmotion[1], moved_max_history=self._moved_max_history,
+                           **self._temporal)
+        self._tspare = (self._converged, self._tcount)
+        self._converged, self._tcount = color, count
+
     # the edited lists become the scene's, with the object-level heaps RebuildObjectLists / the scene builders make for them, and are
     # uploaded (RebuildTrees: SetData of data a buffer already holds changes nothing)
     def _apply_object_edits(self, new_mo, new_sp, mesh_edits, sphere_edits):

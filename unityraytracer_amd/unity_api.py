@@ -80,6 +80,22 @@ class Context:
         self.check(self.lib.urt_debug_refit_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def deform_stats(self) -> dict:
+        """In-place updates of changed _Vertices / _Normals since the context was created (include/urt.h urt_debug_deform_stats): deformed
+        MeshObjects refitted, MeshObjects whose normals were re-gathered, bytes copied to the device, full preparations forced by
+        "refit_rebuild_pct", and the largest cost ratio of the last in-place update."""
+        a = (C.c_uint64 * 6)()
+        self.check(self.lib.urt_debug_deform_stats(self._h, a))
+        return {"deformed": int(a[0]), "renormed": int(a[1]), "bytes_copied": int(a[2]), "forced_rebuilds": int(a[3]),
+                "cost_ratio": float(np.array([int(a[4])], dtype=np.uint32).view(np.float32)[0])}
+
+    def scene_cost(self, n_meshes: int) -> np.ndarray:
+        """(n_meshes, 2) float32: the surface-area cost of every MeshObject's triangle BVH now, and at the last full preparation
+        (include/urt.h urt_debug_scene_cost; prepares a stale scene first)."""
+        out = np.zeros((int(n_meshes), 2), dtype=np.float32)
+        self.check(self.lib.urt_debug_scene_cost(self._h, out.ctypes.data_as(C.c_void_p), int(n_meshes)))
+        return out
+
     def serve_stats(self) -> dict:
         """kernel_mode 5 with count_stats: the shared traversal service since the last reset_counters()."""
         a = (C.c_ulonglong * 6)()
@@ -772,11 +788,25 @@ class ComputeBuffer:
         self.handle = h.value
         self.count, self.stride = int(count), int(stride)
 
-    def SetData(self, data):
+    def SetData(self, data, managed_start: int = 0, compute_start: int = 0, count: int | None = None):
+        """SetData(data): the whole list.  SetData(data, managed_start, compute_start, count): Unity's ranged overload — `count` elements
+        of `data` from element managed_start on go to elements compute_start .. compute_start + count - 1 of the buffer
+        (include/urt.h urt_buffer_set_data_range)."""
         a = np.ascontiguousarray(data)
         if a.nbytes % self.stride:
             raise UrtError(1, f"SetData: {a.nbytes} bytes is not a multiple of stride {self.stride}")
-        self.ctx.check(self.ctx.lib.urt_buffer_set_data(self.ctx._h, self.handle, a.ctypes.data_as(C.c_void_p), a.nbytes // self.stride))
+        n = a.nbytes // self.stride
+        if managed_start == 0 and compute_start == 0 and count is None:
+            self.ctx.check(self.ctx.lib.urt_buffer_set_data(self.ctx._h, self.handle, a.ctypes.data_as(C.c_void_p), n))
+            return
+        for name, v in (("managed_start", managed_start), ("compute_start", compute_start), ("count", n if count is None else count)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"SetData: {name} must be an int, not {type(v).__name__}")
+        count = n - managed_start if count is None else count
+        if managed_start < 0 or count < 0 or managed_start + count > n:
+            raise UrtError(1, f"SetData: elements {managed_start} .. {managed_start + count - 1} lie outside the {n} elements of data")
+        ptr = C.c_void_p(a.ctypes.data + int(managed_start) * self.stride) if n else C.c_void_p(0)
+        self.ctx.check(self.ctx.lib.urt_buffer_set_data_range(self.ctx._h, self.handle, int(compute_start), ptr, int(count)))
 
     def Release(self):
         if self.handle:
