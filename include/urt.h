@@ -51,8 +51,11 @@ enum {
 
 /* ---- library / context ------------------------------------------------------------------- */
 URT_API int urt_abi_version(void);                       /* bumps when this header changes incompatibly (still 4: the ray queries,
-                                                            the feature buffers, the denoiser, the temporal reprojection and the
-                                                            resampling were added without changing anything that existed) */
+                                                            the feature buffers, the denoiser, the temporal reprojection, the
+                                                            resampling, the ranged SetData and the device side of the buffers —
+                                                            urt_buffer_set_data_device, urt_buffer_get_data_range,
+                                                            urt_skin_vertices, urt_buffer_bounds, urt_debug_buffer_state — were
+                                                            added without changing anything that existed) */
 URT_API int urt_device_count(int* out_count);
 /* One context per process and GPU (the one-process-per-GPU model).  device = HIP ordinal. */
 URT_API int urt_context_create(int device, urt_context** out_ctx);
@@ -93,6 +96,65 @@ URT_API int urt_buffer_set_data_range(urt_context* ctx, urt_handle buffer, int f
 URT_API int urt_buffer_get_info(urt_context* ctx, urt_handle buffer, int* out_count, int* out_stride);
 /* buffer.Release()                                                   RM:195-210, 238 */
 URT_API int urt_buffer_release(urt_context* ctx, urt_handle buffer);
+
+/* ---- the device side of a ComputeBuffer ------------------------------------------------------------------------------------------
+ * A buffer is a host copy; the first device-side use below gives it a DEVICE MIRROR of count * stride bytes, filled from the host copy
+ * and from then on kept current: a host SetData pushes what it changed, in stream order.  The writers below leave the HOST copy behind
+ * instead: the elements they wrote are STALE on the host until something reads them there — urt_buffer_get_data_range, a full scene
+ * preparation, the small scene tables, a motion table — which first downloads them (a synchronising device-to-host copy, counted by
+ * urt_debug_buffer_state).  A host SetData never downloads for its compare: elements inside the stale range count as differing and
+ * leave it (when that would split the range, the part behind the written elements is downloaded first).
+ * When _Vertices / _Normals were written on the device and the change is one the scene takes in place (option "refit_vertices"), the
+ * dirty elements reach the scene's copies by a device-to-device copy on the context's stream: no host copy, no upload, no download.
+ * Every other path (a full preparation for whatever reason) sees the device-written data through the download.
+ * urt_buffer_release and urt_context_destroy give the mirror back.  There are no urt_group_* twins of the calls of this section: a group
+ * host reaches the ranks' contexts through urt_group_context. */
+/* Ranged SetData whose source is DEVICE memory (4-byte aligned): the copy is enqueued on the context's stream and the call returns
+ * without synchronising; the source is read in stream order and the caller orders its producer, as with urt_ray_query_device.  Every
+ * element of the range counts as changed (no compare); bound slots are dirtied exactly as by urt_buffer_set_data_range.  Works for a
+ * buffer of any stride; only _Vertices / _Normals have the in-place path, for other bound slots the next preparation downloads.
+ * count == 0 changes nothing.  Checked first, nothing enqueued: unknown handle URT_ERR_INVALID_HANDLE; first < 0, count < 0, a range
+ * beyond the buffer, NULL or misaligned d_data with count > 0 URT_ERR_INVALID_ARGUMENT. */
+URT_API int urt_buffer_set_data_device(urt_context* ctx, urt_handle buffer, int first, const void* d_data, int count);
+/* ComputeBuffer.GetData: the buffer's current contents, elements first .. first+count-1, into host memory; downloads stale elements
+ * (synchronises).  Elements that were never set read as zero bytes.  Errors as urt_buffer_set_data_range. */
+URT_API int urt_buffer_get_data_range(urt_context* ctx, urt_handle buffer, int first, void* out, int count);
+
+/* Linear blend skinning on the GPU.  rest_vertices (stride 12), rest_normals (stride 12; 0 is allowed exactly when dst_normals == 0),
+ * bone_indices (stride 16: int32[4] per vertex), bone_weights (stride 16: float[4] per vertex), bones (stride 48: urt_ObjectMotion's
+ * a[12] — three columns of the linear part, then the translation — object space to object space; n_bones is the buffer's count).
+ * rest_*, bone_indices, bone_weights and the destinations have one common count. */
+typedef struct urt_SkinBuffers {
+  urt_handle rest_vertices, rest_normals, bone_indices, bone_weights, bones;
+} urt_SkinBuffers;   /* 40 bytes */
+/* Skins elements first .. first+count-1 into the device mirrors of dst_vertices (and dst_normals, unless 0).  NORMATIVE arithmetic:
+ * float32, one rounding per operation, no fma, evaluated as written.  For vertex i: P rest position, N rest normal, j[0..3] bone
+ * indices, w[0..3] weights.  Term k is LIVE when w[k] != 0.0f (a NaN weight is live) and 0 <= j[k] < n_bones; a term that is not live
+ * contributes +0.0f per component and its bone is not read, so an index out of range is never a fault and never an error.  Live term,
+ * with a = bones[j[k]].a and r = 0, 1, 2:
+ *     q.r = ((a[r]*P.x + a[3+r]*P.y) + a[6+r]*P.z) + a[9+r]        t_k.r = w[k]*q.r
+ *     m.r = (a[r]*N.x + a[3+r]*N.y) + a[6+r]*N.z                    u_k.r = w[k]*m.r
+ * dst_vertices[i].r = ((t_0.r + t_1.r) + t_2.r) + t_3.r; s.r is the same sum over the u_k and L2 = dot(s, s) of urt_math.h.  When L2 > 0
+ * and finite, dst_normals[i] = normalize(s) of urt_math.h = s * (1.0f / f_sqrt(L2)); otherwise dst_normals[i] = s as it is.  Weights are
+ * not normalised; non-finite inputs flow through the arithmetic.
+ * The inputs get mirrors (above: only what a SetData changed travels — per frame, the bones); ONE kernel is enqueued on the context's
+ * stream, nothing is synchronised and deferred frames stay deferred.  The destination range becomes stale and dirty as a whole, exactly
+ * as with urt_buffer_set_data_device.
+ * URT_ERR_INVALID_ARGUMENT: NULL in, a range outside the buffers, strides or counts that do not fit, a destination equal to an input or
+ * to the other destination, dst_normals without rest_normals.  URT_ERR_INVALID_HANDLE: a required handle that is 0 or unknown.
+ * count == 0 returns URT_OK after the checks.  On any error nothing is enqueued or marked. */
+URT_API int urt_skin_vertices(urt_context* ctx, const urt_SkinBuffers* in, int first, int count, urt_handle dst_vertices,
+                              urt_handle dst_normals);
+/* Where a stride-12 buffer's elements first .. first+count-1 are, read on the device (a host that skins on the GPU still owes the
+ * reference's _MeshBVH leaf boxes, RM:405-433): out6[0..2] the component-wise min and out6[3..5] the max over the elements whose three
+ * components are all finite, *out_n (may be NULL) their number; with none, out6 = (+inf, +inf, +inf, -inf, -inf, -inf).  One reduction
+ * and a small second pass, then the call synchronises (URT_ERR_WATCHDOG as urt_synchronize reports it).  Min and max are exact, so the
+ * result does not depend on the order of the reduction; signed zeros compare as values.
+ * Errors as urt_buffer_set_data_range, plus URT_ERR_INVALID_ARGUMENT for a stride other than 12 and for NULL out6. */
+URT_API int urt_buffer_bounds(urt_context* ctx, urt_handle buffer, int first, int count, float out6[6], int* out_n);
+/* out4: the stale element range (first, last; first > last when it is empty), the bytes of the device mirror (0: none), the downloads
+ * of this buffer since its creation. */
+URT_API int urt_debug_buffer_state(urt_context* ctx, urt_handle buffer, uint64_t out4[4]);
 
 /* ---- RenderTexture / Texture (RGBA32F = ARGBFloat, linear) -------------------------------- */
 /* new RenderTexture(w, h, 0, ARGBFloat, Linear){enableRandomWrite}.Create()   RM:834-840 */

@@ -23,6 +23,13 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_buffer_create(IntPtr ctx, int count, int stride, out ulong buffer);
     [DllImport(Lib)] internal static extern int urt_buffer_set_data(IntPtr ctx, ulong buffer, IntPtr data, int count);
     [DllImport(Lib)] internal static extern int urt_buffer_set_data_range(IntPtr ctx, ulong buffer, int first, IntPtr data, int count);
+    // the device side of a buffer (include/urt.h): SetData from device memory, GetData, skinning, bounds, where the contents live
+    [StructLayout(LayoutKind.Sequential)] internal struct SkinBuffers { public ulong restVertices, restNormals, boneIndices, boneWeights, bones; }   // 40 B; restNormals 0 = positions only
+    [DllImport(Lib)] internal static extern int urt_buffer_set_data_device(IntPtr ctx, ulong buffer, int first, IntPtr deviceData, int count);
+    [DllImport(Lib)] internal static extern int urt_buffer_get_data_range(IntPtr ctx, ulong buffer, int first, IntPtr outData, int count);
+    [DllImport(Lib)] internal static extern int urt_skin_vertices(IntPtr ctx, in SkinBuffers buffers, int first, int count, ulong dstVertices, ulong dstNormals);
+    [DllImport(Lib)] internal static extern int urt_buffer_bounds(IntPtr ctx, ulong buffer, int first, int count, [Out] float[] out6, out int finiteElements);
+    [DllImport(Lib)] internal static extern int urt_debug_buffer_state(IntPtr ctx, ulong buffer, [Out] ulong[] out4);   // stale first, stale last, mirror bytes, downloads
     [DllImport(Lib)] internal static extern int urt_buffer_get_info(IntPtr ctx, ulong buffer, out int count, out int stride);
     [DllImport(Lib)] internal static extern int urt_buffer_release(IntPtr ctx, ulong buffer);
 

@@ -330,6 +330,73 @@ public sealed class UrtComputeBuffer {
     }
 }
 
+/// A skinned mesh animated on the GPU: RayTraceMaster.AttachSkin / SkinMeshes of the Python mirror (include/urt.h urt_skin_vertices,
+/// urt_buffer_bounds).  One instance serves every skinned MeshObject of a scene: it owns rest-pose, bone-index and bone-weight buffers of
+/// the vertex count and one bone table per mesh.  Per frame only the bones travel; the positions are written into the device side of the
+/// _Vertices / _Normals buffers and the library refits the skinned meshes in place (option "refit_vertices").  On one context only: a
+/// group host reaches the ranks through urt_group_context.
+public sealed class UrtSkinnedMesh {
+    sealed class Skin { public int first, count; public ulong bones; public int nBones; }
+    readonly UrtComputeBuffer restVertices, restNormals, boneIndices, boneWeights;
+    readonly Dictionary<int, Skin> skins = new Dictionary<int, Skin>();
+    public UrtSkinnedMesh(int vertexCount) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtSkinnedMesh: skin on one rank's context (urt_group_context)");
+        restVertices = new UrtComputeBuffer(vertexCount, 12); restNormals = new UrtComputeBuffer(vertexCount, 12);
+        boneIndices = new UrtComputeBuffer(vertexCount, 16); boneWeights = new UrtComputeBuffer(vertexCount, 16);
+    }
+    /// The vertex span first .. first + count - 1 of MeshObject meshIndex gets a skin: its rest pose (mesh.vertices / mesh.normals) and per
+    /// vertex four bone indices (BoneWeight.boneIndex0..3) and weights (BoneWeight.weight0..3), four ints / floats per vertex.
+    public void AttachSkin(int meshIndex, int first, List<Vector3> restPositions, List<Vector3> restNormalList, List<int> indices4, List<float> weights4) {
+        int count = restPositions.Count;
+        if (restNormalList.Count != count || indices4.Count != 4 * count || weights4.Count != 4 * count)
+            throw new ArgumentException("UrtSkinnedMesh.AttachSkin: the lists do not describe one vertex span");
+        restVertices.SetData(restPositions, 0, first, count);
+        restNormals.SetData(restNormalList, 0, first, count);
+        SetWords(boneIndices, indices4.ToArray(), first, count);
+        SetWords(boneWeights, weights4.ToArray(), first, count);
+        skins[meshIndex] = new Skin { first = first, count = count };
+    }
+    static void SetWords<T>(UrtComputeBuffer b, T[] words, int first, int count) where T : struct {
+        GCHandle pin = GCHandle.Alloc(words, GCHandleType.Pinned);
+        try { UrtDevice.Check(UrtNative.urt_buffer_set_data_range(UrtDevice.Handle, b.handle, first, pin.AddrOfPinnedObject(), count)); }
+        finally { pin.Free(); }
+    }
+    /// poses: MeshObject index -> its bones, 12 floats each (three columns of the linear part, then the translation), from the mesh's object
+    /// space to itself: worldToLocal(mesh) * SkinnedMeshRenderer.bones[i].localToWorldMatrix * sharedMesh.bindposes[i].  Skins every span
+    /// into `vertices` / `normals` (the buffers bound as _Vertices / _Normals) and returns, per mesh, the object-space bounds of its
+    /// skinned vertices (min.xyz, max.xyz) as the GPU found them: the caller transforms the eight corners by localToWorldMatrix for the
+    /// mesh's _MeshBVH leaf box (RM:405-433), rebuilds the heap and SetData-s it, as after any deformation.
+    public Dictionary<int, float[]> SkinMeshes(Dictionary<int, float[]> poses, UrtComputeBuffer vertices, UrtComputeBuffer normals) {
+        IntPtr ctx = UrtDevice.Handle;
+        foreach (var kv in poses) {
+            if (!skins.TryGetValue(kv.Key, out Skin s)) throw new ArgumentException("UrtSkinnedMesh.SkinMeshes: MeshObject " + kv.Key + " has no skin (AttachSkin)");
+            int nBones = kv.Value.Length / 12;
+            if (nBones < 1 || kv.Value.Length != 12 * nBones) throw new ArgumentException("UrtSkinnedMesh.SkinMeshes: 12 floats per bone");
+            if (s.bones != 0 && s.nBones != nBones) { UrtDevice.Check(UrtNative.urt_buffer_release(ctx, s.bones)); s.bones = 0; }
+            if (s.bones == 0) UrtDevice.Check(UrtNative.urt_buffer_create(ctx, nBones, UrtNative.ObjectMotionStride, out s.bones));
+            s.nBones = nBones;
+            GCHandle pin = GCHandle.Alloc(kv.Value, GCHandleType.Pinned);
+            try { UrtDevice.Check(UrtNative.urt_buffer_set_data(ctx, s.bones, pin.AddrOfPinnedObject(), nBones)); }
+            finally { pin.Free(); }
+            var sb = new UrtNative.SkinBuffers { restVertices = restVertices.handle, restNormals = normals != null ? restNormals.handle : 0,
+                                                 boneIndices = boneIndices.handle, boneWeights = boneWeights.handle, bones = s.bones };
+            UrtDevice.Check(UrtNative.urt_skin_vertices(ctx, in sb, s.first, s.count, vertices.handle, normals != null ? normals.handle : 0));
+        }
+        var boxes = new Dictionary<int, float[]>();
+        foreach (var kv in poses) {                                   // after every kernel is enqueued: each bounds call waits
+            Skin s = skins[kv.Key];
+            var box = new float[6];
+            UrtDevice.Check(UrtNative.urt_buffer_bounds(ctx, vertices.handle, s.first, s.count, box, out int _));
+            boxes[kv.Key] = box;
+        }
+        return boxes;
+    }
+    public void Release() {
+        foreach (var s in skins.Values) if (s.bones != 0) { UrtDevice.Check(UrtNative.urt_buffer_release(UrtDevice.Handle, s.bones)); s.bones = 0; }
+        restVertices.Release(); restNormals.Release(); boneIndices.Release(); boneWeights.Release();
+    }
+}
+
 /// new RenderTexture(w, h, 0, ARGBFloat, Linear) { enableRandomWrite = true }.Create(); .Release(); .width; .height   (RM:824-845)
 public sealed class UrtRenderTexture {
     internal ulong handle;

@@ -1,7 +1,8 @@
 // context.cpp — implementation of the C ABI in include/urt.h.
 //
 // Stands in for the UnityEngine GPU objects RayTraceMaster.cs drives:
-//   ComputeBuffer   -> Buffer   (host copy kept; the device form is DERIVED at the next dispatch)
+//   ComputeBuffer   -> Buffer   (host copy kept; the device form is DERIVED at the next dispatch; an optional device mirror takes
+//                                device-side writes: urt_buffer_set_data_device, urt_skin_vertices)
 //   RenderTexture   -> Texture  (RGBA32F device image)
 //   ComputeShader   -> the uniform/binding table in urt_context + dispatch of the HIP kernels
 //   Graphics.Blit   -> urt_blit / urt_blit_add
@@ -10,10 +11,12 @@
 #include "context_impl.h"
 
 #include <climits>
+#include <limits>
 #include <memory>
 
 #include "present.h"
 #include "reproject.h"
+#include "skin.h"
 
 using namespace urtd;
 
@@ -44,6 +47,31 @@ int check_watchdog(urt_context* ctx) {
   if (n == 0) return URT_OK;
   return fail(ctx, URT_ERR_WATCHDOG, std::to_string(n) + " wave(s) of a trace launch hit the kernel's iteration cap and left pixels unwritten "
                                      "(urt_counters.watchdog_trips): the images written since the last successful synchronisation are incomplete");
+}
+
+// D2H of elements first .. last of the mirror into `host`: synchronises (the stream carries the kernels that wrote them) and is counted.
+int download_elements(urt_context* ctx, Buffer& b, int first, int last) {
+  const size_t at = (size_t)first * (size_t)b.stride, bytes = (size_t)(last - first + 1) * (size_t)b.stride;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  URT_HIP(ctx, hipMemcpyAsync(b.host.data() + at, b.mirror.get() + at, bytes, hipMemcpyDeviceToHost, touch(ctx)));
+  URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
+  b.downloads++;
+  return URT_OK;
+}
+
+// `host` made current: the stale range comes down (nothing to do without one)
+int buffer_sync_host(urt_context* ctx, Buffer& b) {
+  if (!b.stale() || !b.mirror) return URT_OK;
+  if (int rc = download_elements(ctx, b, b.stale_first, b.stale_last)) return rc;
+  b.stale_first = 0; b.stale_last = -1;
+  return URT_OK;
+}
+int sync_bound_hosts(urt_context* ctx, unsigned int slots) {
+  for (int s = 0; s < B_COUNT; s++) {
+    Buffer* b = (slots >> s) & 1u ? find_buffer(ctx, ctx->bound[s]) : nullptr;
+    if (b) if (int rc = buffer_sync_host(ctx, *b)) return rc;
+  }
+  return URT_OK;
 }
 
 // strips first_row, first_row + row_stride, ... of 8-row groups that lie in the first group_rows
@@ -174,21 +202,72 @@ static bool differing_bytes(const uint8_t* a, const uint8_t* b, size_t n, size_t
   return true;
 }
 
+// ---- device mirrors (context_impl.h Buffer::mirror) ----------------------------------------------------------------------------------
+// The mirror, made and filled from `host` at the first need: a synchronous copy, before anything on the stream can use the new memory.
+static int buffer_mirror(urt_context* ctx, Buffer& b) {
+  if (b.mirror) return URT_OK;
+  const size_t bytes = (size_t)b.count * (size_t)b.stride;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  URT_HIP(ctx, b.mirror.alloc(bytes));
+  hipError_t e = hipMemcpy(b.mirror.get(), b.host.data(), bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { b.mirror.reset(); return fail(ctx, URT_ERR_HIP, std::string("buffer mirror upload: ") + hipGetErrorString(e)); }
+  return URT_OK;
+}
+
+// Host elements first .. last -> mirror, on the stream, through a pinned image: the caller may change `host` as soon as this returns, and
+// nothing but the slot's own previous copy is waited for.
+static int push_elements(urt_context* ctx, Buffer& b, int first, int last) {
+  const size_t at = (size_t)first * (size_t)b.stride, bytes = (size_t)(last - first + 1) * (size_t)b.stride;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  urt_context::UpSlot& u = ctx->up_slot[ctx->up_next++ % urt_context::kUpSlots];
+  if (!u.done) URT_HIP(ctx, u.done.create(hipEventDisableTiming));
+  if (u.used) URT_HIP(ctx, hipEventSynchronize(u.done.get()));
+  if (u.host.cap() < bytes) { u.used = false; URT_HIP(ctx, u.host.alloc(bytes)); }
+  std::memcpy(u.host.get(), b.host.data() + at, bytes);
+  URT_HIP(ctx, hipMemcpyAsync(b.mirror.get() + at, u.host.get(), bytes, hipMemcpyHostToDevice, touch(ctx)));
+  URT_HIP(ctx, hipEventRecord(u.done.get(), ctx->stream));
+  u.used = true;
+  return URT_OK;
+}
+
+// Elements first .. last have changed: they join the dirty range, and every slot the buffer is bound to asks for a preparation.
+static void mark_changed(urt_context* ctx, urt_handle buffer, Buffer& b, int first, int last) {
+  b.mark_dirty(first, last);
+  for (int s = 0; s < B_COUNT; s++) if (ctx->bound[s] == buffer) { ctx->scene_dirty = true; ctx->dirty_slots |= 1u << s; }
+}
+
 // SetData of elements first .. first + count - 1 (arguments checked by the callers): data equal to what the buffer holds changes nothing and
 // dirties nothing (the reference re-uploads EVERY list whenever anything changed, RM:738-745; a compare costs what the copy would);
-// else the elements between the first and the last differing byte join the buffer's dirty range.
+// else the elements between the first and the last differing byte join the buffer's dirty range.  Elements inside the stale range differ
+// by definition (the compare does not download): they leave the stale range, and when that would split it in two the part behind the
+// written elements is downloaded first.  What changed is pushed into the mirror, if there is one.
 static int set_data_elements(urt_context* ctx, urt_handle buffer, Buffer& b, int first, const void* data, int count) {
   const size_t bytes = (size_t)count * (size_t)b.stride, at = (size_t)first * (size_t)b.stride;
+  const int last = first + count - 1;
   int d0 = 0, d1 = b.count - 1;                              // a buffer that is set for the first time is new as a whole
+  int p0 = first, p1 = last;                                 // what the mirror lacks
+  const int s0 = std::max(first, b.stale_first), s1 = std::min(last, b.stale_last);
+  const bool meets_stale = count > 0 && b.stale() && s0 <= s1;
   if (b.has_data) {
     size_t f = 0, l = 0;
-    if (bytes == 0 || !differing_bytes(b.host.data() + at, (const uint8_t*)data, bytes, &f, &l)) return URT_OK;
-    d0 = first + (int)(f / (size_t)b.stride); d1 = first + (int)(l / (size_t)b.stride);
+    const bool differs = bytes > 0 && differing_bytes(b.host.data() + at, (const uint8_t*)data, bytes, &f, &l);
+    if (!differs && !meets_stale) return URT_OK;
+    if (differs) { d0 = first + (int)(f / (size_t)b.stride); d1 = first + (int)(l / (size_t)b.stride); }
+    if (meets_stale) { d0 = differs ? std::min(d0, s0) : s0; d1 = differs ? std::max(d1, s1) : s1; }
+    p0 = d0; p1 = d1;
+  }
+  if (meets_stale) {
+    if (b.stale_first < first && last < b.stale_last) {
+      if (int rc = download_elements(ctx, b, last + 1, b.stale_last)) return rc;
+      b.stale_last = first - 1;
+    } else if (b.stale_first >= first && b.stale_last <= last) { b.stale_first = 0; b.stale_last = -1; }
+    else if (b.stale_first < first) b.stale_last = first - 1;
+    else b.stale_first = last + 1;
   }
   if (bytes > 0) std::memcpy(b.host.data() + at, data, bytes);
   b.has_data = true;
-  b.mark_dirty(d0, d1);
-  for (int s = 0; s < B_COUNT; s++) if (ctx->bound[s] == buffer) { ctx->scene_dirty = true; ctx->dirty_slots |= 1u << s; }
+  if (b.mirror && bytes > 0) if (int rc = push_elements(ctx, b, p0, p1)) return rc;
+  mark_changed(ctx, buffer, b, d0, d1);
   return URT_OK;
 }
 
@@ -214,6 +293,128 @@ int urt_buffer_set_data_range(urt_context* ctx, urt_handle buffer, int first, co
   return set_data_elements(ctx, buffer, b, first, data, count);
 }
 
+// A device-side writer has filled elements first .. first + count - 1 of the mirror (count > 0): `host` is behind there, and every element
+// counts as changed.
+static void mark_device_written(urt_context* ctx, urt_handle buffer, Buffer& b, int first, int count) {
+  const bool fresh = !b.has_data;                            // set for the first time: new as a whole, as with SetData
+  b.has_data = true;
+  b.mark_stale(first, first + count - 1);
+  mark_changed(ctx, buffer, b, fresh ? 0 : first, fresh ? b.count - 1 : first + count - 1);
+}
+
+static int check_element_range(urt_context* ctx, const char* who, const Buffer& b, int first, int count) {
+  if (first < 0 || count < 0 || (long long)first + (long long)count > (long long)b.count)
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(who) + ": the element range lies outside the buffer");
+  return URT_OK;
+}
+
+int urt_buffer_set_data_device(urt_context* ctx, urt_handle buffer, int first, const void* d_data, int count) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  Buffer* b = find_buffer(ctx, buffer);
+  if (!b) return fail(ctx, URT_ERR_INVALID_HANDLE, "SetDataDevice: unknown buffer handle");
+  if (int rc = check_element_range(ctx, "SetDataDevice", *b, first, count)) return rc;
+  if (count > 0 && (!d_data || ((uintptr_t)d_data & 3u))) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "SetDataDevice: d_data is NULL or not 4-byte aligned");
+  if (count == 0) return URT_OK;
+  URT_GUARD_BEGIN
+  if (int rc = buffer_mirror(ctx, *b)) return rc;
+  const size_t at = (size_t)first * (size_t)b->stride, bytes = (size_t)count * (size_t)b->stride;
+  URT_HIP(ctx, hipMemcpyAsync(b->mirror.get() + at, d_data, bytes, hipMemcpyDeviceToDevice, touch(ctx)));
+  mark_device_written(ctx, buffer, *b, first, count);
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+int urt_buffer_get_data_range(urt_context* ctx, urt_handle buffer, int first, void* out, int count) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  Buffer* b = find_buffer(ctx, buffer);
+  if (!b) return fail(ctx, URT_ERR_INVALID_HANDLE, "GetData: unknown buffer handle");
+  if (int rc = check_element_range(ctx, "GetData", *b, first, count)) return rc;
+  if (count > 0 && !out) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "GetData: out is NULL");
+  if (count == 0) return URT_OK;
+  if (b->stale() && first <= b->stale_last && first + count - 1 >= b->stale_first)
+    if (int rc = buffer_sync_host(ctx, *b)) return rc;
+  std::memcpy(out, b->host.data() + (size_t)first * (size_t)b->stride, (size_t)count * (size_t)b->stride);
+  return URT_OK;
+}
+
+int urt_skin_vertices(urt_context* ctx, const urt_SkinBuffers* in, int first, int count, urt_handle dst_vertices, urt_handle dst_normals) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (!in) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "skin_vertices: in is NULL");
+  URT_GUARD_BEGIN
+  const bool normals = dst_normals != 0;
+  if (normals && !in->rest_normals) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "skin_vertices: dst_normals without rest_normals");
+  enum { kRestV, kRestN, kIdx, kWgt, kBones, kDstV, kDstN, kArgs };
+  const urt_handle h[kArgs] = {in->rest_vertices, normals ? in->rest_normals : 0, in->bone_indices, in->bone_weights, in->bones, dst_vertices, dst_normals};
+  const char* const name[kArgs] = {"rest_vertices", "rest_normals", "bone_indices", "bone_weights", "bones", "dst_vertices", "dst_normals"};
+  const int stride[kArgs] = {12, 12, 16, 16, (int)sizeof(urt_ObjectMotion), 12, 12};
+  Buffer* b[kArgs];
+  for (int k = 0; k < kArgs; k++) {
+    b[k] = nullptr;
+    if (!normals && (k == kRestN || k == kDstN)) continue;
+    b[k] = find_buffer(ctx, h[k]);
+    if (!b[k]) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string("skin_vertices: ") + name[k] + " is 0 or an unknown buffer handle");
+  }
+  if (!normals && in->rest_normals && !find_buffer(ctx, in->rest_normals))
+    return fail(ctx, URT_ERR_INVALID_HANDLE, "skin_vertices: rest_normals is an unknown buffer handle");
+  for (int k = 0; k < kArgs; k++) {
+    if (!b[k]) continue;
+    if (b[k]->stride != stride[k]) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("skin_vertices: the stride of ") + name[k] + " is not " + std::to_string(stride[k]));
+    if (k != kBones && b[k]->count != b[kRestV]->count) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("skin_vertices: the count of ") + name[k] + " is not that of rest_vertices");
+    if (k < kDstV && (h[k] == dst_vertices || h[k] == dst_normals)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("skin_vertices: ") + name[k] + " is also a destination");
+  }
+  if (normals && dst_normals == dst_vertices) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "skin_vertices: dst_vertices and dst_normals are one buffer");
+  if (int rc = check_element_range(ctx, "skin_vertices", *b[kRestV], first, count)) return rc;
+  if (count == 0) return URT_OK;
+  for (int k = 0; k < kArgs; k++) if (b[k]) if (int rc = buffer_mirror(ctx, *b[k])) return rc;
+  URT_HIP(ctx, skin_vertices((const float*)b[kRestV]->mirror.get(), normals ? (const float*)b[kRestN]->mirror.get() : nullptr,
+                             (const int32_t*)b[kIdx]->mirror.get(), (const float*)b[kWgt]->mirror.get(), (const float*)b[kBones]->mirror.get(),
+                             b[kBones]->count, first, count, (float*)b[kDstV]->mirror.get(), normals ? (float*)b[kDstN]->mirror.get() : nullptr, touch(ctx)));
+  mark_device_written(ctx, dst_vertices, *b[kDstV], first, count);
+  if (normals) mark_device_written(ctx, dst_normals, *b[kDstN], first, count);
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+int urt_buffer_bounds(urt_context* ctx, urt_handle buffer, int first, int count, float out6[6], int* out_n) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  Buffer* b = find_buffer(ctx, buffer);
+  if (!b) return fail(ctx, URT_ERR_INVALID_HANDLE, "buffer_bounds: unknown buffer handle");
+  if (b->stride != 12) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "buffer_bounds: the stride of the buffer is not 12");
+  if (int rc = check_element_range(ctx, "buffer_bounds", *b, first, count)) return rc;
+  if (!out6) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "buffer_bounds: out6 is NULL");
+  URT_GUARD_BEGIN
+  const float inf = std::numeric_limits<float>::infinity();
+  for (int c = 0; c < 3; c++) { out6[c] = inf; out6[3 + c] = -inf; }
+  if (out_n) *out_n = 0;
+  if (count == 0) return URT_OK;
+  if (int rc = buffer_mirror(ctx, *b)) return rc;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t words = (size_t)(kBoundsMaxBlocks + 1) * kBoundsWords;
+  if (int rc = reserve(ctx, ctx->bd_partial, words, "buffer_bounds: scratch allocation", ctx->stream)) return rc;
+  if (!ctx->bd_result) URT_HIP(ctx, ctx->bd_result.alloc(kBoundsWords));
+  float* d_out = ctx->bd_partial.get() + (size_t)kBoundsMaxBlocks * kBoundsWords;
+  URT_HIP(ctx, buffer_bounds((const float*)b->mirror.get(), first, count, ctx->bd_partial.get(), d_out, touch(ctx)));
+  URT_HIP(ctx, hipMemcpyAsync(ctx->bd_result.get(), d_out, kBoundsWords * sizeof(float), hipMemcpyDeviceToHost, touch(ctx)));
+  URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
+  std::memcpy(out6, ctx->bd_result.get(), 6 * sizeof(float));
+  uint32_t n = 0;
+  std::memcpy(&n, ctx->bd_result.get() + 6, 4);
+  if (out_n) *out_n = (int)n;
+  return check_watchdog(ctx);
+  URT_GUARD_END(ctx)
+}
+
+int urt_debug_buffer_state(urt_context* ctx, urt_handle buffer, uint64_t out4[4]) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  const Buffer* b = find_buffer(ctx, buffer);
+  if (!b) return fail(ctx, URT_ERR_INVALID_HANDLE, "buffer_state: unknown buffer handle");
+  if (!out4) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "buffer_state: out4 is NULL");
+  out4[0] = b->stale() ? (uint64_t)b->stale_first : 1; out4[1] = b->stale() ? (uint64_t)b->stale_last : 0;
+  out4[2] = b->mirror ? (uint64_t)b->count * (uint64_t)b->stride : 0;
+  out4[3] = b->downloads;
+  return URT_OK;
+}
+
 int urt_buffer_get_info(urt_context* ctx, urt_handle buffer, int* out_count, int* out_stride) {
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   auto it = ctx->buffers.find(buffer);
@@ -228,6 +429,10 @@ int urt_buffer_release(urt_context* ctx, urt_handle buffer) {
   auto it = ctx->buffers.find(buffer);
   if (it == ctx->buffers.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "Release: unknown buffer handle");
   for (int s = 0; s < B_COUNT; s++) if (ctx->bound[s] == buffer) { ctx->bound[s] = 0; ctx->scene_dirty = true; ctx->dirty_full = true; }
+  if (it->second.mirror) {                                   // kernels and copies queued on the stream may still use the mirror
+    URT_HIP(ctx, hipSetDevice(ctx->device));
+    URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
+  }
   ctx->buffers.erase(it);
   return URT_OK;
 }

@@ -38,6 +38,19 @@ struct Buffer {
     if (dirty_last < dirty_first) { dirty_first = first; dirty_last = last; }
     else { dirty_first = std::min(dirty_first, first); dirty_last = std::max(dirty_last, last); }
   }
+  // Optional device mirror (count * stride bytes), made at the first device-side use and initialised from `host`
+  // (context.cpp buffer_mirror).  Once it exists it is CURRENT everywhere: a host SetData pushes what it changed on the stream.  Device-side
+  // writers (urt_buffer_set_data_device, urt_skin_vertices) leave `host` behind: inside the stale element range (empty while
+  // stale_last < stale_first; kept as ONE range like the dirty one, so it may cover elements that are equal on both sides) the mirror is
+  // newer, and whatever reads `host` downloads the range first (buffer_sync_host).
+  DeviceBuf<char> mirror;
+  int stale_first = 0, stale_last = -1;
+  uint64_t downloads = 0;        // synchronising device-to-host copies of this buffer since its creation (urt_debug_buffer_state)
+  bool stale() const { return stale_last >= stale_first; }
+  void mark_stale(int first, int last) {
+    if (!stale()) { stale_first = first; stale_last = last; }
+    else { stale_first = std::min(stale_first, first); stale_last = std::max(stale_last, last); }
+  }
 };
 
 struct Texture {
@@ -266,6 +279,12 @@ struct urt_context {
   // urt_resample_below: the pixel list and its samples, both sized by the selected count, not by the image
   urtd::DeviceBuf<unsigned int> rs_counts; urtd::PinnedBuf<unsigned int> rs_total;
   urtd::DeviceBuf<urt_PathPixel> rs_pixels; urtd::DeviceBuf<float4> rs_samples;
+  // Buffer mirrors (context.cpp): what a host SetData changed in a mirrored buffer travels through one of kUpSlots pinned images, used
+  // round-robin; a slot is reused once the copy of its previous use has left it (event) — no wait for the stream's other work
+  static constexpr int kUpSlots = 4;
+  struct UpSlot { urtd::PinnedBuf<char> host; urtd::Event done; bool used = false; } up_slot[kUpSlots];
+  unsigned int up_next = 0;
+  urtd::DeviceBuf<float> bd_partial; urtd::PinnedBuf<float> bd_result;   // urt_buffer_bounds: the per-block partials (and, behind them, the result); its host image
 };
 
 namespace urtd {
@@ -294,6 +313,12 @@ inline Texture* find_texture(urt_context* ctx, urt_handle h) {
   return it == ctx->textures.end() ? nullptr : &it->second;
 }
 
+inline Buffer* find_buffer(urt_context* ctx, urt_handle h) {
+  auto it = ctx->buffers.find(h);
+  return it == ctx->buffers.end() ? nullptr : &it->second;
+}
+
+// The bound buffer of a slot, or null when it holds nothing.  Readers of `host` have called buffer_sync_host / sync_bound_hosts.
 inline const Buffer* bound_buffer(urt_context* ctx, int slot) {
   urt_handle h = ctx->bound[slot];
   if (!h) return nullptr;
@@ -322,6 +347,9 @@ inline bool valid_max_history(float v) { return !std::isnan(v) && (v == 0.0f || 
 
 // context.cpp
 int check_watchdog(urt_context* ctx);
+int download_elements(urt_context* ctx, Buffer& b, int first, int last);   // mirror -> host, synchronising, counted
+int buffer_sync_host(urt_context* ctx, Buffer& b);          // downloads the stale range (synchronises; counted), after which `host` is current
+int sync_bound_hosts(urt_context* ctx, unsigned int slots); // ... of the buffers bound to the slots of the mask
 int strip_count(int group_rows, int first_row, int row_stride);
 // scene_prep.cpp
 int prepare_scene(urt_context* ctx);

@@ -313,7 +313,7 @@ static int reproject_impl(urt_context* ctx, const urt_ReprojectImages* images, c
   const urt_ReprojectParams P = *params;
   urt_ReprojectMotion Mo{};
   if (with_motion && motion) Mo = *motion;
-  const Buffer* tab[2] = {nullptr, nullptr};
+  Buffer* tab[2] = {nullptr, nullptr};
   if (with_motion) {
     if (Mo.flags != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: motion flags must be 0");
     if (!valid_max_history(Mo.moved_max_history)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: moved_max_history must be 0 or >= 1");
@@ -361,6 +361,7 @@ static int reproject_impl(urt_context* ctx, const urt_ReprojectImages* images, c
     for (int k = 0; k < 2; k++) {
       if (!tab[k]) continue;
       const size_t bytes = (size_t)tab[k]->count * sizeof(urt_ObjectMotion);
+      if (int rc = buffer_sync_host(ctx, *tab[k])) return rc;                    // a table written on the device
       if (int rc = reserve(ctx, ctx->mo_table[k], (size_t)tab[k]->count, "reproject: motion table allocation", ctx->stream)) return rc;
       URT_HIP(ctx, hipMemcpyAsync(ctx->mo_table[k].get(), tab[k]->host.data(), bytes, hipMemcpyHostToDevice, touch(ctx)));
     }

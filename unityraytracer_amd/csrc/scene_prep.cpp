@@ -415,6 +415,7 @@ int prepare_incremental(urt_context* ctx) {
   urt_context::Scene& C = ctx->scene;
   if (!ctx->opt.refit || ctx->dirty_full || C.scene_allocs.empty()) return 1;
   if (ctx->dirty_slots & ~(small | (ctx->opt.refit_vertices ? geometry : 0u))) return 1;
+  if (int rc = sync_bound_hosts(ctx, small)) return rc;     // the small tables are packed from the host copies
   DevScene& S = C.ds;
   const Buffer* bm = bound_buffer(ctx, B_MESHOBJECTS);
   const Buffer* bs = bound_buffer(ctx, B_SPHERES);
@@ -455,19 +456,19 @@ int prepare_incremental(urt_context* ctx) {
   SceneTables T;
   if ((rc = pack_scene_tables(ctx, bm, bs, bound_buffer(ctx, B_MESHBVH), bound_buffer(ctx, B_SPHEREBVH), C.h_mesh_root, C.h_small_first, T))) return rc;
   if ((rc = store_scene_tables(ctx, T))) return rc;
-  // the dirty element ranges go into the device copies, on the stream, behind the wait above and ahead of the kernels that read them
-  // (the host memory is the buffer's own copy; the stream is waited for below, before a later SetData can change it)
-  uint64_t copied = 0;
-  if (bv) {
-    const size_t at = (size_t)bv->dirty_first * 12, bytes = (size_t)(bv->dirty_last - bv->dirty_first + 1) * 12;
-    URT_HIP(ctx, hipMemcpyAsync((char*)const_cast<float*>(C.refit.vertices) + at, bv->host.data() + at, bytes, hipMemcpyHostToDevice, touch(ctx)));
+  // the dirty element ranges go into the device copies, on the stream, behind the wait above and ahead of the kernels that read them.
+  // From a buffer with a device mirror (current by construction): device to device, and the host is not involved.  Else from the buffer's
+  // own host copy; the stream is waited for below, before a later SetData can change it.
+  uint64_t copied = 0, from_host = 0;
+  auto copy_dirty = [&](const Buffer* b, const float* scene_copy) -> hipError_t {
+    const size_t at = (size_t)b->dirty_first * 12, bytes = (size_t)(b->dirty_last - b->dirty_first + 1) * 12;
     copied += bytes;
-  }
-  if (bn) {
-    const size_t at = (size_t)bn->dirty_first * 12, bytes = (size_t)(bn->dirty_last - bn->dirty_first + 1) * 12;
-    URT_HIP(ctx, hipMemcpyAsync((char*)const_cast<float*>(C.refit.normals) + at, bn->host.data() + at, bytes, hipMemcpyHostToDevice, touch(ctx)));
-    copied += bytes;
-  }
+    if (b->mirror) return hipMemcpyAsync((char*)const_cast<float*>(scene_copy) + at, b->mirror.get() + at, bytes, hipMemcpyDeviceToDevice, touch(ctx));
+    from_host += bytes;
+    return hipMemcpyAsync((char*)const_cast<float*>(scene_copy) + at, b->host.data() + at, bytes, hipMemcpyHostToDevice, touch(ctx));
+  };
+  if (bv) URT_HIP(ctx, copy_dirty(bv, C.refit.vertices));
+  if (bn) URT_HIP(ctx, copy_dirty(bn, C.refit.normals));
   if (n_moved > 0) {
     URT_HIP(ctx, hipMemcpy(C.refit.matrices, matrices.data(), matrices.size() * sizeof(float), hipMemcpyHostToDevice));
     URT_HIP(ctx, hipMemcpy(C.refit.moved, moved.data(), moved.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -481,7 +482,7 @@ int prepare_incremental(urt_context* ctx) {
   }
   if (n_moved > 0 && (rc = rederive_nodes(ctx))) return rc;
   if ((rc = verify_cull_flags(ctx, T.cull, T.mesh_leaf))) return rc;       // against the (refitted) triangle records
-  if (copied > 0) URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));            // the copies have left the buffers' host memory
+  if (from_host > 0) URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));         // the copies have left the buffers' host memory
   if (n_deformed > 0) {
     // a refit keeps the topology, and a large deformation can make it a bad one: the cost of each deformed MeshObject's refitted tree
     // against what it was when the tree was built
@@ -517,6 +518,7 @@ int prepare_scene(urt_context* ctx) {
     int rc = prepare_incremental(ctx);
     if (rc != 1) return rc;                                 // updated in place (or failed)
   }
+  if (int rc = sync_bound_hosts(ctx, (1u << B_COUNT) - 1u)) return rc;   // everything below reads the host copies: device-written data come down first
   free_scene(ctx);
   urt_context::Scene& C = ctx->scene;
   DevScene& S = C.ds;

@@ -76,6 +76,11 @@ class RayTraceMaster:
         self._taov = None                            # temporal: two (hit, normal, id) sets, the previous and the new camera's
         self._moved_max_history = 0.0                # temporal: extra clamp of the count on pixels of moved objects (MoveObjects; 0 = none)
         self._tmotion = [None, None]                 # temporal: the mesh and the sphere motion table of the last MoveObjects (ComputeBuffers)
+        self._skins = {}                             # AttachSkin: MeshObject index -> its span, rest pose, bone indices and weights
+        self._skinBuffers = None                     # SkinMeshes: rest vertices, rest normals, bone indices, bone weights (ComputeBuffers of the vertex count)
+        self._boneBuffers = {}                       # SkinMeshes: MeshObject index -> its bone table (ComputeBuffer)
+        self._skinBoxes = {}                         # SkinMeshes: MeshObject index -> object-space (min, max) of its skinned span, from the GPU
+        self._boxCache = {}                          # SkinMeshes: MeshObject index -> (matrix bytes, id of the vertex list, world lo, world hi)
 
     # RM:215-230
     def RegisterObject(self, obj: RayTraceObject):
@@ -570,6 +575,154 @@ class RayTraceMaster:
         self._tspare = (self._converged, self._tcount)
         self._converged, self._tcount = color, count
 
+    def _mesh_index_arg(self, k, who: str, what: str):
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"{who}: {what} must be ints, not {type(k).__name__}")
+        if not 0 <= k < len(self.scene.mesh_objects):
+            raise IndexError(f"{who}: {what} names MeshObject {k}, the scene has {len(self.scene.mesh_objects)}")
+
+    # A mesh gets a skin: bone_indices (n, 4) int32 and bone_weights (n, 4) float32 for the n vertices of its vertex span (vertex_span).
+    # The span's positions and normals as the scene holds them NOW are kept as the rest pose.  Nothing reaches the library before
+    # SkinMeshes.  (The term rule — which of the four are live — is urt_skin_vertices', include/urt.h.)
+    def AttachSkin(self, mesh_index: int, bone_indices, bone_weights):
+        s = self.scene
+        if self._treesNeedRebuilding and self._rayTraceObjects:                    # the lists the index refers to do not exist yet
+            self.RebuildObjectLists()
+        self._mesh_index_arg(mesh_index, "AttachSkin", "mesh_index")
+        lo, hi = self.vertex_span(mesh_index)
+        n = hi - lo + 1
+        try:
+            idx = np.ascontiguousarray(bone_indices, dtype=np.int32)
+            wgt = np.ascontiguousarray(bone_weights, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("AttachSkin: bone_indices / bone_weights must be (n, 4) arrays") from None
+        for name, a in (("bone_indices", idx), ("bone_weights", wgt)):
+            if a.ndim != 2 or a.shape != (n, 4):
+                raise ValueError(f"AttachSkin: {name} must have shape ({n}, 4), the vertex span of MeshObject {mesh_index}, not {a.shape}")
+        self._skins[int(mesh_index)] = {
+            "span": (lo, hi), "indices": idx.copy(), "weights": wgt.copy(), "uploaded": False,
+            "rest_vertices": np.array(np.asarray(s.vertices, np.float32).reshape(-1, 3)[lo: hi + 1]),
+            "rest_normals": np.array(np.asarray(s.normals, np.float32).reshape(-1, 3)[lo: hi + 1])}
+
+    def _ensure_skin_buffers(self):
+        nv = self._vertexBuffer.count
+        if self._skinBuffers is not None and self._skinBuffers[0].count != nv:
+            for b in self._skinBuffers:
+                b.Release()
+            self._skinBuffers = None
+        if self._skinBuffers is None:
+            self._skinBuffers = tuple(ComputeBuffer(self.ctx, nv, stride) for stride in (12, 12, 16, 16))
+            for sk in self._skins.values():
+                sk["uploaded"] = False
+        for sk in self._skins.values():
+            if not sk["uploaded"] and sk["span"][1] >= sk["span"][0]:
+                for b, key in zip(self._skinBuffers, ("rest_vertices", "rest_normals", "indices", "weights")):
+                    b.SetData(sk[key], 0, sk["span"][0], len(sk[key]))
+                sk["uploaded"] = True
+
+    def _world_box(self, k: int, lo3, hi3):
+        """The float32 box of the eight corners of an object-space box through MeshObject k's localToWorldMatrix: float64, rounded outward."""
+        m = np.asarray(self.scene.mesh_objects[k]["localToWorldMatrix"], dtype=np.float64).reshape(4, 4).T
+        c = np.array([[x, y, z] for x in (lo3[0], hi3[0]) for y in (lo3[1], hi3[1]) for z in (lo3[2], hi3[2])], dtype=np.float64)
+        w = c @ m[:3, :3].T + m[:3, 3]
+        return np.nextafter(w.min(axis=0).astype(np.float32), np.float32(-np.inf)), np.nextafter(w.max(axis=0).astype(np.float32), np.float32(np.inf))
+
+    def _object_heap_with_skins(self):
+        """The object-level heap of the meshes: the skinned ones from the bounds the GPU found, the others from the scene's lists (kept
+        while their matrix and the vertex list stay the same)."""
+        s = self.scene
+        n = len(s.mesh_objects)
+        lo, hi = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+        for k in range(n):
+            if k in self._skinBoxes:
+                if self._skinBoxes[k] is not None:                                  # (None: no finite vertex — an empty box)
+                    lo[k], hi[k] = self._world_box(k, *self._skinBoxes[k])
+                continue
+            key = (np.asarray(s.mesh_objects[k]["localToWorldMatrix"]).tobytes(), id(s.vertices))
+            hit = self._boxCache.get(k)
+            if hit is None or hit[0] != key:
+                if self._rayTraceObjects:
+                    leaf = host_scene.mesh_leaf_bounds(s.mesh_objects[k: k + 1], s.vertices, s.indices)
+                    hit = (key, np.array(leaf["vmin"][0], np.float32), np.array(leaf["vmax"][0], np.float32))
+                else:
+                    l1, h1 = scenes.mesh_bounds(s.mesh_objects[k: k + 1], s.vertices, s.indices)
+                    hit = (key, l1[0], h1[0])
+                self._boxCache[k] = hit
+            lo[k], hi[k] = hit[1], hit[2]
+        if not self._rayTraceObjects:
+            return scenes.build_object_bvh(lo, hi)
+        leaves = np.zeros(n, dtype=scenes.BVHNODE_DT)
+        leaves["vmin"], leaves["vmax"], leaves["index"] = lo, hi, np.arange(n)
+        return host_scene.build_object_bvh(leaves)
+
+    # Skinned meshes move: poses = {MeshObject index: (n_bones, 12) bone matrices} for meshes that have a skin (AttachSkin); a bone is
+    # urt_ObjectMotion's a[12] — three columns of the linear part, then the translation — from the mesh's object space to itself.
+    # The DeformMeshes protocol without a host copy of the positions: the bones are uploaded (a few KB), every span is skinned on the GPU
+    # into the device side of the vertex and the normal buffer (include/urt.h urt_skin_vertices), its bounds come back from the GPU
+    # (urt_buffer_bounds), the object-level heap is rebuilt from the world box of their eight corners and uploaded, and the library refits
+    # the skinned meshes in place without the positions ever crossing the bus.  The scene's vertex and normal lists keep what they held.
+    # History is treated exactly as DeformMeshes treats it: all-NaN motion entries with temporal accumulation on, ResetAccumulation else.
+    def SkinMeshes(self, poses):
+        s = self.scene
+        poses = dict(poses)
+        if self._treesNeedRebuilding and self._rayTraceObjects:
+            self.RebuildObjectLists()
+        checked = {}
+        for k, bones in poses.items():
+            self._mesh_index_arg(k, "SkinMeshes", "the keys of poses")
+            if int(k) not in self._skins:
+                raise ValueError(f"SkinMeshes: MeshObject {k} has no skin (AttachSkin)")
+            try:
+                a = np.ascontiguousarray(bones, dtype=np.float32)
+            except (TypeError, ValueError):
+                raise ValueError(f"SkinMeshes: poses[{k}] must be an (n_bones, 12) array") from None
+            if a.ndim != 2 or a.shape[1] != 12 or a.shape[0] < 1:
+                raise ValueError(f"SkinMeshes: poses[{k}] must have shape (n_bones, 12) with n_bones >= 1, not {a.shape}")
+            checked[int(k)] = a
+        if self._treesNeedRebuilding:                                             # the buffers the skin writes into must exist
+            self._bind_for_queries()
+        history = self._temporal is not None and self._converged is not None and self._currentSample > 0 \
+            and (self._converged.width, self._converged.height) == (self.screen_width, self.screen_height)
+        if history:
+            self._ensure_temporal_textures()
+            prev_m = scenes.world_to_clip(s.camera_to_world, s.camera_inverse_projection)
+            prev, cur = self._taov
+            self.SetShaderParameters()
+            self.ctx.render_aov(prev[0], prev[1], None, prev[2])               # the scene as the history saw it
+        self._ensure_skin_buffers()
+        rest_v, rest_n, idx, wgt = self._skinBuffers
+        for k, a in checked.items():
+            lo, hi = self._skins[k]["span"]
+            if hi < lo:
+                continue
+            self._boneBuffers[k] = self.CreateComputeBuffer(self._boneBuffers.get(k), a, 48)
+            self.ctx.skin_vertices(rest_v, rest_n, idx, wgt, self._boneBuffers[k], lo, hi - lo + 1, self._vertexBuffer, self._normalBuffer)
+        for k in checked:
+            lo, hi = self._skins[k]["span"]
+            if hi < lo:
+                continue
+            lo3, hi3, n = self.ctx.buffer_bounds(self._vertexBuffer, lo, hi - lo + 1)
+            self._skinBoxes[k] = (lo3, hi3) if n > 0 else None
+        if checked:
+            s.mesh_bvh = self._object_heap_with_skins()
+            self._meshObjectBVHBuffer = self.CreateComputeBuffer(self._meshObjectBVHBuffer, s.mesh_bvh, self.BVHNodeSize)
+        if not history:
+            self.ResetAccumulation()
+            return
+        self.SetShaderParameters()
+        self.ctx.render_aov(cur[0], cur[1], None, cur[2])                      # the skinned scene
+        table = host_scene.mesh_motion(s.mesh_objects, s.mesh_objects)             # nothing else has moved: identity entries
+        for k in checked:
+            table[k] = np.nan
+        self._tmotion[0] = self.CreateComputeBuffer(self._tmotion[0], table if checked else np.zeros((0, 12), np.float32), 48)
+        self._tmotion[1] = self.CreateComputeBuffer(self._tmotion[1], np.zeros((0, 12), np.float32), 48)
+        color, count = self._tspare
+        self.ctx.reproject(self._converged, self._tcount, prev[0], prev[1], prev[2], cur[0], cur[1], cur[2], color, count, prev_m,
+                           mesh_motion=self._tmotion[0], sphere_motion=self._tmotion[1], moved_max_history=self._moved_max_history,
+                           **self._temporal)
+        self._tspare = (self._converged, self._tcount)
+        self._converged, self._tcount = color, count
+
     # the edited lists become the scene's, with the object-level heaps RebuildObjectLists / the scene builders make for them, and are
     # uploaded (RebuildTrees: SetData of data a buffer already holds changes nothing)
     def _apply_object_edits(self, new_mo, new_sp, mesh_edits, sphere_edits):
@@ -637,9 +790,10 @@ class RayTraceMaster:
     # RM:188-212
     def OnDisable(self):
         for b in (self._sphereBuffer, self._meshObjectBuffer, self._vertexBuffer, self._indexBuffer, self._normalBuffer,
-                  self._sphereBVHBuffer, self._meshObjectBVHBuffer):
+                  self._sphereBVHBuffer, self._meshObjectBVHBuffer) + tuple(self._skinBuffers or ()) + tuple(self._boneBuffers.values()):
             if b is not None:
                 b.Release()
+        self._skinBuffers, self._boneBuffers = None, {}
         for t in (self._target, self._converged, self.SkyboxTexture, self._denoised) + (self._aov or ()):
             if t is not None:
                 t.Release()

@@ -96,6 +96,46 @@ class Context:
         self.check(self.lib.urt_debug_scene_cost(self._h, out.ctypes.data_as(C.c_void_p), int(n_meshes)))
         return out
 
+    def skin_vertices(self, rest_vertices, rest_normals, bone_indices, bone_weights, bones, first: int, count: int, dst_vertices,
+                      dst_normals=None):
+        """Linear blend skinning of elements first .. first + count - 1 on the GPU, into the device mirrors of dst_vertices (and
+        dst_normals) — include/urt.h urt_skin_vertices.  Every argument but the range is a ComputeBuffer; rest_normals and dst_normals
+        may be None (positions only).  Enqueued on the context's stream; nothing is waited for."""
+        def handle(b, name, optional=False):
+            if b is None and optional:
+                return 0
+            if not isinstance(b, ComputeBuffer):
+                raise TypeError(f"skin_vertices: {name} must be a ComputeBuffer{' or None' if optional else ''}, not {type(b).__name__}")
+            if b.ctx is not self:
+                raise ValueError(f"skin_vertices: {name} belongs to another context")
+            return b.handle
+        for name, v in (("first", first), ("count", count)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"skin_vertices: {name} must be an int, not {type(v).__name__}")
+        sb = _lib.SkinBuffers(handle(rest_vertices, "rest_vertices"), handle(rest_normals, "rest_normals", True),
+                              handle(bone_indices, "bone_indices"), handle(bone_weights, "bone_weights"), handle(bones, "bones"))
+        self.check(self.lib.urt_skin_vertices(self._h, C.byref(sb), int(first), int(count), handle(dst_vertices, "dst_vertices"),
+                                              handle(dst_normals, "dst_normals", True)))
+
+    def buffer_bounds(self, buffer, first: int = 0, count: int | None = None):
+        """(min [3], max [3], n): component-wise bounds over the finite elements first .. first + count - 1 of a stride-12 ComputeBuffer,
+        reduced on the GPU from its current contents, and their number (include/urt.h urt_buffer_bounds; synchronises).  No finite element:
+        (+inf, -inf, 0)."""
+        if not isinstance(buffer, ComputeBuffer):
+            raise TypeError(f"buffer_bounds: buffer must be a ComputeBuffer, not {type(buffer).__name__}")
+        count = buffer.count - int(first) if count is None else count
+        out, n = np.zeros(6, dtype=np.float32), C.c_int()
+        self.check(self.lib.urt_buffer_bounds(self._h, buffer.handle, int(first), int(count), out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out[:3].copy(), out[3:].copy(), n.value
+
+    def buffer_state(self, buffer) -> dict:
+        """Where a ComputeBuffer's contents live (include/urt.h urt_debug_buffer_state): the element range in which the device mirror is
+        newer than the host copy (stale_first > stale_last: none), the mirror's bytes (0: no mirror), and the synchronising downloads of
+        this buffer so far."""
+        a = (C.c_uint64 * 4)()
+        self.check(self.lib.urt_debug_buffer_state(self._h, buffer.handle, a))
+        return {"stale_first": int(a[0]), "stale_last": int(a[1]), "mirror_bytes": int(a[2]), "downloads": int(a[3])}
+
     def serve_stats(self) -> dict:
         """kernel_mode 5 with count_stats: the shared traversal service since the last reset_counters()."""
         a = (C.c_ulonglong * 6)()
@@ -807,6 +847,46 @@ class ComputeBuffer:
             raise UrtError(1, f"SetData: elements {managed_start} .. {managed_start + count - 1} lie outside the {n} elements of data")
         ptr = C.c_void_p(a.ctypes.data + int(managed_start) * self.stride) if n else C.c_void_p(0)
         self.ctx.check(self.ctx.lib.urt_buffer_set_data_range(self.ctx._h, self.handle, int(compute_start), ptr, int(count)))
+
+    def SetDataDevice(self, tensor_or_ptr, compute_start: int = 0, count: int | None = None):
+        """Ranged SetData from DEVICE memory (include/urt.h urt_buffer_set_data_device): `count` elements go to elements compute_start ..
+        compute_start + count - 1 of the buffer.  A contiguous torch tensor on the context's device (count defaults to what it holds; what
+        torch's current stream has written to it is waited for first), or a raw device address with an explicit count, whose producer the
+        caller orders.  The copy is enqueued on the context's stream and not waited for: the source stays as it is until
+        ctx.synchronize()."""
+        for name, v in (("compute_start", compute_start), ("count", 0 if count is None else count)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"SetDataDevice: {name} must be an int, not {type(v).__name__}")
+        if _is_torch(tensor_or_ptr):
+            import torch
+            t = tensor_or_ptr
+            if t.device.type != "cuda" or t.device.index != self.ctx.device:
+                raise ValueError(f"SetDataDevice: the tensor must be on cuda:{self.ctx.device}, not {t.device}")
+            if not t.is_contiguous():
+                raise ValueError("SetDataDevice: the tensor must be contiguous")
+            nbytes = t.numel() * t.element_size()
+            if nbytes % self.stride:
+                raise UrtError(1, f"SetDataDevice: {nbytes} bytes is not a multiple of stride {self.stride}")
+            count = nbytes // self.stride if count is None else count
+            if count < 0 or count * self.stride > nbytes:
+                raise UrtError(1, f"SetDataDevice: {count} elements lie outside the {nbytes // self.stride} elements of the tensor")
+            torch.cuda.current_stream(t.device).synchronize()
+            ptr = t.data_ptr() if nbytes else 0
+        else:
+            if isinstance(tensor_or_ptr, (bool, np.bool_)) or not isinstance(tensor_or_ptr, (int, np.integer)):
+                raise TypeError(f"SetDataDevice: a torch tensor or a device address is needed, not {type(tensor_or_ptr).__name__}")
+            if count is None:
+                raise TypeError("SetDataDevice: count is needed with a device address")
+            ptr = int(tensor_or_ptr)
+        self.ctx.check(self.ctx.lib.urt_buffer_set_data_device(self.ctx._h, self.handle, int(compute_start), C.c_void_p(ptr), int(count)))
+
+    def GetData(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """ComputeBuffer.GetData: elements first .. first + count - 1 as the buffer holds them now, as (count, stride) bytes — the caller
+        views them as its element type (include/urt.h urt_buffer_get_data_range; downloads what was written on the device, waits)."""
+        count = self.count - int(first) if count is None else count
+        out = np.zeros((max(0, int(count)), self.stride), dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.urt_buffer_get_data_range(self.ctx._h, self.handle, int(first), out.ctypes.data_as(C.c_void_p), int(count)))
+        return out
 
     def Release(self):
         if self.handle:
