@@ -54,8 +54,9 @@ URT_API int urt_abi_version(void);                       /* bumps when this head
                                                             the feature buffers, the denoiser, the temporal reprojection, the
                                                             resampling, the ranged SetData and the device side of the buffers —
                                                             urt_buffer_set_data_device, urt_buffer_get_data_range,
-                                                            urt_skin_vertices, urt_buffer_bounds, urt_debug_buffer_state — were
-                                                            added without changing anything that existed) */
+                                                            urt_skin_vertices, urt_buffer_bounds, urt_debug_buffer_state — and
+                                                            the normals on the device were added without changing anything
+                                                            that existed) */
 URT_API int urt_device_count(int* out_count);
 /* One context per process and GPU (the one-process-per-GPU model).  device = HIP ordinal. */
 URT_API int urt_context_create(int device, urt_context** out_ctx);
@@ -155,6 +156,62 @@ URT_API int urt_buffer_bounds(urt_context* ctx, urt_handle buffer, int first, in
 /* out4: the stale element range (first, last; first > last when it is empty), the bytes of the device mirror (0: none), the downloads
  * of this buffer since its creation. */
 URT_API int urt_debug_buffer_state(urt_context* ctx, urt_handle buffer, uint64_t out4[4]);
+
+/* ---- normals on the device ---------------------------------------------------------------------------------------------------------
+ * RayTraceMaster.ComputeNormals (RM:340-368) for positions that live in a buffer's device mirror: what urt_host_compute_normals computes
+ * on the host, bit for bit, written into the device side of a normals buffer, where the in-place update picks it up (option
+ * "refit_vertices").  The reference gives a vertex every index slot, across all meshes, whose vertex position equals its own (-0 == +0;
+ * coordinates below 2^-50 also weld pairwise under EPSILON = 3 * float.Epsilon, which is not transitive), sums the un-normalised face
+ * normals of those slots in ascending slot order (a triangle with two such slots counts twice) and normalises.
+ * That weld relation depends on positions.  A NORMALS PLAN finds it once, on the host, from the buffers' contents at plan time, for
+ * the served vertices first .. first+count-1 against ALL index slots of `indices` (a vertex of another mesh at the same position
+ * contributes).  Its canonical form, which urt_debug_build_normals_plan returns:
+ *   tris     the needed triangles — those that own at least one slot in the list of a served vertex — in ascending original triangle
+ *            number, three vertex indices each: the plan's OWN copy, validated at creation and never re-read from `indices`
+ *   entries  compact triangle ids (positions in tris), one per contributing slot, each list in ascending slot order; the lists are laid
+ *            out in the order of the first served vertex that uses them, and vertices of one position share one list
+ *   ranges   {start, length} into entries, one per served vertex (a vertex no slot names: length 0)
+ * CONTRACT: in the served rows the result of urt_compute_normals equals urt_host_compute_normals of the buffers' current contents
+ * WHENEVER THE CURRENT POSITIONS WELD AS THE PLAN-TIME POSITIONS DID.  The contract covers the vertices buffer only: a host that
+ * changes `indices`, or whose deformation merges or splits coincident vertices, makes a new plan.  A plan that is stale in this sense
+ * still reads only its own validated tris: it is never a fault.
+ * NORMATIVE arithmetic: float32, one rounding per operation, no fma, evaluated as written.  Per needed triangle (a, b, c):
+ *     e1 = b - a, e2 = c - a per component;  face = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x)
+ * per served vertex, from s = (0, 0, 0) and over its entries sequentially in their order:  s = s + face per component; then
+ *     mag = f_sqrt((s.x*s.x + s.y*s.y) + s.z*s.z);   n = mag > 1e-5f ? (s.x / mag, s.y / mag, s.z / mag) : (0, 0, 0)
+ * with IEEE division and the correctly rounded f_sqrt of urt_math.h.  A NaN mag fails the comparison and gives zeros, a served vertex
+ * with an empty list gets (0, 0, 0); non-finite positions flow through the arithmetic and are never a fault and never an error.  One
+ * vertex's sum is never split, chunked or tree-reduced: the order is the specification.
+ * There are no urt_group_* twins of the calls of this section (urt_group_context reaches a rank's context). */
+typedef struct urt_NormalsPlanInfo {
+  int32_t first, count, n_lists, n_triangles, n_entries, max_valence;
+  uint64_t device_bytes;
+} urt_NormalsPlanInfo;   /* 32 bytes */
+/* Makes a plan from the HOST copies of `vertices` (stride 12) and `indices` (stride 4, a count that is a multiple of 3) as they are now:
+ * an explicitly synchronising set-up call — a stale range is downloaded first (counted by urt_debug_buffer_state) — which uploads the
+ * plan and returns its handle.  count == 0 is allowed and gives an empty plan.  URT_ERR_INVALID_HANDLE: a buffer handle that is 0 or
+ * unknown; URT_ERR_INVALID_ARGUMENT: strides or an index count that do not fit, a range outside the vertices buffer, NULL out_plan;
+ * URT_ERR_SCENE: an index outside the vertices buffer; URT_ERR_OUT_OF_MEMORY.  On any error nothing is allocated. */
+URT_API int urt_normals_plan_create(urt_context* ctx, urt_handle vertices, urt_handle indices, int first, int count, urt_handle* out_plan);
+URT_API int urt_normals_plan_info(urt_context* ctx, urt_handle plan, urt_NormalsPlanInfo* out);
+/* Gives the plan's device memory back (urt_context_destroy does the same).  A plan stays releasable after urt_buffer_release of its buffers. */
+URT_API int urt_normals_plan_release(urt_context* ctx, urt_handle plan);
+/* Recomputes the normals of the plan's served vertices from the CURRENT contents of its vertices buffer into the device mirror of
+ * dst_normals (both buffers get mirrors): two kernels are enqueued on the context's stream — the face normals of the needed triangles
+ * into a grow-only scratch of 16 bytes per face held by the context, then one served vertex per lane — nothing is synchronised and
+ * deferred frames stay deferred.  dst_normals[first .. first+count-1] becomes stale and dirty as a whole, exactly as with
+ * urt_skin_vertices; rows outside the served range are not written.
+ * Checked before anything is enqueued or marked: URT_ERR_INVALID_HANDLE for an unknown plan, a plan whose vertices buffer was released,
+ * a dst_normals that is 0 or unknown; URT_ERR_INVALID_ARGUMENT for a dst_normals whose stride is not 12, whose count differs from the
+ * vertices buffer's, or that is the vertices buffer itself.  An empty plan returns URT_OK after the checks. */
+URT_API int urt_compute_normals(urt_context* ctx, urt_handle plan, urt_handle dst_normals);
+/* Host only, no GPU: the canonical plan above, for tests and for hosts that want to inspect it.  ranges takes 2 * count words, entries
+ * up to cap_entries words, tris up to 3 * cap_tris words; out_sizes = n_entries, n_triangles, max_valence.  Every output pointer may be
+ * NULL (to ask for the sizes first); an array that is given and too small is URT_ERR_INVALID_ARGUMENT, as are bad counts, NULL inputs
+ * and a range outside the vertices; URT_ERR_SCENE: an index outside the vertices (urt_host_last_error). */
+URT_API int urt_debug_build_normals_plan(const float* vertices, int n_vertices, const int32_t* indices, int n_indices, int first, int count,
+                                         int32_t* ranges, int32_t* entries, int cap_entries, int32_t* tris, int cap_tris,
+                                         int32_t out_sizes[3]);
 
 /* ---- RenderTexture / Texture (RGBA32F = ARGBFloat, linear) -------------------------------- */
 /* new RenderTexture(w, h, 0, ARGBFloat, Linear){enableRandomWrite}.Create()   RM:834-840 */

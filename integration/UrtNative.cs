@@ -30,6 +30,13 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_skin_vertices(IntPtr ctx, in SkinBuffers buffers, int first, int count, ulong dstVertices, ulong dstNormals);
     [DllImport(Lib)] internal static extern int urt_buffer_bounds(IntPtr ctx, ulong buffer, int first, int count, [Out] float[] out6, out int finiteElements);
     [DllImport(Lib)] internal static extern int urt_debug_buffer_state(IntPtr ctx, ulong buffer, [Out] ulong[] out4);   // stale first, stale last, mirror bytes, downloads
+    // normals on the device (include/urt.h): ComputeNormals of positions that live in a buffer's device mirror, over a plan made once per topology
+    [StructLayout(LayoutKind.Sequential)] internal struct NormalsPlanInfo { public int first, count, nLists, nTriangles, nEntries, maxValence; public ulong deviceBytes; }   // 32 B
+    [DllImport(Lib)] internal static extern int urt_normals_plan_create(IntPtr ctx, ulong vertices, ulong indices, int first, int count, out ulong plan);
+    [DllImport(Lib)] internal static extern int urt_normals_plan_info(IntPtr ctx, ulong plan, out NormalsPlanInfo info);
+    [DllImport(Lib)] internal static extern int urt_normals_plan_release(IntPtr ctx, ulong plan);
+    [DllImport(Lib)] internal static extern int urt_compute_normals(IntPtr ctx, ulong plan, ulong dstNormals);
+    [DllImport(Lib)] internal static extern int urt_debug_build_normals_plan(float[] vertices, int nVertices, int[] indices, int nIndices, int first, int count, [Out] int[] ranges, [Out] int[] entries, int capEntries, [Out] int[] tris, int capTris, [Out] int[] outSizes3);
     [DllImport(Lib)] internal static extern int urt_buffer_get_info(IntPtr ctx, ulong buffer, out int count, out int stride);
     [DllImport(Lib)] internal static extern int urt_buffer_release(IntPtr ctx, ulong buffer);
 

@@ -397,6 +397,26 @@ public sealed class UrtSkinnedMesh {
     }
 }
 
+/// RayTraceMaster.ComputeNormals (RM:340-368) on the GPU for a vertex span whose positions were written on the device (UrtSkinnedMesh, a
+/// SetData from device memory): include/urt.h urt_normals_plan_create / urt_compute_normals.  The plan is made once per topology from the
+/// buffers as they are then (a synchronising set-up call); Compute enqueues two kernels that write the span's normals into the device
+/// side of the _Normals buffer, where the in-place update picks them up.  A host that changes _Indices, or whose deformation merges or
+/// splits coincident vertices, makes a new plan.  On one context only, as UrtSkinnedMesh.
+public sealed class UrtNormalsPlan {
+    ulong handle;
+    public UrtNormalsPlan(UrtComputeBuffer vertices, UrtComputeBuffer indices, int first, int count) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtNormalsPlan: plan on one rank's context (urt_group_context)");
+        UrtDevice.Check(UrtNative.urt_normals_plan_create(UrtDevice.Handle, vertices.handle, indices.handle, first, count, out handle));
+    }
+    /// served vertices, welded lists, needed triangles, contributing slots, the longest list, bytes on the device
+    public void Info(out int first, out int count, out int lists, out int triangles, out int entries, out int maxValence, out ulong deviceBytes) {
+        UrtDevice.Check(UrtNative.urt_normals_plan_info(UrtDevice.Handle, handle, out UrtNative.NormalsPlanInfo i));
+        first = i.first; count = i.count; lists = i.nLists; triangles = i.nTriangles; entries = i.nEntries; maxValence = i.maxValence; deviceBytes = i.deviceBytes;
+    }
+    public void Compute(UrtComputeBuffer dstNormals) { UrtDevice.Check(UrtNative.urt_compute_normals(UrtDevice.Handle, handle, dstNormals.handle)); }
+    public void Release() { if (handle != 0) { UrtDevice.Check(UrtNative.urt_normals_plan_release(UrtDevice.Handle, handle)); handle = 0; } }
+}
+
 /// new RenderTexture(w, h, 0, ARGBFloat, Linear) { enableRandomWrite = true }.Create(); .Release(); .width; .height   (RM:824-845)
 public sealed class UrtRenderTexture {
     internal ulong handle;

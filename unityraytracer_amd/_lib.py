@@ -17,12 +17,12 @@ ERROR_NAMES = {1: "INVALID_ARGUMENT", 2: "INVALID_HANDLE", 3: "NO_DEVICE", 4: "H
 # every symbol include/urt.h declares (tests check that the .so exports each of them)
 ABI_SYMBOLS = [
     "urt_abi_version", "urt_device_count", "urt_context_create", "urt_context_destroy", "urt_last_error", "urt_context_set_stream",
-    "urt_synchronize", "urt_flush", "urt_buffer_create", "urt_buffer_set_data", "urt_buffer_set_data_range", "urt_buffer_set_data_device", "urt_buffer_get_data_range", "urt_skin_vertices", "urt_buffer_bounds", "urt_buffer_get_info", "urt_buffer_release", "urt_texture_create",
+    "urt_synchronize", "urt_flush", "urt_buffer_create", "urt_buffer_set_data", "urt_buffer_set_data_range", "urt_buffer_set_data_device", "urt_buffer_get_data_range", "urt_skin_vertices", "urt_buffer_bounds", "urt_normals_plan_create", "urt_normals_plan_info", "urt_normals_plan_release", "urt_compute_normals", "urt_buffer_get_info", "urt_buffer_release", "urt_texture_create",
     "urt_texture_create_external", "urt_texture_set_pixels", "urt_texture_get_pixels", "urt_texture_get_info", "urt_texture_read_begin", "urt_texture_read_end", "urt_texture_read_begin_format", "urt_texture_read_end_format", "urt_texture_release",
     "urt_shader_set_buffer", "urt_shader_set_texture", "urt_shader_set_matrix", "urt_shader_set_vector", "urt_shader_set_float",
     "urt_shader_set_int", "urt_shader_dispatch", "urt_shader_dispatch_rows", "urt_blit_add", "urt_blit", "urt_texture_pack_rows",
     "urt_texture_unpack_rows", "urt_texture_unpack_rows_on", "urt_texture_pack_rows_rgb", "urt_texture_unpack_rows_rgb", "urt_ray_query", "urt_ray_query_device", "urt_radiance_query", "urt_radiance_query_device", "urt_render_aov", "urt_denoise", "urt_reproject", "urt_reproject_objects", "urt_blit_add_history", "urt_select_pixels", "urt_blend_samples", "urt_resample_below", "urt_set_option", "urt_get_counters", "urt_reset_counters", "urt_debug_build_blas", "urt_debug_get_blas", "urt_debug_blas_cache_stats",
-    "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_read_scene_cones", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_deform_stats", "urt_debug_scene_cost", "urt_debug_buffer_state", "urt_debug_live_resources", "urt_debug_build_walk_table", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
+    "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_read_scene_cones", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_deform_stats", "urt_debug_scene_cost", "urt_debug_buffer_state", "urt_debug_live_resources", "urt_debug_build_walk_table", "urt_debug_build_normals_plan", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
     "urt_host_build_object_bvh", "urt_host_build_object_bvh_pairing", "urt_host_mesh_motion", "urt_host_sphere_motion", "urt_host_last_error", "urt_host_load_hdr", "urt_host_write_pfm", "urt_host_write_png", "urt_host_encode_srgb8", "urt_host_srgb8_first_floats",
     "urt_host_resize_rgba", "urt_host_io_last_error", "urt_host_log", "urt_host_log_scene_counts", "urt_host_log_tree_report", "urt_host_dump_bvh", "urt_host_dump_normals",
     "urt_host_debug_last_error",
@@ -112,6 +112,11 @@ class SkinBuffers(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("rest_vertices", "rest_normals", "bone_indices", "bone_weights", "bones")]
 
 
+class NormalsPlanInfo(C.Structure):
+    """urt_NormalsPlanInfo (include/urt.h), 32 B: what urt_normals_plan_info reports of a normals plan."""
+    _fields_ = [(n, C.c_int32) for n in ("first", "count", "n_lists", "n_triangles", "n_entries", "max_valence")] + [("device_bytes", C.c_uint64)]
+
+
 # the starting values a host passes to urt_reproject / urt_blit_add_history (include/urt.h URT_REPROJECT_DEFAULT_*)
 REPROJECT_DEFAULTS = {"max_history": 64.0, "normal_threshold": 0.9, "plane_threshold": 0.02}
 
@@ -172,6 +177,11 @@ def load():
         "urt_skin_vertices": ([vp, C.POINTER(SkinBuffers), i, i, u64, u64], i),
         "urt_buffer_bounds": ([vp, u64, i, i, vp, pi], i),
         "urt_debug_buffer_state": ([vp, u64, vp], i),
+        "urt_normals_plan_create": ([vp, u64, u64, i, i, C.POINTER(u64)], i),
+        "urt_normals_plan_info": ([vp, u64, C.POINTER(NormalsPlanInfo)], i),
+        "urt_normals_plan_release": ([vp, u64], i),
+        "urt_compute_normals": ([vp, u64, u64], i),
+        "urt_debug_build_normals_plan": ([vp, i, vp, i, i, i, vp, vp, i, vp, i, vp], i),
         "urt_buffer_get_info": ([vp, u64, pi, pi], i),
         "urt_buffer_release": ([vp, u64], i),
         "urt_texture_create": ([vp, i, i, C.POINTER(u64)], i),

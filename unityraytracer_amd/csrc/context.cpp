@@ -14,6 +14,8 @@
 #include <limits>
 #include <memory>
 
+#include "normals.h"
+#include "normals_plan.h"
 #include "present.h"
 #include "reproject.h"
 #include "skin.h"
@@ -413,6 +415,92 @@ int urt_debug_buffer_state(urt_context* ctx, urt_handle buffer, uint64_t out4[4]
   out4[2] = b->mirror ? (uint64_t)b->count * (uint64_t)b->stride : 0;
   out4[3] = b->downloads;
   return URT_OK;
+}
+
+/* ---- normals on the device (include/urt.h; csrc/normals_plan.h, csrc/normals.hip) ---- */
+int urt_normals_plan_create(urt_context* ctx, urt_handle vertices, urt_handle indices, int first, int count, urt_handle* out_plan) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (!out_plan) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "normals_plan_create: out_plan is NULL");
+  *out_plan = 0;
+  URT_GUARD_BEGIN
+  Buffer* v = find_buffer(ctx, vertices);
+  Buffer* ix = find_buffer(ctx, indices);
+  if (!v || !ix) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string("normals_plan_create: ") + (!v ? "vertices" : "indices") + " is 0 or an unknown buffer handle");
+  if (v->stride != 12) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "normals_plan_create: the stride of vertices is not 12");
+  if (ix->stride != 4) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "normals_plan_create: the stride of indices is not 4");
+  if (ix->count % 3 != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "normals_plan_create: the count of indices is not a multiple of 3");
+  if (int rc = check_element_range(ctx, "normals_plan_create", *v, first, count)) return rc;
+  if (int rc = buffer_sync_host(ctx, *v)) return rc;         // the weld is found from the buffers' contents NOW
+  if (int rc = buffer_sync_host(ctx, *ix)) return rc;
+  NormalsPlan plan;
+  if (normals_plan_build((const float*)v->host.data(), v->count, (const int32_t*)ix->host.data(), ix->count, first, count, plan) != kNormalsPlanOk)
+    return fail(ctx, URT_ERR_SCENE, "normals_plan_create: index outside _Vertices");
+  DevNormalsPlan d;
+  d.vertices = vertices; d.n_vertices = v->count;
+  d.first = first; d.count = count; d.n_lists = plan.n_lists; d.max_valence = plan.max_valence;
+  d.n_triangles = (int)(plan.tris.size() / 3); d.n_entries = (int)plan.entries.size();
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  const std::pair<DeviceBuf<int32_t>*, const std::vector<int32_t>*> parts[3] = {{&d.tris, &plan.tris}, {&d.entries, &plan.entries}, {&d.ranges, &plan.ranges}};
+  for (const auto& p : parts) {
+    if (p.second->empty()) continue;
+    const size_t bytes = p.second->size() * sizeof(int32_t);
+    URT_HIP(ctx, p.first->alloc(p.second->size()));           // (a failure leaves through the holders: nothing stays allocated)
+    URT_HIP(ctx, hipMemcpy(p.first->get(), p.second->data(), bytes, hipMemcpyHostToDevice));
+    d.device_bytes += bytes;
+  }
+  const urt_handle h = ctx->next_id++;
+  ctx->normals_plans.emplace(h, std::move(d));
+  *out_plan = h;
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+int urt_normals_plan_info(urt_context* ctx, urt_handle plan, urt_NormalsPlanInfo* out) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  auto it = ctx->normals_plans.find(plan);
+  if (it == ctx->normals_plans.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "normals_plan_info: unknown plan handle");
+  if (!out) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "normals_plan_info: out is NULL");
+  const DevNormalsPlan& d = it->second;
+  out->first = d.first; out->count = d.count; out->n_lists = d.n_lists; out->n_triangles = d.n_triangles;
+  out->n_entries = d.n_entries; out->max_valence = d.max_valence; out->device_bytes = d.device_bytes;
+  return URT_OK;
+}
+
+int urt_normals_plan_release(urt_context* ctx, urt_handle plan) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  auto it = ctx->normals_plans.find(plan);
+  if (it == ctx->normals_plans.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "normals_plan_release: unknown plan handle");
+  if (it->second.device_bytes) {                             // kernels queued on the stream may still read the plan
+    URT_HIP(ctx, hipSetDevice(ctx->device));
+    URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
+  }
+  ctx->normals_plans.erase(it);
+  return URT_OK;
+}
+
+int urt_compute_normals(urt_context* ctx, urt_handle plan, urt_handle dst_normals) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  auto it = ctx->normals_plans.find(plan);
+  if (it == ctx->normals_plans.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "compute_normals: unknown plan handle");
+  const DevNormalsPlan& d = it->second;
+  Buffer* v = find_buffer(ctx, d.vertices);
+  if (!v || v->count != d.n_vertices || v->stride != 12) return fail(ctx, URT_ERR_INVALID_HANDLE, "compute_normals: the plan's vertices buffer was released");
+  Buffer* dst = find_buffer(ctx, dst_normals);
+  if (!dst) return fail(ctx, URT_ERR_INVALID_HANDLE, "compute_normals: dst_normals is 0 or an unknown buffer handle");
+  if (dst->stride != 12) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "compute_normals: the stride of dst_normals is not 12");
+  if (dst->count != v->count) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "compute_normals: the count of dst_normals is not that of the vertices buffer");
+  if (dst_normals == d.vertices) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "compute_normals: dst_normals is the vertices buffer");
+  if (d.count == 0) return URT_OK;
+  if (int rc = buffer_mirror(ctx, *v)) return rc;
+  if (int rc = buffer_mirror(ctx, *dst)) return rc;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = reserve(ctx, ctx->nm_face, (size_t)d.n_triangles, "compute_normals: scratch allocation", ctx->stream)) return rc;
+  URT_HIP(ctx, compute_normals((const float*)v->mirror.get(), d.tris.get(), d.n_triangles, d.ranges.get(), d.entries.get(), d.first, d.count,
+                               ctx->nm_face.get(), (float*)dst->mirror.get(), touch(ctx)));
+  mark_device_written(ctx, dst_normals, *dst, d.first, d.count);
+  return URT_OK;
+  URT_GUARD_END(ctx)
 }
 
 int urt_buffer_get_info(urt_context* ctx, urt_handle buffer, int* out_count, int* out_stride) {

@@ -69,6 +69,16 @@ struct Texture {
   int rg[4] = {0, 0, 0, 0};     // region_w, region_h, first_group_row, row_stride
 };
 
+// urt_normals_plan_create: a normals plan (csrc/normals_plan.h) as the device holds it.  The plan keeps its own validated triangles and
+// only the HANDLE of the vertices buffer, looked up at every use.
+struct DevNormalsPlan {
+  urt_handle vertices = 0;
+  int n_vertices = 0;            // the count of the vertices buffer at creation: every index of `tris` lies below it
+  int first = 0, count = 0, n_lists = 0, n_triangles = 0, n_entries = 0, max_valence = 0;
+  DeviceBuf<int32_t> tris, entries, ranges;
+  uint64_t device_bytes = 0;
+};
+
 enum BindSlot { B_MESHOBJECTS, B_VERTICES, B_INDICES, B_NORMALS, B_SPHERES, B_MESHBVH, B_SPHEREBVH, B_COUNT };
 
 }  // namespace urtd
@@ -80,6 +90,7 @@ struct urt_context {
   std::string err;
   std::unordered_map<urt_handle, urtd::Buffer> buffers;
   std::unordered_map<urt_handle, urtd::Texture> textures;
+  std::unordered_map<urt_handle, urtd::DevNormalsPlan> normals_plans;
   urt_handle next_id = 1;
 
   urt_handle bound[urtd::B_COUNT] = {0, 0, 0, 0, 0, 0, 0};
@@ -285,6 +296,7 @@ struct urt_context {
   struct UpSlot { urtd::PinnedBuf<char> host; urtd::Event done; bool used = false; } up_slot[kUpSlots];
   unsigned int up_next = 0;
   urtd::DeviceBuf<float> bd_partial; urtd::PinnedBuf<float> bd_result;   // urt_buffer_bounds: the per-block partials (and, behind them, the result); its host image
+  urtd::DeviceBuf<float4> nm_face;            // urt_compute_normals: the face normals of the largest plan so far, 16 bytes each
 };
 
 namespace urtd {

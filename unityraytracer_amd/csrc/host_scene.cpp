@@ -16,10 +16,10 @@
 #include <cstring>
 #include <limits>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/urt.h"
+#include "normals_plan.h"
 
 namespace {
 
@@ -33,23 +33,6 @@ inline V3 normalize(V3 v) {                                                     
   return {0.0f, 0.0f, 0.0f};
 }
 inline V3 ld(const float* p) { return {p[0], p[1], p[2]}; }
-
-struct Key {
-  uint32_t a, b, c;
-  bool operator==(const Key& o) const { return a == o.a && b == o.b && c == o.c; }
-};
-struct KeyHash {
-  size_t operator()(const Key& k) const {
-    uint64_t h = 0x9E3779B97F4A7C15ull ^ k.a;
-    h = (h ^ (h >> 32)) * 0xBF58476D1CE4E5B9ull + k.b;
-    h = (h ^ (h >> 29)) * 0x94D049BB133111EBull + k.c;
-    return (size_t)(h ^ (h >> 31));
-  }
-};
-inline uint32_t bits_no_negzero(float f) {           // -0 == +0 for the reference's (a - b).sqrMagnitude test
-  uint32_t u; std::memcpy(&u, &f, 4);
-  return u == 0x80000000u ? 0u : u;
-}
 
 // MultiplyPoint3x4 on a Unity Matrix4x4 stored column-major (m[col*4+row]): rows evaluated left to right, mul then add
 inline V3 multiply_point_3x4(const float* m, V3 p) {
@@ -218,54 +201,14 @@ int urt_host_compute_normals(const float* vertices, int n_vertices, const int32_
   if (n_vertices < 0 || n_indices < 0 || n_indices % 3 != 0) return host_fail(URT_ERR_INVALID_ARGUMENT, "ComputeNormals: bad counts");
   if ((n_vertices && (!vertices || !out_normals)) || (n_indices && !indices)) return host_fail(URT_ERR_INVALID_ARGUMENT, "ComputeNormals: NULL array");
   try {
-    // RM:351 welds index slots whose vertex satisfies (v - v_i).sqrMagnitude <= EPSILON = 3 * float.Epsilon (4.2e-45): that is
-    // plain equality (-0 == +0) EXCEPT for differences so small that their squares underflow.  Two DIFFERENT positions can only
-    // pass when, on every axis, their coordinates are equal or both of magnitude below 2^-50 (distinct floats of magnitude
-    // >= 2^-50 differ by >= 2^-73, whose square 1.1e-44 already exceeds EPSILON; numerical zeros like sin(pi) * r = 1e-17
-    // are common in real meshes, so this is not a corner to ignore).
-    // Step 1: exact groups (O(V + I) position hash).
-    std::unordered_map<Key, int, KeyHash> groups;
-    groups.reserve((size_t)n_vertices * 2);
-    std::vector<int> group_of((size_t)n_vertices);
-    std::vector<int> rep;                                   // one vertex per group
-    for (int i = 0; i < n_vertices; i++) {
-      Key k{bits_no_negzero(vertices[3 * i]), bits_no_negzero(vertices[3 * i + 1]), bits_no_negzero(vertices[3 * i + 2])};
-      auto it = groups.find(k);
-      if (it == groups.end()) { it = groups.emplace(k, (int)groups.size()).first; rep.push_back(i); }
-      group_of[(size_t)i] = it->second;
-    }
-    const size_t ng = groups.size();
-    // Step 2: groups that weld with OTHER groups.  Candidates share a coarse key (coordinates below 2^-50 mapped to 0);
-    // inside a coarse bucket the reference's float test decides, pair by pair (the relation is not transitive).
-    const float kTiny = 8.8817842e-16f;                     // 2^-50
-    const float kEps = 3.0f * 1.401298464e-45f;              // RM:14
-    std::vector<std::vector<int>> partners(0);
-    std::vector<int> partner_slot(ng, -1);                   // group -> index into `partners`, or -1 (the common case)
-    {
-      std::unordered_map<Key, std::vector<int>, KeyHash> coarse;
-      for (size_t g = 0; g < ng; g++) {
-        const float* p = vertices + 3 * (size_t)rep[g];
-        bool has_small = false;
-        uint32_t kk[3];
-        for (int c = 0; c < 3; c++) { bool small = std::fabs(p[c]) < kTiny; has_small = has_small || small; kk[c] = small ? 0u : bits_no_negzero(p[c]); }
-        if (has_small) coarse[Key{kk[0], kk[1], kk[2]}].push_back((int)g);
-      }
-      for (auto& kv : coarse) {
-        const std::vector<int>& b = kv.second;
-        if (b.size() < 2) continue;
-        for (size_t x = 0; x < b.size(); x++)
-          for (size_t y = x + 1; y < b.size(); y++) {
-            V3 d = sub(ld(vertices + 3 * (size_t)rep[(size_t)b[x]]), ld(vertices + 3 * (size_t)rep[(size_t)b[y]]));
-            if (d.x * d.x + d.y * d.y + d.z * d.z <= kEps) {
-              for (int side = 0; side < 2; side++) {
-                int g = side ? b[y] : b[x], o = side ? b[x] : b[y];
-                if (partner_slot[(size_t)g] < 0) { partner_slot[(size_t)g] = (int)partners.size(); partners.emplace_back(); }
-                partners[(size_t)partner_slot[(size_t)g]].push_back(o);
-              }
-            }
-          }
-      }
-    }
+    // RM:351 welds index slots whose vertex satisfies (v - v_i).sqrMagnitude <= EPSILON = 3 * float.Epsilon (4.2e-45): exact groups
+    // (-0 == +0) and, for coordinates below 2^-50, pairwise partner groups — csrc/normals_plan.h, shared with the GPU's plan.
+    urtd::NormalsGroups G;
+    urtd::normals_groups(vertices, n_vertices, G);
+    const std::vector<int>& group_of = G.group_of;
+    const std::vector<int>& partner_slot = G.partner_slot;
+    const std::vector<std::vector<int>>& partners = G.partners;
+    const size_t ng = G.rep.size();
     std::vector<V3> acc(ng, V3{0, 0, 0});
     std::vector<std::vector<int>> slots(partners.size());    // ascending index slots of the groups that have partners
     // every index slot j (ascending, the order of the reference's LINQ query) adds the un-normalised normal of ITS
@@ -304,6 +247,27 @@ int urt_host_compute_normals(const float* vertices, int n_vertices, const int32_
     }
     return URT_OK;
   } catch (...) { return host_fail(URT_ERR_OUT_OF_MEMORY, "ComputeNormals: allocation failed"); }
+}
+
+int urt_debug_build_normals_plan(const float* vertices, int n_vertices, const int32_t* indices, int n_indices, int first, int count,
+                                 int32_t* ranges, int32_t* entries, int cap_entries, int32_t* tris, int cap_tris, int32_t out_sizes[3]) {
+  if (n_vertices < 0 || n_indices < 0 || n_indices % 3 != 0) return host_fail(URT_ERR_INVALID_ARGUMENT, "normals plan: bad counts");
+  if ((n_vertices && !vertices) || (n_indices && !indices)) return host_fail(URT_ERR_INVALID_ARGUMENT, "normals plan: NULL array");
+  if (first < 0 || count < 0 || (long long)first + (long long)count > (long long)n_vertices)
+    return host_fail(URT_ERR_INVALID_ARGUMENT, "normals plan: the served range lies outside the vertices");
+  try {
+    urtd::NormalsPlan plan;
+    if (urtd::normals_plan_build(vertices, n_vertices, indices, n_indices, first, count, plan) != urtd::kNormalsPlanOk)
+      return host_fail(URT_ERR_SCENE, "normals plan: index outside _Vertices");
+    const size_t ne = plan.entries.size(), nt = plan.tris.size() / 3;
+    if ((entries && (cap_entries < 0 || (size_t)cap_entries < ne)) || (tris && (cap_tris < 0 || (size_t)cap_tris < nt)))
+      return host_fail(URT_ERR_INVALID_ARGUMENT, "normals plan: an output array is too small");
+    if (out_sizes) { out_sizes[0] = (int32_t)ne; out_sizes[1] = (int32_t)nt; out_sizes[2] = plan.max_valence; }
+    if (ranges && count) std::memcpy(ranges, plan.ranges.data(), plan.ranges.size() * sizeof(int32_t));
+    if (entries && ne) std::memcpy(entries, plan.entries.data(), ne * sizeof(int32_t));
+    if (tris && nt) std::memcpy(tris, plan.tris.data(), 3 * nt * sizeof(int32_t));
+    return URT_OK;
+  } catch (...) { return host_fail(URT_ERR_OUT_OF_MEMORY, "normals plan: allocation failed"); }
 }
 
 int urt_host_mesh_leaf_bounds(const void* mesh_objects, int n_meshes, const float* vertices, int n_vertices, const int32_t* indices,

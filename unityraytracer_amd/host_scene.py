@@ -30,6 +30,22 @@ def compute_normals(vertices, indices) -> np.ndarray:
     return out
 
 
+def normals_plan(vertices, indices, first: int = 0, count: int | None = None) -> dict:
+    """The canonical normals plan of include/urt.h for the served vertices first .. first + count - 1 (urt_debug_build_normals_plan; no
+    GPU): ranges (count, 2), entries, tris (n_triangles, 3), max_valence."""
+    lib = _lib.load()
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    ix = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+    count = len(v) - int(first) if count is None else int(count)
+    sizes = np.zeros(3, dtype=np.int32)
+    _check(lib, lib.urt_debug_build_normals_plan(_p(v), len(v), _p(ix), ix.size, int(first), count, None, None, 0, None, 0, _p(sizes)))
+    ranges = np.zeros((max(count, 0), 2), dtype=np.int32)
+    entries, tris = np.zeros(int(sizes[0]), dtype=np.int32), np.zeros((int(sizes[1]), 3), dtype=np.int32)
+    _check(lib, lib.urt_debug_build_normals_plan(_p(v), len(v), _p(ix), ix.size, int(first), count, _p(ranges), _p(entries), entries.size,
+                                                 _p(tris), len(tris), _p(sizes)))
+    return {"ranges": ranges, "entries": entries, "tris": tris, "max_valence": int(sizes[2])}
+
+
 def mesh_leaf_bounds(mesh_objects, vertices, indices, literal: bool = False) -> np.ndarray:
     """SetupBVHLeaves(List<MeshObject>) (RM:405-433); literal=True keeps the reference's quirks."""
     lib = _lib.load()

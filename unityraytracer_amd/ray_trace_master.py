@@ -47,6 +47,7 @@ class RayTraceMaster:
     MeshObjectStructSize = 112   # RM:43
     SphereStructSize = 56        # RM:44
     BVHNodeSize = 28             # RM:45
+    _normalsPlans = {}           # (the instance's own from __init__ on; here so that host-only use of a master made without one has none to drop)
 
     def __init__(self, ctx: Context, scene: scenes.Scene, rank: int = 0, world_size: int = 1, frame_seed: int = 0x5EED):
         self.ctx = ctx
@@ -81,6 +82,7 @@ class RayTraceMaster:
         self._boneBuffers = {}                       # SkinMeshes: MeshObject index -> its bone table (ComputeBuffer)
         self._skinBoxes = {}                         # SkinMeshes: MeshObject index -> object-space (min, max) of its skinned span, from the GPU
         self._boxCache = {}                          # SkinMeshes: MeshObject index -> (matrix bytes, id of the vertex list, world lo, world hi)
+        self._normalsPlans = {}                      # RecomputeNormals: MeshObject index -> ((vertex buffer, index buffer, first, last), NormalsPlan, the index list it was made for)
 
     # RM:215-230
     def RegisterObject(self, obj: RayTraceObject):
@@ -95,6 +97,7 @@ class RayTraceMaster:
     # object-level BVHs (RM:405-722 output contract) come from the C++ host library (csrc/host_scene.cpp)
     def RebuildObjectLists(self, literal_leaf_bounds: bool = False, pairing_heap: bool = False):
         s = self.scene
+        self._drop_normals_plans()                                                # the spans and the weld they were made for are gone
         spheres, mesh_objects, verts, idx = [], [], [], []
         nv = ni = 0
         for obj in self._rayTraceObjects:
@@ -655,6 +658,40 @@ class RayTraceMaster:
         leaves["vmin"], leaves["vmax"], leaves["index"] = lo, hi, np.arange(n)
         return host_scene.build_object_bvh(leaves)
 
+    def _drop_normals_plans(self):
+        for hit in self._normalsPlans.values():
+            hit[1].Release()
+        self._normalsPlans = {}
+
+    # RayTraceMaster.ComputeNormals (RM:340-368) on the GPU, for meshes whose positions were written on the device (SkinMeshes, a
+    # ComputeBuffer.SetDataDevice of the vertex buffer): the normals of the vertex spans of the named MeshObjects (default: all) are
+    # recomputed from the vertex buffer's device side into the normal buffer's (include/urt.h urt_compute_normals), and the library
+    # re-gathers the shading normals of the meshes they meet in place.  One plan per span, cached: made from the buffers as they are at
+    # its first use (a synchronising set-up call; it welds against every mesh's index slots); all plans are dropped when the object lists
+    # are rebuilt, and one whose buffers were replaced or whose scene holds another index list since is made anew.  A deformation that merges or splits coincident vertices needs new plans: _drop_normals_plans.
+    # ComputeNormals welds across meshes: a mesh that holds a vertex at the position of a deformed mesh's vertex takes that mesh's faces,
+    # so it is named too.  History is not touched — that is the caller's business, as with ComputeBuffer.SetDataDevice.
+    def RecomputeNormals(self, mesh_indices=None):
+        if self._treesNeedRebuilding and self._rayTraceObjects:
+            self.RebuildObjectLists()
+        ks = list(range(len(self.scene.mesh_objects))) if mesh_indices is None else list(mesh_indices)
+        for k in ks:
+            self._mesh_index_arg(k, "RecomputeNormals", "mesh_indices")
+        if self._treesNeedRebuilding:                                             # the buffers the plans read must exist
+            self._bind_for_queries()
+        for k in ks:
+            lo, hi = self.vertex_span(k)
+            if hi < lo:
+                continue
+            key = (self._vertexBuffer.handle, self._indexBuffer.handle, lo, hi)
+            hit = self._normalsPlans.get(int(k))
+            if hit is None or hit[0] != key or hit[2] is not self.scene.indices:
+                if hit is not None:
+                    hit[1].Release()
+                hit = (key, self.ctx.normals_plan(self._vertexBuffer, self._indexBuffer, lo, hi - lo + 1), self.scene.indices)
+                self._normalsPlans[int(k)] = hit
+            hit[1].compute(self._normalBuffer)
+
     # Skinned meshes move: poses = {MeshObject index: (n_bones, 12) bone matrices} for meshes that have a skin (AttachSkin); a bone is
     # urt_ObjectMotion's a[12] — three columns of the linear part, then the translation — from the mesh's object space to itself.
     # The DeformMeshes protocol without a host copy of the positions: the bones are uploaded (a few KB), every span is skinned on the GPU
@@ -662,7 +699,9 @@ class RayTraceMaster:
     # (urt_buffer_bounds), the object-level heap is rebuilt from the world box of their eight corners and uploaded, and the library refits
     # the skinned meshes in place without the positions ever crossing the bus.  The scene's vertex and normal lists keep what they held.
     # History is treated exactly as DeformMeshes treats it: all-NaN motion entries with temporal accumulation on, ResetAccumulation else.
-    def SkinMeshes(self, poses):
+    # recompute_normals: the bones carry rest normals through their linear part, which is right for rigid bones only; with True the
+    # normals of the skinned spans come from RecomputeNormals of the skinned positions instead, as the reference computes its normals.
+    def SkinMeshes(self, poses, recompute_normals: bool = False):
         s = self.scene
         poses = dict(poses)
         if self._treesNeedRebuilding and self._rayTraceObjects:
@@ -696,7 +735,10 @@ class RayTraceMaster:
             if hi < lo:
                 continue
             self._boneBuffers[k] = self.CreateComputeBuffer(self._boneBuffers.get(k), a, 48)
-            self.ctx.skin_vertices(rest_v, rest_n, idx, wgt, self._boneBuffers[k], lo, hi - lo + 1, self._vertexBuffer, self._normalBuffer)
+            self.ctx.skin_vertices(rest_v, rest_n, idx, wgt, self._boneBuffers[k], lo, hi - lo + 1, self._vertexBuffer,
+                                   None if recompute_normals else self._normalBuffer)
+        if recompute_normals:
+            self.RecomputeNormals(list(checked))
         for k in checked:
             lo, hi = self._skins[k]["span"]
             if hi < lo:
@@ -794,6 +836,7 @@ class RayTraceMaster:
             if b is not None:
                 b.Release()
         self._skinBuffers, self._boneBuffers = None, {}
+        self._drop_normals_plans()
         for t in (self._target, self._converged, self.SkyboxTexture, self._denoised) + (self._aov or ()):
             if t is not None:
                 t.Release()

@@ -136,6 +136,12 @@ class Context:
         self.check(self.lib.urt_debug_buffer_state(self._h, buffer.handle, a))
         return {"stale_first": int(a[0]), "stale_last": int(a[1]), "mirror_bytes": int(a[2]), "downloads": int(a[3])}
 
+    def normals_plan(self, vertices, indices, first: int = 0, count: int | None = None) -> "NormalsPlan":
+        """A NormalsPlan for elements first .. first + count - 1 (default: to the end) of the stride-12 ComputeBuffer `vertices`, welded
+        against every index slot of the stride-4 ComputeBuffer `indices` as both are NOW (include/urt.h urt_normals_plan_create; a
+        synchronising set-up call)."""
+        return NormalsPlan(self, vertices, indices, first, count)
+
     def serve_stats(self) -> dict:
         """kernel_mode 5 with count_stats: the shared traversal service since the last reset_counters()."""
         a = (C.c_ulonglong * 6)()
@@ -891,6 +897,45 @@ class ComputeBuffer:
     def Release(self):
         if self.handle:
             self.ctx.check(self.ctx.lib.urt_buffer_release(self.ctx._h, self.handle))
+            self.handle = 0
+
+
+class NormalsPlan:
+    """RayTraceMaster.ComputeNormals on the GPU for one vertex span (include/urt.h, "normals on the device"): made once per topology from
+    the buffers' contents at that time, then .compute(dst_normals) recomputes the span's normals from the CURRENT device-side positions
+    into the device side of dst_normals — two kernels on the context's stream, nothing waited for, nothing downloaded.  The result is
+    urt_host_compute_normals of the current positions whenever they weld as the plan-time positions did."""
+
+    def __init__(self, ctx: Context, vertices: "ComputeBuffer", indices: "ComputeBuffer", first: int = 0, count: int | None = None):
+        for name, b in (("vertices", vertices), ("indices", indices)):
+            if not isinstance(b, ComputeBuffer):
+                raise TypeError(f"normals_plan: {name} must be a ComputeBuffer, not {type(b).__name__}")
+            if b.ctx is not ctx:
+                raise ValueError(f"normals_plan: {name} belongs to another context")
+        for name, v in (("first", first), ("count", 0 if count is None else count)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"normals_plan: {name} must be an int, not {type(v).__name__}")
+        count = vertices.count - int(first) if count is None else count
+        self.ctx, self.handle = ctx, 0
+        h = C.c_uint64()
+        ctx.check(ctx.lib.urt_normals_plan_create(ctx._h, vertices.handle, indices.handle, int(first), int(count), C.byref(h)))
+        self.handle = h.value
+
+    @property
+    def info(self) -> dict:
+        """first, count, n_lists, n_triangles, n_entries, max_valence, device_bytes (include/urt.h urt_NormalsPlanInfo)."""
+        a = _lib.NormalsPlanInfo()
+        self.ctx.check(self.ctx.lib.urt_normals_plan_info(self.ctx._h, self.handle, C.byref(a)))
+        return {n: int(getattr(a, n)) for n, _ in _lib.NormalsPlanInfo._fields_}
+
+    def compute(self, dst_normals: "ComputeBuffer"):
+        if not isinstance(dst_normals, ComputeBuffer):
+            raise TypeError(f"NormalsPlan.compute: dst_normals must be a ComputeBuffer, not {type(dst_normals).__name__}")
+        self.ctx.check(self.ctx.lib.urt_compute_normals(self.ctx._h, self.handle, dst_normals.handle))
+
+    def Release(self):
+        if self.handle:
+            self.ctx.check(self.ctx.lib.urt_normals_plan_release(self.ctx._h, self.handle))
             self.handle = 0
 
 
