@@ -54,9 +54,9 @@ URT_API int urt_abi_version(void);                       /* bumps when this head
                                                             the feature buffers, the denoiser, the temporal reprojection, the
                                                             resampling, the ranged SetData and the device side of the buffers —
                                                             urt_buffer_set_data_device, urt_buffer_get_data_range,
-                                                            urt_skin_vertices, urt_buffer_bounds, urt_debug_buffer_state — and
-                                                            the normals on the device were added without changing anything
-                                                            that existed) */
+                                                            urt_skin_vertices, urt_buffer_bounds, urt_debug_buffer_state — the
+                                                            normals on the device, urt_buffer_copy and urt_reproject_deformed
+                                                            were added without changing anything that existed) */
 URT_API int urt_device_count(int* out_count);
 /* One context per process and GPU (the one-process-per-GPU model).  device = HIP ordinal. */
 URT_API int urt_context_create(int device, urt_context** out_ctx);
@@ -120,6 +120,15 @@ URT_API int urt_buffer_set_data_device(urt_context* ctx, urt_handle buffer, int 
 /* ComputeBuffer.GetData: the buffer's current contents, elements first .. first+count-1, into host memory; downloads stale elements
  * (synchronises).  Elements that were never set read as zero bytes.  Errors as urt_buffer_set_data_range. */
 URT_API int urt_buffer_get_data_range(urt_context* ctx, urt_handle buffer, int first, void* out, int count);
+/* A snapshot that stays on the device: elements src_first .. src_first+count-1 of src's mirror are copied to elements dst_first ..
+ * dst_first+count-1 of dst's mirror (both buffers get mirrors, as with every first device-side use).  The copy is enqueued on the
+ * context's stream; nothing is synchronised and nothing is downloaded.  The destination range becomes stale and dirty as a whole,
+ * exactly as with urt_buffer_set_data_device.  A source whose host copy is the current one is read from its mirror, which is current by
+ * the rule above; a source written on the device is read where it was written.  (urt_reproject_deformed reads the previous vertex
+ * positions of a deforming mesh from such a snapshot of _Vertices.)
+ * Checked first, nothing enqueued: a handle that is 0 or unknown URT_ERR_INVALID_HANDLE; strides that differ, a negative first or count,
+ * a range outside either buffer, src == dst URT_ERR_INVALID_ARGUMENT.  count == 0 returns URT_OK after the checks. */
+URT_API int urt_buffer_copy(urt_context* ctx, urt_handle src, int src_first, urt_handle dst, int dst_first, int count);
 
 /* Linear blend skinning on the GPU.  rest_vertices (stride 12), rest_normals (stride 12; 0 is allowed exactly when dst_normals == 0),
  * bone_indices (stride 16: int32[4] per vertex), bone_weights (stride 16: float[4] per vertex), bones (stride 48: urt_ObjectMotion's
@@ -530,6 +539,57 @@ typedef struct urt_ReprojectMotion {     /* 24 bytes */
 
 URT_API int urt_reproject_objects(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params,
                                   const urt_ReprojectMotion* motion);
+
+/* Per-vertex motion: urt_reproject_objects for a scene in which MeshObjects have also changed SHAPE between the previous and the current
+ * feature buffers (a deformation: skinning, cloth, blend shapes; csrc/refit.hip refits such a mesh in place).  The topology is the same
+ * then and now (the contract of option "refit_vertices"), and the id feature buffer names, per pixel, the MeshObject, the triangle's
+ * first index slot and the barycentrics of the hit, so the point a pixel shows now is found at the position it HAD by interpolating the
+ * previous vertex positions of the same triangle.  prev_vertices is usually a snapshot of _Vertices taken with urt_buffer_copy before
+ * the deformation; prev_mesh_objects is _MeshObjects as it was then, so an object that deforms and moves in one step needs no entry in
+ * mesh_motion.
+ *
+ * Arithmetic (normative), as urt_reproject_objects'; only what differs:
+ *  - deformed pixel: a surface pixel is DEFORMED when k == 3 (triangle), deform is given, o = bits(id.x) lies in 0 .. n-1 with n the
+ *    common count of deformed and prev_mesh_objects, and deformed[o] != 0.  With deform given, a triangle pixel whose o lies outside
+ *    0 .. n-1 has no history (colour, count and motion are 0).  A deformed pixel does not read its mesh_motion entry.  Every pixel that
+ *    is not deformed follows urt_reproject_objects operation for operation.
+ *  - triangle: i = bits(id.y), u = id.z, v = id.w.  No history unless 0 <= i <= n_indices - 3 and each j_r = indices[i + r], r = 0, 1, 2,
+ *    lies in 0 .. n_prev_vertices - 1 (the counts are the buffers').  An index out of range is never a fault and never an error.
+ *  - previous position: with A_r = prev_vertices[j_r] and m = the 16 floats of prev_mesh_objects[o] (localToWorldMatrix, column-major):
+ *      V_r.c = ((m[c]*A_r.x + m[4+c]*A_r.y) + m[8+c]*A_r.z) + m[12+c], c = 0..2;  w = (1.0f - u) - v;
+ *      P'.c = (V_0.c*w + V_1.c*u) + V_2.c*v.
+ *  - previous face normal: e1 = V_1 - V_0, e2 = V_2 - V_0 (per component),
+ *      g = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x), L = f_sqrt((g.x*g.x + g.y*g.y) + g.z*g.z).
+ *    No history unless P' is finite, L > 0 and L is finite (a NaN barycentric, a previous triangle without area).
+ *  - from here on the pixel is a MOVED pixel of urt_reproject_objects with P' and n' = g: step 2 projects P'; the tap tests on kind,
+ *    object id, prev_hit.w, count and colour are the same; the plane test is
+ *      fabsf((g.x*(Q.x-P'.x) + g.y*(Q.y-P'.y)) + g.z*(Q.z-P'.z)) <= (plane_threshold * z) * L,
+ *    the normal test is (g.x*m.x + g.y*m.y) + g.z*m.z >= deform->normal_threshold * L (m = prev_normal[q].xyz); moved_max_history clamps
+ *    the count as on a moved pixel; the motion image is unchanged in form and holds the true screen-space motion of the deforming surface.
+ *    The normal test has a threshold of its own because g is a FACE normal while the tap's m is an interpolated shading normal: on a
+ *    coarse mesh the two differ by a few tens of degrees, and params->normal_threshold (0.9) would refuse sound taps.
+ * With deform == NULL, or with every element of deformed zero (and every triangle pixel's o inside 0 .. n-1), the three outputs equal
+ * urt_reproject_objects' bit for bit.  Calls and errors as urt_reproject_objects (an observer: deferred frames submitted first, one
+ * kernel enqueued on the context's stream, no synchronisation; the scene is not prepared, urt_counters are not changed; every argument is
+ * checked first and on any error nothing is written or enqueued).  The four buffers are read through their device mirrors (the
+ * section "the device side of a ComputeBuffer"): no download is made, and urt_debug_buffer_state shows none.
+ * URT_ERR_INVALID_HANDLE: a handle of a given deform that is 0 or unknown.  URT_ERR_INVALID_ARGUMENT: a stride other than 12 / 4 / 112 /
+ * 4; an indices count that is not a multiple of 3; counts of deformed and prev_mesh_objects that differ; nonzero flags; a NaN threshold.
+ * The default below was chosen with the quality test of tests/test_gpu_reproject_deform.py (DESIGN.md "Per-vertex motion").
+ * What remains untracked: shadows and reflections cast by a deforming mesh onto other surfaces, as for moved objects; the shading
+ * normals of the previous frame are not consulted. */
+typedef struct urt_ReprojectDeform {     /* 40 bytes */
+  urt_handle prev_vertices;      /* stride 12: object-space positions as _Vertices held them when the history was accumulated */
+  urt_handle indices;            /* stride 4: the buffer bound as _Indices (same topology then and now) */
+  urt_handle prev_mesh_objects;  /* stride 112: _MeshObjects as it was then; only localToWorldMatrix (@0, 16 floats) is read */
+  urt_handle deformed;           /* stride 4: one int32 per MeshObject, nonzero = its triangle pixels take the per-vertex path */
+  float normal_threshold;        /* per-vertex path only: a history tap needs dot(g, n_q) >= this * |g|; NaN is an error */
+  int32_t flags;                 /* 0 (reserved) */
+} urt_ReprojectDeform;
+#define URT_REPROJECT_DEFAULT_DEFORM_NORMAL_THRESHOLD 0.3f
+
+URT_API int urt_reproject_deformed(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params,
+                                   const urt_ReprojectMotion* motion /* may be NULL */, const urt_ReprojectDeform* deform /* may be NULL */);
 
 /* ---- resampling --------------------------------------------------------------------------- */
 /* The step after urt_reproject, kept on the GPU: find the pixels whose history is short (urt_select_pixels), trace fresh samples for them

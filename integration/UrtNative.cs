@@ -161,6 +161,16 @@ internal static class UrtNative {
     }
     internal const int ObjectMotionStride = 48;
     [DllImport(Lib)] internal static extern int urt_reproject_objects(IntPtr ctx, in ReprojectImages images, in ReprojectParams p, in ReprojectMotion motion);
+    // per-vertex motion (include/urt.h urt_reproject_deformed): the previous positions of meshes that changed shape, kept on the device
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct ReprojectDeform {                       // urt_ReprojectDeform, 40 B
+        public ulong prevVertices, indices, prevMeshObjects, deformed;   // buffer handles: strides 12, 4, 112, 4
+        public float normalThreshold;                       // of the per-vertex path; not NaN
+        public int flags;                                   // 0
+    }
+    internal const float ReprojectDefaultDeformNormalThreshold = 0.3f;
+    [DllImport(Lib)] internal static extern int urt_reproject_deformed(IntPtr ctx, in ReprojectImages images, in ReprojectParams p, in ReprojectMotion motion, in ReprojectDeform deform);
+    [DllImport(Lib)] internal static extern int urt_buffer_copy(IntPtr ctx, ulong src, int srcFirst, ulong dst, int dstFirst, int count);
 
     // ---- measurement ----------------------------------------------------------------------------------------------------
     [StructLayout(LayoutKind.Sequential)]

@@ -272,6 +272,76 @@ public static class UrtTemporal {
                                                 planeThreshold = planeThreshold, flags = 0 };
         UrtDevice.Check(UrtNative.urt_reproject_objects(ctx, in im, in p, in mo));
     }
+    // ---- meshes that change shape and keep their history (include/urt.h urt_reproject_deformed) ----
+    static ulong prevVertices, prevObjects, deformedFlags;
+    static int prevVerticesCount, prevObjectsCount;
+    static IntPtr deformCtx = IntPtr.Zero;
+    /// DeformMeshes with keepHistory: RayTraceMaster.DeformMeshes(..., keep_history=True) of the Python mirror.  vertices, indices and
+    /// meshObjects are the handles of the buffers bound as _Vertices, _Indices and _MeshObjects (nVertices and nMeshObjects their counts).
+    /// Before applyEdits() the vertex buffer is copied on the device into a previous-positions buffer (urt_buffer_copy: no download) and
+    /// _MeshObjects into its twin; the motion table then holds the identity for every MeshObject and the deformed ones are flagged, so
+    /// their pixels look up where the points of their triangle were (per-vertex motion) and keep their history.  keepHistory false: the
+    /// overload above, to the bit.
+    public static void DeformMeshes(int nMeshObjects, IEnumerable<int> deformed, Action applyEdits, Action<IntPtr, IntPtr, IntPtr> renderFeatureBuffers,
+                                    IntPtr prevColor, IntPtr prevCount, IntPtr prevHit, IntPtr prevNormal, IntPtr prevId,
+                                    IntPtr hit, IntPtr normal, IntPtr id, IntPtr color, IntPtr count, IntPtr motion, int width, int height,
+                                    Matrix4x4 prevViewProj, bool keepHistory, ulong vertices, int nVertices, ulong indices, ulong meshObjects,
+                                    float maxHistory = 64.0f, float normalThreshold = 0.9f, float planeThreshold = 0.02f,
+                                    float deformNormalThreshold = UrtNative.ReprojectDefaultDeformNormalThreshold) {
+        if (!keepHistory) {
+            DeformMeshes(nMeshObjects, deformed, applyEdits, renderFeatureBuffers, prevColor, prevCount, prevHit, prevNormal, prevId, hit, normal, id,
+                         color, count, motion, width, height, prevViewProj, maxHistory, normalThreshold, planeThreshold);
+            return;
+        }
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtTemporal: reproject on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        var table = new float[12 * nMeshObjects];
+        var flags = new int[nMeshObjects];
+        for (int k = 0; k < nMeshObjects; k++) table[12 * k] = table[12 * k + 4] = table[12 * k + 8] = 1.0f;      // the exact identity: not moved
+        foreach (int k in deformed) {
+            if (k < 0 || k >= nMeshObjects) throw new ArgumentOutOfRangeException(nameof(deformed), "UrtTemporal.DeformMeshes: no such MeshObject");
+            flags[k] = 1;
+        }
+        if (deformCtx != ctx || prevVerticesCount != nVertices || prevObjectsCount != nMeshObjects) {
+            if (deformCtx == ctx)
+                foreach (ulong h in new[] { prevVertices, prevObjects, deformedFlags })
+                    if (h != 0) UrtDevice.Check(UrtNative.urt_buffer_release(ctx, h));
+            UrtDevice.Check(UrtNative.urt_buffer_create(ctx, nVertices, 12, out prevVertices));
+            UrtDevice.Check(UrtNative.urt_buffer_create(ctx, nMeshObjects, 112, out prevObjects));
+            UrtDevice.Check(UrtNative.urt_buffer_create(ctx, nMeshObjects, 4, out deformedFlags));
+            prevVerticesCount = nVertices; prevObjectsCount = nMeshObjects; deformCtx = ctx;
+        }
+        renderFeatureBuffers(prevHit, prevNormal, prevId);
+        UrtDevice.Check(UrtNative.urt_buffer_copy(ctx, vertices, 0, prevVertices, 0, nVertices));         // the scene as the history saw it
+        UrtDevice.Check(UrtNative.urt_buffer_copy(ctx, meshObjects, 0, prevObjects, 0, nMeshObjects));
+        applyEdits();
+        renderFeatureBuffers(hit, normal, id);
+        if (meshTable != 0 && (tableCtx != ctx || meshTableCount != nMeshObjects)) {
+            if (tableCtx == ctx) UrtDevice.Check(UrtNative.urt_buffer_release(ctx, meshTable));
+            meshTable = 0;
+        }
+        GCHandle o = GCHandle.Alloc(table, GCHandleType.Pinned), f = GCHandle.Alloc(flags, GCHandleType.Pinned);
+        try {
+            if (meshTable == 0) UrtDevice.Check(UrtNative.urt_buffer_create(ctx, nMeshObjects, UrtNative.ObjectMotionStride, out meshTable));
+            meshTableCount = nMeshObjects;
+            UrtDevice.Check(UrtNative.urt_buffer_set_data(ctx, meshTable, o.AddrOfPinnedObject(), nMeshObjects));
+            UrtDevice.Check(UrtNative.urt_buffer_set_data(ctx, deformedFlags, f.AddrOfPinnedObject(), nMeshObjects));
+        } finally { o.Free(); f.Free(); }
+        tableCtx = ctx;
+        var mo = new UrtNative.ReprojectMotion { meshMotion = meshTable, sphereMotion = 0, movedMaxHistory = 0.0f, flags = 0 };
+        var de = new UrtNative.ReprojectDeform { prevVertices = prevVertices, indices = indices, prevMeshObjects = prevObjects, deformed = deformedFlags,
+                                                 normalThreshold = deformNormalThreshold, flags = 0 };
+        var m = new float[16];
+        for (int k = 0; k < 16; k++) m[k] = prevViewProj[k];
+        var im = new UrtNative.ReprojectImages {
+            prevColor = Wrap(ctx, prevColor, width, height), prevCount = Wrap(ctx, prevCount, width, height),
+            prevHit = Wrap(ctx, prevHit, width, height), prevNormal = Wrap(ctx, prevNormal, width, height), prevId = Wrap(ctx, prevId, width, height),
+            hit = Wrap(ctx, hit, width, height), normal = Wrap(ctx, normal, width, height), id = Wrap(ctx, id, width, height),
+            color = Wrap(ctx, color, width, height), count = Wrap(ctx, count, width, height), motion = Wrap(ctx, motion, width, height) };
+        var p = new UrtNative.ReprojectParams { prevWorldToClip = m, maxHistory = maxHistory, normalThreshold = normalThreshold,
+                                                planeThreshold = planeThreshold, flags = 0 };
+        UrtDevice.Check(UrtNative.urt_reproject_deformed(ctx, in im, in p, in mo, in de));
+    }
     public static void BlitAddHistory(IntPtr src, IntPtr dst, IntPtr count, int width, int height, float maxHistory = 64.0f) {
         if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtTemporal: blend on one rank's context (urt_group_context)");
         IntPtr ctx = UrtDevice.Handle;

@@ -13,11 +13,17 @@ repeat, so that the three are compared under the same conditions:
   objects_static   urt_reproject_objects with tables that hold only identity entries (a static scene that still passes its tables);
   objects_moved    the same with every wall ("mesh") entry a small rigid motion: every mesh pixel loads its entry and takes the moved path
                    (`moved_share` is the share of such pixels in the image).
+With --deform (urt_reproject_deformed, per-vertex motion) the two walls of the analytic scene become meshes: each is cut into a grid of
+triangles of about six pixels at 1080p, every wall pixel's id texel names its triangle's index slot and barycentrics, and the previous
+positions are the grid's vertices moved a little in the wall's plane.  `reproject`, `objects_moved` (as with --motion) and these alternate:
+  deformed_static  urt_reproject_deformed with every flag zero (a scene that passes its buffers while nothing deforms);
+  deformed_walls   both walls flagged: every mesh pixel gathers three indices, three vertices and its object's matrix
+                   (`moved_share` is the share of such pixels in the image; --camera-z -1 brings it from 1.4 % to 11 %).
 Bytes per pixel are the compulsory traffic (reproject: 48 B of current AOVs, 80 B of previous history and AOVs, 48 B out; blend: 64 B;
 fused n frames with a present: 16 n + 64 B) and `of_6p3TBs` the fraction of the ~6.3 TB/s a float4 copy reaches on the chip.  Kernel times
 come from a separate `rocprofv3 --kernel-trace --stats` run of this script.
 
-    python scripts/reproject_bench.py [--sizes 1080p,2160p] [--iters 20] [--repeats 5] [--motion] [--json out.json]
+    python scripts/reproject_bench.py [--sizes 1080p,2160p] [--iters 20] [--repeats 5] [--motion | --deform] [--json out.json]
 """
 import argparse
 import json
@@ -61,6 +67,38 @@ def report(name, case, w, h, ms, bpp, results):
     results.append(r)
 
 
+WALLS = {4: (6.0, (-4.0, 4.0), (0.0, 3.0), (128, 48)), 5: (2.0, (2.5, 4.5), (0.0, 1.6), (48, 40))}   # tests/reproject_ref.py default_objects; grid cells
+
+
+def wall_meshes(hit, normal, ids, rng):
+    """The two walls as triangle grids: (prev_vertices, indices) and, written into `ids`, every wall pixel's index slot and barycentrics.
+    Cell (i, j) holds the triangles (c00, c01, c10) and (c11, c10, c01), wound so that their face normals look along -z as the walls do."""
+    verts, index, first_slot = [], [], 0
+    iv = ids.view(np.int32)
+    for o, (zc, (x0, x1), (y0, y1), (gx, gy)) in WALLS.items():
+        base = sum(len(v) for v in verts)
+        X, Y = np.meshgrid(np.linspace(x0, x1, gx + 1), np.linspace(y0, y1, gy + 1))
+        verts.append(np.stack([X, Y, np.full_like(X, zc)], -1).reshape(-1, 3))
+        vid = lambda i, j: base + j * (gx + 1) + i  # noqa: E731
+        I, J = np.meshgrid(np.arange(gx), np.arange(gy))
+        tris = np.stack([np.stack([vid(I, J), vid(I, J + 1), vid(I + 1, J)], -1), np.stack([vid(I + 1, J + 1), vid(I + 1, J), vid(I, J + 1)], -1)], 2)
+        index.append(tris.reshape(-1, 3))
+        on = (normal[..., 3] == 3) & (iv[..., 0] == o)
+        fx = np.clip((hit[..., 0].astype(np.float64) - x0) / (x1 - x0) * gx, 0, gx - 1e-9)
+        fy = np.clip((hit[..., 1].astype(np.float64) - y0) / (y1 - y0) * gy, 0, gy - 1e-9)
+        i, j = np.floor(fx).astype(np.int64), np.floor(fy).astype(np.int64)
+        a, b = fx - i, fy - j
+        upper = a + b > 1
+        slot = first_slot + 3 * (2 * (j * gx + i) + upper)
+        iv[..., 1] = np.where(on, slot, iv[..., 1])
+        ids[..., 2] = np.where(on, np.where(upper, 1 - b, b), ids[..., 2]).astype(np.float32)
+        ids[..., 3] = np.where(on, np.where(upper, 1 - a, a), ids[..., 3]).astype(np.float32)
+        first_slot += 3 * 2 * gx * gy
+    pv = np.concatenate(verts)
+    pv[:, :2] += rng.uniform(-0.02, 0.02, (len(pv), 2))                       # where the vertices were: a little off, in the plane
+    return pv.astype(np.float32), np.concatenate(index).astype(np.int32).reshape(-1)
+
+
 def main():
     from reproject_ref import analytic_aovs
     ap = argparse.ArgumentParser()
@@ -69,6 +107,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--motion", action="store_true", help="time urt_reproject_objects (static and all-moved tables) next to urt_reproject")
+    ap.add_argument("--deform", action="store_true", help="time urt_reproject_deformed (no mesh flagged, both walls flagged) next to urt_reproject and urt_reproject_objects")
+    ap.add_argument("--camera-z", type=float, default=-10.0, help="z of both cameras (the walls stand at z = 2 and z = 6: nearer cameras see more mesh pixels)")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -80,9 +120,12 @@ def main():
     rng = np.random.default_rng(1)
     for name in args.sizes.split(","):
         w, h = SIZES[name]
-        cam_a = scenes.camera_matrices(w, h)
-        cam_b = scenes.camera_matrices(w, h, position=(0.1, 1.0, -10.0), yaw_deg=1.0)
+        cam_a = scenes.camera_matrices(w, h, position=(0.0, 1.0, args.camera_z))
+        cam_b = scenes.camera_matrices(w, h, position=(0.1, 1.0, args.camera_z), yaw_deg=1.0)
         prev, cur = analytic_aovs(w, h, *cam_a), analytic_aovs(w, h, *cam_b)
+        if args.deform:
+            cur = [a.copy() for a in cur]
+            prev_vertices, wall_indices = wall_meshes(*cur, rng)
         color = rng.uniform(0, 1, (h, w, 4)).astype(np.float32)
         count = np.zeros((h, w, 4), np.float32)
         count[..., 0] = 16.0
@@ -93,7 +136,7 @@ def main():
         sh.SetMatrix("_CameraToWorld", cam_b[0])
         sh.SetMatrix("_CameraInverseProjection", cam_b[1])
         M = scenes.world_to_clip(*cam_a)
-        if args.motion:
+        if args.motion or args.deform:
             n = 6                                               # the analytic scene's ids: ground 0, spheres 1..3, walls ("meshes") 4 and 5
             ident = np.tile(np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], np.float32), (n, 1))
             moved = ident.copy()
@@ -108,13 +151,30 @@ def main():
             cases = {"reproject": lambda: ctx.reproject(*tex[:10], M, motion=tex[10]),
                      "objects_static": lambda: ctx.reproject(*tex[:10], M, motion=tex[10], mesh_motion=bufs["ident"], sphere_motion=bufs["ident"]),
                      "objects_moved": lambda: ctx.reproject(*tex[:10], M, motion=tex[10], mesh_motion=bufs["moved"], sphere_motion=bufs["ident"])}
+            if args.deform:
+                objects = np.zeros((n, 28), np.float32)
+                objects[:, [0, 5, 10, 15]] = 1.0                   # identity matrices: the walls' vertices are world positions
+                flagged = np.zeros(n, np.int32)
+                flagged[list(WALLS)] = 1
+                for key, a, stride in (("pv", prev_vertices, 12), ("ix", wall_indices, 4), ("mo", objects, 112), ("none", np.zeros(n, np.int32), 4),
+                                       ("walls", flagged, 4)):
+                    bufs[key] = ComputeBuffer(ctx, a.nbytes // stride, stride)
+                    bufs[key].SetData(a)
+                del cases["objects_static"]
+                for c, flags in (("deformed_static", "none"), ("deformed_walls", "walls")):
+                    cases[c] = lambda flags=flags: ctx.reproject(*tex[:10], M, motion=tex[10], mesh_motion=bufs["ident"], sphere_motion=bufs["ident"],
+                                                                 deform=(bufs["pv"], bufs["ix"], bufs["mo"], bufs[flags]))
             ms = {c: [] for c in cases}
-            for _ in range(args.repeats):                       # alternate the three within every repeat
+            for _ in range(args.repeats):                       # alternate the cases within every repeat
                 for c, fn in cases.items():
                     ms[c].append(timed(fn, args.iters, args.warmup))
             for c in cases:
                 report(name, c, w, h, ms[c], 176, results)
-                results[-1]["moved_share"] = share if c == "objects_moved" else 0.0
+                results[-1]["moved_share"] = share if c in ("objects_moved", "deformed_walls") else 0.0
+            if args.deform:                                     # what the flagged walls keep: the cases must not time dead pixels
+                ctx.reproject(*tex[:10], M, motion=tex[10], deform=(bufs["pv"], bufs["ix"], bufs["mo"], bufs["walls"]))
+                kept = tex[9].GetPixels()[..., 0][cur[1][..., 3] == 3] > 0
+                print(json.dumps({"size": name, "case": "deformed_walls_kept_share", "value": float(kept.mean()), "moved_share": share}), flush=True)
             for t in tex + list(bufs.values()):
                 t.Release()
             continue

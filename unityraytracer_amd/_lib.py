@@ -17,11 +17,11 @@ ERROR_NAMES = {1: "INVALID_ARGUMENT", 2: "INVALID_HANDLE", 3: "NO_DEVICE", 4: "H
 # every symbol include/urt.h declares (tests check that the .so exports each of them)
 ABI_SYMBOLS = [
     "urt_abi_version", "urt_device_count", "urt_context_create", "urt_context_destroy", "urt_last_error", "urt_context_set_stream",
-    "urt_synchronize", "urt_flush", "urt_buffer_create", "urt_buffer_set_data", "urt_buffer_set_data_range", "urt_buffer_set_data_device", "urt_buffer_get_data_range", "urt_skin_vertices", "urt_buffer_bounds", "urt_normals_plan_create", "urt_normals_plan_info", "urt_normals_plan_release", "urt_compute_normals", "urt_buffer_get_info", "urt_buffer_release", "urt_texture_create",
+    "urt_synchronize", "urt_flush", "urt_buffer_create", "urt_buffer_set_data", "urt_buffer_set_data_range", "urt_buffer_set_data_device", "urt_buffer_get_data_range", "urt_buffer_copy", "urt_skin_vertices", "urt_buffer_bounds", "urt_normals_plan_create", "urt_normals_plan_info", "urt_normals_plan_release", "urt_compute_normals", "urt_buffer_get_info", "urt_buffer_release", "urt_texture_create",
     "urt_texture_create_external", "urt_texture_set_pixels", "urt_texture_get_pixels", "urt_texture_get_info", "urt_texture_read_begin", "urt_texture_read_end", "urt_texture_read_begin_format", "urt_texture_read_end_format", "urt_texture_release",
     "urt_shader_set_buffer", "urt_shader_set_texture", "urt_shader_set_matrix", "urt_shader_set_vector", "urt_shader_set_float",
     "urt_shader_set_int", "urt_shader_dispatch", "urt_shader_dispatch_rows", "urt_blit_add", "urt_blit", "urt_texture_pack_rows",
-    "urt_texture_unpack_rows", "urt_texture_unpack_rows_on", "urt_texture_pack_rows_rgb", "urt_texture_unpack_rows_rgb", "urt_ray_query", "urt_ray_query_device", "urt_radiance_query", "urt_radiance_query_device", "urt_render_aov", "urt_denoise", "urt_reproject", "urt_reproject_objects", "urt_blit_add_history", "urt_select_pixels", "urt_blend_samples", "urt_resample_below", "urt_set_option", "urt_get_counters", "urt_reset_counters", "urt_debug_build_blas", "urt_debug_get_blas", "urt_debug_blas_cache_stats",
+    "urt_texture_unpack_rows", "urt_texture_unpack_rows_on", "urt_texture_pack_rows_rgb", "urt_texture_unpack_rows_rgb", "urt_ray_query", "urt_ray_query_device", "urt_radiance_query", "urt_radiance_query_device", "urt_render_aov", "urt_denoise", "urt_reproject", "urt_reproject_objects", "urt_reproject_deformed", "urt_blit_add_history", "urt_select_pixels", "urt_blend_samples", "urt_resample_below", "urt_set_option", "urt_get_counters", "urt_reset_counters", "urt_debug_build_blas", "urt_debug_get_blas", "urt_debug_blas_cache_stats",
     "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_read_scene_cones", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_deform_stats", "urt_debug_scene_cost", "urt_debug_buffer_state", "urt_debug_live_resources", "urt_debug_build_walk_table", "urt_debug_build_normals_plan", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
     "urt_host_build_object_bvh", "urt_host_build_object_bvh_pairing", "urt_host_mesh_motion", "urt_host_sphere_motion", "urt_host_last_error", "urt_host_load_hdr", "urt_host_write_pfm", "urt_host_write_png", "urt_host_encode_srgb8", "urt_host_srgb8_first_floats",
     "urt_host_resize_rgba", "urt_host_io_last_error", "urt_host_log", "urt_host_log_scene_counts", "urt_host_log_tree_report", "urt_host_dump_bvh", "urt_host_dump_normals",
@@ -107,6 +107,12 @@ class ReprojectMotion(C.Structure):
     _fields_ = [("mesh_motion", C.c_uint64), ("sphere_motion", C.c_uint64), ("moved_max_history", C.c_float), ("flags", C.c_int32)]
 
 
+class ReprojectDeform(C.Structure):
+    """urt_ReprojectDeform (include/urt.h), 40 B: the four buffer handles of urt_reproject_deformed and the per-vertex path's normal threshold."""
+    _fields_ = [("prev_vertices", C.c_uint64), ("indices", C.c_uint64), ("prev_mesh_objects", C.c_uint64), ("deformed", C.c_uint64),
+                ("normal_threshold", C.c_float), ("flags", C.c_int32)]
+
+
 class SkinBuffers(C.Structure):
     """urt_SkinBuffers (include/urt.h), 40 B: the five input buffer handles of urt_skin_vertices (rest_normals 0 = positions only)."""
     _fields_ = [(n, C.c_uint64) for n in ("rest_vertices", "rest_normals", "bone_indices", "bone_weights", "bones")]
@@ -119,6 +125,8 @@ class NormalsPlanInfo(C.Structure):
 
 # the starting values a host passes to urt_reproject / urt_blit_add_history (include/urt.h URT_REPROJECT_DEFAULT_*)
 REPROJECT_DEFAULTS = {"max_history": 64.0, "normal_threshold": 0.9, "plane_threshold": 0.02}
+# normal_threshold of urt_ReprojectDeform (include/urt.h URT_REPROJECT_DEFAULT_DEFORM_NORMAL_THRESHOLD)
+REPROJECT_DEFORM_NORMAL_THRESHOLD = 0.3
 
 
 class LaunchInfo(C.Structure):
@@ -174,6 +182,7 @@ def load():
         "urt_buffer_set_data_range": ([vp, u64, i, vp, i], i),
         "urt_buffer_set_data_device": ([vp, u64, i, vp, i], i),
         "urt_buffer_get_data_range": ([vp, u64, i, vp, i], i),
+        "urt_buffer_copy": ([vp, u64, i, u64, i, i], i),
         "urt_skin_vertices": ([vp, C.POINTER(SkinBuffers), i, i, u64, u64], i),
         "urt_buffer_bounds": ([vp, u64, i, i, vp, pi], i),
         "urt_debug_buffer_state": ([vp, u64, vp], i),
@@ -217,6 +226,8 @@ def load():
         "urt_denoise": ([vp, u64, u64, u64, u64, u64, C.POINTER(DenoiseParams)], i),
         "urt_reproject": ([vp, C.POINTER(ReprojectImages), C.POINTER(ReprojectParams)], i),
         "urt_reproject_objects": ([vp, C.POINTER(ReprojectImages), C.POINTER(ReprojectParams), C.POINTER(ReprojectMotion)], i),
+        "urt_reproject_deformed": ([vp, C.POINTER(ReprojectImages), C.POINTER(ReprojectParams), C.POINTER(ReprojectMotion),
+                                    C.POINTER(ReprojectDeform)], i),
         "urt_blit_add_history": ([vp, u64, u64, u64, f], i),
         "urt_select_pixels": ([vp, u64, f, vp, i, pi], i),
         "urt_blend_samples": ([vp, vp, vp, i, f, u64, u64, f], i),

@@ -76,6 +76,17 @@ int sync_bound_hosts(urt_context* ctx, unsigned int slots) {
   return URT_OK;
 }
 
+// The mirror, made and filled from `host` at the first need: a synchronous copy, before anything on the stream can use the new memory.
+int buffer_mirror(urt_context* ctx, Buffer& b) {
+  if (b.mirror) return URT_OK;
+  const size_t bytes = (size_t)b.count * (size_t)b.stride;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  URT_HIP(ctx, b.mirror.alloc(bytes));
+  hipError_t e = hipMemcpy(b.mirror.get(), b.host.data(), bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { b.mirror.reset(); return fail(ctx, URT_ERR_HIP, std::string("buffer mirror upload: ") + hipGetErrorString(e)); }
+  return URT_OK;
+}
+
 // strips first_row, first_row + row_stride, ... of 8-row groups that lie in the first group_rows
 int strip_count(int group_rows, int first_row, int row_stride) {
   return first_row < group_rows ? (group_rows - first_row + row_stride - 1) / row_stride : 0;
@@ -204,18 +215,7 @@ static bool differing_bytes(const uint8_t* a, const uint8_t* b, size_t n, size_t
   return true;
 }
 
-// ---- device mirrors (context_impl.h Buffer::mirror) ----------------------------------------------------------------------------------
-// The mirror, made and filled from `host` at the first need: a synchronous copy, before anything on the stream can use the new memory.
-static int buffer_mirror(urt_context* ctx, Buffer& b) {
-  if (b.mirror) return URT_OK;
-  const size_t bytes = (size_t)b.count * (size_t)b.stride;
-  URT_HIP(ctx, hipSetDevice(ctx->device));
-  URT_HIP(ctx, b.mirror.alloc(bytes));
-  hipError_t e = hipMemcpy(b.mirror.get(), b.host.data(), bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { b.mirror.reset(); return fail(ctx, URT_ERR_HIP, std::string("buffer mirror upload: ") + hipGetErrorString(e)); }
-  return URT_OK;
-}
-
+// ---- device mirrors (context_impl.h Buffer::mirror; buffer_mirror above) ---------------------------------------------------------------
 // Host elements first .. last -> mirror, on the stream, through a pinned image: the caller may change `host` as soon as this returns, and
 // nothing but the slot's own previous copy is waited for.
 static int push_elements(urt_context* ctx, Buffer& b, int first, int last) {
@@ -322,6 +322,27 @@ int urt_buffer_set_data_device(urt_context* ctx, urt_handle buffer, int first, c
   const size_t at = (size_t)first * (size_t)b->stride, bytes = (size_t)count * (size_t)b->stride;
   URT_HIP(ctx, hipMemcpyAsync(b->mirror.get() + at, d_data, bytes, hipMemcpyDeviceToDevice, touch(ctx)));
   mark_device_written(ctx, buffer, *b, first, count);
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+int urt_buffer_copy(urt_context* ctx, urt_handle src, int src_first, urt_handle dst, int dst_first, int count) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  Buffer* s = find_buffer(ctx, src);
+  Buffer* d = find_buffer(ctx, dst);
+  if (!s || !d) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string("buffer_copy: ") + (!s ? "src" : "dst") + " is 0 or an unknown buffer handle");
+  if (src == dst) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "buffer_copy: src and dst are one buffer");
+  if (s->stride != d->stride) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "buffer_copy: the strides of src and dst differ");
+  if (int rc = check_element_range(ctx, "buffer_copy (src)", *s, src_first, count)) return rc;
+  if (int rc = check_element_range(ctx, "buffer_copy (dst)", *d, dst_first, count)) return rc;
+  if (count == 0) return URT_OK;
+  URT_GUARD_BEGIN
+  if (int rc = buffer_mirror(ctx, *s)) return rc;
+  if (int rc = buffer_mirror(ctx, *d)) return rc;
+  const size_t bytes = (size_t)count * (size_t)s->stride;
+  URT_HIP(ctx, hipMemcpyAsync(d->mirror.get() + (size_t)dst_first * (size_t)d->stride, s->mirror.get() + (size_t)src_first * (size_t)s->stride, bytes,
+                              hipMemcpyDeviceToDevice, touch(ctx)));
+  mark_device_written(ctx, dst, *d, dst_first, count);
   return URT_OK;
   URT_GUARD_END(ctx)
 }

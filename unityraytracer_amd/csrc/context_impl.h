@@ -362,6 +362,7 @@ int check_watchdog(urt_context* ctx);
 int download_elements(urt_context* ctx, Buffer& b, int first, int last);   // mirror -> host, synchronising, counted
 int buffer_sync_host(urt_context* ctx, Buffer& b);          // downloads the stale range (synchronises; counted), after which `host` is current
 int sync_bound_hosts(urt_context* ctx, unsigned int slots); // ... of the buffers bound to the slots of the mask
+int buffer_mirror(urt_context* ctx, Buffer& b);             // the device mirror, made and filled from `host` at the first need
 int strip_count(int group_rows, int first_row, int row_stride);
 // scene_prep.cpp
 int prepare_scene(urt_context* ctx);

@@ -304,9 +304,11 @@ int urt_denoise(urt_context* ctx, urt_handle src, urt_handle dst, urt_handle hit
 // Every argument is checked before anything is submitted: on an error nothing is enqueued.  Then the deferred frames are submitted
 // (prev_color is usually a deferred blend's destination) and k_reproject is enqueued on the main stream.  The scene is not read and the
 // counters are not changed.  with_motion: urt_reproject_objects, whose tables (ComputeBuffers: host copies) are uploaded on the same
-// stream in front of k_reproject_objects; without a table given the call is urt_reproject's, kernel included.
+// stream in front of k_reproject_objects; without a table given the call is urt_reproject's, kernel included.  deform (only with
+// with_motion): urt_reproject_deformed, whose four buffers are read through their device mirrors; without one the call is
+// urt_reproject_objects', kernel included.
 static int reproject_impl(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params,
-                          const urt_ReprojectMotion* motion, bool with_motion) {
+                          const urt_ReprojectMotion* motion, bool with_motion, const urt_ReprojectDeform* deform = nullptr) {
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   if (!images || !params) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: images or params is NULL");
   URT_GUARD_BEGIN
@@ -328,6 +330,26 @@ static int reproject_impl(urt_context* ctx, const urt_ReprojectImages* images, c
       tab[k] = &it->second;
     }
   }
+  enum { kPrevVertices, kIndices, kPrevObjects, kDeformed, kDeformBuffers };
+  Buffer* db[kDeformBuffers] = {nullptr, nullptr, nullptr, nullptr};
+  urt_ReprojectDeform De{};
+  if (deform) {
+    De = *deform;
+    if (De.flags != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: deform flags must be 0");
+    if (std::isnan(De.normal_threshold)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: the deform normal_threshold is NaN");
+    const urt_handle dh[kDeformBuffers] = {De.prev_vertices, De.indices, De.prev_mesh_objects, De.deformed};
+    const char* const dname[kDeformBuffers] = {"prev_vertices", "indices", "prev_mesh_objects", "deformed"};
+    const int dstride[kDeformBuffers] = {URT_STRIDE_VEC3, URT_STRIDE_INDEX, URT_STRIDE_MESHOBJECT, 4};
+    for (int k = 0; k < kDeformBuffers; k++) {
+      db[k] = find_buffer(ctx, dh[k]);
+      if (!db[k]) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string("reproject: ") + dname[k] + " is 0 or an unknown buffer handle");
+      if (db[k]->stride != dstride[k])
+        return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("reproject: the stride of ") + dname[k] + " is not " + std::to_string(dstride[k]));
+    }
+    if (db[kIndices]->count % 3 != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: the count of indices is not a multiple of 3");
+    if (db[kDeformed]->count != db[kPrevObjects]->count)
+      return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: the counts of deformed and prev_mesh_objects differ");
+  }
   if (P.flags != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: flags must be 0");
   if (std::isnan(P.normal_threshold) || std::isnan(P.plane_threshold)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: a threshold is NaN");
   if (!valid_max_history(P.max_history)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: max_history must be 0 or >= 1");
@@ -345,6 +367,7 @@ static int reproject_impl(urt_context* ctx, const urt_ReprojectImages* images, c
   if (!ctx->c2w_set || !ctx->invp_set)
     return fail(ctx, URT_ERR_UNBOUND, "reproject: _CameraToWorld / _CameraInverseProjection never set (SetMatrix, RM:774-775)");
   URT_HIP(ctx, hipSetDevice(ctx->device));
+  for (Buffer* b : db) if (b) if (int rc = buffer_mirror(ctx, *b)) return rc;   // (before anything is enqueued: an allocation can fail)
   { int rc = flush_pending(ctx); if (rc) return rc; }
   ReprojectImages I{};                                             // device pointers after the flush (a Result texture may be renamed)
   I.prev_color = t[0]->dev; I.prev_count = t[1]->dev; I.prev_hit = t[2]->dev; I.prev_normal = t[3]->dev; I.prev_id = t[4]->dev;
@@ -356,7 +379,7 @@ static int reproject_impl(urt_context* ctx, const urt_ReprojectImages* images, c
   std::memcpy(S.c2w, ctx->c2w, sizeof S.c2w);
   std::memcpy(S.invp, ctx->invp, sizeof S.invp);
   S.max_history = P.max_history; S.normal_threshold = P.normal_threshold; S.plane_threshold = P.plane_threshold;
-  if (tab[0] || tab[1]) {
+  if (tab[0] || tab[1] || deform) {
     ReprojectMotion T{};
     for (int k = 0; k < 2; k++) {
       if (!tab[k]) continue;
@@ -369,6 +392,16 @@ static int reproject_impl(urt_context* ctx, const urt_ReprojectImages* images, c
     T.sphere = tab[1] ? (const float4*)ctx->mo_table[1].get() : nullptr; T.n_sphere = tab[1] ? tab[1]->count : 0;
     T.moved_max_history = Mo.moved_max_history;
     for (int k = kInputs; k < kImages; k++) if (t[k]) t[k]->other_writes = true;
+    if (deform) {
+      ReprojectDeform D{};
+      D.vertices = (const float*)db[kPrevVertices]->mirror.get(); D.n_vertices = db[kPrevVertices]->count;
+      D.indices = (const int*)db[kIndices]->mirror.get(); D.n_indices = db[kIndices]->count;
+      D.objects = (const float4*)db[kPrevObjects]->mirror.get(); D.flags = (const int*)db[kDeformed]->mirror.get();
+      D.n_objects = db[kDeformed]->count;
+      D.normal_threshold = De.normal_threshold;
+      URT_HIP(ctx, launch_reproject_deformed(I, S, T, D, touch(ctx)));
+      return URT_OK;
+    }
     URT_HIP(ctx, launch_reproject_objects(I, S, T, touch(ctx)));
     return URT_OK;
   }
@@ -385,6 +418,11 @@ int urt_reproject(urt_context* ctx, const urt_ReprojectImages* images, const urt
 int urt_reproject_objects(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params,
                           const urt_ReprojectMotion* motion) {
   return reproject_impl(ctx, images, params, motion, true);
+}
+
+int urt_reproject_deformed(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params,
+                           const urt_ReprojectMotion* motion, const urt_ReprojectDeform* deform) {
+  return reproject_impl(ctx, images, params, motion, true, deform);
 }
 
 /* ---- resampling ---- */

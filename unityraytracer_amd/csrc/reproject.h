@@ -1,5 +1,5 @@
-// reproject.h — host-callable launchers of the temporal reprojection (reproject.hip): urt_reproject, urt_reproject_objects and
-// urt_blit_add_history
+// reproject.h — host-callable launchers of the temporal reprojection (reproject.hip): urt_reproject, urt_reproject_objects,
+// urt_reproject_deformed and urt_blit_add_history
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -40,11 +40,26 @@ struct ReprojectMotion {
   float moved_max_history;      // 0 = none
 };
 
+// The buffers of urt_reproject_deformed (include/urt.h urt_ReprojectDeform), as device addresses with their element counts: every index
+// the kernel forms is checked against them.  flags null = no deform given (the call is then urt_reproject_objects' pixel for pixel).
+struct ReprojectDeform {
+  const float* vertices;        // prev_vertices: n_vertices elements of 12 bytes, object space
+  const int* indices;           // the buffer bound as _Indices
+  const float4* objects;        // prev_mesh_objects: n_objects elements of 112 bytes (7 float4), localToWorldMatrix in the first four
+  const int* flags;             // deformed: n_objects int32, nonzero = per-vertex path
+  int n_vertices, n_indices, n_objects;
+  float normal_threshold;       // of the per-vertex path
+};
+
 // Enqueues k_reproject on `st`.  hipErrorInvalidValue when the grid is too tall.
 hipError_t launch_reproject(const ReprojectImages& I, const ReprojectSettings& P, hipStream_t st);
 
 // The same with the tables: enqueues k_reproject_objects.
 hipError_t launch_reproject_objects(const ReprojectImages& I, const ReprojectSettings& P, const ReprojectMotion& T, hipStream_t st);
+
+// The same with the previous vertex positions of deformed meshes: enqueues k_reproject<true, ParamsDeform>.
+hipError_t launch_reproject_deformed(const ReprojectImages& I, const ReprojectSettings& P, const ReprojectMotion& T, const ReprojectDeform& D,
+                                     hipStream_t st);
 
 // One AdditionShader blend with the per-pixel sample count of `count` (urt_blit_add_history), in place on dst and count.
 hipError_t launch_blit_add_history(const float4* src, float4* dst, float4* count, size_t n_pixels, float max_history, hipStream_t st);

@@ -10,6 +10,11 @@
 // object's 48-byte "current world -> previous world" entry (three dwordx4 loads; the object id is uniform over most waves, so the entry
 // comes from one or two cache lines) and projects the point where it WAS.  Ground, sky and scenes without tables pay one uniform branch;
 // k_reproject<false> keeps its argument struct and takes none of the new branches.
+// k_reproject<true, ParamsDeform> (urt_reproject_deformed) is a third instantiation: a triangle pixel of a MeshObject flagged as deformed
+// finds the point it shows where the previous vertex positions of its triangle put it: three dword index loads, three 12-byte vertex
+// gathers and the object's previous matrix as four dwordx4 loads (the object id is uniform over most waves; lanes of one triangle ask
+// for the same addresses, which one cache line serves).  Every index is checked against its buffer before it is used.  The two other
+// instantiations keep their argument structs and their code.
 // k_blit_add_history / k_blit_add_history_multi: grid-stride over the pixels as k_blit_add / k_blit_add_multi; the fused form reads the
 // count and dst once, blends n frames and writes both (and the present) once: 16 n + 64 bytes per pixel with a present.
 #include <hip/hip_runtime.h>
@@ -28,6 +33,15 @@ struct ParamsObjects : Params {
   urtd::ReprojectMotion T;
 };
 
+struct ParamsDeform : ParamsObjects {
+  urtd::ReprojectDeform D;
+};
+
+template <class PARAMS> struct is_deform { static constexpr bool value = false; };
+template <> struct is_deform<ParamsDeform> { static constexpr bool value = true; };
+
+struct Vec3 { float x, y, z; };                                  // an element of a stride-12 buffer
+
 __device__ __forceinline__ bool finite3(float4 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
 __device__ __forceinline__ bool finite4(float4 v) { return finite3(v) && isfinite(v.w); }
 
@@ -40,9 +54,11 @@ __device__ __forceinline__ bool identity_entry(float4 a, float4 b, float4 c) {
 }
 
 // urt_reproject (MOTION false, PARAMS = Params) and urt_reproject_objects (MOTION true, PARAMS = ParamsObjects).  A pixel that is not
-// moved takes exactly the operations of the instantiation without MOTION.
+// moved takes exactly the operations of the instantiation without MOTION.  urt_reproject_deformed (MOTION true, PARAMS = ParamsDeform):
+// a pixel that is not deformed takes exactly the operations of urt_reproject_objects.
 template <bool MOTION, class PARAMS>
 __global__ __launch_bounds__(256) void k_reproject(const PARAMS A) {
+  constexpr bool DEFORM = is_deform<PARAMS>::value;
   const urtd::ReprojectImages& I = A.I;
   const urtd::ReprojectSettings& P = A.P;
   const urtd::ReprojectMotion* T = nullptr;
@@ -65,7 +81,53 @@ __global__ __launch_bounds__(256) void k_reproject(const PARAMS A) {
   float4 hp = h, np = nr;
   float L = 1.0f;
   bool moved = false, dead = false;
-  if (MOTION && surface_in && (k == 2.0f || k == 3.0f)) {
+  bool deformed = false;
+  if constexpr (DEFORM) {
+    const urtd::ReprojectDeform& D = A.D;
+    if (surface_in && k == 3.0f && D.flags) {                    // (uniform; null flags = no deform, reproject.h: the host then launches <true, ParamsObjects>)
+      const float4 idp = I.id[pix];
+      const int o = __float_as_int(idp.x);
+      if (o < 0 || o >= D.n_objects) {
+        dead = true;                                             // no such MeshObject: no history
+      } else if (D.flags[o] != 0) {
+        deformed = true;
+        dead = true;                                             // until the previous triangle is found and sound
+        const int i = __float_as_int(idp.y);
+        const float u = idp.z, v = idp.w;
+        if (i >= 0 && i <= D.n_indices - 3) {
+          const int j0 = D.indices[i], j1 = D.indices[i + 1], j2 = D.indices[i + 2];
+          const int nv = D.n_vertices;
+          if (j0 >= 0 && j0 < nv && j1 >= 0 && j1 < nv && j2 >= 0 && j2 < nv) {
+            const Vec3* vp = (const Vec3*)D.vertices;
+            const Vec3 a0 = vp[j0], a1 = vp[j1], a2 = vp[j2];
+            const float4* mp = D.objects + 7 * (size_t)o;        // a MeshObject: 112 bytes, localToWorldMatrix first
+            const float4 c0 = mp[0], c1 = mp[1], c2 = mp[2], c3 = mp[3];   // its columns
+            const float v0x = ((c0.x * a0.x + c1.x * a0.y) + c2.x * a0.z) + c3.x;
+            const float v0y = ((c0.y * a0.x + c1.y * a0.y) + c2.y * a0.z) + c3.y;
+            const float v0z = ((c0.z * a0.x + c1.z * a0.y) + c2.z * a0.z) + c3.z;
+            const float v1x = ((c0.x * a1.x + c1.x * a1.y) + c2.x * a1.z) + c3.x;
+            const float v1y = ((c0.y * a1.x + c1.y * a1.y) + c2.y * a1.z) + c3.y;
+            const float v1z = ((c0.z * a1.x + c1.z * a1.y) + c2.z * a1.z) + c3.z;
+            const float v2x = ((c0.x * a2.x + c1.x * a2.y) + c2.x * a2.z) + c3.x;
+            const float v2y = ((c0.y * a2.x + c1.y * a2.y) + c2.y * a2.z) + c3.y;
+            const float v2z = ((c0.z * a2.x + c1.z * a2.y) + c2.z * a2.z) + c3.z;
+            const float w = (1.0f - u) - v;
+            hp.x = (v0x * w + v1x * u) + v2x * v;
+            hp.y = (v0y * w + v1y * u) + v2y * v;
+            hp.z = (v0z * w + v1z * u) + v2z * v;
+            const float e1x = v1x - v0x, e1y = v1y - v0y, e1z = v1z - v0z;
+            const float e2x = v2x - v0x, e2y = v2y - v0y, e2z = v2z - v0z;
+            np.x = e1y * e2z - e1z * e2y;
+            np.y = e1z * e2x - e1x * e2z;
+            np.z = e1x * e2y - e1y * e2x;
+            L = urt::f_sqrt((np.x * np.x + np.y * np.y) + np.z * np.z);
+            if (finite3(hp) && L > 0.0f && isfinite(L)) { dead = false; moved = true; }
+          }
+        }
+      }
+    }
+  }
+  if (MOTION && surface_in && (k == 2.0f || k == 3.0f) && !(DEFORM && (deformed || dead))) {
     const float4* tab = k == 3.0f ? T->mesh : T->sphere;
     if (tab) {                                                   // uniform: a scene without tables stops here
       const int o = __float_as_int(I.id[pix].x);
@@ -138,7 +200,8 @@ __global__ __launch_bounds__(256) void k_reproject(const PARAMS A) {
         const int oq = __float_as_int(I.prev_id[q].x);
         const float nd = (np.x * m.x + np.y * m.y) + np.z * m.z;
         const float pd = fabsf((np.x * (Q.x - hp.x) + np.y * (Q.y - hp.y)) + np.z * (Q.z - hp.z));
-        const float nt = MOTION && moved ? P.normal_threshold * L : P.normal_threshold;
+        float nt = MOTION && moved ? P.normal_threshold * L : P.normal_threshold;
+        if constexpr (DEFORM) { if (deformed) nt = A.D.normal_threshold * L; }
         const float pt = MOTION && moved ? (P.plane_threshold * z) * L : P.plane_threshold * z;
         ok = ok && m.w == k && oq == o && isfinite(Q.w) && Q.w > 0.0f && nd >= nt && pd <= pt;
       }
@@ -233,6 +296,17 @@ hipError_t launch_reproject_objects(const ReprojectImages& I, const ReprojectSet
   ParamsObjects A{};
   A.I = I; A.P = P; A.T = T;
   hipLaunchKernelGGL((k_reproject<true, ParamsObjects>), grid, dim3(256), 0, st, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_reproject_deformed(const ReprojectImages& I, const ReprojectSettings& P, const ReprojectMotion& T, const ReprojectDeform& D,
+                                     hipStream_t st) {
+  if (I.width <= 0 || I.height <= 0) return hipSuccess;
+  const dim3 grid((unsigned int)((I.width + 15) / 16), (unsigned int)((I.height + 15) / 16));
+  if (grid.y > 65535u) return hipErrorInvalidValue;
+  ParamsDeform A{};
+  A.I = I; A.P = P; A.T = T; A.D = D;
+  hipLaunchKernelGGL((k_reproject<true, ParamsDeform>), grid, dim3(256), 0, st, A);
   return hipGetLastError();
 }
 

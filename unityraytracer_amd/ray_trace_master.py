@@ -24,7 +24,7 @@ from dataclasses import dataclass, field
 
 from . import host_scene, scenes
 from .unity_api import ComputeBuffer, ComputeShader, Context, Graphics, Material, RenderTexture, _matrix16, _max_history_arg, \
-    denoise_params, reproject_params
+    _number_arg, denoise_params, reproject_params
 
 
 @dataclass
@@ -77,6 +77,8 @@ class RayTraceMaster:
         self._taov = None                            # temporal: two (hit, normal, id) sets, the previous and the new camera's
         self._moved_max_history = 0.0                # temporal: extra clamp of the count on pixels of moved objects (MoveObjects; 0 = none)
         self._tmotion = [None, None]                 # temporal: the mesh and the sphere motion table of the last MoveObjects (ComputeBuffers)
+        self._tdeform = [None, None, None]           # temporal, keep_history: previous positions, previous _MeshObjects, per-mesh flags (ComputeBuffers)
+        self._deform_normal_threshold = None         # temporal, keep_history: urt_ReprojectDeform.normal_threshold (None = the library's default)
         self._skins = {}                             # AttachSkin: MeshObject index -> its span, rest pose, bone indices and weights
         self._skinBuffers = None                     # SkinMeshes: rest vertices, rest normals, bone indices, bone weights (ComputeBuffers of the vertex count)
         self._boneBuffers = {}                       # SkinMeshes: MeshObject index -> its bone table (ComputeBuffer)
@@ -367,14 +369,17 @@ class RayTraceMaster:
     # include/urt.h URT_REPROJECT_DEFAULT_*); max_history also caps the count the blend uses, so a still view keeps a running mean of its
     # last max_history frames (0 = unlimited).
     def EnableTemporalAccumulation(self, max_history: float = None, normal_threshold: float = None, plane_threshold: float = None,
-                                   moved_max_history: float = 0.0):
+                                   moved_max_history: float = 0.0, deform_normal_threshold: float = None):
         from ._lib import REPROJECT_DEFAULTS
         mmh = _max_history_arg(moved_max_history, "EnableTemporalAccumulation", "moved_max_history")
+        if deform_normal_threshold is not None:
+            deform_normal_threshold = _number_arg(deform_normal_threshold, "deform_normal_threshold", "EnableTemporalAccumulation")
         given = {"max_history": max_history, "normal_threshold": normal_threshold, "plane_threshold": plane_threshold}
         settings = {k: (REPROJECT_DEFAULTS[k] if v is None else v) for k, v in given.items()}
         p = reproject_params(np.eye(4, dtype=np.float32).reshape(16), **settings)   # checked before anything is created
         self._temporal = {"max_history": p.max_history, "normal_threshold": p.normal_threshold, "plane_threshold": p.plane_threshold}
         self._moved_max_history = mmh
+        self._deform_normal_threshold = deform_normal_threshold
         self._ensure_temporal_textures()
         self._tcount.SetPixels(np.zeros((self.screen_height, self.screen_width, 4), np.float32))   # creation is not assumed to zero
         self._currentSample = 0                                               # the count texture starts empty: so does the mean
@@ -393,6 +398,31 @@ class RayTraceMaster:
             if b is not None:
                 b.Release()
         self._tmotion = [None, None]
+        for b in self._tdeform:
+            if b is not None:
+                b.Release()
+        self._tdeform = [None, None, None]
+
+    # keep_history, before the edit: the vertex buffer as the history saw it is copied on the device into the previous-positions buffer
+    # (include/urt.h urt_buffer_copy: no download) and the current _MeshObjects list becomes prev_mesh_objects.
+    def _snapshot_for_deform(self):
+        prev_v = self._tdeform[0]
+        if prev_v is not None and prev_v.count != self._vertexBuffer.count:
+            prev_v.Release()
+            prev_v = None
+        if prev_v is None:
+            prev_v = ComputeBuffer(self.ctx, self._vertexBuffer.count, 12)
+        self._tdeform[0] = prev_v
+        prev_v.CopyFrom(self._vertexBuffer)
+        self._tdeform[1] = self.CreateComputeBuffer(self._tdeform[1], self.scene.mesh_objects, 112)
+
+    # keep_history, after the edit: the flags of the edited meshes; -> the deform argument of Context.reproject
+    def _deform_argument(self, edited):
+        flags = np.zeros(len(self.scene.mesh_objects), np.int32)
+        flags[list(edited)] = 1
+        self._tdeform[2] = self.CreateComputeBuffer(self._tdeform[2], flags, 4)
+        d = (self._tdeform[0], self._indexBuffer, self._tdeform[1], self._tdeform[2])
+        return d if self._deform_normal_threshold is None else d + (self._deform_normal_threshold,)
 
     def _ensure_temporal_textures(self):
         w, h = self.screen_width, self.screen_height
@@ -507,8 +537,10 @@ class RayTraceMaster:
     # bounds.  The library refits the deformed meshes on the GPU (include/urt.h option "refit_vertices").  Temporal accumulation off, or
     # no history yet: the accumulation restarts.  On: the MoveObjects protocol with an all-NaN motion entry for each deformed mesh, which
     # urt_reproject_objects defines as "no history": the deformed meshes restart at count 0, everything else keeps its history, and
-    # ResampleDisocclusions fills them.  (Per-vertex motion vectors are out of scope.)
-    def DeformMeshes(self, edits, recompute_normals: bool = True):
+    # ResampleDisocclusions fills them.  keep_history (needs temporal accumulation on, else it changes nothing): the deformed meshes keep
+    # their history through per-vertex motion instead (include/urt.h urt_reproject_deformed) — the vertex buffer is snapshot on the
+    # device before the edit, their motion entries are the identity and their pixels look up where their triangle's points were.
+    def DeformMeshes(self, edits, recompute_normals: bool = True, keep_history: bool = False):
         s = self.scene
         edits = dict(edits)
         if self._treesNeedRebuilding and self._rayTraceObjects:                    # the lists the indices refer to do not exist yet
@@ -537,6 +569,9 @@ class RayTraceMaster:
             prev, cur = self._taov
             self.SetShaderParameters()
             self.ctx.render_aov(prev[0], prev[1], None, prev[2])               # the scene as the history saw it
+        keep = bool(keep_history) and history and bool(edits) and self._vertexBuffer is not None and self._indexBuffer is not None
+        if keep:
+            self._snapshot_for_deform()
         vertices = np.array(s.vertices, dtype=np.float32).reshape(-1, 3)           # (a copy: the caller's scene arrays are not written)
         for k, a in checked.items():
             vertices[spans[k][0]: spans[k][1] + 1] = a
@@ -568,13 +603,15 @@ class RayTraceMaster:
         self.ctx.render_aov(cur[0], cur[1], None, cur[2])                      # the deformed scene
         table = host_scene.mesh_motion(s.mesh_objects, s.mesh_objects)             # nothing else has moved: identity entries
         for k in edits:
-            table[k] = np.nan
+            if not keep:
+                table[k] = np.nan
         self._tmotion[0] = self.CreateComputeBuffer(self._tmotion[0], table if edits else np.zeros((0, 12), np.float32), 48)
         self._tmotion[1] = self.CreateComputeBuffer(self._tmotion[1], np.zeros((0, 12), np.float32), 48)
         color, count = self._tspare
+        extra = {"deform": self._deform_argument(edits)} if keep else {}
         self.ctx.reproject(self._converged, self._tcount, prev[0], prev[1], prev[2], cur[0], cur[1], cur[2], color, count, prev_m,
                            mesh_motion=self._tmotion[0], sphere_motion=self._tmotion[1], moved_max_history=self._moved_max_history,
-                           **self._temporal)
+                           **extra, **self._temporal)
         self._tspare = (self._converged, self._tcount)
         self._converged, self._tcount = color, count
 
@@ -701,7 +738,9 @@ class RayTraceMaster:
     # History is treated exactly as DeformMeshes treats it: all-NaN motion entries with temporal accumulation on, ResetAccumulation else.
     # recompute_normals: the bones carry rest normals through their linear part, which is right for rigid bones only; with True the
     # normals of the skinned spans come from RecomputeNormals of the skinned positions instead, as the reference computes its normals.
-    def SkinMeshes(self, poses, recompute_normals: bool = False):
+    # keep_history: as DeformMeshes' — the snapshot of the vertex buffer is a device-to-device copy, so the positions still never cross
+    # the bus.
+    def SkinMeshes(self, poses, recompute_normals: bool = False, keep_history: bool = False):
         s = self.scene
         poses = dict(poses)
         if self._treesNeedRebuilding and self._rayTraceObjects:
@@ -728,6 +767,9 @@ class RayTraceMaster:
             prev, cur = self._taov
             self.SetShaderParameters()
             self.ctx.render_aov(prev[0], prev[1], None, prev[2])               # the scene as the history saw it
+        keep = bool(keep_history) and history and bool(checked)
+        if keep:
+            self._snapshot_for_deform()
         self._ensure_skin_buffers()
         rest_v, rest_n, idx, wgt = self._skinBuffers
         for k, a in checked.items():
@@ -755,13 +797,15 @@ class RayTraceMaster:
         self.ctx.render_aov(cur[0], cur[1], None, cur[2])                      # the skinned scene
         table = host_scene.mesh_motion(s.mesh_objects, s.mesh_objects)             # nothing else has moved: identity entries
         for k in checked:
-            table[k] = np.nan
+            if not keep:
+                table[k] = np.nan
         self._tmotion[0] = self.CreateComputeBuffer(self._tmotion[0], table if checked else np.zeros((0, 12), np.float32), 48)
         self._tmotion[1] = self.CreateComputeBuffer(self._tmotion[1], np.zeros((0, 12), np.float32), 48)
         color, count = self._tspare
+        extra = {"deform": self._deform_argument(checked)} if keep else {}
         self.ctx.reproject(self._converged, self._tcount, prev[0], prev[1], prev[2], cur[0], cur[1], cur[2], color, count, prev_m,
                            mesh_motion=self._tmotion[0], sphere_motion=self._tmotion[1], moved_max_history=self._moved_max_history,
-                           **self._temporal)
+                           **extra, **self._temporal)
         self._tspare = (self._converged, self._tcount)
         self._converged, self._tcount = color, count
 

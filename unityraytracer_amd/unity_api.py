@@ -446,7 +446,7 @@ class Context:
                   motion=None, max_history: float = _lib.REPROJECT_DEFAULTS["max_history"],
                   normal_threshold: float = _lib.REPROJECT_DEFAULTS["normal_threshold"],
                   plane_threshold: float = _lib.REPROJECT_DEFAULTS["plane_threshold"], *, mesh_motion=None, sphere_motion=None,
-                  moved_max_history: float = 0.0):
+                  moved_max_history: float = 0.0, deform=None):
         """Temporal reprojection (include/urt.h urt_reproject): the history prev_color / prev_count accumulated under the previous camera,
         whose world-to-clip matrix is prev_world_to_clip (16 floats, column-major: scenes.world_to_clip), carried into the current view
         (the bound _CameraToWorld / _CameraInverseProjection) -> color / count, and the optional motion image.  prev_hit / prev_normal /
@@ -454,7 +454,11 @@ class Context:
         of one size.  Enqueued after the deferred frames; a later GetPixels sees the result.
         mesh_motion / sphere_motion: ComputeBuffers of stride 48 (urt_ObjectMotion: host_scene.mesh_motion / sphere_motion) for objects
         that have moved between the two sets of feature buffers, moved_max_history an extra clamp of the count on their pixels: with
-        any of the three given the call is urt_reproject_objects, else urt_reproject."""
+        any of the three given the call is urt_reproject_objects, else urt_reproject.
+        deform: the buffers of meshes that changed shape (include/urt.h urt_ReprojectDeform) as a tuple (prev_vertices, indices,
+        prev_mesh_objects, deformed[, normal_threshold]) of ComputeBuffers of stride 12 / 4 / 112 / 4, or an object with attributes of
+        these names; the threshold defaults to _lib.REPROJECT_DEFORM_NORMAL_THRESHOLD.  Any deform given makes the call
+        urt_reproject_deformed."""
         images = dict(zip(self.REPROJECT_INPUTS, (prev_color, prev_count, prev_hit, prev_normal, prev_id, hit, normal, id)))
         images.update(color=color, count=count, motion=motion)
         for name, t in images.items():
@@ -479,7 +483,13 @@ class Context:
             if b.stride != C.sizeof(_lib.ObjectMotion):
                 raise ValueError(f"reproject: the stride of {name} is {b.stride}, not {C.sizeof(_lib.ObjectMotion)}")
         mmh = _max_history_arg(moved_max_history, "reproject", "moved_max_history")
+        de = None if deform is None else _deform_arg(self, deform)
         im = _lib.ReprojectImages(*(images[n].handle if images[n] is not None else 0 for n, _ in _lib.ReprojectImages._fields_))
+        if de is not None:
+            mo = _lib.ReprojectMotion(mesh_motion.handle if mesh_motion is not None else 0,
+                                      sphere_motion.handle if sphere_motion is not None else 0, mmh, 0)
+            self.check(self.lib.urt_reproject_deformed(self._h, C.byref(im), C.byref(p), C.byref(mo), C.byref(de)))
+            return
         if mesh_motion is None and sphere_motion is None and mmh == 0.0:
             self.check(self.lib.urt_reproject(self._h, C.byref(im), C.byref(p)))
             return
@@ -489,12 +499,29 @@ class Context:
 
     def reproject_arrays(self, prev_color, prev_count, prev_hit, prev_normal, prev_id, hit, normal, id, prev_world_to_clip,
                          camera_to_world, camera_inverse_projection, motion: bool = True, mesh_motion=None, sphere_motion=None,
-                         moved_max_history: float = 0.0, **params) -> dict:
+                         moved_max_history: float = 0.0, deform=None, **params) -> dict:
         """reproject on numpy images (h, w, 4) float32, row 0 = bottom, through temporary textures.  camera_to_world /
         camera_inverse_projection (16 floats each) are bound as the context's current camera uniforms first (they stay bound).
         mesh_motion / sphere_motion: the motion tables as (n, 12) float32 arrays (n >= 1) or None.  Returns
-        {"color", "count"[, "motion"]} as (h, w, 4) arrays."""
+        {"color", "count"[, "motion"]} as (h, w, 4) arrays.
+        deform: (prev_vertices (n, 3) float32, indices (3 t,) int32, prev_mesh_objects (n_objects records of 112 bytes), deformed
+        (n_objects,) int32[, normal_threshold]) as arrays, each with at least one element."""
         tables = {}
+        deform_arrays = None
+        if deform is not None:
+            if not isinstance(deform, (tuple, list)) or len(deform) not in (4, 5):
+                raise ValueError("reproject_arrays: deform must be (prev_vertices, indices, prev_mesh_objects, deformed[, normal_threshold])")
+            pv = np.ascontiguousarray(deform[0], dtype=np.float32)
+            ix = np.ascontiguousarray(deform[1], dtype=np.int32).reshape(-1)
+            mo = np.ascontiguousarray(deform[2])
+            fl = np.ascontiguousarray(deform[3], dtype=np.int32).reshape(-1)
+            if pv.ndim != 2 or pv.shape[1] != 3 or len(pv) < 1:
+                raise ValueError(f"reproject_arrays: deform prev_vertices must have shape (n, 3) with n >= 1, not {pv.shape}")
+            if mo.nbytes == 0 or mo.nbytes % 112:
+                raise ValueError(f"reproject_arrays: deform prev_mesh_objects must hold records of 112 bytes, not {mo.nbytes} bytes")
+            if ix.size < 1 or fl.size < 1:
+                raise ValueError("reproject_arrays: deform indices and deformed need at least one element")
+            deform_arrays = ((pv, 12), (ix, 4), (mo, 112), (fl, 4))
         for name, a in (("mesh_motion", mesh_motion), ("sphere_motion", sphere_motion)):
             if a is None:
                 continue
@@ -513,11 +540,14 @@ class Context:
         reproject_params(prev_world_to_clip, **params)
         c2w, invp = _matrix16(camera_to_world, "camera_to_world"), _matrix16(camera_inverse_projection, "camera_inverse_projection")
         h, w = shape[:2]
-        tex, bufs = [], {}
+        tex, bufs, dbufs = [], {}, []
         try:
             for name, a in tables.items():
                 bufs[name] = ComputeBuffer(self, len(a), 48)
                 bufs[name].SetData(a)
+            for a, stride in deform_arrays or ():
+                dbufs.append(ComputeBuffer(self, a.nbytes // stride, stride))
+                dbufs[-1].SetData(a)
             for a in imgs + [None] * (3 if motion else 2):
                 tex.append(RenderTexture(self, w, h))
                 if a is not None:
@@ -527,13 +557,14 @@ class Context:
             sh.SetMatrix("_CameraInverseProjection", invp)
             outs = tex[8:]
             self.reproject(*tex[:8], outs[0], outs[1], prev_world_to_clip, motion=outs[2] if motion else None,
-                           moved_max_history=moved_max_history, **bufs, **params)
+                           moved_max_history=moved_max_history, deform=None if deform is None else tuple(dbufs) + tuple(deform[4:]),
+                           **bufs, **params)
             res = {"color": outs[0].GetPixels(), "count": outs[1].GetPixels()}
             if motion:
                 res["motion"] = outs[2].GetPixels()
             return res
         finally:
-            for t in tex + list(bufs.values()):
+            for t in tex + list(bufs.values()) + dbufs:
                 t.Release()
 
     def blit_add_history(self, src, dst, count, max_history: float = 0.0):
@@ -625,6 +656,42 @@ def _check_texture(ctx, what: str, name: str, t, like, optional: bool = False):
         raise ValueError(f"{what}: {name} was released")
     if (t.width, t.height) != (like.width, like.height):
         raise ValueError(f"{what}: {name} is {t.width} x {t.height}, not {like.width} x {like.height}")
+
+
+DEFORM_FIELDS = (("prev_vertices", 12), ("indices", 4), ("prev_mesh_objects", 112), ("deformed", 4))
+
+
+def _deform_arg(ctx, deform) -> "_lib.ReprojectDeform":
+    """The checked urt_ReprojectDeform of Context.reproject: a tuple (prev_vertices, indices, prev_mesh_objects, deformed[,
+    normal_threshold]) or an object with these attributes; ComputeBuffers of this context with strides 12 / 4 / 112 / 4, a threshold
+    that is a number and not NaN."""
+    if isinstance(deform, (tuple, list)):
+        if len(deform) not in (4, 5):
+            raise ValueError(f"reproject: deform must hold four buffers and, optionally, the normal threshold, not {len(deform)} items")
+        bufs = list(deform[:4])
+        nt = deform[4] if len(deform) == 5 else None
+    else:
+        try:
+            bufs = [getattr(deform, name) for name, _ in DEFORM_FIELDS]
+        except AttributeError:
+            raise TypeError(f"reproject: deform must be a tuple of four ComputeBuffers (and a threshold) or an object with the attributes "
+                            f"{', '.join(n for n, _ in DEFORM_FIELDS)}, not {type(deform).__name__}") from None
+        nt = getattr(deform, "normal_threshold", None)
+    for (name, stride), b in zip(DEFORM_FIELDS, bufs):
+        if not isinstance(b, ComputeBuffer):
+            raise TypeError(f"reproject: deform {name} must be a ComputeBuffer, not {type(b).__name__}")
+        if b.ctx is not ctx:
+            raise ValueError(f"reproject: deform {name} belongs to another context")
+        if not b.handle:
+            raise ValueError(f"reproject: deform {name} was released")
+        if b.stride != stride:
+            raise ValueError(f"reproject: the stride of deform {name} is {b.stride}, not {stride}")
+    if bufs[1].count % 3:
+        raise ValueError(f"reproject: the count of deform indices ({bufs[1].count}) is not a multiple of 3")
+    if bufs[2].count != bufs[3].count:
+        raise ValueError(f"reproject: deform prev_mesh_objects holds {bufs[2].count} elements, deformed {bufs[3].count}")
+    nt = _number_arg(_lib.REPROJECT_DEFORM_NORMAL_THRESHOLD if nt is None else nt, "deform normal_threshold", "reproject")
+    return _lib.ReprojectDeform(*(b.handle for b in bufs), nt, 0)
 
 
 def _number_arg(v, name: str, what: str) -> float:
@@ -885,6 +952,20 @@ class ComputeBuffer:
                 raise TypeError("SetDataDevice: count is needed with a device address")
             ptr = int(tensor_or_ptr)
         self.ctx.check(self.ctx.lib.urt_buffer_set_data_device(self.ctx._h, self.handle, int(compute_start), C.c_void_p(ptr), int(count)))
+
+    def CopyFrom(self, src: "ComputeBuffer", src_first: int = 0, dst_first: int = 0, count: int | None = None):
+        """A snapshot on the device (include/urt.h urt_buffer_copy): `count` elements of src from src_first on go to elements dst_first ..
+        dst_first + count - 1 of this buffer, mirror to mirror on the context's stream: nothing is downloaded or waited for.  count
+        defaults to what src holds from src_first on."""
+        if not isinstance(src, ComputeBuffer):
+            raise TypeError(f"CopyFrom: src must be a ComputeBuffer, not {type(src).__name__}")
+        if src.ctx is not self.ctx:
+            raise ValueError("CopyFrom: src belongs to another context")
+        for name, v in (("src_first", src_first), ("dst_first", dst_first), ("count", 0 if count is None else count)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"CopyFrom: {name} must be an int, not {type(v).__name__}")
+        count = src.count - int(src_first) if count is None else count
+        self.ctx.check(self.ctx.lib.urt_buffer_copy(self.ctx._h, src.handle, int(src_first), self.handle, int(dst_first), int(count)))
 
     def GetData(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """ComputeBuffer.GetData: elements first .. first + count - 1 as the buffer holds them now, as (count, stride) bytes — the caller
