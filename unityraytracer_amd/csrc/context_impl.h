@@ -271,6 +271,7 @@ struct urt_context {
   unsigned int trace_parity = 0;
   bool main_touched = true;                 // something other than the frame loop's own blends / presents / readbacks was enqueued on the main stream since the last launch
   int slab_cursor = 0, prev_base = 0, prev_n = 0;
+  std::vector<const float4*> prev_writes;   // the device images the deferred blends / copies / presents of the last submission write: the narrow dependency does not cover them
   uint64_t overlapped_launches = 0;
 
   // pipelined readback (urt_texture_read_begin / _end): kReadSlots snapshots in flight, each a device copy + a pinned host image

@@ -334,14 +334,20 @@ int flush_pending(urt_context* ctx) {
     }
     const unsigned int k = ctx->trace_parity++ & 1u;
     const bool disjoint = base >= ctx->prev_base + ctx->prev_n || base + n <= ctx->prev_base;
-    if (ctx->main_touched || !disjoint) {
+    // A launch's dependency covers every image it READS, not only its Result slots: besides the scene that is the sky.  A texture launch
+    // L-1 traced into, or one its deferred blends / copies / presents write (after pre_ev), may have been bound as _SkyboxTexture since.
+    const float4* const prev_slots = ctx->slab.get() + (size_t)ctx->prev_base * ctx->slab_stride;
+    bool sky_written = B.S.sky >= prev_slots && B.S.sky < prev_slots + (size_t)ctx->prev_n * ctx->slab_stride;
+    for (const float4* w : ctx->prev_writes) sky_written = sky_written || w == B.S.sky;
+    const bool wide = ctx->main_touched || !disjoint || sky_written;
+    if (wide) {
       URT_HIP(ctx, hipEventRecord(ctx->dep_ev.get(), ctx->stream));
       URT_HIP(ctx, hipStreamWaitEvent(ctx->trace_q[k].get(), ctx->dep_ev.get(), 0));
     } else {
       URT_HIP(ctx, hipStreamWaitEvent(ctx->trace_q[k].get(), ctx->pre_ev[k ^ 1u].get(), 0));
       ctx->overlapped_launches++;
     }
-    const bool narrow = !(ctx->main_touched || !disjoint);
+    const bool narrow = !wide;
     int rc = launch_sched_frames(ctx, B.S, P, B.T, ctx->slab.get() + (size_t)base * ctx->slab_stride, B.front_mode, B.count, ctx->trace_q[k].get(), (k ? ctx->d_next2 : ctx->d_next).get());
     if (rc) { ctx->main_touched = true; return rc; }
     ctx->last_launch.trace_stream = 1 + (int)k; ctx->last_launch.slab_base = base; ctx->last_launch.overlapped = narrow ? 1 : 0;
@@ -354,6 +360,7 @@ int flush_pending(urt_context* ctx) {
     if (rc) return rc;
   }
   ctx->prev_base = base; ctx->prev_n = n; ctx->slab_cursor = base + n;
+  ctx->prev_writes.clear();                              // (filled below, as the deferred operations are enqueued)
   if (base) {                                            // the Result texture names the LAST frame's slot (do_dispatch named it assuming slot 0)
     Texture* rt = find_texture(ctx, B.tex);
     if (rt && in_slab(ctx, *rt)) rt->dev = ctx->slab.get() + (size_t)(base + n - 1) * ctx->slab_stride;
@@ -375,7 +382,10 @@ int flush_pending(urt_context* ctx) {
         Texture* pt = find_texture(ctx, run.present);
         if (!pt) return fail(ctx, URT_ERR_INVALID_HANDLE, "deferred Blit: destination texture was released");
         pdev = pt->dev;
+        ctx->prev_writes.push_back(pdev);
       }
+      ctx->prev_writes.push_back(d->dev);
+      if (history) ctx->prev_writes.push_back(c->dev);
       const float4* src = slots + (size_t)op.frame * ctx->slab_stride;
       const size_t npix = (size_t)d->w * d->h;
       const bool single = run.frames == 1 && !pdev;
@@ -391,6 +401,7 @@ int flush_pending(urt_context* ctx) {
       Texture* d = find_texture(ctx, op.dst);
       if (!t || !d) return fail(ctx, URT_ERR_INVALID_HANDLE, "deferred Blit: texture was released");
       const float4* img = op.src == B.tex ? slots + (size_t)op.frame * ctx->slab_stride : t->dev;
+      ctx->prev_writes.push_back(d->dev);
       URT_HIP(ctx, hipMemcpyAsync(d->dev, img, (size_t)t->w * t->h * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
       i++;
     } else {
@@ -522,6 +533,8 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
       int rc = ensure_slab(ctx, res_h, *res, limit); if (rc) return rc;
       if (!ctx->slab || ctx->slab_tex != res_h || ctx->slab_frames < 2) limit = 1;
     }
+    // the flush and the new slab may have given the sky's texture other storage (it was the previous batch's Result, detached just now)
+    if (B.n == 0) { int rc = bind_sky(ctx, S); if (rc) return rc; }
     if (limit <= 1) {                                     // not batched: trace this frame now, straight into the texture
       FrameTable T{};
       T.f[0] = fu;
