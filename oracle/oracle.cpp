@@ -76,7 +76,8 @@ namespace {
 
 struct Ray { v3 origin, direction, energy; };                        // RS:23-27
 struct RayTraceParams { v3 color_albedo, color_specular, emission; float smoothness; };  // RS:29-34
-struct RayHit { v3 position; float distance; v3 normal; RayTraceParams lighting; int kind; };  // RS:36-41 (+kind for counters)
+struct RayHit { v3 position; float distance; v3 normal; RayTraceParams lighting; int kind;   // RS:36-41 (+kind for counters)
+                int object, primitive; float u, v; };   // + the identity fields of urt_RayHit (include/urt_types.h), for oracle_probe_aov
 
 static inline v3 ld3(const float* p) { return mk3(p[0], p[1], p[2]); }
 static inline RayTraceParams ldparams(const urt_RayTraceParams& p) {
@@ -122,6 +123,8 @@ struct Tracer {
                f_fma(ts.z, normal.z, f_fma(ts.y, binormal.z, ts.x * tangent.z)));
   }
 
+  int cur_object = -1;   // the sphere / MeshObject the walk is intersecting: what a hit records as its object
+
   // RS:114-120
   static Ray CreateRay(v3 o, v3 d) { Ray r; r.origin = o; r.direction = d; r.energy = mk3(1, 1, 1); return r; }
 
@@ -132,6 +135,7 @@ struct Tracer {
     h.lighting.color_albedo = mk3(0, 0, 0); h.lighting.color_specular = mk3(0, 0, 0);
     h.lighting.smoothness = 0; h.lighting.emission = mk3(0, 0, 0);
     h.kind = 0;
+    h.object = -1; h.primitive = -1; h.u = 0; h.v = 0;
     return h;
   }
 
@@ -156,6 +160,7 @@ struct Tracer {
       bestHit.lighting.smoothness = 0.3f;
       bestHit.lighting.emission = mk3(0, 0, 0);
       bestHit.kind = 1;
+      bestHit.object = -1; bestHit.primitive = -1; bestHit.u = 0; bestHit.v = 0;
     }
   }
 
@@ -175,6 +180,7 @@ struct Tracer {
       bestHit.normal = normalize(bestHit.position - c);
       bestHit.lighting = ldparams(sphere.lighting);
       bestHit.kind = 2;
+      bestHit.object = cur_object; bestHit.primitive = -1; bestHit.u = 0; bestHit.v = 0;
     }
   }
 
@@ -222,6 +228,7 @@ struct Tracer {
         bestHit.normal = normalize((n0 * w) + (n1 * u) + (n2 * v));                        // RS:263
         bestHit.lighting = ldparams(mo.lighting);
         bestHit.kind = 3;
+        bestHit.object = cur_object; bestHit.primitive = (int)i; bestHit.u = u; bestHit.v = v;
       }
     }
   }
@@ -345,7 +352,7 @@ struct Tracer {
       }
       for (int i = 0; i < tests; i++) {
         OracleCounters save = C;
-        if (node.index >= 0 && node.index < S.n_mesh_objects) IntersectMeshObject(ray, bestHit, node.index);
+        if (node.index >= 0 && node.index < S.n_mesh_objects) { cur_object = node.index; IntersectMeshObject(ray, bestHit, node.index); }
         if (i > 0) C = save;   // a repeat changes nothing (strict '<', A.5): count the work once, as the product does it once
       }
     }
@@ -376,7 +383,7 @@ struct Tracer {
       }
       for (int i = 0; i < tests; i++) {
         OracleCounters save = C;
-        if (node.index >= 0 && node.index < S.n_spheres) IntersectSphere(ray, bestHit, S.spheres[node.index]);
+        if (node.index >= 0 && node.index < S.n_spheres) { cur_object = node.index; IntersectSphere(ray, bestHit, S.spheres[node.index]); }
         if (i > 0) C = save;
       }
     }
@@ -674,6 +681,31 @@ void oracle_probe_trace(const OracleScene* scene, int mode, const float* ray6, f
   RayHit h = T.Trace(r);
   out8[0] = h.distance; out8[1] = h.position.x; out8[2] = h.position.y; out8[3] = h.position.z;
   out8[4] = h.normal.x; out8[5] = h.normal.y; out8[6] = h.normal.z; out8[7] = (float)h.kind;
+}
+// include/urt.h urt_render_aov restated for n explicit camera rays (origin3 direction3 each): out = 16 floats per ray, the texels of the
+// hit, normal, albedo and id targets (int fields as their bits).  A miss's albedo is the sky radiance Shade returns.
+void oracle_probe_aov(const OracleScene* scene, int mode, const float* rays6, int n, float* out16) {
+  Tracer T(*scene, mode);
+  for (int k = 0; k < n; k++) {
+    Ray r = Tracer::CreateRay(ld3(rays6 + 6 * k), ld3(rays6 + 6 * k + 3));
+    RayHit h = T.Trace(r);
+    float* o = out16 + 16 * (size_t)k;
+    o[0] = h.position.x; o[1] = h.position.y; o[2] = h.position.z; o[3] = h.distance;
+    o[4] = h.normal.x; o[5] = h.normal.y; o[6] = h.normal.z; o[7] = (float)h.kind;
+    if (h.kind == 0) {
+      Ray s = Tracer::CreateRay(mk3(0, 0, 0), r.direction);
+      RayHit miss = Tracer::CreateRayHit();
+      v3 c = T.Shade(s, miss);
+      o[8] = c.x; o[9] = c.y; o[10] = c.z; o[11] = 0.0f;
+    } else {
+      const RayTraceParams& L = h.lighting;                     // RS:390: min(1 - specular, albedo)
+      o[8] = f_min(1.0f - L.color_specular.x, L.color_albedo.x);
+      o[9] = f_min(1.0f - L.color_specular.y, L.color_albedo.y);
+      o[10] = f_min(1.0f - L.color_specular.z, L.color_albedo.z);
+      o[11] = L.smoothness;
+    }
+    o[12] = bits_f((uint32_t)h.object); o[13] = bits_f((uint32_t)h.primitive); o[14] = h.u; o[15] = h.v;
+  }
 }
 // Sky lookup for a direction (the miss branch of Shade, RS:424-426).
 void oracle_probe_sky(const OracleScene* scene, const float* dir3, float* rgb) {

@@ -74,6 +74,8 @@ def load(build: bool = True):
     lib.oracle_probe_aabb.restype = i
     lib.oracle_probe_trace.argtypes = [C.POINTER(OracleScene), i, vp, vp]
     lib.oracle_probe_trace.restype = None
+    lib.oracle_probe_aov.argtypes = [C.POINTER(OracleScene), i, vp, i, vp]
+    lib.oracle_probe_aov.restype = None
     lib.oracle_probe_sky.argtypes = [C.POINTER(OracleScene), vp, vp]
     lib.oracle_probe_sky.restype = None
     lib.oracle_probe_radiance.argtypes = [C.POINTER(OracleScene), i, vp, i, i, i, vp, i]
@@ -188,6 +190,16 @@ class Oracle:
         out = np.zeros(8, dtype=np.float32)
         self.lib.oracle_probe_trace(C.byref(self.s), mode, _ptr(ray), _ptr(out))
         return {"distance": float(out[0]), "position": out[1:4].copy(), "normal": out[4:7].copy(), "kind": int(out[7])}
+
+    def aov(self, origins, directions, mode: int = 0):
+        """include/urt.h urt_render_aov for explicit camera rays (..., 3): the texels of the hit, normal, albedo and id targets, each
+        (..., 4) float32 (id.xy hold int32 bits), from the Tracer's own Trace and Shade (oracle_probe_aov)."""
+        o = np.asarray(origins, dtype=np.float32)
+        rays = np.ascontiguousarray(np.concatenate([o, np.asarray(directions, dtype=np.float32)], axis=-1).reshape(-1, 6))
+        out = np.zeros((len(rays), 16), dtype=np.float32)
+        self.lib.oracle_probe_aov(C.byref(self.s), mode, _ptr(rays), len(rays), _ptr(out))
+        out = out.reshape(o.shape[:-1] + (16,))
+        return tuple(np.ascontiguousarray(out[..., 4 * k: 4 * k + 4]) for k in range(4))
 
     def sky(self, direction):
         d = np.array(direction, dtype=np.float32)

@@ -1,8 +1,11 @@
 """CPU: the command-stream generator reaches the cases the GPU test exists for, and the sequential model is the documented frame loop.
 
 These are conditions, not measurements: they keep tests/test_gpu_command_stream.py from passing by never getting to a written texture
-bound as the sky, a readback over deferred frames or a scene edit inside a batch."""
+bound as the sky, a readback over deferred frames or a scene edit inside a batch — and tests/test_gpu_command_stream_pipeline.py from
+passing by never feeding an image operation what deferred frames wrote, never writing vertices on the device inside a batch, never
+editing the scene behind an un-waited query, or by reprojecting, selecting and denoising images in which nothing happens."""
 import numpy as np
+import pytest
 
 from oracle import pyoracle
 from unityraytracer_amd import scenes
@@ -66,6 +69,268 @@ def test_model_of_hand_written_programs():
     flat = np.full_like(sc.sky, 1.5)
     want = oracle_frame(sc, flat, 0)
     assert cs.same(tex["S0"], flat) and cs.same(obs[0][2], want) and not cs.same(want, f0)
+
+
+# ---- the pipeline profile ------------------------------------------------------------------------------------------------------------
+F = np.float32
+# sha256 of repr([make_program(seed) for seed in range(24)]), computed on the commit before the pipeline profile existed
+FRAME_PROGRAMS_DIGEST = "770ff5c6ab1c8963024ba34dadfc434fbea4f3047bc31b8d365e4f72afb1fb99"
+
+
+def pipeline(ops, **kw):
+    return cs.run_model(ops, profile="pipeline", **kw)
+
+
+def test_the_frame_loop_programs_are_what_they_were():
+    import hashlib
+    programs = [cs.make_program(seed) for seed in SEEDS]
+    assert hashlib.sha256(repr(programs).encode()).hexdigest() == FRAME_PROGRAMS_DIGEST
+    assert programs == [cs.make_program(seed, profile="frames") for seed in SEEDS]
+    assert not any(op[0] in cs.NEW_KINDS for p in programs for op in p)
+
+
+def test_pipeline_programs_keep_to_the_rules():
+    assert cs.make_program(3, profile="pipeline") == cs.make_program(3, profile="pipeline") != cs.make_program(4, profile="pipeline")
+    lo, hi = cs.pipeline_world()["span"]
+    nv = len(cs.pipeline_world()["rest_v"])
+    for seed in SEEDS:
+        p = cs.make_program(seed, profile="pipeline")
+        assert 40 <= len(p) <= 60, (seed, len(p))
+        tr = cs._PipeTrack()
+        for op in p:
+            k = op[0]
+            assert k in cs.PIPE_KINDS and tr.allowed(op), (seed, op)
+            outputs = [t for t, _ in cs.pipeline_writes_of(op, tr.result)] if k in cs.IMAGE_OPS else []
+            assert tr.sky not in outputs, (seed, op, "an output is the bound sky")
+            if k != "resample":                                  # (resample_below blends into what it reads: its H and N are two textures)
+                assert not set(outputs) & set(cs.pipeline_reads_of(op, tr.result)), (seed, op, "an output is also an input")
+            names = [a for a in op[1:] if isinstance(a, str) and a in cs.ALL_TEX + cs.PIPE_TEX]
+            if k in cs.IMAGE_OPS + ("blit",):
+                assert len({cs.size_class(n) for n in names}) <= 1, (seed, op, "sizes differ")
+            if k == "aov":
+                assert op[2] in range(1, 16)
+            if k == "skin":
+                assert lo <= op[3] and op[4] >= 1 and op[3] + op[4] - 1 <= hi and 0 <= op[1] < len(cs.POSE_ANGLES), (seed, op)
+            if k in ("set_device", "set_host", "bounds"):
+                assert 0 <= op[1] and op[2] >= 1 and op[1] + op[2] <= nv, (seed, op)
+            if k == "get_buffer":
+                assert op[1] in cs.BUFFERS and 0 <= op[2] and op[3] >= 1 and op[2] + op[3] <= nv, (seed, op)
+            if k != "get" and k != "denoise":
+                assert "D" not in op[1:], (seed, op, "the denoised image feeds something")
+            tr.apply(op)
+        assert tr.tickets == 0
+
+
+@pytest.fixture(scope="module")
+def pipeline_models():
+    """The model of every program of the seed set with its figures, made once: [(program, observations, final, stats)]."""
+    out = []
+    for seed in SEEDS:
+        p, stats = cs.make_program(seed, profile="pipeline"), []
+        obs, fin = pipeline(p, stats=stats)
+        out.append((p, obs, fin, stats))
+    return out
+
+
+def test_pipeline_seed_set_reaches_the_interesting_cases(pipeline_models):
+    cov = [cs.pipeline_coverage(p) for p, _, _, _ in pipeline_models]
+    kinds = {k: sum(c["kinds"][k] for c in cov) for k in cs.PIPE_KINDS}
+    cases = {key: sum(c[key] > 0 for c in cov) for key in ("input_deferred", "output_deferred", "vertex_write_in_batch", "async_then_change",
+                                                          "mixed_readback")}
+    print("op kinds over the pipeline seed set:", kinds)
+    print("programs in which ... occurs:", cases)
+    assert all(kinds[k] >= 10 for k in cs.NEW_KINDS), kinds
+    assert all(n >= 3 for n in cases.values()), cases
+    # non-vacuity, on the model's own output
+    stats = [s for _, _, _, st in pipeline_models for s in st]
+    rp = [f for _, k, f in stats if k == "reproject"]
+    good_rp = sum(f["kept"] >= 0.25 and f["lost"] >= 0.02 for f in rp)
+    sel = [f for _, k, f in stats if k in ("select", "resample")]
+    good_sel = sum(1 <= f["selected"] <= f["of"] for f in sel)
+    partial = sum(1 <= f["selected"] < f["of"] for f in sel)
+    dn = [f for _, k, f in stats if k == "denoise"]
+    good_dn = sum(f["changed"] >= 1 and f["identical"] >= 1 for f in dn)
+    print(f"reprojections that keep >= 25 % and lose >= 2 % of the pixels: {good_rp} of {len(rp)};  selections of 1 .. all pixels: {good_sel} of "
+          f"{len(sel)} ({partial} of them not all);  denoise ops that change a surface pixel and keep one: {good_dn} of {len(dn)}")
+    assert 2 * good_rp >= len(rp) and 2 * good_sel >= len(sel) and 2 * good_dn >= len(dn)
+    assert partial >= 10
+    # every async answer is observed, and the final contents hold both sides of every buffer
+    for p, obs, fin, _ in pipeline_models:
+        assert sum(op[0].endswith("_async") for op in p) == sum(k.endswith("_async") for _, k, _ in obs)
+        assert all(n in fin and n + ".dev" in fin for n in cs.BUFFERS)
+
+
+def test_the_comparison_notices_one_changed_op(pipeline_models):
+    """first_difference is not vacuous: leaving out one op that writes (the first of its kind in the program) shows, for most kinds at
+    the very observation or texture it feeds."""
+    noticed = {}
+    for p, obs, fin, _ in pipeline_models[:8]:
+        for kind in ("aov_into", "reproject", "denoise", "resample", "skin", "set_device", "set_host", "snapshot", "normals"):
+            at = [i for i, op in enumerate(p) if op[0] == kind]
+            if not at or kind in noticed:
+                continue
+            q = [op for i, op in enumerate(p) if i != at[0]]
+            if sum(op[0] == "read_begin" for op in q) != sum(op[0] == "read_end" for op in q):
+                continue
+            try:
+                other = pipeline(q)
+            except AssertionError:
+                continue
+            same_obs = len(other[0]) == len(obs) and all(cs.same(a[2], b[2]) for a, b in zip(other[0], obs))
+            same_fin = all(cs.same(np.asarray(other[1][n], fin[n].dtype), fin[n]) for n in fin)
+            if not (same_obs and same_fin):
+                noticed[kind] = True
+    print("kinds whose removal the comparison noticed:", sorted(noticed))
+    assert len(noticed) >= 7, noticed
+
+
+def test_model_of_feature_buffers():
+    import aov_ref
+    sc = cs.make_scene()
+    ref = aov_ref.render_aov_ref(sc)
+    obs, tex = pipeline([("aov", "G", 15, False), ("aov", "P", 5, False), ("aov_into", "C"), ("get", "Gi")])
+    for name, img in zip(cs.G_TEX, ref):
+        assert cs.same(tex[name], img), name
+    assert cs.same(tex["Ph"], ref[0]) and cs.same(tex["Pa"], ref[2]) and not tex["Pn"].any() and not tex["Pi"].any()      # the subset only
+    assert cs.same(tex["C"], ref[2]) and cs.same(obs[0][2], ref[3])
+    # ... and the probe itself against the oracle's Trace, the numpy material table and the triangle the id names
+    hit, nrm, alb, ident = ref
+    kind, obj, prim = nrm[..., 3].astype(np.int32), ident.view(np.int32)[..., 0], ident.view(np.int32)[..., 1]
+    assert set(np.unique(kind).tolist()) == {0, 1, 2, 3}
+    O, D = aov_ref.camera_rays(sc, sc.width, sc.height)
+    orc = pyoracle.Oracle(sc)
+    for y, x in [(y, x) for y in range(0, sc.height, 7) for x in range(0, sc.width, 5)]:
+        r = orc.trace(O[y, x] if O.ndim == 3 else O, D[y, x])
+        assert r["kind"] == kind[y, x] and cs.same(F(r["distance"]).reshape(1), hit[y, x, 3:]) and cs.same(r["position"], hit[y, x, :3])
+        assert cs.same(r["normal"], nrm[y, x, :3])
+    surf = kind != 0
+    tab = aov_ref.material_albedo(sc)
+    m = aov_ref.material_index(sc, kind, obj)
+    assert cs.same(alb[surf], tab[m[surf]])
+    assert (obj[kind == 0] == -1).all() and (obj[kind == 1] == -1).all() and (prim[kind != 3] == -1).all() and (ident[..., 2:][kind != 3] == 0).all()
+    assert all(cs.same(alb[y, x, :3], orc.sky(D[y, x])) and alb[y, x, 3] == 0 for y, x in zip(*np.nonzero(~surf)))
+    tri = kind == 3
+    v, ix = np.asarray(sc.vertices, np.float64).reshape(-1, 3), np.asarray(sc.indices).reshape(-1)
+    mo = sc.mesh_objects[obj[tri]]
+    assert ((prim[tri] >= mo["indices_offset"]) & (prim[tri] < mo["indices_offset"] + mo["indices_count"]) & ((prim[tri] - mo["indices_offset"]) % 3 == 0)).all()
+    M = np.asarray(mo["localToWorldMatrix"], np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)
+    u, w = ident[..., 2][tri].astype(np.float64), ident[..., 3][tri].astype(np.float64)
+    a, b, c = (v[ix[prim[tri] + k]] for k in range(3))
+    local = a * (1 - u - w)[:, None] + b * u[:, None] + c * w[:, None]
+    world = np.einsum("nij,nj->ni", M[:, :3, :3], local) + M[:, :3, 3]
+    assert np.abs(world - hit[tri][:, :3]).max() < 1e-4                       # the point (primitive, u, v) names is the hit position
+    # the frame ray is another ray, under the uniforms of the frame counter
+    _, jit = pipeline([("frame", None), ("aov", "G", 1, True)])
+    s1 = cs.copy.copy(sc)
+    (s1.pixel_offset, s1.seed) = cs.frame_uniforms_of(sc, 1)
+    want = aov_ref.render_aov_ref(s1, frame=(*s1.pixel_offset, s1.seed))[0]
+    assert cs.same(jit["Gh"], want) and not cs.same(want, ref[0])
+
+
+def test_model_of_the_temporal_step():
+    from denoise_ref import denoise_ref
+    from reproject_deform_ref import matrices_of, reproject_deformed_ref
+    from reproject_motion_ref import reproject_objects_ref
+    from reproject_ref import reproject_ref
+    from resample_ref import blend_samples_ref, select_pixels_ref
+    from unityraytracer_amd import host_scene
+    sc = cs.make_scene()
+    head = [("frame", None), ("history", 0.0), ("frame", None), ("history", 0.0), ("aov", "P", 11, False)]
+    for form, change in (("plain", [("camera", 1)]), ("objects", [("move_mesh", 1, 2), ("move_spheres", 0), ("camera", 2)]),
+                         ("deformed", [("snapshot",), ("skin", 1, True, 0, 98), ("camera", 1)])):
+        mid = head + change + [("aov", "G", 15, False)]
+        _, t = pipeline(mid)
+        now = sc
+        for op in change:
+            if op[0] != "snapshot":
+                now = cs.edited_scene(now, op)
+        args = [t[n] for n in ("H", "N", "Ph", "Pn", "Pi", "Gh", "Gn", "Gi")] + \
+               [scenes.world_to_clip(cs.cameras(sc)[0], sc.camera_inverse_projection), now.camera_to_world, now.camera_inverse_projection]
+        tables = dict(mesh_motion=host_scene.mesh_motion(sc.mesh_objects, now.mesh_objects), sphere_motion=host_scene.sphere_motion(sc.spheres, now.spheres))
+        if form == "plain":
+            want = reproject_ref(*args, max_history=8.0)
+        elif form == "objects":
+            want = reproject_objects_ref(*args, max_history=8.0, **tables)
+        else:
+            deform = (np.asarray(sc.vertices, F).reshape(-1, 3), sc.indices, matrices_of(sc.mesh_objects), np.array([1, 0, 0], np.int32))
+            want = reproject_deformed_ref(*args, max_history=8.0, deform=deform, **tables)
+            assert want["kept"].sum() > 10, "no pixel takes the per-vertex path"
+        stats = []
+        obs, fin = pipeline(mid + [("reproject", form, 0, 8.0, "H"), ("select", "RN", 1.0), ("blit", "R", "H"), ("blit", "RN", "N"),
+                                   ("resample", 1.0, 2, 4.0), ("denoise", "H", 2, True), ("get", "D")], stats=stats)
+        count = np.ascontiguousarray(want["count"], F)
+        assert 0.25 < (count[..., 0] > 0).mean() < 0.98, form
+        xy = select_pixels_ref(count, 1.0)
+        assert [o[1] for o in obs] == ["select", "resample", "get"] and cs.same(obs[0][2], xy) and obs[1][2].tolist() == [len(xy)] and len(xy) > 50
+        assert cs.same(fin["MV"], np.ascontiguousarray(want["motion"], F)) and cs.same(fin["R"], np.ascontiguousarray(want["color"], F)), form
+        s = cs.copy.copy(now)
+        s.pixel_offset, s.seed = cs.frame_uniforms_of(sc, 2)                    # two frames have been dispatched
+        s.num_rays = 2
+        img = pyoracle.Oracle(s).render(mode=0, threads=8)
+        h, n = blend_samples_ref(xy, img[xy[:, 1], xy[:, 0]], np.ascontiguousarray(want["color"], F), count, 1.0, 4.0)
+        assert cs.same(fin["H"], h) and cs.same(fin["N"], n), form
+        d = denoise_ref(h, fin["Gh"], fin["Gn"], fin["Ga"], iterations=2)
+        assert fin["D"].dtype == np.float64 and np.array_equal(fin["D"], d, equal_nan=True) and np.array_equal(obs[2][2], d, equal_nan=True)
+        assert cs.same(d.astype(F), fin["D"]) and not cs.same((d * 1.001).astype(F), fin["D"])       # (the bound `same` holds a denoised image to)
+        assert [k for _, k, _ in stats] == ["reproject", "select", "resample", "denoise"]
+
+
+def test_model_of_queries_and_async_answers():
+    sc = cs.make_scene()
+    ops = [("frame", None), ("radiance_pixels", 3), ("ray_query_async", 9), ("radiance_async", 9), ("deform", 0.75), ("move_spheres", 1),
+           ("frame", None), ("radiance_query", 9), ("ray_query", 9)]
+    obs, _ = pipeline(ops)
+    assert [(i, k) for i, k, _ in obs] == [(1, "radiance_pixels"), (2, "ray_query_async"), (3, "radiance_async"), (7, "radiance_query"), (8, "ray_query")]
+    s1 = cs.copy.copy(sc)
+    s1.pixel_offset, s1.seed = cs.frame_uniforms_of(sc, 1)
+    xy = cs.query_xy(3, sc.width, sc.height)
+    assert cs.same(obs[0][2], pyoracle.Oracle(s1).render(mode=0)[xy[:, 1], xy[:, 0]])        # what the next frame writes to those pixels
+    o, d = cs.query_rays(9)
+    rays = pyoracle.path_rays(o, d, cs.query_pixels(), 0.25)
+    assert cs.same(obs[2][2], pyoracle.radiance(pyoracle.Oracle(s1), rays, 1, 2))               # the scene at the call ...
+    s2 = cs.edited_scene(cs.edited_scene(sc, ops[4]), ops[5])
+    s2.pixel_offset, s2.seed = cs.frame_uniforms_of(sc, 2)
+    assert cs.same(obs[3][2], pyoracle.radiance(pyoracle.Oracle(s2), rays, 1, 2)) and not cs.same(obs[2][2], obs[3][2])     # ... not at the observation
+    early, late = obs[1][2], obs[4][2]
+    orc = pyoracle.Oracle(sc)
+    for j in range(cs.N_QUERIES):
+        r = orc.trace(o[j], d[j])
+        assert cs.same(early[j, :7], np.concatenate([[F(r["distance"])], r["position"], r["normal"]]).astype(F)) and early[j, 7:8].view(np.int32)[0] == r["kind"]
+    assert early.shape == (cs.N_QUERIES, 12) and late.shape == (cs.N_QUERIES, 8)
+    assert not cs.same(early[:, :7], late[:, :7])
+    assert (early[:, 8].view(np.int32)[early[:, 7].view(np.int32) == 3] >= 0).all() and (early[:, 8].view(np.int32)[early[:, 7].view(np.int32) < 2] == -1).all()
+
+
+def test_model_of_the_vertex_buffers():
+    import normals_ref
+    import skin_ref
+    sc, w = cs.make_scene(), cs.pipeline_world()
+    lo, hi = w["span"]
+    v0, n0 = np.asarray(sc.vertices, F).reshape(-1, 3), np.asarray(sc.normals, F).reshape(-1, 3)
+    assert (lo, hi) == cs.blob_span(sc) and cs.same(w["rest_v"][lo: hi + 1], v0[lo: hi + 1]) and not w["rest_v"][hi + 1:].any()
+    assert cs.same(normals_ref.apply(w["plan"], v0), n0[lo: hi + 1])           # the plan recomputes the scene's own normals of the blob
+    ops = [("snapshot",), ("skin", 2, True, lo + 10, 40), ("get_buffer", "V", lo, 60), ("get_buffer", "NB", lo, 60), ("bounds", lo, 60),
+           ("set_host", lo + 30, 30, 1.25), ("set_device", 100, 30, 0.75), ("normals",), ("get_buffer", "SNAP", 0, 144), ("frame", None), ("get", "T0")]
+    obs, fin = pipeline(ops)
+    sl = slice(lo + 10, lo + 50)
+    pos, nrm = skin_ref.skin(v0[sl], n0[sl], w["bone_idx"][sl], w["bone_wgt"][sl], w["poses"][2])
+    v1, n1 = v0.copy(), n0.copy()
+    v1[sl], n1[sl] = pos, nrm
+    assert not cs.same(v1, v0) and cs.same(obs[0][2], v1[lo: lo + 60]) and cs.same(obs[1][2], n1[lo: lo + 60])
+    b = skin_ref.bounds(v1, lo, 60)
+    assert cs.same(obs[2][2], np.concatenate([b[0], b[1], [F(60)]]).astype(F))
+    v2 = v1.copy()
+    for first, count, scale in ((lo + 30, 30, 1.25), (100, 30, 0.75)):
+        part = v2[first: first + count]
+        c = part.mean(axis=0, dtype=np.float64).astype(F)
+        v2[first: first + count] = (c + (part - c) * F(scale)).astype(F)
+    n2 = n1.copy()
+    n2[lo: hi + 1] = normals_ref.apply(w["plan"], v2)
+    assert cs.same(obs[3][2], v0) and cs.same(fin["SNAP"], v0) and cs.same(fin["V"], v2) and cs.same(fin["V.dev"], v2) and cs.same(fin["NB"], n2)
+    s = cs.copy.copy(sc)
+    s.vertices, s.normals = v2, n2
+    s.mesh_bvh = scenes.build_object_bvh(*scenes.mesh_bounds(sc.mesh_objects, v2, sc.indices))
+    assert cs.same(obs[4][2], oracle_frame(s, sc.sky, 0)) and not cs.same(obs[4][2], oracle_frame(sc, sc.sky, 0))
 
 
 def test_model_of_six_plain_frames():
