@@ -55,8 +55,8 @@ URT_API int urt_abi_version(void);                       /* bumps when this head
                                                             resampling, the ranged SetData and the device side of the buffers —
                                                             urt_buffer_set_data_device, urt_buffer_get_data_range,
                                                             urt_skin_vertices, urt_buffer_bounds, urt_debug_buffer_state — the
-                                                            normals on the device, urt_buffer_copy and urt_reproject_deformed
-                                                            were added without changing anything that existed) */
+                                                            normals on the device, urt_buffer_copy, urt_reproject_deformed and
+                                                            urt_upsample were added without changing anything that existed) */
 URT_API int urt_device_count(int* out_count);
 /* One context per process and GPU (the one-process-per-GPU model).  device = HIP ordinal. */
 URT_API int urt_context_create(int device, urt_context** out_ctx);
@@ -647,6 +647,70 @@ URT_API int urt_blend_samples(urt_context* ctx, const void* d_pixels, const void
                               urt_handle count, float max_history);
 URT_API int urt_resample_below(urt_context* ctx, urt_handle dst, urt_handle count, float below, int samples, int bounces, float weight,
                                float max_history, int* out_n);
+
+/* ---- guide-driven upsampling -------------------------------------------------------------- */
+/* Trace at low resolution, present at full: the radiance is accumulated on a small pixel grid (w x h), the pixel-centre feature buffers
+ * of urt_render_aov are rendered on both grids under one camera, and urt_upsample reconstructs the W x H image by a bilinear gather that
+ * takes a low-resolution tap only where both grids saw the same surface.  A pixel no tap can serve gets the count 0, which is what
+ * urt_resample_below fills with full-resolution paths.  The one call of this header that reads images of two sizes: the five low_*
+ * images are RGBA32F textures of one size w x h, the others of one size W x H, row 0 at the bottom; any positive sizes (the low grid may
+ * be the larger one, equal, or in a non-integer ratio).  Count textures as in "temporal reprojection" above.
+ *
+ * Arithmetic (normative), in the style of urt_reproject: float32 with one rounding per operation, no fma, evaluated left to right as
+ * written; division is IEEE.  Per full-grid pixel p = (X, Y): k = normal.w, z = hit.w, P = hit.xyz, n = normal.xyz, o = bits(id.x).
+ *  1. class of p: urt_reproject's step 1 (surface when k != 0, z finite and > 0, P and n finite; sky when k == 0); anything else has no
+ *     result.
+ *  2. position on the low grid: qx = (((float)X + 0.5f) * (float)w) / (float)W - 0.5f, qy likewise from Y, h and H.
+ *  3. stage 1, bilinear: fx, gx, fy, gy, x0, y0, the tap order and the weights exactly as urt_reproject's step 3.  A tap q is valid when
+ *     it is inside the w x h image, its weight is > 0, all four components of low_color[q] are finite, its count n_q is finite and > 0
+ *     (n_q = low_count[q].x, or 1.0f without low_count), and in addition
+ *       sky p: low_normal[q].w == 0;
+ *       surface p: low_normal[q].w == k, bits(low_id[q].x) == o, low_hit[q].w finite and > 0,
+ *                  (n.x*m.x + n.y*m.y) + n.z*m.z >= normal_threshold with m = low_normal[q].xyz, and
+ *                  fabsf((n.x*(Q.x-P.x) + n.y*(Q.y-P.y)) + n.z*(Q.z-P.z)) <= plane_threshold * z with Q = low_hit[q].xyz.
+ *     Sums over the valid taps in tap order from 0.0f: S = sum w, A = sum w*low_color[q] (per component), N = sum w*n_q.  A result
+ *     exists when S >= 0.01f.
+ *  4. stage 2, only with URT_UPSAMPLE_WIDE_FALLBACK and no stage-1 result: the sixteen texels (x0-1+i, y0-1+j), j = 0..3 outer,
+ *     i = 0..3 inner, each with w = 1.0f; validity as in stage 1 without the weight test; the same sums, started again from 0.0f.  A
+ *     result exists when S >= 1.0f.
+ *  5. output: with a result color = A / S per component and count = ((N / S) * count_scale, 0, 0, 0); without one color = (0,0,0,0)
+ *     and count = (0,0,0,0).  For a sky p with a result, with URT_UPSAMPLE_SKY_FROM_ALBEDO and an albedo image, color.rgb is replaced
+ *     by albedo[p].rgb (urt_render_aov's miss value: the sky radiance, exact at full resolution); color.a stays.
+ * Calls, as urt_reproject: an observer — it submits the deferred frames first (low_color is usually a deferred blend's destination), then
+ * enqueues one kernel on the context's stream and returns without synchronising.  The scene is not read (not prepared); urt_counters
+ * are not changed.  params == NULL means the defaults below.  Every argument is checked first: on any error nothing is written and
+ * nothing is enqueued.
+ *  - URT_ERR_INVALID_ARGUMENT: NULL images; unknown flags; a NaN threshold; count_scale not finite or <= 0; low images that are not all
+ *    one size; full images that are not all one size; an output equal to an input or to the other output; an output bound as
+ *    _SkyboxTexture.
+ *  - URT_ERR_INVALID_HANDLE: a required handle that is 0 or unknown, or an optional handle (low_count, albedo, count) that is unknown.
+ * Where the guides should look: a frame's samples of pixel (x, y) are centred on (x + 1, y + 1) (rand + _PixelOffset, RS:448-449), half
+ * a pixel of the image's own grid from the pixel centre URT_AOV_PIXEL_CENTER looks through; half a low pixel is a whole full-grid pixel
+ * at a ratio of 2.  A host that upsamples accumulated frames renders each set of guides with _CameraInverseProjection sheared by half a
+ * pixel of that set's grid (translation column += column 0 / width + column 1 / height) and binds its own matrix again afterwards
+ * (DESIGN.md §22); the call itself takes the guides it is given.
+ * The thresholds start at the reprojection's own; the quality test of tests/test_gpu_upsample.py holds them. */
+enum { URT_UPSAMPLE_WIDE_FALLBACK = 1, URT_UPSAMPLE_SKY_FROM_ALBEDO = 2 };
+typedef struct urt_UpsampleParams {      /* 16 bytes */
+  float normal_threshold;        /* a tap needs dot(n_p, n_q) >= this */
+  float plane_threshold;         /* a tap needs |dot(n_p, Q - P)| <= this * z_p */
+  float count_scale;             /* finite, > 0: out count = tap count * this (a host passes e.g. (w*h)/(W*H)) */
+  int32_t flags;                 /* URT_UPSAMPLE_* */
+} urt_UpsampleParams;
+#define URT_UPSAMPLE_DEFAULT_NORMAL_THRESHOLD 0.9f
+#define URT_UPSAMPLE_DEFAULT_PLANE_THRESHOLD 0.02f
+#define URT_UPSAMPLE_DEFAULT_COUNT_SCALE 1.0f
+#define URT_UPSAMPLE_DEFAULT_FLAGS URT_UPSAMPLE_WIDE_FALLBACK
+
+typedef struct urt_UpsampleImages {      /* 11 handles, 88 bytes */
+  urt_handle low_color, low_count;                 /* w x h: the traced image; low_count optional (0: every texel counts 1.0f) */
+  urt_handle low_hit, low_normal, low_id;          /* w x h: urt_render_aov(URT_AOV_PIXEL_CENTER) on the low grid */
+  urt_handle hit, normal, id;                      /* W x H: the same, on the full grid, same camera */
+  urt_handle albedo;                               /* W x H, optional: read only for sky pixels (its miss value is the sky radiance) */
+  urt_handle color, count;                         /* out, W x H; count optional */
+} urt_UpsampleImages;
+
+URT_API int urt_upsample(urt_context* ctx, const urt_UpsampleImages* images, const urt_UpsampleParams* params);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 typedef struct urt_counters {

@@ -172,6 +172,26 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_reproject_deformed(IntPtr ctx, in ReprojectImages images, in ReprojectParams p, in ReprojectMotion motion, in ReprojectDeform deform);
     [DllImport(Lib)] internal static extern int urt_buffer_copy(IntPtr ctx, ulong src, int srcFirst, ulong dst, int dstFirst, int count);
 
+    // ---- guide-driven upsampling (include/urt.h "guide-driven upsampling"): the low* images have one size, the others another ----
+    internal const int UpsampleWideFallback = 1, UpsampleSkyFromAlbedo = 2;
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct UpsampleParams {                        // urt_UpsampleParams, 16 B
+        public float normalThreshold;
+        public float planeThreshold;
+        public float countScale;                            // finite, > 0
+        public int flags;                                   // Upsample*
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct UpsampleImages {                        // urt_UpsampleImages, 88 B: texture handles; lowCount, albedo, count 0 = not given
+        public ulong lowColor, lowCount;
+        public ulong lowHit, lowNormal, lowId;
+        public ulong hit, normal, id;
+        public ulong albedo;
+        public ulong color, count;
+    }
+    internal const float UpsampleDefaultNormalThreshold = 0.9f, UpsampleDefaultPlaneThreshold = 0.02f, UpsampleDefaultCountScale = 1.0f;
+    [DllImport(Lib)] internal static extern int urt_upsample(IntPtr ctx, in UpsampleImages images, in UpsampleParams p);
+
     // ---- measurement ----------------------------------------------------------------------------------------------------
     [StructLayout(LayoutKind.Sequential)]
     internal struct Counters {

@@ -362,6 +362,54 @@ public static class UrtTemporal {
     }
 }
 
+/// Trace at low resolution, present at full (include/urt.h urt_upsample) over device images the engine owns, all ARGBFloat: the low*
+/// images are lowWidth x lowHeight — the accumulated image, optionally its count texture, and the pixel-centre feature buffers
+/// UrtFeatureBuffers.Render wrote on the low grid — the others width x height: the same feature buffers on the full grid under the same
+/// camera, optionally albedo (the exact sky for sky pixels), and the outputs color and, optionally, count.  A pixel no low-resolution
+/// tap can serve gets colour and count 0: UrtTemporal.ResampleDisocclusions(color, count, width, height, ...) with the full-size texture
+/// bound as Result fills those.  Refresh both sets of feature buffers whenever the camera or the scene moves, each rendered with
+/// _CameraInverseProjection sheared by half a pixel of its grid (include/urt.h "Where the guides should look").  Defaults: include/urt.h
+/// URT_UPSAMPLE_DEFAULT_*.
+public static class UrtUpscaler {
+    static IntPtr boundCtx = IntPtr.Zero;
+    static readonly Dictionary<IntPtr, ulong> wrappedLow = new Dictionary<IntPtr, ulong>(), wrappedFull = new Dictionary<IntPtr, ulong>();
+    static int lw, lh, fw, fh;
+    static ulong Wrap(IntPtr ctx, Dictionary<IntPtr, ulong> wrapped, IntPtr p, int width, int height) {
+        if (p == IntPtr.Zero) return 0;
+        if (!wrapped.TryGetValue(p, out ulong handle)) {
+            UrtDevice.Check(UrtNative.urt_texture_create_external(ctx, width, height, p, out handle));
+            wrapped[p] = handle;
+        }
+        return handle;
+    }
+    public static void Upsample(IntPtr lowColor, IntPtr lowHit, IntPtr lowNormal, IntPtr lowId, int lowWidth, int lowHeight,
+                                IntPtr hit, IntPtr normal, IntPtr id, IntPtr color, int width, int height,
+                                IntPtr count = default(IntPtr), IntPtr lowCount = default(IntPtr), IntPtr albedo = default(IntPtr),
+                                float normalThreshold = 0.9f, float planeThreshold = 0.02f, float countScale = 1.0f,
+                                bool wideFallback = true, bool skyFromAlbedo = false) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtUpscaler: upsample on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        if (boundCtx != ctx || lw != lowWidth || lh != lowHeight || fw != width || fh != height) {   // re-wrapped when the context or a size changes
+            if (boundCtx == ctx) {
+                foreach (ulong t in wrappedLow.Values) UrtDevice.Check(UrtNative.urt_texture_release(ctx, t));
+                foreach (ulong t in wrappedFull.Values) UrtDevice.Check(UrtNative.urt_texture_release(ctx, t));
+            }
+            wrappedLow.Clear(); wrappedFull.Clear();
+            boundCtx = ctx; lw = lowWidth; lh = lowHeight; fw = width; fh = height;
+        }
+        var im = new UrtNative.UpsampleImages {
+            lowColor = Wrap(ctx, wrappedLow, lowColor, lw, lh), lowCount = Wrap(ctx, wrappedLow, lowCount, lw, lh),
+            lowHit = Wrap(ctx, wrappedLow, lowHit, lw, lh), lowNormal = Wrap(ctx, wrappedLow, lowNormal, lw, lh), lowId = Wrap(ctx, wrappedLow, lowId, lw, lh),
+            hit = Wrap(ctx, wrappedFull, hit, fw, fh), normal = Wrap(ctx, wrappedFull, normal, fw, fh), id = Wrap(ctx, wrappedFull, id, fw, fh),
+            albedo = Wrap(ctx, wrappedFull, albedo, fw, fh),
+            color = Wrap(ctx, wrappedFull, color, fw, fh), count = Wrap(ctx, wrappedFull, count, fw, fh) };
+        var p = new UrtNative.UpsampleParams { normalThreshold = normalThreshold, planeThreshold = planeThreshold, countScale = countScale,
+                                               flags = (wideFallback ? UrtNative.UpsampleWideFallback : 0) |
+                                                       (skyFromAlbedo ? UrtNative.UpsampleSkyFromAlbedo : 0) };
+        UrtDevice.Check(UrtNative.urt_upsample(ctx, in im, in p));
+    }
+}
+
 /// new ComputeBuffer(count, stride); .SetData(List<T>); .Release(); .count; .stride            (RM:233-252)
 public sealed class UrtComputeBuffer {
     internal ulong handle;

@@ -1,5 +1,5 @@
 // image_ops.cpp — the entry points of include/urt.h that work on whole images or ray batches next to the frame loop: ray queries,
-// radiance queries, feature buffers, the denoiser, temporal reprojection, resampling.
+// radiance queries, feature buffers, the denoiser, temporal reprojection, guide-driven upsampling, resampling.
 #include "experiments.h"
 #include "context_impl.h"
 
@@ -9,6 +9,7 @@
 #include "denoise.h"
 #include "reproject.h"
 #include "resample.h"
+#include "upsample.h"
 
 using namespace urtd;
 
@@ -423,6 +424,46 @@ int urt_reproject_objects(urt_context* ctx, const urt_ReprojectImages* images, c
 int urt_reproject_deformed(urt_context* ctx, const urt_ReprojectImages* images, const urt_ReprojectParams* params,
                            const urt_ReprojectMotion* motion, const urt_ReprojectDeform* deform) {
   return reproject_impl(ctx, images, params, motion, true, deform);
+}
+
+/* ---- guide-driven upsampling ---- */
+// As urt_reproject: every argument is checked before anything is submitted, then the deferred frames are submitted (low_color is usually
+// a deferred blend's destination) and k_upsample is enqueued on the main stream.  The scene is not read and the counters are not
+// changed.  The one image call with textures of two sizes: the low_* images share one, the others another.
+int urt_upsample(urt_context* ctx, const urt_UpsampleImages* images, const urt_UpsampleParams* params) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (!images) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "upsample: images is NULL");
+  URT_GUARD_BEGIN
+  urt_UpsampleParams P{URT_UPSAMPLE_DEFAULT_NORMAL_THRESHOLD, URT_UPSAMPLE_DEFAULT_PLANE_THRESHOLD, URT_UPSAMPLE_DEFAULT_COUNT_SCALE,
+                       URT_UPSAMPLE_DEFAULT_FLAGS};
+  if (params) P = *params;
+  if (P.flags & ~(URT_UPSAMPLE_WIDE_FALLBACK | URT_UPSAMPLE_SKY_FROM_ALBEDO)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "upsample: unknown flags");
+  if (std::isnan(P.normal_threshold) || std::isnan(P.plane_threshold)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "upsample: a threshold is NaN");
+  if (!std::isfinite(P.count_scale) || !(P.count_scale > 0.0f)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "upsample: count_scale must be finite and > 0");
+  enum { kLow = 5, kInputs = 9, kImages = 11 };                    // the low grid's images, then the full grid's; the outputs last
+  const TexArg a[kImages] = {{images->low_color, "low_color", false}, {images->low_count, "low_count", true}, {images->low_hit, "low_hit", false},
+                             {images->low_normal, "low_normal", false}, {images->low_id, "low_id", false}, {images->hit, "hit", false},
+                             {images->normal, "normal", false}, {images->id, "id", false}, {images->albedo, "albedo", true},
+                             {images->color, "color", false}, {images->count, "count", true}};
+  Texture* t[kImages];
+  if (int rc = resolve_textures(ctx, "upsample", a, kImages, t)) return rc;
+  if (int rc = check_same_size(ctx, "upsample (low grid)", t, kLow)) return rc;
+  if (int rc = check_same_size(ctx, "upsample (full grid)", t + kLow, kImages - kLow)) return rc;
+  if (int rc = check_outputs(ctx, "upsample", a, kInputs, kImages)) return rc;
+  if (int rc = check_height(ctx, "upsample", "full-grid textures", t[kLow]->h)) return rc;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  UpsampleImages I{};                                              // device pointers after the flush (a Result texture may be renamed)
+  I.low_color = t[0]->dev; I.low_count = t[1] ? t[1]->dev : nullptr; I.low_hit = t[2]->dev; I.low_normal = t[3]->dev; I.low_id = t[4]->dev;
+  I.hit = t[5]->dev; I.normal = t[6]->dev; I.id = t[7]->dev; I.albedo = t[8] ? t[8]->dev : nullptr;
+  I.color = t[9]->dev; I.count = t[10] ? t[10]->dev : nullptr;
+  I.low_width = t[0]->w; I.low_height = t[0]->h; I.width = t[kLow]->w; I.height = t[kLow]->h;
+  const UpsampleSettings S{P.normal_threshold, P.plane_threshold, P.count_scale, (P.flags & URT_UPSAMPLE_WIDE_FALLBACK) != 0,
+                           (P.flags & URT_UPSAMPLE_SKY_FROM_ALBEDO) != 0};
+  for (int k = kInputs; k < kImages; k++) if (t[k]) t[k]->other_writes = true;
+  URT_HIP(ctx, launch_upsample(I, S, touch(ctx)));
+  return URT_OK;
+  URT_GUARD_END(ctx)
 }
 
 /* ---- resampling ---- */

@@ -49,6 +49,8 @@ class RayTraceMaster:
     BVHNodeSize = 28             # RM:45
     _normalsPlans = {}           # (the instance's own from __init__ on; here so that host-only use of a master made without one has none to drop)
 
+    _uplow = _upaov = _upcount = _upscaled = _uptarget = None   # (likewise: Upscale's textures)
+
     def __init__(self, ctx: Context, scene: scenes.Scene, rank: int = 0, world_size: int = 1, frame_seed: int = 0x5EED):
         self.ctx = ctx
         self.RayTraceShader = ComputeShader(ctx)
@@ -72,6 +74,9 @@ class RayTraceMaster:
         self.screen_width, self.screen_height = scene.width, scene.height
         self._aov = None                             # RenderFeatureBuffers: (hit, normal, albedo, id) of the screen size
         self._denoised = None                        # Denoise without a destination: the denoised image
+        self._uplow = self._upaov = None             # Upscale: (hit, normal, albedo, id) of the traced and of the presented size, through the sample centres
+        self._upcount = self._upscaled = self._uptarget = None   # Upscale: the count texture, the image (without a destination), fill_holes' Result
+        self.upscaleFilled = 0                       # Upscale(fill_holes=True): the pixels the last call traced at full resolution
         self._temporal = None                        # EnableTemporalAccumulation: the reprojection settings (None = off, the reference's behaviour)
         self._tcount = self._tspare = None           # temporal: the count texture of _converged; the spare (colour, count) pair reprojection writes
         self._taov = None                            # temporal: two (hit, normal, id) sets, the previous and the new camera's
@@ -358,6 +363,95 @@ class RayTraceMaster:
         hit, normal, albedo, _ = self._aov
         self.ctx.denoise(self._converged, destination, hit, normal, albedo, **params)
         return destination
+
+    # Trace at low resolution, present at full (include/urt.h urt_upsample; no counterpart in the reference): the progressive image
+    # `_converged`, traced at screen_width x screen_height, reconstructed at width x height with this master's feature buffers on both
+    # grids as guides, rendered here into textures this master owns, through the centres of the frames' samples rather than the pixel
+    # centres (_sample_centre_projection below; RenderFeatureBuffers' own textures are left as they are).  Opt-in:
+    # Render is untouched and screen_width / screen_height stay the traced size.  Writes into `destination` (width x height), or into a
+    # texture this master owns, and returns it; the per-pixel count goes to a count texture this master owns (_upcount): the low image's
+    # counts with temporal accumulation on, else _currentSample scaled by the ratio of the pixel counts.  Sky pixels take the exact sky
+    # from the full-size albedo buffer.  fill_holes: the pixels left with a count below `below` (1.0: the ones no low-resolution tap
+    # could serve) get one frame's worth of full-resolution paths (urt_resample_below), a full-size texture of this master bound as
+    # Result — Render rebinds its own on the next frame; their number is kept in upscaleFilled.  params: normal_threshold,
+    # plane_threshold, wide_fallback of Context.upsample.  A host calls it per presented frame; both sets of guides are rendered anew
+    # on every call, so a moved camera or scene needs nothing more.
+    def Upscale(self, width: int, height: int, destination: RenderTexture | None = None, fill_holes: bool = False, below: float = 1.0, **params):
+        from ._lib import UrtError
+        from .unity_api import upsample_params, _number_arg
+        if self._converged is None or not self._converged.handle or self._currentSample == 0:
+            raise UrtError(2, "Upscale: no accumulated image yet (render a frame first)")
+        for name, v in (("width", width), ("height", height)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"Upscale: {name} must be an int, not {type(v).__name__}")
+            if v <= 0:
+                raise ValueError(f"Upscale: {name} must be positive, not {v}")
+        width, height = int(width), int(height)
+        if destination is not None and not isinstance(destination, RenderTexture):
+            raise TypeError(f"Upscale: destination must be a RenderTexture or None, not {type(destination).__name__}")
+        if destination is not None and (destination.ctx is not self.ctx or not destination.handle):
+            raise ValueError("Upscale: destination belongs to another context or was released")
+        if destination is not None and (destination.width, destination.height) != (width, height):
+            raise ValueError(f"Upscale: destination is {destination.width} x {destination.height}, not {width} x {height}")
+        if not isinstance(fill_holes, (bool, np.bool_)):
+            raise TypeError(f"Upscale: fill_holes must be a bool, not {type(fill_holes).__name__}")
+        below = _number_arg(below, "below", "Upscale")
+        unknown = set(params) - {"normal_threshold", "plane_threshold", "wide_fallback"}
+        if unknown:
+            raise TypeError(f"Upscale: unknown parameters {sorted(unknown)}")
+        upsample_params(**params)                                                 # checked before anything reaches the library
+        self._bind_for_queries()
+        if self._currentSample == 0:
+            raise UrtError(2, "Upscale: the scene changed and no frame has been rendered since")
+        if self._upaov is None or (self._upaov[0].width, self._upaov[0].height) != (width, height) \
+                or (self._uplow[0].width, self._uplow[0].height) != (self.screen_width, self.screen_height):
+            self._release_upscale()
+            self._uplow = tuple(RenderTexture(self.ctx, self.screen_width, self.screen_height) for _ in range(4))
+            self._upaov = tuple(RenderTexture(self.ctx, width, height) for _ in range(4))
+            self._upcount = RenderTexture(self.ctx, width, height)
+        low_hit, low_normal, _, low_id = self._uplow
+        hit, normal, albedo, ids = self._upaov
+        try:                                                                      # the guides look where the frames' samples are centred
+            self.RayTraceShader.SetMatrix("_CameraInverseProjection", self._sample_centre_projection(self.screen_width, self.screen_height))
+            self.ctx.render_aov(*self._uplow)
+            self.RayTraceShader.SetMatrix("_CameraInverseProjection", self._sample_centre_projection(width, height))
+            self.ctx.render_aov(hit, normal, albedo, ids)
+        finally:
+            self.RayTraceShader.SetMatrix("_CameraInverseProjection", self.scene.camera_inverse_projection)
+        if destination is None:
+            if self._upscaled is None:
+                self._upscaled = RenderTexture(self.ctx, width, height)
+            destination = self._upscaled
+        if self._temporal is not None and self._tcount is not None:
+            counts = {"low_count": self._tcount}
+        else:
+            counts = {"count_scale": float(self._currentSample) * (self.screen_width * self.screen_height) / (width * height)}
+        self.ctx.upsample(self._converged, low_hit, low_normal, low_id, hit, normal, ids, destination, self._upcount, albedo=albedo,
+                          sky_from_albedo=True, **counts, **params)
+        self.upscaleFilled = 0
+        if fill_holes:
+            if self._uptarget is None:
+                self._uptarget = RenderTexture(self.ctx, width, height)
+            self.RayTraceShader.SetTexture(0, "Result", self._uptarget)
+            self.upscaleFilled = self.ctx.resample_below(destination, self._upcount, below, self.numRays, self.numBounces, 1.0, 0.0)
+        return destination
+
+    # A frame places the sample of pixel (x, y) at (x + rand + _PixelOffset.x, y + rand + _PixelOffset.y) with both terms in [0, 1)
+    # (RS:448-449, csrc/camera_device.h jitter_uv): an accumulated image is a tent-filtered view centred on (x + 1, y + 1), half a pixel
+    # OF ITS OWN GRID from the pixel centre (x + 0.5, y + 0.5) that urt_render_aov(URT_AOV_PIXEL_CENTER) looks through.  On a low grid
+    # that half pixel is a whole pixel of the presented image, so guides through the pixel centres would label every low texel with the
+    # surface one presented pixel beside the one it holds.  This is _CameraInverseProjection with the uv moved by half a pixel of a
+    # width x height grid (u = s / width * 2 - 1: 1 / width), so that the pixel-centre ray of (x, y) goes through (x + 1, y + 1).
+    def _sample_centre_projection(self, width: int, height: int) -> np.ndarray:
+        p = np.array(self.scene.camera_inverse_projection, dtype=np.float32).reshape(16).copy()
+        p[12:16] += p[0:4] * np.float32(1.0 / width) + p[4:8] * np.float32(1.0 / height)
+        return p
+
+    def _release_upscale(self):
+        for t in (self._uplow or ()) + (self._upaov or ()) + (self._upcount, self._upscaled, self._uptarget):
+            if t is not None:
+                t.Release()
+        self._uplow = self._upaov = self._upcount = self._upscaled = self._uptarget = None
 
     # RM:760-769: a camera move resets the running mean
     def ResetAccumulation(self):
@@ -886,6 +980,7 @@ class RayTraceMaster:
                 t.Release()
         self._target = self._converged = self.SkyboxTexture = self._denoised = None
         self._aov = None
+        self._release_upscale()
         self._release_temporal()
 
     # ---- multi-GPU frame-end gather (no counterpart in the reference: it is single-GPU) -----------

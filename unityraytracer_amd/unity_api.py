@@ -577,6 +577,34 @@ class Context:
         _max_history_arg(max_history, "blit_add_history")
         self.check(self.lib.urt_blit_add_history(self._h, src.handle, dst.handle, count.handle, float(max_history)))
 
+    def upsample(self, low_color, low_hit, low_normal, low_id, hit, normal, id, color, count=None, low_count=None, albedo=None,
+                 normal_threshold: float = _lib.UPSAMPLE_DEFAULTS["normal_threshold"],
+                 plane_threshold: float = _lib.UPSAMPLE_DEFAULTS["plane_threshold"],
+                 count_scale: float = _lib.UPSAMPLE_DEFAULTS["count_scale"], wide_fallback: bool = True, sky_from_albedo: bool = False):
+        """Guide-driven upsampling (include/urt.h urt_upsample): low_color, traced on a small pixel grid, reconstructed on the full grid
+        -> color, by a bilinear gather that takes a low-resolution tap only where low_hit / low_normal / low_id and hit / normal / id —
+        render_aov's pixel-centre buffers of one camera on the two grids — show the same surface.  count (optional) receives the
+        per-pixel sample count, low_count's (None: 1 per texel) times count_scale; a pixel no tap serves gets colour and count 0
+        (resample_below fills those).  wide_fallback: such a pixel first tries the 4 x 4 low texels around it.  sky_from_albedo: a sky
+        pixel with a result takes its rgb from albedo (render_aov's miss value, the sky radiance).  The low_* RenderTextures have one
+        size, the others another.  Enqueued after the deferred frames; a later GetPixels sees the result."""
+        low = {"low_color": low_color, "low_count": low_count, "low_hit": low_hit, "low_normal": low_normal, "low_id": low_id}
+        full = {"hit": hit, "normal": normal, "id": id, "albedo": albedo, "color": color, "count": count}
+        optional = ("low_count", "albedo", "count")
+        for group, like in ((low, low_color), (full, hit)):
+            for name, t in group.items():
+                if t is None and name in optional:
+                    continue
+                _check_texture(self, "upsample", name, t, like if isinstance(like, RenderTexture) else t, optional=name in optional)
+        images = {**low, **full}
+        for o in ("color", "count"):
+            for name, t in images.items():
+                if images[o] is not None and name != o and t is images[o]:
+                    raise ValueError(f"upsample: the output {o} is also {name}")
+        p = upsample_params(normal_threshold, plane_threshold, count_scale, wide_fallback, sky_from_albedo)
+        im = _lib.UpsampleImages(*(images[n].handle if images[n] is not None else 0 for n, _ in _lib.UpsampleImages._fields_))
+        self.check(self.lib.urt_upsample(self._h, C.byref(im), C.byref(p)))
+
     def select_pixels(self, count, below: float = 1.0):
         """The pixels of the count texture whose count is not >= below (include/urt.h urt_select_pixels), found on the GPU: an (n, 2)
         int32 torch tensor of (x, y) on this context's device, in ascending texel order y * width + x — the list radiance_query_pixels
@@ -735,6 +763,23 @@ def reproject_params(prev_world_to_clip, max_history: float = _lib.REPROJECT_DEF
     nt = _number_arg(normal_threshold, "normal_threshold", "reproject")
     pt = _number_arg(plane_threshold, "plane_threshold", "reproject")
     return _lib.ReprojectParams((C.c_float * 16)(*m.tolist()), mh, nt, pt, 0)
+
+
+def upsample_params(normal_threshold: float = _lib.UPSAMPLE_DEFAULTS["normal_threshold"],
+                    plane_threshold: float = _lib.UPSAMPLE_DEFAULTS["plane_threshold"],
+                    count_scale: float = _lib.UPSAMPLE_DEFAULTS["count_scale"], wide_fallback: bool = True,
+                    sky_from_albedo: bool = False) -> _lib.UpsampleParams:
+    """The checked urt_UpsampleParams of Context.upsample: thresholds that are not NaN, a count_scale that is finite and > 0, two bools."""
+    nt = _number_arg(normal_threshold, "normal_threshold", "upsample")
+    pt = _number_arg(plane_threshold, "plane_threshold", "upsample")
+    cs = _number_arg(count_scale, "count_scale", "upsample")
+    if not (np.isfinite(cs) and cs > 0.0):
+        raise ValueError(f"upsample: count_scale must be finite and > 0, not {cs}")
+    for name, v in (("wide_fallback", wide_fallback), ("sky_from_albedo", sky_from_albedo)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise TypeError(f"upsample: {name} must be a bool, not {type(v).__name__}")
+    flags = (_lib.URT_UPSAMPLE_WIDE_FALLBACK if wide_fallback else 0) | (_lib.URT_UPSAMPLE_SKY_FROM_ALBEDO if sky_from_albedo else 0)
+    return _lib.UpsampleParams(nt, pt, cs, flags)
 
 
 # urt_Ray / urt_RayHit (include/urt_types.h) as numpy records
