@@ -55,8 +55,9 @@ URT_API int urt_abi_version(void);                       /* bumps when this head
                                                             resampling, the ranged SetData and the device side of the buffers —
                                                             urt_buffer_set_data_device, urt_buffer_get_data_range,
                                                             urt_skin_vertices, urt_buffer_bounds, urt_debug_buffer_state — the
-                                                            normals on the device, urt_buffer_copy, urt_reproject_deformed and
-                                                            urt_upsample were added without changing anything that existed) */
+                                                            normals on the device, urt_buffer_copy, urt_reproject_deformed,
+                                                            urt_upsample, urt_auto_exposure and urt_tonemap were added without
+                                                            changing anything that existed) */
 URT_API int urt_device_count(int* out_count);
 /* One context per process and GPU (the one-process-per-GPU model).  device = HIP ordinal. */
 URT_API int urt_context_create(int device, urt_context** out_ctx);
@@ -711,6 +712,86 @@ typedef struct urt_UpsampleImages {      /* 11 handles, 88 bytes */
 } urt_UpsampleImages;
 
 URT_API int urt_upsample(urt_context* ctx, const urt_UpsampleImages* images, const urt_UpsampleParams* params);
+
+/* ---- auto-exposure and tone mapping ------------------------------------------------------- */
+/* The last image-space stage ahead of an 8-bit present: the accumulated image is linear HDR radiance (HDR sky, emissive materials), and
+ * the sRGB table of urt_texture_read_begin_format clamps whatever lies above 1.  urt_auto_exposure meters an RGBA32F image into a
+ * caller-owned state in device memory; urt_tonemap scales an image by that exposure and maps it into [0, 1] with one of three
+ * operators.  The result is an ordinary RGBA32F texture: urt_texture_read_begin_format(..., URT_FORMAT_RGBA8_SRGB) presents it as it
+ * presents any other.  No new formats, no new options.
+ *
+ * Arithmetic (normative): float32 with one rounding per operation, no fma, evaluated left to right as written; division is IEEE; there
+ * are no transcendentals.  bits(f) is the uint32 with the float's bit pattern, float_from_bits its inverse.
+ *
+ * urt_auto_exposure(ctx, src, count, params, d_state): src an RGBA32F texture, count an optional count texture of the same size (0: none;
+ * "temporal reprojection" above), d_state caller-owned device memory, 16-byte aligned, holding a urt_ExposureState.  A zero-filled state
+ * is a fresh one.
+ *  1. per texel (r, g, b, .) of src: Y = (0.2126f*r + 0.7152f*g) + 0.0722f*b.  The texel is skipped, and counted in `skipped`, when Y
+ *     is NaN, infinite or not > 0, or when a count texture is given and !(count.x > 0).  Otherwise it is counted in hist[k] with
+ *     k = clamp((int)(bits(Y) >> 21) - 380, 0, 255): four bins per stop, Y == 1.0f in bin 128, 2^-32 .. 2^32.  counted = the sum of
+ *     hist.  hist, counted and skipped are overwritten by every call.
+ *  2. resolve, in unsigned 64-bit integers: T = counted, lo = T*low_permille/1000, hi = T*high_permille/1000 (floored).  The samples
+ *     whose rank lies in [lo, hi), in ascending bin order, are kept: kept_k = the overlap of [prefix_k, prefix_k + hist[k]) with
+ *     [lo, hi), prefix_k = hist[0] + .. + hist[k-1].  M = hi - lo.  With M == 0 exposure and target are left as they are.  Otherwise
+ *       q = (sum k*kept_k * 256) / M,
+ *       L = float_from_bits((380u << 21) + ((uint32_t)q << 13) + (1u << 20))     (the bin-centre luminance, piecewise-linear in bit space)
+ *       target = fminf(fmaxf(key / L, min_exposure), max_exposure);
+ *     when the previous exposure is not finite, is not > 0, or rate >= 1.0f: exposure = target; otherwise
+ *     exposure = prev + (target - prev) * rate.  A host derives rate from its frame time (the library evaluates no exp).
+ * urt_tonemap(ctx, src, dst, params, d_state): src and dst RGBA32F textures of one size; dst == src is allowed (in place).  d_state is
+ * NULL or a urt_ExposureState in device memory, 16-byte aligned, read on the device (no synchronisation).
+ *  1. s = state.exposure; e = s * params.exposure when s is finite and > 0; e = params.exposure when d_state is NULL or s is not.
+ *  2. per colour channel c: x = c * e; if !(x > 0) x = 0, otherwise x = fminf(x, 65504.0f);
+ *       URT_TONEMAP_LINEAR    y = x
+ *       URT_TONEMAP_REINHARD  w2 = white*white, y = fminf((x * (1.0f + x / w2)) / (1.0f + x), 1.0f)
+ *       URT_TONEMAP_ACES      y = fminf((x*(2.51f*x + 0.03f)) / (x*(2.43f*x + 0.59f) + 0.14f), 1.0f)
+ *     alpha is copied bit for bit.
+ * Calls, as urt_reproject: both are observers — they submit the deferred frames first (src is usually a deferred blend's destination),
+ * then enqueue on the context's stream and return without synchronising; urt_auto_exposure zeroes the histogram itself.  The scene is
+ * not read (not prepared); urt_counters are not changed.  params == NULL means the defaults below.  Every argument is checked first: on
+ * any error nothing is written and nothing is enqueued.
+ *  - urt_auto_exposure, URT_ERR_INVALID_ARGUMENT: d_state NULL or not 16-byte aligned; key, min_exposure or max_exposure not finite or
+ *    <= 0; min_exposure > max_exposure; rate NaN or <= 0; permilles outside 0 <= low < high <= 1000; src and count of different sizes;
+ *    more than 2^31 - 1 texels.
+ *  - urt_tonemap, URT_ERR_INVALID_ARGUMENT: an unknown op; flags other than 0; exposure not finite or <= 0; white outside
+ *    [0.01, 65504]; d_state not 16-byte aligned; src and dst of different sizes; dst bound as _SkyboxTexture.
+ *  - URT_ERR_INVALID_HANDLE: src or dst 0 or unknown; a count that is not 0 and unknown. */
+typedef struct urt_ExposureState {       /* 1040 bytes, in device memory; all zero = fresh */
+  float exposure;                /* the exposure urt_tonemap multiplies by (0 or not finite: none yet) */
+  float target;                  /* what the last metering asked for */
+  uint32_t counted;              /* texels in hist */
+  uint32_t skipped;              /* texels left out */
+  uint32_t hist[256];            /* luminance histogram of the last call, four bins per stop */
+} urt_ExposureState;
+typedef struct urt_ExposureParams {      /* 24 bytes */
+  float key;                     /* the metered luminance is exposed to this value (middle grey) */
+  float min_exposure;            /* finite, > 0 */
+  float max_exposure;            /* finite, >= min_exposure */
+  float rate;                    /* > 0; >= 1 snaps to the target, below it the exposure moves this fraction of the way */
+  int32_t low_permille;          /* the darkest low_permille / 1000 of the counted texels are left out of the mean ... */
+  int32_t high_permille;         /* ... and those above high_permille / 1000; 0 <= low < high <= 1000 */
+} urt_ExposureParams;
+#define URT_EXPOSURE_DEFAULT_KEY 0.18f
+#define URT_EXPOSURE_DEFAULT_MIN_EXPOSURE 0.015625f
+#define URT_EXPOSURE_DEFAULT_MAX_EXPOSURE 64.0f
+#define URT_EXPOSURE_DEFAULT_RATE 1.0f
+#define URT_EXPOSURE_DEFAULT_LOW_PERMILLE 100
+#define URT_EXPOSURE_DEFAULT_HIGH_PERMILLE 950
+
+enum { URT_TONEMAP_LINEAR = 0, URT_TONEMAP_REINHARD = 1, URT_TONEMAP_ACES = 2 };
+typedef struct urt_TonemapParams {       /* 16 bytes */
+  float exposure;                /* finite, > 0: multiplies the state's exposure, or stands alone without one */
+  float white;                   /* 0.01 .. 65504: the x that URT_TONEMAP_REINHARD maps to 1 */
+  int32_t op;                    /* URT_TONEMAP_* */
+  int32_t flags;                 /* 0 */
+} urt_TonemapParams;
+#define URT_TONEMAP_DEFAULT_EXPOSURE 1.0f
+#define URT_TONEMAP_DEFAULT_WHITE 4.0f
+#define URT_TONEMAP_DEFAULT_OP URT_TONEMAP_ACES
+#define URT_TONEMAP_DEFAULT_FLAGS 0
+
+URT_API int urt_auto_exposure(urt_context* ctx, urt_handle src, urt_handle count, const urt_ExposureParams* params, void* d_state);
+URT_API int urt_tonemap(urt_context* ctx, urt_handle src, urt_handle dst, const urt_TonemapParams* params, const void* d_state);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 typedef struct urt_counters {

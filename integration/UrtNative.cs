@@ -192,6 +192,41 @@ internal static class UrtNative {
     internal const float UpsampleDefaultNormalThreshold = 0.9f, UpsampleDefaultPlaneThreshold = 0.02f, UpsampleDefaultCountScale = 1.0f;
     [DllImport(Lib)] internal static extern int urt_upsample(IntPtr ctx, in UpsampleImages images, in UpsampleParams p);
 
+    // ---- auto-exposure and tone mapping (include/urt.h "auto-exposure and tone mapping"): the state lives in device memory ----
+    internal const int TonemapLinear = 0, TonemapReinhard = 1, TonemapAces = 2;
+    internal const int ExposureStateBytes = 1040;
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct ExposureState {                         // urt_ExposureState, 1040 B (what a host downloads from its device memory)
+        public float exposure;
+        public float target;
+        public uint counted;
+        public uint skipped;
+        [MarshalAs(UnmanagedType.ByValArray, SizeConst = 256)]
+        public uint[] hist;
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct ExposureParams {                        // urt_ExposureParams, 24 B
+        public float key;
+        public float minExposure;
+        public float maxExposure;
+        public float rate;
+        public int lowPermille;
+        public int highPermille;
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct TonemapParams {                         // urt_TonemapParams, 16 B
+        public float exposure;
+        public float white;                                 // 0.01 .. 65504
+        public int op;                                      // Tonemap*
+        public int flags;                                   // 0
+    }
+    internal const float ExposureDefaultKey = 0.18f, ExposureDefaultMinExposure = 0.015625f, ExposureDefaultMaxExposure = 64.0f, ExposureDefaultRate = 1.0f;
+    internal const int ExposureDefaultLowPermille = 100, ExposureDefaultHighPermille = 950;
+    internal const float TonemapDefaultExposure = 1.0f, TonemapDefaultWhite = 4.0f;
+    internal const int TonemapDefaultOp = TonemapAces, TonemapDefaultFlags = 0;
+    [DllImport(Lib)] internal static extern int urt_auto_exposure(IntPtr ctx, ulong src, ulong count, in ExposureParams p, IntPtr dState);
+    [DllImport(Lib)] internal static extern int urt_tonemap(IntPtr ctx, ulong src, ulong dst, in TonemapParams p, IntPtr dState);
+
     // ---- measurement ----------------------------------------------------------------------------------------------------
     [StructLayout(LayoutKind.Sequential)]
     internal struct Counters {

@@ -410,6 +410,47 @@ public static class UrtUpscaler {
     }
 }
 
+/// Auto-exposure and tone mapping (include/urt.h urt_auto_exposure / urt_tonemap) over device images the engine owns, all ARGBFloat of
+/// one size: Meter writes the exposure for `src` (RM:12 _converged's RenderTexture; `count` optional, the temporal count texture) into
+/// `state`, UrtNative.ExposureStateBytes of 16-byte aligned device memory the host allocated and zero-filled once; ToneMap writes
+/// operator(src * exposure) into `dst` (may be src; state IntPtr.Zero = params' exposure alone).  Call both every presented frame, then
+/// read `dst` back as RGBA8 sRGB (urt_texture_read_begin_format) in place of the RM:819 blit.  Derive `rate` from the frame time
+/// (1 - exp(-dt / tau)); 1 snaps.  Defaults: include/urt.h URT_EXPOSURE_DEFAULT_*, URT_TONEMAP_DEFAULT_*.
+public static class UrtToneMapper {
+    static IntPtr boundCtx = IntPtr.Zero;
+    static readonly Dictionary<IntPtr, ulong> wrapped = new Dictionary<IntPtr, ulong>();
+    static int w, h;
+    static ulong Wrap(IntPtr ctx, IntPtr p, int width, int height) {  // external textures, re-wrapped when the context or the size changes
+        if (p == IntPtr.Zero) return 0;
+        if (boundCtx != ctx || w != width || h != height) {
+            if (boundCtx == ctx) foreach (ulong t in wrapped.Values) UrtDevice.Check(UrtNative.urt_texture_release(ctx, t));
+            wrapped.Clear();
+            boundCtx = ctx; w = width; h = height;
+        }
+        if (!wrapped.TryGetValue(p, out ulong handle)) {
+            UrtDevice.Check(UrtNative.urt_texture_create_external(ctx, width, height, p, out handle));
+            wrapped[p] = handle;
+        }
+        return handle;
+    }
+    public static void Meter(IntPtr src, int width, int height, IntPtr state, IntPtr count = default(IntPtr),
+                             float key = 0.18f, float minExposure = 0.015625f, float maxExposure = 64.0f, float rate = 1.0f,
+                             int lowPermille = 100, int highPermille = 950) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtToneMapper: meter on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        var p = new UrtNative.ExposureParams { key = key, minExposure = minExposure, maxExposure = maxExposure, rate = rate,
+                                               lowPermille = lowPermille, highPermille = highPermille };
+        UrtDevice.Check(UrtNative.urt_auto_exposure(ctx, Wrap(ctx, src, width, height), Wrap(ctx, count, width, height), in p, state));
+    }
+    public static void ToneMap(IntPtr src, IntPtr dst, int width, int height, IntPtr state = default(IntPtr),
+                               int op = UrtNative.TonemapAces, float exposure = 1.0f, float white = 4.0f) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtToneMapper: tone-map on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        var p = new UrtNative.TonemapParams { exposure = exposure, white = white, op = op, flags = 0 };
+        UrtDevice.Check(UrtNative.urt_tonemap(ctx, Wrap(ctx, src, width, height), Wrap(ctx, dst, width, height), in p, state));
+    }
+}
+
 /// new ComputeBuffer(count, stride); .SetData(List<T>); .Release(); .count; .stride            (RM:233-252)
 public sealed class UrtComputeBuffer {
     internal ulong handle;

@@ -291,6 +291,7 @@ struct urt_context {
   // urt_resample_below: the pixel list and its samples, both sized by the selected count, not by the image
   urtd::DeviceBuf<unsigned int> rs_counts; urtd::PinnedBuf<unsigned int> rs_total;
   urtd::DeviceBuf<urt_PathPixel> rs_pixels; urtd::DeviceBuf<float4> rs_samples;
+  urtd::DeviceBuf<unsigned int> ex_accum;     // urt_auto_exposure: the histogram's accumulators (csrc/tonemap.h), zero whenever no call is in flight
   // Buffer mirrors (context.cpp): what a host SetData changed in a mirrored buffer travels through one of kUpSlots pinned images, used
   // round-robin; a slot is reused once the copy of its previous use has left it (event) — no wait for the stream's other work
   static constexpr int kUpSlots = 4;

@@ -1,5 +1,5 @@
 // image_ops.cpp — the entry points of include/urt.h that work on whole images or ray batches next to the frame loop: ray queries,
-// radiance queries, feature buffers, the denoiser, temporal reprojection, guide-driven upsampling, resampling.
+// radiance queries, feature buffers, the denoiser, temporal reprojection, guide-driven upsampling, auto-exposure and tone mapping, resampling.
 #include "experiments.h"
 #include "context_impl.h"
 
@@ -10,6 +10,7 @@
 #include "reproject.h"
 #include "resample.h"
 #include "upsample.h"
+#include "tonemap.h"
 
 using namespace urtd;
 
@@ -462,6 +463,70 @@ int urt_upsample(urt_context* ctx, const urt_UpsampleImages* images, const urt_U
                            (P.flags & URT_UPSAMPLE_SKY_FROM_ALBEDO) != 0};
   for (int k = kInputs; k < kImages; k++) if (t[k]) t[k]->other_writes = true;
   URT_HIP(ctx, launch_upsample(I, S, touch(ctx)));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+/* ---- auto-exposure and tone mapping ---- */
+// As urt_reproject: every argument is checked before anything is submitted, then the deferred frames are submitted (src is usually a
+// deferred blend's destination) and the kernels of csrc/tonemap.hip are enqueued on the main stream.  The scene is not read and the
+// counters are not changed.  The exposure state is the caller's device memory: the library keeps nothing between the calls.
+int urt_auto_exposure(urt_context* ctx, urt_handle src, urt_handle count, const urt_ExposureParams* params, void* d_state) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  urt_ExposureParams P{URT_EXPOSURE_DEFAULT_KEY, URT_EXPOSURE_DEFAULT_MIN_EXPOSURE, URT_EXPOSURE_DEFAULT_MAX_EXPOSURE,
+                       URT_EXPOSURE_DEFAULT_RATE, URT_EXPOSURE_DEFAULT_LOW_PERMILLE, URT_EXPOSURE_DEFAULT_HIGH_PERMILLE};
+  if (params) P = *params;
+  if (!d_state || ((uintptr_t)d_state & 15u)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "auto_exposure: d_state must be 16-byte aligned device memory");
+  for (const float v : {P.key, P.min_exposure, P.max_exposure})
+    if (!std::isfinite(v) || !(v > 0.0f))
+      return fail(ctx, URT_ERR_INVALID_ARGUMENT, "auto_exposure: key, min_exposure and max_exposure must be finite and > 0");
+  if (P.min_exposure > P.max_exposure) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "auto_exposure: min_exposure is above max_exposure");
+  if (!(P.rate > 0.0f)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "auto_exposure: rate must be > 0");
+  if (!(0 <= P.low_permille && P.low_permille < P.high_permille && P.high_permille <= 1000))
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "auto_exposure: the permilles must satisfy 0 <= low < high <= 1000");
+  const TexArg a[2] = {{src, "src", false}, {count, "count", true}};
+  Texture* t[2];
+  if (int rc = resolve_textures(ctx, "auto_exposure", a, 2, t)) return rc;
+  if (int rc = check_same_size(ctx, "auto_exposure", t, 2)) return rc;
+  const size_t n_texels = (size_t)t[0]->w * (size_t)t[0]->h;
+  if (n_texels > 0x7fffffffull) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "auto_exposure: src has more than 2^31 - 1 texels");
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  if (!ctx->ex_accum) {                                            // the histogram's accumulators: zeroed once, here; every call leaves them zero
+    const size_t words = (size_t)kExposureCopies * (size_t)kExposureWords;
+    if (int rc = reserve(ctx, ctx->ex_accum, words, "auto_exposure: scratch allocation", ctx->stream)) return rc;
+    URT_HIP(ctx, hipMemsetAsync(ctx->ex_accum.get(), 0, words * sizeof(unsigned int), ctx->stream));
+    URT_HIP(ctx, hipStreamSynchronize(ctx->stream));               // (the first call only: whatever stream a later call is issued on finds them zero)
+  }
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  const ExposureSettings S{P.key, P.min_exposure, P.max_exposure, P.rate, P.low_permille, P.high_permille};
+  URT_HIP(ctx, launch_auto_exposure(t[0]->dev, t[1] ? t[1]->dev : nullptr, n_texels, S, ctx->ex_accum.get(), (ExposureState*)d_state,
+                                    touch(ctx)));                  // device pointers after the flush (a Result texture may be renamed)
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+int urt_tonemap(urt_context* ctx, urt_handle src, urt_handle dst, const urt_TonemapParams* params, const void* d_state) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  urt_TonemapParams P{URT_TONEMAP_DEFAULT_EXPOSURE, URT_TONEMAP_DEFAULT_WHITE, URT_TONEMAP_DEFAULT_OP, URT_TONEMAP_DEFAULT_FLAGS};
+  if (params) P = *params;
+  if (P.op != URT_TONEMAP_LINEAR && P.op != URT_TONEMAP_REINHARD && P.op != URT_TONEMAP_ACES)
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "tonemap: unknown op");
+  if (P.flags != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "tonemap: flags must be 0");
+  if (!std::isfinite(P.exposure) || !(P.exposure > 0.0f)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "tonemap: exposure must be finite and > 0");
+  if (!(P.white >= 0.01f && P.white <= 65504.0f)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "tonemap: white must lie in [0.01, 65504]");
+  if ((uintptr_t)d_state & 15u) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "tonemap: d_state must be 16-byte aligned");
+  const TexArg a[2] = {{src, "src", false}, {dst, "dst", false}};
+  Texture* t[2];
+  if (int rc = resolve_textures(ctx, "tonemap", a, 2, t)) return rc;
+  if (int rc = check_same_size(ctx, "tonemap", t, 2)) return rc;
+  if (dst == ctx->t_sky) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "tonemap: dst is the texture bound as _SkyboxTexture");
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  const TonemapSettings S{P.exposure, P.white, P.op};
+  t[1]->other_writes = true;
+  URT_HIP(ctx, launch_tonemap(t[0]->dev, t[1]->dev, (size_t)t[0]->w * (size_t)t[0]->h, S, (const ExposureState*)d_state, touch(ctx)));
   return URT_OK;
   URT_GUARD_END(ctx)
 }

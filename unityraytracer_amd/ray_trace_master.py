@@ -50,6 +50,7 @@ class RayTraceMaster:
     _normalsPlans = {}           # (the instance's own from __init__ on; here so that host-only use of a master made without one has none to drop)
 
     _uplow = _upaov = _upcount = _upscaled = _uptarget = None   # (likewise: Upscale's textures)
+    _exposure = _exposureState = _tonemapped = None             # (likewise: auto-exposure and ToneMap)
 
     def __init__(self, ctx: Context, scene: scenes.Scene, rank: int = 0, world_size: int = 1, frame_seed: int = 0x5EED):
         self.ctx = ctx
@@ -77,6 +78,9 @@ class RayTraceMaster:
         self._uplow = self._upaov = None             # Upscale: (hit, normal, albedo, id) of the traced and of the presented size, through the sample centres
         self._upcount = self._upscaled = self._uptarget = None   # Upscale: the count texture, the image (without a destination), fill_holes' Result
         self.upscaleFilled = 0                       # Upscale(fill_holes=True): the pixels the last call traced at full resolution
+        self._exposure = None                        # EnableAutoExposure: the urt_ExposureParams fields given (None = off)
+        self._exposureState = None                   # EnableAutoExposure: the urt_ExposureState, a torch tensor on the context's device
+        self._tonemapped = None                      # ToneMap without a destination: the tone-mapped image
         self._temporal = None                        # EnableTemporalAccumulation: the reprojection settings (None = off, the reference's behaviour)
         self._tcount = self._tspare = None           # temporal: the count texture of _converged; the spare (colour, count) pair reprojection writes
         self._taov = None                            # temporal: two (hit, normal, id) sets, the previous and the new camera's
@@ -452,6 +456,51 @@ class RayTraceMaster:
             if t is not None:
                 t.Release()
         self._uplow = self._upaov = self._upcount = self._upscaled = self._uptarget = None
+
+    # ---- auto-exposure and tone mapping (include/urt.h urt_auto_exposure / urt_tonemap; no counterpart in the reference, whose
+    # _converged goes to an HDR camera target) ----
+    # Opt-in, for a host that presents 8 bits: ToneMap brings the progressive image `_converged` into [0, 1] — with auto-exposure on it
+    # first meters it (with temporal accumulation on, only the pixels that hold samples) — and writes `destination`, or a texture of
+    # _converged's size this master owns, and returns it; a formatted readback of that texture (RGBA8 sRGB) is the presented frame.
+    # _converged itself is never modified, Render / OnRenderImage are untouched.  params: the fields of urt_ExposureParams; the state
+    # starts fresh, so the first metering snaps to its target whatever `rate` is.
+    def EnableAutoExposure(self, **params):
+        import torch
+        from .unity_api import exposure_params
+        exposure_params(**params)                                                 # checked before anything is created
+        self._exposure = dict(params)
+        self._exposureState = torch.zeros(260, dtype=torch.int32, device=torch.device("cuda", self.ctx.device))   # a urt_ExposureState
+
+    def DisableAutoExposure(self):
+        self._exposure = self._exposureState = None
+
+    def ToneMap(self, destination: RenderTexture | None = None, operator="aces", exposure: float = 1.0, white: float = 4.0):
+        from ._lib import UrtError
+        from .unity_api import tonemap_params
+        if self._converged is None or not self._converged.handle:
+            raise UrtError(2, "ToneMap: no accumulated image yet (render a frame first)")
+        if destination is not None and not isinstance(destination, RenderTexture):
+            raise TypeError(f"ToneMap: destination must be a RenderTexture or None, not {type(destination).__name__}")
+        if destination is not None and (destination.ctx is not self.ctx or not destination.handle):
+            raise ValueError("ToneMap: destination belongs to another context or was released")
+        if destination is self._converged:
+            raise ValueError("ToneMap: destination is the accumulated image")
+        if destination is not None and (destination.width, destination.height) != (self._converged.width, self._converged.height):
+            raise ValueError(f"ToneMap: destination is {destination.width} x {destination.height}, not "
+                             f"{self._converged.width} x {self._converged.height}")
+        params = {"op": operator, "exposure": exposure, "white": white}
+        tonemap_params(**params)                                                  # checked before anything reaches the library
+        if destination is None:
+            if self._tonemapped is None or (self._tonemapped.width, self._tonemapped.height) != (self._converged.width, self._converged.height):
+                if self._tonemapped is not None:
+                    self._tonemapped.Release()
+                self._tonemapped = RenderTexture(self.ctx, self._converged.width, self._converged.height)
+            destination = self._tonemapped
+        if self._exposure is not None:
+            count = self._tcount if self._temporal is not None else None
+            self.ctx.auto_exposure(self._converged, self._exposureState, count, **self._exposure)
+        self.ctx.tonemap(self._converged, destination, self._exposureState if self._exposure is not None else None, **params)
+        return destination
 
     # RM:760-769: a camera move resets the running mean
     def ResetAccumulation(self):
@@ -975,10 +1024,10 @@ class RayTraceMaster:
                 b.Release()
         self._skinBuffers, self._boneBuffers = None, {}
         self._drop_normals_plans()
-        for t in (self._target, self._converged, self.SkyboxTexture, self._denoised) + (self._aov or ()):
+        for t in (self._target, self._converged, self.SkyboxTexture, self._denoised, self._tonemapped) + (self._aov or ()):
             if t is not None:
                 t.Release()
-        self._target = self._converged = self.SkyboxTexture = self._denoised = None
+        self._target = self._converged = self.SkyboxTexture = self._denoised = self._tonemapped = None
         self._aov = None
         self._release_upscale()
         self._release_temporal()

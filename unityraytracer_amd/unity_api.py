@@ -605,6 +605,62 @@ class Context:
         im = _lib.UpsampleImages(*(images[n].handle if images[n] is not None else 0 for n, _ in _lib.UpsampleImages._fields_))
         self.check(self.lib.urt_upsample(self._h, C.byref(im), C.byref(p)))
 
+    def auto_exposure(self, src, state, count=None, **params):
+        """Meters src into an exposure state (include/urt.h urt_auto_exposure): a 256-bin luminance histogram, four bins per stop, the
+        mean bin of the texels whose rank lies between low_permille and high_permille, and the exposure that brings its luminance to
+        `key`, clamped to [min_exposure, max_exposure] and approached at `rate` per call (>= 1: at once).  state: a torch tensor on this
+        context's device, contiguous, at least 1040 bytes, 16-byte aligned (torch.zeros(260, dtype=torch.int32) is a fresh one); it
+        stays on the device — exposure_state downloads it.  count (optional): a count texture of src's size; texels whose count is not
+        > 0 are left out.  params: the fields of urt_ExposureParams (_lib.EXPOSURE_DEFAULTS).  Enqueued after the deferred frames."""
+        _check_texture(self, "auto_exposure", "src", src, src)
+        if count is not None:
+            _check_texture(self, "auto_exposure", "count", count, src, optional=True)
+        if src.width * src.height > 0x7fffffff:
+            raise ValueError("auto_exposure: src has more than 2^31 - 1 texels")
+        p = exposure_params(**params)
+        ptr = self._state_arg(state, "auto_exposure")
+        _sync_torch_stream(state)                                  # the state is written on torch's stream, the metering runs on the library's
+        self.check(self.lib.urt_auto_exposure(self._h, src.handle, count.handle if count is not None else 0, C.byref(p), C.c_void_p(ptr)))
+
+    def tonemap(self, src, dst, state=None, **params):
+        """dst = operator(src * exposure) per colour channel, alpha copied (include/urt.h urt_tonemap); dst may be src.  state: None, or
+        the exposure state auto_exposure wrote, whose exposure multiplies params' on the device (no download).  params: exposure, white,
+        op (an int, _lib.URT_TONEMAP_*, or "linear" / "reinhard" / "aces"), flags of urt_TonemapParams (_lib.TONEMAP_DEFAULTS).
+        Enqueued after the deferred frames; a later GetPixels or formatted read sees the result."""
+        _check_texture(self, "tonemap", "src", src, src)
+        _check_texture(self, "tonemap", "dst", dst, src)
+        p = tonemap_params(**params)
+        ptr = 0
+        if state is not None:
+            ptr = self._state_arg(state, "tonemap")
+            _sync_torch_stream(state)
+        self.check(self.lib.urt_tonemap(self._h, src.handle, dst.handle, C.byref(p), C.c_void_p(ptr)))
+
+    def exposure_state(self, state) -> dict:
+        """The exposure state downloaded (waits for the context's stream): exposure, target, counted, skipped and hist (256 uint32)."""
+        self._state_arg(state, "exposure_state")
+        self.synchronize()
+        raw = state.detach().contiguous().view(-1).cpu().numpy().view(np.uint8)[:C.sizeof(_lib.ExposureState)]
+        s = _lib.ExposureState.from_buffer_copy(raw.tobytes())
+        return {"exposure": float(s.exposure), "target": float(s.target), "counted": int(s.counted), "skipped": int(s.skipped),
+                "hist": np.array(s.hist, dtype=np.uint32)}
+
+    def _state_arg(self, state, who: str) -> int:
+        """The device address of an exposure state: a contiguous torch tensor of >= 1040 bytes on this context's device, 16-byte aligned."""
+        if not _is_torch(state):
+            raise TypeError(f"{who}: state must be a torch tensor on cuda:{self.device}, not {type(state).__name__}")
+        if state.device.type != "cuda" or state.device.index != self.device:
+            raise ValueError(f"{who}: state must be on cuda:{self.device}, not {state.device}")
+        if not state.is_contiguous():
+            raise ValueError(f"{who}: state must be contiguous")
+        nbytes = state.numel() * state.element_size()
+        if nbytes < C.sizeof(_lib.ExposureState):
+            raise ValueError(f"{who}: state holds {nbytes} bytes, a urt_ExposureState has {C.sizeof(_lib.ExposureState)}")
+        ptr = state.data_ptr()
+        if ptr & 15:
+            raise ValueError(f"{who}: state must be 16-byte aligned")
+        return ptr
+
     def select_pixels(self, count, below: float = 1.0):
         """The pixels of the count texture whose count is not >= below (include/urt.h urt_select_pixels), found on the GPU: an (n, 2)
         int32 torch tensor of (x, y) on this context's device, in ascending texel order y * width + x — the list radiance_query_pixels
@@ -782,6 +838,77 @@ def upsample_params(normal_threshold: float = _lib.UPSAMPLE_DEFAULTS["normal_thr
     return _lib.UpsampleParams(nt, pt, cs, flags)
 
 
+def _float32_arg(v, name: str, what: str) -> float:
+    """A number as the float32 the library sees (a value beyond its range becomes inf)."""
+    with np.errstate(over="ignore"):
+        return float(np.float32(_number_arg(v, name, what)))
+
+
+def _int_arg(v, name: str, what: str) -> int:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise TypeError(f"{what}: {name} must be an int, not {type(v).__name__}")
+    return int(v)
+
+
+def exposure_params(**params) -> _lib.ExposureParams:
+    """The checked urt_ExposureParams of Context.auto_exposure: key, min_exposure <= max_exposure finite and > 0, rate > 0,
+    0 <= low_permille < high_permille <= 1000; what is not given is _lib.EXPOSURE_DEFAULTS'."""
+    unknown = set(params) - set(_lib.EXPOSURE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"auto_exposure: unknown parameters {sorted(unknown)}")
+    v = {**_lib.EXPOSURE_DEFAULTS, **params}
+    for name in ("key", "min_exposure", "max_exposure"):
+        v[name] = _float32_arg(v[name], name, "auto_exposure")
+        if not (np.isfinite(v[name]) and v[name] > 0.0):
+            raise ValueError(f"auto_exposure: {name} must be finite and > 0, not {v[name]}")
+    if v["min_exposure"] > v["max_exposure"]:
+        raise ValueError(f"auto_exposure: min_exposure {v['min_exposure']} is above max_exposure {v['max_exposure']}")
+    v["rate"] = _float32_arg(v["rate"], "rate", "auto_exposure")
+    if not v["rate"] > 0.0:
+        raise ValueError(f"auto_exposure: rate must be > 0, not {v['rate']}")
+    lo, hi = (_int_arg(v[name], name, "auto_exposure") for name in ("low_permille", "high_permille"))
+    if not 0 <= lo < hi <= 1000:
+        raise ValueError(f"auto_exposure: the permilles must satisfy 0 <= low < high <= 1000, not {lo} and {hi}")
+    return _lib.ExposureParams(v["key"], v["min_exposure"], v["max_exposure"], v["rate"], lo, hi)
+
+
+TONEMAP_OPERATORS = {"linear": _lib.URT_TONEMAP_LINEAR, "reinhard": _lib.URT_TONEMAP_REINHARD, "aces": _lib.URT_TONEMAP_ACES}
+
+
+def tonemap_params(**params) -> _lib.TonemapParams:
+    """The checked urt_TonemapParams of Context.tonemap: exposure finite and > 0, white in [0.01, 65504], a known op (its number or its
+    name in TONEMAP_OPERATORS), flags 0; what is not given is _lib.TONEMAP_DEFAULTS'."""
+    unknown = set(params) - set(_lib.TONEMAP_DEFAULTS)
+    if unknown:
+        raise TypeError(f"tonemap: unknown parameters {sorted(unknown)}")
+    v = {**_lib.TONEMAP_DEFAULTS, **params}
+    exposure = _float32_arg(v["exposure"], "exposure", "tonemap")
+    if not (np.isfinite(exposure) and exposure > 0.0):
+        raise ValueError(f"tonemap: exposure must be finite and > 0, not {exposure}")
+    white = _float32_arg(v["white"], "white", "tonemap")
+    if not (np.float32(0.01) <= white <= 65504.0):
+        raise ValueError(f"tonemap: white must lie in [0.01, 65504], not {white}")
+    op = v["op"]
+    if isinstance(op, str):
+        if op not in TONEMAP_OPERATORS:
+            raise ValueError(f"tonemap: unknown operator {op!r} (one of {sorted(TONEMAP_OPERATORS)})")
+        op = TONEMAP_OPERATORS[op]
+    op = _int_arg(op, "op", "tonemap")
+    if op not in TONEMAP_OPERATORS.values():
+        raise ValueError(f"tonemap: unknown op {op}")
+    flags = _int_arg(v["flags"], "flags", "tonemap")
+    if flags != 0:
+        raise ValueError(f"tonemap: flags must be 0, not {flags}")
+    return _lib.TonemapParams(exposure, white, op, flags)
+
+
+def _sync_torch_stream(t):
+    """Waits for torch's current stream on the tensor's device: what torch enqueued on it (the tensor's initialisation) is not ordered
+    with the library's stream otherwise."""
+    import torch
+    torch.cuda.current_stream(t.device).synchronize()
+
+
 # urt_Ray / urt_RayHit (include/urt_types.h) as numpy records
 RAY_DT = np.dtype([("origin", np.float32, 3), ("t_max", np.float32), ("direction", np.float32, 3), ("reserved", np.int32)])
 RAYHIT_DT = np.dtype([("distance", np.float32), ("position", np.float32, 3), ("normal", np.float32, 3), ("kind", np.int32),
@@ -795,6 +922,9 @@ PATHPIXEL_DT = np.dtype([("x", np.int32), ("y", np.int32)])
 
 # texels one workgroup of the selection kernels handles (csrc/resample.h kSelectChunk): the sizes at which urt_select_pixels changes path
 SELECT_CHUNK = 2048
+# workgroups (of 256 lanes) the luminance histogram of urt_auto_exposure launches at most (csrc/tonemap.h kExposureMaxBlocks): an image of
+# more texels is grid-strided
+EXPOSURE_MAX_BLOCKS = 1024
 
 
 def _radiance_counts(samples, bounces):
