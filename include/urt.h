@@ -849,6 +849,8 @@ typedef struct urt_counters {
  *                  "top_nodes" (0..256 triangle-BVH nodes kept in LDS; -1 auto, the default: 64, or twice the number of big MeshObjects when the object-level phase is the masked one), "top_front" (-1 auto | 0 | 1: where that top is
  *                  walked), "front_list" (-1 auto | 0 | 1 | 2: multi-mesh scenes determine the objects a ray must test first and work them off in voted
  *                  trips — auto / 1: by mask arithmetic over the heap when it has <= 31 nodes, else as a list when <= 12 MeshObjects; 2: always the list), "lds_tlas" (0/1: small object-level tables in LDS),
+ *                  "front_fuse" (-1 auto, the default = on | 0 | 1: where the object-level phase is the plain one — one MeshObject, or "front_list" 0 — a new ray takes its
+ *                  first object-level step in the trip that created it instead of waiting for a voted trip; same pixels, fewer scheduler trips),
  *          mode 4: "pool_k" (1..4), "pool_refill", "pool_blas_min" (1..256), "pool_blas_exit", "pool_inloop",
  *                  "pool_other_min" (1..64),
  *          "blas_leaf_max" (1..8: triangles per BVH leaf, default 2 or the environment variable URT_BLAS_LEAF_MAX read when the

@@ -514,6 +514,8 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
     P.pool_inloop = ctx->opt.serve_refill;
     int front_mode = configure_sched(ctx, S, P, top_in_front);
     P.shade_split = ctx->opt.shade_split != 0;
+    // plain FRONT: new rays take their first object-level step in the trip that created them; as straight-line code when the mesh heap is one node and there are no spheres
+    P.front_fuse = ctx->opt.front_fuse == 0 ? 0 : (S.n_mesh_tlas == 1 && S.n_meshes > 0 && S.n_spheres == 0 ? 2 : 1);
     const FrameUniforms fu = bound_camera(ctx);                   // the uniforms P's head holds
     // May this dispatch be renamed to a fresh slab slot?  Its unwritten pixels must read as before: none (full cover), or
     // still the zeros of creation (only dispatches of this same region ever wrote the image).

@@ -109,6 +109,44 @@ __device__ __forceinline__ bool trace_front(const DevScene& S, bool fresh, v3 o,
   return false;
 }
 
+// The fresh step of trace_front<COUNT, false> for a scene whose mesh heap is ONE node and that has no spheres (C3: one MeshObject), written
+// straight: the ground plane, the three reciprocals, the slab test of node 0, its cull decision, the root lookup — the operations of the
+// loop's only iteration that does anything, in its order, without the loop, the object-level stack or the `check` / `seen` state.  (A
+// node that is no leaf pushes children 1 and 2, which lie past the heap and pop as nothing: the walk ends with nothing seen, here too.)
+// `cs` leaves as the loop would have left it: height 0, the `tests` flag << 8.  The ground-plane distance that the cull compares with is
+// the one computed two lines above — the same division of the same operands that the loop repeats at the leaf.
+template <bool COUNT>
+__device__ __forceinline__ bool front_single(const DevScene& S, v3 o, v3 d, HitRec& best, int& cs, int32_t& cur, LocalCounters& lc, const FrontLds& L) {
+  best.t = URT_INF; best.kid = 0; best.u = 0; best.v = 0;
+  float t = -o.y / d.y;                                     // IntersectGroundPlane RS:156-172
+  if (t > 0 && t < best.t) { best.t = t; best.kid = 1; }
+  v3 rcp = mk3(1.0f / (d.x + kEPSILON), 1.0f / (d.y + kEPSILON), 1.0f / (d.z + kEPSILON));
+  if (COUNT) lc.tlas_nodes++;
+  float4 a, b;
+  if (L.mesh_tlas) { a = L.mesh_tlas[0]; b = L.mesh_tlas[1]; } else { a = S.mesh_tlas[0]; b = S.mesh_tlas[1]; }
+  const int index = as_int(a.w);
+  bool hit; float t_min = 0.0f, t_max = 0.0f; int cull_word = 0;
+  if (S.cull_any != 0) { hit = tlas_slab_t(a, b, o, rcp, t_min, t_max); cull_word = as_int(b.w); }
+  else hit = tlas_slab(a, b, o, rcp);
+  const bool seen = hit && index >= 0;
+  cs = seen ? 256 : 0;
+  bool culled = false;
+  if (cull_word != 0) culled = tlas_cull(t_min, t_max, t > 0 ? t : URT_INF);
+  if (seen && !culled && index < S.n_meshes) {
+    int32_t root;
+    if (L.mesh_root) root = L.mesh_root[index]; else root = S.mesh_root[index];
+    if (root < 0 && root != kBlasDone) {                    // a mesh of <= 8 triangles is one leaf: tested here
+      int bi_local = -1;
+      if (L.small_tris) test_leaf<COUNT>(S, root, o, d, best, bi_local, lc, L.small_tris, L.small_first[index]);
+      else test_leaf<COUNT>(S, root, o, d, best, bi_local, lc);
+    } else if (root != kEmptyMeshRoot) {
+      cur = root;
+      return true;
+    }
+  }
+  return false;
+}
+
 // FRONT for multi-mesh scenes, "listed" form (front mode 2).  In trace_front<TOPF> the expensive bodies — the inline triangle tests
 // of single-leaf MeshObjects (wall quads: ~150 VALU) and the walk of the LDS-resident top of a big MeshObject's BVH (~60 + 50 per
 // node) — sit INSIDE the per-lane heap-walk loop: every iteration of that loop pays for both whenever any lane of the wave

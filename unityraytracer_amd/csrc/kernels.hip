@@ -42,6 +42,13 @@ namespace {
 // `shade_min` lanes, FRONT, refill from `refill_min` dead lanes) run until at least `blas_min` lanes are parked in
 // BLAS, then the traversal loop runs with that many lanes; it hands control back when fewer than `blas_exit` lanes are
 // still traversing (their stack lives in LDS and the node cursor in registers, so they resume later).
+// In the plain forms (FMODE 0, 1) a new ray does not wait in FRONT for a vote (P.front_fuse, the default): every ray is created at the end
+// of a trip — a bounce ray or a pixel's next ray by SHADE / SKY, a camera ray by the refill at the top of the next one — and its fresh
+// object-level step runs right after the refill, ahead of the vote, for all of them at once.  So with fusing on
+//     DEAD -> (refill + fresh step) -> BLAS | SHADE | SKY;   SHADE / SKY -> (fresh step) -> BLAS | SHADE | SKY | DEAD
+// and FRONT trips are voted only for RESUME.  A scene of one heap node and no spheres (front_fuse 2, FMODE 0) takes the fresh step as
+// straight-line code (front_device.h front_single) and never resumes, so it votes no FRONT trip at all.  Fusing off (option "front_fuse"
+// 0) and the listed and masked forms keep the voted FRONT trip for new rays.
 // A workgroup is 4 such waves that share nothing but read-only LDS copies made in the prologue: the breadth-first top
 // of the BVH forest (a ray entering a mesh walks it on its own, at LDS latency, before it joins the wave-wide loop —
 // inside FRONT when TOPF, i.e. for multi-mesh scenes, else at the start of the BLAS phase) and the small object-level
@@ -156,15 +163,18 @@ __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, Fram
 #endif
     unsigned long long mD = wballot(st == ST_DEAD);
     int nD = __popcll(mD);
-    int nB = __popcll(wballot(st == ST_BLAS));
-    int nS = __popcll(wballot(st == ST_SHADE));
-    int nK = __popcll(wballot(st == ST_SKY));
-    int nF = __popcll(wballot(st == ST_FRONT || st == ST_RESUME));
+    int nB = 0, nS = 0, nK = 0, nF = 0;
+    if (FMODE >= 2) {                // (the plain forms count their lanes below, after the new rays' first step)
+      nB = __popcll(wballot(st == ST_BLAS));
+      nS = __popcll(wballot(st == ST_SHADE));
+      nK = __popcll(wballot(st == ST_SKY));
+      nF = __popcll(wballot(st == ST_FRONT || st == ST_RESUME));
+    }
     // ---- refill dead lanes from the frame's work counter (one atomic per refill): when enough lanes are dead, or when
     // nothing else is left to run.  The atomic takes 2.3 us to return (7.6 % of a wave's time on C3, profiles/r03_logs/r3_stamps_refill.log),
     // but hiding it buys nothing — the SIMDs are busy with the other waves' vector work meanwhile: issuing it a trip early cost +23 % (r3_ab_split_refill.log: lanes stay dead a trip longer), reserving several
     // tiles per atomic +4 % (r3_ab_refill_chunk.log: more live state in the loop). ----
-    if (!exhausted && nD > 0 && (nD >= P.refill_min || nB + nS + nK + nF == 0)) {
+    if (!exhausted && nD > 0 && (nD >= P.refill_min || (FMODE < 2 ? nD == 64 : nB + nS + nK + nF == 0))) {   // (every lane is in exactly one state)
       int x = 0, y = 0, frame = 0;
 #ifdef URT_STAMPS
       unsigned long long t_rf = wall_clock64();
@@ -184,8 +194,26 @@ __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, Fram
 #ifdef URT_STAMPS
       rf_t[1] += wall_clock64() - t_rf; rf_t[2]++;
 #endif
-      nF = __popcll(wballot(st == ST_FRONT || st == ST_RESUME));
-      nD = __popcll(wballot(st == ST_DEAD));
+      if (FMODE >= 2) {
+        nF = __popcll(wballot(st == ST_FRONT || st == ST_RESUME));
+        nD = __popcll(wballot(st == ST_DEAD));
+      }
+    }
+    bool fresh_pass = false;
+    if constexpr (FMODE < 2) {
+      // ---- fused FRONT (P.front_fuse): every ray is born in ST_FRONT in the trip that just ended — a bounce ray or a pixel's next ray at the
+      // end of the SHADE / SKY body, a camera ray in the refill above — and a voted FRONT trip would run for these same lanes (44.6 per FRONT
+      // trip against 44.4 per SHADE trip, profiles/r12_logs/r12_stamps_cones.log).  So their fresh step runs now, without a vote: the FRONT
+      // body below, for the new rays alone, and the lanes count toward `blas_min` in the vote that follows it.  Per ray the same device
+      // function with the same operands as in a voted trip; dead lanes run nothing. ----
+      if (P.front_fuse) { nF = __popcll(wballot(st == ST_FRONT)); fresh_pass = nF > 0; }
+      if (!fresh_pass) {
+        nB = __popcll(wballot(st == ST_BLAS));
+        nS = __popcll(wballot(st == ST_SHADE));
+        nK = __popcll(wballot(st == ST_SKY));
+        nF = __popcll(wballot(st == ST_FRONT || st == ST_RESUME));
+        nD = 64 - (nB + nS + nK + nF);
+      }
     }
     bool can_refill = !exhausted && nD >= P.refill_min;
     if (++wave_iters > P.sched_trips) { watchdog = true; break; }   // an exit every wave reaches, whatever the data
@@ -196,7 +224,8 @@ __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, Fram
     // own thresholds (fuller lanes per trip; pays when FRONT is cheap, i.e. one mesh); otherwise they count together and
     // run back to back in one trip, so that FRONT — the expensive phase of multi-mesh scenes — gets all of them at once.
     bool sky_too = false;
-    if (nB >= P.blas_min) { phase = ST_BLAS; if (nS + nK + nF > 0 || can_refill) exit_below = min(P.blas_exit, nB); }   // <= nB: the phase always advances a lane
+    if (fresh_pass) phase = ST_FRONT;
+    else if (nB >= P.blas_min) { phase = ST_BLAS; if (nS + nK + nF > 0 || can_refill) exit_below = min(P.blas_exit, nB); }   // <= nB: the phase always advances a lane
     else if (P.shade_split) {
       if (nS >= P.shade_min) phase = ST_SHADE;
       else if (nK >= P.sky_min) phase = ST_SKY;
@@ -232,12 +261,16 @@ __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, Fram
           if (r == 1) { best_i = -1; st = ST_BLAS; }
           else st = best.t < URT_INF ? ST_SHADE : ST_SKY;
         }
-      } else if (st == ST_FRONT || st == ST_RESUME) {
+      } else if (st == ST_FRONT || (!fresh_pass && st == ST_RESUME)) {
         sp = 1;
-        int check = cs & 0xff; bool seen = (cs >> 8) != 0;
-        bool need = FMODE == 1 ? trace_front<COUNT, true, false, 1, CONES>(S, st == ST_FRONT, o, d, best, check, seen, tl, 64, cur, lc, L, top, P.top_nodes, bl, &sp)
-                               : trace_front<COUNT, false, false, 1>(S, st == ST_FRONT, o, d, best, check, seen, tl, 64, cur, lc, L);
-        cs = check | (seen ? 256 : 0);
+        bool need;
+        if (FMODE == 0 && fresh_pass && P.front_fuse == 2) need = front_single<COUNT>(S, o, d, best, cs, cur, lc, L);
+        else {
+          int check = cs & 0xff; bool seen = (cs >> 8) != 0;
+          need = FMODE == 1 ? trace_front<COUNT, true, false, 1, CONES>(S, st == ST_FRONT, o, d, best, check, seen, tl, 64, cur, lc, L, top, P.top_nodes, bl, &sp)
+                            : trace_front<COUNT, false, false, 1>(S, st == ST_FRONT, o, d, best, check, seen, tl, 64, cur, lc, L);
+          cs = check | (seen ? 256 : 0);
+        }
         if (need) { best_i = -1; st = ST_BLAS; }
         else st = best.t < URT_INF ? ST_SHADE : ST_SKY;
       }

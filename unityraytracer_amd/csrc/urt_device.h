@@ -78,7 +78,12 @@ struct FrameParams {
                             // instead of the heap itself (scene_prep.cpp build_walk_table); 0 = not in use
   int serve;                // mode 5: the traversal phase is a service shared by the waves of a workgroup (kernels_serve.hip k_serve) (0/1)
   int pool_inloop;          // modes 4, 5: idle lanes that trigger a re-feed of the traversal phase from the waiting rays (1..64)
-  int pool_other_min;       // mode 4: lanes of FRONT / SHADE work that make those phases worth a trip while rays queue for the BVH
+  union {                   // one dword, two modes that never share a launch (a field of its own would move the arguments behind FrameParams in the kernel-argument
+                            // segment, and the masked instantiation of k_sched — which reads neither — compiled differently and measured 0.6 % slower on C5)
+    int pool_other_min;     // mode 4: lanes of FRONT / SHADE work that make those phases worth a trip while rays queue for the BVH
+    int front_fuse;         // mode 3, plain FRONT (front modes 0, 1): a new ray takes its first object-level step in the trip that created it.  0 = it waits for a
+                            // voted FRONT trip; 1 = fused; 2 = fused, and the mesh heap is one node and the scene has no spheres (front_device.h front_single)
+  };
   unsigned int watchdog_steps;  // cap on traversal trips per scheduled BLAS phase: a few times (nodes + leaves) of the scene
   unsigned int sched_trips;     // persistent modes: cap on scheduler trips per wave, scaled with the launch (frames x rays x bounces; frame_batch.cpp)
   unsigned int* trip_flag;      // host-mapped word: a wave that leaves through a cap adds 1 (the next synchronising call reports URT_ERR_WATCHDOG)
