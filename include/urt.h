@@ -56,7 +56,7 @@ URT_API int urt_abi_version(void);                       /* bumps when this head
                                                             urt_buffer_set_data_device, urt_buffer_get_data_range,
                                                             urt_skin_vertices, urt_buffer_bounds, urt_debug_buffer_state — the
                                                             normals on the device, urt_buffer_copy, urt_reproject_deformed,
-                                                            urt_upsample, urt_auto_exposure and urt_tonemap were added without
+                                                            urt_upsample, urt_auto_exposure, urt_tonemap and urt_bloom were added without
                                                             changing anything that existed) */
 URT_API int urt_device_count(int* out_count);
 /* One context per process and GPU (the one-process-per-GPU model).  device = HIP ordinal. */
@@ -792,6 +792,70 @@ typedef struct urt_TonemapParams {       /* 16 bytes */
 
 URT_API int urt_auto_exposure(urt_context* ctx, urt_handle src, urt_handle count, const urt_ExposureParams* params, void* d_state);
 URT_API int urt_tonemap(urt_context* ctx, urt_handle src, urt_handle dst, const urt_TonemapParams* params, const void* d_state);
+
+/* ---- bloom -------------------------------------------------------------------------------- */
+/* The step between the exposure and the tone mapping: an emitter or the sun of an HDR sky lies many stops above white, and after
+ * urt_tonemap it is a hard-edged white disc.  urt_bloom spreads what lies above a threshold over its surroundings, in linear radiance,
+ * which is the only place where energy above 1.0 survives into an 8-bit frame.  A host orders the calls urt_auto_exposure, urt_bloom,
+ * urt_tonemap, formatted readback.  The result is an ordinary RGBA32F texture.  No new formats, no new options.
+ *
+ * Arithmetic (normative): float32 with one rounding per operation, no fma, expressions evaluated as written; division is IEEE; there
+ * are no transcendentals.  Row 0 is the bottom, as everywhere.
+ *
+ * urt_bloom(ctx, src, dst, params, d_state): src and dst RGBA32F textures of one size W x H; dst == src is allowed (in place).  d_state
+ * is NULL or a urt_ExposureState in device memory, 16-byte aligned, read on the device (no synchronisation).
+ *  Exposure.  s = state.exposure; e = s when d_state is given and 2^-60 <= s <= 2^60 (NaN fails that test), otherwise e = 1.
+ *     t = threshold / e, cl = clamp / e, k = t * soft_knee: threshold and clamp are given in exposed units and applied to linear
+ *     radiance.
+ *  Level sizes.  w_0 = W, h_0 = H, w_l = (w_{l-1} + 1) >> 1, h_l likewise; L = min(levels, the first l at which w_l == h_l == 1), so
+ *     L >= 1 always.
+ *  Prefilter, per texel of src, colour channels only (level 0; it is never stored):
+ *       c = (c > 0) ? fminf(c, 65504.0f) : 0                      (NaN, negatives, -0 -> 0; +inf -> 65504)
+ *       m = fmaxf(fmaxf(r, g), b)
+ *       q = fminf(fmaxf((m - t) + k, 0), 2*k);  q = (q*q) / (4*k + 1e-5f)
+ *       g = fmaxf(q, m - t) / fmaxf(m, 1e-5f)
+ *       g = g * fminf(1, cl / fmaxf(m, 1e-5f))
+ *       p = c * g                                                 (per channel)
+ *  Downsample, from level l-1 (a) to level l, for the coarse texel (x, y), with the fine columns x_j = clamp(2x - 1 + j, 0, w_{l-1} - 1),
+ *     j = 0..3, and the fine rows y_j likewise:
+ *       h(row) = (a[x_0] + a[x_3]) + 3*(a[x_1] + a[x_2])          for each of the four rows
+ *       D_l    = ((h(y_0) + h(y_3)) + 3*(h(y_1) + h(y_2))) * 0.015625f
+ *     (the binomial [1 3 3 1]^2 / 64, horizontal first).
+ *  Upsample, from level l+1 (a) to the grid of level l, for the fine texel (x, y): n = x >> 1,
+ *     f = clamp(n + ((x & 1) ? 1 : -1), 0, w_{l+1} - 1), and n_y, f_y likewise for the rows:
+ *       h(row) = 3*a[n] + a[f]
+ *       up     = (3*h(n_y) + h(f_y)) * 0.0625f
+ *     U_L = D_L; U_l = D_l + (up(U_{l+1}) - D_l) * scatter for l = L-1 .. 1.
+ *  Composite, with b = up(U_1) on the W x H grid: each colour channel of dst is src.c + b.c * intensity, with URT_BLOOM_FLAG_ONLY it is
+ *     b.c * intensity.  Alpha is copied bit for bit.  Where a colour channel of src is NaN (without the flag), dst holds a NaN whose
+ *     payload is unspecified; everything else is exact to the bit.
+ * Calls, as urt_tonemap: an observer — it submits the deferred frames first, then enqueues on the context's stream and returns without
+ * synchronising; dst counts as written by others.  The scene is not read (not prepared); urt_counters are not changed.  The pyramid
+ * lives in grow-only scratch of the context.  params == NULL means the defaults below.  Every argument is checked before anything is
+ * enqueued or allocated for the call: on any error nothing is written.
+ *  - URT_ERR_INVALID_ARGUMENT: ctx NULL; threshold not in [0, 65504]; soft_knee or scatter not in [0, 1]; clamp not in (0, 65504];
+ *    intensity not finite or < 0; levels not in 1..16; unknown flag bits; d_state not 16-byte aligned; src and dst of different sizes;
+ *    dst bound as _SkyboxTexture; textures taller than 1048560 pixels.
+ *  - URT_ERR_INVALID_HANDLE: src or dst 0 or unknown. */
+#define URT_BLOOM_FLAG_ONLY 1            /* dst receives the bloom alone, not src + bloom */
+typedef struct urt_BloomParams {         /* 28 bytes */
+  float threshold;               /* 0 .. 65504, in exposed units: what lies below contributes nothing */
+  float soft_knee;               /* 0 .. 1: the width of the quadratic knee below the threshold, as a fraction of it (0: a hard threshold) */
+  float clamp;                   /* > 0 .. 65504, in exposed units: the brightest channel of a prefiltered texel is held to it */
+  float scatter;                 /* 0 .. 1: how much of each coarser level reaches the next finer one (the width of the glow) */
+  float intensity;               /* finite, >= 0: the weight of the bloom in dst */
+  int32_t levels;                /* 1 .. 16: pyramid levels at most (the pyramid ends at 1 x 1) */
+  int32_t flags;                 /* URT_BLOOM_FLAG_* */
+} urt_BloomParams;
+#define URT_BLOOM_DEFAULT_THRESHOLD 1.0f
+#define URT_BLOOM_DEFAULT_SOFT_KNEE 0.5f
+#define URT_BLOOM_DEFAULT_CLAMP 65504.0f
+#define URT_BLOOM_DEFAULT_SCATTER 0.7f
+#define URT_BLOOM_DEFAULT_INTENSITY 0.2f
+#define URT_BLOOM_DEFAULT_LEVELS 6
+#define URT_BLOOM_DEFAULT_FLAGS 0
+
+URT_API int urt_bloom(urt_context* ctx, urt_handle src, urt_handle dst, const urt_BloomParams* params, const void* d_state);
 
 /* ---- measurement -------------------------------------------------------------------------- */
 typedef struct urt_counters {

@@ -227,6 +227,22 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_auto_exposure(IntPtr ctx, ulong src, ulong count, in ExposureParams p, IntPtr dState);
     [DllImport(Lib)] internal static extern int urt_tonemap(IntPtr ctx, ulong src, ulong dst, in TonemapParams p, IntPtr dState);
 
+    // ---- bloom (include/urt.h "bloom"): between the metering and the tone mapping, reads the same exposure state ----
+    internal const int BloomFlagOnly = 1;
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct BloomParams {                           // urt_BloomParams, 28 B
+        public float threshold;                             // 0 .. 65504, in exposed units
+        public float softKnee;                              // 0 .. 1
+        public float clamp;                                 // > 0 .. 65504, in exposed units
+        public float scatter;                               // 0 .. 1
+        public float intensity;                             // finite, >= 0
+        public int levels;                                  // 1 .. 16
+        public int flags;                                   // BloomFlag*
+    }
+    internal const float BloomDefaultThreshold = 1.0f, BloomDefaultSoftKnee = 0.5f, BloomDefaultClamp = 65504.0f, BloomDefaultScatter = 0.7f, BloomDefaultIntensity = 0.2f;
+    internal const int BloomDefaultLevels = 6, BloomDefaultFlags = 0;
+    [DllImport(Lib)] internal static extern int urt_bloom(IntPtr ctx, ulong src, ulong dst, in BloomParams p, IntPtr dState);
+
     // ---- measurement ----------------------------------------------------------------------------------------------------
     [StructLayout(LayoutKind.Sequential)]
     internal struct Counters {

@@ -451,6 +451,37 @@ public static class UrtToneMapper {
     }
 }
 
+/// Bloom (include/urt.h urt_bloom) over device images the engine owns, both ARGBFloat of one size: Apply writes src + intensity * bloom(src)
+/// into `dst` (may be src; bloomOnly: the bloom alone).  `state` is the exposure state UrtToneMapper.Meter wrote (IntPtr.Zero: threshold
+/// and clamp count in linear radiance).  Per presented frame: UrtToneMapper.Meter(src), UrtBloom.Apply(src, dst), UrtToneMapper.ToneMap(dst,
+/// dst), then the RGBA8 sRGB readback of dst.  Defaults: include/urt.h URT_BLOOM_DEFAULT_*.
+public static class UrtBloom {
+    static IntPtr boundCtx = IntPtr.Zero;
+    static readonly Dictionary<IntPtr, ulong> wrapped = new Dictionary<IntPtr, ulong>();
+    static int w, h;
+    static ulong Wrap(IntPtr ctx, IntPtr p, int width, int height) {  // external textures, re-wrapped when the context or the size changes
+        if (boundCtx != ctx || w != width || h != height) {
+            if (boundCtx == ctx) foreach (ulong t in wrapped.Values) UrtDevice.Check(UrtNative.urt_texture_release(ctx, t));
+            wrapped.Clear();
+            boundCtx = ctx; w = width; h = height;
+        }
+        if (!wrapped.TryGetValue(p, out ulong handle)) {
+            UrtDevice.Check(UrtNative.urt_texture_create_external(ctx, width, height, p, out handle));
+            wrapped[p] = handle;
+        }
+        return handle;
+    }
+    public static void Apply(IntPtr src, IntPtr dst, int width, int height, IntPtr state = default(IntPtr),
+                             float threshold = 1.0f, float softKnee = 0.5f, float clamp = 65504.0f, float scatter = 0.7f,
+                             float intensity = 0.2f, int levels = 6, bool bloomOnly = false) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtBloom: bloom on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        var p = new UrtNative.BloomParams { threshold = threshold, softKnee = softKnee, clamp = clamp, scatter = scatter,
+                                            intensity = intensity, levels = levels, flags = bloomOnly ? UrtNative.BloomFlagOnly : 0 };
+        UrtDevice.Check(UrtNative.urt_bloom(ctx, Wrap(ctx, src, width, height), Wrap(ctx, dst, width, height), in p, state));
+    }
+}
+
 /// new ComputeBuffer(count, stride); .SetData(List<T>); .Release(); .count; .stride            (RM:233-252)
 public sealed class UrtComputeBuffer {
     internal ulong handle;

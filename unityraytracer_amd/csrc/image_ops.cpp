@@ -1,5 +1,6 @@
 // image_ops.cpp — the entry points of include/urt.h that work on whole images or ray batches next to the frame loop: ray queries,
-// radiance queries, feature buffers, the denoiser, temporal reprojection, guide-driven upsampling, auto-exposure and tone mapping, resampling.
+// radiance queries, feature buffers, the denoiser, temporal reprojection, guide-driven upsampling, auto-exposure and tone mapping, bloom,
+// resampling.
 #include "experiments.h"
 #include "context_impl.h"
 
@@ -11,6 +12,7 @@
 #include "resample.h"
 #include "upsample.h"
 #include "tonemap.h"
+#include "bloom.h"
 
 using namespace urtd;
 
@@ -527,6 +529,43 @@ int urt_tonemap(urt_context* ctx, urt_handle src, urt_handle dst, const urt_Tone
   const TonemapSettings S{P.exposure, P.white, P.op};
   t[1]->other_writes = true;
   URT_HIP(ctx, launch_tonemap(t[0]->dev, t[1]->dev, (size_t)t[0]->w * (size_t)t[0]->h, S, (const ExposureState*)d_state, touch(ctx)));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+/* ---- bloom ---- */
+// As urt_tonemap: every argument is checked before anything is allocated or submitted, then the pyramid's scratch is grown, the deferred
+// frames are submitted and the kernels of csrc/bloom.hip are enqueued on the main stream.  The scene is not read and the counters are not
+// changed.
+int urt_bloom(urt_context* ctx, urt_handle src, urt_handle dst, const urt_BloomParams* params, const void* d_state) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  urt_BloomParams P{URT_BLOOM_DEFAULT_THRESHOLD, URT_BLOOM_DEFAULT_SOFT_KNEE, URT_BLOOM_DEFAULT_CLAMP, URT_BLOOM_DEFAULT_SCATTER,
+                    URT_BLOOM_DEFAULT_INTENSITY, URT_BLOOM_DEFAULT_LEVELS, URT_BLOOM_DEFAULT_FLAGS};
+  if (params) P = *params;
+  if (!(P.threshold >= 0.0f && P.threshold <= 65504.0f)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "bloom: threshold must lie in [0, 65504]");
+  if (!(P.soft_knee >= 0.0f && P.soft_knee <= 1.0f)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "bloom: soft_knee must lie in [0, 1]");
+  if (!(P.clamp > 0.0f && P.clamp <= 65504.0f)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "bloom: clamp must lie in (0, 65504]");
+  if (!(P.scatter >= 0.0f && P.scatter <= 1.0f)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "bloom: scatter must lie in [0, 1]");
+  if (!std::isfinite(P.intensity) || !(P.intensity >= 0.0f)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "bloom: intensity must be finite and >= 0");
+  if (P.levels < 1 || P.levels > kBloomMaxLevels) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "bloom: levels must be 1..16");
+  if (P.flags & ~URT_BLOOM_FLAG_ONLY) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "bloom: unknown flag bits");
+  if ((uintptr_t)d_state & 15u) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "bloom: d_state must be 16-byte aligned");
+  const TexArg a[2] = {{src, "src", false}, {dst, "dst", false}};
+  Texture* t[2];
+  if (int rc = resolve_textures(ctx, "bloom", a, 2, t)) return rc;
+  if (int rc = check_same_size(ctx, "bloom", t, 2)) return rc;
+  if (dst == ctx->t_sky) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "bloom: dst is the texture bound as _SkyboxTexture");
+  const int width = t[0]->w, height = t[0]->h;
+  if (int rc = check_height(ctx, "bloom", "textures", height)) return rc;
+  if (width > kBloomMaxExtent) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "bloom: textures wider than 2^30 pixels");
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = reserve(ctx, ctx->bl_pyramid, bloom_levels(width, height, P.levels).texels, "bloom: scratch allocation", ctx->stream)) return rc;
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  const BloomSettings S{P.threshold, P.soft_knee, P.clamp, P.scatter, P.intensity, P.levels, P.flags};
+  t[1]->other_writes = true;
+  URT_HIP(ctx, launch_bloom(t[0]->dev, t[1]->dev, width, height, S, (const ExposureState*)d_state, ctx->bl_pyramid.get(), touch(ctx)));
+                                                                   // (device pointers after the flush: a Result texture may be renamed)
   return URT_OK;
   URT_GUARD_END(ctx)
 }

@@ -51,6 +51,7 @@ class RayTraceMaster:
 
     _uplow = _upaov = _upcount = _upscaled = _uptarget = None   # (likewise: Upscale's textures)
     _exposure = _exposureState = _tonemapped = None             # (likewise: auto-exposure and ToneMap)
+    _bloom = None                                               # (likewise: EnableBloom)
 
     def __init__(self, ctx: Context, scene: scenes.Scene, rank: int = 0, world_size: int = 1, frame_seed: int = 0x5EED):
         self.ctx = ctx
@@ -81,6 +82,7 @@ class RayTraceMaster:
         self._exposure = None                        # EnableAutoExposure: the urt_ExposureParams fields given (None = off)
         self._exposureState = None                   # EnableAutoExposure: the urt_ExposureState, a torch tensor on the context's device
         self._tonemapped = None                      # ToneMap without a destination: the tone-mapped image
+        self._bloom = None                           # EnableBloom: the urt_BloomParams fields given (None = off)
         self._temporal = None                        # EnableTemporalAccumulation: the reprojection settings (None = off, the reference's behaviour)
         self._tcount = self._tspare = None           # temporal: the count texture of _converged; the spare (colour, count) pair reprojection writes
         self._taov = None                            # temporal: two (hit, normal, id) sets, the previous and the new camera's
@@ -474,6 +476,17 @@ class RayTraceMaster:
     def DisableAutoExposure(self):
         self._exposure = self._exposureState = None
 
+    # Bloom (include/urt.h urt_bloom), opt-in as well: with it on, ToneMap puts _converged + bloom into its destination (threshold and
+    # clamp in the units of the metered exposure when auto-exposure is on) and tone-maps the destination in place; with it off ToneMap
+    # enqueues what it always did.  params: the fields of urt_BloomParams.  Nothing is created here: the pyramid is the context's scratch.
+    def EnableBloom(self, **params):
+        from .unity_api import bloom_params
+        bloom_params(**params)                                                    # checked at once
+        self._bloom = dict(params)
+
+    def DisableBloom(self):
+        self._bloom = None
+
     def ToneMap(self, destination: RenderTexture | None = None, operator="aces", exposure: float = 1.0, white: float = 4.0):
         from ._lib import UrtError
         from .unity_api import tonemap_params
@@ -499,7 +512,12 @@ class RayTraceMaster:
         if self._exposure is not None:
             count = self._tcount if self._temporal is not None else None
             self.ctx.auto_exposure(self._converged, self._exposureState, count, **self._exposure)
-        self.ctx.tonemap(self._converged, destination, self._exposureState if self._exposure is not None else None, **params)
+        state = self._exposureState if self._exposure is not None else None
+        source = self._converged
+        if self._bloom is not None:
+            self.ctx.bloom(self._converged, destination, state, **self._bloom)
+            source = destination
+        self.ctx.tonemap(source, destination, state, **params)
         return destination
 
     # RM:760-769: a camera move resets the running mean

@@ -636,6 +636,22 @@ class Context:
             _sync_torch_stream(state)
         self.check(self.lib.urt_tonemap(self._h, src.handle, dst.handle, C.byref(p), C.c_void_p(ptr)))
 
+    def bloom(self, src, dst, state=None, **params):
+        """dst = src + intensity * bloom(src) per colour channel, alpha copied (include/urt.h urt_bloom); dst may be src.  The bloom is
+        what lies above `threshold` (soft below it over `soft_knee`, held to `clamp`), taken down a pyramid of at most `levels` halved
+        levels and back up, each coarser level reaching the next finer one by `scatter`.  state: None, or the exposure state
+        auto_exposure wrote: threshold and clamp then count in exposed units, divided by its exposure on the device (no download).
+        params: the fields of urt_BloomParams (_lib.BLOOM_DEFAULTS); flags _lib.URT_BLOOM_FLAG_ONLY leaves src out of dst.  Enqueued
+        after the deferred frames, ahead of tonemap."""
+        _check_texture(self, "bloom", "src", src, src)
+        _check_texture(self, "bloom", "dst", dst, src)
+        p = bloom_params(**params)
+        ptr = 0
+        if state is not None:
+            ptr = self._state_arg(state, "bloom")
+            _sync_torch_stream(state)
+        self.check(self.lib.urt_bloom(self._h, src.handle, dst.handle, C.byref(p), C.c_void_p(ptr)))
+
     def exposure_state(self, state) -> dict:
         """The exposure state downloaded (waits for the context's stream): exposure, target, counted, skipped and hist (256 uint32)."""
         self._state_arg(state, "exposure_state")
@@ -900,6 +916,32 @@ def tonemap_params(**params) -> _lib.TonemapParams:
     if flags != 0:
         raise ValueError(f"tonemap: flags must be 0, not {flags}")
     return _lib.TonemapParams(exposure, white, op, flags)
+
+
+def bloom_params(**params) -> _lib.BloomParams:
+    """The checked urt_BloomParams of Context.bloom: threshold in [0, 65504], soft_knee and scatter in [0, 1], clamp in (0, 65504],
+    intensity finite and >= 0, levels 1..16, flags 0 or _lib.URT_BLOOM_FLAG_ONLY; what is not given is _lib.BLOOM_DEFAULTS'."""
+    unknown = set(params) - set(_lib.BLOOM_DEFAULTS)
+    if unknown:
+        raise TypeError(f"bloom: unknown parameters {sorted(unknown)}")
+    v = {**_lib.BLOOM_DEFAULTS, **params}
+    for name in ("threshold", "soft_knee", "clamp", "scatter", "intensity"):
+        v[name] = _float32_arg(v[name], name, "bloom")
+    if not 0.0 <= v["threshold"] <= 65504.0:
+        raise ValueError(f"bloom: threshold must lie in [0, 65504], not {v['threshold']}")
+    for name in ("soft_knee", "scatter"):
+        if not 0.0 <= v[name] <= 1.0:
+            raise ValueError(f"bloom: {name} must lie in [0, 1], not {v[name]}")
+    if not 0.0 < v["clamp"] <= 65504.0:
+        raise ValueError(f"bloom: clamp must lie in (0, 65504], not {v['clamp']}")
+    if not (np.isfinite(v["intensity"]) and v["intensity"] >= 0.0):
+        raise ValueError(f"bloom: intensity must be finite and >= 0, not {v['intensity']}")
+    levels, flags = (_int_arg(v[name], name, "bloom") for name in ("levels", "flags"))
+    if not 1 <= levels <= 16:
+        raise ValueError(f"bloom: levels must be 1..16, not {levels}")
+    if flags & ~_lib.URT_BLOOM_FLAG_ONLY:
+        raise ValueError(f"bloom: unknown flag bits in {flags}")
+    return _lib.BloomParams(v["threshold"], v["soft_knee"], v["clamp"], v["scatter"], v["intensity"], levels, flags)
 
 
 def _sync_torch_stream(t):
