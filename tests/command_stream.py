@@ -62,7 +62,28 @@ NormalsPlan of the blob's span made at the start.  Its ops, besides the ones abo
     ("ray_query_async", seed) / ("radiance_async", seed)   the device entry points on torch tensors, not waited for: observed (under the
                                        op's own index) just before the next op of OBSERVERS or at the end, after ctx.synchronize() —
                                        the model answers with the scene as it was at the call
-The library refuses an output that is the bound sky or one of the call's inputs and resample_below while H or N is the sky."""
+The library refuses an output that is the bound sky or one of the call's inputs and resample_below while H or N is the sky.
+
+The "display" profile (profile="display") adds the display calls to the pipeline profile: every op above, and guide-driven upsampling,
+auto-exposure, tone mapping and bloom.  More textures: a LOW GRID, a third size class — Lc (colour), Ln (count), Lh, Lm (normal), Li
+(id), low_size(width, height) = 24 x 16 under the 64 x 40 frame, so that neither ratio is an integer — and the frame-sized U / UN
+(upsampled colour and count).  Two EXPOSURE STATES E0, E1: torch.zeros(260, dtype=torch.int32) on the context's device, in the model
+the dict tests/tonemap_ref.py passes around; the master's own state is "MS" (it starts with EnableAutoExposure(rate=0.5)) and the
+texture it owns "TM" (all zero until the first ToneMap without a destination makes it).  A state is observed and compared as
+state_words: exposure and target as bits, counted, skipped and the 256 bins as integers.  Its ops:
+    ("aov_low", frame_ray)             ctx.render_aov(Lh, Lm, Lc, Li): the albedo target doubles as the low colour
+    ("upsample", color, count | None, with_low_count, flags)   ctx.upsample(Lc, Lh, Lm, Li, Gh, Gn, Gi, color, count, low_count=Ln if
+                                       with_low_count, albedo=Ga if flags has SKY_FROM_ALBEDO); flags over WIDE_FALLBACK | SKY_FROM_ALBEDO
+    ("meter", src, k, with_count, j)   ctx.auto_exposure(src, E_k, count=N if with_count, **METER[j]); src of any size class
+    ("tonemap", src, dst, k | None, op, exposure)   ctx.tonemap(src, dst, E_k, op=op, exposure=exposure); dst may be src
+    ("bloom", src, dst, k | None, levels, flags)    ctx.bloom(src, dst, E_k, levels=levels, flags=flags); dst may be src
+    ("state_get", k)                   observer: ctx.exposure_state(E_k)
+    ("state_reset", k)                 ctx.synchronize(); E_k.zero_() — see run_gpu: the wait is the caller's part of the contract
+    ("master_bloom", on)               EnableBloom(**MASTER_BLOOM) | DisableBloom()
+    ("present_tm", dest | None, operator)   m.ToneMap(dest, operator): meter C into MS, bloom C into dest with MS if bloom is on, tone-map
+                                       with MS; None = the texture the master owns, "TM" to ("get", "TM") and in the final contents
+The library refuses a tonemap / bloom destination that is the bound sky, textures of two sizes in one of these calls (upsample: within
+either grid), a count image for a source of another size, and ToneMap into _converged."""
 import copy
 
 import numpy as np
@@ -76,7 +97,7 @@ ALL_TEX = FRAME_TEX + SKY_TEX
 FORMATS = ("RGBA32F", "RGBA8_SRGB", "RGBA16F")
 KINDS = ("frame", "dispatch", "blit", "history", "setpixels", "restart", "bind_sky", "bind_result", "move_mesh", "deform", "move_spheres",
          "camera", "flush", "ptr", "get", "read_begin", "read_end", "ray_query", "radiance_query")
-SUBMITTING = ("flush", "get", "read_begin", "setpixels", "ptr")   # ops that always submit the deferred frames themselves
+SUBMITTING = ("flush", "get", "read_begin", "setpixels", "ptr", "state_reset")   # ops that always submit the deferred frames themselves
 WRITER_KINDS = ("blend", "history", "present", "blit", "dispatch", "setpixels")      # what can have written a texture last (coverage)
 FRAME_SEED = 0x5EED
 N_QUERIES = 64
@@ -94,16 +115,57 @@ BUFFERS = ("V", "NB", "SNAP")
 NEW_KINDS = ("aov", "aov_into", "reproject", "denoise", "select", "resample", "radiance_pixels", "skin", "normals", "set_device", "set_host",
              "snapshot", "get_buffer", "bounds", "ray_query_async", "radiance_async")
 PIPE_KINDS = KINDS + NEW_KINDS
-OBSERVERS = ("get", "read_end", "ray_query", "radiance_query", "select", "resample", "radiance_pixels", "get_buffer", "bounds")
+OBSERVERS = ("get", "read_end", "ray_query", "radiance_query", "select", "resample", "radiance_pixels", "get_buffer", "bounds", "state_get")
 IMAGE_OPS = ("aov", "aov_into", "reproject", "denoise", "select", "resample")
 VERTEX_WRITES = ("skin", "normals", "set_device", "set_host")    # in-place writes of V / NB (the last one through the host copy)
 SCENE_CHANGES = ("move_mesh", "deform", "move_spheres") + VERTEX_WRITES
 POSE_ANGLES = (25.0, -40.0, 60.0)
 FORMS = ("plain", "objects", "deformed")
+# the display profile
+LOW_TEX = ("Lc", "Ln", "Lh", "Lm", "Li")                         # the low grid: colour, count, hit, normal, id
+UP_TEX = ("U", "UN")
+STATES = ("E0", "E1")
+DISPLAY_FRAME_TEX = EXACT_TEX + UP_TEX
+DISPLAY_EXACT = DISPLAY_FRAME_TEX + SKY_TEX + LOW_TEX            # what a display call may read: every texture but D
+DISPLAY_KINDS = ("aov_low", "upsample", "meter", "tonemap", "bloom", "state_get", "state_reset", "master_bloom", "present_tm")
+DISP_KINDS = PIPE_KINDS + DISPLAY_KINDS
+DISPLAY_IMAGE_OPS = ("upsample", "meter", "tonemap", "bloom", "present_tm")
+DISPLAY_WRITERS = ("upsample", "tonemap", "bloom")
+WIDE_FALLBACK, SKY_FROM_ALBEDO, BLOOM_ONLY = 1, 2, 1             # URT_UPSAMPLE_WIDE_FALLBACK, _SKY_FROM_ALBEDO; URT_BLOOM_FLAG_ONLY
+TONEMAP_OPS = ("linear", "reinhard", "aces")                     # in the order of URT_TONEMAP_*
+METER = (dict(rate=1.0), dict(rate=0.25), dict(rate=0.5, key=0.25, low_permille=300, high_permille=800), dict(rate=0.5))
+MASTER_EXPOSURE, MASTER_BLOOM = dict(rate=0.5), dict(levels=3)
+STATE_WORDS = 260
 
 
 def size_class(name):
-    return 1 if name in SKY_TEX else 0
+    return 1 if name in SKY_TEX else 2 if name in LOW_TEX else 0
+
+
+def low_size(width, height):
+    """The low grid under a width x height frame: 24 x 16 under 64 x 40."""
+    return width * 3 // 8, height * 2 // 5
+
+
+def pyramid_texels(width, height, levels):
+    """The texels of the levels urt_bloom keeps for a width x height image (include/urt.h "bloom": w_l = (w_{l-1} + 1) >> 1)."""
+    import bloom_ref
+    return sum(w * h for w, h in bloom_ref.level_sizes(width, height, levels))
+
+
+def fresh_state():
+    import tonemap_ref
+    return dict(tonemap_ref.FRESH, hist=tonemap_ref.FRESH["hist"].copy())
+
+
+def state_words(s):
+    """An exposure state (the dict of tests/tonemap_ref.py and of Context.exposure_state) as the 260 words of urt_ExposureState:
+    exposure and target as bits, counted, skipped and the bins as integers."""
+    out = np.zeros(STATE_WORDS, np.uint32)
+    out[:2] = np.array([s["exposure"], s["target"]], F).view(np.uint32)
+    out[2], out[3] = s["counted"], s["skipped"]
+    out[4:] = s["hist"]
+    return out
 
 
 # ---- the world ----------------------------------------------------------------------------------------------------------------------
@@ -325,9 +387,12 @@ def _draw(rng, kind, tr):
 def make_program(seed, n_ops=40, profile="frames"):
     """About n_ops ops, deterministic per seed.  The plain draw is biased towards the cases the suite exists for: a texture that has just
     been written is bound as the sky and traced at once (every writer kind), readbacks and scene edits land between frames.
-    profile="pipeline": make_pipeline_program (the programs of the default profile are what they were before it existed)."""
+    profile="pipeline": make_pipeline_program, profile="display": make_display_program (the programs of a profile are what they were
+    before the next one existed)."""
     if profile == "pipeline":
         return make_pipeline_program(seed, n_ops)
+    if profile == "display":
+        return make_display_program(seed, n_ops)
     assert profile == "frames", profile
     rng = np.random.default_rng(seed)
     kinds = list(_WEIGHTS)
@@ -495,6 +560,60 @@ def _draw_pipeline(rng, kind, tr, nv, span):
     return _draw(rng, kind, tr)                                  # snapshot and normals have no argument
 
 
+def _pipeline_followers(rng, op, result, tr, draw, span, nv):
+    """What the pipeline profile plays right behind `op` (just emitted; `result` = the Result texture bound when it ran): a list of
+    ops and of callables that draw one when their turn comes.  Draws from rng exactly what make_pipeline_program always drew here."""
+    lo, hi = span
+    pick = lambda names: names[int(rng.integers(len(names)))]
+    k, r = op[0], rng.random()
+    written = [t for t, _ in pipeline_writes_of(op, result)]
+    forced = []
+    if k == "history" and r < 0.6:                           # the temporal step
+        prev, form = tr.camera, pick(FORMS)
+        other = ("camera", (prev + 1 + int(rng.integers(len(CAMERA_POSITIONS) - 1))) % len(CAMERA_POSITIONS))
+        change = {"plain": other, "objects": pick((("move_mesh", 1, int(rng.integers(3))), ("move_spheres", int(rng.integers(3))))),
+                  "deformed": pick((("deform", 0.9), ("skin", int(rng.integers(3)), True, lo, hi - lo + 1), ("set_device", lo, 40, 1.25)))}[form]
+        forced = [("aov", "P", 11, False)] + ([("snapshot",)] if form == "deformed" else []) + [change] + \
+                 ([other] if form != "plain" and rng.random() < 0.6 else []) + [("aov", "G", 15, False),
+                  ("reproject", form, prev, float(pick((8.0, 64.0))), "H"), ("select", "RN", float(pick((1.0, 2.0))))]
+        if rng.random() < 0.5:
+            forced += [("blit", "R", "H"), ("blit", "RN", "N"), ("resample", 2.0, 1, 0.0), ("frame", "X0")]
+    elif k in ("ray_query_async", "radiance_async") and r < 0.65:
+        forced = [pick((("deform", 0.9), ("skin", int(rng.integers(3)), False, lo, hi - lo + 1), ("set_device", lo + 10, 50, 0.75),
+                        ("move_mesh", 0, int(rng.integers(3))), ("set_host", lo, 30, 1.25)))]
+        if rng.random() < 0.5:
+            forced.append(("frame", None))
+    elif k in ("skin", "set_device", "normals") and r < 0.45:
+        forced = [("frame", pick((None, "X0")))]
+    elif k in ("skin", "set_device") and r < 0.8:            # a host write over part of what the device wrote, then read back
+        first = op[3] if k == "skin" else op[1]
+        forced = [("set_host", first, 8, 0.9), pick((("get_buffer", "V", first, 24), ("bounds", first, 24)))]
+    elif k == "set_host" and r < 0.4:                        # a run of host uploads into the mirrored buffer
+        forced = [lambda: draw("set_host") for _ in range(int(rng.integers(2, 8)))] + [pick((("frame", None), ("get_buffer", "V", 0, nv)))]
+    elif k == "frame" and r < 0.15:
+        forced = [("aov_into", result), ("frame", None)]
+    elif k in ("frame", "dispatch") and r < 0.35:            # something between two frames of what would be one batch
+        forced = [pick((lambda: draw("skin"), lambda: draw("set_device"), lambda: draw("set_host"), ("normals",), ("deform", 0.9),
+                        ("get", "C"), ("ray_query_async", 7), ("radiance_pixels", 7), ("aov", "G", 15, False))), ("frame", None)]
+    elif written and r < 0.75:                               # written -> read by an image operation, nothing in between
+        t = written[int(rng.integers(len(written)))]
+        if t in ("H", "N"):
+            forced = [pick((lambda: draw("select")[:1] + ("N",) + draw("select")[2:], lambda: draw("resample"),
+                            lambda: draw("reproject")[:4] + ("H",)))]
+        elif t in ("R", "RN", "MV"):
+            forced = [pick((("select", "RN", 1.0), ("denoise", "R", 2, True), ("bind_sky", "R")))]
+            if forced[0][0] == "bind_sky":
+                forced.append(("frame", "X1"))
+        elif t in G_TEX + P_TEX:
+            forced = [pick((lambda: draw("reproject"), lambda: ("denoise", "C") + draw("denoise")[2:]))]
+        elif t != "D":
+            forced = [pick((lambda: ("denoise", t) + draw("denoise")[2:], lambda: draw("reproject")[:4] + (t if t in ("C", "H") else "C",),
+                            ("bind_sky", t)))]
+            if forced[0] == ("bind_sky", t):
+                forced += [("frame", "X1" if t != "X1" else "X2")]
+    return forced
+
+
 def make_pipeline_program(seed, n_ops=40):
     """As make_program, over PIPE_KINDS.  The bias: an image or a buffer that has just been written meets its consumer with nothing in
     between — a written image is the input of reproject / denoise / select / resample, a device-side vertex write is followed by a frame,
@@ -509,7 +628,6 @@ def make_pipeline_program(seed, n_ops=40):
     p = np.array([_PIPE_WEIGHTS[k] for k in kinds], dtype=np.float64)
     p /= p.sum()
     tr, prog, forced = _PipeTrack(), [], []
-    pick = lambda names: names[int(rng.integers(len(names)))]
 
     def emit(op):
         tr.apply(op)
@@ -534,54 +652,305 @@ def make_pipeline_program(seed, n_ops=40):
             continue
         result = tr.result
         emit(op)
-        k, r = op[0], rng.random()
-        written = [t for t, _ in pipeline_writes_of(op, result)]
-        if k == "history" and r < 0.6:                           # the temporal step
-            prev, form = tr.camera, pick(FORMS)
-            other = ("camera", (prev + 1 + int(rng.integers(len(CAMERA_POSITIONS) - 1))) % len(CAMERA_POSITIONS))
-            change = {"plain": other, "objects": pick((("move_mesh", 1, int(rng.integers(3))), ("move_spheres", int(rng.integers(3))))),
-                      "deformed": pick((("deform", 0.9), ("skin", int(rng.integers(3)), True, lo, hi - lo + 1), ("set_device", lo, 40, 1.25)))}[form]
-            forced = [("aov", "P", 11, False)] + ([("snapshot",)] if form == "deformed" else []) + [change] + \
-                     ([other] if form != "plain" and rng.random() < 0.6 else []) + [("aov", "G", 15, False),
-                      ("reproject", form, prev, float(pick((8.0, 64.0))), "H"), ("select", "RN", float(pick((1.0, 2.0))))]
-            if rng.random() < 0.5:
-                forced += [("blit", "R", "H"), ("blit", "RN", "N"), ("resample", 2.0, 1, 0.0), ("frame", "X0")]
-        elif k in ("ray_query_async", "radiance_async") and r < 0.65:
-            forced = [pick((("deform", 0.9), ("skin", int(rng.integers(3)), False, lo, hi - lo + 1), ("set_device", lo + 10, 50, 0.75),
-                            ("move_mesh", 0, int(rng.integers(3))), ("set_host", lo, 30, 1.25)))]
-            if rng.random() < 0.5:
-                forced.append(("frame", None))
-        elif k in ("skin", "set_device", "normals") and r < 0.45:
-            forced = [("frame", pick((None, "X0")))]
-        elif k in ("skin", "set_device") and r < 0.8:            # a host write over part of what the device wrote, then read back
-            first = op[3] if k == "skin" else op[1]
-            forced = [("set_host", first, 8, 0.9), pick((("get_buffer", "V", first, 24), ("bounds", first, 24)))]
-        elif k == "set_host" and r < 0.4:                        # a run of host uploads into the mirrored buffer
-            forced = [lambda: draw("set_host") for _ in range(int(rng.integers(2, 8)))] + [pick((("frame", None), ("get_buffer", "V", 0, nv)))]
-        elif k == "frame" and r < 0.15:
-            forced = [("aov_into", result), ("frame", None)]
-        elif k in ("frame", "dispatch") and r < 0.35:            # something between two frames of what would be one batch
-            forced = [pick((lambda: draw("skin"), lambda: draw("set_device"), lambda: draw("set_host"), ("normals",), ("deform", 0.9),
-                            ("get", "C"), ("ray_query_async", 7), ("radiance_pixels", 7), ("aov", "G", 15, False))), ("frame", None)]
-        elif written and r < 0.75:                               # written -> read by an image operation, nothing in between
-            t = written[int(rng.integers(len(written)))]
-            if t in ("H", "N"):
-                forced = [pick((lambda: draw("select")[:1] + ("N",) + draw("select")[2:], lambda: draw("resample"),
-                                lambda: draw("reproject")[:4] + ("H",)))]
-            elif t in ("R", "RN", "MV"):
-                forced = [pick((("select", "RN", 1.0), ("denoise", "R", 2, True), ("bind_sky", "R")))]
-                if forced[0][0] == "bind_sky":
-                    forced.append(("frame", "X1"))
-            elif t in G_TEX + P_TEX:
-                forced = [pick((lambda: draw("reproject"), lambda: ("denoise", "C") + draw("denoise")[2:]))]
-            elif t != "D":
-                forced = [pick((lambda: ("denoise", t) + draw("denoise")[2:], lambda: draw("reproject")[:4] + (t if t in ("C", "H") else "C",),
-                                ("bind_sky", t)))]
-                if forced[0] == ("bind_sky", t):
-                    forced += [("frame", "X1" if t != "X1" else "X2")]
+        forced = _pipeline_followers(rng, op, result, tr, draw, (lo, hi), nv)
     while tr.tickets:
         emit(("read_end",))
     return prog
+
+
+# ---- programs of the display profile -------------------------------------------------------------------------------------------------
+class _DisplayTrack(_PipeTrack):
+    def __init__(self):
+        super().__init__()
+        self.low_ready = self.ga_ready = self.ln_ready = self.framed = self.tm_ready = False
+
+    def allowed(self, op):
+        k = op[0]
+        if k == "aov_low":
+            return self.sky not in ("Lh", "Lm", "Lc", "Li")
+        if k == "upsample":                                      # (its outputs are no input by construction: see _draw_display)
+            return self.sky is None or self.sky not in op[1:3]
+        if k in ("tonemap", "bloom"):
+            return op[2] != self.sky and size_class(op[1]) == size_class(op[2]) and op[1] in DISPLAY_EXACT and op[2] in DISPLAY_EXACT
+        if k == "meter":
+            return op[1] in DISPLAY_EXACT and (not op[3] or size_class(op[1]) == 0)
+        if k == "present_tm":
+            return op[1] is None or (op[1] not in (self.sky, "C") and op[1] in DISPLAY_FRAME_TEX)
+        if k == "get" and op[1] == "TM":
+            return self.tm_ready
+        if k in ("set_host", "set_device", "bounds", "get_buffer"):      # (a follower's fixed count can reach past the last vertex)
+            return sum(op[-3:-1] if k in ("set_host", "set_device") else op[-2:]) <= len(pipeline_world()["rest_v"])
+        return super().allowed(op)
+
+    def apply(self, op):
+        super().apply(op)
+        k = op[0]
+        if k == "aov_low":
+            self.low_ready = True
+        elif k == "aov" and op[1] == "G" and op[2] & 4:
+            self.ga_ready = True
+        elif k == "setpixels" and op[1] == "Ln":
+            self.ln_ready = op[2] > 0
+        elif k == "frame":
+            self.framed = True
+        elif k == "present_tm" and op[1] is None:
+            self.tm_ready = True
+
+    def prerequisites(self, op):
+        pre = super().prerequisites(op)
+        if op[0] == "upsample":
+            if not self.g_ready or (op[4] & SKY_FROM_ALBEDO and not self.ga_ready):
+                pre.append(("aov", "G", 15, False))
+            if not self.low_ready:
+                pre.append(("aov_low", False))
+            if op[3] and not self.ln_ready:
+                pre.append(("setpixels", "Ln", 1.5))
+        elif op[0] == "present_tm" and not self.framed:
+            pre.append(("frame", None))
+        return pre
+
+
+def display_writes_of(op, result):
+    """pipeline_writes_of for every kind of the display profile; the exposure states (E0, E1, the master's MS) count as resources."""
+    k = op[0]
+    if k == "aov_low":
+        return [(t, "aov") for t in ("Lh", "Lm", "Lc", "Li")]
+    if k == "upsample":
+        return [(op[1], "upsample")] + ([(op[2], "upsample")] if op[2] else [])
+    if k in ("tonemap", "bloom"):
+        return [(op[2], k)]
+    if k == "meter":
+        return [(STATES[op[2]], "meter")]
+    if k == "state_reset":
+        return [(STATES[op[1]], "state_reset")]
+    if k == "present_tm":
+        return [("MS", "present_tm"), (op[1] or "TM", "present_tm")]
+    return pipeline_writes_of(op, result)
+
+
+def display_reads_of(op, result):
+    """pipeline_reads_of for every kind of the display profile (a metering reads the state it writes: its previous exposure)."""
+    k = op[0]
+    if k == "upsample":
+        return ["Lc", "Lh", "Lm", "Li", "Gh", "Gn", "Gi"] + (["Ln"] if op[3] else []) + (["Ga"] if op[4] & SKY_FROM_ALBEDO else [])
+    if k == "meter":
+        return [op[1]] + (["N"] if op[3] else []) + [STATES[op[2]]]
+    if k in ("tonemap", "bloom"):
+        return [op[1]] + ([STATES[op[3]]] if op[3] is not None else [])
+    if k == "state_get":
+        return [STATES[op[1]]]
+    if k == "present_tm":
+        return ["C", "MS"]
+    return pipeline_reads_of(op, result)
+
+
+# the pipeline profile's weights at 0.6, the rare kinds and the frame loop held up; then the display kinds
+_DISPLAY_WEIGHTS = dict({k: 0.6 * v for k, v in _PIPE_WEIGHTS.items()}, frame=18, dispatch=3, history=4, restart=1.5, bind_sky=3, bind_result=2,
+                        ptr=1.5, read_begin=3, read_end=3,
+                        aov_low=3, upsample=6, meter=8, tonemap=8, bloom=8, state_get=4, state_reset=6, master_bloom=3, present_tm=5)
+_SAME_SIZE = {0: ("X0", "X1", "X2", "U", "H"), 1: SKY_TEX, 2: ("Lc", "Ln")}
+
+
+def _draw_display(rng, kind, tr, nv, span):
+    pick = lambda names: names[int(rng.integers(len(names)))]
+    if kind == "aov_low":
+        return ("aov_low", bool(rng.random() < 0.25))
+    if kind == "upsample":                                       # colour and count are never an input of the call
+        return ("upsample", pick(("U", "U", "X0", "H", tr.result)), pick(("UN", "N", None)), bool(rng.random() < 0.5), int(rng.integers(4)))
+    if kind == "meter":
+        src = pick(("C", "C", "C", "C", tr.result, "S0", "Lc") + DISPLAY_EXACT)       # any texture of any size, the id images included
+        return ("meter", src, int(rng.integers(2)), bool(size_class(src) == 0 and rng.random() < 0.3), int(rng.integers(len(METER))))
+    if kind in ("tonemap", "bloom"):
+        src = pick(("C", "C", "C", "H", "X0", "U", tr.result, "S0", "S1", "Lc", "Lc", "R", "Ga", "Gn", "Gi", "RN", "Li", "Lm"))
+        dst = src if rng.random() < 0.3 else pick(_SAME_SIZE[size_class(src)] + ((tr.result,) if size_class(src) == 0 else ()))
+        state = pick((None, 0, 0, 1, 1))
+        if kind == "tonemap":
+            return ("tonemap", src, dst, state, pick(TONEMAP_OPS), float(pick((1.0, 1.0, 0.5, 2.0))))
+        return ("bloom", src, dst, state, int(pick((1, 3, 3, 6, 16))), int(rng.random() < 0.25) * BLOOM_ONLY)
+    if kind in ("state_get", "state_reset"):
+        return (kind, int(rng.integers(2)))
+    if kind == "master_bloom":
+        return ("master_bloom", bool(rng.random() < 0.6))
+    if kind == "present_tm":
+        return ("present_tm", pick((None, None, "X0", "X1", "U", tr.other_result())), pick(TONEMAP_OPS))
+    if kind == "setpixels":
+        return ("setpixels", pick(ALL_TEX + ("Lc", "Ln", "Ln", "U")), float(pick((0.0, 0.25, 1.5))))
+    if kind == "bind_sky":
+        return ("bind_sky", pick((None,) + ALL_TEX + ("R", "Ga", "RN", "U", "Lc")))
+    if kind == "get":
+        return ("get", pick(ALL_TEX + PIPE_TEX + LOW_TEX + UP_TEX + ("TM", "TM", "D", "R")))
+    if kind == "read_begin":
+        return ("read_begin", pick(DISPLAY_FRAME_TEX + ("Lc", "S1")), pick(FORMATS))
+    if kind == "blit" and rng.random() < 0.15:                   # within the low grid, into the colour
+        return ("blit", pick(LOW_TEX[1:]), "Lc")
+    return _draw_pipeline(rng, kind, tr, nv, span)
+
+
+def make_display_program(seed, n_ops=40):
+    """As make_pipeline_program, over DISP_KINDS (what follows an op of the pipeline profile is what follows it there).  The bias of the
+    display calls: a frame's blend into C is followed by its metering, a bloom or tone mapping with that state and an 8-bit readback of
+    the destination, nothing waited for in between; a display call's destination is bound as the sky and traced at once; a display call
+    writes the bound Result texture and a frame follows; C or H is tone-mapped or bloomed in place and a frame or the history blend
+    follows; one state is metered twice in a row at a rate below 1 on sources of two sizes; bloom on a small texture is followed by
+    bloom on a larger one; upsampling into H / N is followed by resample or select; ToneMap of the master follows a frame."""
+    rng = np.random.default_rng(200000 + seed)
+    w = pipeline_world()
+    lo, hi = w["span"]
+    nv = len(w["rest_v"])
+    kinds = list(_DISPLAY_WEIGHTS)
+    p = np.array([_DISPLAY_WEIGHTS[k] for k in kinds], dtype=np.float64)
+    p /= p.sum()
+    tr, prog, forced = _DisplayTrack(), [], []
+    pick = lambda names: names[int(rng.integers(len(names)))]
+
+    def emit(op):
+        tr.apply(op)
+        prog.append(op)
+
+    def draw(kind):
+        return _draw_display(rng, kind, tr, nv, (lo, hi))
+
+    def with_prerequisites(op):
+        return tr.prerequisites(op) + [op]
+
+    def sky_and_frame(t):
+        return [("bind_sky", t), ("frame", "X1" if t != "X1" else "X2")]
+
+    def followers(op, result):
+        k, r = op[0], rng.random()
+        state = int(rng.integers(2))
+        if k == "frame" and r < 0.2:                             # the presented frame: meter, bloom and / or tone-map, read back
+            dest = pick(("X0", "X1", "U"))
+            chain = [("meter", "C", state, bool(rng.random() < 0.2), int(pick((1, 1, 3, 0))))]
+            if rng.random() < 0.6:
+                chain += [("bloom", "C", dest, state, int(pick((3, 6))), 0), ("tonemap", dest, dest, state, "aces", 1.0)]
+            else:
+                chain += [("tonemap", "C", dest, state, pick(TONEMAP_OPS), 1.0)]
+            return chain + [("read_begin", dest, "RGBA8_SRGB")]
+        if k == "frame" and r < 0.24:                            # in place on C or H, then a frame or the history blend
+            t = pick(("C", "H"))
+            return [pick((("tonemap", t, t, None, "reinhard", 1.0), ("bloom", t, t, pick((None, state)), 3, 0))),
+                    pick((("frame", None), ("history", 0.0)))]
+        if k == "frame" and r < 0.34:                            # a display call writes the bound Result, a frame follows
+            writer = pick((("tonemap", "C", tr.result, None, "aces", 1.0), ("bloom", "C", tr.result, None, 3, 0),
+                           ("upsample", tr.result, None, False, WIDE_FALLBACK)))
+            return with_prerequisites(writer) + [("frame", None)]
+        if k == "frame" and r < 0.42:                            # the master's ToneMap, read back
+            dest = pick((None, "X0", "X1"))
+            return [("master_bloom", bool(rng.random() < 0.7)), ("present_tm", dest, "aces")] + \
+                   ([("read_begin", dest, "RGBA8_SRGB")] if dest else [("get", "TM")])
+        if k == "frame" and r < 0.48:                            # upsample into the history pair, then its consumer
+            return with_prerequisites(("upsample", "H", "N", bool(rng.random() < 0.5), int(rng.integers(4)))) + \
+                   [pick((("select", "N", 1.0), ("resample", 2.0, 1, 0.0)))]
+        if k == "meter" and r < 0.5:                             # one state twice in a row below rate 1, on sources of two sizes
+            a, b = pick((("C", "Lc"), ("S0", "C"), ("Lc", "S1"), ("U", "S0")))
+            return [("meter", a, op[2], False, 1), ("meter", b, op[2], False, int(pick((1, 2, 3)))),
+                    pick((("tonemap", "C", "X0", op[2], "aces", 1.0), ("bloom", "C", "X1", op[2], 3, 0), ("state_get", op[2])))]
+        if k == "bloom" and size_class(op[1]) != 1 and r < 0.6:  # bloom on a small texture, then on a larger one
+            return [pick((("bloom", "S0", "S1", None, op[4], 0), ("bloom", "S1", "S1", None, 16, 0))) if size_class(op[1]) == 0 else
+                    pick((("bloom", "C", "X0", None, op[4], 0), ("bloom", "S0", "S1", None, op[4], 0)))]
+        if k == "upsample" and (op[1] == "H" or op[2] == "N") and r < 0.6:
+            return [pick((("select", "N", 1.0), ("resample", 2.0, 1, 0.0)))]
+        if k in DISPLAY_WRITERS + ("present_tm",) and r < 0.8:
+            dest = op[1] if k == "upsample" else op[2] if k != "present_tm" else op[1]
+            if dest is not None and dest != tr.result:          # the destination is bound as the sky and traced at once
+                return sky_and_frame(dest)
+        return []
+
+    while len(prog) < n_ops or forced:
+        if forced:
+            op = forced.pop(0)
+            if callable(op):
+                op = op()
+            drawn = op[0] == "drawn"                             # the drawn op behind its prerequisites: it has its followers, too
+            op = op[1] if drawn else op
+            if not tr.allowed(op):
+                continue
+        else:
+            op, drawn = draw(kinds[int(rng.choice(len(kinds), p=p))]), True
+            if not tr.allowed(op):
+                continue
+            if tr.prerequisites(op):
+                forced = tr.prerequisites(op) + [("drawn", op)]
+                continue
+        result = tr.result
+        emit(op)
+        if not drawn:
+            continue
+        if op[0] in DISPLAY_KINDS or (op[0] == "frame" and rng.random() < 0.6):
+            forced = followers(op, result)
+        else:
+            forced = _pipeline_followers(rng, op, result, tr, draw, (lo, hi), nv)
+    while tr.tickets:
+        emit(("read_end",))
+    return prog
+
+
+def display_coverage(program):
+    """Static facts about a program of the display profile (tests/test_command_stream_model.py holds the seed set to them).  "Quiet" ops
+    are the ones that neither submit the deferred frames nor wait: frames and dispatches themselves, scene and vertex edits, bindings.
+    kinds: op kind -> count;
+    input_deferred: display image calls (upsample, meter, tonemap, bloom, present_tm) that read a texture frames wrote while those frames
+    could still be deferred;  output_deferred: such calls that write one, with a frame after them;
+    state_chain: bloom / tonemap calls reading a state whose last metering read such a texture, with nothing but quiet ops and other
+    bloom / tonemap calls since that metering (nothing has waited: the state is read on the device behind its writer);
+    in_place_then_frame: tonemap / bloom with dst = src whose next op that is not a binding is a frame, a dispatch or the history blend;
+    written_then_sky_traced: writer kind -> textures last written by it that were bound as the sky after that write and traced before
+    anything else wrote them;
+    writes_bound_result: display image calls that write the bound Result texture, with a frame after them;
+    pyramid_regrow: bloom calls that need more pyramid texels than every bloom before them in the program (there is one before);
+    two_meterings_rate_below_1: a metering at a rate below 1 right behind another one of the same state, on a source of another size."""
+    kinds = {k: 0 for k in DISP_KINDS}
+    tr = _DisplayTrack()
+    neutral = ("restart", "bind_sky", "bind_result", "camera", "master_bloom")
+    quiet = neutral + ("frame", "dispatch", "snapshot", "ray_query_async", "radiance_async") + SCENE_CHANGES
+    sizes = {0: (64, 40), 1: make_scene().sky.shape[1::-1], 2: low_size(64, 40)}
+    out = {key: 0 for key in ("input_deferred", "output_deferred", "state_chain", "in_place_then_frame", "writes_bound_result",
+                              "pyramid_regrow", "two_meterings_rate_below_1")}
+    sky_traced = {w: 0 for w in DISPLAY_WRITERS}
+    deferred, chain, last_writer, write_at, bound_at, counted, pyramid = set(), set(), {}, {}, -1, set(), 0
+    frames_after = np.cumsum([op[0] in ("frame", "dispatch") for op in program][::-1])[::-1]
+    for i, op in enumerate(program):
+        k = op[0]
+        kinds[k] += 1
+        result = tr.result if k != "dispatch" else op[1]
+        reads, writes = display_reads_of(op, result), [t for t, _ in display_writes_of(op, result)]
+        if k in DISPLAY_IMAGE_OPS:
+            out["input_deferred"] += bool(deferred & set(reads))
+            out["output_deferred"] += bool(deferred & set(writes) and frames_after[i] > 0)
+            out["writes_bound_result"] += bool(tr.result in writes and frames_after[i] > 0)
+        if k in ("tonemap", "bloom"):
+            out["state_chain"] += bool(op[3] is not None and STATES[op[3]] in chain)
+            following = [q[0] for q in program[i + 1:] if q[0] not in neutral][:1]
+            out["in_place_then_frame"] += bool(op[1] == op[2] and following and following[0] in ("frame", "dispatch", "history"))
+        if k == "bloom":
+            need = pyramid_texels(*sizes[size_class(op[1])], op[4])
+            out["pyramid_regrow"] += bool(0 < pyramid < need)
+            pyramid = max(pyramid, need)
+        if k == "meter":
+            before = program[i - 1] if i else ("",)
+            out["two_meterings_rate_below_1"] += bool(before[0] == "meter" and before[2] == op[2] and METER[before[4]]["rate"] < 1 and
+                                                      METER[op[4]]["rate"] < 1 and size_class(before[1]) != size_class(op[1]))
+        if k in ("frame", "dispatch") and tr.sky in last_writer and bound_at > write_at[tr.sky] and (tr.sky, write_at[tr.sky]) not in counted:
+            counted.add((tr.sky, write_at[tr.sky]))
+            if last_writer[tr.sky] in sky_traced:
+                sky_traced[last_writer[tr.sky]] += 1
+        # the state after the op
+        if k == "meter":
+            chain = (chain | {STATES[op[2]]}) if deferred & set(reads) else (chain - {STATES[op[2]]})
+        elif k not in quiet + ("tonemap", "bloom"):
+            chain = set()
+        if k in ("frame", "dispatch"):
+            deferred |= {t for t, _ in writes_of(op, result)}
+        elif k not in quiet:
+            deferred = set()
+        for t, wk in display_writes_of(op, result):
+            last_writer[t], write_at[t] = wk, i
+        if k == "bind_sky":
+            bound_at = i
+        tr.apply(op)
+    out["kinds"], out["written_then_sky_traced"] = kinds, sky_traced
+    return out
 
 
 def pipeline_coverage(program, nv=None):
@@ -716,12 +1085,23 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
     """-> (observations, final contents): observations is a list of (op index, kind, array | None), final a dict name -> array.
     profile="pipeline": the world and the ops of that profile (final holds the buffers too, under "V", "V.dev", ...: both sides of a
     buffer hold the same in program order); stats, a list, receives (op index, kind, figures) of the reproject / denoise / select /
-    resample ops — what tests/test_command_stream_model.py measures non-vacuity on."""
+    resample ops — what tests/test_command_stream_model.py measures non-vacuity on.
+    profile="display": the world and the ops of that profile on top (final holds the exposure states "E0", "E1" and the master's "MS" as
+    state_words, and "TM"; stats receives the figures of the upsample and meter ops, too)."""
     from oracle import pyoracle
     from reproject_ref import blit_add_history_ref
-    pipeline = profile == "pipeline"
+    assert profile in ("frames", "pipeline", "display"), profile
+    display = profile == "display"
+    pipeline = profile == "pipeline" or display
     sc = make_scene(width, height, bounces)
-    tex = {n: np.zeros((height, width, 4), F) for n in FRAME_TEX + (PIPE_TEX if pipeline else ())}
+    tex = {n: np.zeros((height, width, 4), F) for n in FRAME_TEX + (PIPE_TEX if pipeline else ()) + (UP_TEX + ("TM",) if display else ())}
+    if display:
+        import bloom_ref
+        import tonemap_ref
+        import upsample_ref
+        lw, lh = low_size(width, height)
+        tex.update({n: np.zeros((lh, lw, 4), F) for n in LOW_TEX})
+        states, master_bloom = {n: fresh_state() for n in STATES + ("MS",)}, False
     tex["S0"] = np.array(sc.sky, F)
     tex["S1"] = np.zeros_like(tex["S0"])
     sky, result, sample, frame, tickets, obs = "S0", "T0", 0, 0, [], []
@@ -735,18 +1115,60 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
         s.num_rays = num_rays
         return pyoracle.Oracle(s)
 
-    def aov(frame_ray=False):
+    def aov(frame_ray=False, size=None):
         from aov_ref import camera_rays
         orc = oracle()
         uniforms = (*frame_uniforms_of(sc, frame)[0], frame_uniforms_of(sc, frame)[1]) if frame_ray else None
-        O, D = camera_rays(orc.scene, width, height, uniforms)
+        O, D = camera_rays(orc.scene, *(size or (width, height)), uniforms)
         return orc.aov(np.broadcast_to(O, D.shape), D)
+
+    def exposure_of(k):
+        return None if k is None else states[STATES[k] if k != "MS" else k]["exposure"]
+
+    def tone_map(src, dst, k, op, exposure=1.0):
+        tex[dst] = tonemap_ref.tonemap_ref(tex[src], exposure=exposure, op=TONEMAP_OPS.index(op), state_exposure=exposure_of(k))
+
+    def bloom(src, dst, k, levels, flags=0):
+        tex[dst] = bloom_ref.bloom_ref(tex[src], exposure=exposure_of(k), levels=levels, flags=flags)[0]
 
     for i, op in enumerate(program):
         k = op[0]
         if pipeline and k in OBSERVERS:                          # what the async queries answered is looked at now
             obs += waiting
             waiting = []
+        if display and k in DISPLAY_KINDS:
+            if k == "aov_low":
+                tex["Lh"], tex["Lm"], tex["Lc"], tex["Li"] = aov(op[1], low_size(width, height))
+            elif k == "upsample":
+                _, color, count, with_low_count, flags = op
+                out = upsample_ref.upsample_ref(*[tex[n] for n in ("Lc", "Lh", "Lm", "Li", "Gh", "Gn", "Gi")],
+                                                low_count=tex["Ln"] if with_low_count else None,
+                                                albedo=tex["Ga"] if flags & SKY_FROM_ALBEDO else None, flags=flags)
+                tex[color] = out["color"]
+                if count:
+                    tex[count] = out["count"]
+                stats.append((i, k, {"result": int(out["result"].sum()), "of": int(out["result"].size)}))
+            elif k == "meter":
+                name = STATES[op[2]]
+                states[name] = tonemap_ref.auto_exposure_ref(tex[op[1]], tex["N"] if op[3] else None, states[name], **METER[op[4]])
+                stats.append((i, k, {"counted": states[name]["counted"], "settled": states[name]["exposure"] == states[name]["target"]}))
+            elif k == "tonemap":
+                tone_map(*op[1:])
+            elif k == "bloom":
+                bloom(*op[1:])
+            elif k == "state_get":
+                obs.append((i, k, state_words(states[STATES[op[1]]])))
+            elif k == "state_reset":
+                states[STATES[op[1]]] = fresh_state()
+            elif k == "master_bloom":
+                master_bloom = op[1]
+            elif k == "present_tm":                              # RayTraceMaster.ToneMap: the three explicit calls on the master's state
+                dest = op[1] or "TM"
+                states["MS"] = tonemap_ref.auto_exposure_ref(tex["C"], None, states["MS"], **MASTER_EXPOSURE)
+                if master_bloom:
+                    bloom("C", dest, "MS", **MASTER_BLOOM)
+                tone_map("C" if not master_bloom else dest, dest, "MS", op[2])
+            continue
         if pipeline and k in NEW_KINDS + ("radiance_query",):
             if k == "aov":
                 if op[1] == "P":
@@ -865,6 +1287,8 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
         obs += waiting
         for name, a in (("V", sc.vertices), ("NB", sc.normals), ("SNAP", snap)):
             tex[name] = tex[name + ".dev"] = np.array(np.asarray(a, F).reshape(-1, 3))
+    if display:
+        tex.update({name: state_words(s) for name, s in states.items()})
     return obs, tex
 
 
@@ -917,9 +1341,12 @@ class _PipelineWorld:
 def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=40, bounces=2, profile="frames", probe=None):
     """The program through the Python API -> (observations, final contents, counters, [(op index, launch_info()) after every op of SUBMITTING]).
     probe(op index, op, master, the pipeline profile's buffers | None) is called after every op: for protocols that look at the
-    library's own bookkeeping (it must not call anything that submits or waits, or the run is no longer the program's)."""
+    library's own bookkeeping (it must not call anything that submits or waits, or the run is no longer the program's).
+    profile="display": as in run_model; the states are read at the end through Context.exposure_state."""
     from unityraytracer_amd import Graphics, RayTraceMaster, RenderTexture
-    pipeline = profile == "pipeline"
+    assert profile in ("frames", "pipeline", "display"), profile
+    display = profile == "display"
+    pipeline = profile == "pipeline" or display
     ctx.set_option("kernel_mode", 3)
     ctx.set_option("frames_per_launch", frames_per_launch)
     ctx.set_option("overlap_launches", overlap_launches)
@@ -927,8 +1354,10 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
     try:
         sc = make_scene(width, height, bounces)
         m = RayTraceMaster(ctx, sc, frame_seed=FRAME_SEED)
-        for n in FRAME_TEX + (PIPE_TEX if pipeline else ()):
+        for n in FRAME_TEX + (PIPE_TEX if pipeline else ()) + (UP_TEX if display else ()):
             tex[n] = RenderTexture(ctx, width, height)
+        for n in LOW_TEX if display else ():
+            tex[n] = RenderTexture(ctx, *low_size(width, height))
         m._target, m._converged = tex["T0"], tex["C"]
         m._bind_for_queries()                                  # buffers, the scene's sky, the bindings
         tex["S0"] = m.SkyboxTexture
@@ -940,6 +1369,9 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
             pw = _PipelineWorld(ctx, m, width, height)
             dev = torch.device("cuda", ctx.device)
             bufs = {"V": pw.V, "NB": pw.NB, "SNAP": pw.SNAP}
+        if display:
+            states = [torch.zeros(STATE_WORDS, dtype=torch.int32, device=dev) for _ in STATES]
+            m.EnableAutoExposure(**MASTER_EXPOSURE)
         p_scene, waiting = m.scene, []
         ctx.reset_counters()
         obs, infos, tickets = [], [], []
@@ -957,6 +1389,38 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
             k = op[0]
             if pipeline and k in OBSERVERS:
                 drain()
+            if display and k in DISPLAY_KINDS:
+                state = states[op[3]] if k in ("tonemap", "bloom") and op[3] is not None else None
+                if k == "aov_low":
+                    m.SetShaderParameters()
+                    ctx.render_aov(tex["Lh"], tex["Lm"], tex["Lc"], tex["Li"], frame_ray=op[1])
+                elif k == "upsample":
+                    _, color, count, with_low_count, flags = op
+                    ctx.upsample(*[tex[n] for n in ("Lc", "Lh", "Lm", "Li", "Gh", "Gn", "Gi")], tex[color], tex[count] if count else None,
+                                 low_count=tex["Ln"] if with_low_count else None, albedo=tex["Ga"] if flags & SKY_FROM_ALBEDO else None,
+                                 wide_fallback=bool(flags & WIDE_FALLBACK), sky_from_albedo=bool(flags & SKY_FROM_ALBEDO))
+                elif k == "meter":
+                    ctx.auto_exposure(tex[op[1]], states[op[2]], tex["N"] if op[3] else None, **METER[op[4]])
+                elif k == "tonemap":
+                    ctx.tonemap(tex[op[1]], tex[op[2]], state, op=op[4], exposure=op[5])
+                elif k == "bloom":
+                    ctx.bloom(tex[op[1]], tex[op[2]], state, levels=op[4], flags=op[5])
+                elif k == "state_get":
+                    obs.append((i, k, state_words(ctx.exposure_state(states[op[1]]))))
+                elif k == "state_reset":
+                    # The library orders torch's stream in front of its own (unity_api._sync_torch_stream), not the other way round: a
+                    # caller that writes a state with torch waits for the library first.  That wait is part of the op, in the model too
+                    # (it submits the deferred frames: the op is one of SUBMITTING).
+                    ctx.synchronize()
+                    states[op[1]].zero_()
+                    infos.append((i, ctx.launch_info()))
+                elif k == "master_bloom":
+                    m.EnableBloom(**MASTER_BLOOM) if op[1] else m.DisableBloom()
+                elif k == "present_tm":
+                    m.ToneMap(tex[op[1]] if op[1] else None, op[2])
+                if probe:
+                    probe(i, op, m, pw)
+                continue
             if pipeline and k in NEW_KINDS:
                 if k == "aov":
                     if op[1] == "P":
@@ -1074,7 +1538,7 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
             elif k == "ptr":
                 assert tex[op[1]].device_ptr()
             elif k == "get":
-                obs.append((i, k, tex[op[1]].GetPixels()))
+                obs.append((i, k, (m._tonemapped if op[1] == "TM" else tex[op[1]]).GetPixels()))
             elif k == "read_begin":
                 tickets.append((tex[op[1]], tex[op[1]].ReadBegin(op[2])))
             elif k == "read_end":
@@ -1106,6 +1570,10 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
         if pipeline:
             for name, b in bufs.items():
                 final[name], final[name + ".dev"] = pw.both_sides(b)
+        if display:
+            final["TM"] = m._tonemapped.GetPixels() if m._tonemapped is not None else np.zeros((height, width, 4), F)
+            for name, t in zip(STATES + ("MS",), states + [m._exposureState]):
+                final[name] = state_words(ctx.exposure_state(t))
         return obs, final, ctx.counters(), infos
     finally:
         ctx.set_option("frames_per_launch", 0)

@@ -3,7 +3,10 @@
 These are conditions, not measurements: they keep tests/test_gpu_command_stream.py from passing by never getting to a written texture
 bound as the sky, a readback over deferred frames or a scene edit inside a batch — and tests/test_gpu_command_stream_pipeline.py from
 passing by never feeding an image operation what deferred frames wrote, never writing vertices on the device inside a batch, never
-editing the scene behind an un-waited query, or by reprojecting, selecting and denoising images in which nothing happens."""
+editing the scene behind an un-waited query, or by reprojecting, selecting and denoising images in which nothing happens — and
+tests/test_gpu_command_stream_display.py from passing by never metering, blooming, tone-mapping or upsampling what deferred frames
+wrote, never chaining an exposure state un-waited, never writing the bound Result texture or the next sky with a display call, never
+regrowing the bloom pyramid, or by metering images in which nothing counts."""
 import numpy as np
 import pytest
 
@@ -75,6 +78,8 @@ def test_model_of_hand_written_programs():
 F = np.float32
 # sha256 of repr([make_program(seed) for seed in range(24)]), computed on the commit before the pipeline profile existed
 FRAME_PROGRAMS_DIGEST = "770ff5c6ab1c8963024ba34dadfc434fbea4f3047bc31b8d365e4f72afb1fb99"
+# ... and of repr([make_program(seed, profile="pipeline") for seed in range(24)]), computed on the commit before the display profile existed
+PIPELINE_PROGRAMS_DIGEST = "ac84caddba71acdb56696727b1c59ba88ad9c0c1ea2d81fb6d7fe377db2341cb"
 
 
 def pipeline(ops, **kw):
@@ -87,36 +92,44 @@ def test_the_frame_loop_programs_are_what_they_were():
     assert hashlib.sha256(repr(programs).encode()).hexdigest() == FRAME_PROGRAMS_DIGEST
     assert programs == [cs.make_program(seed, profile="frames") for seed in SEEDS]
     assert not any(op[0] in cs.NEW_KINDS for p in programs for op in p)
+    piped = [cs.make_program(seed, profile="pipeline") for seed in SEEDS]
+    assert hashlib.sha256(repr(piped).encode()).hexdigest() == PIPELINE_PROGRAMS_DIGEST
+    assert not any(op[0] in cs.DISPLAY_KINDS for p in piped for op in p)
+
+
+def pipeline_op_keeps_to_the_rules(seed, op, tr, names=cs.ALL_TEX + cs.PIPE_TEX):
+    """The refusals of the pipeline profile's calls, for an op about to run in the state `tr`."""
+    lo, hi = cs.pipeline_world()["span"]
+    nv = len(cs.pipeline_world()["rest_v"])
+    k = op[0]
+    outputs = [t for t, _ in cs.pipeline_writes_of(op, tr.result)] if k in cs.IMAGE_OPS else []
+    assert tr.sky not in outputs, (seed, op, "an output is the bound sky")
+    if k != "resample":                                          # (resample_below blends into what it reads: its H and N are two textures)
+        assert not set(outputs) & set(cs.pipeline_reads_of(op, tr.result)), (seed, op, "an output is also an input")
+    named = [a for a in op[1:] if isinstance(a, str) and a in names]
+    if k in cs.IMAGE_OPS + ("blit",):
+        assert len({cs.size_class(n) for n in named}) <= 1, (seed, op, "sizes differ")
+    if k == "aov":
+        assert op[2] in range(1, 16)
+    if k == "skin":
+        assert lo <= op[3] and op[4] >= 1 and op[3] + op[4] - 1 <= hi and 0 <= op[1] < len(cs.POSE_ANGLES), (seed, op)
+    if k in ("set_device", "set_host", "bounds"):
+        assert 0 <= op[1] and op[2] >= 1 and op[1] + op[2] <= nv, (seed, op)
+    if k == "get_buffer":
+        assert op[1] in cs.BUFFERS and 0 <= op[2] and op[3] >= 1 and op[2] + op[3] <= nv, (seed, op)
+    if k != "get" and k != "denoise":
+        assert "D" not in op[1:], (seed, op, "the denoised image feeds something")
 
 
 def test_pipeline_programs_keep_to_the_rules():
     assert cs.make_program(3, profile="pipeline") == cs.make_program(3, profile="pipeline") != cs.make_program(4, profile="pipeline")
-    lo, hi = cs.pipeline_world()["span"]
-    nv = len(cs.pipeline_world()["rest_v"])
     for seed in SEEDS:
         p = cs.make_program(seed, profile="pipeline")
         assert 40 <= len(p) <= 60, (seed, len(p))
         tr = cs._PipeTrack()
         for op in p:
-            k = op[0]
-            assert k in cs.PIPE_KINDS and tr.allowed(op), (seed, op)
-            outputs = [t for t, _ in cs.pipeline_writes_of(op, tr.result)] if k in cs.IMAGE_OPS else []
-            assert tr.sky not in outputs, (seed, op, "an output is the bound sky")
-            if k != "resample":                                  # (resample_below blends into what it reads: its H and N are two textures)
-                assert not set(outputs) & set(cs.pipeline_reads_of(op, tr.result)), (seed, op, "an output is also an input")
-            names = [a for a in op[1:] if isinstance(a, str) and a in cs.ALL_TEX + cs.PIPE_TEX]
-            if k in cs.IMAGE_OPS + ("blit",):
-                assert len({cs.size_class(n) for n in names}) <= 1, (seed, op, "sizes differ")
-            if k == "aov":
-                assert op[2] in range(1, 16)
-            if k == "skin":
-                assert lo <= op[3] and op[4] >= 1 and op[3] + op[4] - 1 <= hi and 0 <= op[1] < len(cs.POSE_ANGLES), (seed, op)
-            if k in ("set_device", "set_host", "bounds"):
-                assert 0 <= op[1] and op[2] >= 1 and op[1] + op[2] <= nv, (seed, op)
-            if k == "get_buffer":
-                assert op[1] in cs.BUFFERS and 0 <= op[2] and op[3] >= 1 and op[2] + op[3] <= nv, (seed, op)
-            if k != "get" and k != "denoise":
-                assert "D" not in op[1:], (seed, op, "the denoised image feeds something")
+            assert op[0] in cs.PIPE_KINDS and tr.allowed(op), (seed, op)
+            pipeline_op_keeps_to_the_rules(seed, op, tr)
             tr.apply(op)
         assert tr.tickets == 0
 
@@ -160,9 +173,28 @@ def test_pipeline_seed_set_reaches_the_interesting_cases(pipeline_models):
         assert all(n in fin and n + ".dev" in fin for n in cs.BUFFERS)
 
 
-def test_the_comparison_notices_one_changed_op(pipeline_models):
+CHANGED = {"meter": lambda op: op[:2] + (1 - op[2],) + op[3:],                   # the other state
+           "tonemap": lambda op: op[:5] + (op[5] * 4.0,),                        # two stops more
+           "bloom": lambda op: op[:5] + (op[5] ^ cs.BLOOM_ONLY,),                # with / without the source
+           "upsample": lambda op: op[:4] + (op[4] ^ cs.SKY_FROM_ALBEDO,)}
+
+
+def test_the_comparison_notices_one_changed_op(pipeline_models, display_models):
     """first_difference is not vacuous: leaving out one op that writes (the first of its kind in the program) shows, for most kinds at
-    the very observation or texture it feeds."""
+    the very observation or texture it feeds — and so does changing one argument of one display call (the last of its kind in the
+    program: what it writes is least likely to be overwritten)."""
+    changed = set()
+    for p, obs, fin, _ in display_models[:8]:
+        for kind, change in CHANGED.items():
+            at = [i for i, op in enumerate(p) if op[0] == kind]
+            if not at or kind in changed:
+                continue
+            q = p[:at[-1]] + [change(p[at[-1]])] + p[at[-1] + 1:]
+            assert q != p and len(q) == len(p) and [op[0] for op in q] == [op[0] for op in p]
+            if cs.first_difference(cs.run_model(q, profile="display"), (obs, fin)) is not None:
+                changed.add(kind)
+    print("display kinds of which one changed argument was noticed:", sorted(changed))
+    assert changed == set(CHANGED), changed
     noticed = {}
     for p, obs, fin, _ in pipeline_models[:8]:
         for kind in ("aov_into", "reproject", "denoise", "resample", "skin", "set_device", "set_host", "snapshot", "normals"):
@@ -341,3 +373,219 @@ def test_model_of_six_plain_frames():
         c = pyoracle.accumulate(oracle_frame(sc, sc.sky, k), c, float(k))
     assert obs == [] and cs.same(tex["C"], c)
     assert scenes.frame_uniforms(3, cs.FRAME_SEED) != scenes.frame_uniforms(4, cs.FRAME_SEED)     # (the frames really differ)
+
+
+# ---- the display profile -------------------------------------------------------------------------------------------------------------
+def display(ops, **kw):
+    return cs.run_model(ops, profile="display", **kw)
+
+
+@pytest.fixture(scope="module")
+def display_models():
+    """The model of every display program of the seed set with its figures, made once: [(program, observations, final, stats)]."""
+    out = []
+    for seed in SEEDS:
+        p, stats = cs.make_program(seed, profile="display"), []
+        obs, fin = display(p, stats=stats)
+        out.append((p, obs, fin, stats))
+    return out
+
+
+def test_display_programs_keep_to_the_rules():
+    """Deterministic per seed, and no op the library would refuse: besides the pipeline profile's rules, the refusals of urt_upsample,
+    urt_auto_exposure, urt_tonemap and urt_bloom (csrc/image_ops.cpp) and of RayTraceMaster.ToneMap."""
+    assert cs.make_program(3, profile="display") == cs.make_program(3, profile="display") != cs.make_program(4, profile="display")
+    names = cs.DISPLAY_EXACT + ("D",)
+    seen = {"levels": set(), "bloom_flags": set(), "sizes": set(), "in_place": set(), "operators": set(), "upsample_flags": set(),
+            "rates": set(), "meter_sizes": set()}
+    for seed in SEEDS:
+        p = cs.make_program(seed, profile="display")
+        assert 40 <= len(p) <= 60, (seed, len(p))
+        tr = cs._DisplayTrack()
+        for op in p:
+            k = op[0]
+            assert k in cs.DISP_KINDS and tr.allowed(op), (seed, op)
+            pipeline_op_keeps_to_the_rules(seed, op, tr, names)
+            if k == "aov_low":
+                assert tr.sky not in ("Lh", "Lm", "Lc", "Li"), (seed, op, "a target is the bound sky")
+            if k == "upsample":                                  # unknown flags; one size per grid; an output that is an input or the sky
+                _, color, count, with_low_count, flags = op
+                assert flags in range(4) and isinstance(with_low_count, bool), (seed, op)
+                outputs = [t for t in (color, count) if t is not None]
+                assert len(set(outputs)) == len(outputs) and all(cs.size_class(t) == 0 and t in cs.DISPLAY_FRAME_TEX for t in outputs), (seed, op)
+                assert tr.sky not in outputs and not set(outputs) & set(cs.display_reads_of(op, tr.result)), (seed, op)
+                assert color in ("U", "X0", "H", tr.result) and count in ("UN", "N", None), (seed, op)
+                seen["upsample_flags"].add(flags)
+            if k == "meter":                                     # the parameter checks; a count image of another size
+                _, src, s, with_count, j = op
+                q = dict(key=0.18, min_exposure=1.0 / 64.0, max_exposure=64.0, rate=1.0, low_permille=100, high_permille=950, **{})
+                q.update(cs.METER[j])
+                assert all(np.isfinite(q[n]) and q[n] > 0 for n in ("key", "min_exposure", "max_exposure")) and q["min_exposure"] <= q["max_exposure"]
+                assert q["rate"] > 0 and 0 <= q["low_permille"] < q["high_permille"] <= 1000, (seed, op)
+                assert src in cs.DISPLAY_EXACT and s in (0, 1) and (not with_count or cs.size_class(src) == cs.size_class("N")), (seed, op)
+                seen["rates"].add(q["rate"])
+                seen["meter_sizes"].add(cs.size_class(src))
+            if k in ("tonemap", "bloom"):                        # sizes that differ; a destination that is the bound sky
+                _, src, dst, s, a, b = op
+                assert src in cs.DISPLAY_EXACT and dst in cs.DISPLAY_EXACT and cs.size_class(src) == cs.size_class(dst), (seed, op)
+                assert dst != tr.sky and s in (None, 0, 1), (seed, op)
+                seen["sizes"].add((k, cs.size_class(src)))
+                if src == dst:
+                    seen["in_place"].add(k)
+                if k == "tonemap":                               # an unknown operator, an exposure that is not finite and > 0
+                    assert a in cs.TONEMAP_OPS and np.isfinite(b) and b > 0, (seed, op)
+                    seen["operators"].add(a)
+                else:                                            # levels outside 1 .. 16, unknown flag bits
+                    assert 1 <= a <= 16 and b in (0, cs.BLOOM_ONLY), (seed, op)
+                    seen["levels"].add(a)
+                    seen["bloom_flags"].add(b)
+            if k in ("state_get", "state_reset"):
+                assert op[1] in (0, 1), (seed, op)
+            if k == "present_tm":                                # ToneMap: the accumulated image, another size; tonemap / bloom: the sky
+                assert op[1] is None or (op[1] in cs.DISPLAY_FRAME_TEX and op[1] not in ("C", tr.sky)), (seed, op)
+                assert op[2] in cs.TONEMAP_OPS, (seed, op)
+            if k == "get" and op[1] == "TM":
+                assert tr.tm_ready, (seed, op, "the master owns no texture yet")
+            tr.apply(op)
+        assert tr.tickets == 0
+    print("seen over the display seed set:", seen)
+    assert {1, 3, 16} <= seen["levels"] and seen["bloom_flags"] == {0, cs.BLOOM_ONLY} and seen["operators"] == set(cs.TONEMAP_OPS)
+    assert seen["sizes"] == {(k, c) for k in ("tonemap", "bloom") for c in (0, 1, 2)} and seen["in_place"] == {"tonemap", "bloom"}
+    assert seen["upsample_flags"] == {0, 1, 2, 3} and {1.0, 0.25} <= seen["rates"] and seen["meter_sizes"] == {0, 1, 2}
+    assert {m["rate"] for m in cs.METER} >= {1.0, 0.25} and any("low_permille" in m for m in cs.METER)
+    assert cs.low_size(64, 40) == (24, 16) and {cs.size_class(n) for n in cs.LOW_TEX} == {2} and cs.size_class("U") == cs.size_class("C") == 0
+
+
+def test_display_seed_set_reaches_the_interesting_cases(display_models):
+    cov = [cs.display_coverage(p) for p, _, _, _ in display_models]
+    kinds = {k: sum(c["kinds"][k] for c in cov) for k in cs.DISP_KINDS}
+    keys = ("input_deferred", "output_deferred", "state_chain", "in_place_then_frame", "writes_bound_result", "pyramid_regrow",
+            "two_meterings_rate_below_1")
+    cases = {key: sum(c[key] > 0 for c in cov) for key in keys}
+    sky = {w: sum(c["written_then_sky_traced"][w] > 0 for c in cov) for w in cs.DISPLAY_WRITERS}
+    print("op kinds over the display seed set:", kinds)
+    print("programs in which ... occurs:", cases)
+    print("programs in which a texture last written by ... is bound as the sky and traced:", sky)
+    assert all(kinds[k] >= 10 for k in cs.DISPLAY_KINDS) and all(kinds[k] >= 1 for k in cs.PIPE_KINDS), kinds
+    assert all(n >= 3 for n in cases.values()), cases
+    assert all(n >= 3 for n in sky.values()), sky
+    # non-vacuity, on the model's own output
+    stats = [s for _, _, _, st in display_models for s in st]
+    up = [f for _, k, f in stats if k == "upsample"]
+    good_up = sum(2 * f["result"] >= f["of"] for f in up)
+    mt = [f for _, k, f in stats if k == "meter"]
+    counted, moving = sum(f["counted"] > 0 for f in mt), sum(f["counted"] > 0 and not f["settled"] for f in mt)
+    print(f"upsample ops with a result in at least half of the pixels: {good_up} of {len(up)};  meterings that count a texel: {counted} of "
+          f"{len(mt)}, that leave the exposure on its way to the target: {moving}")
+    assert 2 * good_up >= len(up) and 2 * counted >= len(mt) and moving >= 10
+    for p, obs, fin, _ in display_models:                        # every state is in the final contents, every state_get is observed
+        assert all(fin[n].shape == (cs.STATE_WORDS,) and fin[n].dtype == np.uint32 for n in cs.STATES + ("MS",)) and "TM" in fin
+        assert sum(op[0] == "state_get" for op in p) == sum(k == "state_get" for _, k, _ in obs)
+        assert all(n in fin for n in cs.LOW_TEX + cs.UP_TEX)
+
+
+def test_model_of_the_exposure_state():
+    import tonemap_ref as tm
+    sc = cs.make_scene()
+    f0 = oracle_frame(sc, sc.sky, 0)
+    c = pyoracle.accumulate(f0, np.zeros_like(f0), 0.0)
+    # a fresh state snaps to its target whatever the rate
+    obs, fin = display([("frame", None), ("meter", "C", 0, False, 1), ("state_get", 0)])
+    hist, counted, skipped = tm.luminance_histogram_ref(c)
+    L = tm.metered_luminance(hist)
+    target = min(max(F(0.18) / L, F(1.0 / 64.0)), F(64.0))
+    assert counted > 1000 and counted + skipped == c.shape[0] * c.shape[1] and F(1.0 / 64.0) < target < F(64.0)
+    want = cs.state_words({"exposure": target, "target": target, "counted": counted, "skipped": skipped, "hist": hist})
+    assert obs[0][:2] == (2, "state_get") and cs.same(obs[0][2], want) and cs.same(fin["E0"], want) and not fin["E1"].any() and not fin["MS"].any()
+    # a second metering at rate 0.25 moves a quarter of the way, in the header's arithmetic: prev + (target - prev) * rate
+    obs, fin = display([("frame", None), ("meter", "C", 1, False, 1), ("meter", "S0", 1, False, 1), ("state_get", 1)])
+    hist2, counted2, skipped2 = tm.luminance_histogram_ref(sc.sky)
+    target2 = min(max(F(0.18) / tm.metered_luminance(hist2), F(1.0 / 64.0)), F(64.0))
+    moved = target + (target2 - target) * F(0.25)
+    assert moved.dtype == F and target2 != target and moved not in (target, target2)
+    want = cs.state_words({"exposure": moved, "target": target2, "counted": counted2, "skipped": skipped2, "hist": hist2})
+    assert cs.same(obs[0][2], want) and cs.same(fin["E1"], want) and not fin["E0"].any()
+    # ... with the count image: texels without a sample are left out; a reset state is fresh again
+    obs, fin = display([("frame", None), ("meter", "C", 0, True, 0), ("state_get", 0), ("history", 0.0), ("meter", "C", 0, True, 0), ("state_get", 0),
+                        ("state_reset", 0), ("state_get", 0)])
+    assert obs[0][2][2] == 0 and obs[0][2][3] == c.shape[0] * c.shape[1] and obs[0][2][0] == 0      # N is all zero: nothing counted, no exposure
+    assert cs.same(obs[1][2][:4], cs.state_words({"exposure": target, "target": target, "counted": counted, "skipped": skipped, "hist": hist})[:4])
+    assert not obs[2][2].any() and not fin["E0"].any()
+
+
+def test_model_of_the_masters_tone_map():
+    """present_tm is the three explicit calls on the master's own state, at the master's settings."""
+    by_master = [("frame", None), ("master_bloom", True), ("present_tm", "X0", "aces"), ("frame", None), ("present_tm", "X0", "aces"),
+                 ("master_bloom", False), ("present_tm", None, "reinhard"), ("get", "TM")]
+    explicit = [("frame", None), ("meter", "C", 0, False, 3), ("bloom", "C", "X0", 0, 3, 0), ("tonemap", "X0", "X0", 0, "aces", 1.0),
+                ("frame", None), ("meter", "C", 0, False, 3), ("bloom", "C", "X0", 0, 3, 0), ("tonemap", "X0", "X0", 0, "aces", 1.0),
+                ("meter", "C", 0, False, 3), ("tonemap", "C", "X1", 0, "reinhard", 1.0), ("get", "X1")]
+    assert cs.METER[3] == cs.MASTER_EXPOSURE and cs.MASTER_BLOOM == {"levels": 3}
+    (obs_a, a), (obs_b, b) = display(by_master), display(explicit)
+    assert cs.same(a["X0"], b["X0"]) and cs.same(a["TM"], b["X1"]) and cs.same(obs_a[0][2], obs_b[0][2]) and cs.same(a["MS"], b["E0"])
+    assert a["MS"][0] != a["MS"][1] and a["MS"][0] != 0          # (the third metering did not snap: the state's history is in it)
+    assert not a["E0"].any() and not b["MS"].any() and not b["TM"].any() and a["X0"][..., :3].any() and a["TM"][..., :3].any()
+    assert a["X0"][..., :3].max() <= 1.0 and not cs.same(a["X0"], a["TM"])
+    # ... and the explicit calls are the restatements
+    import bloom_ref
+    import tonemap_ref as tm
+    obs, fin = display([("frame", None), ("meter", "C", 0, False, 0), ("bloom", "C", "X0", 0, 3, cs.BLOOM_ONLY), ("tonemap", "C", "X1", 0, "linear", 2.0),
+                        ("tonemap", "S0", "S0", None, "reinhard", 0.5)])
+    e = fin["E0"][:1].view(F)[0]
+    sc = cs.make_scene()
+    assert cs.same(fin["X0"], bloom_ref.bloom_ref(fin["C"], exposure=e, levels=3, flags=bloom_ref.FLAG_ONLY)[0])
+    assert cs.same(fin["X1"], tm.tonemap_ref(fin["C"], exposure=2.0, op=tm.LINEAR, state_exposure=e))
+    assert cs.same(fin["S0"], tm.tonemap_ref(sc.sky, exposure=0.5, op=tm.REINHARD)) and fin["X0"][..., :3].any()
+
+
+def test_model_of_upsampling_a_constant():
+    """A constant low colour comes out as that constant wherever the call has a result (0.25: a power of two, so that the weighted sum
+    is 0.25 times the sum of the weights exactly), the count as 1, everything else as 0."""
+    import upsample_ref
+    head = [("aov", "G", 15, False), ("aov_low", False)]
+    obs, fin = display(head + [("setpixels", "Lc", 0.25), ("upsample", "U", "UN", False, cs.WIDE_FALLBACK), ("get", "U")])
+    assert fin["Lc"].shape == (16, 24, 4) and fin["Lh"].any() and (fin["Lc"] == 0.25).all()
+    ref = upsample_ref.upsample_ref(*[fin[n] for n in ("Lc", "Lh", "Lm", "Li", "Gh", "Gn", "Gi")], flags=cs.WIDE_FALLBACK)
+    result = ref["result"]
+    assert 0.5 < result.mean() < 1.0 and ref["sky"][result].any() and ref["surface"][result].any()
+    assert (fin["U"][result] == 0.25).all() and not fin["U"][~result].any() and cs.same(obs[0][2], fin["U"])
+    assert (fin["UN"][result][:, 0] == 1.0).all() and not fin["UN"][..., 1:].any() and not fin["UN"][~result].any()
+    # the low count and the sky's albedo take part where the op says so
+    _, with_n = display(head + [("setpixels", "Ln", 1.5), ("upsample", "H", "N", True, cs.WIDE_FALLBACK | cs.SKY_FROM_ALBEDO)])
+    ref2 = upsample_ref.upsample_ref(*[with_n[n] for n in ("Lc", "Lh", "Lm", "Li", "Gh", "Gn", "Gi")], low_count=with_n["Ln"], albedo=with_n["Ga"],
+                                     flags=cs.WIDE_FALLBACK | cs.SKY_FROM_ALBEDO)
+    assert cs.same(with_n["H"], ref2["color"]) and cs.same(with_n["N"], ref2["count"])
+    sky = ref2["sky"] & ref2["result"]
+    assert sky.any() and cs.same(with_n["H"][sky][:, :3], with_n["Ga"][sky][:, :3]) and (np.abs(with_n["N"][ref2["result"]][:, 0] - 1.5) < 1e-6).all()
+
+
+def test_display_coverage_counts_what_it_says():
+    """The analysis the seed set is held to, on programs small enough to count by hand."""
+    chain = [("meter", "C", 0, False, 1), ("bloom", "C", "X0", 0, 3, 0), ("tonemap", "X0", "X0", 0, "aces", 1.0)]
+    c = cs.display_coverage([("frame", None)] + chain + [("bind_sky", "S1"), ("frame", None)])
+    assert (c["input_deferred"], c["state_chain"], c["in_place_then_frame"], c["output_deferred"], c["writes_bound_result"]) == (1, 2, 1, 0, 0)
+    c = cs.display_coverage([("frame", None), ("get", "C")] + chain + [("get", "X0"), ("frame", None)])      # everything was submitted and waited for
+    assert (c["input_deferred"], c["state_chain"], c["in_place_then_frame"]) == (0, 0, 0)
+    c = cs.display_coverage([("frame", None), chain[0], ("state_get", 0)] + chain[1:])                       # a wait between the metering and its readers
+    assert (c["input_deferred"], c["state_chain"]) == (1, 0)
+    c = cs.display_coverage([("frame", None), ("tonemap", "C", "T0", None, "aces", 1.0), ("frame", None)])
+    assert (c["writes_bound_result"], c["output_deferred"], c["input_deferred"]) == (1, 1, 1)
+    c = cs.display_coverage([("frame", None), ("bind_result",), ("tonemap", "C", "T0", None, "aces", 1.0), ("frame", None)])
+    assert (c["writes_bound_result"], c["output_deferred"]) == (0, 1)                                         # (T0 is no longer the bound one)
+    c = cs.display_coverage([("frame", None), ("tonemap", "C", "T0", None, "aces", 1.0)])
+    assert (c["writes_bound_result"], c["output_deferred"]) == (0, 0)                                         # (no frame follows)
+    blooms = [("bloom", "Lc", "Ln", None, 3, 0), ("bloom", "C", "X0", None, 3, 0), ("bloom", "C", "X0", None, 1, 0), ("bloom", "S0", "S1", None, 3, 0),
+              ("bloom", "Lc", "Lc", None, 16, 0)]
+    assert cs.display_coverage(blooms)["pyramid_regrow"] == 2 and cs.display_coverage(blooms[::-1])["pyramid_regrow"] == 1
+    assert cs.pyramid_texels(24, 16, 3) == 12 * 8 + 6 * 4 + 3 * 2 < cs.pyramid_texels(64, 40, 3) < cs.pyramid_texels(128, 64, 3)
+    sky = [("tonemap", "C", "X1", None, "aces", 1.0), ("upsample", "U", "UN", False, 1), ("bloom", "C", "X2", None, 3, 0)]
+    c = cs.display_coverage(sky + [("bind_sky", "X1"), ("frame", "X0"), ("bind_sky", "UN"), ("frame", "X0"), ("frame", "X0")])
+    assert c["written_then_sky_traced"] == {"upsample": 1, "tonemap": 1, "bloom": 0}
+    c = cs.display_coverage(sky + [("setpixels", "X1", 0.25), ("bind_sky", "X1"), ("frame", "X0")])         # something else wrote it since
+    assert c["written_then_sky_traced"] == {"upsample": 0, "tonemap": 0, "bloom": 0}
+    c = cs.display_coverage([("bind_sky", "X2")] + sky + [("restart",), ("frame", "X0")])                     # bound before the write, too
+    assert c["written_then_sky_traced"] == {"upsample": 0, "tonemap": 0, "bloom": 0}
+    pairs = {(("C", 1), ("S0", 2)): 1, (("C", 1), ("X0", 1)): 0, (("C", 0), ("S0", 1)): 0, (("Lc", 3), ("C", 1)): 1}
+    for ((a, ja), (b, jb)), n in pairs.items():                  # another size and both rates below 1
+        assert cs.display_coverage([("meter", a, 0, False, ja), ("meter", b, 0, False, jb)])["two_meterings_rate_below_1"] == n, (a, ja, b, jb)
+    assert cs.display_coverage([("meter", "C", 0, False, 1), ("meter", "S0", 1, False, 1)])["two_meterings_rate_below_1"] == 0   # two states
