@@ -56,8 +56,10 @@ URT_API int urt_abi_version(void);                       /* bumps when this head
                                                             urt_buffer_set_data_device, urt_buffer_get_data_range,
                                                             urt_skin_vertices, urt_buffer_bounds, urt_debug_buffer_state — the
                                                             normals on the device, urt_buffer_copy, urt_reproject_deformed,
-                                                            urt_upsample, urt_auto_exposure, urt_tonemap and urt_bloom were added without
-                                                            changing anything that existed) */
+                                                            urt_upsample, urt_auto_exposure, urt_tonemap, urt_bloom and the blend
+                                                            shapes on the device — urt_morph_plan_create, urt_morph_plan_info,
+                                                            urt_morph_plan_release, urt_morph_vertices, urt_debug_build_morph_plan —
+                                                            were added without changing anything that existed) */
 URT_API int urt_device_count(int* out_count);
 /* One context per process and GPU (the one-process-per-GPU model).  device = HIP ordinal. */
 URT_API int urt_context_create(int device, urt_context** out_ctx);
@@ -222,6 +224,63 @@ URT_API int urt_compute_normals(urt_context* ctx, urt_handle plan, urt_handle ds
 URT_API int urt_debug_build_normals_plan(const float* vertices, int n_vertices, const int32_t* indices, int n_indices, int first, int count,
                                          int32_t* ranges, int32_t* entries, int cap_entries, int32_t* tris, int cap_tris,
                                          int32_t out_sizes[3]);
+
+/* ---- blend shapes on the device -----------------------------------------------------------------------------------------------------
+ * The first stage of a Unity SkinnedMeshRenderer: blend shapes (morph targets) — per-target vertex deltas, scaled by the target's weight
+ * and added to the rest pose BEFORE the bones.  A MORPH PLAN holds the deltas of all targets of the served vertices first ..
+ * first+count-1, laid out per vertex; urt_morph_vertices applies it to rest buffers under a weight table, into the device side of the
+ * destinations (which may be _Vertices / _Normals themselves, or intermediates that urt_skin_vertices takes as its rest pose).
+ * The plan's canonical form, which urt_debug_build_morph_plan returns:
+ *   order    the permutation of the input delta numbers sorted by vertex ascending, then target ascending, then input position
+ *            ascending: duplicates of one (vertex, target) pair are kept and all count; no delta is pruned, not even an all-zero one
+ *   ranges   {start, length} into order, one per served vertex (a vertex no delta names: length 0)
+ * NORMATIVE arithmetic: float32, one rounding per operation, no fma, evaluated as written.  For served vertex i, p = rest_vertices[i]
+ * and n = rest_normals[i]; over its entries e sequentially in plan order, with w = weights[e.target]: the entry is LIVE when w != 0.0f
+ * (a NaN weight is live); a live entry does, for r = 0, 1, 2,
+ *     p.r = p.r + w * e.dp[r]        n.r = n.r + w * e.dn[r]
+ * and an entry that is not live does nothing at all (-0.0f stays -0.0f, an infinite delta under weight 0 makes no NaN).  Then
+ * dst_vertices[i] = p and dst_normals[i] = n; with URT_MORPH_NORMALIZE, L2 = dot(n, n) of urt_math.h and dst_normals[i] = normalize(n) of
+ * urt_math.h when L2 > 0 and finite, else n as it is (the rule of urt_skin_vertices).  A vertex with no live entry gets its rest position
+ * bit for bit.  One vertex's sum is never split or tree-reduced: the order is the specification.  Non-finite inputs flow through the
+ * arithmetic and are never a fault and never an error.
+ * There are no urt_group_* twins of the calls of this section (urt_group_context reaches a rank's context). */
+typedef struct urt_MorphDelta {
+  int32_t vertex;   /* element number in the vertex buffers (absolute, not relative to `first`) */
+  int32_t target;   /* 0 .. n_targets-1 */
+  float dp[3];      /* position delta at weight 1 */
+  float dn[3];      /* normal delta at weight 1 */
+} urt_MorphDelta;   /* 32 bytes */
+typedef struct urt_MorphPlanInfo {
+  int32_t first, count, n_targets, n_entries, max_valence, n_touched;   /* n_touched: served vertices with at least one entry */
+  uint64_t device_bytes;
+} urt_MorphPlanInfo;   /* 32 bytes */
+enum { URT_MORPH_NORMALIZE = 1 };
+/* Makes a plan for the served vertices first .. first+count-1 from n_deltas deltas of n_targets targets; `deltas` is copied before the
+ * call returns.  The plan is independent of any buffer.  n_deltas == 0 and count == 0 are both legal.  URT_ERR_INVALID_ARGUMENT: NULL
+ * deltas with n_deltas > 0, a negative n_deltas or count, a negative first, a served range beyond 2^31 - 1, n_targets outside 1..4096,
+ * NULL out_plan; URT_ERR_SCENE: a vertex outside the served range, a target outside 0..n_targets-1; URT_ERR_OUT_OF_MEMORY.  On any
+ * error nothing stays allocated. */
+URT_API int urt_morph_plan_create(urt_context* ctx, const urt_MorphDelta* deltas, int n_deltas, int n_targets, int first, int count,
+                                  urt_handle* out_plan);
+URT_API int urt_morph_plan_info(urt_context* ctx, urt_handle plan, urt_MorphPlanInfo* out);
+/* Gives the plan's device memory back (urt_context_destroy does the same). */
+URT_API int urt_morph_plan_release(urt_context* ctx, urt_handle plan);
+/* Morphs the plan's served vertices.  rest_vertices, dst_vertices: stride 12; rest_normals, dst_normals: stride 12, rest_normals may be
+ * 0 exactly when dst_normals is 0 (then no normal is read or written); weights: stride 4 and a count equal to the plan's n_targets.  All
+ * 12-byte buffers have one common count, which is >= first+count.  Every buffer gets a mirror, as with urt_skin_vertices; ONE kernel is
+ * enqueued on the context's stream, nothing is synchronised and deferred frames stay deferred.  dst_*[first .. first+count-1] becomes
+ * stale and dirty as a whole, exactly as with urt_skin_vertices; rows outside the served range are not written.
+ * Checked before anything is enqueued or marked: URT_ERR_INVALID_HANDLE for an unknown plan and for a required handle that is 0 or
+ * unknown; URT_ERR_INVALID_ARGUMENT for unknown flags, URT_MORPH_NORMALIZE without dst_normals, dst_normals without rest_normals, strides
+ * or counts that do not fit, a destination equal to an input or to the other destination.  An empty plan (count == 0) returns URT_OK
+ * after the checks. */
+URT_API int urt_morph_vertices(urt_context* ctx, urt_handle plan, urt_handle rest_vertices, urt_handle rest_normals, urt_handle weights,
+                               urt_handle dst_vertices, urt_handle dst_normals, int flags);
+/* Host only, no GPU: the canonical plan above, for tests and for hosts that want to inspect it.  ranges takes 2 * count words, order
+ * n_deltas words; out_sizes = n_entries, max_valence, n_touched.  Every output pointer may be NULL.  Errors as urt_morph_plan_create
+ * (urt_host_last_error). */
+URT_API int urt_debug_build_morph_plan(const urt_MorphDelta* deltas, int n_deltas, int n_targets, int first, int count, int32_t* ranges,
+                                       int32_t* order, int32_t out_sizes[3]);
 
 /* ---- RenderTexture / Texture (RGBA32F = ARGBFloat, linear) -------------------------------- */
 /* new RenderTexture(w, h, 0, ARGBFloat, Linear){enableRandomWrite}.Create()   RM:834-840 */

@@ -37,6 +37,15 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_normals_plan_release(IntPtr ctx, ulong plan);
     [DllImport(Lib)] internal static extern int urt_compute_normals(IntPtr ctx, ulong plan, ulong dstNormals);
     [DllImport(Lib)] internal static extern int urt_debug_build_normals_plan(float[] vertices, int nVertices, int[] indices, int nIndices, int first, int count, [Out] int[] ranges, [Out] int[] entries, int capEntries, [Out] int[] tris, int capTris, [Out] int[] outSizes3);
+    // blend shapes on the device (include/urt.h): per-target vertex deltas added to the rest pose under a weight table, ahead of the bones
+    [StructLayout(LayoutKind.Sequential)] internal struct MorphDelta { public int vertex, target; public float dpx, dpy, dpz, dnx, dny, dnz; }   // 32 B; vertex is absolute
+    [StructLayout(LayoutKind.Sequential)] internal struct MorphPlanInfo { public int first, count, nTargets, nEntries, maxValence, nTouched; public ulong deviceBytes; }   // 32 B
+    internal const int MorphNormalize = 1;   // URT_MORPH_NORMALIZE
+    [DllImport(Lib)] internal static extern int urt_morph_plan_create(IntPtr ctx, MorphDelta[] deltas, int nDeltas, int nTargets, int first, int count, out ulong plan);
+    [DllImport(Lib)] internal static extern int urt_morph_plan_info(IntPtr ctx, ulong plan, out MorphPlanInfo info);
+    [DllImport(Lib)] internal static extern int urt_morph_plan_release(IntPtr ctx, ulong plan);
+    [DllImport(Lib)] internal static extern int urt_morph_vertices(IntPtr ctx, ulong plan, ulong restVertices, ulong restNormals, ulong weights, ulong dstVertices, ulong dstNormals, int flags);
+    [DllImport(Lib)] internal static extern int urt_debug_build_morph_plan(MorphDelta[] deltas, int nDeltas, int nTargets, int first, int count, [Out] int[] ranges, [Out] int[] order, [Out] int[] outSizes3);
     [DllImport(Lib)] internal static extern int urt_buffer_get_info(IntPtr ctx, ulong buffer, out int count, out int stride);
     [DllImport(Lib)] internal static extern int urt_buffer_release(IntPtr ctx, ulong buffer);
 

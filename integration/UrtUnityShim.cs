@@ -526,7 +526,7 @@ public sealed class UrtComputeBuffer {
 /// _Vertices / _Normals buffers and the library refits the skinned meshes in place (option "refit_vertices").  On one context only: a
 /// group host reaches the ranks through urt_group_context.
 public sealed class UrtSkinnedMesh {
-    sealed class Skin { public int first, count; public ulong bones; public int nBones; }
+    sealed class Skin { public int first, count; public ulong bones; public int nBones; public bool morphed; }   // morphed: MorphMesh(intoRestPose) has written this frame's rest pose
     readonly UrtComputeBuffer restVertices, restNormals, boneIndices, boneWeights;
     readonly Dictionary<int, Skin> skins = new Dictionary<int, Skin>();
     public UrtSkinnedMesh(int vertexCount) {
@@ -568,7 +568,9 @@ public sealed class UrtSkinnedMesh {
             GCHandle pin = GCHandle.Alloc(kv.Value, GCHandleType.Pinned);
             try { UrtDevice.Check(UrtNative.urt_buffer_set_data(ctx, s.bones, pin.AddrOfPinnedObject(), nBones)); }
             finally { pin.Free(); }
-            var sb = new UrtNative.SkinBuffers { restVertices = restVertices.handle, restNormals = normals != null ? restNormals.handle : 0,
+            UrtComputeBuffer rv = s.morphed ? morphedVertices : restVertices, rn = s.morphed ? morphedNormals : restNormals;   // blend shapes come before the bones
+            s.morphed = false;
+            var sb = new UrtNative.SkinBuffers { restVertices = rv.handle, restNormals = normals != null ? rn.handle : 0,
                                                  boneIndices = boneIndices.handle, boneWeights = boneWeights.handle, bones = s.bones };
             UrtDevice.Check(UrtNative.urt_skin_vertices(ctx, in sb, s.first, s.count, vertices.handle, normals != null ? normals.handle : 0));
         }
@@ -581,8 +583,70 @@ public sealed class UrtSkinnedMesh {
         }
         return boxes;
     }
+    // ---- blend shapes (include/urt.h urt_morph_vertices): the stage of a SkinnedMeshRenderer that comes before the bones ----
+    sealed class Morph { public int first, count, nTargets; public ulong plan, weights; public float[] frameWeights; }
+    readonly Dictionary<int, Morph> morphs = new Dictionary<int, Morph>();
+    UrtComputeBuffer morphedVertices, morphedNormals;                 // what a morph ahead of a skin writes and the skin reads: device side only
+    /// The vertex span of MeshObject meshIndex (the one AttachSkin named, or `first` on) gets the blend shapes of renderer.sharedMesh:
+    /// sharedMesh.blendShapeCount targets, each the LAST frame of its shape (GetBlendShapeFrameVertices of frame
+    /// GetBlendShapeFrameCount - 1), whose weight is GetBlendShapeWeight / GetBlendShapeFrameWeight of that frame.  In-between frames
+    /// are out of scope: a shape with several frames is blended linearly from the rest pose to its last frame.  Rows whose six deltas are
+    /// all zero are dropped.  The rest pose is the one AttachSkin uploaded, or mesh.vertices / mesh.normals for a mesh without a skin.
+    public void AttachBlendShapes(int meshIndex, int first, SkinnedMeshRenderer renderer) {
+        Mesh mesh = renderer.sharedMesh;
+        int count = mesh.vertexCount, nTargets = mesh.blendShapeCount;
+        if (nTargets < 1) throw new ArgumentException("UrtSkinnedMesh.AttachBlendShapes: the mesh has no blend shapes");
+        if (!skins.ContainsKey(meshIndex)) {
+            restVertices.SetData(new List<Vector3>(mesh.vertices), 0, first, count);
+            restNormals.SetData(new List<Vector3>(mesh.normals), 0, first, count);
+        }
+        var deltas = new List<UrtNative.MorphDelta>();
+        var frameWeights = new float[nTargets];
+        Vector3[] dp = new Vector3[count], dn = new Vector3[count], dt = new Vector3[count];
+        for (int t = 0; t < nTargets; t++) {
+            int last = mesh.GetBlendShapeFrameCount(t) - 1;
+            frameWeights[t] = mesh.GetBlendShapeFrameWeight(t, last);
+            mesh.GetBlendShapeFrameVertices(t, last, dp, dn, dt);    // (tangents are not carried)
+            for (int v = 0; v < count; v++)
+                if (dp[v].x != 0f || dp[v].y != 0f || dp[v].z != 0f || dn[v].x != 0f || dn[v].y != 0f || dn[v].z != 0f)   // (component by component: Vector3's == is approximate)
+                    deltas.Add(new UrtNative.MorphDelta { vertex = first + v, target = t, dpx = dp[v].x, dpy = dp[v].y, dpz = dp[v].z,
+                                                          dnx = dn[v].x, dny = dn[v].y, dnz = dn[v].z });
+        }
+        if (morphs.TryGetValue(meshIndex, out Morph old)) ReleaseMorph(old);
+        var m = new Morph { first = first, count = count, nTargets = nTargets, frameWeights = frameWeights };
+        UrtDevice.Check(UrtNative.urt_morph_plan_create(UrtDevice.Handle, deltas.ToArray(), deltas.Count, nTargets, first, count, out m.plan));
+        UrtDevice.Check(UrtNative.urt_buffer_create(UrtDevice.Handle, nTargets, 4, out m.weights));
+        morphs[meshIndex] = m;
+    }
+    /// Uploads renderer.GetBlendShapeWeight(t) / frameWeight(t) for every target and morphs the span.  Ahead of SkinMeshes (intoRestPose):
+    /// into a pair of intermediate buffers that SkinMeshes then takes as this mesh's rest pose, so blend shapes come before the bones and
+    /// the morphed rest pose never crosses the bus.  Else straight into `vertices` / `normals` (normals normalised); then the caller owes
+    /// the bounds and the heap as after SkinMeshes (urt_buffer_bounds).
+    public void MorphMesh(int meshIndex, SkinnedMeshRenderer renderer, bool intoRestPose, UrtComputeBuffer vertices, UrtComputeBuffer normals) {
+        if (!morphs.TryGetValue(meshIndex, out Morph m)) throw new ArgumentException("UrtSkinnedMesh.MorphMesh: MeshObject " + meshIndex + " has no blend shapes (AttachBlendShapes)");
+        var w = new float[m.nTargets];
+        for (int t = 0; t < m.nTargets; t++) w[t] = renderer.GetBlendShapeWeight(t) / m.frameWeights[t];
+        GCHandle pin = GCHandle.Alloc(w, GCHandleType.Pinned);
+        try { UrtDevice.Check(UrtNative.urt_buffer_set_data(UrtDevice.Handle, m.weights, pin.AddrOfPinnedObject(), m.nTargets)); }
+        finally { pin.Free(); }
+        if (intoRestPose) {
+            if (morphedVertices == null) { morphedVertices = new UrtComputeBuffer(restVertices.count, 12); morphedNormals = new UrtComputeBuffer(restVertices.count, 12); }
+            UrtDevice.Check(UrtNative.urt_morph_vertices(UrtDevice.Handle, m.plan, restVertices.handle, restNormals.handle, m.weights,
+                                                         morphedVertices.handle, morphedNormals.handle, 0));
+            if (skins.TryGetValue(meshIndex, out Skin s)) s.morphed = true;
+        } else {
+            UrtDevice.Check(UrtNative.urt_morph_vertices(UrtDevice.Handle, m.plan, restVertices.handle, normals != null ? restNormals.handle : 0, m.weights,
+                                                         vertices.handle, normals != null ? normals.handle : 0, normals != null ? UrtNative.MorphNormalize : 0));
+        }
+    }
+    void ReleaseMorph(Morph m) {
+        if (m.plan != 0) { UrtDevice.Check(UrtNative.urt_morph_plan_release(UrtDevice.Handle, m.plan)); m.plan = 0; }
+        if (m.weights != 0) { UrtDevice.Check(UrtNative.urt_buffer_release(UrtDevice.Handle, m.weights)); m.weights = 0; }
+    }
     public void Release() {
         foreach (var s in skins.Values) if (s.bones != 0) { UrtDevice.Check(UrtNative.urt_buffer_release(UrtDevice.Handle, s.bones)); s.bones = 0; }
+        foreach (var m in morphs.Values) ReleaseMorph(m);
+        if (morphedVertices != null) { morphedVertices.Release(); morphedNormals.Release(); morphedVertices = morphedNormals = null; }
         restVertices.Release(); restNormals.Release(); boneIndices.Release(); boneWeights.Release();
     }
 }

@@ -17,12 +17,12 @@ ERROR_NAMES = {1: "INVALID_ARGUMENT", 2: "INVALID_HANDLE", 3: "NO_DEVICE", 4: "H
 # every symbol include/urt.h declares (tests check that the .so exports each of them)
 ABI_SYMBOLS = [
     "urt_abi_version", "urt_device_count", "urt_context_create", "urt_context_destroy", "urt_last_error", "urt_context_set_stream",
-    "urt_synchronize", "urt_flush", "urt_buffer_create", "urt_buffer_set_data", "urt_buffer_set_data_range", "urt_buffer_set_data_device", "urt_buffer_get_data_range", "urt_buffer_copy", "urt_skin_vertices", "urt_buffer_bounds", "urt_normals_plan_create", "urt_normals_plan_info", "urt_normals_plan_release", "urt_compute_normals", "urt_buffer_get_info", "urt_buffer_release", "urt_texture_create",
+    "urt_synchronize", "urt_flush", "urt_buffer_create", "urt_buffer_set_data", "urt_buffer_set_data_range", "urt_buffer_set_data_device", "urt_buffer_get_data_range", "urt_buffer_copy", "urt_skin_vertices", "urt_buffer_bounds", "urt_normals_plan_create", "urt_normals_plan_info", "urt_normals_plan_release", "urt_compute_normals", "urt_morph_plan_create", "urt_morph_plan_info", "urt_morph_plan_release", "urt_morph_vertices", "urt_buffer_get_info", "urt_buffer_release", "urt_texture_create",
     "urt_texture_create_external", "urt_texture_set_pixels", "urt_texture_get_pixels", "urt_texture_get_info", "urt_texture_read_begin", "urt_texture_read_end", "urt_texture_read_begin_format", "urt_texture_read_end_format", "urt_texture_release",
     "urt_shader_set_buffer", "urt_shader_set_texture", "urt_shader_set_matrix", "urt_shader_set_vector", "urt_shader_set_float",
     "urt_shader_set_int", "urt_shader_dispatch", "urt_shader_dispatch_rows", "urt_blit_add", "urt_blit", "urt_texture_pack_rows",
     "urt_texture_unpack_rows", "urt_texture_unpack_rows_on", "urt_texture_pack_rows_rgb", "urt_texture_unpack_rows_rgb", "urt_ray_query", "urt_ray_query_device", "urt_radiance_query", "urt_radiance_query_device", "urt_render_aov", "urt_denoise", "urt_reproject", "urt_reproject_objects", "urt_reproject_deformed", "urt_blit_add_history", "urt_upsample", "urt_auto_exposure", "urt_tonemap", "urt_bloom", "urt_select_pixels", "urt_blend_samples", "urt_resample_below", "urt_set_option", "urt_get_counters", "urt_reset_counters", "urt_debug_build_blas", "urt_debug_get_blas", "urt_debug_blas_cache_stats",
-    "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_read_scene_cones", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_deform_stats", "urt_debug_scene_cost", "urt_debug_buffer_state", "urt_debug_live_resources", "urt_debug_build_walk_table", "urt_debug_build_normals_plan", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
+    "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_read_scene_cones", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_deform_stats", "urt_debug_scene_cost", "urt_debug_buffer_state", "urt_debug_live_resources", "urt_debug_build_walk_table", "urt_debug_build_normals_plan", "urt_debug_build_morph_plan", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
     "urt_host_build_object_bvh", "urt_host_build_object_bvh_pairing", "urt_host_mesh_motion", "urt_host_sphere_motion", "urt_host_last_error", "urt_host_load_hdr", "urt_host_write_pfm", "urt_host_write_png", "urt_host_encode_srgb8", "urt_host_srgb8_first_floats",
     "urt_host_resize_rgba", "urt_host_io_last_error", "urt_host_log", "urt_host_log_scene_counts", "urt_host_log_tree_report", "urt_host_dump_bvh", "urt_host_dump_normals",
     "urt_host_debug_last_error",
@@ -121,6 +121,21 @@ class SkinBuffers(C.Structure):
 class NormalsPlanInfo(C.Structure):
     """urt_NormalsPlanInfo (include/urt.h), 32 B: what urt_normals_plan_info reports of a normals plan."""
     _fields_ = [(n, C.c_int32) for n in ("first", "count", "n_lists", "n_triangles", "n_entries", "max_valence")] + [("device_bytes", C.c_uint64)]
+
+
+class MorphDelta(C.Structure):
+    """urt_MorphDelta (include/urt.h), 32 B: one target's delta of one vertex (absolute vertex number) at weight 1."""
+    _fields_ = [("vertex", C.c_int32), ("target", C.c_int32), ("dp", C.c_float * 3), ("dn", C.c_float * 3)]
+
+
+MORPH_DELTA_DT = [("vertex", "<i4"), ("target", "<i4"), ("dp", "<f4", (3,)), ("dn", "<f4", (3,))]      # the same 32 bytes as a numpy dtype
+MORPH_NORMALIZE = 1                                         # URT_MORPH_NORMALIZE
+MORPH_MAX_TARGETS = 4096
+
+
+class MorphPlanInfo(C.Structure):
+    """urt_MorphPlanInfo (include/urt.h), 32 B: what urt_morph_plan_info reports of a morph plan."""
+    _fields_ = [(n, C.c_int32) for n in ("first", "count", "n_targets", "n_entries", "max_valence", "n_touched")] + [("device_bytes", C.c_uint64)]
 
 
 class UpsampleParams(C.Structure):
@@ -241,6 +256,11 @@ def load():
         "urt_normals_plan_release": ([vp, u64], i),
         "urt_compute_normals": ([vp, u64, u64], i),
         "urt_debug_build_normals_plan": ([vp, i, vp, i, i, i, vp, vp, i, vp, i, vp], i),
+        "urt_morph_plan_create": ([vp, vp, i, i, i, i, C.POINTER(u64)], i),
+        "urt_morph_plan_info": ([vp, u64, C.POINTER(MorphPlanInfo)], i),
+        "urt_morph_plan_release": ([vp, u64], i),
+        "urt_morph_vertices": ([vp, u64, u64, u64, u64, u64, u64, i], i),
+        "urt_debug_build_morph_plan": ([vp, i, i, i, i, vp, vp, vp], i),
         "urt_buffer_get_info": ([vp, u64, pi, pi], i),
         "urt_buffer_release": ([vp, u64], i),
         "urt_texture_create": ([vp, i, i, C.POINTER(u64)], i),

@@ -14,6 +14,8 @@
 #include <limits>
 #include <memory>
 
+#include "morph.h"
+#include "morph_plan.h"
 #include "normals.h"
 #include "normals_plan.h"
 #include "present.h"
@@ -520,6 +522,120 @@ int urt_compute_normals(urt_context* ctx, urt_handle plan, urt_handle dst_normal
   URT_HIP(ctx, compute_normals((const float*)v->mirror.get(), d.tris.get(), d.n_triangles, d.ranges.get(), d.entries.get(), d.first, d.count,
                                ctx->nm_face.get(), (float*)dst->mirror.get(), touch(ctx)));
   mark_device_written(ctx, dst_normals, *dst, d.first, d.count);
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+/* ---- blend shapes on the device (include/urt.h; csrc/morph_plan.h, csrc/morph.hip) ---- */
+static_assert(sizeof(urt_MorphDelta) == 32 && sizeof(urtd::MorphDeltaIn) == 32 && sizeof(urt_MorphPlanInfo) == 32, "include/urt.h: morph layouts");
+
+int urt_morph_plan_create(urt_context* ctx, const urt_MorphDelta* deltas, int n_deltas, int n_targets, int first, int count, urt_handle* out_plan) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (!out_plan) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_plan_create: out_plan is NULL");
+  *out_plan = 0;
+  URT_GUARD_BEGIN
+  if (n_deltas < 0 || count < 0 || first < 0 || (long long)first + (long long)count > 0x7fffffffLL)
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_plan_create: a negative n_deltas, first or count, or a served range beyond 2^31 - 1");
+  if (n_deltas > 0 && !deltas) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_plan_create: deltas is NULL");
+  if (n_targets < 1 || n_targets > kMorphMaxTargets) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_plan_create: n_targets is outside 1..4096");
+  const MorphDeltaIn* in = (const MorphDeltaIn*)deltas;
+  MorphPlan plan;
+  if (const int rc = morph_plan_build(in, n_deltas, n_targets, first, count, plan))
+    return fail(ctx, URT_ERR_SCENE, rc == kMorphPlanBadVertex ? "morph_plan_create: a delta names a vertex outside the served range"
+                                                               : "morph_plan_create: a delta names a target outside 0..n_targets-1");
+  // the entries in plan order, as csrc/morph.hip reads them: this is the copy of `deltas`
+  std::vector<int32_t> targets((size_t)n_deltas);
+  std::vector<float> values(6 * (size_t)n_deltas);
+  for (size_t e = 0; e < (size_t)n_deltas; e++) {
+    const MorphDeltaIn& d = in[plan.order[e]];
+    targets[e] = d.target;
+    std::memcpy(&values[6 * e], d.dp, 12);
+    std::memcpy(&values[6 * e + 3], d.dn, 12);
+  }
+  DevMorphPlan d;
+  d.first = first; d.count = count; d.n_targets = n_targets; d.n_entries = n_deltas; d.max_valence = plan.max_valence; d.n_touched = plan.n_touched;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  const auto upload = [&](auto& buf, const auto& host) -> hipError_t {       // (a failure leaves through the holders: nothing stays allocated)
+    if (host.empty()) return hipSuccess;
+    const size_t bytes = host.size() * sizeof(host[0]);
+    if (hipError_t e = buf.alloc(host.size())) return e;
+    d.device_bytes += bytes;
+    return hipMemcpy(buf.get(), host.data(), bytes, hipMemcpyHostToDevice);
+  };
+  URT_HIP(ctx, upload(d.ranges, plan.ranges));
+  URT_HIP(ctx, upload(d.targets, targets));
+  URT_HIP(ctx, upload(d.deltas, values));
+  const urt_handle h = ctx->next_id++;
+  ctx->morph_plans.emplace(h, std::move(d));
+  *out_plan = h;
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+int urt_morph_plan_info(urt_context* ctx, urt_handle plan, urt_MorphPlanInfo* out) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  auto it = ctx->morph_plans.find(plan);
+  if (it == ctx->morph_plans.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "morph_plan_info: unknown plan handle");
+  if (!out) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_plan_info: out is NULL");
+  const DevMorphPlan& d = it->second;
+  out->first = d.first; out->count = d.count; out->n_targets = d.n_targets; out->n_entries = d.n_entries;
+  out->max_valence = d.max_valence; out->n_touched = d.n_touched; out->device_bytes = d.device_bytes;
+  return URT_OK;
+}
+
+int urt_morph_plan_release(urt_context* ctx, urt_handle plan) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  auto it = ctx->morph_plans.find(plan);
+  if (it == ctx->morph_plans.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "morph_plan_release: unknown plan handle");
+  if (it->second.device_bytes) {                             // kernels queued on the stream may still read the plan
+    URT_HIP(ctx, hipSetDevice(ctx->device));
+    URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
+  }
+  ctx->morph_plans.erase(it);
+  return URT_OK;
+}
+
+int urt_morph_vertices(urt_context* ctx, urt_handle plan, urt_handle rest_vertices, urt_handle rest_normals, urt_handle weights,
+                       urt_handle dst_vertices, urt_handle dst_normals, int flags) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  auto it = ctx->morph_plans.find(plan);
+  if (it == ctx->morph_plans.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "morph_vertices: unknown plan handle");
+  const DevMorphPlan& d = it->second;
+  if (flags & ~URT_MORPH_NORMALIZE) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_vertices: unknown flags");
+  const bool normals = dst_normals != 0;
+  if ((flags & URT_MORPH_NORMALIZE) && !normals) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_vertices: URT_MORPH_NORMALIZE without dst_normals");
+  if (normals && !rest_normals) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_vertices: dst_normals without rest_normals");
+  enum { kRestV, kRestN, kWeights, kDstV, kDstN, kArgs };
+  const urt_handle h[kArgs] = {rest_vertices, normals ? rest_normals : 0, weights, dst_vertices, dst_normals};
+  const char* const name[kArgs] = {"rest_vertices", "rest_normals", "weights", "dst_vertices", "dst_normals"};
+  const int stride[kArgs] = {12, 12, 4, 12, 12};
+  Buffer* b[kArgs];
+  for (int k = 0; k < kArgs; k++) {
+    b[k] = nullptr;
+    if (!normals && (k == kRestN || k == kDstN)) continue;
+    b[k] = find_buffer(ctx, h[k]);
+    if (!b[k]) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string("morph_vertices: ") + name[k] + " is 0 or an unknown buffer handle");
+  }
+  if (!normals && rest_normals && !find_buffer(ctx, rest_normals))
+    return fail(ctx, URT_ERR_INVALID_HANDLE, "morph_vertices: rest_normals is an unknown buffer handle");
+  for (int k = 0; k < kArgs; k++) {
+    if (!b[k]) continue;
+    if (b[k]->stride != stride[k]) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("morph_vertices: the stride of ") + name[k] + " is not " + std::to_string(stride[k]));
+    if (k != kWeights && b[k]->count != b[kRestV]->count) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("morph_vertices: the count of ") + name[k] + " is not that of rest_vertices");
+    if (k < kDstV && (h[k] == dst_vertices || h[k] == dst_normals)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("morph_vertices: ") + name[k] + " is also a destination");
+  }
+  if (normals && dst_normals == dst_vertices) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_vertices: dst_vertices and dst_normals are one buffer");
+  if (b[kWeights]->count != d.n_targets) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_vertices: the count of weights is not the plan's n_targets");
+  if (int rc = check_element_range(ctx, "morph_vertices", *b[kRestV], d.first, d.count)) return rc;
+  if (d.count == 0) return URT_OK;
+  for (int k = 0; k < kArgs; k++) if (b[k]) if (int rc = buffer_mirror(ctx, *b[k])) return rc;
+  URT_HIP(ctx, morph_vertices((const float*)b[kRestV]->mirror.get(), normals ? (const float*)b[kRestN]->mirror.get() : nullptr, d.ranges.get(),
+                              d.targets.get(), d.deltas.get(), (const float*)b[kWeights]->mirror.get(), d.first, d.count,
+                              (float*)b[kDstV]->mirror.get(), normals ? (float*)b[kDstN]->mirror.get() : nullptr,
+                              (flags & URT_MORPH_NORMALIZE) != 0, touch(ctx)));
+  mark_device_written(ctx, dst_vertices, *b[kDstV], d.first, d.count);
+  if (normals) mark_device_written(ctx, dst_normals, *b[kDstN], d.first, d.count);
   return URT_OK;
   URT_GUARD_END(ctx)
 }

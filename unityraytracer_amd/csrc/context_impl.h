@@ -79,6 +79,15 @@ struct DevNormalsPlan {
   uint64_t device_bytes = 0;
 };
 
+// urt_morph_plan_create: a morph plan (csrc/morph_plan.h) as the device holds it, entries in plan order: the targets apart from the
+// deltas, so that a lane reads an entry's 24 bytes of deltas only when its weight is live (csrc/morph.hip).  It names no buffer.
+struct DevMorphPlan {
+  int first = 0, count = 0, n_targets = 0, n_entries = 0, max_valence = 0, n_touched = 0;
+  DeviceBuf<int32_t> ranges, targets;    // {start, length} per served vertex; one target per entry
+  DeviceBuf<float> deltas;               // dp[3], dn[3] per entry
+  uint64_t device_bytes = 0;
+};
+
 enum BindSlot { B_MESHOBJECTS, B_VERTICES, B_INDICES, B_NORMALS, B_SPHERES, B_MESHBVH, B_SPHEREBVH, B_COUNT };
 
 }  // namespace urtd
@@ -91,6 +100,7 @@ struct urt_context {
   std::unordered_map<urt_handle, urtd::Buffer> buffers;
   std::unordered_map<urt_handle, urtd::Texture> textures;
   std::unordered_map<urt_handle, urtd::DevNormalsPlan> normals_plans;
+  std::unordered_map<urt_handle, urtd::DevMorphPlan> morph_plans;
   urt_handle next_id = 1;
 
   urt_handle bound[urtd::B_COUNT] = {0, 0, 0, 0, 0, 0, 0};

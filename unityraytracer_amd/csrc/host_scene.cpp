@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/urt.h"
+#include "morph_plan.h"
 #include "normals_plan.h"
 
 namespace {
@@ -268,6 +269,25 @@ int urt_debug_build_normals_plan(const float* vertices, int n_vertices, const in
     if (tris && nt) std::memcpy(tris, plan.tris.data(), 3 * nt * sizeof(int32_t));
     return URT_OK;
   } catch (...) { return host_fail(URT_ERR_OUT_OF_MEMORY, "normals plan: allocation failed"); }
+}
+
+int urt_debug_build_morph_plan(const urt_MorphDelta* deltas, int n_deltas, int n_targets, int first, int count, int32_t* ranges, int32_t* order,
+                               int32_t out_sizes[3]) {
+  static_assert(sizeof(urt_MorphDelta) == sizeof(urtd::MorphDeltaIn), "include/urt.h urt_MorphDelta");
+  if (n_deltas < 0 || count < 0 || first < 0 || (long long)first + (long long)count > 0x7fffffffLL)
+    return host_fail(URT_ERR_INVALID_ARGUMENT, "morph plan: a negative n_deltas, first or count, or a served range beyond 2^31 - 1");
+  if (n_deltas > 0 && !deltas) return host_fail(URT_ERR_INVALID_ARGUMENT, "morph plan: deltas is NULL");
+  if (n_targets < 1 || n_targets > urtd::kMorphMaxTargets) return host_fail(URT_ERR_INVALID_ARGUMENT, "morph plan: n_targets is outside 1..4096");
+  try {
+    urtd::MorphPlan plan;
+    if (const int rc = urtd::morph_plan_build((const urtd::MorphDeltaIn*)deltas, n_deltas, n_targets, first, count, plan))
+      return host_fail(URT_ERR_SCENE, rc == urtd::kMorphPlanBadVertex ? "morph plan: a delta names a vertex outside the served range"
+                                                                      : "morph plan: a delta names a target outside 0..n_targets-1");
+    if (out_sizes) { out_sizes[0] = (int32_t)plan.order.size(); out_sizes[1] = plan.max_valence; out_sizes[2] = plan.n_touched; }
+    if (ranges && count) std::memcpy(ranges, plan.ranges.data(), plan.ranges.size() * sizeof(int32_t));
+    if (order && n_deltas) std::memcpy(order, plan.order.data(), plan.order.size() * sizeof(int32_t));
+    return URT_OK;
+  } catch (...) { return host_fail(URT_ERR_OUT_OF_MEMORY, "morph plan: allocation failed"); }
 }
 
 int urt_host_mesh_leaf_bounds(const void* mesh_objects, int n_meshes, const float* vertices, int n_vertices, const int32_t* indices,

@@ -46,6 +46,29 @@ def normals_plan(vertices, indices, first: int = 0, count: int | None = None) ->
     return {"ranges": ranges, "entries": entries, "tris": tris, "max_valence": int(sizes[2])}
 
 
+def morph_deltas(deltas) -> np.ndarray:
+    """`deltas` as a contiguous array of urt_MorphDelta (_lib.MORPH_DELTA_DT): such an array as it is, or a sequence of
+    (vertex, target, dp[3], dn[3])."""
+    dt = np.dtype(_lib.MORPH_DELTA_DT)
+    if isinstance(deltas, np.ndarray) and deltas.dtype == dt:
+        return np.ascontiguousarray(deltas).reshape(-1)
+    out = np.zeros(len(deltas), dtype=dt)
+    for k, (vertex, target, dp, dn) in enumerate(deltas):
+        out[k] = (vertex, target, dp, dn)
+    return out
+
+
+def morph_plan(deltas, n_targets: int, first: int, count: int) -> dict:
+    """The canonical morph plan of include/urt.h for the served vertices first .. first + count - 1 (urt_debug_build_morph_plan; no
+    GPU): ranges (count, 2), order (n_deltas), n_entries, max_valence, n_touched."""
+    lib = _lib.load()
+    d = morph_deltas(deltas)
+    ranges, order = np.zeros((max(int(count), 0), 2), dtype=np.int32), np.zeros(len(d), dtype=np.int32)
+    sizes = np.zeros(3, dtype=np.int32)
+    _check(lib, lib.urt_debug_build_morph_plan(_p(d), len(d), int(n_targets), int(first), int(count), _p(ranges), _p(order), _p(sizes)))
+    return {"ranges": ranges, "order": order, "n_entries": int(sizes[0]), "max_valence": int(sizes[1]), "n_touched": int(sizes[2])}
+
+
 def mesh_leaf_bounds(mesh_objects, vertices, indices, literal: bool = False) -> np.ndarray:
     """SetupBVHLeaves(List<MeshObject>) (RM:405-433); literal=True keeps the reference's quirks."""
     lib = _lib.load()

@@ -22,7 +22,7 @@ import numpy as np
 
 from dataclasses import dataclass, field
 
-from . import host_scene, scenes
+from . import _lib, host_scene, scenes
 from .unity_api import ComputeBuffer, ComputeShader, Context, Graphics, Material, RenderTexture, _matrix16, _max_history_arg, \
     _number_arg, denoise_params, reproject_params
 
@@ -95,6 +95,9 @@ class RayTraceMaster:
         self._boneBuffers = {}                       # SkinMeshes: MeshObject index -> its bone table (ComputeBuffer)
         self._skinBoxes = {}                         # SkinMeshes: MeshObject index -> object-space (min, max) of its skinned span, from the GPU
         self._boxCache = {}                          # SkinMeshes: MeshObject index -> (matrix bytes, id of the vertex list, world lo, world hi)
+        self._morphs = {}                            # AttachBlendShapes: MeshObject index -> its span, rest pose, deltas, target count and (from the first MorphMeshes on) MorphPlan
+        self._morphBuffers = None                    # MorphMeshes: rest vertices, rest normals, and the pair a morph ahead of a skin writes into (ComputeBuffers of the vertex count)
+        self._morphWeightBuffers = {}                # MorphMeshes: MeshObject index -> its weight table (ComputeBuffer)
         self._normalsPlans = {}                      # RecomputeNormals: MeshObject index -> ((vertex buffer, index buffer, first, last), NormalsPlan, the index list it was made for)
 
     # RM:215-230
@@ -902,23 +905,46 @@ class RayTraceMaster:
     # keep_history: as DeformMeshes' — the snapshot of the vertex buffer is a device-to-device copy, so the positions still never cross
     # the bus.
     def SkinMeshes(self, poses, recompute_normals: bool = False, keep_history: bool = False):
-        s = self.scene
         poses = dict(poses)
         if self._treesNeedRebuilding and self._rayTraceObjects:
             self.RebuildObjectLists()
+        checked = self._checked_poses(poses, "SkinMeshes")
+
+        def skin():
+            self._ensure_skin_buffers()
+            rest_v, rest_n, idx, wgt = self._skinBuffers
+            for k, a in checked.items():
+                lo, hi = self._skins[k]["span"]
+                if hi < lo:
+                    continue
+                self._boneBuffers[k] = self.CreateComputeBuffer(self._boneBuffers.get(k), a, 48)
+                self.ctx.skin_vertices(rest_v, rest_n, idx, wgt, self._boneBuffers[k], lo, hi - lo + 1, self._vertexBuffer,
+                                       None if recompute_normals else self._normalBuffer)
+        self._deform_on_device({k: self._skins[k]["span"] for k in checked}, skin, recompute_normals, keep_history)
+
+    def _checked_poses(self, poses, who: str):
+        """poses = {MeshObject index: (n_bones, 12)} of meshes that have a skin -> {int: float32 array}, or the error SkinMeshes raises."""
         checked = {}
         for k, bones in poses.items():
-            self._mesh_index_arg(k, "SkinMeshes", "the keys of poses")
+            self._mesh_index_arg(k, who, "the keys of poses")
             if int(k) not in self._skins:
-                raise ValueError(f"SkinMeshes: MeshObject {k} has no skin (AttachSkin)")
+                raise ValueError(f"{who}: MeshObject {k} has no skin (AttachSkin)")
             try:
                 a = np.ascontiguousarray(bones, dtype=np.float32)
             except (TypeError, ValueError):
-                raise ValueError(f"SkinMeshes: poses[{k}] must be an (n_bones, 12) array") from None
+                raise ValueError(f"{who}: poses[{k}] must be an (n_bones, 12) array") from None
             if a.ndim != 2 or a.shape[1] != 12 or a.shape[0] < 1:
-                raise ValueError(f"SkinMeshes: poses[{k}] must have shape (n_bones, 12) with n_bones >= 1, not {a.shape}")
+                raise ValueError(f"{who}: poses[{k}] must have shape (n_bones, 12) with n_bones >= 1, not {a.shape}")
             checked[int(k)] = a
-        if self._treesNeedRebuilding:                                             # the buffers the skin writes into must exist
+        return checked
+
+    # The protocol SkinMeshes and MorphMeshes share, for meshes whose vertex spans (spans = {MeshObject index: (lo, hi)}) a device-side
+    # deformation rewrites: the previous feature buffers, the optional snapshot, deform() — which enqueues the deformation into the
+    # device side of the vertex (and normal) buffer —, the optional RecomputeNormals, the spans' bounds from the GPU, the object-level
+    # heap, the new feature buffers and the reprojection.  The arguments were checked by the caller.
+    def _deform_on_device(self, spans, deform, recompute_normals: bool, keep_history: bool):
+        s = self.scene
+        if self._treesNeedRebuilding:                                             # the buffers the deformation writes into must exist
             self._bind_for_queries()
         history = self._temporal is not None and self._converged is not None and self._currentSample > 0 \
             and (self._converged.width, self._converged.height) == (self.screen_width, self.screen_height)
@@ -928,47 +954,163 @@ class RayTraceMaster:
             prev, cur = self._taov
             self.SetShaderParameters()
             self.ctx.render_aov(prev[0], prev[1], None, prev[2])               # the scene as the history saw it
-        keep = bool(keep_history) and history and bool(checked)
+        keep = bool(keep_history) and history and bool(spans)
         if keep:
             self._snapshot_for_deform()
-        self._ensure_skin_buffers()
-        rest_v, rest_n, idx, wgt = self._skinBuffers
-        for k, a in checked.items():
-            lo, hi = self._skins[k]["span"]
-            if hi < lo:
-                continue
-            self._boneBuffers[k] = self.CreateComputeBuffer(self._boneBuffers.get(k), a, 48)
-            self.ctx.skin_vertices(rest_v, rest_n, idx, wgt, self._boneBuffers[k], lo, hi - lo + 1, self._vertexBuffer,
-                                   None if recompute_normals else self._normalBuffer)
+        deform()
         if recompute_normals:
-            self.RecomputeNormals(list(checked))
-        for k in checked:
-            lo, hi = self._skins[k]["span"]
+            self.RecomputeNormals(list(spans))
+        for k, (lo, hi) in spans.items():
             if hi < lo:
                 continue
             lo3, hi3, n = self.ctx.buffer_bounds(self._vertexBuffer, lo, hi - lo + 1)
             self._skinBoxes[k] = (lo3, hi3) if n > 0 else None
-        if checked:
+        if spans:
             s.mesh_bvh = self._object_heap_with_skins()
             self._meshObjectBVHBuffer = self.CreateComputeBuffer(self._meshObjectBVHBuffer, s.mesh_bvh, self.BVHNodeSize)
         if not history:
             self.ResetAccumulation()
             return
         self.SetShaderParameters()
-        self.ctx.render_aov(cur[0], cur[1], None, cur[2])                      # the skinned scene
+        self.ctx.render_aov(cur[0], cur[1], None, cur[2])                      # the deformed scene
         table = host_scene.mesh_motion(s.mesh_objects, s.mesh_objects)             # nothing else has moved: identity entries
-        for k in checked:
+        for k in spans:
             if not keep:
                 table[k] = np.nan
-        self._tmotion[0] = self.CreateComputeBuffer(self._tmotion[0], table if checked else np.zeros((0, 12), np.float32), 48)
+        self._tmotion[0] = self.CreateComputeBuffer(self._tmotion[0], table if spans else np.zeros((0, 12), np.float32), 48)
         self._tmotion[1] = self.CreateComputeBuffer(self._tmotion[1], np.zeros((0, 12), np.float32), 48)
         color, count = self._tspare
-        extra = {"deform": self._deform_argument(checked)} if keep else {}
+        extra = {"deform": self._deform_argument(spans)} if keep else {}
         self.ctx.reproject(self._converged, self._tcount, prev[0], prev[1], prev[2], cur[0], cur[1], cur[2], color, count, prev_m,
                            mesh_motion=self._tmotion[0], sphere_motion=self._tmotion[1], moved_max_history=self._moved_max_history,
                            **extra, **self._temporal)
         self._tspare = (self._converged, self._tcount)
         self._converged, self._tcount = color, count
+
+    # A mesh gets blend shapes (morph targets): targets = [(delta_vertices (n, 3), delta_normals (n, 3) or None), ...], dense over the
+    # n vertices of its vertex span as Mesh.GetBlendShapeFrameVertices returns them.  Rows whose six deltas all compare == 0 are dropped,
+    # the rest become urt_MorphDeltas with absolute vertex numbers.  The span's positions and normals as the scene holds them NOW are
+    # kept as the rest pose, as AttachSkin records it.  Nothing reaches the library before MorphMeshes.
+    def AttachBlendShapes(self, mesh_index: int, targets):
+        s = self.scene
+        if self._treesNeedRebuilding and self._rayTraceObjects:                    # the lists the index refers to do not exist yet
+            self.RebuildObjectLists()
+        self._mesh_index_arg(mesh_index, "AttachBlendShapes", "mesh_index")
+        lo, hi = self.vertex_span(mesh_index)
+        n = hi - lo + 1
+        if isinstance(targets, (str, bytes)) or not hasattr(targets, "__len__"):
+            raise ValueError("AttachBlendShapes: targets must be a list of (delta_vertices, delta_normals or None)")
+        if not 1 <= len(targets) <= _lib.MORPH_MAX_TARGETS:
+            raise ValueError(f"AttachBlendShapes: 1 .. {_lib.MORPH_MAX_TARGETS} targets, not {len(targets)}")
+        parts = []
+        for t, pair in enumerate(targets):
+            if isinstance(pair, (str, bytes, np.ndarray)) or not hasattr(pair, "__len__") or len(pair) != 2:
+                raise ValueError(f"AttachBlendShapes: targets[{t}] must be a pair (delta_vertices, delta_normals or None)")
+            try:
+                dp = np.ascontiguousarray(pair[0], dtype=np.float32)
+                dn = np.zeros((n, 3), np.float32) if pair[1] is None else np.ascontiguousarray(pair[1], dtype=np.float32)
+            except (TypeError, ValueError):
+                raise ValueError(f"AttachBlendShapes: the deltas of targets[{t}] must be (n, 3) arrays") from None
+            for name, a in (("delta_vertices", dp), ("delta_normals", dn)):
+                if a.ndim != 2 or a.shape != (n, 3):
+                    raise ValueError(f"AttachBlendShapes: {name} of targets[{t}] must have shape ({n}, 3), the vertex span of MeshObject "
+                                     f"{mesh_index}, not {a.shape}")
+            rows = np.flatnonzero(~((dp == 0).all(axis=1) & (dn == 0).all(axis=1)))
+            d = np.zeros(len(rows), dtype=np.dtype(_lib.MORPH_DELTA_DT))
+            d["vertex"], d["target"], d["dp"], d["dn"] = lo + rows, t, dp[rows], dn[rows]
+            parts.append(d)
+        old = self._morphs.get(int(mesh_index))
+        if old is not None and old["plan"] is not None:
+            old["plan"].Release()
+        self._morphs[int(mesh_index)] = {
+            "span": (lo, hi), "deltas": np.concatenate(parts), "n_targets": len(targets), "plan": None, "uploaded": False,
+            "rest_vertices": np.array(np.asarray(s.vertices, np.float32).reshape(-1, 3)[lo: hi + 1]),
+            "rest_normals": np.array(np.asarray(s.normals, np.float32).reshape(-1, 3)[lo: hi + 1])}
+
+    def _ensure_morph_buffers(self):
+        nv = self._vertexBuffer.count
+        if self._morphBuffers is not None and self._morphBuffers[0].count != nv:
+            for b in self._morphBuffers:
+                b.Release()
+            self._morphBuffers = None
+        if self._morphBuffers is None:
+            self._morphBuffers = tuple(ComputeBuffer(self.ctx, nv, 12) for _ in range(4))
+            for mp in self._morphs.values():
+                mp["uploaded"] = False
+        for mp in self._morphs.values():
+            lo, hi = mp["span"]
+            if mp["plan"] is None:
+                mp["plan"] = self.ctx.morph_plan(mp["deltas"], mp["n_targets"], lo, hi - lo + 1)
+            if not mp["uploaded"] and hi >= lo:
+                for b, key in zip(self._morphBuffers, ("rest_vertices", "rest_normals")):
+                    b.SetData(mp[key], 0, lo, len(mp[key]))
+                mp["uploaded"] = True
+
+    def _drop_morphs(self):
+        for mp in self._morphs.values():
+            if mp["plan"] is not None:
+                mp["plan"].Release()
+                mp["plan"] = None
+        for b in tuple(self._morphBuffers or ()) + tuple(self._morphWeightBuffers.values()):
+            if b is not None:
+                b.Release()
+        self._morphBuffers, self._morphWeightBuffers = None, {}
+
+    # Blend shapes move: weights = {MeshObject index: (n_targets,) float32} for meshes that have blend shapes (AttachBlendShapes).  The
+    # SkinMeshes protocol with urt_morph_vertices as the deformation: the weights are uploaded (a few bytes per target) and every span is
+    # morphed on the GPU.  A mesh that is not named in `poses` is morphed straight into the device side of the vertex and the normal
+    # buffer, its normals normalised (URT_MORPH_NORMALIZE).  A mesh that also has a skin (AttachSkin) and an entry in poses = {MeshObject
+    # index: (n_bones, 12)} — every key of poses is a key of weights — is morphed, normals as they come, into a pair of intermediate
+    # buffers that urt_skin_vertices then takes as its rest pose: blend shapes come before the bones, and since the skin reads device
+    # mirrors the morphed rest pose never crosses the bus.  recompute_normals and keep_history: as SkinMeshes'.
+    def MorphMeshes(self, weights, poses=None, recompute_normals: bool = False, keep_history: bool = False):
+        weights, poses = dict(weights), dict(poses or {})
+        if self._treesNeedRebuilding and self._rayTraceObjects:
+            self.RebuildObjectLists()
+        checked = {}
+        for k, w in weights.items():
+            self._mesh_index_arg(k, "MorphMeshes", "the keys of weights")
+            if int(k) not in self._morphs:
+                raise ValueError(f"MorphMeshes: MeshObject {k} has no blend shapes (AttachBlendShapes)")
+            try:
+                a = np.ascontiguousarray(w, dtype=np.float32)
+            except (TypeError, ValueError):
+                raise ValueError(f"MorphMeshes: weights[{k}] must be an (n_targets,) array") from None
+            if a.shape != (self._morphs[int(k)]["n_targets"],):
+                raise ValueError(f"MorphMeshes: weights[{k}] must have shape ({self._morphs[int(k)]['n_targets']},), one weight per target, not {a.shape}")
+            checked[int(k)] = a
+        bones = self._checked_poses(poses, "MorphMeshes")
+        for k in bones:
+            if k not in checked:
+                raise ValueError(f"MorphMeshes: poses names MeshObject {k}, which weights does not")
+            if self._skins[k]["span"] != self._morphs[k]["span"]:
+                raise ValueError(f"MorphMeshes: the skin and the blend shapes of MeshObject {k} were attached to different vertex spans")
+
+        def morph():
+            self._ensure_morph_buffers()
+            rest_v, rest_n, mid_v, mid_n = self._morphBuffers
+            if bones:
+                self._ensure_skin_buffers()
+            for k, a in checked.items():
+                lo, hi = self._morphs[k]["span"]
+                if hi < lo:
+                    continue
+                self._morphWeightBuffers[k] = self.CreateComputeBuffer(self._morphWeightBuffers.get(k), a, 4)
+                plan, wb = self._morphs[k]["plan"], self._morphWeightBuffers[k]
+                if k not in bones:
+                    if recompute_normals:
+                        plan.morph(rest_v, None, wb, self._vertexBuffer, None)
+                    else:
+                        plan.morph(rest_v, rest_n, wb, self._vertexBuffer, self._normalBuffer, normalize=True)
+                    continue
+                if recompute_normals:
+                    plan.morph(rest_v, None, wb, mid_v, None)
+                else:
+                    plan.morph(rest_v, rest_n, wb, mid_v, mid_n)
+                self._boneBuffers[k] = self.CreateComputeBuffer(self._boneBuffers.get(k), bones[k], 48)
+                self.ctx.skin_vertices(mid_v, None if recompute_normals else mid_n, self._skinBuffers[2], self._skinBuffers[3], self._boneBuffers[k],
+                                       lo, hi - lo + 1, self._vertexBuffer, None if recompute_normals else self._normalBuffer)
+        self._deform_on_device({k: self._morphs[k]["span"] for k in checked}, morph, recompute_normals, keep_history)
 
     # the edited lists become the scene's, with the object-level heaps RebuildObjectLists / the scene builders make for them, and are
     # uploaded (RebuildTrees: SetData of data a buffer already holds changes nothing)
@@ -1041,6 +1183,7 @@ class RayTraceMaster:
             if b is not None:
                 b.Release()
         self._skinBuffers, self._boneBuffers = None, {}
+        self._drop_morphs()
         self._drop_normals_plans()
         for t in (self._target, self._converged, self.SkyboxTexture, self._denoised, self._tonemapped) + (self._aov or ()):
             if t is not None:

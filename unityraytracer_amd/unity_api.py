@@ -142,6 +142,12 @@ class Context:
         synchronising set-up call)."""
         return NormalsPlan(self, vertices, indices, first, count)
 
+    def morph_plan(self, deltas, n_targets: int, first: int, count: int) -> "MorphPlan":
+        """A MorphPlan (blend shapes) for the served vertices first .. first + count - 1: `deltas` is an array of urt_MorphDelta
+        (_lib.MORPH_DELTA_DT) or a sequence of (vertex, target, dp[3], dn[3]) with absolute vertex numbers (include/urt.h
+        urt_morph_plan_create).  The plan names no buffer."""
+        return MorphPlan(self, deltas, n_targets, first, count)
+
     def serve_stats(self) -> dict:
         """kernel_mode 5 with count_stats: the shared traversal service since the last reset_counters()."""
         a = (C.c_ulonglong * 6)()
@@ -1234,6 +1240,54 @@ class NormalsPlan:
     def Release(self):
         if self.handle:
             self.ctx.check(self.ctx.lib.urt_normals_plan_release(self.ctx._h, self.handle))
+            self.handle = 0
+
+
+class MorphPlan:
+    """Blend shapes (morph targets) on the GPU for one vertex span (include/urt.h, "blend shapes on the device"): the deltas of every
+    target laid out per served vertex, made once per mesh; .morph(...) adds them, scaled by the weight table, to a rest pose into the
+    device side of the destinations — one kernel on the context's stream, nothing waited for, nothing downloaded."""
+
+    def __init__(self, ctx: Context, deltas, n_targets: int, first: int, count: int):
+        from . import host_scene
+        for name, v in (("n_targets", n_targets), ("first", first), ("count", count)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"morph_plan: {name} must be an int, not {type(v).__name__}")
+        try:
+            d = host_scene.morph_deltas(deltas)
+        except (TypeError, ValueError):
+            raise ValueError("morph_plan: deltas must be an array of urt_MorphDelta or a sequence of (vertex, target, dp[3], dn[3])") from None
+        self.ctx, self.handle = ctx, 0
+        h = C.c_uint64()
+        ctx.check(ctx.lib.urt_morph_plan_create(ctx._h, d.ctypes.data_as(C.c_void_p) if d.size else None, len(d), int(n_targets), int(first),
+                                                int(count), C.byref(h)))
+        self.handle = h.value
+
+    def info(self) -> dict:
+        """first, count, n_targets, n_entries, max_valence, n_touched, device_bytes (include/urt.h urt_MorphPlanInfo)."""
+        a = _lib.MorphPlanInfo()
+        self.ctx.check(self.ctx.lib.urt_morph_plan_info(self.ctx._h, self.handle, C.byref(a)))
+        return {n: int(getattr(a, n)) for n, _ in _lib.MorphPlanInfo._fields_}
+
+    def morph(self, rest_v, rest_n, weights, dst_v, dst_n, normalize: bool = False):
+        """dst_v (and dst_n) [first .. first + count - 1] = rest_v (rest_n) + the weighted deltas (urt_morph_vertices).  rest_v, dst_v,
+        rest_n, dst_n: stride-12 ComputeBuffers of one count; rest_n and dst_n may be None (positions only).  weights: a stride-4
+        ComputeBuffer of n_targets floats.  normalize: URT_MORPH_NORMALIZE."""
+        def handle(b, name, optional=False):
+            if b is None and optional:
+                return 0
+            if not isinstance(b, ComputeBuffer):
+                raise TypeError(f"MorphPlan.morph: {name} must be a ComputeBuffer{' or None' if optional else ''}, not {type(b).__name__}")
+            if b.ctx is not self.ctx:
+                raise ValueError(f"MorphPlan.morph: {name} belongs to another context")
+            return b.handle
+        self.ctx.check(self.ctx.lib.urt_morph_vertices(self.ctx._h, self.handle, handle(rest_v, "rest_v"), handle(rest_n, "rest_n", True),
+                                                       handle(weights, "weights"), handle(dst_v, "dst_v"), handle(dst_n, "dst_n", True),
+                                                       _lib.MORPH_NORMALIZE if normalize else 0))
+
+    def Release(self):
+        if self.handle:
+            self.ctx.check(self.ctx.lib.urt_morph_plan_release(self.ctx._h, self.handle))
             self.handle = 0
 
 
