@@ -974,6 +974,9 @@ typedef struct urt_counters {
  *                  trips — auto / 1: by mask arithmetic over the heap when it has <= 31 nodes, else as a list when <= 12 MeshObjects; 2: always the list), "lds_tlas" (0/1: small object-level tables in LDS),
  *                  "front_fuse" (-1 auto, the default = on | 0 | 1: where the object-level phase is the plain one — one MeshObject, or "front_list" 0 — a new ray takes its
  *                  first object-level step in the trip that created it instead of waiting for a voted trip; same pixels, fewer scheduler trips),
+ *                  "handout" (-1 auto, the default = 1 | 0 | 1: how the dead lanes of a wave get their next pixels — 0: every refill adds to the work counter of the
+ *                  wave's shard, one device-scope atomic that the whole wave waits for; 1: the four waves of a workgroup share a reservation of up to 16 tiles
+ *                  of a run in LDS, a refill is a compare-and-swap there and only the wave that drains it goes to the counter; same pixels in another order),
  *          mode 4: "pool_k" (1..4), "pool_refill", "pool_blas_min" (1..256), "pool_blas_exit", "pool_inloop",
  *                  "pool_other_min" (1..64),
  *          "blas_leaf_max" (1..8: triangles per BVH leaf, default 2 or the environment variable URT_BLAS_LEAF_MAX read when the
@@ -1165,6 +1168,7 @@ typedef struct urt_launch_info {
   int overlapped;             /* 1: the launch did not wait for the previous launch (it waited for the main stream as of the previous submission) */
   int overlapped_launches;    /* such launches since the context was created */
   int cones;                  /* 1: the launch's traversal applied the normal cones of option "blas_cones" (kernel_mode 3, not counting, no qnodes) */
+  int handout;                /* kernel_mode 3: tiles per LDS reservation of a workgroup (option "handout": 1..16, a divisor of xcd_run); 0: every wave draws from the work counters */
 } urt_launch_info;
 URT_API int urt_debug_launch_info(urt_context* ctx, urt_launch_info* out_info);
 URT_API int urt_debug_read_scene_blas(urt_context* ctx, float* nodes, int32_t* tri_index, int32_t* mesh_root);

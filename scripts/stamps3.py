@@ -43,6 +43,9 @@ for (w, h, b), wpc in itertools.product(((1920, 1080, 8),), (20,)):
     print(f"   BLAS inner: {trips[:, 3].mean():8.1f} steps/wave, {lanes[:, 3].sum() / max(1, trips[:, 3].sum()):5.1f} active lanes/step, {t[:, 1].sum() / max(1, trips[:, 3].sum()) * 1000:7.1f} ns/step")
     fs = st[:, 25:32].astype(np.float64)
     if fs[:, 3].sum() == 0 and fs[:, 2].sum() > 0:               # single-mesh instantiation: slots 25-27 hold the refill's split
+        adds = (st[:, 27] >> np.uint64(32)).astype(np.float64)   # slot 27: refills | device-scope atomics on the work counters << 32 (0: a build from before the count, one per refill)
+        fs[:, 2] = (st[:, 27] & np.uint64(0xffffffff)).astype(np.float64)
+        print(f"   REFILL: work-counter atomics {adds.mean() if adds.sum() else fs[:, 2].mean():7.1f} per wave")
         print(f"   REFILL: {fs[:, 2].mean():7.1f} refills/wave; work-counter hand-out {fs[:, 0].sum() / 100 / life.sum() * 100:5.1f} % of wave time ({fs[:, 0].sum() / 100 / fs[:, 2].sum():5.2f} us each), "
               f"camera rays {fs[:, 1].sum() / 100 / life.sum() * 100:5.1f} % ({fs[:, 1].sum() / 100 / fs[:, 2].sum():5.2f} us each); "
               f"unaccounted {(1 - (t[:, 0:3].sum() + (fs[:, 0].sum() + fs[:, 1].sum()) / 100) / life.sum()) * 100:5.1f} %")

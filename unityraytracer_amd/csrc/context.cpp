@@ -1100,6 +1100,7 @@ const OptionRow kOptions[] = {
   {"blas_cones", &O::blas_cones, -1, 1, "blas_cones must be -1 (auto), 0 or 1", kStale | kOnChange, nullptr},
   {"front_cull", &O::front_cull, 0, 1, "front_cull must be 0 or 1", kFlushAgain | kStale | kOnChange, nullptr},
   {"front_fuse", &O::front_fuse, -1, 1, "front_fuse must be -1 (auto), 0 or 1", kOnChange, nullptr},
+  {"handout", &O::handout, -1, 1, "handout must be -1 (auto), 0 or 1", 0, nullptr},
   {"refit", &O::refit, INT_MIN, INT_MAX, "", kBool | kStale, nullptr},
   {"refit_vertices", &O::refit_vertices, INT_MIN, INT_MAX, "", kBool, nullptr},
   {"refit_rebuild_pct", &O::refit_rebuild_pct, 0, INT_MAX, "refit_rebuild_pct must be 0 (never rebuild) or greater than 100", 0, [](int v) { return v == 0 || v > 100; }},

@@ -129,6 +129,9 @@ struct urt_context {
     int shade_split = -1;                   // kernel_mode 3: -1 = auto (= split: measured better or equal on C2-C5), 0 = surface hits and misses shaded in one trip
     int front_fuse = -1;                    // kernel_mode 3, plain FRONT (one mesh, or "front_list" 0): -1 = auto (= on), 1 = a new ray takes its first object-level step in the trip that
                                             // created it, 0 = it waits for a voted FRONT trip (A/B and tests: both schedules in one build; same pixels)
+    int handout = -1;                       // kernel_mode 3: how dead lanes get their pixel slots: 0 = every wave draws from its shard's counter (one device-scope atomic per refill),
+                                            // 1 = the waves of a workgroup share a reservation of up to 16 tiles in LDS (one device-scope atomic per reservation), -1 = auto (= 1);
+                                            // any value draws the same pixels (frame_device.h wg_fetch_pixels)
     int tile_order = -1;                    // persistent modes: order in which the frame's tiles are handed out: 0 bottom strip first, 1 top strip first (a launch then ENDS with the
                                             // bottom rows), -1 = auto: top first for scenes without triangle meshes (C2: -3.6 % in bench.py, -9 .. -12 % for launches of 1 - 20 frames),
                                             // bottom first otherwise (C3, driver's 20-frame launch: top first +1.5 %; 64-frame launches, C3D, C4, C5: +-0.4 %) —

@@ -108,6 +108,19 @@ static int auto_run_length(const FrameParams& P, int n_frames) {
   return g;
 }
 
+// Mode 3, option "handout": tiles per reservation of a workgroup (FrameParams::handout), 0 = per-wave atomics.  The largest divisor of the
+// run length that is at most 16 (1024 slots: the reservation word counts slots in 11 bits), so that a reservation never leaves its run —
+// the auto run lengths 1 .. 8 are handed out whole.  Mode 5 keeps the dword for pool_inloop; frames of 2^24 tiles and more keep the counters.
+static void set_handout(urt_context* ctx, FrameParams& P) {
+  if (P.serve) return;
+  int c = 0;
+  if (ctx->opt.handout != 0 && (uint64_t)P.tiles_x * (uint64_t)P.n_strips + (uint64_t)P.xcd_run < (1u << 24)) {
+    c = std::min(P.xcd_run, 16);
+    while (P.xcd_run % c) c--;
+  }
+  P.handout = c;
+}
+
 // One attempt at `groups` workgroups per CU; *degraded = an LDS feature the scene qualifies for had to be given up (or the stacks alone do not fit)
 static int configure_sched_at(urt_context* ctx, const DevScene& S, FrameParams& P, bool top_in_front, size_t groups, bool* degraded) {
   // independent waves; the waves of a workgroup share one LDS copy of the top of the triangle-BVH forest, which shrinks
@@ -206,6 +219,7 @@ static void record_launch(urt_context* ctx, const TraceLaunchRecord& R, int kern
   I.lds_tables = (P.lds_mesh ? 1 : 0) | (P.lds_sphere ? 2 : 0) | (P.lds_small ? 4 : 0) | (P.walk_f4 > 0 ? 8 : 0);
   I.slab_frames = ctx->slab_frames; I.slab_frames_max = ctx->slab_frames_max; I.slab_out_of_memory = ctx->slab_oom_stride != 0 ? 1 : 0;
   I.experiment = URT_ABI_SIGN < 0 ? 1 : 0;
+  I.handout = kernel_mode == 3 ? P.handout : 0;
 }
 
 // One trace launch on stream `st`: `launch(TraceLaunchRecord*)` enqueues it through a launcher of kernels.h, between two timing events
@@ -309,6 +323,7 @@ int flush_pending(urt_context* ctx) {
   P.sched_trips = sched_trip_cap(ctx, P, n);
   P.frame_group = std::max(1, std::min(P.frame_group, n));
   if (ctx->opt.xcd_run <= 0) P.xcd_run = auto_run_length(P, n);
+  set_handout(ctx, P);
   P.frame_stride = (unsigned int)ctx->slab_stride;
   // Small launches (a host that presents every frame) overlap: see urt_context "Overlapped launches".  Launch L goes to trace stream
   // L mod 2 and takes slots [base, base + n) round-robin; it waits for
@@ -514,6 +529,7 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
     P.pool_inloop = ctx->opt.serve_refill;
     int front_mode = configure_sched(ctx, S, P, top_in_front);
     P.shade_split = ctx->opt.shade_split != 0;
+    set_handout(ctx, P);                                          // (batched launches: again at submission, with the launch's run length)
     // plain FRONT: new rays take their first object-level step in the trip that created them; as straight-line code when the mesh heap is one node and there are no spheres
     P.front_fuse = ctx->opt.front_fuse == 0 ? 0 : (S.n_mesh_tlas == 1 && S.n_meshes > 0 && S.n_spheres == 0 ? 2 : 1);
     const FrameUniforms fu = bound_camera(ctx);                   // the uniforms P's head holds

@@ -209,6 +209,125 @@ __device__ __forceinline__ bool wave_fetch_pixels(const FrameParams& P, unsigned
   return slot_pixel(P, tile, local & 63u, x, y);
 }
 
+// ---- The hand-out per WORKGROUP (mode 3, P.handout > 0) ----
+// wave_fetch_pixels parks the whole wave, live lanes too, on a device-scope atomic (~2.3 us) at every refill.  Here the waves of a
+// workgroup share a RESERVATION in LDS instead: one 64-bit word that names a chunk of C = P.handout consecutive tiles of the workgroup's
+// shard (C divides P.xcd_run, so a chunk lies inside one run and therefore inside one frame of an interleaved launch) and how many of its
+// slots are handed out.  A refill takes its slots with a compare-and-swap on that word — an LDS round trip — and only the wave that
+// drains a chunk goes to the shard's counter, for the whole next chunk: one device-scope atomic per C x 64 slots instead of one per refill.
+// The word, low bit first:
+//   used 11 | valid 11 | fetching 1 | exhausted 1 | first tile of the chunk inside its frame 24 | frame 7 | shard 6
+// `valid` > `used` only between the install of a chunk and its drain, and no two chunks of a launch share (frame, first tile): a
+// compare-and-swap that takes slots can never succeed on another chunk's word (no ABA).  Drained words may repeat (a dry shard, a padded
+// chunk); the only transition out of them is the one that sets `fetching`, which is right for whoever wins it.
+// Termination: nothing here waits for another wave.  The wave that set `fetching` depends on no one — it adds to the counter, maps the
+// chunk and installs the word; `fetching` set means that wave is between those steps.  A wave that finds it set skips this refill and
+// runs its live lanes; with none it goes round the scheduler loop (a short s_sleep first), which P.sched_trips bounds like every other
+// trip.  A failed compare-and-swap means another wave's succeeded; it is retried a fixed number of times, then the refill is skipped.
+static constexpr unsigned long long kRunFetching = 1ull << 22, kRunExhausted = 1ull << 23;
+static constexpr int kRunCasTries = 8;
+
+__device__ __forceinline__ unsigned long long wave_uniform64(unsigned long long v) {
+  unsigned int lo = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)v);
+  unsigned int hi = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(v >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long run_word(unsigned int shard, unsigned int frame, unsigned int tile0, unsigned int valid, bool exhausted) {
+  return ((unsigned long long)shard << 55) | ((unsigned long long)frame << 48) | ((unsigned long long)tile0 << 24) | (exhausted ? kRunExhausted : 0ull) |
+         ((unsigned long long)valid << 11);
+}
+
+// The wave that holds `fetching` takes the next chunk of the workgroup's shard from its counter and returns the word to install:
+// wave_fetch_pixels' bookkeeping (dry-shard probe, move to the next shard, `exhausted`) and its slot -> (frame, tile) arithmetic, once
+// per chunk and on wave-uniform values.
+__device__ __forceinline__ unsigned long long wg_fetch_run(const FrameParams& P, unsigned int shard, unsigned int* next, unsigned int ntiles,
+                                                           unsigned int tiles_per_frame) {
+  const int lane = threadIdx.x & 63;
+  const unsigned int G = (unsigned int)P.xcd_run, NS = (unsigned int)P.n_shards, C = (unsigned int)P.handout;
+  const unsigned int own = shard_slots(ntiles, shard, G, NS);
+  unsigned int base = 0;
+  if (lane == 0) base = atomicAdd(next + shard * 32u, C * 64u);
+  base = (unsigned int)__builtin_amdgcn_readfirstlane((int)base);
+  unsigned int nshard = shard;
+  bool exh = false;
+  if (base + C * 64u >= own) {   // this shard is (now) dry: every lane looks at one counter, the workgroup moves to the next shard with work
+    unsigned int seen = __hip_atomic_load(next + lane * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned long long avail = wballot((unsigned int)lane < NS && seen < shard_slots(ntiles, (unsigned int)lane, G, NS)) & ~(1ull << shard);
+    if (!avail) exh = true;      // counters only grow, so this is final (the chunk below, if any, is the workgroup's last)
+    else {
+      unsigned long long after = shard == 63u ? 0ull : avail & ~((2ull << shard) - 1ull);
+      nshard = (unsigned int)__builtin_ctzll(after ? after : avail);
+    }
+  }
+  unsigned int vt = 0, f = 0, t0 = 0;                 // tiles of the chunk that exist, its frame, its first tile there
+  if (base < own) {
+    const unsigned int q0 = base >> 6;                // (every add is C x 64: q0 is a multiple of C, and C divides G)
+    vt = min(C, (own >> 6) - q0);
+    unsigned int tile = shard_tile(shard, q0, G, NS);
+    const unsigned int FG = (unsigned int)P.frame_group;
+    if (FG <= 1u) { f = tile / tiles_per_frame; t0 = tile - f * tiles_per_frame; }   // frame after frame: a chunk may run on into the next frames (wg_fetch_pixels)
+    else {                                            // frames interleaved in groups of FG, as in wave_fetch_pixels
+      unsigned int rg, w, grp, r, q;
+      const unsigned int runs_pf = (tiles_per_frame + G - 1u) / G, group_runs = runs_pf * FG;
+      if ((G & (G - 1u)) == 0u) { rg = tile >> __builtin_ctz(G); w = tile & (G - 1u); } else { rg = tile / G; w = tile - rg * G; }
+      grp = rg / group_runs; r = rg - grp * group_runs;
+      if ((FG & (FG - 1u)) == 0u) { q = r >> __builtin_ctz(FG); f = grp * FG + (r & (FG - 1u)); } else { q = r / FG; f = grp * FG + (r - q * FG); }
+      t0 = q * G + w;
+      if (t0 >= tiles_per_frame || f >= (unsigned int)P.n_frames) { vt = 0; f = 0; t0 = 0; }   // padding of a frame's last run, of the last group
+      else vt = min(vt, tiles_per_frame - t0);
+    }
+  }
+  return run_word(nshard, f, t0, vt * 64u, exh);
+}
+
+// wave_fetch_pixels for a workgroup that shares a reservation `rs` (LDS): the same slots map to the same pixels, handed out in another
+// order.  Lanes the chunk has no slot for stay dead this trip, except in the wave that fetches the next chunk: it takes the rest there.
+__device__ __forceinline__ bool wg_fetch_pixels(const FrameParams& P, unsigned long long want, bool mine, unsigned int* next,
+                                                unsigned int ntiles, unsigned long long* rs, bool& exhausted, int& x, int& y,
+                                                unsigned int tiles_per_frame, int* frame, unsigned long long* n_adds = nullptr) {   // n_adds: -DURT_STAMPS, device-scope atomics issued
+  const int lane = threadIdx.x & 63;
+  const unsigned int n = (unsigned int)__popcll(want);
+  const unsigned int rank = (unsigned int)__popcll(want & ((1ull << lane) - 1ull));
+  unsigned int taken = 0;
+  bool got = false;
+  for (int round = 0; round < 2; round++) {
+    unsigned long long s = 0;
+    unsigned int k = 0, avail = 0;
+    bool fetch = false;
+    for (int tries = 0;; tries++) {
+      if (tries == kRunCasTries) return got;
+      s = wave_uniform64(__hip_atomic_load(rs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+      avail = ((unsigned int)(s >> 11) & 0x7ffu) - ((unsigned int)s & 0x7ffu);
+      unsigned long long s2;
+      if (avail) {
+        k = min(n - taken, avail);
+        fetch = k == avail && !(s & kRunExhausted);           // this wave drains the chunk: it fetches the next one
+        s2 = (s + k) | (fetch ? kRunFetching : 0ull);
+      } else if (s & kRunExhausted) { exhausted = true; return got; }
+      else if (s & kRunFetching) { if (n == 64u) __builtin_amdgcn_s_sleep(2); return got; }   // another wave is fetching: no refill this trip
+      else { k = 0; fetch = true; s2 = s | kRunFetching; }
+      unsigned long long seen = s;
+      if (lane == 0) __hip_atomic_compare_exchange_strong(rs, &seen, s2, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (wave_uniform64(seen) == s) break;
+    }
+    if (mine && rank >= taken && rank < taken + k) {
+      const unsigned int idx = ((unsigned int)s & 0x7ffu) + (rank - taken);
+      unsigned int tile = ((unsigned int)(s >> 24) & 0xffffffu) + (idx >> 6), f = (unsigned int)(s >> 48) & 0x7fu;
+      if (tile >= tiles_per_frame) { unsigned int q = tile / tiles_per_frame; f += q; tile -= q * tiles_per_frame; }   // frame_group 1 only: the chunk runs on into the next frame
+      *frame = (int)f;
+      if (P.tile_order == 1) tile = tiles_per_frame - 1u - tile;   // top strip first
+      got = slot_pixel(P, tile, idx & 63u, x, y);
+    }
+    taken += k;
+    if (!fetch) { if (k == avail) exhausted = true; break; }   // (no fetch after a drain: it was the workgroup's last chunk)
+    const unsigned long long ns = wg_fetch_run(P, (unsigned int)(s >> 55) & 63u, next, ntiles, tiles_per_frame);
+    if (lane == 0) __hip_atomic_store(rs, ns, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // (the only writer while `fetching` is set)
+    if (n_adds) ++*n_adds;
+    if (taken == n) break;
+  }
+  return got;
+}
+
 // Every persistent kernel leaves its scheduler loop after P.sched_trips trips per wave, whatever the data (a frame needs ~1e3-1e5;
 // the host scales the cap with the launch: frames x rays x bounces, frame_batch.cpp).  A wave that leaves that way — or through the
 // per-phase traversal cap — counts itself in DevCounters::watchdog and raises the host-visible flag: its pixels are missing.

@@ -12,7 +12,7 @@
 //    traversal carries (t, kind, id, u, v) and normals/material are fetched once per closest hit;
 //  * the reference is one thread per pixel for all bounces; the default kernel here (k_sched, kernel_mode 3) keeps a
 //    fixed grid of waves resident for the whole frame: a lane whose path has ended takes a new pixel from the frame's
-//    sharded work counter (wave64 ballot + prefix popcount + ONE atomic per refill), and the lanes of a wave are
+//    sharded work counter (wave64 ballot + prefix popcount; the waves of a workgroup draw through a shared reservation in LDS), and the lanes of a wave are
 //    scheduled by phase (object-level walk / triangle-BVH loop / shading) so that the long loops run for the lanes
 //    that need them;
 //  * the hot, small tables live in LDS next to the stacks: the breadth-first top of the triangle-BVH forest, the
@@ -72,14 +72,15 @@ namespace {
 template <bool COUNT, int BLOCK, int FMODE, bool MULTI, bool QN = false>
 __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, FrameParams P, const FrameUniforms* __restrict__ T, float4* __restrict__ result, DevCounters* ctr,
                                                unsigned int* __restrict__ next) {
-  // LDS of the workgroup: [top of the triangle-BVH forest: top_nodes x 64 B, shared by its waves][stacks of wave 0][wave 1]...
-  // The waves of a workgroup share nothing else and never synchronise after this copy.
+  // LDS of the workgroup: [the tile reservation: 16 B][top of the triangle-BVH forest: top_nodes x 64 B, shared by its waves][tables][stacks of wave 0][wave 1]...
+  // Apart from the reservation word (frame_device.h wg_fetch_pixels) the waves of a workgroup share only read-only copies and never synchronise after this prologue.
   constexpr bool CONES = !COUNT && !QN;
   extern __shared__ int lds[];
   float4* lds4 = (float4*)lds;
-  const float4* top = lds4;
-  for (int i = threadIdx.x; i < P.top_nodes * 4; i += blockDim.x) lds4[i] = S.blas_cnodes[i];
-  int at = P.top_nodes * 4;                                     // running offset in float4 units
+  const float4* top = lds4 + 1;
+  if (threadIdx.x == 0) *(unsigned long long*)lds = run_word(blockIdx.x & ((unsigned int)P.n_shards - 1u), 0, 0, 0, false);   // drained, on the workgroup's home shard
+  for (int i = threadIdx.x; i < P.top_nodes * 4; i += blockDim.x) lds4[1 + i] = S.blas_cnodes[i];
+  int at = 1 + P.top_nodes * 4;                                 // running offset in float4 units
   FrontLds L;
   if (P.lds_mesh) {                                             // object-level mesh heap + MeshObject roots
     for (int i = threadIdx.x; i < 2 * S.n_mesh_tlas; i += blockDim.x) lds4[at + i] = S.mesh_tlas[i];
@@ -153,6 +154,7 @@ __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, Fram
   unsigned long long dr_trips[4] = {0, 0, 0, 0}, dr_t[3] = {0, 0, 0}, dr_live = 0, dr_lanes3 = 0;   // after the work ran dry
   unsigned long long fs_arr[7] = {0, 0, 0, 0, 0, 0, 0};   // listed FRONT: time in the heap walk / single-leaf tests / BVH-top walks, walks, single-leaf rounds, top walks, fresh lanes walked
   unsigned long long rf_t[3] = {0, 0, 0};                  // refill: time in the work-counter hand-out (the atomic's round trip), in the camera rays, refills
+  unsigned long long rf_adds = 0;                          // refill: device-scope atomics on the work counters
   unsigned long long bl_part[3] = {0, 0, 0};               // BLAS loop: lanes that took part in their trip (sum), node trips, lanes at a leaf during node trips (sum)
 #endif
 
@@ -170,16 +172,26 @@ __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, Fram
       nK = __popcll(wballot(st == ST_SKY));
       nF = __popcll(wballot(st == ST_FRONT || st == ST_RESUME));
     }
-    // ---- refill dead lanes from the frame's work counter (one atomic per refill): when enough lanes are dead, or when
-    // nothing else is left to run.  The atomic takes 2.3 us to return (7.6 % of a wave's time on C3, profiles/r03_logs/r3_stamps_refill.log),
-    // but hiding it buys nothing — the SIMDs are busy with the other waves' vector work meanwhile: issuing it a trip early cost +23 % (r3_ab_split_refill.log: lanes stay dead a trip longer), reserving several
-    // tiles per atomic +4 % (r3_ab_refill_chunk.log: more live state in the loop). ----
+    // ---- refill dead lanes: when enough lanes are dead, or when nothing else is left to run.  From the workgroup's reservation in LDS
+    // (P.handout > 0, the default: frame_device.h wg_fetch_pixels — a compare-and-swap there, and one work-counter atomic per reservation, by
+    // the wave that drains it), or from the frame's work counter with one atomic per refill (P.handout = 0: wave_fetch_pixels).  That atomic
+    // takes 2.3 us to return (7.6 % of a wave's time on C3, profiles/r03_logs/r3_stamps_refill.log) and the whole wave waits for it; the other
+    // waves of the SIMD cover only part of the wait (C3 +7 % without it).  Two ways of hiding it inside the wave lost: issuing
+    // it a trip early cost +23 % (r3_ab_split_refill.log: lanes stay dead a trip longer), reserving several tiles per wave +4 %
+    // (r3_ab_refill_chunk.log: more live state in the loop). ----
     if (!exhausted && nD > 0 && (nD >= P.refill_min || (FMODE < 2 ? nD == 64 : nB + nS + nK + nF == 0))) {   // (every lane is in exactly one state)
       int x = 0, y = 0, frame = 0;
 #ifdef URT_STAMPS
       unsigned long long t_rf = wall_clock64();
 #endif
-      bool got = wave_fetch_pixels(P, mD, st == ST_DEAD, next, ntiles, wc, exhausted, x, y, tiles_per_frame, &frame);
+#ifdef URT_STAMPS
+      bool got = P.handout ? wg_fetch_pixels(P, mD, st == ST_DEAD, next, ntiles, (unsigned long long*)lds, exhausted, x, y, tiles_per_frame, &frame, &rf_adds)
+                           : wave_fetch_pixels(P, mD, st == ST_DEAD, next, ntiles, wc, exhausted, x, y, tiles_per_frame, &frame);
+      if (!P.handout) rf_adds++;
+#else
+      bool got = P.handout ? wg_fetch_pixels(P, mD, st == ST_DEAD, next, ntiles, (unsigned long long*)lds, exhausted, x, y, tiles_per_frame, &frame)
+                           : wave_fetch_pixels(P, mD, st == ST_DEAD, next, ntiles, wc, exhausted, x, y, tiles_per_frame, &frame);
+#endif
 #ifdef URT_STAMPS
       rf_t[0] += wall_clock64() - t_rf; t_rf = wall_clock64();
 #endif
@@ -383,7 +395,7 @@ __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, Fram
     for (int q = 0; q < 4; q++) { sp_[w + q] = ph_t[q]; sp_[w + 4 + q] = ph_lanes[q]; sp_[w + 8 + q] = ph_trips[q]; }
     sp_[w + 12] = t_begin; sp_[w + 13] = wall_clock64(); sp_[w + 14] = t_dry; sp_[w + 15] = __builtin_amdgcn_s_memtime() - c_begin;
     for (int q = 0; q < 7; q++) sp_[w + 25 + q] = fs_arr[q];
-    if (FMODE < 2) { sp_[w + 25] = rf_t[0]; sp_[w + 26] = rf_t[1]; sp_[w + 27] = rf_t[2]; sp_[w + 28] = 0; sp_[w + 29] = bl_part[0]; sp_[w + 30] = bl_part[1]; sp_[w + 31] = bl_part[2]; }     // (single-mesh instantiations: no FRONT split, the refill's instead)
+    if (FMODE < 2) { sp_[w + 25] = rf_t[0]; sp_[w + 26] = rf_t[1]; sp_[w + 27] = rf_t[2] | (rf_adds << 32); sp_[w + 28] = 0; sp_[w + 29] = bl_part[0]; sp_[w + 30] = bl_part[1]; sp_[w + 31] = bl_part[2]; }     // (single-mesh instantiations: no FRONT split, the refill's instead; slot 27: refills | work-counter atomics << 32)
   }
 #endif
   if (watchdog && (threadIdx.x & 63) == 0) report_watchdog(P, ctr);
@@ -490,6 +502,7 @@ size_t sched_lds_bytes(const DevScene& S, const FrameParams& P) {
   else if (P.lds_small) f4 += ((size_t)S.n_meshes + 3) / 4 + 3 * (size_t)S.n_small;
   if (P.lds_sphere) f4 += 2 * (size_t)S.n_sphere_tlas + (size_t)S.n_spheres;
   if (P.serve) f4 += 2 * (size_t)P.block_threads + 1;          // mode 5: the workgroup's mailbox (k_serve)
+  else f4 += 1;                                                // mode 3: the workgroup's tile reservation (frame_device.h wg_fetch_pixels)
   return f4 * 16 + (size_t)(P.tlas_stack + P.blas_stack) * 64 * (size_t)(P.block_threads / 64) * sizeof(int);
 }
 

@@ -77,7 +77,11 @@ struct FrameParams {
   int walk_f4;              // mode 3, masked FRONT (front mode 3): float4s of the walk table behind the mesh heap's device copy, kept in LDS
                             // instead of the heap itself (scene_prep.cpp build_walk_table); 0 = not in use
   int serve;                // mode 5: the traversal phase is a service shared by the waves of a workgroup (kernels_serve.hip k_serve) (0/1)
-  int pool_inloop;          // modes 4, 5: idle lanes that trigger a re-feed of the traversal phase from the waiting rays (1..64)
+  union {                   // one dword again: mode 3 has no use for pool_inloop
+    int pool_inloop;        // modes 4, 5: idle lanes that trigger a re-feed of the traversal phase from the waiting rays (1..64)
+    int handout;            // mode 3: 0 = every wave draws its pixel slots from the shard's counter (frame_device.h wave_fetch_pixels); C > 0 = the waves of a
+                            // workgroup share a reservation of C tiles in LDS (wg_fetch_pixels); C divides xcd_run and is at most 16
+  };
   union {                   // one dword, two modes that never share a launch (a field of its own would move the arguments behind FrameParams in the kernel-argument
                             // segment, and the masked instantiation of k_sched — which reads neither — compiled differently and measured 0.6 % slower on C5)
     int pool_other_min;     // mode 4: lanes of FRONT / SHADE work that make those phases worth a trip while rays queue for the BVH
