@@ -336,5 +336,15 @@ URT_HD float rand_next(float& seed, float px, float py) {
   seed = seed + 0.5f;
   return r;
 }
+// rand_next in its two halves, for a draw whose seed is the same for many pixels (a frame's first two draws start from _Seed and
+// _Seed + 0.5 in every pixel): rand_scale is the part that depends on the seed alone, rand_draw the rest.  The same operations on the
+// same operands as rand_next: rand_draw(rand_scale(seed), px, py) is its value bit for bit; the caller advances the seed by 0.5f.
+URT_HD float rand_scale(float seed) {
+  return f_div_const(seed + f_div_const(seed, 17.0f, 1.0f / 17.0f), 100.0f, 1.0f / 100.0f);   // (seed + seed / 17) / 100, RS:78
+}
+URT_HD float rand_draw(float a, float px, float py) {
+  float d = dot2(px, py, 12.9898f, 78.233f);
+  return f_frac(f_sin(a * d) * 43758.5453f);
+}
 
 }  // namespace urt

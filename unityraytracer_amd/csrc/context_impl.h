@@ -220,7 +220,7 @@ struct urt_context {
   // frame tables of the batched launches: kTableSlots pinned host images + device copies, used round-robin; a slot is reused
   // once the copy of its previous use has left the host image (event)
   static constexpr int kTableSlots = 4;
-  urtd::PinnedBuf<urtd::FrameUniforms> h_tables; urtd::DeviceBuf<urtd::FrameUniforms> d_tables;
+  urtd::PinnedBuf<urtd::FrameEntry> h_tables; urtd::DeviceBuf<urtd::FrameEntry> d_tables;
   urtd::Event table_ev[kTableSlots];
   unsigned int table_next = 0;
   uint64_t pixels_dispatched = 0;

@@ -10,7 +10,7 @@
 // unityraytracer_amd/build.py build_variant() adds -DURT_EXPERIMENT by itself.
 #pragma once
 
-#if defined(URT_STAMPS) || defined(URT_SCHED_OCC) || defined(URT_SERVE_OCC) || defined(URT_SERVE_SLEEP) || defined(URT_SKY_FASTWRAP) || \
+#if defined(URT_STAMPS) || defined(URT_SCHED_OCC) || defined(URT_SERVE_OCC) || defined(URT_SERVE_SLEEP) || defined(URT_SKY_FASTWRAP) || defined(URT_UNIFORM_REFILL) || \
     defined(URT_SAH_BINS) || defined(URT_AB)
 #ifndef URT_EXPERIMENT
 #error "A/B, probe and diagnostic switches (-DURT_STAMPS, -DURT_SCHED_OCC, -DURT_SAH_BINS, ...) need -DURT_EXPERIMENT: the library then reports a negative urt_abi_version and loaders refuse it unless they opt in (csrc/experiments.h)"

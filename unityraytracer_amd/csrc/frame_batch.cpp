@@ -258,10 +258,10 @@ static int launch_sched_frames(urt_context* ctx, const DevScene& S, const FrameP
   }
   const unsigned int slot = ctx->table_next++ % (unsigned int)urt_context::kTableSlots;
   if (ctx->table_next > (unsigned int)urt_context::kTableSlots) URT_HIP(ctx, hipEventSynchronize(ctx->table_ev[slot].get()));   // (four launches ago: long done)
-  FrameUniforms* h_slot = ctx->h_tables.get() + (size_t)slot * kMaxFramesPerLaunch;
-  FrameUniforms* d_table = ctx->d_tables.get() + (size_t)slot * kMaxFramesPerLaunch;
-  std::memcpy(h_slot, T.f, sizeof(FrameUniforms) * (size_t)P.n_frames);
-  URT_HIP(ctx, hipMemcpyAsync(d_table, h_slot, sizeof(FrameUniforms) * (size_t)P.n_frames, hipMemcpyHostToDevice, st));
+  FrameEntry* h_slot = ctx->h_tables.get() + (size_t)slot * kMaxFramesPerLaunch;
+  FrameEntry* d_table = ctx->d_tables.get() + (size_t)slot * kMaxFramesPerLaunch;
+  std::memcpy(h_slot, T.f, sizeof(FrameEntry) * (size_t)P.n_frames);
+  URT_HIP(ctx, hipMemcpyAsync(d_table, h_slot, sizeof(FrameEntry) * (size_t)P.n_frames, hipMemcpyHostToDevice, st));
   URT_HIP(ctx, hipEventRecord(ctx->table_ev[slot].get(), st));
   int waves_per_block = P.block_threads / 64;
   long want = ((long)P.tiles_x * P.n_strips * P.n_frames + waves_per_block - 1) / waves_per_block;
@@ -555,7 +555,7 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
     if (B.n == 0) { int rc = bind_sky(ctx, S); if (rc) return rc; }
     if (limit <= 1) {                                     // not batched: trace this frame now, straight into the texture
       FrameTable T{};
-      T.f[0] = fu;
+      T.f[0] = frame_entry(fu);
       P.frame_group = 1;
       int rc = launch_sched_frames(ctx, S, P, T, res->dev, front_mode, count);
       if (rc) return rc;
@@ -564,7 +564,7 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
         B.limit = std::min(limit, ctx->slab_frames);
         B.tex = res_h; B.scene_epoch = ctx->scene_epoch; B.S = S; B.P = P; B.front_mode = front_mode; B.count = count;
       }
-      B.T.f[B.n] = fu;
+      B.T.f[B.n] = frame_entry(fu);
       res->dev = ctx->slab.get() + (size_t)B.n * ctx->slab_stride;   // Result now names this frame's slot
       B.n++;
     }

@@ -47,10 +47,29 @@ __device__ __forceinline__ void camera_ray(const FrameParams& P, int x, int y, f
 }
 // The same for a batched launch (modes 3, 5): the uniforms of the path's frame come from the launch's frame table in device
 // memory, read with scalar loads (table pointer and frame index are wave-uniform).  `f` must be wave-uniform.
-__device__ __forceinline__ void camera_ray_frame(const FrameUniforms* T, int f, const FrameParams& P, int x, int y, bool new_pixel, float& seed, v3& o, v3& d) {
+// A NEW pixel's two draws start from the frame's _Seed and _Seed + 0.5 in every lane, and the ray's origin is the same for the whole
+// frame: the seed-only half of both draws (two constant divisions each) and the origin come from the table entry, where the host put
+// them (frame_derived.h: the same urt_math.h functions on the same operands), and only rand_draw runs per lane.  The next ray of a
+// pixel carries its own seed and draws as before.  -DURT_UNIFORM_REFILL=0 (an experiment build): everything per lane, as it was.
+#ifndef URT_UNIFORM_REFILL
+#define URT_UNIFORM_REFILL 1
+#endif
+__device__ __forceinline__ void camera_ray_frame(const FrameEntry* T, int f, const FrameParams& P, int x, int y, bool new_pixel, float& seed, v3& o, v3& d) {
   kfloatp q = (kfloatp)(unsigned long long)(T + __builtin_amdgcn_readfirstlane(f));
-  if (new_pixel) seed = q[34];                     // RS:16: every pixel starts from the frame's _Seed; it carries over between a pixel's rays (RS:444)
   float px = (float)x, py = (float)y;
+  if (URT_UNIFORM_REFILL && new_pixel) {
+    float r0 = rand_draw(q[36], px, py);
+    float r1 = rand_draw(q[37], px, py);
+    seed = (q[34] + 0.5f) + 0.5f;                  // the two steps of the two draws, not one add
+    float u = axis_uv(px + r0 + q[32], P.width);
+    float v = axis_uv(py + r1 + q[33], P.height);
+    v3 dir = mul_m4_k(q + 16, u, v, 0.0f, 1.0f);   // camera_ray_uv with the origin read instead of computed
+    dir = mul_m4_k(q, dir.x, dir.y, dir.z, 0.0f);
+    o = mk3(q[38], q[39], q[40]);
+    d = normalize(dir);
+    return;
+  }
+  if (new_pixel) seed = q[34];                     // RS:16: every pixel starts from the frame's _Seed; it carries over between a pixel's rays (RS:444)
   float r0 = rand_next(seed, px, py);
   float r1 = rand_next(seed, px, py);
   float u = axis_uv(px + r0 + q[32], P.width);     // jitter_uv written out: called through it, the table entry's scalar loads land elsewhere and k_sched's bytes change
@@ -58,7 +77,8 @@ __device__ __forceinline__ void camera_ray_frame(const FrameUniforms* T, int f, 
   camera_ray_uv(q, q + 16, u, v, o, d);
 }
 static_assert(__builtin_offsetof(FrameUniforms, invp) == 64 && __builtin_offsetof(FrameUniforms, pixel_off_x) == 128 &&
-              __builtin_offsetof(FrameUniforms, seed) == 136, "camera_ray_frame indexes the table as floats");
+              __builtin_offsetof(FrameUniforms, seed) == 136 && __builtin_offsetof(FrameEntry, d) == 144 && __builtin_offsetof(FrameDerived, a1) == 4 &&
+              __builtin_offsetof(FrameDerived, origin) == 8 && sizeof(FrameEntry) == 164, "camera_ray_frame indexes the table as floats");
 
 // Runs body(frame index as a wave-uniform value, lane predicate) once per distinct frame among the lanes of `pred` (almost
 // always one: a wave's refill straddles two frames only at a frame boundary of the launch).
@@ -310,6 +330,29 @@ __device__ __forceinline__ bool wg_fetch_pixels(const FrameParams& P, unsigned l
       if (lane == 0) __hip_atomic_compare_exchange_strong(rs, &seen, s2, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       if (wave_uniform64(seen) == s) break;
     }
+#if URT_UNIFORM_REFILL
+    // The k slots are consecutive slots of the chunk (k <= popcount(want) <= 64): they lie in at most two of its tiles.  Frame, tile order and the tile's pixel origin
+    // (a division by tiles_x, the strip arithmetic) are worked out once per tile on wave-uniform values, in scalar registers; what is
+    // left per lane is the slot's place inside its 8x8 tile and the region test.  slot_pixel's integers, tile by tile.
+    if (k) {
+      const unsigned int first = (unsigned int)s & 0x7ffu;
+      const unsigned int idx = first + (rank - taken);
+      const bool in = mine && rank >= taken && rank < taken + k;
+      for (unsigned int t = first >> 6; t <= (first + k - 1u) >> 6; t++) {
+        unsigned int tile = ((unsigned int)(s >> 24) & 0xffffffu) + t, f = (unsigned int)(s >> 48) & 0x7fu;
+        if (tile >= tiles_per_frame) { unsigned int q = tile / tiles_per_frame; f += q; tile -= q * tiles_per_frame; }   // frame_group 1 only: the chunk runs on into the next frame
+        if (P.tile_order == 1) tile = tiles_per_frame - 1u - tile;   // top strip first
+        const int ty = (int)tile / P.tiles_x, tx = (int)tile - ty * P.tiles_x;
+        const int x0 = tx * 8, y0 = (P.first_group_row + ty * P.row_stride) * 8;
+        if (in && (idx >> 6) == t) {
+          *frame = (int)f;
+          x = x0 + (int)(idx & 7u);
+          y = y0 + (int)((idx >> 3) & 7u);
+          got = x < P.region_w && y < P.region_h;
+        }
+      }
+    }
+#else
     if (mine && rank >= taken && rank < taken + k) {
       const unsigned int idx = ((unsigned int)s & 0x7ffu) + (rank - taken);
       unsigned int tile = ((unsigned int)(s >> 24) & 0xffffffu) + (idx >> 6), f = (unsigned int)(s >> 48) & 0x7fu;
@@ -318,6 +361,7 @@ __device__ __forceinline__ bool wg_fetch_pixels(const FrameParams& P, unsigned l
       if (P.tile_order == 1) tile = tiles_per_frame - 1u - tile;   // top strip first
       got = slot_pixel(P, tile, idx & 63u, x, y);
     }
+#endif
     taken += k;
     if (!fetch) { if (k == avail) exhausted = true; break; }   // (no fetch after a drain: it was the workgroup's last chunk)
     const unsigned long long ns = wg_fetch_run(P, (unsigned int)(s >> 55) & 63u, next, ntiles, tiles_per_frame);

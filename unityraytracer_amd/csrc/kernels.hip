@@ -70,7 +70,7 @@ namespace {
 // The cone words ride in the nodes' two spare dwords and are 0 (never skip) while option "blas_cones" is off, so the instantiation — and its
 // name — is the same either way; the counting instantiation walks like the oracle, event for event.
 template <bool COUNT, int BLOCK, int FMODE, bool MULTI, bool QN = false>
-__global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, FrameParams P, const FrameUniforms* __restrict__ T, float4* __restrict__ result, DevCounters* ctr,
+__global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, FrameParams P, const FrameEntry* __restrict__ T, float4* __restrict__ result, DevCounters* ctr,
                                                unsigned int* __restrict__ next) {
   // LDS of the workgroup: [the tile reservation: 16 B][top of the triangle-BVH forest: top_nodes x 64 B, shared by its waves][tables][stacks of wave 0][wave 1]...
   // Apart from the reservation word (frame_device.h wg_fetch_pixels) the waves of a workgroup share only read-only copies and never synchronise after this prologue.
@@ -508,7 +508,7 @@ size_t sched_lds_bytes(const DevScene& S, const FrameParams& P) {
 
 // The k_sched instantiation for the runtime values: entry i of a table over (COUNT, MULTI, QN, FMODE 0-3, BLOCK 64 / 256), bit by bit.
 // QN never comes with COUNT (the counting instantiation walks the float nodes, like the oracle): those entries are not instantiated.
-using SchedKernel = void (*)(DevScene, FrameParams, const FrameUniforms*, float4*, DevCounters*, unsigned int*);
+using SchedKernel = void (*)(DevScene, FrameParams, const FrameEntry*, float4*, DevCounters*, unsigned int*);
 template <int I>
 static constexpr SchedKernel sched_entry() {
   constexpr bool COUNT = (I & 1) != 0, MULTI = (I & 2) != 0, QN = (I & 4) != 0;
@@ -521,7 +521,7 @@ static SchedKernel sched_kernel(bool count, int block, int fmode, bool multi, bo
   return table[(count ? 1 : 0) | (multi ? 2 : 0) | (qn ? 4 : 0) | (fmode << 3) | (block == 256 ? 32 : 0)];
 }
 
-hipError_t launch_sched(const DevScene& S, const FrameParams& P, const FrameUniforms* T, float4* result, DevCounters* ctr,
+hipError_t launch_sched(const DevScene& S, const FrameParams& P, const FrameEntry* T, float4* result, DevCounters* ctr,
                         unsigned int* next, int n_blocks, int front_mode, bool count, hipStream_t st, TraceLaunchRecord* rec) {
   if (n_blocks <= 0) return hipSuccess;
   if (P.block_threads != 64 && P.block_threads != 256) return hipErrorInvalidValue;   // independent waves; a workgroup shares the LDS top-of-tree copy

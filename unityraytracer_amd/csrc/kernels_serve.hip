@@ -54,7 +54,7 @@ __device__ __forceinline__ void serve_wait(bool waiting, const int* my_flag, con
   }
 }
 template <bool COUNT, int BLOCK, int FMODE, bool MULTI>
-__global__ __launch_bounds__(BLOCK, URT_SERVE_OCC) void k_serve(DevScene S, FrameParams P, const FrameUniforms* __restrict__ T, float4* __restrict__ result, DevCounters* ctr,
+__global__ __launch_bounds__(BLOCK, URT_SERVE_OCC) void k_serve(DevScene S, FrameParams P, const FrameEntry* __restrict__ T, float4* __restrict__ result, DevCounters* ctr,
                                                unsigned int* __restrict__ next, float4* __restrict__ mail) {
   constexpr int NW = BLOCK / 64;
   static_assert(NW >= 1 && (NW & (NW - 1)) == 0, "waves per workgroup: a power of two");
@@ -378,7 +378,7 @@ __global__ __launch_bounds__(BLOCK, URT_SERVE_OCC) void k_serve(DevScene S, Fram
 // ---------------------------------------------------------------------------------------------------
 namespace urtd {
 
-using ServeKernel = void (*)(DevScene, FrameParams, const FrameUniforms*, float4*, DevCounters*, unsigned int*, float4*);
+using ServeKernel = void (*)(DevScene, FrameParams, const FrameEntry*, float4*, DevCounters*, unsigned int*, float4*);
 template <bool COUNT, bool MULTI>
 static ServeKernel serve_kernel_f(int fmode) {                   // front modes 0 - 2 (no masked FRONT in mode 5)
   return fmode == 2 ? k_serve<COUNT, 256, 2, MULTI> : fmode == 1 ? k_serve<COUNT, 256, 1, MULTI> : k_serve<COUNT, 256, 0, MULTI>;
@@ -388,7 +388,7 @@ static ServeKernel serve_kernel(bool count, int fmode, bool multi) {
                : (multi ? serve_kernel_f<false, true>(fmode) : serve_kernel_f<false, false>(fmode));
 }
 
-hipError_t launch_serve(const DevScene& S, const FrameParams& P, const FrameUniforms* T, float4* result, DevCounters* ctr,
+hipError_t launch_serve(const DevScene& S, const FrameParams& P, const FrameEntry* T, float4* result, DevCounters* ctr,
                         unsigned int* next, float4* mail, int n_blocks, int front_mode, bool count, hipStream_t st, TraceLaunchRecord* rec) {
   if (n_blocks <= 0) return hipSuccess;
   if (P.block_threads != 256 || !P.serve || !mail) return hipErrorInvalidValue;

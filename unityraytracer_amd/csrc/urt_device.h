@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "blas_builder.h"   // kBlasNodeFloats, kEmptyMeshRoot
+#include "frame_derived.h"  // FrameDerived: the per-frame values of a batched launch's table
 
 namespace urtd {
 
@@ -107,8 +108,16 @@ struct FrameUniforms {
   float seed;               // _Seed
   float pad;
 };
-static constexpr int kMaxFramesPerLaunch = 64;      // the table lives in device memory (frame_batch.cpp stages it through pinned host slots): 64 x 144 B
-struct FrameTable { FrameUniforms f[kMaxFramesPerLaunch]; };   // host-side image of one launch's table
+// One entry of a batched launch's frame table: the uniforms and, behind them, what every pixel of the frame derives from them alone
+// (frame_derived.h).  The kernels that take a FrameUniforms by value (aov.hip, radiance.hip) keep their arguments; k_sched / k_serve take
+// a pointer to the table's first entry.
+struct FrameEntry {
+  FrameUniforms u;
+  FrameDerived d;
+};
+inline FrameEntry frame_entry(const FrameUniforms& u) { return FrameEntry{u, frame_derived(u.c2w, u.seed)}; }
+static constexpr int kMaxFramesPerLaunch = 64;      // the table lives in device memory (frame_batch.cpp stages it through pinned host slots): 64 x 164 B
+struct FrameTable { FrameEntry f[kMaxFramesPerLaunch]; };   // host-side image of one launch's table
 
 // LDS entries per lane of the two traversal stacks of a kernel that traces one ray per lane (trace_device.h lane_stacks)
 struct LaneStackSize { int tlas, blas; };
