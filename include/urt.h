@@ -59,7 +59,10 @@ URT_API int urt_abi_version(void);                       /* bumps when this head
                                                             urt_upsample, urt_auto_exposure, urt_tonemap, urt_bloom and the blend
                                                             shapes on the device — urt_morph_plan_create, urt_morph_plan_info,
                                                             urt_morph_plan_release, urt_morph_vertices, urt_debug_build_morph_plan —
-                                                            were added without changing anything that existed) */
+                                                            and the object-level BVH on the device —
+                                                            urt_mesh_leaf_bounds_device, urt_sphere_leaf_bounds_device,
+                                                            urt_build_object_bvh_device — were added without changing anything
+                                                            that existed) */
 URT_API int urt_device_count(int* out_count);
 /* One context per process and GPU (the one-process-per-GPU model).  device = HIP ordinal. */
 URT_API int urt_context_create(int device, urt_context** out_ctx);
@@ -281,6 +284,57 @@ URT_API int urt_morph_vertices(urt_context* ctx, urt_handle plan, urt_handle res
  * (urt_host_last_error). */
 URT_API int urt_debug_build_morph_plan(const urt_MorphDelta* deltas, int n_deltas, int n_targets, int first, int count, int32_t* ranges,
                                        int32_t* order, int32_t out_sizes[3]);
+
+/* ---- the object-level BVH on the device ---------------------------------------------------------------------------------------------
+ * The leaf boxes of _MeshObjects and _Spheres and the implicit heap over them (_MeshBVH / _SphereBVH, one leaf per object), computed from
+ * and written into the DEVICE side of buffers: what urt_host_mesh_leaf_bounds(literal = 0), urt_host_sphere_leaf_bounds(literal = 0) and
+ * urt_host_build_object_bvh compute on the host, value for value, for a host whose vertices live on the device (urt_skin_vertices,
+ * urt_morph_vertices) or that does not want the host pass.
+ * All three calls enqueue on the context's stream and synchronise nothing; deferred frames stay deferred and urt_counters does not change.
+ * Every buffer named gets a device mirror at first use, as with urt_skin_vertices.  The destination's WHOLE element range becomes stale
+ * and dirty, exactly as with urt_buffer_set_data_device: a destination that is bound as _MeshBVH / _SphereBVH is picked up by the next
+ * preparation, which downloads it as it downloads every device-written small table.  Checked before anything is enqueued or marked:
+ * URT_ERR_INVALID_HANDLE for a handle that is 0 or unknown; URT_ERR_INVALID_ARGUMENT for a NULL context, strides or counts that do not
+ * fit and a destination that is also an input.  On any error nothing is enqueued or marked.
+ * There are no urt_group_* twins of the calls of this section (urt_group_context reaches a rank's context). */
+/* mesh_objects (stride 112), vertices (stride 12), indices (stride 4), dst_leaves (stride 28, the count of mesh_objects).  Leaf m is what
+ * urt_host_mesh_leaf_bounds(..., literal = 0, ...) writes, read from the CURRENT device contents of `vertices`.  With M the matrix of
+ * MeshObject m, per index slot i of [indices_offset, indices_offset + indices_count): p = vertices[indices[i]] and, for r = 0, 1, 2,
+ *     w.r = ((M[r]*p.x + M[4+r]*p.y) + M[8+r]*p.z) + M[12+r]
+ * in float32, one rounding per operation, no fma; vmin / vmax = the component-wise min / max of the w, index = m.  A MeshObject with
+ * indices_count == 0 gets an all-zero box and index = m.
+ * The per-mesh (offset, count) and the matrices come from `mesh_objects`; the ranges are validated on that buffer's host copy (a stale
+ * one is downloaded first: the one case in which this call synchronises): offset < 0, count < 0 or offset + count beyond `indices` is
+ * URT_ERR_SCENE.  Index VALUES are not validated: a slot whose index lies outside `vertices` is skipped, which is never a fault and never
+ * an error.  A NaN coordinate takes no part in that component's min or max; a component with no contributing value gets (+inf, -inf);
+ * signed zeros compare as values.
+ * CONTRACT: equal to the host function, by value, whenever every index is in range and no transformed coordinate is NaN.
+ * Two kernels: per-workgroup partial boxes (at most URT_MESH_LEAF_BLOCKS workgroups per MeshObject, 256 slots each per pass) into a
+ * grow-only scratch held by the context, then one workgroup per MeshObject.  Zero MeshObjects: URT_OK after the checks. */
+URT_API int urt_mesh_leaf_bounds_device(urt_context* ctx, urt_handle mesh_objects, urt_handle vertices, urt_handle indices,
+                                        urt_handle dst_leaves);
+#define URT_MESH_LEAF_BLOCKS 256
+/* spheres (stride 56), dst_leaves (stride 28), equal counts.  Per component a = position - (-radius), b = position - radius,
+ * vmin = min(a, b), vmax = max(a, b), index = i: urt_host_sphere_leaf_bounds(literal = 0), equal by value for all non-NaN inputs. */
+URT_API int urt_sphere_leaf_bounds_device(urt_context* ctx, urt_handle spheres, urt_handle dst_leaves);
+/* leaves and dst_nodes have stride 28; with n = the count of leaves, dst_nodes has the count urt_host_object_bvh_length(n).
+ * n > URT_OBJECT_BVH_DEVICE_MAX is URT_ERR_INVALID_ARGUMENT (the kernel is one workgroup, the object walk's stack is 32 deep and the
+ * reference's scenes hold 6 to 21 objects): such a heap is built with urt_host_build_object_bvh.
+ * The result is what urt_host_build_object_bvh(leaves, n, ...) writes, read from the current device contents of `leaves`.  NORMATIVE:
+ *   - the heap is implicit, children of node i at 2i+1 and 2i+2; the root holds the range of all n leaves;
+ *   - filler nodes are all zero with index = -1;
+ *   - a one-object range copies its leaf record verbatim: box corners as given, inverted boxes included, and the leaf's own index field;
+ *   - an interior node is the union over min(vmin, vmax) / max(vmin, vmax) of its leaves, with index = -1;
+ *   - centres are 0.5f*vmin + 0.5f*vmax per component;
+ *   - the axis: start with ax = 0; move to 1 if extent 1 is greater than extent 0; then move to 2 if extent 2 is greater than the extent
+ *     of ax.  Extents are max - min of the range's centres;
+ *   - the range is ordered by (centre[ax], leaf number); the left child takes the first (cnt + 1) / 2.
+ * CONTRACT: integer fields equal bit for bit and floats equal by value, whenever every leaf coordinate is finite.  With non-finite
+ * coordinates the call never faults and the heap stays well formed — every leaf appears exactly once — the device ordering keys by a
+ * total order in which -0 = +0 and every NaN ranks above +inf; equality with the host is not promised there (the host's std::sort has
+ * no defined answer for that input). */
+URT_API int urt_build_object_bvh_device(urt_context* ctx, urt_handle leaves, urt_handle dst_nodes);
+#define URT_OBJECT_BVH_DEVICE_MAX 1024
 
 /* ---- RenderTexture / Texture (RGBA32F = ARGBFloat, linear) -------------------------------- */
 /* new RenderTexture(w, h, 0, ARGBFloat, Linear){enableRandomWrite}.Create()   RM:834-840 */

@@ -46,6 +46,11 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_morph_plan_release(IntPtr ctx, ulong plan);
     [DllImport(Lib)] internal static extern int urt_morph_vertices(IntPtr ctx, ulong plan, ulong restVertices, ulong restNormals, ulong weights, ulong dstVertices, ulong dstNormals, int flags);
     [DllImport(Lib)] internal static extern int urt_debug_build_morph_plan(MorphDelta[] deltas, int nDeltas, int nTargets, int first, int count, [Out] int[] ranges, [Out] int[] order, [Out] int[] outSizes3);
+    // the object-level BVH on the device (include/urt.h): leaf boxes and the implicit heap written into the device side of buffers; nothing is waited for
+    internal const int ObjectBvhDeviceMax = 1024;   // URT_OBJECT_BVH_DEVICE_MAX
+    [DllImport(Lib)] internal static extern int urt_mesh_leaf_bounds_device(IntPtr ctx, ulong meshObjects, ulong vertices, ulong indices, ulong dstLeaves);
+    [DllImport(Lib)] internal static extern int urt_sphere_leaf_bounds_device(IntPtr ctx, ulong spheres, ulong dstLeaves);
+    [DllImport(Lib)] internal static extern int urt_build_object_bvh_device(IntPtr ctx, ulong leaves, ulong dstNodes);
     [DllImport(Lib)] internal static extern int urt_buffer_get_info(IntPtr ctx, ulong buffer, out int count, out int stride);
     [DllImport(Lib)] internal static extern int urt_buffer_release(IntPtr ctx, ulong buffer);
 

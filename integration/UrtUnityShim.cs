@@ -520,6 +520,41 @@ public sealed class UrtComputeBuffer {
     }
 }
 
+/// The object-level heaps (_MeshBVH / _SphereBVH) built on the GPU: RayTraceMaster.device_object_heaps of the Python mirror (include/urt.h
+/// "the object-level BVH on the device").  For a host whose vertices live on the device (UrtSkinnedMesh) or that does not want the host
+/// pass of SetupBVHLeaves / CreateBVH: the boxes are those of the mesh's own points, read from the device side of _Vertices.  It owns the
+/// two leaf buffers.  On one context only, as UrtSkinnedMesh.
+public sealed class UrtObjectHeaps {
+    UrtComputeBuffer meshLeaves, sphereLeaves;
+    static UrtComputeBuffer Sized(UrtComputeBuffer b, int count) {
+        if (b != null && b.count != count) { b.Release(); b = null; }
+        return b ?? new UrtComputeBuffer(count, 28);
+    }
+    /// Leaf boxes, then the heap, into the device side of meshBvh and sphereBvh (the buffers bound as _MeshBVH / _SphereBVH, sized by
+    /// CreateBVH's length for their object counts): five kernels on the context's stream, nothing is waited for; the next frame's
+    /// preparation picks the heaps up.  Either triple may be null (no such objects).  More than UrtNative.ObjectBvhDeviceMax objects of one
+    /// kind: build that heap on the host.
+    public void RebuildObjectHeapsOnDevice(UrtComputeBuffer meshObjects, UrtComputeBuffer vertices, UrtComputeBuffer indices, UrtComputeBuffer meshBvh,
+                                           UrtComputeBuffer spheres, UrtComputeBuffer sphereBvh) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtObjectHeaps: build on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        if (meshObjects != null && meshBvh != null) {
+            meshLeaves = Sized(meshLeaves, meshObjects.count);
+            UrtDevice.Check(UrtNative.urt_mesh_leaf_bounds_device(ctx, meshObjects.handle, vertices.handle, indices.handle, meshLeaves.handle));
+            UrtDevice.Check(UrtNative.urt_build_object_bvh_device(ctx, meshLeaves.handle, meshBvh.handle));
+        }
+        if (spheres != null && sphereBvh != null) {
+            sphereLeaves = Sized(sphereLeaves, spheres.count);
+            UrtDevice.Check(UrtNative.urt_sphere_leaf_bounds_device(ctx, spheres.handle, sphereLeaves.handle));
+            UrtDevice.Check(UrtNative.urt_build_object_bvh_device(ctx, sphereLeaves.handle, sphereBvh.handle));
+        }
+    }
+    public void Release() {
+        if (meshLeaves != null) { meshLeaves.Release(); meshLeaves = null; }
+        if (sphereLeaves != null) { sphereLeaves.Release(); sphereLeaves = null; }
+    }
+}
+
 /// A skinned mesh animated on the GPU: RayTraceMaster.AttachSkin / SkinMeshes of the Python mirror (include/urt.h urt_skin_vertices,
 /// urt_buffer_bounds).  One instance serves every skinned MeshObject of a scene: it owns rest-pose, bone-index and bone-weight buffers of
 /// the vertex count and one bone table per mesh.  Per frame only the bones travel; the positions are written into the device side of the

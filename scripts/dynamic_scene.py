@@ -11,6 +11,11 @@ from unityraytracer_amd import Context, RayTraceMaster, scenes
 ctx = Context(0)
 names = [a for a in sys.argv[1:] if not a.startswith("--")] or ["C4", "C5"]
 if "--move-objects" in sys.argv:
+    # --device-heaps: RayTraceMaster.device_object_heaps on (the object-level heaps are built on the GPU); --alternate: off and on, move by
+    # move, in one process; --repeats N (default 1): N moves per label and form, each to a new place, reported as median [min .. max]
+    repeats = int(sys.argv[sys.argv.index("--repeats") + 1]) if "--repeats" in sys.argv else 1
+    names = [a for a in names if not a.isdigit()] or ["C4", "C5"]
+    forms = (False, True) if "--alternate" in sys.argv else (True,) if "--device-heaps" in sys.argv else (False,)
     for name in names:
         sc = scenes.CONFIGS[name](640, 360)
         m = RayTraceMaster(ctx, sc)
@@ -18,21 +23,36 @@ if "--move-objects" in sys.argv:
         for _ in range(8):
             m.OnRenderImage()
         ctx.synchronize()
-        out = []
+        out, step = [], 0
         for label, ks in (("one moved", [len(sc.mesh_objects) - 1]), ("all moved", range(len(sc.mesh_objects))), ("all moved again", range(len(sc.mesh_objects)))):
-            edits = {}
-            for k in ks:
-                mat = np.asarray(sc.mesh_objects[k]["localToWorldMatrix"], np.float32).copy(); mat[12] += 0.05; edits[k] = mat
-            t0 = time.perf_counter()
-            m.MoveObjects(edits)
-            t_host = (time.perf_counter() - t0) * 1e3
-            ctx.synchronize()
-            wall = (time.perf_counter() - t0) * 1e3
-            kept = float((m._tcount.GetPixels()[..., 0] > 0).mean())
-            out.append(f"{label}: host {t_host:.1f} ms, edits-to-GPU-done {wall:.1f} ms, {kept:.3f} of the pixels keep history")
-            for _ in range(4):
-                m.OnRenderImage()
-            ctx.synchronize()
+            t = {f: [] for f in forms}
+            for rep in range(repeats):
+                for on in forms:
+                    m.device_object_heaps = on
+                    step += 1
+                    edits = {}
+                    for k in ks:
+                        mat = np.asarray(sc.mesh_objects[k]["localToWorldMatrix"], np.float32).copy()
+                        mat[12] += 0.05 if repeats == 1 else 0.01 * step
+                        edits[k] = mat
+                    t0 = time.perf_counter()
+                    m.MoveObjects(edits)
+                    t_host = (time.perf_counter() - t0) * 1e3
+                    ctx.synchronize()
+                    wall = (time.perf_counter() - t0) * 1e3
+                    kept = float((m._tcount.GetPixels()[..., 0] > 0).mean())
+                    t[on].append((t_host, wall, kept))
+                    for _ in range(4):
+                        m.OnRenderImage()
+                    ctx.synchronize()
+            for on in forms:
+                host, wall, kept = (np.array(c) for c in zip(*t[on]))
+                tag = "heaps on the device" if on else "heaps on the host"
+                if repeats == 1:
+                    out.append(f"{label} ({tag}): host {host[0]:.1f} ms, edits-to-GPU-done {wall[0]:.1f} ms, {kept[0]:.3f} of the pixels keep history")
+                else:
+                    out.append(f"{label} ({tag}, {repeats} moves): host median {np.median(host):.2f} ms [{host.min():.2f} .. {host.max():.2f}], "
+                               f"edits-to-GPU-done median {np.median(wall):.2f} ms [{wall.min():.2f} .. {wall.max():.2f}], {np.median(kept):.3f} of the pixels keep history")
         print(f"{name} {sc.n_triangles} triangles, {len(sc.mesh_objects)} MeshObjects, 640x360, MoveObjects with temporal accumulation: " + "; ".join(out), flush=True)
         m.OnDisable()
     sys.exit(0)

@@ -3,7 +3,9 @@
       _Normals and _MeshBVH and the preparation — what a host had to do before the buffers had a device side.  `--parent-lib` runs this
       part on the parent commit's library too, in a child process in the same session;
   (b) the device path: RayTraceMaster.SkinMeshes — bones SetData + urt_skin_vertices + urt_buffer_bounds, the heap rebuilt from the
-      returned bounds and SetData — and the preparation;
+      returned bounds and SetData — and the preparation.  `--parent-lib` runs this part on the parent commit's library too;
+  (b') the same with RayTraceMaster.device_object_heaps: urt_mesh_leaf_bounds_device + urt_build_object_bvh_device instead of the
+      bounds calls and the host's heap — no synchronising call before the preparation.  (b) and (b') alternate, update by update;
   (c) positions that already live on the GPU: urt_buffer_set_data_device from torch tensors, SetData of _MeshBVH, the preparation.
 Cases: C3's blob (one MeshObject, 34,802 vertices, 1920x1080), C5 with one and with all twelve MeshObjects skinned; every update is another
 two-bone bend.  After the updates of (a) and of (b) with one and the same pose, the time of a 16-frame launch: the same tree, so the
@@ -116,27 +118,41 @@ def part_update(args, tag, results):
             r.update(summary("update_ms", [x[1] for x in t]))
             r.update(summary("launch16_ms", [launch_ms(ctx, m) for _ in range(3)]))
             print(json.dumps(r), flush=True); results.append(r)
-            if not device_side:
-                m.OnDisable()
-                continue
-            # (b) the device path, ending on the pose (a) ended on
+            # (b) the device path, ending on the pose (a) ended on, and (b') the same with the heaps built on the device: they alternate
             for k in meshes:
                 m.AttachSkin(k, *case.skin[k])
             m._vertexBuffer.SetData(sc.vertices); m._normalBuffer.SetData(sc.normals); finish(ctx)
-            t = []
+            t = {False: [], True: []}
             bone_sets = [{k: case.bones(k, s + 1) for k in meshes} for s in range(args.repeats + 1)]      # (what an animation system hands over)
+            forms = (False, True) if device_side else (False,)                    # (the parent's library has no device heaps)
             for bones in bone_sets:
-                ctx.synchronize()
-                t0 = time.perf_counter()
-                m.SkinMeshes(bones)
-                finish(ctx)
-                t.append((time.perf_counter() - t0) * 1e3)
+                for on in forms:
+                    m.device_object_heaps = on
+                    ctx.synchronize()
+                    t0 = time.perf_counter()
+                    m.SkinMeshes(bones)
+                    finish(ctx)
+                    t[on].append((time.perf_counter() - t0) * 1e3)
+            m.device_object_heaps = False
+            m.SkinMeshes(bone_sets[-1]); finish(ctx)                              # (the launch below: on the host path's heap, as before)
             r = dict(base, path="b_skin_on_device")
-            r.update(summary("update_ms", t[1:]))
+            r.update(summary("update_ms", t[False][1:]))
             r.update(summary("launch16_ms", [launch_ms(ctx, m) for _ in range(3)]))
             r["downloads"] = ctx.buffer_state(m._vertexBuffer)["downloads"] + ctx.buffer_state(m._normalBuffer)["downloads"]
             r["in_place"] = ctx.deform_stats()["deformed"]
             print(json.dumps(r), flush=True); results.append(r)
+            if not device_side:
+                m.OnDisable()
+                continue
+            m.device_object_heaps = True
+            m.SkinMeshes(bone_sets[-1]); finish(ctx)
+            r = dict(base, path="b2_skin_on_device_heaps_on_device")
+            r.update(summary("update_ms", t[True][1:]))
+            r.update(summary("launch16_ms", [launch_ms(ctx, m) for _ in range(3)]))
+            r["downloads"] = ctx.buffer_state(m._vertexBuffer)["downloads"] + ctx.buffer_state(m._normalBuffer)["downloads"]
+            r["heap_downloads"] = ctx.buffer_state(m._meshObjectBVHBuffer)["downloads"]
+            print(json.dumps(r), flush=True); results.append(r)
+            m.device_object_heaps = False
             # (c) positions that live in torch tensors
             lo, hi = min(case.sp[k][0] for k in meshes), max(case.sp[k][1] for k in meshes)
             dev = [(torch.from_numpy(v[lo:hi]).cuda(), torch.from_numpy(nr[lo:hi]).cuda()) for v, nr, _ in poses]

@@ -17,7 +17,7 @@ ERROR_NAMES = {1: "INVALID_ARGUMENT", 2: "INVALID_HANDLE", 3: "NO_DEVICE", 4: "H
 # every symbol include/urt.h declares (tests check that the .so exports each of them)
 ABI_SYMBOLS = [
     "urt_abi_version", "urt_device_count", "urt_context_create", "urt_context_destroy", "urt_last_error", "urt_context_set_stream",
-    "urt_synchronize", "urt_flush", "urt_buffer_create", "urt_buffer_set_data", "urt_buffer_set_data_range", "urt_buffer_set_data_device", "urt_buffer_get_data_range", "urt_buffer_copy", "urt_skin_vertices", "urt_buffer_bounds", "urt_normals_plan_create", "urt_normals_plan_info", "urt_normals_plan_release", "urt_compute_normals", "urt_morph_plan_create", "urt_morph_plan_info", "urt_morph_plan_release", "urt_morph_vertices", "urt_buffer_get_info", "urt_buffer_release", "urt_texture_create",
+    "urt_synchronize", "urt_flush", "urt_buffer_create", "urt_buffer_set_data", "urt_buffer_set_data_range", "urt_buffer_set_data_device", "urt_buffer_get_data_range", "urt_buffer_copy", "urt_skin_vertices", "urt_buffer_bounds", "urt_normals_plan_create", "urt_normals_plan_info", "urt_normals_plan_release", "urt_compute_normals", "urt_morph_plan_create", "urt_morph_plan_info", "urt_morph_plan_release", "urt_morph_vertices", "urt_mesh_leaf_bounds_device", "urt_sphere_leaf_bounds_device", "urt_build_object_bvh_device", "urt_buffer_get_info", "urt_buffer_release", "urt_texture_create",
     "urt_texture_create_external", "urt_texture_set_pixels", "urt_texture_get_pixels", "urt_texture_get_info", "urt_texture_read_begin", "urt_texture_read_end", "urt_texture_read_begin_format", "urt_texture_read_end_format", "urt_texture_release",
     "urt_shader_set_buffer", "urt_shader_set_texture", "urt_shader_set_matrix", "urt_shader_set_vector", "urt_shader_set_float",
     "urt_shader_set_int", "urt_shader_dispatch", "urt_shader_dispatch_rows", "urt_blit_add", "urt_blit", "urt_texture_pack_rows",
@@ -136,6 +136,12 @@ MORPH_MAX_TARGETS = 4096
 class MorphPlanInfo(C.Structure):
     """urt_MorphPlanInfo (include/urt.h), 32 B: what urt_morph_plan_info reports of a morph plan."""
     _fields_ = [(n, C.c_int32) for n in ("first", "count", "n_targets", "n_entries", "max_valence", "n_touched")] + [("device_bytes", C.c_uint64)]
+
+
+# the object-level BVH on the device (include/urt.h URT_OBJECT_BVH_DEVICE_MAX, URT_MESH_LEAF_BLOCKS): the most leaves urt_build_object_bvh_device
+# takes, and the per-MeshObject workgroup cap of urt_mesh_leaf_bounds_device (a MeshObject of more than 256 * MESH_LEAF_BLOCKS index slots is strided over)
+OBJECT_BVH_DEVICE_MAX = 1024
+MESH_LEAF_BLOCKS = 256
 
 
 class UpsampleParams(C.Structure):
@@ -261,6 +267,9 @@ def load():
         "urt_morph_plan_release": ([vp, u64], i),
         "urt_morph_vertices": ([vp, u64, u64, u64, u64, u64, u64, i], i),
         "urt_debug_build_morph_plan": ([vp, i, i, i, i, vp, vp, vp], i),
+        "urt_mesh_leaf_bounds_device": ([vp, u64, u64, u64, u64], i),
+        "urt_sphere_leaf_bounds_device": ([vp, u64, u64], i),
+        "urt_build_object_bvh_device": ([vp, u64, u64], i),
         "urt_buffer_get_info": ([vp, u64, pi, pi], i),
         "urt_buffer_release": ([vp, u64], i),
         "urt_texture_create": ([vp, i, i, C.POINTER(u64)], i),

@@ -16,6 +16,7 @@
 
 #include "morph.h"
 #include "morph_plan.h"
+#include "object_bvh.h"
 #include "normals.h"
 #include "normals_plan.h"
 #include "present.h"
@@ -426,6 +427,94 @@ int urt_buffer_bounds(urt_context* ctx, urt_handle buffer, int first, int count,
   std::memcpy(&n, ctx->bd_result.get() + 6, 4);
   if (out_n) *out_n = (int)n;
   return check_watchdog(ctx);
+  URT_GUARD_END(ctx)
+}
+
+/* ---- the object-level BVH on the device (include/urt.h; csrc/object_bvh.hip) ---- */
+static_assert(URT_OBJECT_BVH_DEVICE_MAX == urtd::kObjectBvhDeviceMax && URT_MESH_LEAF_BLOCKS == urtd::kMeshLeafBlocks, "include/urt.h: the constants of csrc/object_bvh.h");
+
+// The buffers of one of the three calls, looked up and checked: handles first, then strides.  b[k] is set for every k on URT_OK.
+static int object_bvh_buffers(urt_context* ctx, const char* who, int n, const urt_handle* h, const char* const* name, const int* stride, Buffer** b) {
+  for (int k = 0; k < n; k++) {
+    b[k] = find_buffer(ctx, h[k]);
+    if (!b[k]) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string(who) + ": " + name[k] + " is 0 or an unknown buffer handle");
+  }
+  for (int k = 0; k < n; k++)
+    if (b[k]->stride != stride[k]) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(who) + ": the stride of " + name[k] + " is not " + std::to_string(stride[k]));
+  for (int k = 0; k + 1 < n; k++)
+    if (h[k] == h[n - 1]) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + name[k] + " is also the destination");
+  return URT_OK;
+}
+
+int urt_mesh_leaf_bounds_device(urt_context* ctx, urt_handle mesh_objects, urt_handle vertices, urt_handle indices, urt_handle dst_leaves) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  enum { kMeshes, kVerts, kIdx, kDst, kArgs };
+  const urt_handle h[kArgs] = {mesh_objects, vertices, indices, dst_leaves};
+  const char* const name[kArgs] = {"mesh_objects", "vertices", "indices", "dst_leaves"};
+  const int stride[kArgs] = {URT_STRIDE_MESHOBJECT, URT_STRIDE_VEC3, URT_STRIDE_INDEX, URT_STRIDE_BVHNODE};
+  Buffer* b[kArgs];
+  if (int rc = object_bvh_buffers(ctx, "mesh_leaf_bounds_device", kArgs, h, name, stride, b)) return rc;
+  const int n = b[kMeshes]->count;
+  if (b[kDst]->count != n) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "mesh_leaf_bounds_device: the count of dst_leaves is not that of mesh_objects");
+  if (n == 0) return URT_OK;
+  if (int rc = buffer_sync_host(ctx, *b[kMeshes])) return rc;   // the ranges are validated where the host can read them
+  for (int m = 0; m < n; m++) {
+    urt_MeshObject mo;
+    std::memcpy(&mo, b[kMeshes]->host.data() + (size_t)m * sizeof mo, sizeof mo);
+    if (mo.indices_offset < 0 || mo.indices_count < 0 || (long long)mo.indices_offset + (long long)mo.indices_count > (long long)b[kIdx]->count)
+      return fail(ctx, URT_ERR_SCENE, "mesh_leaf_bounds_device: MeshObject " + std::to_string(m) + " names a range outside indices");
+  }
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t rows = (size_t)std::min(n, 65535);
+  if (int rc = reserve(ctx, ctx->ob_partial, rows * kMeshLeafBlocks * kMeshLeafWords, "mesh_leaf_bounds_device: scratch allocation", ctx->stream)) return rc;
+  for (int k = 0; k < kArgs; k++) if (int rc = buffer_mirror(ctx, *b[k])) return rc;
+  URT_HIP(ctx, mesh_leaf_bounds(b[kMeshes]->mirror.get(), n, (const float*)b[kVerts]->mirror.get(), b[kVerts]->count,
+                                (const int32_t*)b[kIdx]->mirror.get(), b[kIdx]->count, ctx->ob_partial.get(), b[kDst]->mirror.get(), touch(ctx)));
+  mark_device_written(ctx, dst_leaves, *b[kDst], 0, n);
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+int urt_sphere_leaf_bounds_device(urt_context* ctx, urt_handle spheres, urt_handle dst_leaves) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  const urt_handle h[2] = {spheres, dst_leaves};
+  const char* const name[2] = {"spheres", "dst_leaves"};
+  const int stride[2] = {URT_STRIDE_SPHERE, URT_STRIDE_BVHNODE};
+  Buffer* b[2];
+  if (int rc = object_bvh_buffers(ctx, "sphere_leaf_bounds_device", 2, h, name, stride, b)) return rc;
+  const int n = b[0]->count;
+  if (b[1]->count != n) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "sphere_leaf_bounds_device: the count of dst_leaves is not that of spheres");
+  if (n == 0) return URT_OK;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  for (int k = 0; k < 2; k++) if (int rc = buffer_mirror(ctx, *b[k])) return rc;
+  URT_HIP(ctx, sphere_leaf_bounds(b[0]->mirror.get(), n, b[1]->mirror.get(), touch(ctx)));
+  mark_device_written(ctx, dst_leaves, *b[1], 0, n);
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+int urt_build_object_bvh_device(urt_context* ctx, urt_handle leaves, urt_handle dst_nodes) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  const urt_handle h[2] = {leaves, dst_nodes};
+  const char* const name[2] = {"leaves", "dst_nodes"};
+  const int stride[2] = {URT_STRIDE_BVHNODE, URT_STRIDE_BVHNODE};
+  Buffer* b[2];
+  if (int rc = object_bvh_buffers(ctx, "build_object_bvh_device", 2, h, name, stride, b)) return rc;
+  const int n = b[0]->count;
+  if (n > URT_OBJECT_BVH_DEVICE_MAX)
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "build_object_bvh_device: more than " + std::to_string(URT_OBJECT_BVH_DEVICE_MAX) +
+                                                   " leaves: build this heap with urt_host_build_object_bvh");
+  const int len = urt_host_object_bvh_length(n);
+  if (b[1]->count != len) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "build_object_bvh_device: the count of dst_nodes is not urt_host_object_bvh_length(" + std::to_string(n) + ") = " + std::to_string(len));
+  if (n == 0) return URT_OK;
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  for (int k = 0; k < 2; k++) if (int rc = buffer_mirror(ctx, *b[k])) return rc;
+  URT_HIP(ctx, build_object_bvh(b[0]->mirror.get(), n, b[1]->mirror.get(), len, touch(ctx)));
+  mark_device_written(ctx, dst_nodes, *b[1], 0, len);
+  return URT_OK;
   URT_GUARD_END(ctx)
 }
 

@@ -314,6 +314,7 @@ struct urt_context {
   struct UpSlot { urtd::PinnedBuf<char> host; urtd::Event done; bool used = false; } up_slot[kUpSlots];
   unsigned int up_next = 0;
   urtd::DeviceBuf<float> bd_partial; urtd::PinnedBuf<float> bd_result;   // urt_buffer_bounds: the per-block partials (and, behind them, the result); its host image
+  urtd::DeviceBuf<float> ob_partial;          // urt_mesh_leaf_bounds_device: the per-block partials of the largest call so far (csrc/object_bvh.h)
   urtd::DeviceBuf<float4> nm_face;            // urt_compute_normals: the face normals of the largest plan so far, 16 bytes each
 };
 

@@ -11,7 +11,7 @@
 #pragma once
 
 #if defined(URT_STAMPS) || defined(URT_SCHED_OCC) || defined(URT_SERVE_OCC) || defined(URT_SERVE_SLEEP) || defined(URT_SKY_FASTWRAP) || defined(URT_UNIFORM_REFILL) || \
-    defined(URT_SAH_BINS) || defined(URT_AB)
+    defined(URT_SAH_BINS) || defined(URT_AB) || defined(URT_MESH_LEAF_BLOCKS_SWEEP)
 #ifndef URT_EXPERIMENT
 #error "A/B, probe and diagnostic switches (-DURT_STAMPS, -DURT_SCHED_OCC, -DURT_SAH_BINS, ...) need -DURT_EXPERIMENT: the library then reports a negative urt_abi_version and loaders refuse it unless they opt in (csrc/experiments.h)"
 #endif

@@ -9,11 +9,16 @@
 #include <algorithm>
 
 #include "../../include/urt_math.h"
+#include "bounds_device.h"
 
 namespace {
 
 using namespace urt;
+using urtd::Bounds;
+using urtd::empty_bounds;
+using urtd::join;
 using urtd::kBoundsWords;
+using urtd::reduce_and_store;
 using urtd::kSkinBlock;
 
 // One bone's contribution to a vertex: t = w * (A P + b), u = w * (A N); a[12] = three columns of A, then b.
@@ -90,42 +95,6 @@ __global__ __launch_bounds__(kSkinBlock) void k_skin(const float* __restrict__ r
   for (int k = tid; k < span; k += kSkinBlock) {
     dst_v[base + (size_t)k] = s_p[k];
     if (kNormals) dst_n[base + (size_t)k] = s_n[k];
-  }
-}
-
-struct Bounds { float lo[3], hi[3]; unsigned int n; };
-
-__device__ __forceinline__ Bounds empty_bounds() {
-  Bounds b;
-  for (int c = 0; c < 3; c++) { b.lo[c] = __builtin_inff(); b.hi[c] = -__builtin_inff(); }
-  b.n = 0;
-  return b;
-}
-
-__device__ __forceinline__ void join(Bounds& b, const float lo[3], const float hi[3], unsigned int n) {
-  for (int c = 0; c < 3; c++) { b.lo[c] = lo[c] < b.lo[c] ? lo[c] : b.lo[c]; b.hi[c] = hi[c] > b.hi[c] ? hi[c] : b.hi[c]; }
-  b.n += n;
-}
-
-// The workgroup's union, written by its first lane to out[kBoundsWords]: lanes by shuffles, the four waves through LDS.  Min and max are
-// exact, so the order does not matter.
-__device__ __forceinline__ void reduce_and_store(Bounds b, float* __restrict__ out) {
-  for (int off = 32; off > 0; off >>= 1) {
-    float lo[3], hi[3];
-    for (int c = 0; c < 3; c++) { lo[c] = __shfl_xor(b.lo[c], off, 64); hi[c] = __shfl_xor(b.hi[c], off, 64); }
-    const unsigned int n = (unsigned int)__shfl_xor((int)b.n, off, 64);
-    join(b, lo, hi, n);
-  }
-  __shared__ float s_lo[4][3], s_hi[4][3];
-  __shared__ unsigned int s_cnt[4];
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-  if (lane == 0) { for (int c = 0; c < 3; c++) { s_lo[wave][c] = b.lo[c]; s_hi[wave][c] = b.hi[c]; } s_cnt[wave] = b.n; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    Bounds r = empty_bounds();
-    for (int w = 0; w < (int)(blockDim.x >> 6); w++) join(r, s_lo[w], s_hi[w], s_cnt[w]);
-    out[0] = r.lo[0]; out[1] = r.lo[1]; out[2] = r.lo[2]; out[3] = r.hi[0]; out[4] = r.hi[1]; out[5] = r.hi[2];
-    out[6] = __uint_as_float(r.n); out[7] = 0.0f;
   }
 }
 

@@ -52,6 +52,15 @@ class RayTraceMaster:
     _uplow = _upaov = _upcount = _upscaled = _uptarget = None   # (likewise: Upscale's textures)
     _exposure = _exposureState = _tonemapped = None             # (likewise: auto-exposure and ToneMap)
     _bloom = None                                               # (likewise: EnableBloom)
+    # With True, SkinMeshes, MorphMeshes and MoveObjects build the object-level heaps on the GPU (include/urt.h "the object-level BVH on the
+    # device": urt_mesh_leaf_bounds_device / urt_sphere_leaf_bounds_device, then urt_build_object_bvh_device into the heap buffers) instead
+    # of on the host, and make no synchronising call of their own.  scene.mesh_bvh / scene.sphere_bvh are then BEHIND the device, as
+    # scene.vertices already is after SkinMeshes: a host that wants them (OnDrawGizmos, a checkpoint of the scene) calls SyncObjectHeaps()
+    # first, which reads them back (GetData: it synchronises).  The boxes are those of the host functions (the mesh's own points), not the
+    # loose box of eight transformed corners.  False (the default): nothing differs from a master without the attribute.
+    device_object_heaps = False
+    _leafBuffers = (None, None)                                 # (likewise: the leaf records the device heaps are built from)
+    _heapsBehind = (False, False)                               # (likewise: scene.mesh_bvh / scene.sphere_bvh are behind their buffers)
 
     def __init__(self, ctx: Context, scene: scenes.Scene, rank: int = 0, world_size: int = 1, frame_seed: int = 0x5EED):
         self.ctx = ctx
@@ -98,6 +107,8 @@ class RayTraceMaster:
         self._morphs = {}                            # AttachBlendShapes: MeshObject index -> its span, rest pose, deltas, target count and (from the first MorphMeshes on) MorphPlan
         self._morphBuffers = None                    # MorphMeshes: rest vertices, rest normals, and the pair a morph ahead of a skin writes into (ComputeBuffers of the vertex count)
         self._morphWeightBuffers = {}                # MorphMeshes: MeshObject index -> its weight table (ComputeBuffer)
+        self._leafBuffers = [None, None]             # device_object_heaps: the mesh and the sphere leaf records (ComputeBuffers of the object counts)
+        self._heapsBehind = [False, False]           # device_object_heaps: scene.mesh_bvh / scene.sphere_bvh are behind the heap buffers' device side
         self._normalsPlans = {}                      # RecomputeNormals: MeshObject index -> ((vertex buffer, index buffer, first, last), NormalsPlan, the index list it was made for)
 
     # RM:215-230
@@ -142,6 +153,7 @@ class RayTraceMaster:
             if len(s.mesh_objects) else np.zeros(0, scenes.BVHNODE_DT)
         s.sphere_bvh = host_scene.build_object_bvh(host_scene.sphere_leaf_bounds(s.spheres, literal_leaf_bounds), pairing_heap) \
             if len(s.spheres) else np.zeros(0, scenes.BVHNODE_DT)
+        self._heapsBehind = [False, False]                                        # the lists are the newest heaps again
         if getattr(self, "rayDebug", None) is not None:                             # RM:331-335
             self.rayDebug.LogSceneCounts(len(s.spheres), len(s.mesh_objects), len(s.vertices), len(s.indices), len(s.normals))
 
@@ -170,6 +182,8 @@ class RayTraceMaster:
 
     def RebuildTrees(self):
         s = self.scene
+        if self.device_object_heaps:                                              # never upload a host heap that is behind the device's
+            self.SyncObjectHeaps()
         if self.rayDebug is not None:                                             # RM:731-735
             self.rayDebug.LogTreeReport(len(s.mesh_objects), self.tree_depth(len(s.mesh_objects)), len(s.mesh_bvh),
                                         len(s.spheres), self.tree_depth(len(s.spheres)), len(s.sphere_bvh))
@@ -960,14 +974,20 @@ class RayTraceMaster:
         deform()
         if recompute_normals:
             self.RecomputeNormals(list(spans))
-        for k, (lo, hi) in spans.items():
+        if spans and self._can_build_heaps_on_device(0):
+            self._build_heap_on_device(0)
+            spans_to_bound = {}
+        else:
+            spans_to_bound = spans
+        for k, (lo, hi) in spans_to_bound.items():
             if hi < lo:
                 continue
             lo3, hi3, n = self.ctx.buffer_bounds(self._vertexBuffer, lo, hi - lo + 1)
             self._skinBoxes[k] = (lo3, hi3) if n > 0 else None
-        if spans:
+        if spans_to_bound:
             s.mesh_bvh = self._object_heap_with_skins()
             self._meshObjectBVHBuffer = self.CreateComputeBuffer(self._meshObjectBVHBuffer, s.mesh_bvh, self.BVHNodeSize)
+            self._heapsBehind[0] = False
         if not history:
             self.ResetAccumulation()
             return
@@ -1124,14 +1144,75 @@ class RayTraceMaster:
                 meshes[k].localToWorldMatrix = np.array(new_mo[k]["localToWorldMatrix"], np.float32)
             for k in sphere_edits:
                 spheres[k].position, spheres[k].radius = tuple(float(v) for v in new_sp[k]["position"]), float(new_sp[k]["radius"])
+        on_device = [bool(e) and not self._treesNeedRebuilding and self._can_build_heaps_on_device(k)
+                     for k, e in enumerate((mesh_edits, sphere_edits))]
+        if any(on_device):
+            # the edited lists go up by SetData as always; the heaps of the edited kinds are built where the buffers live.  (RebuildTrees
+            # would read the heaps back first.)  An edited kind whose heap the device cannot build takes the host path, as without the flag.
+            if mesh_edits and not on_device[0]:
+                s.mesh_bvh = host_scene.build_object_bvh(host_scene.mesh_leaf_bounds(new_mo, s.vertices, s.indices)) if self._rayTraceObjects \
+                    else scenes.build_object_bvh(*scenes.mesh_bounds(new_mo, s.vertices, s.indices))
+                self._meshObjectBVHBuffer = self.CreateComputeBuffer(self._meshObjectBVHBuffer, s.mesh_bvh, self.BVHNodeSize)
+                self._heapsBehind[0] = False
+            if sphere_edits and not on_device[1]:
+                s.sphere_bvh = host_scene.build_object_bvh(host_scene.sphere_leaf_bounds(new_sp)) if self._rayTraceObjects \
+                    else scenes.build_object_bvh(*scenes.sphere_bounds(new_sp))
+                self._sphereBVHBuffer = self.CreateComputeBuffer(self._sphereBVHBuffer, s.sphere_bvh, self.BVHNodeSize)
+                self._heapsBehind[1] = False
+            self._meshObjectBuffer = self.CreateComputeBuffer(self._meshObjectBuffer, s.mesh_objects, self.MeshObjectStructSize)
+            self._sphereBuffer = self.CreateComputeBuffer(self._sphereBuffer, s.spheres, self.SphereStructSize)
+            for k in (0, 1):
+                if on_device[k]:
+                    self._build_heap_on_device(k)
+            return
         if mesh_edits:
             s.mesh_bvh = host_scene.build_object_bvh(host_scene.mesh_leaf_bounds(new_mo, s.vertices, s.indices)) if self._rayTraceObjects \
                 else scenes.build_object_bvh(*scenes.mesh_bounds(new_mo, s.vertices, s.indices))
         if sphere_edits:
             s.sphere_bvh = host_scene.build_object_bvh(host_scene.sphere_leaf_bounds(new_sp)) if self._rayTraceObjects \
                 else scenes.build_object_bvh(*scenes.sphere_bounds(new_sp))
+        self._heapsBehind = [b and not e for b, e in zip(self._heapsBehind, (mesh_edits, sphere_edits))]   # the recomputed lists are the newest
         if not self._treesNeedRebuilding:                                          # else the next frame uploads everything anyway
             self.RebuildTrees()
+
+    # ---- device_object_heaps: the object-level heaps built where the buffers live (kind 0 = meshes, 1 = spheres) ----
+    def _can_build_heaps_on_device(self, kind: int) -> bool:
+        """The flag is set and the buffers the device builder reads and writes exist (RebuildTrees has made them)."""
+        if not self.device_object_heaps:
+            return False
+        if kind == 0:
+            need = (self._meshObjectBuffer, self._vertexBuffer, self._indexBuffer, self._meshObjectBVHBuffer)
+        else:
+            need = (self._sphereBuffer, self._sphereBVHBuffer)
+        return all(b is not None for b in need)
+
+    def _build_heap_on_device(self, kind: int):
+        """Leaf boxes, then the heap into the bound heap buffer's device side: three (spheres: two) kernels on the context's stream, nothing
+        waited for.  The library takes the heap at the next preparation, through the download every device-written small table gets."""
+        objects, heap = (self._meshObjectBuffer, self._meshObjectBVHBuffer) if kind == 0 else (self._sphereBuffer, self._sphereBVHBuffer)
+        leaves = self._leafBuffers[kind]
+        if leaves is not None and leaves.count != objects.count:
+            leaves.Release()
+            leaves = None
+        if leaves is None:
+            leaves = self._leafBuffers[kind] = ComputeBuffer(self.ctx, objects.count, self.BVHNodeSize)
+        if kind == 0:
+            self.ctx.mesh_leaf_bounds(objects, self._vertexBuffer, self._indexBuffer, leaves)
+        else:
+            self.ctx.sphere_leaf_bounds(objects, leaves)
+        self.ctx.build_object_bvh(leaves, heap)
+        self._heapsBehind[kind] = True
+
+    def SyncObjectHeaps(self, meshes: bool = True, spheres: bool = True):
+        """scene.mesh_bvh / scene.sphere_bvh as the heap buffers hold them now: reads back the heaps that device_object_heaps built on the
+        GPU (ComputeBuffer.GetData: a synchronising download).  Nothing to do for a heap the host built."""
+        s = self.scene
+        if meshes and self._heapsBehind[0] and self._meshObjectBVHBuffer is not None:
+            s.mesh_bvh = self._meshObjectBVHBuffer.GetData().reshape(-1).view(scenes.BVHNODE_DT).copy()
+            self._heapsBehind[0] = False
+        if spheres and self._heapsBehind[1] and self._sphereBVHBuffer is not None:
+            s.sphere_bvh = self._sphereBVHBuffer.GetData().reshape(-1).view(scenes.BVHNODE_DT).copy()
+            self._heapsBehind[1] = False
 
     # RM:761-763: F12 -> ScreenCapture.CaptureScreenshot("Screenshots/" + Time.time + "-" + _currentSample + ".png")
     def CaptureScreenshot(self, directory: str, time_seconds: float) -> str:
@@ -1178,11 +1259,15 @@ class RayTraceMaster:
 
     # RM:188-212
     def OnDisable(self):
+        if self.device_object_heaps:                                              # the scene's lists outlive the buffers
+            self.SyncObjectHeaps()
         for b in (self._sphereBuffer, self._meshObjectBuffer, self._vertexBuffer, self._indexBuffer, self._normalBuffer,
-                  self._sphereBVHBuffer, self._meshObjectBVHBuffer) + tuple(self._skinBuffers or ()) + tuple(self._boneBuffers.values()):
+                  self._sphereBVHBuffer, self._meshObjectBVHBuffer) + tuple(self._skinBuffers or ()) + tuple(self._boneBuffers.values()) \
+                + tuple(self._leafBuffers):
             if b is not None:
                 b.Release()
         self._skinBuffers, self._boneBuffers = None, {}
+        self._leafBuffers, self._heapsBehind = [None, None], [False, False]
         self._drop_morphs()
         self._drop_normals_plans()
         for t in (self._target, self._converged, self.SkyboxTexture, self._denoised, self._tonemapped) + (self._aov or ()):

@@ -128,6 +128,35 @@ class Context:
         self.check(self.lib.urt_buffer_bounds(self._h, buffer.handle, int(first), int(count), out.ctypes.data_as(C.c_void_p), C.byref(n)))
         return out[:3].copy(), out[3:].copy(), n.value
 
+    def _buffer_handles(self, who: str, **buffers):
+        out = []
+        for name, b in buffers.items():
+            if not isinstance(b, ComputeBuffer):
+                raise TypeError(f"{who}: {name} must be a ComputeBuffer, not {type(b).__name__}")
+            if b.ctx is not self:
+                raise ValueError(f"{who}: {name} belongs to another context")
+            out.append(b.handle)
+        return out
+
+    def mesh_leaf_bounds(self, mesh_objects, vertices, indices, dst_leaves):
+        """The world-space leaf box of every MeshObject, computed on the GPU from the current device contents of `vertices` into the
+        device side of dst_leaves (stride 28, the count of mesh_objects) — include/urt.h urt_mesh_leaf_bounds_device: what
+        host_scene.mesh_leaf_bounds computes, by value.  Enqueued on the context's stream; nothing is waited for."""
+        h = self._buffer_handles("mesh_leaf_bounds", mesh_objects=mesh_objects, vertices=vertices, indices=indices, dst_leaves=dst_leaves)
+        self.check(self.lib.urt_mesh_leaf_bounds_device(self._h, *h))
+
+    def sphere_leaf_bounds(self, spheres, dst_leaves):
+        """The leaf box of every sphere into the device side of dst_leaves (include/urt.h urt_sphere_leaf_bounds_device)."""
+        h = self._buffer_handles("sphere_leaf_bounds", spheres=spheres, dst_leaves=dst_leaves)
+        self.check(self.lib.urt_sphere_leaf_bounds_device(self._h, *h))
+
+    def build_object_bvh(self, leaves, dst_nodes):
+        """The implicit heap of host_scene.build_object_bvh over the device contents of `leaves` (at most _lib.OBJECT_BVH_DEVICE_MAX),
+        into the device side of dst_nodes, whose count is host_scene.object_bvh_length(leaves.count) — include/urt.h
+        urt_build_object_bvh_device.  Enqueued on the context's stream; nothing is waited for."""
+        h = self._buffer_handles("build_object_bvh", leaves=leaves, dst_nodes=dst_nodes)
+        self.check(self.lib.urt_build_object_bvh_device(self._h, *h))
+
     def buffer_state(self, buffer) -> dict:
         """Where a ComputeBuffer's contents live (include/urt.h urt_debug_buffer_state): the element range in which the device mirror is
         newer than the host copy (stale_first > stale_last: none), the mirror's bytes (0: no mirror), and the synchronising downloads of
