@@ -56,9 +56,10 @@ URT_API int urt_abi_version(void);                       /* bumps when this head
                                                             urt_buffer_set_data_device, urt_buffer_get_data_range,
                                                             urt_skin_vertices, urt_buffer_bounds, urt_debug_buffer_state — the
                                                             normals on the device, urt_buffer_copy, urt_reproject_deformed,
-                                                            urt_upsample, urt_auto_exposure, urt_tonemap, urt_bloom and the blend
-                                                            shapes on the device — urt_morph_plan_create, urt_morph_plan_info,
-                                                            urt_morph_plan_release, urt_morph_vertices, urt_debug_build_morph_plan —
+                                                            urt_upsample, urt_auto_exposure, urt_tonemap, urt_bloom,
+                                                            urt_depth_of_field and the blend shapes on the device —
+                                                            urt_morph_plan_create, urt_morph_plan_info, urt_morph_plan_release,
+                                                            urt_morph_vertices, urt_debug_build_morph_plan —
                                                             and the object-level BVH on the device —
                                                             urt_mesh_leaf_bounds_device, urt_sphere_leaf_bounds_device,
                                                             urt_build_object_bvh_device — were added without changing anything
@@ -905,6 +906,65 @@ typedef struct urt_TonemapParams {       /* 16 bytes */
 
 URT_API int urt_auto_exposure(urt_context* ctx, urt_handle src, urt_handle count, const urt_ExposureParams* params, void* d_state);
 URT_API int urt_tonemap(urt_context* ctx, urt_handle src, urt_handle dst, const urt_TonemapParams* params, const void* d_state);
+
+/* ---- depth of field ----------------------------------------------------------------------- */
+/* The camera of the trace kernels is a pinhole: everything is sharp.  urt_depth_of_field blurs a converged image by the circle of
+ * confusion of a thin lens, in image space, from the depth urt_render_aov already provides: the `hit` target carries the camera ray's
+ * hit distance in .w, +inf for the sky.  It costs nothing when it is not called, and a host pulls focus on a converged image without
+ * tracing a ray.  A host orders the calls urt_auto_exposure, urt_depth_of_field, urt_bloom, urt_tonemap, formatted readback.  The result
+ * is an ordinary RGBA32F texture.  No new formats, no new options.
+ *
+ * urt_depth_of_field(ctx, src, hit, dst, params): src, hit and dst RGBA32F textures of one size W x H, row 0 at the bottom; of hit only
+ * .w is read.  dst is neither src nor hit: the gather reads neighbours, there is no in-place form.
+ *
+ * Arithmetic (normative): float32 with one rounding per operation, no fma, expressions evaluated as written; division is IEEE; f_sqrt
+ * of urt_math.h is the correctly rounded square root; fminf / fmaxf are C's (of a NaN and a number, the number); there are no other
+ * transcendentals.  With s = focus_distance, K = scale, Rmax = max_radius:
+ *  1. Class of the pixel p.  z_p = hit[p].w, c_p = src[p].rgb.  p PASSES THROUGH when z_p is NaN or not > 0, or when a component of c_p
+ *     is not finite or exceeds 2^100 in magnitude: dst[p] = src[p] bit for bit, and p is never a tap of another pixel.  Every other
+ *     pixel is a LENS pixel; a distance of +inf (the sky) is one.  (2^100: a weight is at most 4 and a pixel has at most 1089 taps, so
+ *     no sum below reaches FLT_MAX.)
+ *  2. Blur radius, in pixels: a_p = fmaxf(fminf(fabsf(K * (1.0f - s / z_p)), Rmax), 0.5f).  A point in focus covers its own pixel,
+ *     a = 0.5; for z = +inf, s / z = 0 and a = min(K, Rmax), clamped below by 0.5.  (Where s / z_p overflows and K is 0 the product is
+ *     NaN and fminf returns Rmax: a distance below s / FLT_MAX is as far out of focus as a pixel gets.)
+ *  3. Gather.  The taps of p are the lens pixels q = p + (dx, dy) inside the image, |dx| and |dy| <= 16, taken with dy ascending in the
+ *     outer loop and dx ascending in the inner one.  For a tap
+ *       d   = f_sqrt((float)(dx*dx + dy*dy))
+ *       ae  = (z_q > z_p) ? fminf(a_q, a_p) : a_q
+ *       cov = fminf(fmaxf((ae - d) + 0.5f, 0.0f), 1.0f)
+ *       w   = cov / (ae * ae)
+ *     (a point behind p never spreads onto p wider than p's own blur, so a sharp foreground stays sharp over a defocused background;
+ *     near blur still bleeds over what lies behind it).  A tap whose cov is not > 0 is SKIPPED — it is not added as zero.  Over the
+ *     remaining taps, in that order, from +0.0f: S = S + w and A.c = A.c + w * c_q.c per colour channel.  The own tap has cov = 1, so
+ *     S > 0.
+ *  4. Output: dst[p].c = A.c / S per colour channel; with URT_DOF_FLAG_COC dst[p].rgb = (a_p, a_p, a_p) instead, (0, 0, 0) at a
+ *     pass-through pixel.  Alpha is src[p].a, bit for bit, in both cases.  One pixel's sum is never split or tree-reduced: the order is
+ *     the specification.
+ * How far an implementation looks.  A skipped tap contributes nothing at all, so the result does not depend on the taps visited as long
+ * as every tap with cov > 0 is among them.  Rounding is monotonic, so d >= ae + 0.5 implies that cov is not > 0; ae <= a_q <= 16, so no
+ * tap with |dx| or |dy| above 16 can count, and a tap q can count only for |dx|, |dy| <= d < a_q + 0.5.  An implementation may therefore
+ * bound its loops by the largest a of the region the taps come from; the kernels do so per 16 x 16 tile (csrc/dof.hip).
+ * Calls, as urt_bloom: an observer — it submits the deferred frames first, then enqueues on the context's stream and returns without
+ * synchronising; dst counts as written by others.  The scene is not read (not prepared); urt_counters are not changed.  The
+ * intermediates live in grow-only scratch of the context.  params == NULL means the defaults below.  Every argument is checked before
+ * anything is enqueued or allocated for the call: on any error nothing is written.
+ *  - URT_ERR_INVALID_ARGUMENT: ctx NULL; focus_distance not finite or <= 0; scale not finite or < 0; max_radius not in [0.5, 16] (NaN
+ *    fails the test); unknown flag bits; textures of different sizes; dst == src or dst == hit; dst bound as _SkyboxTexture; textures
+ *    taller than 1048560 pixels.
+ *  - URT_ERR_INVALID_HANDLE: src, hit or dst 0 or unknown. */
+#define URT_DOF_FLAG_COC 1              /* dst.rgb receives the pixel's blur radius a_p (pass-through pixels: 0, 0, 0) instead of the image */
+#define URT_DOF_MAX_RADIUS 16.0f
+typedef struct urt_DofParams {          /* 16 bytes */
+  float focus_distance;   /* finite, > 0: the hit distance that is sharp, in scene units */
+  float scale;            /* finite, >= 0: the blur radius in pixels of a point at infinity (K above) */
+  float max_radius;       /* 0.5 .. URT_DOF_MAX_RADIUS: no pixel blurs wider than this */
+  int32_t flags;          /* URT_DOF_FLAG_* */
+} urt_DofParams;
+#define URT_DOF_DEFAULT_FOCUS_DISTANCE 10.0f
+#define URT_DOF_DEFAULT_SCALE 8.0f
+#define URT_DOF_DEFAULT_MAX_RADIUS 8.0f
+#define URT_DOF_DEFAULT_FLAGS 0
+URT_API int urt_depth_of_field(urt_context* ctx, urt_handle src, urt_handle hit, urt_handle dst, const urt_DofParams* params);
 
 /* ---- bloom -------------------------------------------------------------------------------- */
 /* The step between the exposure and the tone mapping: an emitter or the sun of an HDR sky lies many stops above white, and after

@@ -241,6 +241,20 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_auto_exposure(IntPtr ctx, ulong src, ulong count, in ExposureParams p, IntPtr dState);
     [DllImport(Lib)] internal static extern int urt_tonemap(IntPtr ctx, ulong src, ulong dst, in TonemapParams p, IntPtr dState);
 
+    // ---- depth of field (include/urt.h "depth of field"): between the metering and the bloom, reads the hit target of urt_render_aov ----
+    internal const int DofFlagCoc = 1;
+    internal const float DofMaxRadius = 16.0f;
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct DofParams {                             // urt_DofParams, 16 B
+        public float focusDistance;                         // finite, > 0: the hit distance that is sharp
+        public float scale;                                 // finite, >= 0: the blur radius in pixels of a point at infinity
+        public float maxRadius;                             // 0.5 .. DofMaxRadius
+        public int flags;                                   // DofFlag*
+    }
+    internal const float DofDefaultFocusDistance = 10.0f, DofDefaultScale = 8.0f, DofDefaultMaxRadius = 8.0f;
+    internal const int DofDefaultFlags = 0;
+    [DllImport(Lib)] internal static extern int urt_depth_of_field(IntPtr ctx, ulong src, ulong hit, ulong dst, in DofParams p);
+
     // ---- bloom (include/urt.h "bloom"): between the metering and the tone mapping, reads the same exposure state ----
     internal const int BloomFlagOnly = 1;
     [StructLayout(LayoutKind.Sequential)]

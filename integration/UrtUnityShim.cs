@@ -482,6 +482,43 @@ public static class UrtBloom {
     }
 }
 
+/// Depth of field (include/urt.h urt_depth_of_field) over device images the engine owns, all ARGBFloat of one size: Apply writes `src`
+/// blurred by a thin lens' circle of confusion into `dst` (neither src nor hit).  `hit` is the hit target of urt_render_aov for the
+/// same camera: its .w is the distance, +inf for the sky.  Per presented frame: UrtToneMapper.Meter(src), UrtDepthOfField.Apply(src, hit,
+/// dst), UrtBloom.Apply(dst, dst), UrtToneMapper.ToneMap(dst, dst), then the RGBA8 sRGB readback of dst.  Scale gives `scale` for a
+/// physical camera.  Defaults: include/urt.h URT_DOF_DEFAULT_*.
+public static class UrtDepthOfField {
+    static IntPtr boundCtx = IntPtr.Zero;
+    static readonly Dictionary<IntPtr, ulong> wrapped = new Dictionary<IntPtr, ulong>();
+    static int w, h;
+    static ulong Wrap(IntPtr ctx, IntPtr p, int width, int height) {  // external textures, re-wrapped when the context or the size changes
+        if (boundCtx != ctx || w != width || h != height) {
+            if (boundCtx == ctx) foreach (ulong t in wrapped.Values) UrtDevice.Check(UrtNative.urt_texture_release(ctx, t));
+            wrapped.Clear();
+            boundCtx = ctx; w = width; h = height;
+        }
+        if (!wrapped.TryGetValue(p, out ulong handle)) {
+            UrtDevice.Check(UrtNative.urt_texture_create_external(ctx, width, height, p, out handle));
+            wrapped[p] = handle;
+        }
+        return handle;
+    }
+    /// The blur radius in pixels of a point at infinity: 0.5 * height * f^2 / (N * (s - f) * sensorHeight), lengths in scene units.
+    public static float Scale(int height, float focusDistance, float fNumber = 5.6f, float focalLength = 0.05f, float sensorHeight = 0.024f) {
+        if (!(focusDistance > focalLength)) throw new ArgumentException("UrtDepthOfField: the focus distance must lie beyond the focal length");
+        return (float)(0.5 * height * (double)focalLength * focalLength / ((double)fNumber * ((double)focusDistance - focalLength) * sensorHeight));
+    }
+    public static void Apply(IntPtr src, IntPtr hit, IntPtr dst, int width, int height,
+                             float focusDistance = 10.0f, float scale = 8.0f, float maxRadius = 8.0f, bool showCoc = false) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtDepthOfField: depth of field on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        var p = new UrtNative.DofParams { focusDistance = focusDistance, scale = scale, maxRadius = maxRadius,
+                                          flags = showCoc ? UrtNative.DofFlagCoc : 0 };
+        UrtDevice.Check(UrtNative.urt_depth_of_field(ctx, Wrap(ctx, src, width, height), Wrap(ctx, hit, width, height),
+                                                     Wrap(ctx, dst, width, height), in p));
+    }
+}
+
 /// new ComputeBuffer(count, stride); .SetData(List<T>); .Release(); .count; .stride            (RM:233-252)
 public sealed class UrtComputeBuffer {
     internal ulong handle;

@@ -1,6 +1,6 @@
 // image_ops.cpp — the entry points of include/urt.h that work on whole images or ray batches next to the frame loop: ray queries,
-// radiance queries, feature buffers, the denoiser, temporal reprojection, guide-driven upsampling, auto-exposure and tone mapping, bloom,
-// resampling.
+// radiance queries, feature buffers, the denoiser, temporal reprojection, guide-driven upsampling, auto-exposure and tone mapping, depth of field,
+// bloom, resampling.
 #include "experiments.h"
 #include "context_impl.h"
 
@@ -12,6 +12,7 @@
 #include "resample.h"
 #include "upsample.h"
 #include "tonemap.h"
+#include "dof.h"
 #include "bloom.h"
 
 using namespace urtd;
@@ -529,6 +530,39 @@ int urt_tonemap(urt_context* ctx, urt_handle src, urt_handle dst, const urt_Tone
   const TonemapSettings S{P.exposure, P.white, P.op};
   t[1]->other_writes = true;
   URT_HIP(ctx, launch_tonemap(t[0]->dev, t[1]->dev, (size_t)t[0]->w * (size_t)t[0]->h, S, (const ExposureState*)d_state, touch(ctx)));
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+/* ---- depth of field ---- */
+// As urt_bloom: every argument is checked before anything is allocated or submitted, then the scratch is grown, the deferred frames are
+// submitted and the kernels of csrc/dof.hip are enqueued on the main stream.  The scene is not read and the counters are not changed.
+int urt_depth_of_field(urt_context* ctx, urt_handle src, urt_handle hit, urt_handle dst, const urt_DofParams* params) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  urt_DofParams P{URT_DOF_DEFAULT_FOCUS_DISTANCE, URT_DOF_DEFAULT_SCALE, URT_DOF_DEFAULT_MAX_RADIUS, URT_DOF_DEFAULT_FLAGS};
+  if (params) P = *params;
+  if (!std::isfinite(P.focus_distance) || !(P.focus_distance > 0.0f))
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "depth_of_field: focus_distance must be finite and > 0");
+  if (!std::isfinite(P.scale) || !(P.scale >= 0.0f)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "depth_of_field: scale must be finite and >= 0");
+  if (!(P.max_radius >= 0.5f && P.max_radius <= URT_DOF_MAX_RADIUS))
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "depth_of_field: max_radius must lie in [0.5, 16]");
+  if (P.flags & ~URT_DOF_FLAG_COC) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "depth_of_field: unknown flag bits");
+  const TexArg a[3] = {{src, "src", false}, {hit, "hit", false}, {dst, "dst", false}};
+  Texture* t[3];
+  if (int rc = resolve_textures(ctx, "depth_of_field", a, 3, t)) return rc;
+  if (int rc = check_same_size(ctx, "depth_of_field", t, 3)) return rc;
+  if (int rc = check_outputs(ctx, "depth_of_field", a, 2, 3)) return rc;      // dst is neither src nor hit (no in-place form) nor the sky
+  const int width = t[0]->w, height = t[0]->h;
+  if (int rc = check_height(ctx, "depth_of_field", "textures", height)) return rc;
+  if (width > kDofMaxExtent) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "depth_of_field: textures wider than 2^30 pixels");
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = reserve(ctx, ctx->df_scratch, dof_scratch_floats(width, height), "depth_of_field: scratch allocation", ctx->stream)) return rc;
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  const DofSettings S{P.focus_distance, P.scale, P.max_radius, P.flags};
+  t[2]->other_writes = true;
+  URT_HIP(ctx, launch_depth_of_field(t[0]->dev, t[1]->dev, t[2]->dev, width, height, S, ctx->df_scratch.get(), touch(ctx)));
+                                                                   // (device pointers after the flush: a Result texture may be renamed)
   return URT_OK;
   URT_GUARD_END(ctx)
 }

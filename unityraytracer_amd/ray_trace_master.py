@@ -52,6 +52,7 @@ class RayTraceMaster:
     _uplow = _upaov = _upcount = _upscaled = _uptarget = None   # (likewise: Upscale's textures)
     _exposure = _exposureState = _tonemapped = None             # (likewise: auto-exposure and ToneMap)
     _bloom = None                                               # (likewise: EnableBloom)
+    _dof = _dofHit = None                                       # (likewise: EnableDepthOfField)
     # With True, SkinMeshes, MorphMeshes and MoveObjects build the object-level heaps on the GPU (include/urt.h "the object-level BVH on the
     # device": urt_mesh_leaf_bounds_device / urt_sphere_leaf_bounds_device, then urt_build_object_bvh_device into the heap buffers) instead
     # of on the host, and make no synchronising call of their own.  scene.mesh_bvh / scene.sphere_bvh are then BEHIND the device, as
@@ -92,6 +93,8 @@ class RayTraceMaster:
         self._exposureState = None                   # EnableAutoExposure: the urt_ExposureState, a torch tensor on the context's device
         self._tonemapped = None                      # ToneMap without a destination: the tone-mapped image
         self._bloom = None                           # EnableBloom: the urt_BloomParams fields given (None = off)
+        self._dof = None                             # EnableDepthOfField: the urt_DofParams fields given (None = off)
+        self._dofHit = None                          # ToneMap with depth of field on: the hit guide of _converged's size
         self._temporal = None                        # EnableTemporalAccumulation: the reprojection settings (None = off, the reference's behaviour)
         self._tcount = self._tspare = None           # temporal: the count texture of _converged; the spare (colour, count) pair reprojection writes
         self._taov = None                            # temporal: two (hit, normal, id) sets, the previous and the new camera's
@@ -504,6 +507,25 @@ class RayTraceMaster:
     def DisableBloom(self):
         self._bloom = None
 
+    # Depth of field (include/urt.h urt_depth_of_field), opt-in as well: with it on, ToneMap renders the hit guide of the bound camera
+    # into a texture of _converged's size this master owns — through the centres of the frames' samples, as Upscale's guides
+    # (_sample_centre_projection), the host's _CameraInverseProjection bound again afterwards — puts the blurred _converged into its
+    # destination, and bloom (if enabled) and the tone mapping follow in place.  With it off ToneMap enqueues what it always did.
+    # params: the fields of urt_DofParams; unity_api.dof_scale gives `scale` for a physical camera.  Focus and aperture change between
+    # two ToneMap calls without a ray being traced: _converged is never modified.  Nothing is created here.
+    def EnableDepthOfField(self, **params):
+        from .unity_api import dof_params
+        dof_params(**params)                                                      # checked at once
+        self._dof = dict(params)
+
+    def DisableDepthOfField(self):
+        self._dof = None
+
+    def _release_dof(self):
+        if self._dofHit is not None:
+            self._dofHit.Release()
+        self._dofHit = None
+
     def ToneMap(self, destination: RenderTexture | None = None, operator="aces", exposure: float = 1.0, white: float = 4.0):
         from ._lib import UrtError
         from .unity_api import tonemap_params
@@ -531,8 +553,21 @@ class RayTraceMaster:
             self.ctx.auto_exposure(self._converged, self._exposureState, count, **self._exposure)
         state = self._exposureState if self._exposure is not None else None
         source = self._converged
+        if self._dof is not None:
+            width, height = self._converged.width, self._converged.height
+            self._bind_for_queries()
+            if self._dofHit is None or (self._dofHit.width, self._dofHit.height) != (width, height):
+                self._release_dof()
+                self._dofHit = RenderTexture(self.ctx, width, height)
+            try:                                                                  # the guide looks where the frames' samples are centred
+                self.RayTraceShader.SetMatrix("_CameraInverseProjection", self._sample_centre_projection(width, height))
+                self.ctx.render_aov(hit=self._dofHit)
+            finally:
+                self.RayTraceShader.SetMatrix("_CameraInverseProjection", self.scene.camera_inverse_projection)
+            self.ctx.depth_of_field(self._converged, self._dofHit, destination, **self._dof)
+            source = destination
         if self._bloom is not None:
-            self.ctx.bloom(self._converged, destination, state, **self._bloom)
+            self.ctx.bloom(source, destination, state, **self._bloom)
             source = destination
         self.ctx.tonemap(source, destination, state, **params)
         return destination
@@ -1277,6 +1312,7 @@ class RayTraceMaster:
         self._aov = None
         self._release_upscale()
         self._release_temporal()
+        self._release_dof()
 
     # ---- multi-GPU frame-end gather (no counterpart in the reference: it is single-GPU) -----------
     def gather_converged(self, dist, device):

@@ -671,6 +671,20 @@ class Context:
             _sync_torch_stream(state)
         self.check(self.lib.urt_tonemap(self._h, src.handle, dst.handle, C.byref(p), C.c_void_p(ptr)))
 
+    def depth_of_field(self, src, hit, dst, **params):
+        """dst = src blurred by a thin lens' circle of confusion, alpha copied (include/urt.h urt_depth_of_field).  hit: the hit target of
+        render_aov for the same camera (its .w is the distance, +inf for the sky).  A pixel at `focus_distance` is sharp, a point at
+        infinity blurs over `scale` pixels (dof_scale derives it from a physical camera), nothing blurs wider than `max_radius` (at most
+        _lib.URT_DOF_MAX_RADIUS).  dst is neither src nor hit.  params: the fields of urt_DofParams (_lib.DOF_DEFAULTS); flags
+        _lib.URT_DOF_FLAG_COC writes each pixel's blur radius instead of the image.  Enqueued after the deferred frames, ahead of bloom."""
+        _check_texture(self, "depth_of_field", "src", src, src)
+        _check_texture(self, "depth_of_field", "hit", hit, src)
+        _check_texture(self, "depth_of_field", "dst", dst, src)
+        if dst is src or dst is hit or dst.handle in (src.handle, hit.handle):
+            raise ValueError("depth_of_field: dst is also an input (there is no in-place form)")
+        p = dof_params(**params)
+        self.check(self.lib.urt_depth_of_field(self._h, src.handle, hit.handle, dst.handle, C.byref(p)))
+
     def bloom(self, src, dst, state=None, **params):
         """dst = src + intensity * bloom(src) per colour channel, alpha copied (include/urt.h urt_bloom); dst may be src.  The bloom is
         what lies above `threshold` (soft below it over `soft_knee`, held to `clamp`), taken down a pyramid of at most `levels` halved
@@ -977,6 +991,48 @@ def bloom_params(**params) -> _lib.BloomParams:
     if flags & ~_lib.URT_BLOOM_FLAG_ONLY:
         raise ValueError(f"bloom: unknown flag bits in {flags}")
     return _lib.BloomParams(v["threshold"], v["soft_knee"], v["clamp"], v["scatter"], v["intensity"], levels, flags)
+
+
+def dof_params(**params) -> _lib.DofParams:
+    """The checked urt_DofParams of Context.depth_of_field: focus_distance finite and > 0, scale finite and >= 0, max_radius in
+    [0.5, 16], flags 0 or _lib.URT_DOF_FLAG_COC; what is not given is _lib.DOF_DEFAULTS'."""
+    unknown = set(params) - set(_lib.DOF_DEFAULTS)
+    if unknown:
+        raise TypeError(f"depth_of_field: unknown parameters {sorted(unknown)}")
+    v = {**_lib.DOF_DEFAULTS, **params}
+    for name in ("focus_distance", "scale", "max_radius"):
+        v[name] = _float32_arg(v[name], name, "depth_of_field")
+    if not (np.isfinite(v["focus_distance"]) and v["focus_distance"] > 0.0):
+        raise ValueError(f"depth_of_field: focus_distance must be finite and > 0, not {v['focus_distance']}")
+    if not (np.isfinite(v["scale"]) and v["scale"] >= 0.0):
+        raise ValueError(f"depth_of_field: scale must be finite and >= 0, not {v['scale']}")
+    if not 0.5 <= v["max_radius"] <= _lib.URT_DOF_MAX_RADIUS:
+        raise ValueError(f"depth_of_field: max_radius must lie in [0.5, 16], not {v['max_radius']}")
+    flags = _int_arg(v["flags"], "flags", "depth_of_field")
+    if flags & ~_lib.URT_DOF_FLAG_COC:
+        raise ValueError(f"depth_of_field: unknown flag bits in {flags}")
+    return _lib.DofParams(v["focus_distance"], v["scale"], v["max_radius"], flags)
+
+
+def dof_scale(height, focus_distance, f_number=5.6, focal_length=0.05, sensor_height=0.024) -> np.float32:
+    """urt_DofParams.scale of a physical camera: the thin-lens circle of confusion of a point at infinity as a RADIUS in pixels of an image
+    `height` pixels tall, K = 0.5 * height * f^2 / (N * (s - f) * sensor_height), with the lens focused at s = focus_distance, focal
+    length f and sensor height in the scene's units (the defaults: Unity's physical camera, 50 mm at f/5.6 on a 24 mm sensor, in metres).
+    Evaluated in double precision and rounded once.  s must lie beyond f."""
+    h = _int_arg(height, "height", "dof_scale")
+    if h <= 0:
+        raise ValueError(f"dof_scale: height must be positive, not {h}")
+    s, n, f, sh = (_number_arg(v, name, "dof_scale") for name, v in (("focus_distance", focus_distance), ("f_number", f_number),
+                                                                       ("focal_length", focal_length), ("sensor_height", sensor_height)))
+    for name, v in (("f_number", n), ("focal_length", f), ("sensor_height", sh)):
+        if not (np.isfinite(v) and v > 0.0):
+            raise ValueError(f"dof_scale: {name} must be finite and > 0, not {v}")
+    if not (np.isfinite(s) and s > f):
+        raise ValueError(f"dof_scale: focus_distance ({s}) must be finite and lie beyond the focal length ({f})")
+    k = np.float32(0.5 * h * f * f / (n * (s - f) * sh))
+    if not np.isfinite(k):
+        raise ValueError("dof_scale: the scale does not fit a float32")
+    return k
 
 
 def _sync_torch_stream(t):
