@@ -43,6 +43,14 @@ class RayTraceObject:
     localToWorldMatrix: np.ndarray = field(default_factory=lambda: scenes.trs())            # transform.localToWorldMatrix
 
 
+def _index_arg(k, n: int, who: str, what: str, names: str):
+    """k names one of the scene's n objects, or the error the edits raise: `what` is what must be ints, `names` how k is quoted."""
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"{who}: {what} must be ints, not {type(k).__name__}")
+    if not 0 <= k < n:
+        raise IndexError(f"{who}: {names} {k}, the scene has {n}")
+
+
 class RayTraceMaster:
     MeshObjectStructSize = 112   # RM:43
     SphereStructSize = 56        # RM:44
@@ -270,25 +278,24 @@ class RayTraceMaster:
 
     # RM:848-866
     def OnRenderImage(self, destination: RenderTexture | None = None):
+        if self._treesNeedRebuilding:                                             # (tested here too: a frame pays no call for it)
+            self._scene_ready()
+        self.SetShaderParameters()
+        self.Render(destination)
+
+    # RM:850-859: the scene buffers exist once this has run; a rebuild restarts the accumulation
+    def _scene_ready(self):
         if self._treesNeedRebuilding:
             self._currentSample = 0
             self._treesNeedRebuilding = False
             if self._rayTraceObjects:
                 self.RebuildObjectLists()
             self.RebuildTrees()
-        self.SetShaderParameters()
-        self.Render(destination)
 
     # The "Raycast" every engine binding offers (and the "test ray" of the reference's RayTraceDebug.cs:119-129): one closest-hit query
     # against the scene this master renders (include/urt.h urt_ray_query).  None for a miss, else the urt_RayHit fields as a dict.
     def Raycast(self, origin, direction, max_distance: float = math.inf):
-        if self._treesNeedRebuilding:                                             # the scene buffers exist once OnRenderImage has run once
-            self._currentSample = 0
-            self._treesNeedRebuilding = False
-            if self._rayTraceObjects:
-                self.RebuildObjectLists()
-            self.RebuildTrees()
-        self.SetShaderParameters()
+        self._bind_for_queries()
         o = np.asarray(origin, dtype=np.float32).reshape(1, 3)
         d = np.asarray(direction, dtype=np.float32).reshape(1, 3)
         h = self.ctx.ray_query(o, d, t_max=float(max_distance))[0]
@@ -297,12 +304,7 @@ class RayTraceMaster:
         return {k: (h[k].copy() if h[k].shape else h[k].item()) for k in h.dtype.names}
 
     def _bind_for_queries(self):
-        if self._treesNeedRebuilding:                                             # the scene buffers exist once OnRenderImage has run once
-            self._currentSample = 0
-            self._treesNeedRebuilding = False
-            if self._rayTraceObjects:
-                self.RebuildObjectLists()
-            self.RebuildTrees()
+        self._scene_ready()
         self.SetShaderParameters()
 
     # Path-traced radiance arriving along rays of the host's own — light probes, irradiance volumes, lightmap texels — with the scene
@@ -350,20 +352,39 @@ class RayTraceMaster:
     # the camera moves — when the accumulation resets too.  Returns the four RenderTextures (filled once the deferred work has run:
     # GetPixels waits for it).
     def RenderFeatureBuffers(self, frame_ray: bool = False):
-        if self._treesNeedRebuilding:
-            self._currentSample = 0
-            self._treesNeedRebuilding = False
-            if self._rayTraceObjects:
-                self.RebuildObjectLists()
-            self.RebuildTrees()
-        self.SetShaderParameters()
-        if self._aov is None or self._aov[0].width != self.screen_width or self._aov[0].height != self.screen_height:
-            if self._aov is not None:
-                for t in self._aov:
-                    t.Release()
-            self._aov = tuple(RenderTexture(self.ctx, self.screen_width, self.screen_height) for _ in range(4))
+        self._bind_for_queries()
+        self._aov = self._sized(self._aov, self.screen_width, self.screen_height, 4)
         self.ctx.render_aov(*self._aov, frame_ray=frame_ray)
         return self._aov
+
+    # A texture this master owns (or, with n, a tuple of n of one size) at width x height: the one given if it has that size, else it
+    # is released and a new one made — as InitRenderTexture re-creates the frame's with the screen (RM:834-840).
+    def _sized(self, owned, width: int, height: int, n: int | None = None):
+        held = () if owned is None else owned if n else (owned,)
+        if held and (held[0].width, held[0].height) == (width, height):
+            return owned
+        for t in held:
+            t.Release()
+        made = tuple(RenderTexture(self.ctx, width, height) for _ in range(n or 1))
+        return made if n else made[0]
+
+    # The destination argument of Denoise, Upscale and ToneMap: None, or a live RenderTexture of this master's context (the callers
+    # check its size)
+    def _destination_arg(self, destination, who: str):
+        if destination is not None and not isinstance(destination, RenderTexture):
+            raise TypeError(f"{who}: destination must be a RenderTexture or None, not {type(destination).__name__}")
+        if destination is not None and (destination.ctx is not self.ctx or not destination.handle):
+            raise ValueError(f"{who}: destination belongs to another context or was released")
+
+    # Feature buffers through the centres of the frames' samples (_sample_centre_projection below), for each (width, height, targets of
+    # render_aov) in turn; the host's _CameraInverseProjection is bound again afterwards, whatever happens.
+    def _render_through_sample_centres(self, *renders):
+        try:
+            for width, height, targets in renders:
+                self.RayTraceShader.SetMatrix("_CameraInverseProjection", self._sample_centre_projection(width, height))
+                self.ctx.render_aov(*targets)
+        finally:
+            self.RayTraceShader.SetMatrix("_CameraInverseProjection", self.scene.camera_inverse_projection)
 
     # The progressive image `_converged` (RM:12), denoised with this master's feature buffers as guides (include/urt.h urt_denoise):
     # hit, normal and albedo of RenderFeatureBuffers, rendered here when they do not exist yet or have another size (a host refreshes
@@ -373,19 +394,12 @@ class RayTraceMaster:
         from ._lib import UrtError
         if self._converged is None or not self._converged.handle:
             raise UrtError(2, "Denoise: no accumulated image yet (render a frame first)")
-        if destination is not None and not isinstance(destination, RenderTexture):
-            raise TypeError(f"Denoise: destination must be a RenderTexture or None, not {type(destination).__name__}")
-        if destination is not None and (destination.ctx is not self.ctx or not destination.handle):
-            raise ValueError("Denoise: destination belongs to another context or was released")
+        self._destination_arg(destination, "Denoise")
         denoise_params(**params)                                                  # checked before anything reaches the library
         if self._aov is None or self._aov[0].width != self._converged.width or self._aov[0].height != self._converged.height:
             self.RenderFeatureBuffers()
         if destination is None:
-            if self._denoised is None or self._denoised.width != self._converged.width or self._denoised.height != self._converged.height:
-                if self._denoised is not None:
-                    self._denoised.Release()
-                self._denoised = RenderTexture(self.ctx, self._converged.width, self._converged.height)
-            destination = self._denoised
+            destination = self._denoised = self._sized(self._denoised, self._converged.width, self._converged.height)
         hit, normal, albedo, _ = self._aov
         self.ctx.denoise(self._converged, destination, hit, normal, albedo, **params)
         return destination
@@ -413,10 +427,7 @@ class RayTraceMaster:
             if v <= 0:
                 raise ValueError(f"Upscale: {name} must be positive, not {v}")
         width, height = int(width), int(height)
-        if destination is not None and not isinstance(destination, RenderTexture):
-            raise TypeError(f"Upscale: destination must be a RenderTexture or None, not {type(destination).__name__}")
-        if destination is not None and (destination.ctx is not self.ctx or not destination.handle):
-            raise ValueError("Upscale: destination belongs to another context or was released")
+        self._destination_arg(destination, "Upscale")
         if destination is not None and (destination.width, destination.height) != (width, height):
             raise ValueError(f"Upscale: destination is {destination.width} x {destination.height}, not {width} x {height}")
         if not isinstance(fill_holes, (bool, np.bool_)):
@@ -437,13 +448,7 @@ class RayTraceMaster:
             self._upcount = RenderTexture(self.ctx, width, height)
         low_hit, low_normal, _, low_id = self._uplow
         hit, normal, albedo, ids = self._upaov
-        try:                                                                      # the guides look where the frames' samples are centred
-            self.RayTraceShader.SetMatrix("_CameraInverseProjection", self._sample_centre_projection(self.screen_width, self.screen_height))
-            self.ctx.render_aov(*self._uplow)
-            self.RayTraceShader.SetMatrix("_CameraInverseProjection", self._sample_centre_projection(width, height))
-            self.ctx.render_aov(hit, normal, albedo, ids)
-        finally:
-            self.RayTraceShader.SetMatrix("_CameraInverseProjection", self.scene.camera_inverse_projection)
+        self._render_through_sample_centres((self.screen_width, self.screen_height, self._uplow), (width, height, self._upaov))
         if destination is None:
             if self._upscaled is None:
                 self._upscaled = RenderTexture(self.ctx, width, height)
@@ -531,10 +536,7 @@ class RayTraceMaster:
         from .unity_api import tonemap_params
         if self._converged is None or not self._converged.handle:
             raise UrtError(2, "ToneMap: no accumulated image yet (render a frame first)")
-        if destination is not None and not isinstance(destination, RenderTexture):
-            raise TypeError(f"ToneMap: destination must be a RenderTexture or None, not {type(destination).__name__}")
-        if destination is not None and (destination.ctx is not self.ctx or not destination.handle):
-            raise ValueError("ToneMap: destination belongs to another context or was released")
+        self._destination_arg(destination, "ToneMap")
         if destination is self._converged:
             raise ValueError("ToneMap: destination is the accumulated image")
         if destination is not None and (destination.width, destination.height) != (self._converged.width, self._converged.height):
@@ -543,11 +545,7 @@ class RayTraceMaster:
         params = {"op": operator, "exposure": exposure, "white": white}
         tonemap_params(**params)                                                  # checked before anything reaches the library
         if destination is None:
-            if self._tonemapped is None or (self._tonemapped.width, self._tonemapped.height) != (self._converged.width, self._converged.height):
-                if self._tonemapped is not None:
-                    self._tonemapped.Release()
-                self._tonemapped = RenderTexture(self.ctx, self._converged.width, self._converged.height)
-            destination = self._tonemapped
+            destination = self._tonemapped = self._sized(self._tonemapped, self._converged.width, self._converged.height)
         if self._exposure is not None:
             count = self._tcount if self._temporal is not None else None
             self.ctx.auto_exposure(self._converged, self._exposureState, count, **self._exposure)
@@ -556,14 +554,8 @@ class RayTraceMaster:
         if self._dof is not None:
             width, height = self._converged.width, self._converged.height
             self._bind_for_queries()
-            if self._dofHit is None or (self._dofHit.width, self._dofHit.height) != (width, height):
-                self._release_dof()
-                self._dofHit = RenderTexture(self.ctx, width, height)
-            try:                                                                  # the guide looks where the frames' samples are centred
-                self.RayTraceShader.SetMatrix("_CameraInverseProjection", self._sample_centre_projection(width, height))
-                self.ctx.render_aov(hit=self._dofHit)
-            finally:
-                self.RayTraceShader.SetMatrix("_CameraInverseProjection", self.scene.camera_inverse_projection)
+            self._dofHit = self._sized(self._dofHit, width, height)
+            self._render_through_sample_centres((width, height, (self._dofHit,)))
             self.ctx.depth_of_field(self._converged, self._dofHit, destination, **self._dof)
             source = destination
         if self._bloom is not None:
@@ -647,6 +639,55 @@ class RayTraceMaster:
         self._taov = tuple(tuple(RenderTexture(self.ctx, w, h) for _ in range(3)) for _ in range(2))
         self._currentSample = 0                                               # a new count texture: the next frame zeroes it
 
+    # ---- the protocol every edit that keeps history follows (MoveCamera, MoveObjects, DeformMeshes, SkinMeshes / MorphMeshes) ----
+    # With _has_history(): _history_begin() renders the pixel-centre feature buffers of the scene and the camera as the history saw
+    # them; the caller applies its edit (lists, uploads, the new camera matrices); _history_finish() renders the feature buffers of
+    # what the next frame will see, uploads the motion tables of the edit, reprojects the accumulated image and its counts into the
+    # spare pair and swaps the pairs, so that the next frame blends into the reprojected one.  Without history the caller applies its
+    # edit and ends in ResetAccumulation().
+    def _has_history(self) -> bool:
+        return self._temporal is not None and self._converged is not None and self._currentSample > 0 and not self._treesNeedRebuilding \
+            and (self._converged.width, self._converged.height) == (self.screen_width, self.screen_height)
+
+    def _history_begin(self) -> np.ndarray:
+        """-> the world-to-clip matrix of the camera the history was accumulated under, for _history_finish."""
+        s = self.scene
+        self._ensure_temporal_textures()
+        prev_m = scenes.world_to_clip(s.camera_to_world, s.camera_inverse_projection)
+        hit, normal, ids = self._taov[0]
+        self.SetShaderParameters()
+        self.ctx.render_aov(hit, normal, None, ids)
+        return prev_m
+
+    def _history_finish(self, prev_m, motion: dict | None = None):
+        """motion: the keywords of _motion_arguments for an edit that moved or deformed objects.  None (a camera move) passes none of
+        Context.reproject's motion keywords, which makes the call urt_reproject rather than urt_reproject_objects."""
+        prev, cur = self._taov
+        self.SetShaderParameters()
+        self.ctx.render_aov(cur[0], cur[1], None, cur[2])
+        moved = {} if motion is None else self._motion_arguments(**motion)
+        color, count = self._tspare
+        self.ctx.reproject(self._converged, self._tcount, *prev, *cur, color, count, prev_m, **moved, **self._temporal)
+        self._tspare = (self._converged, self._tcount)
+        self._converged, self._tcount = color, count
+
+    def _motion_arguments(self, mesh=None, sphere=None, deformed=(), keep: bool = False) -> dict:
+        """Uploads the motion tables of an edit into _tmotion; -> the keywords of Context.reproject that name them.  mesh / sphere:
+        MoveObjects' "current world -> previous world" tables, None for a kind nothing of which moved (a table of no rows makes
+        CreateComputeBuffer release the buffer).  deformed: the meshes that changed shape and nothing else has moved — identity
+        entries, all-NaN ("no history") for the deformed ones unless `keep`, which hands them to the per-vertex path instead."""
+        s = self.scene
+        if deformed:
+            mesh = host_scene.mesh_motion(s.mesh_objects, s.mesh_objects)
+            if not keep:
+                mesh[list(deformed)] = np.nan
+        for k, table in enumerate((mesh, sphere)):
+            self._tmotion[k] = self.CreateComputeBuffer(self._tmotion[k], table if table is not None else np.zeros((0, 12), np.float32), 48)
+        moved = {"mesh_motion": self._tmotion[0], "sphere_motion": self._tmotion[1], "moved_max_history": self._moved_max_history}
+        if keep:
+            moved["deform"] = self._deform_argument(deformed)
+        return moved
+
     # A camera move.  camera_to_world / camera_inverse_projection: 16 floats each in Unity Matrix4x4 memory order (the inverse projection
     # stays when not given).  Temporal accumulation off: the new matrices and ResetAccumulation() (RM:765-767).  On: the pixel-centre
     # feature buffers of the previous and the new camera are rendered, the accumulated image and its counts are reprojected into the new
@@ -656,25 +697,13 @@ class RayTraceMaster:
         c2w = np.ascontiguousarray(camera_to_world, dtype=np.float32).reshape(16).copy()
         invp = s.camera_inverse_projection if camera_inverse_projection is None else \
             np.ascontiguousarray(camera_inverse_projection, dtype=np.float32).reshape(16).copy()
-        history = self._temporal is not None and self._converged is not None and self._currentSample > 0 and not self._treesNeedRebuilding \
-            and (self._converged.width, self._converged.height) == (self.screen_width, self.screen_height)
+        history = self._has_history()
+        prev_m = self._history_begin() if history else None
+        s.camera_to_world, s.camera_inverse_projection = c2w, invp
         if not history:
-            s.camera_to_world, s.camera_inverse_projection = c2w, invp
             self.ResetAccumulation()
             return
-        self._ensure_temporal_textures()
-        prev_m = scenes.world_to_clip(s.camera_to_world, s.camera_inverse_projection)
-        prev, cur = self._taov
-        self.SetShaderParameters()
-        self.ctx.render_aov(prev[0], prev[1], None, prev[2])                   # the previous camera's buffers
-        s.camera_to_world, s.camera_inverse_projection = c2w, invp
-        self.SetShaderParameters()
-        self.ctx.render_aov(cur[0], cur[1], None, cur[2])                      # the new camera's
-        color, count = self._tspare
-        self.ctx.reproject(self._converged, self._tcount, prev[0], prev[1], prev[2], cur[0], cur[1], cur[2], color, count, prev_m,
-                           **self._temporal)
-        self._tspare = (self._converged, self._tcount)
-        self._converged, self._tcount = color, count
+        self._history_finish(prev_m)
 
     # Objects move (and, optionally, the camera with them).  mesh_edits: {MeshObject index: 16-float localToWorldMatrix}; sphere_edits:
     # {sphere index: (position, radius)}.  The edits go into the scene's lists, the object-level heaps are rebuilt and everything is
@@ -692,10 +721,7 @@ class RayTraceMaster:
         new_mo, new_sp = s.mesh_objects.copy(), s.spheres.copy()
         for what, edits, n in (("mesh_edits", mesh_edits, len(new_mo)), ("sphere_edits", sphere_edits, len(new_sp))):
             for k in edits:
-                if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
-                    raise TypeError(f"MoveObjects: the keys of {what} must be ints, not {type(k).__name__}")
-                if not 0 <= k < n:
-                    raise IndexError(f"MoveObjects: {what} names object {k}, the scene has {n}")
+                _index_arg(k, n, "MoveObjects", f"the keys of {what}", f"{what} names object")
         for k, mat in mesh_edits.items():
             new_mo[k]["localToWorldMatrix"] = _matrix16(mat, f"MoveObjects: mesh_edits[{k}]")
         for k, edit in sphere_edits.items():
@@ -709,32 +735,16 @@ class RayTraceMaster:
         c2w = s.camera_to_world if camera_to_world is None else _matrix16(camera_to_world, "MoveObjects: camera_to_world").copy()
         invp = s.camera_inverse_projection if camera_inverse_projection is None else \
             _matrix16(camera_inverse_projection, "MoveObjects: camera_inverse_projection").copy()
-        history = self._temporal is not None and self._converged is not None and self._currentSample > 0 and not self._treesNeedRebuilding \
-            and (self._converged.width, self._converged.height) == (self.screen_width, self.screen_height)
-        if history:
-            self._ensure_temporal_textures()
-            prev_m = scenes.world_to_clip(s.camera_to_world, s.camera_inverse_projection)
-            prev, cur = self._taov
-            self.SetShaderParameters()
-            self.ctx.render_aov(prev[0], prev[1], None, prev[2])               # the scene and the camera as the history saw them
+        history = self._has_history()
+        prev_m = self._history_begin() if history else None
         prev_mo, prev_sp = s.mesh_objects, s.spheres
         self._apply_object_edits(new_mo, new_sp, mesh_edits, sphere_edits)
-        s.camera_to_world, s.camera_inverse_projection = c2w, invp
+        s.camera_to_world, s.camera_inverse_projection = c2w, invp              # (before the second set of feature buffers)
         if not history:
             self.ResetAccumulation()
             return
-        self.SetShaderParameters()
-        self.ctx.render_aov(cur[0], cur[1], None, cur[2])                      # the moved scene under the new camera
-        tables = [host_scene.mesh_motion(prev_mo, new_mo) if mesh_edits else None,
-                  host_scene.sphere_motion(prev_sp, new_sp) if sphere_edits else None]
-        for k, t in enumerate(tables):
-            self._tmotion[k] = self.CreateComputeBuffer(self._tmotion[k], t if t is not None else np.zeros((0, 12), np.float32), 48)
-        color, count = self._tspare
-        self.ctx.reproject(self._converged, self._tcount, prev[0], prev[1], prev[2], cur[0], cur[1], cur[2], color, count, prev_m,
-                           mesh_motion=self._tmotion[0], sphere_motion=self._tmotion[1], moved_max_history=self._moved_max_history,
-                           **self._temporal)
-        self._tspare = (self._converged, self._tcount)
-        self._converged, self._tcount = color, count
+        self._history_finish(prev_m, {"mesh": host_scene.mesh_motion(prev_mo, new_mo) if mesh_edits else None,
+                                      "sphere": host_scene.sphere_motion(prev_sp, new_sp) if sphere_edits else None})
 
     def vertex_span(self, k: int) -> tuple:
         """(first, last) vertex the index range of MeshObject k refers to; (0, -1) when it has no triangle."""
@@ -760,10 +770,7 @@ class RayTraceMaster:
             self.RebuildObjectLists()
         n = len(s.mesh_objects)
         for k in edits:
-            if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
-                raise TypeError(f"DeformMeshes: the keys of edits must be ints, not {type(k).__name__}")
-            if not 0 <= k < n:
-                raise IndexError(f"DeformMeshes: edits names MeshObject {k}, the scene has {n}")
+            _index_arg(k, n, "DeformMeshes", "the keys of edits", "edits names MeshObject")
         spans, checked = {}, {}
         for k, pos in edits.items():
             lo, hi = spans[k] = self.vertex_span(k)
@@ -774,14 +781,8 @@ class RayTraceMaster:
             if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] != hi - lo + 1:
                 raise ValueError(f"DeformMeshes: edits[{k}] must have shape ({hi - lo + 1}, 3), the vertex span of MeshObject {k}, not {a.shape}")
             checked[k] = a
-        history = self._temporal is not None and self._converged is not None and self._currentSample > 0 and not self._treesNeedRebuilding \
-            and (self._converged.width, self._converged.height) == (self.screen_width, self.screen_height)
-        if history:
-            self._ensure_temporal_textures()
-            prev_m = scenes.world_to_clip(s.camera_to_world, s.camera_inverse_projection)
-            prev, cur = self._taov
-            self.SetShaderParameters()
-            self.ctx.render_aov(prev[0], prev[1], None, prev[2])               # the scene as the history saw it
+        history = self._has_history()
+        prev_m = self._history_begin() if history else None
         keep = bool(keep_history) and history and bool(edits) and self._vertexBuffer is not None and self._indexBuffer is not None
         if keep:
             self._snapshot_for_deform()
@@ -799,8 +800,7 @@ class RayTraceMaster:
             if uploaded:
                 self._normalBuffer = self.CreateComputeBuffer(self._normalBuffer, np.ascontiguousarray(s.normals, np.float32), 12)
         if edits:
-            s.mesh_bvh = host_scene.build_object_bvh(host_scene.mesh_leaf_bounds(s.mesh_objects, s.vertices, s.indices)) if self._rayTraceObjects \
-                else scenes.build_object_bvh(*scenes.mesh_bounds(s.mesh_objects, s.vertices, s.indices))
+            s.mesh_bvh = self._host_mesh_heap(s.mesh_objects)
             if self._rayTraceObjects:                                             # keep the registered objects in step with the lists
                 meshes, first = [o for o in self._rayTraceObjects if o.type != 1], 0
                 for o in meshes:
@@ -812,27 +812,10 @@ class RayTraceMaster:
         if not history:
             self.ResetAccumulation()
             return
-        self.SetShaderParameters()
-        self.ctx.render_aov(cur[0], cur[1], None, cur[2])                      # the deformed scene
-        table = host_scene.mesh_motion(s.mesh_objects, s.mesh_objects)             # nothing else has moved: identity entries
-        for k in edits:
-            if not keep:
-                table[k] = np.nan
-        self._tmotion[0] = self.CreateComputeBuffer(self._tmotion[0], table if edits else np.zeros((0, 12), np.float32), 48)
-        self._tmotion[1] = self.CreateComputeBuffer(self._tmotion[1], np.zeros((0, 12), np.float32), 48)
-        color, count = self._tspare
-        extra = {"deform": self._deform_argument(edits)} if keep else {}
-        self.ctx.reproject(self._converged, self._tcount, prev[0], prev[1], prev[2], cur[0], cur[1], cur[2], color, count, prev_m,
-                           mesh_motion=self._tmotion[0], sphere_motion=self._tmotion[1], moved_max_history=self._moved_max_history,
-                           **extra, **self._temporal)
-        self._tspare = (self._converged, self._tcount)
-        self._converged, self._tcount = color, count
+        self._history_finish(prev_m, {"deformed": edits, "keep": keep})
 
     def _mesh_index_arg(self, k, who: str, what: str):
-        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
-            raise TypeError(f"{who}: {what} must be ints, not {type(k).__name__}")
-        if not 0 <= k < len(self.scene.mesh_objects):
-            raise IndexError(f"{who}: {what} names MeshObject {k}, the scene has {len(self.scene.mesh_objects)}")
+        _index_arg(k, len(self.scene.mesh_objects), who, what, f"{what} names MeshObject")
 
     # A mesh gets a skin: bone_indices (n, 4) int32 and bone_weights (n, 4) float32 for the n vertices of its vertex span (vertex_span).
     # The span's positions and normals as the scene holds them NOW are kept as the rest pose.  Nothing reaches the library before
@@ -995,14 +978,10 @@ class RayTraceMaster:
         s = self.scene
         if self._treesNeedRebuilding:                                             # the buffers the deformation writes into must exist
             self._bind_for_queries()
-        history = self._temporal is not None and self._converged is not None and self._currentSample > 0 \
-            and (self._converged.width, self._converged.height) == (self.screen_width, self.screen_height)
-        if history:
-            self._ensure_temporal_textures()
-            prev_m = scenes.world_to_clip(s.camera_to_world, s.camera_inverse_projection)
-            prev, cur = self._taov
-            self.SetShaderParameters()
-            self.ctx.render_aov(prev[0], prev[1], None, prev[2])               # the scene as the history saw it
+        # (the trees never need rebuilding here: _bind_for_queries has just cleared the flag — and zeroed _currentSample, so a rebuild
+        # means no history, as in the other edits)
+        history = self._has_history()
+        prev_m = self._history_begin() if history else None
         keep = bool(keep_history) and history and bool(spans)
         if keep:
             self._snapshot_for_deform()
@@ -1026,21 +1005,7 @@ class RayTraceMaster:
         if not history:
             self.ResetAccumulation()
             return
-        self.SetShaderParameters()
-        self.ctx.render_aov(cur[0], cur[1], None, cur[2])                      # the deformed scene
-        table = host_scene.mesh_motion(s.mesh_objects, s.mesh_objects)             # nothing else has moved: identity entries
-        for k in spans:
-            if not keep:
-                table[k] = np.nan
-        self._tmotion[0] = self.CreateComputeBuffer(self._tmotion[0], table if spans else np.zeros((0, 12), np.float32), 48)
-        self._tmotion[1] = self.CreateComputeBuffer(self._tmotion[1], np.zeros((0, 12), np.float32), 48)
-        color, count = self._tspare
-        extra = {"deform": self._deform_argument(spans)} if keep else {}
-        self.ctx.reproject(self._converged, self._tcount, prev[0], prev[1], prev[2], cur[0], cur[1], cur[2], color, count, prev_m,
-                           mesh_motion=self._tmotion[0], sphere_motion=self._tmotion[1], moved_max_history=self._moved_max_history,
-                           **extra, **self._temporal)
-        self._tspare = (self._converged, self._tcount)
-        self._converged, self._tcount = color, count
+        self._history_finish(prev_m, {"deformed": spans, "keep": keep})
 
     # A mesh gets blend shapes (morph targets): targets = [(delta_vertices (n, 3), delta_normals (n, 3) or None), ...], dense over the
     # n vertices of its vertex span as Mesh.GetBlendShapeFrameVertices returns them.  Rows whose six deltas all compare == 0 are dropped,
@@ -1167,6 +1132,19 @@ class RayTraceMaster:
                                        lo, hi - lo + 1, self._vertexBuffer, None if recompute_normals else self._normalBuffer)
         self._deform_on_device({k: self._morphs[k]["span"] for k in checked}, morph, recompute_normals, keep_history)
 
+    # The object-level heap of a mesh / sphere list on the host: through the C++ host library for registered objects, as
+    # RebuildObjectLists builds them, else with the builders of scenes.py that made the pre-flattened scene's.
+    def _host_mesh_heap(self, mesh_objects) -> np.ndarray:
+        s = self.scene
+        if self._rayTraceObjects:
+            return host_scene.build_object_bvh(host_scene.mesh_leaf_bounds(mesh_objects, s.vertices, s.indices))
+        return scenes.build_object_bvh(*scenes.mesh_bounds(mesh_objects, s.vertices, s.indices))
+
+    def _host_sphere_heap(self, spheres) -> np.ndarray:
+        if self._rayTraceObjects:
+            return host_scene.build_object_bvh(host_scene.sphere_leaf_bounds(spheres))
+        return scenes.build_object_bvh(*scenes.sphere_bounds(spheres))
+
     # the edited lists become the scene's, with the object-level heaps RebuildObjectLists / the scene builders make for them, and are
     # uploaded (RebuildTrees: SetData of data a buffer already holds changes nothing)
     def _apply_object_edits(self, new_mo, new_sp, mesh_edits, sphere_edits):
@@ -1181,34 +1159,27 @@ class RayTraceMaster:
                 spheres[k].position, spheres[k].radius = tuple(float(v) for v in new_sp[k]["position"]), float(new_sp[k]["radius"])
         on_device = [bool(e) and not self._treesNeedRebuilding and self._can_build_heaps_on_device(k)
                      for k, e in enumerate((mesh_edits, sphere_edits))]
-        if any(on_device):
-            # the edited lists go up by SetData as always; the heaps of the edited kinds are built where the buffers live.  (RebuildTrees
-            # would read the heaps back first.)  An edited kind whose heap the device cannot build takes the host path, as without the flag.
-            if mesh_edits and not on_device[0]:
-                s.mesh_bvh = host_scene.build_object_bvh(host_scene.mesh_leaf_bounds(new_mo, s.vertices, s.indices)) if self._rayTraceObjects \
-                    else scenes.build_object_bvh(*scenes.mesh_bounds(new_mo, s.vertices, s.indices))
-                self._meshObjectBVHBuffer = self.CreateComputeBuffer(self._meshObjectBVHBuffer, s.mesh_bvh, self.BVHNodeSize)
-                self._heapsBehind[0] = False
-            if sphere_edits and not on_device[1]:
-                s.sphere_bvh = host_scene.build_object_bvh(host_scene.sphere_leaf_bounds(new_sp)) if self._rayTraceObjects \
-                    else scenes.build_object_bvh(*scenes.sphere_bounds(new_sp))
-                self._sphereBVHBuffer = self.CreateComputeBuffer(self._sphereBVHBuffer, s.sphere_bvh, self.BVHNodeSize)
-                self._heapsBehind[1] = False
-            self._meshObjectBuffer = self.CreateComputeBuffer(self._meshObjectBuffer, s.mesh_objects, self.MeshObjectStructSize)
-            self._sphereBuffer = self.CreateComputeBuffer(self._sphereBuffer, s.spheres, self.SphereStructSize)
-            for k in (0, 1):
-                if on_device[k]:
-                    self._build_heap_on_device(k)
+        on_host = [bool(e) and not d for e, d in zip((mesh_edits, sphere_edits), on_device)]
+        if on_host[0]:
+            s.mesh_bvh = self._host_mesh_heap(new_mo)
+        if on_host[1]:
+            s.sphere_bvh = self._host_sphere_heap(new_sp)
+        self._heapsBehind = [b and not h for b, h in zip(self._heapsBehind, on_host)]   # the recomputed lists are the newest
+        if not any(on_device):
+            if not self._treesNeedRebuilding:                                      # else the next frame uploads everything anyway
+                self.RebuildTrees()
             return
-        if mesh_edits:
-            s.mesh_bvh = host_scene.build_object_bvh(host_scene.mesh_leaf_bounds(new_mo, s.vertices, s.indices)) if self._rayTraceObjects \
-                else scenes.build_object_bvh(*scenes.mesh_bounds(new_mo, s.vertices, s.indices))
-        if sphere_edits:
-            s.sphere_bvh = host_scene.build_object_bvh(host_scene.sphere_leaf_bounds(new_sp)) if self._rayTraceObjects \
-                else scenes.build_object_bvh(*scenes.sphere_bounds(new_sp))
-        self._heapsBehind = [b and not e for b, e in zip(self._heapsBehind, (mesh_edits, sphere_edits))]   # the recomputed lists are the newest
-        if not self._treesNeedRebuilding:                                          # else the next frame uploads everything anyway
-            self.RebuildTrees()
+        # the edited lists go up by SetData as always; the heaps of the edited kinds are built where the buffers live.  (RebuildTrees
+        # would read the heaps back first.)  An edited kind whose heap the device cannot build takes the host path, as without the flag.
+        if on_host[0]:
+            self._meshObjectBVHBuffer = self.CreateComputeBuffer(self._meshObjectBVHBuffer, s.mesh_bvh, self.BVHNodeSize)
+        if on_host[1]:
+            self._sphereBVHBuffer = self.CreateComputeBuffer(self._sphereBVHBuffer, s.sphere_bvh, self.BVHNodeSize)
+        self._meshObjectBuffer = self.CreateComputeBuffer(self._meshObjectBuffer, s.mesh_objects, self.MeshObjectStructSize)
+        self._sphereBuffer = self.CreateComputeBuffer(self._sphereBuffer, s.spheres, self.SphereStructSize)
+        for k in (0, 1):
+            if on_device[k]:
+                self._build_heap_on_device(k)
 
     # ---- device_object_heaps: the object-level heaps built where the buffers live (kind 0 = meshes, 1 = spheres) ----
     def _can_build_heaps_on_device(self, kind: int) -> bool:

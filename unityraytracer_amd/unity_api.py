@@ -14,6 +14,7 @@ status and message) — a caller wanting Unity's behaviour catches, logs and con
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -101,14 +102,7 @@ class Context:
         """Linear blend skinning of elements first .. first + count - 1 on the GPU, into the device mirrors of dst_vertices (and
         dst_normals) — include/urt.h urt_skin_vertices.  Every argument but the range is a ComputeBuffer; rest_normals and dst_normals
         may be None (positions only).  Enqueued on the context's stream; nothing is waited for."""
-        def handle(b, name, optional=False):
-            if b is None and optional:
-                return 0
-            if not isinstance(b, ComputeBuffer):
-                raise TypeError(f"skin_vertices: {name} must be a ComputeBuffer{' or None' if optional else ''}, not {type(b).__name__}")
-            if b.ctx is not self:
-                raise ValueError(f"skin_vertices: {name} belongs to another context")
-            return b.handle
+        handle = functools.partial(_buffer_handle, self, "skin_vertices")
         for name, v in (("first", first), ("count", count)):
             if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
                 raise TypeError(f"skin_vertices: {name} must be an int, not {type(v).__name__}")
@@ -807,6 +801,17 @@ def _check_texture(ctx, what: str, name: str, t, like, optional: bool = False):
         raise ValueError(f"{what}: {name} is {t.width} x {t.height}, not {like.width} x {like.height}")
 
 
+def _buffer_handle(ctx, what: str, b, name: str, optional: bool = False) -> int:
+    """The handle of a ComputeBuffer of ctx (0 for None where that is allowed)."""
+    if b is None and optional:
+        return 0
+    if not isinstance(b, ComputeBuffer):
+        raise TypeError(f"{what}: {name} must be a ComputeBuffer{' or None' if optional else ''}, not {type(b).__name__}")
+    if b.ctx is not ctx:
+        raise ValueError(f"{what}: {name} belongs to another context")
+    return b.handle
+
+
 DEFORM_FIELDS = (("prev_vertices", 12), ("indices", 4), ("prev_mesh_objects", 112), ("deformed", 4))
 
 
@@ -1358,14 +1363,7 @@ class MorphPlan:
         """dst_v (and dst_n) [first .. first + count - 1] = rest_v (rest_n) + the weighted deltas (urt_morph_vertices).  rest_v, dst_v,
         rest_n, dst_n: stride-12 ComputeBuffers of one count; rest_n and dst_n may be None (positions only).  weights: a stride-4
         ComputeBuffer of n_targets floats.  normalize: URT_MORPH_NORMALIZE."""
-        def handle(b, name, optional=False):
-            if b is None and optional:
-                return 0
-            if not isinstance(b, ComputeBuffer):
-                raise TypeError(f"MorphPlan.morph: {name} must be a ComputeBuffer{' or None' if optional else ''}, not {type(b).__name__}")
-            if b.ctx is not self.ctx:
-                raise ValueError(f"MorphPlan.morph: {name} belongs to another context")
-            return b.handle
+        handle = functools.partial(_buffer_handle, self.ctx, "MorphPlan.morph")
         self.ctx.check(self.ctx.lib.urt_morph_vertices(self.ctx._h, self.handle, handle(rest_v, "rest_v"), handle(rest_n, "rest_n", True),
                                                        handle(weights, "weights"), handle(dst_v, "dst_v"), handle(dst_n, "dst_n", True),
                                                        _lib.MORPH_NORMALIZE if normalize else 0))
