@@ -83,7 +83,29 @@ state_words: exposure and target as bits, counted, skipped and the 256 bins as i
     ("present_tm", dest | None, operator)   m.ToneMap(dest, operator): meter C into MS, bloom C into dest with MS if bloom is on, tone-map
                                        with MS; None = the texture the master owns, "TM" to ("get", "TM") and in the final contents
 The library refuses a tonemap / bloom destination that is the bound sky, textures of two sizes in one of these calls (upsample: within
-either grid), a count image for a source of another size, and ToneMap into _converged."""
+either grid), a count image for a source of another size, and ToneMap into _converged.
+
+The "dynamic" profile (profile="dynamic") adds blend shapes, the object-level heaps built on the device and depth of field to the
+display profile: every op above, and the ones below.  More of the world (dynamic_world): a MorphPlan of three sparse targets over the
+blob's span (the rest pose is the skin ops'), the weights buffer W (stride 4) that the host rewrites in front of every morph, the leaf
+buffers LM / LS (stride 28, one leaf per MeshObject / sphere), the names HM / HS for the two BOUND heap buffers (_MeshBVH / _SphereBVH), and
+"DH", the hit guide the master owns once ToneMap has run with depth of field on (all zero until then).  Its ops:
+    ("morph", j, with_normals, normalize)   W.SetData(MORPH_WEIGHTS[j]), plan.morph(rest_v, rest_n, W, V, NB | None, normalize) — the rest
+                                       normals are passed exactly when NB is — and SetData of the heap, as the other vertex writes do
+    ("device_heap", edit)              `edit` — an op of DEVICE_EDITS: SCENE_CHANGES without "normals", and "morph" — WITHOUT its host SetData of
+                                       the heap; instead ctx.mesh_leaf_bounds(_MeshObjects, V, _Indices, LM), ctx.build_object_bvh(LM, HM), or
+                                       the sphere pair for "move_spheres": three (two) kernels on the context's stream into the bound heap
+                                       buffer's device side.  The model: host_scene.build_object_bvh(host_scene.mesh_leaf_bounds(...)) — the
+                                       values the device computes, NOT scenes.mesh_bounds, which rounds outward
+    ("rebuild_heap", kind)             the device build of kind 0 (meshes) | 1 (spheres) with no edit in front of it
+    ("get_buffer", which, first, count)     also of HM | HS | LM | LS, observed as heap_words: 7 words per element
+    ("dof", src, hit, dst, j)          ctx.depth_of_field(src, hit, dst, **DOF[j]): hit is Gh | Ph with frame-sized src / dst, or Lh with src /
+                                       dst of the low grid
+    ("master_dof", j | None)           EnableDepthOfField(**DOF[j]) | DisableDepthOfField(); while on, ("present_tm", ...) meters, renders the
+                                       hit guide through the sample centres into DH, blurs C into the destination, blooms it in place if
+                                       bloom is on and tone-maps it in place; the host's projection is bound again afterwards
+The library refuses a depth-of-field destination that is the source, the hit image or the bound sky, textures of two sizes, normalize
+without normals; the heap calls a destination that is also an input."""
 import copy
 
 import numpy as np
@@ -136,6 +158,31 @@ TONEMAP_OPS = ("linear", "reinhard", "aces")                     # in the order 
 METER = (dict(rate=1.0), dict(rate=0.25), dict(rate=0.5, key=0.25, low_permille=300, high_permille=800), dict(rate=0.5))
 MASTER_EXPOSURE, MASTER_BLOOM = dict(rate=0.5), dict(levels=3)
 STATE_WORDS = 260
+# the dynamic profile
+DYNAMIC_KINDS = ("morph", "device_heap", "rebuild_heap", "dof", "master_dof")
+DYN_KINDS = DISP_KINDS + DYNAMIC_KINDS
+DEVICE_EDITS = tuple(k for k in SCENE_CHANGES if k != "normals") + ("morph",)      # what ("device_heap", edit) wraps
+HEAP_BUFFERS = ("HM", "HS", "LM", "LS")                          # the bound heaps and the leaves under them: stride 28
+DYN_BUFFERS = BUFFERS + ("W",) + HEAP_BUFFERS
+N_TARGETS = 3
+MORPH_WEIGHTS = ((0.0, 0.0, 0.0), (1.0, 0.0, 0.5), (0.5, -0.75, 0.0), (0.25, 0.5, 1.0))      # [0] all zero, [2] with a negative weight
+DOF_FLAG_COC = 1                                                 # URT_DOF_FLAG_COC
+# max_radius in each of the three reaches of csrc/dof.hip (<= 4, <= 8, <= 16).  [3] leaves the foreground sharp: from the first camera
+# nothing is nearer than 1.56, and |scale * (1 - focus_distance / z)| <= 0.5 for every z in [1.36, 2.26] — each pixel nearer than 2.26 has
+# the smallest blur radius and nothing in front of it is blurred, so its own tap is its only one (dof_foreground).  [4]: the blur radius
+# instead of the image
+DOF = (dict(focus_distance=3.0, scale=5.0, max_radius=4.0), dict(focus_distance=6.0, scale=9.0, max_radius=8.0),
+       dict(focus_distance=2.25, scale=14.0, max_radius=16.0), dict(focus_distance=1.7, scale=2.0, max_radius=6.0),
+       dict(focus_distance=10.0, scale=8.0, max_radius=8.0, flags=DOF_FLAG_COC))
+DOF_IN_FOCUS = 3
+
+
+def dof_foreground(hit):
+    """The pixels DOF[DOF_IN_FOCUS] leaves bit for bit when nothing of the image is nearer than 1.36: those nearer than 2.26."""
+    z = np.asarray(hit, F)[..., 3]
+    assert not ((z > 0) & (z < F(1.36))).any(), "something lies in front of the in-focus band"
+    return (z > 0) & (z < F(2.26))
+DYNAMIC_IMAGE_OPS = DISPLAY_IMAGE_OPS + ("dof",)
 
 
 def size_class(name):
@@ -232,8 +279,43 @@ def edited_scene(sc, op):
         out.vertices, out.normals = v, n
         if op[0] != "normals":
             out.mesh_bvh = scenes.build_object_bvh(*scenes.mesh_bounds(sc.mesh_objects, v, sc.indices))
+    elif op[0] == "morph":
+        import morph_ref
+        w = dynamic_world(sc.width, sc.height)
+        lo, hi = w["span"]
+        _, j, with_normals, normalize = op
+        v, n = np.array(sc.vertices, F).reshape(-1, 3), np.array(sc.normals, F).reshape(-1, 3)
+        pos, nrm = morph_ref.morph(w["rest_v"], w["rest_n"] if with_normals else None, w["deltas"], lo, hi - lo + 1, MORPH_WEIGHTS[j], normalize)
+        v[lo: hi + 1] = pos
+        if with_normals:
+            n[lo: hi + 1] = nrm
+        out.vertices, out.normals = v, n
+        out.mesh_bvh = scenes.build_object_bvh(*scenes.mesh_bounds(sc.mesh_objects, v, sc.indices))
     else:
         raise ValueError(op)
+    return out
+
+
+def heap_kind(edit):
+    """0 (meshes) | 1 (spheres): the object-level heap an op of DEVICE_EDITS makes stale."""
+    return 1 if edit[0] == "move_spheres" else 0
+
+
+def device_heap_of(sc, kind):
+    """(leaves, heap) of kind 0 | 1 as the device builds them from the scene's lists (include/urt.h "the object-level BVH on the device":
+    what urt_host_*_leaf_bounds(literal = 0) and urt_host_build_object_bvh compute, by value).  NOT scenes.mesh_bounds / sphere_bounds:
+    they round outward, so their heaps differ from these by value."""
+    from unityraytracer_amd import host_scene
+    leaves = host_scene.sphere_leaf_bounds(sc.spheres) if kind else host_scene.mesh_leaf_bounds(sc.mesh_objects, sc.vertices, sc.indices)
+    return leaves, host_scene.build_object_bvh(leaves)
+
+
+def heap_words(nodes):
+    """BVHNodes (28 bytes each, as bytes or as records) as (n, 7) words: the six floats as bits — +0 for a zero of either sign, the header
+    promises the device's floats by value — and the index."""
+    a = np.ascontiguousarray(nodes).reshape(-1).view(np.uint8).reshape(-1, 28)
+    out = np.array(a.view(np.uint32).reshape(-1, 7))
+    out[:, :6] = (out[:, :6].view(F) + F(0.0)).view(np.uint32)
     return out
 
 
@@ -259,6 +341,34 @@ def pipeline_world(width=64, height=40):
         _WORLDS[(width, height)] = {"span": (lo, hi), "rest_v": rest_v, "rest_n": rest_n, "bone_idx": idx, "bone_wgt": wgt, "poses": poses,
                                     "plan": normals_ref.plan(v, sc.indices, lo, hi - lo + 1), "deformed": flags}
     return _WORLDS[(width, height)]
+
+
+_DYNAMIC_WORLDS = {}
+
+
+def dynamic_world(width=64, height=40):
+    """What the dynamic profile adds to pipeline_world (whose entries it holds, too), made once per size: "deltas", the urt_MorphDelta
+    array of N_TARGETS sparse targets over the blob's span — served vertex i is named by target 0 when i % 2 == 0, by target 1 when
+    i % 3 == 0 and by target 2 when i % 5 == 0, so some vertices are touched by none and some by all three — and "counts", the element
+    counts of the four stride-28 buffers."""
+    if (width, height) not in _DYNAMIC_WORLDS:
+        import morph_ref
+        w = dict(pipeline_world(width, height))
+        sc = make_scene(width, height)
+        lo, hi = w["span"]
+        rng = np.random.default_rng(4242)
+        vertex, target = [], []
+        for t, step in enumerate((2, 3, 5)):
+            at = np.arange(lo, hi + 1)[(np.arange(hi - lo + 1) % step) == 0]
+            vertex.append(at)
+            target.append(np.full(len(at), t))
+        vertex, target = np.concatenate(vertex), np.concatenate(target)
+        dp = (w["rest_n"][vertex] * F(0.35) * rng.uniform(0.5, 1.0, (len(vertex), 1)) + rng.normal(scale=0.05, size=(len(vertex), 3))).astype(F)
+        dn = rng.normal(scale=0.3, size=(len(vertex), 3)).astype(F)
+        w["deltas"] = morph_ref.deltas_array(vertex, target, dp, dn)
+        w["counts"] = {"LM": len(sc.mesh_objects), "LS": len(sc.spheres), "HM": len(sc.mesh_bvh), "HS": len(sc.sphere_bvh)}
+        _DYNAMIC_WORLDS[(width, height)] = w
+    return _DYNAMIC_WORLDS[(width, height)]
 
 
 def aov_targets(op):
@@ -393,6 +503,8 @@ def make_program(seed, n_ops=40, profile="frames"):
         return make_pipeline_program(seed, n_ops)
     if profile == "display":
         return make_display_program(seed, n_ops)
+    if profile == "dynamic":
+        return make_dynamic_program(seed, n_ops)
     assert profile == "frames", profile
     rng = np.random.default_rng(seed)
     kinds = list(_WEIGHTS)
@@ -786,6 +898,59 @@ def _draw_display(rng, kind, tr, nv, span):
     return _draw_pipeline(rng, kind, tr, nv, span)
 
 
+def _sky_and_frame(t):
+    return [("bind_sky", t), ("frame", "X1" if t != "X1" else "X2")]
+
+
+def _display_followers(rng, op, result, tr):
+    """What the display profile plays right behind a display op or a frame (`op`, just emitted).  Draws from rng exactly what
+    make_display_program always drew here."""
+    pick = lambda names: names[int(rng.integers(len(names)))]
+
+    def with_prerequisites(op):
+        return tr.prerequisites(op) + [op]
+
+    k, r = op[0], rng.random()
+    state = int(rng.integers(2))
+    if k == "frame" and r < 0.2:                             # the presented frame: meter, bloom and / or tone-map, read back
+        dest = pick(("X0", "X1", "U"))
+        chain = [("meter", "C", state, bool(rng.random() < 0.2), int(pick((1, 1, 3, 0))))]
+        if rng.random() < 0.6:
+            chain += [("bloom", "C", dest, state, int(pick((3, 6))), 0), ("tonemap", dest, dest, state, "aces", 1.0)]
+        else:
+            chain += [("tonemap", "C", dest, state, pick(TONEMAP_OPS), 1.0)]
+        return chain + [("read_begin", dest, "RGBA8_SRGB")]
+    if k == "frame" and r < 0.24:                            # in place on C or H, then a frame or the history blend
+        t = pick(("C", "H"))
+        return [pick((("tonemap", t, t, None, "reinhard", 1.0), ("bloom", t, t, pick((None, state)), 3, 0))),
+                pick((("frame", None), ("history", 0.0)))]
+    if k == "frame" and r < 0.34:                            # a display call writes the bound Result, a frame follows
+        writer = pick((("tonemap", "C", tr.result, None, "aces", 1.0), ("bloom", "C", tr.result, None, 3, 0),
+                       ("upsample", tr.result, None, False, WIDE_FALLBACK)))
+        return with_prerequisites(writer) + [("frame", None)]
+    if k == "frame" and r < 0.42:                            # the master's ToneMap, read back
+        dest = pick((None, "X0", "X1"))
+        return [("master_bloom", bool(rng.random() < 0.7)), ("present_tm", dest, "aces")] + \
+               ([("read_begin", dest, "RGBA8_SRGB")] if dest else [("get", "TM")])
+    if k == "frame" and r < 0.48:                            # upsample into the history pair, then its consumer
+        return with_prerequisites(("upsample", "H", "N", bool(rng.random() < 0.5), int(rng.integers(4)))) + \
+               [pick((("select", "N", 1.0), ("resample", 2.0, 1, 0.0)))]
+    if k == "meter" and r < 0.5:                             # one state twice in a row below rate 1, on sources of two sizes
+        a, b = pick((("C", "Lc"), ("S0", "C"), ("Lc", "S1"), ("U", "S0")))
+        return [("meter", a, op[2], False, 1), ("meter", b, op[2], False, int(pick((1, 2, 3)))),
+                pick((("tonemap", "C", "X0", op[2], "aces", 1.0), ("bloom", "C", "X1", op[2], 3, 0), ("state_get", op[2])))]
+    if k == "bloom" and size_class(op[1]) != 1 and r < 0.6:  # bloom on a small texture, then on a larger one
+        return [pick((("bloom", "S0", "S1", None, op[4], 0), ("bloom", "S1", "S1", None, 16, 0))) if size_class(op[1]) == 0 else
+                pick((("bloom", "C", "X0", None, op[4], 0), ("bloom", "S0", "S1", None, op[4], 0)))]
+    if k == "upsample" and (op[1] == "H" or op[2] == "N") and r < 0.6:
+        return [pick((("select", "N", 1.0), ("resample", 2.0, 1, 0.0)))]
+    if k in DISPLAY_WRITERS + ("present_tm",) and r < 0.8:
+        dest = op[1] if k == "upsample" else op[2] if k != "present_tm" else op[1]
+        if dest is not None and dest != tr.result:          # the destination is bound as the sky and traced at once
+            return _sky_and_frame(dest)
+    return []
+
+
 def make_display_program(seed, n_ops=40):
     """As make_pipeline_program, over DISP_KINDS (what follows an op of the pipeline profile is what follows it there).  The bias of the
     display calls: a frame's blend into C is followed by its metering, a bloom or tone mapping with that state and an 8-bit readback of
@@ -801,7 +966,6 @@ def make_display_program(seed, n_ops=40):
     p = np.array([_DISPLAY_WEIGHTS[k] for k in kinds], dtype=np.float64)
     p /= p.sum()
     tr, prog, forced = _DisplayTrack(), [], []
-    pick = lambda names: names[int(rng.integers(len(names)))]
 
     def emit(op):
         tr.apply(op)
@@ -810,52 +974,8 @@ def make_display_program(seed, n_ops=40):
     def draw(kind):
         return _draw_display(rng, kind, tr, nv, (lo, hi))
 
-    def with_prerequisites(op):
-        return tr.prerequisites(op) + [op]
-
-    def sky_and_frame(t):
-        return [("bind_sky", t), ("frame", "X1" if t != "X1" else "X2")]
-
     def followers(op, result):
-        k, r = op[0], rng.random()
-        state = int(rng.integers(2))
-        if k == "frame" and r < 0.2:                             # the presented frame: meter, bloom and / or tone-map, read back
-            dest = pick(("X0", "X1", "U"))
-            chain = [("meter", "C", state, bool(rng.random() < 0.2), int(pick((1, 1, 3, 0))))]
-            if rng.random() < 0.6:
-                chain += [("bloom", "C", dest, state, int(pick((3, 6))), 0), ("tonemap", dest, dest, state, "aces", 1.0)]
-            else:
-                chain += [("tonemap", "C", dest, state, pick(TONEMAP_OPS), 1.0)]
-            return chain + [("read_begin", dest, "RGBA8_SRGB")]
-        if k == "frame" and r < 0.24:                            # in place on C or H, then a frame or the history blend
-            t = pick(("C", "H"))
-            return [pick((("tonemap", t, t, None, "reinhard", 1.0), ("bloom", t, t, pick((None, state)), 3, 0))),
-                    pick((("frame", None), ("history", 0.0)))]
-        if k == "frame" and r < 0.34:                            # a display call writes the bound Result, a frame follows
-            writer = pick((("tonemap", "C", tr.result, None, "aces", 1.0), ("bloom", "C", tr.result, None, 3, 0),
-                           ("upsample", tr.result, None, False, WIDE_FALLBACK)))
-            return with_prerequisites(writer) + [("frame", None)]
-        if k == "frame" and r < 0.42:                            # the master's ToneMap, read back
-            dest = pick((None, "X0", "X1"))
-            return [("master_bloom", bool(rng.random() < 0.7)), ("present_tm", dest, "aces")] + \
-                   ([("read_begin", dest, "RGBA8_SRGB")] if dest else [("get", "TM")])
-        if k == "frame" and r < 0.48:                            # upsample into the history pair, then its consumer
-            return with_prerequisites(("upsample", "H", "N", bool(rng.random() < 0.5), int(rng.integers(4)))) + \
-                   [pick((("select", "N", 1.0), ("resample", 2.0, 1, 0.0)))]
-        if k == "meter" and r < 0.5:                             # one state twice in a row below rate 1, on sources of two sizes
-            a, b = pick((("C", "Lc"), ("S0", "C"), ("Lc", "S1"), ("U", "S0")))
-            return [("meter", a, op[2], False, 1), ("meter", b, op[2], False, int(pick((1, 2, 3)))),
-                    pick((("tonemap", "C", "X0", op[2], "aces", 1.0), ("bloom", "C", "X1", op[2], 3, 0), ("state_get", op[2])))]
-        if k == "bloom" and size_class(op[1]) != 1 and r < 0.6:  # bloom on a small texture, then on a larger one
-            return [pick((("bloom", "S0", "S1", None, op[4], 0), ("bloom", "S1", "S1", None, 16, 0))) if size_class(op[1]) == 0 else
-                    pick((("bloom", "C", "X0", None, op[4], 0), ("bloom", "S0", "S1", None, op[4], 0)))]
-        if k == "upsample" and (op[1] == "H" or op[2] == "N") and r < 0.6:
-            return [pick((("select", "N", 1.0), ("resample", 2.0, 1, 0.0)))]
-        if k in DISPLAY_WRITERS + ("present_tm",) and r < 0.8:
-            dest = op[1] if k == "upsample" else op[2] if k != "present_tm" else op[1]
-            if dest is not None and dest != tr.result:          # the destination is bound as the sky and traced at once
-                return sky_and_frame(dest)
-        return []
+        return _display_followers(rng, op, result, tr)
 
     while len(prog) < n_ops or forced:
         if forced:
@@ -884,6 +1004,290 @@ def make_display_program(seed, n_ops=40):
     while tr.tickets:
         emit(("read_end",))
     return prog
+
+
+# ---- programs of the dynamic profile -------------------------------------------------------------------------------------------------
+class _DynamicTrack(_DisplayTrack):
+    def __init__(self):
+        super().__init__()
+        self.master_dof = None                                   # the preset EnableDepthOfField was last given (None: off)
+
+    def allowed(self, op):
+        k = op[0]
+        if k == "morph":                                         # (URT_MORPH_NORMALIZE without dst_normals is refused)
+            return 0 <= op[1] < len(MORPH_WEIGHTS) and (op[2] or not op[3])
+        if k == "device_heap":
+            return op[1][0] in DEVICE_EDITS and self.allowed(op[1])
+        if k == "rebuild_heap":
+            return op[1] in (0, 1)
+        if k == "dof":                                           # sizes that differ; a destination that is an input or the bound sky
+            _, src, hit, dst, j = op
+            cls = 2 if hit == "Lh" else 0
+            return hit in ("Gh", "Ph", "Lh") and src in DISPLAY_EXACT and dst in DISPLAY_EXACT and 0 <= j < len(DOF) and \
+                size_class(src) == size_class(dst) == cls and dst not in (src, hit, self.sky)
+        if k == "master_dof":
+            return op[1] is None or 0 <= op[1] < len(DOF)
+        if k == "get_buffer" and op[1] in HEAP_BUFFERS:
+            return 0 <= op[2] and op[3] >= 1 and op[2] + op[3] <= dynamic_world()["counts"][op[1]]
+        return super().allowed(op)
+
+    def apply(self, op):
+        super().apply(op)
+        if op[0] == "master_dof":
+            self.master_dof = op[1]
+        elif op[0] == "device_heap":
+            super().apply(op[1])
+
+    def prerequisites(self, op):
+        pre = super().prerequisites(op)
+        if op[0] == "dof":                                       # a hit image nothing has rendered makes every pixel pass through
+            ready = {"Gh": self.g_ready, "Ph": self.p_ready, "Lh": self.low_ready}[op[2]]
+            if not ready:
+                pre.append({"Gh": ("aov", "G", 15, False), "Ph": ("aov", "P", 11, False), "Lh": ("aov_low", False)}[op[2]])
+        return pre
+
+
+def dynamic_writes_of(op, result):
+    """display_writes_of for every kind of the dynamic profile (textures and states; the buffers are dynamic_coverage's own business)."""
+    if op[0] == "dof":
+        return [(op[3], "dof")]
+    if op[0] == "device_heap":
+        return []
+    return display_writes_of(op, result)
+
+
+def dynamic_reads_of(op, result):
+    if op[0] == "dof":
+        return [op[1], op[2]]
+    return display_reads_of(op, result)
+
+
+# the display profile's weights at 0.75, the frame loop held up; then the dynamic kinds
+_DYNAMIC_WEIGHTS = dict({k: 0.75 * v for k, v in _DISPLAY_WEIGHTS.items()}, frame=18, get_buffer=4, ray_query_async=3, present_tm=4,
+                        morph=6, device_heap=9, rebuild_heap=3, dof=8, master_dof=3)
+_DOF_DST = {0: ("X0", "X1", "X2", "U", "H"), 2: ("Lc", "Ln")}
+
+
+def _draw_dynamic(rng, kind, tr, nv, span):
+    pick = lambda names: names[int(rng.integers(len(names)))]
+    lo, hi = span
+    if kind == "morph":
+        with_normals = bool(rng.random() < 0.6)
+        return ("morph", int(rng.integers(len(MORPH_WEIGHTS))), with_normals, bool(with_normals and rng.random() < 0.5))
+    if kind == "device_heap":
+        edit = pick(("move_mesh", "move_mesh", "deform", "move_spheres", "move_spheres", "skin", "set_device", "set_host", "set_host", "morph"))
+        return ("device_heap", _draw_dynamic(rng, edit, tr, nv, span))
+    if kind == "rebuild_heap":
+        return ("rebuild_heap", int(rng.integers(2)))
+    if kind == "dof":
+        low = rng.random() < 0.3
+        hit = "Lh" if low else pick(("Gh", "Gh", "Ph"))
+        src = "Lc" if low else pick(("C", "C", "C", "H", "X0", "U", tr.result, "R", "Ga"))
+        dst = pick(tuple(t for t in _DOF_DST[2 if low else 0] + (() if low else (tr.result, tr.result)) if t != src))
+        return ("dof", src, hit, dst, int(rng.integers(len(DOF))))
+    if kind == "master_dof":
+        return ("master_dof", int(rng.integers(len(DOF))) if rng.random() < 0.7 else None)
+    if kind == "get_buffer" and rng.random() < 0.5:
+        which = pick(HEAP_BUFFERS)
+        n = dynamic_world()["counts"][which]
+        first = int(rng.integers(n))
+        return ("get_buffer", which, first, int(rng.integers(1, n - first + 1)))
+    return _draw_display(rng, kind, tr, nv, span)
+
+
+def _dynamic_followers(rng, op, result, tr, draw):
+    """What the dynamic profile plays right behind a dynamic op, an async query or (for some of them) a frame."""
+    pick = lambda names: names[int(rng.integers(len(names)))]
+    k, r = op[0], rng.random()
+
+    def device_heap(*kinds):
+        return lambda: ("device_heap", draw(pick(kinds)))
+
+    if k == "frame" and r < 0.3:                                 # a device build inside what would be one batch, an earlier present read back
+        build = pick((device_heap("move_mesh", "move_spheres"), device_heap("set_host", "deform"), device_heap("morph", "skin"),
+                      lambda: draw("rebuild_heap")))
+        return [("frame", "X0"), build, ("frame", None)] + ([("read_begin", "X0", pick(FORMATS))] if rng.random() < 0.5 else [])
+    if k == "frame" and r < 0.5:                                 # depth of field of what the deferred frame wrote
+        if rng.random() < 0.4:
+            return tr.prerequisites(("dof", "C", "Gh", tr.result, 0)) + [("dof", "C", "Gh", tr.result, int(rng.integers(len(DOF)))), ("frame", None)]
+        dst = pick(("X0", "X1", "U"))
+        return [("aov", "G", 15, False), ("frame", None), ("dof", pick(("C", tr.result)), "Gh", dst, int(rng.integers(len(DOF))))]
+    if k == "frame" and r < 0.62:                                # the master's ToneMap with depth of field on, then the next frame
+        dest = pick((None, "X0", "X1"))
+        return [("master_dof", int(rng.integers(len(DOF)))), ("master_bloom", bool(rng.random() < 0.5)), ("present_tm", dest, pick(TONEMAP_OPS)),
+                ("frame", None)] + ([("get", "TM")] if dest is None else [("read_begin", dest, "RGBA8_SRGB")])
+    if k in ("ray_query_async", "radiance_async") and r < 0.7:   # the query is left waiting across a device build
+        return [pick((device_heap("deform", "set_host"), device_heap("move_mesh"), device_heap("morph", "skin")))] + \
+               ([("frame", None)] if rng.random() < 0.5 else [])
+    if k == "morph" and r < 0.45:                                # the host rewrites W while the first kernel may still wait for its turn
+        j = (op[1] + 1 + int(rng.integers(len(MORPH_WEIGHTS) - 1))) % len(MORPH_WEIGHTS)
+        return [("morph", j, op[2], op[3])] + ([("frame", None)] if rng.random() < 0.6 else [("get_buffer", "V", 0, 64)])
+    if k == "morph" and r < 0.75:
+        return [pick((("rebuild_heap", 0), ("frame", None), ("get_buffer", "V", 0, 64)))]
+    if k in ("skin", "set_host", "deform") and r < 0.4:
+        return [("rebuild_heap", 0)] + ([("frame", None)] if rng.random() < 0.6 else [])
+    if k in ("device_heap", "rebuild_heap"):
+        kind = heap_kind(op[1]) if k == "device_heap" else op[1]
+        heap, leaves = ("HS", "LS") if kind else ("HM", "LM")
+        n = dynamic_world()["counts"]
+        if r < 0.35:
+            return [("frame", pick((None, "X0")))]
+        if r < 0.6:                                              # the SyncObjectHeaps download
+            return [pick((("get_buffer", heap, 0, n[heap]), ("get_buffer", heap, 1, 2), ("get_buffer", leaves, 0, n[leaves]))), ("frame", None)]
+        if r < 0.85:                                             # the host writes the heap that the device has just written
+            return [(lambda: draw("move_spheres")) if kind else pick((lambda: draw("move_mesh"), lambda: draw("set_host"), lambda: draw("morph")))] + \
+                   ([("frame", None)] if rng.random() < 0.7 else [])
+        return []
+    if k == "dof":
+        if size_class(op[3]) == 2 and r < 0.6:                   # the scratch grows: a frame-sized call behind one on the low grid
+            return tr.prerequisites(("dof", "C", "Gh", "X0", 0)) + [("frame", None), ("dof", "C", "Gh", pick(("X0", "X1")), int(rng.integers(len(DOF))))]
+        if op[3] != tr.result and r < 0.7:                       # the destination is bound as the sky and traced at once
+            return _sky_and_frame(op[3])
+        if op[3] == tr.result and r < 0.8:
+            return [("frame", None)]
+    return []
+
+
+def make_dynamic_program(seed, n_ops=40):
+    """As make_display_program, over DYN_KINDS (what follows an op of the older profiles is mostly what follows it there).  The bias of
+    the dynamic ops: a device build of a heap sits between two frames of what would be one batch, behind a host upload of vertices, a
+    morph or a skin, with an async query left waiting across it; the heap it wrote is read back or overwritten by the host at once; a
+    morph follows a morph under another weight table; depth of field reads what a deferred frame wrote, writes the bound Result or
+    the next sky, and a frame-sized call follows one on the low grid; the master's ToneMap with depth of field on is followed by a frame."""
+    rng = np.random.default_rng(300000 + seed)
+    w = dynamic_world()
+    lo, hi = w["span"]
+    nv = len(w["rest_v"])
+    kinds = list(_DYNAMIC_WEIGHTS)
+    p = np.array([_DYNAMIC_WEIGHTS[k] for k in kinds], dtype=np.float64)
+    p /= p.sum()
+    tr, prog, forced = _DynamicTrack(), [], []
+
+    def emit(op):
+        tr.apply(op)
+        prog.append(op)
+
+    def draw(kind):
+        return _draw_dynamic(rng, kind, tr, nv, (lo, hi))
+
+    while len(prog) < n_ops or forced:
+        if forced:
+            op = forced.pop(0)
+            if callable(op):
+                op = op()
+            drawn = op[0] == "drawn"
+            op = op[1] if drawn else op
+            if not tr.allowed(op):
+                continue
+        else:
+            op, drawn = draw(kinds[int(rng.choice(len(kinds), p=p))]), True
+            if not tr.allowed(op):
+                continue
+            if tr.prerequisites(op):
+                forced = tr.prerequisites(op) + [("drawn", op)]
+                continue
+        result = tr.result
+        emit(op)
+        if not drawn:
+            continue
+        k = op[0]
+        if k in DYNAMIC_KINDS or (k in ("frame", "ray_query_async", "radiance_async", "morph", "skin", "set_host", "deform") and rng.random() < 0.5):
+            forced = _dynamic_followers(rng, op, result, tr, draw)
+        elif k in DISPLAY_KINDS or (k == "frame" and rng.random() < 0.6):
+            forced = _display_followers(rng, op, result, tr)
+        else:
+            forced = _pipeline_followers(rng, op, result, tr, draw, (lo, hi), nv)
+    while tr.tickets:
+        emit(("read_end",))
+    return prog
+
+
+def dynamic_coverage(program):
+    """Static facts about a program of the dynamic profile (tests/test_command_stream_model.py holds the seed set to them).  A DEVICE BUILD
+    is a device_heap or a rebuild_heap op; "quiet" ops are the ones of display_coverage and the dynamic ones but dof (a device build
+    and a morph enqueue on the context's stream and leave the deferred frames deferred).  A heap is DEVICE-WRITTEN from its device
+    build until something takes it: the next op that prepares the scene, a get_buffer of it, or a host SetData of it.
+    kinds: op kind -> count (a wrapped edit counts as device_heap);
+    build_between_frames: device builds with a deferred frame in front of them and a frame directly behind;
+    build_behind_upload / build_behind_morph_or_skin: device builds whose vertices were last written by deform / set_host, or by morph /
+    skin, since the scene was last prepared (the wrapped edit included);
+    host_write_of_device_heap: host SetData of a heap (an unwrapped edit of its kind) while it is device-written;
+    get_device_heap: get_buffer of HM / HS while it is device-written;
+    morph_after_morph: a morph directly behind a morph with another weight table;
+    async_across_build: device builds reached while an async query has not been observed;
+    dof_input_deferred: dof ops whose source or hit was written by frames that could still be deferred;
+    dof_into_result: dof ops that write the bound Result texture, with a frame after them;
+    dof_regrow: frame-sized dof ops behind a dof on the low grid and before any other frame-sized one;
+    master_dof_then_frame: present_tm with depth of field on whose next op that is not a binding is a frame;
+    dof_sky_traced: dof destinations bound as the sky after the write and traced before anything else wrote them."""
+    kinds = {k: 0 for k in DYN_KINDS}
+    tr = _DynamicTrack()
+    neutral = ("restart", "bind_sky", "bind_result", "camera", "master_bloom", "master_dof")
+    quiet = neutral + ("frame", "dispatch", "snapshot", "ray_query_async", "radiance_async", "morph", "device_heap", "rebuild_heap") + SCENE_CHANGES
+    prepares = ("frame", "dispatch", "aov", "aov_into", "aov_low", "ray_query", "radiance_query", "radiance_pixels", "resample", "ray_query_async",
+                "radiance_async", "present_tm")
+    out = {key: 0 for key in ("build_between_frames", "build_behind_upload", "build_behind_morph_or_skin", "host_write_of_device_heap",
+                              "get_device_heap", "morph_after_morph", "async_across_build", "dof_input_deferred", "dof_into_result", "dof_regrow",
+                              "master_dof_then_frame", "dof_sky_traced")}
+    deferred, pending, async_open, vertex_writer, device_written = set(), 0, False, None, [False, False]
+    last_writer, write_at, bound_at, counted, low_dof_open = {}, {}, -1, set(), False
+    frames_after = np.cumsum([op[0] in ("frame", "dispatch") for op in program][::-1])[::-1]
+    for i, op in enumerate(program):
+        k = op[0]
+        kinds[k] += 1
+        result = tr.result if k != "dispatch" else op[1]
+        edit = op[1] if k == "device_heap" else op if k in DEVICE_EDITS else None
+        following = [q[0] for q in program[i + 1:] if q[0] not in neutral][:1]
+        if edit is not None and edit[0] in ("deform", "set_host"):
+            vertex_writer = "upload"
+        elif edit is not None and edit[0] in ("morph", "skin"):
+            vertex_writer = "device"
+        if k in ("device_heap", "rebuild_heap"):
+            kind = heap_kind(op[1]) if k == "device_heap" else op[1]
+            out["build_between_frames"] += bool(pending > 0 and program[i + 1: i + 2] and program[i + 1][0] == "frame")
+            out["build_behind_upload"] += bool(kind == 0 and vertex_writer == "upload")
+            out["build_behind_morph_or_skin"] += bool(kind == 0 and vertex_writer == "device")
+            out["async_across_build"] += bool(async_open)
+            device_written[kind] = True
+        elif edit is not None:                                   # an unwrapped edit: the host writes the heap of its kind
+            out["host_write_of_device_heap"] += bool(device_written[heap_kind(edit)])
+            device_written[heap_kind(edit)] = False
+        if k == "get_buffer" and op[1] in ("HM", "HS"):
+            out["get_device_heap"] += bool(device_written[op[1] == "HS"])
+            device_written[op[1] == "HS"] = False
+        if k == "morph":
+            before = program[i - 1] if i else ("",)
+            out["morph_after_morph"] += bool(before[0] == "morph" and MORPH_WEIGHTS[before[1]] != MORPH_WEIGHTS[op[1]])
+        if k == "dof":
+            frame_sized = size_class(op[3]) == 0
+            out["dof_input_deferred"] += bool(deferred & set(dynamic_reads_of(op, result)))
+            out["dof_into_result"] += bool(op[3] == tr.result and frames_after[i] > 0)
+            out["dof_regrow"] += bool(frame_sized and low_dof_open)
+            low_dof_open = not frame_sized
+        if k == "present_tm":
+            out["master_dof_then_frame"] += bool(tr.master_dof is not None and following == ["frame"])
+        if k in ("frame", "dispatch") and tr.sky in last_writer and bound_at > write_at[tr.sky] and (tr.sky, write_at[tr.sky]) not in counted:
+            counted.add((tr.sky, write_at[tr.sky]))
+            out["dof_sky_traced"] += last_writer[tr.sky] == "dof"
+        # the state after the op
+        if k in OBSERVERS:
+            async_open = False
+        if k in ("ray_query_async", "radiance_async"):
+            async_open = True
+        if k in prepares:
+            vertex_writer, device_written = None, [False, False]
+        if k in ("frame", "dispatch"):
+            pending += 1
+            deferred |= {t for t, _ in writes_of(op, result)}
+        elif k not in quiet:
+            pending, deferred = 0, set()
+        for t, wk in dynamic_writes_of(op, result):
+            last_writer[t], write_at[t] = wk, i
+        if k == "bind_sky":
+            bound_at = i
+        tr.apply(op)
+    out["kinds"] = kinds
+    return out
 
 
 def display_coverage(program):
@@ -1081,20 +1485,42 @@ def ray_hits(orc, o, d):
     return out
 
 
-def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frames", stats=None):
+def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frames", stats=None, stale_builds=()):
     """-> (observations, final contents): observations is a list of (op index, kind, array | None), final a dict name -> array.
     profile="pipeline": the world and the ops of that profile (final holds the buffers too, under "V", "V.dev", ...: both sides of a
     buffer hold the same in program order); stats, a list, receives (op index, kind, figures) of the reproject / denoise / select /
     resample ops — what tests/test_command_stream_model.py measures non-vacuity on.
     profile="display": the world and the ops of that profile on top (final holds the exposure states "E0", "E1" and the master's "MS" as
-    state_words, and "TM"; stats receives the figures of the upsample and meter ops, too)."""
+    state_words, and "TM"; stats receives the figures of the upsample and meter ops, too).
+    profile="dynamic": the world and the ops of that profile on top (final holds "DH" and both sides of W, LM, LS, HM, HS, the stride-28
+    ones as heap_words; stats receives the figures of the morph and dof ops, too).  stale_builds: op indices of device builds that leave
+    the heap and the leaves as they were — the non-vacuity probe of tests/test_command_stream_model.py, not a thing the library does."""
     from oracle import pyoracle
     from reproject_ref import blit_add_history_ref
-    assert profile in ("frames", "pipeline", "display"), profile
-    display = profile == "display"
+    assert profile in ("frames", "pipeline", "display", "dynamic"), profile
+    dynamic = profile == "dynamic"
+    display = profile == "display" or dynamic
     pipeline = profile == "pipeline" or display
     sc = make_scene(width, height, bounces)
-    tex = {n: np.zeros((height, width, 4), F) for n in FRAME_TEX + (PIPE_TEX if pipeline else ()) + (UP_TEX + ("TM",) if display else ())}
+    tex = {n: np.zeros((height, width, 4), F) for n in FRAME_TEX + (PIPE_TEX if pipeline else ()) + (UP_TEX + ("TM",) if display else ()) +
+           (("DH",) if dynamic else ())}
+    if dynamic:
+        import dof_ref
+        weights, master_dof = np.zeros(N_TARGETS, F), None
+        leaves = [np.zeros(len(sc.mesh_objects), scenes.BVHNODE_DT), np.zeros(len(sc.spheres), scenes.BVHNODE_DT)]
+
+        def device_build(i, kind, old):
+            """The heap of `kind` built from the lists of sc; a stale build keeps the heap of the scene `old` (and the leaves)."""
+            nonlocal sc
+            sc = copy.copy(sc)
+            if i in stale_builds:
+                sc.mesh_bvh, sc.sphere_bvh = old.mesh_bvh, old.sphere_bvh
+                return
+            leaves[kind], heap = device_heap_of(sc, kind)
+            setattr(sc, "sphere_bvh" if kind else "mesh_bvh", heap)
+
+        def heap_buffers():
+            return {"LM": leaves[0], "LS": leaves[1], "HM": sc.mesh_bvh, "HS": sc.sphere_bvh}
     if display:
         import bloom_ref
         import tonemap_ref
@@ -1115,11 +1541,18 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
         s.num_rays = num_rays
         return pyoracle.Oracle(s)
 
-    def aov(frame_ray=False, size=None):
+    def aov(frame_ray=False, size=None, sample_centres=False):
         from aov_ref import camera_rays
         orc = oracle()
         uniforms = (*frame_uniforms_of(sc, frame)[0], frame_uniforms_of(sc, frame)[1]) if frame_ray else None
-        O, D = camera_rays(orc.scene, *(size or (width, height)), uniforms)
+        cam = orc.scene
+        if sample_centres:                                       # RayTraceMaster._sample_centre_projection: the uv moved by half a pixel
+            w, h = size or (width, height)
+            p = np.array(cam.camera_inverse_projection, F).reshape(16).copy()
+            p[12:16] += p[0:4] * F(1.0 / w) + p[4:8] * F(1.0 / h)
+            cam = copy.copy(cam)
+            cam.camera_inverse_projection = p
+        O, D = camera_rays(cam, *(size or (width, height)), uniforms)
         return orc.aov(np.broadcast_to(O, D.shape), D)
 
     def exposure_of(k):
@@ -1136,6 +1569,32 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
         if pipeline and k in OBSERVERS:                          # what the async queries answered is looked at now
             obs += waiting
             waiting = []
+        if dynamic and (k in DYNAMIC_KINDS or (k == "get_buffer" and op[1] in HEAP_BUFFERS)):
+            if k == "morph":
+                before = np.array(sc.vertices, F).reshape(-1, 3)
+                weights = np.array(MORPH_WEIGHTS[op[1]], F)
+                sc = edited_scene(sc, op)
+                stats.append((i, k, {"moved": int((np.asarray(sc.vertices, F).reshape(-1, 3) != before).any(axis=1).sum())}))
+            elif k == "device_heap":
+                old = sc
+                if op[1][0] == "morph":
+                    weights = np.array(MORPH_WEIGHTS[op[1][1]], F)
+                sc = edited_scene(sc, op[1])
+                sc.mesh_bvh, sc.sphere_bvh = old.mesh_bvh, old.sphere_bvh      # the edit without its host SetData of the heap ...
+                device_build(i, heap_kind(op[1]), old)                           # ... and the heap built where the buffers live
+            elif k == "rebuild_heap":
+                device_build(i, op[1], sc)
+            elif k == "dof":
+                _, src, hit, dst, j = op
+                out = dof_ref.dof_ref(tex[src], tex[hit], **DOF[j])
+                same_px = (out.view(np.uint32) == np.asarray(tex[src], F).view(np.uint32)).all(axis=-1)
+                stats.append((i, k, {"changed": int((~same_px).sum()), "identical": int(same_px.sum())}))
+                tex[dst] = out
+            elif k == "master_dof":
+                master_dof = op[1]
+            elif k == "get_buffer":
+                obs.append((i, k, heap_words(heap_buffers()[op[1]][op[2]: op[2] + op[3]])))
+            continue
         if display and k in DISPLAY_KINDS:
             if k == "aov_low":
                 tex["Lh"], tex["Lm"], tex["Lc"], tex["Li"] = aov(op[1], low_size(width, height))
@@ -1165,9 +1624,15 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
             elif k == "present_tm":                              # RayTraceMaster.ToneMap: the three explicit calls on the master's state
                 dest = op[1] or "TM"
                 states["MS"] = tonemap_ref.auto_exposure_ref(tex["C"], None, states["MS"], **MASTER_EXPOSURE)
+                source = "C"
+                if dynamic and master_dof is not None:           # the hit guide through the sample centres, then the blur into dest
+                    tex["DH"] = aov(sample_centres=True)[0]
+                    tex[dest] = dof_ref.dof_ref(tex["C"], tex["DH"], **DOF[master_dof])
+                    source = dest
                 if master_bloom:
-                    bloom("C", dest, "MS", **MASTER_BLOOM)
-                tone_map("C" if not master_bloom else dest, dest, "MS", op[2])
+                    bloom(source, dest, "MS", **MASTER_BLOOM)
+                    source = dest
+                tone_map(source, dest, "MS", op[2])
             continue
         if pipeline and k in NEW_KINDS + ("radiance_query",):
             if k == "aov":
@@ -1289,6 +1754,10 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
             tex[name] = tex[name + ".dev"] = np.array(np.asarray(a, F).reshape(-1, 3))
     if display:
         tex.update({name: state_words(s) for name, s in states.items()})
+    if dynamic:
+        tex["W"] = tex["W.dev"] = weights
+        for name, a in heap_buffers().items():
+            tex[name] = tex[name + ".dev"] = heap_words(a)
     return obs, tex
 
 
@@ -1321,13 +1790,13 @@ class _PipelineWorld:
         self.plan = ctx.normals_plan(self.V, m._indexBuffer, lo, hi - lo + 1)
         self.keep = []                                           # torch tensors the library may still read or write
 
-    def both_sides(self, b):
-        """(GetData of the whole buffer, what a device-to-device copy of it holds)."""
-        host = b.GetData().view(F).reshape(-1, 3)
+    def both_sides(self, b, view=lambda raw: raw.view(F).reshape(-1, 3)):
+        """(GetData of the whole buffer, what a device-to-device copy of it holds), each through `view`."""
+        host = view(b.GetData())
         scratch = self.ComputeBuffer(self.ctx, b.count, b.stride)
         try:
             scratch.CopyFrom(b)
-            return host, scratch.GetData().view(F).reshape(-1, 3)
+            return host, view(scratch.GetData())
         finally:
             scratch.Release()
 
@@ -1338,14 +1807,53 @@ class _PipelineWorld:
             b.Release()
 
 
+class _DynamicWorld(_PipelineWorld):
+    """... and what the dynamic profile adds (dynamic_world holds the contents): the morph plan, W, the leaf buffers, and the two bound
+    heap buffers under their names."""
+
+    def __init__(self, ctx, m, width, height):
+        super().__init__(ctx, m, width, height)
+        w = dynamic_world(width, height)
+        lo, hi = w["span"]
+        self.morph_plan = ctx.morph_plan(w["deltas"], N_TARGETS, lo, hi - lo + 1)
+        n = w["counts"]
+        self.W = self.made_buffer(N_TARGETS, 4, np.zeros(N_TARGETS, F))
+        self.LM = self.made_buffer(n["LM"], 28, np.zeros(n["LM"], scenes.BVHNODE_DT))
+        self.LS = self.made_buffer(n["LS"], 28, np.zeros(n["LS"], scenes.BVHNODE_DT))
+        self.HM, self.HS = m._meshObjectBVHBuffer, m._sphereBVHBuffer
+        assert (self.HM.count, self.HS.count) == (n["HM"], n["HS"])
+
+    def made_buffer(self, count, stride, data):
+        b = self.ComputeBuffer(self.ctx, count, stride)
+        self.made.append(b)
+        b.SetData(data)
+        return b
+
+    def device_build(self, m, kind):
+        """The heap of kind 0 | 1 built where the buffers live: leaf boxes, then the heap into the bound heap buffer's device side."""
+        if kind == 0:
+            self.ctx.mesh_leaf_bounds(m._meshObjectBuffer, self.V, m._indexBuffer, self.LM)
+            self.ctx.build_object_bvh(self.LM, self.HM)
+        else:
+            self.ctx.sphere_leaf_bounds(m._sphereBuffer, self.LS)
+            self.ctx.build_object_bvh(self.LS, self.HS)
+
+    def release(self):
+        if self.morph_plan.handle:
+            self.morph_plan.Release()
+        super().release()
+
+
 def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=40, bounces=2, profile="frames", probe=None):
     """The program through the Python API -> (observations, final contents, counters, [(op index, launch_info()) after every op of SUBMITTING]).
     probe(op index, op, master, the pipeline profile's buffers | None) is called after every op: for protocols that look at the
     library's own bookkeeping (it must not call anything that submits or waits, or the run is no longer the program's).
-    profile="display": as in run_model; the states are read at the end through Context.exposure_state."""
+    profile="display": as in run_model; the states are read at the end through Context.exposure_state.
+    profile="dynamic": as in run_model (the probe's last argument is then a _DynamicWorld, with W, LM, LS, HM and HS)."""
     from unityraytracer_amd import Graphics, RayTraceMaster, RenderTexture
-    assert profile in ("frames", "pipeline", "display"), profile
-    display = profile == "display"
+    assert profile in ("frames", "pipeline", "display", "dynamic"), profile
+    dynamic = profile == "dynamic"
+    display = profile == "display" or dynamic
     pipeline = profile == "pipeline" or display
     ctx.set_option("kernel_mode", 3)
     ctx.set_option("frames_per_launch", frames_per_launch)
@@ -1366,9 +1874,10 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
         if pipeline:
             import torch
             from unityraytracer_amd import host_scene
-            pw = _PipelineWorld(ctx, m, width, height)
+            pw = (_DynamicWorld if dynamic else _PipelineWorld)(ctx, m, width, height)
             dev = torch.device("cuda", ctx.device)
             bufs = {"V": pw.V, "NB": pw.NB, "SNAP": pw.SNAP}
+            heap_bufs = {n: getattr(pw, n) for n in HEAP_BUFFERS} if dynamic else {}
         if display:
             states = [torch.zeros(STATE_WORDS, dtype=torch.int32, device=dev) for _ in STATES]
             m.EnableAutoExposure(**MASTER_EXPOSURE)
@@ -1385,10 +1894,67 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
                     obs.append((j, kind, out.cpu().numpy()))
                 del waiting[:]
 
+        def vertex_edit(op, host_heap=True):
+            """An op of VERTEX_WRITES or a morph, with (the ops as the older profiles know them) or without the host SetData of the heap."""
+            k = op[0]
+            new = edited_scene(m.scene, op)
+            if k == "skin":
+                ctx.skin_vertices(*pw.skin, pw.bones[op[1]], op[3], op[4], pw.V, pw.NB if op[2] else None)
+            elif k == "normals":
+                pw.plan.compute(pw.NB)
+            elif k == "morph":
+                pw.W.SetData(np.array(MORPH_WEIGHTS[op[1]], F))
+                pw.morph_plan.morph(pw.skin[0], pw.skin[1] if op[2] else None, pw.W, pw.V, pw.NB if op[2] else None, op[3])
+            else:
+                part = np.ascontiguousarray(np.asarray(new.vertices, F).reshape(-1, 3)[op[1]: op[1] + op[2]])
+                if k == "set_device":
+                    t = torch.from_numpy(part).to(dev)
+                    pw.keep.append(t)                    # (the copy is only enqueued)
+                    pw.V.SetDataDevice(t, op[1], op[2])
+                else:
+                    pw.V.SetData(part, 0, op[1], op[2])
+            if k != "normals" and host_heap:
+                m._meshObjectBVHBuffer.SetData(new.mesh_bvh)
+            m.scene = new
+
+        def object_edit(op, host_heap=True):
+            """move_mesh, deform, move_spheres or camera, likewise."""
+            k = op[0]
+            new = edited_scene(m.scene, op)
+            if k == "move_mesh":
+                m._meshObjectBuffer.SetData(new.mesh_objects)
+            elif k == "deform":
+                lo, hi = blob_span(new)
+                m._vertexBuffer.SetData(np.ascontiguousarray(new.vertices[lo: hi + 1]), 0, lo, hi - lo + 1)
+            elif k == "move_spheres":
+                m._sphereBuffer.SetData(new.spheres)
+            if host_heap and k in ("move_mesh", "deform"):
+                m._meshObjectBVHBuffer.SetData(new.mesh_bvh)
+            elif host_heap and k == "move_spheres":
+                m._sphereBVHBuffer.SetData(new.sphere_bvh)
+            m.scene = new
+
         for i, op in enumerate(program):
             k = op[0]
             if pipeline and k in OBSERVERS:
                 drain()
+            if dynamic and (k in DYNAMIC_KINDS or (k == "get_buffer" and op[1] in HEAP_BUFFERS)):
+                if k == "morph":
+                    vertex_edit(op)
+                elif k == "device_heap":
+                    (vertex_edit if op[1][0] in VERTEX_WRITES + ("morph",) else object_edit)(op[1], host_heap=False)
+                    pw.device_build(m, heap_kind(op[1]))
+                elif k == "rebuild_heap":
+                    pw.device_build(m, op[1])
+                elif k == "dof":
+                    ctx.depth_of_field(tex[op[1]], tex[op[2]], tex[op[3]], **DOF[op[4]])
+                elif k == "master_dof":
+                    m.EnableDepthOfField(**DOF[op[1]]) if op[1] is not None else m.DisableDepthOfField()
+                elif k == "get_buffer":
+                    obs.append((i, k, heap_words(heap_bufs[op[1]].GetData(op[2], op[3]))))
+                if probe:
+                    probe(i, op, m, pw)
+                continue
             if display and k in DISPLAY_KINDS:
                 state = states[op[3]] if k in ("tonemap", "bloom") and op[3] is not None else None
                 if k == "aov_low":
@@ -1473,22 +2039,7 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
                         ctx.check(ctx.lib.urt_radiance_query_device(ctx._h, d_rays.data_ptr(), N_QUERIES, 1, bounces, d_out.data_ptr(), 0))
                     waiting.append((i, k, d_out, d_rays))        # not waited for
                 elif k in VERTEX_WRITES:
-                    new = edited_scene(m.scene, op)
-                    if k == "skin":
-                        ctx.skin_vertices(*pw.skin, pw.bones[op[1]], op[3], op[4], pw.V, pw.NB if op[2] else None)
-                    elif k == "normals":
-                        pw.plan.compute(pw.NB)
-                    else:
-                        part = np.ascontiguousarray(np.asarray(new.vertices, F).reshape(-1, 3)[op[1]: op[1] + op[2]])
-                        if k == "set_device":
-                            t = torch.from_numpy(part).to(dev)
-                            pw.keep.append(t)                    # (the copy is only enqueued)
-                            pw.V.SetDataDevice(t, op[1], op[2])
-                        else:
-                            pw.V.SetData(part, 0, op[1], op[2])
-                    if k != "normals":
-                        m._meshObjectBVHBuffer.SetData(new.mesh_bvh)
-                    m.scene = new
+                    vertex_edit(op)
                 elif k == "snapshot":
                     pw.SNAP.CopyFrom(pw.V)
                 elif k == "get_buffer":
@@ -1521,18 +2072,7 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
             elif k == "bind_result":
                 m._target = tex["T1"] if m._target is tex["T0"] else tex["T0"]
             elif k in ("move_mesh", "deform", "move_spheres", "camera"):
-                new = edited_scene(m.scene, op)
-                if k == "move_mesh":
-                    m._meshObjectBuffer.SetData(new.mesh_objects)
-                    m._meshObjectBVHBuffer.SetData(new.mesh_bvh)
-                elif k == "deform":
-                    lo, hi = blob_span(new)
-                    m._vertexBuffer.SetData(np.ascontiguousarray(new.vertices[lo: hi + 1]), 0, lo, hi - lo + 1)
-                    m._meshObjectBVHBuffer.SetData(new.mesh_bvh)
-                elif k == "move_spheres":
-                    m._sphereBuffer.SetData(new.spheres)
-                    m._sphereBVHBuffer.SetData(new.sphere_bvh)
-                m.scene = new
+                object_edit(op)
             elif k == "flush":
                 ctx.flush()
             elif k == "ptr":
@@ -1574,6 +2114,11 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
             final["TM"] = m._tonemapped.GetPixels() if m._tonemapped is not None else np.zeros((height, width, 4), F)
             for name, t in zip(STATES + ("MS",), states + [m._exposureState]):
                 final[name] = state_words(ctx.exposure_state(t))
+        if dynamic:
+            final["DH"] = m._dofHit.GetPixels() if m._dofHit is not None else np.zeros((height, width, 4), F)
+            final["W"], final["W.dev"] = pw.both_sides(pw.W, lambda raw: raw.view(F).reshape(-1))
+            for name, b in heap_bufs.items():
+                final[name], final[name + ".dev"] = pw.both_sides(b, heap_words)
         return obs, final, ctx.counters(), infos
     finally:
         ctx.set_option("frames_per_launch", 0)

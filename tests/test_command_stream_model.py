@@ -6,7 +6,10 @@ passing by never feeding an image operation what deferred frames wrote, never wr
 editing the scene behind an un-waited query, or by reprojecting, selecting and denoising images in which nothing happens — and
 tests/test_gpu_command_stream_display.py from passing by never metering, blooming, tone-mapping or upsampling what deferred frames
 wrote, never chaining an exposure state un-waited, never writing the bound Result texture or the next sky with a display call, never
-regrowing the bloom pyramid, or by metering images in which nothing counts."""
+regrowing the bloom pyramid, or by metering images in which nothing counts — and tests/test_gpu_command_stream_dynamic.py from
+passing by never building a heap on the device between deferred frames, behind an upload, a morph or an un-waited query, never reading
+back or overwriting a device-written heap, never morphing twice in a row, never blurring what deferred frames wrote, or by heaps,
+weights and blurs that change nothing of what is compared."""
 import numpy as np
 import pytest
 
@@ -80,6 +83,8 @@ F = np.float32
 FRAME_PROGRAMS_DIGEST = "770ff5c6ab1c8963024ba34dadfc434fbea4f3047bc31b8d365e4f72afb1fb99"
 # ... and of repr([make_program(seed, profile="pipeline") for seed in range(24)]), computed on the commit before the display profile existed
 PIPELINE_PROGRAMS_DIGEST = "ac84caddba71acdb56696727b1c59ba88ad9c0c1ea2d81fb6d7fe377db2341cb"
+# ... and of repr([make_program(seed, profile="display") for seed in range(24)]), computed on the commit before the dynamic profile existed
+DISPLAY_PROGRAMS_DIGEST = "63f148d9def3cd1d403ffa6a9b1770aa3091c52cc5a956935e9328b74ceb8c84"
 
 
 def pipeline(ops, **kw):
@@ -95,6 +100,10 @@ def test_the_frame_loop_programs_are_what_they_were():
     piped = [cs.make_program(seed, profile="pipeline") for seed in SEEDS]
     assert hashlib.sha256(repr(piped).encode()).hexdigest() == PIPELINE_PROGRAMS_DIGEST
     assert not any(op[0] in cs.DISPLAY_KINDS for p in piped for op in p)
+    displayed = [cs.make_program(seed, profile="display") for seed in SEEDS]
+    assert hashlib.sha256(repr(displayed).encode()).hexdigest() == DISPLAY_PROGRAMS_DIGEST
+    for p in programs + piped + displayed:                       # no older program holds a dynamic kind, or a buffer only that profile has
+        assert not any(op[0] in cs.DYNAMIC_KINDS or (op[0] == "get_buffer" and op[1] in cs.HEAP_BUFFERS) for op in p)
 
 
 def pipeline_op_keeps_to_the_rules(seed, op, tr, names=cs.ALL_TEX + cs.PIPE_TEX):
@@ -179,7 +188,14 @@ CHANGED = {"meter": lambda op: op[:2] + (1 - op[2],) + op[3:],                  
            "upsample": lambda op: op[:4] + (op[4] ^ cs.SKY_FROM_ALBEDO,)}
 
 
-def test_the_comparison_notices_one_changed_op(pipeline_models, display_models):
+DYNAMIC_CHANGED = {"morph": lambda op: ("morph", (op[1] + 1) % len(cs.MORPH_WEIGHTS)) + op[2:],        # another weight table
+                   "dof": lambda op: op[:4] + ((op[4] + 1) % len(cs.DOF),),                              # another preset
+                   "device_heap": lambda op: ("device_heap", ("move_mesh", 1, 1) if op[1] != ("move_mesh", 1, 1) else ("move_mesh", 1, 0)),
+                   "rebuild_heap": lambda op: ("rebuild_heap", 1 - op[1]),                               # the other kind's heap
+                   "master_dof": lambda op: ("master_dof", 0 if op[1] is None else None)}              # on / off
+
+
+def test_the_comparison_notices_one_changed_op(pipeline_models, display_models, dynamic_models):
     """first_difference is not vacuous: leaving out one op that writes (the first of its kind in the program) shows, for most kinds at
     the very observation or texture it feeds — and so does changing one argument of one display call (the last of its kind in the
     program: what it writes is least likely to be overwritten)."""
@@ -214,6 +230,18 @@ def test_the_comparison_notices_one_changed_op(pipeline_models, display_models):
                 noticed[kind] = True
     print("kinds whose removal the comparison noticed:", sorted(noticed))
     assert len(noticed) >= 7, noticed
+    changed = set()
+    for p, obs, fin, _ in dynamic_models[:8]:
+        for kind, change in DYNAMIC_CHANGED.items():
+            at = [i for i, op in enumerate(p) if op[0] == kind]
+            if not at or kind in changed:
+                continue
+            q = p[:at[-1]] + [change(p[at[-1]])] + p[at[-1] + 1:]
+            assert q != p and len(q) == len(p) and [op[0] for op in q] == [op[0] for op in p]
+            if cs.first_difference(cs.run_model(q, profile="dynamic"), (obs, fin)) is not None:
+                changed.add(kind)
+    print("dynamic kinds of which one changed argument was noticed:", sorted(changed))
+    assert changed == set(DYNAMIC_CHANGED), changed
 
 
 def test_model_of_feature_buffers():
@@ -589,3 +617,282 @@ def test_display_coverage_counts_what_it_says():
     for ((a, ja), (b, jb)), n in pairs.items():                  # another size and both rates below 1
         assert cs.display_coverage([("meter", a, 0, False, ja), ("meter", b, 0, False, jb)])["two_meterings_rate_below_1"] == n, (a, ja, b, jb)
     assert cs.display_coverage([("meter", "C", 0, False, 1), ("meter", "S0", 1, False, 1)])["two_meterings_rate_below_1"] == 0   # two states
+
+
+# ---- the dynamic profile -------------------------------------------------------------------------------------------------------------
+def dynamic(ops, **kw):
+    return cs.run_model(ops, profile="dynamic", **kw)
+
+
+@pytest.fixture(scope="module")
+def dynamic_models():
+    """The model of every dynamic program of the seed set with its figures, made once: [(program, observations, final, stats)]."""
+    out = []
+    for seed in SEEDS:
+        p, stats = cs.make_program(seed, profile="dynamic"), []
+        obs, fin = dynamic(p, stats=stats)
+        out.append((p, obs, fin, stats))
+    return out
+
+
+def test_the_dynamic_world_is_what_the_issue_asks_for():
+    import morph_ref
+    w = cs.dynamic_world()
+    lo, hi = w["span"]
+    _, _, (n_entries, max_valence, n_touched) = morph_ref.plan(w["deltas"], lo, hi - lo + 1)
+    assert cs.N_TARGETS >= 3 and set(w["deltas"]["target"].tolist()) == set(range(cs.N_TARGETS))
+    assert max_valence == cs.N_TARGETS > 1 and 0 < n_touched < hi - lo + 1 and n_entries == len(w["deltas"])      # touched by none, by all
+    assert w["rest_v"] is cs.pipeline_world()["rest_v"]                           # the rest pose is in the buffers the skin ops use
+    assert all(len(t) == cs.N_TARGETS for t in cs.MORPH_WEIGHTS) and not any(cs.MORPH_WEIGHTS[0])
+    assert any(x < 0 for t in cs.MORPH_WEIGHTS for x in t)
+    reaches = [p["max_radius"] for p in cs.DOF]
+    assert any(r <= 4 for r in reaches) and any(4 < r <= 8 for r in reaches) and any(8 < r <= 16 for r in reaches)
+    assert any(p.get("flags", 0) & cs.DOF_FLAG_COC for p in cs.DOF)
+    sc = cs.make_scene()
+    assert w["counts"] == {"LM": len(sc.mesh_objects), "LS": len(sc.spheres), "HM": len(sc.mesh_bvh), "HS": len(sc.sphere_bvh)}
+    from unityraytracer_amd import _lib                            # the heap calls: counts that fit, at most URT_OBJECT_BVH_DEVICE_MAX leaves
+    for leaves, heap in (("LM", "HM"), ("LS", "HS")):
+        assert 0 < w["counts"][leaves] <= _lib.OBJECT_BVH_DEVICE_MAX and w["counts"][heap] == _lib.load().urt_host_object_bvh_length(w["counts"][leaves])
+    assert "normals" not in cs.DEVICE_EDITS and set(cs.DEVICE_EDITS) == set(cs.SCENE_CHANGES) - {"normals"} | {"morph"}
+
+
+def dynamic_op_keeps_to_the_rules(seed, op, tr):
+    """The refusals of urt_depth_of_field, urt_morph_vertices and the three heap calls (include/urt.h), for an op about to run in `tr`."""
+    counts = cs.dynamic_world()["counts"]
+    k = op[0]
+    if k == "morph":                                             # URT_MORPH_NORMALIZE without dst_normals; the weights' count is n_targets
+        _, j, with_normals, normalize = op
+        assert 0 <= j < len(cs.MORPH_WEIGHTS) and len(cs.MORPH_WEIGHTS[j]) == cs.N_TARGETS, (seed, op)
+        assert isinstance(with_normals, bool) and isinstance(normalize, bool) and (with_normals or not normalize), (seed, op)
+    if k == "rebuild_heap":
+        assert op[1] in (0, 1), (seed, op)
+    if k == "dof":                                               # sizes that differ; dst == src, dst == hit, dst the bound sky; the parameters
+        _, src, hit, dst, j = op
+        assert hit in ("Gh", "Ph", "Lh") and src in cs.DISPLAY_EXACT and dst in cs.DISPLAY_EXACT, (seed, op)
+        assert cs.size_class(src) == cs.size_class(hit) == cs.size_class(dst) in (0, 2), (seed, op, "sizes differ")
+        assert dst not in (src, hit) and dst != tr.sky, (seed, op, "the destination is an input or the bound sky")
+        q = dict(focus_distance=10.0, scale=8.0, max_radius=8.0, flags=0)
+        q.update(cs.DOF[j])
+        assert np.isfinite(q["focus_distance"]) and q["focus_distance"] > 0 and np.isfinite(q["scale"]) and q["scale"] >= 0, (seed, op)
+        assert 0.5 <= q["max_radius"] <= 16.0 and q["flags"] in (0, cs.DOF_FLAG_COC), (seed, op)
+    if k == "master_dof":
+        assert op[1] is None or 0 <= op[1] < len(cs.DOF), (seed, op)
+    if k == "present_tm" and tr.master_dof is not None:          # the blur's destination: not C (its source), not the bound sky
+        assert op[1] is None or op[1] not in ("C", tr.sky), (seed, op)
+    if k == "get_buffer" and op[1] in cs.HEAP_BUFFERS:
+        assert 0 <= op[2] and op[3] >= 1 and op[2] + op[3] <= counts[op[1]], (seed, op)
+
+
+def test_dynamic_programs_keep_to_the_rules():
+    assert cs.make_program(3, profile="dynamic") == cs.make_program(3, profile="dynamic") != cs.make_program(4, profile="dynamic")
+    names = cs.DISPLAY_EXACT + ("D",)
+    seen = {"presets": set(), "dof_sizes": set(), "wrapped": set(), "morph_forms": set(), "rebuilt": set(), "buffers": set()}
+    for seed in SEEDS:
+        p = cs.make_program(seed, profile="dynamic")
+        assert 40 <= len(p) <= 60, (seed, len(p))
+        tr = cs._DynamicTrack()
+        for op in p:
+            k = op[0]
+            assert k in cs.DYN_KINDS and tr.allowed(op), (seed, op)
+            for inner in (op, op[1]) if k == "device_heap" else (op,):
+                if inner[0] not in cs.DYNAMIC_KINDS and not (inner[0] == "get_buffer" and inner[1] in cs.HEAP_BUFFERS):
+                    pipeline_op_keeps_to_the_rules(seed, inner, tr, names)
+                dynamic_op_keeps_to_the_rules(seed, inner, tr)
+            if k == "device_heap":                               # the leaves and the heap are never an input of their own build (two buffers each)
+                assert op[1][0] in cs.DEVICE_EDITS and op[1][0] != "normals", (seed, op)
+                seen["wrapped"].add(op[1][0])
+            if k == "dof":
+                seen["presets"].add(op[4])
+                seen["dof_sizes"].add(cs.size_class(op[3]))
+            if k == "morph":
+                seen["morph_forms"].add(op[2:])
+            if k == "rebuild_heap":
+                seen["rebuilt"].add(op[1])
+            if k == "get_buffer":
+                seen["buffers"].add(op[1])
+            tr.apply(op)
+        assert tr.tickets == 0
+    print("seen over the dynamic seed set:", seen)
+    assert seen["presets"] == set(range(len(cs.DOF))) and seen["dof_sizes"] == {0, 2} and seen["wrapped"] == set(cs.DEVICE_EDITS)
+    assert seen["morph_forms"] == {(False, False), (True, False), (True, True)} and seen["rebuilt"] == {0, 1}
+    assert seen["buffers"] >= set(cs.HEAP_BUFFERS) | {"V"}
+
+
+DYNAMIC_CASES = ("build_between_frames", "build_behind_upload", "build_behind_morph_or_skin", "host_write_of_device_heap", "get_device_heap",
+                 "morph_after_morph", "async_across_build", "dof_input_deferred", "dof_into_result", "dof_regrow", "master_dof_then_frame",
+                 "dof_sky_traced")
+
+
+def test_dynamic_seed_set_reaches_the_interesting_cases(dynamic_models):
+    cov = [cs.dynamic_coverage(p) for p, _, _, _ in dynamic_models]
+    kinds = {k: sum(c["kinds"][k] for c in cov) for k in cs.DYN_KINDS}
+    cases = {key: sum(c[key] > 0 for c in cov) for key in DYNAMIC_CASES}
+    print("op kinds over the dynamic seed set:", kinds)
+    print("programs in which ... occurs:", cases)
+    assert all(kinds[k] >= 10 for k in cs.DYNAMIC_KINDS) and all(kinds[k] >= 1 for k in cs.DISP_KINDS), kinds
+    assert all(n >= 3 for n in cases.values()), cases
+    # non-vacuity, on the model's own output
+    stats = [s for _, _, _, st in dynamic_models for s in st]
+    dof = [f for _, k, f in stats if k == "dof"]
+    changing, keeping = sum(f["changed"] >= 1 for f in dof), sum(f["identical"] >= 1 for f in dof)
+    moving = sum(f["moved"] >= 1 for _, k, f in stats if k == "morph")
+    print(f"dof ops that change a pixel of their source: {changing} of {len(dof)}, that leave one bit for bit: {keeping};  morph ops that move "
+          f"a vertex: {moving}")
+    assert 2 * changing >= len(dof) and keeping >= 5 and moving >= 10
+    for p, obs, fin, _ in dynamic_models:                        # both sides of every buffer, the guide and every async answer
+        assert all(n in fin and n + ".dev" in fin for n in cs.DYN_BUFFERS) and "DH" in fin
+        assert all(fin[n].shape[1:] == (7,) and fin[n].dtype == np.uint32 for n in cs.HEAP_BUFFERS)
+        assert sum(op[0].endswith("_async") for op in p) == sum(k.endswith("_async") for _, k, _ in obs)
+
+
+def test_a_stale_heap_shows_in_what_is_compared(dynamic_models):
+    """The heap matters: the model with ONE device build left stale (the edit applied, the old heap and leaves kept) differs in a later
+    observation that is no readback of those buffers, or in a final texture."""
+    images = lambda fin: [n for n in fin if n.split(".")[0] not in cs.DYN_BUFFERS]
+    showing = tried = 0
+    for p, obs, fin, _ in dynamic_models:
+        for at in [i for i, op in enumerate(p) if op[0] == "device_heap"][:2]:
+            if showing >= 12:
+                break
+            tried += 1
+            obs2, fin2 = dynamic(p, stale_builds=(at,))
+            seen = [(a, b) for (_, k, a), (_, _, b) in zip(obs, obs2) if not (k == "get_buffer" and a.dtype == np.uint32)]
+            showing += (not all(cs.same(b, a) for a, b in seen)) or not all(cs.same(fin2[n], fin[n]) for n in images(fin))
+    print(f"device builds whose stale heap shows in a later observation or a final texture: {showing} of {tried} tried")
+    assert showing >= 10
+
+
+def test_model_of_morphing():
+    import morph_ref
+    sc, w = cs.make_scene(), cs.dynamic_world()
+    lo, hi = w["span"]
+    v0, n0 = np.asarray(sc.vertices, F).reshape(-1, 3), np.asarray(sc.normals, F).reshape(-1, 3)
+    # the zero table returns the rest pose to the bit, whatever was there
+    obs, fin = dynamic([("deform", 0.75), ("get_buffer", "V", 0, 144), ("morph", 0, True, False), ("get_buffer", "V", 0, 144)])
+    assert not cs.same(obs[0][2], v0) and cs.same(obs[1][2], v0) and cs.same(fin["V"], v0) and cs.same(fin["NB"], n0) and not fin["W"].any()
+    # a table with a negative weight: the restatement, the weights in W, and the frame shows the pose
+    obs, fin = dynamic([("morph", 2, True, True), ("frame", None), ("get", "T0")])
+    pos, nrm = morph_ref.morph(w["rest_v"], w["rest_n"], w["deltas"], lo, hi - lo + 1, cs.MORPH_WEIGHTS[2], True)
+    assert cs.same(fin["V"][lo: hi + 1], pos) and cs.same(fin["NB"][lo: hi + 1], nrm) and cs.same(fin["V"][hi + 1:], v0[hi + 1:])
+    assert cs.same(fin["W"], np.array(cs.MORPH_WEIGHTS[2], F)) and (pos != v0[lo: hi + 1]).any() and (pos == v0[lo: hi + 1]).all(axis=1).any()
+    assert not cs.same(obs[0][2], oracle_frame(sc, sc.sky, 0))
+    # positions only: the normals stay
+    _, fin = dynamic([("morph", 3, False, False)])
+    assert cs.same(fin["NB"], n0) and not cs.same(fin["V"], v0)
+
+
+def test_model_of_the_device_built_heaps():
+    from unityraytracer_amd import host_scene
+    sc = cs.make_scene()
+    edit = ("move_mesh", 0, 1)
+    moved = cs.edited_scene(sc, edit)
+    leaves = host_scene.mesh_leaf_bounds(moved.mesh_objects, moved.vertices, moved.indices, literal=False)
+    want = cs.heap_words(host_scene.build_object_bvh(leaves))
+    outward = cs.heap_words(scenes.build_object_bvh(*scenes.mesh_bounds(moved.mesh_objects, moved.vertices, moved.indices)))
+    n = cs.dynamic_world()["counts"]
+    obs, fin = dynamic([("device_heap", edit), ("get_buffer", "HM", 0, n["HM"]), ("get_buffer", "LM", 1, 2), ("frame", None), ("get", "T0")])
+    assert cs.same(obs[0][2], want) and cs.same(fin["HM"], want) and cs.same(fin["HM.dev"], want) and cs.same(obs[1][2], cs.heap_words(leaves)[1:3])
+    assert want.shape == outward.shape and (want != outward).any(), "the outward-rounded heap is the same: the model's choice decides nothing"
+    assert cs.same(fin["HS"], cs.heap_words(sc.sphere_bvh)) and not fin["LS"].any()          # the other kind is left alone
+    s = cs.copy.copy(moved)
+    s.mesh_bvh = host_scene.build_object_bvh(leaves)
+    assert cs.same(obs[2][2], oracle_frame(s, sc.sky, 0)) and not cs.same(obs[2][2], oracle_frame(sc, sc.sky, 0))
+    # the host's SetData of the heap after it (an unwrapped edit) brings the outward-rounded values back; a rebuild replaces them again
+    _, fin = dynamic([("device_heap", edit), edit])
+    assert cs.same(fin["HM"], outward) and cs.same(fin["LM"], cs.heap_words(leaves))
+    _, fin = dynamic([edit, ("rebuild_heap", 0), ("rebuild_heap", 1)])
+    assert cs.same(fin["HM"], want) and cs.same(fin["LS"], cs.heap_words(host_scene.sphere_leaf_bounds(sc.spheres)))
+    assert cs.same(fin["HS"], cs.heap_words(host_scene.build_object_bvh(host_scene.sphere_leaf_bounds(sc.spheres))))
+    # a stale build keeps the old heap under the edited lists (the probe of the test above)
+    _, stale = dynamic([("device_heap", edit)], stale_builds=(0,))
+    assert cs.same(stale["HM"], cs.heap_words(sc.mesh_bvh)) and not stale["LM"].any()
+    zeros = np.zeros(2, scenes.BVHNODE_DT)
+    zeros["vmin"][0, 0], zeros["vmax"][1, 2] = -0.0, -0.0
+    assert not cs.heap_words(zeros).any()                        # a zero of either sign is one value
+
+
+def test_model_of_depth_of_field():
+    import dof_ref
+    head = [("frame", None), ("frame", None), ("aov", "G", 15, False)]
+    _, fin = dynamic(head + [("dof", "C", "Gh", "X0", cs.DOF_IN_FOCUS), ("dof", "C", "Gh", "X1", 4), ("aov_low", False), ("dof", "Lc", "Lh", "Ln", 1)])
+    near = cs.dof_foreground(fin["Gh"])
+    assert near.sum() > 100 and (~near).sum() > 100
+    assert cs.same(fin["X0"][near], fin["C"][near]), "the in-focus preset does not leave the foreground's bits"
+    assert (fin["X0"][~near][:, :3] != fin["C"][~near][:, :3]).any() and cs.same(fin["X0"][..., 3], fin["C"][..., 3])
+    assert cs.same(fin["X0"], dof_ref.dof_ref(fin["C"], fin["Gh"], **cs.DOF[cs.DOF_IN_FOCUS]))
+    a = dof_ref.coc_ref(fin["C"], fin["Gh"], **{k: v for k, v in cs.DOF[4].items() if k != "flags"})[0]
+    assert cs.same(fin["X1"][..., 0], a) and cs.same(fin["X1"][..., 3], fin["C"][..., 3]) and a.max() == 8.0 and a[a > 0].min() == 0.5
+    assert fin["Ln"].shape == (16, 24, 4) and cs.same(fin["Ln"], dof_ref.dof_ref(fin["Lc"], fin["Lh"], **cs.DOF[1])) and not cs.same(fin["Ln"], fin["Lc"])
+
+
+def test_model_of_the_masters_tone_map_with_depth_of_field():
+    """present_tm with depth of field on is the four explicit calls behind the guide through the sample centres, and leaves the camera
+    as it was: the frame after it is the frame it would have been."""
+    import aov_ref
+    import dof_ref
+    sc = cs.make_scene()
+    j = 1
+    by_master = [("frame", None), ("master_dof", j), ("master_bloom", True), ("present_tm", "X0", "aces"), ("frame", None), ("present_tm", None, "reinhard"),
+                 ("master_dof", None), ("master_bloom", False), ("present_tm", "X1", "aces"), ("get", "TM")]
+    (obs, a) = dynamic(by_master)
+    s = cs.copy.copy(sc)
+    p = np.array(sc.camera_inverse_projection, F).reshape(16).copy()
+    p[12:16] += p[0:4] * F(1.0 / sc.width) + p[4:8] * F(1.0 / sc.height)
+    s.camera_inverse_projection = p
+    guide = aov_ref.render_aov_ref(s)[0]
+    assert cs.same(a["DH"], guide) and not cs.same(guide, aov_ref.render_aov_ref(sc)[0])
+    # the explicit calls: the guide set by hand into Ph (nothing else writes it), the master's state as E0
+    f0 = oracle_frame(sc, sc.sky, 0)
+    c0 = pyoracle.accumulate(f0, np.zeros_like(f0), 0.0)
+    import bloom_ref
+    import tonemap_ref as tm
+    state = tm.auto_exposure_ref(c0, None, cs.fresh_state(), **cs.MASTER_EXPOSURE)
+    blurred = dof_ref.dof_ref(c0, guide, **cs.DOF[j])
+    bloomed = bloom_ref.bloom_ref(blurred, exposure=state["exposure"], **cs.MASTER_BLOOM)[0]
+    first = tm.tonemap_ref(bloomed, exposure=1.0, op=tm.ACES, state_exposure=state["exposure"])
+    assert not cs.same(blurred, c0) and cs.same(a["X0"], first)
+    c1 = pyoracle.accumulate(oracle_frame(sc, sc.sky, 1), c0, 1.0)
+    assert cs.same(a["C"], c1), "ToneMap changed the accumulated image or the frame behind it"
+    state = tm.auto_exposure_ref(c1, None, state, **cs.MASTER_EXPOSURE)
+    blurred = dof_ref.dof_ref(c1, guide, **cs.DOF[j])
+    bloomed = bloom_ref.bloom_ref(blurred, exposure=state["exposure"], **cs.MASTER_BLOOM)[0]
+    assert cs.same(obs[0][2], tm.tonemap_ref(bloomed, exposure=1.0, op=tm.REINHARD, state_exposure=state["exposure"])) and cs.same(a["TM"], obs[0][2])
+    state = tm.auto_exposure_ref(c1, None, state, **cs.MASTER_EXPOSURE)
+    assert cs.same(a["X1"], tm.tonemap_ref(c1, exposure=1.0, op=tm.ACES, state_exposure=state["exposure"])) and cs.same(a["MS"], cs.state_words(state))
+    # ... and the display profile's model of the same ops without the two dynamic ones is the model with depth of field off
+    plain = [op for op in by_master if op[0] != "master_dof"]
+    assert cs.same(display(plain)[1]["X1"], dynamic(plain)[1]["X1"]) and not cs.same(dynamic(plain)[1]["X0"], a["X0"])
+
+
+def test_dynamic_coverage_counts_what_it_says():
+    """The analysis the seed set is held to, on programs small enough to count by hand."""
+    build = ("device_heap", ("move_mesh", 0, 1))
+    c = cs.dynamic_coverage([("frame", None), build, ("frame", None), ("get", "C")])
+    assert (c["build_between_frames"], c["build_behind_upload"], c["async_across_build"], c["kinds"]["device_heap"], c["kinds"]["move_mesh"]) == (1, 0, 0, 1, 0)
+    c = cs.dynamic_coverage([("frame", None), ("get", "C"), build, ("frame", None)])                          # nothing is deferred in front of it
+    assert c["build_between_frames"] == 0
+    c = cs.dynamic_coverage([("frame", None), build, ("get_buffer", "HM", 0, 7), ("get_buffer", "HM", 0, 7), ("frame", None)])
+    assert (c["build_between_frames"], c["get_device_heap"]) == (0, 1)                                          # (the first readback took it)
+    c = cs.dynamic_coverage([build, ("frame", None), ("get_buffer", "HM", 0, 7), ("move_mesh", 0, 2)])       # the preparation took it
+    assert (c["get_device_heap"], c["host_write_of_device_heap"]) == (0, 0)
+    c = cs.dynamic_coverage([build, ("move_spheres", 1), ("move_mesh", 0, 2), ("move_mesh", 0, 0)])
+    assert c["host_write_of_device_heap"] == 1                                                                  # (the other kind's heap is not it)
+    c = cs.dynamic_coverage([("set_host", 0, 8, 0.9), ("rebuild_heap", 1), ("rebuild_heap", 0), ("skin", 0, True, 0, 98), ("rebuild_heap", 0),
+                             ("device_heap", ("deform", 0.9)), ("frame", None), ("rebuild_heap", 0)])
+    assert (c["build_behind_upload"], c["build_behind_morph_or_skin"]) == (2, 1)
+    c = cs.dynamic_coverage([("ray_query_async", 1), build, ("get", "C"), build, ("radiance_async", 1), ("frame", None), ("rebuild_heap", 0)])
+    assert c["async_across_build"] == 2
+    c = cs.dynamic_coverage([("morph", 1, True, False), ("morph", 1, False, False), ("morph", 2, True, False), ("frame", None), ("morph", 0, True, False)])
+    assert c["morph_after_morph"] == 1
+    g = ("aov", "G", 15, False)
+    c = cs.dynamic_coverage([g, ("frame", None), ("dof", "C", "Gh", "T0", 0), ("frame", None), ("dof", "C", "Gh", "T0", 0)])
+    assert (c["dof_input_deferred"], c["dof_into_result"]) == (2, 1)                                           # (no frame follows the second)
+    c = cs.dynamic_coverage([("frame", None), g, ("dof", "X0", "Gh", "X1", 0)])
+    assert c["dof_input_deferred"] == 0
+    low, full = ("dof", "Lc", "Lh", "Ln", 0), ("dof", "C", "Gh", "X0", 0)
+    assert cs.dynamic_coverage([full, low, low, full, full, low])["dof_regrow"] == 1
+    c = cs.dynamic_coverage([full, ("bind_sky", "X0"), ("frame", "X1"), ("dof", "C", "Gh", "X2", 0), ("setpixels", "X2", 0.25), ("bind_sky", "X2"), ("frame", "X1")])
+    assert c["dof_sky_traced"] == 1
+    tm = ("present_tm", None, "aces")
+    c = cs.dynamic_coverage([("frame", None), ("master_dof", 1), tm, ("bind_sky", "S1"), ("frame", None), tm, ("get", "TM"), ("master_dof", None), tm, ("frame", None)])
+    assert c["master_dof_then_frame"] == 1
