@@ -14,7 +14,8 @@
  *  - handles are opaque 64-bit ids owned by the library until *_release();
  *  - one caller thread per context (Unity main thread); work is issued in order on one HIP stream,
  *    so no synchronisation is needed between dispatch and blit; urt_synchronize() or a readback
- *    waits for completion;
+ *    waits for completion.  The context-free urt_host_* helpers may be called from any thread
+ *    concurrently: each thread has its own last-error strings;
  *  - buffer layouts are the byte layouts of urt_types.h (RM:42-45), matrices are 16 floats in
  *    Unity Matrix4x4 memory order (column-major), images are RGBA32F with row 0 = bottom row
  *    (RS:434,468: id.y = 0 is uv.y = -1);
@@ -1094,7 +1095,8 @@ typedef struct urt_counters {
  *          mode 4: "pool_k" (1..4), "pool_refill", "pool_blas_min" (1..256), "pool_blas_exit", "pool_inloop",
  *                  "pool_other_min" (1..64),
  *          "blas_leaf_max" (1..8: triangles per BVH leaf, default 2 or the environment variable URT_BLAS_LEAF_MAX read when the
- *          library is loaded — a process-wide builder setting; rebuilds the BVH),
+ *          library is loaded — a process-wide builder setting; rebuilds the BVH; changing it while another thread prepares a scene
+ *          is not supported),
  *          "stack_pad" (0..96: test hook, unused extra entries per traversal stack -> the > 64 KiB LDS launch path),
  *          "radiance_persist" (-1 auto, the default | 0 | 1: urt_radiance_query on a resident grid whose lanes take the next query from a
  *                              work counter when theirs is finished, instead of one query per thread; same results),
@@ -1170,6 +1172,12 @@ URT_API int urt_group_get_counters(urt_group* group, urt_counters* out);   /* su
 URT_API int urt_group_reset_counters(urt_group* group);
 
 /* ---- host-side scene preparation (no GPU needed) ---------------------- */
+/* Common to the urt_host_* helpers of this and the next two sections.  URT_ERR_INVALID_ARGUMENT: a negative count, a NULL array with a
+ * positive count, an output capacity that is too small — checked first, nothing is written.  URT_ERR_SCENE: a record that points
+ * outside the arrays (a MeshObject range outside the indices, an index outside the vertices); it is found while the records are
+ * walked, so outputs that belong to earlier records (leaf boxes of earlier MeshObjects, lines already in a file) may have been written,
+ * never more than the stated size of an output.  Non-finite and denormal coordinates are data, not errors.  Every failing call leaves a
+ * non-empty message for the section's *_last_error(). */
 /* RayTraceMaster.ComputeNormals (RM:340-368): per-vertex sum of the un-normalised face normals of every index slot whose
  * vertex POSITION equals this vertex's (weld across all meshes), in ascending slot order, then Vector3.Normalize —
  * O(V + I) by position hashing instead of the reference's O(V * I).  out_normals = 3 * n_vertices floats. */
@@ -1177,7 +1185,8 @@ URT_API int urt_host_compute_normals(const float* vertices, int n_vertices, cons
                                      float* out_normals);
 /* SetupBVHLeaves(List<MeshObject>) (RM:405-433): one world-space box per MeshObject (112-B records).  literal != 0 keeps
  * the reference's quirks (box seeded from _vertices[_indices[0]], the mesh's own first index slot skipped, A.7);
- * literal == 0 gives the tight box. */
+ * literal == 0 gives the tight box.  NULL vertices or indices with a positive count: URT_ERR_INVALID_ARGUMENT.  Boxes are a plain
+ * loop of lo = min(lo, p), hi = max(hi, p) in that argument order (a NaN coordinate is skipped unless it comes first). */
 URT_API int urt_host_mesh_leaf_bounds(const void* mesh_objects, int n_meshes, const float* vertices, int n_vertices,
                                       const int32_t* indices, int n_indices, int literal, urt_BVHNode* out_leaves);
 /* SetupBVHLeaves(List<Sphere>) (RM:436-455): literal != 0 keeps the inverted boxes (vmin = pos + r, vmax = pos - r). */
@@ -1185,13 +1194,18 @@ URT_API int urt_host_sphere_leaf_bounds(const void* spheres, int n_spheres, int 
 /* CreateBVH's output contract (RM:681-722): implicit heap of 2^D - 1 nodes, D = ceil(log2 n) + 1, children 2i+1 / 2i+2,
  * interior and filler nodes index -1 (fillers all-zero, RM:490-494).  This one builds the tree by a deterministic median split
  * (O(n log n)); urt_host_build_object_bvh_pairing below is the reference's own O(n^3) pairing heuristic.  Pixels do not depend on
- * which of the two made the heap. */
+ * which of the two made the heap.  urt_host_object_bvh_length: 0 for n_objects <= 0, and -1 where 2^D - 1 does not fit in an int
+ * (n_objects > 2^30); both builders answer a negative length, like a capacity below the length, with URT_ERR_INVALID_ARGUMENT.  The
+ * median split takes any coordinates (a NaN centre sorts after every number; every leaf still appears exactly once). */
 URT_API int urt_host_object_bvh_length(int n_objects);
 URT_API int urt_host_build_object_bvh(const urt_BVHNode* leaves, int n_objects, urt_BVHNode* out_nodes, int capacity);
 /* The reference's OWN builder restated literally — SetupBVHRankList / PairBVHBounds / JoinBVH / CreateBVH (RM:459-722): nearest-
  * neighbour ranking with "forbidden" pairs last, greedy pairing from start index n-1 (the volume comparison is dead code: the
  * candidate list is aliased, RM:670), lone trees joined under a copy of their own root, layers woven into the implicit heap.
- * Only the order of exact ties in the ranking sort (an unstable List.Sort in the reference) is this library's choice (stable). */
+ * Only the order of exact ties in the ranking sort (an unstable List.Sort in the reference) is this library's choice (stable).
+ * A leaf with a NaN or infinite corner is URT_ERR_SCENE, nothing written: the reference's FindIndex (Vector3 ==) cannot find such a box
+ * and its pairing throws.  A lone tree is joined with nothing under a copy of its root, so an interior node may have one filler child
+ * and an object's leaf may appear a second time on an interior position. */
 URT_API int urt_host_build_object_bvh_pairing(const urt_BVHNode* leaves, int n_objects, urt_BVHNode* out_nodes, int capacity);
 /* The motion tables of urt_reproject_objects from the object lists before and after a move (n entries of _MeshObjects / _Spheres
  * each), entry i = current world -> previous world of object i.  Mesh: prevL * inverse(curL) of the two localToWorldMatrix fields
@@ -1201,15 +1215,24 @@ URT_API int urt_host_build_object_bvh_pairing(const urt_BVHNode* leaves, int n_o
  * all-NaN entry (that object then has no history) and is not an error.  URT_ERR_INVALID_ARGUMENT: n < 0, or a NULL pointer with n > 0. */
 URT_API int urt_host_mesh_motion(const void* prev_mesh_objects, const void* cur_mesh_objects, int n, urt_ObjectMotion* out);
 URT_API int urt_host_sphere_motion(const void* prev_spheres, const void* cur_spheres, int n, urt_ObjectMotion* out);
+/* The message of the calling thread's last failing call of this section; the pointer stays valid until that thread's next failing
+ * call of the section. */
 URT_API const char* urt_host_last_error(void);
 
 /* ---- host-side image I/O (no GPU needed) ---------------------------------- */
 /* Radiance RGBE (.hdr, FORMAT=32-bit_rle_rgbe, flat or new-style RLE scanlines) -> RGBA32F, row 0 = bottom: the pixels a
- * caller hands to urt_texture_set_pixels for "_SkyboxTexture" (RM:776).  out_rgba == NULL queries the size. */
+ * caller hands to urt_texture_set_pixels for "_SkyboxTexture" (RM:776).  out_rgba == NULL queries the size.  Sizes 1..65536; new-style
+ * RLE where the width is 8..32767, flat rows otherwise; header lines of up to 4096 bytes.  URT_ERR_INVALID_ARGUMENT: a NULL or
+ * unopenable path, capacity_floats below width * height * 4 (nothing is written).  URT_ERR_LAYOUT: anything that is not such a file,
+ * or one that ends early or whose runs overrun a row; *out_width / *out_height are set once the header is read, rows decoded before the
+ * fault stay in out_rgba, and never more than width * height * 4 floats are written.  URT_OK: exactly those floats, alpha 1. */
 URT_API int urt_host_load_hdr(const char* path, int* out_width, int* out_height, float* out_rgba, size_t capacity_floats);
 /* RGBA32F image -> RGBA32F image of another size with a separable Mitchell-Netravali filter: the importer step the reference's sky
  * assets go through (`maxTextureSize: 2048`, `resizeAlgorithm: 0`, Assets/Skyboxes/CloudedSunGlow4k.hdr.meta:36,73).  An approximation
- * of Unity's closed-source resampler (its BC6H compression is not reproduced). */
+ * of Unity's closed-source resampler (its BC6H compression is not reproduced).  Output texel d takes the source texels floor(c - s) ..
+ * ceil(c + s) around c = (d + 0.5) * scale - 0.5 with s = 2 * max(1, scale), indices clamped to the edge, weights
+ * Mitchell((k - c) / max(1, scale)) normalised to sum 1 (evaluated in double, rounded once), rows first, then columns; sums in float32.
+ * Sides 1 .. 2^28. */
 URT_API int urt_host_resize_rgba(const float* src, int width, int height, float* dst, int new_width, int new_height);
 /* RGBA32F image (row 0 = bottom) -> .pfm (float RGB, bottom row first). */
 URT_API int urt_host_write_pfm(const char* path, const float* rgba, int width, int height);
@@ -1220,6 +1243,7 @@ URT_API int urt_host_write_png(const char* path, const float* rgba, int width, i
  * encoder of urt_texture_read_begin_format searches. */
 URT_API int urt_host_encode_srgb8(const float* rgba, size_t n_pixels, unsigned char* out_rgba8);
 URT_API int urt_host_srgb8_first_floats(float* out256);
+/* As urt_host_last_error, for this section: per thread, valid until the same thread's next failing call of the section. */
 URT_API const char* urt_host_io_last_error(void);
 
 /* ---- host-side debug log and BVH inspection (no GPU needed) ------------------ */
@@ -1243,6 +1267,8 @@ URT_API int urt_host_dump_bvh(const char* path, const urt_BVHNode* nodes, int n_
  * one line "mesh slot (base) -> (tip)".  out_lines = slots written. */
 URT_API int urt_host_dump_normals(const char* path, const void* mesh_objects, int n_meshes, const float* vertices, int n_vertices,
                                   const int32_t* indices, int n_indices, const float* normals, int n_normals, int* out_lines);
+/* As urt_host_last_error, for this section: per thread, valid until the same thread's next failing call of the section.  A call
+ * that fails on its arguments creates no file and sets *out_lines to 0. */
 URT_API const char* urt_host_debug_last_error(void);
 
 /* ---- introspection for tests (host only, no GPU needed) ------------------------------------ */

@@ -317,7 +317,7 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_host_compute_normals(IntPtr vertices, int nVertices, IntPtr indices, int nIndices, IntPtr outNormals);
     [DllImport(Lib)] internal static extern int urt_host_mesh_leaf_bounds(IntPtr meshObjects, int nMeshes, IntPtr vertices, int nVertices, IntPtr indices, int nIndices, int literal, IntPtr outLeaves);
     [DllImport(Lib)] internal static extern int urt_host_sphere_leaf_bounds(IntPtr spheres, int nSpheres, int literal, IntPtr outLeaves);
-    [DllImport(Lib)] internal static extern int urt_host_object_bvh_length(int nObjects);
+    [DllImport(Lib)] internal static extern int urt_host_object_bvh_length(int nObjects);   // < 0 (more than 2^30 objects): treat as URT_ERR_INVALID_ARGUMENT, as both builders do
     [DllImport(Lib)] internal static extern int urt_host_build_object_bvh(IntPtr leaves, int nObjects, IntPtr outNodes, int capacity);
     [DllImport(Lib)] internal static extern int urt_host_load_hdr(string path, out int width, out int height, [Out] float[] rgba, UIntPtr capacityFloats);
     [DllImport(Lib)] internal static extern int urt_host_write_pfm(string path, float[] rgba, int width, int height);

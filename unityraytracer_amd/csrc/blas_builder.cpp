@@ -62,6 +62,15 @@ int g_leaf_max = leaf_max_from_env();   // SAH leaves (tunable: URT_BLAS_LEAF_MA
 constexpr int kLeafHardMax = 8;  // encoding limit (3 bits)
 constexpr int kForkMinPrims = 8192;   // subtrees at least this big may get a thread of their own
 
+// The SAH bin of a centroid at distance t * (ext / kBins) from the low end: trunc(t) clamped to [0, kBins - 1], compared first and
+// converted only where an int can hold it.  What an int cannot hold lands in bin 0: a NaN t (a non-finite vertex: NaN - lo, or inf * 0
+// when the extent overflows) and t >= 2^31 (+inf: a denormal extent makes kBins / ext infinite).  That is where the bare cast put them
+// on x86 (cvttss2si answers INT_MIN, the clamp made it 0), and the trees of such meshes are kept as they were.
+inline int sah_bin(float t) {
+  if (!(t >= 1.0f) || !(t < 2147483648.0f)) return 0;
+  return t >= (float)(kBins - 1) ? kBins - 1 : (int)t;
+}
+
 struct Builder {
   std::vector<Prim> prims;           // owned by the MeshObject's root builder ...
   Prim* P = nullptr;                 // ... and shared (disjoint index ranges) with the builders of its big subtrees
@@ -121,8 +130,7 @@ struct Builder {
       for (auto& b : bb) b.reset();
       float scale = (float)kBins / ext;
       for (int q = lo; q < hi; q++) {
-        int b = (int)((P[q].c[ax] - cb.lo[ax]) * scale);
-        b = std::min(std::max(b, 0), kBins - 1);
+        int b = sah_bin((P[q].c[ax] - cb.lo[ax]) * scale);
         cnt[b]++; bb[b].grow(P[q].lo, P[q].hi);
       }
       float right_area[kBins]; int right_cnt[kBins];
@@ -143,9 +151,7 @@ struct Builder {
       float clo = cb.lo[best_axis];
       int ax = best_axis, bin = best_bin;
       Prim* it = std::partition(P + lo, P + hi, [=](const Prim& p) {
-        int b = (int)((p.c[ax] - clo) * scale);
-        b = std::min(std::max(b, 0), kBins - 1);
-        return b <= bin;
+        return sah_bin((p.c[ax] - clo) * scale) <= bin;
       });
       mid = (int)(it - P);
     } else {

@@ -19,7 +19,7 @@
 
 namespace {
 
-std::string g_dbg_error;
+thread_local std::string g_dbg_error;   // per thread (include/urt.h)
 int dbg_fail(int code, const std::string& m) { g_dbg_error = m; return code; }
 
 // RD:70-89 literally: `end` is turned into a direction first; EPSILON is float.Epsilon (1.4e-45), not the shader's 1e-8

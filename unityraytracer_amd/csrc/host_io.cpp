@@ -18,7 +18,7 @@
 
 namespace {
 
-std::string g_io_error;
+thread_local std::string g_io_error;   // per thread (include/urt.h)
 int io_fail(int code, const std::string& m) { g_io_error = m; return code; }
 
 bool read_line(FILE* f, std::string& line) {
@@ -38,15 +38,14 @@ inline void rgbe_to_float(const unsigned char* p, float* out) {     // Ward's rg
   out[0] = (float)p[0] * f; out[1] = (float)p[1] * f; out[2] = (float)p[2] * f;
 }
 
-uint32_t crc_table[256];
-bool crc_ready = false;
+struct CrcTable {
+  uint32_t t[256];
+  CrcTable() { for (uint32_t i = 0; i < 256; i++) { uint32_t c = i; for (int k = 0; k < 8; k++) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1; t[i] = c; } }
+};
 uint32_t crc32(uint32_t crc, const unsigned char* p, size_t n) {
-  if (!crc_ready) {
-    for (uint32_t i = 0; i < 256; i++) { uint32_t c = i; for (int k = 0; k < 8; k++) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1; crc_table[i] = c; }
-    crc_ready = true;
-  }
+  static const CrcTable table;                  // a function-local static: filled once, whichever thread comes first
   crc = ~crc;
-  for (size_t i = 0; i < n; i++) crc = crc_table[(crc ^ p[i]) & 0xff] ^ (crc >> 8);
+  for (size_t i = 0; i < n; i++) crc = table.t[(crc ^ p[i]) & 0xff] ^ (crc >> 8);
   return ~crc;
 }
 void put32(std::vector<unsigned char>& v, uint32_t x) { v.push_back(x >> 24); v.push_back((x >> 16) & 0xff); v.push_back((x >> 8) & 0xff); v.push_back(x & 0xff); }
@@ -107,30 +106,35 @@ int urt_host_srgb8_first_floats(float* out256) {
 // (platformSettings.resizeAlgorithm: 0 = Mitchell): separable Mitchell-Netravali (B = C = 1/3), the kernel widened by the scale
 // factor (area filtering), edges clamped, weights normalised.  Unity's own resampler is closed source — its edge rule and the
 // BC6H compression the .meta also asks for (textureCompression: 1) are NOT reproduced: an approximation of the import, unpinned.
-static inline float mitchell(float x) {
+// The filter's geometry and weights are evaluated in double and each normalised weight is rounded to float once: in float the
+// cancelling cubic and the centre (d + 0.5) * scale - 0.5 cost more than the sum itself (tests/host_fuzz_main.cpp, section resize).
+static inline double mitchell(double x) {
   x = std::fabs(x);
-  const float B = 1.0f / 3.0f, C = 1.0f / 3.0f;
-  if (x < 1.0f) return ((12 - 9 * B - 6 * C) * x * x * x + (-18 + 12 * B + 6 * C) * x * x + (6 - 2 * B)) / 6.0f;
-  if (x < 2.0f) return ((-B - 6 * C) * x * x * x + (6 * B + 30 * C) * x * x + (-12 * B - 48 * C) * x + (8 * B + 24 * C)) / 6.0f;
-  return 0.0f;
+  const double B = 1.0 / 3.0, C = 1.0 / 3.0;
+  if (x < 1.0) return ((12 - 9 * B - 6 * C) * x * x * x + (-18 + 12 * B + 6 * C) * x * x + (6 - 2 * B)) / 6.0;
+  if (x < 2.0) return ((-B - 6 * C) * x * x * x + (6 * B + 30 * C) * x * x + (-12 * B - 48 * C) * x + (8 * B + 24 * C)) / 6.0;
+  return 0.0;
 }
 
 static void resize_axis(const float* src, int n_src, int other, int n_dst, float* dst, bool along_x) {
   // along_x: src is [other rows][n_src cols][4], dst [other][n_dst][4]; else src is [n_src rows][other cols][4], dst [n_dst][other][4]
-  float scale = (float)n_src / (float)n_dst, support = 2.0f * std::max(1.0f, scale), inv = 1.0f / std::max(1.0f, scale);
+  const double scale = (double)n_src / (double)n_dst, wide = std::max(1.0, scale), support = 2.0 * wide;
+  std::vector<double> wd;
   std::vector<float> w;
   for (int d = 0; d < n_dst; d++) {
-    float centre = ((float)d + 0.5f) * scale - 0.5f;
-    int lo = (int)std::floor(centre - support), hi = (int)std::ceil(centre + support);
-    w.assign((size_t)(hi - lo + 1), 0.0f);
-    float sum = 0;
-    for (int k = lo; k <= hi; k++) { float v = mitchell(((float)k - centre) * inv); w[(size_t)(k - lo)] = v; sum += v; }
+    const double centre = ((double)d + 0.5) * scale - 0.5;
+    const int lo = (int)std::floor(centre - support), hi = (int)std::ceil(centre + support);     // |centre| + support < 3 * n_src: fits
+    wd.assign((size_t)(hi - lo + 1), 0.0);
+    double sum = 0;
+    for (int k = lo; k <= hi; k++) { double v = mitchell(((double)k - centre) / wide); wd[(size_t)(k - lo)] = v; sum += v; }
+    w.resize(wd.size());
+    for (size_t k = 0; k < wd.size(); k++) w[k] = (float)(wd[k] / sum);
     for (int o = 0; o < other; o++) {
       float acc[4] = {0, 0, 0, 0};
       for (int k = lo; k <= hi; k++) {
         int kk = std::min(std::max(k, 0), n_src - 1);
         const float* p = along_x ? src + 4 * ((size_t)o * n_src + kk) : src + 4 * ((size_t)kk * other + o);
-        float wk = w[(size_t)(k - lo)] / sum;
+        const float wk = w[(size_t)(k - lo)];
         for (int c = 0; c < 4; c++) acc[c] += wk * p[c];
       }
       float* q = along_x ? dst + 4 * ((size_t)o * n_dst + d) : dst + 4 * ((size_t)d * other + o);
@@ -141,6 +145,8 @@ static void resize_axis(const float* src, int n_src, int other, int n_dst, float
 
 int urt_host_resize_rgba(const float* src, int width, int height, float* dst, int new_width, int new_height) {
   if (!src || !dst || width <= 0 || height <= 0 || new_width <= 0 || new_height <= 0) return io_fail(URT_ERR_INVALID_ARGUMENT, "resize: bad arguments");
+  const int kMaxSide = 1 << 28;                      // the filter's window (up to three source sides wide) is counted in int
+  if (width > kMaxSide || height > kMaxSide || new_width > kMaxSide || new_height > kMaxSide) return io_fail(URT_ERR_INVALID_ARGUMENT, "resize: a side above 2^28");
   try {
     std::vector<float> tmp((size_t)new_width * height * 4);
     resize_axis(src, width, height, new_width, tmp.data(), true);

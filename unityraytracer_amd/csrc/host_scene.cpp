@@ -42,7 +42,7 @@ inline V3 multiply_point_3x4(const float* m, V3 p) {
           m[2] * p.x + m[6] * p.y + m[10] * p.z + m[14]};
 }
 
-std::string g_host_error;
+thread_local std::string g_host_error;   // per thread: the context-free helpers may run on any thread (include/urt.h)
 int host_fail(int code, const std::string& msg) { g_host_error = msg; return code; }
 
 }  // namespace
@@ -184,11 +184,15 @@ extern "C" {
 
 int urt_host_build_object_bvh_pairing(const urt_BVHNode* leaves, int n_objects, urt_BVHNode* out_nodes, int capacity) {
   int len = urt_host_object_bvh_length(n_objects);
-  if (n_objects < 0 || (n_objects && (!leaves || !out_nodes)) || capacity < len) return host_fail(URT_ERR_INVALID_ARGUMENT, "CreateBVH: bad arguments");
+  if (n_objects < 0 || len < 0 || (n_objects && (!leaves || !out_nodes)) || capacity < len) return host_fail(URT_ERR_INVALID_ARGUMENT, "CreateBVH: bad arguments");
   if (n_objects == 0) return URT_OK;                 // (the reference throws on an empty list, A.7; an empty list is "no buffer" here)
+  // nodes.FindIndex(x => x == other) (RM:557) does not find a box that is not equal to itself — a NaN corner, or an infinite one
+  // (inf - inf) — and the reference then throws on nodes[-1]: that throw is this error, before anything is written
+  for (int i = 0; i < n_objects; i++)
+    if (!node_equal(leaves[i], leaves[i])) return host_fail(URT_ERR_SCENE, "CreateBVH: leaf " + std::to_string(i) + " has a non-finite corner, which the reference's pairing cannot look up");
   try {
     int depth = 1;
-    while ((1 << (depth - 1)) < n_objects) depth++;  // RM:683,705: Mathf.CeilToInt(Mathf.Log(n, 2)) + 1
+    while ((1 << (depth - 1)) < n_objects) depth++;  // RM:683,705: Mathf.CeilToInt(Mathf.Log(n, 2)) + 1 (n <= 2^30: len >= 0)
     std::vector<Tree> trees((size_t)n_objects);
     for (int i = 0; i < n_objects; i++) trees[(size_t)i].push_back(leaves[i]);
     for (int i = 0; i < depth - 1; i++) pair_bvh_bounds(trees);
@@ -293,6 +297,7 @@ int urt_debug_build_morph_plan(const urt_MorphDelta* deltas, int n_deltas, int n
 int urt_host_mesh_leaf_bounds(const void* mesh_objects, int n_meshes, const float* vertices, int n_vertices, const int32_t* indices,
                               int n_indices, int literal, urt_BVHNode* out_leaves) {
   if (n_meshes < 0 || (n_meshes && (!mesh_objects || !out_leaves))) return host_fail(URT_ERR_INVALID_ARGUMENT, "SetupBVHLeaves: bad arguments");
+  if ((n_vertices > 0 && !vertices) || (n_indices > 0 && !indices)) return host_fail(URT_ERR_INVALID_ARGUMENT, "SetupBVHLeaves: NULL array");
   for (int m = 0; m < n_meshes; m++) {
     urt_MeshObject mo;
     std::memcpy(&mo, (const uint8_t*)mesh_objects + (size_t)m * sizeof mo, sizeof mo);
@@ -350,14 +355,15 @@ int urt_host_sphere_leaf_bounds(const void* spheres, int n_spheres, int literal,
 
 int urt_host_object_bvh_length(int n_objects) {       // RM:683,705: depth = ceil(log2 n) + 1, length 2^depth - 1
   if (n_objects <= 0) return 0;
+  if (n_objects > (1 << 30)) return -1;               // 2^32 - 1 nodes do not fit in an int: the builders refuse a negative length
   int depth = 1;
-  while ((1 << (depth - 1)) < n_objects) depth++;
-  return (1 << depth) - 1;
+  while ((1 << (depth - 1)) < n_objects) depth++;    // depth <= 31
+  return (int)((1u << depth) - 1u);
 }
 
 int urt_host_build_object_bvh(const urt_BVHNode* leaves, int n_objects, urt_BVHNode* out_nodes, int capacity) {
   int len = urt_host_object_bvh_length(n_objects);
-  if (n_objects < 0 || (n_objects && (!leaves || !out_nodes)) || capacity < len) return host_fail(URT_ERR_INVALID_ARGUMENT, "CreateBVH: bad arguments");
+  if (n_objects < 0 || len < 0 || (n_objects && (!leaves || !out_nodes)) || capacity < len) return host_fail(URT_ERR_INVALID_ARGUMENT, "CreateBVH: bad arguments");
   try {
     for (int i = 0; i < len; i++) { std::memset(&out_nodes[i], 0, sizeof(urt_BVHNode)); out_nodes[i].index = -1; }   // filler (RM:490-494)
     if (n_objects == 0) return URT_OK;
@@ -389,7 +395,10 @@ int urt_host_build_object_bvh(const urt_BVHNode* leaves, int n_objects, urt_BVHN
       int ax = 0;
       if (chi[1] - clo[1] > chi[ax] - clo[ax]) ax = 1;
       if (chi[2] - clo[2] > chi[ax] - clo[ax]) ax = 2;
+      // a strict total order, as std::sort requires: a NaN centre (a NaN corner, or +inf and -inf averaged) sorts after every number
       std::sort(items.begin() + j.lo, items.begin() + j.hi, [ax](const Item& a, const Item& b) {
+        const bool an = a.c[ax] != a.c[ax], bn = b.c[ax] != b.c[ax];
+        if (an || bn) return an == bn ? a.leaf < b.leaf : bn;
         return a.c[ax] < b.c[ax] || (a.c[ax] == b.c[ax] && a.leaf < b.leaf);
       });
       int half = (j.hi - j.lo + 1) / 2;

@@ -95,6 +95,8 @@ def build_object_bvh(leaves: np.ndarray, pairing: bool = False) -> np.ndarray:
     lib = _lib.load()
     lv = np.ascontiguousarray(leaves, dtype=BVHNODE_DT)
     n = lib.urt_host_object_bvh_length(len(lv))
+    if n < 0:                                                # more than 2^30 leaves: 2^D - 1 has no int (include/urt.h)
+        raise UrtError(1, f"CreateBVH: the heap of {len(lv)} objects has no int length")
     out = np.zeros(n, dtype=BVHNODE_DT)
     fn = lib.urt_host_build_object_bvh_pairing if pairing else lib.urt_host_build_object_bvh
     _check(lib, fn(_p(lv), len(lv), _p(out), n))
