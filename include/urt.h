@@ -1111,6 +1111,16 @@ typedef struct urt_counters {
  *                        behind: the reference's own back-face culling (RS:211) rejects every one of them, so the skip is exact.  A ray
  *                        that leaves a closed mesh no longer walks the boxes around its origin down to their leaves.  The counting
  *                        instantiation ("count_stats") and "qnodes" walk without it.  See urt_debug_read_scene_cones),
+ *          "tile_entry" (-1 auto, the default | 0 off | 1 on: kernel_mode 3 on a scene of one MeshObject and no spheres.  While an image
+ *                        accumulates the camera stands still, and all camera rays of an 8x8 tile descend the triangle BVH through the same
+ *                        ancestors.  A pre-pass walks that common part once per tile — dropping the children whose box lies outside the
+ *                        tile's frustum or whose normal cone faces away from all of its rays — and leaves up to 8 entry nodes per tile, 32 B;
+ *                        camera rays start there instead of at the root.  Used by a launch whose frames all have the same camera matrices,
+ *                        bit for bit, and pixel offsets in [0, 1]; the table is kept until the camera, the image size or the BVH changes.
+ *                        auto builds a table only for a camera that has stood still — a launch of two frames or more, or the camera of the
+ *                        previous launch — so that a camera that moves with every submitted frame pays no pre-pass; 1 builds it at once.
+ *                        Not in the counting instantiation, not with "qnodes".  csrc/tile_entry.h; see urt_debug_read_tile_entry and
+ *                        urt_launch_info::tile_entry),
  *          "refit" (0/1, default 1: moved and deformed MeshObjects are refitted on the GPU instead of rebuilt — see urt_debug_refit_stats;
  *                   0 turns the in-place update off altogether),
  *          "refit_vertices" (0/1, default 1: a SetData that changes elements of _Vertices / _Normals — same counts, _Indices untouched — is
@@ -1309,6 +1319,8 @@ typedef struct urt_launch_info {
   int overlapped_launches;    /* such launches since the context was created */
   int cones;                  /* 1: the launch's traversal applied the normal cones of option "blas_cones" (kernel_mode 3, not counting, no qnodes) */
   int handout;                /* kernel_mode 3: tiles per LDS reservation of a workgroup (option "handout": 1..16, a divisor of xcd_run); 0: every wave draws from the work counters */
+  int tile_entry;             /* 1: the launch's camera rays started at the entries of a tile entry table (option "tile_entry") */
+  int tile_entry_k;           /* entries per tile of that table (0: no table) */
 } urt_launch_info;
 URT_API int urt_debug_launch_info(urt_context* ctx, urt_launch_info* out_info);
 URT_API int urt_debug_read_scene_blas(urt_context* ctx, float* nodes, int32_t* tri_index, int32_t* mesh_root);
@@ -1323,6 +1335,14 @@ URT_API int urt_debug_read_scene_qnodes(urt_context* ctx, float* out, int* out_n
  * e2.xyz of every leaf-order triangle of the world-space records the cones were derived from (what Moller-Trumbore reads).  Either may
  * be NULL.  *out_in_use = 1 when the words are filled in (the option is on and the scene has triangle BVHs), else they are all 0. */
 URT_API int urt_debug_read_scene_cones(urt_context* ctx, uint32_t* words, float* tri_edges, int* out_in_use);
+/* The tile entry table of option "tile_entry" as the last launch that used one read it (deferred frames are submitted first; synchronises):
+ * *out_tiles_x x *out_tiles_y records, row by row over the 8x8 tiles of the whole image, *out_k dwords each — the node codes a camera ray
+ * of the tile starts from (>= 0 an interior node of the triangle BVH, < 0 a leaf code), padded with 0x80000000; a record of padding alone
+ * means that no camera ray of the tile can hit the mesh.  All three are 0 while the context holds no table.  out (may be NULL) receives at
+ * most capacity_words dwords.  *out_builds: tables built since the context was created — a launch with the camera, image size and BVH
+ * of the cached table builds none.  Any pointer may be NULL. */
+URT_API int urt_debug_read_tile_entry(urt_context* ctx, int32_t* out, uint64_t capacity_words, int* out_tiles_x, int* out_tiles_y, int* out_k,
+                                      uint64_t* out_builds);
 /* Scene preparation of a context keeps the triangle BVH of every MeshObject and reuses it at the next preparation when the
  * MeshObject's matrix and the positions behind its index slots are unchanged (the reference re-uploads every buffer when
  * any object moves, RM:262-336).  Reports how many MeshObject BVHs were reused / built since the context was created. */

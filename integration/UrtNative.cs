@@ -344,9 +344,10 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_debug_build_blas(IntPtr meshObjects, int nMeshes, float[] vertices, int nVertices, int[] indices, int nIndices, out int nNodes, out int nTris, out int maxDepth);
     [DllImport(Lib)] internal static extern int urt_debug_get_blas([Out] float[] nodes, [Out] int[] triIndex, [Out] int[] meshRoot, [Out] int[] meshFirstTri);
     [DllImport(Lib)] internal static extern int urt_debug_scene_info(IntPtr ctx, out int nNodes, out int nTris, out int maxDepth, out float prepareMs);
-    [DllImport(Lib)] internal static extern int urt_debug_launch_info(IntPtr ctx, [Out] byte[] launchInfo196);   // urt_launch_info: char kernel[96] + 25 ints
+    [DllImport(Lib)] internal static extern int urt_debug_launch_info(IntPtr ctx, [Out] byte[] launchInfo208);   // urt_launch_info: char kernel[96] + 28 ints
     [DllImport(Lib)] internal static extern int urt_debug_read_scene_blas(IntPtr ctx, [Out] float[] nodes, [Out] int[] triIndex, [Out] int[] meshRoot);
     [DllImport(Lib)] internal static extern int urt_debug_read_scene_qnodes(IntPtr ctx, [Out] float[] qnodes, out int nNodes, out int inUse);
+    [DllImport(Lib)] internal static extern int urt_debug_read_tile_entry(IntPtr ctx, [Out] int[] words, ulong capacityWords, out int tilesX, out int tilesY, out int k, out ulong builds);
     [DllImport(Lib)] internal static extern int urt_debug_read_scene_cones(IntPtr ctx, [Out] uint[] words, [Out] float[] triEdges, out int inUse);
     [DllImport(Lib)] internal static extern int urt_debug_blas_cache_stats(IntPtr ctx, out ulong reused, out ulong built);
     [DllImport(Lib)] internal static extern int urt_debug_serve_stats(IntPtr ctx, [Out] ulong[] out6);

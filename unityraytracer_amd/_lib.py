@@ -22,7 +22,7 @@ ABI_SYMBOLS = [
     "urt_shader_set_buffer", "urt_shader_set_texture", "urt_shader_set_matrix", "urt_shader_set_vector", "urt_shader_set_float",
     "urt_shader_set_int", "urt_shader_dispatch", "urt_shader_dispatch_rows", "urt_blit_add", "urt_blit", "urt_texture_pack_rows",
     "urt_texture_unpack_rows", "urt_texture_unpack_rows_on", "urt_texture_pack_rows_rgb", "urt_texture_unpack_rows_rgb", "urt_ray_query", "urt_ray_query_device", "urt_radiance_query", "urt_radiance_query_device", "urt_render_aov", "urt_denoise", "urt_reproject", "urt_reproject_objects", "urt_reproject_deformed", "urt_blit_add_history", "urt_upsample", "urt_auto_exposure", "urt_tonemap", "urt_depth_of_field", "urt_bloom", "urt_select_pixels", "urt_blend_samples", "urt_resample_below", "urt_set_option", "urt_get_counters", "urt_reset_counters", "urt_debug_build_blas", "urt_debug_get_blas", "urt_debug_blas_cache_stats",
-    "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_read_scene_cones", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_deform_stats", "urt_debug_scene_cost", "urt_debug_buffer_state", "urt_debug_live_resources", "urt_debug_build_walk_table", "urt_debug_build_normals_plan", "urt_debug_build_morph_plan", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
+    "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_read_scene_cones", "urt_debug_read_tile_entry", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_deform_stats", "urt_debug_scene_cost", "urt_debug_buffer_state", "urt_debug_live_resources", "urt_debug_build_walk_table", "urt_debug_build_normals_plan", "urt_debug_build_morph_plan", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
     "urt_host_build_object_bvh", "urt_host_build_object_bvh_pairing", "urt_host_mesh_motion", "urt_host_sphere_motion", "urt_host_last_error", "urt_host_load_hdr", "urt_host_write_pfm", "urt_host_write_png", "urt_host_encode_srgb8", "urt_host_srgb8_first_floats",
     "urt_host_resize_rgba", "urt_host_io_last_error", "urt_host_log", "urt_host_log_scene_counts", "urt_host_log_tree_report", "urt_host_dump_bvh", "urt_host_dump_normals",
     "urt_host_debug_last_error",
@@ -217,7 +217,7 @@ class LaunchInfo(C.Structure):
     _fields_ = [("kernel", C.c_char * 96)] + [(n, C.c_int) for n in (
         "kernel_mode", "front_mode", "count_stats", "n_blocks", "block_threads", "lds_bytes", "waves_per_cu", "n_frames", "frame_group",
         "xcd_run", "tile_order", "top_nodes", "tlas_stack", "blas_stack", "lds_tables", "slab_frames", "slab_frames_max",
-        "slab_out_of_memory", "experiment", "blas_builder", "trace_stream", "slab_base", "overlapped", "overlapped_launches", "cones", "handout")]
+        "slab_out_of_memory", "experiment", "blas_builder", "trace_stream", "slab_base", "overlapped", "overlapped_launches", "cones", "handout", "tile_entry", "tile_entry_k")]
 
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_}
@@ -346,6 +346,7 @@ def load():
         "urt_debug_read_scene_blas": ([vp, vp, vp, vp], i),
         "urt_debug_read_scene_qnodes": ([vp, vp, pi, pi], i),
         "urt_debug_read_scene_cones": ([vp, vp, vp, pi], i),
+        "urt_debug_read_tile_entry": ([vp, vp, u64, pi, pi, pi, vp], i),
         "urt_host_compute_normals": ([vp, i, vp, i, vp], i),
         "urt_host_mesh_leaf_bounds": ([vp, i, vp, i, vp, i, i, vp], i),
         "urt_host_sphere_leaf_bounds": ([vp, i, i, vp], i),

@@ -9,6 +9,7 @@
 // There is deliberately no CPU path: without a HIP device context creation fails.
 #include "experiments.h"
 #include "context_impl.h"
+#include "tile_entry.h"
 
 #include <climits>
 #include <limits>
@@ -1187,6 +1188,7 @@ const OptionRow kOptions[] = {
   {"lbvh_slack", &O::lbvh_slack, 0, 16, "lbvh_slack must be 0..16", kStale | kOnChange, nullptr},
   {"overlap_launches", &O::overlap_launches, 0, 2, "overlap_launches must be 0 (off), 1 (auto) or 2 (always)", kFlushAgain, nullptr},
   {"blas_cones", &O::blas_cones, -1, 1, "blas_cones must be -1 (auto), 0 or 1", kStale | kOnChange, nullptr},
+  {"tile_entry", &O::tile_entry, -1, 1, "tile_entry must be -1 (auto), 0 or 1", 0, nullptr},
   {"front_cull", &O::front_cull, 0, 1, "front_cull must be 0 or 1", kFlushAgain | kStale | kOnChange, nullptr},
   {"front_fuse", &O::front_fuse, -1, 1, "front_fuse must be -1 (auto), 0 or 1", kOnChange, nullptr},
   {"handout", &O::handout, -1, 1, "handout must be -1 (auto), 0 or 1", 0, nullptr},
@@ -1431,6 +1433,26 @@ int urt_debug_read_scene_cones(urt_context* ctx, uint32_t* words, float* tri_edg
     std::vector<float> tv(nt * 12);
     URT_HIP(ctx, hipMemcpy(tv.data(), S.tri_verts, tv.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (size_t k = 0; k < nt; k++) { std::memcpy(&tri_edges[6 * k], &tv[k * 12 + 4], 12); std::memcpy(&tri_edges[6 * k + 3], &tv[k * 12 + 8], 12); }
+  }
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+int urt_debug_read_tile_entry(urt_context* ctx, int32_t* out, uint64_t capacity_words, int* out_tiles_x, int* out_tiles_y, int* out_k, uint64_t* out_builds) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = flush_pending(ctx)) return rc;
+  const bool have = ctx->te_valid && ctx->te_table;
+  const int tx = have ? (ctx->te_key.width + 7) / 8 : 0, ty = have ? (ctx->te_key.height + 7) / 8 : 0;
+  if (out_tiles_x) *out_tiles_x = tx;
+  if (out_tiles_y) *out_tiles_y = ty;
+  if (out_k) *out_k = have ? kTileEntryK : 0;
+  if (out_builds) *out_builds = ctx->te_builds;
+  if (out && have) {
+    URT_HIP(ctx, hipEventSynchronize(ctx->te_ready.get()));
+    const uint64_t words = std::min<uint64_t>(capacity_words, (uint64_t)tx * (uint64_t)ty * kTileEntryK);
+    if (words) URT_HIP(ctx, hipMemcpy(out, ctx->te_table.get(), words * sizeof(int32_t), hipMemcpyDeviceToHost));
   }
   return URT_OK;
   URT_GUARD_END(ctx)

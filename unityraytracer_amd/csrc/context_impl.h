@@ -149,6 +149,9 @@ struct urt_context {
     int overlap_launches = 1;               // see "Overlapped launches" below
     int blas_cones = -1;                    // normal cones per triangle-BVH child (csrc/cones.hip): the scheduled kernel skips children whose triangles the ray sees from behind.
                                             // -1 = auto (= on), 0 = off (the words stay 0), 1 = on
+    int tile_entry = -1;                    // kernel_mode 3, one MeshObject and no spheres: camera rays start their triangle-BVH walk at per-tile entry nodes (csrc/tile_entry.h)
+                                            // while every frame of a launch has the same camera.  -1 = auto: on once the camera has stood still (a launch of >= 2 frames, or
+                                            // the camera of the previous launch), 0 = off, 1 = on for every such launch; same pixels
   } opt;
 
   // ---- derived device scene ---------------------------------------------------------------------------------------------
@@ -204,6 +207,18 @@ struct urt_context {
   uint64_t deformed_meshes = 0, renormed_meshes = 0, deform_bytes = 0, forced_rebuilds = 0;   // urt_debug_deform_stats
   float last_cost_ratio = 0;                // largest cost / baseline among the deformed MeshObjects of the last in-place update
   urtd::BlasCache blas_cache;               // per-MeshObject BVHs of the previous scene (reused when a MeshObject is unchanged)
+  uint64_t nodes_epoch = 0;                 // bumps whenever the nodes the trace kernels read are rewritten (scene_prep.cpp rederive_nodes): builds, refits, cones
+  // The tile entry table (csrc/tile_entry.h, option "tile_entry"): one table, for the camera, image size and node contents of `te_key`; a launch
+  // with another key rebuilds it on its stream, behind the launches that still read it.  te_ready orders the build before launches on the other
+  // streams; te_used[s] is recorded behind the last launch that read the table on stream s (0 the main stream, 1 / 2 the trace streams).
+  struct TileEntryKey { float c2w[16], invp[16]; int width, height; uint64_t scene_epoch, nodes_epoch; const void* nodes; };
+  urtd::DeviceBuf<int32_t> te_table;
+  TileEntryKey te_key{}, te_seen_key{};     // the table's; the previous qualifying launch's (auto builds a table for a camera that stood still)
+  bool te_valid = false, te_seen = false;
+  hipStream_t te_stream = nullptr;          // the stream the table was built on
+  urtd::Event te_ready, te_used[3];
+  bool te_used_set[3] = {false, false, false};
+  uint64_t te_builds = 0;                   // tables built since the context was created (urt_debug_read_tile_entry)
   int sched_groups = 0;                     // kernel_mode 3: workgroups per CU the last configuration counts on when fewer than the default fit (0 = default)
   urtd::DeviceBuf<float4> zero_sky;
 
@@ -220,6 +235,7 @@ struct urt_context {
   // frame tables of the batched launches: kTableSlots pinned host images + device copies, used round-robin; a slot is reused
   // once the copy of its previous use has left the host image (event)
   static constexpr int kTableSlots = 4;
+  static constexpr int kTableSlotEntries = urtd::kMaxFramesPerLaunch + 1;   // a launch's entries and, behind the last, 8 bytes: the address of its tile entry table
   urtd::PinnedBuf<urtd::FrameEntry> h_tables; urtd::DeviceBuf<urtd::FrameEntry> d_tables;
   urtd::Event table_ev[kTableSlots];
   unsigned int table_next = 0;

@@ -4,6 +4,7 @@
 #include "context_impl.h"
 
 #include "reproject.h"
+#include "tile_entry.h"
 
 namespace urtd {
 
@@ -244,6 +245,61 @@ static int timed_launch(urt_context* ctx, hipStream_t st, int kernel_mode, int f
   return URT_OK;
 }
 
+// ---- The tile entry table (csrc/tile_entry.h) -----------------------------------------------------------------------------------------------
+// What a dispatch can tell of a launch's right to the table before its frames are known: the plain single-mesh form of kernel_mode 3, in the
+// instantiation that applies the cones' rule (not counting, no quantized nodes).  do_dispatch gives such a launch the stack entries
+// tile_entry_start stores to.
+static bool tile_entry_form(const urt_context* ctx, const DevScene& S, bool count, bool serve, bool top_in_front) {
+  return ctx->opt.tile_entry != 0 && ctx->opt.front_fuse != 0 && !serve && !top_in_front && !count && !S.blas_qnodes && S.blas_cnodes && S.mesh_tlas &&
+         S.mesh_root && S.n_mesh_tlas == 1 && S.n_meshes > 0 && S.n_spheres == 0 && ctx->scene.n_blas_nodes > 0;
+}
+
+// The table for this launch, or null when the launch runs without one: every frame must have frame 0's camera, bit for bit, and pixel
+// offsets in [0, 1] (the sample rectangle tile_entry.h derives its frustum from).  Cached by camera, image size and node contents; a miss
+// builds it on `st`, behind the launches on the other streams that still read the old one.
+static int tile_entry_for_launch(urt_context* ctx, const DevScene& S, const FrameParams& P, const FrameTable& T, int front_mode, bool count,
+                                 hipStream_t st, const int32_t** out) {
+  *out = nullptr;
+  if (front_mode != 0 || P.front_fuse != 2 || P.blas_stack < kTileEntryK || !tile_entry_form(ctx, S, count, P.serve != 0, false)) return URT_OK;
+  const FrameUniforms& u0 = T.f[0].u;
+  for (int f = 0; f < P.n_frames; f++) {
+    const FrameUniforms& u = T.f[f].u;
+    if (std::memcmp(u.c2w, u0.c2w, sizeof u.c2w) != 0 || std::memcmp(u.invp, u0.invp, sizeof u.invp) != 0) return URT_OK;
+    if (!(u.pixel_off_x >= 0.0f && u.pixel_off_x <= 1.0f && u.pixel_off_y >= 0.0f && u.pixel_off_y <= 1.0f)) return URT_OK;
+  }
+  urt_context::TileEntryKey key{};
+  std::memcpy(key.c2w, u0.c2w, sizeof key.c2w); std::memcpy(key.invp, u0.invp, sizeof key.invp);
+  key.width = P.width; key.height = P.height; key.scene_epoch = ctx->scene_epoch; key.nodes_epoch = ctx->nodes_epoch; key.nodes = S.blas_cnodes;
+  const int si = ctx->trace_q[0] && st == ctx->trace_q[0].get() ? 1 : ctx->trace_q[1] && st == ctx->trace_q[1].get() ? 2 : 0;
+  if (!ctx->te_ready) {
+    URT_HIP(ctx, ctx->te_ready.create(hipEventDisableTiming));
+    for (Event& ev : ctx->te_used) URT_HIP(ctx, ev.create(hipEventDisableTiming));
+  }
+  // auto: a table is built for a camera that has demonstrably stood still — a launch of two frames or more, or the key of the previous launch —
+  // so that a host whose camera moves with every submitted frame does not pay a pre-pass per frame (0.57 ms at 1080p on C3)
+  const bool still = P.n_frames >= 2 || (ctx->te_seen && std::memcmp(&key, &ctx->te_seen_key, sizeof key) == 0);
+  ctx->te_seen_key = key; ctx->te_seen = true;
+  if (!ctx->te_valid || std::memcmp(&key, &ctx->te_key, sizeof key) != 0) {
+    if (ctx->opt.tile_entry < 0 && !still) return URT_OK;
+    ctx->te_valid = false;
+    const size_t words = (size_t)((P.width + 7) / 8) * (size_t)((P.height + 7) / 8) * kTileEntryK;
+    for (int k = 0; k < 3; k++) {                            // the readers of the old table, wherever they run
+      if (!ctx->te_used_set[k]) continue;
+      if (words > ctx->te_table.cap()) URT_HIP(ctx, hipEventSynchronize(ctx->te_used[k].get()));
+      else if (k != si) URT_HIP(ctx, hipStreamWaitEvent(st, ctx->te_used[k].get(), 0));
+      ctx->te_used_set[k] = false;
+    }
+    if (int rc = reserve(ctx, ctx->te_table, words, "tile entry table", nullptr)) return rc;
+    URT_HIP(ctx, launch_tile_entry(S, ctx->scene.n_blas_nodes, key.c2w, key.invp, P.width, P.height, ctx->te_table.get(), st));
+    URT_HIP(ctx, hipEventRecord(ctx->te_ready.get(), st));
+    ctx->te_key = key; ctx->te_valid = true; ctx->te_stream = st; ctx->te_builds++;
+  } else if (st != ctx->te_stream) {
+    URT_HIP(ctx, hipStreamWaitEvent(st, ctx->te_ready.get(), 0));
+  }
+  *out = ctx->te_table.get();
+  return URT_OK;
+}
+
 // Launch the phase-scheduled trace kernel for P.n_frames frames (uniforms T) into result + f * P.frame_stride.
 static constexpr int kAutoFrames = 64;     // frames per launch when "frames_per_launch" is 0 (auto) on the library's own stream
 
@@ -252,16 +308,20 @@ static int launch_sched_frames(urt_context* ctx, const DevScene& S, const FrameP
   if (!st) { st = touch(ctx); next = ctx->d_next.get(); }       // the main stream; flush_pending may pass one of its trace streams and that stream's work counters
   // the launch's frame table -> device memory, in stream order (pinned staging slot: the copy does not wait for the stream)
   if (!ctx->h_tables) {
-    URT_HIP(ctx, ctx->h_tables.alloc((size_t)kMaxFramesPerLaunch * urt_context::kTableSlots));
-    URT_HIP(ctx, ctx->d_tables.alloc((size_t)kMaxFramesPerLaunch * urt_context::kTableSlots));
+    URT_HIP(ctx, ctx->h_tables.alloc((size_t)urt_context::kTableSlotEntries * urt_context::kTableSlots));
+    URT_HIP(ctx, ctx->d_tables.alloc((size_t)urt_context::kTableSlotEntries * urt_context::kTableSlots));
     for (Event& ev : ctx->table_ev) URT_HIP(ctx, ev.create(hipEventDisableTiming));
   }
   const unsigned int slot = ctx->table_next++ % (unsigned int)urt_context::kTableSlots;
   if (ctx->table_next > (unsigned int)urt_context::kTableSlots) URT_HIP(ctx, hipEventSynchronize(ctx->table_ev[slot].get()));   // (four launches ago: long done)
-  FrameEntry* h_slot = ctx->h_tables.get() + (size_t)slot * kMaxFramesPerLaunch;
-  FrameEntry* d_table = ctx->d_tables.get() + (size_t)slot * kMaxFramesPerLaunch;
+  FrameEntry* h_slot = ctx->h_tables.get() + (size_t)slot * urt_context::kTableSlotEntries;
+  FrameEntry* d_table = ctx->d_tables.get() + (size_t)slot * urt_context::kTableSlotEntries;
+  const int32_t* te = nullptr;                               // the launch's tile entry table: its address rides behind the last entry (kernels.h launch_sched)
+  if (int rc = tile_entry_for_launch(ctx, S, P, T, front_mode, count, st, &te)) return rc;
+  const uint64_t te_addr = (uint64_t)(uintptr_t)te;
   std::memcpy(h_slot, T.f, sizeof(FrameEntry) * (size_t)P.n_frames);
-  URT_HIP(ctx, hipMemcpyAsync(d_table, h_slot, sizeof(FrameEntry) * (size_t)P.n_frames, hipMemcpyHostToDevice, st));
+  std::memcpy(h_slot + P.n_frames, &te_addr, sizeof te_addr);
+  URT_HIP(ctx, hipMemcpyAsync(d_table, h_slot, sizeof(FrameEntry) * (size_t)P.n_frames + sizeof te_addr, hipMemcpyHostToDevice, st));
   URT_HIP(ctx, hipEventRecord(ctx->table_ev[slot].get(), st));
   int waves_per_block = P.block_threads / 64;
   long want = ((long)P.tiles_x * P.n_strips * P.n_frames + waves_per_block - 1) / waves_per_block;
@@ -280,6 +340,12 @@ static int launch_sched_frames(urt_context* ctx, const DevScene& S, const FrameP
     return P.serve ? launch_serve(S, P, d_table, result, ctx->d_counters.get(), next, ctx->d_mail.get(), nb, front_mode, count, st, rec)
                    : launch_sched(S, P, d_table, result, ctx->d_counters.get(), next, nb, front_mode, count, st, rec);
   });
+  if (te) {                                                    // a later rebuild of the table waits for this launch
+    const int si = ctx->trace_q[0] && st == ctx->trace_q[0].get() ? 1 : ctx->trace_q[1] && st == ctx->trace_q[1].get() ? 2 : 0;
+    URT_HIP(ctx, hipEventRecord(ctx->te_used[si].get(), st));
+    ctx->te_used_set[si] = true;
+  }
+  if (rc == URT_OK) { ctx->last_launch.tile_entry = te ? 1 : 0; ctx->last_launch.tile_entry_k = te ? kTileEntryK : 0; }
   // the cone test runs in the instantiations of k_sched that neither count nor read quantized nodes (kernels.hip), on the words of this scene
   if (rc == URT_OK) ctx->last_launch.cones = !P.serve && !count && !S.blas_qnodes && S.blas_cnodes && ctx->scene.cones_in_use ? 1 : 0;
   return rc;
@@ -527,6 +593,7 @@ int do_dispatch(urt_context* ctx, int kernel, int gx, int gy, int gz, int first_
     bool top_in_front = ctx->opt.top_front < 0 ? S.n_meshes > 1 : ctx->opt.top_front != 0;
     P.serve = mode == 5 && ctx->scene.n_blas_nodes > 0;            // no triangle BVH, nothing to serve: mode 3's kernel
     P.pool_inloop = ctx->opt.serve_refill;
+    if (tile_entry_form(ctx, S, count, P.serve != 0, top_in_front)) P.blas_stack = std::max(P.blas_stack, (int)kTileEntryK);   // front_device.h tile_entry_start stores kTileEntryK - 1 entries
     int front_mode = configure_sched(ctx, S, P, top_in_front);
     P.shade_split = ctx->opt.shade_split != 0;
     set_handout(ctx, P);                                          // (batched launches: again at submission, with the launch's run length)

@@ -3,6 +3,7 @@
 // LDS copies of the object-level tables that the kernel's prologue makes (FrontLds, WalkLds; kernels.hip k_sched).
 #pragma once
 #include "frame_device.h"
+#include "tile_entry.h"      // kTileEntryK: the record tile_entry_start reads
 
 namespace {
 
@@ -147,7 +148,32 @@ __device__ __forceinline__ bool front_single(const DevScene& S, v3 o, v3 d, HitR
   return false;
 }
 
-// FRONT for multi-mesh scenes, "listed" form (front mode 2).  In trace_front<TOPF> the expensive bodies — the inline triangle tests
+// A camera ray that front_single sends into the mesh's triangle BVH starts at its tile's entries instead of the root (tile_entry.h:
+// the pre-pass has walked what all rays of the 8x8 tile have in common and dropped the children none of them can enter or keep).
+// `te`: the table, 8 dwords per tile of the whole image (width pixels wide), row by row: word 0 = the first node, words 1 .. 7 = the
+// stack above the sentinel, bottom first, padded with kBlasDone.  All 7 go to the lane's stack — the launcher guarantees that many
+// entries, and what lies above the height is free room —, the height counts the ones that are entries.  Returns false for an empty
+// list: nothing of the mesh is near any ray of the tile.  The walk that follows is the usual one: the same node steps, leaf tests and
+// tie rule on every triangle the ray can hit, so the winner is the same.
+static_assert(kTileEntryK == 8 && kTileEntryDone == kBlasDone, "tile_entry_start reads two int4 per tile");
+// the table's address: two dwords behind the launch's last frame entry (kernels.h launch_sched), read with scalar loads where it is used
+__device__ __forceinline__ const int4* launch_tile_entry_table(const FrameEntry* T, int n_frames) {
+  typedef const __attribute__((address_space(4))) unsigned int* kuintp;
+  kuintp p = (kuintp)(unsigned long long)(T + __builtin_amdgcn_readfirstlane(n_frames));
+  asm volatile("" : "+s"(p));                      // opaque to LICM: the load stays at its use, not in two scalar registers across the trace loop
+  return (const int4*)(((unsigned long long)p[1] << 32) | (unsigned long long)p[0]);
+}
+__device__ __forceinline__ bool tile_entry_start(const int4* __restrict__ te, int width, int xy, int* bl, int32_t& cur, int& sp) {
+  const unsigned int tiles_w = ((unsigned int)width + 7u) >> 3;
+  const int4* rec = te + 2u * (((unsigned int)xy >> 19) * tiles_w + (((unsigned int)xy & 0xffffu) >> 3));
+  const int4 a = rec[0], b = rec[1];
+  cur = a.x;
+  bl[64] = a.y; bl[128] = a.z; bl[192] = a.w; bl[256] = b.x; bl[320] = b.y; bl[384] = b.z; bl[448] = b.w;
+  sp = 1 + (a.y != kBlasDone) + (a.z != kBlasDone) + (a.w != kBlasDone) + (b.x != kBlasDone) + (b.y != kBlasDone) + (b.z != kBlasDone) + (b.w != kBlasDone);
+  return a.x != kBlasDone;
+}
+
+// FRONT for multi-mesh scenes, "listed" form (front mode 2). In trace_front<TOPF> the expensive bodies — the inline triangle tests
 // of single-leaf MeshObjects (wall quads: ~150 VALU) and the walk of the LDS-resident top of a big MeshObject's BVH (~60 + 50 per
 // node) — sit INSIDE the per-lane heap-walk loop: every iteration of that loop pays for both whenever any lane of the wave
 // happens to be at such a leaf.  The object-level slab test (RS:271-291) never looks at the best hit so far, so WHICH objects a ray

@@ -24,8 +24,14 @@ hipError_t launch_persist(const DevScene& S, const FrameParams& P, float4* resul
 // front_mode: 0 = rays enter a triangle BVH through the BLAS phase only, 1 = they first walk its LDS-resident top inside FRONT,
 // 2 = listed form of 1 (needs P.lds_mesh and n_meshes <= 12), 3 = masked form of 2 (mesh heap of <= 31 nodes: P.walk_f4 float4s of walk
 // table behind S.mesh_tlas, P.lds_mesh = 0; front_device.h front_masked)
+// Behind T[n_frames - 1], where entry n_frames would start: 8 bytes, the device address of the tile entry table of the launch's one camera
+// (tile_entry.h; kTileEntryK dwords per 8x8 tile of the whole image, row by row) or 0.  With a table the camera rays of the plain single-mesh
+// form (front_mode 0, P.front_fuse 2, not counting, no quantized nodes) start their triangle-BVH walk at their tile's entries; that needs
+// P.blas_stack >= kTileEntryK.  Every other form ignores the address.
 hipError_t launch_sched(const DevScene& S, const FrameParams& P, const FrameEntry* T, float4* result, DevCounters* ctr,
                         unsigned int* next, int n_blocks, int front_mode, bool count, hipStream_t st, TraceLaunchRecord* rec);
+// tile_entry.hip: builds that table for camera (c2w, invp) and a width x height image over the scene's (centre, half extent) nodes
+hipError_t launch_tile_entry(const DevScene& S, int n_nodes, const float* c2w, const float* invp, int width, int height, int32_t* table, hipStream_t st);
 // mode 5: mode 3 with the triangle-BVH phase as a service shared by the 4 waves of a workgroup (k_serve); `mail` = 2 float4 per
 // thread of the grid (ray origin / direction of the posted rays); needs P.serve = 1 and P.block_threads = 256
 hipError_t launch_serve(const DevScene& S, const FrameParams& P, const FrameEntry* T, float4* result, DevCounters* ctr,

@@ -69,6 +69,9 @@ namespace {
 // not see this child's triangles from behind" into both child hits of every node step, in the walk of the LDS top and in the wave-wide loop.
 // The cone words ride in the nodes' two spare dwords and are 0 (never skip) while option "blas_cones" is off, so the instantiation — and its
 // name — is the same either way; the counting instantiation walks like the oracle, event for event.
+// The tile entry table (tile_entry.h) — FMODE 0 with the cone instantiation only: a camera ray that front_single sends into the mesh starts at
+// its tile's entries (front_device.h tile_entry_start).  The table's address rides behind the last entry of the frame table (0: the launch
+// has none), so that the kernel's arguments — and with them every other instantiation — stay as they are.
 template <bool COUNT, int BLOCK, int FMODE, bool MULTI, bool QN = false>
 __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, FrameParams P, const FrameEntry* __restrict__ T, float4* __restrict__ result, DevCounters* ctr,
                                                unsigned int* __restrict__ next) {
@@ -276,8 +279,15 @@ __global__ __launch_bounds__(BLOCK, URT_SCHED_OCC) void k_sched(DevScene S, Fram
       } else if (st == ST_FRONT || (!fresh_pass && st == ST_RESUME)) {
         sp = 1;
         bool need;
-        if (FMODE == 0 && fresh_pass && P.front_fuse == 2) need = front_single<COUNT>(S, o, d, best, cs, cur, lc, L);
-        else {
+        if (FMODE == 0 && fresh_pass && P.front_fuse == 2) {
+          need = front_single<COUNT>(S, o, d, best, cs, cur, lc, L);
+          if constexpr (FMODE == 0 && CONES) {
+            if (need && (kf & 0xffffff) == 0) {                 // a camera ray: from its tile's entries
+              const int4* te = launch_tile_entry_table(T, P.n_frames);
+              if (te) need = tile_entry_start(te, P.width, xy, bl, cur, sp);
+            }
+          }
+        } else {
           int check = cs & 0xff; bool seen = (cs >> 8) != 0;
           need = FMODE == 1 ? trace_front<COUNT, true, false, 1, CONES>(S, st == ST_FRONT, o, d, best, check, seen, tl, 64, cur, lc, L, top, P.top_nodes, bl, &sp)
                             : trace_front<COUNT, false, false, 1>(S, st == ST_FRONT, o, d, best, check, seen, tl, 64, cur, lc, L);

@@ -236,6 +236,7 @@ int rederive_nodes(urt_context* ctx) {
   DevScene& S = C.ds;
   S.blas_cnodes = nullptr;
   C.cones_in_use = false;
+  ctx->nodes_epoch++;                       // what was derived from the old node contents (the tile entry table) is stale
   if (C.cbuf && C.n_blas_nodes > 0) {
     URT_HIP(ctx, center_nodes(S.blas_nodes, C.n_blas_nodes, C.cbuf, touch(ctx)));
     S.blas_cnodes = C.cbuf;

@@ -222,6 +222,17 @@ class Context:
         self.check(self.lib.urt_debug_read_scene_cones(self._h, words.ctypes.data_as(C.c_void_p), edges.ctypes.data_as(C.c_void_p), C.byref(use)))
         return words, edges[:, :3].copy(), edges[:, 3:].copy(), bool(use.value)
 
+    def read_tile_entry(self):
+        """(table[tiles_y, tiles_x, k] i32, builds) — the tile entry table of option "tile_entry" as the last launch that used one read it
+        (include/urt.h urt_debug_read_tile_entry): per 8x8 tile of the image the node codes its camera rays start from, padded with
+        -2^31; an empty (0, 0, 0) array while the context holds no table.  builds: tables built since the context was created."""
+        tx, ty, k, builds = C.c_int(), C.c_int(), C.c_int(), C.c_uint64()
+        self.check(self.lib.urt_debug_read_tile_entry(self._h, None, 0, C.byref(tx), C.byref(ty), C.byref(k), C.byref(builds)))
+        table = np.zeros((ty.value, tx.value, k.value), dtype=np.int32)
+        if table.size:
+            self.check(self.lib.urt_debug_read_tile_entry(self._h, table.ctypes.data_as(C.c_void_p), table.size, None, None, None, None))
+        return table, builds.value
+
     def ray_query(self, origins, directions, t_max=None, any_hit: bool = False):
         """Batched ray queries against the bound scene (include/urt.h urt_ray_query): what the frame kernels' Trace (RS:364-383)
         returns for each ray, bounded by t_max (exclusive; None = +inf; a scalar or one value per ray).
