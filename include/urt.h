@@ -967,6 +967,74 @@ typedef struct urt_DofParams {          /* 16 bytes */
 #define URT_DOF_DEFAULT_FLAGS 0
 URT_API int urt_depth_of_field(urt_context* ctx, urt_handle src, urt_handle hit, urt_handle dst, const urt_DofParams* params);
 
+/* ---- motion blur (urt_motion_blur) -------------------------------------------------------- */
+/* A frame of the trace kernels is an instant: a host that moves something every frame and presents every frame gets a strobed image.
+ * urt_motion_blur streaks a converged image along the screen-space motion its pixels had while the shutter was open, in image space,
+ * from two images the library already produces: the `motion` image of urt_reproject / urt_reproject_objects / urt_reproject_deformed
+ * ((qx - x, qy - y, S, 0): the displacement in pixels to where the pixel's point was, S > 0 where it is valid) and the `hit` target of
+ * urt_render_aov (.w: the camera ray's hit distance, +inf for the sky).  It costs nothing when it is not called.  A host orders the
+ * calls urt_auto_exposure, urt_depth_of_field, urt_motion_blur, urt_bloom, urt_tonemap, formatted readback.  The result is an ordinary
+ * RGBA32F texture.  No new formats, no new options.
+ *
+ * urt_motion_blur(ctx, src, motion, hit, dst, params): src, motion, hit and dst RGBA32F textures of one size W x H, row 0 at the
+ * bottom; of hit only .w is read, of motion .xyz.  dst is none of the three inputs: the gather reads neighbours, there is no in-place
+ * form.  (The inputs may be one another.)
+ *
+ * Arithmetic (normative): float32 with one rounding per operation, no fma, expressions evaluated as written; division is IEEE; f_sqrt
+ * of urt_math.h is the correctly rounded square root; fminf / fmaxf are C's (of a NaN and a number, the number); ceilf / floorf are
+ * C's; there are no other transcendentals.  With h = shutter * 0.5f and R = max_radius:
+ *  1. Class of the pixel p.  z_p = hit[p].w, c_p = src[p].rgb.  p PASSES THROUGH when z_p is NaN or not > 0, or when a component of c_p
+ *     is not finite or exceeds 2^100 in magnitude: dst[p] = src[p] bit for bit, p is never a tap of another pixel and never decides a
+ *     tile's velocity.  Every other pixel is a MOVING pixel, even at velocity 0; a distance of +inf (the sky) is one.
+ *  2. Velocity of a moving pixel, in pixels, to either side of it.  t = motion[p]; when t.x and t.y are finite and t.z > 0,
+ *     v = (h * t.x, h * t.y), else v = (0, 0).  l = f_sqrt(v.x*v.x + v.y*v.y); when l > R: s = R / l, v = (v.x * s, v.y * s).  Then
+ *     per component v.c = fminf(fmaxf(v.c, -R), R): whatever the rounding, no tap offset exceeds 16.  Finally
+ *     m_p = v.x*v.x + v.y*v.y and l_p = f_sqrt(m_p).  (A vector so long that the first sum overflows has l = inf, s = 0 and ends as
+ *     v = 0: it is no motion a shutter could show.)  A pass-through pixel has m_p = -1.
+ *  3. Tile velocity.  Tiles are 16 x 16 pixels, anchored at pixel (0, 0), ragged at the right and the top edge.  A tile's dominant pixel
+ *     is the one with the largest m, among equal m the one with the lowest y * W + x; the tile carries its v and m.  A tile of
+ *     pass-through pixels only has m = -1 and v = (+0, +0).  (An order-free maximum over a (value, index) key.)
+ *  4. Neighbourhood velocity.  Of the tiles of a tile's 3 x 3 neighbourhood that lie inside the image, the one with the largest m,
+ *     among equal m the first in the order dy ascending, then dx ascending: its v is n, its m is mn.
+ *  5. Still tiles.  When mn is not >= 0.25f (nothing within reach moves half a pixel) every pixel of the tile gets dst[p] = src[p] bit
+ *     for bit.
+ *  6. Gather, everywhere else, for a moving pixel p.  M = (int)ceilf(fmaxf(fabsf(n.x), fabsf(n.y))), which is 1 .. 16.  For
+ *     k = -M .. M ascending: dx = (int)floorf(((float)k * n.x) / (float)M + 0.5f), dy likewise from n.y.  A k whose (dx, dy) equals
+ *     that of k - 1 is skipped (a repeated pixel of the line).  q = p + (dx, dy) is skipped when it lies outside the image or passes
+ *     through.  Otherwise
+ *       d   = f_sqrt((float)(dx*dx + dy*dy))
+ *       ae  = (z_q < z_p) ? fmaxf(l_q, 0.5f) : fmaxf(l_p, 0.5f)
+ *       cov = fminf(fmaxf(1.0f - d / ae, 0.0f), 1.0f)
+ *       w   = cov / ae
+ *     (what lies in front of p reaches it as far as ITS streak goes; what lies at or behind p's depth shows through as far as p's OWN
+ *     streak makes p transparent: a still foreground stays sharp over a moving background, a moving foreground smears over a still
+ *     background).  A tap whose cov is not > 0 is SKIPPED — it is not added as zero.  Over the remaining taps, in that order, from
+ *     +0.0f: S = S + w and A.c = A.c + w * c_q.c per colour channel.  k = 0 is the own tap with cov = 1, so S > 0; w <= 2 and there
+ *     are at most 33 taps, so with the 2^100 bound no sum reaches FLT_MAX.
+ *  7. Output: dst[p].c = A.c / S per colour channel; alpha is src[p].a, bit for bit.  With URT_MOTION_BLUR_FLAG_VELOCITY
+ *     dst[p].rgb = (n.x, n.y, l_p) instead, (n.x, n.y, 0) at a pass-through pixel, still tiles included (they are written, not
+ *     copied); alpha as before.  One pixel's sum is never split or tree-reduced: the order is the specification.
+ * Calls, as urt_depth_of_field: an observer — it submits the deferred frames first, then enqueues on the context's stream and returns
+ * without synchronising; dst counts as written by others.  The scene is not read (not prepared); urt_counters are not changed.  The
+ * intermediates live in grow-only scratch of the context.  params == NULL means the defaults below.  Every argument is checked before
+ * anything is enqueued or allocated for the call: on any error nothing is written.
+ *  - URT_ERR_INVALID_ARGUMENT: ctx NULL; shutter not finite or outside [0, 1]; max_radius not in [0.5, 16] (NaN fails the test);
+ *    unknown flag bits; reserved != 0; textures of different sizes; dst == src, motion or hit; dst bound as _SkyboxTexture; textures
+ *    taller than 1048560 pixels.
+ *  - URT_ERR_INVALID_HANDLE: src, motion, hit or dst 0 or unknown. */
+#define URT_MOTION_BLUR_FLAG_VELOCITY 1   /* dst.rgb = (n.x, n.y, l_p): the tile neighbourhood's dominant velocity and the pixel's own length */
+#define URT_MOTION_BLUR_MAX_RADIUS 16.0f
+typedef struct urt_MotionBlurParams {     /* 16 bytes */
+  float shutter;      /* finite, 0 .. 1: the part of the frame interval the shutter is open; the streak is shutter * |motion| long */
+  float max_radius;   /* 0.5 .. URT_MOTION_BLUR_MAX_RADIUS: no pixel streaks further than this to either side, in pixels */
+  int32_t flags;      /* URT_MOTION_BLUR_FLAG_* */
+  int32_t reserved;   /* 0 */
+} urt_MotionBlurParams;
+#define URT_MOTION_BLUR_DEFAULT_SHUTTER 0.5f
+#define URT_MOTION_BLUR_DEFAULT_MAX_RADIUS 16.0f
+URT_API int urt_motion_blur(urt_context* ctx, urt_handle src, urt_handle motion, urt_handle hit, urt_handle dst,
+                            const urt_MotionBlurParams* params);
+
 /* ---- bloom -------------------------------------------------------------------------------- */
 /* The step between the exposure and the tone mapping: an emitter or the sun of an HDR sky lies many stops above white, and after
  * urt_tonemap it is a hard-edged white disc.  urt_bloom spreads what lies above a threshold over its surroundings, in linear radiance,

@@ -255,6 +255,20 @@ internal static class UrtNative {
     internal const int DofDefaultFlags = 0;
     [DllImport(Lib)] internal static extern int urt_depth_of_field(IntPtr ctx, ulong src, ulong hit, ulong dst, in DofParams p);
 
+    // ---- motion blur (include/urt.h "motion blur"): between the depth of field and the bloom, reads the motion image of urt_reproject*
+    // and the hit target of urt_render_aov ----
+    internal const int MotionBlurFlagVelocity = 1;
+    internal const float MotionBlurMaxRadius = 16.0f;
+    [StructLayout(LayoutKind.Sequential)]
+    internal struct MotionBlurParams {                      // urt_MotionBlurParams, 16 B
+        public float shutter;                               // finite, 0 .. 1: the part of the frame interval the shutter is open
+        public float maxRadius;                             // 0.5 .. MotionBlurMaxRadius
+        public int flags;                                   // MotionBlurFlag*
+        public int reserved;                                // 0
+    }
+    internal const float MotionBlurDefaultShutter = 0.5f, MotionBlurDefaultMaxRadius = 16.0f;
+    [DllImport(Lib)] internal static extern int urt_motion_blur(IntPtr ctx, ulong src, ulong motion, ulong hit, ulong dst, in MotionBlurParams p);
+
     // ---- bloom (include/urt.h "bloom"): between the metering and the tone mapping, reads the same exposure state ----
     internal const int BloomFlagOnly = 1;
     [StructLayout(LayoutKind.Sequential)]

@@ -519,6 +519,39 @@ public static class UrtDepthOfField {
     }
 }
 
+/// Motion blur (include/urt.h urt_motion_blur) over device images the engine owns, all ARGBFloat of one size: Apply writes `src`
+/// streaked along the motion of the open shutter into `dst` (none of src, motion and hit).  `motion` is the motion image of
+/// urt_reproject / urt_reproject_objects / urt_reproject_deformed for the edit the frame shows, `hit` the hit target of urt_render_aov for
+/// the same camera.  Per presented frame: UrtToneMapper.Meter(src), UrtDepthOfField.Apply(src, hit, tmp), UrtMotionBlur.Apply(tmp, motion,
+/// hit, dst), UrtBloom.Apply(dst, dst), UrtToneMapper.ToneMap(dst, dst), then the RGBA8 sRGB readback of dst.  A frame nothing moved in
+/// skips the call.  Defaults: include/urt.h URT_MOTION_BLUR_DEFAULT_*.
+public static class UrtMotionBlur {
+    static IntPtr boundCtx = IntPtr.Zero;
+    static readonly Dictionary<IntPtr, ulong> wrapped = new Dictionary<IntPtr, ulong>();
+    static int w, h;
+    static ulong Wrap(IntPtr ctx, IntPtr p, int width, int height) {  // external textures, re-wrapped when the context or the size changes
+        if (boundCtx != ctx || w != width || h != height) {
+            if (boundCtx == ctx) foreach (ulong t in wrapped.Values) UrtDevice.Check(UrtNative.urt_texture_release(ctx, t));
+            wrapped.Clear();
+            boundCtx = ctx; w = width; h = height;
+        }
+        if (!wrapped.TryGetValue(p, out ulong handle)) {
+            UrtDevice.Check(UrtNative.urt_texture_create_external(ctx, width, height, p, out handle));
+            wrapped[p] = handle;
+        }
+        return handle;
+    }
+    public static void Apply(IntPtr src, IntPtr motion, IntPtr hit, IntPtr dst, int width, int height,
+                             float shutter = 0.5f, float maxRadius = 16.0f, bool showVelocity = false) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtMotionBlur: motion blur on one rank's context (urt_group_context)");
+        IntPtr ctx = UrtDevice.Handle;
+        var p = new UrtNative.MotionBlurParams { shutter = shutter, maxRadius = maxRadius,
+                                                 flags = showVelocity ? UrtNative.MotionBlurFlagVelocity : 0, reserved = 0 };
+        UrtDevice.Check(UrtNative.urt_motion_blur(ctx, Wrap(ctx, src, width, height), Wrap(ctx, motion, width, height),
+                                                  Wrap(ctx, hit, width, height), Wrap(ctx, dst, width, height), in p));
+    }
+}
+
 /// new ComputeBuffer(count, stride); .SetData(List<T>); .Release(); .count; .stride            (RM:233-252)
 public sealed class UrtComputeBuffer {
     internal ulong handle;

@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "urt_texture_create_external", "urt_texture_set_pixels", "urt_texture_get_pixels", "urt_texture_get_info", "urt_texture_read_begin", "urt_texture_read_end", "urt_texture_read_begin_format", "urt_texture_read_end_format", "urt_texture_release",
     "urt_shader_set_buffer", "urt_shader_set_texture", "urt_shader_set_matrix", "urt_shader_set_vector", "urt_shader_set_float",
     "urt_shader_set_int", "urt_shader_dispatch", "urt_shader_dispatch_rows", "urt_blit_add", "urt_blit", "urt_texture_pack_rows",
-    "urt_texture_unpack_rows", "urt_texture_unpack_rows_on", "urt_texture_pack_rows_rgb", "urt_texture_unpack_rows_rgb", "urt_ray_query", "urt_ray_query_device", "urt_radiance_query", "urt_radiance_query_device", "urt_render_aov", "urt_denoise", "urt_reproject", "urt_reproject_objects", "urt_reproject_deformed", "urt_blit_add_history", "urt_upsample", "urt_auto_exposure", "urt_tonemap", "urt_depth_of_field", "urt_bloom", "urt_select_pixels", "urt_blend_samples", "urt_resample_below", "urt_set_option", "urt_get_counters", "urt_reset_counters", "urt_debug_build_blas", "urt_debug_get_blas", "urt_debug_blas_cache_stats",
+    "urt_texture_unpack_rows", "urt_texture_unpack_rows_on", "urt_texture_pack_rows_rgb", "urt_texture_unpack_rows_rgb", "urt_ray_query", "urt_ray_query_device", "urt_radiance_query", "urt_radiance_query_device", "urt_render_aov", "urt_denoise", "urt_reproject", "urt_reproject_objects", "urt_reproject_deformed", "urt_blit_add_history", "urt_upsample", "urt_auto_exposure", "urt_tonemap", "urt_depth_of_field", "urt_motion_blur", "urt_bloom", "urt_select_pixels", "urt_blend_samples", "urt_resample_below", "urt_set_option", "urt_get_counters", "urt_reset_counters", "urt_debug_build_blas", "urt_debug_get_blas", "urt_debug_blas_cache_stats",
     "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_read_scene_cones", "urt_debug_read_tile_entry", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_deform_stats", "urt_debug_scene_cost", "urt_debug_buffer_state", "urt_debug_live_resources", "urt_debug_build_walk_table", "urt_debug_build_normals_plan", "urt_debug_build_morph_plan", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
     "urt_host_build_object_bvh", "urt_host_build_object_bvh_pairing", "urt_host_mesh_motion", "urt_host_sphere_motion", "urt_host_last_error", "urt_host_load_hdr", "urt_host_write_pfm", "urt_host_write_png", "urt_host_encode_srgb8", "urt_host_srgb8_first_floats",
     "urt_host_resize_rgba", "urt_host_io_last_error", "urt_host_log", "urt_host_log_scene_counts", "urt_host_log_tree_report", "urt_host_dump_bvh", "urt_host_dump_normals",
@@ -195,6 +195,18 @@ URT_DOF_MAX_RADIUS = 16.0
 DOF_DEFAULTS = {"focus_distance": 10.0, "scale": 8.0, "max_radius": 8.0, "flags": 0}
 
 
+class MotionBlurParams(C.Structure):
+    """urt_MotionBlurParams (include/urt.h), 16 B."""
+    _fields_ = [("shutter", C.c_float), ("max_radius", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+# the flag and the limit of urt_MotionBlurParams and the values params == NULL stands for (include/urt.h URT_MOTION_BLUR_FLAG_VELOCITY,
+# URT_MOTION_BLUR_MAX_RADIUS, URT_MOTION_BLUR_DEFAULT_*)
+URT_MOTION_BLUR_FLAG_VELOCITY = 1
+URT_MOTION_BLUR_MAX_RADIUS = 16.0
+MOTION_BLUR_DEFAULTS = {"shutter": 0.5, "max_radius": 16.0, "flags": 0}
+
+
 class BloomParams(C.Structure):
     """urt_BloomParams (include/urt.h), 28 B."""
     _fields_ = [("threshold", C.c_float), ("soft_knee", C.c_float), ("clamp", C.c_float), ("scatter", C.c_float), ("intensity", C.c_float),
@@ -324,6 +336,7 @@ def load():
         "urt_auto_exposure": ([vp, u64, u64, C.POINTER(ExposureParams), vp], i),
         "urt_tonemap": ([vp, u64, u64, C.POINTER(TonemapParams), vp], i),
         "urt_depth_of_field": ([vp, u64, u64, u64, C.POINTER(DofParams)], i),
+        "urt_motion_blur": ([vp, u64, u64, u64, u64, C.POINTER(MotionBlurParams)], i),
         "urt_bloom": ([vp, u64, u64, C.POINTER(BloomParams), vp], i),
         "urt_select_pixels": ([vp, u64, f, vp, i, pi], i),
         "urt_blend_samples": ([vp, vp, vp, i, f, u64, u64, f], i),

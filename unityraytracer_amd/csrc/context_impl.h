@@ -325,6 +325,7 @@ struct urt_context {
   urtd::DeviceBuf<unsigned int> ex_accum;     // urt_auto_exposure: the histogram's accumulators (csrc/tonemap.h), zero whenever no call is in flight
   urtd::DeviceBuf<float4> bl_pyramid;         // urt_bloom: the levels 1..L of the largest call so far, back to back (csrc/bloom.h); every call writes what it reads
   urtd::DeviceBuf<float> df_scratch;          // urt_depth_of_field: {a, z} per pixel and the tile table of the largest call so far (csrc/dof.h); every call writes what it reads
+  urtd::DeviceBuf<float> mb_scratch;          // urt_motion_blur: the tile table and {l, z} per pixel of the largest call so far (csrc/motion_blur.h); every call writes what it reads
   // Buffer mirrors (context.cpp): what a host SetData changed in a mirrored buffer travels through one of kUpSlots pinned images, used
   // round-robin; a slot is reused once the copy of its previous use has left it (event) — no wait for the stream's other work
   static constexpr int kUpSlots = 4;

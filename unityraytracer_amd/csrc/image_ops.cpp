@@ -1,6 +1,6 @@
 // image_ops.cpp — the entry points of include/urt.h that work on whole images or ray batches next to the frame loop: ray queries,
 // radiance queries, feature buffers, the denoiser, temporal reprojection, guide-driven upsampling, auto-exposure and tone mapping, depth of field,
-// bloom, resampling.
+// motion blur, bloom, resampling.
 #include "experiments.h"
 #include "context_impl.h"
 
@@ -13,6 +13,7 @@
 #include "upsample.h"
 #include "tonemap.h"
 #include "dof.h"
+#include "motion_blur.h"
 #include "bloom.h"
 
 using namespace urtd;
@@ -562,6 +563,39 @@ int urt_depth_of_field(urt_context* ctx, urt_handle src, urt_handle hit, urt_han
   const DofSettings S{P.focus_distance, P.scale, P.max_radius, P.flags};
   t[2]->other_writes = true;
   URT_HIP(ctx, launch_depth_of_field(t[0]->dev, t[1]->dev, t[2]->dev, width, height, S, ctx->df_scratch.get(), touch(ctx)));
+                                                                   // (device pointers after the flush: a Result texture may be renamed)
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+/* ---- motion blur ---- */
+// As urt_depth_of_field: every argument is checked before anything is allocated or submitted, then the scratch is grown, the deferred
+// frames are submitted and the kernels of csrc/motion_blur.hip are enqueued on the main stream.  The scene is not read and the counters
+// are not changed.
+int urt_motion_blur(urt_context* ctx, urt_handle src, urt_handle motion, urt_handle hit, urt_handle dst, const urt_MotionBlurParams* params) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  URT_GUARD_BEGIN
+  urt_MotionBlurParams P{URT_MOTION_BLUR_DEFAULT_SHUTTER, URT_MOTION_BLUR_DEFAULT_MAX_RADIUS, 0, 0};
+  if (params) P = *params;
+  if (!(P.shutter >= 0.0f && P.shutter <= 1.0f)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "motion_blur: shutter must lie in [0, 1]");
+  if (!(P.max_radius >= 0.5f && P.max_radius <= URT_MOTION_BLUR_MAX_RADIUS))
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "motion_blur: max_radius must lie in [0.5, 16]");
+  if (P.flags & ~URT_MOTION_BLUR_FLAG_VELOCITY) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "motion_blur: unknown flag bits");
+  if (P.reserved != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "motion_blur: reserved must be 0");
+  const TexArg a[4] = {{src, "src", false}, {motion, "motion", false}, {hit, "hit", false}, {dst, "dst", false}};
+  Texture* t[4];
+  if (int rc = resolve_textures(ctx, "motion_blur", a, 4, t)) return rc;
+  if (int rc = check_same_size(ctx, "motion_blur", t, 4)) return rc;
+  if (int rc = check_outputs(ctx, "motion_blur", a, 3, 4)) return rc;         // dst is none of the inputs (no in-place form) nor the sky
+  const int width = t[0]->w, height = t[0]->h;
+  if (int rc = check_height(ctx, "motion_blur", "textures", height)) return rc;
+  if (width > kMotionBlurMaxExtent) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "motion_blur: textures wider than 2^30 pixels");
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = reserve(ctx, ctx->mb_scratch, motion_blur_scratch_floats(width, height), "motion_blur: scratch allocation", ctx->stream)) return rc;
+  { int rc = flush_pending(ctx); if (rc) return rc; }
+  const MotionBlurSettings S{P.shutter, P.max_radius, P.flags};
+  t[3]->other_writes = true;
+  URT_HIP(ctx, launch_motion_blur(t[0]->dev, t[1]->dev, t[2]->dev, t[3]->dev, width, height, S, ctx->mb_scratch.get(), touch(ctx)));
                                                                    // (device pointers after the flush: a Result texture may be renamed)
   return URT_OK;
   URT_GUARD_END(ctx)

@@ -61,6 +61,7 @@ class RayTraceMaster:
     _exposure = _exposureState = _tonemapped = None             # (likewise: auto-exposure and ToneMap)
     _bloom = None                                               # (likewise: EnableBloom)
     _dof = _dofHit = None                                       # (likewise: EnableDepthOfField)
+    _mblur = _mbMotion = _mbStage = _mbAge = None               # (likewise: EnableMotionBlur)
     # With True, SkinMeshes, MorphMeshes and MoveObjects build the object-level heaps on the GPU (include/urt.h "the object-level BVH on the
     # device": urt_mesh_leaf_bounds_device / urt_sphere_leaf_bounds_device, then urt_build_object_bvh_device into the heap buffers) instead
     # of on the host, and make no synchronising call of their own.  scene.mesh_bvh / scene.sphere_bvh are then BEHIND the device, as
@@ -103,6 +104,10 @@ class RayTraceMaster:
         self._bloom = None                           # EnableBloom: the urt_BloomParams fields given (None = off)
         self._dof = None                             # EnableDepthOfField: the urt_DofParams fields given (None = off)
         self._dofHit = None                          # ToneMap with depth of field on: the hit guide of _converged's size
+        self._mblur = None                           # EnableMotionBlur: the urt_MotionBlurParams fields given (None = off)
+        self._mbMotion = None                        # motion blur: the motion image the edits' reprojection writes, of _converged's size
+        self._mbStage = None                         # ToneMap with depth of field AND motion blur on: the image between the two
+        self._mbAge = None                           # motion blur: frames rendered since _mbMotion was written (None = it holds nothing)
         self._temporal = None                        # EnableTemporalAccumulation: the reprojection settings (None = off, the reference's behaviour)
         self._tcount = self._tspare = None           # temporal: the count texture of _converged; the spare (colour, count) pair reprojection writes
         self._taov = None                            # temporal: two (hit, normal, id) sets, the previous and the new camera's
@@ -275,6 +280,8 @@ class RayTraceMaster:
             Graphics.Blit(self._converged, destination)
         self._currentSample += 1
         self._frame += 1
+        if self._mbAge is not None:
+            self._mbAge += 1
 
     # RM:848-866
     def OnRenderImage(self, destination: RenderTexture | None = None):
@@ -531,6 +538,34 @@ class RayTraceMaster:
             self._dofHit.Release()
         self._dofHit = None
 
+    # Motion blur (include/urt.h urt_motion_blur), opt-in as well and only with temporal accumulation on, whose reprojection is where
+    # the motion vectors come from: with it on, every edit that keeps history (MoveCamera, MoveObjects, DeformMeshes, SkinMeshes,
+    # MorphMeshes) has its reprojection write the motion image into a texture this master owns, and ToneMap streaks the image along it
+    # — after the depth of field, ahead of the bloom, with the hit guide the depth of field uses — while that motion is no older than
+    # one rendered frame.  A still view therefore presents unblurred; a host that edits every frame gets a streak every frame.  With
+    # it off the master issues the calls it always did.  params: the fields of urt_MotionBlurParams.  Nothing is created here.
+    def EnableMotionBlur(self, **params):
+        from .unity_api import motion_blur_params
+        motion_blur_params(**params)                                              # checked at once
+        if self._temporal is None:
+            raise ValueError("EnableMotionBlur: temporal accumulation is off (EnableTemporalAccumulation first): without a reprojection "
+                             "there are no motion vectors")
+        self._mblur = dict(params)
+
+    def DisableMotionBlur(self):
+        self._mblur = None
+        self._mbAge = None
+
+    def _release_motion_blur(self):
+        for t in (self._mbMotion, self._mbStage):
+            if t is not None:
+                t.Release()
+        self._mbMotion = self._mbStage = self._mbAge = None
+
+    def _motion_is_fresh(self) -> bool:
+        return self._mblur is not None and self._mbAge is not None and self._mbAge <= 1 and self._mbMotion is not None \
+            and (self._mbMotion.width, self._mbMotion.height) == (self._converged.width, self._converged.height)
+
     def ToneMap(self, destination: RenderTexture | None = None, operator="aces", exposure: float = 1.0, white: float = 4.0):
         from ._lib import UrtError
         from .unity_api import tonemap_params
@@ -551,12 +586,19 @@ class RayTraceMaster:
             self.ctx.auto_exposure(self._converged, self._exposureState, count, **self._exposure)
         state = self._exposureState if self._exposure is not None else None
         source = self._converged
-        if self._dof is not None:
+        streak = self._motion_is_fresh()
+        if self._dof is not None or streak:
             width, height = self._converged.width, self._converged.height
             self._bind_for_queries()
             self._dofHit = self._sized(self._dofHit, width, height)
             self._render_through_sample_centres((width, height, (self._dofHit,)))
-            self.ctx.depth_of_field(self._converged, self._dofHit, destination, **self._dof)
+        if self._dof is not None:
+            if streak:                                                            # the streak has no in-place form: it reads a stage of this master's
+                self._mbStage = self._sized(self._mbStage, width, height)
+            source = self._mbStage if streak else destination
+            self.ctx.depth_of_field(self._converged, self._dofHit, source, **self._dof)
+        if streak:
+            self.ctx.motion_blur(source, self._mbMotion, self._dofHit, destination, **self._mblur)
             source = destination
         if self._bloom is not None:
             self.ctx.bloom(source, destination, state, **self._bloom)
@@ -591,6 +633,7 @@ class RayTraceMaster:
 
     def DisableTemporalAccumulation(self):
         self._release_temporal()
+        self._mblur = None                                                    # (no reprojection, no motion vectors)
         self._temporal = None
         self._currentSample = 0
 
@@ -599,6 +642,7 @@ class RayTraceMaster:
             if t is not None:
                 t.Release()
         self._tcount = self._tspare = self._taov = None
+        self._release_motion_blur()
         for b in self._tmotion:
             if b is not None:
                 b.Release()
@@ -667,6 +711,10 @@ class RayTraceMaster:
         self.ctx.render_aov(cur[0], cur[1], None, cur[2])
         moved = {} if motion is None else self._motion_arguments(**motion)
         color, count = self._tspare
+        if self._mblur is not None:                                               # the motion image of this edit, for ToneMap's streak
+            self._mbMotion = self._sized(self._mbMotion, self._converged.width, self._converged.height)
+            moved["motion"] = self._mbMotion
+            self._mbAge = 0
         self.ctx.reproject(self._converged, self._tcount, *prev, *cur, color, count, prev_m, **moved, **self._temporal)
         self._tspare = (self._converged, self._tcount)
         self._converged, self._tcount = color, count

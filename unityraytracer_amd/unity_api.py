@@ -690,6 +690,23 @@ class Context:
         p = dof_params(**params)
         self.check(self.lib.urt_depth_of_field(self._h, src.handle, hit.handle, dst.handle, C.byref(p)))
 
+    def motion_blur(self, src, motion, hit, dst, **params):
+        """dst = src streaked along the screen-space motion of the open shutter, alpha copied (include/urt.h urt_motion_blur).  motion:
+        the motion image of reproject (the displacement in pixels to where each pixel's point was, .z > 0 where valid); hit: the hit
+        target of render_aov for the same camera.  The streak of a pixel is `shutter` times its motion long, at most `max_radius` (at
+        most _lib.URT_MOTION_BLUR_MAX_RADIUS) to either side; tiles near which nothing moves half a pixel are copied.  dst is none of
+        the inputs.  params: the fields of urt_MotionBlurParams (_lib.MOTION_BLUR_DEFAULTS); flags _lib.URT_MOTION_BLUR_FLAG_VELOCITY
+        writes the velocity each pixel is gathered along instead of the image.  Enqueued after the deferred frames, after
+        depth_of_field and ahead of bloom."""
+        _check_texture(self, "motion_blur", "src", src, src)
+        _check_texture(self, "motion_blur", "motion", motion, src)
+        _check_texture(self, "motion_blur", "hit", hit, src)
+        _check_texture(self, "motion_blur", "dst", dst, src)
+        if any(dst is t or dst.handle == t.handle for t in (src, motion, hit)):
+            raise ValueError("motion_blur: dst is also an input (there is no in-place form)")
+        p = motion_blur_params(**params)
+        self.check(self.lib.urt_motion_blur(self._h, src.handle, motion.handle, hit.handle, dst.handle, C.byref(p)))
+
     def bloom(self, src, dst, state=None, **params):
         """dst = src + intensity * bloom(src) per colour channel, alpha copied (include/urt.h urt_bloom); dst may be src.  The bloom is
         what lies above `threshold` (soft below it over `soft_knee`, held to `clamp`), taken down a pyramid of at most `levels` halved
@@ -1028,6 +1045,25 @@ def dof_params(**params) -> _lib.DofParams:
     if flags & ~_lib.URT_DOF_FLAG_COC:
         raise ValueError(f"depth_of_field: unknown flag bits in {flags}")
     return _lib.DofParams(v["focus_distance"], v["scale"], v["max_radius"], flags)
+
+
+def motion_blur_params(**params) -> _lib.MotionBlurParams:
+    """The checked urt_MotionBlurParams of Context.motion_blur: shutter finite in [0, 1], max_radius in [0.5, 16], flags 0 or
+    _lib.URT_MOTION_BLUR_FLAG_VELOCITY; what is not given is _lib.MOTION_BLUR_DEFAULTS'."""
+    unknown = set(params) - set(_lib.MOTION_BLUR_DEFAULTS)
+    if unknown:
+        raise TypeError(f"motion_blur: unknown parameters {sorted(unknown)}")
+    v = {**_lib.MOTION_BLUR_DEFAULTS, **params}
+    for name in ("shutter", "max_radius"):
+        v[name] = _float32_arg(v[name], name, "motion_blur")
+    if not 0.0 <= v["shutter"] <= 1.0:
+        raise ValueError(f"motion_blur: shutter must lie in [0, 1], not {v['shutter']}")
+    if not 0.5 <= v["max_radius"] <= _lib.URT_MOTION_BLUR_MAX_RADIUS:
+        raise ValueError(f"motion_blur: max_radius must lie in [0.5, 16], not {v['max_radius']}")
+    flags = _int_arg(v["flags"], "flags", "motion_blur")
+    if flags & ~_lib.URT_MOTION_BLUR_FLAG_VELOCITY:
+        raise ValueError(f"motion_blur: unknown flag bits in {flags}")
+    return _lib.MotionBlurParams(v["shutter"], v["max_radius"], flags, 0)
 
 
 def dof_scale(height, focus_distance, f_number=5.6, focal_length=0.05, sensor_height=0.024) -> np.float32:
