@@ -115,7 +115,12 @@ URT_API int urt_buffer_release(urt_context* ctx, urt_handle buffer);
  * leave it (when that would split the range, the part behind the written elements is downloaded first).
  * When _Vertices / _Normals were written on the device and the change is one the scene takes in place (option "refit_vertices"), the
  * dirty elements reach the scene's copies by a device-to-device copy on the context's stream: no host copy, no upload, no download.
- * Every other path (a full preparation for whatever reason) sees the device-written data through the download.
+ * A full preparation (for whatever reason: _Indices rewritten, buffers of another count bound, "refit" / "refit_vertices" off, a rebuild
+ * forced by "refit_rebuild_pct") sees the device-written data through the download by default.  With option "prepare_device" = 1 it takes
+ * _Vertices / _Indices / _Normals from their mirrors instead — a device-to-device copy on the context's stream into the scene's own copies,
+ * a build on the GPU, the MeshObjects' vertex spans found on the GPU (csrc/index_span.hip): none of the three is downloaded, their stale
+ * ranges stay, and a buffer that was only ever written on the device needs no host SetData at all.  The small tables (_MeshObjects,
+ * _MeshBVH, _Spheres, _SphereBVH) are packed on the host either way and come down first when they were written on the device.
  * urt_buffer_release and urt_context_destroy give the mirror back.  There are no urt_group_* twins of the calls of this section: a group
  * host reaches the ranks' contexts through urt_group_context. */
 /* Ranged SetData whose source is DEVICE memory (4-byte aligned): the copy is enqueued on the context's stream and the call returns
@@ -1195,6 +1200,12 @@ typedef struct urt_counters {
  *                            taken in place: only the changed element range is copied to the device, and the MeshObjects whose vertex
  *                            span it meets are refitted / get their shading normals re-gathered; 0 = such a change prepares from scratch,
  *                            matrix moves are still refitted — see urt_debug_deform_stats),
+ *          "prepare_device" (0/1, default 0: 1 = a full preparation reads _Vertices / _Indices / _Normals from their device mirrors (a buffer
+ *                            without one is uploaded from its host copy, which is current then): no download of the three and no host
+ *                            pass over them, their stale ranges and download counters stay as they are.  The triangle BVHs are then
+ *                            always built on the GPU — by the builder "blas_builder" names when it is >= 1, else by 3 — and the
+ *                            MeshObjects' vertex spans come from csrc/index_span.hip; same pixels.  See "the device side of a
+ *                            ComputeBuffer", urt_debug_scene_vertex_spans and urt_debug_prepare_stats),
  *          "refit_rebuild_pct" (0, the default = never | > 100: when the surface-area cost of a deformed MeshObject's refitted tree exceeds
  *                               pct / 100 x the cost it had at the last full preparation, the in-place update is abandoned and the scene is
  *                               prepared from scratch — see urt_debug_scene_cost),
@@ -1439,6 +1450,18 @@ URT_API int urt_debug_deform_stats(urt_context* ctx, uint64_t out6[6]);
  * count for a leaf, 1 for a node) / area(root box); 0 for a MeshObject without nodes or with a root box of zero or non-finite area.
  * per MeshObject: cost now and baseline cost (2 floats each); prepares a stale scene first */
 URT_API int urt_debug_scene_cost(urt_context* ctx, float* out, int n_meshes);
+/* The vertex spans the prepared scene holds: per MeshObject the signed minimum (out_lo) and maximum (out_hi) of
+ * _Indices[indices_offset .. indices_offset + (indices_count / 3) * 3 - 1], INT32_MAX / -1 for a MeshObject with fewer than three indices.
+ * A changed range of _Vertices / _Normals deforms the MeshObjects whose span it meets (option "refit_vertices").  The full preparation
+ * computes them: on the host from the host copy of _Indices, with option "prepare_device" on the GPU from the scene's device copy.
+ * Every entry is INT32_MAX / -1 when the scene kept none ("refit" = 0, or no triangles).  Prepares a stale scene first, as
+ * urt_debug_scene_info does, and nothing more.  URT_ERR_INVALID_ARGUMENT: a NULL pointer, or n_meshes is not the scene's number of MeshObjects. */
+URT_API int urt_debug_scene_vertex_spans(urt_context* ctx, int32_t* out_lo, int32_t* out_hi, int n_meshes);
+/* Full preparations of this context: out4 = those completed since the context was created, those of them that option "prepare_device"
+ * fed from device memory, the number of indices one work item of the vertex-span kernel scans (csrc/index_span.h kSpanChunk), and — as
+ * float bits, in milliseconds, measured with events while option "time_dispatch" is on, else 0 — the device time of the last span pass.
+ * Prepares nothing. */
+URT_API int urt_debug_prepare_stats(urt_context* ctx, uint64_t out4[4]);
 /* What the library holds right now, PROCESS-WIDE (every context and group of the process; needs none): out4 = device bytes, pinned host
  * bytes, events, streams.  Counts only the library's own holders (csrc/owned.h) — not external textures, the caller's streams or what
  * the HIP runtime keeps for itself.  A context or group that is destroyed gives back everything it took. */

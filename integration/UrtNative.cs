@@ -346,6 +346,8 @@ internal static class UrtNative {
     [DllImport(Lib)] internal static extern int urt_debug_refit_stats(IntPtr ctx, out ulong refittedMeshes, out ulong incrementalPreparations);
     [DllImport(Lib)] internal static extern int urt_debug_deform_stats(IntPtr ctx, [Out] ulong[] out6);   // deformed, renormed, bytes copied, forced rebuilds, cost-ratio float bits, 0
     [DllImport(Lib)] internal static extern int urt_debug_scene_cost(IntPtr ctx, [Out] float[] out2PerMesh, int nMeshes);
+    [DllImport(Lib)] internal static extern int urt_debug_scene_vertex_spans(IntPtr ctx, [Out] int[] outLo, [Out] int[] outHi, int nMeshes);   // INT32_MAX / -1: none
+    [DllImport(Lib)] internal static extern int urt_debug_prepare_stats(IntPtr ctx, [Out] ulong[] out4);   // full preparations, device-fed ones, span chunk, span ms float bits
     [DllImport(Lib)] internal static extern int urt_debug_live_resources([Out] ulong[] out4);   // process-wide: device bytes, pinned bytes, events, streams
     [DllImport(Lib)] internal static extern int urt_host_mesh_motion(IntPtr prevMeshObjects, IntPtr curMeshObjects, int n, IntPtr outMotion);   // 48 B per entry
     [DllImport(Lib)] internal static extern int urt_host_sphere_motion(IntPtr prevSpheres, IntPtr curSpheres, int n, IntPtr outMotion);

@@ -625,6 +625,40 @@ public sealed class UrtObjectHeaps {
     }
 }
 
+/// Geometry that is made on the GPU (an LOD switch, procedural or re-meshed geometry): RayTraceMaster.ReplaceGeometryDevice and
+/// device_prepare of the Python mirror (include/urt.h "the device side of a ComputeBuffer", option "prepare_device").  It owns the three
+/// geometry buffers a host binds as _Vertices / _Indices / _Normals; with DevicePrepare on, the full preparation that new topology asks
+/// for reads them where they are: nothing is downloaded, and the triangle BVHs are built on the GPU.  On one context only, as UrtSkinnedMesh.
+public sealed class UrtDeviceGeometry {
+    public UrtComputeBuffer vertices, indices, normals;
+    /// Option "prepare_device" of the context (off by default: a full preparation downloads device-written geometry first).
+    public static void SetDevicePrepare(bool on) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtDeviceGeometry: set the option on one rank's context (urt_group_context)");
+        UrtDevice.Check(UrtNative.urt_set_option(UrtDevice.Handle, "prepare_device", on ? 1 : 0));
+    }
+    static UrtComputeBuffer FromDevice(UrtComputeBuffer b, IntPtr deviceData, int count, int stride) {
+        if (b != null && b.count != count) { b.Release(); b = null; }                 // a buffer whose count fits is reused
+        if (b == null) b = new UrtComputeBuffer(count, stride);                       // else a new one, with this write as its first and only
+        UrtDevice.Check(UrtNative.urt_buffer_set_data_device(UrtDevice.Handle, b.handle, 0, deviceData, count));
+        return b;
+    }
+    /// The three lists from device memory (4-byte aligned addresses, element counts; the copies are enqueued on the context's stream and
+    /// the caller orders their producers).  The caller then binds the buffers, sets _MeshObjects through SetData, supplies _MeshBVH
+    /// (UrtObjectHeaps.RebuildObjectHeapsOnDevice builds it without a host pass) and restarts its accumulation: topology changed, so no
+    /// history is kept.
+    public void ReplaceGeometryDevice(IntPtr deviceVertices, int nVertices, IntPtr deviceIndices, int nIndices, IntPtr deviceNormals, int nNormals) {
+        if (UrtDevice.IsGroup) throw new InvalidOperationException("UrtDeviceGeometry: replace on one rank's context (urt_group_context)");
+        vertices = FromDevice(vertices, deviceVertices, nVertices, 12);
+        indices = FromDevice(indices, deviceIndices, nIndices, 4);
+        normals = FromDevice(normals, deviceNormals, nNormals, 12);
+    }
+    public void Release() {
+        if (vertices != null) { vertices.Release(); vertices = null; }
+        if (indices != null) { indices.Release(); indices = null; }
+        if (normals != null) { normals.Release(); normals = null; }
+    }
+}
+
 /// A skinned mesh animated on the GPU: RayTraceMaster.AttachSkin / SkinMeshes of the Python mirror (include/urt.h urt_skin_vertices,
 /// urt_buffer_bounds).  One instance serves every skinned MeshObject of a scene: it owns rest-pose, bone-index and bone-weight buffers of
 /// the vertex count and one bone table per mesh.  Per frame only the bones travel; the positions are written into the device side of the

@@ -22,7 +22,7 @@ ABI_SYMBOLS = [
     "urt_shader_set_buffer", "urt_shader_set_texture", "urt_shader_set_matrix", "urt_shader_set_vector", "urt_shader_set_float",
     "urt_shader_set_int", "urt_shader_dispatch", "urt_shader_dispatch_rows", "urt_blit_add", "urt_blit", "urt_texture_pack_rows",
     "urt_texture_unpack_rows", "urt_texture_unpack_rows_on", "urt_texture_pack_rows_rgb", "urt_texture_unpack_rows_rgb", "urt_ray_query", "urt_ray_query_device", "urt_radiance_query", "urt_radiance_query_device", "urt_render_aov", "urt_denoise", "urt_reproject", "urt_reproject_objects", "urt_reproject_deformed", "urt_blit_add_history", "urt_upsample", "urt_auto_exposure", "urt_tonemap", "urt_depth_of_field", "urt_motion_blur", "urt_bloom", "urt_select_pixels", "urt_blend_samples", "urt_resample_below", "urt_set_option", "urt_get_counters", "urt_reset_counters", "urt_debug_build_blas", "urt_debug_get_blas", "urt_debug_blas_cache_stats",
-    "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_read_scene_cones", "urt_debug_read_tile_entry", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_deform_stats", "urt_debug_scene_cost", "urt_debug_buffer_state", "urt_debug_live_resources", "urt_debug_build_walk_table", "urt_debug_build_normals_plan", "urt_debug_build_morph_plan", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
+    "urt_debug_scene_info", "urt_debug_launch_info", "urt_debug_read_scene_blas", "urt_debug_read_scene_qnodes", "urt_debug_read_scene_cones", "urt_debug_read_tile_entry", "urt_debug_serve_stats", "urt_debug_refit_stats", "urt_debug_deform_stats", "urt_debug_scene_cost", "urt_debug_scene_vertex_spans", "urt_debug_prepare_stats", "urt_debug_buffer_state", "urt_debug_live_resources", "urt_debug_build_walk_table", "urt_debug_build_normals_plan", "urt_debug_build_morph_plan", "urt_host_compute_normals", "urt_host_mesh_leaf_bounds", "urt_host_sphere_leaf_bounds", "urt_host_object_bvh_length",
     "urt_host_build_object_bvh", "urt_host_build_object_bvh_pairing", "urt_host_mesh_motion", "urt_host_sphere_motion", "urt_host_last_error", "urt_host_load_hdr", "urt_host_write_pfm", "urt_host_write_png", "urt_host_encode_srgb8", "urt_host_srgb8_first_floats",
     "urt_host_resize_rgba", "urt_host_io_last_error", "urt_host_log", "urt_host_log_scene_counts", "urt_host_log_tree_report", "urt_host_dump_bvh", "urt_host_dump_normals",
     "urt_host_debug_last_error",
@@ -353,6 +353,8 @@ def load():
         "urt_debug_refit_stats": ([vp, vp, vp], i),
         "urt_debug_deform_stats": ([vp, vp], i),
         "urt_debug_scene_cost": ([vp, vp, i], i),
+        "urt_debug_scene_vertex_spans": ([vp, vp, vp, i], i),
+        "urt_debug_prepare_stats": ([vp, vp], i),
         "urt_debug_live_resources": ([vp], i),
         "urt_debug_build_walk_table": ([vp, i, i, vp, vp, vp, i, pi], i),
         "urt_host_dump_normals": ([C.c_char_p, vp, i, vp, i, vp, i, vp, i, pi], i),

@@ -15,6 +15,7 @@
 #include <limits>
 #include <memory>
 
+#include "index_span.h"
 #include "morph.h"
 #include "morph_plan.h"
 #include "object_bvh.h"
@@ -1194,6 +1195,7 @@ const OptionRow kOptions[] = {
   {"handout", &O::handout, -1, 1, "handout must be -1 (auto), 0 or 1", 0, nullptr},
   {"refit", &O::refit, INT_MIN, INT_MAX, "", kBool | kStale, nullptr},
   {"refit_vertices", &O::refit_vertices, INT_MIN, INT_MAX, "", kBool, nullptr},
+  {"prepare_device", &O::prepare_device, INT_MIN, INT_MAX, "", kBool | kStale, nullptr},
   {"refit_rebuild_pct", &O::refit_rebuild_pct, 0, INT_MAX, "refit_rebuild_pct must be 0 (never rebuild) or greater than 100", 0, [](int v) { return v == 0 || v > 100; }},
   {"watchdog_cap", &O::watchdog_cap, 0, INT_MAX, "watchdog_cap must be >= 0 (0 = auto)", 0, nullptr},
   {"xcd_run", &O::xcd_run, 0, 4096, "xcd_run must be in [0, 4096] (0 = auto)", 0, nullptr},
@@ -1380,6 +1382,31 @@ int urt_debug_scene_info(urt_context* ctx, int* out_n_nodes, int* out_n_tris, in
   if (out_prepare_ms) *out_prepare_ms = ctx->last_prepare_ms;
   return URT_OK;
   URT_GUARD_END(ctx)
+}
+
+int urt_debug_scene_vertex_spans(urt_context* ctx, int32_t* out_lo, int32_t* out_hi, int n_meshes) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (n_meshes < 0 || (n_meshes > 0 && (!out_lo || !out_hi))) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "urt_debug_scene_vertex_spans: out_lo / out_hi is NULL or n_meshes negative");
+  URT_GUARD_BEGIN
+  URT_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = current_scene(ctx)) return rc;
+  if (n_meshes != ctx->scene.ds.n_meshes) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "urt_debug_scene_vertex_spans: n_meshes is not the scene's number of MeshObjects");
+  const bool kept = ctx->scene.h_vert_lo.size() == (size_t)n_meshes && ctx->scene.h_vert_hi.size() == (size_t)n_meshes;
+  for (int m = 0; m < n_meshes; m++) {
+    out_lo[m] = kept ? ctx->scene.h_vert_lo[(size_t)m] : INT32_MAX;
+    out_hi[m] = kept ? ctx->scene.h_vert_hi[(size_t)m] : -1;
+  }
+  return URT_OK;
+  URT_GUARD_END(ctx)
+}
+
+int urt_debug_prepare_stats(urt_context* ctx, uint64_t out4[4]) {
+  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  if (!out4) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "out4 is NULL");
+  uint32_t ms_bits;
+  std::memcpy(&ms_bits, &ctx->last_span_ms, 4);
+  out4[0] = ctx->full_preps; out4[1] = ctx->device_preps; out4[2] = (uint64_t)kSpanChunk; out4[3] = ms_bits;
+  return URT_OK;
 }
 
 int urt_debug_read_scene_blas(urt_context* ctx, float* nodes, int32_t* tri_index, int32_t* mesh_root) {

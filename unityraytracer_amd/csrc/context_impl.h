@@ -116,6 +116,8 @@ struct urt_context {
     int refit = 1;                          // 0 = always prepare from scratch
     int refit_vertices = 1;                 // 0 = changed _Vertices / _Normals prepare from scratch (matrix moves are still refitted)
     int refit_rebuild_pct = 0;              // a deformed MeshObject whose tree cost exceeds pct / 100 x its baseline forces a full preparation (0 = never, else > 100)
+    int prepare_device = 0;                 // 1 = a full preparation takes _Vertices / _Indices / _Normals from their device mirrors (no download, no host pass over them)
+                                            // and always builds on the GPU: the builder asked for when blas_builder >= 1, else 3 (scene_prep.cpp prepare_scene)
     int qnodes = 0;                         // 32-byte quantized nodes in the traversal loop: 0 = off (default: measured -1.3 % on C3 / C3D, +1.3 % on C4 / C5 — the loop waits on the latency of ONE dependent fetch per step, not on its width), 1 = on, -1 = on unless a MeshObject is only a few grid cells wide
     int count_stats = 0, time_dispatch = 0, kernel_mode = 3;
     int block_threads = 64, xcd_run = 0 /* auto */, work_shards = 64, frame_group = 64, refill_min = 16, waves_per_cu = 0 /* auto */, blas_min = 0 /* auto */, blas_exit = 0 /* auto */;
@@ -206,6 +208,8 @@ struct urt_context {
   uint64_t refitted_meshes = 0, incremental_preps = 0;
   uint64_t deformed_meshes = 0, renormed_meshes = 0, deform_bytes = 0, forced_rebuilds = 0;   // urt_debug_deform_stats
   float last_cost_ratio = 0;                // largest cost / baseline among the deformed MeshObjects of the last in-place update
+  uint64_t full_preps = 0, device_preps = 0; // full preparations completed; those of them that option "prepare_device" fed from device memory (urt_debug_prepare_stats)
+  float last_span_ms = 0;                   // option "time_dispatch": device time of the last vertex-span pass of a device-fed preparation (csrc/index_span.hip), else 0
   urtd::BlasCache blas_cache;               // per-MeshObject BVHs of the previous scene (reused when a MeshObject is unchanged)
   uint64_t nodes_epoch = 0;                 // bumps whenever the nodes the trace kernels read are rewritten (scene_prep.cpp rederive_nodes): builds, refits, cones
   // The tile entry table (csrc/tile_entry.h, option "tile_entry"): one table, for the camera, image size and node contents of `te_key`; a launch

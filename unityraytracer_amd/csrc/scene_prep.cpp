@@ -7,6 +7,7 @@
 #include <chrono>
 
 #include "lbvh.h"
+#include "index_span.h"
 #include "refit.h"
 #include "qnodes.h"
 #include "cones.h"
@@ -519,7 +520,11 @@ int prepare_scene(urt_context* ctx) {
     int rc = prepare_incremental(ctx);
     if (rc != 1) return rc;                                 // updated in place (or failed)
   }
-  if (int rc = sync_bound_hosts(ctx, (1u << B_COUNT) - 1u)) return rc;   // everything below reads the host copies: device-written data come down first
+  // Everything below reads the host copies, so device-written data come down first — except, with option "prepare_device", the three
+  // geometry buffers: the GPU builder takes them from their mirrors, their host copies are not read and their stale ranges stay as they are.
+  const bool from_device = ctx->opt.prepare_device != 0;
+  const unsigned int geometry_slots = (1u << B_VERTICES) | (1u << B_INDICES) | (1u << B_NORMALS);
+  if (int rc = sync_bound_hosts(ctx, ((1u << B_COUNT) - 1u) & ~(from_device ? geometry_slots : 0u))) return rc;
   free_scene(ctx);
   urt_context::Scene& C = ctx->scene;
   DevScene& S = C.ds;
@@ -534,6 +539,7 @@ int prepare_scene(urt_context* ctx) {
   // meshes: the triangle BVH ("BLAS") of every MeshObject, by the host SAH builder or by the GPU LBVH builder
   auto t_begin = std::chrono::steady_clock::now();
   std::vector<int32_t> mesh_root_host, small_first;
+  std::vector<int32_t> span_lo_hi;                           // option "prepare_device": (lo, hi) per MeshObject from csrc/index_span.hip
   int blas_max_depth = 0;
   size_t n_blas_nodes = 0, n_tris = 0;
   if (n_meshes > 0) {
@@ -549,6 +555,7 @@ int prepare_scene(urt_context* ctx) {
     constexpr long kGpuBuildTriangles = 200000;
     int builder = ctx->opt.blas_builder;
     if (builder < 0) builder = tris >= kGpuBuildTriangles ? 3 : 0;
+    if (from_device && builder < 1) builder = 3;             // the host builder is host-fed; pixels do not depend on the tree
     ctx->last_builder = builder;
     if (builder >= 1) {
       // device copies of the buffers exactly as SetData delivered them; the whole build runs on the GPU (csrc/lbvh.hip)
@@ -558,11 +565,40 @@ int prepare_scene(urt_context* ctx) {
       size_t b_n = bn ? (((size_t)bn->count * 12 + 255) & ~(size_t)255) : 0;
       URT_HIP(ctx, raw.alloc(b_mo + b_v + b_i + b_n + 256));
       char* rb = raw.get();
+      // A geometry buffer reaches the scene's own copy from its host copy — or, with option "prepare_device", from its mirror: device to
+      // device on the stream, ahead of the build; the mirror is current by construction, the host copy may be stale and is not read.  (A buffer
+      // without a mirror has never been written on the device: its host copy is current.)  The scene never aliases a mirror: frames in
+      // flight and the refit read these copies.
+      auto feed = [&](const Buffer* b, char* dst, size_t bytes) -> hipError_t {
+        if (from_device && b->mirror) return hipMemcpyAsync(dst, b->mirror.get(), bytes, hipMemcpyDeviceToDevice, touch(ctx));
+        return hipMemcpy(dst, b->host.data(), bytes, hipMemcpyHostToDevice);
+      };
       hipError_t e = hipMemcpy(rb, bm->host.data(), (size_t)n_meshes * URT_STRIDE_MESHOBJECT, hipMemcpyHostToDevice);
-      if (e == hipSuccess && bv) e = hipMemcpy(rb + b_mo, bv->host.data(), (size_t)bv->count * 12, hipMemcpyHostToDevice);
-      if (e == hipSuccess && bi) e = hipMemcpy(rb + b_mo + b_v, bi->host.data(), (size_t)bi->count * 4, hipMemcpyHostToDevice);
-      if (e == hipSuccess && bn) e = hipMemcpy(rb + b_mo + b_v + b_i, bn->host.data(), (size_t)bn->count * 12, hipMemcpyHostToDevice);
+      if (e == hipSuccess && bv) e = feed(bv, rb + b_mo, (size_t)bv->count * 12);
+      if (e == hipSuccess && bi) e = feed(bi, rb + b_mo + b_v, (size_t)bi->count * 4);
+      if (e == hipSuccess && bn) e = feed(bn, rb + b_mo + b_v + b_i, (size_t)bn->count * 12);
       if (e != hipSuccess) return fail(ctx, URT_ERR_HIP, std::string("scene upload: ") + hipGetErrorString(e));
+      // The vertex spans of a device-fed preparation (kept below for prepare_incremental) come from the scene's copy of _Indices
+      // (csrc/index_span.hip): queued here, ahead of the build, and read back after the wait the build ends with.  Ranges outside _Indices
+      // queue nothing: the build refuses them.
+      DeviceBuf<char> span_mem;
+      std::vector<SpanItem> span_tab;
+      Event span_t0, span_t1;
+      size_t b_tab = 0;
+      bool spans_queued = false;
+      if (from_device && ctx->opt.refit && tris > 0 && bv && bi && span_items(offs.data(), cnts.data(), n_meshes, bi->count, span_tab)) {
+        b_tab = (span_tab.size() * sizeof(SpanItem) + 255) & ~(size_t)255;
+        URT_HIP(ctx, span_mem.alloc(b_tab + (size_t)n_meshes * 8));
+        URT_HIP(ctx, hipMemcpy(span_mem.get(), span_tab.data(), span_tab.size() * sizeof(SpanItem), hipMemcpyHostToDevice));
+        if (ctx->opt.time_dispatch) {
+          URT_HIP(ctx, span_t0.create(hipEventDefault)); URT_HIP(ctx, span_t1.create(hipEventDefault));
+          URT_HIP(ctx, hipEventRecord(span_t0.get(), touch(ctx)));
+        }
+        URT_HIP(ctx, index_spans((const int32_t*)(rb + b_mo + b_v), (const SpanItem*)span_mem.get(), (int)span_tab.size(),
+                                 (int32_t*)(span_mem.get() + b_tab), n_meshes, touch(ctx)));
+        if (span_t1) URT_HIP(ctx, hipEventRecord(span_t1.get(), touch(ctx)));
+        spans_queued = true;
+      }
       LbvhInput in;
       in.mesh_objects = (const uint8_t*)rb; in.n_meshes = n_meshes;
       in.vertices = bv ? (const float*)(rb + b_mo) : nullptr; in.n_vertices = bv ? bv->count : 0;
@@ -573,7 +609,13 @@ int prepare_scene(urt_context* ctx) {
       std::string err;
       rc = lbvh_build(in, touch(ctx), o, err);
       if (rc) return fail(ctx, rc, err);
-      ctx->scene.scene_allocs.push_back(std::move(raw));                 // _Vertices / _Indices stay resident: a moved MeshObject is refitted from them
+      if (spans_queued) {                                                  // (the build has waited for the stream)
+        span_lo_hi.resize((size_t)n_meshes * 2);
+        URT_HIP(ctx, hipMemcpy(span_lo_hi.data(), span_mem.get() + b_tab, span_lo_hi.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        ctx->last_span_ms = 0;
+        if (span_t1) URT_HIP(ctx, hipEventElapsedTime(&ctx->last_span_ms, span_t0.get(), span_t1.get()));
+      }
+      ctx->scene.scene_allocs.push_back(std::move(raw));                // _Vertices / _Indices stay resident: a moved MeshObject is refitted from them
       ctx->scene.refit.vertices = in.vertices; ctx->scene.refit.indices = in.indices; ctx->scene.refit.normals = in.normals;
       for (DeviceBuf<char>& a : o.allocs) ctx->scene.scene_allocs.push_back(std::move(a));
       S.mesh_root = o.mesh_root; S.blas_nodes = o.nodes; S.tri_verts = o.tri_verts; S.tri_norms = o.tri_norms;
@@ -655,8 +697,11 @@ int prepare_scene(urt_context* ctx) {
     {   // the span of vertices every MeshObject's index range refers to: a later SetData of _Vertices / _Normals deforms the MeshObjects
         // whose span its dirty range meets (prepare_incremental).  The builders have checked the ranges and the indices.
       C.h_vert_lo.assign((size_t)n_meshes, 0); C.h_vert_hi.assign((size_t)n_meshes, -1);
-      const int32_t* idx = (const int32_t*)bi->host.data();
-      for (int m = 0; m < n_meshes; m++) {
+      if (from_device && span_lo_hi.size() != 2 * (size_t)n_meshes)      // (the pass above was queued under this block's own condition)
+        return fail(ctx, URT_ERR_SCENE, "prepare_device: the vertex spans of the MeshObjects were not computed");
+      const int32_t* idx = from_device ? nullptr : (const int32_t*)bi->host.data();      // the host copy of _Indices may be stale: not read
+      for (int m = 0; m < n_meshes && from_device; m++) { C.h_vert_lo[(size_t)m] = span_lo_hi[2 * (size_t)m]; C.h_vert_hi[(size_t)m] = span_lo_hi[2 * (size_t)m + 1]; }
+      for (int m = 0; m < n_meshes && !from_device; m++) {
         const urt_MeshObject mo = mesh_object(bm->host, m);
         int32_t lo = INT32_MAX, hi = -1;
         for (long i = mo.indices_offset, e = (long)mo.indices_offset + (long)(mo.indices_count / 3) * 3; i < e; i++) { lo = std::min(lo, idx[i]); hi = std::max(hi, idx[i]); }
@@ -683,6 +728,7 @@ int prepare_scene(urt_context* ctx) {
   clear_dirty_ranges(ctx);
   ctx->scene_dirty = false; ctx->dirty_slots = 0; ctx->dirty_full = false;
   ctx->scene_epoch++;
+  ctx->full_preps++; ctx->device_preps += from_device ? 1u : 0u;
   ctx->last_prepare_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   return URT_OK;
 }

@@ -51,6 +51,25 @@ def _index_arg(k, n: int, who: str, what: str, names: str):
         raise IndexError(f"{who}: {names} {k}, the scene has {n}")
 
 
+def _device_list_arg(a, stride: int, name: str):
+    """A list in device memory for ReplaceGeometryDevice: a torch tensor, or (device address, element count) -> (what
+    ComputeBuffer.SetDataDevice takes, element count)."""
+    if isinstance(a, tuple) and len(a) == 2:
+        ptr, count = a
+        for what, v in (("device address", ptr), ("count", count)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"ReplaceGeometryDevice: the {what} of {name} must be an int, not {type(v).__name__}")
+        if count < 0:
+            raise ValueError(f"ReplaceGeometryDevice: the count of {name} is negative")
+        return int(ptr), int(count)
+    if hasattr(a, "data_ptr") and hasattr(a, "element_size"):
+        nbytes = a.numel() * a.element_size()
+        if nbytes % stride:
+            raise ValueError(f"ReplaceGeometryDevice: {name} holds {nbytes} bytes, not a multiple of its stride {stride}")
+        return a, nbytes // stride
+    raise TypeError(f"ReplaceGeometryDevice: {name} must be a torch tensor or (device address, count), not {type(a).__name__}")
+
+
 class RayTraceMaster:
     MeshObjectStructSize = 112   # RM:43
     SphereStructSize = 56        # RM:44
@@ -69,6 +88,10 @@ class RayTraceMaster:
     # first, which reads them back (GetData: it synchronises).  The boxes are those of the host functions (the mesh's own points), not the
     # loose box of eight transformed corners.  False (the default): nothing differs from a master without the attribute.
     device_object_heaps = False
+    # device_prepare (a property, below): with True the context's full preparations take _Vertices / _Indices / _Normals from the buffers'
+    # device side (include/urt.h option "prepare_device").  False (the default): nothing differs from a master without the attribute.
+    _devicePrepare = False
+    _geometryBehind = False                                     # (ReplaceGeometryDevice: scene.vertices / indices / normals are behind their buffers)
     _leafBuffers = (None, None)                                 # (likewise: the leaf records the device heaps are built from)
     _heapsBehind = (False, False)                               # (likewise: scene.mesh_bvh / scene.sphere_bvh are behind their buffers)
 
@@ -127,6 +150,18 @@ class RayTraceMaster:
         self._heapsBehind = [False, False]           # device_object_heaps: scene.mesh_bvh / scene.sphere_bvh are behind the heap buffers' device side
         self._normalsPlans = {}                      # RecomputeNormals: MeshObject index -> ((vertex buffer, index buffer, first, last), NormalsPlan, the index list it was made for)
 
+    # Geometry that ReplaceGeometryDevice, SkinMeshes, MorphMeshes or SetDataDevice wrote on the device is then never downloaded for a
+    # rebuild (new topology, buffers of another count, a rebuild forced by "refit_rebuild_pct"), and the triangle BVHs are always built
+    # on the GPU.  Setting it sets the context's option, which every master of the context shares.
+    @property
+    def device_prepare(self) -> bool:
+        return self._devicePrepare
+
+    @device_prepare.setter
+    def device_prepare(self, on):
+        self.ctx.set_option("prepare_device", 1 if on else 0)
+        self._devicePrepare = bool(on)
+
     # RM:215-230
     def RegisterObject(self, obj: RayTraceObject):
         self._rayTraceObjects.append(obj)
@@ -170,6 +205,7 @@ class RayTraceMaster:
         s.sphere_bvh = host_scene.build_object_bvh(host_scene.sphere_leaf_bounds(s.spheres, literal_leaf_bounds), pairing_heap) \
             if len(s.spheres) else np.zeros(0, scenes.BVHNODE_DT)
         self._heapsBehind = [False, False]                                        # the lists are the newest heaps again
+        self._geometryBehind = False                                              # ... and the newest geometry
         if getattr(self, "rayDebug", None) is not None:                             # RM:331-335
             self.rayDebug.LogSceneCounts(len(s.spheres), len(s.mesh_objects), len(s.vertices), len(s.indices), len(s.normals))
 
@@ -200,6 +236,7 @@ class RayTraceMaster:
         s = self.scene
         if self.device_object_heaps:                                              # never upload a host heap that is behind the device's
             self.SyncObjectHeaps()
+        self.SyncGeometry()                                                       # ... nor geometry that is
         if self.rayDebug is not None:                                             # RM:731-735
             self.rayDebug.LogTreeReport(len(s.mesh_objects), self.tree_depth(len(s.mesh_objects)), len(s.mesh_bvh),
                                         len(s.spheres), self.tree_depth(len(s.spheres)), len(s.sphere_bvh))
@@ -862,6 +899,83 @@ class RayTraceMaster:
             return
         self._history_finish(prev_m, {"deformed": edits, "keep": keep})
 
+    # The meshes are REPLACED by geometry that lives in device memory (an LOD switch, procedurally generated or re-meshed geometry):
+    # vertices / normals (stride 12) and indices (stride 4) are torch tensors on the context's device or (device address, element count)
+    # pairs, mesh_objects the new MeshObject records (host data), mesh_bvh their object-level heap — or None with device_object_heaps,
+    # which builds it where the buffers live.  A buffer whose count fits is reused; otherwise a new one is created, with SetDataDevice as
+    # its first and only write, and the old one released.  The counts may all differ from the scene's: the next frame prepares from
+    # scratch, and with device_prepare the geometry never crosses the bus.  The scene's vertices / indices / normals lists are BEHIND the
+    # device afterwards (SyncGeometry() reads them back); skins, blend shapes and normals plans referred to the old vertex spans and
+    # are dropped.  Topology changed, so no history is kept: the edit ends in ResetAccumulation(), as every edit without history does.
+    def ReplaceGeometryDevice(self, vertices, indices, normals, mesh_objects, mesh_bvh=None):
+        s = self.scene
+        mo = np.ascontiguousarray(mesh_objects)
+        if mo.dtype != scenes.MESHOBJECT_DT or mo.ndim != 1:
+            raise ValueError("ReplaceGeometryDevice: mesh_objects must be a 1-d array of MeshObject records (scenes.MESHOBJECT_DT)")
+        if mesh_bvh is None and not self.device_object_heaps:
+            raise ValueError("ReplaceGeometryDevice: mesh_bvh is needed unless device_object_heaps is on (the host holds no positions to build it from)")
+        if mesh_bvh is not None:
+            mesh_bvh = np.ascontiguousarray(mesh_bvh)
+            if mesh_bvh.dtype != scenes.BVHNODE_DT or mesh_bvh.ndim != 1:
+                raise ValueError("ReplaceGeometryDevice: mesh_bvh must be a 1-d array of BVH nodes (scenes.BVHNODE_DT)")
+        sources = [_device_list_arg(a, stride, name) for a, stride, name in ((vertices, 12, "vertices"), (indices, 4, "indices"), (normals, 12, "normals"))]
+        if len(mo) and not all(count > 0 for _, count in sources):
+            raise ValueError("ReplaceGeometryDevice: vertices, indices and normals must not be empty")
+        if self._treesNeedRebuilding:                                             # the buffers of the other lists must exist, and no later rebuild may overwrite these
+            self._scene_ready()
+        old = [self._vertexBuffer, self._indexBuffer, self._normalBuffer]
+        new = []
+        for buf, (src, count), stride in zip(old, sources, (12, 4, 12)):
+            if buf is None or buf.count != count:
+                buf = ComputeBuffer(self.ctx, count, stride) if count else None
+            if buf is not None:
+                buf.SetDataDevice(src, 0, count)
+            new.append(buf)
+        self._vertexBuffer, self._indexBuffer, self._normalBuffer = new
+        for a, b in zip(old, new):
+            if a is not None and a is not b:
+                a.Release()
+        s.mesh_objects = mo.copy()
+        self._meshObjectBuffer = self.CreateComputeBuffer(self._meshObjectBuffer, s.mesh_objects, self.MeshObjectStructSize)
+        self._geometryBehind = True
+        if mesh_bvh is not None:
+            s.mesh_bvh = mesh_bvh.copy()
+            self._meshObjectBVHBuffer = self.CreateComputeBuffer(self._meshObjectBVHBuffer, s.mesh_bvh, self.BVHNodeSize)
+            self._heapsBehind[0] = False
+        else:
+            n = max(0, _lib.load().urt_host_object_bvh_length(len(mo)))
+            s.mesh_bvh = np.zeros(n, scenes.BVHNODE_DT)                           # its length is what the shader is told; the contents are behind
+            heap = self._meshObjectBVHBuffer
+            if heap is not None and heap.count != n:
+                heap.Release()
+                heap = None
+            if heap is None and n:
+                heap = ComputeBuffer(self.ctx, n, self.BVHNodeSize)
+            self._meshObjectBVHBuffer = heap
+            if n:
+                self._build_heap_on_device(0)
+        # what referred to the old vertex spans
+        self._skins, self._skinBoxes, self._boxCache = {}, {}, {}
+        for b in tuple(self._skinBuffers or ()) + tuple(self._boneBuffers.values()):
+            b.Release()
+        self._skinBuffers, self._boneBuffers = None, {}
+        self._drop_morphs()
+        self._morphs = {}
+        self._drop_normals_plans()
+        self.ResetAccumulation()
+
+    def SyncGeometry(self):
+        """scene.vertices / indices / normals as the buffers hold them now, after ReplaceGeometryDevice left them behind the device
+        (ComputeBuffer.GetData: synchronising downloads).  Nothing to do otherwise."""
+        s = self.scene
+        if not self._geometryBehind:
+            return
+        get = lambda b, dt, shape: (b.GetData().reshape(-1).view(dt) if b is not None else np.zeros(0, dt)).reshape(shape).copy()
+        s.vertices = get(self._vertexBuffer, np.float32, (-1, 3))
+        s.indices = get(self._indexBuffer, np.int32, (-1,))
+        s.normals = get(self._normalBuffer, np.float32, (-1, 3))
+        self._geometryBehind = False
+
     def _mesh_index_arg(self, k, who: str, what: str):
         _index_arg(k, len(self.scene.mesh_objects), who, what, f"{what} names MeshObject")
 
@@ -1315,6 +1429,7 @@ class RayTraceMaster:
     def OnDisable(self):
         if self.device_object_heaps:                                              # the scene's lists outlive the buffers
             self.SyncObjectHeaps()
+        self.SyncGeometry()
         for b in (self._sphereBuffer, self._meshObjectBuffer, self._vertexBuffer, self._indexBuffer, self._normalBuffer,
                   self._sphereBVHBuffer, self._meshObjectBVHBuffer) + tuple(self._skinBuffers or ()) + tuple(self._boneBuffers.values()) \
                 + tuple(self._leafBuffers):

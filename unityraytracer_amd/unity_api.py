@@ -97,6 +97,22 @@ class Context:
         self.check(self.lib.urt_debug_scene_cost(self._h, out.ctypes.data_as(C.c_void_p), int(n_meshes)))
         return out
 
+    def scene_vertex_spans(self, n_meshes: int) -> tuple:
+        """(lo[n_meshes], hi[n_meshes]) int32: the smallest and the largest vertex every MeshObject's index range names, as the prepared
+        scene holds them (include/urt.h urt_debug_scene_vertex_spans; prepares a stale scene first).  INT32_MAX / -1: none."""
+        lo, hi = np.zeros(int(n_meshes), dtype=np.int32), np.zeros(int(n_meshes), dtype=np.int32)
+        self.check(self.lib.urt_debug_scene_vertex_spans(self._h, lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), int(n_meshes)))
+        return lo, hi
+
+    def prepare_stats(self) -> dict:
+        """Full preparations since the context was created, those of them option "prepare_device" fed from device memory, the indices one
+        work item of the vertex-span kernel scans, and the device time of the last span pass in ms (0 unless "time_dispatch" is on) —
+        include/urt.h urt_debug_prepare_stats."""
+        a = (C.c_uint64 * 4)()
+        self.check(self.lib.urt_debug_prepare_stats(self._h, a))
+        return {"full": int(a[0]), "device": int(a[1]), "span_chunk": int(a[2]),
+                "span_ms": float(np.array([int(a[3])], dtype=np.uint32).view(np.float32)[0])}
+
     def skin_vertices(self, rest_vertices, rest_normals, bone_indices, bone_weights, bones, first: int, count: int, dst_vertices,
                       dst_normals=None):
         """Linear blend skinning of elements first .. first + count - 1 on the GPU, into the device mirrors of dst_vertices (and
