@@ -105,7 +105,19 @@ buffers LM / LS (stride 28, one leaf per MeshObject / sphere), the names HM / HS
                                        hit guide through the sample centres into DH, blurs C into the destination, blooms it in place if
                                        bloom is on and tone-maps it in place; the host's projection is bound again afterwards
 The library refuses a depth-of-field destination that is the source, the hit image or the bound sky, textures of two sizes, normalize
-without normals; the heap calls a destination that is also an input."""
+without normals; the heap calls a destination that is also an input.
+
+A second WORLD, world="solo" (make_scene, cameras, edited_scene, pipeline_world, dynamic_world, run_model, run_gpu; the default "mixed" is
+everything above): the blob of the mixed scene alone — one MeshObject, no sphere, the same material, transform and sky — so that a trace
+launch is the plain single-mesh form of the kernel, with the normal cones and the tile entry table.  The blob's span is the whole vertex
+list; the skin, the morph targets, the normals plan and the rest pose are made from that span as in the mixed world.  Zero-count buffers
+(sphere motion, LS, HS) do not exist in it.  The "solo" profile (profile="solo", which implies the world) is the dynamic profile without
+the spheres' ops — no move_spheres, no rebuild_heap 1, no get_buffer of HS / LS, move_mesh of object 0 only, reproject form "objects"
+with the mesh table only — and
+    ("motion_blur", src, hit, dst, j)  ctx.motion_blur(src, MV, hit, dst, **MBLUR[j]): hit is Gh | Ph, src any exact frame-sized texture,
+                                       dst any frame-sized texture but src, MV, hit and the bound sky (the library refuses those);
+                                       played only once a reproject has written MV and an aov the hit set
+run_gpu(options=...) sets tile_entry / refit / prepare_device for one run."""
 import copy
 
 import numpy as np
@@ -216,13 +228,30 @@ def state_words(s):
 
 
 # ---- the world ----------------------------------------------------------------------------------------------------------------------
-def make_scene(width=64, height=40, bounces=2):
-    sc = scenes.mixed_test_scene(width, height)
+WORLDS = ("mixed", "solo")
+SOLO_BLOB = (20, 15)                                             # slices, stacks of the solo world's blob: 282 vertices, 560 triangles
+
+
+def solo_scene(width, height):
+    """The blob of scenes.mixed_test_scene alone: one MeshObject under the same transform and material, no sphere, the same sky.  The
+    plain single-mesh form of the trace kernel (front_fuse 2, the normal cones, the tile entry table) runs on nothing else.  The
+    tessellation is SOLO_BLOB: a triangle BVH of depth 11 (deeper than the stack minimum of 8) whose subtrees the 8 x 8 tiles of a
+    64 x 40 frame can tell apart (tests/test_gpu_command_stream_solo.py says what the table holds)."""
+    b = scenes.MeshSceneBuilder()
+    b.add(*scenes.uv_blob(*SOLO_BLOB), scenes.trs(translate=(-2.0, 1.3, 1.0), scale=(1.2, 1.0, 0.9), yaw_deg=33.0),
+          scenes._params((0.7, 0.4, 0.3), (0.2, 0.2, 0.2), (0, 0, 0), 0.6))
+    mo, vv, ii, nn, bvh = b.finish()
+    return scenes.Scene("solo", width, height, 4, 1, mesh_objects=mo, vertices=vv, indices=ii, normals=nn, mesh_bvh=bvh, sky=scenes.make_sky(128, 64))
+
+
+def make_scene(width=64, height=40, bounces=2, world="mixed"):
+    assert world in WORLDS, world
+    sc = scenes.mixed_test_scene(width, height) if world == "mixed" else solo_scene(width, height)
     sc.num_bounces, sc.num_rays = bounces, 1
     return sc
 
 
-def cameras(sc):
+def cameras(sc, world="mixed"):
     return [scenes.camera_matrices(sc.width, sc.height, position=p)[0] for p in CAMERA_POSITIONS]
 
 
@@ -233,8 +262,9 @@ def blob_span(sc):
     return int(sl.min()), int(sl.max())
 
 
-def edited_scene(sc, op):
-    """A copy of `sc` after a scene-edit op (no array of `sc` is written).  Both sides use it: it is plain host arithmetic on the lists."""
+def edited_scene(sc, op, world="mixed"):
+    """A copy of `sc` after a scene-edit op (no array of `sc` is written).  Both sides use it: it is plain host arithmetic on the lists.
+    world: the world `sc` is of (the skin, the plan and the morph targets are that world's)."""
     out = copy.copy(sc)
     if op[0] == "move_mesh":
         mo = sc.mesh_objects.copy()
@@ -255,9 +285,9 @@ def edited_scene(sc, op):
         out.spheres = sp
         out.sphere_bvh = scenes.build_object_bvh(*scenes.sphere_bounds(sp))
     elif op[0] == "camera":
-        out.camera_to_world = cameras(sc)[op[1]]
+        out.camera_to_world = cameras(sc, world)[op[1]]
     elif op[0] in VERTEX_WRITES:
-        w = pipeline_world(sc.width, sc.height)
+        w = pipeline_world(sc.width, sc.height, world)
         v, n = np.array(sc.vertices, F).reshape(-1, 3), np.array(sc.normals, F).reshape(-1, 3)
         if op[0] == "skin":
             import skin_ref
@@ -281,7 +311,7 @@ def edited_scene(sc, op):
             out.mesh_bvh = scenes.build_object_bvh(*scenes.mesh_bounds(sc.mesh_objects, v, sc.indices))
     elif op[0] == "morph":
         import morph_ref
-        w = dynamic_world(sc.width, sc.height)
+        w = dynamic_world(sc.width, sc.height, world)
         lo, hi = w["span"]
         _, j, with_normals, normalize = op
         v, n = np.array(sc.vertices, F).reshape(-1, 3), np.array(sc.normals, F).reshape(-1, 3)
@@ -322,13 +352,13 @@ def heap_words(nodes):
 _WORLDS = {}
 
 
-def pipeline_world(width=64, height=40):
+def pipeline_world(width=64, height=40, world="mixed"):
     """What the pipeline profile adds to the world, from the untouched scene (made once per size): the blob's span, its rest pose in
     buffers of the vertex count, a two-bone skin with one bone table per pose, and the canonical normals plan of the span."""
-    if (width, height) not in _WORLDS:
+    if (width, height, world) not in _WORLDS:
         import normals_ref
         import skin_ref
-        sc = make_scene(width, height)
+        sc = make_scene(width, height, world=world)
         lo, hi = blob_span(sc)
         v, n = np.array(sc.vertices, F).reshape(-1, 3), np.array(sc.normals, F).reshape(-1, 3)
         idx, wgt = np.zeros((len(v), 4), np.int32), np.zeros((len(v), 4), F)
@@ -338,23 +368,23 @@ def pipeline_world(width=64, height=40):
         rest_v[lo: hi + 1], rest_n[lo: hi + 1] = v[lo: hi + 1], n[lo: hi + 1]
         flags = np.zeros(len(sc.mesh_objects), np.int32)
         flags[0] = 1
-        _WORLDS[(width, height)] = {"span": (lo, hi), "rest_v": rest_v, "rest_n": rest_n, "bone_idx": idx, "bone_wgt": wgt, "poses": poses,
+        _WORLDS[(width, height, world)] = {"span": (lo, hi), "rest_v": rest_v, "rest_n": rest_n, "bone_idx": idx, "bone_wgt": wgt, "poses": poses,
                                     "plan": normals_ref.plan(v, sc.indices, lo, hi - lo + 1), "deformed": flags}
-    return _WORLDS[(width, height)]
+    return _WORLDS[(width, height, world)]
 
 
 _DYNAMIC_WORLDS = {}
 
 
-def dynamic_world(width=64, height=40):
+def dynamic_world(width=64, height=40, world="mixed"):
     """What the dynamic profile adds to pipeline_world (whose entries it holds, too), made once per size: "deltas", the urt_MorphDelta
     array of N_TARGETS sparse targets over the blob's span — served vertex i is named by target 0 when i % 2 == 0, by target 1 when
     i % 3 == 0 and by target 2 when i % 5 == 0, so some vertices are touched by none and some by all three — and "counts", the element
     counts of the four stride-28 buffers."""
-    if (width, height) not in _DYNAMIC_WORLDS:
+    if (width, height, world) not in _DYNAMIC_WORLDS:
         import morph_ref
-        w = dict(pipeline_world(width, height))
-        sc = make_scene(width, height)
+        w = dict(pipeline_world(width, height, world))
+        sc = make_scene(width, height, world=world)
         lo, hi = w["span"]
         rng = np.random.default_rng(4242)
         vertex, target = [], []
@@ -367,8 +397,8 @@ def dynamic_world(width=64, height=40):
         dn = rng.normal(scale=0.3, size=(len(vertex), 3)).astype(F)
         w["deltas"] = morph_ref.deltas_array(vertex, target, dp, dn)
         w["counts"] = {"LM": len(sc.mesh_objects), "LS": len(sc.spheres), "HM": len(sc.mesh_bvh), "HS": len(sc.sphere_bvh)}
-        _DYNAMIC_WORLDS[(width, height)] = w
-    return _DYNAMIC_WORLDS[(width, height)]
+        _DYNAMIC_WORLDS[(width, height, world)] = w
+    return _DYNAMIC_WORLDS[(width, height, world)]
 
 
 def aov_targets(op):
@@ -505,6 +535,8 @@ def make_program(seed, n_ops=40, profile="frames"):
         return make_display_program(seed, n_ops)
     if profile == "dynamic":
         return make_dynamic_program(seed, n_ops)
+    if profile == "solo":
+        return make_solo_program(seed, n_ops)
     assert profile == "frames", profile
     rng = np.random.default_rng(seed)
     kinds = list(_WEIGHTS)
@@ -1202,6 +1234,296 @@ def make_dynamic_program(seed, n_ops=40):
     return prog
 
 
+# ---- programs of the solo profile ----------------------------------------------------------------------------------------------------
+# The solo world (make_scene(world="solo")): one MeshObject, no sphere.  The profile's ops are the dynamic profile's that mean something
+# without spheres — no move_spheres, no device_heap of it, no rebuild_heap 1, no get_buffer of HS / LS (zero-count buffers do not exist);
+# move_mesh always moves object 0 — and
+#     ("motion_blur", src, hit, dst, j)   ctx.motion_blur(src, MV, hit, dst, **MBLUR[j]): hit is Gh | Ph, src any exact frame-sized texture,
+#                                         dst any frame-sized texture but src, MV, hit and the bound sky (the library refuses those)
+MBLUR_FLAG_VELOCITY = 1                                          # URT_MOTION_BLUR_FLAG_VELOCITY
+MBLUR = (dict(), dict(shutter=1.0, max_radius=4.0), dict(shutter=0.25, max_radius=0.5), dict(flags=MBLUR_FLAG_VELOCITY))
+SOLO_KINDS = tuple(k for k in DYN_KINDS if k != "move_spheres") + ("motion_blur",)
+SOLO_IMAGE_OPS = DYNAMIC_IMAGE_OPS + ("motion_blur",)
+SOLO_WRITERS = DISPLAY_WRITERS + ("motion_blur",)
+SOLO_VERTEX_WRITES = ("skin", "morph", "set_device", "set_host")
+
+
+def solo_fix(op):
+    """An op a follower of the older profiles plays, as the solo world means it: the spheres' ops become the mesh's, every move_mesh moves
+    object 0, the sphere heap's readbacks become the mesh heap's (one leaf, one node)."""
+    k = op[0]
+    if k == "move_spheres":
+        return ("move_mesh", 0, op[1] % len(MOVES))
+    if k == "move_mesh":
+        return ("move_mesh", 0, op[2])
+    if k == "device_heap":
+        return ("device_heap", solo_fix(op[1]))
+    if k == "rebuild_heap":
+        return ("rebuild_heap", 0)
+    if k == "get_buffer" and op[1] in HEAP_BUFFERS:
+        return ("get_buffer", {"HS": "HM", "LS": "LM"}.get(op[1], op[1]), 0, 1)
+    return op
+
+
+class _SoloTrack(_DynamicTrack):
+    def __init__(self):
+        super().__init__()
+        self.mv_ready = False                                    # a reproject has written MV
+        self.nv = len(pipeline_world(world="solo")["rest_v"])
+
+    def allowed(self, op):
+        k = op[0]
+        if k == "move_spheres" or "HS" in op[1:] or "LS" in op[1:]:
+            return False
+        if k == "move_mesh":
+            return op[1] == 0 and 0 <= op[2] < len(MOVES)
+        if k == "rebuild_heap":
+            return op[1] == 0
+        if k == "get_buffer" and op[1] in ("HM", "LM"):
+            return op[2:] == (0, 1)
+        if k in ("set_host", "set_device", "bounds", "get_buffer"):
+            first, count = op[-3:-1] if k in ("set_host", "set_device") else op[-2:]
+            return 0 <= first and count >= 1 and first + count <= self.nv
+        if k == "motion_blur":                                   # sizes that differ; a destination that is an input or the bound sky
+            _, src, hit, dst, j = op
+            if not (hit in ("Gh", "Ph") and self.mv_ready and (self.g_ready if hit == "Gh" else self.p_ready)):
+                return False                                     # (a prerequisite that was refused: nothing to blur along)
+            return src in DISPLAY_FRAME_TEX and dst in DISPLAY_FRAME_TEX and 0 <= j < len(MBLUR) and dst not in (src, "MV", hit, self.sky)
+        return super().allowed(op)
+
+    def apply(self, op):
+        super().apply(op)
+        if op[0] == "reproject":
+            self.mv_ready = True
+
+    def prerequisites(self, op):
+        pre = super().prerequisites(op)
+        if op[0] == "motion_blur":                               # a motion image nothing has written makes every tile still
+            if not self.mv_ready:
+                rp = ("reproject", "plain", (self.camera + 1) % len(CAMERA_POSITIONS), 8.0, "C")
+                pre += super().prerequisites(rp) + [rp]
+            want = ("aov", "G", 15, False) if op[2] == "Gh" else ("aov", "P", 11, False)
+            if not (self.g_ready if op[2] == "Gh" else self.p_ready) and want not in pre:      # (the reproject's own may render both sets)
+                pre.append(want)
+        return pre
+
+
+def solo_writes_of(op, result):
+    if op[0] == "motion_blur":
+        return [(op[3], "motion_blur")]
+    return dynamic_writes_of(op, result)
+
+
+def solo_reads_of(op, result):
+    if op[0] == "motion_blur":
+        return [op[1], "MV", op[2]]
+    return dynamic_reads_of(op, result)
+
+
+# the dynamic profile's weights without the spheres' kind, the frame loop and the vertex writes held up; then motion blur
+_SOLO_WEIGHTS = dict({k: v for k, v in _DYNAMIC_WEIGHTS.items() if k != "move_spheres"}, frame=20, camera=3, bind_result=2.5, skin=4, set_device=3,
+                     set_host=3, morph=5, device_heap=6, dof=4, motion_blur=9)
+
+
+def _draw_solo(rng, kind, tr, nv, span):
+    pick = lambda names: names[int(rng.integers(len(names)))]
+    if kind == "motion_blur":
+        src = pick(("C", "C", "C", "H", "X0", "U", tr.result, "R"))
+        dst = pick(tuple(t for t in ("X0", "X1", "X2", "U", "H", tr.result, tr.result) if t != src))
+        return ("motion_blur", src, pick(("Gh", "Gh", "Ph")), dst, int(rng.integers(len(MBLUR))))
+    if kind == "move_mesh":
+        return ("move_mesh", 0, int(rng.integers(len(MOVES))))
+    if kind == "device_heap":
+        edit = pick(("move_mesh", "move_mesh", "deform", "skin", "set_device", "set_host", "set_host", "morph"))
+        return ("device_heap", _draw_solo(rng, edit, tr, nv, span))
+    if kind == "rebuild_heap":
+        return ("rebuild_heap", 0)
+    if kind == "get_buffer" and rng.random() < 0.3:
+        return ("get_buffer", pick(("HM", "LM")), 0, 1)
+    if kind == "get_buffer":
+        return _draw_pipeline(rng, kind, tr, nv, span)
+    return solo_fix(_draw_dynamic(rng, kind, tr, nv, span))
+
+
+def _solo_followers(rng, op, result, tr, draw):
+    """What the solo profile plays right behind a motion blur, a vertex write or (for some of them) a frame."""
+    pick = lambda names: names[int(rng.integers(len(names)))]
+    k, r = op[0], rng.random()
+    if k == "frame" and r < 0.12:                                # a camera change inside what would be one batch
+        return [("camera", (tr.camera + 1 + int(rng.integers(len(CAMERA_POSITIONS) - 1))) % len(CAMERA_POSITIONS)), ("frame", pick((None, "X0")))]
+    if k == "frame" and r < 0.3:                                 # ... or a scene edit
+        mid = pick((("deform", float(pick((1.25, 0.75)))), lambda: draw("skin"), lambda: draw("skin"), lambda: draw("morph"),
+                    lambda: draw("set_device"), lambda: draw("set_host"), lambda: draw("device_heap"), lambda: draw("move_mesh")))
+        return [mid, ("frame", pick((None, "X0")))]
+    if k == "frame" and r < 0.42:                                # the other Result texture under the same camera
+        return [("bind_result",), ("frame", None)]
+    if k == "frame" and r < 0.75:                                # motion blur of what a deferred frame wrote
+        hit, j = pick(("Gh", "Gh", "Ph")), int(rng.integers(len(MBLUR)))
+        dst = pick((tr.result, "X1", "X0", "U"))
+        blur = ("motion_blur", pick(("C", "C", tr.result if dst != tr.result else "C")), hit, dst, j)
+        tail = [("frame", None)] if dst == tr.result else _sky_and_frame(dst) if rng.random() < 0.6 else []
+        return tr.prerequisites(blur) + [("frame", None), blur] + tail
+    if k == "motion_blur":
+        if r < 0.35:                                             # the same once more under another preset
+            return [op[:4] + ((op[4] + 1 + int(rng.integers(len(MBLUR) - 1))) % len(MBLUR),)]
+        if op[3] != tr.result and r < 0.7:                       # the destination is bound as the sky and traced at once
+            return _sky_and_frame(op[3])
+        if op[3] == tr.result and r < 0.8:
+            return [("frame", None)]
+    if k in SOLO_VERTEX_WRITES and r < 0.7:                      # the frame's preparation reads what nothing has waited for
+        return [("frame", pick((None, "X0")))]
+    return []
+
+
+def make_solo_program(seed, n_ops=40):
+    """As make_dynamic_program, over SOLO_KINDS in the solo world, with a random stream, weights, a tracker and followers of its own (what
+    follows an op of the older profiles is mostly what follows it there, through solo_fix).  The bias of this profile: a camera change or a
+    scene edit sits between two frames of what would be one batch (the tile entry table of the launch behind it is another one), the
+    Result texture is swapped between two frames of one camera (the same table), a vertex write of every kind is followed by a frame
+    with nothing that looks at the vertices in between, motion blur reads what a deferred frame wrote, writes the bound Result or the
+    next sky, and is called twice under two presets."""
+    rng = np.random.default_rng(400000 + seed)
+    w = dynamic_world(world="solo")
+    lo, hi = w["span"]
+    nv = len(w["rest_v"])
+    kinds = list(_SOLO_WEIGHTS)
+    p = np.array([_SOLO_WEIGHTS[k] for k in kinds], dtype=np.float64)
+    p /= p.sum()
+    tr, prog, forced = _SoloTrack(), [], []
+
+    def emit(op):
+        tr.apply(op)
+        prog.append(op)
+
+    def draw(kind):
+        return _draw_solo(rng, kind, tr, nv, (lo, hi))
+
+    while len(prog) < n_ops or forced:
+        if forced:
+            op = forced.pop(0)
+            if callable(op):
+                op = op()
+            drawn = op[0] == "drawn"
+            op = solo_fix(op[1] if drawn else op)
+            if not tr.allowed(op):
+                continue
+        else:
+            op, drawn = draw(kinds[int(rng.choice(len(kinds), p=p))]), True
+            if not tr.allowed(op):
+                continue
+            if tr.prerequisites(op):
+                forced = tr.prerequisites(op) + [("drawn", op)]
+                continue
+        result = tr.result
+        emit(op)
+        if not drawn:
+            continue
+        k = op[0]
+        if k == "motion_blur" or (k in ("frame",) + SOLO_VERTEX_WRITES and rng.random() < 0.6):
+            forced = _solo_followers(rng, op, result, tr, draw)
+        elif k in DYNAMIC_KINDS or (k in ("frame", "ray_query_async", "radiance_async", "morph", "skin", "set_host", "deform") and rng.random() < 0.5):
+            forced = _dynamic_followers(rng, op, result, tr, draw)
+        elif k in DISPLAY_KINDS or (k == "frame" and rng.random() < 0.6):
+            forced = _display_followers(rng, op, result, tr)
+        else:
+            forced = _pipeline_followers(rng, op, result, tr, draw, (lo, hi), nv)
+    while tr.tickets:
+        emit(("read_end",))
+    return prog
+
+
+# the ops that leave the deferred frames deferred (dynamic_coverage's "quiet" ops); every other op has submitted them when it returns
+SOLO_QUIET = ("restart", "bind_sky", "bind_result", "camera", "master_bloom", "master_dof", "frame", "dispatch", "snapshot", "ray_query_async",
+              "radiance_async", "morph", "device_heap", "rebuild_heap") + SCENE_CHANGES
+
+
+SOLO_CASES = ("edit_between_frames", "camera_between_frames", "bind_result_between_frames", "blur_input_deferred", "blur_into_result_or_sky",
+              "write_then_frame_skin", "write_then_frame_morph", "write_then_frame_set_device", "write_then_frame_set_host", "two_presets")
+
+
+def solo_coverage(program):
+    """Static facts about a program of the solo profile (tests/test_command_stream_model.py holds the seed set to them).  "Quiet" ops are
+    dynamic_coverage's: they leave the deferred frames deferred.  A frame is OPEN while it could still be deferred: nothing but quiet ops
+    has run since.
+    kinds: op kind -> count (a wrapped edit counts as device_heap);
+    edit_between_frames / camera_between_frames: scene changes (device builds and morphs included) / camera ops with an open frame in
+    front of them and a frame behind them before anything that is not quiet — and, for a scene change, no camera op between those two
+    frames: both are the same camera's, only the scene differs;
+    bind_result_between_frames: bind_result ops likewise, no camera op between the two frames;
+    blur_input_deferred: motion_blur ops whose source or hit image was written by an open frame;
+    blur_into_result_or_sky: motion_blur ops that write the bound Result texture with a frame after them, or whose destination is bound
+    as the sky after the write and traced before anything else writes it;
+    write_then_frame_K, K of skin | morph | set_device | set_host: vertex writes of that kind (wrapped ones included) with a frame behind
+    them and nothing between that reads V or prepares the scene;
+    two_presets: 1 when the program's motion_blur ops use two presets or more."""
+    kinds = {k: 0 for k in SOLO_KINDS}
+    tr = _SoloTrack()
+    quiet = SOLO_QUIET
+    readers_of_v = ("get_buffer", "bounds", "snapshot", "aov", "aov_into", "aov_low", "ray_query", "radiance_query", "radiance_pixels", "resample",
+                    "ray_query_async", "radiance_async", "present_tm", "dispatch", "normals", "rebuild_heap", "reproject")
+    out = {key: 0 for key in SOLO_CASES}
+    deferred, pending, presets = set(), 0, set()
+    last_writer, write_at, bound_at, counted = {}, {}, -1, set()
+    frames_after = np.cumsum([op[0] in ("frame", "dispatch") for op in program][::-1])[::-1]
+
+    def frame_behind(i, no_camera):
+        """A frame follows op i before anything that is not quiet (and before a camera op, if no_camera)."""
+        for q in program[i + 1:]:
+            if q[0] == "frame":
+                return True
+            if q[0] not in quiet or (no_camera and q[0] == "camera"):
+                return False
+        return False
+
+    def camera_since_frame(i):
+        for q in program[:i][::-1]:
+            if q[0] in ("frame", "dispatch"):
+                return False
+            if q[0] == "camera":
+                return True
+        return False
+
+    for i, op in enumerate(program):
+        k = op[0]
+        kinds[k] += 1
+        result = tr.result if k != "dispatch" else op[1]
+        edit = op[1] if k == "device_heap" else op if k in DEVICE_EDITS else None
+        if edit is not None:
+            out["edit_between_frames"] += bool(pending > 0 and not camera_since_frame(i) and frame_behind(i, True))
+            if edit[0] in SOLO_VERTEX_WRITES:
+                behind = None
+                for q in program[i + 1:]:
+                    if q[0] == "frame" or q[0] in readers_of_v or (q[0] == "device_heap"):
+                        behind = q[0]
+                        break
+                out["write_then_frame_" + edit[0]] += behind == "frame"
+        if k == "camera":
+            out["camera_between_frames"] += bool(pending > 0 and frame_behind(i, False))
+        if k == "bind_result":
+            out["bind_result_between_frames"] += bool(pending > 0 and not camera_since_frame(i) and frame_behind(i, True))
+        if k == "motion_blur":
+            presets.add(op[4])
+            out["blur_input_deferred"] += bool(deferred & {op[1], op[2]})
+            out["blur_into_result_or_sky"] += bool(op[3] == tr.result and frames_after[i] > 0)
+        if k in ("frame", "dispatch") and tr.sky in last_writer and bound_at > write_at[tr.sky] and (tr.sky, write_at[tr.sky]) not in counted:
+            counted.add((tr.sky, write_at[tr.sky]))
+            out["blur_into_result_or_sky"] += last_writer[tr.sky] == "motion_blur"
+        # the state after the op
+        if k in ("frame", "dispatch"):
+            pending += 1
+            deferred |= {t for t, _ in writes_of(op, result)}
+        elif k not in quiet:
+            pending, deferred = 0, set()
+        for t, wk in solo_writes_of(op, result):
+            last_writer[t], write_at[t] = wk, i
+        if k == "bind_sky":
+            bound_at = i
+        tr.apply(op)
+    out["two_presets"] = int(len(presets) >= 2)
+    out["kinds"] = kinds
+    return out
+
+
 def dynamic_coverage(program):
     """Static facts about a program of the dynamic profile (tests/test_command_stream_model.py holds the seed set to them).  A DEVICE BUILD
     is a device_heap or a rebuild_heap op; "quiet" ops are the ones of display_coverage and the dynamic ones but dof (a device build
@@ -1485,7 +1807,7 @@ def ray_hits(orc, o, d):
     return out
 
 
-def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frames", stats=None, stale_builds=()):
+def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frames", stats=None, stale_builds=(), world="mixed"):
     """-> (observations, final contents): observations is a list of (op index, kind, array | None), final a dict name -> array.
     profile="pipeline": the world and the ops of that profile (final holds the buffers too, under "V", "V.dev", ...: both sides of a
     buffer hold the same in program order); stats, a list, receives (op index, kind, figures) of the reproject / denoise / select /
@@ -1494,14 +1816,19 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
     state_words, and "TM"; stats receives the figures of the upsample and meter ops, too).
     profile="dynamic": the world and the ops of that profile on top (final holds "DH" and both sides of W, LM, LS, HM, HS, the stride-28
     ones as heap_words; stats receives the figures of the morph and dof ops, too).  stale_builds: op indices of device builds that leave
-    the heap and the leaves as they were — the non-vacuity probe of tests/test_command_stream_model.py, not a thing the library does."""
+    the heap and the leaves as they were — the non-vacuity probe of tests/test_command_stream_model.py, not a thing the library does.
+    profile="solo": the dynamic profile's ops and motion_blur in the solo world (world="solo" goes with it; final holds neither LS nor HS:
+    zero-count buffers do not exist; stats receives the figures of the motion_blur ops, too).  world="solo" under another profile: that
+    profile's ops on the solo scene."""
     from oracle import pyoracle
     from reproject_ref import blit_add_history_ref
-    assert profile in ("frames", "pipeline", "display", "dynamic"), profile
-    dynamic = profile == "dynamic"
+    assert profile in ("frames", "pipeline", "display", "dynamic", "solo"), profile
+    world = "solo" if profile == "solo" else world
+    solo = world == "solo"
+    dynamic = profile in ("dynamic", "solo")
     display = profile == "display" or dynamic
     pipeline = profile == "pipeline" or display
-    sc = make_scene(width, height, bounces)
+    sc = make_scene(width, height, bounces, world)
     tex = {n: np.zeros((height, width, 4), F) for n in FRAME_TEX + (PIPE_TEX if pipeline else ()) + (UP_TEX + ("TM",) if display else ()) +
            (("DH",) if dynamic else ())}
     if dynamic:
@@ -1520,7 +1847,7 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
             setattr(sc, "sphere_bvh" if kind else "mesh_bvh", heap)
 
         def heap_buffers():
-            return {"LM": leaves[0], "LS": leaves[1], "HM": sc.mesh_bvh, "HS": sc.sphere_bvh}
+            return {"LM": leaves[0], "HM": sc.mesh_bvh} if solo else {"LM": leaves[0], "LS": leaves[1], "HM": sc.mesh_bvh, "HS": sc.sphere_bvh}
     if display:
         import bloom_ref
         import tonemap_ref
@@ -1569,17 +1896,26 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
         if pipeline and k in OBSERVERS:                          # what the async queries answered is looked at now
             obs += waiting
             waiting = []
+        if k == "motion_blur":
+            import motion_blur_ref
+            assert profile == "solo", op
+            _, src, hit, dst, j = op
+            out = motion_blur_ref.motion_blur_ref(tex[src], tex["MV"], tex[hit], **MBLUR[j])
+            same_px = (out.view(np.uint32) == np.asarray(tex[src], F).view(np.uint32)).all(axis=-1)
+            stats.append((i, k, {"changed": int((~same_px).sum()), "identical": int(same_px.sum())}))
+            tex[dst] = out
+            continue
         if dynamic and (k in DYNAMIC_KINDS or (k == "get_buffer" and op[1] in HEAP_BUFFERS)):
             if k == "morph":
                 before = np.array(sc.vertices, F).reshape(-1, 3)
                 weights = np.array(MORPH_WEIGHTS[op[1]], F)
-                sc = edited_scene(sc, op)
+                sc = edited_scene(sc, op, world)
                 stats.append((i, k, {"moved": int((np.asarray(sc.vertices, F).reshape(-1, 3) != before).any(axis=1).sum())}))
             elif k == "device_heap":
                 old = sc
                 if op[1][0] == "morph":
                     weights = np.array(MORPH_WEIGHTS[op[1][1]], F)
-                sc = edited_scene(sc, op[1])
+                sc = edited_scene(sc, op[1], world)
                 sc.mesh_bvh, sc.sphere_bvh = old.mesh_bvh, old.sphere_bvh      # the edit without its host SetData of the heap ...
                 device_build(i, heap_kind(op[1]), old)                           # ... and the heap built where the buffers live
             elif k == "rebuild_heap":
@@ -1650,16 +1986,16 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
                 from unityraytracer_amd import host_scene
                 _, form, j, max_history, src = op
                 args = [tex[n] for n in (src, "N", "Ph", "Pn", "Pi", "Gh", "Gn", "Gi")]
-                args += [scenes.world_to_clip(cameras(sc)[j], sc.camera_inverse_projection), sc.camera_to_world, sc.camera_inverse_projection]
+                args += [scenes.world_to_clip(cameras(sc, world)[j], sc.camera_inverse_projection), sc.camera_to_world, sc.camera_inverse_projection]
                 if form == "plain":
                     out = reproject_ref(*args, max_history=max_history)
                 else:
                     tables = dict(mesh_motion=host_scene.mesh_motion(p_scene.mesh_objects, sc.mesh_objects),
-                                  sphere_motion=host_scene.sphere_motion(p_scene.spheres, sc.spheres))
+                                  sphere_motion=None if solo else host_scene.sphere_motion(p_scene.spheres, sc.spheres))
                     if form == "objects":
                         out = reproject_objects_ref(*args, max_history=max_history, **tables)
                     else:
-                        deform = (snap, sc.indices, matrices_of(p_scene.mesh_objects), pipeline_world(width, height)["deformed"])
+                        deform = (snap, sc.indices, matrices_of(p_scene.mesh_objects), pipeline_world(width, height, world)["deformed"])
                         out = reproject_deformed_ref(*args, max_history=max_history, deform=deform, **tables)
                 tex["R"], tex["RN"], tex["MV"] = (np.ascontiguousarray(out[n], F) for n in ("color", "count", "motion"))
                 stats.append((i, k, {"kept": float((tex["RN"][..., 0] > 0).mean()), "lost": float((tex["RN"][..., 0] == 0).mean())}))
@@ -1694,7 +2030,7 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
             elif k == "ray_query_async":
                 waiting.append((i, k, ray_hits(oracle(), *query_rays(op[1]))))
             elif k in VERTEX_WRITES:
-                sc = edited_scene(sc, op)
+                sc = edited_scene(sc, op, world)
             elif k == "snapshot":
                 snap = np.array(sc.vertices, F).reshape(-1, 3)
             elif k == "get_buffer":
@@ -1728,7 +2064,7 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
         elif k == "bind_result":
             result = "T1" if result == "T0" else "T0"
         elif k in ("move_mesh", "deform", "move_spheres", "camera"):
-            sc = edited_scene(sc, op)
+            sc = edited_scene(sc, op, world)
         elif k == "get":
             obs.append((i, k, tex[op[1]].copy()))
         elif k == "read_begin":
@@ -1765,9 +2101,9 @@ def run_model(program, width=64, height=40, bounces=2, threads=8, profile="frame
 class _PipelineWorld:
     """The buffers and the plan the pipeline profile adds, on the GPU (pipeline_world holds their contents)."""
 
-    def __init__(self, ctx, m, width, height):
+    def __init__(self, ctx, m, width, height, world="mixed"):
         from unityraytracer_amd.unity_api import ComputeBuffer
-        w = pipeline_world(width, height)
+        w = pipeline_world(width, height, world)
         nv = len(w["rest_v"])
         self.made = []
 
@@ -1784,7 +2120,8 @@ class _PipelineWorld:
         self.SNAP.CopyFrom(self.V)                               # (from here on V has a device mirror: host SetData goes through the upload ring)
         self.skin = [buffer(nv, 12, w["rest_v"]), buffer(nv, 12, w["rest_n"]), buffer(nv, 16, w["bone_idx"]), buffer(nv, 16, w["bone_wgt"])]
         self.bones = [buffer(len(p), 48, p) for p in w["poses"]]
-        self.mesh_motion, self.sphere_motion = buffer(len(m.scene.mesh_objects), 48), buffer(len(m.scene.spheres), 48)
+        self.mesh_motion = buffer(len(m.scene.mesh_objects), 48)
+        self.sphere_motion = buffer(len(m.scene.spheres), 48) if len(m.scene.spheres) else None      # (a zero-count buffer does not exist)
         self.prev_objects, self.deformed = buffer(len(m.scene.mesh_objects), 112), buffer(len(m.scene.mesh_objects), 4, w["deformed"])
         lo, hi = w["span"]
         self.plan = ctx.normals_plan(self.V, m._indexBuffer, lo, hi - lo + 1)
@@ -1811,17 +2148,17 @@ class _DynamicWorld(_PipelineWorld):
     """... and what the dynamic profile adds (dynamic_world holds the contents): the morph plan, W, the leaf buffers, and the two bound
     heap buffers under their names."""
 
-    def __init__(self, ctx, m, width, height):
-        super().__init__(ctx, m, width, height)
-        w = dynamic_world(width, height)
+    def __init__(self, ctx, m, width, height, world="mixed"):
+        super().__init__(ctx, m, width, height, world)
+        w = dynamic_world(width, height, world)
         lo, hi = w["span"]
         self.morph_plan = ctx.morph_plan(w["deltas"], N_TARGETS, lo, hi - lo + 1)
         n = w["counts"]
         self.W = self.made_buffer(N_TARGETS, 4, np.zeros(N_TARGETS, F))
         self.LM = self.made_buffer(n["LM"], 28, np.zeros(n["LM"], scenes.BVHNODE_DT))
-        self.LS = self.made_buffer(n["LS"], 28, np.zeros(n["LS"], scenes.BVHNODE_DT))
+        self.LS = self.made_buffer(n["LS"], 28, np.zeros(n["LS"], scenes.BVHNODE_DT)) if n["LS"] else None
         self.HM, self.HS = m._meshObjectBVHBuffer, m._sphereBVHBuffer
-        assert (self.HM.count, self.HS.count) == (n["HM"], n["HS"])
+        assert (self.HM.count, self.HS.count if self.HS is not None else 0) == (n["HM"], n["HS"])
 
     def made_buffer(self, count, stride, data):
         b = self.ComputeBuffer(self.ctx, count, stride)
@@ -1844,23 +2181,36 @@ class _DynamicWorld(_PipelineWorld):
         super().release()
 
 
-def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=40, bounces=2, profile="frames", probe=None):
-    """The program through the Python API -> (observations, final contents, counters, [(op index, launch_info()) after every op of SUBMITTING]).
+OPTION_DEFAULTS = {"tile_entry": -1, "refit": 1, "prepare_device": 0}      # the library's defaults of the options run_gpu's `options` may name
+
+
+def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=40, bounces=2, profile="frames", probe=None, world="mixed",
+            options=None):
+    """The program through the Python API -> (observations, final contents, counters, [(op index, launch_info()) after every op of SUBMITTING]
+    — profile="solo": after every op outside SOLO_QUIET, and (-1, launch_info()) at the end).
     probe(op index, op, master, the pipeline profile's buffers | None) is called after every op: for protocols that look at the
     library's own bookkeeping (it must not call anything that submits or waits, or the run is no longer the program's).
     profile="display": as in run_model; the states are read at the end through Context.exposure_state.
-    profile="dynamic": as in run_model (the probe's last argument is then a _DynamicWorld, with W, LM, LS, HM and HS)."""
+    profile="dynamic": as in run_model (the probe's last argument is then a _DynamicWorld, with W, LM, LS, HM and HS).
+    profile="solo" / world: as in run_model (LS and HS are None then).  options: {name of OPTION_DEFAULTS: value}, set behind the three
+    options every run sets and put back to the library's defaults at the end."""
     from unityraytracer_amd import Graphics, RayTraceMaster, RenderTexture
-    assert profile in ("frames", "pipeline", "display", "dynamic"), profile
-    dynamic = profile == "dynamic"
+    assert profile in ("frames", "pipeline", "display", "dynamic", "solo"), profile
+    world = "solo" if profile == "solo" else world
+    solo = world == "solo"
+    dynamic = profile in ("dynamic", "solo")
     display = profile == "display" or dynamic
     pipeline = profile == "pipeline" or display
+    options = dict(options or {})
+    assert set(options) <= set(OPTION_DEFAULTS), options
     ctx.set_option("kernel_mode", 3)
     ctx.set_option("frames_per_launch", frames_per_launch)
     ctx.set_option("overlap_launches", overlap_launches)
     m, tex, pw = None, {}, None
     try:
-        sc = make_scene(width, height, bounces)
+        for name, value in options.items():
+            ctx.set_option(name, value)
+        sc = make_scene(width, height, bounces, world)
         m = RayTraceMaster(ctx, sc, frame_seed=FRAME_SEED)
         for n in FRAME_TEX + (PIPE_TEX if pipeline else ()) + (UP_TEX if display else ()):
             tex[n] = RenderTexture(ctx, width, height)
@@ -1874,10 +2224,10 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
         if pipeline:
             import torch
             from unityraytracer_amd import host_scene
-            pw = (_DynamicWorld if dynamic else _PipelineWorld)(ctx, m, width, height)
+            pw = (_DynamicWorld if dynamic else _PipelineWorld)(ctx, m, width, height, world)
             dev = torch.device("cuda", ctx.device)
             bufs = {"V": pw.V, "NB": pw.NB, "SNAP": pw.SNAP}
-            heap_bufs = {n: getattr(pw, n) for n in HEAP_BUFFERS} if dynamic else {}
+            heap_bufs = {n: getattr(pw, n) for n in HEAP_BUFFERS if getattr(pw, n) is not None} if dynamic else {}
         if display:
             states = [torch.zeros(STATE_WORDS, dtype=torch.int32, device=dev) for _ in STATES]
             m.EnableAutoExposure(**MASTER_EXPOSURE)
@@ -1897,7 +2247,7 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
         def vertex_edit(op, host_heap=True):
             """An op of VERTEX_WRITES or a morph, with (the ops as the older profiles know them) or without the host SetData of the heap."""
             k = op[0]
-            new = edited_scene(m.scene, op)
+            new = edited_scene(m.scene, op, world)
             if k == "skin":
                 ctx.skin_vertices(*pw.skin, pw.bones[op[1]], op[3], op[4], pw.V, pw.NB if op[2] else None)
             elif k == "normals":
@@ -1920,7 +2270,7 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
         def object_edit(op, host_heap=True):
             """move_mesh, deform, move_spheres or camera, likewise."""
             k = op[0]
-            new = edited_scene(m.scene, op)
+            new = edited_scene(m.scene, op, world)
             if k == "move_mesh":
                 m._meshObjectBuffer.SetData(new.mesh_objects)
             elif k == "deform":
@@ -1936,8 +2286,16 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
 
         for i, op in enumerate(program):
             k = op[0]
+            if profile == "solo" and i and program[i - 1][0] not in SOLO_QUIET + SUBMITTING:
+                infos.append((i - 1, ctx.launch_info()))         # (the op before this one has submitted what was deferred: asking changes nothing)
             if pipeline and k in OBSERVERS:
                 drain()
+            if k == "motion_blur":
+                assert profile == "solo", op
+                ctx.motion_blur(tex[op[1]], tex["MV"], tex[op[2]], tex[op[3]], **MBLUR[op[4]])
+                if probe:
+                    probe(i, op, m, pw)
+                continue
             if dynamic and (k in DYNAMIC_KINDS or (k == "get_buffer" and op[1] in HEAP_BUFFERS)):
                 if k == "morph":
                     vertex_edit(op)
@@ -2002,13 +2360,15 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
                     extra = {}
                     if form != "plain":
                         pw.mesh_motion.SetData(host_scene.mesh_motion(p_scene.mesh_objects, m.scene.mesh_objects))
-                        pw.sphere_motion.SetData(host_scene.sphere_motion(p_scene.spheres, m.scene.spheres))
-                        extra = dict(mesh_motion=pw.mesh_motion, sphere_motion=pw.sphere_motion)
+                        extra = dict(mesh_motion=pw.mesh_motion)
+                        if pw.sphere_motion is not None:
+                            pw.sphere_motion.SetData(host_scene.sphere_motion(p_scene.spheres, m.scene.spheres))
+                            extra["sphere_motion"] = pw.sphere_motion
                     if form == "deformed":
                         pw.prev_objects.SetData(p_scene.mesh_objects)
                         extra["deform"] = (pw.SNAP, m._indexBuffer, pw.prev_objects, pw.deformed)
                     ctx.reproject(*[tex[n] for n in (src, "N", "Ph", "Pn", "Pi", "Gh", "Gn", "Gi", "R", "RN")],
-                                  scenes.world_to_clip(cameras(m.scene)[j], m.scene.camera_inverse_projection), motion=tex["MV"],
+                                  scenes.world_to_clip(cameras(m.scene, world)[j], m.scene.camera_inverse_projection), motion=tex["MV"],
                                   max_history=max_history, **extra)
                 elif k == "denoise":
                     ctx.denoise(tex[op[1]], tex["D"], tex["Gh"], tex["Gn"], tex["Ga"] if op[3] else None, iterations=op[2])
@@ -2107,6 +2467,8 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
         if pipeline:
             drain()
         final = {n: t.GetPixels() for n, t in tex.items()}
+        if profile == "solo":                                    # (everything is submitted: the last launch of the run, under the index -1)
+            infos.append((-1, ctx.launch_info()))
         if pipeline:
             for name, b in bufs.items():
                 final[name], final[name + ".dev"] = pw.both_sides(b)
@@ -2123,6 +2485,8 @@ def run_gpu(ctx, program, frames_per_launch, overlap_launches, width=64, height=
     finally:
         ctx.set_option("frames_per_launch", 0)
         ctx.set_option("overlap_launches", 1)
+        for name in options:
+            ctx.set_option(name, OPTION_DEFAULTS[name])
         if pw is not None:
             ctx.synchronize()                                    # (nothing enqueued still reads a tensor or a buffer of this run)
             pw.release()
