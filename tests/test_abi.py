@@ -51,7 +51,7 @@ def test_experiment_switches_are_quarantined():
     for name in used:
         assert f"defined({name})" in guard, f"{name} is a compile-time switch that csrc/experiments.h does not guard"
     sources = {f for f in os.listdir(csrc) if f.endswith((".cpp", ".hip")) and '#include "experiments.h"' in open(os.path.join(csrc, f)).read()}
-    assert {"scene_prep.cpp", "frame_batch.cpp", "image_ops.cpp"} <= sources       # the files context.cpp was split into
+    assert {"scene_prep.cpp", "frame_batch.cpp", "image_ops.cpp", "geometry_ops.cpp"} <= sources       # the files context.cpp was split into
     for src in sorted(sources | {"kernels.hip", "kernels_basic.hip", "kernels_serve.hip", "kernels_pool.hip", "context.cpp", "blas_builder.cpp"}):
         head = open(os.path.join(csrc, src)).read()
         first_include = re.search(r'^#include\s+[<"]([^">]+)[">]', head, re.M).group(1)

@@ -19,8 +19,8 @@ HIPCC_FLAGS = [
     "-Wall", "-Wno-unused-function",
 ]
 # the sources that see the -D switches of an A/B build (through csrc/experiments.h); build_variant recompiles exactly these
-VARIANT_SOURCES = ["kernels.hip", "kernels_basic.hip", "kernels_serve.hip", "kernels_pool.hip", "context.cpp", "scene_prep.cpp", "frame_batch.cpp", "image_ops.cpp", "blas_builder.cpp"]
-SOURCES = ["kernels.hip", "kernels_basic.hip", "kernels_serve.hip", "kernels_pool.hip", "query.hip", "radiance.hip", "aov.hip", "denoise.hip", "reproject.hip", "upsample.hip", "tonemap.hip", "bloom.hip", "dof.hip", "motion_blur.hip", "resample.hip", "lbvh.hip", "refit.hip", "index_span.hip", "skin.hip", "object_bvh.hip", "morph.hip", "normals.hip", "qnodes.hip", "cones.hip", "tile_entry.hip", "cullflags.hip", "present.hip", "context.cpp", "scene_prep.cpp", "frame_batch.cpp", "image_ops.cpp", "blas_builder.cpp", "host_scene.cpp", "normals_plan.cpp", "morph_plan.cpp", "host_io.cpp", "host_debug.cpp", "group.cpp"]
+VARIANT_SOURCES = ["kernels.hip", "kernels_basic.hip", "kernels_serve.hip", "kernels_pool.hip", "context.cpp", "scene_prep.cpp", "frame_batch.cpp", "image_ops.cpp", "geometry_ops.cpp", "blas_builder.cpp"]
+SOURCES = ["kernels.hip", "kernels_basic.hip", "kernels_serve.hip", "kernels_pool.hip", "query.hip", "radiance.hip", "aov.hip", "denoise.hip", "reproject.hip", "upsample.hip", "tonemap.hip", "bloom.hip", "dof.hip", "motion_blur.hip", "resample.hip", "lbvh.hip", "refit.hip", "index_span.hip", "skin.hip", "object_bvh.hip", "morph.hip", "normals.hip", "qnodes.hip", "cones.hip", "tile_entry.hip", "cullflags.hip", "present.hip", "context.cpp", "scene_prep.cpp", "frame_batch.cpp", "image_ops.cpp", "geometry_ops.cpp", "blas_builder.cpp", "host_scene.cpp", "normals_plan.cpp", "morph_plan.cpp", "host_io.cpp", "host_debug.cpp", "group.cpp"]
 
 
 def _newer(target: str, deps) -> bool:

@@ -1,8 +1,8 @@
-// context.cpp — implementation of the C ABI in include/urt.h.
+// context.cpp — implementation of the C ABI in include/urt.h: the context and the objects it hands out (the other files: context_impl.h).
 //
 // Stands in for the UnityEngine GPU objects RayTraceMaster.cs drives:
 //   ComputeBuffer   -> Buffer   (host copy kept; the device form is DERIVED at the next dispatch; an optional device mirror takes
-//                                device-side writes: urt_buffer_set_data_device, urt_skin_vertices)
+//                                device-side writes: urt_buffer_set_data_device and urt_buffer_copy here, the calls of geometry_ops.cpp)
 //   RenderTexture   -> Texture  (RGBA32F device image)
 //   ComputeShader   -> the uniform/binding table in urt_context + dispatch of the HIP kernels
 //   Graphics.Blit   -> urt_blit / urt_blit_add
@@ -12,18 +12,11 @@
 #include "tile_entry.h"
 
 #include <climits>
-#include <limits>
 #include <memory>
 
 #include "index_span.h"
-#include "morph.h"
-#include "morph_plan.h"
-#include "object_bvh.h"
-#include "normals.h"
-#include "normals_plan.h"
 #include "present.h"
 #include "reproject.h"
-#include "skin.h"
 
 using namespace urtd;
 
@@ -95,6 +88,27 @@ int buffer_mirror(urt_context* ctx, Buffer& b) {
 // strips first_row, first_row + row_stride, ... of 8-row groups that lie in the first group_rows
 int strip_count(int group_rows, int first_row, int row_stride) {
   return first_row < group_rows ? (group_rows - first_row + row_stride - 1) / row_stride : 0;
+}
+
+// Elements first .. last have changed: they join the dirty range, and every slot the buffer is bound to asks for a preparation.
+static void mark_changed(urt_context* ctx, urt_handle buffer, Buffer& b, int first, int last) {
+  b.mark_dirty(first, last);
+  for (int s = 0; s < B_COUNT; s++) if (ctx->bound[s] == buffer) { ctx->scene_dirty = true; ctx->dirty_slots |= 1u << s; }
+}
+
+// A device-side writer has filled elements first .. first + count - 1 of the mirror (count > 0): `host` is behind there, and every element
+// counts as changed.
+void mark_device_written(urt_context* ctx, urt_handle buffer, Buffer& b, int first, int count) {
+  const bool fresh = !b.has_data;                            // set for the first time: new as a whole, as with SetData
+  b.has_data = true;
+  b.mark_stale(first, first + count - 1);
+  mark_changed(ctx, buffer, b, fresh ? 0 : first, fresh ? b.count - 1 : first + count - 1);
+}
+
+int check_element_range(urt_context* ctx, const char* who, const Buffer& b, int first, int count) {
+  if (first < 0 || count < 0 || (long long)first + (long long)count > (long long)b.count)
+    return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(who) + ": the element range lies outside the buffer");
+  return URT_OK;
 }
 
 }  // namespace urtd
@@ -237,12 +251,6 @@ static int push_elements(urt_context* ctx, Buffer& b, int first, int last) {
   return URT_OK;
 }
 
-// Elements first .. last have changed: they join the dirty range, and every slot the buffer is bound to asks for a preparation.
-static void mark_changed(urt_context* ctx, urt_handle buffer, Buffer& b, int first, int last) {
-  b.mark_dirty(first, last);
-  for (int s = 0; s < B_COUNT; s++) if (ctx->bound[s] == buffer) { ctx->scene_dirty = true; ctx->dirty_slots |= 1u << s; }
-}
-
 // SetData of elements first .. first + count - 1 (arguments checked by the callers): data equal to what the buffer holds changes nothing and
 // dirties nothing (the reference re-uploads EVERY list whenever anything changed, RM:738-745; a compare costs what the copy would);
 // else the elements between the first and the last differing byte join the buffer's dirty range.  Elements inside the stale range differ
@@ -300,21 +308,6 @@ int urt_buffer_set_data_range(urt_context* ctx, urt_handle buffer, int first, co
   return set_data_elements(ctx, buffer, b, first, data, count);
 }
 
-// A device-side writer has filled elements first .. first + count - 1 of the mirror (count > 0): `host` is behind there, and every element
-// counts as changed.
-static void mark_device_written(urt_context* ctx, urt_handle buffer, Buffer& b, int first, int count) {
-  const bool fresh = !b.has_data;                            // set for the first time: new as a whole, as with SetData
-  b.has_data = true;
-  b.mark_stale(first, first + count - 1);
-  mark_changed(ctx, buffer, b, fresh ? 0 : first, fresh ? b.count - 1 : first + count - 1);
-}
-
-static int check_element_range(urt_context* ctx, const char* who, const Buffer& b, int first, int count) {
-  if (first < 0 || count < 0 || (long long)first + (long long)count > (long long)b.count)
-    return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(who) + ": the element range lies outside the buffer");
-  return URT_OK;
-}
-
 int urt_buffer_set_data_device(urt_context* ctx, urt_handle buffer, int first, const void* d_data, int count) {
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   Buffer* b = find_buffer(ctx, buffer);
@@ -365,161 +358,6 @@ int urt_buffer_get_data_range(urt_context* ctx, urt_handle buffer, int first, vo
   return URT_OK;
 }
 
-int urt_skin_vertices(urt_context* ctx, const urt_SkinBuffers* in, int first, int count, urt_handle dst_vertices, urt_handle dst_normals) {
-  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  if (!in) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "skin_vertices: in is NULL");
-  URT_GUARD_BEGIN
-  const bool normals = dst_normals != 0;
-  if (normals && !in->rest_normals) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "skin_vertices: dst_normals without rest_normals");
-  enum { kRestV, kRestN, kIdx, kWgt, kBones, kDstV, kDstN, kArgs };
-  const urt_handle h[kArgs] = {in->rest_vertices, normals ? in->rest_normals : 0, in->bone_indices, in->bone_weights, in->bones, dst_vertices, dst_normals};
-  const char* const name[kArgs] = {"rest_vertices", "rest_normals", "bone_indices", "bone_weights", "bones", "dst_vertices", "dst_normals"};
-  const int stride[kArgs] = {12, 12, 16, 16, (int)sizeof(urt_ObjectMotion), 12, 12};
-  Buffer* b[kArgs];
-  for (int k = 0; k < kArgs; k++) {
-    b[k] = nullptr;
-    if (!normals && (k == kRestN || k == kDstN)) continue;
-    b[k] = find_buffer(ctx, h[k]);
-    if (!b[k]) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string("skin_vertices: ") + name[k] + " is 0 or an unknown buffer handle");
-  }
-  if (!normals && in->rest_normals && !find_buffer(ctx, in->rest_normals))
-    return fail(ctx, URT_ERR_INVALID_HANDLE, "skin_vertices: rest_normals is an unknown buffer handle");
-  for (int k = 0; k < kArgs; k++) {
-    if (!b[k]) continue;
-    if (b[k]->stride != stride[k]) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("skin_vertices: the stride of ") + name[k] + " is not " + std::to_string(stride[k]));
-    if (k != kBones && b[k]->count != b[kRestV]->count) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("skin_vertices: the count of ") + name[k] + " is not that of rest_vertices");
-    if (k < kDstV && (h[k] == dst_vertices || h[k] == dst_normals)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("skin_vertices: ") + name[k] + " is also a destination");
-  }
-  if (normals && dst_normals == dst_vertices) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "skin_vertices: dst_vertices and dst_normals are one buffer");
-  if (int rc = check_element_range(ctx, "skin_vertices", *b[kRestV], first, count)) return rc;
-  if (count == 0) return URT_OK;
-  for (int k = 0; k < kArgs; k++) if (b[k]) if (int rc = buffer_mirror(ctx, *b[k])) return rc;
-  URT_HIP(ctx, skin_vertices((const float*)b[kRestV]->mirror.get(), normals ? (const float*)b[kRestN]->mirror.get() : nullptr,
-                             (const int32_t*)b[kIdx]->mirror.get(), (const float*)b[kWgt]->mirror.get(), (const float*)b[kBones]->mirror.get(),
-                             b[kBones]->count, first, count, (float*)b[kDstV]->mirror.get(), normals ? (float*)b[kDstN]->mirror.get() : nullptr, touch(ctx)));
-  mark_device_written(ctx, dst_vertices, *b[kDstV], first, count);
-  if (normals) mark_device_written(ctx, dst_normals, *b[kDstN], first, count);
-  return URT_OK;
-  URT_GUARD_END(ctx)
-}
-
-int urt_buffer_bounds(urt_context* ctx, urt_handle buffer, int first, int count, float out6[6], int* out_n) {
-  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  Buffer* b = find_buffer(ctx, buffer);
-  if (!b) return fail(ctx, URT_ERR_INVALID_HANDLE, "buffer_bounds: unknown buffer handle");
-  if (b->stride != 12) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "buffer_bounds: the stride of the buffer is not 12");
-  if (int rc = check_element_range(ctx, "buffer_bounds", *b, first, count)) return rc;
-  if (!out6) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "buffer_bounds: out6 is NULL");
-  URT_GUARD_BEGIN
-  const float inf = std::numeric_limits<float>::infinity();
-  for (int c = 0; c < 3; c++) { out6[c] = inf; out6[3 + c] = -inf; }
-  if (out_n) *out_n = 0;
-  if (count == 0) return URT_OK;
-  if (int rc = buffer_mirror(ctx, *b)) return rc;
-  URT_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t words = (size_t)(kBoundsMaxBlocks + 1) * kBoundsWords;
-  if (int rc = reserve(ctx, ctx->bd_partial, words, "buffer_bounds: scratch allocation", ctx->stream)) return rc;
-  if (!ctx->bd_result) URT_HIP(ctx, ctx->bd_result.alloc(kBoundsWords));
-  float* d_out = ctx->bd_partial.get() + (size_t)kBoundsMaxBlocks * kBoundsWords;
-  URT_HIP(ctx, buffer_bounds((const float*)b->mirror.get(), first, count, ctx->bd_partial.get(), d_out, touch(ctx)));
-  URT_HIP(ctx, hipMemcpyAsync(ctx->bd_result.get(), d_out, kBoundsWords * sizeof(float), hipMemcpyDeviceToHost, touch(ctx)));
-  URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
-  std::memcpy(out6, ctx->bd_result.get(), 6 * sizeof(float));
-  uint32_t n = 0;
-  std::memcpy(&n, ctx->bd_result.get() + 6, 4);
-  if (out_n) *out_n = (int)n;
-  return check_watchdog(ctx);
-  URT_GUARD_END(ctx)
-}
-
-/* ---- the object-level BVH on the device (include/urt.h; csrc/object_bvh.hip) ---- */
-static_assert(URT_OBJECT_BVH_DEVICE_MAX == urtd::kObjectBvhDeviceMax && URT_MESH_LEAF_BLOCKS == urtd::kMeshLeafBlocks, "include/urt.h: the constants of csrc/object_bvh.h");
-
-// The buffers of one of the three calls, looked up and checked: handles first, then strides.  b[k] is set for every k on URT_OK.
-static int object_bvh_buffers(urt_context* ctx, const char* who, int n, const urt_handle* h, const char* const* name, const int* stride, Buffer** b) {
-  for (int k = 0; k < n; k++) {
-    b[k] = find_buffer(ctx, h[k]);
-    if (!b[k]) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string(who) + ": " + name[k] + " is 0 or an unknown buffer handle");
-  }
-  for (int k = 0; k < n; k++)
-    if (b[k]->stride != stride[k]) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(who) + ": the stride of " + name[k] + " is not " + std::to_string(stride[k]));
-  for (int k = 0; k + 1 < n; k++)
-    if (h[k] == h[n - 1]) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + name[k] + " is also the destination");
-  return URT_OK;
-}
-
-int urt_mesh_leaf_bounds_device(urt_context* ctx, urt_handle mesh_objects, urt_handle vertices, urt_handle indices, urt_handle dst_leaves) {
-  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  URT_GUARD_BEGIN
-  enum { kMeshes, kVerts, kIdx, kDst, kArgs };
-  const urt_handle h[kArgs] = {mesh_objects, vertices, indices, dst_leaves};
-  const char* const name[kArgs] = {"mesh_objects", "vertices", "indices", "dst_leaves"};
-  const int stride[kArgs] = {URT_STRIDE_MESHOBJECT, URT_STRIDE_VEC3, URT_STRIDE_INDEX, URT_STRIDE_BVHNODE};
-  Buffer* b[kArgs];
-  if (int rc = object_bvh_buffers(ctx, "mesh_leaf_bounds_device", kArgs, h, name, stride, b)) return rc;
-  const int n = b[kMeshes]->count;
-  if (b[kDst]->count != n) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "mesh_leaf_bounds_device: the count of dst_leaves is not that of mesh_objects");
-  if (n == 0) return URT_OK;
-  if (int rc = buffer_sync_host(ctx, *b[kMeshes])) return rc;   // the ranges are validated where the host can read them
-  for (int m = 0; m < n; m++) {
-    urt_MeshObject mo;
-    std::memcpy(&mo, b[kMeshes]->host.data() + (size_t)m * sizeof mo, sizeof mo);
-    if (mo.indices_offset < 0 || mo.indices_count < 0 || (long long)mo.indices_offset + (long long)mo.indices_count > (long long)b[kIdx]->count)
-      return fail(ctx, URT_ERR_SCENE, "mesh_leaf_bounds_device: MeshObject " + std::to_string(m) + " names a range outside indices");
-  }
-  URT_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t rows = (size_t)std::min(n, 65535);
-  if (int rc = reserve(ctx, ctx->ob_partial, rows * kMeshLeafBlocks * kMeshLeafWords, "mesh_leaf_bounds_device: scratch allocation", ctx->stream)) return rc;
-  for (int k = 0; k < kArgs; k++) if (int rc = buffer_mirror(ctx, *b[k])) return rc;
-  URT_HIP(ctx, mesh_leaf_bounds(b[kMeshes]->mirror.get(), n, (const float*)b[kVerts]->mirror.get(), b[kVerts]->count,
-                                (const int32_t*)b[kIdx]->mirror.get(), b[kIdx]->count, ctx->ob_partial.get(), b[kDst]->mirror.get(), touch(ctx)));
-  mark_device_written(ctx, dst_leaves, *b[kDst], 0, n);
-  return URT_OK;
-  URT_GUARD_END(ctx)
-}
-
-int urt_sphere_leaf_bounds_device(urt_context* ctx, urt_handle spheres, urt_handle dst_leaves) {
-  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  URT_GUARD_BEGIN
-  const urt_handle h[2] = {spheres, dst_leaves};
-  const char* const name[2] = {"spheres", "dst_leaves"};
-  const int stride[2] = {URT_STRIDE_SPHERE, URT_STRIDE_BVHNODE};
-  Buffer* b[2];
-  if (int rc = object_bvh_buffers(ctx, "sphere_leaf_bounds_device", 2, h, name, stride, b)) return rc;
-  const int n = b[0]->count;
-  if (b[1]->count != n) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "sphere_leaf_bounds_device: the count of dst_leaves is not that of spheres");
-  if (n == 0) return URT_OK;
-  URT_HIP(ctx, hipSetDevice(ctx->device));
-  for (int k = 0; k < 2; k++) if (int rc = buffer_mirror(ctx, *b[k])) return rc;
-  URT_HIP(ctx, sphere_leaf_bounds(b[0]->mirror.get(), n, b[1]->mirror.get(), touch(ctx)));
-  mark_device_written(ctx, dst_leaves, *b[1], 0, n);
-  return URT_OK;
-  URT_GUARD_END(ctx)
-}
-
-int urt_build_object_bvh_device(urt_context* ctx, urt_handle leaves, urt_handle dst_nodes) {
-  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  URT_GUARD_BEGIN
-  const urt_handle h[2] = {leaves, dst_nodes};
-  const char* const name[2] = {"leaves", "dst_nodes"};
-  const int stride[2] = {URT_STRIDE_BVHNODE, URT_STRIDE_BVHNODE};
-  Buffer* b[2];
-  if (int rc = object_bvh_buffers(ctx, "build_object_bvh_device", 2, h, name, stride, b)) return rc;
-  const int n = b[0]->count;
-  if (n > URT_OBJECT_BVH_DEVICE_MAX)
-    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "build_object_bvh_device: more than " + std::to_string(URT_OBJECT_BVH_DEVICE_MAX) +
-                                                   " leaves: build this heap with urt_host_build_object_bvh");
-  const int len = urt_host_object_bvh_length(n);
-  if (b[1]->count != len) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "build_object_bvh_device: the count of dst_nodes is not urt_host_object_bvh_length(" + std::to_string(n) + ") = " + std::to_string(len));
-  if (n == 0) return URT_OK;
-  URT_HIP(ctx, hipSetDevice(ctx->device));
-  for (int k = 0; k < 2; k++) if (int rc = buffer_mirror(ctx, *b[k])) return rc;
-  URT_HIP(ctx, build_object_bvh(b[0]->mirror.get(), n, b[1]->mirror.get(), len, touch(ctx)));
-  mark_device_written(ctx, dst_nodes, *b[1], 0, len);
-  return URT_OK;
-  URT_GUARD_END(ctx)
-}
-
 int urt_debug_buffer_state(urt_context* ctx, urt_handle buffer, uint64_t out4[4]) {
   if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
   const Buffer* b = find_buffer(ctx, buffer);
@@ -529,206 +367,6 @@ int urt_debug_buffer_state(urt_context* ctx, urt_handle buffer, uint64_t out4[4]
   out4[2] = b->mirror ? (uint64_t)b->count * (uint64_t)b->stride : 0;
   out4[3] = b->downloads;
   return URT_OK;
-}
-
-/* ---- normals on the device (include/urt.h; csrc/normals_plan.h, csrc/normals.hip) ---- */
-int urt_normals_plan_create(urt_context* ctx, urt_handle vertices, urt_handle indices, int first, int count, urt_handle* out_plan) {
-  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  if (!out_plan) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "normals_plan_create: out_plan is NULL");
-  *out_plan = 0;
-  URT_GUARD_BEGIN
-  Buffer* v = find_buffer(ctx, vertices);
-  Buffer* ix = find_buffer(ctx, indices);
-  if (!v || !ix) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string("normals_plan_create: ") + (!v ? "vertices" : "indices") + " is 0 or an unknown buffer handle");
-  if (v->stride != 12) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "normals_plan_create: the stride of vertices is not 12");
-  if (ix->stride != 4) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "normals_plan_create: the stride of indices is not 4");
-  if (ix->count % 3 != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "normals_plan_create: the count of indices is not a multiple of 3");
-  if (int rc = check_element_range(ctx, "normals_plan_create", *v, first, count)) return rc;
-  if (int rc = buffer_sync_host(ctx, *v)) return rc;         // the weld is found from the buffers' contents NOW
-  if (int rc = buffer_sync_host(ctx, *ix)) return rc;
-  NormalsPlan plan;
-  if (normals_plan_build((const float*)v->host.data(), v->count, (const int32_t*)ix->host.data(), ix->count, first, count, plan) != kNormalsPlanOk)
-    return fail(ctx, URT_ERR_SCENE, "normals_plan_create: index outside _Vertices");
-  DevNormalsPlan d;
-  d.vertices = vertices; d.n_vertices = v->count;
-  d.first = first; d.count = count; d.n_lists = plan.n_lists; d.max_valence = plan.max_valence;
-  d.n_triangles = (int)(plan.tris.size() / 3); d.n_entries = (int)plan.entries.size();
-  URT_HIP(ctx, hipSetDevice(ctx->device));
-  const std::pair<DeviceBuf<int32_t>*, const std::vector<int32_t>*> parts[3] = {{&d.tris, &plan.tris}, {&d.entries, &plan.entries}, {&d.ranges, &plan.ranges}};
-  for (const auto& p : parts) {
-    if (p.second->empty()) continue;
-    const size_t bytes = p.second->size() * sizeof(int32_t);
-    URT_HIP(ctx, p.first->alloc(p.second->size()));           // (a failure leaves through the holders: nothing stays allocated)
-    URT_HIP(ctx, hipMemcpy(p.first->get(), p.second->data(), bytes, hipMemcpyHostToDevice));
-    d.device_bytes += bytes;
-  }
-  const urt_handle h = ctx->next_id++;
-  ctx->normals_plans.emplace(h, std::move(d));
-  *out_plan = h;
-  return URT_OK;
-  URT_GUARD_END(ctx)
-}
-
-int urt_normals_plan_info(urt_context* ctx, urt_handle plan, urt_NormalsPlanInfo* out) {
-  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  auto it = ctx->normals_plans.find(plan);
-  if (it == ctx->normals_plans.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "normals_plan_info: unknown plan handle");
-  if (!out) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "normals_plan_info: out is NULL");
-  const DevNormalsPlan& d = it->second;
-  out->first = d.first; out->count = d.count; out->n_lists = d.n_lists; out->n_triangles = d.n_triangles;
-  out->n_entries = d.n_entries; out->max_valence = d.max_valence; out->device_bytes = d.device_bytes;
-  return URT_OK;
-}
-
-int urt_normals_plan_release(urt_context* ctx, urt_handle plan) {
-  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  auto it = ctx->normals_plans.find(plan);
-  if (it == ctx->normals_plans.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "normals_plan_release: unknown plan handle");
-  if (it->second.device_bytes) {                             // kernels queued on the stream may still read the plan
-    URT_HIP(ctx, hipSetDevice(ctx->device));
-    URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
-  }
-  ctx->normals_plans.erase(it);
-  return URT_OK;
-}
-
-int urt_compute_normals(urt_context* ctx, urt_handle plan, urt_handle dst_normals) {
-  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  URT_GUARD_BEGIN
-  auto it = ctx->normals_plans.find(plan);
-  if (it == ctx->normals_plans.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "compute_normals: unknown plan handle");
-  const DevNormalsPlan& d = it->second;
-  Buffer* v = find_buffer(ctx, d.vertices);
-  if (!v || v->count != d.n_vertices || v->stride != 12) return fail(ctx, URT_ERR_INVALID_HANDLE, "compute_normals: the plan's vertices buffer was released");
-  Buffer* dst = find_buffer(ctx, dst_normals);
-  if (!dst) return fail(ctx, URT_ERR_INVALID_HANDLE, "compute_normals: dst_normals is 0 or an unknown buffer handle");
-  if (dst->stride != 12) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "compute_normals: the stride of dst_normals is not 12");
-  if (dst->count != v->count) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "compute_normals: the count of dst_normals is not that of the vertices buffer");
-  if (dst_normals == d.vertices) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "compute_normals: dst_normals is the vertices buffer");
-  if (d.count == 0) return URT_OK;
-  if (int rc = buffer_mirror(ctx, *v)) return rc;
-  if (int rc = buffer_mirror(ctx, *dst)) return rc;
-  URT_HIP(ctx, hipSetDevice(ctx->device));
-  if (int rc = reserve(ctx, ctx->nm_face, (size_t)d.n_triangles, "compute_normals: scratch allocation", ctx->stream)) return rc;
-  URT_HIP(ctx, compute_normals((const float*)v->mirror.get(), d.tris.get(), d.n_triangles, d.ranges.get(), d.entries.get(), d.first, d.count,
-                               ctx->nm_face.get(), (float*)dst->mirror.get(), touch(ctx)));
-  mark_device_written(ctx, dst_normals, *dst, d.first, d.count);
-  return URT_OK;
-  URT_GUARD_END(ctx)
-}
-
-/* ---- blend shapes on the device (include/urt.h; csrc/morph_plan.h, csrc/morph.hip) ---- */
-static_assert(sizeof(urt_MorphDelta) == 32 && sizeof(urtd::MorphDeltaIn) == 32 && sizeof(urt_MorphPlanInfo) == 32, "include/urt.h: morph layouts");
-
-int urt_morph_plan_create(urt_context* ctx, const urt_MorphDelta* deltas, int n_deltas, int n_targets, int first, int count, urt_handle* out_plan) {
-  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  if (!out_plan) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_plan_create: out_plan is NULL");
-  *out_plan = 0;
-  URT_GUARD_BEGIN
-  if (n_deltas < 0 || count < 0 || first < 0 || (long long)first + (long long)count > 0x7fffffffLL)
-    return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_plan_create: a negative n_deltas, first or count, or a served range beyond 2^31 - 1");
-  if (n_deltas > 0 && !deltas) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_plan_create: deltas is NULL");
-  if (n_targets < 1 || n_targets > kMorphMaxTargets) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_plan_create: n_targets is outside 1..4096");
-  const MorphDeltaIn* in = (const MorphDeltaIn*)deltas;
-  MorphPlan plan;
-  if (const int rc = morph_plan_build(in, n_deltas, n_targets, first, count, plan))
-    return fail(ctx, URT_ERR_SCENE, rc == kMorphPlanBadVertex ? "morph_plan_create: a delta names a vertex outside the served range"
-                                                               : "morph_plan_create: a delta names a target outside 0..n_targets-1");
-  // the entries in plan order, as csrc/morph.hip reads them: this is the copy of `deltas`
-  std::vector<int32_t> targets((size_t)n_deltas);
-  std::vector<float> values(6 * (size_t)n_deltas);
-  for (size_t e = 0; e < (size_t)n_deltas; e++) {
-    const MorphDeltaIn& d = in[plan.order[e]];
-    targets[e] = d.target;
-    std::memcpy(&values[6 * e], d.dp, 12);
-    std::memcpy(&values[6 * e + 3], d.dn, 12);
-  }
-  DevMorphPlan d;
-  d.first = first; d.count = count; d.n_targets = n_targets; d.n_entries = n_deltas; d.max_valence = plan.max_valence; d.n_touched = plan.n_touched;
-  URT_HIP(ctx, hipSetDevice(ctx->device));
-  const auto upload = [&](auto& buf, const auto& host) -> hipError_t {       // (a failure leaves through the holders: nothing stays allocated)
-    if (host.empty()) return hipSuccess;
-    const size_t bytes = host.size() * sizeof(host[0]);
-    if (hipError_t e = buf.alloc(host.size())) return e;
-    d.device_bytes += bytes;
-    return hipMemcpy(buf.get(), host.data(), bytes, hipMemcpyHostToDevice);
-  };
-  URT_HIP(ctx, upload(d.ranges, plan.ranges));
-  URT_HIP(ctx, upload(d.targets, targets));
-  URT_HIP(ctx, upload(d.deltas, values));
-  const urt_handle h = ctx->next_id++;
-  ctx->morph_plans.emplace(h, std::move(d));
-  *out_plan = h;
-  return URT_OK;
-  URT_GUARD_END(ctx)
-}
-
-int urt_morph_plan_info(urt_context* ctx, urt_handle plan, urt_MorphPlanInfo* out) {
-  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  auto it = ctx->morph_plans.find(plan);
-  if (it == ctx->morph_plans.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "morph_plan_info: unknown plan handle");
-  if (!out) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_plan_info: out is NULL");
-  const DevMorphPlan& d = it->second;
-  out->first = d.first; out->count = d.count; out->n_targets = d.n_targets; out->n_entries = d.n_entries;
-  out->max_valence = d.max_valence; out->n_touched = d.n_touched; out->device_bytes = d.device_bytes;
-  return URT_OK;
-}
-
-int urt_morph_plan_release(urt_context* ctx, urt_handle plan) {
-  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  auto it = ctx->morph_plans.find(plan);
-  if (it == ctx->morph_plans.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "morph_plan_release: unknown plan handle");
-  if (it->second.device_bytes) {                             // kernels queued on the stream may still read the plan
-    URT_HIP(ctx, hipSetDevice(ctx->device));
-    URT_HIP(ctx, hipStreamSynchronize(touch(ctx)));
-  }
-  ctx->morph_plans.erase(it);
-  return URT_OK;
-}
-
-int urt_morph_vertices(urt_context* ctx, urt_handle plan, urt_handle rest_vertices, urt_handle rest_normals, urt_handle weights,
-                       urt_handle dst_vertices, urt_handle dst_normals, int flags) {
-  if (!ctx) return fail(nullptr, URT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  URT_GUARD_BEGIN
-  auto it = ctx->morph_plans.find(plan);
-  if (it == ctx->morph_plans.end()) return fail(ctx, URT_ERR_INVALID_HANDLE, "morph_vertices: unknown plan handle");
-  const DevMorphPlan& d = it->second;
-  if (flags & ~URT_MORPH_NORMALIZE) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_vertices: unknown flags");
-  const bool normals = dst_normals != 0;
-  if ((flags & URT_MORPH_NORMALIZE) && !normals) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_vertices: URT_MORPH_NORMALIZE without dst_normals");
-  if (normals && !rest_normals) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_vertices: dst_normals without rest_normals");
-  enum { kRestV, kRestN, kWeights, kDstV, kDstN, kArgs };
-  const urt_handle h[kArgs] = {rest_vertices, normals ? rest_normals : 0, weights, dst_vertices, dst_normals};
-  const char* const name[kArgs] = {"rest_vertices", "rest_normals", "weights", "dst_vertices", "dst_normals"};
-  const int stride[kArgs] = {12, 12, 4, 12, 12};
-  Buffer* b[kArgs];
-  for (int k = 0; k < kArgs; k++) {
-    b[k] = nullptr;
-    if (!normals && (k == kRestN || k == kDstN)) continue;
-    b[k] = find_buffer(ctx, h[k]);
-    if (!b[k]) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string("morph_vertices: ") + name[k] + " is 0 or an unknown buffer handle");
-  }
-  if (!normals && rest_normals && !find_buffer(ctx, rest_normals))
-    return fail(ctx, URT_ERR_INVALID_HANDLE, "morph_vertices: rest_normals is an unknown buffer handle");
-  for (int k = 0; k < kArgs; k++) {
-    if (!b[k]) continue;
-    if (b[k]->stride != stride[k]) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("morph_vertices: the stride of ") + name[k] + " is not " + std::to_string(stride[k]));
-    if (k != kWeights && b[k]->count != b[kRestV]->count) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("morph_vertices: the count of ") + name[k] + " is not that of rest_vertices");
-    if (k < kDstV && (h[k] == dst_vertices || h[k] == dst_normals)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("morph_vertices: ") + name[k] + " is also a destination");
-  }
-  if (normals && dst_normals == dst_vertices) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_vertices: dst_vertices and dst_normals are one buffer");
-  if (b[kWeights]->count != d.n_targets) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "morph_vertices: the count of weights is not the plan's n_targets");
-  if (int rc = check_element_range(ctx, "morph_vertices", *b[kRestV], d.first, d.count)) return rc;
-  if (d.count == 0) return URT_OK;
-  for (int k = 0; k < kArgs; k++) if (b[k]) if (int rc = buffer_mirror(ctx, *b[k])) return rc;
-  URT_HIP(ctx, morph_vertices((const float*)b[kRestV]->mirror.get(), normals ? (const float*)b[kRestN]->mirror.get() : nullptr, d.ranges.get(),
-                              d.targets.get(), d.deltas.get(), (const float*)b[kWeights]->mirror.get(), d.first, d.count,
-                              (float*)b[kDstV]->mirror.get(), normals ? (float*)b[kDstN]->mirror.get() : nullptr,
-                              (flags & URT_MORPH_NORMALIZE) != 0, touch(ctx)));
-  mark_device_written(ctx, dst_vertices, *b[kDstV], d.first, d.count);
-  if (normals) mark_device_written(ctx, dst_normals, *b[kDstN], d.first, d.count);
-  return URT_OK;
-  URT_GUARD_END(ctx)
 }
 
 int urt_buffer_get_info(urt_context* ctx, urt_handle buffer, int* out_count, int* out_stride) {

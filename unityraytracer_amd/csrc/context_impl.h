@@ -1,8 +1,9 @@
 // context_impl.h — the context behind the C ABI of include/urt.h, as the translation units that implement it share it:
-//   context.cpp      context lifetime, stream, buffers, textures, readback, uniforms, blits, strip packing, options, counters, debug accessors
+//   context.cpp      the Unity stand-ins: context lifetime, stream, buffers and their mirrors, textures, readback, uniforms, blits, strip packing, options, counters, debug accessors
 //   scene_prep.cpp   bound buffers -> device scene (full and in-place preparation)
 //   frame_batch.cpp  deferred frames, the Result slab, trace launches (do_dispatch, flush_pending)
-//   image_ops.cpp    ray queries, radiance queries, feature buffers, denoiser, reprojection, resampling
+//   image_ops.cpp    ray queries, radiance queries, feature buffers, denoiser, reprojection, upsampling, auto-exposure and tone mapping, depth of field, motion blur, bloom, resampling
+//   geometry_ops.cpp skinning, buffer bounds, the object-level BVH on the device, normals plans, morph plans; the buffer-argument checks (BufArg)
 //   owned.h          the holders every GPU resource below lives in (DeviceBuf, PinnedBuf, Event, Stream) and `reserve`, the grow-only policy
 // Private: nothing else includes it.  What crosses the files lives in namespace urtd and stays hidden (-fvisibility=hidden).
 #pragma once
@@ -74,18 +75,16 @@ struct Texture {
 struct DevNormalsPlan {
   urt_handle vertices = 0;
   int n_vertices = 0;            // the count of the vertices buffer at creation: every index of `tris` lies below it
-  int first = 0, count = 0, n_lists = 0, n_triangles = 0, n_entries = 0, max_valence = 0;
+  urt_NormalsPlanInfo info{};    // what urt_normals_plan_info reports
   DeviceBuf<int32_t> tris, entries, ranges;
-  uint64_t device_bytes = 0;
 };
 
 // urt_morph_plan_create: a morph plan (csrc/morph_plan.h) as the device holds it, entries in plan order: the targets apart from the
 // deltas, so that a lane reads an entry's 24 bytes of deltas only when its weight is live (csrc/morph.hip).  It names no buffer.
 struct DevMorphPlan {
-  int first = 0, count = 0, n_targets = 0, n_entries = 0, max_valence = 0, n_touched = 0;
+  urt_MorphPlanInfo info{};              // what urt_morph_plan_info reports
   DeviceBuf<int32_t> ranges, targets;    // {start, length} per served vertex; one target per entry
   DeviceBuf<float> deltas;               // dp[3], dn[3] per entry
-  uint64_t device_bytes = 0;
 };
 
 enum BindSlot { B_MESHOBJECTS, B_VERTICES, B_INDICES, B_NORMALS, B_SPHERES, B_MESHBVH, B_SPHEREBVH, B_COUNT };
@@ -405,6 +404,12 @@ int buffer_sync_host(urt_context* ctx, Buffer& b);          // downloads the sta
 int sync_bound_hosts(urt_context* ctx, unsigned int slots); // ... of the buffers bound to the slots of the mask
 int buffer_mirror(urt_context* ctx, Buffer& b);             // the device mirror, made and filled from `host` at the first need
 int strip_count(int group_rows, int first_row, int row_stride);
+void mark_device_written(urt_context* ctx, urt_handle buffer, Buffer& b, int first, int count);   // a kernel or copy has filled these elements (count > 0) of the mirror
+int check_element_range(urt_context* ctx, const char* who, const Buffer& b, int first, int count);
+// geometry_ops.cpp: the buffer arguments of a call that works on device mirrors, looked up as image_ops.cpp looks up its textures (TexArg)
+struct BufArg { urt_handle h; const char* name; int stride; bool absent = false; };   // absent: not part of this call (no normals wanted), whatever h is
+int resolve_buffers(urt_context* ctx, const char* who, const BufArg* a, int n, Buffer** b);   // b[k] = the buffer of a[k] (null: absent): every handle, then every stride, in argument order
+int mirror_buffers(urt_context* ctx, Buffer* const* b, int n);   // buffer_mirror of every buffer given: after the last check, before anything is enqueued
 // scene_prep.cpp
 int prepare_scene(urt_context* ctx);
 int scene_cost(urt_context* ctx, std::vector<float>& now, std::vector<float>& base);

@@ -343,15 +343,10 @@ static int reproject_impl(urt_context* ctx, const urt_ReprojectImages* images, c
     De = *deform;
     if (De.flags != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: deform flags must be 0");
     if (std::isnan(De.normal_threshold)) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: the deform normal_threshold is NaN");
-    const urt_handle dh[kDeformBuffers] = {De.prev_vertices, De.indices, De.prev_mesh_objects, De.deformed};
-    const char* const dname[kDeformBuffers] = {"prev_vertices", "indices", "prev_mesh_objects", "deformed"};
-    const int dstride[kDeformBuffers] = {URT_STRIDE_VEC3, URT_STRIDE_INDEX, URT_STRIDE_MESHOBJECT, 4};
-    for (int k = 0; k < kDeformBuffers; k++) {
-      db[k] = find_buffer(ctx, dh[k]);
-      if (!db[k]) return fail(ctx, URT_ERR_INVALID_HANDLE, std::string("reproject: ") + dname[k] + " is 0 or an unknown buffer handle");
-      if (db[k]->stride != dstride[k])
-        return fail(ctx, URT_ERR_INVALID_ARGUMENT, std::string("reproject: the stride of ") + dname[k] + " is not " + std::to_string(dstride[k]));
-    }
+    const BufArg da[kDeformBuffers] = {{De.prev_vertices, "prev_vertices", URT_STRIDE_VEC3}, {De.indices, "indices", URT_STRIDE_INDEX},
+                                       {De.prev_mesh_objects, "prev_mesh_objects", URT_STRIDE_MESHOBJECT}, {De.deformed, "deformed", 4}};
+    for (int k = 0; k < kDeformBuffers; k++)                 // one by one: a buffer's stride is checked before the next handle is looked up
+      if (int rc = resolve_buffers(ctx, "reproject", &da[k], 1, &db[k])) return rc;
     if (db[kIndices]->count % 3 != 0) return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: the count of indices is not a multiple of 3");
     if (db[kDeformed]->count != db[kPrevObjects]->count)
       return fail(ctx, URT_ERR_INVALID_ARGUMENT, "reproject: the counts of deformed and prev_mesh_objects differ");
@@ -373,7 +368,7 @@ static int reproject_impl(urt_context* ctx, const urt_ReprojectImages* images, c
   if (!ctx->c2w_set || !ctx->invp_set)
     return fail(ctx, URT_ERR_UNBOUND, "reproject: _CameraToWorld / _CameraInverseProjection never set (SetMatrix, RM:774-775)");
   URT_HIP(ctx, hipSetDevice(ctx->device));
-  for (Buffer* b : db) if (b) if (int rc = buffer_mirror(ctx, *b)) return rc;   // (before anything is enqueued: an allocation can fail)
+  if (int rc = mirror_buffers(ctx, db, kDeformBuffers)) return rc;   // (before anything is enqueued: an allocation can fail)
   { int rc = flush_pending(ctx); if (rc) return rc; }
   ReprojectImages I{};                                             // device pointers after the flush (a Result texture may be renamed)
   I.prev_color = t[0]->dev; I.prev_count = t[1]->dev; I.prev_hit = t[2]->dev; I.prev_normal = t[3]->dev; I.prev_id = t[4]->dev;

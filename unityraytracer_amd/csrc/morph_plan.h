@@ -7,7 +7,7 @@
 
 namespace urtd {
 
-// urt_MorphDelta of include/urt.h, member for member (context.cpp asserts the size).
+// urt_MorphDelta of include/urt.h, member for member (geometry_ops.cpp asserts the size).
 struct MorphDeltaIn {
   int32_t vertex, target;
   float dp[3], dn[3];
